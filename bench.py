@@ -8,13 +8,15 @@ in HBM: one 2^20-term Pallas MSM (== best_multiexp / commit over a registered SR
 all-gather of the commitment vector across ranks (a no-op at N = 1).  One process per GPU;
 N > 1 is launched by torch.distributed.run, units are independent per rank (weak scaling).
 
-After the timed region (never inside it) rank 0 also (a) checks the 2^20 MSM and NTT results of the measured configuration
+A plain run does only that: it sets up, warms up, times the K steps, writes what the last step computed when --dump-outputs is given, and prints
+the line.  With --full, after the timed region (never inside it) rank 0 also (a) checks the 2^20 MSM and NTT results of the measured configuration
 against the CPU port that serves as `cpu_baseline`, (b) makes REAL proofs with the device `create_proof` for the reference's two
 circuit shapes -- delay_enc (k = 17, 5 lookups, degree 5) and pose_enc (k = 11) -- asserts them byte-identical to the CPU
 restatement's proofs (whose time is the CPU figure beside them) and accepted by the verifier, and (c) proves a small batch per
-GPU and all-gathers the commitments (configs[4]: `--proofs 64` on 8 GPUs).
+GPU and all-gathers the commitments (configs[4]: `--proofs 64` on 8 GPUs), beside the one-step-at-a-time pass, the measured copy ceiling and the
+per-k figures.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--no-cpu-baseline] [--proofs P] [--proof-k 17]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--proofs P] [--proof-k 17]]
 """
 from __future__ import annotations
 
@@ -69,6 +71,12 @@ def parse():
     ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"), help="where the verbose record (every field, with its sentences) is written; "
                     "stdout carries the compact line only ('' = nowhere)")
     ap.add_argument("--inflight", type=int, default=4, help="independent steps in flight, each on its own HIP stream / workspace")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything beside the headline: the one-step-at-a-time pass, the copy "
+                    "ceiling, the CPU baseline and parity check, the per-k figures, the proofs and batch mode, and write the verbose record (--no-single-stream, "
+                    "--no-cpu-baseline, --proof-k, --proofs, --fixed-batch, --proofs-inflight, --no-verify and --full-out act on these sections)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): "
+                    "msm_commitment_affine (each rank's commitment as an affine point) and ntt_output_sample (a fixed sample of rows of the transformed "
+                    "polynomial, their indices in ntt_sample_rows).  Field elements are the 32-bit little-endian words of their 4 x 64-bit Montgomery limbs")
     return ap.parse_args()
 
 
@@ -614,6 +622,22 @@ def measured_copy_ceiling():
     return out
 
 
+NTT_SAMPLE_ROWS = 1 << 16      # 4 MiB of the 2^20-point transform's 64 MiB as float64 words
+
+
+def dump_outputs(out_dir, ctx, curve, last_commitments, d_poly, n):
+    """--dump-outputs: what the last timed step handed its caller -- the commitment of every rank (Jacobian, normalised to affine so that two builds
+    compare point for point) and the transformed polynomial (a fixed, seeded sample of its rows) -- as float64 words, exact for 32-bit words."""
+    import numpy as np
+    words = lambda a: np.ascontiguousarray(a, dtype=np.uint64).view(np.uint32).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    affine = ctx.to_affine(curve.id, last_commitments.cpu().numpy().view(np.uint64))
+    np.save(os.path.join(out_dir, "msm_commitment_affine.npy"), words(affine))
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, NTT_SAMPLE_ROWS), replace=False))
+    np.save(os.path.join(out_dir, "ntt_output_sample.npy"), words(ctx.download_tensor(d_poly)[rows]))
+    np.save(os.path.join(out_dir, "ntt_sample_rows.npy"), rows.astype(np.float64))
+
+
 def fence_all(world):
     import torch
     import torch.distributed as dist
@@ -907,6 +931,10 @@ def main():
     import gc
     gc.collect(); gc.disable()      # (as timeit does: no collector pause of the interpreter inside the 30 ms region -- and none between the preheat and it)
     preheat_steps = preheat(step_preheat, lambda: [c.synchronize() for c in ctxs]) if PREHEAT_S > 0 else 0
+    # the NTTs run in place: fresh polynomials after the preheat (whose number of steps varies with the clocks), so that the warm-up and timed steps
+    # transform the same inputs in every run with the same arguments
+    d_polys[:] = [ctx.upload(poly_h) for _ in range(inflight)]
+    torch.cuda.synchronize()
     for _ in range(args.warmup):
         step()
     gather_commitments(0, max(args.warmup, 1))
@@ -926,6 +954,9 @@ def main():
     elapsed = sharding.max_over_ranks(elapsed)
     for c in ctxs:
         c.timing_enable(False)
+    if args.dump_outputs and rank == 0:      # before anything else reuses the last step's buffers
+        last = (args.warmup + args.steps - 1) % inflight
+        dump_outputs(args.dump_outputs, ctx, curve, commitments[-world:], d_polys[last], n)
 
     # Not part of the metric: the same step with nothing else in flight, so that the per-kernel device
     # times are free of the overlap with the neighbouring steps' kernels (reported as single_stream).
@@ -933,7 +964,7 @@ def main():
         return {kid: (sum(c.timing_get(kid)[0] for c in cs), sum(c.timing_get(kid)[1] for c in cs))
                 for kid in (_lib.K_MSM_ACCUMULATE, _lib.K_MSM_SORT, _lib.K_MSM_REDUCE, _lib.K_NTT_PASS)}
     overlapped = collect(ctxs) if rank == 0 else None
-    ss_steps = 0 if args.no_single_stream else min(10, args.steps)
+    ss_steps = 0 if args.no_single_stream or not args.full else min(10, args.steps)
 
     def one_step_alone():
         ctx.msm_device(bases, d_scalars.data_ptr(), n, 1, d_out_all[0].data_ptr(), 0)
@@ -952,7 +983,7 @@ def main():
 
     n_proofs = args.proofs if args.proofs >= 0 else 32 * world
     batch = None
-    if args.proof_k > 0 and n_proofs > 0:
+    if args.full and args.proof_k > 0 and n_proofs > 0:
         batch = batch_proofs(pkg, ctx, args.proof_k, n_proofs, rank, world, args.dist_backend, local_rank, args.proofs_inflight, also_total=args.fixed_batch)
 
     if rank == 0:
@@ -972,7 +1003,7 @@ def main():
         roof_ms, roof_src = (acc_alone_ms, "one step at a time (single_stream pass, %d launches)" % ss_steps) if acc_alone_ms > 0 else \
                             (acc_avg_ms, "timed region, %d steps in flight (overlap-inflated)" % inflight)
         achieved = MSM_BYTES_PER_TERM * n / (roof_ms * 1e-3) / 1e9 if roof_ms > 0 else 0.0
-        ceiling = measured_copy_ceiling()
+        ceiling = measured_copy_ceiling() if args.full else None
         # HBM traffic cannot be read by the process itself: it comes from separate rocprofv3 --pmc passes over this same command
         # (profiles/README.md), summarised by tools/pmc_summary.py into profiles/pmc_traffic.json together with the source revision
         traffic, traffic_src = None, None
@@ -1053,8 +1084,8 @@ def main():
         if os.environ.get("DEHALO_BENCH_FIRST_ATTEMPT"):      # supervise(): a first measuring process died by a signal; what is known about it travels in the line
             out["first_attempt"] = json.loads(os.environ["DEHALO_BENCH_FIRST_ATTEMPT"])
         out["rccl_world"] = rccl_world
-        note("roofline inputs, cpu baseline, secondary numbers")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
+            note("cpu baseline, secondary numbers")
             # the CPU port on rank 0's own inputs: the reported baseline AND the parity check of the measured 2^20 configuration
             out["cpu_baseline"], want_msm, want_ntt = cpu_baseline(co, po, curve, field, log_n, bases_h, scalars_h, poly_h)
             got = ctx.to_affine(curve.id, ctx.download_tensor(d_out_all[args.warmup:args.warmup + args.steps].contiguous()))
@@ -1080,11 +1111,11 @@ def main():
                 for kk, (_, b) in tables.items():
                     if kk != log_n:
                         b.release()
-        if args.proof_k > 0:
+        if args.full and args.proof_k > 0:
             with_cpu = not args.no_cpu_baseline
             verify = not args.no_verify
             out["proof"] = proof_numbers(pkg, co, po, ctx, args.proof_k, "delay_enc", with_cpu, verify)
-        if args.proof_k > 0 and world == 1:      # (N > 1: rank 0 makes the headline proof only -- the other ranks wait at the final barrier meanwhile)
+        if args.full and args.proof_k > 0 and world == 1:      # (N > 1: rank 0 makes the headline proof only -- the other ranks wait at the final barrier meanwhile)
             out["proof_mod_pow"] = proof_numbers(pkg, co, po, ctx, 17, "mod_pow", with_cpu, verify)              # BASELINE configs[2]
             out["proof_pose_enc"] = proof_numbers(pkg, co, po, ctx, 11, "pose_enc", with_cpu, verify)            # BASELINE configs[0]
             # north star: k in {14, 17, 20}: each byte-compared with the CPU restatement's proof (k = 20: one CPU proof, about a minute) and pairing-checked
@@ -1092,7 +1123,7 @@ def main():
         if batch is not None:
             out["batch_proofs"] = batch
         out["log_n"] = log_n
-        if args.full_out:      # the verbose record, sentences included (scratch: copied into profiles/ by hand when it is the one to keep)
+        if args.full and args.full_out:      # the verbose record, sentences included (scratch: copied into profiles/ by hand when it is the one to keep)
             try:
                 os.makedirs(os.path.dirname(args.full_out) or ".", exist_ok=True)
                 with open(args.full_out, "w") as fh:

@@ -136,7 +136,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--proofs", "8", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--force-device", "0", "--proofs", "8", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env)
     if r.returncode == 0:
         import json

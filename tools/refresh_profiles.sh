@@ -5,7 +5,7 @@ set -e
 rev=${1:?kernel revision}
 export TMPDIR=/tmp
 out=gpurun_out/final; rm -rf $out; mkdir -p $out
-echo "[1] bench line"; timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err
+echo "[1] bench line"; timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err
 echo "[2] kernel stats, timed region"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o kt -- python3 bench.py --in-process --no-single-stream --no-cpu-baseline --proof-k 0 --proofs 0 > $out/bench_timed_region_under_rocprof.json 2> $out/kt.err
 echo "[3] kernel stats, create_proof k=17"
@@ -19,6 +19,6 @@ echo "[5b] field-vector primitives"; timeout -k 10 400 python tools/poly_bench.p
 echo "[6] one-shot sweep"; timeout -k 10 300 python tools/sweep_single_row.py pallas > $out/one_shot_window_sweep.txt 2>/dev/null
 echo "[7] acc points sweep"; bash tools/sweep_acc_points.sh > $out/sweep_acc_points.txt 2>&1
 echo "[8] two ranks on one GPU (gloo)"
-timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --dist-backend gloo --force-device 0 --proofs 6 --no-cpu-baseline > $out/bench_2rank_one_gpu_gloo.log 2>&1 || echo "2-rank run failed"
+timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --dist-backend gloo --force-device 0 --proofs 6 --no-cpu-baseline > $out/bench_2rank_one_gpu_gloo.log 2>&1 || echo "2-rank run failed"
 rm -rf $out/kt/*agent_info* $out/kp/*agent_info*
 ls -la $out

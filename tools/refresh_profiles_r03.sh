@@ -2,7 +2,7 @@
 # Regenerates round 3's measurement artifacts on the GPU box into gpurun_out/final/ (tools/install_profiles_r03.sh copies them into profiles/).
 export TMPDIR=/tmp
 out=gpurun_out/final; rm -rf $out; mkdir -p $out
-echo "[1] bench line"; timeout -k 10 700 python bench.py > $out/bench.json 2> $out/bench.err || echo "bench failed"
+echo "[1] bench line"; timeout -k 10 700 python bench.py --full > $out/bench.json 2> $out/bench.err || echo "bench failed"
 echo "[2] kernel stats, timed region one step at a time (the duration the roofline is computed from)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/k1 -o k1 -- python3 bench.py --in-process --inflight 1 --no-single-stream --no-cpu-baseline --proof-k 0 --proofs 0 > $out/bench_one_step_at_a_time_under_rocprof.json 2> $out/k1.err
 python3 tools/accum0_launches.py $out/k1/k1_kernel_trace.csv > $out/accum0_launch_durations.txt
@@ -24,13 +24,13 @@ echo "[5] python-driven vs native prover"; timeout -k 10 400 python tools/native
 echo "[6] microbenchmarks"; timeout -k 5 100 ./tools/stream_concurrency > $out/stream_concurrency.txt 2>&1; timeout -k 5 100 ./tools/ubench_mfma_price > $out/ubench_mfma_price.txt 2>&1; timeout -k 5 100 ./tools/pmc_calib > $out/pmc_calib.txt 2>&1
 timeout -k 5 100 ./tools/ubench_chain > $out/ubench_chain.txt 2>&1; timeout -k 10 200 python tools/ntt_bench.py > $out/ntt_bench.txt 2>/dev/null
 echo "[6b] clock ramp: the step bench by untimed work before the timed region"
-for p in 0 0.3 1.0 3.0; do timeout -k 10 200 python bench.py --no-cpu-baseline --proof-k 0 --proofs 0 --preheat-s $p 2>/dev/null | python3 -c "
+for p in 0 0.3 1.0 3.0; do timeout -k 10 200 python bench.py --full --no-cpu-baseline --proof-k 0 --proofs 0 --preheat-s $p 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print('preheat %.1f s (%d steps): %.1f Mpoints/s, %.4f ms per step; k_msm_accum0 alone %.4f ms' % (d['preheat']['seconds'], d['preheat']['steps'], d['value'], d['ms_per_step'], d['roofline']['avg_kernel_ms']))
 "; done > $out/clock_ramp.txt
 echo "[7] two ranks on one GPU (gloo)"
-timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --dist-backend gloo --force-device 0 --proofs 16 --no-cpu-baseline > $out/bench_2rank_one_gpu_gloo.log 2>&1 || echo "2-rank run failed"
+timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --dist-backend gloo --force-device 0 --proofs 16 --no-cpu-baseline > $out/bench_2rank_one_gpu_gloo.log 2>&1 || echo "2-rank run failed"
 rm -f $out/kp/kp_kernel_trace.csv $out/kt/kt_kernel_trace.csv $out/k1/k1_kernel_trace.csv $out/bt/bt_kernel_trace.csv; rm -rf $out/*/*agent_info*
 ls -la $out

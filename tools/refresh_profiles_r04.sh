@@ -7,7 +7,7 @@ part=${1:-a}
 if [ "$part" = a ]; then
 rm -rf gpurun_out/final
 mkdir -p gpurun_out/final
-echo "[1] bench line"; timeout -k 10 500 python bench.py > $out/bench.json 2> $out/bench.err || echo "bench failed"
+echo "[1] bench line"; timeout -k 10 500 python bench.py --full > $out/bench.json 2> $out/bench.err || echo "bench failed"
 echo "[2] kernel stats, timed region one step at a time (the duration the roofline is computed from)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/k1 -o k1 -- python3 bench.py --in-process --inflight 1 --no-single-stream --no-cpu-baseline --proof-k 0 --proofs 0 > $out/bench_one_step_at_a_time_under_rocprof.json 2> $out/k1.err
 python3 tools/accum0_launches.py $out/k1/k1_kernel_trace.csv > $out/accum0_launch_durations.txt
@@ -44,7 +44,7 @@ for k in 11 17 20; do echo "== k $k"; DEHALO_MSM_BRED_STAMPS=1 timeout -k 10 120
 tools/trace_k11.sh > $out/trace_k11.log 2>&1; cp gpurun_out/trace_k11/proof_timeline.txt $out/create_proof_k11_kernel_timeline.txt
 echo "[7] microbenchmarks"; timeout -k 5 100 ./tools/ubench_qmem > $out/ubench_qmem.txt 2>&1; timeout -k 10 200 python tools/ntt_bench.py > $out/ntt_bench.txt 2>/dev/null
 echo "[8] N = 2 from the bare command (two ranks on this one GPU, gloo for the gather), and the one-rank RCCL test"
-timeout -k 10 400 python3 bench.py --gpus 2 --dist-backend gloo --force-device 0 --proofs 8 > $out/bench_gpus2_bare_command.json 2> $out/bench_gpus2_bare_command.err; echo "rc=$?" >> $out/bench_gpus2_bare_command.err
+timeout -k 10 400 python3 bench.py --full --gpus 2 --dist-backend gloo --force-device 0 --proofs 8 > $out/bench_gpus2_bare_command.json 2> $out/bench_gpus2_bare_command.err; echo "rc=$?" >> $out/bench_gpus2_bare_command.err
 timeout -k 10 300 python -m pytest tests/test_sharding.py -q -m gpu -s > $out/rccl_one_rank_test.log 2>&1
 find gpurun_out/final -name "*kernel_trace.csv" -delete
 find gpurun_out/final -name "*agent_info*" -delete

@@ -6,7 +6,7 @@ out=gpurun_out/final
 part=${1:-a}
 mkdir -p $out
 if [ "$part" = a ]; then
-echo "[1] bench line (the driver's command) + the verbose record"; timeout -k 10 900 python bench.py --full-out $out/bench_full.json > $out/bench.json 2> $out/bench.err || echo "bench failed"
+echo "[1] bench line (the driver's command) + the verbose record"; timeout -k 10 900 python bench.py --full --full-out $out/bench_full.json > $out/bench.json 2> $out/bench.err || echo "bench failed"
 wc -c $out/bench.json
 echo "[2] kernel stats, timed region one step at a time (the duration the roofline is computed from)"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/k1 -o k1 -- python3 bench.py --in-process --inflight 1 --no-single-stream --no-cpu-baseline --proof-k 0 --proofs 0 --full-out "" > $out/bench_one_step_at_a_time_under_rocprof.json 2> $out/k1.err
@@ -42,7 +42,7 @@ echo "[6] batch mode: throughput by provers"
 for p in 2 3 4 6; do timeout -k 10 200 python tools/batch_trace.py 17 $p 64 0 1 | grep batch; done > $out/batch_throughput_by_provers.txt 2>/dev/null
 echo "[7] ntt bench; N = 2 from the bare command (two ranks on this one GPU, gloo for the gather)"
 timeout -k 10 200 python tools/ntt_bench.py > $out/ntt_bench.txt 2>/dev/null
-timeout -k 10 500 python3 bench.py --gpus 2 --dist-backend gloo --force-device 0 --proofs 8 --no-cpu-baseline --full-out "" > $out/bench_gpus2_bare_command.json 2> $out/bench_gpus2_bare_command.err; echo "rc=$?" >> $out/bench_gpus2_bare_command.err
+timeout -k 10 500 python3 bench.py --full --gpus 2 --dist-backend gloo --force-device 0 --proofs 8 --no-cpu-baseline --full-out "" > $out/bench_gpus2_bare_command.json 2> $out/bench_gpus2_bare_command.err; echo "rc=$?" >> $out/bench_gpus2_bare_command.err
 find gpurun_out/final -name "*kernel_trace.csv" -delete
 find gpurun_out/final -name "*agent_info*" -delete
 else

@@ -6,7 +6,7 @@ out=gpurun_out/final6
 part=${1:-a}
 mkdir -p $out
 if [ "$part" = a ]; then
-echo "[1] bench line (the driver's command) + the verbose record"; timeout -k 10 900 python bench.py --full-out $out/bench_full.json > $out/bench.json 2> $out/bench.err || echo "bench failed"
+echo "[1] bench line (the driver's command) + the verbose record"; timeout -k 10 900 python bench.py --full --full-out $out/bench_full.json > $out/bench.json 2> $out/bench.err || echo "bench failed"
 wc -c $out/bench.json
 echo "[2] kernel stats, timed region one step at a time (the duration the roofline is computed from)"
 rm -rf $out/k1
@@ -22,7 +22,7 @@ find $out -name "*kernel_trace.csv" -delete
 find $out -name "*agent_info*" -delete
 else
 echo "[4] N = 5 from the bare command (five ranks on this one GPU, gloo for the gather: the pool allows six processes on a card and the launcher is one of them): both batches, every proof re-made alone"
-timeout -k 10 1000 python3 bench.py --gpus 5 --dist-backend gloo --force-device 0 --proofs 10 --fixed-batch 64 --no-cpu-baseline --full-out "" > $out/bench_gpus5_bare_command.json 2> $out/bench_gpus5_bare_command.err; echo "rc=$?" >> $out/bench_gpus5_bare_command.err
+timeout -k 10 1000 python3 bench.py --full --gpus 5 --dist-backend gloo --force-device 0 --proofs 10 --fixed-batch 64 --no-cpu-baseline --full-out "" > $out/bench_gpus5_bare_command.json 2> $out/bench_gpus5_bare_command.err; echo "rc=$?" >> $out/bench_gpus5_bare_command.err
 echo "[5] synthesize at the metric's size"
 python tools/synth_bench.py > $out/synthesize_k17.txt 2>&1
 fi

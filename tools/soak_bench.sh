@@ -8,7 +8,7 @@ out=gpurun_out/soak/$tag.txt
 echo "# $(date -u +%FT%TZ) host $(hostname) full bench.py --in-process x $n" > $out
 for i in $(seq 1 $n); do
   t0=$(date +%s)
-  timeout -k 10 600 python bench.py --in-process > gpurun_out/soak/$tag.$i.json 2> gpurun_out/soak/$tag.$i.err
+  timeout -k 10 600 python bench.py --full --in-process > ${out%.txt}.$i.json 2> ${out%.txt}.$i.err
   rc=$?
   t1=$(date +%s)
   if [ $rc -eq 0 ]; then
