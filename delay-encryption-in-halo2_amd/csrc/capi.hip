@@ -4,15 +4,15 @@
 // or group operation runs on the device, and context creation fails without one.
 #include <algorithm>
 #include <atomic>
+#include <initializer_list>
 
 #include <map>
+#include <memory>
 
 #include "evalh_types.hpp"
 #include "internal.hpp"
 
 namespace {
-
-hipStream_t pick_stream(dehalo_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
 // Window bits by measurement on MI355X (tools/sweep_c.py, tools/profile_prover.py with WINDOW_BITS): the bucket
 // reduction costs ~ 2^(c-1) group operations on a latency chain, the accumulation n * ceil(256 / c) additions.
@@ -67,151 +67,19 @@ uint32_t signed_windows(const uint32_t r_words[8], uint32_t c) {
     }
     return (256 + c - 1) / c;
 }
-const uint32_t* scalar_modulus_words(int curve) {
-    return curve == DEHALO_CURVE_BN254_G1 ? Bn254Fr::P : curve == DEHALO_CURVE_PALLAS ? PastaFq::P : PastaFp::P;
+// the op tables of the per-field / per-curve translation units (ntt_*.hip, msm_*.hip) by dehalo_field / dehalo_curve id; null for an unknown id
+const FieldOps* field_ops(int field) {
+    static const FieldOps* const ops[] = {&bn254_fr_field_ops(), &bn254_fq_field_ops(), &pasta_fp_field_ops(), &pasta_fq_field_ops()};
+    static_assert(DEHALO_FIELD_BN254_FR == 0 && DEHALO_FIELD_BN254_FQ == 1 && DEHALO_FIELD_PASTA_FP == 2 && DEHALO_FIELD_PASTA_FQ == 3, "field ids");
+    return field >= 0 && field < 4 ? ops[field] : nullptr;
 }
-
-int do_msm(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, size_t len, size_t batch, jacobian_t* d_out, hipStream_t s) {
-    switch (bases->curve) {
-        case DEHALO_CURVE_BN254_G1: return run_msm_bn254(ctx, bases, d_scalars, len, batch, d_out, s);
-        case DEHALO_CURVE_PALLAS: return run_msm_pallas(ctx, bases, d_scalars, len, batch, d_out, s);
-        case DEHALO_CURVE_VESTA: return run_msm_vesta(ctx, bases, d_scalars, len, batch, d_out, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
-    }
+const CurveOps* curve_ops(int curve) {
+    static const CurveOps* const ops[] = {&bn254_curve_ops(), &pallas_curve_ops(), &vesta_curve_ops()};
+    static_assert(DEHALO_CURVE_BN254_G1 == 0 && DEHALO_CURVE_PALLAS == 1 && DEHALO_CURVE_VESTA == 2, "curve ids");
+    return curve >= 0 && curve < 3 ? ops[curve] : nullptr;
 }
-int do_build_table(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_std, hipStream_t s) {
-    switch (b->curve) {
-        case DEHALO_CURVE_BN254_G1: return build_table_bn254(ctx, b, d_std, s);
-        case DEHALO_CURVE_PALLAS: return build_table_pallas(ctx, b, d_std, s);
-        case DEHALO_CURVE_VESTA: return build_table_vesta(ctx, b, d_std, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
-    }
-}
-int do_to_affine(dehalo_ctx* ctx, int curve, const jacobian_t* d_in, affine_t* d_out, uint32_t count, hipStream_t s) {
-    switch (curve) {
-        case DEHALO_CURVE_BN254_G1: return to_affine_bn254(ctx, d_in, d_out, count, s);
-        case DEHALO_CURVE_PALLAS: return to_affine_pallas(ctx, d_in, d_out, count, s);
-        case DEHALO_CURVE_VESTA: return to_affine_vesta(ctx, d_in, d_out, count, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
-    }
-}
-int do_point_sum(dehalo_ctx* ctx, int curve, const jacobian_t* d_in, uint32_t count, jacobian_t* d_out, hipStream_t s) {
-    switch (curve) {
-        case DEHALO_CURVE_BN254_G1: return point_sum_bn254(ctx, d_in, count, d_out, s);
-        case DEHALO_CURVE_PALLAS: return point_sum_pallas(ctx, d_in, count, d_out, s);
-        case DEHALO_CURVE_VESTA: return point_sum_vesta(ctx, d_in, count, d_out, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
-    }
-}
-int do_ntt(dehalo_ctx* ctx, int field, const fe* src, uint64_t src_len, uint64_t src_stride, fe* dst, uint64_t dst_stride, uint32_t log_n,
-           const uint64_t omega[4], size_t batch, const NttScale& sc, hipStream_t s) {
-    switch (field) {
-        case DEHALO_FIELD_BN254_FR: return run_ntt_bn254_fr(ctx, src, src_len, src_stride, dst, dst_stride, log_n, omega, batch, sc, s);
-        case DEHALO_FIELD_BN254_FQ: return run_ntt_bn254_fq(ctx, src, src_len, src_stride, dst, dst_stride, log_n, omega, batch, sc, s);
-        case DEHALO_FIELD_PASTA_FP: return run_ntt_pasta_fp(ctx, src, src_len, src_stride, dst, dst_stride, log_n, omega, batch, sc, s);
-        case DEHALO_FIELD_PASTA_FQ: return run_ntt_pasta_fq(ctx, src, src_len, src_stride, dst, dst_stride, log_n, omega, batch, sc, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
-    }
-}
-int do_field_op(dehalo_ctx* ctx, int field, int op, const fe* a, const fe* b, fe* out, uint64_t n, hipStream_t s) {
-    switch (field) {
-        case DEHALO_FIELD_BN254_FR: return field_op_bn254_fr(ctx, op, a, b, out, n, s);
-        case DEHALO_FIELD_BN254_FQ: return field_op_bn254_fq(ctx, op, a, b, out, n, s);
-        case DEHALO_FIELD_PASTA_FP: return field_op_pasta_fp(ctx, op, a, b, out, n, s);
-        case DEHALO_FIELD_PASTA_FQ: return field_op_pasta_fq(ctx, op, a, b, out, n, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
-    }
-}
-
-#define FIELD_SWITCH(ctx, field, CALL)                                                  \
-    switch (field) {                                                                    \
-        case DEHALO_FIELD_BN254_FR: return CALL(bn254_fr);                              \
-        case DEHALO_FIELD_BN254_FQ: return CALL(bn254_fq);                              \
-        case DEHALO_FIELD_PASTA_FP: return CALL(pasta_fp);                              \
-        case DEHALO_FIELD_PASTA_FQ: return CALL(pasta_fq);                              \
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");           \
-    }
-int do_eval_poly(dehalo_ctx* ctx, int field, const fe* c, uint64_t len, uint64_t stride, size_t batch, const uint64_t pt[4], fe* out, hipStream_t s) {
-#define CALL(N) eval_poly_##N(ctx, c, len, stride, batch, pt, out, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_eval_poly_multi(dehalo_ctx* ctx, int field, const fe* const* polys, size_t count, uint64_t len, const uint64_t* pts, uint32_t npts, fe* out, hipStream_t s,
-                       const uint8_t* masks = nullptr) {
-#define CALL(N) eval_poly_multi_##N(ctx, polys, count, len, pts, npts, out, s, masks)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_batch_invert(dehalo_ctx* ctx, int field, fe* v, uint64_t len, hipStream_t s) {
-#define CALL(N) batch_invert_##N(ctx, v, len, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_prefix_product(dehalo_ctx* ctx, int field, const fe* in, uint64_t len, fe* out, hipStream_t s) {
-#define CALL(N) prefix_product_##N(ctx, in, len, out, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_grand_product(dehalo_ctx* ctx, int field, const fe* num, const fe* den, uint64_t len, size_t batch, uint64_t stride, fe* z, hipStream_t s) {
-#define CALL(N) grand_product_##N(ctx, num, den, len, batch, stride, z, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-
-int do_lincomb(dehalo_ctx* ctx, int field, const fe* const* cols, const uint64_t* coefs, size_t count, uint64_t len, fe* out, const uint64_t* sub0, hipStream_t s) {
-#define CALL(N) lincomb_##N(ctx, cols, coefs, count, len, out, sub0, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_scale(dehalo_ctx* ctx, int field, fe* a, uint64_t len, const uint64_t* pattern, uint32_t period, const fe* d_factor, hipStream_t s) {
-#define CALL(N) scale_##N(ctx, a, len, pattern, period, d_factor, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_kate_division(dehalo_ctx* ctx, int field, const fe* a, uint64_t len, const uint64_t pt[4], fe* q, hipStream_t s) {
-#define CALL(N) kate_division_##N(ctx, a, len, pt, q, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-
-int do_kate_division_batch(dehalo_ctx* ctx, int field, const fe* const* a, uint64_t len, const uint64_t* pts, fe* const* q, size_t count, hipStream_t s) {
-#define CALL(N) kate_division_batch_##N(ctx, a, len, pts, q, count, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-
-int do_convert_form(dehalo_ctx* ctx, int field, const fe* in, fe* out, uint64_t n, int to_internal, hipStream_t s) {
-#define CALL(N) convert_form_##N(ctx, in, out, n, to_internal, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_graph_upload(dehalo_ctx* ctx, int field, dehalo_graph* g, const uint64_t* constants, hipStream_t s) {
-#define CALL(N) graph_upload_##N(ctx, g, constants, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_graph_evaluate(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale, const fe* prev, fe* out,
-                      hipStream_t s) {
-#define CALL(N) graph_evaluate_##N(ctx, g, in, log_rows, rot_scale, prev, out, s)
-    FIELD_SWITCH(ctx, g->field, CALL)
-#undef CALL
-}
-int do_perm_h(dehalo_ctx* ctx, int field, const dehalo_perm_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s) {
-#define CALL(N) perm_h_##N(ctx, in, log_rows, rot_scale, v, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-int do_lookup_h(dehalo_ctx* ctx, int field, const dehalo_lookup_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s) {
-#define CALL(N) lookup_h_##N(ctx, in, log_rows, rot_scale, v, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
-
-int do_lookup_h_batch(dehalo_ctx* ctx, int field, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s) {
-#define CALL(N) lookup_h_batch_##N(ctx, in, count, log_rows, rot_scale, v, s)
-    FIELD_SWITCH(ctx, field, CALL)
-#undef CALL
-}
+int unknown_field(dehalo_ctx* ctx) { return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id"); }
+int unknown_curve(dehalo_ctx* ctx) { return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id"); }
 
 // Host-side compilation of upstream's GraphEvaluator into the device program: sources are
 // resolved to table indices, and every intermediate gets a slot from a liveness scan (a slot is
@@ -352,45 +220,104 @@ int compile_graph(dehalo_ctx* ctx, dehalo_graph* g, const int32_t* rotations, ui
     return 0;
 }
 
+// a compiled graph and its device arrays, freed together unless handed to the caller
+struct GraphFree {
+    void operator()(dehalo_graph* g) const {
+        (void)hipFree(g->d_calcs); (void)hipFree(g->d_parts); (void)hipFree(g->d_constants);
+        delete g;
+    }
+};
+
+// The host-buffer forms: under the context's lock, each input is uploaded into its workspace buffer (a null host pointer only sizes the buffer),
+// dev() runs the device form on the workspace copies, and the output is downloaded from out_buf, synchronously.  Every caller names the buffers it
+// has always used: the device form it calls may use some of the others itself.
+struct HostIn { DevBuf& buf; const void* p; size_t bytes; };
+template <class Dev>
+int with_host_io(dehalo_ctx* ctx, std::initializer_list<HostIn> ins, DevBuf& out_buf, void* out, size_t out_bytes, Dev&& dev) {
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    for (const HostIn& in : ins) TRY(dh_ensure(ctx, in.buf, std::max<size_t>(32, in.bytes)));
+    TRY(dh_ensure(ctx, out_buf, std::max<size_t>(32, out_bytes)));
+    for (const HostIn& in : ins)
+        if (in.p) TRY(dh_h2d(ctx, in.buf.p, in.p, in.bytes, ctx->stream));
+    TRY(dev());
+    TRY(dh_d2h(ctx, out, out_buf.p, out_bytes, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// a device-form entry point over one field / curve: dh_device (internal.hpp) with its op table, "unknown field id" / "unknown curve id" without one
+template <class Body>
+int field_device(dehalo_ctx* ctx, int field, void* stream, Body&& body) {
+    return dh_device(ctx, stream, [&](hipStream_t s) {
+        const FieldOps* f = field_ops(field);
+        return f ? body(*f, s) : unknown_field(ctx);
+    });
+}
+template <class Body>
+int curve_device(dehalo_ctx* ctx, int curve, void* stream, Body&& body) {
+    return dh_device(ctx, stream, [&](hipStream_t s) {
+        const CurveOps* cv = curve_ops(curve);
+        return cv ? body(*cv, s) : unknown_curve(ctx);
+    });
+}
+
+// the NTT family's host-buffer forms: ws_ntt_io in, ws_ntt_io2 out unless in place; dev(d_in, d_out)
+template <class Dev>
+int ntt_host_io(dehalo_ctx* ctx, const uint64_t* in, size_t in_elems, uint64_t* out, size_t out_elems, bool inplace, Dev&& dev) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!in || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "null buffer");
+    return dh_guard(ctx, [&] {
+        HostPin pin_in(in, in_elems * 32), pin_out(out == in ? nullptr : out, out_elems * 32);
+        DevBuf& d_in = ctx->ws_ntt_io;
+        DevBuf& d_out = inplace ? ctx->ws_ntt_io : ctx->ws_ntt_io2;
+        return with_host_io(ctx, {{d_in, in, in_elems * 32}}, d_out, out, out_elems * 32, [&] { return dev((uint64_t*)d_in.p, (uint64_t*)d_out.p); });
+    });
+}
+
+// a bases object and its table, freed together unless handed to the caller
+struct BasesFree {
+    void operator()(dehalo_bases* b) const {
+        if (b->table) (void)hipFree(b->table);
+        delete b;
+    }
+};
+
 int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t n, size_t stride_bytes, int window_bits, int precompute,
                   dehalo_bases** out, bool on_device = false) {
     if (!affine_xy || !out || n == 0 || stride_bytes < 64 || n >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_register: bad argument");
     if (window_bits != 0 && (window_bits < 4 || window_bits > (precompute ? 17 : 16)))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "window_bits must be 0 or in [4, 16] (17 with precomputed rows)");
+    const CurveOps* cv = curve_ops(curve);
+    if (!cv) return unknown_curve(ctx);
     uint32_t c = window_bits ? (uint32_t)window_bits : (precompute ? choose_window(n) : choose_window_single(n));
     if (!window_bits && precompute) {      // DEHALO_WINDOW_BITS: tuning experiments (results never depend on the window)
         const char* e = DH_EXPERIMENT_ENV("DEHALO_WINDOW_BITS");
         if (e && atoi(e) >= 4 && atoi(e) <= 17) c = (uint32_t)atoi(e);
     }
     if (c < 4) c = 4;
-    uint32_t W = signed_windows(scalar_modulus_words(curve), c);
+    uint32_t W = signed_windows(cv->scalar_modulus, c);
     if (precompute && (uint64_t)n * W >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "precomputed table too large");      // 30-bit table indices in the sorted list (msm.cuh)
     // stage the caller's points (standard Montgomery form) on the device, then build the table
     if (!on_device) TRY(dh_ensure(ctx, ctx->ws_tmp_bases, n * sizeof(affine_t)));
-    dehalo_bases* b = new dehalo_bases();
+    std::unique_ptr<dehalo_bases, BasesFree> b(new dehalo_bases());
     b->curve = curve; b->n = n; b->c = c; b->W = W; b->precomp = precompute ? 1 : 0; b->table = nullptr;
     size_t rows = precompute ? W : 1;
     hipError_t e = hipMalloc((void**)&b->table, rows * n * sizeof(affine_t));
-    if (e != hipSuccess) { delete b; return dh_fail(ctx, DEHALO_ERR_OOM, std::string("bases table: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return dh_fail(ctx, DEHALO_ERR_OOM, std::string("bases table: ") + hipGetErrorString(e));
     // 64 MiB of SRS points at 2^20: DMA straight from the caller's pages -- only when these bytes are what is copied (host memory, contiguous points)
     HostPin pin_bases(on_device || stride_bytes != 64 ? nullptr : affine_xy, n * stride_bytes);
     // (contiguous points: a plain copy -- the 2-D path took 3 of the 4.1 ms of registering 2^20 points)
-    int rc = 0;
     std::vector<uint64_t> packed;      // (points with a trailing flag byte: gathered on the host, so that the upload is one contiguous copy)
     if (stride_bytes != 64 && !on_device) {
         packed.resize(n * 8);
         for (size_t i = 0; i < n; i++) memcpy(&packed[i * 8], (const char*)affine_xy + i * stride_bytes, 64);
     }
-    if (!on_device) rc = dh_h2d(ctx, ctx->ws_tmp_bases.p, stride_bytes == 64 ? (const void*)affine_xy : (const void*)packed.data(), n * 64, ctx->stream);
-    if (rc != 0) { (void)hipFree(b->table); delete b; return rc; }
-    if (e == hipSuccess) rc = do_build_table(ctx, b, on_device ? (const affine_t*)affine_xy : (const affine_t*)ctx->ws_tmp_bases.p, ctx->stream);
-    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess || rc != 0) {
-        (void)hipFree(b->table);
-        delete b;
-        return rc ? rc : dh_fail(ctx, DEHALO_ERR_HIP, std::string("bases upload: ") + hipGetErrorString(e));
-    }
-    *out = b;
+    if (!on_device) TRY(dh_h2d(ctx, ctx->ws_tmp_bases.p, stride_bytes == 64 ? (const void*)affine_xy : (const void*)packed.data(), n * 64, ctx->stream));
+    TRY(cv->build_table(ctx, b.get(), on_device ? (const affine_t*)affine_xy : (const affine_t*)ctx->ws_tmp_bases.p, ctx->stream));
+    e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return dh_fail(ctx, DEHALO_ERR_HIP, std::string("bases upload: ") + hipGetErrorString(e));
+    *out = b.release();
     return 0;
 }
 
@@ -398,7 +325,8 @@ int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t 
 
 // the limit of a precomputed table registered with window_bits = 0: n x windows < 2^30 (30-bit table indices in the sorted list, msm.cuh)
 bool dh_precomputed_table_fits(int curve, size_t n) {
-    return n < (1ull << 30) && (uint64_t)n * signed_windows(scalar_modulus_words(curve), std::max<uint32_t>(4, choose_window(n))) < (1ull << 30);
+    const CurveOps* cv = curve_ops(curve);
+    return cv && n < (1ull << 30) && (uint64_t)n * signed_windows(cv->scalar_modulus, std::max<uint32_t>(4, choose_window(n))) < (1ull << 30);
 }
 
 // ==========================================================================================
@@ -411,45 +339,47 @@ int dehalo_ctx_create(int device, dehalo_ctx** out) { return dehalo_ctx_create_w
 int dehalo_ctx_create_with_priority(int device, int priority, dehalo_ctx** out) {
     if (!out) return DEHALO_ERR_INVALID;
     *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return DEHALO_ERR_NO_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return DEHALO_ERR_NO_DEVICE;
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return DEHALO_ERR_NO_DEVICE;  // code objects are gfx950-only
-    if (hipSetDevice(device) != hipSuccess) return DEHALO_ERR_NO_DEVICE;
-    dehalo_ctx* ctx = new dehalo_ctx();
-    ctx->device = device;
-    ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    {   // priority > 0: the device's highest stream priority (a context of small kernels beside another context's long ones), < 0: lowest
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        const int prio = priority > 0 ? greatest : (priority < 0 ? least : 0);
-        // Experiment (DEHALO_CU_PARTITION = P, measurements only): the i-th context created by this process gets a stream that may only use the (i mod P)-th
-        // P-th of the compute units (hipExtStreamCreateWithCUMask), so that the provers of a batch do not wait for each other's workgroups to leave a CU.
-        static const int cu_parts = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_CU_PARTITION"); return e ? atoi(e) : 0; }();
-        static std::atomic<int> cu_next{0};
-        hipError_t e;
-        if (cu_parts > 1 && cu_parts <= 16) {
-            const int part = cu_next.fetch_add(1) % cu_parts, ncu = ctx->num_cus, per = ncu / cu_parts;
-            std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-            static const bool interleave = DH_EXPERIMENT_ENV("DEHALO_CU_PARTITION_INTERLEAVE") != nullptr;
-            for (int cu = 0; cu < ncu; cu++) {
-                const bool mine = interleave ? (cu % cu_parts) == part : (cu / per) == part;
-                if (mine) mask[cu / 32] |= 1u << (cu % 32);
-            }
-            e = hipExtStreamCreateWithCUMask(&ctx->stream, (uint32_t)mask.size(), mask.data());
-            if (e == hipSuccess) ctx->num_cus = per;
-        } else
-        e = priority == 0 ? hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)
-                          : hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio);
-        if (e != hipSuccess) { delete ctx; return DEHALO_ERR_HIP; }
-    }
-    if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_MIN_LAYERS")) ctx->msm_acc_min_layers = std::max(1, std::min(4, atoi(e)));
-    if (const char* e = DH_EXPERIMENT_ENV("DEHALO_HOST_SPIN_US")) ctx->host_wait_spin_us = std::max(0, std::min(1000000, atoi(e)));
-    if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_BLOCK")) ctx->msm_acc_block = atoi(e) == 768 ? 768 : 128;                                      // launch geometry only
-    if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_POINTS")) ctx->msm_acc_points = std::max(0, std::min(4096, atoi(e)));   // launch geometry only (dehalo_ctx_set_tuning)
-    *out = ctx;
-    return 0;
+    return dh_guard(nullptr, [&]() -> int {
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return DEHALO_ERR_NO_DEVICE;
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) != hipSuccess) return DEHALO_ERR_NO_DEVICE;
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return DEHALO_ERR_NO_DEVICE;  // code objects are gfx950-only
+        if (hipSetDevice(device) != hipSuccess) return DEHALO_ERR_NO_DEVICE;
+        std::unique_ptr<dehalo_ctx> ctx(new dehalo_ctx());
+        ctx->device = device;
+        ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+        {   // priority > 0: the device's highest stream priority (a context of small kernels beside another context's long ones), < 0: lowest
+            int least = 0, greatest = 0;
+            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+            const int prio = priority > 0 ? greatest : (priority < 0 ? least : 0);
+            // Experiment (DEHALO_CU_PARTITION = P, measurements only): the i-th context created by this process gets a stream that may only use the (i mod P)-th
+            // P-th of the compute units (hipExtStreamCreateWithCUMask), so that the provers of a batch do not wait for each other's workgroups to leave a CU.
+            static const int cu_parts = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_CU_PARTITION"); return e ? atoi(e) : 0; }();
+            static std::atomic<int> cu_next{0};
+            hipError_t e;
+            if (cu_parts > 1 && cu_parts <= 16) {
+                const int part = cu_next.fetch_add(1) % cu_parts, ncu = ctx->num_cus, per = ncu / cu_parts;
+                std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
+                static const bool interleave = DH_EXPERIMENT_ENV("DEHALO_CU_PARTITION_INTERLEAVE") != nullptr;
+                for (int cu = 0; cu < ncu; cu++) {
+                    const bool mine = interleave ? (cu % cu_parts) == part : (cu / per) == part;
+                    if (mine) mask[cu / 32] |= 1u << (cu % 32);
+                }
+                e = hipExtStreamCreateWithCUMask(&ctx->stream, (uint32_t)mask.size(), mask.data());
+                if (e == hipSuccess) ctx->num_cus = per;
+            } else
+            e = priority == 0 ? hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)
+                              : hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio);
+            if (e != hipSuccess) return DEHALO_ERR_HIP;
+        }
+        if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_MIN_LAYERS")) ctx->msm_acc_min_layers = std::max(1, std::min(4, atoi(e)));
+        if (const char* e = DH_EXPERIMENT_ENV("DEHALO_HOST_SPIN_US")) ctx->host_wait_spin_us = std::max(0, std::min(1000000, atoi(e)));
+        if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_BLOCK")) ctx->msm_acc_block = atoi(e) == 768 ? 768 : 128;                                      // launch geometry only
+        if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_POINTS")) ctx->msm_acc_points = std::max(0, std::min(4096, atoi(e)));   // launch geometry only (dehalo_ctx_set_tuning)
+        *out = ctx.release();
+        return 0;
+    });
 }
 
 void dehalo_ctx_destroy(dehalo_ctx* ctx) {
@@ -477,103 +407,118 @@ const char* dehalo_last_error(const dehalo_ctx* ctx) {
     if (!ctx) return "null context";
     // a copy per calling thread, taken under the lock: another thread's error path may replace ctx->err at any time
     static thread_local std::string copy;
-    {
+    try {
         std::lock_guard<std::mutex> lk(const_cast<dehalo_ctx*>(ctx)->err_mu);
         copy = ctx->err;
+    } catch (...) {
+        return "out of host memory copying the last error";
     }
     return copy.c_str();
 }
 
 int dehalo_ctx_set_tuning(dehalo_ctx* ctx, const char* key, int value) {
     if (!ctx || !key) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!strcmp(key, "msm_acc_points")) {
-        if (value < 0 || value > 4096) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_acc_points must be in [0, 4096]");
-        ctx->msm_acc_points = value;
-        return 0;
-    }
-    if (!strcmp(key, "msm_acc_waves")) {
-        if (value < 1 || value > 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_acc_waves must be in [1, 4]");
-        ctx->msm_acc_waves = value;
-        return 0;
-    }
-    if (!strcmp(key, "host_wait_spin_us")) {
-        if (value < 0 || value > 1000000) return dh_fail(ctx, DEHALO_ERR_INVALID, "host_wait_spin_us must be in [0, 1000000]");
-        ctx->host_wait_spin_us = value;
-        return 0;
-    }
-    if (!strcmp(key, "msm_sort_block")) {
-        if (value != 512 && value != 1024) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_sort_block must be 512 or 1024");
-        ctx->msm_sort_block = value;
-        return 0;
-    }
-    if (!strcmp(key, "msm_acc_block")) {
-        if (value != 128 && value != 768) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_acc_block must be 128 or 768");
-        ctx->msm_acc_block = value;
-        return 0;
-    }
-    if (!strcmp(key, "ntt_full_table_log")) {
-        if (value < 0 || value > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "ntt_full_table_log must be in [0, 30]");
-        ctx->ntt_full_table_log = value;
-        return 0;
-    }
-    return dh_fail(ctx, DEHALO_ERR_INVALID, std::string("unknown tuning key: ") + key);
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        if (!strcmp(key, "msm_acc_points")) {
+            if (value < 0 || value > 4096) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_acc_points must be in [0, 4096]");
+            ctx->msm_acc_points = value;
+            return 0;
+        }
+        if (!strcmp(key, "msm_acc_waves")) {
+            if (value < 1 || value > 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_acc_waves must be in [1, 4]");
+            ctx->msm_acc_waves = value;
+            return 0;
+        }
+        if (!strcmp(key, "host_wait_spin_us")) {
+            if (value < 0 || value > 1000000) return dh_fail(ctx, DEHALO_ERR_INVALID, "host_wait_spin_us must be in [0, 1000000]");
+            ctx->host_wait_spin_us = value;
+            return 0;
+        }
+        if (!strcmp(key, "msm_sort_block")) {
+            if (value != 512 && value != 1024) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_sort_block must be 512 or 1024");
+            ctx->msm_sort_block = value;
+            return 0;
+        }
+        if (!strcmp(key, "msm_acc_block")) {
+            if (value != 128 && value != 768) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_acc_block must be 128 or 768");
+            ctx->msm_acc_block = value;
+            return 0;
+        }
+        if (!strcmp(key, "ntt_full_table_log")) {
+            if (value < 0 || value > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "ntt_full_table_log must be in [0, 30]");
+            ctx->ntt_full_table_log = value;
+            return 0;
+        }
+        return dh_fail(ctx, DEHALO_ERR_INVALID, std::string("unknown tuning key: ") + key);
+    });
 }
 
 void* dehalo_ctx_stream(dehalo_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
 int dehalo_ctx_synchronize(dehalo_ctx* ctx) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return 0;
+    });
 }
 
 int dehalo_download(dehalo_ctx* ctx, const void* d_src, size_t bytes, void* host_dst) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    if ((!d_src || !host_dst) && bytes) return dh_fail(ctx, DEHALO_ERR_INVALID, "download: null argument");
-    (void)hipSetDevice(ctx->device);
-    if (bytes) TRY(dh_d2h(ctx, host_dst, d_src, bytes, ctx->stream));
-    HIP_TRY(ctx, dh_stream_wait(ctx, ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        if ((!d_src || !host_dst) && bytes) return dh_fail(ctx, DEHALO_ERR_INVALID, "download: null argument");
+        (void)hipSetDevice(ctx->device);
+        if (bytes) TRY(dh_d2h(ctx, host_dst, d_src, bytes, ctx->stream));
+        HIP_TRY(ctx, dh_stream_wait(ctx, ctx->stream));
+        return 0;
+    });
 }
 
 int dehalo_upload(dehalo_ctx* ctx, const void* host_src, size_t bytes, void* d_dst) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    if ((!host_src || !d_dst) && bytes) return dh_fail(ctx, DEHALO_ERR_INVALID, "upload: null argument");
-    (void)hipSetDevice(ctx->device);
-    {
-        HostPin pin(host_src, bytes);      // 4 MiB and more: one DMA from the caller's pages, released below, after the stream has drained
-        TRY(dh_h2d(ctx, d_dst, host_src, bytes, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        if ((!host_src || !d_dst) && bytes) return dh_fail(ctx, DEHALO_ERR_INVALID, "upload: null argument");
+        (void)hipSetDevice(ctx->device);
+        {
+            HostPin pin(host_src, bytes);      // 4 MiB and more: one DMA from the caller's pages, released below, after the stream has drained
+            TRY(dh_h2d(ctx, d_dst, host_src, bytes, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        return 0;
+    });
 }
 
 int dehalo_bases_register(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t n, size_t stride_bytes, int window_bits, int precompute,
                           dehalo_bases** out) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    if (curve < 0 || curve > 2) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return register_impl(ctx, curve, affine_xy, n, stride_bytes, window_bits, precompute, out);
+    if (!curve_ops(curve)) return unknown_curve(ctx);
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        return register_impl(ctx, curve, affine_xy, n, stride_bytes, window_bits, precompute, out);
+    });
 }
 
 int dehalo_bases_register_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t n, int window_bits, int precompute, dehalo_bases** out) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    if (curve < 0 || curve > 2) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return register_impl(ctx, curve, d_affine_xy, n, 64, window_bits, precompute, out, true);
+    if (!curve_ops(curve)) return unknown_curve(ctx);
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        return register_impl(ctx, curve, d_affine_xy, n, 64, window_bits, precompute, out, true);
+    });
 }
 
 int dehalo_bases_release(dehalo_ctx* ctx, dehalo_bases* bases) {
     if (!ctx || !bases) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(bases->table);
-    delete bases;
-    return 0;
+    return dh_guard(ctx, [&] {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        (void)hipDeviceSynchronize();
+        BasesFree()(bases);
+        return 0;
+    });
 }
 
 size_t dehalo_bases_len(const dehalo_bases* bases) { return bases ? bases->n : 0; }
@@ -588,32 +533,33 @@ int dehalo_bases_info(const dehalo_bases* bases, uint32_t* window_bits, uint32_t
 
 int dehalo_msm_device(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t* d_scalars, size_t len, size_t batch, uint64_t* d_out_jacobian,
                       void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!bases || (!d_scalars && len) || !d_out_jacobian) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: null argument");
     if (len > bases->n) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: more scalars than registered bases");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_msm(ctx, bases, (const fe*)d_scalars, len, batch, (jacobian_t*)d_out_jacobian, pick_stream(ctx, stream));
+    return curve_device(ctx, bases->curve, stream, [&](const CurveOps& cv, hipStream_t s) {
+        return cv.run_msm(ctx, bases, (const fe*)d_scalars, len, batch, (jacobian_t*)d_out_jacobian, s);
+    });
 }
 
 int dehalo_msm_device_affine(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t* d_scalars, size_t len, size_t batch, uint64_t* d_out_jacobian,
                              uint64_t* d_out_affine, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!bases || (!d_scalars && len) || !d_out_affine) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: null argument");
     if (len > bases->n) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: more scalars than registered bases");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = pick_stream(ctx, stream);
-    if (len == 0 || batch == 0) {   // the empty sum: identity = (0, 0)
-        if (batch) HIP_TRY(ctx, hipMemsetAsync(d_out_affine, 0, batch * sizeof(affine_t), s));
-        if (batch && d_out_jacobian) HIP_TRY(ctx, hipMemsetAsync(d_out_jacobian, 0, batch * sizeof(jacobian_t), s));
-        return 0;
-    }
-    ctx->msm_affine_out = (affine_t*)d_out_affine;
-    // (without a Jacobian destination the kernel skips that form; run_msm_t only passes the pointer on)
-    int rc = do_msm(ctx, bases, (const fe*)d_scalars, len, batch, (jacobian_t*)d_out_jacobian, s);
-    ctx->msm_affine_out = nullptr;
-    return rc;
+    return dh_device(ctx, stream, [&](hipStream_t s) -> int {
+        if (len == 0 || batch == 0) {   // the empty sum: identity = (0, 0)
+            if (batch) HIP_TRY(ctx, hipMemsetAsync(d_out_affine, 0, batch * sizeof(affine_t), s));
+            if (batch && d_out_jacobian) HIP_TRY(ctx, hipMemsetAsync(d_out_jacobian, 0, batch * sizeof(jacobian_t), s));
+            return 0;
+        }
+        const CurveOps* cv = curve_ops(bases->curve);
+        if (!cv) return unknown_curve(ctx);
+        // (without a Jacobian destination the kernel skips that form; run_msm_t only passes the pointer on)
+        struct AffineOut {      // set for this call only, also when it throws
+            dehalo_ctx* ctx;
+            ~AffineOut() { ctx->msm_affine_out = nullptr; }
+        } reset{ctx};
+        ctx->msm_affine_out = (affine_t*)d_out_affine;
+        return cv->run_msm(ctx, bases, (const fe*)d_scalars, len, batch, (jacobian_t*)d_out_jacobian, s);
+    });
 }
 
 int dehalo_msm_batch(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t* const* scalars, size_t len, size_t batch, uint64_t* out_jacobian) {
@@ -623,9 +569,9 @@ int dehalo_msm_batch(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t*
     if (batch && len > (SIZE_MAX / 32) / batch) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: batch * len overflows");
     for (size_t b = 0; b < batch; b++)
         if (!scalars[b] && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: null scalar column");
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    // (not with_host_io: the columns are separate host arrays, each pinned and copied on its own into one workspace buffer)
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
         (void)hipSetDevice(ctx->device);
         TRY(dh_ensure(ctx, ctx->ws_scalars, std::max<size_t>(32, batch * len * 32)));
         TRY(dh_ensure(ctx, ctx->ws_out, std::max<size_t>(96, batch * 96)));
@@ -634,12 +580,11 @@ int dehalo_msm_batch(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t*
             TRY(dh_h2d(ctx, (char*)ctx->ws_scalars.p + b * len * 32, scalars[b], len * 32, ctx->stream));
             if (pin.p) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the pin ends with this scope
         }
-    }
-    TRY(dehalo_msm_device(ctx, bases, (const uint64_t*)ctx->ws_scalars.p, len, batch, (uint64_t*)ctx->ws_out.p, nullptr));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(dh_d2h(ctx, out_jacobian, ctx->ws_out.p, batch * 96, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+        TRY(dehalo_msm_device(ctx, bases, (const uint64_t*)ctx->ws_scalars.p, len, batch, (uint64_t*)ctx->ws_out.p, nullptr));
+        TRY(dh_d2h(ctx, out_jacobian, ctx->ws_out.p, batch * 96, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return 0;
+    });
 }
 
 int dehalo_msm(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t* scalars, size_t len, uint64_t out_jacobian[12]) {
@@ -650,23 +595,24 @@ int dehalo_msm(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t* scala
 int dehalo_best_multiexp(dehalo_ctx* ctx, int curve, const uint64_t* scalars, const uint64_t* affine_xy, size_t len, uint64_t out_jacobian[12]) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (!out_jacobian || ((!scalars || !affine_xy) && len)) return dh_fail(ctx, DEHALO_ERR_INVALID, "best_multiexp: null argument");
-    if (curve < 0 || curve > 2) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve id");
+    if (!curve_ops(curve)) return unknown_curve(ctx);
     if (len == 0) { memset(out_jacobian, 0, 96); return 0; }
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);
-    dehalo_bases* b = nullptr;
-    TRY(dehalo_bases_register(ctx, curve, affine_xy, len, 64, 0, 0, &b));
-    int rc = dehalo_msm(ctx, b, scalars, len, out_jacobian);
-    dehalo_bases_release(ctx, b);
-    return rc;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> hold(ctx->mu);
+        dehalo_bases* b = nullptr;
+        TRY(dehalo_bases_register(ctx, curve, affine_xy, len, 64, 0, 0, &b));
+        int rc = dehalo_msm(ctx, b, scalars, len, out_jacobian);
+        dehalo_bases_release(ctx, b);
+        return rc;
+    });
 }
 
 int dehalo_point_sum_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobian, size_t count, uint64_t* d_out_jacobian, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_jacobian && count) || !d_out_jacobian) return dh_fail(ctx, DEHALO_ERR_INVALID, "point_sum: null argument");
     if (count >= (1ull << 31)) return dh_fail(ctx, DEHALO_ERR_INVALID, "point_sum: too many points");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_point_sum(ctx, curve, (const jacobian_t*)d_jacobian, (uint32_t)count, (jacobian_t*)d_out_jacobian, pick_stream(ctx, stream));
+    return curve_device(ctx, curve, stream, [&](const CurveOps& cv, hipStream_t s) {
+        return cv.point_sum(ctx, (const jacobian_t*)d_jacobian, (uint32_t)count, (jacobian_t*)d_out_jacobian, s);
+    });
 }
 
 int dehalo_to_affine_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobian, size_t count, uint64_t* d_affine_xy, void* stream) {
@@ -674,9 +620,9 @@ int dehalo_to_affine_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobi
     if ((!d_jacobian || !d_affine_xy) && count) return dh_fail(ctx, DEHALO_ERR_INVALID, "to_affine: null argument");
     if (count == 0) return 0;
     if (count >= (1ull << 31)) return dh_fail(ctx, DEHALO_ERR_INVALID, "to_affine: too many points");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_to_affine(ctx, curve, (const jacobian_t*)d_jacobian, (affine_t*)d_affine_xy, (uint32_t)count, pick_stream(ctx, stream));
+    return curve_device(ctx, curve, stream, [&](const CurveOps& cv, hipStream_t s) {
+        return cv.to_affine(ctx, (const jacobian_t*)d_jacobian, (affine_t*)d_affine_xy, (uint32_t)count, s);
+    });
 }
 
 int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_t count, uint64_t* affine_xy) {
@@ -684,25 +630,21 @@ int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_
     if ((!jacobian || !affine_xy) && count) return dh_fail(ctx, DEHALO_ERR_INVALID, "to_affine: null argument");
     if (count == 0) return 0;
     if (count >= (1ull << 31)) return dh_fail(ctx, DEHALO_ERR_INVALID, "to_affine: too many points");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    TRY(dh_ensure(ctx, ctx->ws_fop[0], count * 96));
-    TRY(dh_ensure(ctx, ctx->ws_fop[1], count * 64));
-    TRY(dh_h2d(ctx, ctx->ws_fop[0].p, jacobian, count * 96, ctx->stream));
-    TRY(do_to_affine(ctx, curve, (const jacobian_t*)ctx->ws_fop[0].p, (affine_t*)ctx->ws_fop[1].p, (uint32_t)count, ctx->stream));
-    TRY(dh_d2h(ctx, affine_xy, ctx->ws_fop[1].p, count * 64, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&] {
+        return with_host_io(ctx, {{ctx->ws_fop[0], jacobian, count * 96}}, ctx->ws_fop[1], affine_xy, count * 64, [&] {
+            const CurveOps* cv = curve_ops(curve);
+            return cv ? cv->to_affine(ctx, (const jacobian_t*)ctx->ws_fop[0].p, (affine_t*)ctx->ws_fop[1].p, (uint32_t)count, ctx->stream) : unknown_curve(ctx);
+        });
+    });
 }
 
 // ---- NTT family -----------------------------------------------------------------------------
 static int ntt_device_impl(dehalo_ctx* ctx, int field, const uint64_t* d_src, uint64_t src_len, uint64_t src_stride, uint64_t* d_dst,
                            uint64_t dst_stride, uint32_t log_n, const uint64_t omega[4], size_t batch, const NttScale& sc, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!d_src || !d_dst || !omega) return dh_fail(ctx, DEHALO_ERR_INVALID, "ntt: null argument");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_ntt(ctx, field, (const fe*)d_src, src_len, src_stride, (fe*)d_dst, dst_stride, log_n, omega, batch, sc, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.run_ntt(ctx, (const fe*)d_src, src_len, src_stride, (fe*)d_dst, dst_stride, log_n, omega, batch, sc, s);
+    });
 }
 
 int dehalo_ntt_device(dehalo_ctx* ctx, int field, uint64_t* d_a, uint32_t log_n, const uint64_t omega[4], size_t batch, void* stream) {
@@ -767,119 +709,68 @@ int dehalo_coset_intt_device(dehalo_ctx* ctx, int field, uint64_t* d_a, uint32_t
 }
 
 int dehalo_convert_form_device(dehalo_ctx* ctx, int field, const uint64_t* d_in, uint64_t* d_out, size_t n, int to_internal, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_in || !d_out) && n) return dh_fail(ctx, DEHALO_ERR_INVALID, "convert_form: null argument");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_convert_form(ctx, field, (const fe*)d_in, (fe*)d_out, n, to_internal, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.convert_form(ctx, (const fe*)d_in, (fe*)d_out, n, to_internal, s); });
 }
-
-// host-buffer forms: upload, transform, download
-static int with_host_io(dehalo_ctx* ctx, const uint64_t* in, size_t in_elems, uint64_t* out, size_t out_elems, bool inplace,
-                        int (*fn)(dehalo_ctx*, uint64_t*, uint64_t*, void*), void* arg) {
-    if (!ctx) return DEHALO_ERR_INVALID;
-    if (!in || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "null buffer");
-    HostPin pin_in(in, in_elems * 32), pin_out(out == in ? nullptr : out, out_elems * 32);
-    uint64_t *d_in, *d_out;
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        TRY(dh_ensure(ctx, ctx->ws_ntt_io, std::max<size_t>(32, in_elems * 32)));
-        d_in = (uint64_t*)ctx->ws_ntt_io.p;
-        if (inplace) d_out = d_in;
-        else {
-            TRY(dh_ensure(ctx, ctx->ws_ntt_io2, std::max<size_t>(32, out_elems * 32)));
-            d_out = (uint64_t*)ctx->ws_ntt_io2.p;
-        }
-        TRY(dh_h2d(ctx, d_in, in, in_elems * 32, ctx->stream));
-    }
-    TRY(fn(ctx, d_in, d_out, arg));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(dh_d2h(ctx, out, d_out, out_elems * 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-struct NttArgs { int field; uint32_t log_n, log_ext; const uint64_t *w, *s, *z; };
 
 int dehalo_ntt(dehalo_ctx* ctx, int field, uint64_t* a, uint32_t log_n, const uint64_t omega[4]) {
     if (log_n > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "log_n > 30");
-    NttArgs A{field, log_n, 0, omega, nullptr, nullptr};
     size_t N = (size_t)1 << log_n;
-    return with_host_io(ctx, a, N, a, N, true, [](dehalo_ctx* c, uint64_t* di, uint64_t*, void* p) {
-        NttArgs* A = (NttArgs*)p;
-        return dehalo_ntt_device(c, A->field, di, A->log_n, A->w, 1, nullptr);
-    }, &A);
+    return ntt_host_io(ctx, a, N, a, N, true, [&](uint64_t* di, uint64_t*) { return dehalo_ntt_device(ctx, field, di, log_n, omega, 1, nullptr); });
 }
 
 int dehalo_intt_scaled(dehalo_ctx* ctx, int field, uint64_t* a, uint32_t log_n, const uint64_t omega_inv[4], const uint64_t n_inv[4]) {
     if (log_n > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "log_n > 30");
-    NttArgs A{field, log_n, 0, omega_inv, n_inv, nullptr};
     size_t N = (size_t)1 << log_n;
-    return with_host_io(ctx, a, N, a, N, true, [](dehalo_ctx* c, uint64_t* di, uint64_t*, void* p) {
-        NttArgs* A = (NttArgs*)p;
-        return dehalo_intt_scaled_device(c, A->field, di, A->log_n, A->w, A->s, 1, nullptr);
-    }, &A);
+    return ntt_host_io(ctx, a, N, a, N, true, [&](uint64_t* di, uint64_t*) { return dehalo_intt_scaled_device(ctx, field, di, log_n, omega_inv, n_inv, 1, nullptr); });
 }
 
 int dehalo_coset_ntt(dehalo_ctx* ctx, int field, const uint64_t* coeffs, uint32_t log_n, uint64_t* ext_out, uint32_t log_ext,
                      const uint64_t omega_ext[4], const uint64_t zeta[4]) {
     if (log_ext > 30 || log_ext < log_n) return dh_fail(ctx, DEHALO_ERR_INVALID, "coset_ntt: bad sizes");
-    NttArgs A{field, log_n, log_ext, omega_ext, nullptr, zeta};
-    return with_host_io(ctx, coeffs, (size_t)1 << log_n, ext_out, (size_t)1 << log_ext, false, [](dehalo_ctx* c, uint64_t* di, uint64_t* dout, void* p) {
-        NttArgs* A = (NttArgs*)p;
-        return dehalo_coset_ntt_device(c, A->field, di, A->log_n, dout, A->log_ext, A->w, A->z, 1, nullptr);
-    }, &A);
+    return ntt_host_io(ctx, coeffs, (size_t)1 << log_n, ext_out, (size_t)1 << log_ext, false, [&](uint64_t* di, uint64_t* dout) {
+        return dehalo_coset_ntt_device(ctx, field, di, log_n, dout, log_ext, omega_ext, zeta, 1, nullptr);
+    });
 }
 
 int dehalo_coset_intt(dehalo_ctx* ctx, int field, uint64_t* a, uint32_t log_ext, const uint64_t omega_ext_inv[4], const uint64_t ext_n_inv[4],
                       const uint64_t zeta[4]) {
     if (log_ext > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "log_ext > 30");
-    NttArgs A{field, 0, log_ext, omega_ext_inv, ext_n_inv, zeta};
     size_t N = (size_t)1 << log_ext;
-    return with_host_io(ctx, a, N, a, N, true, [](dehalo_ctx* c, uint64_t* di, uint64_t*, void* p) {
-        NttArgs* A = (NttArgs*)p;
-        return dehalo_coset_intt_device(c, A->field, di, A->log_ext, A->w, A->s, A->z, 1, nullptr);
-    }, &A);
+    return ntt_host_io(ctx, a, N, a, N, true, [&](uint64_t* di, uint64_t*) {
+        return dehalo_coset_intt_device(ctx, field, di, log_ext, omega_ext_inv, ext_n_inv, zeta, 1, nullptr);
+    });
 }
 
 int dehalo_field_op(dehalo_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (!a || !out || op < 0 || op > 6) return dh_fail(ctx, DEHALO_ERR_INVALID, "field_op: bad argument");
     if (n == 0) return 0;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    TRY(dh_ensure(ctx, ctx->ws_fop[0], n * 32));
-    TRY(dh_ensure(ctx, ctx->ws_fop[1], n * 32));
-    TRY(dh_ensure(ctx, ctx->ws_fop[2], n * 32));
-    TRY(dh_h2d(ctx, ctx->ws_fop[0].p, a, n * 32, ctx->stream));
-    if (b) TRY(dh_h2d(ctx, ctx->ws_fop[1].p, b, n * 32, ctx->stream));
-    TRY(do_field_op(ctx, field, op, (const fe*)ctx->ws_fop[0].p, b ? (const fe*)ctx->ws_fop[1].p : nullptr, (fe*)ctx->ws_fop[2].p, n, ctx->stream));
-    TRY(dh_d2h(ctx, out, ctx->ws_fop[2].p, n * 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&] {
+        DevBuf* w = ctx->ws_fop;
+        return with_host_io(ctx, {{w[0], a, n * 32}, {w[1], b, n * 32}}, w[2], out, n * 32, [&] {
+            const FieldOps* f = field_ops(field);
+            return f ? f->field_op(ctx, op, (const fe*)w[0].p, b ? (const fe*)w[1].p : nullptr, (fe*)w[2].p, n, ctx->stream) : unknown_field(ctx);
+        });
+    });
 }
 
 int dehalo_field_op_device(dehalo_ctx* ctx, int field, int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (((!d_a || !d_out) && n) || op < 0 || op > 6) return dh_fail(ctx, DEHALO_ERR_INVALID, "field_op: bad argument");
     if (n == 0) return 0;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_field_op(ctx, field, op, (const fe*)d_a, (const fe*)d_b, (fe*)d_out, n, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.field_op(ctx, op, (const fe*)d_a, (const fe*)d_b, (fe*)d_out, n, s); });
 }
 
 // ---- field-vector primitives (poly.cuh) ---------------------------------------------------------
 int dehalo_eval_polynomial_device(dehalo_ctx* ctx, int field, const uint64_t* d_coeffs, size_t len, size_t stride_elems, size_t batch,
                                   const uint64_t point[4], uint64_t* d_out, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_coeffs && len) || !point || !d_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial: null argument");
     if (batch > 1 && stride_elems < len) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial: stride shorter than the polynomial");
     if (batch >= 65536) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial: batch too large");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_eval_poly(ctx, field, (const fe*)d_coeffs, len, stride_elems, batch, point, (fe*)d_out, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.eval_poly(ctx, (const fe*)d_coeffs, len, stride_elems, batch, point, (fe*)d_out, s);
+    });
 }
 
 int dehalo_eval_polynomial_multi_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_polys, size_t count, size_t len, const uint64_t* points,
@@ -889,80 +780,59 @@ int dehalo_eval_polynomial_multi_device(dehalo_ctx* ctx, int field, const uint64
 
 int dehalo_eval_polynomial_multi_masked_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_polys, size_t count, size_t len, const uint64_t* points,
                                                uint32_t num_points, const uint8_t* wanted, uint64_t* d_out, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((count && !d_polys) || !points || !d_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_multi: null argument");
     for (size_t j = 0; j < count; j++)
         if (!d_polys[j] && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_multi: null polynomial");
     if (num_points == 0 || num_points > 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_multi: 1 to 4 points");
     if (count >= 65536) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_multi: too many polynomials");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_eval_poly_multi(ctx, field, (const fe* const*)d_polys, count, len, points, num_points, (fe*)d_out, pick_stream(ctx, stream), wanted);
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.eval_poly_multi(ctx, (const fe* const*)d_polys, count, len, points, num_points, (fe*)d_out, s, wanted);
+    });
 }
 
 int dehalo_eval_polynomial(dehalo_ctx* ctx, int field, const uint64_t* coeffs, size_t len, const uint64_t point[4], uint64_t out[4]) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!coeffs && len) || !point || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial: null argument");
-    HostPin pin_c(coeffs, len * 32);
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        TRY(dh_ensure(ctx, ctx->ws_poly_io[0], std::max<size_t>(32, len * 32)));
-        TRY(dh_ensure(ctx, ctx->ws_poly_io[1], 32));
-        if (len) TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, coeffs, len * 32, ctx->stream));
-    }
-    TRY(dehalo_eval_polynomial_device(ctx, field, (const uint64_t*)ctx->ws_poly_io[0].p, len, len, 1, point, (uint64_t*)ctx->ws_poly_io[1].p, nullptr));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(dh_d2h(ctx, out, ctx->ws_poly_io[1].p, 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&] {
+        HostPin pin_c(coeffs, len * 32);
+        DevBuf* w = ctx->ws_poly_io;
+        return with_host_io(ctx, {{w[0], coeffs, len * 32}}, w[1], out, 32, [&] {
+            return dehalo_eval_polynomial_device(ctx, field, (const uint64_t*)w[0].p, len, len, 1, point, (uint64_t*)w[1].p, nullptr);
+        });
+    });
 }
 
 int dehalo_batch_invert_device(dehalo_ctx* ctx, int field, uint64_t* d_values, size_t len, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!d_values && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "batch_invert: null argument");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_batch_invert(ctx, field, (fe*)d_values, len, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.batch_invert(ctx, (fe*)d_values, len, s); });
 }
 
 int dehalo_batch_invert(dehalo_ctx* ctx, int field, uint64_t* values, size_t len) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (!values && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "batch_invert: null argument");
-    HostPin pin_v(values, len * 32);
-    if (len == 0) return 0;
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        TRY(dh_ensure(ctx, ctx->ws_poly_io[0], len * 32));
-        TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, values, len * 32, ctx->stream));
-    }
-    TRY(dehalo_batch_invert_device(ctx, field, (uint64_t*)ctx->ws_poly_io[0].p, len, nullptr));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(dh_d2h(ctx, values, ctx->ws_poly_io[0].p, len * 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&] {
+        HostPin pin_v(values, len * 32);
+        if (len == 0) return 0;
+        DevBuf* w = ctx->ws_poly_io;
+        return with_host_io(ctx, {{w[0], values, len * 32}}, w[0], values, len * 32, [&] {
+            return dehalo_batch_invert_device(ctx, field, (uint64_t*)w[0].p, len, nullptr);
+        });
+    });
 }
 
 int dehalo_prefix_product_device(dehalo_ctx* ctx, int field, const uint64_t* d_in, size_t len, uint64_t* d_out, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_in || !d_out) && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "prefix_product: null argument");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_prefix_product(ctx, field, (const fe*)d_in, len, (fe*)d_out, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.prefix_product(ctx, (const fe*)d_in, len, (fe*)d_out, s); });
 }
 
 int dehalo_grand_product_batch_device(dehalo_ctx* ctx, int field, const uint64_t* d_num, const uint64_t* d_den, size_t len, size_t batch, size_t stride_elems,
                                       uint64_t* d_z, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_num || !d_den || !d_z) && len && batch) return dh_fail(ctx, DEHALO_ERR_INVALID, "grand_product: null argument");
     if (batch > 1 && stride_elems < len) return dh_fail(ctx, DEHALO_ERR_INVALID, "grand_product: stride shorter than the columns");
     if (batch >= 65536) return dh_fail(ctx, DEHALO_ERR_INVALID, "grand_product: batch too large");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_grand_product(ctx, field, (const fe*)d_num, (const fe*)d_den, len, batch, stride_elems, (fe*)d_z, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.grand_product(ctx, (const fe*)d_num, (const fe*)d_den, len, batch, stride_elems, (fe*)d_z, s);
+    });
 }
 
 int dehalo_grand_product_device(dehalo_ctx* ctx, int field, const uint64_t* d_num, const uint64_t* d_den, size_t len, uint64_t* d_z, void* stream) {
@@ -972,56 +842,40 @@ int dehalo_grand_product_device(dehalo_ctx* ctx, int field, const uint64_t* d_nu
 int dehalo_grand_product(dehalo_ctx* ctx, int field, const uint64_t* num, const uint64_t* den, size_t len, uint64_t* z) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!num || !den || !z) && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "grand_product: null argument");
-    HostPin pin_n(num, len * 32), pin_d(den, len * 32), pin_z(z, len * 32);
-    if (len == 0) return 0;
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        for (int i = 0; i < 3; i++) TRY(dh_ensure(ctx, ctx->ws_poly_io[i], len * 32));
-        TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, num, len * 32, ctx->stream));
-        TRY(dh_h2d(ctx, ctx->ws_poly_io[1].p, den, len * 32, ctx->stream));
-    }
-    TRY(dehalo_grand_product_device(ctx, field, (const uint64_t*)ctx->ws_poly_io[0].p, (const uint64_t*)ctx->ws_poly_io[1].p, len,
-                                    (uint64_t*)ctx->ws_poly_io[2].p, nullptr));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(dh_d2h(ctx, z, ctx->ws_poly_io[2].p, len * 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&] {
+        HostPin pin_n(num, len * 32), pin_d(den, len * 32), pin_z(z, len * 32);
+        if (len == 0) return 0;
+        DevBuf* w = ctx->ws_poly_io;
+        return with_host_io(ctx, {{w[0], num, len * 32}, {w[1], den, len * 32}}, w[2], z, len * 32, [&] {
+            return dehalo_grand_product_device(ctx, field, (const uint64_t*)w[0].p, (const uint64_t*)w[1].p, len, (uint64_t*)w[2].p, nullptr);
+        });
+    });
 }
 
 int dehalo_lincomb_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_cols, const uint64_t* coefs, size_t count, size_t len, uint64_t* d_out,
                           const uint64_t* sub_const, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((count && (!d_cols || !coefs)) || (!d_out && len)) return dh_fail(ctx, DEHALO_ERR_INVALID, "lincomb: null argument");
     for (size_t j = 0; j < count; j++)
         if (!d_cols[j] && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "lincomb: null column");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_lincomb(ctx, field, (const fe* const*)d_cols, coefs, count, len, (fe*)d_out, sub_const, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.lincomb(ctx, (const fe* const*)d_cols, coefs, count, len, (fe*)d_out, sub_const, s);
+    });
 }
 
 int dehalo_scale_device(dehalo_ctx* ctx, int field, uint64_t* d_a, size_t len, const uint64_t* pattern, uint32_t period, const uint64_t* d_factor, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_a && len) || (period && !pattern)) return dh_fail(ctx, DEHALO_ERR_INVALID, "scale: null argument");
     if (period > 8 || (period & (period - 1))) return dh_fail(ctx, DEHALO_ERR_INVALID, "scale: period must be 0, 1, 2, 4 or 8");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_scale(ctx, field, (fe*)d_a, len, pattern, period, (const fe*)d_factor, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.scale(ctx, (fe*)d_a, len, pattern, period, (const fe*)d_factor, s); });
 }
 
 int dehalo_kate_division_device(dehalo_ctx* ctx, int field, const uint64_t* d_a, size_t len, const uint64_t point[4], uint64_t* d_q, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (((!d_a || !d_q) && len > 1) || !point) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division: null argument");
     if (d_a == d_q) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division: a and q may not alias");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_kate_division(ctx, field, (const fe*)d_a, len, point, (fe*)d_q, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.kate_division(ctx, (const fe*)d_a, len, point, (fe*)d_q, s); });
 }
 
 int dehalo_kate_division_batch_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_a, size_t len, const uint64_t* points, uint64_t* const* d_q,
                                       size_t count, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (count && (!d_a || !d_q || !points)) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division_batch: null argument");
     if (count > 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division_batch: at most 8 divisions per call");
     if (len > (1ull << 22)) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division_batch: polynomials of at most 2^22 coefficients");
@@ -1029,41 +883,37 @@ int dehalo_kate_division_batch_device(dehalo_ctx* ctx, int field, const uint64_t
         if ((!d_a[y] || !d_q[y]) && len > 1) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division_batch: null polynomial");
         if (d_a[y] == d_q[y]) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division_batch: a and q may not alias");
     }
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_kate_division_batch(ctx, field, (const fe* const*)d_a, len, points, (fe* const*)d_q, count, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.kate_division_batch(ctx, (const fe* const*)d_a, len, points, (fe* const*)d_q, count, s);
+    });
 }
 
 int dehalo_kate_division(dehalo_ctx* ctx, int field, const uint64_t* a, size_t len, const uint64_t point[4], uint64_t* q) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (((!a || !q) && len > 1) || !point) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division: null argument");
-    HostPin pin_a(a, len * 32), pin_q(q, (len - 1) * 32);
-    if (len <= 1) return 0;
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    TRY(dh_ensure(ctx, ctx->ws_poly_io[0], len * 32));
-    TRY(dh_ensure(ctx, ctx->ws_poly_io[1], len * 32));
-    TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, a, len * 32, ctx->stream));
-    TRY(dehalo_kate_division_device(ctx, field, (const uint64_t*)ctx->ws_poly_io[0].p, len, point, (uint64_t*)ctx->ws_poly_io[1].p, nullptr));
-    TRY(dh_d2h(ctx, q, ctx->ws_poly_io[1].p, (len - 1) * 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return dh_guard(ctx, [&] {
+        HostPin pin_a(a, len * 32), pin_q(q, (len - 1) * 32);
+        if (len <= 1) return 0;
+        DevBuf* w = ctx->ws_poly_io;      // (q: len - 1 coefficients in a buffer sized for len, as a)
+        return with_host_io(ctx, {{w[0], a, len * 32}, {w[1], nullptr, len * 32}}, w[1], q, (len - 1) * 32, [&] {
+            return dehalo_kate_division_device(ctx, field, (const uint64_t*)w[0].p, len, point, (uint64_t*)w[1].p, nullptr);
+        });
+    });
 }
 
 int dehalo_permute_expression_pair_batch_device(dehalo_ctx* ctx, int field, const uint64_t* d_inputs, const uint64_t* d_tables, size_t usable_rows, size_t batch,
                                                 size_t stride_elems, uint64_t* d_permuted_inputs, uint64_t* d_permuted_tables, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_inputs || !d_tables || !d_permuted_inputs || !d_permuted_tables) && usable_rows && batch)
         return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: null argument");
     if (d_permuted_inputs == d_inputs || d_permuted_tables == d_tables || d_permuted_inputs == d_tables || d_permuted_tables == d_inputs)
         return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: outputs may not alias inputs");
     if (batch > 1 && stride_elems < usable_rows) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: stride shorter than the columns");
     if (batch >= 4096) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: batch too large");
-    if (field < 0 || field > 3) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return lookup_permute_impl(ctx, field, (const fe*)d_inputs, (const fe*)d_tables, usable_rows, batch, stride_elems, (fe*)d_permuted_inputs,
-                               (fe*)d_permuted_tables, pick_stream(ctx, stream));
+    if (!field_ops(field)) return unknown_field(ctx);
+    return dh_device(ctx, stream, [&](hipStream_t s) {
+        return lookup_permute_impl(ctx, field, (const fe*)d_inputs, (const fe*)d_tables, usable_rows, batch, stride_elems, (fe*)d_permuted_inputs,
+                                   (fe*)d_permuted_tables, s);
+    });
 }
 
 static int permute_ptrs(dehalo_ctx* ctx, int field, const uint64_t* const* d_inputs, const uint64_t* const* d_tables, size_t usable_rows, size_t batch,
@@ -1082,32 +932,34 @@ static int permute_ptrs(dehalo_ctx* ctx, int field, const uint64_t* const* d_inp
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!d_inputs || !d_tables || !d_permuted_inputs || !d_permuted_tables) && batch) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: null argument");
     if (batch >= 4096) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: batch too large");
-    if (field < 0 || field > 3) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
+    if (!field_ops(field)) return unknown_field(ctx);
     for (size_t y = 0; y < batch && usable_rows; y++) {
         if (!d_inputs[y] || !d_tables[y] || !d_permuted_inputs[y] || !d_permuted_tables[y]) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: null column");
         for (size_t z = 0; z < batch; z++)
             if (d_permuted_inputs[y] == d_inputs[z] || d_permuted_inputs[y] == d_tables[z] || d_permuted_tables[y] == d_inputs[z] || d_permuted_tables[y] == d_tables[z])
                 return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: outputs may not alias inputs");
     }
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return lookup_permute_ptrs(ctx, field, (const fe* const*)d_inputs, (const fe* const*)d_tables, usable_rows, batch, (fe* const*)d_permuted_inputs, (fe* const*)d_permuted_tables,
-                               pick_stream(ctx, stream), d_status, distinct);
+    return dh_device(ctx, stream, [&](hipStream_t s) {
+        return lookup_permute_ptrs(ctx, field, (const fe* const*)d_inputs, (const fe* const*)d_tables, usable_rows, batch, (fe* const*)d_permuted_inputs,
+                                   (fe* const*)d_permuted_tables, s, d_status, distinct);
+    });
 }
 int dehalo_permute_expression_pair_distinct_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_inputs, const uint64_t* const* d_tables, size_t usable_rows, size_t batch,
                                                    uint64_t* const* d_permuted_inputs, uint64_t* const* d_permuted_tables, const uint32_t* const* d_rep_rows,
                                                    const uint32_t* const* d_multiplicities, const uint32_t* distinct_count, int32_t* d_status, void* stream) {
     if (ctx && batch && (!d_rep_rows || !d_multiplicities || !distinct_count)) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: null argument");
-    std::vector<LookupDistinct> dist(batch);
-    for (size_t y = 0; y < batch; y++) {
-        dist[y] = LookupDistinct{d_rep_rows[y], d_multiplicities[y], distinct_count[y]};
-        if (distinct_count[y] && (!d_rep_rows[y] || !d_multiplicities[y])) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: null distinct-row array");
-        if (distinct_count[y] > usable_rows) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: more distinct rows than usable rows");
-        for (size_t z = 0; z < y; z++)      // lookups of one table must describe it alike
-            if (d_tables && d_tables[z] == d_tables[y] && (d_rep_rows[z] != d_rep_rows[y] || d_multiplicities[z] != d_multiplicities[y] || distinct_count[z] != distinct_count[y]))
-                return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: lookups that share a table must pass the same distinct-row arrays");
-    }
-    return permute_ptrs(ctx, field, d_inputs, d_tables, usable_rows, batch, d_permuted_inputs, d_permuted_tables, (int*)d_status, stream, dist.data());
+    return dh_guard(ctx, [&] {
+        std::vector<LookupDistinct> dist(batch);
+        for (size_t y = 0; y < batch; y++) {
+            dist[y] = LookupDistinct{d_rep_rows[y], d_multiplicities[y], distinct_count[y]};
+            if (distinct_count[y] && (!d_rep_rows[y] || !d_multiplicities[y])) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: null distinct-row array");
+            if (distinct_count[y] > usable_rows) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: more distinct rows than usable rows");
+            for (size_t z = 0; z < y; z++)      // lookups of one table must describe it alike
+                if (d_tables && d_tables[z] == d_tables[y] && (d_rep_rows[z] != d_rep_rows[y] || d_multiplicities[z] != d_multiplicities[y] || distinct_count[z] != distinct_count[y]))
+                    return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair_distinct: lookups that share a table must pass the same distinct-row arrays");
+        }
+        return permute_ptrs(ctx, field, d_inputs, d_tables, usable_rows, batch, d_permuted_inputs, d_permuted_tables, (int*)d_status, stream, dist.data());
+    });
 }
 
 int dehalo_permute_expression_pair_device(dehalo_ctx* ctx, int field, const uint64_t* d_input, const uint64_t* d_table, size_t usable_rows,
@@ -1119,25 +971,24 @@ int dehalo_permute_expression_pair(dehalo_ctx* ctx, int field, const uint64_t* i
                                    uint64_t* permuted_table) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!input || !table || !permuted_input || !permuted_table) && usable_rows) return dh_fail(ctx, DEHALO_ERR_INVALID, "permute_expression_pair: null argument");
-    HostPin pin_i(input, usable_rows * 32), pin_t(table, usable_rows * 32), pin_pi(permuted_input, usable_rows * 32), pin_pt(permuted_table, usable_rows * 32);
-    if (usable_rows == 0) return 0;
-    std::lock_guard<std::recursive_mutex> hold(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
-    {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    // (not with_host_io: two columns back to back in one workspace buffer each way)
+    return dh_guard(ctx, [&] {
+        HostPin pin_i(input, usable_rows * 32), pin_t(table, usable_rows * 32), pin_pi(permuted_input, usable_rows * 32), pin_pt(permuted_table, usable_rows * 32);
+        if (usable_rows == 0) return 0;
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);   // one critical section per host-buffer call: staging, kernels, download
         (void)hipSetDevice(ctx->device);
         TRY(dh_ensure(ctx, ctx->ws_poly_io[0], usable_rows * 64));
         TRY(dh_ensure(ctx, ctx->ws_poly_io[1], usable_rows * 64));
         TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, input, usable_rows * 32, ctx->stream));
         TRY(dh_h2d(ctx, (char*)ctx->ws_poly_io[0].p + usable_rows * 32, table, usable_rows * 32, ctx->stream));
-    }
-    uint64_t* d_in = (uint64_t*)ctx->ws_poly_io[0].p;
-    uint64_t* d_out = (uint64_t*)ctx->ws_poly_io[1].p;
-    TRY(dehalo_permute_expression_pair_device(ctx, field, d_in, d_in + usable_rows * 4, usable_rows, d_out, d_out + usable_rows * 4, nullptr));
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(dh_d2h(ctx, permuted_input, d_out, usable_rows * 32, ctx->stream));
-    TRY(dh_d2h(ctx, permuted_table, d_out + usable_rows * 4, usable_rows * 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+        uint64_t* d_in = (uint64_t*)ctx->ws_poly_io[0].p;
+        uint64_t* d_out = (uint64_t*)ctx->ws_poly_io[1].p;
+        TRY(dehalo_permute_expression_pair_device(ctx, field, d_in, d_in + usable_rows * 4, usable_rows, d_out, d_out + usable_rows * 4, nullptr));
+        TRY(dh_d2h(ctx, permuted_input, d_out, usable_rows * 32, ctx->stream));
+        TRY(dh_d2h(ctx, permuted_table, d_out + usable_rows * 4, usable_rows * 32, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return 0;
+    });
 }
 
 // ---- quotient numerator (evalh.cuh) -----------------------------------------------------------------
@@ -1147,109 +998,97 @@ int dehalo_graph_create(dehalo_ctx* ctx, int field, const uint64_t* constants, u
     if (!ctx) return DEHALO_ERR_INVALID;
     if (!out || (num_constants && !constants) || (num_rotations && !rotations) || (num_calcs && !calcs) || (num_horner_parts && !horner_parts))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_create: null argument");
-    if (field < 0 || field > 3) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
+    const FieldOps* f = field_ops(field);
+    if (!f) return unknown_field(ctx);
     if (num_calcs > (1u << 20) || num_intermediates > (1u << 20)) return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_create: program too large");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    dehalo_graph* g = new dehalo_graph();
-    memset(g, 0, sizeof(*g));
-    g->field = field; g->num_calcs = num_calcs; g->num_parts = num_horner_parts; g->num_constants = num_constants;
-    std::vector<DevCalc> dc;
-    std::vector<DevSrc> dp;
-    int rc = compile_graph(ctx, g, rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, dc, dp);
-    hipError_t e = hipSuccess;
-    if (rc == 0) e = hipMalloc((void**)&g->d_calcs, std::max<size_t>(1, dc.size()) * sizeof(DevCalc));
-    if (rc == 0 && e == hipSuccess) e = hipMalloc((void**)&g->d_parts, dp.size() * sizeof(DevSrc));
-    if (rc == 0 && e == hipSuccess) e = hipMalloc((void**)&g->d_constants, std::max<size_t>(1, num_constants) * sizeof(fe));
-    if (rc == 0 && e == hipSuccess && !dc.empty()) e = hipMemcpy(g->d_calcs, dc.data(), dc.size() * sizeof(DevCalc), hipMemcpyHostToDevice);
-    if (rc == 0 && e == hipSuccess) e = hipMemcpy(g->d_parts, dp.data(), dp.size() * sizeof(DevSrc), hipMemcpyHostToDevice);
-    if (rc == 0 && e == hipSuccess) rc = do_graph_upload(ctx, field, g, constants, ctx->stream);
-    if (rc != 0 || e != hipSuccess) {
-        (void)hipFree(g->d_calcs); (void)hipFree(g->d_parts); (void)hipFree(g->d_constants);
-        delete g;
-        return rc ? rc : dh_fail(ctx, e == hipErrorOutOfMemory ? DEHALO_ERR_OOM : DEHALO_ERR_HIP, std::string("graph_create: ") + hipGetErrorString(e));
-    }
-    *out = g;
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        std::unique_ptr<dehalo_graph, GraphFree> g(new dehalo_graph());
+        memset(g.get(), 0, sizeof(*g));
+        g->field = field; g->num_calcs = num_calcs; g->num_parts = num_horner_parts; g->num_constants = num_constants;
+        std::vector<DevCalc> dc;
+        std::vector<DevSrc> dp;
+        TRY(compile_graph(ctx, g.get(), rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, dc, dp));
+        hipError_t e = hipMalloc((void**)&g->d_calcs, std::max<size_t>(1, dc.size()) * sizeof(DevCalc));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->d_parts, dp.size() * sizeof(DevSrc));
+        if (e == hipSuccess) e = hipMalloc((void**)&g->d_constants, std::max<size_t>(1, num_constants) * sizeof(fe));
+        if (e == hipSuccess && !dc.empty()) e = hipMemcpy(g->d_calcs, dc.data(), dc.size() * sizeof(DevCalc), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(g->d_parts, dp.data(), dp.size() * sizeof(DevSrc), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return dh_fail(ctx, e == hipErrorOutOfMemory ? DEHALO_ERR_OOM : DEHALO_ERR_HIP, std::string("graph_create: ") + hipGetErrorString(e));
+        TRY(f->graph_upload(ctx, g.get(), constants, ctx->stream));
+        *out = g.release();
+        return 0;
+    });
 }
 
 int dehalo_graph_release(dehalo_ctx* ctx, dehalo_graph* g) {
     if (!ctx || !g) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
-    (void)hipFree(g->d_calcs); (void)hipFree(g->d_parts); (void)hipFree(g->d_constants);
-    delete g;
-    return 0;
+    return dh_guard(ctx, [&] {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        (void)hipDeviceSynchronize();
+        GraphFree()(g);
+        return 0;
+    });
 }
 
 int dehalo_graph_evaluate_device(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale,
                                  const uint64_t* d_previous, uint64_t* d_out, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!g || !in || !d_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_evaluate: null argument");
     if (log_rows > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_evaluate: log_rows > 30");
     if (in->num_fixed < g->max_fixed || in->num_advice < g->max_advice || in->num_instance < g->max_instance || in->num_challenges < g->max_challenge)
         return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_evaluate: the program reads a column or challenge that was not supplied");
     if ((in->num_fixed && !in->fixed) || (in->num_advice && !in->advice) || (in->num_instance && !in->instance) || (in->num_challenges && !in->challenges))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_evaluate: null column table");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_graph_evaluate(ctx, g, in, log_rows, rot_scale, (const fe*)d_previous, (fe*)d_out, pick_stream(ctx, stream));
+    return field_device(ctx, g->field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.graph_evaluate(ctx, g, in, log_rows, rot_scale, (const fe*)d_previous, (fe*)d_out, s);
+    });
 }
 
 int dehalo_graph_evaluate_batch_device(dehalo_ctx* ctx, const dehalo_graph* const* graphs, uint32_t count, const dehalo_eval_inputs* in, uint32_t log_rows,
                                        uint32_t rot_scale, uint64_t* const* d_outs, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if ((count && (!graphs || !d_outs)) || !in) return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_evaluate_batch: null argument");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    // DEHALO_GRAPH_BATCH=0: one staging + one evaluation launch per program, as before round 4 (A/B measurements)
-    static const bool batched = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_GRAPH_BATCH"); return !(e && e[0] == '0'); }();
-    bool same_field = count >= 2 && log_rows <= 30;
-    for (uint32_t i = 0; same_field && i < count; i++) {
-        const dehalo_graph* g = graphs[i];
-        same_field = g && d_outs[i] && g->field == graphs[0]->field && in->num_fixed >= g->max_fixed && in->num_advice >= g->max_advice && in->num_instance >= g->max_instance &&
-                     in->num_challenges >= g->max_challenge;
-    }
-    if (same_field && ((in->num_fixed && !in->fixed) || (in->num_advice && !in->advice) || (in->num_instance && !in->instance) || (in->num_challenges && !in->challenges))) same_field = false;
-    if (!batched || !same_field) {      // (the single-program entry point reports what is wrong with an argument)
-        for (uint32_t i = 0; i < count; i++)
-            TRY(dehalo_graph_evaluate_device(ctx, graphs[i], in, log_rows, rot_scale, nullptr, d_outs[i], stream));
-        return 0;
-    }
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = pick_stream(ctx, stream);
-#define CALL(N) graph_evaluate_batch_##N(ctx, graphs, count, in, log_rows, rot_scale, (fe* const*)d_outs, s)
-    FIELD_SWITCH(ctx, graphs[0]->field, CALL)
-#undef CALL
+    return dh_device(ctx, stream, [&](hipStream_t s) -> int {
+        // DEHALO_GRAPH_BATCH=0: one staging + one evaluation launch per program, as before round 4 (A/B measurements)
+        static const bool batched = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_GRAPH_BATCH"); return !(e && e[0] == '0'); }();
+        bool same_field = count >= 2 && log_rows <= 30;
+        for (uint32_t i = 0; same_field && i < count; i++) {
+            const dehalo_graph* g = graphs[i];
+            same_field = g && d_outs[i] && g->field == graphs[0]->field && in->num_fixed >= g->max_fixed && in->num_advice >= g->max_advice && in->num_instance >= g->max_instance &&
+                         in->num_challenges >= g->max_challenge;
+        }
+        if (same_field && ((in->num_fixed && !in->fixed) || (in->num_advice && !in->advice) || (in->num_instance && !in->instance) || (in->num_challenges && !in->challenges))) same_field = false;
+        if (!batched || !same_field) {      // (the single-program entry point reports what is wrong with an argument)
+            for (uint32_t i = 0; i < count; i++)
+                TRY(dehalo_graph_evaluate_device(ctx, graphs[i], in, log_rows, rot_scale, nullptr, d_outs[i], stream));
+            return 0;
+        }
+        const FieldOps* f = field_ops(graphs[0]->field);
+        return f ? f->graph_evaluate_batch(ctx, graphs, count, in, log_rows, rot_scale, (fe* const*)d_outs, s) : unknown_field(ctx);
+    });
 }
 
 int dehalo_permutation_h_device(dehalo_ctx* ctx, int field, const dehalo_perm_inputs* in, uint32_t log_rows, uint32_t rot_scale, uint64_t* d_values,
                                 void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!in || !d_values || !in->l0 || !in->l_last || !in->l_active_row || !in->beta || !in->gamma || !in->y || !in->delta || !in->beta_zeta || !in->extended_omega)
         return dh_fail(ctx, DEHALO_ERR_INVALID, "permutation_h: null argument");
     if ((in->num_sets && !in->z) || (in->num_columns && (!in->columns || !in->sigma))) return dh_fail(ctx, DEHALO_ERR_INVALID, "permutation_h: null column table");
     if (log_rows == 0 || log_rows > 30 || in->chunk_len == 0 || (uint64_t)in->num_sets * in->chunk_len < in->num_columns)
         return dh_fail(ctx, DEHALO_ERR_INVALID, "permutation_h: sets * chunk_len must cover the columns");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_perm_h(ctx, field, in, log_rows, rot_scale, (fe*)d_values, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.perm_h(ctx, in, log_rows, rot_scale, (fe*)d_values, s); });
 }
 
 int dehalo_lookup_h_device(dehalo_ctx* ctx, int field, const dehalo_lookup_inputs* in, uint32_t log_rows, uint32_t rot_scale, uint64_t* d_values,
                            void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!in || !d_values || !in->product_coset || !in->permuted_input_coset || !in->permuted_table_coset || !in->table_value || !in->l0 || !in->l_last ||
         !in->l_active_row || !in->beta || !in->gamma || !in->y)
         return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_h: null argument");
     if (log_rows > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_h: log_rows > 30");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_lookup_h(ctx, field, in, log_rows, rot_scale, (fe*)d_values, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.lookup_h(ctx, in, log_rows, rot_scale, (fe*)d_values, s); });
 }
 
 int dehalo_product_terms_device(dehalo_ctx* ctx, int field, const dehalo_product_inputs* in, size_t n, uint64_t* d_num, uint64_t* d_den, size_t stride_elems, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!in || !d_num || !d_den || !in->beta || !in->gamma) return dh_fail(ctx, DEHALO_ERR_INVALID, "product_terms: null argument");
     if (in->num_columns && (!in->columns || !in->sigma || !in->omega_powers || !in->delta || !in->set_factors || in->chunk_len == 0))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "product_terms: incomplete permutation inputs");
@@ -1257,21 +1096,11 @@ int dehalo_product_terms_device(dehalo_ctx* ctx, int field, const dehalo_product
         return dh_fail(ctx, DEHALO_ERR_INVALID, "product_terms: incomplete lookup inputs");
     if (in->num_columns > 256 || in->num_lookups > 256) return dh_fail(ctx, DEHALO_ERR_INVALID, "product_terms: too many columns");
     if (stride_elems < n) return dh_fail(ctx, DEHALO_ERR_INVALID, "product_terms: stride shorter than the columns");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    hipStream_t s = pick_stream(ctx, stream);
-    switch (field) {
-        case DEHALO_FIELD_BN254_FR: return product_terms_bn254_fr(ctx, in, n, (fe*)d_num, (fe*)d_den, stride_elems, s);
-        case DEHALO_FIELD_BN254_FQ: return product_terms_bn254_fq(ctx, in, n, (fe*)d_num, (fe*)d_den, stride_elems, s);
-        case DEHALO_FIELD_PASTA_FP: return product_terms_pasta_fp(ctx, in, n, (fe*)d_num, (fe*)d_den, stride_elems, s);
-        case DEHALO_FIELD_PASTA_FQ: return product_terms_pasta_fq(ctx, in, n, (fe*)d_num, (fe*)d_den, stride_elems, s);
-        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
-    }
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.product_terms(ctx, in, n, (fe*)d_num, (fe*)d_den, stride_elems, s); });
 }
 
 int dehalo_lookup_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale,
                                  uint64_t* d_values, void* stream) {
-    if (!ctx) return DEHALO_ERR_INVALID;
     if (!in || !d_values || count == 0) return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_h_batch: null argument");
     if (count > 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_h_batch: more than 8 lookups in one call");
     for (uint32_t l = 0; l < count; l++) {
@@ -1284,17 +1113,17 @@ int dehalo_lookup_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_lookup
             return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_h_batch: the lookups of one call share l0 / l_last / l_active_row, the challenges and the form flags");
     }
     if (log_rows > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_h: log_rows > 30");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return do_lookup_h_batch(ctx, field, in, count, log_rows, rot_scale, (fe*)d_values, pick_stream(ctx, stream));
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.lookup_h_batch(ctx, in, count, log_rows, rot_scale, (fe*)d_values, s); });
 }
 
 // ---- measurement ------------------------------------------------------------------------------
 int dehalo_timing_enable(dehalo_ctx* ctx, int on) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    ctx->timing = on != 0;
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        ctx->timing = on != 0;
+        return 0;
+    });
 }
 
 static int timing_collect(dehalo_ctx* ctx) {
@@ -1314,32 +1143,38 @@ static int timing_collect(dehalo_ctx* ctx) {
 
 int dehalo_timing_reset(dehalo_ctx* ctx) {
     if (!ctx) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(timing_collect(ctx));
-    for (int i = 0; i < DEHALO_K_COUNT; i++) { ctx->timing_ms[i] = 0; ctx->timing_cnt[i] = 0; }
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        TRY(timing_collect(ctx));
+        for (int i = 0; i < DEHALO_K_COUNT; i++) { ctx->timing_ms[i] = 0; ctx->timing_cnt[i] = 0; }
+        return 0;
+    });
 }
 
 int dehalo_timing_get(dehalo_ctx* ctx, int kernel_id, double* total_ms, uint64_t* count) {
     if (!ctx || kernel_id < 0 || kernel_id >= DEHALO_K_COUNT || !total_ms || !count) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    TRY(timing_collect(ctx));
-    *total_ms = ctx->timing_ms[kernel_id];
-    *count = ctx->timing_cnt[kernel_id];
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        TRY(timing_collect(ctx));
+        *total_ms = ctx->timing_ms[kernel_id];
+        *count = ctx->timing_cnt[kernel_id];
+        return 0;
+    });
 }
 
 int dehalo_msm_last_shape(dehalo_ctx* ctx, uint32_t out[6]) {
     if (!ctx || !out) return DEHALO_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    memset(out, 0, 6 * sizeof(uint32_t));
-    if (!ctx->ws_counters.p) return 0;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    uint32_t raw[10];      // eight merge-class counters (k_msm_merge_classify2: 2 | 3-4 | 5-8 | 9-64 | 65-512 records, parts of heavy buckets, heavy buckets, unused), L0, M
-    HIP_TRY(ctx, hipMemcpy(raw, ctx->ws_counters.p, sizeof(raw), hipMemcpyDeviceToHost));
-    out[0] = raw[0] + raw[1] + raw[2]; out[1] = raw[3]; out[2] = raw[4]; out[3] = raw[6]; out[4] = raw[8]; out[5] = raw[9];      // light (2-8 records) | 9-64 | 65-512 | > 512
-    return 0;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        memset(out, 0, 6 * sizeof(uint32_t));
+        if (!ctx->ws_counters.p) return 0;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        uint32_t raw[10];      // eight merge-class counters (k_msm_merge_classify2: 2 | 3-4 | 5-8 | 9-64 | 65-512 records, parts of heavy buckets, heavy buckets, unused), L0, M
+        HIP_TRY(ctx, hipMemcpy(raw, ctx->ws_counters.p, sizeof(raw), hipMemcpyDeviceToHost));
+        out[0] = raw[0] + raw[1] + raw[2]; out[1] = raw[3]; out[2] = raw[4]; out[3] = raw[6]; out[4] = raw[8]; out[5] = raw[9];      // light (2-8 records) | 9-64 | 65-512 | > 512
+        return 0;
+    });
 }
 
 }  // extern "C"

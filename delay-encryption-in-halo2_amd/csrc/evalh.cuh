@@ -19,6 +19,8 @@
 
 #include "fp29.cuh"
 #include "internal.hpp"
+#include "ntt.cuh"
+#include "poly.cuh"
 
 #include "evalh_types.hpp"
 
@@ -663,21 +665,19 @@ int product_terms_t(dehalo_ctx* ctx, const dehalo_product_inputs* in, uint64_t n
     return 0;
 }
 
-#define DEFINE_EVALH_ENTRY(NAME, F)                                                                                                              \
-    int convert_form_##NAME(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_internal, hipStream_t s) {                                \
-        if (n) k_convert_form<F><<<(u32)((n + 255) / 256), 256, 0, s>>>(in, out, n, to_internal);                                                  \
-        HIP_TRY(ctx, hipGetLastError());                                                                                                         \
-        return 0; }                                                                                                                              \
-    int graph_upload_##NAME(dehalo_ctx* ctx, dehalo_graph* g, const uint64_t* constants, hipStream_t s) { return graph_upload_t<F>(ctx, g, constants, s); } \
-    int graph_evaluate_##NAME(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale,      \
-                              const fe* prev, fe* out, hipStream_t s) { return graph_evaluate_t<F>(ctx, g, in, log_rows, rot_scale, prev, out, s); } \
-    int graph_evaluate_batch_##NAME(dehalo_ctx* ctx, const dehalo_graph* const* graphs, uint32_t count, const dehalo_eval_inputs* in, uint32_t log_rows,     \
-                                    uint32_t rot_scale, fe* const* outs, hipStream_t s) { return graph_evaluate_batch_t<F>(ctx, graphs, count, in, log_rows, rot_scale, outs, s); } \
-    int perm_h_##NAME(dehalo_ctx* ctx, const dehalo_perm_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s) {             \
-        return perm_h_t<F>(ctx, in, log_rows, rot_scale, v, s); }                                                                                \
-    int lookup_h_##NAME(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s) {         \
-        return lookup_h_t<F>(ctx, in, log_rows, rot_scale, v, s); }                                                                              \
-    int lookup_h_batch_##NAME(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s) { \
-        return lookup_h_batch_t<F>(ctx, in, count, log_rows, rot_scale, v, s); }                                                                 \
-    int product_terms_##NAME(dehalo_ctx* ctx, const dehalo_product_inputs* in, uint64_t n, fe* num, fe* den, uint64_t stride, hipStream_t s) {    \
-        return product_terms_t<F>(ctx, in, n, num, den, stride, s); }
+template <class F>
+int convert_form_t(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_internal, hipStream_t s) {
+    if (n) k_convert_form<F><<<(u32)((n + 255) / 256), 256, 0, s>>>(in, out, n, to_internal);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// the per-field table (internal.hpp FieldOps), in its members' order
+template <class F>
+constexpr FieldOps make_field_ops() {
+    return {&run_ntt_t<F>, &field_op_t<F>,
+            &eval_poly_t<F>, &eval_poly_multi_t<F>, &batch_invert_t<F>, &prefix_product_one_t<F>, &grand_product_t<F>, &lincomb_t<F>, &scale_t<F>,
+            &kate_division_t<F>, &kate_division_batch_t<F>,
+            &convert_form_t<F>, &graph_upload_t<F>, &graph_evaluate_t<F>, &graph_evaluate_batch_t<F>, &perm_h_t<F>, &lookup_h_t<F>, &lookup_h_batch_t<F>,
+            &product_terms_t<F>};
+}

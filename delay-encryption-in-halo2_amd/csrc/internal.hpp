@@ -15,6 +15,7 @@
 
 #include "../../include/dehalo.h"
 #include "ec.cuh"
+#include "guard.hpp"
 
 // Caller buffers of the host entry points are ordinary pageable memory (a Rust Vec<F>): large ones are pinned for the duration of the
 // call so that the copy engine reads / writes them directly instead of going through the runtime's bounce buffers (measured on
@@ -139,12 +140,33 @@ struct dehalo_bases {
     affine_t* table;  // n * (precomp ? W : 1) affine points in HBM, internal (R' = 2^261) canonical form
 };
 
-inline int dh_fail(dehalo_ctx* ctx, int code, const std::string& msg) {
-    if (ctx) {
+// never throws, so that argument checks may run in front of an entry point's guard: a message that cannot be stored is dropped
+inline int dh_fail(dehalo_ctx* ctx, int code, const char* msg) noexcept {
+    if (ctx) try {
         std::lock_guard<std::mutex> lk(ctx->err_mu);
         ctx->err = msg;
-    }
+    } catch (...) {}
     return code;
+}
+inline int dh_fail(dehalo_ctx* ctx, int code, const std::string& msg) noexcept { return dh_fail(ctx, code, msg.c_str()); }
+
+// the guard of a C entry point (guard.hpp) with the context whose last error receives the message
+template <class Body>
+int dh_guard(dehalo_ctx* ctx, Body&& body) noexcept {
+    return dh_guard_noting([ctx](const char* msg) { dh_fail(ctx, DEHALO_ERR_INVALID, msg); }, body);
+}
+
+inline hipStream_t pick_stream(dehalo_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+
+// a device-form entry point: guarded, under the context's lock, on its device, body(stream) on the caller's stream or the context's
+template <class Body>
+int dh_device(dehalo_ctx* ctx, void* stream, Body&& body) noexcept {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        return body(pick_stream(ctx, stream));
+    });
 }
 
 #define HIP_TRY(ctx, expr)                                                                   \
@@ -354,46 +376,55 @@ struct NttScale {
     int form_shift = 0;   // +1: emit the internal form (x * 2^261, canonical, packed); -1: the input is in it
 };
 
-// per-curve / per-field entry points (one translation unit each: msm_*.hip, ntt_*.hip)
-#define DECL_MSM(NAME)                                                                                                                   \
-    int run_msm_##NAME(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, size_t len, size_t batch, jacobian_t* d_out,     \
-                       hipStream_t s);                                                                                                   \
-    int build_table_##NAME(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_std_points, hipStream_t s);                               \
-    int to_affine_##NAME(dehalo_ctx* ctx, const jacobian_t* d_in, affine_t* d_out, uint32_t count, hipStream_t s);                      \
-    int point_sum_##NAME(dehalo_ctx* ctx, const jacobian_t* d_in, uint32_t count, jacobian_t* d_out, hipStream_t s);
-DECL_MSM(bn254)
-DECL_MSM(pallas)
-DECL_MSM(vesta)
-#undef DECL_MSM
+// per-curve operations, one table per curve (msm_*.hip: make_curve_ops in msm.cuh)
+struct CurveOps {
+    int (*run_msm)(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, size_t len, size_t batch, jacobian_t* d_out, hipStream_t s);
+    int (*build_table)(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_std_points, hipStream_t s);
+    int (*to_affine)(dehalo_ctx* ctx, const jacobian_t* d_in, affine_t* d_out, uint32_t count, hipStream_t s);
+    int (*point_sum)(dehalo_ctx* ctx, const jacobian_t* d_in, uint32_t count, jacobian_t* d_out, hipStream_t s);
+    const uint32_t* scalar_modulus;   // r, eight 32-bit words, least significant first
+};
+// (functions rather than const objects: a const namespace-scope object would also be emitted into the device code, pointing at host functions)
+const CurveOps& bn254_curve_ops();
+const CurveOps& pallas_curve_ops();
+const CurveOps& vesta_curve_ops();
 // ParamsKZG::setup's device half (setup.cuh, instantiated in msm_bn254.hip): g[i] = [s^i] G, g_lagrange[i] = [L_i(s)] G into device memory
 int kzg_setup_bn254(dehalo_ctx* ctx, uint32_t k, const uint64_t s[4], const uint64_t omega[4], const uint64_t cfac[4], affine_t* d_g, affine_t* d_gl, hipStream_t st);
 
-#define DECL_NTT(NAME)                                                                                                                       \
-    int run_ntt_##NAME(dehalo_ctx* ctx, const fe* src, uint64_t src_len, uint64_t src_stride, fe* dst, uint64_t dst_stride, uint32_t log_n, \
-                       const uint64_t omega[4], size_t batch, const NttScale& sc, hipStream_t s);                                            \
-    int field_op_##NAME(dehalo_ctx* ctx, int op, const fe* a, const fe* b, fe* out, uint64_t n, hipStream_t s);
-DECL_NTT(bn254_fr)
-DECL_NTT(bn254_fq)
-DECL_NTT(pasta_fp)
-DECL_NTT(pasta_fq)
-#undef DECL_NTT
-
-// field-vector primitives (poly.cuh), instantiated in the same per-field translation units
-#define DECL_POLY(NAME)                                                                                                                     \
-    int eval_poly_##NAME(dehalo_ctx* ctx, const fe* c, uint64_t len, uint64_t stride, size_t batch, const uint64_t pt[4], fe* out, hipStream_t s); \
-    int eval_poly_multi_##NAME(dehalo_ctx* ctx, const fe* const* polys, size_t count, uint64_t len, const uint64_t* pts, uint32_t npts, fe* out, hipStream_t s, const uint8_t* masks); \
-    int batch_invert_##NAME(dehalo_ctx* ctx, fe* v, uint64_t len, hipStream_t s);                                                           \
-    int prefix_product_##NAME(dehalo_ctx* ctx, const fe* in, uint64_t len, fe* out, hipStream_t s);                                         \
-    int grand_product_##NAME(dehalo_ctx* ctx, const fe* num, const fe* den, uint64_t len, size_t batch, uint64_t stride, fe* z, hipStream_t s); \
-    int lincomb_##NAME(dehalo_ctx* ctx, const fe* const* cols, const uint64_t* coefs, size_t count, uint64_t len, fe* out, const uint64_t* sub0, hipStream_t s); \
-    int scale_##NAME(dehalo_ctx* ctx, fe* a, uint64_t len, const uint64_t* pattern, uint32_t period, const fe* d_factor, hipStream_t s);    \
-    int kate_division_##NAME(dehalo_ctx* ctx, const fe* a, uint64_t len, const uint64_t pt[4], fe* q, hipStream_t s);                       \
-    int kate_division_batch_##NAME(dehalo_ctx* ctx, const fe* const* a, uint64_t len, const uint64_t* pts, fe* const* q, size_t count, hipStream_t s);
-DECL_POLY(bn254_fr)
-DECL_POLY(bn254_fq)
-DECL_POLY(pasta_fp)
-DECL_POLY(pasta_fq)
-#undef DECL_POLY
+// per-field operations, one table per field (ntt_*.hip: make_field_ops in evalh.cuh)
+struct dehalo_graph;
+struct FieldOps {
+    // ntt.cuh
+    int (*run_ntt)(dehalo_ctx* ctx, const fe* src, uint64_t src_len, uint64_t src_stride, fe* dst, uint64_t dst_stride, uint32_t log_n, const uint64_t omega[4],
+                   size_t batch, const NttScale& sc, hipStream_t s);
+    int (*field_op)(dehalo_ctx* ctx, int op, const fe* a, const fe* b, fe* out, uint64_t n, hipStream_t s);
+    // field-vector primitives (poly.cuh)
+    int (*eval_poly)(dehalo_ctx* ctx, const fe* c, uint64_t len, uint64_t stride, size_t batch, const uint64_t pt[4], fe* out, hipStream_t s);
+    int (*eval_poly_multi)(dehalo_ctx* ctx, const fe* const* polys, size_t count, uint64_t len, const uint64_t* pts, uint32_t npts, fe* out, hipStream_t s,
+                           const uint8_t* masks);
+    int (*batch_invert)(dehalo_ctx* ctx, fe* v, uint64_t len, hipStream_t s);
+    int (*prefix_product)(dehalo_ctx* ctx, const fe* in, uint64_t len, fe* out, hipStream_t s);
+    int (*grand_product)(dehalo_ctx* ctx, const fe* num, const fe* den, uint64_t len, size_t batch, uint64_t stride, fe* z, hipStream_t s);
+    int (*lincomb)(dehalo_ctx* ctx, const fe* const* cols, const uint64_t* coefs, size_t count, uint64_t len, fe* out, const uint64_t* sub0, hipStream_t s);
+    int (*scale)(dehalo_ctx* ctx, fe* a, uint64_t len, const uint64_t* pattern, uint32_t period, const fe* d_factor, hipStream_t s);
+    int (*kate_division)(dehalo_ctx* ctx, const fe* a, uint64_t len, const uint64_t pt[4], fe* q, hipStream_t s);
+    int (*kate_division_batch)(dehalo_ctx* ctx, const fe* const* a, uint64_t len, const uint64_t* pts, fe* const* q, size_t count, hipStream_t s);
+    // quotient-numerator kernels (evalh.cuh)
+    int (*convert_form)(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_internal, hipStream_t s);
+    int (*graph_upload)(dehalo_ctx* ctx, dehalo_graph* g, const uint64_t* constants, hipStream_t s);
+    int (*graph_evaluate)(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale, const fe* prev, fe* out,
+                          hipStream_t s);
+    int (*graph_evaluate_batch)(dehalo_ctx* ctx, const dehalo_graph* const* graphs, uint32_t count, const dehalo_eval_inputs* in, uint32_t log_rows,
+                                uint32_t rot_scale, fe* const* outs, hipStream_t s);
+    int (*perm_h)(dehalo_ctx* ctx, const dehalo_perm_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);
+    int (*lookup_h)(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);
+    int (*lookup_h_batch)(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);
+    int (*product_terms)(dehalo_ctx* ctx, const dehalo_product_inputs* in, uint64_t n, fe* num, fe* den, uint64_t stride, hipStream_t s);
+};
+const FieldOps& bn254_fr_field_ops();
+const FieldOps& bn254_fq_field_ops();
+const FieldOps& pasta_fp_field_ops();
+const FieldOps& pasta_fq_field_ops();
 
 // lookup_permute.hip
 int lookup_permute_impl(dehalo_ctx* ctx, int field, const fe* d_inputs, const fe* d_tables, uint64_t n, size_t batch, uint64_t stride, fe* d_out_inputs,
@@ -404,22 +435,3 @@ int lookup_permute_impl(dehalo_ctx* ctx, int field, const fe* d_inputs, const fe
 struct LookupDistinct { const uint32_t* d_rep_rows; const uint32_t* d_mult; uint32_t count; };
 int lookup_permute_ptrs(dehalo_ctx* ctx, int field, const fe* const* d_inputs, const fe* const* d_tables, uint64_t n, size_t batch, fe* const* d_out_inputs,
                         fe* const* d_out_tables, hipStream_t s, int* d_status = nullptr, const LookupDistinct* distinct = nullptr);
-
-// quotient-numerator kernels (evalh.cuh)
-struct dehalo_graph;
-#define DECL_EVALH(NAME)                                                                                                                    \
-    int convert_form_##NAME(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_internal, hipStream_t s);                           \
-    int graph_upload_##NAME(dehalo_ctx* ctx, dehalo_graph* g, const uint64_t* constants, hipStream_t s);                                   \
-    int graph_evaluate_##NAME(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale, \
-                              const fe* prev, fe* out, hipStream_t s);                                                                     \
-    int graph_evaluate_batch_##NAME(dehalo_ctx* ctx, const dehalo_graph* const* graphs, uint32_t count, const dehalo_eval_inputs* in, uint32_t log_rows, \
-                                    uint32_t rot_scale, fe* const* outs, hipStream_t s);                                                   \
-    int perm_h_##NAME(dehalo_ctx* ctx, const dehalo_perm_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);         \
-    int lookup_h_##NAME(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);    \
-    int lookup_h_batch_##NAME(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s); \
-    int product_terms_##NAME(dehalo_ctx* ctx, const dehalo_product_inputs* in, uint64_t n, fe* num, fe* den, uint64_t stride, hipStream_t s);
-DECL_EVALH(bn254_fr)
-DECL_EVALH(bn254_fq)
-DECL_EVALH(pasta_fp)
-DECL_EVALH(pasta_fq)
-#undef DECL_EVALH

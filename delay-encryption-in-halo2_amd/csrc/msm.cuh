@@ -1081,12 +1081,9 @@ int to_affine_t(dehalo_ctx* ctx, const jacobian_t* d_in, affine_t* d_out, uint32
     return 0;
 }
 
-#define DEFINE_MSM_ENTRY(NAME, CV)                                                                                                        \
-    int run_msm_##NAME(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, size_t len, size_t batch, jacobian_t* d_out,      \
-                       hipStream_t s) { return run_msm_t<CV>(ctx, bases, d_scalars, len, batch, d_out, s); }                              \
-    int build_table_##NAME(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_std_points, hipStream_t s) {                               \
-        return build_table_t<CV>(ctx, b, d_std_points, s); }                                                                              \
-    int to_affine_##NAME(dehalo_ctx* ctx, const jacobian_t* d_in, affine_t* d_out, uint32_t count, hipStream_t s) {                       \
-        return to_affine_t<CV>(ctx, d_in, d_out, count, s); }                                                                             \
-    int point_sum_##NAME(dehalo_ctx* ctx, const jacobian_t* d_in, uint32_t count, jacobian_t* d_out, hipStream_t s) {                     \
-        return point_sum_t<CV>(ctx, d_in, count, d_out, s); }
+// the per-curve table (internal.hpp CurveOps)
+template <class CV>
+constexpr CurveOps make_curve_ops() {
+    return {&run_msm_t<CV>, &build_table_t<CV>, &to_affine_t<CV>, &point_sum_t<CV>, CV::Scalar::P};
+}
+

@@ -1,3 +1,3 @@
 // MSM kernels + driver instantiated for CurvePallas (one translation unit per curve: parallel builds).
 #include "msm.cuh"
-DEFINE_MSM_ENTRY(pallas, CurvePallas)
+const CurveOps& pallas_curve_ops() { static constexpr CurveOps ops = make_curve_ops<CurvePallas>(); return ops; }

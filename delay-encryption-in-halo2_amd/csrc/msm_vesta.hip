@@ -1,3 +1,3 @@
 // MSM kernels + driver instantiated for CurveVesta (one translation unit per curve: parallel builds).
 #include "msm.cuh"
-DEFINE_MSM_ENTRY(vesta, CurveVesta)
+const CurveOps& vesta_curve_ops() { static constexpr CurveOps ops = make_curve_ops<CurveVesta>(); return ops; }

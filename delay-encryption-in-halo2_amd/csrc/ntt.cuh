@@ -575,9 +575,3 @@ int field_op_t(dehalo_ctx* ctx, int op, const fe* a, const fe* b, fe* out, uint6
     return 0;
 }
 
-#define DEFINE_NTT_ENTRY(NAME, F)                                                                                                            \
-    int run_ntt_##NAME(dehalo_ctx* ctx, const fe* src, uint64_t src_len, uint64_t src_stride, fe* dst, uint64_t dst_stride, uint32_t log_n, \
-                       const uint64_t omega[4], size_t batch, const NttScale& sc, hipStream_t s) {                                           \
-        return run_ntt_t<F>(ctx, src, src_len, src_stride, dst, dst_stride, log_n, omega, batch, sc, s); }                                   \
-    int field_op_##NAME(dehalo_ctx* ctx, int op, const fe* a, const fe* b, fe* out, uint64_t n, hipStream_t s) {                             \
-        return field_op_t<F>(ctx, op, a, b, out, n, s); }

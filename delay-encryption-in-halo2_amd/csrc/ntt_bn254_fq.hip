@@ -2,6 +2,4 @@
 #include "ntt.cuh"
 #include "poly.cuh"
 #include "evalh.cuh"
-DEFINE_NTT_ENTRY(bn254_fq, Bn254Fq)
-DEFINE_POLY_ENTRY(bn254_fq, Bn254Fq)
-DEFINE_EVALH_ENTRY(bn254_fq, Bn254Fq)
+const FieldOps& bn254_fq_field_ops() { static constexpr FieldOps ops = make_field_ops<Bn254Fq>(); return ops; }

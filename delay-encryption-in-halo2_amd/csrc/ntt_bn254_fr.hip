@@ -2,6 +2,4 @@
 #include "ntt.cuh"
 #include "poly.cuh"
 #include "evalh.cuh"
-DEFINE_NTT_ENTRY(bn254_fr, Bn254Fr)
-DEFINE_POLY_ENTRY(bn254_fr, Bn254Fr)
-DEFINE_EVALH_ENTRY(bn254_fr, Bn254Fr)
+const FieldOps& bn254_fr_field_ops() { static constexpr FieldOps ops = make_field_ops<Bn254Fr>(); return ops; }

@@ -2,6 +2,4 @@
 #include "ntt.cuh"
 #include "poly.cuh"
 #include "evalh.cuh"
-DEFINE_NTT_ENTRY(pasta_fp, PastaFp)
-DEFINE_POLY_ENTRY(pasta_fp, PastaFp)
-DEFINE_EVALH_ENTRY(pasta_fp, PastaFp)
+const FieldOps& pasta_fp_field_ops() { static constexpr FieldOps ops = make_field_ops<PastaFp>(); return ops; }

@@ -2,6 +2,4 @@
 #include "ntt.cuh"
 #include "poly.cuh"
 #include "evalh.cuh"
-DEFINE_NTT_ENTRY(pasta_fq, PastaFq)
-DEFINE_POLY_ENTRY(pasta_fq, PastaFq)
-DEFINE_EVALH_ENTRY(pasta_fq, PastaFq)
+const FieldOps& pasta_fq_field_ops() { static constexpr FieldOps ops = make_field_ops<PastaFq>(); return ops; }

@@ -756,22 +756,9 @@ int kate_division_t(dehalo_ctx* ctx, const fe* d_a, uint64_t len, const uint64_t
     return 0;
 }
 
-#define DEFINE_POLY_ENTRY(NAME, F)                                                                                                              \
-    int eval_poly_##NAME(dehalo_ctx* ctx, const fe* c, uint64_t len, uint64_t stride, size_t batch, const uint64_t pt[4], fe* out, hipStream_t s) { \
-        return eval_poly_t<F>(ctx, c, len, stride, batch, pt, out, s); }                                                                         \
-    int eval_poly_multi_##NAME(dehalo_ctx* ctx, const fe* const* polys, size_t count, uint64_t len, const uint64_t* pts, uint32_t npts, fe* out, hipStream_t s, \
-                               const uint8_t* masks) {                                                                                                             \
-        return eval_poly_multi_t<F>(ctx, polys, count, len, pts, npts, out, s, masks); }                                                     \
-    int batch_invert_##NAME(dehalo_ctx* ctx, fe* v, uint64_t len, hipStream_t s) { return batch_invert_t<F>(ctx, v, len, s); }                    \
-    int prefix_product_##NAME(dehalo_ctx* ctx, const fe* in, uint64_t len, fe* out, hipStream_t s) {                                             \
-        return prefix_product_t<F>(ctx, in, len, nullptr, 0, len, 1, out, len, s); }                                                             \
-    int grand_product_##NAME(dehalo_ctx* ctx, const fe* num, const fe* den, uint64_t len, size_t batch, uint64_t stride, fe* z, hipStream_t s) { \
-        return grand_product_t<F>(ctx, num, den, len, batch, stride, z, s); }                                                                   \
-    int lincomb_##NAME(dehalo_ctx* ctx, const fe* const* cols, const uint64_t* coefs, size_t count, uint64_t len, fe* out, const uint64_t* sub0, hipStream_t s) { \
-        return lincomb_t<F>(ctx, cols, coefs, count, len, out, sub0, s); }                                                                       \
-    int scale_##NAME(dehalo_ctx* ctx, fe* a, uint64_t len, const uint64_t* pattern, uint32_t period, const fe* d_factor, hipStream_t s) {        \
-        return scale_t<F>(ctx, a, len, pattern, period, d_factor, s); }                                                                          \
-    int kate_division_##NAME(dehalo_ctx* ctx, const fe* a, uint64_t len, const uint64_t pt[4], fe* q, hipStream_t s) {                           \
-        return kate_division_t<F>(ctx, a, len, pt, q, s); }                                                                                      \
-    int kate_division_batch_##NAME(dehalo_ctx* ctx, const fe* const* a, uint64_t len, const uint64_t* pts, fe* const* q, size_t count, hipStream_t s) { \
-        return kate_division_batch_t<F>(ctx, a, len, pts, q, count, s); }
+// prefix_product_t over one column (dehalo_prefix_product_device)
+template <class F>
+int prefix_product_one_t(dehalo_ctx* ctx, const fe* in, uint64_t len, fe* out, hipStream_t s) {
+    return prefix_product_t<F>(ctx, in, len, nullptr, 0, len, 1, out, len, s);
+}
+

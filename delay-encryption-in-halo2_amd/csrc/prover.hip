@@ -3,7 +3,7 @@
 // plonk/prover.rs, plonk/{lookup,permutation,vanishing}/prover.rs, poly/kzg/multiopen/gwc/prover.rs] -- the calls the reference makes at
 // benches/delay_enc.rs:41-54 (params), :84-115 (keys), :120-134 (create_proof into a Blake2bWrite transcript).
 //
-// Every C entry point is a function-try-block: an allocation failure on the host (std::bad_alloc) leaves as DEHALO_ERR_OOM, never as an exception.
+// Every C entry point runs its body under dh_guard (guard.hpp): an exception leaves as DEHALO_ERR_OOM (std::bad_alloc) or DEHALO_ERR_INVALID, never as an exception.
 // Host logic only: it orders the phases, hashes the transcript and does O(1) field arithmetic per challenge (hostfield.hpp); every column
 // operation is one of this library's device entry points (include/dehalo.h), called directly.  No CPU path for column work exists.
 #include <atomic>
@@ -117,24 +117,26 @@ struct dehalo_params {
 };
 
 extern "C" int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint8_t* g2, const uint8_t* s_g2,
-                                    dehalo_params** out) try {
-    if (!ctx || !out || !g || !g_lagrange) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_create: null argument");
-    if (k > 28 || curve_scalar_field(curve) < 0) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_create: k or curve out of range");
-    std::unique_ptr<dehalo_params> p(new dehalo_params);
-    p->ctx = ctx; p->curve = curve; p->k = k; p->n = (size_t)1 << k;
-    p->g.assign(g, g + 8 * p->n);
-    p->g_lagrange.assign(g_lagrange, g_lagrange + 8 * p->n);
-    if (g2) memcpy(p->g2, g2, 128);
-    if (s_g2) memcpy(p->s_g2, s_g2, 128);
-    TRY(dehalo_bases_register(ctx, curve, g, p->n, 64, 0, 1, &p->bases_g));
-    const int rc = dehalo_bases_register(ctx, curve, g_lagrange, p->n, 64, 0, 1, &p->bases_gl);
-    if (rc) {
-        (void)dehalo_bases_release(ctx, p->bases_g);
-        return rc;
-    }
-    *out = p.release();
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+                                    dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !out || !g || !g_lagrange) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_create: null argument");
+        if (k > 28 || curve_scalar_field(curve) < 0) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_create: k or curve out of range");
+        std::unique_ptr<dehalo_params> p(new dehalo_params);
+        p->ctx = ctx; p->curve = curve; p->k = k; p->n = (size_t)1 << k;
+        p->g.assign(g, g + 8 * p->n);
+        p->g_lagrange.assign(g_lagrange, g_lagrange + 8 * p->n);
+        if (g2) memcpy(p->g2, g2, 128);
+        if (s_g2) memcpy(p->s_g2, s_g2, 128);
+        TRY(dehalo_bases_register(ctx, curve, g, p->n, 64, 0, 1, &p->bases_g));
+        const int rc = dehalo_bases_register(ctx, curve, g_lagrange, p->n, 64, 0, 1, &p->bases_gl);
+        if (rc) {
+            (void)dehalo_bases_release(ctx, p->bases_g);
+            return rc;
+        }
+        *out = p.release();
+        return 0;
+    });
+}
 
 // ---- ParamsKZG::setup: the two G2 points on the host (O(1): one 254-bit scalar multiplication over Fq2 = Fq[i] / (i^2 + 1)) -------------------
 namespace {
@@ -187,99 +189,109 @@ const uint64_t BN254_G2_GEN[4][4] = {{0x46debd5cd992f6edull, 0x674322d4f75edaddu
                                      {0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull}};
 }   // namespace
 
-extern "C" int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s[4], dehalo_params** out) try {
-    if (!ctx || !out || !s) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: null argument");
-    if (curve != DEHALO_CURVE_BN254_G1) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_setup: ParamsKZG needs a pairing: BN254 only");
-    const HostField* f = host_field(curve_scalar_field(curve));
-    if (k > f->two_adicity) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: k out of range");
-    if (k > 25) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: k > 25: the SRS tables would be too large (include/dehalo.h)");      // (2 x 15 x 2^26 x 64 B = 128 GB at k = 26: fits the index and the card, never exercised)
-    // checked BEFORE the 2^(k+1) fixed-base multiplications: the tables this call registers must fit (BN254: k <= 25, include/dehalo.h)
-    if (!dh_precomputed_table_fits(curve, (size_t)1 << k)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: 2^k x windows >= 2^30: precomputed table too large");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    Fe sm;
-    memcpy(sm.v, s, 32);
-    const size_t n = (size_t)1 << k;
-    // omega = ROOT_OF_UNITY^(2^(S - k));  (s^n - 1) / n
-    Fe omega = f->root_of_unity;
-    for (uint32_t i = k; i < f->two_adicity; i++) omega = f->sqr(omega);
-    Fe sn = sm;
-    for (uint32_t i = 0; i < k; i++) sn = f->sqr(sn);
-    const Fe cfac = f->mul(f->sub(sn, f->one), f->invert(f->from_u64((uint64_t)n)));
-    std::unique_ptr<dehalo_params> p(new dehalo_params);
-    p->ctx = ctx; p->curve = curve; p->k = k; p->n = n;
-    DevMem dg, dgl;
-    TRY(dg.alloc(ctx, 2 * n, false));
-    TRY(dgl.alloc(ctx, 2 * n, false));
-    TRY(kzg_setup_bn254(ctx, k, sm.v, omega.v, cfac.v, (affine_t*)dg.p, (affine_t*)dgl.p, ctx->stream));
-    TRY(dehalo_bases_register_device(ctx, curve, dg.u64(), n, 0, 1, &p->bases_g));
-    int rc = dehalo_bases_register_device(ctx, curve, dgl.u64(), n, 0, 1, &p->bases_gl);
-    if (rc == 0) {
-        p->g.resize(8 * n); p->g_lagrange.resize(8 * n);
-        rc = dehalo_download(ctx, dg.p, 64 * n, p->g.data());
-        if (rc == 0) rc = dehalo_download(ctx, dgl.p, 64 * n, p->g_lagrange.data());
-    }
-    if (rc) {
-        (void)dehalo_bases_release(ctx, p->bases_g);
-        if (p->bases_gl) (void)dehalo_bases_release(ctx, p->bases_gl);
-        return rc;
-    }
-    {   // g2 = the generator, s_g2 = [s] g2
-        const HostField* q = host_field(curve_base_field(curve));
-        G2Host g2(q);
-        G2Host::Pt G;
-        G.inf = false;
-        Fe c[4];
-        for (int i = 0; i < 4; i++) { memcpy(c[i].v, BN254_G2_GEN[i], 32); c[i] = q->from_canonical(c[i]); }
-        G.x = {c[0], c[1]}; G.y = {c[2], c[3]};
-        const Fe sc = f->to_canonical(sm);
-        g2.to_raw(G, p->g2);
-        g2.to_raw(g2.scalar_mul(sc.v, G), p->s_g2);
-    }
-    *out = p.release();
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s[4], dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !out || !s) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: null argument");
+        if (curve != DEHALO_CURVE_BN254_G1) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_setup: ParamsKZG needs a pairing: BN254 only");
+        const HostField* f = host_field(curve_scalar_field(curve));
+        if (k > f->two_adicity) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: k out of range");
+        if (k > 25) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: k > 25: the SRS tables would be too large (include/dehalo.h)");      // (2 x 15 x 2^26 x 64 B = 128 GB at k = 26: fits the index and the card, never exercised)
+        // checked BEFORE the 2^(k+1) fixed-base multiplications: the tables this call registers must fit (BN254: k <= 25, include/dehalo.h)
+        if (!dh_precomputed_table_fits(curve, (size_t)1 << k)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: 2^k x windows >= 2^30: precomputed table too large");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        Fe sm;
+        memcpy(sm.v, s, 32);
+        const size_t n = (size_t)1 << k;
+        // omega = ROOT_OF_UNITY^(2^(S - k));  (s^n - 1) / n
+        Fe omega = f->root_of_unity;
+        for (uint32_t i = k; i < f->two_adicity; i++) omega = f->sqr(omega);
+        Fe sn = sm;
+        for (uint32_t i = 0; i < k; i++) sn = f->sqr(sn);
+        const Fe cfac = f->mul(f->sub(sn, f->one), f->invert(f->from_u64((uint64_t)n)));
+        std::unique_ptr<dehalo_params> p(new dehalo_params);
+        p->ctx = ctx; p->curve = curve; p->k = k; p->n = n;
+        DevMem dg, dgl;
+        TRY(dg.alloc(ctx, 2 * n, false));
+        TRY(dgl.alloc(ctx, 2 * n, false));
+        TRY(kzg_setup_bn254(ctx, k, sm.v, omega.v, cfac.v, (affine_t*)dg.p, (affine_t*)dgl.p, ctx->stream));
+        TRY(dehalo_bases_register_device(ctx, curve, dg.u64(), n, 0, 1, &p->bases_g));
+        int rc = dehalo_bases_register_device(ctx, curve, dgl.u64(), n, 0, 1, &p->bases_gl);
+        if (rc == 0) {
+            p->g.resize(8 * n); p->g_lagrange.resize(8 * n);
+            rc = dehalo_download(ctx, dg.p, 64 * n, p->g.data());
+            if (rc == 0) rc = dehalo_download(ctx, dgl.p, 64 * n, p->g_lagrange.data());
+        }
+        if (rc) {
+            (void)dehalo_bases_release(ctx, p->bases_g);
+            if (p->bases_gl) (void)dehalo_bases_release(ctx, p->bases_gl);
+            return rc;
+        }
+        {   // g2 = the generator, s_g2 = [s] g2
+            const HostField* q = host_field(curve_base_field(curve));
+            G2Host g2(q);
+            G2Host::Pt G;
+            G.inf = false;
+            Fe c[4];
+            for (int i = 0; i < 4; i++) { memcpy(c[i].v, BN254_G2_GEN[i], 32); c[i] = q->from_canonical(c[i]); }
+            G.x = {c[0], c[1]}; G.y = {c[2], c[3]};
+            const Fe sc = f->to_canonical(sm);
+            g2.to_raw(G, p->g2);
+            g2.to_raw(g2.scalar_mul(sc.v, G), p->s_g2);
+        }
+        *out = p.release();
+        return 0;
+    });
+}
 
-extern "C" int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out) try {
-    if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: null argument");
-    if (len < 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: unexpected end of input");
-    const uint32_t k = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);      // u32 LE
-    if (k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: k out of range");
-    const size_t n = (size_t)1 << k;
-    if (len != 4 + 2 * 64 * n + 256) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: length does not match k");
-    // (the points are 8-byte aligned only if the caller's buffer is: copy through aligned vectors)
-    std::vector<uint64_t> g(8 * n), gl(8 * n);
-    memcpy(g.data(), bytes + 4, 64 * n);
-    memcpy(gl.data(), bytes + 4 + 64 * n, 64 * n);
-    return dehalo_params_create(ctx, curve, k, g.data(), gl.data(), bytes + 4 + 128 * n, bytes + 4 + 128 * n + 128, out);
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: null argument");
+        if (len < 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: unexpected end of input");
+        const uint32_t k = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);      // u32 LE
+        if (k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: k out of range");
+        const size_t n = (size_t)1 << k;
+        if (len != 4 + 2 * 64 * n + 256) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: length does not match k");
+        // (the points are 8-byte aligned only if the caller's buffer is: copy through aligned vectors)
+        std::vector<uint64_t> g(8 * n), gl(8 * n);
+        memcpy(g.data(), bytes + 4, 64 * n);
+        memcpy(gl.data(), bytes + 4 + 64 * n, 64 * n);
+        return dehalo_params_create(ctx, curve, k, g.data(), gl.data(), bytes + 4 + 128 * n, bytes + 4 + 128 * n + 128, out);
+    });
+}
 
 extern "C" size_t dehalo_params_size(const dehalo_params* p) { return p ? 4 + 2 * 64 * p->n + 256 : 0; }
 
-extern "C" int dehalo_params_write(const dehalo_params* p, uint8_t* out, size_t cap) try {
-    if (!p || !out) return DEHALO_ERR_INVALID;
-    if (cap < dehalo_params_size(p)) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "params_write: buffer too small");
-    for (int i = 0; i < 4; i++) out[i] = (uint8_t)(p->k >> (8 * i));
-    memcpy(out + 4, p->g.data(), 64 * p->n);
-    memcpy(out + 4 + 64 * p->n, p->g_lagrange.data(), 64 * p->n);
-    memcpy(out + 4 + 128 * p->n, p->g2, 128);
-    memcpy(out + 4 + 128 * p->n + 128, p->s_g2, 128);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_params_write(const dehalo_params* p, uint8_t* out, size_t cap) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !out) return DEHALO_ERR_INVALID;
+        if (cap < dehalo_params_size(p)) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "params_write: buffer too small");
+        for (int i = 0; i < 4; i++) out[i] = (uint8_t)(p->k >> (8 * i));
+        memcpy(out + 4, p->g.data(), 64 * p->n);
+        memcpy(out + 4 + 64 * p->n, p->g_lagrange.data(), 64 * p->n);
+        memcpy(out + 4 + 128 * p->n, p->g2, 128);
+        memcpy(out + 4 + 128 * p->n + 128, p->s_g2, 128);
+        return 0;
+    });
+}
 
-extern "C" int dehalo_params_release(dehalo_ctx* ctx, dehalo_params* p) try {
-    if (!p) return 0;
-    if (p->bases_g) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_g);
-    if (p->bases_gl) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_gl);
-    delete p;
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_params_release(dehalo_ctx* ctx, dehalo_params* p) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!p) return 0;
+        if (p->bases_g) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_g);
+        if (p->bases_gl) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_gl);
+        delete p;
+        return 0;
+    });
+}
 
 extern "C" int dehalo_params_commit_device(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_polys, size_t batch, int lagrange, uint64_t* d_out_affine,
-                                           void* stream) try {
-    if (!ctx || !p) return DEHALO_ERR_INVALID;
-    return dehalo_msm_device_affine(ctx, lagrange ? p->bases_gl : p->bases_g, d_polys, p->n, batch, nullptr, d_out_affine, stream);
-} catch (...) { return DEHALO_ERR_OOM; }
+                                           void* stream) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !p) return DEHALO_ERR_INVALID;
+        return dehalo_msm_device_affine(ctx, lagrange ? p->bases_gl : p->bases_g, d_polys, p->n, batch, nullptr, d_out_affine, stream);
+    });
+}
 
 // ================================================================================================ transcript
 struct dehalo_transcript {
@@ -336,66 +348,82 @@ struct dehalo_transcript {
     }
 };
 
-extern "C" int dehalo_transcript_create(int curve, dehalo_transcript** out) try {
-    if (!out || curve_scalar_field(curve) < 0) return DEHALO_ERR_INVALID;
-    dehalo_transcript* t = new dehalo_transcript;
-    t->init(curve);
-    *out = t;
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
-extern "C" int dehalo_transcript_common_scalar(dehalo_transcript* t, const uint64_t s[4]) try {
-    if (!t || !s) return DEHALO_ERR_INVALID;
-    Fe v;
-    memcpy(v.v, s, 32);
-    t->common_scalar(v);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
-extern "C" int dehalo_transcript_write_scalar(dehalo_transcript* t, const uint64_t s[4]) try {
-    if (!t || !s) return DEHALO_ERR_INVALID;
-    Fe v;
-    memcpy(v.v, s, 32);
-    t->write_scalar(v);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
-extern "C" int dehalo_transcript_write_point(dehalo_transcript* t, const uint64_t xy[8]) try {
-    if (!t || !xy) return DEHALO_ERR_INVALID;
-    return t->write_point(xy) ? 0 : DEHALO_ERR_INVALID;
-} catch (...) { return DEHALO_ERR_OOM; }
-extern "C" int dehalo_transcript_squeeze_challenge(dehalo_transcript* t, uint64_t out[4]) try {
-    if (!t || !out) return DEHALO_ERR_INVALID;
-    const Fe c = t->squeeze();
-    memcpy(out, c.v, 32);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_transcript_create(int curve, dehalo_transcript** out) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!out || curve_scalar_field(curve) < 0) return DEHALO_ERR_INVALID;
+        dehalo_transcript* t = new dehalo_transcript;
+        t->init(curve);
+        *out = t;
+        return 0;
+    });
+}
+extern "C" int dehalo_transcript_common_scalar(dehalo_transcript* t, const uint64_t s[4]) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || !s) return DEHALO_ERR_INVALID;
+        Fe v;
+        memcpy(v.v, s, 32);
+        t->common_scalar(v);
+        return 0;
+    });
+}
+extern "C" int dehalo_transcript_write_scalar(dehalo_transcript* t, const uint64_t s[4]) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || !s) return DEHALO_ERR_INVALID;
+        Fe v;
+        memcpy(v.v, s, 32);
+        t->write_scalar(v);
+        return 0;
+    });
+}
+extern "C" int dehalo_transcript_write_point(dehalo_transcript* t, const uint64_t xy[8]) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || !xy) return DEHALO_ERR_INVALID;
+        return t->write_point(xy) ? 0 : DEHALO_ERR_INVALID;
+    });
+}
+extern "C" int dehalo_transcript_squeeze_challenge(dehalo_transcript* t, uint64_t out[4]) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || !out) return DEHALO_ERR_INVALID;
+        const Fe c = t->squeeze();
+        memcpy(out, c.v, 32);
+        return 0;
+    });
+}
 extern "C" size_t dehalo_transcript_len(const dehalo_transcript* t) { return t ? t->proof.size() : 0; }
-extern "C" int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* out, size_t cap) try {
-    if (!t || (!out && !t->proof.empty())) return DEHALO_ERR_INVALID;
-    if (cap < t->proof.size()) return DEHALO_ERR_INVALID;
-    if (!t->proof.empty()) memcpy(out, t->proof.data(), t->proof.size());
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* out, size_t cap) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || (!out && !t->proof.empty())) return DEHALO_ERR_INVALID;
+        if (cap < t->proof.size()) return DEHALO_ERR_INVALID;
+        if (!t->proof.empty()) memcpy(out, t->proof.data(), t->proof.size());
+        return 0;
+    });
+}
 extern "C" void dehalo_transcript_release(dehalo_transcript* t) { delete t; }
 
-extern "C" int dehalo_field_info(int field, uint64_t out[24]) try {
-    const HostField* f = host_field(field);
-    if (!f || !out) return DEHALO_ERR_INVALID;
-    memcpy(out, f->p, 32);
-    memcpy(out + 4, f->one.v, 32);
-    memcpy(out + 8, f->root_of_unity.v, 32);
-    memcpy(out + 12, f->zeta.v, 32);
-    memcpy(out + 16, f->delta.v, 32);
-    memcpy(out + 20, f->gen.v, 32);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_field_info(int field, uint64_t out[24]) {
+    return dh_guard(nullptr, [&]() -> int {
+        const HostField* f = host_field(field);
+        if (!f || !out) return DEHALO_ERR_INVALID;
+        memcpy(out, f->p, 32);
+        memcpy(out + 4, f->one.v, 32);
+        memcpy(out + 8, f->root_of_unity.v, 32);
+        memcpy(out + 12, f->zeta.v, 32);
+        memcpy(out + 16, f->delta.v, 32);
+        memcpy(out + 20, f->gen.v, 32);
+        return 0;
+    });
+}
 
-extern "C" int dehalo_rng_scalars(dehalo_rng* rng, int field, uint64_t skip, uint64_t* out, size_t count) try {
-    const HostField* f = host_field(field);
-    if (!f || (!out && count)) return DEHALO_ERR_INVALID;
-    HostRng r;
-    TRY(r.init(rng, f));
-    r.skip(skip);
-    return r.scalars(out, count);
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_rng_scalars(dehalo_rng* rng, int field, uint64_t skip, uint64_t* out, size_t count) {
+    return dh_guard(nullptr, [&]() -> int {
+        const HostField* f = host_field(field);
+        if (!f || (!out && count)) return DEHALO_ERR_INVALID;
+        HostRng r;
+        TRY(r.init(rng, f));
+        r.skip(skip);
+        return r.scalars(out, count);
+    });
+}
 
 // ================================================================================================ keys
 struct dehalo_pk {
@@ -515,212 +543,226 @@ int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col) {
 }   // namespace
 
 extern "C" int dehalo_keygen(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_constraint_system* csd, const uint64_t* fixed, const uint64_t* mapping,
-                             const uint8_t* const* selectors, uint32_t num_selectors, uint32_t flags, dehalo_pk** out) try {
-    if (!ctx || !params || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null argument");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
-    TRY(pk_common_init(ctx, params->curve, csd, params->k, pk.get()));
-    const HostCS& cs = pk->cs;
-    const HostDomain& d = pk->dom;
-    const size_t n = d.n, m = d.m, nf = cs.num_fixed, npc = cs.perm_cols.size();
-    if ((nf && !fixed) || (npc && !mapping) || (num_selectors && !selectors)) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null column data");
-    const int fid = pk->f->id;
-    // fixed columns
-    TRY(pk->fixed_values.alloc(ctx, nf * n, false));
-    TRY(pk->fixed_polys.alloc(ctx, nf * n, false));
-    TRY(pk->fixed_cosets.alloc(ctx, nf * m, false));
-    pk->fixed_commitments.assign(8 * nf, 0);
-    if (nf) {
-        HostPin pin_fixed(fixed, nf * n * 32);
-        TRY(dh_h2d(ctx, pk->fixed_values.p, fixed, nf * n * 32, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (flags & DEHALO_KEYGEN_FIXED_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, pk->fixed_values.u64(), nullptr, pk->fixed_values.u64(), nf * n, nullptr));
-        TRY(lagrange_to_all(pk.get(), params, pk->fixed_values.p, nf, pk->fixed_polys.p, pk->fixed_cosets.p, pk->fixed_commitments.data()));
-    }
-    // permutation: sigma_j(omega^i) = delta^(column of the mapped cell) * omega^(its row)  [permutation::keygen::Assembly::build_pk]
-    TRY(pk->perm_values.alloc(ctx, npc * n, false));
-    TRY(pk->perm_polys.alloc(ctx, npc * n, false));
-    TRY(pk->perm_cosets.alloc(ctx, npc * m, false));
-    pk->perm_commitments.assign(8 * npc, 0);
-    if (npc) {
-        for (size_t i = 0; i < npc * n; i++)
-            if (mapping[i] >= npc * n) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: permutation mapping points outside the permutation's columns");
-        DevMem ident, w;
-        uint64_t* d_map = nullptr;
-        TRY(ident.alloc(ctx, npc * n, false));
-        TRY(w.alloc(ctx, n, false));
-        TRY(omega_powers(ctx, d, w.p));
-        Fe dj = pk->f->one;
-        for (size_t j = 0; j < npc; j++) {
-            HIP_TRY(ctx, hipMemcpyAsync(ident.at(j * n), w.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
-            if (j) TRY(dehalo_scale_device(ctx, fid, ident.u64(j * n), n, dj.v, 1, nullptr, nullptr));
-            dj = pk->f->mul(dj, pk->f->delta);
+                             const uint8_t* const* selectors, uint32_t num_selectors, uint32_t flags, dehalo_pk** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !params || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null argument");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
+        TRY(pk_common_init(ctx, params->curve, csd, params->k, pk.get()));
+        const HostCS& cs = pk->cs;
+        const HostDomain& d = pk->dom;
+        const size_t n = d.n, m = d.m, nf = cs.num_fixed, npc = cs.perm_cols.size();
+        if ((nf && !fixed) || (npc && !mapping) || (num_selectors && !selectors)) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null column data");
+        const int fid = pk->f->id;
+        // fixed columns
+        TRY(pk->fixed_values.alloc(ctx, nf * n, false));
+        TRY(pk->fixed_polys.alloc(ctx, nf * n, false));
+        TRY(pk->fixed_cosets.alloc(ctx, nf * m, false));
+        pk->fixed_commitments.assign(8 * nf, 0);
+        if (nf) {
+            HostPin pin_fixed(fixed, nf * n * 32);
+            TRY(dh_h2d(ctx, pk->fixed_values.p, fixed, nf * n * 32, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (flags & DEHALO_KEYGEN_FIXED_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, pk->fixed_values.u64(), nullptr, pk->fixed_values.u64(), nf * n, nullptr));
+            TRY(lagrange_to_all(pk.get(), params, pk->fixed_values.p, nf, pk->fixed_polys.p, pk->fixed_cosets.p, pk->fixed_commitments.data()));
         }
-        HIP_TRY(ctx, hipMalloc((void**)&d_map, npc * n * 8));
-        HostPin pin_map(mapping, npc * n * 8);
-        hipError_t e = dh_h2d(ctx, d_map, mapping, npc * n * 8, ctx->stream) == 0 ? hipSuccess : hipErrorUnknown;
-        if (e == hipSuccess) {
-            k_gather_elems<<<(unsigned)((npc * n + 255) / 256), 256, 0, ctx->stream>>>(ident.p, d_map, pk->perm_values.p, npc * n);
-            e = hipStreamSynchronize(ctx->stream);
+        // permutation: sigma_j(omega^i) = delta^(column of the mapped cell) * omega^(its row)  [permutation::keygen::Assembly::build_pk]
+        TRY(pk->perm_values.alloc(ctx, npc * n, false));
+        TRY(pk->perm_polys.alloc(ctx, npc * n, false));
+        TRY(pk->perm_cosets.alloc(ctx, npc * m, false));
+        pk->perm_commitments.assign(8 * npc, 0);
+        if (npc) {
+            for (size_t i = 0; i < npc * n; i++)
+                if (mapping[i] >= npc * n) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: permutation mapping points outside the permutation's columns");
+            DevMem ident, w;
+            uint64_t* d_map = nullptr;
+            TRY(ident.alloc(ctx, npc * n, false));
+            TRY(w.alloc(ctx, n, false));
+            TRY(omega_powers(ctx, d, w.p));
+            Fe dj = pk->f->one;
+            for (size_t j = 0; j < npc; j++) {
+                HIP_TRY(ctx, hipMemcpyAsync(ident.at(j * n), w.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
+                if (j) TRY(dehalo_scale_device(ctx, fid, ident.u64(j * n), n, dj.v, 1, nullptr, nullptr));
+                dj = pk->f->mul(dj, pk->f->delta);
+            }
+            HIP_TRY(ctx, hipMalloc((void**)&d_map, npc * n * 8));
+            HostPin pin_map(mapping, npc * n * 8);
+            hipError_t e = dh_h2d(ctx, d_map, mapping, npc * n * 8, ctx->stream) == 0 ? hipSuccess : hipErrorUnknown;
+            if (e == hipSuccess) {
+                k_gather_elems<<<(unsigned)((npc * n + 255) / 256), 256, 0, ctx->stream>>>(ident.p, d_map, pk->perm_values.p, npc * n);
+                e = hipStreamSynchronize(ctx->stream);
+            }
+            (void)hipFree(d_map);
+            HIP_TRY(ctx, e);
+            TRY(lagrange_to_all(pk.get(), params, pk->perm_values.p, npc, pk->perm_polys.p, pk->perm_cosets.p, pk->perm_commitments.data()));
         }
-        (void)hipFree(d_map);
-        HIP_TRY(ctx, e);
-        TRY(lagrange_to_all(pk.get(), params, pk->perm_values.p, npc, pk->perm_polys.p, pk->perm_cosets.p, pk->perm_commitments.data()));
-    }
-    // l0, l_last, l_active_row = 1 - (l_last + l_blind) over the extended domain
-    {
-        const size_t u = n - (cs.blinding_factors() + 1);
-        std::vector<Fe> lag(3 * n, Fe{{0, 0, 0, 0}});
-        lag[0] = pk->f->one;
-        lag[n + u] = pk->f->one;
-        for (size_t i = 0; i < u; i++) lag[2 * n + i] = pk->f->one;
-        DevMem vals, polys;
-        TRY(vals.alloc(ctx, 3 * n, false));
-        TRY(polys.alloc(ctx, 3 * n, false));
-        TRY(pk->l_ext.alloc(ctx, 3 * m, false));
-        HostPin pin_lag(lag.data(), 3 * n * 32);
-        TRY(dh_h2d(ctx, vals.p, lag.data(), 3 * n * 32, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        TRY(lagrange_to_all(pk.get(), params, vals.p, 3, polys.p, pk->l_ext.p, nullptr));
-    }
-    pk->num_selectors = num_selectors;
-    for (uint32_t s = 0; s < num_selectors; s++) {
-        if (!selectors[s]) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null selector");
-        std::vector<uint8_t> packed((n + 7) / 8, 0);
-        for (size_t i = 0; i < n; i++)
-            if (selectors[s][i]) packed[i >> 3] |= (uint8_t)(1u << (i & 7));
-        pk->selectors.push_back(std::move(packed));
-    }
-    pk->default_transcript_repr();
-    TRY(pk->compile_graphs());
-    TRY(dehalo_ctx_synchronize(ctx));
-    *out = pk.release();
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+        // l0, l_last, l_active_row = 1 - (l_last + l_blind) over the extended domain
+        {
+            const size_t u = n - (cs.blinding_factors() + 1);
+            std::vector<Fe> lag(3 * n, Fe{{0, 0, 0, 0}});
+            lag[0] = pk->f->one;
+            lag[n + u] = pk->f->one;
+            for (size_t i = 0; i < u; i++) lag[2 * n + i] = pk->f->one;
+            DevMem vals, polys;
+            TRY(vals.alloc(ctx, 3 * n, false));
+            TRY(polys.alloc(ctx, 3 * n, false));
+            TRY(pk->l_ext.alloc(ctx, 3 * m, false));
+            HostPin pin_lag(lag.data(), 3 * n * 32);
+            TRY(dh_h2d(ctx, vals.p, lag.data(), 3 * n * 32, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            TRY(lagrange_to_all(pk.get(), params, vals.p, 3, polys.p, pk->l_ext.p, nullptr));
+        }
+        pk->num_selectors = num_selectors;
+        for (uint32_t s = 0; s < num_selectors; s++) {
+            if (!selectors[s]) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null selector");
+            std::vector<uint8_t> packed((n + 7) / 8, 0);
+            for (size_t i = 0; i < n; i++)
+                if (selectors[s][i]) packed[i >> 3] |= (uint8_t)(1u << (i & 7));
+            pk->selectors.push_back(std::move(packed));
+        }
+        pk->default_transcript_repr();
+        TRY(pk->compile_graphs());
+        TRY(dehalo_ctx_synchronize(ctx));
+        *out = pk.release();
+        return 0;
+    });
+}
 
 extern "C" size_t dehalo_pk_size(const dehalo_pk* pk) { return pk ? pk->size() : 0; }
 extern "C" size_t dehalo_vk_size(const dehalo_pk* pk) { return pk ? pk->vk_size() : 0; }
-extern "C" int dehalo_vk_write(const dehalo_pk* pk, uint8_t* out, size_t cap) try {
-    if (!pk || !out) return DEHALO_ERR_INVALID;
-    if (cap < pk->vk_size()) return dh_fail(pk->ctx, DEHALO_ERR_INVALID, "vk_write: buffer too small");
-    pk->vk_write(out);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_vk_write(const dehalo_pk* pk, uint8_t* out, size_t cap) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        if (cap < pk->vk_size()) return dh_fail(pk->ctx, DEHALO_ERR_INVALID, "vk_write: buffer too small");
+        pk->vk_write(out);
+        return 0;
+    });
+}
 
-extern "C" int dehalo_pk_write(dehalo_ctx* ctx, const dehalo_pk* pk, uint8_t* out, size_t cap) try {
-    if (!pk || !out) return DEHALO_ERR_INVALID;
-    if (!ctx) ctx = pk->ctx;
-    if (cap < pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_write: buffer too small");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
-    pk->vk_write(out);
-    uint8_t* o = out + pk->vk_size();
-    DevMem tmp;      // extended-domain columns leave in upstream's standard form
-    TRY(tmp.alloc(ctx, m, false));
-    auto poly = [&](const fe* src, size_t len, bool internal) -> int {
-        put_u32_be(o, (uint32_t)len);
-        o += 4;
-        if (internal) {
-            TRY(dehalo_convert_form_device(ctx, pk->f->id, (const uint64_t*)src, tmp.u64(), len, 0, nullptr));
-            src = tmp.p;
+extern "C" int dehalo_pk_write(dehalo_ctx* ctx, const dehalo_pk* pk, uint8_t* out, size_t cap) {
+    return dh_guard(ctx ? ctx : pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        if (!ctx) ctx = pk->ctx;
+        if (cap < pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_write: buffer too small");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
+        pk->vk_write(out);
+        uint8_t* o = out + pk->vk_size();
+        DevMem tmp;      // extended-domain columns leave in upstream's standard form
+        TRY(tmp.alloc(ctx, m, false));
+        auto poly = [&](const fe* src, size_t len, bool internal) -> int {
+            put_u32_be(o, (uint32_t)len);
+            o += 4;
+            if (internal) {
+                TRY(dehalo_convert_form_device(ctx, pk->f->id, (const uint64_t*)src, tmp.u64(), len, 0, nullptr));
+                src = tmp.p;
+            }
+            TRY(dehalo_download(ctx, src, len * 32, o));
+            o += len * 32;
+            return 0;
+        };
+        auto slice = [&](const DevMem& mem, size_t cnt, size_t len, bool internal) -> int {
+            put_u32_be(o, (uint32_t)cnt);
+            o += 4;
+            for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * len), len, internal));
+            return 0;
+        };
+        for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
+        TRY(slice(pk->fixed_values, nf, n, false));
+        TRY(slice(pk->fixed_polys, nf, n, false));
+        TRY(slice(pk->fixed_cosets, nf, m, true));
+        TRY(slice(pk->perm_values, npc, n, false));
+        TRY(slice(pk->perm_polys, npc, n, false));
+        TRY(slice(pk->perm_cosets, npc, m, true));
+        return 0;
+    });
+}
+
+extern "C" int dehalo_pk_read(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* csd, const uint8_t* bytes, size_t len, uint32_t num_selectors, dehalo_pk** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: null argument");
+        if (len < 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: unexpected end of input");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const uint32_t k = get_u32_be(bytes), nf_file = get_u32_be(bytes + 4);
+        std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
+        TRY(pk_common_init(ctx, curve, csd, k, pk.get()));
+        const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
+        if (nf_file != nf) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: the key's number of fixed commitments differs from the circuit's fixed columns");
+        pk->num_selectors = num_selectors;
+        if (len != pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: length does not match the circuit (unexpected end of input or trailing bytes)");
+        HostPin pin_blob(bytes, len);      // every polynomial below is copied straight out of the caller's blob
+        const uint8_t* p = bytes + 8;
+        pk->fixed_commitments.resize(8 * nf);
+        memcpy(pk->fixed_commitments.data(), p, 64 * nf);
+        p += 64 * nf;
+        pk->perm_commitments.resize(8 * npc);
+        memcpy(pk->perm_commitments.data(), p, 64 * npc);
+        p += 64 * npc;
+        for (uint32_t s = 0; s < num_selectors; s++) {
+            pk->selectors.emplace_back(p, p + (n + 7) / 8);
+            p += (n + 7) / 8;
         }
-        TRY(dehalo_download(ctx, src, len * 32, o));
-        o += len * 32;
+        const int fid = pk->f->id;
+        auto poly = [&](fe* dst, size_t want, bool to_internal) -> int {
+            if (get_u32_be(p) != want) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial length differs from the domain's");
+            p += 4;
+            TRY(dh_h2d(ctx, dst, p, want * 32, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            p += want * 32;
+            if (to_internal) TRY(dehalo_convert_form_device(ctx, fid, (const uint64_t*)dst, (uint64_t*)dst, want, 1, nullptr));
+            return 0;
+        };
+        auto slice = [&](DevMem& mem, size_t cnt, size_t ln, bool to_internal) -> int {
+            if (get_u32_be(p) != cnt) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial count differs from the circuit's");
+            p += 4;
+            TRY(mem.alloc(ctx, cnt * ln, false));
+            for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * ln), ln, to_internal));
+            return 0;
+        };
+        TRY(pk->l_ext.alloc(ctx, 3 * m, false));
+        for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
+        TRY(slice(pk->fixed_values, nf, n, false));
+        TRY(slice(pk->fixed_polys, nf, n, false));
+        TRY(slice(pk->fixed_cosets, nf, m, true));
+        TRY(slice(pk->perm_values, npc, n, false));
+        TRY(slice(pk->perm_polys, npc, n, false));
+        TRY(slice(pk->perm_cosets, npc, m, true));
+        pk->default_transcript_repr();
+        TRY(pk->compile_graphs());
+        TRY(dehalo_ctx_synchronize(ctx));
+        *out = pk.release();
         return 0;
-    };
-    auto slice = [&](const DevMem& mem, size_t cnt, size_t len, bool internal) -> int {
-        put_u32_be(o, (uint32_t)cnt);
-        o += 4;
-        for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * len), len, internal));
-        return 0;
-    };
-    for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
-    TRY(slice(pk->fixed_values, nf, n, false));
-    TRY(slice(pk->fixed_polys, nf, n, false));
-    TRY(slice(pk->fixed_cosets, nf, m, true));
-    TRY(slice(pk->perm_values, npc, n, false));
-    TRY(slice(pk->perm_polys, npc, n, false));
-    TRY(slice(pk->perm_cosets, npc, m, true));
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+    });
+}
 
-extern "C" int dehalo_pk_read(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* csd, const uint8_t* bytes, size_t len, uint32_t num_selectors, dehalo_pk** out) try {
-    if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: null argument");
-    if (len < 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: unexpected end of input");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    const uint32_t k = get_u32_be(bytes), nf_file = get_u32_be(bytes + 4);
-    std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
-    TRY(pk_common_init(ctx, curve, csd, k, pk.get()));
-    const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
-    if (nf_file != nf) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: the key's number of fixed commitments differs from the circuit's fixed columns");
-    pk->num_selectors = num_selectors;
-    if (len != pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: length does not match the circuit (unexpected end of input or trailing bytes)");
-    HostPin pin_blob(bytes, len);      // every polynomial below is copied straight out of the caller's blob
-    const uint8_t* p = bytes + 8;
-    pk->fixed_commitments.resize(8 * nf);
-    memcpy(pk->fixed_commitments.data(), p, 64 * nf);
-    p += 64 * nf;
-    pk->perm_commitments.resize(8 * npc);
-    memcpy(pk->perm_commitments.data(), p, 64 * npc);
-    p += 64 * npc;
-    for (uint32_t s = 0; s < num_selectors; s++) {
-        pk->selectors.emplace_back(p, p + (n + 7) / 8);
-        p += (n + 7) / 8;
-    }
-    const int fid = pk->f->id;
-    auto poly = [&](fe* dst, size_t want, bool to_internal) -> int {
-        if (get_u32_be(p) != want) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial length differs from the domain's");
-        p += 4;
-        TRY(dh_h2d(ctx, dst, p, want * 32, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        p += want * 32;
-        if (to_internal) TRY(dehalo_convert_form_device(ctx, fid, (const uint64_t*)dst, (uint64_t*)dst, want, 1, nullptr));
+extern "C" int dehalo_pk_set_transcript_repr(dehalo_pk* pk, const uint64_t repr[4]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !repr) return DEHALO_ERR_INVALID;
+        memcpy(pk->transcript_repr.v, repr, 32);
         return 0;
-    };
-    auto slice = [&](DevMem& mem, size_t cnt, size_t ln, bool to_internal) -> int {
-        if (get_u32_be(p) != cnt) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial count differs from the circuit's");
-        p += 4;
-        TRY(mem.alloc(ctx, cnt * ln, false));
-        for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * ln), ln, to_internal));
+    });
+}
+extern "C" int dehalo_pk_get_transcript_repr(const dehalo_pk* pk, uint64_t repr[4]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !repr) return DEHALO_ERR_INVALID;
+        memcpy(repr, pk->transcript_repr.v, 32);
         return 0;
-    };
-    TRY(pk->l_ext.alloc(ctx, 3 * m, false));
-    for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
-    TRY(slice(pk->fixed_values, nf, n, false));
-    TRY(slice(pk->fixed_polys, nf, n, false));
-    TRY(slice(pk->fixed_cosets, nf, m, true));
-    TRY(slice(pk->perm_values, npc, n, false));
-    TRY(slice(pk->perm_polys, npc, n, false));
-    TRY(slice(pk->perm_cosets, npc, m, true));
-    pk->default_transcript_repr();
-    TRY(pk->compile_graphs());
-    TRY(dehalo_ctx_synchronize(ctx));
-    *out = pk.release();
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
-
-extern "C" int dehalo_pk_set_transcript_repr(dehalo_pk* pk, const uint64_t repr[4]) try {
-    if (!pk || !repr) return DEHALO_ERR_INVALID;
-    memcpy(pk->transcript_repr.v, repr, 32);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
-extern "C" int dehalo_pk_get_transcript_repr(const dehalo_pk* pk, uint64_t repr[4]) try {
-    if (!pk || !repr) return DEHALO_ERR_INVALID;
-    memcpy(repr, pk->transcript_repr.v, 32);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
-extern "C" int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk) try {
-    if (!pk) return 0;
-    dehalo_ctx* c = ctx ? ctx : pk->ctx;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    delete pk;
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+    });
+}
+extern "C" int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk) {
+    return dh_guard(ctx ? ctx : pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk) return 0;
+        dehalo_ctx* c = ctx ? ctx : pk->ctx;
+        std::lock_guard<std::recursive_mutex> lk(c->mu);
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        delete pk;
+        return 0;
+    });
+}
 
 // ================================================================================================ create_proof
 struct dehalo_prover {
@@ -1605,84 +1647,98 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     return 0;
 }
 
-extern "C" int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out) try {
-    if (!ctx || !params || !pk || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: null argument");
-    if (params->k != pk->k || params->curve != pk->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: params and proving key disagree on k / curve");
-    if (side_ctx && (side_ctx == ctx || side_ctx->device != ctx->device)) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: the side context must be another context of the same device");
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    std::unique_ptr<dehalo_prover> p(new dehalo_prover);
-    TRY(p->init(ctx, side_ctx, params, pk));
-    *out = p.release();
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !params || !pk || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: null argument");
+        if (params->k != pk->k || params->curve != pk->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: params and proving key disagree on k / curve");
+        if (side_ctx && (side_ctx == ctx || side_ctx->device != ctx->device)) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: the side context must be another context of the same device");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        std::unique_ptr<dehalo_prover> p(new dehalo_prover);
+        TRY(p->init(ctx, side_ctx, params, pk));
+        *out = p.release();
+        return 0;
+    });
+}
 
-extern "C" int dehalo_prover_release(dehalo_prover* p) try {
-    if (!p) return 0;
-    (void)hipSetDevice(p->ctx->device);
-    (void)hipStreamSynchronize(p->ctx->stream);
-    if (p->side) (void)hipStreamSynchronize(p->side->stream);
-    delete p;
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_prover_release(dehalo_prover* p) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p) return 0;
+        (void)hipSetDevice(p->ctx->device);
+        (void)hipStreamSynchronize(p->ctx->stream);
+        if (p->side) (void)hipStreamSynchronize(p->side->stream);
+        delete p;
+        return 0;
+    });
+}
 
 extern "C" int dehalo_create_proof(dehalo_prover* p, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
-                                   dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags) try {
-    if (!p || !transcript) return DEHALO_ERR_INVALID;
-    if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
-    std::lock_guard<std::mutex> lk(p->mu);
-    const int rc = p->run(advice, instances, instance_lens, num_instance_columns, rng, transcript, flags);
-    if (rc) {      // leave nothing of this proof in flight on either context
-        (void)hipStreamSynchronize(p->ctx->stream);
-        if (p->side) (void)hipStreamSynchronize(p->side->stream);
-    }
-    return rc;
-} catch (...) { return DEHALO_ERR_OOM; }
+                                   dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !transcript) return DEHALO_ERR_INVALID;
+        if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
+        std::lock_guard<std::mutex> lk(p->mu);
+        const int rc = p->run(advice, instances, instance_lens, num_instance_columns, rng, transcript, flags);
+        if (rc) {      // leave nothing of this proof in flight on either context
+            (void)hipStreamSynchronize(p->ctx->stream);
+            if (p->side) (void)hipStreamSynchronize(p->side->stream);
+        }
+        return rc;
+    });
+}
 
-extern "C" int dehalo_prover_set_shard(dehalo_prover* p, uint32_t rank, uint32_t world, dehalo_gather_fn gather, void* user) try {
-    if (!p || world == 0 || rank >= world || (world > 1 && !gather)) return DEHALO_ERR_INVALID;
-    p->shard_rank = rank; p->shard_world = world; p->shard_gather = world > 1 ? gather : nullptr; p->shard_user = user;
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_prover_set_shard(dehalo_prover* p, uint32_t rank, uint32_t world, dehalo_gather_fn gather, void* user) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || world == 0 || rank >= world || (world > 1 && !gather)) return DEHALO_ERR_INVALID;
+        p->shard_rank = rank; p->shard_world = world; p->shard_gather = world > 1 ? gather : nullptr; p->shard_user = user;
+        return 0;
+    });
+}
 
-extern "C" int dehalo_prover_last_timings(const dehalo_prover* p, double out[8]) try {
-    if (!p || !out) return DEHALO_ERR_INVALID;
-    memcpy(out, p->timings, sizeof p->timings);
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_prover_last_timings(const dehalo_prover* p, double out[8]) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !out) return DEHALO_ERR_INVALID;
+        memcpy(out, p->timings, sizeof p->timings);
+        return 0;
+    });
+}
 
-extern "C" int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]) try {
-    if (!pk || !out) return DEHALO_ERR_INVALID;
-    const HostCS& cs = pk->cs;
-    const uint32_t L = (uint32_t)cs.lookups.size(), S = cs.num_sets();
-    out[0] = pk->k;
-    out[1] = pk->dom.extended_k;
-    out[2] = cs.blinding_factors();
-    out[3] = cs.degree();
-    out[4] = S;
-    out[5] = cs.num_advice + 2 * L + S + L + 1 + (cs.degree() - 1);
-    out[6] = (uint32_t)(cs.advice_q.size() + cs.fixed_q.size() + 1 + cs.perm_cols.size() + (S ? 3 * S - 1 : 0) + 5 * L);
-    std::vector<int32_t> rs = {0, 1, -(int32_t)(cs.blinding_factors() + 1)};
-    if (L) rs.push_back(-1);
-    for (auto& q : cs.advice_q) rs.push_back(q.rotation);
-    for (auto& q : cs.fixed_q) rs.push_back(q.rotation);
-    std::sort(rs.begin(), rs.end());
-    out[7] = (uint32_t)(std::unique(rs.begin(), rs.end()) - rs.begin());
-    return 0;
-} catch (...) { return DEHALO_ERR_OOM; }
+extern "C" int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        const HostCS& cs = pk->cs;
+        const uint32_t L = (uint32_t)cs.lookups.size(), S = cs.num_sets();
+        out[0] = pk->k;
+        out[1] = pk->dom.extended_k;
+        out[2] = cs.blinding_factors();
+        out[3] = cs.degree();
+        out[4] = S;
+        out[5] = cs.num_advice + 2 * L + S + L + 1 + (cs.degree() - 1);
+        out[6] = (uint32_t)(cs.advice_q.size() + cs.fixed_q.size() + 1 + cs.perm_cols.size() + (S ? 3 * S - 1 : 0) + 5 * L);
+        std::vector<int32_t> rs = {0, 1, -(int32_t)(cs.blinding_factors() + 1)};
+        if (L) rs.push_back(-1);
+        for (auto& q : cs.advice_q) rs.push_back(q.rotation);
+        for (auto& q : cs.fixed_q) rs.push_back(q.rotation);
+        std::sort(rs.begin(), rs.end());
+        out[7] = (uint32_t)(std::unique(rs.begin(), rs.end()) - rs.begin());
+        return 0;
+    });
+}
 
 extern "C" int dehalo_create_proof_circuit(dehalo_prover* p, const dehalo_circuit_inputs* in, dehalo_synthesis_info* info, const uint64_t* const* instances,
-                                           const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng, dehalo_transcript* transcript) try {
-    if (!p || !transcript || !in) return DEHALO_ERR_INVALID;
-    if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
-    std::lock_guard<std::mutex> lk(p->mu);
-    const int rc = p->run(nullptr, instances, instance_lens, num_instance_columns, rng, transcript, 0, in, info);
-    if (rc) {
-        (void)hipStreamSynchronize(p->ctx->stream);
-        if (p->side) (void)hipStreamSynchronize(p->side->stream);
-    }
-    return rc;
-} catch (...) { return DEHALO_ERR_OOM; }
+                                           const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng, dehalo_transcript* transcript) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !transcript || !in) return DEHALO_ERR_INVALID;
+        if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
+        std::lock_guard<std::mutex> lk(p->mu);
+        const int rc = p->run(nullptr, instances, instance_lens, num_instance_columns, rng, transcript, 0, in, info);
+        if (rc) {
+            (void)hipStreamSynchronize(p->ctx->stream);
+            if (p->side) (void)hipStreamSynchronize(p->side->stream);
+        }
+        return rc;
+    });
+}
 
 namespace {
 // proof i on prover i mod num_provers, one library thread per prover; `one` makes proof i on prover p into `tr`
@@ -1716,18 +1772,22 @@ int proofs_on_threads(dehalo_prover* const* provers, uint32_t num_provers, uint3
 }   // namespace
 
 extern "C" int dehalo_create_proofs(dehalo_prover* const* provers, uint32_t num_provers, const uint64_t* const* advice, uint32_t count, dehalo_rng* rngs, uint32_t flags,
-                                    uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens) try {
-    if (!provers || !num_provers || (count && (!advice || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
-    return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
-        return dehalo_create_proof(p, advice[i], nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr, flags);
+                                    uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!provers || !num_provers || (count && (!advice || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
+        return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
+            return dehalo_create_proof(p, advice[i], nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr, flags);
+        });
     });
-} catch (...) { return DEHALO_ERR_OOM; }
+}
 
 // the same with every proof's circuit synthesized inside its call (dehalo_create_proof_circuit): inputs[i] -> proof i
 extern "C" int dehalo_create_proofs_circuit(dehalo_prover* const* provers, uint32_t num_provers, const dehalo_circuit_inputs* inputs, uint32_t count, dehalo_rng* rngs,
-                                            uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens) try {
-    if (!provers || !num_provers || (count && (!inputs || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
-    return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
-        return dehalo_create_proof_circuit(p, &inputs[i], nullptr, nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr);
+                                            uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!provers || !num_provers || (count && (!inputs || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
+        return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
+            return dehalo_create_proof_circuit(p, &inputs[i], nullptr, nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr);
+        });
     });
-} catch (...) { return DEHALO_ERR_OOM; }
+}

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/dehalo.h"
+#include "guard.hpp"
 #include "hostfield.hpp"
 
 namespace {
@@ -1223,113 +1224,115 @@ Fe fe_from(const uint64_t* p) {
 }   // namespace
 
 extern "C" int dehalo_synthesize(const dehalo_circuit_inputs* in, uint64_t* advice, uint64_t* fixed, uint64_t* mapping, uint8_t* const* selectors,
-                                 dehalo_synthesis_info* info) try {
-    if (!in || (!advice && !fixed && !mapping && !info)) return DEHALO_ERR_INVALID;
-    const HostField* f = host_field(DEHALO_FIELD_BN254_FR);
-    const bool keygen_outputs = fixed || mapping || selectors;
-    const bool range_lookups = in->circuit != DEHALO_CIRCUIT_POSE_ENC;
-    if (in->circuit > DEHALO_CIRCUIT_POSE_ENC || in->k < 4 || in->k > 24) return DEHALO_ERR_INVALID;
-    const uint32_t t = in->t ? in->t : 5, rate = in->rate ? in->rate : 4, r_f = in->r_f ? in->r_f : 8, r_p = in->r_p ? in->r_p : 57;
-    if (t != 5 || rate != 4) return DEHALO_ERR_UNSUPPORTED;      // the row layout (linear()) is the T = 5 one the reference instantiates (src/lib.rs:120-121)
-    if (in->message_len > 2 || (in->message_len && !in->message)) return DEHALO_ERR_INVALID;
-    const size_t n = (size_t)1 << in->k;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto trace = [&](const char* what) {
-        if (getenv("DEHALO_SYNTH_TRACE")) fprintf(stderr, "synthesize: %-28s +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    };
-    Layouter lay(f, keygen_outputs, advice, n);
-    std::vector<Fe> message;
-    for (uint32_t i = 0; i < in->message_len; i++) {
-        Fe m = fe_from(in->message + 4 * i);
-        if (HostField::geq(m.v, f->p)) return DEHALO_ERR_INVALID;
-        message.push_back(m);
-    }
-    dehalo_synthesis_info inf{};
-    std::vector<Fe> cipher_vals;
-    if (in->circuit == DEHALO_CIRCUIT_POSE_ENC) {
-        if (!in->key) return DEHALO_ERR_INVALID;
-        const std::shared_ptr<const PoseidonSpec> spec_ref = poseidon_spec(f, t, r_f, r_p);
-        const PoseidonSpec& spec = *spec_ref;
-        const Fe key[2] = {fe_from(in->key), fe_from(in->key + 4)};
-        for (auto& c : cipher_region(lay, spec, key, message, nullptr, rate)) cipher_vals.push_back(c.val);
-    } else {
-        if (!in->n || !in->x || in->bits_len % LIMB_WIDTH || in->bits_len == 0 || in->bits_len > 8192 || in->exp_bits == 0 || in->exp_bits > 64) return DEHALO_ERR_INVALID;
-        const size_t num_limbs = in->bits_len / LIMB_WIDTH;
-        lay.range = RangeLens(num_limbs);
-        Big n_big(in->n, in->n + num_limbs), x(in->x, in->x + num_limbs);
-        { Big t0 = n_big; big_trim(t0); if (t0.empty()) return DEHALO_ERR_INVALID; }
-        if (in->exp_bits < 64 && (in->e >> in->exp_bits)) return DEHALO_ERR_INVALID;
-        // hash region, then the cipher keyed by the digest's words 1 and 2 (src/lib.rs:216-316)
-        auto hash_and_cipher = [&](Layouter& L, const std::vector<Cell>& rsa_out) {
+                                 dehalo_synthesis_info* info) {
+    // (a constraint of the reference's circuit that does not hold for these inputs -- x >= n, an exponent wider than exp_bits, a non-zero message --
+    // throws NotSatisfied: DEHALO_ERR_INVALID, as any exception other than std::bad_alloc)
+    return dh_guard(nullptr, [&]() -> int {
+        if (!in || (!advice && !fixed && !mapping && !info)) return DEHALO_ERR_INVALID;
+        const HostField* f = host_field(DEHALO_FIELD_BN254_FR);
+        const bool keygen_outputs = fixed || mapping || selectors;
+        const bool range_lookups = in->circuit != DEHALO_CIRCUIT_POSE_ENC;
+        if (in->circuit > DEHALO_CIRCUIT_POSE_ENC || in->k < 4 || in->k > 24) return DEHALO_ERR_INVALID;
+        const uint32_t t = in->t ? in->t : 5, rate = in->rate ? in->rate : 4, r_f = in->r_f ? in->r_f : 8, r_p = in->r_p ? in->r_p : 57;
+        if (t != 5 || rate != 4) return DEHALO_ERR_UNSUPPORTED;      // the row layout (linear()) is the T = 5 one the reference instantiates (src/lib.rs:120-121)
+        if (in->message_len > 2 || (in->message_len && !in->message)) return DEHALO_ERR_INVALID;
+        const size_t n = (size_t)1 << in->k;
+        const auto t_begin = std::chrono::steady_clock::now();
+        auto trace = [&](const char* what) {
+            if (getenv("DEHALO_SYNTH_TRACE")) fprintf(stderr, "synthesize: %-28s +%.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+        };
+        Layouter lay(f, keygen_outputs, advice, n);
+        std::vector<Fe> message;
+        for (uint32_t i = 0; i < in->message_len; i++) {
+            Fe m = fe_from(in->message + 4 * i);
+            if (HostField::geq(m.v, f->p)) return DEHALO_ERR_INVALID;
+            message.push_back(m);
+        }
+        dehalo_synthesis_info inf{};
+        std::vector<Fe> cipher_vals;
+        if (in->circuit == DEHALO_CIRCUIT_POSE_ENC) {
+            if (!in->key) return DEHALO_ERR_INVALID;
             const std::shared_ptr<const PoseidonSpec> spec_ref = poseidon_spec(f, t, r_f, r_p);
             const PoseidonSpec& spec = *spec_ref;
-            Cell key_cells[2];
-            hash_region(L, spec, rsa_out, rate, key_cells);
-            const Fe key_vals[2] = {key_cells[0].val, key_cells[1].val};
-            for (auto& c : cipher_region(L, spec, key_vals, message, key_cells, rate)) cipher_vals.push_back(c.val);
-        };
-        const bool with_hash = in->circuit == DEHALO_CIRCUIT_DELAY_ENC;
-        uint32_t rsa_rows_beside = 0;
-        if (!keygen_outputs)      // proving: everything behind the exponentiation may be written beside it (BigIntChip::pow_mod_threads)
-            lay.after_pow = [&](Layouter& sub, const std::vector<Cell>& powed) {
-                const std::vector<Cell> valid = rsa_expected_rows(sub, powed);
-                rsa_rows_beside = sub.rows();
-                if (with_hash) hash_and_cipher(sub, valid);
+            const Fe key[2] = {fe_from(in->key), fe_from(in->key + 4)};
+            for (auto& c : cipher_region(lay, spec, key, message, nullptr, rate)) cipher_vals.push_back(c.val);
+        } else {
+            if (!in->n || !in->x || in->bits_len % LIMB_WIDTH || in->bits_len == 0 || in->bits_len > 8192 || in->exp_bits == 0 || in->exp_bits > 64) return DEHALO_ERR_INVALID;
+            const size_t num_limbs = in->bits_len / LIMB_WIDTH;
+            lay.range = RangeLens(num_limbs);
+            Big n_big(in->n, in->n + num_limbs), x(in->x, in->x + num_limbs);
+            { Big t0 = n_big; big_trim(t0); if (t0.empty()) return DEHALO_ERR_INVALID; }
+            if (in->exp_bits < 64 && (in->e >> in->exp_bits)) return DEHALO_ERR_INVALID;
+            // hash region, then the cipher keyed by the digest's words 1 and 2 (src/lib.rs:216-316)
+            auto hash_and_cipher = [&](Layouter& L, const std::vector<Cell>& rsa_out) {
+                const std::shared_ptr<const PoseidonSpec> spec_ref = poseidon_spec(f, t, r_f, r_p);
+                const PoseidonSpec& spec = *spec_ref;
+                Cell key_cells[2];
+                hash_region(L, spec, rsa_out, rate, key_cells);
+                const Fe key_vals[2] = {key_cells[0].val, key_cells[1].val};
+                for (auto& c : cipher_region(L, spec, key_vals, message, key_cells, rate)) cipher_vals.push_back(c.val);
             };
-        Big want;
-        const std::vector<Cell> rsa_out = rsa_region(lay, n_big, in->e, x, in->exp_bits, num_limbs, want);
-        inf.rsa_rows = lay.after_pow_done ? rsa_rows_beside : lay.rows();
-        trace(lay.after_pow_done ? "rsa, hash and cipher regions" : "rsa region");
-        const Big wl = big_limbs(want, std::min<size_t>(num_limbs, 128));
-        for (size_t i = 0; i < wl.size() && i < 128; i++) inf.rsa_result[i] = wl[i];
-        if (with_hash && !lay.after_pow_done) hash_and_cipher(lay, rsa_out);
-    }
-    trace("hash and cipher regions");
-    inf.total_rows = lay.rows();
-    if (in->circuit == DEHALO_CIRCUIT_POSE_ENC) inf.rsa_rows = 0;
-    for (size_t i = 0; i < cipher_vals.size() && i < 3; i++) memcpy(inf.cipher + 4 * i, cipher_vals[i].v, 32);
-    inf.cipher_len = (uint32_t)std::min<size_t>(cipher_vals.size(), 3);
-    if (info) *info = inf;
-    // ---- into 2^k-row columns
-    const uint32_t bf = 5;      // blinding_factors of both constraint systems: max(3, 2 queries of advice column e) + 2
-    const size_t u = n - (bf + 1);
-    if ((size_t)lay.rows() + 1 > u) return DEHALO_ERR_INVALID;      // "not enough rows available" (upstream: Error::NotEnoughRowsAvailable)
-    const size_t rows = lay.rows();
-    if (advice)      // (the used rows are already in place)
-        for (int c = 0; c < 5; c++) memset(advice + ((size_t)c * n + rows) * 4, 0, (n - rows) * 32);
-    trace("unused rows zeroed");
-    const uint32_t num_fixed = range_lookups ? 15 : 9;
-    if (fixed) {
-        memset(fixed, 0, (size_t)num_fixed * n * 32);
-        for (uint32_t c = 0; c < num_fixed; c++) memcpy(fixed + (size_t)c * n * 4, lay.fix[c].data(), rows * 32);
-        if (range_lookups) {      // RangeChip::load_table rows (tag, value): the disabled row (0, 0), then every value of every bit length
-            size_t r = 1;
-            for (unsigned ti = 0; ti < lay.range.count; ti++)
-                for (uint64_t v = 0; v < ((uint64_t)1 << lay.range.bits[ti]); v++, r++) {
-                    if (r >= u) return DEHALO_ERR_INVALID;
-                    fixed[((size_t)RC_T_TAG * n + r) * 4] = ti + 1;
-                    fixed[((size_t)RC_T_VALUE * n + r) * 4] = v;
-                }
+            const bool with_hash = in->circuit == DEHALO_CIRCUIT_DELAY_ENC;
+            uint32_t rsa_rows_beside = 0;
+            if (!keygen_outputs)      // proving: everything behind the exponentiation may be written beside it (BigIntChip::pow_mod_threads)
+                lay.after_pow = [&](Layouter& sub, const std::vector<Cell>& powed) {
+                    const std::vector<Cell> valid = rsa_expected_rows(sub, powed);
+                    rsa_rows_beside = sub.rows();
+                    if (with_hash) hash_and_cipher(sub, valid);
+                };
+            Big want;
+            const std::vector<Cell> rsa_out = rsa_region(lay, n_big, in->e, x, in->exp_bits, num_limbs, want);
+            inf.rsa_rows = lay.after_pow_done ? rsa_rows_beside : lay.rows();
+            trace(lay.after_pow_done ? "rsa, hash and cipher regions" : "rsa region");
+            const Big wl = big_limbs(want, std::min<size_t>(num_limbs, 128));
+            for (size_t i = 0; i < wl.size() && i < 128; i++) inf.rsa_result[i] = wl[i];
+            if (with_hash && !lay.after_pow_done) hash_and_cipher(lay, rsa_out);
         }
-    }
-    if (!range_lookups && keygen_outputs)
-        for (int c = 9; c < NUM_FIX; c++)
-            for (auto& v : lay.fix[c])
-                if (!v.is_zero()) return DEHALO_ERR_INVALID;      // range rows in a MainGate-only circuit
-    if (mapping) {
-        Assembly asm_(6, n);
-        for (auto& c : lay.copies) asm_.copy(c);
-        memcpy(mapping, asm_.mapping.data(), 6 * n * 8);
-    }
-    if (selectors && range_lookups) {
-        for (int s = 0; s < 2; s++) {
-            if (!selectors[s]) continue;
-            memset(selectors[s], 0, n);
-            const auto& col = lay.fix[s == 0 ? RC_S_COMPOSITION : RC_S_OVERFLOW];
-            for (size_t r = 0; r < rows; r++) selectors[s][r] = col[r].is_zero() ? 0 : 1;
+        trace("hash and cipher regions");
+        inf.total_rows = lay.rows();
+        if (in->circuit == DEHALO_CIRCUIT_POSE_ENC) inf.rsa_rows = 0;
+        for (size_t i = 0; i < cipher_vals.size() && i < 3; i++) memcpy(inf.cipher + 4 * i, cipher_vals[i].v, 32);
+        inf.cipher_len = (uint32_t)std::min<size_t>(cipher_vals.size(), 3);
+        if (info) *info = inf;
+        // ---- into 2^k-row columns
+        const uint32_t bf = 5;      // blinding_factors of both constraint systems: max(3, 2 queries of advice column e) + 2
+        const size_t u = n - (bf + 1);
+        if ((size_t)lay.rows() + 1 > u) return DEHALO_ERR_INVALID;      // "not enough rows available" (upstream: Error::NotEnoughRowsAvailable)
+        const size_t rows = lay.rows();
+        if (advice)      // (the used rows are already in place)
+            for (int c = 0; c < 5; c++) memset(advice + ((size_t)c * n + rows) * 4, 0, (n - rows) * 32);
+        trace("unused rows zeroed");
+        const uint32_t num_fixed = range_lookups ? 15 : 9;
+        if (fixed) {
+            memset(fixed, 0, (size_t)num_fixed * n * 32);
+            for (uint32_t c = 0; c < num_fixed; c++) memcpy(fixed + (size_t)c * n * 4, lay.fix[c].data(), rows * 32);
+            if (range_lookups) {      // RangeChip::load_table rows (tag, value): the disabled row (0, 0), then every value of every bit length
+                size_t r = 1;
+                for (unsigned ti = 0; ti < lay.range.count; ti++)
+                    for (uint64_t v = 0; v < ((uint64_t)1 << lay.range.bits[ti]); v++, r++) {
+                        if (r >= u) return DEHALO_ERR_INVALID;
+                        fixed[((size_t)RC_T_TAG * n + r) * 4] = ti + 1;
+                        fixed[((size_t)RC_T_VALUE * n + r) * 4] = v;
+                    }
+            }
         }
-    }
-    return 0;
-} catch (const NotSatisfied&) {
-    return DEHALO_ERR_INVALID;      // a constraint of the reference's circuit does not hold for these inputs (x >= n, an exponent wider than exp_bits, a non-zero message)
-} catch (...) { return DEHALO_ERR_OOM; }
+        if (!range_lookups && keygen_outputs)
+            for (int c = 9; c < NUM_FIX; c++)
+                for (auto& v : lay.fix[c])
+                    if (!v.is_zero()) return DEHALO_ERR_INVALID;      // range rows in a MainGate-only circuit
+        if (mapping) {
+            Assembly asm_(6, n);
+            for (auto& c : lay.copies) asm_.copy(c);
+            memcpy(mapping, asm_.mapping.data(), 6 * n * 8);
+        }
+        if (selectors && range_lookups) {
+            for (int s = 0; s < 2; s++) {
+                if (!selectors[s]) continue;
+                memset(selectors[s], 0, n);
+                const auto& col = lay.fix[s == 0 ? RC_S_COMPOSITION : RC_S_OVERFLOW];
+                for (size_t r = 0; r < rows; r++) selectors[s][r] = col[r].is_zero() ? 0 : 1;
+            }
+        }
+        return 0;
+    });
+}

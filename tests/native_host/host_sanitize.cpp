@@ -5,10 +5,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
+#include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "../../include/dehalo.h"
 #include "../../delay-encryption-in-halo2_amd/csrc/blake2b.hpp"
+#include "../../delay-encryption-in-halo2_amd/csrc/guard.hpp"
 #include "../../delay-encryption-in-halo2_amd/csrc/hostrng.hpp"
 
 int main(int argc, char** argv) {
@@ -49,6 +53,32 @@ int main(int argc, char** argv) {
     if (dehalo_synthesize(&in, advice.data(), nullptr, nullptr, nullptr, nullptr) == 0) { printf("k = 10 accepted\n"); return 1; }
     in.k = k; in.exp_bits = 65;
     if (dehalo_synthesize(&in, advice.data(), nullptr, nullptr, nullptr, nullptr) == 0) { printf("exp_bits = 65 accepted\n"); return 1; }
+    // a constraint that cannot hold (the circuit is satisfiable for the zero message only) throws inside the call and leaves it as DEHALO_ERR_INVALID
+    in.exp_bits = exp_bits;
+    const uint64_t message1[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+    in.message = message1;
+    if (dehalo_synthesize(&in, advice.data(), nullptr, nullptr, nullptr, nullptr) != DEHALO_ERR_INVALID) { printf("non-zero message not refused\n"); return 1; }
+    in.message = message;
+    // the entry points' guard: return codes pass through, exceptions become codes (std::bad_alloc: OOM; anything else: INVALID, its message noted)
+    {
+        struct Unsatisfied : std::runtime_error { using std::runtime_error::runtime_error; };      // as witness.hip's NotSatisfied
+        std::string noted;
+        auto note = [&](const char* m) { noted = m; };
+        auto expect = [&](const char* what, int got, int want, const char* msg) {
+            const bool ok = got == want && noted == msg;
+            if (!ok) printf("guard: %s returned %d (noted \"%s\"), not %d (\"%s\")\n", what, got, noted.c_str(), want, msg);
+            noted.clear();
+            return ok;
+        };
+        if (!expect("0", dh_guard_noting(note, [] { return 0; }), 0, "")) return 1;
+        if (!expect("a code", dh_guard_noting(note, [] { return (int)DEHALO_ERR_UNSUPPORTED; }), DEHALO_ERR_UNSUPPORTED, "")) return 1;
+        if (!expect("bad_alloc", dh_guard_noting(note, []() -> int { throw std::bad_alloc(); }), DEHALO_ERR_OOM, "")) return 1;
+        if (!expect("runtime_error", dh_guard_noting(note, []() -> int { throw std::runtime_error("runtime"); }), DEHALO_ERR_INVALID, "runtime")) return 1;
+        if (!expect("derived", dh_guard_noting(note, []() -> int { throw Unsatisfied("derived"); }), DEHALO_ERR_INVALID, "derived")) return 1;
+        if (!expect("int", dh_guard_noting(note, []() -> int { throw 7; }), DEHALO_ERR_INVALID, "unexpected exception")) return 1;
+        if (!expect("no context", dh_guard(nullptr, []() -> int { throw std::runtime_error("x"); }), DEHALO_ERR_INVALID, "")) return 1;
+        if (!expect("no context, bad_alloc", dh_guard(nullptr, []() -> int { throw std::bad_alloc(); }), DEHALO_ERR_OOM, "")) return 1;
+    }
     // random scalars: OS entropy below p, PCG64 with a seek
     const HostField* f = host_field(0);
     HostRng r;
