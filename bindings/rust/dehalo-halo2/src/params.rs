@@ -123,3 +123,33 @@ impl Drop for DehaloParamsKZG<'_> {
         }
     }
 }
+
+/// `ParamsIPA<EqAffine>` (Vesta) from the vectors upstream's `ParamsIPA` holds (`params.g`, `params.g_lagrange`, `params.w`, `params.u`):
+/// `dehalo_params_ipa_create`.  `ParamsIPA::new`, `read` / `write` and whole `ProverIPA` proofs are not provided by the library; what it
+/// provides over these params is keygen (`commit_lagrange` with a zero blind) and the opening argument of one polynomial (`dehalo_ipa_open`,
+/// upstream's `poly::ipa::commitment::create_proof`).
+pub struct DehaloParamsIPA<'c> {
+    pub(crate) ctx: &'c Context,
+    pub(crate) raw: *mut sys::dehalo_params,
+    pub k: u32,
+}
+
+impl<'c> DehaloParamsIPA<'c> {
+    pub fn from_vectors(ctx: &'c Context, k: u32, g: &[halo2curves::pasta::EqAffine], g_lagrange: &[halo2curves::pasta::EqAffine], w: &halo2curves::pasta::EqAffine,
+                        u: &halo2curves::pasta::EqAffine) -> Result<Self, DehaloError> {
+        assert_eq!(g.len(), 1usize << k);
+        assert_eq!(g_lagrange.len(), 1usize << k);
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe {
+            sys::dehalo_params_ipa_create(ctx.as_ptr(), sys::DEHALO_CURVE_VESTA, k, g.as_ptr() as *const u64, g_lagrange.as_ptr() as *const u64,
+                                          w as *const _ as *const u64, u as *const _ as *const u64, &mut raw)
+        })?;
+        Ok(Self { ctx, raw, k })
+    }
+}
+
+impl Drop for DehaloParamsIPA<'_> {
+    fn drop(&mut self) {
+        unsafe { sys::dehalo_params_release(self.ctx.as_ptr(), self.raw) };
+    }
+}

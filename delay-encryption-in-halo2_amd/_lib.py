@@ -30,6 +30,7 @@ SYMBOLS = [
     "dehalo_transcript_create", "dehalo_transcript_common_scalar", "dehalo_transcript_write_scalar", "dehalo_transcript_write_point",
     "dehalo_transcript_squeeze_challenge", "dehalo_transcript_len", "dehalo_transcript_finalize", "dehalo_transcript_release",
     "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs",
+    "dehalo_params_ipa_create", "dehalo_params_scheme", "dehalo_generator_collapse_device", "dehalo_ipa_open",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
 ]
 
@@ -158,6 +159,7 @@ def load_library():
     lib.dehalo_best_multiexp.argtypes = [P, C.c_int, u64p, u64p, sz, u64p]
     lib.dehalo_to_affine.argtypes = [P, C.c_int, u64p, sz, u64p]
     lib.dehalo_to_affine_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
+    lib.dehalo_generator_collapse_device.argtypes = [P, C.c_int, u64p, sz, u64p, u64p, P]
     lib.dehalo_point_sum_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
     lib.dehalo_ntt.argtypes = [P, C.c_int, u64p, u32, u64p]
     lib.dehalo_ntt_device.argtypes = [P, C.c_int, u64p, u32, u64p, sz, P]
@@ -219,6 +221,8 @@ def load_library():
     lib.dehalo_params_write.argtypes = [P, P, sz]
     lib.dehalo_params_release.argtypes = [P, P]
     lib.dehalo_params_commit_device.argtypes = [P, P, u64p, sz, C.c_int, u64p, P]
+    lib.dehalo_params_ipa_create.argtypes = [P, C.c_int, u32, u64p, u64p, u64p, u64p, PP]
+    lib.dehalo_params_scheme.argtypes = [P]
     lib.dehalo_keygen.argtypes = [P, P, C.POINTER(CConstraintSystem), u64p, u64p, C.POINTER(C.c_void_p), u32, u32, PP]
     lib.dehalo_pk_read.argtypes = [P, C.c_int, C.POINTER(CConstraintSystem), P, sz, u32, PP]
     lib.dehalo_pk_size.argtypes = [P]
@@ -234,6 +238,7 @@ def load_library():
     lib.dehalo_synthesize.argtypes = [C.POINTER(CCircuitInputs), u64p, u64p, u64p, C.POINTER(C.c_void_p), C.POINTER(CSynthesisInfo)]
     lib.dehalo_field_info.argtypes = [C.c_int, u64p]
     lib.dehalo_rng_scalars.argtypes = [C.POINTER(CRng), C.c_int, C.c_uint64, u64p, sz]
+    lib.dehalo_ipa_open.argtypes = [P, P, u64p, u64p, u64p, C.POINTER(CRng), P]
     lib.dehalo_transcript_create.argtypes = [C.c_int, PP]
     lib.dehalo_transcript_common_scalar.argtypes = [P, u64p]
     lib.dehalo_transcript_write_scalar.argtypes = [P, u64p]
@@ -415,6 +420,11 @@ class Context:
 
     def point_sum_device(self, curve: int, d_jacobian: int, count: int, d_out: int, stream: int = 0):
         self._check(self.lib.dehalo_point_sum_device(self.handle, curve, d_jacobian, count, d_out, stream or None))
+
+    def generator_collapse_device(self, curve: int, d_affine: int, length: int, challenge, d_out: int, stream: int = 0):
+        """parallel_generator_collapse: d_out[i] = g[i] + [challenge] g[length / 2 + i] (challenge = 4 x u64 Montgomery)"""
+        ch = np.ascontiguousarray(challenge, dtype=np.uint64).reshape(4)
+        self._check(self.lib.dehalo_generator_collapse_device(self.handle, curve, d_affine, length, ch.ctypes.data, d_out, stream or None))
 
     def to_affine_device(self, curve: int, d_jacobian: int, count: int, d_affine: int, stream: int = 0):
         self._check(self.lib.dehalo_to_affine_device(self.handle, curve, d_jacobian, count, d_affine, stream or None))

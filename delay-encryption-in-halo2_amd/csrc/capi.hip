@@ -10,6 +10,7 @@
 #include <memory>
 
 #include "evalh_types.hpp"
+#include "hostfield.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -323,6 +324,29 @@ int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t 
 
 }  // namespace
 
+const IpaOps* ipa_ops(int curve) {
+    if (curve == DEHALO_CURVE_PALLAS) return &pallas_ipa_ops();
+    if (curve == DEHALO_CURVE_VESTA) return &vesta_ipa_ops();
+    return nullptr;
+}
+
+int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, dehalo_bases** out) {
+    if (!curve_ops(curve) || cap == 0 || cap >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_plain_alloc: bad argument");
+    std::unique_ptr<dehalo_bases, BasesFree> b(new dehalo_bases());
+    b->curve = curve; b->n = 0; b->c = 4; b->W = 0; b->precomp = 0; b->table = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&b->table, cap * sizeof(affine_t)));
+    *out = b.release();
+    return 0;
+}
+
+int dh_bases_plain_rebuild(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_points, size_t n, hipStream_t s) {
+    const CurveOps* cv = curve_ops(b->curve);
+    b->n = n;
+    b->c = std::max<uint32_t>(4, choose_window_single(n));
+    b->W = signed_windows(cv->scalar_modulus, b->c);
+    return cv->build_table(ctx, b, d_points, s);
+}
+
 // the limit of a precomputed table registered with window_bits = 0: n x windows < 2^30 (30-bit table indices in the sorted list, msm.cuh)
 bool dh_precomputed_table_fits(int curve, size_t n) {
     const CurveOps* cv = curve_ops(curve);
@@ -623,6 +647,27 @@ int dehalo_to_affine_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobi
     return curve_device(ctx, curve, stream, [&](const CurveOps& cv, hipStream_t s) {
         return cv.to_affine(ctx, (const jacobian_t*)d_jacobian, (affine_t*)d_affine_xy, (uint32_t)count, s);
     });
+}
+
+int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t len, const uint64_t challenge[4], uint64_t* d_out_affine_xy,
+                                     void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!curve_ops(curve)) return unknown_curve(ctx);
+    const IpaOps* ops = ipa_ops(curve);
+    if (!ops) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "generator_collapse: Pallas and Vesta only (IPA)");
+    if (!challenge || ((!d_affine_xy || !d_out_affine_xy) && len)) return dh_fail(ctx, DEHALO_ERR_INVALID, "generator_collapse: null argument");
+    if (len & 1) return dh_fail(ctx, DEHALO_ERR_INVALID, "generator_collapse: odd length");
+    if (len >= (1ull << 31)) return dh_fail(ctx, DEHALO_ERR_INVALID, "generator_collapse: too many points");
+    if (len == 0) return 0;
+    const size_t half = len / 2;
+    // out == the input is the in-place collapse; any other overlap with the input would be read after it is written
+    const uintptr_t ia = (uintptr_t)d_affine_xy, ib = ia + 64 * len, oa = (uintptr_t)d_out_affine_xy, ob = oa + 64 * half;
+    if (oa != ia && oa < ib && ia < ob) return dh_fail(ctx, DEHALO_ERR_INVALID, "generator_collapse: the output overlaps the input other than in place");
+    const HostField* f = host_field(curve_scalar_field(curve));
+    Fe u;
+    memcpy(u.v, challenge, 32);
+    const Fe uc = f->to_canonical(u);
+    return dh_device(ctx, stream, [&](hipStream_t s) { return ops->collapse(ctx, (const affine_t*)d_affine_xy, half, uc.v, (affine_t*)d_out_affine_xy, s); });
 }
 
 int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_t count, uint64_t* affine_xy) {

@@ -388,6 +388,21 @@ struct CurveOps {
 const CurveOps& bn254_curve_ops();
 const CurveOps& pallas_curve_ops();
 const CurveOps& vesta_curve_ops();
+// the IPA opening argument's kernels, one table per Pasta curve (ipa.cuh, instantiated in msm_pallas.hip / msm_vesta.hip)
+struct IpaOps {
+    // out[i] = g[i] + [u] g[half + i] for i < half; u canonical (4 x u64)
+    int (*collapse)(dehalo_ctx* ctx, const affine_t* d_g, uint64_t half, const uint64_t u_canon[4], affine_t* d_out, hipStream_t s);
+    // one round's scalar slots of the [G' | U | W] MSM (dehalo_ipa_open)
+    int (*slots)(dehalo_ctx* ctx, const fe* d_evals, const uint64_t coef_l[4], const uint64_t coef_r[4], const fe* d_rands, fe* d_sl, fe* d_sr, hipStream_t s);
+};
+const IpaOps& pallas_ipa_ops();
+const IpaOps& vesta_ipa_ops();
+const IpaOps* ipa_ops(int curve);       // capi.hip: null unless Pallas / Vesta
+// A plain (precompute 0) registration whose points are replaced on the stream, without a host wait or an allocation (capi.hip): the IPA rounds'
+// shrinking generator vector.  alloc: room for `cap` points, empty; rebuild: n <= cap points from d_points (standard Montgomery), the window
+// chosen for n as dehalo_bases_register_device would; queued on s, so the caller may overwrite d_points once later work on s reads the table.
+int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, dehalo_bases** out);
+int dh_bases_plain_rebuild(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_points, size_t n, hipStream_t s);
 // ParamsKZG::setup's device half (setup.cuh, instantiated in msm_bn254.hip): g[i] = [s^i] G, g_lagrange[i] = [L_i(s)] G into device memory
 int kzg_setup_bn254(dehalo_ctx* ctx, uint32_t k, const uint64_t s[4], const uint64_t omega[4], const uint64_t cfac[4], affine_t* d_g, affine_t* d_gl, hipStream_t st);
 

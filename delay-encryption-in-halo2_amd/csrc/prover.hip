@@ -114,6 +114,11 @@ struct dehalo_params {
     std::vector<uint64_t> g, g_lagrange;      // host copies (write())
     uint8_t g2[128] = {}, s_g2[128] = {};
     dehalo_bases *bases_g = nullptr, *bases_gl = nullptr;
+    int scheme = DEHALO_SCHEME_KZG;
+    // ParamsIPA only: g as plain affine points followed by u, w (n + 2 points, standard Montgomery): the generator vector the opening collapses
+    DevMem d_guw;
+    dehalo_bases* bases_uw = nullptr;         // [U | W] plain: the extra bases of round 1, whose G' part runs over bases_g
+    uint64_t u[8] = {}, w[8] = {};
 };
 
 extern "C" int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint8_t* g2, const uint8_t* s_g2,
@@ -260,11 +265,12 @@ extern "C" int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* byt
     });
 }
 
-extern "C" size_t dehalo_params_size(const dehalo_params* p) { return p ? 4 + 2 * 64 * p->n + 256 : 0; }
+extern "C" size_t dehalo_params_size(const dehalo_params* p) { return p && p->scheme == DEHALO_SCHEME_KZG ? 4 + 2 * 64 * p->n + 256 : 0; }
 
 extern "C" int dehalo_params_write(const dehalo_params* p, uint8_t* out, size_t cap) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || !out) return DEHALO_ERR_INVALID;
+        if (p->scheme != DEHALO_SCHEME_KZG) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "params_write: ParamsIPA::write is not implemented");
         if (cap < dehalo_params_size(p)) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "params_write: buffer too small");
         for (int i = 0; i < 4; i++) out[i] = (uint8_t)(p->k >> (8 * i));
         memcpy(out + 4, p->g.data(), 64 * p->n);
@@ -280,6 +286,7 @@ extern "C" int dehalo_params_release(dehalo_ctx* ctx, dehalo_params* p) {
         if (!p) return 0;
         if (p->bases_g) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_g);
         if (p->bases_gl) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_gl);
+        if (p->bases_uw) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_uw);
         delete p;
         return 0;
     });
@@ -399,6 +406,185 @@ extern "C" int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* o
     });
 }
 extern "C" void dehalo_transcript_release(dehalo_transcript* t) { delete t; }
+
+// ================================================================================================ ParamsIPA and the IPA opening argument
+extern "C" int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8],
+                                        const uint64_t u[8], dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !out || !g || !g_lagrange || !w || !u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: null argument");
+        if (curve != DEHALO_CURVE_PALLAS && curve != DEHALO_CURVE_VESTA) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_ipa_create: IPA over Pallas / Vesta only");
+        if (k < 1 || k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: k out of range");
+        const size_t n = (size_t)1 << k;
+        if (!dh_precomputed_table_fits(curve, n)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: 2^k x windows >= 2^30: precomputed table too large");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        dehalo_params* raw = nullptr;
+        TRY(dehalo_params_create(ctx, curve, k, g, g_lagrange, nullptr, nullptr, &raw));
+        std::unique_ptr<dehalo_params, void (*)(dehalo_params*)> p(raw, [](dehalo_params* q) { (void)dehalo_params_release(q->ctx, q); });
+        p->scheme = DEHALO_SCHEME_IPA;
+        memcpy(p->w, w, 64);
+        memcpy(p->u, u, 64);
+        TRY(p->d_guw.alloc(ctx, 2 * (n + 2), false));
+        TRY(dh_h2d(ctx, p->d_guw.p, g, 64 * n, ctx->stream));
+        TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream));
+        TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream));
+        TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, &p->bases_uw));
+        *out = p.release();
+        return 0;
+    });
+}
+
+extern "C" int dehalo_params_scheme(const dehalo_params* p) { return p ? p->scheme : DEHALO_ERR_INVALID; }
+
+namespace {
+
+// commit(poly, blind) of ParamsIPA = MSM(poly, g) + [blind] W, affine into d_pair[0] (d_pair: two points of scratch; [1] receives W): the MSM's affine
+// result and W make a two-point generator vector whose collapse by `blind` is exactly C + [blind] W
+int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, uint64_t* d_pair, hipStream_t s) {
+    TRY(dehalo_msm_device_affine(ctx, p->bases_g, d_poly, p->n, 1, nullptr, d_pair, s));
+    HIP_TRY(ctx, hipMemcpyAsync(d_pair + 8, p->d_guw.at(2 * p->n + 2), 64, hipMemcpyDeviceToDevice, s));
+    return dehalo_generator_collapse_device(ctx, p->curve, d_pair, 2, blind.v, d_pair, s);
+}
+}   // namespace
+
+extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const uint64_t blind_in[4], const uint64_t x3_in[4], dehalo_rng* rng_in,
+                               dehalo_transcript* t) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !p || !d_poly || !blind_in || !x3_in || !t) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: null argument");
+        if (p->scheme != DEHALO_SCHEME_IPA) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: needs ParamsIPA (dehalo_params_ipa_create)");
+        if (t->curve != p->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: transcript and params disagree on the curve");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const hipStream_t s = ctx->stream;
+        const int fid = curve_scalar_field(p->curve);
+        const HostField* f = host_field(fid);
+        const IpaOps* ops = ipa_ops(p->curve);
+        const size_t n = p->n;
+        const uint32_t k = p->k;
+        Fe blind, x3;
+        memcpy(blind.v, blind_in, 32);
+        memcpy(x3.v, x3_in, 32);
+        DevMem s_poly, s_adj, pa, pb, guw, sc, ev, rr, pts, uwsc;
+        TRY(s_poly.alloc(ctx, n, false));
+        TRY(s_adj.alloc(ctx, n, false));
+        TRY(pa.alloc(ctx, n, false));
+        TRY(pb.alloc(ctx, n, false));
+        TRY(guw.alloc(ctx, n + 4, false));           // G' of rounds 2.., then U, W: n / 2 + 2 points of 2 elements
+        TRY(sc.alloc(ctx, 2 * n, false));
+        TRY(ev.alloc(ctx, 2, false));
+        TRY(rr.alloc(ctx, 2 * (size_t)k, false));
+        TRY(pts.alloc(ctx, 8, false));
+        TRY(uwsc.alloc(ctx, 4, false));
+        // ---- draws, in upstream's order: s_poly (n), s_poly_blind, (l_rand, r_rand) per round.  The n scalars are the proof's large draw and come, as
+        // the prover's random polynomial does, from the generator forked at their position: for DEHALO_RNG_OS a ChaCha20 kernel under the call's key
+        // (stream 1); for PCG64 / a callback the fork yields exactly the scalars a serial draw would, drawn on the host and uploaded.
+        HostRng rng;
+        TRY(rng.init(rng_in, f));
+        HostRng rng_poly = rng.fork(0, 1);
+        rng.skip(n);
+        Fe s_blind;
+        std::vector<uint64_t> rands(8 * (size_t)k);
+        TRY(rng.scalars(s_blind.v, 1));
+        TRY(rng.scalars(rands.data(), 2 * (size_t)k));
+        if (rng.kind == DEHALO_RNG_OS) {
+            ChaKey ck;
+            memcpy(ck.k, rng.key, 32);
+            fe pw;
+            for (int i = 0; i < 4; i++) { pw.v[2 * i] = (u32)f->p[i]; pw.v[2 * i + 1] = (u32)(f->p[i] >> 32); }
+            const u32 top_mask = f->bits >= 256 ? 0xffffffffu : ((1u << (f->bits - 224)) - 1);
+            k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ck, /* stream of the fork */ 1, pw, top_mask, s_poly.p, n);
+            HIP_TRY(ctx, hipGetLastError());
+        } else {
+            std::vector<uint64_t> s_host(4 * n);
+            TRY(rng_poly.scalars(s_host.data(), n));
+            TRY(dh_h2d(ctx, s_poly.p, s_host.data(), 32 * n, s));
+        }
+        TRY(dh_h2d(ctx, rr.p, rands.data(), 64 * (size_t)k, s));
+        // ---- s(x3) and p(x3); s_poly[0] -= s(x3)
+        TRY(dehalo_eval_polynomial_device(ctx, fid, s_poly.u64(), n, n, 1, x3.v, ev.u64(0), s));
+        TRY(dehalo_eval_polynomial_device(ctx, fid, d_poly, n, n, 1, x3.v, ev.u64(1), s));
+        Fe at[2];
+        TRY(dehalo_download(ctx, ev.p, 64, at));
+        const uint64_t* one_col[1] = {s_poly.u64()};
+        TRY(dehalo_lincomb_device(ctx, fid, one_col, f->one.v, 1, n, s_adj.u64(), at[0].v, s));
+        // ---- S = commit(s_poly, s_poly_blind)
+        TRY(ipa_commit_blinded(ctx, p, s_adj.u64(), s_blind, pts.u64(), s));
+        uint64_t S[8];
+        TRY(dehalo_download(ctx, pts.p, 64, S));
+        if (!t->write_point(S)) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: s_poly commitment at infinity");
+        const Fe xi = t->squeeze();
+        const Fe z = t->squeeze();
+        // ---- p' = p + xi s, p'[0] -= p'(x3) (= p(x3): s(x3) = 0 now); f = s_poly_blind xi + blind
+        {
+            const uint64_t* cols[2] = {d_poly, s_adj.u64()};
+            Fe coefs[2] = {f->one, xi};
+            TRY(dehalo_lincomb_device(ctx, fid, cols, coefs[0].v, 2, n, pa.u64(), at[1].v, s));
+        }
+        Fe fsum = f->add(f->mul(s_blind, xi), blind);
+        // ---- k rounds; b stays geometric: b^(j)[i] = c_j x3^i.  Round 1 runs over the resident precomputed table of g (its [U | W] terms over
+        // bases_uw, added by a collapse with u = 1); rounds 2.. over one plain registration of [G' | U | W], rebuilt on the stream each round.
+        dehalo_bases* breg = nullptr;
+        TRY(dh_bases_plain_alloc(ctx, p->curve, n / 2 + 2, &breg));
+        std::unique_ptr<dehalo_bases, void (*)(dehalo_bases*)> breg_own(breg, [](dehalo_bases* b) { if (b->table) (void)hipFree(b->table); delete b; });
+        std::vector<Fe> x3_pow(k + 1);           // x3^(2^i)
+        x3_pow[0] = x3;
+        for (uint32_t i = 1; i <= k; i++) x3_pow[i] = f->sqr(x3_pow[i - 1]);
+        Fe c = f->one;
+        DevMem* cur = &pa;
+        DevMem* nxt = &pb;
+        for (uint32_t j = 0; j < k; j++) {
+            const size_t nj = n >> j, half = nj / 2, m = j == 0 ? nj : nj + 2;
+            const Fe x3h = x3_pow[k - 1 - j];                  // x3^half
+            // scalars: L = [p'_hi | 0 | z value_l | l_rand], R = [0 | p'_lo | z value_r | r_rand] (round 1: the [U | W] slots in uwsc)
+            fe* sl = sc.at(0);
+            fe* sr = sc.at(m);
+            HIP_TRY(ctx, hipMemcpyAsync(sl, cur->at(half), 32 * half, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(ctx, hipMemsetAsync(sl + half, 0, 32 * half, s));
+            HIP_TRY(ctx, hipMemsetAsync(sr, 0, 32 * half, s));
+            HIP_TRY(ctx, hipMemcpyAsync(sr + half, cur->p, 32 * half, hipMemcpyDeviceToDevice, s));
+            TRY(dehalo_eval_polynomial_device(ctx, fid, cur->u64(), half, half, 2, x3.v, ev.u64(), s));      // p'_lo(x3), p'_hi(x3)
+            const Fe zc = f->mul(z, c), zch = f->mul(zc, x3h);
+            if (j == 0) {
+                TRY(ops->slots(ctx, ev.p, zc.v, zch.v, rr.at(0), uwsc.at(0), uwsc.at(2), s));
+                TRY(dehalo_msm_device_affine(ctx, p->bases_g, sc.u64(), n, 2, nullptr, pts.u64(0), s));       // L_g, R_g
+                TRY(dehalo_msm_device_affine(ctx, p->bases_uw, uwsc.u64(), 2, 2, nullptr, pts.u64(4), s));    // L_uw, R_uw (points 2, 3)
+                const uint64_t one_m[4] = {f->one.v[0], f->one.v[1], f->one.v[2], f->one.v[3]};
+                TRY(dehalo_generator_collapse_device(ctx, p->curve, pts.u64(), 4, one_m, pts.u64(), s));      // [L_g + L_uw, R_g + R_uw]
+            } else {
+                TRY(ops->slots(ctx, ev.p, zc.v, zch.v, rr.at(2 * j), sl + nj, sr + nj, s));
+                HIP_TRY(ctx, hipMemcpyAsync(guw.at(2 * nj), p->d_guw.at(2 * n), 128, hipMemcpyDeviceToDevice, s));     // U, W behind G'
+                TRY(dh_bases_plain_rebuild(ctx, breg, (const affine_t*)guw.p, m, s));
+                TRY(dehalo_msm_device_affine(ctx, breg, sc.u64(), m, 2, nullptr, pts.u64(), s));
+            }
+            uint64_t LR[16];
+            TRY(dehalo_download(ctx, pts.p, 128, LR));      // the round's one host wait
+            if (!t->write_point(LR) || !t->write_point(LR + 8)) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: L_j or R_j at infinity");
+            const Fe u = t->squeeze();
+            const Fe u_inv = f->invert(u);
+            Fe lr, rrnd;
+            memcpy(lr.v, &rands[8 * j], 32);
+            memcpy(rrnd.v, &rands[8 * j + 4], 32);
+            fsum = f->add(fsum, f->add(f->mul(lr, u_inv), f->mul(rrnd, u)));
+            c = f->mul(c, f->add(f->one, f->mul(u, x3h)));
+            // p' <- p'_lo + u^-1 p'_hi (into the other buffer: lincomb's out may alias no column); G' <- G'_lo + [u] G'_hi (round 1 reads g, later
+            // rounds collapse in place; the last round's G' would never be read)
+            const uint64_t* cols[2] = {cur->u64(), cur->u64(half)};
+            Fe coefs[2] = {f->one, u_inv};
+            TRY(dehalo_lincomb_device(ctx, fid, cols, coefs[0].v, 2, half, nxt->u64(), nullptr, s));
+            if (j + 1 < k) TRY(dehalo_generator_collapse_device(ctx, p->curve, j == 0 ? p->d_guw.u64() : guw.u64(), nj, u.v, guw.u64(), s));
+            std::swap(cur, nxt);
+        }
+        Fe cfin;
+        TRY(dehalo_download(ctx, cur->p, 32, cfin.v));
+        t->write_scalar(cfin);
+        t->write_scalar(fsum);
+        if (rng_in && rng_in->kind == DEHALO_RNG_PCG64) {      // a PCG64 caller's generator moves past the draws (upstream's `&mut rng`)
+            rng_in->pcg_state[0] = (uint64_t)rng.pcg.state;
+            rng_in->pcg_state[1] = (uint64_t)(rng.pcg.state >> 64);
+        }
+        return 0;
+    });
+}
 
 extern "C" int dehalo_field_info(int field, uint64_t out[24]) {
     return dh_guard(nullptr, [&]() -> int {
@@ -1651,6 +1837,7 @@ extern "C" int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !params || !pk || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: null argument");
         if (params->k != pk->k || params->curve != pk->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: params and proving key disagree on k / curve");
+        if (params->scheme != DEHALO_SCHEME_KZG) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "prover_create: whole proofs are KZG / GWC only (ParamsIPA: dehalo_ipa_open)");
         if (side_ctx && (side_ctx == ctx || side_ctx->device != ctx->device)) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: the side context must be another context of the same device");
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);

@@ -146,6 +146,40 @@ class ParamsKZG:
             self.handle = None
 
 
+class ParamsIPA(ParamsKZG):
+    """dehalo_params over IPACommitmentScheme<C> (Pallas / Vesta): g, g_lagrange, w, u handed over as the caller's ParamsIPA holds them
+    (dehalo_params_ipa_create).  ProvingKey.keygen takes it as it takes ParamsKZG; whole proofs are KZG only -- open one polynomial with
+    `open`."""
+
+    @classmethod
+    def create(cls, ctx: Context, curve: CurveSpec, k: int, g, g_lagrange, w, u) -> "ParamsIPA":
+        g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+        gl = np.ascontiguousarray(g_lagrange, dtype=np.uint64).reshape(-1, 8)
+        w = np.ascontiguousarray(w, dtype=np.uint64).reshape(8)
+        u = np.ascontiguousarray(u, dtype=np.uint64).reshape(8)
+        if g.shape[0] != 1 << k or gl.shape[0] != 1 << k:
+            raise ValueError("g and g_lagrange must hold 2^k points")
+        h = C.c_void_p()
+        _check(ctx, load_library().dehalo_params_ipa_create(ctx.handle, curve.id, k, g.ctypes.data, gl.ctypes.data, w.ctypes.data, u.ctypes.data, C.byref(h)))
+        return cls(ctx, curve, h)
+
+    @classmethod
+    def setup(cls, *a, **kw):
+        raise NotImplementedError("ParamsIPA::new is not provided: pass g, g_lagrange, w, u to ParamsIPA.create")
+
+    read = setup
+
+    def open(self, d_poly: int, blind: int, x3: int, transcript: Optional["Blake2bWrite"] = None, rng=None) -> "Blake2bWrite":
+        """commitment::create_proof of the 2^k coefficients at d_poly (device, Montgomery) with blind `blind` at x3 (dehalo_ipa_open)."""
+        t = transcript if transcript is not None else Blake2bWrite(self.curve)
+        r = rng_struct(rng)
+        f = self.curve.scalar
+        b, x = f.encode(blind % f.p), f.encode(x3 % f.p)
+        _check(self.ctx, load_library().dehalo_ipa_open(self.ctx.handle, self.handle, d_poly, b.ctypes.data, x.ctypes.data, C.byref(r) if r is not None else None, t.handle))
+        rng_writeback(rng, r)
+        return t
+
+
 class ProvingKey:
     """dehalo_pk: ProvingKey (with its VerifyingKey and compiled programs) resident on the device."""
 

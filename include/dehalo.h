@@ -154,6 +154,12 @@ int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_
 int dehalo_point_sum_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobian, size_t count, uint64_t* d_out_jacobian, void* stream);
 /* device-pointer form: `count` Jacobian points (96 B each) -> affine (64 B each), asynchronous on the stream */
 int dehalo_to_affine_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobian, size_t count, uint64_t* d_affine_xy, void* stream);
+/* The generator collapse of the IPA opening argument [UPSTREAM halo2_proofs/src/poly/ipa/commitment/prover.rs: parallel_generator_collapse]:
+ * out[i] = g[i] + [challenge] g[len / 2 + i] for i < len / 2, affine {x, y} (64 B, identity = (0, 0), standard Montgomery) in and out, device memory;
+ * challenge = one scalar (4 x u64 Montgomery).  len even, < 2^31.  d_out_affine_xy may be d_affine_xy itself (upstream collapses in place), and may
+ * overlap it in no other way.  Pallas and Vesta only (DEHALO_ERR_UNSUPPORTED otherwise).  Asynchronous on the stream; no workspace. */
+int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t len, const uint64_t challenge[4], uint64_t* d_out_affine_xy,
+                                     void* stream);
 
 /* ---- NTT == halo2_proofs::arithmetic::best_fft(a, omega, log_n) ---------------------------
  * [halo2_proofs/src/arithmetic.rs].  In place, natural order in and out,
@@ -402,7 +408,7 @@ int dehalo_lookup_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_lookup
  * What arrives from the caller is what halo2 holds at that point: the constraint system as data, the fixed columns and the permutation
  * assembly keygen produced, the advice columns `synthesize` filled (witness generation stays the front-end's).
  */
-typedef struct dehalo_params dehalo_params;         /* ParamsKZG<E>: k, g, g_lagrange (resident MSM tables), g2, s_g2 */
+typedef struct dehalo_params dehalo_params;         /* ParamsKZG<E>: k, g, g_lagrange (resident MSM tables), g2, s_g2; or ParamsIPA<C>: k, g, g_lagrange, w, u */
 typedef struct dehalo_pk dehalo_pk;                 /* ProvingKey<C> incl. its VerifyingKey and the compiled GraphEvaluator programs */
 typedef struct dehalo_prover dehalo_prover;         /* device buffers of ONE proof in flight (reused by every create_proof on it) */
 typedef struct dehalo_transcript dehalo_transcript; /* Blake2bWrite<Vec<u8>, C, Challenge255<C>> */
@@ -417,6 +423,19 @@ int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t*
  * `ParamsKZG::<Bn256>::setup(K, OsRng)` (benches/delay_enc.rs:43).  BN254 only (a KZG SRS needs the pairing); k <= 25 (checked before any device work: k = 26, whose two tables
  * would take 128 GB, is DEHALO_ERR_INVALID). */
 int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s[4], dehalo_params** out);
+/* ParamsIPA<C> [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs] from its parts, as the caller's ParamsIPA holds them: g / g_lagrange = 2^k affine
+ * points each, w and u one point each ({x, y} Montgomery, 64 B, the layout of dehalo_params_create).  Pallas or Vesta (IPACommitmentScheme<EqAffine>
+ * is Vesta; its scalar field is pasta::Fp); any other curve is DEHALO_ERR_UNSUPPORTED.  g and g_lagrange are registered with precomputed tables
+ * as for KZG, so dehalo_keygen and dehalo_params_commit_device work unchanged (vk commitments are commit_lagrange with Blind::default(), a zero
+ * blind: no [blind] W term).  g, u and w also stay on the device as plain points for the opening argument (dehalo_ipa_open).
+ * Not provided: ParamsIPA::new (hash-to-curve of "Halo2-Parameters"), ParamsIPA::{read, write} (dehalo_params_size is 0 and dehalo_params_write
+ * DEHALO_ERR_UNSUPPORTED for these params) and g_to_lagrange (a group FFT): the caller passes params.g, params.g_lagrange, params.w and params.u.
+ * Whole proofs over IPA (ProverIPA's multiopen) are not provided either: dehalo_prover_create with these params is DEHALO_ERR_UNSUPPORTED. */
+int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
+                             dehalo_params** out);
+/* The commitment scheme of params: DEHALO_SCHEME_KZG (dehalo_params_create / _setup / _read) or DEHALO_SCHEME_IPA (dehalo_params_ipa_create); < 0 for null. */
+typedef enum { DEHALO_SCHEME_KZG = 0, DEHALO_SCHEME_IPA = 1 } dehalo_scheme;
+int dehalo_params_scheme(const dehalo_params* params);
 int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out);
 size_t dehalo_params_size(const dehalo_params* params);
 int dehalo_params_write(const dehalo_params* params, uint8_t* out, size_t cap);
@@ -495,6 +514,20 @@ int dehalo_transcript_squeeze_challenge(dehalo_transcript* t, uint64_t out[4]); 
 size_t dehalo_transcript_len(const dehalo_transcript* t);
 int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* out, size_t cap);                /* the proof bytes written so far */
 void dehalo_transcript_release(dehalo_transcript* t);
+
+/* The IPA opening of ONE polynomial [UPSTREAM halo2_proofs/src/poly/ipa/commitment/prover.rs: create_proof(params, rng, transcript, p_poly, p_blind,
+ * x_3)]: proves that the commitment P = MSM(p, g) + [blind] W opens to p(x_3) -- what ProverIPA's multiopen ends with, and what a test or an integrator
+ * can call on its own.  params: dehalo_params_ipa_create; d_poly: 2^k coefficients in device memory (Montgomery, read only); blind, x3: Montgomery.
+ * Neither P nor p(x_3) is written: the caller's transcript holds them already, as upstream's does.
+ * Draws, in upstream's order: s_poly (2^k scalars), s_poly_blind, then (l_rand, r_rand) for each of the k rounds.  s_poly is the call's large draw and
+ * comes from the generator forked at its position, as create_proof's random polynomial does: with DEHALO_RNG_OS a ChaCha20 kernel (fork stream 1) under
+ * the call's key, with PCG64 / a callback exactly the scalars a serial draw would give.  A PCG64 rng is advanced past all of them.
+ * Writes: the point S = commit(s_poly, s_poly_blind); squeezes xi, z; per round j < k the points L_j, R_j and squeezes u_j; then the scalars c, f.
+ * Proof bytes: 32 (S) + k x 64 (L_j | R_j) + 64 (c | f).  Each round queues its launches on the context's stream and waits once (L_j, R_j): round 1
+ * runs over the precomputed table of g, later rounds over one plain registration of [G' | U | W] that is rebuilt on the stream (no allocation, no wait). 
+ * Errors: DEHALO_ERR_INVALID for KZG params / null arguments / a point at infinity that the transcript cannot take. */
+int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t* d_poly, const uint64_t blind[4], const uint64_t x3[4], dehalo_rng* rng,
+                    dehalo_transcript* transcript);
 
 /* A prover = the device buffers of one proof for a given key, on `ctx` (stream + workspace).  `side_ctx` (may be NULL): a second context of
  * the same device; work no transcript challenge waits for (lagrange_to_coeff / coeff_to_extended of a phase's columns, the random
