@@ -1,4 +1,4 @@
-//! `plonk::ConstraintSystem<Fr>` -> `dehalo_constraint_system` (include/dehalo.h): the walk a patched `keygen_pk` / `ProvingKey::read` performs once per circuit.
+//! `plonk::ConstraintSystem<F>` (bn256::Fr, or pasta::Fp under IPA) -> `dehalo_constraint_system` (include/dehalo.h): the walk a patched `keygen_pk` / `ProvingKey::read` performs once per circuit.
 //! Executable versions of the same walk: `native.ConstraintSystemDescriptor` (Python, delay-encryption-in-halo2_amd/native.py) and `halo2_amd::ConstraintSystem`
 //! (C++, host/halo2_backend.hpp); the library's tests pin both against the CPU restatement's statement of the MainGate + RangeChip shape (oracle/shapes.py).
 //!
@@ -10,9 +10,9 @@ use halo2_proofs::poly::Rotation;
 use halo2curves::bn256::Fr;
 
 /// Owns the arrays a `dehalo_constraint_system` points into.
-pub struct Descriptor {
+pub struct Descriptor<F: ff::Field = Fr> {
     nodes: Vec<sys::dehalo_expr_node>,
-    constants: Vec<Fr>,
+    constants: Vec<F>,
     gates: Vec<u32>,
     lookup_lens: Vec<u32>,
     lookup_inputs: Vec<u32>,
@@ -39,8 +39,8 @@ fn query(col: &Column<Any>, rot: Rotation) -> sys::dehalo_column_query {
     sys::dehalo_column_query { kind: column_kind(col.column_type()), index: col.index() as u32, rotation: rot.0 }
 }
 
-impl Descriptor {
-    pub fn from_constraint_system(cs: &ConstraintSystem<Fr>) -> Self {
+impl<F: ff::Field> Descriptor<F> {
+    pub fn from_constraint_system(cs: &ConstraintSystem<F>) -> Self {
         let mut d = Descriptor {
             nodes: vec![], constants: vec![], gates: vec![], lookup_lens: vec![], lookup_inputs: vec![], lookup_tables: vec![],
             permutation_columns: cs.permutation().get_columns().iter().map(|c| query(c, Rotation::cur())).collect(),
@@ -77,7 +77,7 @@ impl Descriptor {
         (self.nodes.len() - 1) as u32
     }
 
-    fn constant(&mut self, c: Fr) -> u32 {
+    fn constant(&mut self, c: F) -> u32 {
         if let Some(i) = self.constants.iter().position(|x| *x == c) {
             return i as u32;
         }
@@ -86,7 +86,7 @@ impl Descriptor {
     }
 
     /// post-order: children are pushed (and numbered) before their parent
-    fn lower(&mut self, e: &Expression<Fr>) -> u32 {
+    fn lower(&mut self, e: &Expression<F>) -> u32 {
         match e {
             Expression::Constant(c) => {
                 let i = self.constant(*c);

@@ -125,9 +125,9 @@ impl Drop for DehaloParamsKZG<'_> {
 }
 
 /// `ParamsIPA<EqAffine>` (Vesta) from the vectors upstream's `ParamsIPA` holds (`params.g`, `params.g_lagrange`, `params.w`, `params.u`):
-/// `dehalo_params_ipa_create`.  `ParamsIPA::new`, `read` / `write` and whole `ProverIPA` proofs are not provided by the library; what it
-/// provides over these params is keygen (`commit_lagrange` with a zero blind) and the opening argument of one polynomial (`dehalo_ipa_open`,
-/// upstream's `poly::ipa::commitment::create_proof`).
+/// `dehalo_params_ipa_create`.  `ParamsIPA::new` and `read` / `write` are not provided by the library; what it provides over these params is
+/// keygen (`commit_lagrange` with `Blind::default()`), whole `ProverIPA` proofs (`prover::create_proof_ipa`) and the opening argument of one
+/// polynomial (`dehalo_ipa_open`, upstream's `poly::ipa::commitment::create_proof`).
 pub struct DehaloParamsIPA<'c> {
     pub(crate) ctx: &'c Context,
     pub(crate) raw: *mut sys::dehalo_params,

@@ -181,3 +181,51 @@ pub fn create_proof<R: RngCore + Send>(device: i32, params_raw_bytes: &[u8], cs:
     let prover = DehaloProver::new(&ctx, Some(&side), &params, &pk)?;
     prover.create_proof(advice, instances, rng)
 }
+
+unsafe extern "C" fn fill_from_fp<R: RngCore + Send>(user: *mut c_void, out: *mut u64, count: usize, _position: u64) -> i32 {
+    let rng = &mut *(user as *mut R);
+    for i in 0..count {
+        let s = halo2curves::pasta::Fp::random(&mut *rng);
+        core::ptr::copy_nonoverlapping(&s as *const _ as *const u64, out.add(4 * i), 4);
+    }
+    0
+}
+
+/// `plonk::create_proof::<IPACommitmentScheme<EqAffine>, ProverIPA<_>, Challenge255<_>, _, Blake2bWrite<_, _, _>, _>` for ONE circuit over
+/// `DehaloParamsIPA` (Vesta; scalars in `pasta::Fp`): keygen, prover and proof through the same three C calls as the KZG flow above -- the params'
+/// scheme selects ProverIPA inside `dehalo_create_proof` (blinded commitments, committed instance columns, the multiopen, the opening argument).
+/// The verifying key this keygen makes commits the fixed and permutation columns with `Blind::default()` taken as `Blind(F::ONE)` (INTEGRATION.md
+/// section 7: parity with upstream unpinned).  Returns the transcript bytes; their length is `dehalo_prover_proof_size`.
+pub fn create_proof_ipa<R: RngCore + Send>(ctx: &Context, side: Option<&Context>, params: &crate::params::DehaloParamsIPA<'_>,
+                                           cs: &ConstraintSystem<halo2curves::pasta::Fp>, fixed: &[halo2curves::pasta::Fp], mapping: &[u64], selectors: &[Vec<u8>],
+                                           transcript_repr: &halo2curves::pasta::Fp, advice: &[halo2curves::pasta::Fp], instances: &[&[halo2curves::pasta::Fp]],
+                                           rng: &mut R) -> Result<Vec<u8>, DehaloError> {
+    let d = Descriptor::from_constraint_system(cs);
+    let c = d.as_c();
+    let sel: Vec<*const u8> = selectors.iter().map(|s| s.as_ptr()).collect();
+    let mut pk = core::ptr::null_mut();
+    ctx.check(unsafe { sys::dehalo_keygen(ctx.as_ptr(), params.raw, &c, fixed.as_ptr() as *const u64, mapping.as_ptr(), sel.as_ptr(), sel.len() as u32, 0, &mut pk) })?;
+    let mut prover = core::ptr::null_mut();
+    let mut t = core::ptr::null_mut();
+    let inst_ptrs: Vec<*const u64> = instances.iter().map(|c| c.as_ptr() as *const u64).collect();
+    let inst_lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
+    let mut r = sys::dehalo_rng { kind: sys::DEHALO_RNG_CALLBACK, pcg_state: [0; 2], pcg_inc: [0; 2], fill: Some(fill_from_fp::<R>), user: rng as *mut R as *mut c_void };
+    let run = (|| {
+        ctx.check(unsafe { sys::dehalo_pk_set_transcript_repr(pk, transcript_repr as *const _ as *const u64) })?;
+        ctx.check(unsafe { sys::dehalo_prover_create(ctx.as_ptr(), side.map_or(core::ptr::null_mut(), |s| s.as_ptr()), params.raw, pk, &mut prover) })?;
+        ctx.check(unsafe { sys::dehalo_transcript_create(sys::DEHALO_CURVE_VESTA, &mut t) })?;
+        ctx.check(unsafe {
+            sys::dehalo_create_proof(prover, advice.as_ptr() as *const u64, inst_ptrs.as_ptr(), inst_lens.as_ptr(), inst_ptrs.len() as u32, &mut r, t, 0)
+        })?;
+        let mut bytes = vec![0u8; unsafe { sys::dehalo_transcript_len(t) }];
+        debug_assert_eq!(bytes.len(), unsafe { sys::dehalo_prover_proof_size(prover) });
+        ctx.check(unsafe { sys::dehalo_transcript_finalize(t, bytes.as_mut_ptr(), bytes.len()) })?;
+        Ok(bytes)
+    })();
+    unsafe {
+        if !t.is_null() { sys::dehalo_transcript_release(t); }
+        if !prover.is_null() { sys::dehalo_prover_release(prover); }
+        sys::dehalo_pk_release(ctx.as_ptr(), pk);
+    }
+    run
+}

@@ -30,7 +30,7 @@ SYMBOLS = [
     "dehalo_transcript_create", "dehalo_transcript_common_scalar", "dehalo_transcript_write_scalar", "dehalo_transcript_write_point",
     "dehalo_transcript_squeeze_challenge", "dehalo_transcript_len", "dehalo_transcript_finalize", "dehalo_transcript_release",
     "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs",
-    "dehalo_params_ipa_create", "dehalo_params_scheme", "dehalo_generator_collapse_device", "dehalo_ipa_open",
+    "dehalo_params_ipa_create", "dehalo_params_scheme", "dehalo_generator_collapse_device", "dehalo_ipa_open", "dehalo_blind_commitments_device", "dehalo_prover_proof_size",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
 ]
 
@@ -160,6 +160,7 @@ def load_library():
     lib.dehalo_to_affine.argtypes = [P, C.c_int, u64p, sz, u64p]
     lib.dehalo_to_affine_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
     lib.dehalo_generator_collapse_device.argtypes = [P, C.c_int, u64p, sz, u64p, u64p, P]
+    lib.dehalo_blind_commitments_device.argtypes = [P, C.c_int, u64p, u64p, sz, u64p, P]
     lib.dehalo_point_sum_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
     lib.dehalo_ntt.argtypes = [P, C.c_int, u64p, u32, u64p]
     lib.dehalo_ntt_device.argtypes = [P, C.c_int, u64p, u32, u64p, sz, P]
@@ -255,6 +256,8 @@ def load_library():
     lib.dehalo_create_proof_circuit.argtypes = [P, C.POINTER(CCircuitInputs), C.POINTER(CSynthesisInfo), C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P]
     lib.dehalo_create_proofs_circuit.argtypes = [C.POINTER(C.c_void_p), u32, C.POINTER(CCircuitInputs), u32, C.POINTER(CRng), C.POINTER(C.c_void_p), sz, C.POINTER(sz)]
     lib.dehalo_prover_last_timings.argtypes = [P, C.POINTER(C.c_double)]
+    lib.dehalo_prover_proof_size.argtypes = [P]
+    lib.dehalo_prover_proof_size.restype = sz
     lib.dehalo_prover_set_shard.argtypes = [P, C.c_uint32, C.c_uint32, GATHER_FN, P]
     lib.dehalo_create_proofs.argtypes = [C.POINTER(C.c_void_p), u32, C.POINTER(C.c_void_p), u32, C.POINTER(CRng), u32, C.POINTER(C.c_void_p), sz, C.POINTER(sz)]
     lib.dehalo_timing_enable.argtypes = [P, C.c_int]
@@ -425,6 +428,10 @@ class Context:
         """parallel_generator_collapse: d_out[i] = g[i] + [challenge] g[length / 2 + i] (challenge = 4 x u64 Montgomery)"""
         ch = np.ascontiguousarray(challenge, dtype=np.uint64).reshape(4)
         self._check(self.lib.dehalo_generator_collapse_device(self.handle, curve, d_affine, length, ch.ctypes.data, d_out, stream or None))
+
+    def blind_commitments_device(self, curve: int, d_jacobian: int, d_blinds: int, count: int, d_w_affine: int, stream: int = 0):
+        """ParamsIPA's blinding term for one batched MSM's results: d_jacobian[i] += [d_blinds[i]] W, in place (all device pointers; one launch)"""
+        self._check(self.lib.dehalo_blind_commitments_device(self.handle, curve, d_jacobian or None, d_blinds or None, count, d_w_affine or None, stream or None))
 
     def to_affine_device(self, curve: int, d_jacobian: int, count: int, d_affine: int, stream: int = 0):
         self._check(self.lib.dehalo_to_affine_device(self.handle, curve, d_jacobian, count, d_affine, stream or None))

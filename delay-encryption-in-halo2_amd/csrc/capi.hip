@@ -670,6 +670,17 @@ int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t*
     return dh_device(ctx, stream, [&](hipStream_t s) { return ops->collapse(ctx, (const affine_t*)d_affine_xy, half, uc.v, (affine_t*)d_out_affine_xy, s); });
 }
 
+int dehalo_blind_commitments_device(dehalo_ctx* ctx, int curve, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, const uint64_t* d_w_affine_xy, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!curve_ops(curve)) return unknown_curve(ctx);
+    const IpaOps* ops = ipa_ops(curve);
+    if (!ops) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "blind_commitments: Pallas and Vesta only (IPA)");
+    if (!d_w_affine_xy || ((!d_jacobian || !d_blinds) && count)) return dh_fail(ctx, DEHALO_ERR_INVALID, "blind_commitments: null argument");
+    if (count >= (1ull << 29)) return dh_fail(ctx, DEHALO_ERR_INVALID, "blind_commitments: too many points");
+    if (count == 0) return 0;
+    return dh_device(ctx, stream, [&](hipStream_t s) { return ops->blind(ctx, (jacobian_t*)d_jacobian, (const fe*)d_blinds, (const affine_t*)d_w_affine_xy, count, s); });
+}
+
 int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_t count, uint64_t* affine_xy) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!jacobian || !affine_xy) && count) return dh_fail(ctx, DEHALO_ERR_INVALID, "to_affine: null argument");

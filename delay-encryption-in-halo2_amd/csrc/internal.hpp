@@ -394,6 +394,8 @@ struct IpaOps {
     int (*collapse)(dehalo_ctx* ctx, const affine_t* d_g, uint64_t half, const uint64_t u_canon[4], affine_t* d_out, hipStream_t s);
     // one round's scalar slots of the [G' | U | W] MSM (dehalo_ipa_open)
     int (*slots)(dehalo_ctx* ctx, const fe* d_evals, const uint64_t coef_l[4], const uint64_t coef_r[4], const fe* d_rands, fe* d_sl, fe* d_sr, hipStream_t s);
+    // pts[i] <- pts[i] + [blinds[i]] W for i < m: Jacobian points as dehalo_msm_device leaves them, blinds standard Montgomery, all on the device
+    int (*blind)(dehalo_ctx* ctx, jacobian_t* d_pts, const fe* d_blinds, const affine_t* d_w, uint64_t m, hipStream_t s);
 };
 const IpaOps& pallas_ipa_ops();
 const IpaOps& vesta_ipa_ops();

@@ -98,6 +98,50 @@ int ipa_collapse_t(dehalo_ctx* ctx, const affine_t* d_g, uint64_t half, const ui
     return 0;
 }
 
+// Blinded commitments: C_i <- C_i + [b_i] W for the m results of one batched MSM (ParamsIPA::commit / commit_lagrange = MSM + [blind] W, [UPSTREAM
+// halo2_proofs/src/poly/ipa/commitment.rs]).  One shared base, a different scalar per point, both on the device: the scalars are a proof's blinds,
+// drawn before the MSM was queued, so the launch follows the MSM on its stream and the points reach the host blinded -- no host wait in between.
+// The points are read and written where the MSM leaves them (Jacobian {x, y, z}, standard Montgomery, 96 B; z = 0: the identity).  Four lanes per
+// point as in the collapse; every quad walks all 255 bits of its own scalar (plain double-and-add: the scalars differ per quad, so the trip count is
+// kept uniform across the wave and only the additions branch, quad-uniformly).  m is a few dozen at most: one workgroup is typical.  No scratch.
+template <class CV>
+__global__ __launch_bounds__(256) void k_ipa_blind(jacobian_t* pts, const fe* __restrict__ blinds, const affine_t* __restrict__ w, u32 m) {
+    typedef f29_lat<typename f29_of<typename CV::Base>::type> F;
+    typedef typename CV::Scalar FS;
+    const u32 i = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+    const u32 role = threadIdx.x & 3;
+    if (i >= m) return;                       // (a quad is live or not as a whole)
+    const fe b = f_from_mont<FS>(f_load(&blinds[i]));      // canonical: bit j of the scalar is bit j & 31 of word j >> 5
+    bool w_id;
+    const aff29 wa = ipa_load_affine<F>(w, w_id);
+    const xyzz29 wp = x29_from_affine<F>(wa, w_id);
+    xyzz29 acc = x29_identity();
+    for (int j = 254; j >= 0; j--) {
+        acc = x29_double_quad<F>(acc);
+        if ((b.v[j >> 5] >> (j & 31)) & 1u) acc = x29_add_quad<F>(acc, wp);
+    }
+    // the MSM's point: {X, Y, Z} with x = X / Z^2, y = Y / Z^3 -> XYZZ (X, Y, Z^2, Z^3)
+    const fe z = f_load(&pts[i].z);
+    xyzz29 c = x29_identity();
+    if (!f_is_zero(z)) {
+        const f29 z9 = f29_from_std<F>(z);
+        c.x = f29_canon<F>(f29_from_std<F>(f_load(&pts[i].x)));
+        c.y = f29_canon<F>(f29_from_std<F>(f_load(&pts[i].y)));
+        c.zz = f29_sqr<F>(z9);
+        c.zzz = f29_mul<F>(c.zz, z9);
+    }
+    acc = x29_add_quad<F>(acc, c);
+    if (role == 0) msm_emit<F>(acc, &pts[i], nullptr);
+}
+
+template <class CV>
+int ipa_blind_t(dehalo_ctx* ctx, jacobian_t* d_pts, const fe* d_blinds, const affine_t* d_w, uint64_t m, hipStream_t s) {
+    if (m == 0) return 0;
+    k_ipa_blind<CV><<<(u32)((4 * m + 255) / 256), 256, 0, s>>>(d_pts, d_blinds, d_w, (u32)m);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 // The scalar slots of one round's batch-2 MSM over [G' | U | W] (dehalo_ipa_open): L's column gets z c_j p'_hi(x3) and l_rand, R's column
 // z c_j x3^half p'_lo(x3) and r_rand.  evals = {p'_lo(x3), p'_hi(x3)}; coef = {z c_j, z c_j x3^half}; rands = {l_rand, r_rand}; all standard
 // Montgomery.  One thread.
@@ -120,5 +164,5 @@ int ipa_slots_t(dehalo_ctx* ctx, const fe* d_evals, const uint64_t coef_l[4], co
 
 template <class CV>
 constexpr IpaOps make_ipa_ops() {
-    return {&ipa_collapse_t<CV>, &ipa_slots_t<CV>};
+    return {&ipa_collapse_t<CV>, &ipa_slots_t<CV>, &ipa_blind_t<CV>};
 }

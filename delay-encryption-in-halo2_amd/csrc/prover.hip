@@ -438,6 +438,11 @@ extern "C" int dehalo_params_scheme(const dehalo_params* p) { return p ? p->sche
 
 namespace {
 
+// Blind::default() of upstream's poly/commitment.rs, the blind of every commitment that is not hiding: the verifying key's fixed and permutation columns and,
+// under IPA, the instance columns.  Taken to be Blind(F::ONE) (no upstream source at hand: parity unpinned).  Keygen and the prover
+// read this constant only; the CPU restatement and the verifier of the tests have its twin (tests/plonk_ipa_reference.py DEFAULT_BLIND).
+constexpr uint64_t IPA_DEFAULT_BLIND = 1;
+
 // commit(poly, blind) of ParamsIPA = MSM(poly, g) + [blind] W, affine into d_pair[0] (d_pair: two points of scratch; [1] receives W): the MSM's affine
 // result and W make a two-point generator vector whose collapse by `blind` is exactly C + [blind] W
 int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, uint64_t* d_pair, hipStream_t s) {
@@ -445,25 +450,16 @@ int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* 
     HIP_TRY(ctx, hipMemcpyAsync(d_pair + 8, p->d_guw.at(2 * p->n + 2), 64, hipMemcpyDeviceToDevice, s));
     return dehalo_generator_collapse_device(ctx, p->curve, d_pair, 2, blind.v, d_pair, s);
 }
-}   // namespace
 
-extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const uint64_t blind_in[4], const uint64_t x3_in[4], dehalo_rng* rng_in,
-                               dehalo_transcript* t) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !p || !d_poly || !blind_in || !x3_in || !t) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: null argument");
-        if (p->scheme != DEHALO_SCHEME_IPA) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: needs ParamsIPA (dehalo_params_ipa_create)");
-        if (t->curve != p->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: transcript and params disagree on the curve");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
+// commitment::create_proof on `rng` as it stands (dehalo_ipa_open: a fresh generator; a whole proof: the proof's generator, right behind f's blind).
+// cha_stream: the ChaCha20 stream of the n-scalar draw under DEHALO_RNG_OS -- within one proof it must differ from the random polynomial's (1).
+int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t) {
         const hipStream_t s = ctx->stream;
         const int fid = curve_scalar_field(p->curve);
         const HostField* f = host_field(fid);
         const IpaOps* ops = ipa_ops(p->curve);
         const size_t n = p->n;
         const uint32_t k = p->k;
-        Fe blind, x3;
-        memcpy(blind.v, blind_in, 32);
-        memcpy(x3.v, x3_in, 32);
         DevMem s_poly, s_adj, pa, pb, guw, sc, ev, rr, pts, uwsc;
         TRY(s_poly.alloc(ctx, n, false));
         TRY(s_adj.alloc(ctx, n, false));
@@ -478,9 +474,7 @@ extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const ui
         // ---- draws, in upstream's order: s_poly (n), s_poly_blind, (l_rand, r_rand) per round.  The n scalars are the proof's large draw and come, as
         // the prover's random polynomial does, from the generator forked at their position: for DEHALO_RNG_OS a ChaCha20 kernel under the call's key
         // (stream 1); for PCG64 / a callback the fork yields exactly the scalars a serial draw would, drawn on the host and uploaded.
-        HostRng rng;
-        TRY(rng.init(rng_in, f));
-        HostRng rng_poly = rng.fork(0, 1);
+        HostRng rng_poly = rng.fork(0, cha_stream);
         rng.skip(n);
         Fe s_blind;
         std::vector<uint64_t> rands(8 * (size_t)k);
@@ -492,7 +486,7 @@ extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const ui
             fe pw;
             for (int i = 0; i < 4; i++) { pw.v[2 * i] = (u32)f->p[i]; pw.v[2 * i + 1] = (u32)(f->p[i] >> 32); }
             const u32 top_mask = f->bits >= 256 ? 0xffffffffu : ((1u << (f->bits - 224)) - 1);
-            k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ck, /* stream of the fork */ 1, pw, top_mask, s_poly.p, n);
+            k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ck, /* stream of the fork */ cha_stream, pw, top_mask, s_poly.p, n);
             HIP_TRY(ctx, hipGetLastError());
         } else {
             std::vector<uint64_t> s_host(4 * n);
@@ -578,6 +572,24 @@ extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const ui
         TRY(dehalo_download(ctx, cur->p, 32, cfin.v));
         t->write_scalar(cfin);
         t->write_scalar(fsum);
+        return 0;
+}
+}   // namespace
+
+extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const uint64_t blind_in[4], const uint64_t x3_in[4], dehalo_rng* rng_in,
+                               dehalo_transcript* t) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !p || !d_poly || !blind_in || !x3_in || !t) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: null argument");
+        if (p->scheme != DEHALO_SCHEME_IPA) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: needs ParamsIPA (dehalo_params_ipa_create)");
+        if (t->curve != p->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: transcript and params disagree on the curve");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        Fe blind, x3;
+        memcpy(blind.v, blind_in, 32);
+        memcpy(x3.v, x3_in, 32);
+        HostRng rng;
+        TRY(rng.init(rng_in, host_field(curve_scalar_field(p->curve))));
+        TRY(ipa_open_body(ctx, p, d_poly, blind, x3, rng, 1, t));
         if (rng_in && rng_in->kind == DEHALO_RNG_PCG64) {      // a PCG64 caller's generator moves past the draws (upstream's `&mut rng`)
             rng_in->pcg_state[0] = (uint64_t)rng.pcg.state;
             rng_in->pcg_state[1] = (uint64_t)(rng.pcg.state >> 64);
@@ -704,10 +716,19 @@ int lagrange_to_all(dehalo_pk* pk, const dehalo_params* params, const fe* values
     dehalo_ctx* ctx = pk->ctx;
     if (!cnt) return 0;
     const HostDomain& d = pk->dom;
-    DevMem aff;
+    DevMem aff, jac, bl;
     if (commitments_host) {
         TRY(aff.alloc(ctx, 2 * cnt, false));
-        TRY(dehalo_msm_device_affine(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
+        if (params->scheme == DEHALO_SCHEME_IPA) {      // commit_lagrange(values, Blind::default()): MSM + [default blind] W
+            const Fe b = pk->f->from_u64(IPA_DEFAULT_BLIND);
+            std::vector<Fe> bh(cnt, b);
+            TRY(jac.alloc(ctx, 3 * cnt, false));
+            TRY(bl.alloc(ctx, cnt, false));
+            TRY(dehalo_upload(ctx, bh.data(), cnt * 32, bl.p));
+            TRY(dehalo_msm_device(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, jac.u64(), nullptr));
+            TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64(), bl.u64(), cnt, params->d_guw.u64(2 * params->n + 2), nullptr));
+            TRY(dehalo_to_affine_device(ctx, params->curve, jac.u64(), cnt, aff.u64(), nullptr));
+        } else TRY(dehalo_msm_device_affine(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
     }
     TRY(dehalo_lagrange_to_coeff_device(ctx, pk->f->id, (const uint64_t*)values, (uint64_t*)polys, d.k, d.omega_inv.v, d.ifft_divisor.v, cnt, nullptr));
     TRY(dehalo_coset_ntt_form_device(ctx, pk->f->id, (const uint64_t*)polys, d.k, (uint64_t*)cosets, d.extended_k, d.ext_omega.v, d.g_coset.v, cnt, DEHALO_FORM_OUT_INTERNAL,
@@ -983,6 +1004,20 @@ struct dehalo_prover {
     std::vector<Group> groups;
     std::vector<const uint64_t*> hp_ptrs;
     size_t hpiece0 = 0, eval_count = 0;
+    // ---- ProverIPA (params of DEHALO_SCHEME_IPA) ----
+    // One blind per commitment, in one device array: [advice A | permuted 2 L | products S + L | random 1 | h pieces | folded h | f | default x max(I, 1)].
+    // Everything up to the pieces is drawn before the first launch and uploaded with the blinding rows; the folded h's blind exists on the host only.
+    bool ipa = false;
+    DevMem ipa_blinds, ipa_q, ipa_wa, ipa_wb, ipa_f, ipa_p;
+    uint32_t bi_adv = 0, bi_perm = 0, bi_prod = 0, bi_rand = 0, bi_h = 0, bi_hfold = 0, bi_f = 0, bi_def = 0, bi_count = 0;
+    // the multiopen's plan [UPSTREAM poly/ipa/multiopen.rs construct_intermediate_sets]: the distinct commitments in order of first appearance, each with its
+    // blind and its point set; the point sets in order of first appearance, each an ascending list of point indices (points numbered by first appearance)
+    struct IpaCommitment { const uint64_t* ptr; uint32_t blind, set; };
+    std::vector<IpaCommitment> ipa_commitments;
+    std::vector<std::vector<uint32_t>> ipa_sets;
+    std::vector<int32_t> ipa_point_rot;      // point index -> rotation
+    std::vector<int64_t> ipa_inst_write;     // the instance evaluations, written first
+    const fe* blind_at(uint32_t i) const { return ipa ? ipa_blinds.at(i) : nullptr; }
     // host staging
     std::vector<uint64_t> blind_host, host_aff, host_jac, host_evals;
     double timings[8] = {};
@@ -1068,9 +1103,10 @@ struct dehalo_prover {
         std::vector<int32_t> rs = {0, 1, -1, -(int32_t)(bf + 1)};
         for (auto& q : cs.advice_q) rs.push_back(q.rotation);
         for (auto& q : cs.fixed_q) rs.push_back(q.rotation);
+        if (ipa) for (auto& q : cs.instance_q) rs.push_back(q.rotation);      // QUERY_INSTANCE = true
         std::sort(rs.begin(), rs.end());
         rs.erase(std::unique(rs.begin(), rs.end()), rs.end());
-        if (rs.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more than four distinct opening rotations");
+        if (rs.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more than four distinct opening rotations");      // (the multi-point evaluation's pass takes four)
         rots = rs;
         const size_t nfix = cs.num_fixed, npc = cs.perm_cols.size();
         hp_ptrs.clear();
@@ -1080,8 +1116,9 @@ struct dehalo_prover {
         for (size_t c = 0; c < nfix; c++) plist.push_back(col_ptr(pk->fixed_polys, c, n));
         for (size_t c = 0; c < npc; c++) plist.push_back(col_ptr(pk->perm_polys, c, n));
         for (auto* p : hp_ptrs) plist.push_back(p);
+        if (ipa) for (uint32_t c = 0; c < I; c++) plist.push_back(col_ptr(instance, c, n));      // opened under IPA only
         const size_t ntot = plist.size();
-        const size_t b_cols = 0, b_fixed = NC, b_sigma = NC + nfix, b_hp = NC + nfix + npc;
+        const size_t b_cols = 0, b_fixed = NC, b_sigma = NC + nfix, b_hp = NC + nfix + npc, b_inst = b_hp + pieces;
         auto ridx = [&](int32_t r) { return (size_t)(std::find(rots.begin(), rots.end(), r) - rots.begin()); };
         auto idx = [&](size_t base, size_t col, int32_t r) { return (int64_t)(ridx(r) * ntot + base + col); };
         const int32_t last = -(int32_t)(bf + 1);
@@ -1136,12 +1173,64 @@ struct dehalo_prover {
             g->ptrs.push_back(q.ptr);
             g->idx.push_back(q.i);
         }
-        if (groups.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more opening points than the prover's buffers hold");
+        if (!ipa && groups.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more opening points than the prover's buffers hold");      // (GWC: qbuf / wbuf)
+        ipa_inst_write.clear();
+        if (ipa) {
+            // the queries in upstream's order (instance first), each with its commitment's blind
+            struct IQ { const uint64_t* ptr; uint32_t blind; int32_t rot; };
+            std::vector<IQ> iq;
+            for (auto& q : cs.instance_q) {
+                iq.push_back({col_ptr(instance, q.index, n), bi_def, q.rotation});
+                ipa_inst_write.push_back(idx(b_inst, q.index, q.rotation));
+            }
+            for (auto& q : cs.advice_q) iq.push_back({cptr(o_adv + q.index), bi_adv + q.index, q.rotation});
+            for (uint32_t s = 0; s < S; s++) {
+                iq.push_back({cptr(o_pz + s), bi_prod + s, 0});
+                iq.push_back({cptr(o_pz + s), bi_prod + s, 1});
+            }
+            for (int s = (int)S - 2; s >= 0; s--) iq.push_back({cptr(o_pz + s), bi_prod + (uint32_t)s, last});
+            for (uint32_t l = 0; l < L; l++) {
+                const size_t zc = o_lz + l, ai = o_perm + 2 * l, ti = o_perm + 2 * l + 1;
+                const uint32_t zb = bi_prod + S + l, ab = bi_perm + 2 * l, tb = bi_perm + 2 * l + 1;
+                iq.push_back({cptr(zc), zb, 0});
+                iq.push_back({cptr(ai), ab, 0});
+                iq.push_back({cptr(ti), tb, 0});
+                iq.push_back({cptr(ai), ab, -1});
+                iq.push_back({cptr(zc), zb, 1});
+            }
+            for (auto& q : cs.fixed_q) iq.push_back({col_ptr(pk->fixed_polys, q.index, n), bi_def, q.rotation});
+            for (size_t j = 0; j < npc; j++) iq.push_back({col_ptr(pk->perm_polys, j, n), bi_def, 0});
+            iq.push_back({hfold.u64(), bi_hfold, 0});
+            iq.push_back({cptr(o_rand), bi_rand, 0});
+            // construct_intermediate_sets
+            ipa_commitments.clear(); ipa_sets.clear(); ipa_point_rot.clear();
+            std::vector<std::vector<uint32_t>> cpoints;
+            for (auto& q : iq) {
+                uint32_t pi = (uint32_t)(std::find(ipa_point_rot.begin(), ipa_point_rot.end(), q.rot) - ipa_point_rot.begin());
+                if (pi == ipa_point_rot.size()) ipa_point_rot.push_back(q.rot);
+                size_t ci = 0;
+                while (ci < ipa_commitments.size() && !(ipa_commitments[ci].ptr == q.ptr && ipa_commitments[ci].blind == q.blind)) ci++;
+                if (ci == ipa_commitments.size()) {
+                    ipa_commitments.push_back({q.ptr, q.blind, 0});
+                    cpoints.push_back({});
+                }
+                cpoints[ci].push_back(pi);
+            }
+            for (size_t ci = 0; ci < ipa_commitments.size(); ci++) {
+                std::vector<uint32_t> ps = cpoints[ci];
+                std::sort(ps.begin(), ps.end());
+                ps.erase(std::unique(ps.begin(), ps.end()), ps.end());
+                const size_t si = (size_t)(std::find(ipa_sets.begin(), ipa_sets.end(), ps) - ipa_sets.begin());
+                if (si == ipa_sets.size()) ipa_sets.push_back(ps);
+                ipa_commitments[ci].set = (uint32_t)si;
+            }
+        }
         hpiece0 = (size_t)idx(b_hp, 0, 0);
         eval_count = rots.size() * ntot;
         eval_wanted.assign(ntot, 0);
         auto want = [&](int64_t i) { if (i >= 0) eval_wanted[(size_t)i % ntot] |= (uint8_t)(1u << ((size_t)i / ntot)); };
         for (int64_t i : write_idx) want(i);
+        for (int64_t i : ipa_inst_write) want(i);
         for (auto& g : groups) for (int64_t i : g.idx) want(i);
         for (uint32_t i = 0; i < pieces; i++) want((int64_t)hpiece0 + i);                // the pieces of h at x: the folded quotient's value
         return 0;
@@ -1149,6 +1238,7 @@ struct dehalo_prover {
 
     int init(dehalo_ctx* c, dehalo_ctx* s, const dehalo_params* pa, const dehalo_pk* key) {
         ctx = c; side = s; params = pa; pk = key; f = key->f;
+        ipa = pa->scheme == DEHALO_SCHEME_IPA;
         const HostCS& cs = pk->cs;
         const HostDomain& d = pk->dom;
         n = d.n; m = d.m; k = d.k; ek = d.extended_k;
@@ -1159,6 +1249,9 @@ struct dehalo_prover {
         NC = A + 2 * L + S + L + 1;
         o_adv = 0; o_perm = A; o_pz = A + 2 * L; o_lz = A + 2 * L + S; o_rand = A + 2 * L + S + L;
         if ((size_t)pieces * n > m) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "quotient does not fit the extended domain");
+        bi_adv = 0; bi_perm = A; bi_prod = A + 2 * L; bi_rand = bi_prod + S + L; bi_h = bi_rand + 1; bi_hfold = bi_h + pieces; bi_f = bi_hfold + 1; bi_def = bi_f + 1;
+        bi_count = bi_def + std::max<uint32_t>(I, 1);
+        if (ipa) TRY(ipa_blinds.alloc(ctx, bi_count));
         TRY(cols.alloc(ctx, (size_t)NC * n));
         if (side) TRY(polys_own.alloc(ctx, (size_t)NC * n));
         polys = side ? polys_own.p : cols.p;
@@ -1173,7 +1266,8 @@ struct dehalo_prover {
         TRY(hfold.alloc(ctx, n));
         TRY(qbuf.alloc(ctx, 4 * n));
         TRY(wbuf.alloc(ctx, 4 * n));
-        TRY(jac.alloc(ctx, 3 * (size_t)std::max<uint32_t>(NC, 8) + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
+        const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, 8), std::max<uint32_t>(I, pieces));      // the most points one phase commits
+        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
         TRY(jac_side.alloc(ctx, 3));
         // blinding values of a proof but the random polynomial, compacted: [advice rows | permuted rows | product rows]
         const size_t rows = n - u;
@@ -1185,13 +1279,22 @@ struct dehalo_prover {
         TRY(find_table_rows());
         TRY(build_product_graphs());
         TRY(opening_plan());
+        if (ipa) {      // the multiopen's buffers, sized from the constraint system: one polynomial per point set, twice more for the division chain
+            const size_t ns = ipa_sets.size();
+            TRY(ipa_q.alloc(ctx, ns * n));
+            TRY(ipa_wa.alloc(ctx, ns * n));
+            TRY(ipa_wb.alloc(ctx, ns * n));
+            TRY(ipa_f.alloc(ctx, n));
+            TRY(ipa_p.alloc(ctx, n));
+            TRY(evals.alloc(ctx, eval_count + 8 + ns));
+        } else
         TRY(evals.alloc(ctx, eval_count + 8));
         for (hipEvent_t* e : {&ev_ready[0], &ev_ready[1], &ev_ready[2], &ev_inst, &ev_side, &ev_helper}) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_TRY(ctx, hipHostMalloc((void**)&pin_helper, 128, hipHostMallocDefault));
         HIP_TRY(ctx, hipHostMalloc((void**)&rand_pin, (size_t)n * 32, hipHostMallocDefault));
         if (side) HIP_TRY(ctx, hipStreamCreateWithFlags(&hs, hipStreamNonBlocking));
-        host_aff.resize(8 * (size_t)std::max<uint32_t>(NC, 8));
-        host_jac.resize(12 * (size_t)std::max<uint32_t>(NC, 8) + 8 + L);
+        host_aff.resize(8 * (size_t)maxpts);
+        host_jac.resize(12 * (size_t)maxpts + 8 + L);
         host_evals.resize(4 * eval_count);
         TRY(dehalo_ctx_synchronize(ctx));
         return 0;
@@ -1288,12 +1391,18 @@ struct dehalo_prover {
 
     // commit `count` columns starting at `src`, read back, normalise, absorb (and append to the proof)
     // `flags` > 0: that many int32 status words sit behind the points in `jac` (deferred lookup permutation) and come back with them; any non-zero one fails the call
-    int commit(dehalo_transcript* tr, const fe* src, size_t count, bool lagrange, const std::function<int()>& before_sync = nullptr, size_t flags = 0) {
+    // `d_blinds` (ParamsIPA; null under KZG): one blind per column on the device -- [blind] W joins each point on the stream, behind the MSM, in one launch
+    // `to_proof` false: absorbed only (common_point: the instance commitments)
+    int commit(dehalo_transcript* tr, const fe* src, size_t count, bool lagrange, const std::function<int()>& before_sync = nullptr, size_t flags = 0,
+               const fe* d_blinds = nullptr, bool to_proof = true) {
         // sharded (dehalo_prover_set_shard): this process's share of the columns only; everything else of the proof is computed by every process
         const bool sharded = shard_world > 1 && shard_gather && count > 1;
         const size_t lo = sharded ? count * shard_rank / shard_world : 0, hi = sharded ? count * (shard_rank + 1) / shard_world : count;
         if (hi > lo)
             TRY(dehalo_msm_device(ctx, lagrange ? params->bases_gl : params->bases_g, (const uint64_t*)(src + lo * n), n, hi - lo, jac.u64() + 12 * lo, nullptr));
+        if (ipa && !d_blinds) return dh_fail(ctx, DEHALO_ERR_INVALID, "commit: a ParamsIPA commitment without its blind");
+        if (ipa && hi > lo)
+            TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64() + 12 * lo, (const uint64_t*)(d_blinds + lo), hi - lo, params->d_guw.u64(2 * params->n + 2), nullptr));
         tk("commit queued");
         if (before_sync) TRY(before_sync());
         tk("side work queued");
@@ -1314,8 +1423,14 @@ struct dehalo_prover {
             tk("points gathered");
         }
         for (size_t i = 0; i < count; i++)
-            if (!tr->write_point(host_aff.data() + 8 * i)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
+            if (!tr->write_point(host_aff.data() + 8 * i, to_proof)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
         return 0;
+    }
+
+    size_t proof_size() const {
+        const size_t points = (size_t)A + 2 * L + S + L + 1 + pieces;
+        if (!ipa) return 32 * (points + groups.size() + write_idx.size());
+        return 32 * (points + 2 + 2 * (size_t)k + ipa_inst_write.size() + write_idx.size() + ipa_sets.size() + 2);
     }
 
     int run(const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng_in,
@@ -1355,9 +1470,10 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     (void)hipSetDevice(ctx->device);
     hipStream_t ms = ctx->stream, ss = side ? side->stream : nullptr;
 
-    // ---- random scalars, in upstream's order: advice blinding rows (column after column), one blind per advice column (unused by KZG), per
-    // lookup (bf + 1 rows permuted input, bf + 1 permuted table, two unused blinds), per grand product (bf rows + one unused blind), the random
-    // polynomial (n), its blind, the h pieces' blinds
+    // ---- random scalars, in upstream's order: advice blinding rows (column after column), one blind per advice column, per lookup (bf + 1 rows
+    // permuted input, bf + 1 permuted table, the two columns' blinds), per grand product (bf rows + its blind), the random polynomial (n), its blind,
+    // the h pieces' blinds and, under IPA, f's blind.  KZG commitments are not hiding: it draws the blinds and drops them.  No draw depends on the
+    // device, so all of them are made here, in that order, and the blinds go up with the blinding rows in one copy.
     HostRng rng;
     TRY(rng.init(rng_in, f));
     const size_t c_adv = (size_t)A * rows, c_advb = A, c_lk = (size_t)L * (2 * rows + 2), c_pr = (size_t)(S + L) * (bf + 1);
@@ -1367,6 +1483,24 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     // thread while the earlier phases run
     HostRng rng_poly = rng.fork(draws_before, 1);
     TRY(rng.scalars(blind_host.data(), draws_before));
+    rng.skip(n);                                             // the random polynomial: rng_poly's
+    std::vector<Fe> late(1 + (size_t)pieces + (ipa ? 1 : 0));      // random_blind, h_blinds, (IPA) f_blind
+    TRY(rng.scalars(late[0].v, late.size()));
+    std::vector<Fe> bl(bi_count, Fe{{0, 0, 0, 0}});         // the proof's blinds, by commitment (dehalo_prover: ipa_blinds)
+    if (ipa) {
+        const Fe* B = (const Fe*)blind_host.data();
+        for (uint32_t i = 0; i < A; i++) bl[bi_adv + i] = B[c_adv + i];
+        for (uint32_t l = 0; l < L; l++) {
+            bl[bi_perm + 2 * l] = B[c_adv + c_advb + (size_t)l * (2 * rows + 2) + 2 * rows];
+            bl[bi_perm + 2 * l + 1] = B[c_adv + c_advb + (size_t)l * (2 * rows + 2) + 2 * rows + 1];
+        }
+        for (uint32_t s2 = 0; s2 < S + L; s2++) bl[bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
+        bl[bi_rand] = late[0];
+        for (uint32_t i = 0; i < pieces; i++) bl[bi_h + i] = late[1 + i];
+        bl[bi_f] = late[1 + pieces];
+        for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
+        TRY(dh_h2d(ctx, ipa_blinds.p, bl.data(), (size_t)bi_count * 32, ctx->stream));      // (waited for with the blinding rows below)
+    }
     std::atomic<int> helper_rc{0};
     uint64_t rand_point[8] = {};
     std::thread helper;
@@ -1377,7 +1511,7 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     // draws and uploads, and the polynomial rides as ONE MORE COLUMN of the products' MSM launch -- a whole sort / accumulate / merge / reduce pipeline per proof
     // less, and none running beside the lookups' phase.  DEHALO_PROVER_RANDOM_SEPARATE=1: the helper commits it with an MSM of its own, as in round 3 (A/B measurements).
     static const bool random_separate_env = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_PROVER_RANDOM_SEPARATE"); return e && e[0] == '1'; }();
-    const bool random_separate = random_separate_env;
+    const bool random_separate = random_separate_env && !ipa;      // (the helper's own MSM would leave the point unblinded)
     auto device_draw = [&](fe* dst, hipStream_t st) -> int {
         ChaKey ck;
         memcpy(ck.k, rng.key, 32);
@@ -1455,10 +1589,8 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
             memcpy(packed.data() + 4 * o, pr + 4 * (size_t)s * (bf + 1), 32 * bf);
             o += bf;
         }
-        if (total) {
-            TRY(dh_h2d(ctx, blind_dev.p, packed.data(), total * 32, ms));
-            HIP_TRY(ctx, hipStreamSynchronize(ms));      // `packed` is a local
-        }
+        if (total) TRY(dh_h2d(ctx, blind_dev.p, packed.data(), total * 32, ms));
+        if (total || ipa) HIP_TRY(ctx, hipStreamSynchronize(ms));      // `packed` and `bl` are locals
     }
     tk("blinds drawn and uploaded");
     const fe* bl_adv = blind_dev.p;
@@ -1473,7 +1605,7 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
         const size_t len = instance_lens ? instance_lens[i] : 0;
         if (len > u) return dh_fail(ctx, DEHALO_ERR_INVALID, "instance column too long");      // Error::InstanceTooLarge
         if (len && (!instances || !instances[i])) return dh_fail(ctx, DEHALO_ERR_INVALID, "null instance column");
-        for (size_t j = 0; j < len; j++) {
+        for (size_t j = 0; j < len && !ipa; j++) {
             Fe v;
             memcpy(v.v, instances[i] + 4 * j, 32);
             tr->common_scalar(v);
@@ -1483,6 +1615,8 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
             HIP_TRY(ctx, hipStreamSynchronize(ms));
         }
     }
+    // IPA (QUERY_INSTANCE = true): commit_lagrange(instance, Blind::default()), absorbed as points
+    if (I && ipa) TRY(commit(tr, instance.p, I, true, nullptr, 0, blind_at(bi_def), false));
     if (I) HIP_TRY(ctx, hipMemcpyAsync(instance_values.p, instance.p, (size_t)I * n * 32, hipMemcpyDeviceToDevice, ms));
     const uint32_t nco = NC - 1;
     if (I && side) HIP_TRY(ctx, hipEventRecord(ev_inst, ms));
@@ -1543,7 +1677,7 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
         if (!synth_in) helper = std::thread(helper_body);      // the host is idle from here to the read-back
         return 0;
     };
-    TRY(commit(tr, cols.at((size_t)o_adv * n), A, true, after_advice_queued));
+    TRY(commit(tr, cols.at((size_t)o_adv * n), A, true, after_advice_queued, 0, blind_at(bi_adv)));
     mark(0);
     const Fe theta = tr->squeeze();
     tk("theta");
@@ -1586,7 +1720,7 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
                                                            reinterpret_cast<int32_t*>(jac.u64() + 12 * 2 * (size_t)L), nullptr));
         tk("permute queued");
         if (side) HIP_TRY(ctx, hipEventRecord(ev_ready[1], ms));
-        TRY(commit(tr, cols.at((size_t)o_perm * n), 2 * L, true, side ? std::function<int()>([&]() { return side_ntt(o_perm, 2 * L, ev_ready[1]); }) : nullptr, L));
+        TRY(commit(tr, cols.at((size_t)o_perm * n), 2 * L, true, side ? std::function<int()>([&]() { return side_ntt(o_perm, 2 * L, ev_ready[1]); }) : nullptr, L, blind_at(bi_perm)));
     }
     mark(1);
     const Fe beta = tr->squeeze();
@@ -1614,7 +1748,7 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
         return 0;
     };
     if (S + L == 0 && extra) {
-        TRY(commit(tr, cols.at((size_t)o_rand * n), 1, true, [&]() { return restore_random(); }));
+        TRY(commit(tr, cols.at((size_t)o_rand * n), 1, true, [&]() { return restore_random(); }, 0, blind_at(bi_rand)));
     }
     if (S + L) {
         std::vector<Fe> chal(std::max<uint32_t>(npc, 1));
@@ -1668,7 +1802,7 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
             }
             return 0;
         };
-        TRY(commit(tr, cols.at((size_t)o_pz * n), S + L + extra, true, std::function<int()>(after_products_queued)));
+        TRY(commit(tr, cols.at((size_t)o_pz * n), S + L + extra, true, std::function<int()>(after_products_queued), 0, blind_at(bi_prod)));
     }
     mark(2);
 
@@ -1678,11 +1812,6 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     tk("helper joined");
     if (trace) fprintf(stderr, "  helper: draw %.3f, upload + commit queued %.3f, point on host %.3f ms after its start\n", helper_ms[0], helper_ms[1], helper_ms[2]);
     if (helper_rc.load()) return helper_rc.load();
-    rng.skip(n);
-    {
-        uint64_t blind[4];
-        TRY(rng.scalars(blind, 1));      // random_blind (unused by KZG)
-    }
     if (!random_separate) {
         // (written with the products' commitments above)
     } else if (side) {
@@ -1759,12 +1888,8 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     }
     TRY(dehalo_scale_device(ctx, fid, h.u64(), m, (const uint64_t*)d.t_inv.data(), (uint32_t)d.t_inv.size(), nullptr, nullptr));      // divide_by_vanishing_poly
     TRY(dehalo_coset_intt_form_device(ctx, fid, h.u64(), ek, d.ext_omega_inv.v, d.ext_ifft_divisor.v, d.g_coset.v, 1, DEHALO_FORM_IN_INTERNAL, nullptr));
-    {
-        std::vector<uint64_t> hb(4 * (size_t)pieces);
-        TRY(rng.scalars(hb.data(), pieces));      // h_blinds (unused by KZG)
-    }
     tk("quotient queued");
-    TRY(commit(tr, h.p, pieces, false));
+    TRY(commit(tr, h.p, pieces, false, nullptr, 0, blind_at(bi_h)));
     mark(4);
     const Fe x = tr->squeeze();
     const Fe xn = f->pow_u64(x, (uint64_t)n);
@@ -1789,8 +1914,96 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
     const Fe* E = (const Fe*)host_evals.data();
     Fe hfold_eval = zero;
     for (uint32_t i = 0; i < pieces; i++) hfold_eval = f->add(hfold_eval, f->mul(xs[i], E[hpiece0 + i]));
+    for (int64_t i : ipa_inst_write) tr->write_scalar(E[i]);      // (IPA: the instance evaluations come first)
     for (int64_t i : write_idx) tr->write_scalar(E[i]);
     mark(5);
+    if (ipa) {
+        // ---- ProverIPA::create_proof [UPSTREAM poly/ipa/multiopen/prover.rs]
+        const Fe x1 = tr->squeeze();
+        const Fe x2 = tr->squeeze();
+        bl[bi_hfold] = zero;                                   // h's blinds fold with x^n as its pieces do
+        for (uint32_t i = 0; i < pieces; i++) bl[bi_hfold] = f->add(bl[bi_hfold], f->mul(xs[i], bl[bi_h + i]));
+        const size_t ns = ipa_sets.size();
+        // q_i = the set's polynomials folded with x_1 in commitment order (q <- x_1 q + poly), the blinds likewise
+        std::vector<Fe> qblind(ns, zero);
+        size_t depth = 0;
+        for (size_t si = 0; si < ns; si++) {
+            std::vector<const uint64_t*> ptrs;
+            std::vector<uint32_t> bi;
+            for (auto& cm : ipa_commitments)
+                if (cm.set == si) { ptrs.push_back(cm.ptr); bi.push_back(cm.blind); }
+            std::vector<Fe> coefs(ptrs.size());
+            Fe pw = f->one;
+            for (size_t j = ptrs.size(); j-- > 0;) {
+                coefs[j] = pw;
+                qblind[si] = f->add(qblind[si], f->mul(pw, bl[bi[j]]));
+                pw = f->mul(pw, x1);
+            }
+            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ptrs.size(), n, ipa_q.u64(si * n), nullptr, nullptr));
+            depth = std::max(depth, ipa_sets[si].size());
+        }
+        // each q_i divided by (X - point) for every point of its set in turn, remainders dropped: one batched launch per division depth over the sets
+        // that still have a point left (a division writes n - 1 coefficients: the top one of both buffers stays zero)
+        HIP_TRY(ctx, hipMemsetAsync(ipa_wa.p, 0, ns * n * 32, ms));
+        HIP_TRY(ctx, hipMemsetAsync(ipa_wb.p, 0, ns * n * 32, ms));
+        std::vector<const uint64_t*> cur(ns);
+        for (size_t si = 0; si < ns; si++) cur[si] = ipa_q.u64(si * n);
+        for (size_t dd = 0; dd < depth; dd++) {
+            std::vector<const uint64_t*> ins;
+            std::vector<uint64_t*> outs;
+            std::vector<Fe> pts;
+            std::vector<size_t> which;
+            for (size_t si = 0; si < ns; si++)
+                if (ipa_sets[si].size() > dd) {
+                    ins.push_back(cur[si]);
+                    outs.push_back((dd & 1 ? ipa_wb : ipa_wa).u64(si * n));
+                    pts.push_back(d.rotate_omega(x, ipa_point_rot[ipa_sets[si][dd]]));
+                    which.push_back(si);
+                }
+            for (size_t first = 0; first < ins.size(); first += 8)      // (the batched division takes eight at a time)
+                TRY(dehalo_kate_division_batch_device(ctx, fid, ins.data() + first, n, (const uint64_t*)(pts.data() + first), outs.data() + first,
+                                                      std::min<size_t>(8, ins.size() - first), nullptr));
+            for (size_t j = 0; j < which.size(); j++) cur[which[j]] = outs[j];
+        }
+        // f = the quotients folded with x_2; commit(f, f_blind)
+        {
+            std::vector<Fe> coefs(ns);
+            Fe pw = f->one;
+            for (size_t j = ns; j-- > 0;) { coefs[j] = pw; pw = f->mul(pw, x2); }
+            TRY(dehalo_lincomb_device(ctx, fid, cur.data(), (const uint64_t*)coefs.data(), ns, n, ipa_f.u64(), nullptr, nullptr));
+        }
+        TRY(commit(tr, ipa_f.p, 1, false, nullptr, 0, blind_at(bi_f)));
+        const Fe x3 = tr->squeeze();
+        // q_i(x_3) for every set: one evaluation call, one download
+        fe* qe = evals.at(eval_count + 8);
+        TRY(dehalo_eval_polynomial_device(ctx, fid, ipa_q.u64(), n, n, ns, x3.v, (uint64_t*)qe, nullptr));
+        std::vector<Fe> qev(ns);
+        TRY(dehalo_download(ctx, qe, ns * 32, qev.data()));
+        for (size_t si = 0; si < ns; si++) tr->write_scalar(qev[si]);
+        const Fe x4 = tr->squeeze();
+        // p = f, then p <- x_4 p + q_i over the sets; the blind likewise
+        Fe pblind = bl[bi_f];
+        {
+            std::vector<const uint64_t*> ptrs = {ipa_f.u64()};
+            for (size_t si = 0; si < ns; si++) ptrs.push_back(ipa_q.u64(si * n));
+            std::vector<Fe> coefs(ns + 1);
+            Fe pw = f->one;
+            for (size_t j = ns + 1; j-- > 0;) { coefs[j] = pw; pw = f->mul(pw, x4); }
+            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ns + 1, n, ipa_p.u64(), nullptr, nullptr));
+            for (size_t si = 0; si < ns; si++) pblind = f->add(f->mul(pblind, x4), qblind[si]);
+        }
+        tk("multiopen done");
+        // commitment::create_proof on p at x_3: same transcript, same generator (right behind f's blind)
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        TRY(ipa_open_body(ctx, params, ipa_p.u64(), pblind, x3, rng, 2, tr));
+        mark(6);
+        timings[7] = ms_since(t_start);
+        if (rng_in && rng_in->kind == DEHALO_RNG_PCG64) {
+            rng_in->pcg_state[0] = (uint64_t)rng.pcg.state;
+            rng_in->pcg_state[1] = (uint64_t)(rng.pcg.state >> 64);
+        }
+        return 0;
+    }
 
     // ---- ProverGWC::create_proof: one witness polynomial per distinct point, in order of first appearance
     const Fe v = tr->squeeze();
@@ -1837,7 +2050,6 @@ extern "C" int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !params || !pk || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: null argument");
         if (params->k != pk->k || params->curve != pk->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: params and proving key disagree on k / curve");
-        if (params->scheme != DEHALO_SCHEME_KZG) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "prover_create: whole proofs are KZG / GWC only (ParamsIPA: dehalo_ipa_open)");
         if (side_ctx && (side_ctx == ctx || side_ctx->device != ctx->device)) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: the side context must be another context of the same device");
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
@@ -1881,6 +2093,8 @@ extern "C" int dehalo_prover_set_shard(dehalo_prover* p, uint32_t rank, uint32_t
         return 0;
     });
 }
+
+extern "C" size_t dehalo_prover_proof_size(const dehalo_prover* p) { return p ? p->proof_size() : 0; }
 
 extern "C" int dehalo_prover_last_timings(const dehalo_prover* p, double out[8]) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {

@@ -148,8 +148,8 @@ class ParamsKZG:
 
 class ParamsIPA(ParamsKZG):
     """dehalo_params over IPACommitmentScheme<C> (Pallas / Vesta): g, g_lagrange, w, u handed over as the caller's ParamsIPA holds them
-    (dehalo_params_ipa_create).  ProvingKey.keygen takes it as it takes ParamsKZG; whole proofs are KZG only -- open one polynomial with
-    `open`."""
+    (dehalo_params_ipa_create).  ProvingKey.keygen and Prover take it as they take ParamsKZG: Prover(params, pk).create_proof then writes a ProverIPA
+    proof (blinded commitments, committed instance columns, the multiopen and the opening argument).  `open` opens one polynomial."""
 
     @classmethod
     def create(cls, ctx: Context, curve: CurveSpec, k: int, g, g_lagrange, w, u) -> "ParamsIPA":
@@ -397,6 +397,10 @@ class Prover:
             raise DehaloError(rc, lib.dehalo_last_error(self.ctx.handle).decode())
         rng_writeback(rng, r)
         return tr, _info_dict(info)
+
+    def proof_size(self) -> int:
+        """Byte length of one proof for this prover's params (KZG / GWC or IPA), instance commitments and evaluations included."""
+        return int(load_library().dehalo_prover_proof_size(self.handle))
 
     def last_timings(self) -> dict:
         out = (C.c_double * 8)()

@@ -160,6 +160,13 @@ int dehalo_to_affine_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobi
  * overlap it in no other way.  Pallas and Vesta only (DEHALO_ERR_UNSUPPORTED otherwise).  Asynchronous on the stream; no workspace. */
 int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t len, const uint64_t challenge[4], uint64_t* d_out_affine_xy,
                                      void* stream);
+/* The blinding term of ParamsIPA::commit / commit_lagrange [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs: MSM(poly, g) + [blind] W] for the results of
+ * one batched MSM: d_jacobian[i] <- d_jacobian[i] + [d_blinds[i]] W for i < count, in place.  Points as dehalo_msm_device leaves them (Jacobian, 96 B,
+ * z = 0: the identity), blinds one scalar per point (4 x u64 Montgomery), W one affine point {x, y} (64 B, standard Montgomery): all device memory.
+ * One launch for the whole batch, queued behind the MSM on the stream: no host wait between the two.  An identity point gives [b] W, a zero blind
+ * leaves the point as it is.  count < 2^29.  Pallas and Vesta only (DEHALO_ERR_UNSUPPORTED otherwise).  Asynchronous on the stream; no workspace. */
+int dehalo_blind_commitments_device(dehalo_ctx* ctx, int curve, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, const uint64_t* d_w_affine_xy,
+                                    void* stream);
 
 /* ---- NTT == halo2_proofs::arithmetic::best_fft(a, omega, log_n) ---------------------------
  * [halo2_proofs/src/arithmetic.rs].  In place, natural order in and out,
@@ -426,11 +433,12 @@ int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s
 /* ParamsIPA<C> [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs] from its parts, as the caller's ParamsIPA holds them: g / g_lagrange = 2^k affine
  * points each, w and u one point each ({x, y} Montgomery, 64 B, the layout of dehalo_params_create).  Pallas or Vesta (IPACommitmentScheme<EqAffine>
  * is Vesta; its scalar field is pasta::Fp); any other curve is DEHALO_ERR_UNSUPPORTED.  g and g_lagrange are registered with precomputed tables
- * as for KZG, so dehalo_keygen and dehalo_params_commit_device work unchanged (vk commitments are commit_lagrange with Blind::default(), a zero
- * blind: no [blind] W term).  g, u and w also stay on the device as plain points for the opening argument (dehalo_ipa_open).
+ * as for KZG, so dehalo_keygen works on them: under these params the verifying key's fixed and permutation commitments are commit_lagrange with
+ * Blind::default(), taken to be Blind(F::ONE) -- MSM + W (parity with upstream unpinned); under KZG params keygen is unchanged.
+ * dehalo_params_commit_device is the bare MSM under either scheme.  g, u and w also stay on the device as plain points for the opening argument.
  * Not provided: ParamsIPA::new (hash-to-curve of "Halo2-Parameters"), ParamsIPA::{read, write} (dehalo_params_size is 0 and dehalo_params_write
  * DEHALO_ERR_UNSUPPORTED for these params) and g_to_lagrange (a group FFT): the caller passes params.g, params.g_lagrange, params.w and params.u.
- * Whole proofs over IPA (ProverIPA's multiopen) are not provided either: dehalo_prover_create with these params is DEHALO_ERR_UNSUPPORTED. */
+ * Whole proofs: dehalo_prover_create / dehalo_create_proof with these params write a ProverIPA proof (below). */
 int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
                              dehalo_params** out);
 /* The commitment scheme of params: DEHALO_SCHEME_KZG (dehalo_params_create / _setup / _read) or DEHALO_SCHEME_IPA (dehalo_params_ipa_create); < 0 for null. */
@@ -532,15 +540,24 @@ int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t
 /* A prover = the device buffers of one proof for a given key, on `ctx` (stream + workspace).  `side_ctx` (may be NULL): a second context of
  * the same device; work no transcript challenge waits for (lagrange_to_coeff / coeff_to_extended of a phase's columns, the random
  * polynomial's commitment, the gate and table-value passes of evaluate_h) is queued there and runs beside the commitment phases.
- * Several provers over one key, each on its own context(s), may run concurrently from different threads (batch proving). */
+ * Several provers over one key, each on its own context(s), may run concurrently from different threads (batch proving).
+ * `params` decides the scheme: ParamsKZG -> ProverGWC, ParamsIPA (Pallas / Vesta) -> ProverIPA.  DEHALO_ERR_UNSUPPORTED: more than four distinct
+ * opening rotations (either scheme), more than four opening points (KZG). */
 int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out);
 int dehalo_prover_release(dehalo_prover* prover);
+/* Byte length of one proof of this prover (its params' scheme, instance commitments and evaluations included); 0 for null.
+ *   KZG / GWC: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + opening points) + 32 x evaluations
+ *   IPA: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + 1 (f) + 1 (S) + 2 k) + 32 x (instance queries + evaluations + point sets + 2) */
+size_t dehalo_prover_proof_size(const dehalo_prover* prover);
 /* create_proof: one circuit, its instance columns, the caller's rng and transcript.
  *   advice     num_advice x 2^k x 4 u64 Montgomery (rows >= usable are overwritten by blinding), host memory, or device memory when
  *              DEHALO_PROOF_ADVICE_ON_DEVICE
  *   instances  num_instance_columns arrays of instance_lens[i] scalars (Montgomery); the reference passes none (&[&[&[]]])
  * Errors follow upstream's: DEHALO_ERR_INVALID for instances.len() != num_instance_columns / an instance column longer than the usable
- * rows / a commitment at infinity; DEHALO_ERR_NOT_IN_TABLE when a lookup input is missing from its table. */
+ * rows / a commitment at infinity; DEHALO_ERR_NOT_IN_TABLE when a lookup input is missing from its table.
+ * Under ParamsIPA (create_proof::<IPACommitmentScheme<_>, ProverIPA<_>, ..>) every commitment carries its blind ([blind] W, dehalo_blind_commitments_device: one
+ * launch per phase), the instance columns are committed with Blind::default() and absorbed as points, their evaluations are written first, and the proof ends
+ * with ProverIPA's multiopen (x_1, x_2, f, x_3, the q evaluations, x_4) and the opening argument of dehalo_ipa_open on the same transcript and generator. */
 enum { DEHALO_PROOF_ADVICE_ON_DEVICE = 1, DEHALO_PROOF_ADVICE_CANONICAL = 2 /* plain integers < p: converted on the device */ };
 int dehalo_create_proof(dehalo_prover* prover, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                         dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
