@@ -303,10 +303,15 @@ def test_msm_every_merge_class(pkg, co, ctx):
             column(1000, [40] * 300 + [7] * 500), column(5000, [130] * 100), column(9000, [2] * 9000), column(1, [n]),
             co.fill_scalars(spec.scalar.id, "uniform", n, 5)]
     want = [co.to_affine(spec.id, co.best_multiexp(spec.id, c, bases, 8)) for c in cols]
-    for c, w in zip(cols, want):
+    for j, (c, w) in enumerate(zip(cols, want)):
         assert np.array_equal(ctx.to_affine(spec.id, ctx.msm(h, c))[0], w)
+        if j == 0:      # the column of 1 .. 6000 points a bucket: every class had buckets (2-8 partial sums | 9-64 | 65-512 | more than 512)
+            sh = ctx.msm_last_shape()
+            assert sh["merge_light"] and sh["merge_32"] and sh["merge_wave"] and sh["merge_block"], sh
     assert len(cols) * (1 << (h.window_bits - 1)) > 65536 or h.window_bits < 15     # the batch is past the quad-mode bound at c = 15
     got = ctx.to_affine(spec.id, ctx.msm_batch(h, cols))
+    sh = ctx.msm_last_shape()
+    assert sh["merge_light"] and sh["merge_32"] and sh["merge_wave"] and sh["merge_block"], sh
     for g, w in zip(got, want):
         assert np.array_equal(g, w)
     h.release()
