@@ -1,7 +1,7 @@
 //! The one-call integration: `plonk::create_proof::<KZGCommitmentScheme<Bn256>, ProverGWC<_>, Challenge255<_>, _, Blake2bWrite<_, _, _>, _>` behind the C ABI
 //! [UPSTREAM halo2_proofs/src/plonk/prover.rs @ v2023_04_20; the reference's timed call: benches/delay_enc.rs:123-131, benches/mod_pow.rs:201-209,
 //! benches/pose_enc.rs:127-135].  From the first advice commitment to the last opening -- phases, Blake2b transcript, blinding, every launch -- in C++
-//! (csrc/prover.hip); this module builds the objects and passes pointers, the sequence of `host/example.cpp` (which `tests/test_native.py` runs).
+//! (csrc/params.hip, keygen.hip, prover.hip); this module builds the objects and passes pointers, the sequence of `host/example.cpp` (which `tests/test_native.py` runs).
 //!
 //! The patched `plonk/prover.rs` keeps its signature; its body becomes
 //!

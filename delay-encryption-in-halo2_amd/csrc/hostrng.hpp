@@ -2,7 +2,7 @@
 // `rng: R` argument of create_proof [UPSTREAM halo2_proofs/src/plonk/prover.rs; the reference passes OsRng, benches/delay_enc.rs:128].
 //   DEHALO_RNG_OS        the default: 32 bytes of operating-system entropy (getrandom) key a ChaCha20 stream per call; every scalar is
 //                        256 stream bits masked to the modulus' bit length and rejected when >= p -- uniform over the field (the blinding
-//                        rows on the host; the random polynomial's n scalars by a ChaCha20 KERNEL under the same key, prover.hip);
+//                        rows on the host; the random polynomial's n scalars by a ChaCha20 KERNEL under the same key, params.hip);
 //   DEHALO_RNG_PCG64     TESTS / BENCHMARKS ONLY (not a CSPRNG): numpy's PCG64 stream from a given state, four 64-bit outputs per scalar,
 //                        top word masked to 61 bits -- the stream dehalo2_amd.prover.SeededRng and the CPU restatement consume, so that
 //                        proofs can be compared byte for byte;
@@ -126,6 +126,11 @@ struct HostRng {
     void skip(uint64_t count) {
         position += count;
         if (kind == DEHALO_RNG_PCG64) pcg.advance((u128)4 * count);
+    }
+    void write_back(dehalo_rng* r) const {      // a PCG64 caller's generator moves past the call's draws (upstream's `&mut rng`)
+        if (!r || r->kind != DEHALO_RNG_PCG64) return;
+        r->pcg_state[0] = (uint64_t)pcg.state;
+        r->pcg_state[1] = (uint64_t)(pcg.state >> 64);
     }
     uint64_t cc64() {
         if (ccpos >= 16) {

@@ -1,0 +1,367 @@
+// keygen.hip -- the keys behind the C ABI: keygen_vk / keygen_pk, ProvingKey / VerifyingKey RawBytes and the verifying key's transcript representation
+// [UPSTREAM halo2_proofs @ v2023_04_20: plonk/keygen.rs, plonk.rs, plonk/permutation/keygen.rs] -- the calls the reference makes at
+// benches/delay_enc.rs:84-115 (keys).
+// C entry points run under dh_guard and the column work goes through the library's device entry points, as in prover.hip; the one kernel here is a gather.
+#include <memory>
+
+#include "whole_call.hpp"
+
+namespace {
+
+__global__ void k_gather_elems(const fe* __restrict__ src, const uint64_t* __restrict__ idx, fe* __restrict__ dst, uint64_t count) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) dst[i] = src[idx[i]];
+}
+
+void put_u32_be(uint8_t* o, uint32_t v) { for (int i = 0; i < 4; i++) o[i] = (uint8_t)(v >> (8 * (3 - i))); }
+uint32_t get_u32_be(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+
+int pk_common_init(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* csd, uint32_t k, dehalo_pk* pk) {
+    pk->ctx = ctx;
+    pk->curve = curve;
+    pk->k = k;
+    pk->f = host_field(curve_scalar_field(curve));
+    if (!pk->f) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve");
+    const std::string err = pk->cs.load(csd);
+    if (!err.empty()) return dh_fail(ctx, DEHALO_ERR_INVALID, err);
+    if (k > 28 || !pk->dom.init(pk->f, pk->cs.degree(), k)) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "extended_k exceeds the field's two-adicity");
+    if (pk->dom.n < (size_t)pk->cs.blinding_factors() + 3) return dh_fail(ctx, DEHALO_ERR_INVALID, "not enough rows available");      // Error::NotEnoughRowsAvailable
+    return 0;
+}
+
+// values (cnt x n, standard form, device) -> polys (lagrange_to_coeff), cosets (coeff_to_extended, internal form), commitments to the host
+int lagrange_to_all(dehalo_pk* pk, const dehalo_params* params, const fe* values, size_t cnt, fe* polys, fe* cosets, uint64_t* commitments_host) {
+    dehalo_ctx* ctx = pk->ctx;
+    if (!cnt) return 0;
+    const HostDomain& d = pk->dom;
+    DevMem aff, jac, bl;
+    if (commitments_host) {
+        TRY(aff.alloc(ctx, 2 * cnt, false));
+        if (params->scheme == DEHALO_SCHEME_IPA) {      // commit_lagrange(values, Blind::default()): MSM + [default blind] W
+            const Fe b = pk->f->from_u64(IPA_DEFAULT_BLIND);
+            std::vector<Fe> bh(cnt, b);
+            TRY(jac.alloc(ctx, 3 * cnt, false));
+            TRY(bl.alloc(ctx, cnt, false));
+            TRY(dehalo_upload(ctx, bh.data(), cnt * 32, bl.p));
+            TRY(dehalo_msm_device(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, jac.u64(), nullptr));
+            TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64(), bl.u64(), cnt, params->d_guw.u64(2 * params->n + 2), nullptr));
+            TRY(dehalo_to_affine_device(ctx, params->curve, jac.u64(), cnt, aff.u64(), nullptr));
+        } else TRY(dehalo_msm_device_affine(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
+    }
+    TRY(dehalo_lagrange_to_coeff_device(ctx, pk->f->id, (const uint64_t*)values, (uint64_t*)polys, d.k, d.omega_inv.v, d.ifft_divisor.v, cnt, nullptr));
+    TRY(dehalo_coset_ntt_form_device(ctx, pk->f->id, (const uint64_t*)polys, d.k, (uint64_t*)cosets, d.extended_k, d.ext_omega.v, d.g_coset.v, cnt, DEHALO_FORM_OUT_INTERNAL,
+                                     nullptr));
+    if (commitments_host) TRY(dehalo_download(ctx, aff.p, cnt * 64, commitments_host));
+    else TRY(dehalo_ctx_synchronize(ctx));
+    return 0;
+}
+
+}   // namespace
+
+dehalo_pk::~dehalo_pk() {
+    if (custom_gates) (void)dehalo_graph_release(ctx, custom_gates);
+    for (auto* g : lookup_graphs) (void)dehalo_graph_release(ctx, g);
+    for (auto& g : compress_graphs) {
+        (void)dehalo_graph_release(ctx, g.first);
+        (void)dehalo_graph_release(ctx, g.second);
+    }
+}
+size_t dehalo_pk::vk_size() const { return 8 + 64 * (size_t)cs.num_fixed + 64 * cs.perm_cols.size() + (size_t)num_selectors * ((dom.n + 7) / 8); }
+void dehalo_pk::vk_write(uint8_t* o) const {
+    put_u32_be(o, k);
+    put_u32_be(o + 4, cs.num_fixed);
+    o += 8;
+    memcpy(o, fixed_commitments.data(), 64 * (size_t)cs.num_fixed);
+    o += 64 * (size_t)cs.num_fixed;
+    memcpy(o, perm_commitments.data(), 64 * cs.perm_cols.size());
+    o += 64 * cs.perm_cols.size();
+    for (auto& s : selectors) {
+        memcpy(o, s.data(), s.size());
+        o += s.size();
+    }
+}
+size_t dehalo_pk::size() const {
+    const size_t n = dom.n, m = dom.m, nf = cs.num_fixed, npc = cs.perm_cols.size();
+    auto poly = [](size_t ln) { return 4 + 32 * ln; };
+    auto sl = [&](size_t cnt, size_t ln) { return 4 + cnt * poly(ln); };
+    return vk_size() + 3 * poly(m) + 2 * sl(nf, n) + sl(nf, m) + 2 * sl(npc, n) + sl(npc, m);
+}
+void dehalo_pk::default_transcript_repr() {
+    std::vector<uint8_t> body(vk_size());
+    vk_write(body.data());
+    cs.encode(body);
+    Blake2b h;
+    h.init(64, "Halo2-Verify-Key");
+    const uint64_t len = body.size();
+    h.update(&len, 8);
+    h.update(body.data(), body.size());
+    uint8_t d[64];
+    h.digest(d);
+    transcript_repr = f->from_u512(d);
+}
+int dehalo_pk::compile_graphs() {
+    TRY(custom_gates_graph(cs, f).compile(ctx, &custom_gates));
+    for (auto& lk : cs.lookups) {
+        dehalo_graph *g = nullptr, *gi = nullptr, *gt = nullptr;
+        TRY(lookup_table_value_graph(cs, lk, f).compile(ctx, &g));
+        lookup_graphs.push_back(g);
+        TRY(compress_graph(cs, lk.inputs, f).compile(ctx, &gi));
+        const int rc = compress_graph(cs, lk.tables, f).compile(ctx, &gt);
+        compress_graphs.push_back({gi, gt});
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// (n, 4) device column of omega^i: the forward NTT of the unit vector e_1
+int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col) {
+    HIP_TRY(ctx, hipMemsetAsync(col, 0, d.n * sizeof(fe), ctx->stream));
+    TRY(dh_h2d(ctx, col + (d.n > 1 ? 1 : 0), d.f->one.v, 32, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (the source is a host object: copied before returning)
+    if (d.n > 1) TRY(dehalo_ntt_device(ctx, d.f->id, (uint64_t*)col, d.k, d.omega.v, 1, nullptr));
+    return 0;
+}
+
+extern "C" int dehalo_keygen(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_constraint_system* csd, const uint64_t* fixed, const uint64_t* mapping,
+                             const uint8_t* const* selectors, uint32_t num_selectors, uint32_t flags, dehalo_pk** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !params || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null argument");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
+        TRY(pk_common_init(ctx, params->curve, csd, params->k, pk.get()));
+        const HostCS& cs = pk->cs;
+        const HostDomain& d = pk->dom;
+        const size_t n = d.n, m = d.m, nf = cs.num_fixed, npc = cs.perm_cols.size();
+        if ((nf && !fixed) || (npc && !mapping) || (num_selectors && !selectors)) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null column data");
+        const int fid = pk->f->id;
+        // fixed columns
+        TRY(pk->fixed_values.alloc(ctx, nf * n, false));
+        TRY(pk->fixed_polys.alloc(ctx, nf * n, false));
+        TRY(pk->fixed_cosets.alloc(ctx, nf * m, false));
+        pk->fixed_commitments.assign(8 * nf, 0);
+        if (nf) {
+            HostPin pin_fixed(fixed, nf * n * 32);
+            TRY(dh_h2d(ctx, pk->fixed_values.p, fixed, nf * n * 32, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (flags & DEHALO_KEYGEN_FIXED_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, pk->fixed_values.u64(), nullptr, pk->fixed_values.u64(), nf * n, nullptr));
+            TRY(lagrange_to_all(pk.get(), params, pk->fixed_values.p, nf, pk->fixed_polys.p, pk->fixed_cosets.p, pk->fixed_commitments.data()));
+        }
+        // permutation: sigma_j(omega^i) = delta^(column of the mapped cell) * omega^(its row)  [permutation::keygen::Assembly::build_pk]
+        TRY(pk->perm_values.alloc(ctx, npc * n, false));
+        TRY(pk->perm_polys.alloc(ctx, npc * n, false));
+        TRY(pk->perm_cosets.alloc(ctx, npc * m, false));
+        pk->perm_commitments.assign(8 * npc, 0);
+        if (npc) {
+            for (size_t i = 0; i < npc * n; i++)
+                if (mapping[i] >= npc * n) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: permutation mapping points outside the permutation's columns");
+            DevMem ident, w;
+            uint64_t* d_map = nullptr;
+            TRY(ident.alloc(ctx, npc * n, false));
+            TRY(w.alloc(ctx, n, false));
+            TRY(omega_powers(ctx, d, w.p));
+            Fe dj = pk->f->one;
+            for (size_t j = 0; j < npc; j++) {
+                HIP_TRY(ctx, hipMemcpyAsync(ident.at(j * n), w.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
+                if (j) TRY(dehalo_scale_device(ctx, fid, ident.u64(j * n), n, dj.v, 1, nullptr, nullptr));
+                dj = pk->f->mul(dj, pk->f->delta);
+            }
+            HIP_TRY(ctx, hipMalloc((void**)&d_map, npc * n * 8));
+            HostPin pin_map(mapping, npc * n * 8);
+            hipError_t e = dh_h2d(ctx, d_map, mapping, npc * n * 8, ctx->stream) == 0 ? hipSuccess : hipErrorUnknown;
+            if (e == hipSuccess) {
+                k_gather_elems<<<(unsigned)((npc * n + 255) / 256), 256, 0, ctx->stream>>>(ident.p, d_map, pk->perm_values.p, npc * n);
+                e = hipStreamSynchronize(ctx->stream);
+            }
+            (void)hipFree(d_map);
+            HIP_TRY(ctx, e);
+            TRY(lagrange_to_all(pk.get(), params, pk->perm_values.p, npc, pk->perm_polys.p, pk->perm_cosets.p, pk->perm_commitments.data()));
+        }
+        // l0, l_last, l_active_row = 1 - (l_last + l_blind) over the extended domain
+        {
+            const size_t u = n - (cs.blinding_factors() + 1);
+            std::vector<Fe> lag(3 * n, Fe{{0, 0, 0, 0}});
+            lag[0] = pk->f->one;
+            lag[n + u] = pk->f->one;
+            for (size_t i = 0; i < u; i++) lag[2 * n + i] = pk->f->one;
+            DevMem vals, polys;
+            TRY(vals.alloc(ctx, 3 * n, false));
+            TRY(polys.alloc(ctx, 3 * n, false));
+            TRY(pk->l_ext.alloc(ctx, 3 * m, false));
+            HostPin pin_lag(lag.data(), 3 * n * 32);
+            TRY(dh_h2d(ctx, vals.p, lag.data(), 3 * n * 32, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            TRY(lagrange_to_all(pk.get(), params, vals.p, 3, polys.p, pk->l_ext.p, nullptr));
+        }
+        pk->num_selectors = num_selectors;
+        for (uint32_t s = 0; s < num_selectors; s++) {
+            if (!selectors[s]) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null selector");
+            std::vector<uint8_t> packed((n + 7) / 8, 0);
+            for (size_t i = 0; i < n; i++)
+                if (selectors[s][i]) packed[i >> 3] |= (uint8_t)(1u << (i & 7));
+            pk->selectors.push_back(std::move(packed));
+        }
+        pk->default_transcript_repr();
+        TRY(pk->compile_graphs());
+        TRY(dehalo_ctx_synchronize(ctx));
+        *out = pk.release();
+        return 0;
+    });
+}
+
+extern "C" size_t dehalo_pk_size(const dehalo_pk* pk) { return pk ? pk->size() : 0; }
+extern "C" size_t dehalo_vk_size(const dehalo_pk* pk) { return pk ? pk->vk_size() : 0; }
+extern "C" int dehalo_vk_write(const dehalo_pk* pk, uint8_t* out, size_t cap) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        if (cap < pk->vk_size()) return dh_fail(pk->ctx, DEHALO_ERR_INVALID, "vk_write: buffer too small");
+        pk->vk_write(out);
+        return 0;
+    });
+}
+
+extern "C" int dehalo_pk_write(dehalo_ctx* ctx, const dehalo_pk* pk, uint8_t* out, size_t cap) {
+    return dh_guard(ctx ? ctx : pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        if (!ctx) ctx = pk->ctx;
+        if (cap < pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_write: buffer too small");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
+        pk->vk_write(out);
+        uint8_t* o = out + pk->vk_size();
+        DevMem tmp;      // extended-domain columns leave in upstream's standard form
+        TRY(tmp.alloc(ctx, m, false));
+        auto poly = [&](const fe* src, size_t len, bool internal) -> int {
+            put_u32_be(o, (uint32_t)len);
+            o += 4;
+            if (internal) {
+                TRY(dehalo_convert_form_device(ctx, pk->f->id, (const uint64_t*)src, tmp.u64(), len, 0, nullptr));
+                src = tmp.p;
+            }
+            TRY(dehalo_download(ctx, src, len * 32, o));
+            o += len * 32;
+            return 0;
+        };
+        auto slice = [&](const DevMem& mem, size_t cnt, size_t len, bool internal) -> int {
+            put_u32_be(o, (uint32_t)cnt);
+            o += 4;
+            for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * len), len, internal));
+            return 0;
+        };
+        for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
+        TRY(slice(pk->fixed_values, nf, n, false));
+        TRY(slice(pk->fixed_polys, nf, n, false));
+        TRY(slice(pk->fixed_cosets, nf, m, true));
+        TRY(slice(pk->perm_values, npc, n, false));
+        TRY(slice(pk->perm_polys, npc, n, false));
+        TRY(slice(pk->perm_cosets, npc, m, true));
+        return 0;
+    });
+}
+
+extern "C" int dehalo_pk_read(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* csd, const uint8_t* bytes, size_t len, uint32_t num_selectors, dehalo_pk** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: null argument");
+        if (len < 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: unexpected end of input");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const uint32_t k = get_u32_be(bytes), nf_file = get_u32_be(bytes + 4);
+        std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
+        TRY(pk_common_init(ctx, curve, csd, k, pk.get()));
+        const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
+        if (nf_file != nf) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: the key's number of fixed commitments differs from the circuit's fixed columns");
+        pk->num_selectors = num_selectors;
+        if (len != pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: length does not match the circuit (unexpected end of input or trailing bytes)");
+        HostPin pin_blob(bytes, len);      // every polynomial below is copied straight out of the caller's blob
+        const uint8_t* p = bytes + 8;
+        pk->fixed_commitments.resize(8 * nf);
+        memcpy(pk->fixed_commitments.data(), p, 64 * nf);
+        p += 64 * nf;
+        pk->perm_commitments.resize(8 * npc);
+        memcpy(pk->perm_commitments.data(), p, 64 * npc);
+        p += 64 * npc;
+        for (uint32_t s = 0; s < num_selectors; s++) {
+            pk->selectors.emplace_back(p, p + (n + 7) / 8);
+            p += (n + 7) / 8;
+        }
+        const int fid = pk->f->id;
+        auto poly = [&](fe* dst, size_t want, bool to_internal) -> int {
+            if (get_u32_be(p) != want) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial length differs from the domain's");
+            p += 4;
+            TRY(dh_h2d(ctx, dst, p, want * 32, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            p += want * 32;
+            if (to_internal) TRY(dehalo_convert_form_device(ctx, fid, (const uint64_t*)dst, (uint64_t*)dst, want, 1, nullptr));
+            return 0;
+        };
+        auto slice = [&](DevMem& mem, size_t cnt, size_t ln, bool to_internal) -> int {
+            if (get_u32_be(p) != cnt) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial count differs from the circuit's");
+            p += 4;
+            TRY(mem.alloc(ctx, cnt * ln, false));
+            for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * ln), ln, to_internal));
+            return 0;
+        };
+        TRY(pk->l_ext.alloc(ctx, 3 * m, false));
+        for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
+        TRY(slice(pk->fixed_values, nf, n, false));
+        TRY(slice(pk->fixed_polys, nf, n, false));
+        TRY(slice(pk->fixed_cosets, nf, m, true));
+        TRY(slice(pk->perm_values, npc, n, false));
+        TRY(slice(pk->perm_polys, npc, n, false));
+        TRY(slice(pk->perm_cosets, npc, m, true));
+        pk->default_transcript_repr();
+        TRY(pk->compile_graphs());
+        TRY(dehalo_ctx_synchronize(ctx));
+        *out = pk.release();
+        return 0;
+    });
+}
+
+extern "C" int dehalo_pk_set_transcript_repr(dehalo_pk* pk, const uint64_t repr[4]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !repr) return DEHALO_ERR_INVALID;
+        memcpy(pk->transcript_repr.v, repr, 32);
+        return 0;
+    });
+}
+extern "C" int dehalo_pk_get_transcript_repr(const dehalo_pk* pk, uint64_t repr[4]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !repr) return DEHALO_ERR_INVALID;
+        memcpy(repr, pk->transcript_repr.v, 32);
+        return 0;
+    });
+}
+extern "C" int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk) {
+    return dh_guard(ctx ? ctx : pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk) return 0;
+        dehalo_ctx* c = ctx ? ctx : pk->ctx;
+        std::lock_guard<std::recursive_mutex> lk(c->mu);
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+        delete pk;
+        return 0;
+    });
+}
+
+extern "C" int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        const HostCS& cs = pk->cs;
+        const uint32_t L = (uint32_t)cs.lookups.size(), S = cs.num_sets();
+        out[0] = pk->k;
+        out[1] = pk->dom.extended_k;
+        out[2] = cs.blinding_factors();
+        out[3] = cs.degree();
+        out[4] = S;
+        out[5] = cs.num_advice + 2 * L + S + L + 1 + (cs.degree() - 1);
+        out[6] = (uint32_t)(cs.advice_q.size() + cs.fixed_q.size() + 1 + cs.perm_cols.size() + (S ? 3 * S - 1 : 0) + 5 * L);
+        std::vector<int32_t> rs = {0, 1, -(int32_t)(cs.blinding_factors() + 1)};
+        if (L) rs.push_back(-1);
+        for (auto& q : cs.advice_q) rs.push_back(q.rotation);
+        for (auto& q : cs.fixed_q) rs.push_back(q.rotation);
+        std::sort(rs.begin(), rs.end());
+        out[7] = (uint32_t)(std::unique(rs.begin(), rs.end()) - rs.begin());
+        return 0;
+    });
+}

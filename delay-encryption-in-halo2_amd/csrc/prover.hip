@@ -1,7 +1,6 @@
-// prover.hip -- the whole call behind the C ABI: ParamsKZG, keygen_vk / keygen_pk, ProvingKey / VerifyingKey RawBytes, Blake2bWrite and
-// create_proof (KZG / GWC) [UPSTREAM halo2_proofs @ v2023_04_20: poly/kzg/commitment.rs, plonk/keygen.rs, plonk.rs, transcript.rs,
-// plonk/prover.rs, plonk/{lookup,permutation,vanishing}/prover.rs, poly/kzg/multiopen/gwc/prover.rs] -- the calls the reference makes at
-// benches/delay_enc.rs:41-54 (params), :84-115 (keys), :120-134 (create_proof into a Blake2bWrite transcript).
+// prover.hip -- create_proof behind the C ABI (KZG / GWC and IPA) [UPSTREAM halo2_proofs @ v2023_04_20: plonk/prover.rs,
+// plonk/{lookup,permutation,vanishing}/prover.rs, poly/kzg/multiopen/gwc/prover.rs, poly/ipa/multiopen/prover.rs] -- the call the reference makes at
+// benches/delay_enc.rs:120-134 (create_proof into a Blake2bWrite transcript).  dehalo_prover: what outlives a proof; ProofRun: one proof, a function per phase.
 //
 // Every C entry point runs its body under dh_guard (guard.hpp): an exception leaves as DEHALO_ERR_OOM (std::bad_alloc) or DEHALO_ERR_INVALID, never as an exception.
 // Host logic only: it orders the phases, hashes the transcript and does O(1) field arithmetic per challenge (hostfield.hpp); every column
@@ -15,40 +14,12 @@
 #include <thread>
 #include <unordered_map>
 
-#include "blake2b.hpp"
-#include "hostrng.hpp"
-#include "internal.hpp"
-#include "plonk_host.hpp"
+#include "whole_call.hpp"
 
 namespace {
 
 using clk = std::chrono::steady_clock;
 inline double ms_since(clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); }
-
-// ---- device memory owned by an object of this file ----
-struct DevMem {
-    fe* p = nullptr;
-    size_t elems = 0;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        elems = 0;
-    }
-    int alloc(dehalo_ctx* ctx, size_t n_elems, bool zero = true) {
-        reset();
-        if (!n_elems) return 0;
-        HIP_TRY(ctx, hipMalloc((void**)&p, n_elems * sizeof(fe)));
-        elems = n_elems;
-        if (zero) HIP_TRY(ctx, hipMemsetAsync(p, 0, n_elems * sizeof(fe), ctx->stream));
-        return 0;
-    }
-    fe* at(size_t elem) const { return p + elem; }
-    uint64_t* u64(size_t elem = 0) const { return (uint64_t*)(p + elem); }
-};
 
 // the blinding rows of a phase's columns: column c gets `rows` elements at dst + c * dst_pitch from src + c * rows (a 2-D device copy through the
 // runtime took 10-45 us for these few hundred bytes on the proving thread's stream, right before the phase's commitment)
@@ -57,919 +28,9 @@ __global__ void k_place_rows(fe* __restrict__ dst, uint64_t dst_pitch, const fe*
     if (i < rows * ncols) dst[(uint64_t)(i / rows) * dst_pitch + i % rows] = src[i];
 }
 
-__global__ void k_gather_elems(const fe* __restrict__ src, const uint64_t* __restrict__ idx, fe* __restrict__ dst, uint64_t count) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) dst[i] = src[idx[i]];
-}
-
-// DEHALO_RNG_OS, the vanishing argument's random polynomial (n scalars: 4 MiB at k = 17): generated ON THE DEVICE from the proof's ChaCha20 key (32 bytes of
-// operating-system entropy) instead of being drawn on a host thread and uploaded.  Scalar i = the first of ChaCha20 blocks (counter low = i, counter high =
-// attempt 0, 1, ...), nonce = the helper's stream, whose first 256 bits masked to the modulus' length are < p: uniform over the field.
-struct ChaKey { u32 k[8]; };
-__device__ __forceinline__ u32 cha_rotl(u32 x, int n) { return (x << n) | (x >> (32 - n)); }
-__global__ void k_chacha_scalars(ChaKey key, u64 stream, fe p, u32 top_mask, fe* out, u64 n) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (u32 attempt = 0;; attempt++) {
-        u32 st[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.k[0], key.k[1], key.k[2], key.k[3], key.k[4], key.k[5], key.k[6], key.k[7],
-                      (u32)i, ((u32)(i >> 32) & 0xffffu) | (attempt << 16), (u32)stream, (u32)(stream >> 32)};
-        u32 x[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) x[j] = st[j];
-#define CHA_QR(a, b, c, d)                                                                                         \
-    x[a] += x[b]; x[d] = cha_rotl(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = cha_rotl(x[b] ^ x[c], 12);                \
-    x[a] += x[b]; x[d] = cha_rotl(x[d] ^ x[a], 8);  x[c] += x[d]; x[b] = cha_rotl(x[b] ^ x[c], 7);
-        for (int r = 0; r < 10; r++) {
-            CHA_QR(0, 4, 8, 12) CHA_QR(1, 5, 9, 13) CHA_QR(2, 6, 10, 14) CHA_QR(3, 7, 11, 15)
-            CHA_QR(0, 5, 10, 15) CHA_QR(1, 6, 11, 12) CHA_QR(2, 7, 8, 13) CHA_QR(3, 4, 9, 14)
-        }
-#undef CHA_QR
-        fe v;
-#pragma unroll
-        for (int j = 0; j < 8; j++) v.v[j] = x[j] + st[j];
-        v.v[7] &= top_mask;
-        bool below = false, decided = false;
-#pragma unroll
-        for (int j = 7; j >= 0; j--)
-            if (!decided && v.v[j] != p.v[j]) { below = v.v[j] < p.v[j]; decided = true; }
-        if (below) {
-            out[i] = v;
-            return;
-        }
-    }
-}
-
-void put_u32_be(std::vector<uint8_t>& o, uint32_t v) { for (int i = 3; i >= 0; i--) o.push_back((uint8_t)(v >> (8 * i))); }
-void put_u32_be(uint8_t* o, uint32_t v) { for (int i = 0; i < 4; i++) o[i] = (uint8_t)(v >> (8 * (3 - i))); }
-uint32_t get_u32_be(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+const uint64_t* col_ptr(const DevMem& mem, size_t col, size_t len) { return (const uint64_t*)mem.at(col * len); }
 
 }   // namespace
-
-// ================================================================================================ ParamsKZG
-struct dehalo_params {
-    dehalo_ctx* ctx = nullptr;
-    int curve = 0;
-    uint32_t k = 0;
-    size_t n = 0;
-    std::vector<uint64_t> g, g_lagrange;      // host copies (write())
-    uint8_t g2[128] = {}, s_g2[128] = {};
-    dehalo_bases *bases_g = nullptr, *bases_gl = nullptr;
-    int scheme = DEHALO_SCHEME_KZG;
-    // ParamsIPA only: g as plain affine points followed by u, w (n + 2 points, standard Montgomery): the generator vector the opening collapses
-    DevMem d_guw;
-    dehalo_bases* bases_uw = nullptr;         // [U | W] plain: the extra bases of round 1, whose G' part runs over bases_g
-    uint64_t u[8] = {}, w[8] = {};
-};
-
-extern "C" int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint8_t* g2, const uint8_t* s_g2,
-                                    dehalo_params** out) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !out || !g || !g_lagrange) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_create: null argument");
-        if (k > 28 || curve_scalar_field(curve) < 0) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_create: k or curve out of range");
-        std::unique_ptr<dehalo_params> p(new dehalo_params);
-        p->ctx = ctx; p->curve = curve; p->k = k; p->n = (size_t)1 << k;
-        p->g.assign(g, g + 8 * p->n);
-        p->g_lagrange.assign(g_lagrange, g_lagrange + 8 * p->n);
-        if (g2) memcpy(p->g2, g2, 128);
-        if (s_g2) memcpy(p->s_g2, s_g2, 128);
-        TRY(dehalo_bases_register(ctx, curve, g, p->n, 64, 0, 1, &p->bases_g));
-        const int rc = dehalo_bases_register(ctx, curve, g_lagrange, p->n, 64, 0, 1, &p->bases_gl);
-        if (rc) {
-            (void)dehalo_bases_release(ctx, p->bases_g);
-            return rc;
-        }
-        *out = p.release();
-        return 0;
-    });
-}
-
-// ---- ParamsKZG::setup: the two G2 points on the host (O(1): one 254-bit scalar multiplication over Fq2 = Fq[i] / (i^2 + 1)) -------------------
-namespace {
-struct Fq2 { Fe a, b; };
-struct G2Host {
-    const HostField* q;
-    explicit G2Host(const HostField* f) : q(f) {}
-    Fq2 add(const Fq2& x, const Fq2& y) const { return {q->add(x.a, y.a), q->add(x.b, y.b)}; }
-    Fq2 sub(const Fq2& x, const Fq2& y) const { return {q->sub(x.a, y.a), q->sub(x.b, y.b)}; }
-    Fq2 mul(const Fq2& x, const Fq2& y) const { return {q->sub(q->mul(x.a, y.a), q->mul(x.b, y.b)), q->add(q->mul(x.a, y.b), q->mul(x.b, y.a))}; }
-    Fq2 inv(const Fq2& x) const {
-        const Fe d = q->invert(q->add(q->sqr(x.a), q->sqr(x.b)));
-        return {q->mul(x.a, d), q->neg(q->mul(x.b, d))};
-    }
-    bool is_zero(const Fq2& x) const { return x.a.is_zero() && x.b.is_zero(); }
-    struct Pt { Fq2 x, y; bool inf; };
-    Pt padd(const Pt& P, const Pt& Q) const {      // affine chord-and-tangent (a = 0): 381 inversions for one scalar multiplication are nothing here
-        if (P.inf) return Q;
-        if (Q.inf) return P;
-        Fq2 lam;
-        if (is_zero(sub(P.x, Q.x))) {
-            if (is_zero(add(P.y, Q.y))) return Pt{{}, {}, true};
-            const Fq2 xx = mul(P.x, P.x);
-            lam = mul(add(add(xx, xx), xx), inv(add(P.y, P.y)));
-        } else lam = mul(sub(Q.y, P.y), inv(sub(Q.x, P.x)));
-        Pt R;
-        R.inf = false;
-        R.x = sub(sub(mul(lam, lam), P.x), Q.x);
-        R.y = sub(mul(lam, sub(P.x, R.x)), P.y);
-        return R;
-    }
-    Pt scalar_mul(const uint64_t k_canonical[4], Pt P) const {
-        Pt acc{{}, {}, true};
-        for (int i = 0; i < 256; i++) {
-            if ((k_canonical[i >> 6] >> (i & 63)) & 1) acc = padd(acc, P);
-            P = padd(P, P);
-        }
-        return acc;
-    }
-    void to_raw(const Pt& P, uint8_t out[128]) const {      // G2Affine RawBytes: x.c0 | x.c1 | y.c0 | y.c1, Montgomery limbs; all zero = identity
-        memset(out, 0, 128);
-        if (P.inf) return;
-        memcpy(out, P.x.a.v, 32); memcpy(out + 32, P.x.b.v, 32); memcpy(out + 64, P.y.a.v, 32); memcpy(out + 96, P.y.b.v, 32);
-    }
-};
-// the generator of BN254's G2 (halo2curves bn256::G2Affine::generator(); canonical limbs)
-const uint64_t BN254_G2_GEN[4][4] = {{0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull},
-                                     {0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull},
-                                     {0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull},
-                                     {0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull}};
-}   // namespace
-
-extern "C" int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s[4], dehalo_params** out) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !out || !s) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: null argument");
-        if (curve != DEHALO_CURVE_BN254_G1) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_setup: ParamsKZG needs a pairing: BN254 only");
-        const HostField* f = host_field(curve_scalar_field(curve));
-        if (k > f->two_adicity) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: k out of range");
-        if (k > 25) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: k > 25: the SRS tables would be too large (include/dehalo.h)");      // (2 x 15 x 2^26 x 64 B = 128 GB at k = 26: fits the index and the card, never exercised)
-        // checked BEFORE the 2^(k+1) fixed-base multiplications: the tables this call registers must fit (BN254: k <= 25, include/dehalo.h)
-        if (!dh_precomputed_table_fits(curve, (size_t)1 << k)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: 2^k x windows >= 2^30: precomputed table too large");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        Fe sm;
-        memcpy(sm.v, s, 32);
-        const size_t n = (size_t)1 << k;
-        // omega = ROOT_OF_UNITY^(2^(S - k));  (s^n - 1) / n
-        Fe omega = f->root_of_unity;
-        for (uint32_t i = k; i < f->two_adicity; i++) omega = f->sqr(omega);
-        Fe sn = sm;
-        for (uint32_t i = 0; i < k; i++) sn = f->sqr(sn);
-        const Fe cfac = f->mul(f->sub(sn, f->one), f->invert(f->from_u64((uint64_t)n)));
-        std::unique_ptr<dehalo_params> p(new dehalo_params);
-        p->ctx = ctx; p->curve = curve; p->k = k; p->n = n;
-        DevMem dg, dgl;
-        TRY(dg.alloc(ctx, 2 * n, false));
-        TRY(dgl.alloc(ctx, 2 * n, false));
-        TRY(kzg_setup_bn254(ctx, k, sm.v, omega.v, cfac.v, (affine_t*)dg.p, (affine_t*)dgl.p, ctx->stream));
-        TRY(dehalo_bases_register_device(ctx, curve, dg.u64(), n, 0, 1, &p->bases_g));
-        int rc = dehalo_bases_register_device(ctx, curve, dgl.u64(), n, 0, 1, &p->bases_gl);
-        if (rc == 0) {
-            p->g.resize(8 * n); p->g_lagrange.resize(8 * n);
-            rc = dehalo_download(ctx, dg.p, 64 * n, p->g.data());
-            if (rc == 0) rc = dehalo_download(ctx, dgl.p, 64 * n, p->g_lagrange.data());
-        }
-        if (rc) {
-            (void)dehalo_bases_release(ctx, p->bases_g);
-            if (p->bases_gl) (void)dehalo_bases_release(ctx, p->bases_gl);
-            return rc;
-        }
-        {   // g2 = the generator, s_g2 = [s] g2
-            const HostField* q = host_field(curve_base_field(curve));
-            G2Host g2(q);
-            G2Host::Pt G;
-            G.inf = false;
-            Fe c[4];
-            for (int i = 0; i < 4; i++) { memcpy(c[i].v, BN254_G2_GEN[i], 32); c[i] = q->from_canonical(c[i]); }
-            G.x = {c[0], c[1]}; G.y = {c[2], c[3]};
-            const Fe sc = f->to_canonical(sm);
-            g2.to_raw(G, p->g2);
-            g2.to_raw(g2.scalar_mul(sc.v, G), p->s_g2);
-        }
-        *out = p.release();
-        return 0;
-    });
-}
-
-extern "C" int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: null argument");
-        if (len < 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: unexpected end of input");
-        const uint32_t k = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);      // u32 LE
-        if (k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: k out of range");
-        const size_t n = (size_t)1 << k;
-        if (len != 4 + 2 * 64 * n + 256) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read: length does not match k");
-        // (the points are 8-byte aligned only if the caller's buffer is: copy through aligned vectors)
-        std::vector<uint64_t> g(8 * n), gl(8 * n);
-        memcpy(g.data(), bytes + 4, 64 * n);
-        memcpy(gl.data(), bytes + 4 + 64 * n, 64 * n);
-        return dehalo_params_create(ctx, curve, k, g.data(), gl.data(), bytes + 4 + 128 * n, bytes + 4 + 128 * n + 128, out);
-    });
-}
-
-extern "C" size_t dehalo_params_size(const dehalo_params* p) { return p && p->scheme == DEHALO_SCHEME_KZG ? 4 + 2 * 64 * p->n + 256 : 0; }
-
-extern "C" int dehalo_params_write(const dehalo_params* p, uint8_t* out, size_t cap) {
-    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
-        if (!p || !out) return DEHALO_ERR_INVALID;
-        if (p->scheme != DEHALO_SCHEME_KZG) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "params_write: ParamsIPA::write is not implemented");
-        if (cap < dehalo_params_size(p)) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "params_write: buffer too small");
-        for (int i = 0; i < 4; i++) out[i] = (uint8_t)(p->k >> (8 * i));
-        memcpy(out + 4, p->g.data(), 64 * p->n);
-        memcpy(out + 4 + 64 * p->n, p->g_lagrange.data(), 64 * p->n);
-        memcpy(out + 4 + 128 * p->n, p->g2, 128);
-        memcpy(out + 4 + 128 * p->n + 128, p->s_g2, 128);
-        return 0;
-    });
-}
-
-extern "C" int dehalo_params_release(dehalo_ctx* ctx, dehalo_params* p) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!p) return 0;
-        if (p->bases_g) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_g);
-        if (p->bases_gl) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_gl);
-        if (p->bases_uw) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_uw);
-        delete p;
-        return 0;
-    });
-}
-
-extern "C" int dehalo_params_commit_device(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_polys, size_t batch, int lagrange, uint64_t* d_out_affine,
-                                           void* stream) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !p) return DEHALO_ERR_INVALID;
-        return dehalo_msm_device_affine(ctx, lagrange ? p->bases_gl : p->bases_g, d_polys, p->n, batch, nullptr, d_out_affine, stream);
-    });
-}
-
-// ================================================================================================ transcript
-struct dehalo_transcript {
-    int curve = 0;
-    const HostField *fq = nullptr, *fr = nullptr;      // base field (coordinates), scalar field (challenges)
-    Blake2b state;
-    std::vector<uint8_t> proof;
-
-    void init(int c) {
-        curve = c;
-        fq = host_field(curve_base_field(c));
-        fr = host_field(curve_scalar_field(c));
-        state.init(64, "Halo2-Transcript");
-        proof.clear();
-    }
-    Fe squeeze() {      // Challenge255: Blake2b-512 over everything absorbed + the prefix byte 0 (which stays absorbed), reduced mod r
-        const uint8_t z = 0;
-        state.update(&z, 1);
-        uint8_t d[64];
-        state.digest(d);
-        return fr->from_u512(d);
-    }
-    void common_scalar(const Fe& s) {
-        uint8_t b[33];
-        b[0] = 2;
-        fr->to_bytes(s, b + 1);
-        state.update(b, 33);
-    }
-    void write_scalar(const Fe& s) {
-        uint8_t b[33];
-        b[0] = 2;
-        fr->to_bytes(s, b + 1);
-        state.update(b, 33);
-        proof.insert(proof.end(), b + 1, b + 33);
-    }
-    // affine {x, y} Montgomery; false for the identity (upstream: "cannot write points at infinity to the transcript")
-    bool write_point(const uint64_t xy[8], bool also_to_proof = true) {
-        Fe x, y;
-        memcpy(x.v, xy, 32);
-        memcpy(y.v, xy + 4, 32);
-        if (x.is_zero() && y.is_zero()) return false;
-        uint8_t b[65];
-        b[0] = 1;
-        fq->to_bytes(x, b + 1);
-        fq->to_bytes(y, b + 33);
-        state.update(b, 65);
-        if (also_to_proof) {      // GroupEncoding: x little-endian, bit 7 of the last byte = y is odd
-            uint8_t c[32];
-            memcpy(c, b + 1, 32);
-            c[31] |= (uint8_t)((b[33] & 1) << 7);
-            proof.insert(proof.end(), c, c + 32);
-        }
-        return true;
-    }
-};
-
-extern "C" int dehalo_transcript_create(int curve, dehalo_transcript** out) {
-    return dh_guard(nullptr, [&]() -> int {
-        if (!out || curve_scalar_field(curve) < 0) return DEHALO_ERR_INVALID;
-        dehalo_transcript* t = new dehalo_transcript;
-        t->init(curve);
-        *out = t;
-        return 0;
-    });
-}
-extern "C" int dehalo_transcript_common_scalar(dehalo_transcript* t, const uint64_t s[4]) {
-    return dh_guard(nullptr, [&]() -> int {
-        if (!t || !s) return DEHALO_ERR_INVALID;
-        Fe v;
-        memcpy(v.v, s, 32);
-        t->common_scalar(v);
-        return 0;
-    });
-}
-extern "C" int dehalo_transcript_write_scalar(dehalo_transcript* t, const uint64_t s[4]) {
-    return dh_guard(nullptr, [&]() -> int {
-        if (!t || !s) return DEHALO_ERR_INVALID;
-        Fe v;
-        memcpy(v.v, s, 32);
-        t->write_scalar(v);
-        return 0;
-    });
-}
-extern "C" int dehalo_transcript_write_point(dehalo_transcript* t, const uint64_t xy[8]) {
-    return dh_guard(nullptr, [&]() -> int {
-        if (!t || !xy) return DEHALO_ERR_INVALID;
-        return t->write_point(xy) ? 0 : DEHALO_ERR_INVALID;
-    });
-}
-extern "C" int dehalo_transcript_squeeze_challenge(dehalo_transcript* t, uint64_t out[4]) {
-    return dh_guard(nullptr, [&]() -> int {
-        if (!t || !out) return DEHALO_ERR_INVALID;
-        const Fe c = t->squeeze();
-        memcpy(out, c.v, 32);
-        return 0;
-    });
-}
-extern "C" size_t dehalo_transcript_len(const dehalo_transcript* t) { return t ? t->proof.size() : 0; }
-extern "C" int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* out, size_t cap) {
-    return dh_guard(nullptr, [&]() -> int {
-        if (!t || (!out && !t->proof.empty())) return DEHALO_ERR_INVALID;
-        if (cap < t->proof.size()) return DEHALO_ERR_INVALID;
-        if (!t->proof.empty()) memcpy(out, t->proof.data(), t->proof.size());
-        return 0;
-    });
-}
-extern "C" void dehalo_transcript_release(dehalo_transcript* t) { delete t; }
-
-// ================================================================================================ ParamsIPA and the IPA opening argument
-extern "C" int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8],
-                                        const uint64_t u[8], dehalo_params** out) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !out || !g || !g_lagrange || !w || !u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: null argument");
-        if (curve != DEHALO_CURVE_PALLAS && curve != DEHALO_CURVE_VESTA) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_ipa_create: IPA over Pallas / Vesta only");
-        if (k < 1 || k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: k out of range");
-        const size_t n = (size_t)1 << k;
-        if (!dh_precomputed_table_fits(curve, n)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: 2^k x windows >= 2^30: precomputed table too large");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        dehalo_params* raw = nullptr;
-        TRY(dehalo_params_create(ctx, curve, k, g, g_lagrange, nullptr, nullptr, &raw));
-        std::unique_ptr<dehalo_params, void (*)(dehalo_params*)> p(raw, [](dehalo_params* q) { (void)dehalo_params_release(q->ctx, q); });
-        p->scheme = DEHALO_SCHEME_IPA;
-        memcpy(p->w, w, 64);
-        memcpy(p->u, u, 64);
-        TRY(p->d_guw.alloc(ctx, 2 * (n + 2), false));
-        TRY(dh_h2d(ctx, p->d_guw.p, g, 64 * n, ctx->stream));
-        TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream));
-        TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream));
-        TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, &p->bases_uw));
-        *out = p.release();
-        return 0;
-    });
-}
-
-extern "C" int dehalo_params_scheme(const dehalo_params* p) { return p ? p->scheme : DEHALO_ERR_INVALID; }
-
-namespace {
-
-// Blind::default() of upstream's poly/commitment.rs, the blind of every commitment that is not hiding: the verifying key's fixed and permutation columns and,
-// under IPA, the instance columns.  Taken to be Blind(F::ONE) (no upstream source at hand: parity unpinned).  Keygen and the prover
-// read this constant only; the CPU restatement and the verifier of the tests have its twin (tests/plonk_ipa_reference.py DEFAULT_BLIND).
-constexpr uint64_t IPA_DEFAULT_BLIND = 1;
-
-// commit(poly, blind) of ParamsIPA = MSM(poly, g) + [blind] W, affine into d_pair[0] (d_pair: two points of scratch; [1] receives W): the MSM's affine
-// result and W make a two-point generator vector whose collapse by `blind` is exactly C + [blind] W
-int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, uint64_t* d_pair, hipStream_t s) {
-    TRY(dehalo_msm_device_affine(ctx, p->bases_g, d_poly, p->n, 1, nullptr, d_pair, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pair + 8, p->d_guw.at(2 * p->n + 2), 64, hipMemcpyDeviceToDevice, s));
-    return dehalo_generator_collapse_device(ctx, p->curve, d_pair, 2, blind.v, d_pair, s);
-}
-
-// commitment::create_proof on `rng` as it stands (dehalo_ipa_open: a fresh generator; a whole proof: the proof's generator, right behind f's blind).
-// cha_stream: the ChaCha20 stream of the n-scalar draw under DEHALO_RNG_OS -- within one proof it must differ from the random polynomial's (1).
-int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t) {
-        const hipStream_t s = ctx->stream;
-        const int fid = curve_scalar_field(p->curve);
-        const HostField* f = host_field(fid);
-        const IpaOps* ops = ipa_ops(p->curve);
-        const size_t n = p->n;
-        const uint32_t k = p->k;
-        DevMem s_poly, s_adj, pa, pb, guw, sc, ev, rr, pts, uwsc;
-        TRY(s_poly.alloc(ctx, n, false));
-        TRY(s_adj.alloc(ctx, n, false));
-        TRY(pa.alloc(ctx, n, false));
-        TRY(pb.alloc(ctx, n, false));
-        TRY(guw.alloc(ctx, n + 4, false));           // G' of rounds 2.., then U, W: n / 2 + 2 points of 2 elements
-        TRY(sc.alloc(ctx, 2 * n, false));
-        TRY(ev.alloc(ctx, 2, false));
-        TRY(rr.alloc(ctx, 2 * (size_t)k, false));
-        TRY(pts.alloc(ctx, 8, false));
-        TRY(uwsc.alloc(ctx, 4, false));
-        // ---- draws, in upstream's order: s_poly (n), s_poly_blind, (l_rand, r_rand) per round.  The n scalars are the proof's large draw and come, as
-        // the prover's random polynomial does, from the generator forked at their position: for DEHALO_RNG_OS a ChaCha20 kernel under the call's key
-        // (stream 1); for PCG64 / a callback the fork yields exactly the scalars a serial draw would, drawn on the host and uploaded.
-        HostRng rng_poly = rng.fork(0, cha_stream);
-        rng.skip(n);
-        Fe s_blind;
-        std::vector<uint64_t> rands(8 * (size_t)k);
-        TRY(rng.scalars(s_blind.v, 1));
-        TRY(rng.scalars(rands.data(), 2 * (size_t)k));
-        if (rng.kind == DEHALO_RNG_OS) {
-            ChaKey ck;
-            memcpy(ck.k, rng.key, 32);
-            fe pw;
-            for (int i = 0; i < 4; i++) { pw.v[2 * i] = (u32)f->p[i]; pw.v[2 * i + 1] = (u32)(f->p[i] >> 32); }
-            const u32 top_mask = f->bits >= 256 ? 0xffffffffu : ((1u << (f->bits - 224)) - 1);
-            k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ck, /* stream of the fork */ cha_stream, pw, top_mask, s_poly.p, n);
-            HIP_TRY(ctx, hipGetLastError());
-        } else {
-            std::vector<uint64_t> s_host(4 * n);
-            TRY(rng_poly.scalars(s_host.data(), n));
-            TRY(dh_h2d(ctx, s_poly.p, s_host.data(), 32 * n, s));
-        }
-        TRY(dh_h2d(ctx, rr.p, rands.data(), 64 * (size_t)k, s));
-        // ---- s(x3) and p(x3); s_poly[0] -= s(x3)
-        TRY(dehalo_eval_polynomial_device(ctx, fid, s_poly.u64(), n, n, 1, x3.v, ev.u64(0), s));
-        TRY(dehalo_eval_polynomial_device(ctx, fid, d_poly, n, n, 1, x3.v, ev.u64(1), s));
-        Fe at[2];
-        TRY(dehalo_download(ctx, ev.p, 64, at));
-        const uint64_t* one_col[1] = {s_poly.u64()};
-        TRY(dehalo_lincomb_device(ctx, fid, one_col, f->one.v, 1, n, s_adj.u64(), at[0].v, s));
-        // ---- S = commit(s_poly, s_poly_blind)
-        TRY(ipa_commit_blinded(ctx, p, s_adj.u64(), s_blind, pts.u64(), s));
-        uint64_t S[8];
-        TRY(dehalo_download(ctx, pts.p, 64, S));
-        if (!t->write_point(S)) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: s_poly commitment at infinity");
-        const Fe xi = t->squeeze();
-        const Fe z = t->squeeze();
-        // ---- p' = p + xi s, p'[0] -= p'(x3) (= p(x3): s(x3) = 0 now); f = s_poly_blind xi + blind
-        {
-            const uint64_t* cols[2] = {d_poly, s_adj.u64()};
-            Fe coefs[2] = {f->one, xi};
-            TRY(dehalo_lincomb_device(ctx, fid, cols, coefs[0].v, 2, n, pa.u64(), at[1].v, s));
-        }
-        Fe fsum = f->add(f->mul(s_blind, xi), blind);
-        // ---- k rounds; b stays geometric: b^(j)[i] = c_j x3^i.  Round 1 runs over the resident precomputed table of g (its [U | W] terms over
-        // bases_uw, added by a collapse with u = 1); rounds 2.. over one plain registration of [G' | U | W], rebuilt on the stream each round.
-        dehalo_bases* breg = nullptr;
-        TRY(dh_bases_plain_alloc(ctx, p->curve, n / 2 + 2, &breg));
-        std::unique_ptr<dehalo_bases, void (*)(dehalo_bases*)> breg_own(breg, [](dehalo_bases* b) { if (b->table) (void)hipFree(b->table); delete b; });
-        std::vector<Fe> x3_pow(k + 1);           // x3^(2^i)
-        x3_pow[0] = x3;
-        for (uint32_t i = 1; i <= k; i++) x3_pow[i] = f->sqr(x3_pow[i - 1]);
-        Fe c = f->one;
-        DevMem* cur = &pa;
-        DevMem* nxt = &pb;
-        for (uint32_t j = 0; j < k; j++) {
-            const size_t nj = n >> j, half = nj / 2, m = j == 0 ? nj : nj + 2;
-            const Fe x3h = x3_pow[k - 1 - j];                  // x3^half
-            // scalars: L = [p'_hi | 0 | z value_l | l_rand], R = [0 | p'_lo | z value_r | r_rand] (round 1: the [U | W] slots in uwsc)
-            fe* sl = sc.at(0);
-            fe* sr = sc.at(m);
-            HIP_TRY(ctx, hipMemcpyAsync(sl, cur->at(half), 32 * half, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(ctx, hipMemsetAsync(sl + half, 0, 32 * half, s));
-            HIP_TRY(ctx, hipMemsetAsync(sr, 0, 32 * half, s));
-            HIP_TRY(ctx, hipMemcpyAsync(sr + half, cur->p, 32 * half, hipMemcpyDeviceToDevice, s));
-            TRY(dehalo_eval_polynomial_device(ctx, fid, cur->u64(), half, half, 2, x3.v, ev.u64(), s));      // p'_lo(x3), p'_hi(x3)
-            const Fe zc = f->mul(z, c), zch = f->mul(zc, x3h);
-            if (j == 0) {
-                TRY(ops->slots(ctx, ev.p, zc.v, zch.v, rr.at(0), uwsc.at(0), uwsc.at(2), s));
-                TRY(dehalo_msm_device_affine(ctx, p->bases_g, sc.u64(), n, 2, nullptr, pts.u64(0), s));       // L_g, R_g
-                TRY(dehalo_msm_device_affine(ctx, p->bases_uw, uwsc.u64(), 2, 2, nullptr, pts.u64(4), s));    // L_uw, R_uw (points 2, 3)
-                const uint64_t one_m[4] = {f->one.v[0], f->one.v[1], f->one.v[2], f->one.v[3]};
-                TRY(dehalo_generator_collapse_device(ctx, p->curve, pts.u64(), 4, one_m, pts.u64(), s));      // [L_g + L_uw, R_g + R_uw]
-            } else {
-                TRY(ops->slots(ctx, ev.p, zc.v, zch.v, rr.at(2 * j), sl + nj, sr + nj, s));
-                HIP_TRY(ctx, hipMemcpyAsync(guw.at(2 * nj), p->d_guw.at(2 * n), 128, hipMemcpyDeviceToDevice, s));     // U, W behind G'
-                TRY(dh_bases_plain_rebuild(ctx, breg, (const affine_t*)guw.p, m, s));
-                TRY(dehalo_msm_device_affine(ctx, breg, sc.u64(), m, 2, nullptr, pts.u64(), s));
-            }
-            uint64_t LR[16];
-            TRY(dehalo_download(ctx, pts.p, 128, LR));      // the round's one host wait
-            if (!t->write_point(LR) || !t->write_point(LR + 8)) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: L_j or R_j at infinity");
-            const Fe u = t->squeeze();
-            const Fe u_inv = f->invert(u);
-            Fe lr, rrnd;
-            memcpy(lr.v, &rands[8 * j], 32);
-            memcpy(rrnd.v, &rands[8 * j + 4], 32);
-            fsum = f->add(fsum, f->add(f->mul(lr, u_inv), f->mul(rrnd, u)));
-            c = f->mul(c, f->add(f->one, f->mul(u, x3h)));
-            // p' <- p'_lo + u^-1 p'_hi (into the other buffer: lincomb's out may alias no column); G' <- G'_lo + [u] G'_hi (round 1 reads g, later
-            // rounds collapse in place; the last round's G' would never be read)
-            const uint64_t* cols[2] = {cur->u64(), cur->u64(half)};
-            Fe coefs[2] = {f->one, u_inv};
-            TRY(dehalo_lincomb_device(ctx, fid, cols, coefs[0].v, 2, half, nxt->u64(), nullptr, s));
-            if (j + 1 < k) TRY(dehalo_generator_collapse_device(ctx, p->curve, j == 0 ? p->d_guw.u64() : guw.u64(), nj, u.v, guw.u64(), s));
-            std::swap(cur, nxt);
-        }
-        Fe cfin;
-        TRY(dehalo_download(ctx, cur->p, 32, cfin.v));
-        t->write_scalar(cfin);
-        t->write_scalar(fsum);
-        return 0;
-}
-}   // namespace
-
-extern "C" int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const uint64_t blind_in[4], const uint64_t x3_in[4], dehalo_rng* rng_in,
-                               dehalo_transcript* t) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !p || !d_poly || !blind_in || !x3_in || !t) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: null argument");
-        if (p->scheme != DEHALO_SCHEME_IPA) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: needs ParamsIPA (dehalo_params_ipa_create)");
-        if (t->curve != p->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_open: transcript and params disagree on the curve");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        Fe blind, x3;
-        memcpy(blind.v, blind_in, 32);
-        memcpy(x3.v, x3_in, 32);
-        HostRng rng;
-        TRY(rng.init(rng_in, host_field(curve_scalar_field(p->curve))));
-        TRY(ipa_open_body(ctx, p, d_poly, blind, x3, rng, 1, t));
-        if (rng_in && rng_in->kind == DEHALO_RNG_PCG64) {      // a PCG64 caller's generator moves past the draws (upstream's `&mut rng`)
-            rng_in->pcg_state[0] = (uint64_t)rng.pcg.state;
-            rng_in->pcg_state[1] = (uint64_t)(rng.pcg.state >> 64);
-        }
-        return 0;
-    });
-}
-
-extern "C" int dehalo_field_info(int field, uint64_t out[24]) {
-    return dh_guard(nullptr, [&]() -> int {
-        const HostField* f = host_field(field);
-        if (!f || !out) return DEHALO_ERR_INVALID;
-        memcpy(out, f->p, 32);
-        memcpy(out + 4, f->one.v, 32);
-        memcpy(out + 8, f->root_of_unity.v, 32);
-        memcpy(out + 12, f->zeta.v, 32);
-        memcpy(out + 16, f->delta.v, 32);
-        memcpy(out + 20, f->gen.v, 32);
-        return 0;
-    });
-}
-
-extern "C" int dehalo_rng_scalars(dehalo_rng* rng, int field, uint64_t skip, uint64_t* out, size_t count) {
-    return dh_guard(nullptr, [&]() -> int {
-        const HostField* f = host_field(field);
-        if (!f || (!out && count)) return DEHALO_ERR_INVALID;
-        HostRng r;
-        TRY(r.init(rng, f));
-        r.skip(skip);
-        return r.scalars(out, count);
-    });
-}
-
-// ================================================================================================ keys
-struct dehalo_pk {
-    dehalo_ctx* ctx = nullptr;
-    int curve = 0;
-    const HostField* f = nullptr;
-    HostCS cs;
-    HostDomain dom;
-    uint32_t k = 0, num_selectors = 0;
-    std::vector<uint64_t> fixed_commitments, perm_commitments;      // Montgomery affine, 8 u64 each
-    std::vector<std::vector<uint8_t>> selectors;                    // packed 8 bools per byte, LSB first
-    Fe transcript_repr{};
-    // device: values / polys in upstream's standard form, extended-domain columns in the kernels' internal form
-    DevMem l_ext, fixed_values, fixed_polys, fixed_cosets, perm_values, perm_polys, perm_cosets;
-    dehalo_graph* custom_gates = nullptr;
-    std::vector<dehalo_graph*> lookup_graphs;
-    std::vector<std::pair<dehalo_graph*, dehalo_graph*>> compress_graphs;
-
-    ~dehalo_pk() {
-        if (custom_gates) (void)dehalo_graph_release(ctx, custom_gates);
-        for (auto* g : lookup_graphs) (void)dehalo_graph_release(ctx, g);
-        for (auto& g : compress_graphs) {
-            (void)dehalo_graph_release(ctx, g.first);
-            (void)dehalo_graph_release(ctx, g.second);
-        }
-    }
-    size_t vk_size() const { return 8 + 64 * (size_t)cs.num_fixed + 64 * cs.perm_cols.size() + (size_t)num_selectors * ((dom.n + 7) / 8); }
-    void vk_write(uint8_t* o) const {
-        put_u32_be(o, k);
-        put_u32_be(o + 4, cs.num_fixed);
-        o += 8;
-        memcpy(o, fixed_commitments.data(), 64 * (size_t)cs.num_fixed);
-        o += 64 * (size_t)cs.num_fixed;
-        memcpy(o, perm_commitments.data(), 64 * cs.perm_cols.size());
-        o += 64 * cs.perm_cols.size();
-        for (auto& s : selectors) {
-            memcpy(o, s.data(), s.size());
-            o += s.size();
-        }
-    }
-    size_t size() const {
-        const size_t n = dom.n, m = dom.m, nf = cs.num_fixed, npc = cs.perm_cols.size();
-        auto poly = [](size_t ln) { return 4 + 32 * ln; };
-        auto sl = [&](size_t cnt, size_t ln) { return 4 + cnt * poly(ln); };
-        return vk_size() + 3 * poly(m) + 2 * sl(nf, n) + sl(nf, m) + 2 * sl(npc, n) + sl(npc, m);
-    }
-    void default_transcript_repr() {
-        std::vector<uint8_t> body(vk_size());
-        vk_write(body.data());
-        cs.encode(body);
-        Blake2b h;
-        h.init(64, "Halo2-Verify-Key");
-        const uint64_t len = body.size();
-        h.update(&len, 8);
-        h.update(body.data(), body.size());
-        uint8_t d[64];
-        h.digest(d);
-        transcript_repr = f->from_u512(d);
-    }
-    int compile_graphs() {
-        TRY(custom_gates_graph(cs, f).compile(ctx, &custom_gates));
-        for (auto& lk : cs.lookups) {
-            dehalo_graph *g = nullptr, *gi = nullptr, *gt = nullptr;
-            TRY(lookup_table_value_graph(cs, lk, f).compile(ctx, &g));
-            lookup_graphs.push_back(g);
-            TRY(compress_graph(cs, lk.inputs, f).compile(ctx, &gi));
-            const int rc = compress_graph(cs, lk.tables, f).compile(ctx, &gt);
-            compress_graphs.push_back({gi, gt});
-            if (rc) return rc;
-        }
-        return 0;
-    }
-};
-
-namespace {
-
-int pk_common_init(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* csd, uint32_t k, dehalo_pk* pk) {
-    pk->ctx = ctx;
-    pk->curve = curve;
-    pk->k = k;
-    pk->f = host_field(curve_scalar_field(curve));
-    if (!pk->f) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve");
-    const std::string err = pk->cs.load(csd);
-    if (!err.empty()) return dh_fail(ctx, DEHALO_ERR_INVALID, err);
-    if (k > 28 || !pk->dom.init(pk->f, pk->cs.degree(), k)) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "extended_k exceeds the field's two-adicity");
-    if (pk->dom.n < (size_t)pk->cs.blinding_factors() + 3) return dh_fail(ctx, DEHALO_ERR_INVALID, "not enough rows available");      // Error::NotEnoughRowsAvailable
-    return 0;
-}
-
-// values (cnt x n, standard form, device) -> polys (lagrange_to_coeff), cosets (coeff_to_extended, internal form), commitments to the host
-int lagrange_to_all(dehalo_pk* pk, const dehalo_params* params, const fe* values, size_t cnt, fe* polys, fe* cosets, uint64_t* commitments_host) {
-    dehalo_ctx* ctx = pk->ctx;
-    if (!cnt) return 0;
-    const HostDomain& d = pk->dom;
-    DevMem aff, jac, bl;
-    if (commitments_host) {
-        TRY(aff.alloc(ctx, 2 * cnt, false));
-        if (params->scheme == DEHALO_SCHEME_IPA) {      // commit_lagrange(values, Blind::default()): MSM + [default blind] W
-            const Fe b = pk->f->from_u64(IPA_DEFAULT_BLIND);
-            std::vector<Fe> bh(cnt, b);
-            TRY(jac.alloc(ctx, 3 * cnt, false));
-            TRY(bl.alloc(ctx, cnt, false));
-            TRY(dehalo_upload(ctx, bh.data(), cnt * 32, bl.p));
-            TRY(dehalo_msm_device(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, jac.u64(), nullptr));
-            TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64(), bl.u64(), cnt, params->d_guw.u64(2 * params->n + 2), nullptr));
-            TRY(dehalo_to_affine_device(ctx, params->curve, jac.u64(), cnt, aff.u64(), nullptr));
-        } else TRY(dehalo_msm_device_affine(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
-    }
-    TRY(dehalo_lagrange_to_coeff_device(ctx, pk->f->id, (const uint64_t*)values, (uint64_t*)polys, d.k, d.omega_inv.v, d.ifft_divisor.v, cnt, nullptr));
-    TRY(dehalo_coset_ntt_form_device(ctx, pk->f->id, (const uint64_t*)polys, d.k, (uint64_t*)cosets, d.extended_k, d.ext_omega.v, d.g_coset.v, cnt, DEHALO_FORM_OUT_INTERNAL,
-                                     nullptr));
-    if (commitments_host) TRY(dehalo_download(ctx, aff.p, cnt * 64, commitments_host));
-    else TRY(dehalo_ctx_synchronize(ctx));
-    return 0;
-}
-
-// (n, 4) device column of omega^i: the forward NTT of the unit vector e_1
-int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col) {
-    HIP_TRY(ctx, hipMemsetAsync(col, 0, d.n * sizeof(fe), ctx->stream));
-    TRY(dh_h2d(ctx, col + (d.n > 1 ? 1 : 0), d.f->one.v, 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (the source is a host object: copied before returning)
-    if (d.n > 1) TRY(dehalo_ntt_device(ctx, d.f->id, (uint64_t*)col, d.k, d.omega.v, 1, nullptr));
-    return 0;
-}
-
-}   // namespace
-
-extern "C" int dehalo_keygen(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_constraint_system* csd, const uint64_t* fixed, const uint64_t* mapping,
-                             const uint8_t* const* selectors, uint32_t num_selectors, uint32_t flags, dehalo_pk** out) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !params || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null argument");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
-        TRY(pk_common_init(ctx, params->curve, csd, params->k, pk.get()));
-        const HostCS& cs = pk->cs;
-        const HostDomain& d = pk->dom;
-        const size_t n = d.n, m = d.m, nf = cs.num_fixed, npc = cs.perm_cols.size();
-        if ((nf && !fixed) || (npc && !mapping) || (num_selectors && !selectors)) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null column data");
-        const int fid = pk->f->id;
-        // fixed columns
-        TRY(pk->fixed_values.alloc(ctx, nf * n, false));
-        TRY(pk->fixed_polys.alloc(ctx, nf * n, false));
-        TRY(pk->fixed_cosets.alloc(ctx, nf * m, false));
-        pk->fixed_commitments.assign(8 * nf, 0);
-        if (nf) {
-            HostPin pin_fixed(fixed, nf * n * 32);
-            TRY(dh_h2d(ctx, pk->fixed_values.p, fixed, nf * n * 32, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (flags & DEHALO_KEYGEN_FIXED_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, pk->fixed_values.u64(), nullptr, pk->fixed_values.u64(), nf * n, nullptr));
-            TRY(lagrange_to_all(pk.get(), params, pk->fixed_values.p, nf, pk->fixed_polys.p, pk->fixed_cosets.p, pk->fixed_commitments.data()));
-        }
-        // permutation: sigma_j(omega^i) = delta^(column of the mapped cell) * omega^(its row)  [permutation::keygen::Assembly::build_pk]
-        TRY(pk->perm_values.alloc(ctx, npc * n, false));
-        TRY(pk->perm_polys.alloc(ctx, npc * n, false));
-        TRY(pk->perm_cosets.alloc(ctx, npc * m, false));
-        pk->perm_commitments.assign(8 * npc, 0);
-        if (npc) {
-            for (size_t i = 0; i < npc * n; i++)
-                if (mapping[i] >= npc * n) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: permutation mapping points outside the permutation's columns");
-            DevMem ident, w;
-            uint64_t* d_map = nullptr;
-            TRY(ident.alloc(ctx, npc * n, false));
-            TRY(w.alloc(ctx, n, false));
-            TRY(omega_powers(ctx, d, w.p));
-            Fe dj = pk->f->one;
-            for (size_t j = 0; j < npc; j++) {
-                HIP_TRY(ctx, hipMemcpyAsync(ident.at(j * n), w.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
-                if (j) TRY(dehalo_scale_device(ctx, fid, ident.u64(j * n), n, dj.v, 1, nullptr, nullptr));
-                dj = pk->f->mul(dj, pk->f->delta);
-            }
-            HIP_TRY(ctx, hipMalloc((void**)&d_map, npc * n * 8));
-            HostPin pin_map(mapping, npc * n * 8);
-            hipError_t e = dh_h2d(ctx, d_map, mapping, npc * n * 8, ctx->stream) == 0 ? hipSuccess : hipErrorUnknown;
-            if (e == hipSuccess) {
-                k_gather_elems<<<(unsigned)((npc * n + 255) / 256), 256, 0, ctx->stream>>>(ident.p, d_map, pk->perm_values.p, npc * n);
-                e = hipStreamSynchronize(ctx->stream);
-            }
-            (void)hipFree(d_map);
-            HIP_TRY(ctx, e);
-            TRY(lagrange_to_all(pk.get(), params, pk->perm_values.p, npc, pk->perm_polys.p, pk->perm_cosets.p, pk->perm_commitments.data()));
-        }
-        // l0, l_last, l_active_row = 1 - (l_last + l_blind) over the extended domain
-        {
-            const size_t u = n - (cs.blinding_factors() + 1);
-            std::vector<Fe> lag(3 * n, Fe{{0, 0, 0, 0}});
-            lag[0] = pk->f->one;
-            lag[n + u] = pk->f->one;
-            for (size_t i = 0; i < u; i++) lag[2 * n + i] = pk->f->one;
-            DevMem vals, polys;
-            TRY(vals.alloc(ctx, 3 * n, false));
-            TRY(polys.alloc(ctx, 3 * n, false));
-            TRY(pk->l_ext.alloc(ctx, 3 * m, false));
-            HostPin pin_lag(lag.data(), 3 * n * 32);
-            TRY(dh_h2d(ctx, vals.p, lag.data(), 3 * n * 32, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            TRY(lagrange_to_all(pk.get(), params, vals.p, 3, polys.p, pk->l_ext.p, nullptr));
-        }
-        pk->num_selectors = num_selectors;
-        for (uint32_t s = 0; s < num_selectors; s++) {
-            if (!selectors[s]) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: null selector");
-            std::vector<uint8_t> packed((n + 7) / 8, 0);
-            for (size_t i = 0; i < n; i++)
-                if (selectors[s][i]) packed[i >> 3] |= (uint8_t)(1u << (i & 7));
-            pk->selectors.push_back(std::move(packed));
-        }
-        pk->default_transcript_repr();
-        TRY(pk->compile_graphs());
-        TRY(dehalo_ctx_synchronize(ctx));
-        *out = pk.release();
-        return 0;
-    });
-}
-
-extern "C" size_t dehalo_pk_size(const dehalo_pk* pk) { return pk ? pk->size() : 0; }
-extern "C" size_t dehalo_vk_size(const dehalo_pk* pk) { return pk ? pk->vk_size() : 0; }
-extern "C" int dehalo_vk_write(const dehalo_pk* pk, uint8_t* out, size_t cap) {
-    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
-        if (!pk || !out) return DEHALO_ERR_INVALID;
-        if (cap < pk->vk_size()) return dh_fail(pk->ctx, DEHALO_ERR_INVALID, "vk_write: buffer too small");
-        pk->vk_write(out);
-        return 0;
-    });
-}
-
-extern "C" int dehalo_pk_write(dehalo_ctx* ctx, const dehalo_pk* pk, uint8_t* out, size_t cap) {
-    return dh_guard(ctx ? ctx : pk ? pk->ctx : nullptr, [&]() -> int {
-        if (!pk || !out) return DEHALO_ERR_INVALID;
-        if (!ctx) ctx = pk->ctx;
-        if (cap < pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_write: buffer too small");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
-        pk->vk_write(out);
-        uint8_t* o = out + pk->vk_size();
-        DevMem tmp;      // extended-domain columns leave in upstream's standard form
-        TRY(tmp.alloc(ctx, m, false));
-        auto poly = [&](const fe* src, size_t len, bool internal) -> int {
-            put_u32_be(o, (uint32_t)len);
-            o += 4;
-            if (internal) {
-                TRY(dehalo_convert_form_device(ctx, pk->f->id, (const uint64_t*)src, tmp.u64(), len, 0, nullptr));
-                src = tmp.p;
-            }
-            TRY(dehalo_download(ctx, src, len * 32, o));
-            o += len * 32;
-            return 0;
-        };
-        auto slice = [&](const DevMem& mem, size_t cnt, size_t len, bool internal) -> int {
-            put_u32_be(o, (uint32_t)cnt);
-            o += 4;
-            for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * len), len, internal));
-            return 0;
-        };
-        for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
-        TRY(slice(pk->fixed_values, nf, n, false));
-        TRY(slice(pk->fixed_polys, nf, n, false));
-        TRY(slice(pk->fixed_cosets, nf, m, true));
-        TRY(slice(pk->perm_values, npc, n, false));
-        TRY(slice(pk->perm_polys, npc, n, false));
-        TRY(slice(pk->perm_cosets, npc, m, true));
-        return 0;
-    });
-}
-
-extern "C" int dehalo_pk_read(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* csd, const uint8_t* bytes, size_t len, uint32_t num_selectors, dehalo_pk** out) {
-    return dh_guard(ctx, [&]() -> int {
-        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: null argument");
-        if (len < 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: unexpected end of input");
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        const uint32_t k = get_u32_be(bytes), nf_file = get_u32_be(bytes + 4);
-        std::unique_ptr<dehalo_pk> pk(new dehalo_pk);
-        TRY(pk_common_init(ctx, curve, csd, k, pk.get()));
-        const size_t n = pk->dom.n, m = pk->dom.m, nf = pk->cs.num_fixed, npc = pk->cs.perm_cols.size();
-        if (nf_file != nf) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: the key's number of fixed commitments differs from the circuit's fixed columns");
-        pk->num_selectors = num_selectors;
-        if (len != pk->size()) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: length does not match the circuit (unexpected end of input or trailing bytes)");
-        HostPin pin_blob(bytes, len);      // every polynomial below is copied straight out of the caller's blob
-        const uint8_t* p = bytes + 8;
-        pk->fixed_commitments.resize(8 * nf);
-        memcpy(pk->fixed_commitments.data(), p, 64 * nf);
-        p += 64 * nf;
-        pk->perm_commitments.resize(8 * npc);
-        memcpy(pk->perm_commitments.data(), p, 64 * npc);
-        p += 64 * npc;
-        for (uint32_t s = 0; s < num_selectors; s++) {
-            pk->selectors.emplace_back(p, p + (n + 7) / 8);
-            p += (n + 7) / 8;
-        }
-        const int fid = pk->f->id;
-        auto poly = [&](fe* dst, size_t want, bool to_internal) -> int {
-            if (get_u32_be(p) != want) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial length differs from the domain's");
-            p += 4;
-            TRY(dh_h2d(ctx, dst, p, want * 32, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            p += want * 32;
-            if (to_internal) TRY(dehalo_convert_form_device(ctx, fid, (const uint64_t*)dst, (uint64_t*)dst, want, 1, nullptr));
-            return 0;
-        };
-        auto slice = [&](DevMem& mem, size_t cnt, size_t ln, bool to_internal) -> int {
-            if (get_u32_be(p) != cnt) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial count differs from the circuit's");
-            p += 4;
-            TRY(mem.alloc(ctx, cnt * ln, false));
-            for (size_t i = 0; i < cnt; i++) TRY(poly(mem.at(i * ln), ln, to_internal));
-            return 0;
-        };
-        TRY(pk->l_ext.alloc(ctx, 3 * m, false));
-        for (int i = 0; i < 3; i++) TRY(poly(pk->l_ext.at((size_t)i * m), m, true));
-        TRY(slice(pk->fixed_values, nf, n, false));
-        TRY(slice(pk->fixed_polys, nf, n, false));
-        TRY(slice(pk->fixed_cosets, nf, m, true));
-        TRY(slice(pk->perm_values, npc, n, false));
-        TRY(slice(pk->perm_polys, npc, n, false));
-        TRY(slice(pk->perm_cosets, npc, m, true));
-        pk->default_transcript_repr();
-        TRY(pk->compile_graphs());
-        TRY(dehalo_ctx_synchronize(ctx));
-        *out = pk.release();
-        return 0;
-    });
-}
-
-extern "C" int dehalo_pk_set_transcript_repr(dehalo_pk* pk, const uint64_t repr[4]) {
-    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
-        if (!pk || !repr) return DEHALO_ERR_INVALID;
-        memcpy(pk->transcript_repr.v, repr, 32);
-        return 0;
-    });
-}
-extern "C" int dehalo_pk_get_transcript_repr(const dehalo_pk* pk, uint64_t repr[4]) {
-    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
-        if (!pk || !repr) return DEHALO_ERR_INVALID;
-        memcpy(repr, pk->transcript_repr.v, 32);
-        return 0;
-    });
-}
-extern "C" int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk) {
-    return dh_guard(ctx ? ctx : pk ? pk->ctx : nullptr, [&]() -> int {
-        if (!pk) return 0;
-        dehalo_ctx* c = ctx ? ctx : pk->ctx;
-        std::lock_guard<std::recursive_mutex> lk(c->mu);
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
-        delete pk;
-        return 0;
-    });
-}
 
 // ================================================================================================ create_proof
 struct dehalo_prover {
@@ -980,7 +41,7 @@ struct dehalo_prover {
     size_t n = 0, m = 0, u = 0;
     uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, I = 0, NC = 0, pieces = 0;
     uint32_t o_adv = 0, o_perm = 0, o_pz = 0, o_lz = 0, o_rand = 0;
-    DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, hfold, qbuf, wbuf, jac, jac_side, evals, blind_dev, omega_col;
+    DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, hfold, qbuf, wbuf, jac, evals, blind_dev, omega_col;
     fe* polys = nullptr;      // coefficient forms: polys_own with a side context, cols (in place) without
     std::vector<std::pair<dehalo_graph*, dehalo_graph*>> perm_graphs;      // per set: (denominator, numerator)
     std::vector<uint32_t> table_rep;      // per lookup: the first lookup with the same table expressions (shares its compressed table)
@@ -990,9 +51,8 @@ struct dehalo_prover {
     std::vector<TableRows> table_rows;
     dehalo_graph *lookup_den = nullptr, *lookup_num = nullptr;
     hipEvent_t ev_ready[3] = {nullptr, nullptr, nullptr}, ev_inst = nullptr, ev_side = nullptr;      // ev_ready: one per commitment phase
-    hipEvent_t ev_helper = nullptr;      // the helper thread waits for ITS work on the side stream through this event: a hipStreamSynchronize there holds the
-    uint64_t* pin_helper = nullptr;      // stream against the proving thread's launches (0.4 ms of the lookups' phase); its point lands in this page-locked slot
-    hipStream_t hs = nullptr;            // ... and its work (upload, the random polynomial's commitment) runs on a stream of its own beside the side context's
+    hipEvent_t ev_helper = nullptr;      // the helper thread waits for ITS upload through this event: a hipStreamSynchronize on the side stream holds that stream
+    hipStream_t hs = nullptr;            // against the proving thread's launches (0.4 ms of the lookups' phase); the upload runs on a stream of its own beside it
     uint64_t* adv_pin = nullptr;         // dehalo_create_proof_circuit: the advice columns the witness generator writes (page-locked, kept across proofs)
     uint64_t* rand_pin = nullptr;        // host-drawn random polynomial (page-locked: its upload is one DMA that holds no stream)
     // opening plan (depends on the circuit only)
@@ -1029,9 +89,7 @@ struct dehalo_prover {
     bool trace = false;      // DEHALO_PROVER_TRACE=1: host timestamps inside the phases go to stderr after each proof
     std::vector<std::pair<const char*, double>> ticks;
     clk::time_point t0;
-    void tk(const char* label) {
-        if (trace) ticks.push_back({label, ms_since(t0)});
-    }
+    void tk(const char* label) { if (trace) ticks.push_back({label, ms_since(t0)}); }
     std::mutex mu;      // one create_proof at a time per prover
 
     ~dehalo_prover() {
@@ -1043,7 +101,6 @@ struct dehalo_prover {
         if (lookup_num) (void)dehalo_graph_release(ctx, lookup_num);
         for (hipEvent_t e : {ev_ready[0], ev_ready[1], ev_ready[2], ev_inst, ev_side, ev_helper})
             if (e) (void)hipEventDestroy(e);
-        if (pin_helper) (void)hipHostFree(pin_helper);
         if (rand_pin) (void)hipHostFree(rand_pin);
         if (adv_pin) (void)hipHostFree(adv_pin);
         if (hs) (void)hipStreamDestroy(hs);
@@ -1052,8 +109,6 @@ struct dehalo_prover {
             if (t.d_mult) (void)hipFree(t.d_mult);
         }
     }
-
-    const uint64_t* col_ptr(const DevMem& mem, size_t col, size_t len) const { return (const uint64_t*)mem.at(col * len); }
 
     int build_product_graphs() {
         const HostCS& cs = pk->cs;
@@ -1140,27 +195,28 @@ struct dehalo_prover {
             write_idx.push_back(idx(b_cols, ai, -1));
             write_idx.push_back(idx(b_cols, ti, 0));
         }
-        struct Q { int32_t r; const uint64_t* ptr; int64_t i; };
+        struct Q { int32_t r; const uint64_t* ptr; int64_t i; uint32_t blind; };      // (blind: the commitment's, read by the IPA multiopen)
         std::vector<Q> qs;
         auto cptr = [&](size_t c) { return (const uint64_t*)(polys + c * n); };
-        for (auto& q : cs.advice_q) qs.push_back({q.rotation, cptr(o_adv + q.index), idx(b_cols, o_adv + q.index, q.rotation)});
+        for (auto& q : cs.advice_q) qs.push_back({q.rotation, cptr(o_adv + q.index), idx(b_cols, o_adv + q.index, q.rotation), bi_adv + q.index});
         for (uint32_t s = 0; s < S; s++) {                                              // permutation::Constructed::open
-            qs.push_back({0, cptr(o_pz + s), idx(b_cols, o_pz + s, 0)});
-            qs.push_back({1, cptr(o_pz + s), idx(b_cols, o_pz + s, 1)});
+            qs.push_back({0, cptr(o_pz + s), idx(b_cols, o_pz + s, 0), bi_prod + s});
+            qs.push_back({1, cptr(o_pz + s), idx(b_cols, o_pz + s, 1), bi_prod + s});
         }
-        for (int s = (int)S - 2; s >= 0; s--) qs.push_back({last, cptr(o_pz + s), idx(b_cols, o_pz + s, last)});      // sets.iter().rev().skip(1)
+        for (int s = (int)S - 2; s >= 0; s--) qs.push_back({last, cptr(o_pz + s), idx(b_cols, o_pz + s, last), bi_prod + (uint32_t)s});      // sets.iter().rev().skip(1)
         for (uint32_t l = 0; l < L; l++) {                                              // lookup::Evaluated::open
             const size_t zc = o_lz + l, ai = o_perm + 2 * l, ti = o_perm + 2 * l + 1;
-            qs.push_back({0, cptr(zc), idx(b_cols, zc, 0)});
-            qs.push_back({0, cptr(ai), idx(b_cols, ai, 0)});
-            qs.push_back({0, cptr(ti), idx(b_cols, ti, 0)});
-            qs.push_back({-1, cptr(ai), idx(b_cols, ai, -1)});
-            qs.push_back({1, cptr(zc), idx(b_cols, zc, 1)});
+            const uint32_t zb = bi_prod + S + l, ab = bi_perm + 2 * l, tb = bi_perm + 2 * l + 1;
+            qs.push_back({0, cptr(zc), idx(b_cols, zc, 0), zb});
+            qs.push_back({0, cptr(ai), idx(b_cols, ai, 0), ab});
+            qs.push_back({0, cptr(ti), idx(b_cols, ti, 0), tb});
+            qs.push_back({-1, cptr(ai), idx(b_cols, ai, -1), ab});
+            qs.push_back({1, cptr(zc), idx(b_cols, zc, 1), zb});
         }
-        for (auto& q : cs.fixed_q) qs.push_back({q.rotation, col_ptr(pk->fixed_polys, q.index, n), idx(b_fixed, q.index, q.rotation)});
-        for (size_t j = 0; j < npc; j++) qs.push_back({0, col_ptr(pk->perm_polys, j, n), idx(b_sigma, j, 0)});      // pk.permutation.open
-        qs.push_back({0, hfold.u64(), -1});                                            // vanishing::Evaluated::open: h, then the random polynomial
-        qs.push_back({0, cptr(o_rand), idx(b_cols, o_rand, 0)});
+        for (auto& q : cs.fixed_q) qs.push_back({q.rotation, col_ptr(pk->fixed_polys, q.index, n), idx(b_fixed, q.index, q.rotation), bi_def});
+        for (size_t j = 0; j < npc; j++) qs.push_back({0, col_ptr(pk->perm_polys, j, n), idx(b_sigma, j, 0), bi_def});      // pk.permutation.open
+        qs.push_back({0, hfold.u64(), -1, bi_hfold});                                  // vanishing::Evaluated::open: h, then the random polynomial
+        qs.push_back({0, cptr(o_rand), idx(b_cols, o_rand, 0), bi_rand});
         groups.clear();
         for (auto& q : qs) {
             Group* g = nullptr;
@@ -1176,38 +232,19 @@ struct dehalo_prover {
         if (!ipa && groups.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more opening points than the prover's buffers hold");      // (GWC: qbuf / wbuf)
         ipa_inst_write.clear();
         if (ipa) {
-            // the queries in upstream's order (instance first), each with its commitment's blind
-            struct IQ { const uint64_t* ptr; uint32_t blind; int32_t rot; };
-            std::vector<IQ> iq;
+            // the queries in upstream's order: the instance columns' (default blind) in front of the others
+            std::vector<Q> iq;
             for (auto& q : cs.instance_q) {
-                iq.push_back({col_ptr(instance, q.index, n), bi_def, q.rotation});
-                ipa_inst_write.push_back(idx(b_inst, q.index, q.rotation));
+                iq.push_back({q.rotation, col_ptr(instance, q.index, n), idx(b_inst, q.index, q.rotation), bi_def});
+                ipa_inst_write.push_back(iq.back().i);
             }
-            for (auto& q : cs.advice_q) iq.push_back({cptr(o_adv + q.index), bi_adv + q.index, q.rotation});
-            for (uint32_t s = 0; s < S; s++) {
-                iq.push_back({cptr(o_pz + s), bi_prod + s, 0});
-                iq.push_back({cptr(o_pz + s), bi_prod + s, 1});
-            }
-            for (int s = (int)S - 2; s >= 0; s--) iq.push_back({cptr(o_pz + s), bi_prod + (uint32_t)s, last});
-            for (uint32_t l = 0; l < L; l++) {
-                const size_t zc = o_lz + l, ai = o_perm + 2 * l, ti = o_perm + 2 * l + 1;
-                const uint32_t zb = bi_prod + S + l, ab = bi_perm + 2 * l, tb = bi_perm + 2 * l + 1;
-                iq.push_back({cptr(zc), zb, 0});
-                iq.push_back({cptr(ai), ab, 0});
-                iq.push_back({cptr(ti), tb, 0});
-                iq.push_back({cptr(ai), ab, -1});
-                iq.push_back({cptr(zc), zb, 1});
-            }
-            for (auto& q : cs.fixed_q) iq.push_back({col_ptr(pk->fixed_polys, q.index, n), bi_def, q.rotation});
-            for (size_t j = 0; j < npc; j++) iq.push_back({col_ptr(pk->perm_polys, j, n), bi_def, 0});
-            iq.push_back({hfold.u64(), bi_hfold, 0});
-            iq.push_back({cptr(o_rand), bi_rand, 0});
+            iq.insert(iq.end(), qs.begin(), qs.end());
             // construct_intermediate_sets
             ipa_commitments.clear(); ipa_sets.clear(); ipa_point_rot.clear();
             std::vector<std::vector<uint32_t>> cpoints;
             for (auto& q : iq) {
-                uint32_t pi = (uint32_t)(std::find(ipa_point_rot.begin(), ipa_point_rot.end(), q.rot) - ipa_point_rot.begin());
-                if (pi == ipa_point_rot.size()) ipa_point_rot.push_back(q.rot);
+                uint32_t pi = (uint32_t)(std::find(ipa_point_rot.begin(), ipa_point_rot.end(), q.r) - ipa_point_rot.begin());
+                if (pi == ipa_point_rot.size()) ipa_point_rot.push_back(q.r);
                 size_t ci = 0;
                 while (ci < ipa_commitments.size() && !(ipa_commitments[ci].ptr == q.ptr && ipa_commitments[ci].blind == q.blind)) ci++;
                 if (ci == ipa_commitments.size()) {
@@ -1268,7 +305,6 @@ struct dehalo_prover {
         TRY(wbuf.alloc(ctx, 4 * n));
         const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, 8), std::max<uint32_t>(I, pieces));      // the most points one phase commits
         TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
-        TRY(jac_side.alloc(ctx, 3));
         // blinding values of a proof but the random polynomial, compacted: [advice rows | permuted rows | product rows]
         const size_t rows = n - u;
         TRY(blind_dev.alloc(ctx, std::max<size_t>(1, (size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf)));
@@ -1290,7 +326,6 @@ struct dehalo_prover {
         } else
         TRY(evals.alloc(ctx, eval_count + 8));
         for (hipEvent_t* e : {&ev_ready[0], &ev_ready[1], &ev_ready[2], &ev_inst, &ev_side, &ev_helper}) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
-        HIP_TRY(ctx, hipHostMalloc((void**)&pin_helper, 128, hipHostMallocDefault));
         HIP_TRY(ctx, hipHostMalloc((void**)&rand_pin, (size_t)n * 32, hipHostMallocDefault));
         if (side) HIP_TRY(ctx, hipStreamCreateWithFlags(&hs, hipStreamNonBlocking));
         host_aff.resize(8 * (size_t)maxpts);
@@ -1432,9 +467,6 @@ struct dehalo_prover {
         if (!ipa) return 32 * (points + groups.size() + write_idx.size());
         return 32 * (points + 2 + 2 * (size_t)k + ipa_inst_write.size() + write_idx.size() + ipa_sets.size() + 2);
     }
-
-    int run(const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng_in,
-            dehalo_transcript* tr, uint32_t flags, const dehalo_circuit_inputs* synth_in = nullptr, dehalo_synthesis_info* synth_info = nullptr);
 };
 
 namespace {
@@ -1448,137 +480,152 @@ struct EvalIn {      // dehalo_eval_inputs with owned scalar storage
     }
 };
 
-}   // namespace
+constexpr uint32_t FF = DEHALO_EVAL_COLUMNS_INTERNAL | DEHALO_EVAL_VALUES_INTERNAL;
+const Fe zero{{0, 0, 0, 0}};
 
-int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng_in,
-                       dehalo_transcript* tr, uint32_t flags, const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
-    const HostCS& cs = pk->cs;
-    const HostDomain& d = pk->dom;
-    const int fid = f->id;
-    const size_t rows = n - u;
-    const uint32_t rot_scale = (uint32_t)(m / n);
-    const auto t_start = clk::now();
-    auto t_phase = t_start;
-    ticks.clear();
-    t0 = t_start;
-    trace = getenv("DEHALO_PROVER_TRACE") != nullptr;
-    auto mark = [&](int slot) {
+// 1, c, ..., c^(count - 1), or descending: the coefficients of `count` terms folded as acc <- c acc + term (the multiopen's x_1, x_2, x_4)
+std::vector<Fe> powers(const HostField* f, const Fe& c, size_t count, bool descending = false) {
+    std::vector<Fe> out(count);
+    Fe pw = f->one;
+    for (size_t j = 0; j < count; j++) { out[descending ? count - 1 - j : j] = pw; pw = f->mul(pw, c); }
+    return out;
+}
+// sum of coefs[i] terms[i]: a value or a blind folded as its polynomials are
+Fe fold(const HostField* f, const Fe* coefs, const Fe* terms, size_t count) {
+    Fe acc = zero;
+    for (size_t i = 0; i < count; i++) acc = f->add(acc, f->mul(coefs[i], terms[i]));
+    return acc;
+}
+
+// One create_proof: what lives from the first draw to the last opening.  `p` is the prover (what outlives a proof: buffers, plans, events); the names copied from
+// it below are the circuit's shape.  Each phase is one member function, called by run() in upstream's order.
+struct ProofRun {
+    dehalo_prover& p;
+    dehalo_transcript* const tr;
+    dehalo_rng* const rng_in;
+    dehalo_ctx *const ctx, *const side;
+    const hipStream_t ms, ss;
+    const HostField* const f;
+    const HostCS& cs;
+    const HostDomain& d;
+    const int fid;
+    const size_t n, m, u, rows;
+    const uint32_t k, ek, bf, A, L, S, I, pieces, nco, rot_scale;
+    const bool ipa;
+    // one gate polynomial: Horner(0, [g], y) = g does not depend on y, so the custom-gate pass of evaluate_h needs the advice (and instance)
+    // cosets only -- queued on the side context right behind them, long before y exists
+    const bool gates_early;
+    const clk::time_point t_start = clk::now();
+    clk::time_point t_phase = t_start;
+
+    HostRng rng, rng_poly;      // the proof's generator; its fork at the random polynomial's position (the helper thread's)
+    bool device_rng = false;    // the large draw comes from a ChaCha20 kernel keyed with this proof's entropy
+    size_t c_adv = 0, c_advb = 0, c_lk = 0, c_pr = 0;      // how many scalars each group of blinding values draws
+    std::vector<Fe> bl;         // the proof's blinds by commitment (dehalo_prover: ipa_blinds)
+    std::thread helper;         // draws (and, with a side context, uploads) the random polynomial while the earlier phases run
+    std::atomic<int> helper_rc{0};
+    double helper_ms[3] = {};
+    // a host witness is pinned until this proof ends (every stream has been synchronised by then); one that is page-locked already stays as it is
+    std::unique_ptr<HostPin> pin_advice;
+    std::vector<const uint64_t*> fixed_v, adv_v, inst_v, fixed_c, adv_c, inst_c;      // pointer tables of the phases: values, cosets
+    Fe theta{}, beta{}, gamma{}, y{}, x{}, hfold_eval{};
+    std::vector<Fe> point, xs;      // x at every rotation of the plan; x^(n i)
+    const Fe* E = nullptr;          // the evaluations on the host, indexed by the opening plan
+
+    ProofRun(dehalo_prover& pv, dehalo_transcript* t, dehalo_rng* r)
+        : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream), ss(pv.side ? pv.side->stream : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
+          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), pieces(pv.pieces), nco(pv.NC - 1),
+          rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1) {}
+    ~ProofRun() {      // whatever path the proof took: the witness' copy (asynchronous) has landed before its pin goes, and the helper has finished
+        if (pin_advice && pin_advice->p) (void)hipStreamSynchronize(ms);
+        pin_advice.reset();
+        if (helper.joinable()) helper.join();
+    }
+    void mark(int slot) {
         const auto now = clk::now();
-        timings[slot] = std::chrono::duration<double, std::milli>(now - t_phase).count();
+        p.timings[slot] = std::chrono::duration<double, std::milli>(now - t_phase).count();
         t_phase = now;
-    };
-    (void)hipSetDevice(ctx->device);
-    hipStream_t ms = ctx->stream, ss = side ? side->stream : nullptr;
+    }
 
     // ---- random scalars, in upstream's order: advice blinding rows (column after column), one blind per advice column, per lookup (bf + 1 rows
     // permuted input, bf + 1 permuted table, the two columns' blinds), per grand product (bf rows + its blind), the random polynomial (n), its blind,
     // the h pieces' blinds and, under IPA, f's blind.  KZG commitments are not hiding: it draws the blinds and drops them.  No draw depends on the
     // device, so all of them are made here, in that order, and the blinds go up with the blinding rows in one copy.
-    HostRng rng;
-    TRY(rng.init(rng_in, f));
-    const size_t c_adv = (size_t)A * rows, c_advb = A, c_lk = (size_t)L * (2 * rows + 2), c_pr = (size_t)(S + L) * (bf + 1);
-    const size_t draws_before = c_adv + c_advb + c_lk + c_pr;
-    blind_host.resize(4 * std::max<size_t>(1, draws_before));
-    // the one large draw (n scalars, drawn AFTER every blinding value) is produced, uploaded and -- with a side context -- committed by a helper
-    // thread while the earlier phases run
-    HostRng rng_poly = rng.fork(draws_before, 1);
-    TRY(rng.scalars(blind_host.data(), draws_before));
-    rng.skip(n);                                             // the random polynomial: rng_poly's
-    std::vector<Fe> late(1 + (size_t)pieces + (ipa ? 1 : 0));      // random_blind, h_blinds, (IPA) f_blind
-    TRY(rng.scalars(late[0].v, late.size()));
-    std::vector<Fe> bl(bi_count, Fe{{0, 0, 0, 0}});         // the proof's blinds, by commitment (dehalo_prover: ipa_blinds)
-    if (ipa) {
-        const Fe* B = (const Fe*)blind_host.data();
-        for (uint32_t i = 0; i < A; i++) bl[bi_adv + i] = B[c_adv + i];
-        for (uint32_t l = 0; l < L; l++) {
-            bl[bi_perm + 2 * l] = B[c_adv + c_advb + (size_t)l * (2 * rows + 2) + 2 * rows];
-            bl[bi_perm + 2 * l + 1] = B[c_adv + c_advb + (size_t)l * (2 * rows + 2) + 2 * rows + 1];
+    int draw_blinds() {
+        TRY(rng.init(rng_in, f));
+        device_rng = rng.kind == DEHALO_RNG_OS;
+        c_adv = (size_t)A * rows; c_advb = A; c_lk = (size_t)L * (2 * rows + 2); c_pr = (size_t)(S + L) * (bf + 1);
+        const size_t draws_before = c_adv + c_advb + c_lk + c_pr;
+        p.blind_host.resize(4 * std::max<size_t>(1, draws_before));
+        // the one large draw (n scalars, drawn AFTER every blinding value) is produced and -- with a side context -- uploaded by a helper
+        // thread while the earlier phases run
+        rng_poly = rng.fork(draws_before, 1);
+        TRY(rng.scalars(p.blind_host.data(), draws_before));
+        rng.skip(n);                                             // the random polynomial: rng_poly's
+        std::vector<Fe> late(1 + (size_t)pieces + (ipa ? 1 : 0));      // random_blind, h_blinds, (IPA) f_blind
+        TRY(rng.scalars(late[0].v, late.size()));
+        bl.assign(p.bi_count, zero);
+        if (ipa) {
+            const Fe* B = (const Fe*)p.blind_host.data();
+            for (uint32_t i = 0; i < A; i++) bl[p.bi_adv + i] = B[c_adv + i];
+            for (uint32_t c = 0; c < 2 * L; c++) bl[p.bi_perm + c] = B[c_adv + c_advb + (size_t)(c / 2) * (2 * rows + 2) + 2 * rows + (c & 1)];
+            for (uint32_t s2 = 0; s2 < S + L; s2++) bl[p.bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
+            bl[p.bi_rand] = late[0];
+            for (uint32_t i = 0; i < pieces; i++) bl[p.bi_h + i] = late[1 + i];
+            bl[p.bi_f] = late[1 + pieces];
+            for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[p.bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
+            TRY(dh_h2d(ctx, p.ipa_blinds.p, bl.data(), (size_t)p.bi_count * 32, ctx->stream));      // (waited for with the blinding rows, upload_blinds)
         }
-        for (uint32_t s2 = 0; s2 < S + L; s2++) bl[bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
-        bl[bi_rand] = late[0];
-        for (uint32_t i = 0; i < pieces; i++) bl[bi_h + i] = late[1 + i];
-        bl[bi_f] = late[1 + pieces];
-        for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
-        TRY(dh_h2d(ctx, ipa_blinds.p, bl.data(), (size_t)bi_count * 32, ctx->stream));      // (waited for with the blinding rows below)
-    }
-    std::atomic<int> helper_rc{0};
-    uint64_t rand_point[8] = {};
-    std::thread helper;
-    double helper_ms[3] = {};
-    const bool device_rng = rng.kind == DEHALO_RNG_OS;      // the large draw comes from a ChaCha20 kernel keyed with this proof's entropy
-    // The random polynomial's commitment.  Committing COEFFICIENTS over g equals committing their forward transform (the values on the domain) over g_lagrange,
-    // and upstream writes the point right behind the grand products' commitments with no challenge in between: so (round 4, with a side context) the helper only
-    // draws and uploads, and the polynomial rides as ONE MORE COLUMN of the products' MSM launch -- a whole sort / accumulate / merge / reduce pipeline per proof
-    // less, and none running beside the lookups' phase.  DEHALO_PROVER_RANDOM_SEPARATE=1: the helper commits it with an MSM of its own, as in round 3 (A/B measurements).
-    static const bool random_separate_env = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_PROVER_RANDOM_SEPARATE"); return e && e[0] == '1'; }();
-    const bool random_separate = random_separate_env && !ipa;      // (the helper's own MSM would leave the point unblinded)
-    auto device_draw = [&](fe* dst, hipStream_t st) -> int {
-        ChaKey ck;
-        memcpy(ck.k, rng.key, 32);
-        fe pw;
-        for (int i = 0; i < 4; i++) { pw.v[2 * i] = (u32)f->p[i]; pw.v[2 * i + 1] = (u32)(f->p[i] >> 32); }
-        const u32 top_mask = f->bits >= 256 ? 0xffffffffu : ((1u << (f->bits - 224)) - 1);
-        k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(ck, /* stream of the fork */ 1, pw, top_mask, dst, n);
-        HIP_TRY(ctx, hipGetLastError());
         return 0;
-    };
-    auto helper_body = [&]() {
+    }
+
+    // The random polynomial's commitment.  Committing COEFFICIENTS over g equals committing their forward transform (the values on the domain) over g_lagrange,
+    // and upstream writes the point right behind the grand products' commitments with no challenge in between: so the helper only draws and (with a side
+    // context) uploads, and the polynomial rides as ONE MORE COLUMN of the products' MSM launch -- a whole sort / accumulate / merge / reduce pipeline per proof
+    // less, and none running beside the lookups' phase.
+    void start_random_polynomial() { helper = std::thread([this] { helper_body(); }); }
+    void helper_body() {
         (void)hipSetDevice(ctx->device);
         const auto th0 = clk::now();
         int rc = 0;
-        if (!device_rng) {
-            rc = rng_poly.scalars(rand_pin, n);
-        }
+        if (!device_rng) rc = rng_poly.scalars(p.rand_pin, n);
         helper_ms[0] = ms_since(th0);
-        if (!rc) {
-            if (side) {
-                fe* dst = polys + (size_t)o_rand * n;
-                hipError_t e = hipSuccess;
-                if (device_rng) rc = device_draw(dst, hs);
-                else e = hipMemcpyAsync(dst, rand_pin, n * 32, hipMemcpyHostToDevice, hs);
-                if (e != hipSuccess) rc = dh_fail(side, DEHALO_ERR_HIP, std::string("random polynomial upload: ") + hipGetErrorString(e));
-                if (!rc && random_separate) rc = dehalo_msm_device(side, params->bases_g, (const uint64_t*)dst, n, 1, jac_side.u64(), hs);      // (the side context's MSM workspace is this thread's alone)
-                helper_ms[1] = ms_since(th0);
-                if (!rc) {      // wait for this stream through an event of this thread's own: the coefficients (and the point) are there before the join
-                    if (random_separate) e = hipMemcpyAsync(pin_helper, jac_side.p, 96, hipMemcpyDeviceToHost, hs);
-                    if (e == hipSuccess) e = hipEventRecord(ev_helper, hs);
-                    if (e == hipSuccess) e = hipEventSynchronize(ev_helper);
-                    if (e != hipSuccess) rc = dh_fail(side, DEHALO_ERR_HIP, std::string("random polynomial: ") + hipGetErrorString(e));
-                }
-                if (!rc && random_separate && !normalize_host(pin_helper, 1, rand_point)) memset(rand_point, 0, sizeof rand_point);      // (the identity: refused by write_point below)
-                helper_ms[2] = ms_since(th0);
-            } else {
-                // without a side context only the draw is taken off the critical path; the upload is queued by the proving thread
+        if (!rc && side) {      // (without a side context only the draw is taken off the critical path; the upload is queued by the proving thread)
+            fe* dst = p.polys + (size_t)p.o_rand * n;
+            hipError_t e = hipSuccess;
+            if (device_rng) rc = chacha_scalars_device(ctx, rng_poly, 1, dst, n, p.hs);
+            else e = hipMemcpyAsync(dst, p.rand_pin, n * 32, hipMemcpyHostToDevice, p.hs);
+            if (e != hipSuccess) rc = dh_fail(side, DEHALO_ERR_HIP, std::string("random polynomial upload: ") + hipGetErrorString(e));
+            helper_ms[1] = ms_since(th0);
+            if (!rc) {      // wait for this stream through an event of this thread's own: the coefficients are there before the join
+                e = hipEventRecord(p.ev_helper, p.hs);
+                if (e == hipSuccess) e = hipEventSynchronize(p.ev_helper);
+                if (e != hipSuccess) rc = dh_fail(side, DEHALO_ERR_HIP, std::string("random polynomial: ") + hipGetErrorString(e));
             }
+            helper_ms[2] = ms_since(th0);
         }
         helper_rc.store(rc);
-    };
-    struct Joiner {      // the helper must have finished before this call returns, whatever path it takes
-        std::thread& t;
-        ~Joiner() { if (t.joinable()) t.join(); }
-    } joiner{helper};
-
-    // create_proof of a CIRCUIT (upstream's call synthesizes inside): the random polynomial's draw, upload and commitment start now, on the helper's
-    // thread and stream, and run on an otherwise idle device while this thread (and the synthesis pool) writes the advice columns
-    if (synth_in) {
-        if (synth_in->k != k || A != 5) return dh_fail(ctx, DEHALO_ERR_INVALID, "create_proof_circuit: the circuit's k / advice columns differ from the key's");
-        if (!adv_pin) HIP_TRY(ctx, hipHostMalloc((void**)&adv_pin, (size_t)A * n * 32, hipHostMallocDefault));
-        helper = std::thread(helper_body);
-        const int src = dehalo_synthesize(synth_in, adv_pin, nullptr, nullptr, nullptr, synth_info);
-        if (src) return dh_fail(ctx, src, "create_proof_circuit: the circuit's inputs are invalid or it does not fit 2^k rows");
-        advice = adv_pin;
-        flags = (flags & ~(uint32_t)DEHALO_PROOF_ADVICE_ON_DEVICE) | DEHALO_PROOF_ADVICE_CANONICAL;
-        tk("witness synthesized");
     }
 
-    // compacted blinding rows -> one upload
-    {
+    // create_proof of a CIRCUIT (upstream's call synthesizes inside): the random polynomial's draw and upload start now, on the helper's thread and
+    // stream, and run on an otherwise idle device while this thread (and the synthesis pool) writes the advice columns
+    int synthesize(const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
+        if (synth_in->k != k || A != 5) return dh_fail(ctx, DEHALO_ERR_INVALID, "create_proof_circuit: the circuit's k / advice columns differ from the key's");
+        if (!p.adv_pin) HIP_TRY(ctx, hipHostMalloc((void**)&p.adv_pin, (size_t)A * n * 32, hipHostMallocDefault));
+        start_random_polynomial();
+        const int src = dehalo_synthesize(synth_in, p.adv_pin, nullptr, nullptr, nullptr, synth_info);
+        if (src) return dh_fail(ctx, src, "create_proof_circuit: the circuit's inputs are invalid or it does not fit 2^k rows");
+        p.tk("witness synthesized");
+        return 0;
+    }
+
+    // compacted blinding rows [advice | permuted | products] -> one upload
+    int upload_blinds() {
         const size_t total = (size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf;
-        std::vector<uint64_t>& b = blind_host;
+        std::vector<uint64_t>& b = p.blind_host;
         std::vector<uint64_t> packed(4 * std::max<size_t>(1, total));
-        size_t o = 0;
+        size_t o = c_adv;
         memcpy(packed.data(), b.data(), 32 * c_adv);
-        o += c_adv;
         const uint64_t* lk = b.data() + 4 * (c_adv + c_advb);
         for (uint32_t l = 0; l < L; l++) {      // (input rows, table rows, two unused blinds) per lookup
             memcpy(packed.data() + 4 * o, lk + 4 * (size_t)l * (2 * rows + 2), 32 * 2 * rows);
@@ -1589,168 +636,148 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
             memcpy(packed.data() + 4 * o, pr + 4 * (size_t)s * (bf + 1), 32 * bf);
             o += bf;
         }
-        if (total) TRY(dh_h2d(ctx, blind_dev.p, packed.data(), total * 32, ms));
-        if (total || ipa) HIP_TRY(ctx, hipStreamSynchronize(ms));      // `packed` and `bl` are locals
+        if (total) TRY(dh_h2d(ctx, p.blind_dev.p, packed.data(), total * 32, ms));
+        if (total || ipa) HIP_TRY(ctx, hipStreamSynchronize(ms));      // `packed` is a local (and the blinds' copy of draw_blinds lands here)
+        p.tk("blinds drawn and uploaded");
+        return 0;
     }
-    tk("blinds drawn and uploaded");
-    const fe* bl_adv = blind_dev.p;
-    const fe* bl_perm = blind_dev.p + (size_t)A * rows;
-    const fe* bl_prod = bl_perm + (size_t)2 * L * rows;
 
-    tr->common_scalar(pk->transcript_repr);      // vk.hash_into
     // ---- instance columns: values into the transcript (KZG: QUERY_INSTANCE = false), polynomials on the device
-    if (num_instance_columns != I) return dh_fail(ctx, DEHALO_ERR_INVALID, "instances.len() != num_instance_columns");      // Error::InvalidInstances
-    if (I) HIP_TRY(ctx, hipMemsetAsync(instance.p, 0, (size_t)I * n * 32, ms));
-    for (uint32_t i = 0; i < I; i++) {
-        const size_t len = instance_lens ? instance_lens[i] : 0;
-        if (len > u) return dh_fail(ctx, DEHALO_ERR_INVALID, "instance column too long");      // Error::InstanceTooLarge
-        if (len && (!instances || !instances[i])) return dh_fail(ctx, DEHALO_ERR_INVALID, "null instance column");
-        for (size_t j = 0; j < len && !ipa; j++) {
-            Fe v;
-            memcpy(v.v, instances[i] + 4 * j, 32);
-            tr->common_scalar(v);
+    int instance_columns(const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns) {
+        if (num_instance_columns != I) return dh_fail(ctx, DEHALO_ERR_INVALID, "instances.len() != num_instance_columns");      // Error::InvalidInstances
+        if (I) HIP_TRY(ctx, hipMemsetAsync(p.instance.p, 0, (size_t)I * n * 32, ms));
+        for (uint32_t i = 0; i < I; i++) {
+            const size_t len = instance_lens ? instance_lens[i] : 0;
+            if (len > u) return dh_fail(ctx, DEHALO_ERR_INVALID, "instance column too long");      // Error::InstanceTooLarge
+            if (len && (!instances || !instances[i])) return dh_fail(ctx, DEHALO_ERR_INVALID, "null instance column");
+            for (size_t j = 0; j < len && !ipa; j++) {
+                Fe v;
+                memcpy(v.v, instances[i] + 4 * j, 32);
+                tr->common_scalar(v);
+            }
+            if (len) {
+                TRY(dh_h2d(ctx, p.instance.at((size_t)i * n), instances[i], len * 32, ms));
+                HIP_TRY(ctx, hipStreamSynchronize(ms));
+            }
         }
-        if (len) {
-            TRY(dh_h2d(ctx, instance.at((size_t)i * n), instances[i], len * 32, ms));
-            HIP_TRY(ctx, hipStreamSynchronize(ms));
-        }
+        // IPA (QUERY_INSTANCE = true): commit_lagrange(instance, Blind::default()), absorbed as points
+        if (I && ipa) TRY(p.commit(tr, p.instance.p, I, true, nullptr, 0, p.blind_at(p.bi_def), false));
+        if (I) HIP_TRY(ctx, hipMemcpyAsync(p.instance_values.p, p.instance.p, (size_t)I * n * 32, hipMemcpyDeviceToDevice, ms));
+        if (I && side) HIP_TRY(ctx, hipEventRecord(p.ev_inst, ms));
+        if (I && !side) TRY(dehalo_intt_scaled_device(ctx, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
+        return 0;
     }
-    // IPA (QUERY_INSTANCE = true): commit_lagrange(instance, Blind::default()), absorbed as points
-    if (I && ipa) TRY(commit(tr, instance.p, I, true, nullptr, 0, blind_at(bi_def), false));
-    if (I) HIP_TRY(ctx, hipMemcpyAsync(instance_values.p, instance.p, (size_t)I * n * 32, hipMemcpyDeviceToDevice, ms));
-    const uint32_t nco = NC - 1;
-    if (I && side) HIP_TRY(ctx, hipEventRecord(ev_inst, ms));
-    if (I && !side) TRY(dehalo_intt_scaled_device(ctx, fid, instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
 
-    auto side_ntt = [&](uint32_t first, uint32_t count, hipEvent_t e) -> int {
-        // polys[first..] = lagrange_to_coeff(cols[..]), ext[..] = coeff_to_extended(..) on the side context once `e` (recorded BEFORE the phase's
-        // commitment was queued) has passed; the launches themselves are made after the commitment's, while this thread would only wait
+    // polys[first..] = lagrange_to_coeff(cols[..]), ext[..] = coeff_to_extended(..) on the side context once `e` (recorded BEFORE the phase's
+    // commitment was queued) has passed; the launches themselves are made after the commitment's, while this thread would only wait
+    EvalIn coset_inputs() const {      // every column over the extended domain, internal form
+        EvalIn e;
+        e.cols(fixed_c, adv_c, inst_c);
+        e.in.form_flags = FF;
+        return e;
+    }
+    int side_ntt(uint32_t first, uint32_t count, hipEvent_t e) {
         HIP_TRY(side, hipStreamWaitEvent(ss, e, 0));
         // (out of place: no copy of the columns first -- a 42 MB device-to-device hipMemcpyAsync held this thread for 0.4 ms in the lookups' phase)
-        TRY(dehalo_lagrange_to_coeff_device(side, fid, (const uint64_t*)cols.at((size_t)first * n), (uint64_t*)(polys + (size_t)first * n), k, d.omega_inv.v, d.ifft_divisor.v, count,
-                                            nullptr));
-        TRY(dehalo_coset_ntt_form_device(side, fid, (const uint64_t*)(polys + (size_t)first * n), k, ext.u64((size_t)first * m), ek, d.ext_omega.v, d.g_coset.v, count,
+        TRY(dehalo_lagrange_to_coeff_device(side, fid, (const uint64_t*)p.cols.at((size_t)first * n), (uint64_t*)(p.polys + (size_t)first * n), k, d.omega_inv.v, d.ifft_divisor.v,
+                                            count, nullptr));
+        TRY(dehalo_coset_ntt_form_device(side, fid, (const uint64_t*)(p.polys + (size_t)first * n), k, p.ext.u64((size_t)first * m), ek, d.ext_omega.v, d.g_coset.v, count,
                                          DEHALO_FORM_OUT_INTERNAL, nullptr));
         return 0;
-    };
+    }
 
     // ---- advice: witness, blinding rows, commitments
-    if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
-    // a host witness is pinned until this call returns (every stream has been synchronised by then); one that is page-locked already stays as it is
-    struct PinnedUpload {      // (the copy below is asynchronous: on every way out, wait for its stream before the pin goes)
-        HostPin pin;
-        hipStream_t s;
-        PinnedUpload(const void* ptr, size_t bytes, hipStream_t s_) : pin(ptr, bytes), s(s_) {}
-        ~PinnedUpload() { if (pin.p) (void)hipStreamSynchronize(s); }
-    } pin_advice((flags & DEHALO_PROOF_ADVICE_ON_DEVICE) || synth_in ? nullptr : advice, (size_t)A * n * 32, ms);
-    if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(cols.at((size_t)o_adv * n), advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
-    else TRY(dh_h2d(ctx, cols.at((size_t)o_adv * n), advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
-    if (flags & DEHALO_PROOF_ADVICE_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, cols.u64((size_t)o_adv * n), nullptr, cols.u64((size_t)o_adv * n), (size_t)A * n, nullptr));
-    if (A) k_place_rows<<<(unsigned)((rows * A + 255) / 256), 256, 0, ms>>>(cols.at((size_t)o_adv * n + u), n, bl_adv, (uint32_t)rows, A);
-    if (side) HIP_TRY(ctx, hipEventRecord(ev_ready[0], ms));
-
-    // pointer tables of the phases
-    std::vector<const uint64_t*> fixed_v, adv_v, inst_v, fixed_c, adv_c, inst_c, none;
-    for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(pk->fixed_cosets, i, m));
-    for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(cols, o_adv + i, n)), adv_c.push_back(col_ptr(ext, o_adv + i, m));
-    for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(instance_values, i, n)), inst_c.push_back(col_ptr(ext, nco + i, m));
-    const uint32_t FF = DEHALO_EVAL_COLUMNS_INTERNAL | DEHALO_EVAL_VALUES_INTERNAL;
-    // one gate polynomial: Horner(0, [g], y) = g does not depend on y, so the custom-gate pass of evaluate_h needs the advice (and instance)
-    // cosets only -- queued on the side context right behind them, long before y exists
-    const bool gates_early = side && cs.gates.size() == 1;
-    const Fe zero{{0, 0, 0, 0}};
-
-    auto after_advice_queued = [&]() -> int {
+    int advice_columns(const uint64_t* advice, uint32_t flags) {
+        if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
+        const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin;      // (the witness generator's output is page-locked already)
+        pin_advice.reset(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
+        fe* adv = p.cols.at((size_t)p.o_adv * n);
+        if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
+        else TRY(dh_h2d(ctx, adv, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
+        if (flags & DEHALO_PROOF_ADVICE_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, (uint64_t*)adv, nullptr, (uint64_t*)adv, (size_t)A * n, nullptr));
+        if (A) k_place_rows<<<(unsigned)((rows * A + 255) / 256), 256, 0, ms>>>(adv + u, n, p.blind_dev.p, (uint32_t)rows, A);
+        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[0], ms));
+        for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(p.pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(p.pk->fixed_cosets, i, m));
+        for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.o_adv + i, n)), adv_c.push_back(col_ptr(p.ext, p.o_adv + i, m));
+        for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(p.instance_values, i, n)), inst_c.push_back(col_ptr(p.ext, nco + i, m));
+        return p.commit(tr, adv, A, true, [this] { return after_advice_queued(); }, 0, p.blind_at(p.bi_adv));
+    }
+    int after_advice_queued() {
         if (I && side) {
-            HIP_TRY(side, hipStreamWaitEvent(ss, ev_inst, 0));
-            TRY(dehalo_intt_scaled_device(side, fid, instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
-            TRY(dehalo_coset_ntt_form_device(side, fid, instance.u64(), k, ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
+            HIP_TRY(side, hipStreamWaitEvent(ss, p.ev_inst, 0));
+            TRY(dehalo_intt_scaled_device(side, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
+            TRY(dehalo_coset_ntt_form_device(side, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         }
-        if (side) TRY(side_ntt(o_adv, A, ev_ready[0]));
+        if (side) TRY(side_ntt(p.o_adv, A, p.ev_ready[0]));
         if (gates_early) {
-            EvalIn e;
-            e.cols(fixed_c, adv_c, inst_c);
-            e.in.form_flags = FF;
+            EvalIn e = coset_inputs();
             e.in.y = zero.v;
-            TRY(dehalo_graph_evaluate_device(side, pk->custom_gates, &e.in, ek, rot_scale, nullptr, h.u64(), nullptr));
+            TRY(dehalo_graph_evaluate_device(side, p.pk->custom_gates, &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
         }
-        if (!synth_in) helper = std::thread(helper_body);      // the host is idle from here to the read-back
+        if (!helper.joinable()) start_random_polynomial();      // (unless it runs since the synthesis) the host is idle from here to the read-back
         return 0;
-    };
-    TRY(commit(tr, cols.at((size_t)o_adv * n), A, true, after_advice_queued, 0, blind_at(bi_adv)));
-    mark(0);
-    const Fe theta = tr->squeeze();
-    tk("theta");
+    }
 
     // ---- lookups: compress, permute, blind, commit
-    if (L) {
+    int lookups() {
+        if (!L) return 0;
         std::vector<const dehalo_graph*> graphs;
         std::vector<uint64_t*> outs;
         for (uint32_t l = 0; l < L; l++) {      // lookups with the same table expressions share ONE compressed table column (their representative's)
-            graphs.push_back(pk->compress_graphs[l].first);
-            outs.push_back(compressed.u64((size_t)2 * l * n));
-            if (table_rep[l] == l) {
-                graphs.push_back(pk->compress_graphs[l].second);
-                outs.push_back(compressed.u64((size_t)(2 * l + 1) * n));
+            graphs.push_back(p.pk->compress_graphs[l].first);
+            outs.push_back(p.compressed.u64((size_t)2 * l * n));
+            if (p.table_rep[l] == l) {
+                graphs.push_back(p.pk->compress_graphs[l].second);
+                outs.push_back(p.compressed.u64((size_t)(2 * l + 1) * n));
             }
         }
         EvalIn e;
         e.cols(fixed_v, adv_v, inst_v);
         e.in.theta = theta.v;
         TRY(dehalo_graph_evaluate_batch_device(ctx, graphs.data(), (uint32_t)graphs.size(), &e.in, k, 1, outs.data(), nullptr));
-        tk("compress queued");
+        p.tk("compress queued");
         // the blinding rows [u, n) first: the permutation writes rows [0, u) only and ends with a read-back
-        k_place_rows<<<(unsigned)((rows * 2 * L + 255) / 256), 256, 0, ms>>>(cols.at((size_t)o_perm * n + u), n, bl_perm, (uint32_t)rows, 2 * L);
+        const fe* bl_perm = p.blind_dev.p + (size_t)A * rows;
+        k_place_rows<<<(unsigned)((rows * 2 * L + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.o_perm * n + u), n, bl_perm, (uint32_t)rows, 2 * L);
         std::vector<const uint64_t*> pin, ptab;
         std::vector<uint64_t*> pout_in, pout_tab;
         for (uint32_t l = 0; l < L; l++) {
-            pin.push_back(compressed.u64((size_t)2 * l * n));
-            ptab.push_back(compressed.u64((size_t)(2 * table_rep[l] + 1) * n));
-            pout_in.push_back(cols.u64((size_t)(o_perm + 2 * l) * n));
-            pout_tab.push_back(cols.u64((size_t)(o_perm + 2 * l + 1) * n));
+            pin.push_back(p.compressed.u64((size_t)2 * l * n));
+            ptab.push_back(p.compressed.u64((size_t)(2 * p.table_rep[l] + 1) * n));
+            pout_in.push_back(p.cols.u64((size_t)(p.o_perm + 2 * l) * n));
+            pout_tab.push_back(p.cols.u64((size_t)(p.o_perm + 2 * l + 1) * n));
         }
         // status flags behind the 2 L points of this phase: the stream runs from the permutation straight into the commitment, the flags come back with the points
         std::vector<const uint32_t*> trep, tmult;
         std::vector<uint32_t> tcount;
         for (uint32_t l = 0; l < L; l++) {
-            const TableRows& t = table_rows[table_rep[l]];
+            const dehalo_prover::TableRows& t = p.table_rows[p.table_rep[l]];
             trep.push_back(t.d_rep); tmult.push_back(t.d_mult); tcount.push_back(t.count);
         }
         TRY(dehalo_permute_expression_pair_distinct_device(ctx, fid, pin.data(), ptab.data(), u, L, pout_in.data(), pout_tab.data(), trep.data(), tmult.data(), tcount.data(),
-                                                           reinterpret_cast<int32_t*>(jac.u64() + 12 * 2 * (size_t)L), nullptr));
-        tk("permute queued");
-        if (side) HIP_TRY(ctx, hipEventRecord(ev_ready[1], ms));
-        TRY(commit(tr, cols.at((size_t)o_perm * n), 2 * L, true, side ? std::function<int()>([&]() { return side_ntt(o_perm, 2 * L, ev_ready[1]); }) : nullptr, L, blind_at(bi_perm)));
+                                                           reinterpret_cast<int32_t*>(p.jac.u64() + 12 * 2 * (size_t)L), nullptr));
+        p.tk("permute queued");
+        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[1], ms));
+        return p.commit(tr, p.cols.at((size_t)p.o_perm * n), 2 * L, true, side ? std::function<int()>([this] { return after_lookups_queued(); }) : nullptr, L, p.blind_at(p.bi_perm));
     }
-    mark(1);
-    const Fe beta = tr->squeeze();
-    const Fe gamma = tr->squeeze();
-    tk("beta gamma");
+    int after_lookups_queued() { return side_ntt(p.o_perm, 2 * L, p.ev_ready[1]); }
 
-    // ---- grand products: permutation sets, then lookups; one batched inversion
-    const uint32_t npc = (uint32_t)cs.perm_cols.size();
-    const uint32_t extra = random_separate ? 0u : 1u;      // the random polynomial's values as the launch's last column (cols[o_rand] sits right behind the products)
-    if (extra) {
+    // ---- grand products: permutation sets, then lookups; one batched inversion.  The random polynomial's values are the launch's last column
+    // (cols[o_rand] sits right behind the products): its commitment is written with theirs
+    int products_and_random() {
+        const uint32_t npc = (uint32_t)cs.perm_cols.size();
         if (helper.joinable()) helper.join();              // (long finished: the draw takes 0.5 ms at k = 17 and started before the advice commitment)
-        tk("helper joined");
+        p.tk("helper joined");
         if (helper_rc.load()) return helper_rc.load();
-        fe* rl = cols.at((size_t)o_rand * n);
-        if (side) HIP_TRY(ctx, hipMemcpyAsync(rl, polys + (size_t)o_rand * n, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));      // (the helper put the coefficients there)
+        fe* rl = p.cols.at((size_t)p.o_rand * n);
+        if (side) HIP_TRY(ctx, hipMemcpyAsync(rl, p.polys + (size_t)p.o_rand * n, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));      // (the helper put the coefficients there)
         else {      // without a side context the coefficient forms live in `cols` itself: keep a copy for after the commitment
-            if (device_rng) TRY(device_draw(rl, ms));
-            else HIP_TRY(ctx, hipMemcpyAsync(rl, rand_pin, n * 32, hipMemcpyHostToDevice, ms));      // (rand_pin: page-locked, the library's own)
-            HIP_TRY(ctx, hipMemcpyAsync(wbuf.p, rl, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
+            if (device_rng) TRY(chacha_scalars_device(ctx, rng_poly, 1, rl, n, ms));
+            else HIP_TRY(ctx, hipMemcpyAsync(rl, p.rand_pin, n * 32, hipMemcpyHostToDevice, ms));      // (rand_pin: page-locked, the library's own)
+            HIP_TRY(ctx, hipMemcpyAsync(p.wbuf.p, rl, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
         }
         TRY(dehalo_ntt_device(ctx, fid, (uint64_t*)rl, k, d.omega.v, 1, nullptr));
-    }
-    auto restore_random = [&]() -> int {      // (queued behind the MSM's kernels on the same stream)
-        if (extra && !side) HIP_TRY(ctx, hipMemcpyAsync(cols.at((size_t)o_rand * n), wbuf.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
-        return 0;
-    };
-    if (S + L == 0 && extra) {
-        TRY(commit(tr, cols.at((size_t)o_rand * n), 1, true, [&]() { return restore_random(); }, 0, blind_at(bi_rand)));
-    }
-    if (S + L) {
+        if (S + L == 0) return p.commit(tr, rl, 1, true, [this] { return restore_random(); }, 0, p.blind_at(p.bi_rand));
         std::vector<Fe> chal(std::max<uint32_t>(npc, 1));
         Fe dj = beta;
         for (uint32_t j = 0; j < npc; j++) {
@@ -1760,204 +787,167 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
         // every product's numerator and denominator columns in ONE launch (k_product_terms) instead of a GraphEvaluator program per column
         std::vector<const uint64_t*> pcolv, psig, pA, pS, pa, ps;
         for (auto& pc : cs.perm_cols) pcolv.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_v[pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_v[pc.index] : inst_v[pc.index]);
-        for (uint32_t j = 0; j < npc; j++) psig.push_back(col_ptr(pk->perm_values, j, n));
+        for (uint32_t j = 0; j < npc; j++) psig.push_back(col_ptr(p.pk->perm_values, j, n));
         for (uint32_t l = 0; l < L; l++) {
-            pA.push_back(col_ptr(compressed, 2 * l, n));
-            pS.push_back(col_ptr(compressed, 2 * table_rep[l] + 1, n));
-            pa.push_back(col_ptr(cols, o_perm + 2 * l, n));
-            ps.push_back(col_ptr(cols, o_perm + 2 * l + 1, n));
+            pA.push_back(col_ptr(p.compressed, 2 * l, n));
+            pS.push_back(col_ptr(p.compressed, 2 * p.table_rep[l] + 1, n));
+            pa.push_back(col_ptr(p.cols, p.o_perm + 2 * l, n));
+            ps.push_back(col_ptr(p.cols, p.o_perm + 2 * l + 1, n));
         }
         std::vector<Fe> set_factors(std::max<uint32_t>(S, 1));
         for (uint32_t s2 = 0; s2 < S; s2++) set_factors[s2] = chal[std::min<uint32_t>(s2 * cs.chunk_len(), npc ? npc - 1 : 0)];      // beta delta^(first column of the set)
         dehalo_product_inputs pin{};
         pin.columns = pcolv.data(); pin.sigma = psig.data(); pin.num_columns = npc; pin.chunk_len = cs.chunk_len();
-        pin.omega_powers = omega_col.u64();
+        pin.omega_powers = p.omega_col.u64();
         pin.beta = beta.v; pin.gamma = gamma.v; pin.delta = f->delta.v;
         pin.set_factors = (const uint64_t*)set_factors.data();
         pin.compressed_input = pA.data(); pin.compressed_table = pS.data(); pin.permuted_input = pa.data(); pin.permuted_table = ps.data();
         pin.num_lookups = L;
-        TRY(dehalo_product_terms_device(ctx, fid, &pin, n, num.u64(), den.u64(), n, nullptr));
-        tk("product graphs queued");
-        TRY(dehalo_grand_product_batch_device(ctx, fid, num.u64(), den.u64(), n, S + L, n, cols.u64((size_t)o_pz * n), nullptr));
+        TRY(dehalo_product_terms_device(ctx, fid, &pin, n, p.num.u64(), p.den.u64(), n, nullptr));
+        p.tk("product graphs queued");
+        TRY(dehalo_grand_product_batch_device(ctx, fid, p.num.u64(), p.den.u64(), n, S + L, n, p.cols.u64((size_t)p.o_pz * n), nullptr));
         for (uint32_t s = 1; s < S; s++)      // z_s starts where z_{s-1} ended: z = vec![last_z]
-            TRY(dehalo_scale_device(ctx, fid, cols.u64((size_t)(o_pz + s) * n), n, nullptr, 0, cols.u64((size_t)(o_pz + s - 1) * n + u), nullptr));
+            TRY(dehalo_scale_device(ctx, fid, p.cols.u64((size_t)(p.o_pz + s) * n), n, nullptr, 0, p.cols.u64((size_t)(p.o_pz + s - 1) * n + u), nullptr));
         // per column: bf blinding rows (n - bf .. n)
-        k_place_rows<<<(unsigned)(((size_t)bf * (S + L) + 255) / 256), 256, 0, ms>>>(cols.at((size_t)o_pz * n + (n - bf)), n, bl_prod, bf, S + L);
-        if (side) HIP_TRY(ctx, hipEventRecord(ev_ready[2], ms));
-        auto after_products_queued = [&]() -> int {
-            TRY(restore_random());
-            if (!side) return 0;
-            TRY(side_ntt(o_pz, S + L, ev_ready[2]));
-            // the lookups' (compressed input + beta)(compressed table + gamma) over the extended domain need theta, beta, gamma and the advice /
-            // fixed cosets: all there -- on the side context, beside the products' commitment, instead of after y
-            if (L) {
-                std::vector<const dehalo_graph*> graphs(pk->lookup_graphs.begin(), pk->lookup_graphs.end());
-                std::vector<uint64_t*> outs;
-                for (uint32_t l = 0; l < L; l++) outs.push_back(table_value.u64((size_t)l * m));
-                EvalIn e;
-                e.cols(fixed_c, adv_c, inst_c);
-                e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
-                e.in.form_flags = FF;
-                TRY(dehalo_graph_evaluate_batch_device(side, graphs.data(), L, &e.in, ek, rot_scale, outs.data(), nullptr));
-            }
-            return 0;
-        };
-        TRY(commit(tr, cols.at((size_t)o_pz * n), S + L + extra, true, std::function<int()>(after_products_queued), 0, blind_at(bi_prod)));
+        const fe* bl_prod = p.blind_dev.p + (size_t)(A + 2 * L) * rows;
+        k_place_rows<<<(unsigned)(((size_t)bf * (S + L) + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.o_pz * n + (n - bf)), n, bl_prod, bf, S + L);
+        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[2], ms));
+        return p.commit(tr, p.cols.at((size_t)p.o_pz * n), S + L + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.bi_prod));
     }
-    mark(2);
-
-    // ---- vanishing argument: a random polynomial
-    tk("products done");
-    if (helper.joinable()) helper.join();
-    tk("helper joined");
-    if (trace) fprintf(stderr, "  helper: draw %.3f, upload + commit queued %.3f, point on host %.3f ms after its start\n", helper_ms[0], helper_ms[1], helper_ms[2]);
-    if (helper_rc.load()) return helper_rc.load();
-    if (!random_separate) {
-        // (written with the products' commitments above)
-    } else if (side) {
-        if (!tr->write_point(rand_point)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
-    } else {
-        if (device_rng) TRY(device_draw(cols.at((size_t)o_rand * n), ms));
-        else HIP_TRY(ctx, hipMemcpyAsync(cols.at((size_t)o_rand * n), rand_pin, n * 32, hipMemcpyHostToDevice, ms));      // (rand_pin: page-locked, the library's own)
-        TRY(commit(tr, cols.at((size_t)o_rand * n), 1, false));
+    int restore_random() {      // (queued behind the MSM's kernels on the same stream)
+        if (!side) HIP_TRY(ctx, hipMemcpyAsync(p.cols.at((size_t)p.o_rand * n), p.wbuf.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
+        return 0;
     }
-    mark(3);
-    const Fe y = tr->squeeze();
-    tk("y");
-
-    // ---- coefficient forms and cosets of everything committed so far
-    if (!side) {
-        TRY(dehalo_intt_scaled_device(ctx, fid, cols.u64(), k, d.omega_inv.v, d.ifft_divisor.v, nco, nullptr));
-        TRY(dehalo_coset_ntt_form_device(ctx, fid, cols.u64(), k, ext.u64(), ek, d.ext_omega.v, d.g_coset.v, nco, DEHALO_FORM_OUT_INTERNAL, nullptr));
-        if (I) TRY(dehalo_coset_ntt_form_device(ctx, fid, instance.u64(), k, ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
-    } else {      // queued phase by phase on the side context: wait for it
-        HIP_TRY(side, hipEventRecord(ev_side, ss));
-        HIP_TRY(ctx, hipStreamWaitEvent(ms, ev_side, 0));
+    int after_products_queued() {
+        TRY(restore_random());
+        if (!side) return 0;
+        TRY(side_ntt(p.o_pz, S + L, p.ev_ready[2]));
+        // the lookups' (compressed input + beta)(compressed table + gamma) over the extended domain need theta, beta, gamma and the advice /
+        // fixed cosets: all there -- on the side context, beside the products' commitment, instead of after y
+        if (L) {
+            std::vector<const dehalo_graph*> graphs(p.pk->lookup_graphs.begin(), p.pk->lookup_graphs.end());
+            std::vector<uint64_t*> outs;
+            for (uint32_t l = 0; l < L; l++) outs.push_back(p.table_value.u64((size_t)l * m));
+            EvalIn e = coset_inputs();
+            e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
+            TRY(dehalo_graph_evaluate_batch_device(side, graphs.data(), L, &e.in, ek, rot_scale, outs.data(), nullptr));
+        }
+        return 0;
     }
 
-    // ---- evaluate_h, / t(X), extended_to_coeff
-    const uint64_t *l0 = pk->l_ext.u64(0), *l_last = pk->l_ext.u64(m), *l_active = pk->l_ext.u64(2 * m);
-    if (!gates_early) {
-        EvalIn e;
-        e.cols(fixed_c, adv_c, inst_c);
-        e.in.y = y.v;
-        e.in.form_flags = FF;
-        TRY(dehalo_graph_evaluate_device(ctx, pk->custom_gates, &e.in, ek, rot_scale, nullptr, h.u64(), nullptr));
-    }
-    if (S) {
-        std::vector<const uint64_t*> z, pcols, sigma;
-        for (uint32_t s = 0; s < S; s++) z.push_back(col_ptr(ext, o_pz + s, m));
-        for (auto& pc : cs.perm_cols) pcols.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_c[pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_c[pc.index] : inst_c[pc.index]);
-        for (uint32_t j = 0; j < npc; j++) sigma.push_back(col_ptr(pk->perm_cosets, j, m));
-        const Fe beta_zeta = f->mul(beta, d.g_coset);
-        dehalo_perm_inputs pi{};
-        pi.z = z.data(); pi.num_sets = S;
-        pi.columns = pcols.data(); pi.sigma = sigma.data(); pi.num_columns = npc;
-        pi.chunk_len = cs.chunk_len();
-        pi.last_rotation = -(int32_t)(bf + 1);
-        pi.l0 = l0; pi.l_last = l_last; pi.l_active_row = l_active;
-        pi.beta = beta.v; pi.gamma = gamma.v; pi.y = y.v; pi.delta = f->delta.v; pi.beta_zeta = beta_zeta.v; pi.extended_omega = d.ext_omega.v;
-        pi.form_flags = FF;
-        TRY(dehalo_permutation_h_device(ctx, fid, &pi, ek, rot_scale, h.u64(), nullptr));
-    }
-    if (L) {
+    // ---- coefficient forms and cosets of everything committed so far; evaluate_h, / t(X), extended_to_coeff; the pieces' commitments
+    int quotient() {
+        const uint32_t npc = (uint32_t)cs.perm_cols.size();
         if (!side) {
-            for (uint32_t l = 0; l < L; l++) {
-                EvalIn e;
-                e.cols(fixed_c, adv_c, inst_c);
-                e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
-                e.in.form_flags = FF;
-                TRY(dehalo_graph_evaluate_device(ctx, pk->lookup_graphs[l], &e.in, ek, rot_scale, nullptr, table_value.u64((size_t)l * m), nullptr));
-            }
+            TRY(dehalo_intt_scaled_device(ctx, fid, p.cols.u64(), k, d.omega_inv.v, d.ifft_divisor.v, nco, nullptr));
+            TRY(dehalo_coset_ntt_form_device(ctx, fid, p.cols.u64(), k, p.ext.u64(), ek, d.ext_omega.v, d.g_coset.v, nco, DEHALO_FORM_OUT_INTERNAL, nullptr));
+            if (I) TRY(dehalo_coset_ntt_form_device(ctx, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
+        } else {      // queued phase by phase on the side context: wait for it
+            HIP_TRY(side, hipEventRecord(p.ev_side, ss));
+            HIP_TRY(ctx, hipStreamWaitEvent(ms, p.ev_side, 0));
+        }
+        const uint64_t *l0 = p.pk->l_ext.u64(0), *l_last = p.pk->l_ext.u64(m), *l_active = p.pk->l_ext.u64(2 * m);
+        if (!gates_early) {
+            EvalIn e = coset_inputs();
+            e.in.y = y.v;
+            TRY(dehalo_graph_evaluate_device(ctx, p.pk->custom_gates, &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
+        }
+        if (S) {
+            std::vector<const uint64_t*> z, pcols, sigma;
+            for (uint32_t s = 0; s < S; s++) z.push_back(col_ptr(p.ext, p.o_pz + s, m));
+            for (auto& pc : cs.perm_cols) pcols.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_c[pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_c[pc.index] : inst_c[pc.index]);
+            for (uint32_t j = 0; j < npc; j++) sigma.push_back(col_ptr(p.pk->perm_cosets, j, m));
+            const Fe beta_zeta = f->mul(beta, d.g_coset);
+            dehalo_perm_inputs pi{};
+            pi.z = z.data(); pi.num_sets = S;
+            pi.columns = pcols.data(); pi.sigma = sigma.data(); pi.num_columns = npc;
+            pi.chunk_len = cs.chunk_len();
+            pi.last_rotation = -(int32_t)(bf + 1);
+            pi.l0 = l0; pi.l_last = l_last; pi.l_active_row = l_active;
+            pi.beta = beta.v; pi.gamma = gamma.v; pi.y = y.v; pi.delta = f->delta.v; pi.beta_zeta = beta_zeta.v; pi.extended_omega = d.ext_omega.v;
+            pi.form_flags = FF;
+            TRY(dehalo_permutation_h_device(ctx, fid, &pi, ek, rot_scale, p.h.u64(), nullptr));
+        }
+        for (uint32_t l = 0; l < L && !side; l++) {
+            EvalIn e = coset_inputs();
+            e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
+            TRY(dehalo_graph_evaluate_device(ctx, p.pk->lookup_graphs[l], &e.in, ek, rot_scale, nullptr, p.table_value.u64((size_t)l * m), nullptr));
         }
         for (uint32_t first = 0; first < L; first += 8) {
             std::vector<dehalo_lookup_inputs> li;
             for (uint32_t l = first; l < std::min(L, first + 8); l++) {
-                dehalo_lookup_inputs x{};
-                x.product_coset = col_ptr(ext, o_lz + l, m);
-                x.permuted_input_coset = col_ptr(ext, o_perm + 2 * l, m);
-                x.permuted_table_coset = col_ptr(ext, o_perm + 2 * l + 1, m);
-                x.table_value = table_value.u64((size_t)l * m);
-                x.l0 = l0; x.l_last = l_last; x.l_active_row = l_active;
-                x.beta = beta.v; x.gamma = gamma.v; x.y = y.v;
-                x.form_flags = FF;
-                li.push_back(x);
+                dehalo_lookup_inputs q{};
+                q.product_coset = col_ptr(p.ext, p.o_lz + l, m);
+                q.permuted_input_coset = col_ptr(p.ext, p.o_perm + 2 * l, m);
+                q.permuted_table_coset = col_ptr(p.ext, p.o_perm + 2 * l + 1, m);
+                q.table_value = p.table_value.u64((size_t)l * m);
+                q.l0 = l0; q.l_last = l_last; q.l_active_row = l_active;
+                q.beta = beta.v; q.gamma = gamma.v; q.y = y.v;
+                q.form_flags = FF;
+                li.push_back(q);
             }
-            TRY(dehalo_lookup_h_batch_device(ctx, fid, li.data(), (uint32_t)li.size(), ek, rot_scale, h.u64(), nullptr));
+            TRY(dehalo_lookup_h_batch_device(ctx, fid, li.data(), (uint32_t)li.size(), ek, rot_scale, p.h.u64(), nullptr));
         }
+        TRY(dehalo_scale_device(ctx, fid, p.h.u64(), m, (const uint64_t*)d.t_inv.data(), (uint32_t)d.t_inv.size(), nullptr, nullptr));      // divide_by_vanishing_poly
+        TRY(dehalo_coset_intt_form_device(ctx, fid, p.h.u64(), ek, d.ext_omega_inv.v, d.ext_ifft_divisor.v, d.g_coset.v, 1, DEHALO_FORM_IN_INTERNAL, nullptr));
+        p.tk("quotient queued");
+        return p.commit(tr, p.h.p, pieces, false, nullptr, 0, p.blind_at(p.bi_h));
     }
-    TRY(dehalo_scale_device(ctx, fid, h.u64(), m, (const uint64_t*)d.t_inv.data(), (uint32_t)d.t_inv.size(), nullptr, nullptr));      // divide_by_vanishing_poly
-    TRY(dehalo_coset_intt_form_device(ctx, fid, h.u64(), ek, d.ext_omega_inv.v, d.ext_ifft_divisor.v, d.g_coset.v, 1, DEHALO_FORM_IN_INTERNAL, nullptr));
-    tk("quotient queued");
-    TRY(commit(tr, h.p, pieces, false, nullptr, 0, blind_at(bi_h)));
-    mark(4);
-    const Fe x = tr->squeeze();
-    const Fe xn = f->pow_u64(x, (uint64_t)n);
 
     // ---- evaluations, in upstream's order: every opened polynomial at every rotation in ONE call
-    std::vector<Fe> point(rots.size());
-    for (size_t i = 0; i < rots.size(); i++) point[i] = d.rotate_omega(x, rots[i]);
-    TRY(dehalo_eval_polynomial_multi_masked_device(ctx, fid, plist.data(), plist.size(), n, (const uint64_t*)point.data(), (uint32_t)rots.size(), eval_wanted.data(), evals.u64(), nullptr));
-    // the folded quotient h(X) = sum_i x^(n i) h_i(X) (opened below; its value at x comes from the pieces' values)
-    std::vector<Fe> xs(pieces);
-    {
-        Fe cur = f->one;
-        for (uint32_t i = 0; i < pieces; i++) {
-            xs[i] = cur;
-            cur = f->mul(cur, xn);
-        }
+    int evaluations() {
+        point.resize(p.rots.size());
+        for (size_t i = 0; i < p.rots.size(); i++) point[i] = d.rotate_omega(x, p.rots[i]);
+        TRY(dehalo_eval_polynomial_multi_masked_device(ctx, fid, p.plist.data(), p.plist.size(), n, (const uint64_t*)point.data(), (uint32_t)p.rots.size(), p.eval_wanted.data(),
+                                                       p.evals.u64(), nullptr));
+        // the folded quotient h(X) = sum_i x^(n i) h_i(X) (opened below; its value at x comes from the pieces' values)
+        xs = powers(f, f->pow_u64(x, (uint64_t)n), pieces);
+        TRY(dehalo_lincomb_device(ctx, fid, p.hp_ptrs.data(), (const uint64_t*)xs.data(), pieces, n, p.hfold.u64(), nullptr, nullptr));
+        p.tk("evaluations queued");
+        TRY(dehalo_download(ctx, p.evals.p, p.eval_count * 32, p.host_evals.data()));
+        p.tk("evaluations on host");
+        E = (const Fe*)p.host_evals.data();
+        hfold_eval = fold(f, xs.data(), E + p.hpiece0, pieces);
+        for (int64_t i : p.ipa_inst_write) tr->write_scalar(E[i]);      // (IPA: the instance evaluations come first)
+        for (int64_t i : p.write_idx) tr->write_scalar(E[i]);
+        return 0;
     }
-    TRY(dehalo_lincomb_device(ctx, fid, hp_ptrs.data(), (const uint64_t*)xs.data(), pieces, n, hfold.u64(), nullptr, nullptr));
-    tk("evaluations queued");
-    TRY(dehalo_download(ctx, evals.p, eval_count * 32, host_evals.data()));
-    tk("evaluations on host");
-    const Fe* E = (const Fe*)host_evals.data();
-    Fe hfold_eval = zero;
-    for (uint32_t i = 0; i < pieces; i++) hfold_eval = f->add(hfold_eval, f->mul(xs[i], E[hpiece0 + i]));
-    for (int64_t i : ipa_inst_write) tr->write_scalar(E[i]);      // (IPA: the instance evaluations come first)
-    for (int64_t i : write_idx) tr->write_scalar(E[i]);
-    mark(5);
-    if (ipa) {
-        // ---- ProverIPA::create_proof [UPSTREAM poly/ipa/multiopen/prover.rs]
+
+    // ---- ProverIPA::create_proof [UPSTREAM poly/ipa/multiopen/prover.rs]
+    int open_ipa() {
         const Fe x1 = tr->squeeze();
         const Fe x2 = tr->squeeze();
-        bl[bi_hfold] = zero;                                   // h's blinds fold with x^n as its pieces do
-        for (uint32_t i = 0; i < pieces; i++) bl[bi_hfold] = f->add(bl[bi_hfold], f->mul(xs[i], bl[bi_h + i]));
-        const size_t ns = ipa_sets.size();
+        bl[p.bi_hfold] = fold(f, xs.data(), &bl[p.bi_h], pieces);      // h's blinds fold with x^n as its pieces do
+        const size_t ns = p.ipa_sets.size();
         // q_i = the set's polynomials folded with x_1 in commitment order (q <- x_1 q + poly), the blinds likewise
-        std::vector<Fe> qblind(ns, zero);
+        std::vector<Fe> pblinds(1 + ns);      // of f and of every q_i
         size_t depth = 0;
         for (size_t si = 0; si < ns; si++) {
             std::vector<const uint64_t*> ptrs;
-            std::vector<uint32_t> bi;
-            for (auto& cm : ipa_commitments)
-                if (cm.set == si) { ptrs.push_back(cm.ptr); bi.push_back(cm.blind); }
-            std::vector<Fe> coefs(ptrs.size());
-            Fe pw = f->one;
-            for (size_t j = ptrs.size(); j-- > 0;) {
-                coefs[j] = pw;
-                qblind[si] = f->add(qblind[si], f->mul(pw, bl[bi[j]]));
-                pw = f->mul(pw, x1);
-            }
-            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ptrs.size(), n, ipa_q.u64(si * n), nullptr, nullptr));
-            depth = std::max(depth, ipa_sets[si].size());
+            std::vector<Fe> blinds;
+            for (auto& cm : p.ipa_commitments)
+                if (cm.set == si) { ptrs.push_back(cm.ptr); blinds.push_back(bl[cm.blind]); }
+            const std::vector<Fe> coefs = powers(f, x1, ptrs.size(), true);
+            pblinds[1 + si] = fold(f, coefs.data(), blinds.data(), ptrs.size());
+            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ptrs.size(), n, p.ipa_q.u64(si * n), nullptr, nullptr));
+            depth = std::max(depth, p.ipa_sets[si].size());
         }
         // each q_i divided by (X - point) for every point of its set in turn, remainders dropped: one batched launch per division depth over the sets
         // that still have a point left (a division writes n - 1 coefficients: the top one of both buffers stays zero)
-        HIP_TRY(ctx, hipMemsetAsync(ipa_wa.p, 0, ns * n * 32, ms));
-        HIP_TRY(ctx, hipMemsetAsync(ipa_wb.p, 0, ns * n * 32, ms));
+        HIP_TRY(ctx, hipMemsetAsync(p.ipa_wa.p, 0, ns * n * 32, ms));
+        HIP_TRY(ctx, hipMemsetAsync(p.ipa_wb.p, 0, ns * n * 32, ms));
         std::vector<const uint64_t*> cur(ns);
-        for (size_t si = 0; si < ns; si++) cur[si] = ipa_q.u64(si * n);
+        for (size_t si = 0; si < ns; si++) cur[si] = p.ipa_q.u64(si * n);
         for (size_t dd = 0; dd < depth; dd++) {
             std::vector<const uint64_t*> ins;
             std::vector<uint64_t*> outs;
             std::vector<Fe> pts;
             std::vector<size_t> which;
             for (size_t si = 0; si < ns; si++)
-                if (ipa_sets[si].size() > dd) {
+                if (p.ipa_sets[si].size() > dd) {
                     ins.push_back(cur[si]);
-                    outs.push_back((dd & 1 ? ipa_wb : ipa_wa).u64(si * n));
-                    pts.push_back(d.rotate_omega(x, ipa_point_rot[ipa_sets[si][dd]]));
+                    outs.push_back((dd & 1 ? p.ipa_wb : p.ipa_wa).u64(si * n));
+                    pts.push_back(d.rotate_omega(x, p.ipa_point_rot[p.ipa_sets[si][dd]]));
                     which.push_back(si);
                 }
             for (size_t first = 0; first < ins.size(); first += 8)      // (the batched division takes eight at a time)
@@ -1966,85 +956,123 @@ int dehalo_prover::run(const uint64_t* advice, const uint64_t* const* instances,
             for (size_t j = 0; j < which.size(); j++) cur[which[j]] = outs[j];
         }
         // f = the quotients folded with x_2; commit(f, f_blind)
-        {
-            std::vector<Fe> coefs(ns);
-            Fe pw = f->one;
-            for (size_t j = ns; j-- > 0;) { coefs[j] = pw; pw = f->mul(pw, x2); }
-            TRY(dehalo_lincomb_device(ctx, fid, cur.data(), (const uint64_t*)coefs.data(), ns, n, ipa_f.u64(), nullptr, nullptr));
-        }
-        TRY(commit(tr, ipa_f.p, 1, false, nullptr, 0, blind_at(bi_f)));
+        TRY(dehalo_lincomb_device(ctx, fid, cur.data(), (const uint64_t*)powers(f, x2, ns, true).data(), ns, n, p.ipa_f.u64(), nullptr, nullptr));
+        TRY(p.commit(tr, p.ipa_f.p, 1, false, nullptr, 0, p.blind_at(p.bi_f)));
         const Fe x3 = tr->squeeze();
         // q_i(x_3) for every set: one evaluation call, one download
-        fe* qe = evals.at(eval_count + 8);
-        TRY(dehalo_eval_polynomial_device(ctx, fid, ipa_q.u64(), n, n, ns, x3.v, (uint64_t*)qe, nullptr));
+        fe* qe = p.evals.at(p.eval_count + 8);
+        TRY(dehalo_eval_polynomial_device(ctx, fid, p.ipa_q.u64(), n, n, ns, x3.v, (uint64_t*)qe, nullptr));
         std::vector<Fe> qev(ns);
         TRY(dehalo_download(ctx, qe, ns * 32, qev.data()));
         for (size_t si = 0; si < ns; si++) tr->write_scalar(qev[si]);
         const Fe x4 = tr->squeeze();
         // p = f, then p <- x_4 p + q_i over the sets; the blind likewise
-        Fe pblind = bl[bi_f];
-        {
-            std::vector<const uint64_t*> ptrs = {ipa_f.u64()};
-            for (size_t si = 0; si < ns; si++) ptrs.push_back(ipa_q.u64(si * n));
-            std::vector<Fe> coefs(ns + 1);
-            Fe pw = f->one;
-            for (size_t j = ns + 1; j-- > 0;) { coefs[j] = pw; pw = f->mul(pw, x4); }
-            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ns + 1, n, ipa_p.u64(), nullptr, nullptr));
-            for (size_t si = 0; si < ns; si++) pblind = f->add(f->mul(pblind, x4), qblind[si]);
-        }
-        tk("multiopen done");
+        std::vector<const uint64_t*> ptrs = {p.ipa_f.u64()};
+        for (size_t si = 0; si < ns; si++) ptrs.push_back(p.ipa_q.u64(si * n));
+        pblinds[0] = bl[p.bi_f];
+        const std::vector<Fe> coefs = powers(f, x4, ns + 1, true);
+        TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ns + 1, n, p.ipa_p.u64(), nullptr, nullptr));
+        const Fe pblind = fold(f, coefs.data(), pblinds.data(), ns + 1);
+        p.tk("multiopen done");
         // commitment::create_proof on p at x_3: same transcript, same generator (right behind f's blind)
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        TRY(ipa_open_body(ctx, params, ipa_p.u64(), pblind, x3, rng, 2, tr));
-        mark(6);
-        timings[7] = ms_since(t_start);
-        if (rng_in && rng_in->kind == DEHALO_RNG_PCG64) {
-            rng_in->pcg_state[0] = (uint64_t)rng.pcg.state;
-            rng_in->pcg_state[1] = (uint64_t)(rng.pcg.state >> 64);
-        }
-        return 0;
+        return ipa_open_body(ctx, p.params, p.ipa_p.u64(), pblind, x3, rng, 2, tr);
     }
 
     // ---- ProverGWC::create_proof: one witness polynomial per distinct point, in order of first appearance
-    const Fe v = tr->squeeze();
-    tk("v");
-    HIP_TRY(ctx, hipMemsetAsync(wbuf.p, 0, 4 * n * 32, ms));
-    std::vector<const uint64_t*> qptrs;
-    std::vector<uint64_t*> wptrs;
-    std::vector<Fe> qpoints;
-    for (size_t gi = 0; gi < groups.size(); gi++) {
-        const Group& g = groups[gi];
-        std::vector<Fe> coefs(g.idx.size());
-        Fe eval_batch = zero, pw = f->one;
-        for (size_t i = 0; i < g.idx.size(); i++) {
-            coefs[i] = pw;
-            eval_batch = f->add(eval_batch, f->mul(pw, g.idx[i] >= 0 ? E[g.idx[i]] : hfold_eval));
-            pw = f->mul(pw, v);
+    int open_gwc() {
+        const Fe v = tr->squeeze();
+        p.tk("v");
+        HIP_TRY(ctx, hipMemsetAsync(p.wbuf.p, 0, 4 * n * 32, ms));
+        std::vector<const uint64_t*> qptrs;
+        std::vector<uint64_t*> wptrs;
+        std::vector<Fe> qpoints;
+        for (size_t gi = 0; gi < p.groups.size(); gi++) {
+            const dehalo_prover::Group& g = p.groups[gi];
+            const std::vector<Fe> coefs = powers(f, v, g.idx.size());
+            std::vector<Fe> values;
+            for (int64_t i : g.idx) values.push_back(i >= 0 ? E[i] : hfold_eval);
+            const Fe eval_batch = fold(f, coefs.data(), values.data(), values.size());
+            TRY(dehalo_lincomb_device(ctx, fid, g.ptrs.data(), (const uint64_t*)coefs.data(), g.ptrs.size(), n, p.qbuf.u64(gi * n), eval_batch.v, nullptr));
+            qptrs.push_back(p.qbuf.u64(gi * n));
+            wptrs.push_back(p.wbuf.u64(gi * n));
+            qpoints.push_back(point[(size_t)(std::find(p.rots.begin(), p.rots.end(), g.rot) - p.rots.begin())]);
         }
-        TRY(dehalo_lincomb_device(ctx, fid, g.ptrs.data(), (const uint64_t*)coefs.data(), g.ptrs.size(), n, qbuf.u64(gi * n), eval_batch.v, nullptr));
-        qptrs.push_back(qbuf.u64(gi * n));
-        wptrs.push_back(wbuf.u64(gi * n));
-        qpoints.push_back(point[(size_t)(std::find(rots.begin(), rots.end(), g.rot) - rots.begin())]);
+        TRY(dehalo_kate_division_batch_device(ctx, fid, qptrs.data(), n, (const uint64_t*)qpoints.data(), wptrs.data(), p.groups.size(), nullptr));
+        return p.commit(tr, p.wbuf.p, p.groups.size(), false);
     }
-    TRY(dehalo_kate_division_batch_device(ctx, fid, qptrs.data(), n, (const uint64_t*)qpoints.data(), wptrs.data(), groups.size(), nullptr));
-    TRY(commit(tr, wbuf.p, groups.size(), false));
-    mark(6);
-    timings[7] = ms_since(t_start);
-    if (trace) {
-        double prev = 0;
-        for (auto& t : ticks) {
-            fprintf(stderr, "  %8.3f (+%6.3f) %s\n", t.second, t.second - prev, t.first);
-            prev = t.second;
+
+    void finish() {
+        mark(6);
+        p.timings[7] = ms_since(t_start);
+        if (p.trace) {
+            double prev = 0;
+            for (auto& t : p.ticks) {
+                fprintf(stderr, "  %8.3f (+%6.3f) %s\n", t.second, t.second - prev, t.first);
+                prev = t.second;
+            }
+            fprintf(stderr, "  %8.3f total\n", p.timings[7]);
         }
-        fprintf(stderr, "  %8.3f total\n", timings[7]);
+        rng.write_back(rng_in);
     }
-    // a PCG64 caller's generator moves past this proof's draws (upstream's `&mut rng`)
-    if (rng_in && rng_in->kind == DEHALO_RNG_PCG64) {
-        rng_in->pcg_state[0] = (uint64_t)rng.pcg.state;
-        rng_in->pcg_state[1] = (uint64_t)(rng.pcg.state >> 64);
+
+    // create_proof [UPSTREAM plonk/prover.rs]; `synth_in`: of a circuit, synthesized inside (its advice replaces `advice`)
+    int run(const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, uint32_t flags,
+            const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
+        p.ticks.clear();
+        p.t0 = t_start;
+        p.trace = getenv("DEHALO_PROVER_TRACE") != nullptr;
+        (void)hipSetDevice(ctx->device);
+        TRY(draw_blinds());
+        if (synth_in) {
+            TRY(synthesize(synth_in, synth_info));
+            advice = p.adv_pin;
+            flags = (flags & ~(uint32_t)DEHALO_PROOF_ADVICE_ON_DEVICE) | DEHALO_PROOF_ADVICE_CANONICAL;
+        }
+        TRY(upload_blinds());
+        tr->common_scalar(p.pk->transcript_repr);      // vk.hash_into
+        TRY(instance_columns(instances, instance_lens, num_instance_columns));
+        TRY(advice_columns(advice, flags));
+        mark(0);
+        theta = tr->squeeze();
+        p.tk("theta");
+        TRY(lookups());
+        mark(1);
+        beta = tr->squeeze();
+        gamma = tr->squeeze();
+        p.tk("beta gamma");
+        TRY(products_and_random());
+        mark(2);
+        p.tk("products done");
+        p.tk("helper joined");      // (joined in front of the products since the random polynomial rides with them; the label stays where traces have it)
+        if (p.trace) fprintf(stderr, "  helper: draw %.3f, upload queued %.3f, upload done %.3f ms after its start\n", helper_ms[0], helper_ms[1], helper_ms[2]);
+        mark(3);
+        y = tr->squeeze();
+        p.tk("y");
+        TRY(quotient());
+        mark(4);
+        x = tr->squeeze();
+        TRY(evaluations());
+        mark(5);
+        TRY(ipa ? open_ipa() : open_gwc());
+        finish();
+        return 0;
     }
-    return 0;
+};
+
+int prove(dehalo_prover* p, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng,
+          dehalo_transcript* transcript, uint32_t flags, const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
+    if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
+    std::lock_guard<std::mutex> lk(p->mu);
+    const int rc = ProofRun(*p, transcript, rng).run(advice, instances, instance_lens, num_instance_columns, flags, synth_in, synth_info);
+    if (rc) {      // leave nothing of this proof in flight on either context
+        (void)hipStreamSynchronize(p->ctx->stream);
+        if (p->side) (void)hipStreamSynchronize(p->side->stream);
+    }
+    return rc;
 }
+
+}   // namespace
 
 extern "C" int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out) {
     return dh_guard(ctx, [&]() -> int {
@@ -2075,14 +1103,7 @@ extern "C" int dehalo_create_proof(dehalo_prover* p, const uint64_t* advice, con
                                    dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || !transcript) return DEHALO_ERR_INVALID;
-        if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
-        std::lock_guard<std::mutex> lk(p->mu);
-        const int rc = p->run(advice, instances, instance_lens, num_instance_columns, rng, transcript, flags);
-        if (rc) {      // leave nothing of this proof in flight on either context
-            (void)hipStreamSynchronize(p->ctx->stream);
-            if (p->side) (void)hipStreamSynchronize(p->side->stream);
-        }
-        return rc;
+        return prove(p, advice, instances, instance_lens, num_instance_columns, rng, transcript, flags, nullptr, nullptr);
     });
 }
 
@@ -2104,40 +1125,11 @@ extern "C" int dehalo_prover_last_timings(const dehalo_prover* p, double out[8])
     });
 }
 
-extern "C" int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]) {
-    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
-        if (!pk || !out) return DEHALO_ERR_INVALID;
-        const HostCS& cs = pk->cs;
-        const uint32_t L = (uint32_t)cs.lookups.size(), S = cs.num_sets();
-        out[0] = pk->k;
-        out[1] = pk->dom.extended_k;
-        out[2] = cs.blinding_factors();
-        out[3] = cs.degree();
-        out[4] = S;
-        out[5] = cs.num_advice + 2 * L + S + L + 1 + (cs.degree() - 1);
-        out[6] = (uint32_t)(cs.advice_q.size() + cs.fixed_q.size() + 1 + cs.perm_cols.size() + (S ? 3 * S - 1 : 0) + 5 * L);
-        std::vector<int32_t> rs = {0, 1, -(int32_t)(cs.blinding_factors() + 1)};
-        if (L) rs.push_back(-1);
-        for (auto& q : cs.advice_q) rs.push_back(q.rotation);
-        for (auto& q : cs.fixed_q) rs.push_back(q.rotation);
-        std::sort(rs.begin(), rs.end());
-        out[7] = (uint32_t)(std::unique(rs.begin(), rs.end()) - rs.begin());
-        return 0;
-    });
-}
-
 extern "C" int dehalo_create_proof_circuit(dehalo_prover* p, const dehalo_circuit_inputs* in, dehalo_synthesis_info* info, const uint64_t* const* instances,
                                            const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng, dehalo_transcript* transcript) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || !transcript || !in) return DEHALO_ERR_INVALID;
-        if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
-        std::lock_guard<std::mutex> lk(p->mu);
-        const int rc = p->run(nullptr, instances, instance_lens, num_instance_columns, rng, transcript, 0, in, info);
-        if (rc) {
-            (void)hipStreamSynchronize(p->ctx->stream);
-            if (p->side) (void)hipStreamSynchronize(p->side->stream);
-        }
-        return rc;
+        return prove(p, nullptr, instances, instance_lens, num_instance_columns, rng, transcript, 0, in, info);
     });
 }
 

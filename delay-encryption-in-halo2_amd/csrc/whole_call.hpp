@@ -1,0 +1,142 @@
+// whole_call.hpp -- what the three units of the whole call share (host only): params.hip (ParamsKZG / ParamsIPA, the Blake2b transcript, the IPA opening
+// argument), keygen.hip (keygen_vk / keygen_pk, the RawBytes formats) and prover.hip (create_proof).  The objects behind the C ABI's opaque handles
+// [UPSTREAM halo2_proofs @ v2023_04_20: poly/kzg/commitment.rs ParamsKZG, poly/ipa/commitment.rs ParamsIPA, transcript.rs Blake2bWrite, plonk.rs
+// ProvingKey / VerifyingKey] and the few functions one unit calls in another.  Everything else of a unit stays in its anonymous namespace.
+#pragma once
+#include "blake2b.hpp"
+#include "hostrng.hpp"
+#include "internal.hpp"
+#include "plonk_host.hpp"
+
+// ---- device memory owned by an object of the whole call ----
+struct DevMem {
+    fe* p = nullptr;
+    size_t elems = 0;
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        elems = 0;
+    }
+    int alloc(dehalo_ctx* ctx, size_t n_elems, bool zero = true) {
+        reset();
+        if (!n_elems) return 0;
+        HIP_TRY(ctx, hipMalloc((void**)&p, n_elems * sizeof(fe)));
+        elems = n_elems;
+        if (zero) HIP_TRY(ctx, hipMemsetAsync(p, 0, n_elems * sizeof(fe), ctx->stream));
+        return 0;
+    }
+    fe* at(size_t elem) const { return p + elem; }
+    uint64_t* u64(size_t elem = 0) const { return (uint64_t*)(p + elem); }
+};
+
+// ================================================================================================ ParamsKZG / ParamsIPA (params.hip)
+struct dehalo_params {
+    dehalo_ctx* ctx = nullptr;
+    int curve = 0;
+    uint32_t k = 0;
+    size_t n = 0;
+    std::vector<uint64_t> g, g_lagrange;      // host copies (write())
+    uint8_t g2[128] = {}, s_g2[128] = {};
+    dehalo_bases *bases_g = nullptr, *bases_gl = nullptr;
+    int scheme = DEHALO_SCHEME_KZG;
+    // ParamsIPA only: g as plain affine points followed by u, w (n + 2 points, standard Montgomery): the generator vector the opening collapses
+    DevMem d_guw;
+    dehalo_bases* bases_uw = nullptr;         // [U | W] plain: the extra bases of round 1, whose G' part runs over bases_g
+    uint64_t u[8] = {}, w[8] = {};
+};
+
+// Blind::default() of upstream's poly/commitment.rs, the blind of every commitment that is not hiding: the verifying key's fixed and permutation columns and,
+// under IPA, the instance columns.  Taken to be Blind(F::ONE) (no upstream source at hand: parity unpinned).  Keygen and the prover
+// read this constant only; the CPU restatement and the verifier of the tests have its twin (tests/plonk_ipa_reference.py DEFAULT_BLIND).
+constexpr uint64_t IPA_DEFAULT_BLIND = 1;
+
+// ================================================================================================ transcript (C entry points: params.hip)
+struct dehalo_transcript {
+    int curve = 0;
+    const HostField *fq = nullptr, *fr = nullptr;      // base field (coordinates), scalar field (challenges)
+    Blake2b state;
+    std::vector<uint8_t> proof;
+
+    void init(int c) {
+        curve = c;
+        fq = host_field(curve_base_field(c));
+        fr = host_field(curve_scalar_field(c));
+        state.init(64, "Halo2-Transcript");
+        proof.clear();
+    }
+    Fe squeeze() {      // Challenge255: Blake2b-512 over everything absorbed + the prefix byte 0 (which stays absorbed), reduced mod r
+        const uint8_t z = 0;
+        state.update(&z, 1);
+        uint8_t d[64];
+        state.digest(d);
+        return fr->from_u512(d);
+    }
+    void common_scalar(const Fe& s) {
+        uint8_t b[33];
+        b[0] = 2;
+        fr->to_bytes(s, b + 1);
+        state.update(b, 33);
+    }
+    void write_scalar(const Fe& s) {
+        common_scalar(s);
+        uint8_t b[32];
+        fr->to_bytes(s, b);
+        proof.insert(proof.end(), b, b + 32);
+    }
+    // affine {x, y} Montgomery; false for the identity (upstream: "cannot write points at infinity to the transcript")
+    bool write_point(const uint64_t xy[8], bool also_to_proof = true) {
+        Fe x, y;
+        memcpy(x.v, xy, 32);
+        memcpy(y.v, xy + 4, 32);
+        if (x.is_zero() && y.is_zero()) return false;
+        uint8_t b[65];
+        b[0] = 1;
+        fq->to_bytes(x, b + 1);
+        fq->to_bytes(y, b + 33);
+        state.update(b, 65);
+        if (also_to_proof) {      // GroupEncoding: x little-endian, bit 7 of the last byte = y is odd
+            uint8_t c[32];
+            memcpy(c, b + 1, 32);
+            c[31] |= (uint8_t)((b[33] & 1) << 7);
+            proof.insert(proof.end(), c, c + 32);
+        }
+        return true;
+    }
+};
+
+// ================================================================================================ keys (keygen.hip, which defines the member functions)
+struct dehalo_pk {
+    dehalo_ctx* ctx = nullptr;
+    int curve = 0;
+    const HostField* f = nullptr;
+    HostCS cs;
+    HostDomain dom;
+    uint32_t k = 0, num_selectors = 0;
+    std::vector<uint64_t> fixed_commitments, perm_commitments;      // Montgomery affine, 8 u64 each
+    std::vector<std::vector<uint8_t>> selectors;                    // packed 8 bools per byte, LSB first
+    Fe transcript_repr{};
+    // device: values / polys in upstream's standard form, extended-domain columns in the kernels' internal form
+    DevMem l_ext, fixed_values, fixed_polys, fixed_cosets, perm_values, perm_polys, perm_cosets;
+    dehalo_graph* custom_gates = nullptr;
+    std::vector<dehalo_graph*> lookup_graphs;
+    std::vector<std::pair<dehalo_graph*, dehalo_graph*>> compress_graphs;
+
+    ~dehalo_pk();
+    size_t vk_size() const;
+    void vk_write(uint8_t* o) const;
+    size_t size() const;
+    void default_transcript_repr();
+    int compile_graphs();
+};
+
+// ================================================================================================ functions that cross units
+// params.hip: commitment::create_proof of ParamsIPA on `rng` as it stands, into `t` (dehalo_ipa_open; the last step of a ProverIPA proof)
+int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t);
+// params.hip: out[0 .. n) = uniform scalars of rng's field from ChaCha20 stream `cha_stream` under rng's key (DEHALO_RNG_OS), one kernel launch on `s`
+int chacha_scalars_device(dehalo_ctx* ctx, const HostRng& rng, uint64_t cha_stream, fe* out, size_t n, hipStream_t s);
+// keygen.hip: (n, 4) device column of omega^i
+int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col);

@@ -21,7 +21,7 @@ from plonk_oracle import Shape
 from verifier import eval_expr
 
 # Blind::default(): the blind of the verifying key's fixed and permutation commitments and of the instance commitments.  The library's twin is
-# IPA_DEFAULT_BLIND (csrc/prover.hip).
+# IPA_DEFAULT_BLIND (csrc/whole_call.hpp).
 DEFAULT_BLIND = 1
 
 

@@ -1,4 +1,4 @@
-"""The whole call behind the C ABI (include/dehalo.h "the whole call"; csrc/prover.hip): dehalo_params_*, dehalo_keygen, dehalo_pk_*,
+"""The whole call behind the C ABI (include/dehalo.h "the whole call"; csrc/params.hip, keygen.hip, prover.hip): dehalo_params_*, dehalo_keygen, dehalo_pk_*,
 dehalo_transcript_*, dehalo_create_proof(s) -- the reference's objects and call at benches/delay_enc.rs:41-54, 84-115, 120-134.
 
 CPU suite -- what needs no device: the transcript against the Python mirror and hashlib, the three random-scalar sources, the
