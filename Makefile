@@ -42,6 +42,10 @@ host_sanitize: tests/native_host/host_sanitize.cpp $(CSRC)/witness.hip $(HDRS)
 host_tsan: tests/native_host/host_sanitize.cpp $(CSRC)/witness.hip $(HDRS)
 	g++ -std=c++17 -O1 -g -fsanitize=thread -x c++ -o tests/native_host/host_tsan tests/native_host/host_sanitize.cpp -x c++ $(CSRC)/witness.hip -lpthread
 
+# the MSM's launch planner (csrc/msm_plan.hpp: no HIP headers) swept over shapes and tunings under the same sanitizers
+msm_plan_check: tests/native_host/msm_plan_check.cpp $(CSRC)/msm_plan.hpp $(CSRC)/experiment_env.hpp $(CSRC)/field_constants.h
+	g++ -std=c++17 -O2 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/msm_plan_check tests/native_host/msm_plan_check.cpp
+
 clean:
 	rm -rf $(LIB) $(OBJDIR) $(PKG)/host/example; $(MAKE) -C oracle clean
-.PHONY: all oracle clean host_example host_sanitize host_tsan
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check

@@ -12,62 +12,10 @@
 #include "evalh_types.hpp"
 #include "hostfield.hpp"
 #include "internal.hpp"
+#include "msm_plan.hpp"      // the window rules: choose_window, choose_window_single, signed_windows, msm_table_fits
 
 namespace {
 
-// Window bits by measurement on MI355X (tools/sweep_c.py, tools/profile_prover.py with WINDOW_BITS): the bucket
-// reduction costs ~ 2^(c-1) group operations on a latency chain, the accumulation n * ceil(256 / c) additions.
-// 2^20 and up: 16; 2^17 .. 2^19: 15; 2^10 .. 2^16: 13 (prover-shaped schedule at k = 14: 2.9 ms of MSMs with
-// c = 13, 3.1 with 15, 3.5 with 14 -- even c leaves a top window of few bits whose buckets are hot).
-uint32_t choose_window(size_t n) {
-    uint32_t l = log2_ceil(n ? n : 1);
-    // 2^20 and up: 17 bits -- 15 rows instead of 16 (6 % fewer additions), 2^16 buckets whose histogram fits the LDS as packed 16-bit counters; four alternating pairs
-    // at 2^20: 760.7 -> 779.1 Mpoints/s in the step, one MSM alone 1.55 -> 1.48 ms (profiles/r06_window_17.txt)
-    if (l >= 20) return 17;
-    if (l >= 19) return 16;      // k = 19 proofs 25.7 -> 25.0 ms against 15 bits (17: 26.4); k = 17 / 18 stay at 15 (7.25 / 12.9 ms against 7.5 / 13.0 at 16): profiles/r06_window_sweep_proofs.txt
-    if (l >= 17) return 15;
-    if (l >= 10) return 13;
-    return std::max<uint32_t>(6, l + 1);
-}
-
-// Single-row tables (the one-shot, unregistered path: every window keeps its own buckets and the window sums are combined by
-// c (W - 1) doublings): fewer buckets per window pay for the extra windows.  Measured on MI355X (tools/sweep_single_row.py, Pallas,
-// uniform scalars, device time): 2^14 c = 10 0.81 ms (13: 0.95, 16: 1.12); 2^17 c = 13 1.15 (10: 1.21, 15: 1.39); 2^20 c = 13 3.13 (16: 3.51).
-uint32_t choose_window_single(size_t n) {
-    uint32_t l = log2_ceil(n ? n : 1);
-    if (l >= 16) return 13;
-    if (l >= 12) return 10;
-    return choose_window(n);
-}
-
-// Windows of the signed-digit recoding: the smallest W for which no canonical scalar s < r leaves a carry after window W - 1
-// (msm.cuh for_each_digit drops it).  With top = (r - 1) >> c(W - 1) that holds when top + 1 <= 2^(c-1), and also when top == 2^(c-1)
-// exactly while the c bits of r - 1 just below the top window are all zero (then s with that top digit has a zero digit in window
-// W - 2, which absorbs any carry).  E.g. BN254 Fr, c = 15: 17 windows instead of ceil(256 / 15) = 18; Pasta Fq, c = 17: 15.
-uint32_t signed_windows(const uint32_t r_words[8], uint32_t c) {
-    uint64_t r1[4];                                                  // r - 1 (r is odd)
-    for (int i = 0; i < 4; i++) r1[i] = (uint64_t)r_words[2 * i] | ((uint64_t)r_words[2 * i + 1] << 32);
-    r1[0] -= 1;
-    auto bits_at = [&](uint32_t lo, uint32_t count) -> uint64_t {   // bits [lo, lo + count) of r - 1, count <= 32
-        uint64_t v = 0;
-        for (uint32_t b = 0; b < count; b++) {
-            uint32_t pos = lo + b;
-            if (pos < 256 && ((r1[pos >> 6] >> (pos & 63)) & 1)) v |= 1ull << b;
-        }
-        return v;
-    };
-    for (uint32_t W = (254 + c - 1) / c; W <= (256 + c - 1) / c; W++) {
-        if (W < 2) continue;
-        const uint32_t shift = c * (W - 1);
-        bool above = false;                                          // anything of r - 1 above the top window?
-        for (uint32_t pos = shift + c; pos < 256; pos++) above |= ((r1[pos >> 6] >> (pos & 63)) & 1) != 0;
-        if (above) continue;
-        const uint64_t top = bits_at(shift, c), half = 1ull << (c - 1);
-        if (top + 1 <= half) return W;
-        if (top == half && bits_at(shift - c, c) == 0) return W;
-    }
-    return (256 + c - 1) / c;
-}
 // the op tables of the per-field / per-curve translation units (ntt_*.hip, msm_*.hip) by dehalo_field / dehalo_curve id; null for an unknown id
 const FieldOps* field_ops(int field) {
     static const FieldOps* const ops[] = {&bn254_fr_field_ops(), &bn254_fq_field_ops(), &pasta_fp_field_ops(), &pasta_fq_field_ops()};
@@ -287,18 +235,18 @@ struct BasesFree {
 int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t n, size_t stride_bytes, int window_bits, int precompute,
                   dehalo_bases** out, bool on_device = false) {
     if (!affine_xy || !out || n == 0 || stride_bytes < 64 || n >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_register: bad argument");
-    if (window_bits != 0 && (window_bits < 4 || window_bits > (precompute ? 17 : 16)))
+    if (window_bits != 0 && (window_bits < (int)MSM_WINDOW_MIN || window_bits > (int)msm_window_max(precompute != 0)))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "window_bits must be 0 or in [4, 16] (17 with precomputed rows)");
     const CurveOps* cv = curve_ops(curve);
     if (!cv) return unknown_curve(ctx);
     uint32_t c = window_bits ? (uint32_t)window_bits : (precompute ? choose_window(n) : choose_window_single(n));
     if (!window_bits && precompute) {      // DEHALO_WINDOW_BITS: tuning experiments (results never depend on the window)
         const char* e = DH_EXPERIMENT_ENV("DEHALO_WINDOW_BITS");
-        if (e && atoi(e) >= 4 && atoi(e) <= 17) c = (uint32_t)atoi(e);
+        if (e && atoi(e) >= (int)MSM_WINDOW_MIN && atoi(e) <= (int)msm_window_max(true)) c = (uint32_t)atoi(e);
     }
-    if (c < 4) c = 4;
+    c = std::max<uint32_t>(MSM_WINDOW_MIN, c);
     uint32_t W = signed_windows(cv->scalar_modulus, c);
-    if (precompute && (uint64_t)n * W >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "precomputed table too large");      // 30-bit table indices in the sorted list (msm.cuh)
+    if (precompute && !msm_table_fits(n, W)) return dh_fail(ctx, DEHALO_ERR_INVALID, "precomputed table too large");      // 30-bit table indices in the sorted list (msm.cuh)
     // stage the caller's points (standard Montgomery form) on the device, then build the table
     if (!on_device) TRY(dh_ensure(ctx, ctx->ws_tmp_bases, n * sizeof(affine_t)));
     std::unique_ptr<dehalo_bases, BasesFree> b(new dehalo_bases());
@@ -342,7 +290,7 @@ int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, dehalo_bases** 
 int dh_bases_plain_rebuild(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_points, size_t n, hipStream_t s) {
     const CurveOps* cv = curve_ops(b->curve);
     b->n = n;
-    b->c = std::max<uint32_t>(4, choose_window_single(n));
+    b->c = std::max<uint32_t>(MSM_WINDOW_MIN, choose_window_single(n));
     b->W = signed_windows(cv->scalar_modulus, b->c);
     return cv->build_table(ctx, b, d_points, s);
 }
@@ -350,7 +298,7 @@ int dh_bases_plain_rebuild(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_p
 // the limit of a precomputed table registered with window_bits = 0: n x windows < 2^30 (30-bit table indices in the sorted list, msm.cuh)
 bool dh_precomputed_table_fits(int curve, size_t n) {
     const CurveOps* cv = curve_ops(curve);
-    return cv && n < (1ull << 30) && (uint64_t)n * signed_windows(cv->scalar_modulus, std::max<uint32_t>(4, choose_window(n))) < (1ull << 30);
+    return cv && msm_table_fits(n, signed_windows(cv->scalar_modulus, std::max<uint32_t>(MSM_WINDOW_MIN, choose_window(n))));
 }
 
 // ==========================================================================================

@@ -15,6 +15,7 @@
 
 #include "../../include/dehalo.h"
 #include "ec.cuh"
+#include "experiment_env.hpp"
 #include "guard.hpp"
 
 // Caller buffers of the host entry points are ordinary pageable memory (a Rust Vec<F>): large ones are pinned for the duration of the
@@ -310,16 +311,6 @@ inline int dh_d2h(dehalo_ctx* ctx, void* h_dst, const void* d_src, size_t bytes,
 // the limit of a precomputed table registered with window_bits = 0: n x windows < 2^30 (capi.hip)
 bool dh_precomputed_table_fits(int curve, size_t n);
 
-// Experiment switches.  The default build reads NO tuning from the environment: DH_EXPERIMENT_ENV("DEHALO_...") is a null pointer there and the name is not even in
-// the binary, so an environment variable cannot change which kernels a drop-in library runs (per-context tuning goes through dehalo_ctx_set_tuning, validated).
-// A measurement build (`make EXPERIMENTS=1`: -DDEHALO_EXPERIMENTS, what tools/ab_*.sh build) turns them back into getenv and compiles the wall-clock phase stamps in.
-// The default build reads three diagnostics, host side only: DEHALO_PROVER_TRACE, DEHALO_SYNTH_TRACE (timelines on stderr), DEHALO_SYNTH_THREADS (witness threads).
-#ifdef DEHALO_EXPERIMENTS
-#define DH_EXPERIMENT_ENV(name) getenv(name)
-#else
-#define DH_EXPERIMENT_ENV(name) ((const char*)nullptr)
-#endif
-
 // DEHALO_CO_LDS (bytes; experiments with co-resident contexts): every latency-bound kernel that is meant to run in the wave slot a
 // 768-thread accumulation block leaves free asks for at least this much LDS per block in all (its own + unused padding), so that no two such blocks
 // fit one compute unit (> 80 KB of the 160) and the accumulation's next block always finds its three waves per SIMD.  0 = off.
@@ -362,12 +353,6 @@ inline fe fe_from_u64(const uint64_t v[4]) {
         r.v[2 * i + 1] = (u32)(v[i] >> 32);
     }
     return r;
-}
-
-inline uint32_t log2_ceil(size_t n) {
-    uint32_t l = 0;
-    while (((size_t)1 << l) < n) l++;
-    return l;
 }
 
 struct NttScale {

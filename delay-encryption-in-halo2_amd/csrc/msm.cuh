@@ -32,11 +32,8 @@
 
 #include "ec29.cuh"
 #include "internal.hpp"
+#include "msm_plan.hpp"      // MsmGeom, the block sizes and every other constant the kernels share with the launch planner
 
-#define MSM_SORT_THREADS 1024
-#define MSM_ACC_THREADS 128        // the accumulation's default block: 2 waves (4 waves x 122 VGPRs fill a SIMD's register file)
-#define MSM_ACC_THREADS_MAX 768    // msm_acc_block = 768: ONE block of 12 waves per CU = 3 waves per SIMD and no room for a second block -- a quarter of every
-                                   // SIMD's registers (and all of the LDS) stays free for the <= 128-VGPR kernels of the other contexts
 // (measured: 2 and 3 resident waves per SIMD give the same k_msm_accum0 time -- the loop is
 // VALU-issue-bound -- and capping residency at 2 did not improve multi-stream overlap)
 #ifndef MSM_ACC_WAVES_ATTR
@@ -51,7 +48,6 @@
 #else
 #define MSM_HIST_ATTR
 #endif
-#define MSM_MERGE_COUNTERS 8   // merge-class counters in ws_counters, in front of [L0 | M]
 
 // Experiment, off (round 4): the MSM's latency-bound kernels (sort, scans, merge, bucket reduction) raising their waves' issue priority with s_setprio, so that beside
 // another stream's throughput kernels (the side context's NTTs in a proof, a neighbour step's accumulation) the SIMD's arbiter takes their instructions first.
@@ -67,24 +63,7 @@ FP_DEV void msm_tail_prio() {
 }
 
 // classes of k_msm_merge2 (msm_bred.cuh) by the number S of partial sums of a bucket; S > MERGE2_CHUNK: cut into parts of MERGE2_CHUNK records
-#define MERGE2_CHUNK 512
 FP_DEV u32 merge2_class(u32 S) { return S <= 2 ? 0u : S <= 4 ? 1u : S <= 8 ? 2u : S <= 64 ? 3u : S <= MERGE2_CHUNK ? 4u : 5u; }
-
-#define MSM_IDX_FIRST 0x40000000u     // sorted entry, bit 30: first point of its bucket
-#define MSM_IDX_MASK 0x3fffffffu      // table index (precomputed tables: window * table_n + point < 2^30, checked at registration)
-
-struct MsmGeom {
-    u32 n;          // scalars per MSM
-    u32 table_n;    // registered points (row pitch of the window tables)
-    u32 c;          // window bits
-    u32 W;          // windows = ceil(256 / c)
-    u32 nb;         // buckets per group = 2^(c-1)
-    u32 G;          // bucket groups per MSM: 1 (precomputed tables) or W
-    u32 batch;      // independent MSMs in this launch
-    u32 slices;     // sort blocks per (group, batch)
-    u32 L0;         // points per lane of k_msm_accum0
-    u32 wb;         // G == W only: windows (= bucket groups) one sort block covers; the sort's grid.y = ceil(G / wb)
-};
 
 // ---- scalar -> signed digits -------------------------------------------------------------
 // canonical scalar s < 2^255, digits d_w in [-(2^(c-1) - 1), 2^(c-1)], sum d_w 2^(cw) = s.
@@ -139,10 +118,6 @@ struct DigitStream {
         bucket = mag - 1;   // mag == 0 -> 0xffffffff
     }
 };
-
-// second-level split of the bucket index: buckets = partitions x 2^sub sub-buckets
-// (17-bit windows: 512 sub-buckets, so that the 2^16 buckets are still 128 partitions -- k_msm_part's lists -- and a k_msm_bucket round is still 2048 pairs)
-__host__ __device__ inline u32 msm_sub_bits(u32 c) { return c - 1 < 8 ? c - 1 : (c >= 17 ? 9u : 8u); }
 
 // Groups of equal scalars inside a wave.  A grand-product column over unused rows, a permuted lookup column's runs of equal inputs and a sorted table hand a
 // wave ONE value -- or two or three where runs meet; lanes that hold the same scalar have the same digits, so per window one lane per GROUP counts / reserves
@@ -272,7 +247,6 @@ FP_DEV u32 colscan_one(u32 nb, u32 slices, u32 total_buckets, u32* bh, const uns
 }
 // (256 threads.)  A block of the first table also leaves the sums of its 256 buckets -- points and non-empty buckets -- for the scan below:
 // bsum_items / bsum_tasks [blockIdx] (until round 4 a launch of its own, k_scan_block_sums).
-#define SCAN_THREADS 256
 static __global__ __launch_bounds__(SCAN_THREADS) void k_msm_colscan(u32 nb, u32 slices, u32 total_buckets, u32* bh, const unsigned short* bh16, u32* count, u32 blocks_a, u32 P,
                                                                      u32 total_parts, u32* pc, u32* bsum_items, u32* bsum_tasks, u32* merge_counters) {
     msm_tail_prio();
@@ -410,9 +384,7 @@ static __global__ __launch_bounds__(SCAN_THREADS) void k_scan_offsets(const u32*
 // place -- wave-synchronous, no block barrier), reserves its share of every partition run with one
 // returning atomic per partition, and copies the staged pairs out in staging order: a store
 // instruction then touches ~8-16 cache lines instead of 64 (these kernels wait to ISSUE stores).
-// LDS of one wave: the staging of 512 pairs (8 B + a 2-B partition tag each) and four words per list (count, first slot, cursor, reserved position); `lists` = 128,
-// or 256 for the 256 partitions of a 17-bit window
-#define MSM_PART_WAVE_LDS(lists) (4 * (lists) * 4 + 512 * 8 + 512 * 2)
+// LDS of one wave: MSM_PART_WAVE_LDS(lists) (msm_plan.hpp)
 template <class FS>
 __global__ __launch_bounds__(MSM_SORT_THREADS) void k_msm_part(MsmGeom g, const fe* scalars, const u32* off, const u32* pc, unsigned long long* pairs, u32 lists) {
     msm_tail_prio();
@@ -535,7 +507,6 @@ __global__ __launch_bounds__(MSM_SORT_THREADS) void k_msm_part(MsmGeom g, const 
 // grid (P * ceil(slices / MSM_BUCKET_SLICES), total_groups); 256 threads.  A block walks
 // MSM_BUCKET_SLICES consecutive slices of one partition: the sort is stable, so after slice k the
 // cursors already stand at slice k + 1's first positions -- no re-initialisation.
-#define MSM_BUCKET_SLICES 4
 static __global__ __launch_bounds__(256) void k_msm_bucket(u32 nb, u32 c, u32 slices, const u32* off, const u32* bh, const u32* pc,
                                                           const unsigned long long* pairs, u32* idx_out, u32 per_block) {
     msm_tail_prio();
@@ -819,6 +790,15 @@ __global__ void k_jac_to_affine(const jacobian_t* in, affine_t* out, u32 count) 
 // host driver (instantiated once per curve in msm_<curve>.hip)
 // ==========================================================================================
 
+static_assert(sizeof(xyzz29_rec) == MSM_REC_BYTES, "msm_plan.hpp sizes the record buffers");
+
+// the workspace buffers of a launch, in the order of MsmPlan::ws_bytes
+static DevBuf dehalo_ctx::* const msm_ws_bufs[MSM_WS_N] = {
+    &dehalo_ctx::ws_count, &dehalo_ctx::ws_counters, &dehalo_ctx::ws_bhist, &dehalo_ctx::ws_pcount, &dehalo_ctx::ws_pairs, &dehalo_ctx::ws_off, &dehalo_ctx::ws_records,
+    &dehalo_ctx::ws_merge_parts, &dehalo_ctx::ws_merge_lists, &dehalo_ctx::ws_idx, &dehalo_ctx::ws_partial0, &dehalo_ctx::ws_buckets, &dehalo_ctx::ws_contrib, &dehalo_ctx::ws_tree,
+    &dehalo_ctx::ws_bred_cnt, &dehalo_ctx::ws_gsums, &dehalo_ctx::ws_bsum};
+
+// plan (msm_plan.hpp: every number of the launch), ensure the workspace, launch
 template <class CV>
 int run_msm_t(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, size_t len, size_t batch, jacobian_t* d_out, hipStream_t s) {
     typedef typename CV::Scalar FS;
@@ -827,208 +807,78 @@ int run_msm_t(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, s
         HIP_TRY(ctx, hipMemsetAsync(d_out, 0, batch * sizeof(jacobian_t), s));
         return 0;
     }
-    MsmGeom g;
-    g.n = (u32)len; g.table_n = (u32)bases->n; g.c = bases->c; g.W = bases->W; g.nb = 1u << (g.c - 1);
-    g.G = bases->precomp ? 1 : g.W;
-    g.batch = (u32)batch;
-    // sort blocks (k_msm_hist, k_msm_part): msm_sort_block threads, two scalars a thread until the grid has 256 K threads, then longer slices.  1024-thread
-    // blocks (the default) take 128 and 115 KiB of LDS and so a compute unit to themselves; 512-thread blocks take 64 KiB (packed 16-bit histogram) and 58 KiB
-    // (eight waves' staging) and start beside an NTT tile / merge / reduction block of another context -- which removes the sort's waiting and nothing else:
-    // the chip is throughput-bound, the time moves to the kernels the sort now shares a CU with, and twice the per-slice histograms cost 26 us of the lone sort
-    // (profiles/r06_sort_block_ab.txt; DESIGN.md sections 4 and 8)
-    const u32 sort_threads = ctx->msm_sort_block == 512 ? 512u : 1024u;
-    g.slices = (u32)std::min<size_t>(256 * (1024 / sort_threads), std::max<size_t>(1, len / (2 * sort_threads)));
-    {   // small precomputed-table launches: 2048 scalars a sort block leave a 2^14 column 8 blocks and a 2^11 column ONE for k_msm_hist / k_msm_part (21 + 34 us of
-        // latency where the work is 2); down to 256 scalars a block until ~128 blocks are there (DEHALO_MSM_SMALL_SLICES=0: the A/B)
-        static const bool small_slices = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_SMALL_SLICES"); return !(e && e[0] == '0'); }();
-        if (small_slices && g.G == 1 && (size_t)g.slices * batch < 128)
-            g.slices = (u32)std::max<size_t>(g.slices, std::min<size_t>(std::max<size_t>(1, len / 256), (128 + batch - 1) / batch));
-    }
-    if ((size_t)g.nb * 4 > 128 * 1024) {      // a 17-bit window (2^16 buckets: precomputed tables only): the histogram fits the LDS only as packed 16-bit counters --
-        if (g.G != 1) return dh_fail(ctx, DEHALO_ERR_INVALID, "a 17-bit window needs a precomputed table");
-        g.slices = (u32)std::max<uint64_t>(g.slices, ((uint64_t)len * g.W + 65534) / 65535);      // -- so a slice's scalars times the windows stay below 2^16
-    }
-    {   // single-row tables: windows per sort block -- the block's histograms fit 128 KiB of LDS and its (group, partition) runs the 128 staging lists
-        const u32 sb = msm_sub_bits(g.c), Pg = g.nb >> sb;
-        const u32 fit = std::min<u32>(std::min<u32>(g.W, 128 / Pg), (128u * 1024 / 4) / g.nb);
-        const u32 fill = (u32)((uint64_t)g.W * g.slices * batch / 256);        // ... while the grid keeps >= 256 blocks (2^14: one window per block as before)
-        g.wb = g.G == 1 ? g.W : std::max<u32>(1, std::min<u32>(fit, fill));
-    }
-    const uint64_t total_groups = (uint64_t)batch * g.G;
-    const uint64_t total_buckets = total_groups * g.nb;
-    const uint64_t Mmax = (uint64_t)batch * len * g.W;
-    if (Mmax >= (1ull << 32) || total_buckets >= (1ull << 31))
-        return dh_fail(ctx, DEHALO_ERR_INVALID, "batch * len * windows too large for one launch");
-    // points per lane: the lanes fill the chip (msm_acc_waves waves per SIMD of k_msm_accum0) a whole number of times.  The value is
-    // fixed ON THE DEVICE from the number of points actually sorted (k_scan_offsets); the host only bounds the lane count.
-    const uint32_t lcap = (uint32_t)ctx->msm_acc_points;
-    const uint64_t resident = (uint64_t)ctx->num_cus * 4 * (lcap ? 1 : (uint64_t)ctx->msm_acc_waves) * 64;
-    const uint64_t lmax = 64 * 4 / (uint64_t)ctx->msm_acc_waves;
-    g.L0 = 0;
-    const uint32_t acc_block = ctx->msm_acc_block == MSM_ACC_THREADS_MAX ? MSM_ACC_THREADS_MAX : MSM_ACC_THREADS;
-    uint64_t lanes_max;
-    if (lcap) {
-        uint64_t k = 4;
-        while (Mmax > k * resident * lcap) k += 2;
-        lanes_max = k * resident + acc_block;
-    } else {
-        const uint64_t rounds_max = std::max<uint64_t>(1, (Mmax + resident * lmax - 1) / (resident * lmax));
-        lanes_max = rounds_max * resident + acc_block;
-    }
-    const uint64_t nt0_max = lanes_max + total_buckets;        // records: one per lane + one per non-empty bucket (upper bound)
-    const size_t REC = sizeof(xyzz29_rec);
+    MsmTuning tuning = msm_experiment_tuning();
+    tuning.sort_block = ctx->msm_sort_block; tuning.acc_block = ctx->msm_acc_block; tuning.acc_points = ctx->msm_acc_points; tuning.acc_waves = ctx->msm_acc_waves;
+    tuning.acc_min_layers = ctx->msm_acc_min_layers; tuning.num_cus = ctx->num_cus;
+    MsmPlan p;
+    if (const char* refused = msm_plan(MsmShape{len, batch, bases->n, bases->c, bases->W, bases->precomp != 0}, tuning, &p)) return dh_fail(ctx, DEHALO_ERR_INVALID, refused);
+    const MsmGeom& g = p.g;
 
-    TRY(dh_ensure(ctx, ctx->ws_count, total_buckets * 4));
-    TRY(dh_ensure(ctx, ctx->ws_counters, 64));                                   // 8 merge-class counters | L0 | M
-    TRY(dh_ensure(ctx, ctx->ws_bhist, total_buckets * (size_t)g.slices * 6));   // per-block histograms: the prefixes (u32), and behind them the packed 16-bit counts when k_msm_hist writes those
-    const u32 sub_bits = msm_sub_bits(g.c), P = g.nb >> sub_bits;
-    TRY(dh_ensure(ctx, ctx->ws_pcount, total_groups * (size_t)g.slices * P * 4));   // per-(slice, partition) counts
-    TRY(dh_ensure(ctx, ctx->ws_pairs, Mmax * 8));                                   // partition-sorted (sub-bucket, reference) pairs
-    TRY(dh_ensure(ctx, ctx->ws_off, (total_buckets + 1) * 4));
-    TRY(dh_ensure(ctx, ctx->ws_records, (total_buckets + 1) * 4 * 3));           // nrank | rbeg | rend
-    // merge-class lists: `cap` words per class -- a bucket index per listed bucket, or (classes 5 / 6 of k_msm_merge2) 2 words per 512-record part and 4 per heavy bucket
-    const u32 merge_cap = (u32)std::max<uint64_t>(std::min<uint64_t>(total_buckets, nt0_max / 2 + 1), 4 * (nt0_max / MERGE2_CHUNK + 2));
-    TRY(dh_ensure(ctx, ctx->ws_merge_parts, (2 * (nt0_max / MERGE2_CHUNK) + 4) * sizeof(xyzz29_rec)));   // part sums of the heavy buckets
-    TRY(dh_ensure(ctx, ctx->ws_merge_lists, (size_t)merge_cap * MSM_MERGE_COUNTERS * 4));   // merge-class lists
-    TRY(dh_ensure(ctx, ctx->ws_idx, Mmax * 4));
-    TRY(dh_ensure(ctx, ctx->ws_partial0, nt0_max * REC));
-    TRY(dh_ensure(ctx, ctx->ws_buckets, total_buckets * REC));
-    // (the radix-2 bucket reduction keeps its node vectors in the same two buffers: BRED_VMAX records per block of 128 / 256 buckets / per cluster of 16 blocks)
-    const size_t bred_blocks = std::max<size_t>(1, g.nb / BRED_BLOCK_BUCKETS_MIN);
-    TRY(dh_ensure(ctx, ctx->ws_contrib, total_groups * bred_blocks * BRED_VMAX * REC));
-    TRY(dh_ensure(ctx, ctx->ws_tree, total_groups * 16 * BRED_VMAX * REC));
-    if ((size_t)total_groups * BRED_CNT_PER_GROUP * 4 > ctx->ws_bred_cnt.cap) {      // cluster / group arrival counters: zero when allocated, left zero by every launch
-        TRY(dh_ensure(ctx, ctx->ws_bred_cnt, (size_t)total_groups * BRED_CNT_PER_GROUP * 4));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->ws_bred_cnt.p, 0, ctx->ws_bred_cnt.cap, s));
+    for (u32 i = 0; i < MSM_WS_N; i++) {
+        DevBuf& b = ctx->*msm_ws_bufs[i];
+        const bool grows = p.ws_bytes[i] > b.cap;
+        TRY(dh_ensure(ctx, b, p.ws_bytes[i]));
+        if (grows && i == MSM_WS_BRED_CNT) HIP_TRY(ctx, hipMemsetAsync(b.p, 0, b.cap, s));      // cluster / group arrival counters: zero when allocated, left zero by every launch
     }
-    TRY(dh_ensure(ctx, ctx->ws_gsums, total_groups * REC));
+    const u32 tb = (u32)p.total_buckets;
     u32* count = (u32*)ctx->ws_count.p;
-    u32* cursor = (u32*)ctx->ws_counters.p;
+    u32* merge_counters = (u32*)ctx->ws_counters.p;      // 8 merge-class counters | L0 | M
+    u32* geo = merge_counters + MSM_MERGE_COUNTERS;
     u32* off = (u32*)ctx->ws_off.p;
     u32* nrank = (u32*)ctx->ws_records.p;
-    u32* rbeg = nrank + (total_buckets + 1);
-    u32* rend = rbeg + (total_buckets + 1);
+    u32* rbeg = nrank + (p.total_buckets + 1);
+    u32* rend = rbeg + (p.total_buckets + 1);
     u32* merge_lists = (u32*)ctx->ws_merge_lists.p;
-    u32* merge_counters = cursor;
     u32* bh = (u32*)ctx->ws_bhist.p;
+    unsigned short* bh16 = reinterpret_cast<unsigned short*>(bh + p.total_buckets * (size_t)g.slices);
     u32* pc = (u32*)ctx->ws_pcount.p;
     unsigned long long* pairs = (unsigned long long*)ctx->ws_pairs.p;
+    u32* bs_i = (u32*)ctx->ws_bsum.p;
+    u32* bs_t = bs_i + p.cs_a;
     u32* idx = (u32*)ctx->ws_idx.p;
     xyzz29_rec* partial0 = (xyzz29_rec*)ctx->ws_partial0.p;
     xyzz29_rec* buckets = (xyzz29_rec*)ctx->ws_buckets.p;
     xyzz29_rec* gsums = (xyzz29_rec*)ctx->ws_gsums.p;
 
-    // packed 16-bit counters when no bucket of a block can be counted 2^16 times: every scalar of the slice in every window of the block (all windows for G == 1)
-    const u32 per_slice = (u32)((len + g.slices - 1) / g.slices);
-    const bool pack16 = g.nb >= 2 && (uint64_t)per_slice * (g.G == 1 ? g.W : g.wb) <= 65535;
-    const size_t lds_hist = (size_t)g.nb * (pack16 ? 2 : 4) * (g.G == 1 ? 1 : g.wb);
-    const void* hist_fn = pack16 ? (const void*)k_msm_hist<FS, true> : (const void*)k_msm_hist<FS, false>;
-    if (lds_hist > 48 * 1024) {
-        HIP_TRY(ctx, dh_func_lds(ctx, hist_fn, (int)lds_hist));
-    }
-    // block sizes of the two scalar-decoding sort kernels (DEHALO_MSM_HIST_THREADS / DEHALO_MSM_PART_THREADS, 64 .. 1024): smaller blocks fit beside a
-    // resident accumulation of another context (msm_acc_block = 768 leaves one 128-VGPR wave slot per SIMD: 512 threads x 62 VGPRs, 256 x 77)
-    static const u32 hist_threads_env = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_HIST_THREADS"); const int v = e ? atoi(e) : 0; return (u32)std::max(0, std::min(MSM_SORT_THREADS, v & ~63)); }();
-    static const u32 part_threads_env = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_PART_THREADS"); const int v = e ? atoi(e) : 0; return (u32)std::max(0, std::min(MSM_SORT_THREADS, v & ~63)); }();
-    const u32 hist_threads = hist_threads_env ? hist_threads_env : sort_threads, part_threads = part_threads_env ? part_threads_env : sort_threads;
-    const u32 part_lists = (g.G == 1 ? P : 128u) > 128u ? 256u : 128u;      // (G == W: wb windows x Pg partitions <= 128 by the choice of wb above)
-    const size_t lds_part = dh_co_lds_pad(0, 4 * (size_t)part_lists + (size_t)(part_threads / 64) * MSM_PART_WAVE_LDS(part_lists));
+    // dynamic LDS: what the plan says, padded where co-residency experiments ask for it (dh_co_lds_pad); above 48 KiB a kernel has to be told once
+    const void* hist_fn = p.pack16 ? (const void*)k_msm_hist<FS, true> : (const void*)k_msm_hist<FS, false>;
+    if (p.lds_hist > 48 * 1024) HIP_TRY(ctx, dh_func_lds(ctx, hist_fn, (int)p.lds_hist));
+    const size_t lds_part = dh_co_lds_pad(0, p.lds_part);
     HIP_TRY(ctx, dh_func_lds(ctx, (const void*)k_msm_part<FS>, (int)lds_part));
-    const u32 tb = (u32)total_buckets;
+    const size_t lds_bk = dh_co_lds_pad(p.lds_bucket, 0), lds_m = dh_co_lds_pad(18 * 1024, 0), lds_b = dh_co_lds_pad(41 * 1024, 0);
+    TRY(dh_co_lds_attr(ctx, (const void*)k_msm_bucket, lds_bk));
     {
         ScopedTimer t(ctx, s, DEHALO_K_MSM_SORT);
-        dim3 grid(g.slices, g.G == 1 ? 1 : (g.G + g.wb - 1) / g.wb, (u32)batch);
-        unsigned short* bh16 = reinterpret_cast<unsigned short*>(bh + total_buckets * (size_t)g.slices);
-        if (pack16) k_msm_hist<FS, true><<<grid, hist_threads, lds_hist, s>>>(g, d_scalars, reinterpret_cast<u32*>(bh16), pc);
-        else k_msm_hist<FS, false><<<grid, hist_threads, lds_hist, s>>>(g, d_scalars, bh, pc);
-        const u32 cs_a = (tb + 255) / 256, cs_b = ((u32)total_groups * P + 255) / 256;
-        TRY(dh_ensure(ctx, ctx->ws_bsum, (size_t)cs_a * 2 * sizeof(u32)));
-        u32* bs_i = (u32*)ctx->ws_bsum.p;
-        u32* bs_t = bs_i + cs_a;
-        k_msm_colscan<<<cs_a + cs_b, SCAN_THREADS, 0, s>>>(g.nb, g.slices, tb, bh, pack16 ? bh16 : nullptr, count, cs_a, P, (u32)total_groups * P, pc, bs_i, bs_t, merge_counters);
-        k_scan_offsets<<<cs_a, SCAN_THREADS, 0, s>>>(count, tb, bs_i, bs_t, cs_a, cursor + MSM_MERGE_COUNTERS, (u32)resident, (u32)lmax, lcap, (u32)ctx->msm_acc_min_layers, off, nrank, rbeg, rend,
-                                                     merge_lists, merge_cap);
+        const dim3 grid(p.sort_grid[0], p.sort_grid[1], p.sort_grid[2]);
+        if (p.pack16) k_msm_hist<FS, true><<<grid, p.hist_threads, p.lds_hist, s>>>(g, d_scalars, reinterpret_cast<u32*>(bh16), pc);
+        else k_msm_hist<FS, false><<<grid, p.hist_threads, p.lds_hist, s>>>(g, d_scalars, bh, pc);
+        k_msm_colscan<<<p.cs_a + p.cs_b, SCAN_THREADS, 0, s>>>(g.nb, g.slices, tb, bh, p.pack16 ? bh16 : nullptr, count, p.cs_a, p.P, (u32)p.total_groups * p.P, pc, bs_i, bs_t, merge_counters);
+        k_scan_offsets<<<p.cs_a, SCAN_THREADS, 0, s>>>(count, tb, bs_i, bs_t, p.cs_a, geo, (u32)p.resident, (u32)p.lmax, p.lcap, p.kmin, off, nrank, rbeg, rend,
+                                                       merge_lists, p.merge_cap);
         HIP_TRY(ctx, hipGetLastError());
-        k_msm_part<FS><<<grid, part_threads, lds_part, s>>>(g, d_scalars, off, pc, pairs, part_lists);
-        const size_t lds_bk = dh_co_lds_pad(22 * 1024, 0);
-        TRY(dh_co_lds_attr(ctx, (const void*)k_msm_bucket, lds_bk));
-        // slices per block: 4 (measured best on dense columns) unless DEHALO_MSM_BUCKET_SLICES says otherwise (1 / 2 / 4 / 8: A/B measurements on the
-        // skewed columns of a proof, where a block's run can be 17 windows x 4 slices of ONE value)
-        static const u32 bucket_slices = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_BUCKET_SLICES"); const int v = e ? atoi(e) : MSM_BUCKET_SLICES; return (u32)(v >= 1 && v <= 16 ? v : MSM_BUCKET_SLICES); }();
-        // ... and fewer while the grid would not give every CU a block (2^14: 16 partitions x 8 slices -- 32 blocks of 10 k pairs each took 49 us a column, round 4)
-        u32 bslices = bucket_slices;
-        static const bool bucket_fill = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_BUCKET_FILL"); return !(e && e[0] == '0'); }();
-        while (bucket_fill && bslices > 1 && (uint64_t)P * ((g.slices + bslices - 1) / bslices) * total_groups < (uint64_t)ctx->num_cus) bslices >>= 1;
-        k_msm_bucket<<<dim3(P * ((g.slices + bslices - 1) / bslices), (u32)total_groups), 256, lds_bk, s>>>(g.nb, g.c, g.slices, off, bh, pc, pairs, idx, bslices);
+        k_msm_part<FS><<<grid, p.part_threads, lds_part, s>>>(g, d_scalars, off, pc, pairs, p.part_lists);
+        k_msm_bucket<<<dim3(p.bucket_grid[0], p.bucket_grid[1]), p.bucket_threads, lds_bk, s>>>(g.nb, g.c, g.slices, off, bh, pc, pairs, idx, p.bslices);
         HIP_TRY(ctx, hipGetLastError());
     }
     {
         ScopedTimer t(ctx, s, DEHALO_K_MSM_ACCUMULATE);
-        u32 blocks = (u32)((lanes_max + acc_block - 1) / acc_block);
-        // DEHALO_MSM_ACC_LDS (bytes of dynamic LDS per block, unused by the kernel): caps the accumulation's resident blocks per CU so that
-        // wave slots and registers stay free for the kernels of other contexts (tuning experiments; results never depend on it)
-        static const unsigned acc_lds = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_LDS"); return e ? (unsigned)atoi(e) : 0u; }();
-        k_msm_accum0<CV><<<blocks, acc_block, acc_lds, s>>>(g, tb, idx, off, nrank, bases->table, partial0, cursor + MSM_MERGE_COUNTERS);
+        k_msm_accum0<CV><<<p.acc_grid, p.acc_block, p.acc_lds, s>>>(g, tb, idx, off, nrank, bases->table, partial0, geo);
         HIP_TRY(ctx, hipGetLastError());
     }
     {
         ScopedTimer t(ctx, s, DEHALO_K_MSM_REDUCE);
+        TRY(dh_co_lds_attr(ctx, (const void*)k_msm_merge2<CV>, lds_m));
+        TRY(dh_co_lds_attr(ctx, (const void*)k_msm_bred<CV>, lds_b));
+        TRY(msm_stamps_arm(ctx));
         // partial sums -> one point per bucket: every size class in one launch (k_msm_merge2, msm_bred.cuh: operands in LDS, < 128 VGPRs, quads throughout)
-        {
-            const size_t lds_m = dh_co_lds_pad(18 * 1024, 0);
-            TRY(dh_co_lds_attr(ctx, (const void*)k_msm_merge2<CV>, lds_m));
-#ifdef DEHALO_EXPERIMENTS
-            static const bool merge_stamps = getenv("DEHALO_MSM_MERGE_STAMPS") != nullptr;
-            static const int merge_q3 = [] { const char* e = getenv("DEHALO_MSM_MERGE_Q3"); return e ? atoi(e) : 0; }();
-            static bool merge_q3_set = false;
-            if (merge_q3 && !merge_q3_set) { HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_merge2_q3), &merge_q3, sizeof(int))); merge_q3_set = true; }
-            if (merge_stamps) { const int on = 1; HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_merge2_stamps_on), &on, sizeof(on))); }
-#endif
-            k_msm_merge2<CV><<<MERGE2_GRID, 256, lds_m, s>>>(rbeg, rend, partial0, buckets, merge_counters, merge_lists, merge_cap, (xyzz29_rec*)ctx->ws_merge_parts.p, tb);
-#ifdef DEHALO_EXPERIMENTS
-            if (merge_stamps) TRY(merge2_report_stamps(ctx, tb, s));
-#endif
-        }
+        k_msm_merge2<CV><<<MERGE2_GRID, 256, lds_m, s>>>(rbeg, rend, partial0, buckets, merge_counters, merge_lists, p.merge_cap, (xyzz29_rec*)ctx->ws_merge_parts.p, tb);
         // bucket reduction: ONE launch of the radix-2 recursion (msm_bred.cuh: 2 additions per bucket, operands in LDS, < 128 VGPRs; the last block of a group
-        // weights, sums and writes the result)
-        bool emitted = false;
-        if (g.nb < 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm: window below 4 bits");      // (unreachable through dehalo_bases_register: c >= 4)
-        {
-            // buckets per block: 128 up to 2^13 buckets (the kernel alone 119 -> 107 us at 4096 buckets, 134 -> 125 at 16384, 153 -> 153 at 32768 where the third level costs
-            // what the shorter first one saves); 256 above: measured on k = 17 proofs the 128-bucket blocks -- twice as many, beside the side context's transforms -- cost
-            // 0.1 ms (profiles/r04_bred_block_buckets.txt).
-            static const u32 bred_bb_env = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_BRED_BLOCK"); const int v = e ? atoi(e) : 0; return v == 128 || v == 256 ? (u32)v : 0u; }();
-            const u32 bred_bb = bred_bb_env ? bred_bb_env : (g.nb <= 8192 ? 128u : 256u);
-            const u32 nblk = std::max<u32>(1, g.nb / bred_bb);
-            const bool fin = g.G == 1;
-            const size_t lds_b = dh_co_lds_pad(41 * 1024, 0);
-            TRY(dh_co_lds_attr(ctx, (const void*)k_msm_bred<CV>, lds_b));
-#ifdef DEHALO_EXPERIMENTS
-            static const bool bred_stamps = getenv("DEHALO_MSM_BRED_STAMPS") != nullptr;
-            if (bred_stamps) {
-                const int on = 1; unsigned long long init[12] = {0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, 0, 0};
-                HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_bred_stamps_on), &on, sizeof(on)));
-                HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_bred_stamps), init, sizeof(init)));
-            }
-#endif
-            k_msm_bred<CV><<<dim3(nblk, (u32)total_groups), BRED_THREADS, lds_b, s>>>(g.nb, bred_bb, buckets, (xyzz29_rec*)ctx->ws_contrib.p, (xyzz29_rec*)ctx->ws_tree.p, (u32*)ctx->ws_bred_cnt.p, gsums,
-                                                                                 fin ? d_out : nullptr, fin ? ctx->msm_affine_out : nullptr);
-            emitted = fin;
-#ifdef DEHALO_EXPERIMENTS
-            if (bred_stamps) {
-                unsigned long long st[12];
-                HIP_TRY(ctx, hipStreamSynchronize(s));
-                HIP_TRY(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_bred_stamps), sizeof(st)));
-                auto us = [&](int i) { return (double)(st[i] - st[7]) / 100.0; };
-                fprintf(stderr, "k_msm_bred nb %u groups %u, us after the first block's start (the block that finishes group 0): its start %.1f | phase 0 tree done %.1f | phase 1 %.1f | phase 2 %.1f | "
-                        "doublings done %.1f | final tree %.1f | result written %.1f || hand-offs: phase 1 last arrival known %.1f, siblings in LDS %.1f | phase 2 %.1f, %.1f\n", g.nb, (unsigned)total_groups,
-                        us(0), us(1), st[2] ? us(2) : 0.0, st[3] ? us(3) : 0.0, us(5), us(4), us(6), st[8] ? us(8) : 0.0, st[9] ? us(9) : 0.0, st[10] ? us(10) : 0.0, st[11] ? us(11) : 0.0);
-            }
-#endif
-        }
-        if (!emitted) {
-            k_msm_final<CV><<<(u32)batch, 256, 0, s>>>(g, gsums, d_out, ctx->msm_affine_out);
-        }
+        // weights, sums and writes the result -- of the MSM when the group is all of it)
+        const bool fin = g.G == 1;
+        k_msm_bred<CV><<<dim3(p.nblk, (u32)p.total_groups), BRED_THREADS, lds_b, s>>>(g.nb, p.bred_bb, buckets, (xyzz29_rec*)ctx->ws_contrib.p, (xyzz29_rec*)ctx->ws_tree.p, (u32*)ctx->ws_bred_cnt.p, gsums,
+                                                                                     fin ? d_out : nullptr, fin ? ctx->msm_affine_out : nullptr);
+        TRY(msm_stamps_report(ctx, g.nb, (u32)p.total_groups, tb, s));
+        if (!fin) k_msm_final<CV><<<g.batch, 256, 0, s>>>(g, gsums, d_out, ctx->msm_affine_out);
         HIP_TRY(ctx, hipGetLastError());
     }
     return 0;

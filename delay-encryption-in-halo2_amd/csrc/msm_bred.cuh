@@ -19,6 +19,7 @@
 // vectors, and that same block weights, sums and emits the result: one launch per MSM batch instead of three.
 #pragma once
 #include "ec29.cuh"
+#include "msm_plan.hpp"
 
 // the measurement hooks (wall-clock stamps of the phases: DEHALO_MSM_BRED_STAMPS, DEHALO_MSM_MERGE_STAMPS, DEHALO_MSM_MERGE_Q3) exist in -DDEHALO_EXPERIMENTS builds only
 #ifndef DEHALO_PHASE_STAMPS
@@ -28,13 +29,8 @@
 #define DEHALO_PHASE_STAMPS 0
 #endif
 #endif
-#define BRED_THREADS 256
+// (BRED_THREADS, BRED_BLOCK_BUCKETS[_MIN], BRED_FANIN, BRED_VMAX, BRED_CNT_PER_GROUP and the MERGE2_* grid sections: msm_plan.hpp -- they size buffers and grids)
 #define BRED_QUADS (BRED_THREADS / 4)
-#define BRED_BLOCK_BUCKETS 256      // buckets of a block at most (the LDS array): 4 per quad
-#define BRED_BLOCK_BUCKETS_MIN 128  // ... and at least (sizes the node buffers); run_msm_t picks (msm_bred_block)
-#define BRED_FANIN 16               // node vectors one block combines in the second / third stage
-#define BRED_VMAX 17                // points per node vector in HBM: A_0 .. A_15, X
-#define BRED_CNT_PER_GROUP 32       // u32 counters per bucket group: clusters [0, 16), group [16]
 
 // ---- quad-cooperative group operations on records in memory (LDS or HBM): record = 36 words, coordinate c at words [9 c, 9 c + 9) ----
 FP_DEV f29 q_ld(const u32* rec, u32 coord) {
@@ -351,14 +347,6 @@ FP_DEV void q_strided_sum(u32* acc, u32* inc, const xyzz29_rec* partial, u32 fir
     __builtin_amdgcn_wave_barrier();
 }
 
-#define MERGE2_BLOCKS_LIGHT 1024     // per light class
-#define MERGE2_BLOCKS_Q8 512
-#define MERGE2_BLOCKS_BLOCK 512
-#define MERGE2_BLOCKS_PARTS 1024
-#define MERGE2_BLOCKS_COPY 256        // buckets with one partial sum (copied) or none (identity): one lane per bucket, the last section of the grid
-#define MERGE2_GRID_SUMS (MERGE2_BLOCKS_PARTS + MERGE2_BLOCKS_BLOCK + MERGE2_BLOCKS_Q8 + 3 * MERGE2_BLOCKS_LIGHT)
-#define MERGE2_GRID (MERGE2_GRID_SUMS + MERGE2_BLOCKS_COPY)
-
 // classification for k_msm_merge2: one lane per bucket; S = 0 -> identity, S = 1 -> copy, otherwise the bucket is queued in the list of its class
 // (one atomic per wave and class).  The classes are cut so that no chain is longer than ~14 additions whatever S is:
 //   0 | 1 | 2   S = 2 | 3-4 | 5-8: one quad walks the bucket's records (three lists, three grid sections side by side: a wave of 16 quads runs as long as its
@@ -522,4 +510,36 @@ static inline int merge2_report_stamps(dehalo_ctx* ctx, u32 tb, hipStream_t s) {
     fprintf(stderr, "\n");
     return 0;
 }
+static inline bool msm_merge_stamps_wanted() { static const bool on = getenv("DEHALO_MSM_MERGE_STAMPS") != nullptr; return on; }
+static inline bool msm_bred_stamps_wanted() { static const bool on = getenv("DEHALO_MSM_BRED_STAMPS") != nullptr; return on; }
+// measurement only, before k_msm_merge2 and k_msm_bred are launched: switch the wanted stamps on (and DEHALO_MSM_MERGE_Q3 through)
+static inline int msm_stamps_arm(dehalo_ctx* ctx) {
+    static const int merge_q3 = [] { const char* e = getenv("DEHALO_MSM_MERGE_Q3"); return e ? atoi(e) : 0; }();
+    static bool merge_q3_set = false;
+    const int on = 1;
+    if (merge_q3 && !merge_q3_set) { HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_merge2_q3), &merge_q3, sizeof(int))); merge_q3_set = true; }
+    if (msm_merge_stamps_wanted()) HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_merge2_stamps_on), &on, sizeof(on)));
+    if (msm_bred_stamps_wanted()) {
+        unsigned long long init[12] = {0, 0, 0, 0, 0, 0, 0, ~0ull, 0, 0, 0, 0};
+        HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_bred_stamps_on), &on, sizeof(on)));
+        HIP_TRY(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_bred_stamps), init, sizeof(init)));
+    }
+    return 0;
+}
+// ... and after both: what the stamps say (stderr)
+static inline int msm_stamps_report(dehalo_ctx* ctx, u32 nb, u32 groups, u32 tb, hipStream_t s) {
+    if (msm_merge_stamps_wanted()) TRY(merge2_report_stamps(ctx, tb, s));
+    if (!msm_bred_stamps_wanted()) return 0;
+    unsigned long long st[12];
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, hipMemcpyFromSymbol(st, HIP_SYMBOL(g_bred_stamps), sizeof(st)));
+    auto us = [&](int i) { return (double)(st[i] - st[7]) / 100.0; };
+    fprintf(stderr, "k_msm_bred nb %u groups %u, us after the first block's start (the block that finishes group 0): its start %.1f | phase 0 tree done %.1f | phase 1 %.1f | phase 2 %.1f | "
+            "doublings done %.1f | final tree %.1f | result written %.1f || hand-offs: phase 1 last arrival known %.1f, siblings in LDS %.1f | phase 2 %.1f, %.1f\n", nb, groups,
+            us(0), us(1), st[2] ? us(2) : 0.0, st[3] ? us(3) : 0.0, us(5), us(4), us(6), st[8] ? us(8) : 0.0, st[9] ? us(9) : 0.0, st[10] ? us(10) : 0.0, st[11] ? us(11) : 0.0);
+    return 0;
+}
+#else
+static inline int msm_stamps_arm(dehalo_ctx*) { return 0; }
+static inline int msm_stamps_report(dehalo_ctx*, u32, u32, u32, hipStream_t) { return 0; }
 #endif

@@ -161,3 +161,19 @@ def test_bench_first_attempt_travels_to_the_second():
     err = "[bench 0.1 s] steps: preheat\nnoise\n[bench 12.0 s] proof delay_enc k = 17: proving\nMemory access fault by GPU node-2\n"
     assert bench._section_of(err) == "proof delay_enc k = 17: proving"
     assert bench._section_of("") == ""
+
+
+def test_msm_launch_planner_invariants_under_sanitizers():
+    """csrc/msm_plan.hpp -- the MSM's window rules, launch shapes and workspace sizes, free of HIP headers -- built by g++ with -fsanitize=address,undefined and
+    swept by tests/native_host/msm_plan_check.cpp: every len in 1 .. 2^17 and the 2^k edges up to 2^22, eight batch sizes, both table modes, c = 4 .. 17 for the three
+    scalar fields, every tuning the suite and bench.py set.  Each plan that is not a refusal keeps the invariants the kernels rely on (LDS limits, 16-bit counter
+    range, list and grid coverage, the device's lanes-per-launch rule, the bucket reduction's counter range) and sizes every buffer by its closed form."""
+    import os
+    import subprocess
+    from conftest import ROOT
+
+    out = subprocess.run(["make", "-C", ROOT, "msm_plan_check"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout + out.stderr
+    run = subprocess.run([os.path.join(ROOT, "tests", "native_host", "msm_plan_check")], capture_output=True, text=True, timeout=900)
+    assert run.returncode == 0 and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stdout + run.stderr
+    assert "all invariants hold" in run.stdout
