@@ -125,7 +125,8 @@ impl Drop for DehaloParamsKZG<'_> {
 }
 
 /// `ParamsIPA<EqAffine>` (Vesta) from the vectors upstream's `ParamsIPA` holds (`params.g`, `params.g_lagrange`, `params.w`, `params.u`):
-/// `dehalo_params_ipa_create`.  `ParamsIPA::new` and `read` / `write` are not provided by the library; what it provides over these params is
+/// `dehalo_params_ipa_create`; from `params.g`, `params.w`, `params.u` alone (`from_g`: `g_to_lagrange` runs on the device); or from `ParamsIPA::write`'s
+/// bytes (`read` / `write`).  `ParamsIPA::new` (the hash-to-curve generators) is not provided by the library; what it provides over these params is
 /// keygen (`commit_lagrange` with `Blind::default()`), whole `ProverIPA` proofs (`prover::create_proof_ipa`) and the opening argument of one
 /// polynomial (`dehalo_ipa_open`, upstream's `poly::ipa::commitment::create_proof`).
 pub struct DehaloParamsIPA<'c> {
@@ -145,6 +146,31 @@ impl<'c> DehaloParamsIPA<'c> {
                                           w as *const _ as *const u64, u as *const _ as *const u64, &mut raw)
         })?;
         Ok(Self { ctx, raw, k })
+    }
+
+    /// `ParamsIPA` from `g` alone: `g_lagrange = g_to_lagrange(g, k)` on the device, then as `from_vectors` (`dehalo_params_ipa_from_g`)
+    pub fn from_g(ctx: &'c Context, k: u32, g: &[halo2curves::pasta::EqAffine], w: &halo2curves::pasta::EqAffine, u: &halo2curves::pasta::EqAffine) -> Result<Self, DehaloError> {
+        assert_eq!(g.len(), 1usize << k);
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe {
+            sys::dehalo_params_ipa_from_g(ctx.as_ptr(), sys::DEHALO_CURVE_VESTA, k, g.as_ptr() as *const u64, w as *const _ as *const u64, u as *const _ as *const u64, &mut raw)
+        })?;
+        Ok(Self { ctx, raw, k })
+    }
+
+    /// `ParamsIPA::read(&mut reader)`: k | g | g_lagrange | w | u, compressed points (`dehalo_params_ipa_read`)
+    pub fn read(ctx: &'c Context, bytes: &[u8]) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe { sys::dehalo_params_ipa_read(ctx.as_ptr(), sys::DEHALO_CURVE_VESTA, bytes.as_ptr(), bytes.len(), &mut raw) })?;
+        let k = if bytes.len() >= 4 { u32::from_le_bytes([bytes[0], bytes[1], bytes[2], bytes[3]]) } else { 0 };
+        Ok(Self { ctx, raw, k })
+    }
+
+    /// `params.write(&mut writer)` (`dehalo_params_ipa_write`)
+    pub fn write(&self) -> Result<Vec<u8>, DehaloError> {
+        let mut out = vec![0u8; unsafe { sys::dehalo_params_ipa_size(self.raw) }];
+        self.ctx.check(unsafe { sys::dehalo_params_ipa_write(self.raw, out.as_mut_ptr(), out.len()) })?;
+        Ok(out)
     }
 }
 

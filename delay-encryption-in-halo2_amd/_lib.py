@@ -31,6 +31,7 @@ SYMBOLS = [
     "dehalo_transcript_squeeze_challenge", "dehalo_transcript_len", "dehalo_transcript_finalize", "dehalo_transcript_release",
     "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs",
     "dehalo_params_ipa_create", "dehalo_params_scheme", "dehalo_generator_collapse_device", "dehalo_ipa_open", "dehalo_blind_commitments_device", "dehalo_prover_proof_size",
+    "dehalo_g_to_lagrange_device", "dehalo_params_ipa_from_g", "dehalo_params_ipa_size", "dehalo_params_ipa_write", "dehalo_params_ipa_read",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
 ]
 
@@ -224,6 +225,12 @@ def load_library():
     lib.dehalo_params_commit_device.argtypes = [P, P, u64p, sz, C.c_int, u64p, P]
     lib.dehalo_params_ipa_create.argtypes = [P, C.c_int, u32, u64p, u64p, u64p, u64p, PP]
     lib.dehalo_params_scheme.argtypes = [P]
+    lib.dehalo_g_to_lagrange_device.argtypes = [P, C.c_int, u64p, u32, u64p, P]
+    lib.dehalo_params_ipa_from_g.argtypes = [P, C.c_int, u32, u64p, u64p, u64p, PP]
+    lib.dehalo_params_ipa_size.argtypes = [P]
+    lib.dehalo_params_ipa_size.restype = sz
+    lib.dehalo_params_ipa_write.argtypes = [P, P, sz]
+    lib.dehalo_params_ipa_read.argtypes = [P, C.c_int, P, sz, PP]
     lib.dehalo_keygen.argtypes = [P, P, C.POINTER(CConstraintSystem), u64p, u64p, C.POINTER(C.c_void_p), u32, u32, PP]
     lib.dehalo_pk_read.argtypes = [P, C.c_int, C.POINTER(CConstraintSystem), P, sz, u32, PP]
     lib.dehalo_pk_size.argtypes = [P]
@@ -428,6 +435,10 @@ class Context:
         """parallel_generator_collapse: d_out[i] = g[i] + [challenge] g[length / 2 + i] (challenge = 4 x u64 Montgomery)"""
         ch = np.ascontiguousarray(challenge, dtype=np.uint64).reshape(4)
         self._check(self.lib.dehalo_generator_collapse_device(self.handle, curve, d_affine, length, ch.ctypes.data, d_out, stream or None))
+
+    def g_to_lagrange(self, curve: int, d_g: int, k: int, d_out: Optional[int] = None, stream: int = 0):
+        """g_to_lagrange: d_out[i] = [n^-1] sum_j [omega^(-i j)] d_g[j] over 2^k affine points (64 B each, device); d_out None: in place"""
+        self._check(self.lib.dehalo_g_to_lagrange_device(self.handle, curve, d_g, k, d_g if d_out is None else d_out, stream or None))
 
     def blind_commitments_device(self, curve: int, d_jacobian: int, d_blinds: int, count: int, d_w_affine: int, stream: int = 0):
         """ParamsIPA's blinding term for one batched MSM's results: d_jacobian[i] += [d_blinds[i]] W, in place (all device pointers; one launch)"""

@@ -278,6 +278,11 @@ const IpaOps* ipa_ops(int curve) {
     return nullptr;
 }
 
+const GfftOps* gfft_ops(int curve) {
+    static const GfftOps* const ops[] = {&bn254_gfft_ops(), &pallas_gfft_ops(), &vesta_gfft_ops()};
+    return curve >= 0 && curve < 3 ? ops[curve] : nullptr;
+}
+
 int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, dehalo_bases** out) {
     if (!curve_ops(curve) || cap == 0 || cap >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_plain_alloc: bad argument");
     std::unique_ptr<dehalo_bases, BasesFree> b(new dehalo_bases());
@@ -362,7 +367,7 @@ void dehalo_ctx_destroy(dehalo_ctx* ctx) {
                       &ctx->ws_bhist, &ctx->ws_pcount, &ctx->ws_pairs, &ctx->ws_bsum, &ctx->ws_idx, &ctx->ws_partial0, &ctx->ws_buckets, &ctx->ws_contrib, &ctx->ws_tree, &ctx->ws_bred_cnt,
                       &ctx->ws_gsums, &ctx->ws_ntt_scratch, &ctx->ws_ntt_io, &ctx->ws_ntt_io2, &ctx->ws_fop[0], &ctx->ws_fop[1], &ctx->ws_fop[2],
                       &ctx->ws_tmp_bases, &ctx->ws_poly[0], &ctx->ws_poly[1], &ctx->ws_poly[2], &ctx->ws_poly[3], &ctx->ws_poly[4], &ctx->ws_poly_io[0], &ctx->ws_poly_io[1],
-                      &ctx->ws_poly_io[2], &ctx->ws_evh[0], &ctx->ws_evh[1], &ctx->ws_evh[2], &ctx->ws_evh[3], &ctx->ws_lookup};
+                      &ctx->ws_poly_io[2], &ctx->ws_evh[0], &ctx->ws_evh[1], &ctx->ws_evh[2], &ctx->ws_evh[3], &ctx->ws_lookup, &ctx->ws_gfft};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& t : ctx->twiddles) (void)hipFree(t.tw);
@@ -616,6 +621,31 @@ int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t*
     memcpy(u.v, challenge, 32);
     const Fe uc = f->to_canonical(u);
     return dh_device(ctx, stream, [&](hipStream_t s) { return ops->collapse(ctx, (const affine_t*)d_affine_xy, half, uc.v, (affine_t*)d_out_affine_xy, s); });
+}
+
+int dehalo_g_to_lagrange_device(dehalo_ctx* ctx, int curve, const uint64_t* d_g_affine_xy, uint32_t k, uint64_t* d_out_affine_xy, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    const GfftOps* ops = gfft_ops(curve);
+    if (!ops) return unknown_curve(ctx);
+    if (!d_g_affine_xy || !d_out_affine_xy) return dh_fail(ctx, DEHALO_ERR_INVALID, "g_to_lagrange: null argument");
+    if (k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "g_to_lagrange: k out of range");
+    const size_t n = (size_t)1 << k;
+    // out == the input is the in-place transform; any other overlap would be read after it is written
+    const uintptr_t ia = (uintptr_t)d_g_affine_xy, ib = ia + 64 * n, oa = (uintptr_t)d_out_affine_xy, ob = oa + 64 * n;
+    if (oa != ia && oa < ib && ia < ob) return dh_fail(ctx, DEHALO_ERR_INVALID, "g_to_lagrange: the output overlaps the input other than in place");
+    // omega_inv = (ROOT_OF_UNITY^(2^(S - k)))^-1, n_inv = (2^k)^-1 [UPSTREAM halo2_proofs/src/poly/commitment.rs g_to_lagrange: ROOT_OF_UNITY_INV squared S - k times, TWO_INV^k]
+    const HostField* f = host_field(curve_scalar_field(curve));
+    if (k > f->two_adicity) return dh_fail(ctx, DEHALO_ERR_INVALID, "g_to_lagrange: k out of range");
+    Fe omega = f->root_of_unity;
+    for (uint32_t i = k; i < f->two_adicity; i++) omega = f->sqr(omega);
+    const Fe omega_inv = f->invert(omega), n_inv = f->to_canonical(f->invert(f->from_u64((uint64_t)n)));
+    return dh_device(ctx, stream, [&](hipStream_t s) -> int {
+        if (k == 0) {      // one point: the transform is the identity map
+            if (oa != ia) HIP_TRY(ctx, hipMemcpyAsync(d_out_affine_xy, d_g_affine_xy, 64, hipMemcpyDeviceToDevice, s));
+            return 0;
+        }
+        return ops->g_to_lagrange(ctx, (const affine_t*)d_g_affine_xy, k, omega_inv.v, n_inv.v, (affine_t*)d_out_affine_xy, s);
+    });
 }
 
 int dehalo_blind_commitments_device(dehalo_ctx* ctx, int curve, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, const uint64_t* d_w_affine_xy, void* stream) {

@@ -1,5 +1,7 @@
-// MSM kernels + driver and the IPA opening's kernels instantiated for CurveVesta (one translation unit per curve: parallel builds).
+// MSM kernels + driver the IPA opening's kernels and the group FFT instantiated for CurveVesta (one translation unit per curve: parallel builds).
 #include "msm.cuh"
 #include "ipa.cuh"
+#include "gfft.cuh"
 const CurveOps& vesta_curve_ops() { static constexpr CurveOps ops = make_curve_ops<CurveVesta>(); return ops; }
 const IpaOps& vesta_ipa_ops() { static constexpr IpaOps ops = make_ipa_ops<CurveVesta>(); return ops; }
+const GfftOps& vesta_gfft_ops() { static constexpr GfftOps ops = make_gfft_ops<CurveVesta>(); return ops; }

@@ -295,29 +295,126 @@ extern "C" int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* o
 extern "C" void dehalo_transcript_release(dehalo_transcript* t) { delete t; }
 
 // ================================================================================================ ParamsIPA and the IPA opening argument
+namespace {
+
+// what dehalo_params_ipa_create and dehalo_params_ipa_from_g share once g_lagrange is known: the two resident MSM tables, g | u | w as plain points on the
+// device and the [U | W] registration
+int ipa_params_finish(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
+                      dehalo_params** out) {
+    const size_t n = (size_t)1 << k;
+    dehalo_params* raw = nullptr;
+    TRY(dehalo_params_create(ctx, curve, k, g, g_lagrange, nullptr, nullptr, &raw));
+    std::unique_ptr<dehalo_params, void (*)(dehalo_params*)> p(raw, [](dehalo_params* q) { (void)dehalo_params_release(q->ctx, q); });
+    p->scheme = DEHALO_SCHEME_IPA;
+    memcpy(p->w, w, 64);
+    memcpy(p->u, u, 64);
+    TRY(p->d_guw.alloc(ctx, 2 * (n + 2), false));
+    TRY(dh_h2d(ctx, p->d_guw.p, g, 64 * n, ctx->stream));
+    TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream));
+    TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream));
+    TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, &p->bases_uw));
+    *out = p.release();
+    return 0;
+}
+
+// the range checks of a ParamsIPA under construction (null arguments are the caller's to report)
+int ipa_params_check(dehalo_ctx* ctx, const std::string& who, int curve, uint32_t k) {
+    if (curve != DEHALO_CURVE_PALLAS && curve != DEHALO_CURVE_VESTA) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, who + ": IPA over Pallas / Vesta only");
+    if (k < 1 || k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, who + ": k out of range");
+    if (!dh_precomputed_table_fits(curve, (size_t)1 << k)) return dh_fail(ctx, DEHALO_ERR_INVALID, who + ": 2^k x windows >= 2^30: precomputed table too large");
+    return 0;
+}
+
+}   // namespace
+
 extern "C" int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8],
                                         const uint64_t u[8], dehalo_params** out) {
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !out || !g || !g_lagrange || !w || !u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: null argument");
-        if (curve != DEHALO_CURVE_PALLAS && curve != DEHALO_CURVE_VESTA) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_ipa_create: IPA over Pallas / Vesta only");
-        if (k < 1 || k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: k out of range");
-        const size_t n = (size_t)1 << k;
-        if (!dh_precomputed_table_fits(curve, n)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_create: 2^k x windows >= 2^30: precomputed table too large");
+        TRY(ipa_params_check(ctx, "params_ipa_create", curve, k));
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
-        dehalo_params* raw = nullptr;
-        TRY(dehalo_params_create(ctx, curve, k, g, g_lagrange, nullptr, nullptr, &raw));
-        std::unique_ptr<dehalo_params, void (*)(dehalo_params*)> p(raw, [](dehalo_params* q) { (void)dehalo_params_release(q->ctx, q); });
-        p->scheme = DEHALO_SCHEME_IPA;
-        memcpy(p->w, w, 64);
-        memcpy(p->u, u, 64);
-        TRY(p->d_guw.alloc(ctx, 2 * (n + 2), false));
-        TRY(dh_h2d(ctx, p->d_guw.p, g, 64 * n, ctx->stream));
-        TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream));
-        TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream));
-        TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, &p->bases_uw));
-        *out = p.release();
+        return ipa_params_finish(ctx, curve, k, g, g_lagrange, w, u, out);
+    });
+}
+
+// ParamsIPA from g alone: g_lagrange = g_to_lagrange(g) on the device (gfft.cuh), then as dehalo_params_ipa_create
+extern "C" int dehalo_params_ipa_from_g(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t w[8], const uint64_t u[8], dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !out || !g || !w || !u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_from_g: null argument");
+        TRY(ipa_params_check(ctx, "params_ipa_from_g", curve, k));
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const size_t n = (size_t)1 << k;
+        DevMem dg, dgl;
+        TRY(dg.alloc(ctx, 2 * n, false));
+        TRY(dgl.alloc(ctx, 2 * n, false));
+        TRY(dh_h2d(ctx, dg.p, g, 64 * n, ctx->stream));
+        TRY(dehalo_g_to_lagrange_device(ctx, curve, dg.u64(), k, dgl.u64(), ctx->stream));
+        std::vector<uint64_t> gl(8 * n);
+        TRY(dehalo_download(ctx, dgl.p, 64 * n, gl.data()));
+        return ipa_params_finish(ctx, curve, k, g, gl.data(), w, u, out);
+    });
+}
+
+// ---- ParamsIPA::{write, read} [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs]: k: u32 LE | g | g_lagrange | w | u, every point GroupEncoding::to_bytes
+// (x little-endian canonical, bit 255 = y is odd, the identity all zero: what dehalo_transcript::write_point appends to a proof)
+namespace {
+void ipa_compress(const HostField* fq, const uint64_t xy[8], uint8_t out[32]) {
+    Fe x, y;
+    memcpy(x.v, xy, 32);
+    memcpy(y.v, xy + 4, 32);
+    if (x.is_zero() && y.is_zero()) { memset(out, 0, 32); return; }
+    uint8_t yb[32];
+    fq->to_bytes(x, out);
+    fq->to_bytes(y, yb);
+    out[31] |= (uint8_t)((yb[0] & 1) << 7);
+}
+}   // namespace
+
+extern "C" size_t dehalo_params_ipa_size(const dehalo_params* p) { return p && p->scheme == DEHALO_SCHEME_IPA ? 4 + 2 * 32 * p->n + 64 : 0; }
+
+extern "C" int dehalo_params_ipa_write(const dehalo_params* p, uint8_t* out, size_t cap) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !out) return DEHALO_ERR_INVALID;
+        if (p->scheme != DEHALO_SCHEME_IPA) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "params_ipa_write: not ParamsIPA (ParamsKZG: dehalo_params_write)");
+        if (cap < dehalo_params_ipa_size(p)) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "params_ipa_write: buffer too small");
+        const HostField* fq = host_field(curve_base_field(p->curve));
+        for (int i = 0; i < 4; i++) out[i] = (uint8_t)(p->k >> (8 * i));
+        uint8_t* o = out + 4;
+        for (size_t i = 0; i < p->n; i++, o += 32) ipa_compress(fq, &p->g[8 * i], o);
+        for (size_t i = 0; i < p->n; i++, o += 32) ipa_compress(fq, &p->g_lagrange[8 * i], o);
+        ipa_compress(fq, p->w, o);
+        ipa_compress(fq, p->u, o + 32);
         return 0;
+    });
+}
+
+extern "C" int dehalo_params_ipa_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: null argument");
+        if (len < 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: unexpected end of input");
+        const uint32_t k = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);      // u32 LE
+        TRY(ipa_params_check(ctx, "params_ipa_read", curve, k));
+        const size_t n = (size_t)1 << k, count = 2 * n + 2;
+        if (len != 4 + 32 * count) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: length does not match k");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        // the encodings go up as they are and come back as affine points: one lane per point takes the square root (k_decompress, gfft.cuh)
+        DevMem enc, pts, status;
+        TRY(enc.alloc(ctx, count, false));
+        TRY(pts.alloc(ctx, 2 * count, false));
+        TRY(status.alloc(ctx, 1, true));
+        TRY(dh_h2d(ctx, enc.p, bytes + 4, 32 * count, ctx->stream));
+        TRY(gfft_ops(curve)->decompress(ctx, (const uint8_t*)enc.p, (affine_t*)pts.p, count, (uint32_t*)status.p, ctx->stream));
+        uint32_t bad[8];
+        TRY(dehalo_download(ctx, status.p, 32, bad));
+        if (bad[0] & 1u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: an x coordinate is not below the modulus");
+        if (bad[0] & 4u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: x = 0 with the sign bit set is not an encoding");
+        if (bad[0] & 2u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: an x coordinate is not on the curve");
+        std::vector<uint64_t> host(8 * count);
+        TRY(dehalo_download(ctx, pts.p, 64 * count, host.data()));
+        return ipa_params_finish(ctx, curve, k, host.data(), host.data() + 8 * n, host.data() + 16 * n, host.data() + 16 * n + 8, out);
     });
 }
 

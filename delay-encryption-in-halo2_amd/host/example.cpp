@@ -53,6 +53,31 @@ int main(int argc, char** argv) {
             std::vector<Fe> a(4, Fe{0, 0, 0, 0});
             Fe one_m{0x34786d38fffffffdULL, 0x992c350be41914adULL, 0xffffffffffffffffULL, 0x3fffffffffffffffULL};  // pasta::Fp R
             be.best_fft(DEHALO_FIELD_PASTA_FP, a, one_m, 2);
+            {   // ParamsIPA over Vesta from g alone (g[i] = [i + 2] G, G = (-1, 2)), written, read back and written again
+                const uint32_t k = 3;
+                uint64_t info[24];
+                be.check(dehalo_field_info(DEHALO_FIELD_PASTA_FQ, info));      // Vesta's base field: info[4 .. 8) = R = 1 in Montgomery form
+                Fe zero{0, 0, 0, 0}, one, two, minus_one;
+                memcpy(one.data(), info + 4, 32);
+                be.check(dehalo_field_op(be.raw(), DEHALO_FIELD_PASTA_FQ, 0 /* add */, one.data(), one.data(), two.data(), 1));
+                be.check(dehalo_field_op(be.raw(), DEHALO_FIELD_PASTA_FQ, 1 /* sub */, zero.data(), one.data(), minus_one.data(), 1));
+                Affine gen;
+                memcpy(gen.data(), minus_one.data(), 32);
+                memcpy(gen.data() + 4, two.data(), 32);
+                std::vector<Affine> pts((size_t(1) << k) + 2);
+                for (size_t i = 0; i < pts.size(); i++) {
+                    Fe s{i + 2, 0, 0, 0};
+                    be.check(dehalo_field_op(be.raw(), DEHALO_FIELD_PASTA_FP, 4 /* canonical -> Montgomery */, s.data(), nullptr, s.data(), 1));
+                    const Projective pr = be.best_multiexp(DEHALO_CURVE_VESTA, {s}, {gen});
+                    be.check(dehalo_to_affine(be.raw(), DEHALO_CURVE_VESTA, pr.data(), 1, pts[i].data()));
+                }
+                const Affine w = pts[pts.size() - 2], u = pts[pts.size() - 1];
+                pts.resize(size_t(1) << k);
+                const std::vector<uint8_t> written = ParamsIPAHandle::from_g(be, DEHALO_CURVE_VESTA, k, pts, w, u).write();
+                const std::vector<uint8_t> again = ParamsIPAHandle::read(be, DEHALO_CURVE_VESTA, written).write();
+                if (written.size() != 4 + 64 * (size_t(1) << k) + 64 || written != again) throw std::runtime_error("ParamsIPA: from_g -> write -> read -> write changed the bytes");
+                std::printf("ParamsIPA from_g / write / read: %zu bytes\n", written.size());
+            }
             std::printf("%s ok\n", dehalo_version());
             return 0;
         }

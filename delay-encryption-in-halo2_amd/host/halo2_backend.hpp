@@ -249,6 +249,40 @@ class ParamsKZG {
     dehalo_params* p_ = nullptr;
 };
 
+// ParamsIPA<C> of the whole call (Pallas / Vesta): the object dehalo_prover_create takes for ProverIPA proofs.  (The class ParamsIPA above is the
+// fine-grained commit / commit_lagrange mirror over two registered tables; this one owns a dehalo_params.)
+class ParamsIPAHandle {
+  public:
+    // from g alone, as upstream's ParamsIPA::new ends: g_lagrange = g_to_lagrange(g), a group FFT on the device
+    static ParamsIPAHandle from_g(const Backend& be, dehalo_curve curve, uint32_t k, const std::vector<Affine>& g, const Affine& w, const Affine& u) {
+        if (g.size() != (size_t(1) << k)) throw std::invalid_argument("ParamsIPA::from_g: g.len() != 1 << k");
+        ParamsIPAHandle p(be);
+        be.check(dehalo_params_ipa_from_g(be.raw(), curve, k, g[0].data(), w.data(), u.data(), &p.p_));
+        return p;
+    }
+    // ParamsIPA::read: k: u32 LE | g | g_lagrange | w | u, 32-byte compressed points
+    static ParamsIPAHandle read(const Backend& be, dehalo_curve curve, const std::vector<uint8_t>& bytes) {
+        ParamsIPAHandle p(be);
+        be.check(dehalo_params_ipa_read(be.raw(), curve, bytes.data(), bytes.size(), &p.p_));
+        return p;
+    }
+    ~ParamsIPAHandle() { if (p_) dehalo_params_release(be_.raw(), p_); }
+    ParamsIPAHandle(const ParamsIPAHandle&) = delete;
+    ParamsIPAHandle(ParamsIPAHandle&& o) : be_(o.be_), p_(o.p_) { o.p_ = nullptr; }
+    // ParamsIPA::write
+    std::vector<uint8_t> write() const {
+        std::vector<uint8_t> out(dehalo_params_ipa_size(p_));
+        be_.check(dehalo_params_ipa_write(p_, out.data(), out.size()));
+        return out;
+    }
+    dehalo_params* raw() const { return p_; }
+
+  private:
+    explicit ParamsIPAHandle(const Backend& be) : be_(be) {}
+    const Backend& be_;
+    dehalo_params* p_ = nullptr;
+};
+
 // ProvingKey<G1Affine> (with its VerifyingKey)
 class ProvingKey {
   public:

@@ -5,6 +5,8 @@ upstream's on-disk formats.
   ParamsKZG::{write, read}      [UPSTREAM halo2_proofs/src/poly/kzg/commitment.rs, SerdeFormat::RawBytes]
       k: u32 LE | g[0..n) | g_lagrange[0..n) | g2 | s_g2 ; a G1 point = x, y as 4 x u64 LE Montgomery limbs (64 B),
       a G2 point = x.c0, x.c1, y.c0, y.c1 (128 B).
+  ParamsIPA::{write, read}      [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs]
+      k: u32 LE | g[0..n) | g_lagrange[0..n) | w | u ; a point = its 32-byte GroupEncoding (params_ipa_bytes / params_ipa_from_bytes).
   VerifyingKey::{write, read}   [UPSTREAM halo2_proofs/src/plonk.rs]
       k: u32 BE | #fixed commitments: u32 BE | commitments (64 B raw each) | permutation commitments |
       selectors packed 8 bools per byte (LSB first), ceil(n / 8) bytes per selector.
@@ -136,6 +138,36 @@ class ParamsKZG:
         gl = np.frombuffer(_exact(fh, 64 * n), dtype=np.uint64).reshape(n, 8)
         g2, s_g2 = _exact(fh, 128), _exact(fh, 128)
         return cls(ctx, curve, k, g, gl, g2, s_g2, window_bits)
+
+
+# ---- ParamsIPA::{write, read} ----------------------------------------------------------------------------
+def params_ipa_bytes(curve: CurveSpec, k: int, g, g_lagrange, w, u) -> bytes:
+    """ParamsIPA::write [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs]: k: u32 LE | g | g_lagrange | w | u, every point its 32-byte GroupEncoding
+    (transcript.compress).  g, g_lagrange: (2^k, 8) u64 Montgomery affine; w, u: 8 u64 each."""
+    from .transcript import compress
+
+    g, gl = decode_points(curve, g), decode_points(curve, g_lagrange)
+    if len(g) != 1 << k or len(gl) != 1 << k:
+        raise ValueError("g and g_lagrange must hold 2^k points")
+    pts = g + gl + decode_points(curve, w) + decode_points(curve, u)
+    return struct.pack("<I", k) + b"".join(compress(curve, P) for P in pts)
+
+
+def params_ipa_from_bytes(curve: CurveSpec, data: bytes):
+    """ParamsIPA::read: -> (k, g, g_lagrange, w, u) in the layout params_ipa_bytes takes; ValueError for a wrong length or an encoding that is not a point."""
+    from .transcript import decompress
+
+    data = bytes(data)
+    if len(data) < 4:
+        raise ValueError("unexpected end of input")
+    (k,) = struct.unpack("<I", data[:4])
+    if k > 28:
+        raise ValueError("params: k out of range")
+    n = 1 << k
+    if len(data) != 4 + 64 * n + 64:
+        raise ValueError("params: length does not match k")
+    pts = encode_points(curve, [decompress(curve, data[4 + 32 * i:36 + 32 * i]) for i in range(2 * n + 2)])
+    return k, pts[:n], pts[n:2 * n], pts[2 * n], pts[2 * n + 1]
 
 
 def _exact(fh, nbytes: int) -> bytes:

@@ -148,7 +148,7 @@ class ParamsKZG:
 
 class ParamsIPA(ParamsKZG):
     """dehalo_params over IPACommitmentScheme<C> (Pallas / Vesta): g, g_lagrange, w, u handed over as the caller's ParamsIPA holds them
-    (dehalo_params_ipa_create).  ProvingKey.keygen and Prover take it as they take ParamsKZG: Prover(params, pk).create_proof then writes a ProverIPA
+    (dehalo_params_ipa_create), built from g, w, u alone (from_g) or read from ParamsIPA::write's bytes (read).  ProvingKey.keygen and Prover take it as they take ParamsKZG: Prover(params, pk).create_proof then writes a ProverIPA
     proof (blinded commitments, committed instance columns, the multiopen and the opening argument).  `open` opens one polynomial."""
 
     @classmethod
@@ -164,10 +164,35 @@ class ParamsIPA(ParamsKZG):
         return cls(ctx, curve, h)
 
     @classmethod
-    def setup(cls, *a, **kw):
-        raise NotImplementedError("ParamsIPA::new is not provided: pass g, g_lagrange, w, u to ParamsIPA.create")
+    def from_g(cls, ctx: Context, curve: CurveSpec, k: int, g, w, u) -> "ParamsIPA":
+        """ParamsIPA from g alone, as upstream builds it: g_lagrange = g_to_lagrange(g), a group FFT on the device (dehalo_params_ipa_from_g)."""
+        g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+        w = np.ascontiguousarray(w, dtype=np.uint64).reshape(8)
+        u = np.ascontiguousarray(u, dtype=np.uint64).reshape(8)
+        if g.shape[0] != 1 << k:
+            raise ValueError("g must hold 2^k points")
+        h = C.c_void_p()
+        _check(ctx, load_library().dehalo_params_ipa_from_g(ctx.handle, curve.id, k, g.ctypes.data, w.ctypes.data, u.ctypes.data, C.byref(h)))
+        return cls(ctx, curve, h)
 
-    read = setup
+    @classmethod
+    def setup(cls, *a, **kw):
+        raise NotImplementedError("ParamsIPA::new (hash-to-curve generators) is not provided: pass g, w, u to ParamsIPA.from_g, or g, g_lagrange, w, u to ParamsIPA.create")
+
+    @classmethod
+    def read(cls, ctx: Context, curve: CurveSpec, data: bytes) -> "ParamsIPA":
+        """ParamsIPA::read: k | g | g_lagrange | w | u with 32-byte compressed points, decompressed on the device (dehalo_params_ipa_read)."""
+        h = C.c_void_p()
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        _check(ctx, load_library().dehalo_params_ipa_read(ctx.handle, curve.id, buf.ctypes.data if buf.size else None, buf.size, C.byref(h)))
+        return cls(ctx, curve, h)
+
+    def write(self) -> bytes:
+        """ParamsIPA::write (dehalo_params_ipa_write)."""
+        lib = load_library()
+        out = np.empty(lib.dehalo_params_ipa_size(self.handle), dtype=np.uint8)
+        _check(self.ctx, lib.dehalo_params_ipa_write(self.handle, out.ctypes.data, out.size))
+        return out.tobytes()
 
     def open(self, d_poly: int, blind: int, x3: int, transcript: Optional["Blake2bWrite"] = None, rng=None) -> "Blake2bWrite":
         """commitment::create_proof of the 2^k coefficients at d_poly (device, Montgomery) with blind `blind` at x3 (dehalo_ipa_open)."""

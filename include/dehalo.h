@@ -168,6 +168,14 @@ int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t*
 int dehalo_blind_commitments_device(dehalo_ctx* ctx, int curve, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, const uint64_t* d_w_affine_xy,
                                     void* stream);
 
+/* g_to_lagrange [UPSTREAM halo2_proofs/src/poly/commitment.rs, poly/ipa/commitment.rs: best_fft(&mut g, omega_inv, k); g[i] *= n_inv; batch_normalize]:
+ * out[i] = [n^-1] sum_j [omega^(-i j)] g[j] over n = 2^k points, omega the 2^k-th root of unity of the curve's scalar field -- the group FFT that takes a
+ * commitment key to its Lagrange basis.  Affine {x, y} (64 B, identity = (0, 0), standard Montgomery) in and out, device memory; the output is the
+ * canonical affine point, whatever the order of evaluation.  All three curves; 0 <= k <= 28 (k = 0: the output is the input).  d_out_affine_xy may be
+ * d_g_affine_xy itself (in place) or disjoint from it; any partial overlap is DEHALO_ERR_INVALID.  About k 2^(k-1) + 2^k variable-base scalar
+ * multiplications, k + 2 launches.  Asynchronous on the stream; workspace: 32 B x 2^(k-1) of twiddles, kept by the context. */
+int dehalo_g_to_lagrange_device(dehalo_ctx* ctx, int curve, const uint64_t* d_g_affine_xy, uint32_t k, uint64_t* d_out_affine_xy, void* stream);
+
 /* ---- NTT == halo2_proofs::arithmetic::best_fft(a, omega, log_n) ---------------------------
  * [halo2_proofs/src/arithmetic.rs].  In place, natural order in and out,
  * a'[i] = sum_j a[j] * omega^(i*j), no scaling.  a: 2^log_n x 4 u64.  omega must be a
@@ -436,12 +444,26 @@ int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s
  * as for KZG, so dehalo_keygen works on them: under these params the verifying key's fixed and permutation commitments are commit_lagrange with
  * Blind::default(), taken to be Blind(F::ONE) -- MSM + W (parity with upstream unpinned); under KZG params keygen is unchanged.
  * dehalo_params_commit_device is the bare MSM under either scheme.  g, u and w also stay on the device as plain points for the opening argument.
- * Not provided: ParamsIPA::new (hash-to-curve of "Halo2-Parameters"), ParamsIPA::{read, write} (dehalo_params_size is 0 and dehalo_params_write
- * DEHALO_ERR_UNSUPPORTED for these params) and g_to_lagrange (a group FFT): the caller passes params.g, params.g_lagrange, params.w and params.u.
+ * Not provided: ParamsIPA::new.  Its generators are hash-to-curve outputs ("Halo2-Parameters"), and the simplified SWU map of the Pasta curves needs the
+ * constants of their 3-isogenies, which this library has no checked source for and will not restate from memory: the caller passes params.g, params.w and
+ * params.u (dehalo_params_ipa_from_g) or a written ParamsIPA (dehalo_params_ipa_read).
  * Whole proofs: dehalo_prover_create / dehalo_create_proof with these params write a ProverIPA proof (below). */
 int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
                              dehalo_params** out);
-/* The commitment scheme of params: DEHALO_SCHEME_KZG (dehalo_params_create / _setup / _read) or DEHALO_SCHEME_IPA (dehalo_params_ipa_create); < 0 for null. */
+/* ParamsIPA from g alone, as upstream builds it: g_lagrange = g_to_lagrange(g) on the device (dehalo_g_to_lagrange_device), then exactly
+ * dehalo_params_ipa_create(g, g_lagrange, w, u).  Host pointers; the same range checks and return codes as dehalo_params_ipa_create. */
+int dehalo_params_ipa_from_g(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t w[8], const uint64_t u[8], dehalo_params** out);
+/* ParamsIPA::{write, read} [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs]: k: u32 LE | g (2^k x 32 B) | g_lagrange (2^k x 32 B) | w (32 B) | u (32 B), every
+ * point GroupEncoding::to_bytes -- x little-endian, bit 255 = y & 1, the identity all zeros: the encoding dehalo_transcript_write_point appends to a proof.
+ * size = 4 + 64 x 2^k + 64; for ParamsKZG size is 0 and write DEHALO_ERR_UNSUPPORTED.  These are entry points of their own, beside dehalo_params_size /
+ * dehalo_params_write, because those two are pinned for IPA params (0 and DEHALO_ERR_UNSUPPORTED: callers tell the schemes apart by them) and stay so.
+ * read decompresses the 2 x 2^k + 2 points on the device (y = sqrt(x^3 + b), sign from bit 255) and then does what dehalo_params_ipa_create does;
+ * DEHALO_ERR_INVALID, with nothing allocated left behind, for a length other than 4 + 64 x 2^k + 64 for the k in the first four bytes, an x coordinate
+ * not below the modulus, an x that is not on the curve, and the encoding "x = 0 with the sign bit set". */
+size_t dehalo_params_ipa_size(const dehalo_params* params);
+int dehalo_params_ipa_write(const dehalo_params* params, uint8_t* out, size_t cap);
+int dehalo_params_ipa_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out);
+/* The commitment scheme of params: DEHALO_SCHEME_KZG (dehalo_params_create / _setup / _read) or DEHALO_SCHEME_IPA (dehalo_params_ipa_create / _from_g / _read); < 0 for null. */
 typedef enum { DEHALO_SCHEME_KZG = 0, DEHALO_SCHEME_IPA = 1 } dehalo_scheme;
 int dehalo_params_scheme(const dehalo_params* params);
 int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out);
