@@ -47,7 +47,8 @@ int compile_graph(dehalo_ctx* ctx, dehalo_graph* g, const int32_t* rotations, ui
         {
             std::vector<DevCalc> tc;
             std::vector<DevSrc> tp;
-            dehalo_graph probe = *g;
+            dehalo_graph probe{};      // (the validation reads the number of constants only)
+            probe.num_constants = g->num_constants;
             TRY(compile_graph(ctx, &probe, rotations, num_rotations, calcs, num_calcs, parts, num_parts, num_intermediates, tc, tp, false));
         }
         std::vector<uint32_t> defs(num_intermediates, 0);
@@ -169,14 +170,6 @@ int compile_graph(dehalo_ctx* ctx, dehalo_graph* g, const int32_t* rotations, ui
     return 0;
 }
 
-// a compiled graph and its device arrays, freed together unless handed to the caller
-struct GraphFree {
-    void operator()(dehalo_graph* g) const {
-        (void)hipFree(g->d_calcs); (void)hipFree(g->d_parts); (void)hipFree(g->d_constants);
-        delete g;
-    }
-};
-
 // The host-buffer forms: under the context's lock, each input is uploaded into its workspace buffer (a null host pointer only sizes the buffer),
 // dev() runs the device form on the workspace copies, and the output is downloaded from out_buf, synchronously.  Every caller names the buffers it
 // has always used: the device form it calls may use some of the others itself.
@@ -188,10 +181,10 @@ int with_host_io(dehalo_ctx* ctx, std::initializer_list<HostIn> ins, DevBuf& out
     for (const HostIn& in : ins) TRY(dh_ensure(ctx, in.buf, std::max<size_t>(32, in.bytes)));
     TRY(dh_ensure(ctx, out_buf, std::max<size_t>(32, out_bytes)));
     for (const HostIn& in : ins)
-        if (in.p) TRY(dh_h2d(ctx, in.buf.p, in.p, in.bytes, ctx->stream));
+        if (in.p) TRY(dh_h2d(ctx, in.buf.p, in.p, in.bytes, ctx->stream.get()));
     TRY(dev());
-    TRY(dh_d2h(ctx, out, out_buf.p, out_bytes, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    TRY(dh_d2h(ctx, out, out_buf.p, out_bytes, ctx->stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
     return 0;
 }
 
@@ -224,17 +217,9 @@ int ntt_host_io(dehalo_ctx* ctx, const uint64_t* in, size_t in_elems, uint64_t* 
     });
 }
 
-// a bases object and its table, freed together unless handed to the caller
-struct BasesFree {
-    void operator()(dehalo_bases* b) const {
-        if (b->table) (void)hipFree(b->table);
-        delete b;
-    }
-};
-
 int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t n, size_t stride_bytes, int window_bits, int precompute,
-                  dehalo_bases** out, bool on_device = false) {
-    if (!affine_xy || !out || n == 0 || stride_bytes < 64 || n >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_register: bad argument");
+                  BasesPtr& out, bool on_device) {
+    if (!affine_xy || n == 0 || stride_bytes < 64 || n >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_register: bad argument");
     if (window_bits != 0 && (window_bits < (int)MSM_WINDOW_MIN || window_bits > (int)msm_window_max(precompute != 0)))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "window_bits must be 0 or in [4, 16] (17 with precomputed rows)");
     const CurveOps* cv = curve_ops(curve);
@@ -249,11 +234,10 @@ int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t 
     if (precompute && !msm_table_fits(n, W)) return dh_fail(ctx, DEHALO_ERR_INVALID, "precomputed table too large");      // 30-bit table indices in the sorted list (msm.cuh)
     // stage the caller's points (standard Montgomery form) on the device, then build the table
     if (!on_device) TRY(dh_ensure(ctx, ctx->ws_tmp_bases, n * sizeof(affine_t)));
-    std::unique_ptr<dehalo_bases, BasesFree> b(new dehalo_bases());
-    b->curve = curve; b->n = n; b->c = c; b->W = W; b->precomp = precompute ? 1 : 0; b->table = nullptr;
+    BasesPtr b(new dehalo_bases(), BasesFree{ctx});
+    b->curve = curve; b->n = n; b->c = c; b->W = W; b->precomp = precompute ? 1 : 0;
     size_t rows = precompute ? W : 1;
-    hipError_t e = hipMalloc((void**)&b->table, rows * n * sizeof(affine_t));
-    if (e != hipSuccess) return dh_fail(ctx, DEHALO_ERR_OOM, std::string("bases table: ") + hipGetErrorString(e));
+    TRY(b->table.alloc(ctx, rows * n, false));
     // 64 MiB of SRS points at 2^20: DMA straight from the caller's pages -- only when these bytes are what is copied (host memory, contiguous points)
     HostPin pin_bases(on_device || stride_bytes != 64 ? nullptr : affine_xy, n * stride_bytes);
     // (contiguous points: a plain copy -- the 2-D path took 3 of the 4.1 ms of registering 2^20 points)
@@ -262,12 +246,27 @@ int register_impl(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t 
         packed.resize(n * 8);
         for (size_t i = 0; i < n; i++) memcpy(&packed[i * 8], (const char*)affine_xy + i * stride_bytes, 64);
     }
-    if (!on_device) TRY(dh_h2d(ctx, ctx->ws_tmp_bases.p, stride_bytes == 64 ? (const void*)affine_xy : (const void*)packed.data(), n * 64, ctx->stream));
-    TRY(cv->build_table(ctx, b.get(), on_device ? (const affine_t*)affine_xy : (const affine_t*)ctx->ws_tmp_bases.p, ctx->stream));
-    e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return dh_fail(ctx, DEHALO_ERR_HIP, std::string("bases upload: ") + hipGetErrorString(e));
-    *out = b.release();
+    if (!on_device) TRY(dh_h2d(ctx, ctx->ws_tmp_bases.p, stride_bytes == 64 ? (const void*)affine_xy : (const void*)packed.data(), n * 64, ctx->stream.get()));
+    TRY(cv->build_table(ctx, b.get(), on_device ? (const affine_t*)affine_xy : (const affine_t*)ctx->ws_tmp_bases.p, ctx->stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
+    out = std::move(b);
     return 0;
+}
+
+// dehalo_bases_register / dehalo_bases_register_device: register_impl under the guard, the context's lock and its device; the handle crosses the ABI on success only
+int register_entry(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t n, size_t stride_bytes, int window_bits, int precompute, dehalo_bases** out,
+                   bool on_device) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!curve_ops(curve)) return unknown_curve(ctx);
+    if (!out) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_register: bad argument");
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        BasesPtr b;
+        TRY(register_impl(ctx, curve, affine_xy, n, stride_bytes, window_bits, precompute, b, on_device));
+        *out = b.release();
+        return 0;
+    });
 }
 
 }  // namespace
@@ -283,12 +282,12 @@ const GfftOps* gfft_ops(int curve) {
     return curve >= 0 && curve < 3 ? ops[curve] : nullptr;
 }
 
-int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, dehalo_bases** out) {
+int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, BasesPtr& out) {
     if (!curve_ops(curve) || cap == 0 || cap >= (1ull << 30)) return dh_fail(ctx, DEHALO_ERR_INVALID, "bases_plain_alloc: bad argument");
-    std::unique_ptr<dehalo_bases, BasesFree> b(new dehalo_bases());
-    b->curve = curve; b->n = 0; b->c = 4; b->W = 0; b->precomp = 0; b->table = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&b->table, cap * sizeof(affine_t)));
-    *out = b.release();
+    BasesPtr b(new dehalo_bases(), BasesFree{ctx});
+    b->curve = curve; b->n = 0; b->c = 4; b->W = 0; b->precomp = 0;
+    TRY(b->table.alloc(ctx, cap, false));
+    out = std::move(b);
     return 0;
 }
 
@@ -335,6 +334,7 @@ int dehalo_ctx_create_with_priority(int device, int priority, dehalo_ctx** out) 
             static const int cu_parts = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_CU_PARTITION"); return e ? atoi(e) : 0; }();
             static std::atomic<int> cu_next{0};
             hipError_t e;
+            hipStream_t st = nullptr;
             if (cu_parts > 1 && cu_parts <= 16) {
                 const int part = cu_next.fetch_add(1) % cu_parts, ncu = ctx->num_cus, per = ncu / cu_parts;
                 std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
@@ -343,12 +343,13 @@ int dehalo_ctx_create_with_priority(int device, int priority, dehalo_ctx** out) 
                     const bool mine = interleave ? (cu % cu_parts) == part : (cu / per) == part;
                     if (mine) mask[cu / 32] |= 1u << (cu % 32);
                 }
-                e = hipExtStreamCreateWithCUMask(&ctx->stream, (uint32_t)mask.size(), mask.data());
+                e = hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data());
                 if (e == hipSuccess) ctx->num_cus = per;
             } else
-            e = priority == 0 ? hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)
-                              : hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio);
+            e = priority == 0 ? hipStreamCreateWithFlags(&st, hipStreamNonBlocking)
+                              : hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio);
             if (e != hipSuccess) return DEHALO_ERR_HIP;
+            ctx->stream.reset(st);
         }
         if (const char* e = DH_EXPERIMENT_ENV("DEHALO_MSM_ACC_MIN_LAYERS")) ctx->msm_acc_min_layers = std::max(1, std::min(4, atoi(e)));
         if (const char* e = DH_EXPERIMENT_ENV("DEHALO_HOST_SPIN_US")) ctx->host_wait_spin_us = std::max(0, std::min(1000000, atoi(e)));
@@ -363,20 +364,7 @@ void dehalo_ctx_destroy(dehalo_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    DevBuf* bufs[] = {&ctx->ws_scalars, &ctx->ws_out, &ctx->ws_count, &ctx->ws_counters, &ctx->ws_off, &ctx->ws_records, &ctx->ws_merge_lists, &ctx->ws_merge_parts,
-                      &ctx->ws_bhist, &ctx->ws_pcount, &ctx->ws_pairs, &ctx->ws_bsum, &ctx->ws_idx, &ctx->ws_partial0, &ctx->ws_buckets, &ctx->ws_contrib, &ctx->ws_tree, &ctx->ws_bred_cnt,
-                      &ctx->ws_gsums, &ctx->ws_ntt_scratch, &ctx->ws_ntt_io, &ctx->ws_ntt_io2, &ctx->ws_fop[0], &ctx->ws_fop[1], &ctx->ws_fop[2],
-                      &ctx->ws_tmp_bases, &ctx->ws_poly[0], &ctx->ws_poly[1], &ctx->ws_poly[2], &ctx->ws_poly[3], &ctx->ws_poly[4], &ctx->ws_poly_io[0], &ctx->ws_poly_io[1],
-                      &ctx->ws_poly_io[2], &ctx->ws_evh[0], &ctx->ws_evh[1], &ctx->ws_evh[2], &ctx->ws_evh[3], &ctx->ws_lookup, &ctx->ws_gfft};
-    for (DevBuf* b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (auto& t : ctx->twiddles) (void)hipFree(t.tw);
-    for (auto& r : ctx->regions) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (int i = 0; i < 2; i++) {
-        if (ctx->stage.buf[i]) (void)hipHostFree(ctx->stage.buf[i]);
-        if (ctx->stage.ev[i]) (void)hipEventDestroy(ctx->stage.ev[i]);
-    }
-    (void)hipStreamDestroy(ctx->stream);
+    // (the context's members free what they hold, in reverse order of declaration: the stream goes last)
     delete ctx;
 }
 
@@ -431,12 +419,12 @@ int dehalo_ctx_set_tuning(dehalo_ctx* ctx, const char* key, int value) {
     });
 }
 
-void* dehalo_ctx_stream(dehalo_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+void* dehalo_ctx_stream(dehalo_ctx* ctx) { return ctx ? (void*)ctx->stream.get() : nullptr; }
 
 int dehalo_ctx_synchronize(dehalo_ctx* ctx) {
     if (!ctx) return DEHALO_ERR_INVALID;
     return dh_guard(ctx, [&]() -> int {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
         return 0;
     });
 }
@@ -446,8 +434,8 @@ int dehalo_download(dehalo_ctx* ctx, const void* d_src, size_t bytes, void* host
     return dh_guard(ctx, [&]() -> int {
         if ((!d_src || !host_dst) && bytes) return dh_fail(ctx, DEHALO_ERR_INVALID, "download: null argument");
         (void)hipSetDevice(ctx->device);
-        if (bytes) TRY(dh_d2h(ctx, host_dst, d_src, bytes, ctx->stream));
-        HIP_TRY(ctx, dh_stream_wait(ctx, ctx->stream));
+        if (bytes) TRY(dh_d2h(ctx, host_dst, d_src, bytes, ctx->stream.get()));
+        HIP_TRY(ctx, dh_stream_wait(ctx, ctx->stream.get()));
         return 0;
     });
 }
@@ -459,8 +447,8 @@ int dehalo_upload(dehalo_ctx* ctx, const void* host_src, size_t bytes, void* d_d
         (void)hipSetDevice(ctx->device);
         {
             HostPin pin(host_src, bytes);      // 4 MiB and more: one DMA from the caller's pages, released below, after the stream has drained
-            TRY(dh_h2d(ctx, d_dst, host_src, bytes, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            TRY(dh_h2d(ctx, d_dst, host_src, bytes, ctx->stream.get()));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
         }
         return 0;
     });
@@ -468,23 +456,11 @@ int dehalo_upload(dehalo_ctx* ctx, const void* host_src, size_t bytes, void* d_d
 
 int dehalo_bases_register(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t n, size_t stride_bytes, int window_bits, int precompute,
                           dehalo_bases** out) {
-    if (!ctx) return DEHALO_ERR_INVALID;
-    if (!curve_ops(curve)) return unknown_curve(ctx);
-    return dh_guard(ctx, [&]() -> int {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        return register_impl(ctx, curve, affine_xy, n, stride_bytes, window_bits, precompute, out);
-    });
+    return register_entry(ctx, curve, affine_xy, n, stride_bytes, window_bits, precompute, out, false);
 }
 
 int dehalo_bases_register_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t n, int window_bits, int precompute, dehalo_bases** out) {
-    if (!ctx) return DEHALO_ERR_INVALID;
-    if (!curve_ops(curve)) return unknown_curve(ctx);
-    return dh_guard(ctx, [&]() -> int {
-        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        (void)hipSetDevice(ctx->device);
-        return register_impl(ctx, curve, d_affine_xy, n, 64, window_bits, precompute, out, true);
-    });
+    return register_entry(ctx, curve, d_affine_xy, n, 64, window_bits, precompute, out, true);
 }
 
 int dehalo_bases_release(dehalo_ctx* ctx, dehalo_bases* bases) {
@@ -493,7 +469,7 @@ int dehalo_bases_release(dehalo_ctx* ctx, dehalo_bases* bases) {
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();
-        BasesFree()(bases);
+        delete bases;
         return 0;
     });
 }
@@ -554,12 +530,12 @@ int dehalo_msm_batch(dehalo_ctx* ctx, const dehalo_bases* bases, const uint64_t*
         TRY(dh_ensure(ctx, ctx->ws_out, std::max<size_t>(96, batch * 96)));
         for (size_t b = 0; b < batch && len; b++) {
             HostPin pin(scalars[b], len * 32);
-            TRY(dh_h2d(ctx, (char*)ctx->ws_scalars.p + b * len * 32, scalars[b], len * 32, ctx->stream));
-            if (pin.p) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // the pin ends with this scope
+            TRY(dh_h2d(ctx, (char*)ctx->ws_scalars.p + b * len * 32, scalars[b], len * 32, ctx->stream.get()));
+            if (pin.p) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));      // the pin ends with this scope
         }
         TRY(dehalo_msm_device(ctx, bases, (const uint64_t*)ctx->ws_scalars.p, len, batch, (uint64_t*)ctx->ws_out.p, nullptr));
-        TRY(dh_d2h(ctx, out_jacobian, ctx->ws_out.p, batch * 96, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        TRY(dh_d2h(ctx, out_jacobian, ctx->ws_out.p, batch * 96, ctx->stream.get()));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
         return 0;
     });
 }
@@ -576,11 +552,9 @@ int dehalo_best_multiexp(dehalo_ctx* ctx, int curve, const uint64_t* scalars, co
     if (len == 0) { memset(out_jacobian, 0, 96); return 0; }
     return dh_guard(ctx, [&]() -> int {
         std::lock_guard<std::recursive_mutex> hold(ctx->mu);
-        dehalo_bases* b = nullptr;
-        TRY(dehalo_bases_register(ctx, curve, affine_xy, len, 64, 0, 0, &b));
-        int rc = dehalo_msm(ctx, b, scalars, len, out_jacobian);
-        dehalo_bases_release(ctx, b);
-        return rc;
+        BasesPtr b;
+        TRY(dehalo_bases_register(ctx, curve, affine_xy, len, 64, 0, 0, adopt(ctx, b)));
+        return dehalo_msm(ctx, b.get(), scalars, len, out_jacobian);
     });
 }
 
@@ -667,7 +641,7 @@ int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_
     return dh_guard(ctx, [&] {
         return with_host_io(ctx, {{ctx->ws_fop[0], jacobian, count * 96}}, ctx->ws_fop[1], affine_xy, count * 64, [&] {
             const CurveOps* cv = curve_ops(curve);
-            return cv ? cv->to_affine(ctx, (const jacobian_t*)ctx->ws_fop[0].p, (affine_t*)ctx->ws_fop[1].p, (uint32_t)count, ctx->stream) : unknown_curve(ctx);
+            return cv ? cv->to_affine(ctx, (const jacobian_t*)ctx->ws_fop[0].p, (affine_t*)ctx->ws_fop[1].p, (uint32_t)count, ctx->stream.get()) : unknown_curve(ctx);
         });
     });
 }
@@ -784,7 +758,7 @@ int dehalo_field_op(dehalo_ctx* ctx, int field, int op, const uint64_t* a, const
         DevBuf* w = ctx->ws_fop;
         return with_host_io(ctx, {{w[0], a, n * 32}, {w[1], b, n * 32}}, w[2], out, n * 32, [&] {
             const FieldOps* f = field_ops(field);
-            return f ? f->field_op(ctx, op, (const fe*)w[0].p, b ? (const fe*)w[1].p : nullptr, (fe*)w[2].p, n, ctx->stream) : unknown_field(ctx);
+            return f ? f->field_op(ctx, op, (const fe*)w[0].p, b ? (const fe*)w[1].p : nullptr, (fe*)w[2].p, n, ctx->stream.get()) : unknown_field(ctx);
         });
     });
 }
@@ -1013,14 +987,14 @@ int dehalo_permute_expression_pair(dehalo_ctx* ctx, int field, const uint64_t* i
         (void)hipSetDevice(ctx->device);
         TRY(dh_ensure(ctx, ctx->ws_poly_io[0], usable_rows * 64));
         TRY(dh_ensure(ctx, ctx->ws_poly_io[1], usable_rows * 64));
-        TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, input, usable_rows * 32, ctx->stream));
-        TRY(dh_h2d(ctx, (char*)ctx->ws_poly_io[0].p + usable_rows * 32, table, usable_rows * 32, ctx->stream));
+        TRY(dh_h2d(ctx, ctx->ws_poly_io[0].p, input, usable_rows * 32, ctx->stream.get()));
+        TRY(dh_h2d(ctx, (char*)ctx->ws_poly_io[0].p + usable_rows * 32, table, usable_rows * 32, ctx->stream.get()));
         uint64_t* d_in = (uint64_t*)ctx->ws_poly_io[0].p;
         uint64_t* d_out = (uint64_t*)ctx->ws_poly_io[1].p;
         TRY(dehalo_permute_expression_pair_device(ctx, field, d_in, d_in + usable_rows * 4, usable_rows, d_out, d_out + usable_rows * 4, nullptr));
-        TRY(dh_d2h(ctx, permuted_input, d_out, usable_rows * 32, ctx->stream));
-        TRY(dh_d2h(ctx, permuted_table, d_out + usable_rows * 4, usable_rows * 32, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        TRY(dh_d2h(ctx, permuted_input, d_out, usable_rows * 32, ctx->stream.get()));
+        TRY(dh_d2h(ctx, permuted_table, d_out + usable_rows * 4, usable_rows * 32, ctx->stream.get()));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
         return 0;
     });
 }
@@ -1038,19 +1012,17 @@ int dehalo_graph_create(dehalo_ctx* ctx, int field, const uint64_t* constants, u
     return dh_guard(ctx, [&]() -> int {
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
-        std::unique_ptr<dehalo_graph, GraphFree> g(new dehalo_graph());
-        memset(g.get(), 0, sizeof(*g));
+        GraphPtr g(new dehalo_graph(), GraphFree{ctx});
         g->field = field; g->num_calcs = num_calcs; g->num_parts = num_horner_parts; g->num_constants = num_constants;
         std::vector<DevCalc> dc;
         std::vector<DevSrc> dp;
         TRY(compile_graph(ctx, g.get(), rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, dc, dp));
-        hipError_t e = hipMalloc((void**)&g->d_calcs, std::max<size_t>(1, dc.size()) * sizeof(DevCalc));
-        if (e == hipSuccess) e = hipMalloc((void**)&g->d_parts, dp.size() * sizeof(DevSrc));
-        if (e == hipSuccess) e = hipMalloc((void**)&g->d_constants, std::max<size_t>(1, num_constants) * sizeof(fe));
-        if (e == hipSuccess && !dc.empty()) e = hipMemcpy(g->d_calcs, dc.data(), dc.size() * sizeof(DevCalc), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(g->d_parts, dp.data(), dp.size() * sizeof(DevSrc), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return dh_fail(ctx, e == hipErrorOutOfMemory ? DEHALO_ERR_OOM : DEHALO_ERR_HIP, std::string("graph_create: ") + hipGetErrorString(e));
-        TRY(f->graph_upload(ctx, g.get(), constants, ctx->stream));
+        TRY(g->d_calcs.alloc(ctx, std::max<size_t>(1, dc.size()), false));
+        TRY(g->d_parts.alloc(ctx, dp.size(), false));
+        TRY(g->d_constants.alloc(ctx, std::max<size_t>(1, num_constants), false));
+        if (!dc.empty()) HIP_TRY(ctx, hipMemcpy(g->d_calcs.p, dc.data(), dc.size() * sizeof(DevCalc), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(g->d_parts.p, dp.data(), dp.size() * sizeof(DevSrc), hipMemcpyHostToDevice));
+        TRY(f->graph_upload(ctx, g.get(), constants, ctx->stream.get()));
         *out = g.release();
         return 0;
     });
@@ -1062,7 +1034,7 @@ int dehalo_graph_release(dehalo_ctx* ctx, dehalo_graph* g) {
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
         (void)hipDeviceSynchronize();
-        GraphFree()(g);
+        delete g;
         return 0;
     });
 }
@@ -1163,13 +1135,11 @@ int dehalo_timing_enable(dehalo_ctx* ctx, int on) {
 static int timing_collect(dehalo_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     for (auto& r : ctx->regions) {
-        HIP_TRY(ctx, hipEventSynchronize(r.b));
+        HIP_TRY(ctx, hipEventSynchronize(r.b.get()));
         float ms = 0;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, r.a, r.b));
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, r.a.get(), r.b.get()));
         ctx->timing_ms[r.kernel_id] += ms;
         ctx->timing_cnt[r.kernel_id] += 1;
-        (void)hipEventDestroy(r.a);
-        (void)hipEventDestroy(r.b);
     }
     ctx->regions.clear();
     return 0;
@@ -1203,7 +1173,7 @@ int dehalo_msm_last_shape(dehalo_ctx* ctx, uint32_t out[6]) {
         (void)hipSetDevice(ctx->device);
         memset(out, 0, 6 * sizeof(uint32_t));
         if (!ctx->ws_counters.p) return 0;
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
         uint32_t raw[10];      // eight merge-class counters (k_msm_merge_classify2: 2 | 3-4 | 5-8 | 9-64 | 65-512 records, parts of heavy buckets, heavy buckets, unused), L0, M
         HIP_TRY(ctx, hipMemcpy(raw, ctx->ws_counters.p, sizeof(raw), hipMemcpyDeviceToHost));
         out[0] = raw[0] + raw[1] + raw[2]; out[1] = raw[3]; out[2] = raw[4]; out[3] = raw[6]; out[4] = raw[8]; out[5] = raw[9];      // light (2-8 records) | 9-64 | 65-512 | > 512

@@ -417,15 +417,11 @@ template <class F>
 int graph_upload_t(dehalo_ctx* ctx, dehalo_graph* g, const uint64_t* constants, hipStream_t s) {
     // constants: standard form on the host -> internal packed on the device, once
     if (g->num_constants) {
-        fe* tmp = nullptr;
-        HIP_TRY(ctx, hipMalloc((void**)&tmp, (size_t)g->num_constants * sizeof(fe)));
-        hipError_t e = dh_h2d(ctx, tmp, constants, (size_t)g->num_constants * sizeof(fe), s) == 0 ? hipSuccess : hipErrorUnknown;
-        if (e == hipSuccess) {
-            k_evh_scalars<F><<<(g->num_constants + 127) / 128, 128, 0, s>>>(tmp, g->d_constants, g->num_constants);
-            e = hipStreamSynchronize(s);
-        }
-        (void)hipFree(tmp);
-        HIP_TRY(ctx, e);
+        DevMem tmp;
+        TRY(tmp.alloc(ctx, g->num_constants, false));
+        TRY(dh_h2d(ctx, tmp.p, constants, (size_t)g->num_constants * sizeof(fe), s));
+        k_evh_scalars<F><<<(g->num_constants + 127) / 128, 128, 0, s>>>(tmp.p, g->d_constants.p, g->num_constants);
+        HIP_TRY(ctx, hipStreamSynchronize(s));
     }
     return 0;
 }
@@ -472,7 +468,7 @@ int graph_evaluate_t(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_i
         EvhStage st{};
         for (int i = 0; i < 4; i++) st.v[i] = four[i] ? fe_from_u64(four[i]) : fe{};
         for (u32 i = 0; i < in->num_challenges; i++) st.v[4 + i] = fe_from_u64(in->challenges + 4 * (size_t)i);
-        st.constants = g->d_constants; st.nconst = g->num_constants; st.nchal = in->num_challenges;
+        st.constants = g->d_constants.p; st.nconst = g->num_constants; st.nchal = in->num_challenges;
         st.ncols = ncol;
         for (u32 i = 0; i < ncol; i++) st.cols[i] = cols[i];
         const u32 work = std::max<u32>(nsc, ncol);
@@ -482,14 +478,14 @@ int graph_evaluate_t(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_i
         for (int i = 0; i < 4; i++) head[i] = four[i] ? fe_from_u64(four[i]) : fe{};
         for (u32 i = 0; i < in->num_challenges; i++) chal[i] = fe_from_u64(in->challenges + 4 * (size_t)i);
         TRY(evh_stage_scalars<F>(ctx, head, table, s));
-        if (g->num_constants) HIP_TRY(ctx, hipMemcpyAsync(table + 4, g->d_constants, (size_t)g->num_constants * sizeof(fe), hipMemcpyDeviceToDevice, s));
+        if (g->num_constants) HIP_TRY(ctx, hipMemcpyAsync(table + 4, g->d_constants.p, (size_t)g->num_constants * sizeof(fe), hipMemcpyDeviceToDevice, s));
         TRY(evh_stage_scalars<F>(ctx, chal, table + 4 + g->num_constants, s));
         TRY(evh_stage_ptrs(ctx, cols, (const void**)ctx->ws_evh[2].p, s));
     }
     EvhArgs A{};
     A.columns = (const fe* const*)ctx->ws_evh[2].p;
     if (g->hbm_slots) TRY(dh_ensure(ctx, ctx->ws_evh[3], (size_t)g->hbm_slots * rows * sizeof(fe)));
-    A.calcs = g->d_calcs; A.parts = g->d_parts; A.scalars = table;
+    A.calcs = g->d_calcs.p; A.parts = g->d_parts.p; A.scalars = table;
     A.num_calcs = g->num_calcs; A.fixed_base = 0; A.advice_base = in->num_fixed; A.instance_base = in->num_fixed + in->num_advice;
     A.rows_mask = (u32)(rows - 1); A.rot_scale = rot_scale;
     A.previous = d_previous; A.out = d_out; A.spill = (fe*)ctx->ws_evh[3].p; A.rows = rows; A.result = g->result;
@@ -545,10 +541,10 @@ int graph_evaluate_batch_t(dehalo_ctx* ctx, const dehalo_graph* const* graphs, u
         for (u32 i = 0; i < in->num_instance; i++) st.cols[in->num_fixed + in->num_advice + i] = in->instance[i];
         for (u32 j = 0; j < cnt; j++) {
             const dehalo_graph* g = graphs[first + j];
-            st.constants[j] = g->d_constants; st.nconst[j] = g->num_constants;
+            st.constants[j] = g->d_constants.p; st.nconst[j] = g->num_constants;
             EvhArgs& A = st.args[j];
             A.columns = (const fe* const*)ptrs;
-            A.calcs = g->d_calcs; A.parts = g->d_parts; A.scalars = table + (size_t)j * tstride;
+            A.calcs = g->d_calcs.p; A.parts = g->d_parts.p; A.scalars = table + (size_t)j * tstride;
             A.num_calcs = g->num_calcs; A.fixed_base = 0; A.advice_base = in->num_fixed; A.instance_base = in->num_fixed + in->num_advice;
             A.rows_mask = (u32)(rows - 1); A.rot_scale = rot_scale;
             A.previous = nullptr; A.out = d_outs[first + j]; A.spill = nullptr; A.rows = rows; A.result = g->result;

@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "fp.cuh"
+#include "owners.hpp"
 
 #define EVH_THREADS 128
 #define EVH_LDS_BYTES (60 * 1024)
@@ -29,9 +30,9 @@ struct dehalo_graph {
     uint32_t num_calcs, num_parts, num_constants, lds_slots, hbm_slots;
     uint32_t max_fixed, max_advice, max_instance, max_challenge;   // highest index referenced + 1
     bool uses_previous;
-    DevCalc* d_calcs;
-    DevSrc* d_parts;
-    fe* d_constants;        // internal packed form
+    DevArray<DevCalc> d_calcs;
+    DevArray<DevSrc> d_parts;
+    DevArray<fe> d_constants;        // internal packed form
     DevSrc result;          // where the last calculation's value lives
 };
 

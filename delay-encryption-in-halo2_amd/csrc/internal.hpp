@@ -17,59 +17,9 @@
 #include "ec.cuh"
 #include "experiment_env.hpp"
 #include "guard.hpp"
+#include "owners.hpp"
 
-// Caller buffers of the host entry points are ordinary pageable memory (a Rust Vec<F>): large ones are pinned for the duration of the
-// call so that the copy engine reads / writes them directly instead of going through the runtime's bounce buffers (measured on
-// MI355X, profiles/r02_host_path_measurements.txt: dehalo_ntt at 2^20, 32 MiB each way, 5.73 -> 1.35 ms), and so that the lifetime of the device's mapping of
-// caller memory is this object's and nothing else's (the pin ends only after the stream that copies has been synchronised).  Registration failing (already
-// pinned, exotic mapping) just leaves the pageable path.
-// Several threads may hand over the SAME host buffer at once (batch proving: one witness array, four provers): the first registers it, the others count
-// themselves in, and the pages are released by whoever leaves last -- a copy that found the buffer page-locked by another thread's registration must not
-// lose that registration in flight.  A range that only partly overlaps a registered one registers (or falls back to the pageable path) independently.
-struct HostPinRegistry {
-    struct Entry { uintptr_t a, b; int refs; };
-    std::mutex mu;
-    std::vector<Entry> entries;
-};
-inline HostPinRegistry& host_pin_registry() { static HostPinRegistry r; return r; }
-
-struct HostPin {
-    void* p = nullptr;          // the caller's pointer when its pages are page-locked through this object (by its own registration or one it shares)
-    uintptr_t key = 0;          // start of the registration it holds a reference to
-    HostPin(const void* ptr, size_t bytes) {
-        if (!ptr || bytes < HOST_PIN_MIN_BYTES) return;
-        HostPinRegistry& reg = host_pin_registry();
-        std::lock_guard<std::mutex> lk(reg.mu);
-        const uintptr_t a = (uintptr_t)ptr, b = a + bytes;
-        for (auto& e : reg.entries)
-            if (e.a <= a && b <= e.b) { e.refs++; key = e.a; p = const_cast<void*>(ptr); return; }
-        if (hipHostRegister(const_cast<void*>(ptr), bytes, hipHostRegisterDefault) == hipSuccess) {
-            reg.entries.push_back({a, b, 1});
-            key = a; p = const_cast<void*>(ptr);
-        } else (void)hipGetLastError();
-    }
-    HostPin(const HostPin&) = delete;
-    HostPin& operator=(const HostPin&) = delete;
-    ~HostPin() {
-        if (!p) return;
-        HostPinRegistry& reg = host_pin_registry();
-        std::lock_guard<std::mutex> lk(reg.mu);
-        for (size_t i = 0; i < reg.entries.size(); i++)
-            if (reg.entries[i].a == key) {
-                if (--reg.entries[i].refs == 0) {
-                    (void)hipHostUnregister((void*)key);
-                    reg.entries.erase(reg.entries.begin() + i);
-                }
-                return;
-            }
-    }
-    static constexpr size_t HOST_PIN_MIN_BYTES = 4u << 20;
-};
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
+using DevMem = DevArray<fe>;
 
 // Two library-owned page-locked chunks per context: every byte that travels between CALLER memory and the device either goes through them (a host memcpy
 // on one side, a DMA on the other) or moves by DMA from / to pages that are page-locked for the duration of the call (HostPin, or locked by the caller).
@@ -80,8 +30,8 @@ struct HostStage {
     static constexpr size_t CHUNK = 4u << 20;
     static constexpr size_t DIRECT_MAX = 64u << 10;      // below this the runtime copies through its own staging buffer (a host memcpy): nothing is pinned
     std::mutex mu;
-    void* buf[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Pinned<void> buf[2];
+    Event ev[2];
     bool busy[2] = {false, false};
 };
 
@@ -91,18 +41,18 @@ struct TwiddleEntry {
     int form;  // 0: standard Montgomery (R = 2^256)
     uint64_t omega[4];
     uint64_t len;   // powers held: N (full table) or N / 2
-    fe* tw;
+    DevMem tw;
 };
 
 struct TimedRegion {
     int kernel_id;
-    hipEvent_t a, b;
+    Event a, b;
 };
 
 struct dehalo_ctx {
     int device = 0;
     int num_cus = 256;
-    hipStream_t stream = nullptr;
+    Stream stream;             // declared in front of everything that was used on it: members go in reverse order, so the stream is destroyed last
     std::string err;           // guarded by err_mu (written on error paths of any thread, with or without mu held)
     std::mutex err_mu;
     std::recursive_mutex mu;   // recursive: host-buffer entry points hold it across their device-form calls
@@ -138,7 +88,7 @@ struct dehalo_bases {
     size_t n;
     uint32_t c, W;
     int precomp;
-    affine_t* table;  // n * (precomp ? W : 1) affine points in HBM, internal (R' = 2^261) canonical form
+    DevArray<affine_t> table;  // n * (precomp ? W : 1) affine points in HBM, internal (R' = 2^261) canonical form
 };
 
 // never throws, so that argument checks may run in front of an entry point's guard: a message that cannot be stored is dropped
@@ -157,7 +107,8 @@ int dh_guard(dehalo_ctx* ctx, Body&& body) noexcept {
     return dh_guard_noting([ctx](const char* msg) { dh_fail(ctx, DEHALO_ERR_INVALID, msg); }, body);
 }
 
-inline hipStream_t pick_stream(dehalo_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+inline hipStream_t pick_stream(dehalo_ctx* ctx, void* stream) { return stream ? (hipStream_t)stream : ctx->stream.get(); }
+inline hipStream_t dh_ctx_stream(dehalo_ctx* ctx) { return ctx->stream.get(); }
 
 // a device-form entry point: guarded, under the context's lock, on its device, body(stream) on the caller's stream or the context's
 template <class Body>
@@ -169,21 +120,6 @@ int dh_device(dehalo_ctx* ctx, void* stream, Body&& body) noexcept {
         return body(pick_stream(ctx, stream));
     });
 }
-
-#define HIP_TRY(ctx, expr)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            int code_ = (e_ == hipErrorOutOfMemory) ? DEHALO_ERR_OOM : DEHALO_ERR_HIP;        \
-            return dh_fail(ctx, code_, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-        }                                                                                    \
-    } while (0)
-
-#define TRY(expr)                 \
-    do {                          \
-        int rc_ = (expr);         \
-        if (rc_ != 0) return rc_; \
-    } while (0)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize of a kernel on the context's device: set once per (device, kernel) and only ever raised --
 // the call costs microseconds, and every MSM / NTT / graph launch used to make it
@@ -198,20 +134,7 @@ inline hipError_t dh_func_lds(dehalo_ctx* ctx, const void* fn, int bytes) {
     return e;
 }
 
-inline int dh_ensure(dehalo_ctx* ctx, DevBuf& b, size_t bytes) {
-    if (bytes <= b.cap) return 0;
-    if (b.p) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    size_t want = bytes + bytes / 8 + 256;
-    HIP_TRY(ctx, hipMalloc(&b.p, want));
-    b.cap = want;
-    return 0;
-}
+inline int dh_ensure(dehalo_ctx* ctx, DevBuf& b, size_t bytes) { return b.ensure(ctx, bytes); }
 
 inline bool dh_host_locked(const void* ptr, size_t bytes) {
     {
@@ -230,8 +153,8 @@ inline bool dh_host_locked(const void* ptr, size_t bytes) {
 inline int dh_stage_init(dehalo_ctx* ctx) {
     HostStage& st = ctx->stage;
     for (int i = 0; i < 2; i++) {
-        if (!st.buf[i]) HIP_TRY(ctx, hipHostMalloc(&st.buf[i], HostStage::CHUNK, hipHostMallocDefault));
-        if (!st.ev[i]) HIP_TRY(ctx, hipEventCreateWithFlags(&st.ev[i], hipEventDisableTiming));
+        if (!st.buf[i]) HIP_TRY(ctx, make_pinned(st.buf[i], HostStage::CHUNK));
+        if (!st.ev[i]) HIP_TRY(ctx, make_event(st.ev[i], hipEventDisableTiming));
     }
     return 0;
 }
@@ -250,10 +173,10 @@ inline int dh_h2d(dehalo_ctx* ctx, void* d_dst, const void* h_src, size_t bytes,
     int i = 0;
     for (size_t off = 0; off < bytes; off += HostStage::CHUNK, i ^= 1) {
         const size_t len = std::min(HostStage::CHUNK, bytes - off);
-        if (st.busy[i]) { HIP_TRY(ctx, hipEventSynchronize(st.ev[i])); st.busy[i] = false; }
-        memcpy(st.buf[i], (const char*)h_src + off, len);
-        HIP_TRY(ctx, hipMemcpyAsync((char*)d_dst + off, st.buf[i], len, hipMemcpyHostToDevice, s));
-        HIP_TRY(ctx, hipEventRecord(st.ev[i], s));
+        if (st.busy[i]) { HIP_TRY(ctx, hipEventSynchronize(st.ev[i].get())); st.busy[i] = false; }
+        memcpy(st.buf[i].get(), (const char*)h_src + off, len);
+        HIP_TRY(ctx, hipMemcpyAsync((char*)d_dst + off, st.buf[i].get(), len, hipMemcpyHostToDevice, s));
+        HIP_TRY(ctx, hipEventRecord(st.ev[i].get(), s));
         st.busy[i] = true;
     }
     return 0;
@@ -290,21 +213,21 @@ inline int dh_d2h(dehalo_ctx* ctx, void* h_dst, const void* d_src, size_t bytes,
     std::lock_guard<std::mutex> lk(st.mu);
     TRY(dh_stage_init(ctx));
     for (int i = 0; i < 2; i++)
-        if (st.busy[i]) { HIP_TRY(ctx, hipEventSynchronize(st.ev[i])); st.busy[i] = false; }
+        if (st.busy[i]) { HIP_TRY(ctx, hipEventSynchronize(st.ev[i].get())); st.busy[i] = false; }
     int i = 0;
     size_t prev_off = 0, prev_len = 0;
     for (size_t off = 0; off < bytes; off += HostStage::CHUNK, i ^= 1) {
         const size_t len = std::min(HostStage::CHUNK, bytes - off);
-        HIP_TRY(ctx, hipMemcpyAsync(st.buf[i], (const char*)d_src + off, len, hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipEventRecord(st.ev[i], s));
+        HIP_TRY(ctx, hipMemcpyAsync(st.buf[i].get(), (const char*)d_src + off, len, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipEventRecord(st.ev[i].get(), s));
         if (prev_len) {      // the previous chunk lands in the other buffer: hand it to the caller while this one is in flight
-            HIP_TRY(ctx, hipEventSynchronize(st.ev[i ^ 1]));
-            memcpy((char*)h_dst + prev_off, st.buf[i ^ 1], prev_len);
+            HIP_TRY(ctx, hipEventSynchronize(st.ev[i ^ 1].get()));
+            memcpy((char*)h_dst + prev_off, st.buf[i ^ 1].get(), prev_len);
         }
         prev_off = off; prev_len = len;
     }
-    HIP_TRY(ctx, hipEventSynchronize(st.ev[i ^ 1]));
-    memcpy((char*)h_dst + prev_off, st.buf[i ^ 1], prev_len);
+    HIP_TRY(ctx, hipEventSynchronize(st.ev[i ^ 1].get()));
+    memcpy((char*)h_dst + prev_off, st.buf[i ^ 1].get(), prev_len);
     return 0;
 }
 
@@ -328,20 +251,14 @@ struct ScopedTimer {
     dehalo_ctx* ctx;
     hipStream_t s;
     int id;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     ScopedTimer(dehalo_ctx* c, hipStream_t st, int kid) : ctx(c), s(st), id(kid) {
-        if (ctx->timing) {
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
-                a = b = nullptr;
-                return;
-            }
-            (void)hipEventRecord(a, s);
-        }
+        if (ctx->timing && make_event(a, hipEventDefault) == hipSuccess && make_event(b, hipEventDefault) == hipSuccess) (void)hipEventRecord(a.get(), s);
     }
     ~ScopedTimer() {
         if (a && b) {
-            (void)hipEventRecord(b, s);
-            ctx->regions.push_back({id, a, b});
+            (void)hipEventRecord(b.get(), s);
+            ctx->regions.push_back({id, std::move(a), std::move(b)});
         }
     }
 };
@@ -399,7 +316,7 @@ const GfftOps* gfft_ops(int curve);     // capi.hip: null for an unknown curve
 // A plain (precompute 0) registration whose points are replaced on the stream, without a host wait or an allocation (capi.hip): the IPA rounds'
 // shrinking generator vector.  alloc: room for `cap` points, empty; rebuild: n <= cap points from d_points (standard Montgomery), the window
 // chosen for n as dehalo_bases_register_device would; queued on s, so the caller may overwrite d_points once later work on s reads the table.
-int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, dehalo_bases** out);
+int dh_bases_plain_alloc(dehalo_ctx* ctx, int curve, size_t cap, BasesPtr& out);
 int dh_bases_plain_rebuild(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_points, size_t n, hipStream_t s);
 // ParamsKZG::setup's device half (setup.cuh, instantiated in msm_bn254.hip): g[i] = [s^i] G, g_lagrange[i] = [L_i(s)] G into device memory
 int kzg_setup_bn254(dehalo_ctx* ctx, uint32_t k, const uint64_t s[4], const uint64_t omega[4], const uint64_t cfac[4], affine_t* d_g, affine_t* d_gl, hipStream_t st);

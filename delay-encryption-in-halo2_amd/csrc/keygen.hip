@@ -43,10 +43,10 @@ int lagrange_to_all(dehalo_pk* pk, const dehalo_params* params, const fe* values
             TRY(jac.alloc(ctx, 3 * cnt, false));
             TRY(bl.alloc(ctx, cnt, false));
             TRY(dehalo_upload(ctx, bh.data(), cnt * 32, bl.p));
-            TRY(dehalo_msm_device(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, jac.u64(), nullptr));
+            TRY(dehalo_msm_device(ctx, params->bases_gl.get(), (const uint64_t*)values, d.n, cnt, jac.u64(), nullptr));
             TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64(), bl.u64(), cnt, params->d_guw.u64(2 * params->n + 2), nullptr));
             TRY(dehalo_to_affine_device(ctx, params->curve, jac.u64(), cnt, aff.u64(), nullptr));
-        } else TRY(dehalo_msm_device_affine(ctx, params->bases_gl, (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
+        } else TRY(dehalo_msm_device_affine(ctx, params->bases_gl.get(), (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
     }
     TRY(dehalo_lagrange_to_coeff_device(ctx, pk->f->id, (const uint64_t*)values, (uint64_t*)polys, d.k, d.omega_inv.v, d.ifft_divisor.v, cnt, nullptr));
     TRY(dehalo_coset_ntt_form_device(ctx, pk->f->id, (const uint64_t*)polys, d.k, (uint64_t*)cosets, d.extended_k, d.ext_omega.v, d.g_coset.v, cnt, DEHALO_FORM_OUT_INTERNAL,
@@ -58,14 +58,6 @@ int lagrange_to_all(dehalo_pk* pk, const dehalo_params* params, const fe* values
 
 }   // namespace
 
-dehalo_pk::~dehalo_pk() {
-    if (custom_gates) (void)dehalo_graph_release(ctx, custom_gates);
-    for (auto* g : lookup_graphs) (void)dehalo_graph_release(ctx, g);
-    for (auto& g : compress_graphs) {
-        (void)dehalo_graph_release(ctx, g.first);
-        (void)dehalo_graph_release(ctx, g.second);
-    }
-}
 size_t dehalo_pk::vk_size() const { return 8 + 64 * (size_t)cs.num_fixed + 64 * cs.perm_cols.size() + (size_t)num_selectors * ((dom.n + 7) / 8); }
 void dehalo_pk::vk_write(uint8_t* o) const {
     put_u32_be(o, k);
@@ -100,24 +92,23 @@ void dehalo_pk::default_transcript_repr() {
     transcript_repr = f->from_u512(d);
 }
 int dehalo_pk::compile_graphs() {
-    TRY(custom_gates_graph(cs, f).compile(ctx, &custom_gates));
+    TRY(custom_gates_graph(cs, f).compile(ctx, adopt(ctx, custom_gates)));
     for (auto& lk : cs.lookups) {
-        dehalo_graph *g = nullptr, *gi = nullptr, *gt = nullptr;
-        TRY(lookup_table_value_graph(cs, lk, f).compile(ctx, &g));
-        lookup_graphs.push_back(g);
-        TRY(compress_graph(cs, lk.inputs, f).compile(ctx, &gi));
-        const int rc = compress_graph(cs, lk.tables, f).compile(ctx, &gt);
-        compress_graphs.push_back({gi, gt});
-        if (rc) return rc;
+        GraphPtr g, gi, gt;
+        TRY(lookup_table_value_graph(cs, lk, f).compile(ctx, adopt(ctx, g)));
+        lookup_graphs.push_back(std::move(g));
+        TRY(compress_graph(cs, lk.inputs, f).compile(ctx, adopt(ctx, gi)));
+        TRY(compress_graph(cs, lk.tables, f).compile(ctx, adopt(ctx, gt)));
+        compress_graphs.emplace_back(std::move(gi), std::move(gt));
     }
     return 0;
 }
 
 // (n, 4) device column of omega^i: the forward NTT of the unit vector e_1
 int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col) {
-    HIP_TRY(ctx, hipMemsetAsync(col, 0, d.n * sizeof(fe), ctx->stream));
-    TRY(dh_h2d(ctx, col + (d.n > 1 ? 1 : 0), d.f->one.v, 32, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (the source is a host object: copied before returning)
+    HIP_TRY(ctx, hipMemsetAsync(col, 0, d.n * sizeof(fe), ctx->stream.get()));
+    TRY(dh_h2d(ctx, col + (d.n > 1 ? 1 : 0), d.f->one.v, 32, ctx->stream.get()));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));      // (the source is a host object: copied before returning)
     if (d.n > 1) TRY(dehalo_ntt_device(ctx, d.f->id, (uint64_t*)col, d.k, d.omega.v, 1, nullptr));
     return 0;
 }
@@ -142,8 +133,8 @@ extern "C" int dehalo_keygen(dehalo_ctx* ctx, const dehalo_params* params, const
         pk->fixed_commitments.assign(8 * nf, 0);
         if (nf) {
             HostPin pin_fixed(fixed, nf * n * 32);
-            TRY(dh_h2d(ctx, pk->fixed_values.p, fixed, nf * n * 32, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            TRY(dh_h2d(ctx, pk->fixed_values.p, fixed, nf * n * 32, ctx->stream.get()));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
             if (flags & DEHALO_KEYGEN_FIXED_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, pk->fixed_values.u64(), nullptr, pk->fixed_values.u64(), nf * n, nullptr));
             TRY(lagrange_to_all(pk.get(), params, pk->fixed_values.p, nf, pk->fixed_polys.p, pk->fixed_cosets.p, pk->fixed_commitments.data()));
         }
@@ -156,25 +147,21 @@ extern "C" int dehalo_keygen(dehalo_ctx* ctx, const dehalo_params* params, const
             for (size_t i = 0; i < npc * n; i++)
                 if (mapping[i] >= npc * n) return dh_fail(ctx, DEHALO_ERR_INVALID, "keygen: permutation mapping points outside the permutation's columns");
             DevMem ident, w;
-            uint64_t* d_map = nullptr;
+            DevArray<uint64_t> d_map;
             TRY(ident.alloc(ctx, npc * n, false));
             TRY(w.alloc(ctx, n, false));
             TRY(omega_powers(ctx, d, w.p));
             Fe dj = pk->f->one;
             for (size_t j = 0; j < npc; j++) {
-                HIP_TRY(ctx, hipMemcpyAsync(ident.at(j * n), w.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_TRY(ctx, hipMemcpyAsync(ident.at(j * n), w.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ctx->stream.get()));
                 if (j) TRY(dehalo_scale_device(ctx, fid, ident.u64(j * n), n, dj.v, 1, nullptr, nullptr));
                 dj = pk->f->mul(dj, pk->f->delta);
             }
-            HIP_TRY(ctx, hipMalloc((void**)&d_map, npc * n * 8));
+            TRY(d_map.alloc(ctx, npc * n, false));
             HostPin pin_map(mapping, npc * n * 8);
-            hipError_t e = dh_h2d(ctx, d_map, mapping, npc * n * 8, ctx->stream) == 0 ? hipSuccess : hipErrorUnknown;
-            if (e == hipSuccess) {
-                k_gather_elems<<<(unsigned)((npc * n + 255) / 256), 256, 0, ctx->stream>>>(ident.p, d_map, pk->perm_values.p, npc * n);
-                e = hipStreamSynchronize(ctx->stream);
-            }
-            (void)hipFree(d_map);
-            HIP_TRY(ctx, e);
+            TRY(dh_h2d(ctx, d_map.p, mapping, npc * n * 8, ctx->stream.get()));
+            k_gather_elems<<<(unsigned)((npc * n + 255) / 256), 256, 0, ctx->stream.get()>>>(ident.p, d_map.p, pk->perm_values.p, npc * n);
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
             TRY(lagrange_to_all(pk.get(), params, pk->perm_values.p, npc, pk->perm_polys.p, pk->perm_cosets.p, pk->perm_commitments.data()));
         }
         // l0, l_last, l_active_row = 1 - (l_last + l_blind) over the extended domain
@@ -189,8 +176,8 @@ extern "C" int dehalo_keygen(dehalo_ctx* ctx, const dehalo_params* params, const
             TRY(polys.alloc(ctx, 3 * n, false));
             TRY(pk->l_ext.alloc(ctx, 3 * m, false));
             HostPin pin_lag(lag.data(), 3 * n * 32);
-            TRY(dh_h2d(ctx, vals.p, lag.data(), 3 * n * 32, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            TRY(dh_h2d(ctx, vals.p, lag.data(), 3 * n * 32, ctx->stream.get()));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
             TRY(lagrange_to_all(pk.get(), params, vals.p, 3, polys.p, pk->l_ext.p, nullptr));
         }
         pk->num_selectors = num_selectors;
@@ -289,8 +276,8 @@ extern "C" int dehalo_pk_read(dehalo_ctx* ctx, int curve, const dehalo_constrain
         auto poly = [&](fe* dst, size_t want, bool to_internal) -> int {
             if (get_u32_be(p) != want) return dh_fail(ctx, DEHALO_ERR_INVALID, "pk_read: polynomial length differs from the domain's");
             p += 4;
-            TRY(dh_h2d(ctx, dst, p, want * 32, ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            TRY(dh_h2d(ctx, dst, p, want * 32, ctx->stream.get()));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));
             p += want * 32;
             if (to_internal) TRY(dehalo_convert_form_device(ctx, fid, (const uint64_t*)dst, (uint64_t*)dst, want, 1, nullptr));
             return 0;
@@ -338,7 +325,7 @@ extern "C" int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk) {
         dehalo_ctx* c = ctx ? ctx : pk->ctx;
         std::lock_guard<std::recursive_mutex> lk(c->mu);
         (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->stream);
+        (void)hipStreamSynchronize(c->stream.get());
         delete pk;
         return 0;
     });

@@ -862,7 +862,7 @@ int run_msm_t(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, s
     }
     {
         ScopedTimer t(ctx, s, DEHALO_K_MSM_ACCUMULATE);
-        k_msm_accum0<CV><<<p.acc_grid, p.acc_block, p.acc_lds, s>>>(g, tb, idx, off, nrank, bases->table, partial0, geo);
+        k_msm_accum0<CV><<<p.acc_grid, p.acc_block, p.acc_lds, s>>>(g, tb, idx, off, nrank, bases->table.p, partial0, geo);
         HIP_TRY(ctx, hipGetLastError());
     }
     {
@@ -887,7 +887,7 @@ int run_msm_t(dehalo_ctx* ctx, const dehalo_bases* bases, const fe* d_scalars, s
 template <class CV>
 int build_table_t(dehalo_ctx* ctx, dehalo_bases* b, const affine_t* d_std_points, hipStream_t s) {
     u32 rows = b->precomp ? b->W : 1;
-    k_msm_build_table<CV><<<(u32)((b->n + 127) / 128), 128, 0, s>>>(d_std_points, b->table, (u32)b->n, b->c, rows);
+    k_msm_build_table<CV><<<(u32)((b->n + 127) / 128), 128, 0, s>>>(d_std_points, b->table.p, (u32)b->n, b->c, rows);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

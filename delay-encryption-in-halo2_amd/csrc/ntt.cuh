@@ -436,33 +436,31 @@ int get_twiddles(dehalo_ctx* ctx, uint32_t log_n, const uint64_t omega[4], hipSt
     if (full) *full = want_full;
     for (auto& t : ctx->twiddles)
         if (t.field == F::ID && t.log_n == log_n && t.form == 0 && t.len == half && !memcmp(t.omega, omega, 32)) {
-            *out = t.tw;
+            *out = t.tw.p;
             return 0;
         }
-    fe* tw = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&tw, half * sizeof(fe)));
+    DevMem tw;      // this function's until the table is in the cache
+    TRY(tw.alloc(ctx, half, false));
     uint64_t threads = (half + 63) / 64;
     uint32_t blocks = (uint32_t)((threads + 127) / 128);
-    k_twiddle_gen<F><<<blocks, 128, 0, s>>>(tw, fe_from_u64(omega), half);
+    k_twiddle_gen<F><<<blocks, 128, 0, s>>>(tw.p, fe_from_u64(omega), half);
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->twiddles.size() >= 16) {  // bounded cache: drop the oldest
         HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipFree(ctx->twiddles.front().tw));
-        ctx->twiddles.erase(ctx->twiddles.begin());
+        ctx->twiddles.erase(ctx->twiddles.begin());      // (frees its table)
     }
     TwiddleEntry e;
-    e.field = F::ID; e.log_n = log_n; e.form = 0; memcpy(e.omega, omega, 32); e.len = half; e.tw = tw;
-    ctx->twiddles.push_back(e);
-    *out = tw;
+    e.field = F::ID; e.log_n = log_n; e.form = 0; memcpy(e.omega, omega, 32); e.len = half; e.tw = std::move(tw);
+    ctx->twiddles.push_back(std::move(e));
+    *out = ctx->twiddles.back().tw.p;
     return 0;
 }
 
 #ifdef DEHALO_EXPERIMENTS
 // measurement only: phases of the workgroups of one pass from their wall-clock stamps (100 MHz), relative to the first workgroup's start
-static inline void ntt_report_stamps(dehalo_ctx* ctx, unsigned long long* d, uint64_t nblk, uint32_t pass, uint32_t r, uint32_t tile_log, hipStream_t s) {
+static inline void ntt_report_stamps(dehalo_ctx* ctx, const unsigned long long* d, uint64_t nblk, uint32_t pass, uint32_t r, uint32_t tile_log, hipStream_t s) {
     std::vector<unsigned long long> h(nblk * 4);
-    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h.data(), d, nblk * 32, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipFree(d); return; }
-    (void)hipFree(d);
+    if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(h.data(), d, nblk * 32, hipMemcpyDeviceToHost) != hipSuccess) return;
     unsigned long long t0 = ~0ull;
     for (uint64_t i = 0; i < nblk; i++) t0 = std::min(t0, h[4 * i]);
     const char* names[4] = {"start", "tile in LDS", "stages done", "stores issued"};
@@ -556,7 +554,9 @@ int run_ntt_t(dehalo_ctx* ctx, const fe* src, uint64_t src_len, uint64_t src_str
         }
 #ifdef DEHALO_EXPERIMENTS
         static const bool stamps_on = getenv("DEHALO_NTT_STAMPS") != nullptr;
-        if (stamps_on) HIP_TRY(ctx, hipMalloc((void**)&P.stamps, tiles * batch * 4 * sizeof(unsigned long long)));
+        DevArray<unsigned long long> stamps;
+        if (stamps_on) TRY(stamps.alloc(ctx, tiles * batch * 4, false));
+        P.stamps = stamps.p;
 #endif
         k_ntt_pass<F><<<grid, NTT_THREADS >> (NTT_TILE_LOG - tile_log), lds, s>>>(P);
         HIP_TRY(ctx, hipGetLastError());

@@ -73,12 +73,8 @@ extern "C" int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, cons
         p->g_lagrange.assign(g_lagrange, g_lagrange + 8 * p->n);
         if (g2) memcpy(p->g2, g2, 128);
         if (s_g2) memcpy(p->s_g2, s_g2, 128);
-        TRY(dehalo_bases_register(ctx, curve, g, p->n, 64, 0, 1, &p->bases_g));
-        const int rc = dehalo_bases_register(ctx, curve, g_lagrange, p->n, 64, 0, 1, &p->bases_gl);
-        if (rc) {
-            (void)dehalo_bases_release(ctx, p->bases_g);
-            return rc;
-        }
+        TRY(dehalo_bases_register(ctx, curve, g, p->n, 64, 0, 1, adopt(ctx, p->bases_g)));
+        TRY(dehalo_bases_register(ctx, curve, g_lagrange, p->n, 64, 0, 1, adopt(ctx, p->bases_gl)));
         *out = p.release();
         return 0;
     });
@@ -160,19 +156,12 @@ extern "C" int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const
         DevMem dg, dgl;
         TRY(dg.alloc(ctx, 2 * n, false));
         TRY(dgl.alloc(ctx, 2 * n, false));
-        TRY(kzg_setup_bn254(ctx, k, sm.v, omega.v, cfac.v, (affine_t*)dg.p, (affine_t*)dgl.p, ctx->stream));
-        TRY(dehalo_bases_register_device(ctx, curve, dg.u64(), n, 0, 1, &p->bases_g));
-        int rc = dehalo_bases_register_device(ctx, curve, dgl.u64(), n, 0, 1, &p->bases_gl);
-        if (rc == 0) {
-            p->g.resize(8 * n); p->g_lagrange.resize(8 * n);
-            rc = dehalo_download(ctx, dg.p, 64 * n, p->g.data());
-            if (rc == 0) rc = dehalo_download(ctx, dgl.p, 64 * n, p->g_lagrange.data());
-        }
-        if (rc) {
-            (void)dehalo_bases_release(ctx, p->bases_g);
-            if (p->bases_gl) (void)dehalo_bases_release(ctx, p->bases_gl);
-            return rc;
-        }
+        TRY(kzg_setup_bn254(ctx, k, sm.v, omega.v, cfac.v, (affine_t*)dg.p, (affine_t*)dgl.p, ctx->stream.get()));
+        TRY(dehalo_bases_register_device(ctx, curve, dg.u64(), n, 0, 1, adopt(ctx, p->bases_g)));
+        TRY(dehalo_bases_register_device(ctx, curve, dgl.u64(), n, 0, 1, adopt(ctx, p->bases_gl)));
+        p->g.resize(8 * n); p->g_lagrange.resize(8 * n);
+        TRY(dehalo_download(ctx, dg.p, 64 * n, p->g.data()));
+        TRY(dehalo_download(ctx, dgl.p, 64 * n, p->g_lagrange.data()));
         {   // g2 = the generator, s_g2 = [s] g2
             const HostField* q = host_field(curve_base_field(curve));
             G2Host g2(q);
@@ -224,11 +213,7 @@ extern "C" int dehalo_params_write(const dehalo_params* p, uint8_t* out, size_t 
 
 extern "C" int dehalo_params_release(dehalo_ctx* ctx, dehalo_params* p) {
     return dh_guard(ctx, [&]() -> int {
-        if (!p) return 0;
-        if (p->bases_g) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_g);
-        if (p->bases_gl) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_gl);
-        if (p->bases_uw) (void)dehalo_bases_release(ctx ? ctx : p->ctx, p->bases_uw);
-        delete p;
+        delete p;      // (its bases release themselves, each as dehalo_bases_release does, on the context the params were made on)
         return 0;
     });
 }
@@ -237,7 +222,7 @@ extern "C" int dehalo_params_commit_device(dehalo_ctx* ctx, const dehalo_params*
                                            void* stream) {
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !p) return DEHALO_ERR_INVALID;
-        return dehalo_msm_device_affine(ctx, lagrange ? p->bases_gl : p->bases_g, d_polys, p->n, batch, nullptr, d_out_affine, stream);
+        return dehalo_msm_device_affine(ctx, (lagrange ? p->bases_gl : p->bases_g).get(), d_polys, p->n, batch, nullptr, d_out_affine, stream);
     });
 }
 
@@ -304,15 +289,15 @@ int ipa_params_finish(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g,
     const size_t n = (size_t)1 << k;
     dehalo_params* raw = nullptr;
     TRY(dehalo_params_create(ctx, curve, k, g, g_lagrange, nullptr, nullptr, &raw));
-    std::unique_ptr<dehalo_params, void (*)(dehalo_params*)> p(raw, [](dehalo_params* q) { (void)dehalo_params_release(q->ctx, q); });
+    std::unique_ptr<dehalo_params> p(raw);
     p->scheme = DEHALO_SCHEME_IPA;
     memcpy(p->w, w, 64);
     memcpy(p->u, u, 64);
     TRY(p->d_guw.alloc(ctx, 2 * (n + 2), false));
-    TRY(dh_h2d(ctx, p->d_guw.p, g, 64 * n, ctx->stream));
-    TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream));
-    TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream));
-    TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, &p->bases_uw));
+    TRY(dh_h2d(ctx, p->d_guw.p, g, 64 * n, ctx->stream.get()));
+    TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream.get()));
+    TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream.get()));
+    TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, adopt(ctx, p->bases_uw)));
     *out = p.release();
     return 0;
 }
@@ -349,8 +334,8 @@ extern "C" int dehalo_params_ipa_from_g(dehalo_ctx* ctx, int curve, uint32_t k, 
         DevMem dg, dgl;
         TRY(dg.alloc(ctx, 2 * n, false));
         TRY(dgl.alloc(ctx, 2 * n, false));
-        TRY(dh_h2d(ctx, dg.p, g, 64 * n, ctx->stream));
-        TRY(dehalo_g_to_lagrange_device(ctx, curve, dg.u64(), k, dgl.u64(), ctx->stream));
+        TRY(dh_h2d(ctx, dg.p, g, 64 * n, ctx->stream.get()));
+        TRY(dehalo_g_to_lagrange_device(ctx, curve, dg.u64(), k, dgl.u64(), ctx->stream.get()));
         std::vector<uint64_t> gl(8 * n);
         TRY(dehalo_download(ctx, dgl.p, 64 * n, gl.data()));
         return ipa_params_finish(ctx, curve, k, g, gl.data(), w, u, out);
@@ -405,8 +390,8 @@ extern "C" int dehalo_params_ipa_read(dehalo_ctx* ctx, int curve, const uint8_t*
         TRY(enc.alloc(ctx, count, false));
         TRY(pts.alloc(ctx, 2 * count, false));
         TRY(status.alloc(ctx, 1, true));
-        TRY(dh_h2d(ctx, enc.p, bytes + 4, 32 * count, ctx->stream));
-        TRY(gfft_ops(curve)->decompress(ctx, (const uint8_t*)enc.p, (affine_t*)pts.p, count, (uint32_t*)status.p, ctx->stream));
+        TRY(dh_h2d(ctx, enc.p, bytes + 4, 32 * count, ctx->stream.get()));
+        TRY(gfft_ops(curve)->decompress(ctx, (const uint8_t*)enc.p, (affine_t*)pts.p, count, (uint32_t*)status.p, ctx->stream.get()));
         uint32_t bad[8];
         TRY(dehalo_download(ctx, status.p, 32, bad));
         if (bad[0] & 1u) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_read: an x coordinate is not below the modulus");
@@ -425,7 +410,7 @@ namespace {
 // commit(poly, blind) of ParamsIPA = MSM(poly, g) + [blind] W, affine into d_pair[0] (d_pair: two points of scratch; [1] receives W): the MSM's affine
 // result and W make a two-point generator vector whose collapse by `blind` is exactly C + [blind] W
 int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, uint64_t* d_pair, hipStream_t s) {
-    TRY(dehalo_msm_device_affine(ctx, p->bases_g, d_poly, p->n, 1, nullptr, d_pair, s));
+    TRY(dehalo_msm_device_affine(ctx, p->bases_g.get(), d_poly, p->n, 1, nullptr, d_pair, s));
     HIP_TRY(ctx, hipMemcpyAsync(d_pair + 8, p->d_guw.at(2 * p->n + 2), 64, hipMemcpyDeviceToDevice, s));
     return dehalo_generator_collapse_device(ctx, p->curve, d_pair, 2, blind.v, d_pair, s);
 }
@@ -435,7 +420,7 @@ int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* 
 // commitment::create_proof on `rng` as it stands (dehalo_ipa_open: a fresh generator; a whole proof: the proof's generator, right behind f's blind).
 // cha_stream: the ChaCha20 stream of the n-scalar draw under DEHALO_RNG_OS -- within one proof it must differ from the random polynomial's (1).
 int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t) {
-        const hipStream_t s = ctx->stream;
+        const hipStream_t s = ctx->stream.get();
         const int fid = curve_scalar_field(p->curve);
         const HostField* f = host_field(fid);
         const IpaOps* ops = ipa_ops(p->curve);
@@ -491,9 +476,8 @@ int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_pol
         Fe fsum = f->add(f->mul(s_blind, xi), blind);
         // ---- k rounds; b stays geometric: b^(j)[i] = c_j x3^i.  Round 1 runs over the resident precomputed table of g (its [U | W] terms over
         // bases_uw, added by a collapse with u = 1); rounds 2.. over one plain registration of [G' | U | W], rebuilt on the stream each round.
-        dehalo_bases* breg = nullptr;
-        TRY(dh_bases_plain_alloc(ctx, p->curve, n / 2 + 2, &breg));
-        std::unique_ptr<dehalo_bases, void (*)(dehalo_bases*)> breg_own(breg, [](dehalo_bases* b) { if (b->table) (void)hipFree(b->table); delete b; });
+        BasesPtr breg;
+        TRY(dh_bases_plain_alloc(ctx, p->curve, n / 2 + 2, breg));
         std::vector<Fe> x3_pow(k + 1);           // x3^(2^i)
         x3_pow[0] = x3;
         for (uint32_t i = 1; i <= k; i++) x3_pow[i] = f->sqr(x3_pow[i - 1]);
@@ -514,15 +498,15 @@ int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_pol
             const Fe zc = f->mul(z, c), zch = f->mul(zc, x3h);
             if (j == 0) {
                 TRY(ops->slots(ctx, ev.p, zc.v, zch.v, rr.at(0), uwsc.at(0), uwsc.at(2), s));
-                TRY(dehalo_msm_device_affine(ctx, p->bases_g, sc.u64(), n, 2, nullptr, pts.u64(0), s));       // L_g, R_g
-                TRY(dehalo_msm_device_affine(ctx, p->bases_uw, uwsc.u64(), 2, 2, nullptr, pts.u64(4), s));    // L_uw, R_uw (points 2, 3)
+                TRY(dehalo_msm_device_affine(ctx, p->bases_g.get(), sc.u64(), n, 2, nullptr, pts.u64(0), s));       // L_g, R_g
+                TRY(dehalo_msm_device_affine(ctx, p->bases_uw.get(), uwsc.u64(), 2, 2, nullptr, pts.u64(4), s));    // L_uw, R_uw (points 2, 3)
                 const uint64_t one_m[4] = {f->one.v[0], f->one.v[1], f->one.v[2], f->one.v[3]};
                 TRY(dehalo_generator_collapse_device(ctx, p->curve, pts.u64(), 4, one_m, pts.u64(), s));      // [L_g + L_uw, R_g + R_uw]
             } else {
                 TRY(ops->slots(ctx, ev.p, zc.v, zch.v, rr.at(2 * j), sl + nj, sr + nj, s));
                 HIP_TRY(ctx, hipMemcpyAsync(guw.at(2 * nj), p->d_guw.at(2 * n), 128, hipMemcpyDeviceToDevice, s));     // U, W behind G'
-                TRY(dh_bases_plain_rebuild(ctx, breg, (const affine_t*)guw.p, m, s));
-                TRY(dehalo_msm_device_affine(ctx, breg, sc.u64(), m, 2, nullptr, pts.u64(), s));
+                TRY(dh_bases_plain_rebuild(ctx, breg.get(), (const affine_t*)guw.p, m, s));
+                TRY(dehalo_msm_device_affine(ctx, breg.get(), sc.u64(), m, 2, nullptr, pts.u64(), s));
             }
             uint64_t LR[16];
             TRY(dehalo_download(ctx, pts.p, 128, LR));      // the round's one host wait

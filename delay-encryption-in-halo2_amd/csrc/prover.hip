@@ -43,18 +43,10 @@ struct dehalo_prover {
     uint32_t o_adv = 0, o_perm = 0, o_pz = 0, o_lz = 0, o_rand = 0;
     DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, hfold, qbuf, wbuf, jac, evals, blind_dev, omega_col;
     fe* polys = nullptr;      // coefficient forms: polys_own with a side context, cols (in place) without
-    std::vector<std::pair<dehalo_graph*, dehalo_graph*>> perm_graphs;      // per set: (denominator, numerator)
     std::vector<uint32_t> table_rep;      // per lookup: the first lookup with the same table expressions (shares its compressed table)
     // tables of fixed columns as distinct rows (lookup_permute.hip): per representative lookup one row index per distinct tuple of its table expressions' values over
     // the usable rows and the tuple's multiplicity, on the device; count 0: not such a table, or more distinct rows than the permutation's one-tile path takes
-    struct TableRows { uint32_t* d_rep = nullptr; uint32_t* d_mult = nullptr; uint32_t count = 0; };
-    std::vector<TableRows> table_rows;
-    dehalo_graph *lookup_den = nullptr, *lookup_num = nullptr;
-    hipEvent_t ev_ready[3] = {nullptr, nullptr, nullptr}, ev_inst = nullptr, ev_side = nullptr;      // ev_ready: one per commitment phase
-    hipEvent_t ev_helper = nullptr;      // the helper thread waits for ITS upload through this event: a hipStreamSynchronize on the side stream holds that stream
-    hipStream_t hs = nullptr;            // against the proving thread's launches (0.4 ms of the lookups' phase); the upload runs on a stream of its own beside it
-    uint64_t* adv_pin = nullptr;         // dehalo_create_proof_circuit: the advice columns the witness generator writes (page-locked, kept across proofs)
-    uint64_t* rand_pin = nullptr;        // host-drawn random polynomial (page-locked: its upload is one DMA that holds no stream)
+    struct TableRows { DevArray<uint32_t> d_rep, d_mult; uint32_t count = 0; };
     // opening plan (depends on the circuit only)
     std::vector<int32_t> rots;
     std::vector<const uint64_t*> plist;
@@ -92,23 +84,16 @@ struct dehalo_prover {
     void tk(const char* label) { if (trace) ticks.push_back({label, ms_since(t0)}); }
     std::mutex mu;      // one create_proof at a time per prover
 
-    ~dehalo_prover() {
-        for (auto& g : perm_graphs) {
-            if (g.first) (void)dehalo_graph_release(ctx, g.first);
-            if (g.second) (void)dehalo_graph_release(ctx, g.second);
-        }
-        if (lookup_den) (void)dehalo_graph_release(ctx, lookup_den);
-        if (lookup_num) (void)dehalo_graph_release(ctx, lookup_num);
-        for (hipEvent_t e : {ev_ready[0], ev_ready[1], ev_ready[2], ev_inst, ev_side, ev_helper})
-            if (e) (void)hipEventDestroy(e);
-        if (rand_pin) (void)hipHostFree(rand_pin);
-        if (adv_pin) (void)hipHostFree(adv_pin);
-        if (hs) (void)hipStreamDestroy(hs);
-        for (auto& t : table_rows) {
-            if (t.d_rep) (void)hipFree(t.d_rep);
-            if (t.d_mult) (void)hipFree(t.d_mult);
-        }
-    }
+    // Everything that is not plain device memory comes last and is declared in the reverse of the order it is released in: members are destroyed bottom-up, so the
+    // graphs go first, each behind a device synchronise, then the events, the page-locked buffers, the helper's stream, the tables' rows and the arrays above.
+    std::vector<TableRows> table_rows;
+    Stream hs;                     // a hipStreamSynchronize on the side stream holds that stream against the proving thread's launches (0.4 ms of the lookups' phase):
+    Event ev_helper;               // the helper thread's upload runs on a stream of its own beside it, and the helper waits for ITS upload through this event
+    Pinned<uint64_t> adv_pin;      // dehalo_create_proof_circuit: the advice columns the witness generator writes (page-locked, kept across proofs)
+    Pinned<uint64_t> rand_pin;     // host-drawn random polynomial (page-locked: its upload is one DMA that holds no stream)
+    Event ev_side, ev_inst, ev_ready[3];      // ev_ready: one per commitment phase
+    GraphPtr lookup_num, lookup_den;
+    std::vector<std::pair<GraphPtr, GraphPtr>> perm_graphs;      // per set: (denominator, numerator)
 
     int build_product_graphs() {
         const HostCS& cs = pk->cs;
@@ -133,11 +118,10 @@ struct dehalo_prover {
             }
             gd.add_calc(DEHALO_CALC_STORE, dacc);
             gn.add_calc(DEHALO_CALC_STORE, nacc);
-            dehalo_graph *d = nullptr, *nn = nullptr;
-            TRY(gd.compile(ctx, &d));
-            const int rc = gn.compile(ctx, &nn);
-            perm_graphs.push_back({d, nn});
-            if (rc) return rc;
+            GraphPtr d, nn;
+            TRY(gd.compile(ctx, adopt(ctx, d)));
+            TRY(gn.compile(ctx, adopt(ctx, nn)));
+            perm_graphs.emplace_back(std::move(d), std::move(nn));
         }
         // advice slots: [compressed_input, compressed_table, permuted_input, permuted_table]
         GraphBuilder gd(f), gn(f);
@@ -145,8 +129,8 @@ struct dehalo_prover {
                     gd.add_calc(DEHALO_CALC_ADD, gd.column(DEHALO_SRC_ADVICE, 3), GSrc{DEHALO_SRC_GAMMA, 0, 0}));
         gn.add_calc(DEHALO_CALC_MUL, gn.add_calc(DEHALO_CALC_ADD, gn.column(DEHALO_SRC_ADVICE, 0), GSrc{DEHALO_SRC_BETA, 0, 0}),
                     gn.add_calc(DEHALO_CALC_ADD, gn.column(DEHALO_SRC_ADVICE, 1), GSrc{DEHALO_SRC_GAMMA, 0, 0}));
-        TRY(gd.compile(ctx, &lookup_den));
-        TRY(gn.compile(ctx, &lookup_num));
+        TRY(gd.compile(ctx, adopt(ctx, lookup_den)));
+        TRY(gn.compile(ctx, adopt(ctx, lookup_num)));
         return 0;
     }
 
@@ -325,9 +309,9 @@ struct dehalo_prover {
             TRY(evals.alloc(ctx, eval_count + 8 + ns));
         } else
         TRY(evals.alloc(ctx, eval_count + 8));
-        for (hipEvent_t* e : {&ev_ready[0], &ev_ready[1], &ev_ready[2], &ev_inst, &ev_side, &ev_helper}) HIP_TRY(ctx, hipEventCreateWithFlags(e, hipEventDisableTiming));
-        HIP_TRY(ctx, hipHostMalloc((void**)&rand_pin, (size_t)n * 32, hipHostMallocDefault));
-        if (side) HIP_TRY(ctx, hipStreamCreateWithFlags(&hs, hipStreamNonBlocking));
+        for (Event* e : {&ev_ready[0], &ev_ready[1], &ev_ready[2], &ev_inst, &ev_side, &ev_helper}) HIP_TRY(ctx, make_event(*e, hipEventDisableTiming));
+        HIP_TRY(ctx, make_pinned(rand_pin, (size_t)n * 32));
+        if (side) HIP_TRY(ctx, make_stream(hs, hipStreamNonBlocking));
         host_aff.resize(8 * (size_t)maxpts);
         host_jac.resize(12 * (size_t)maxpts + 8 + L);
         host_evals.resize(4 * eval_count);
@@ -351,7 +335,7 @@ struct dehalo_prover {
     }
     int find_table_rows() {
         const HostCS& cs = pk->cs;
-        table_rows.assign(L, TableRows{});
+        table_rows = std::vector<TableRows>(L);
         static const bool enabled = [] { const char* e = DH_EXPERIMENT_ENV("DEHALO_PROVER_TABLE_ROWS"); return !(e && e[0] == '0'); }();      // (0: every table sorted in full, for the A/B)
         if (!enabled) return 0;
         std::vector<std::vector<Fe>> colv(cs.num_fixed);
@@ -386,10 +370,10 @@ struct dehalo_prover {
             }
             if (too_many || rep.empty()) continue;
             TableRows& tr = table_rows[l];
-            HIP_TRY(ctx, hipMalloc((void**)&tr.d_rep, rep.size() * 4));
-            HIP_TRY(ctx, hipMalloc((void**)&tr.d_mult, rep.size() * 4));
-            TRY(dehalo_upload(ctx, rep.data(), rep.size() * 4, tr.d_rep));
-            TRY(dehalo_upload(ctx, mult.data(), mult.size() * 4, tr.d_mult));
+            TRY(tr.d_rep.alloc(ctx, rep.size(), false));
+            TRY(tr.d_mult.alloc(ctx, rep.size(), false));
+            TRY(dehalo_upload(ctx, rep.data(), rep.size() * 4, tr.d_rep.p));
+            TRY(dehalo_upload(ctx, mult.data(), mult.size() * 4, tr.d_mult.p));
             tr.count = (uint32_t)rep.size();
         }
         return 0;
@@ -434,7 +418,7 @@ struct dehalo_prover {
         const bool sharded = shard_world > 1 && shard_gather && count > 1;
         const size_t lo = sharded ? count * shard_rank / shard_world : 0, hi = sharded ? count * (shard_rank + 1) / shard_world : count;
         if (hi > lo)
-            TRY(dehalo_msm_device(ctx, lagrange ? params->bases_gl : params->bases_g, (const uint64_t*)(src + lo * n), n, hi - lo, jac.u64() + 12 * lo, nullptr));
+            TRY(dehalo_msm_device(ctx, (lagrange ? params->bases_gl : params->bases_g).get(), (const uint64_t*)(src + lo * n), n, hi - lo, jac.u64() + 12 * lo, nullptr));
         if (ipa && !d_blinds) return dh_fail(ctx, DEHALO_ERR_INVALID, "commit: a ParamsIPA commitment without its blind");
         if (ipa && hi > lo)
             TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64() + 12 * lo, (const uint64_t*)(d_blinds + lo), hi - lo, params->d_guw.u64(2 * params->n + 2), nullptr));
@@ -533,7 +517,7 @@ struct ProofRun {
     const Fe* E = nullptr;          // the evaluations on the host, indexed by the opening plan
 
     ProofRun(dehalo_prover& pv, dehalo_transcript* t, dehalo_rng* r)
-        : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream), ss(pv.side ? pv.side->stream : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
+        : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream.get()), ss(pv.side ? pv.side->stream.get() : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
           fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), pieces(pv.pieces), nco(pv.NC - 1),
           rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1) {}
     ~ProofRun() {      // whatever path the proof took: the witness' copy (asynchronous) has landed before its pin goes, and the helper has finished
@@ -574,7 +558,7 @@ struct ProofRun {
             for (uint32_t i = 0; i < pieces; i++) bl[p.bi_h + i] = late[1 + i];
             bl[p.bi_f] = late[1 + pieces];
             for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[p.bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
-            TRY(dh_h2d(ctx, p.ipa_blinds.p, bl.data(), (size_t)p.bi_count * 32, ctx->stream));      // (waited for with the blinding rows, upload_blinds)
+            TRY(dh_h2d(ctx, p.ipa_blinds.p, bl.data(), (size_t)p.bi_count * 32, ctx->stream.get()));      // (waited for with the blinding rows, upload_blinds)
         }
         return 0;
     }
@@ -588,18 +572,18 @@ struct ProofRun {
         (void)hipSetDevice(ctx->device);
         const auto th0 = clk::now();
         int rc = 0;
-        if (!device_rng) rc = rng_poly.scalars(p.rand_pin, n);
+        if (!device_rng) rc = rng_poly.scalars(p.rand_pin.get(), n);
         helper_ms[0] = ms_since(th0);
         if (!rc && side) {      // (without a side context only the draw is taken off the critical path; the upload is queued by the proving thread)
             fe* dst = p.polys + (size_t)p.o_rand * n;
             hipError_t e = hipSuccess;
-            if (device_rng) rc = chacha_scalars_device(ctx, rng_poly, 1, dst, n, p.hs);
-            else e = hipMemcpyAsync(dst, p.rand_pin, n * 32, hipMemcpyHostToDevice, p.hs);
+            if (device_rng) rc = chacha_scalars_device(ctx, rng_poly, 1, dst, n, p.hs.get());
+            else e = hipMemcpyAsync(dst, p.rand_pin.get(), n * 32, hipMemcpyHostToDevice, p.hs.get());
             if (e != hipSuccess) rc = dh_fail(side, DEHALO_ERR_HIP, std::string("random polynomial upload: ") + hipGetErrorString(e));
             helper_ms[1] = ms_since(th0);
             if (!rc) {      // wait for this stream through an event of this thread's own: the coefficients are there before the join
-                e = hipEventRecord(p.ev_helper, p.hs);
-                if (e == hipSuccess) e = hipEventSynchronize(p.ev_helper);
+                e = hipEventRecord(p.ev_helper.get(), p.hs.get());
+                if (e == hipSuccess) e = hipEventSynchronize(p.ev_helper.get());
                 if (e != hipSuccess) rc = dh_fail(side, DEHALO_ERR_HIP, std::string("random polynomial: ") + hipGetErrorString(e));
             }
             helper_ms[2] = ms_since(th0);
@@ -611,9 +595,9 @@ struct ProofRun {
     // stream, and run on an otherwise idle device while this thread (and the synthesis pool) writes the advice columns
     int synthesize(const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
         if (synth_in->k != k || A != 5) return dh_fail(ctx, DEHALO_ERR_INVALID, "create_proof_circuit: the circuit's k / advice columns differ from the key's");
-        if (!p.adv_pin) HIP_TRY(ctx, hipHostMalloc((void**)&p.adv_pin, (size_t)A * n * 32, hipHostMallocDefault));
+        if (!p.adv_pin) HIP_TRY(ctx, make_pinned(p.adv_pin, (size_t)A * n * 32));
         start_random_polynomial();
-        const int src = dehalo_synthesize(synth_in, p.adv_pin, nullptr, nullptr, nullptr, synth_info);
+        const int src = dehalo_synthesize(synth_in, p.adv_pin.get(), nullptr, nullptr, nullptr, synth_info);
         if (src) return dh_fail(ctx, src, "create_proof_circuit: the circuit's inputs are invalid or it does not fit 2^k rows");
         p.tk("witness synthesized");
         return 0;
@@ -663,7 +647,7 @@ struct ProofRun {
         // IPA (QUERY_INSTANCE = true): commit_lagrange(instance, Blind::default()), absorbed as points
         if (I && ipa) TRY(p.commit(tr, p.instance.p, I, true, nullptr, 0, p.blind_at(p.bi_def), false));
         if (I) HIP_TRY(ctx, hipMemcpyAsync(p.instance_values.p, p.instance.p, (size_t)I * n * 32, hipMemcpyDeviceToDevice, ms));
-        if (I && side) HIP_TRY(ctx, hipEventRecord(p.ev_inst, ms));
+        if (I && side) HIP_TRY(ctx, hipEventRecord(p.ev_inst.get(), ms));
         if (I && !side) TRY(dehalo_intt_scaled_device(ctx, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
         return 0;
     }
@@ -689,14 +673,14 @@ struct ProofRun {
     // ---- advice: witness, blinding rows, commitments
     int advice_columns(const uint64_t* advice, uint32_t flags) {
         if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
-        const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin;      // (the witness generator's output is page-locked already)
+        const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin.get();      // (the witness generator's output is page-locked already)
         pin_advice.reset(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
         fe* adv = p.cols.at((size_t)p.o_adv * n);
         if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
         else TRY(dh_h2d(ctx, adv, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
         if (flags & DEHALO_PROOF_ADVICE_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, (uint64_t*)adv, nullptr, (uint64_t*)adv, (size_t)A * n, nullptr));
         if (A) k_place_rows<<<(unsigned)((rows * A + 255) / 256), 256, 0, ms>>>(adv + u, n, p.blind_dev.p, (uint32_t)rows, A);
-        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[0], ms));
+        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[0].get(), ms));
         for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(p.pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(p.pk->fixed_cosets, i, m));
         for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.o_adv + i, n)), adv_c.push_back(col_ptr(p.ext, p.o_adv + i, m));
         for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(p.instance_values, i, n)), inst_c.push_back(col_ptr(p.ext, nco + i, m));
@@ -704,15 +688,15 @@ struct ProofRun {
     }
     int after_advice_queued() {
         if (I && side) {
-            HIP_TRY(side, hipStreamWaitEvent(ss, p.ev_inst, 0));
+            HIP_TRY(side, hipStreamWaitEvent(ss, p.ev_inst.get(), 0));
             TRY(dehalo_intt_scaled_device(side, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
             TRY(dehalo_coset_ntt_form_device(side, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         }
-        if (side) TRY(side_ntt(p.o_adv, A, p.ev_ready[0]));
+        if (side) TRY(side_ntt(p.o_adv, A, p.ev_ready[0].get()));
         if (gates_early) {
             EvalIn e = coset_inputs();
             e.in.y = zero.v;
-            TRY(dehalo_graph_evaluate_device(side, p.pk->custom_gates, &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
+            TRY(dehalo_graph_evaluate_device(side, p.pk->custom_gates.get(), &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
         }
         if (!helper.joinable()) start_random_polynomial();      // (unless it runs since the synthesis) the host is idle from here to the read-back
         return 0;
@@ -724,10 +708,10 @@ struct ProofRun {
         std::vector<const dehalo_graph*> graphs;
         std::vector<uint64_t*> outs;
         for (uint32_t l = 0; l < L; l++) {      // lookups with the same table expressions share ONE compressed table column (their representative's)
-            graphs.push_back(p.pk->compress_graphs[l].first);
+            graphs.push_back(p.pk->compress_graphs[l].first.get());
             outs.push_back(p.compressed.u64((size_t)2 * l * n));
             if (p.table_rep[l] == l) {
-                graphs.push_back(p.pk->compress_graphs[l].second);
+                graphs.push_back(p.pk->compress_graphs[l].second.get());
                 outs.push_back(p.compressed.u64((size_t)(2 * l + 1) * n));
             }
         }
@@ -752,15 +736,15 @@ struct ProofRun {
         std::vector<uint32_t> tcount;
         for (uint32_t l = 0; l < L; l++) {
             const dehalo_prover::TableRows& t = p.table_rows[p.table_rep[l]];
-            trep.push_back(t.d_rep); tmult.push_back(t.d_mult); tcount.push_back(t.count);
+            trep.push_back(t.d_rep.p); tmult.push_back(t.d_mult.p); tcount.push_back(t.count);
         }
         TRY(dehalo_permute_expression_pair_distinct_device(ctx, fid, pin.data(), ptab.data(), u, L, pout_in.data(), pout_tab.data(), trep.data(), tmult.data(), tcount.data(),
                                                            reinterpret_cast<int32_t*>(p.jac.u64() + 12 * 2 * (size_t)L), nullptr));
         p.tk("permute queued");
-        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[1], ms));
+        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[1].get(), ms));
         return p.commit(tr, p.cols.at((size_t)p.o_perm * n), 2 * L, true, side ? std::function<int()>([this] { return after_lookups_queued(); }) : nullptr, L, p.blind_at(p.bi_perm));
     }
-    int after_lookups_queued() { return side_ntt(p.o_perm, 2 * L, p.ev_ready[1]); }
+    int after_lookups_queued() { return side_ntt(p.o_perm, 2 * L, p.ev_ready[1].get()); }
 
     // ---- grand products: permutation sets, then lookups; one batched inversion.  The random polynomial's values are the launch's last column
     // (cols[o_rand] sits right behind the products): its commitment is written with theirs
@@ -773,7 +757,7 @@ struct ProofRun {
         if (side) HIP_TRY(ctx, hipMemcpyAsync(rl, p.polys + (size_t)p.o_rand * n, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));      // (the helper put the coefficients there)
         else {      // without a side context the coefficient forms live in `cols` itself: keep a copy for after the commitment
             if (device_rng) TRY(chacha_scalars_device(ctx, rng_poly, 1, rl, n, ms));
-            else HIP_TRY(ctx, hipMemcpyAsync(rl, p.rand_pin, n * 32, hipMemcpyHostToDevice, ms));      // (rand_pin: page-locked, the library's own)
+            else HIP_TRY(ctx, hipMemcpyAsync(rl, p.rand_pin.get(), n * 32, hipMemcpyHostToDevice, ms));      // (rand_pin: page-locked, the library's own)
             HIP_TRY(ctx, hipMemcpyAsync(p.wbuf.p, rl, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
         }
         TRY(dehalo_ntt_device(ctx, fid, (uint64_t*)rl, k, d.omega.v, 1, nullptr));
@@ -811,7 +795,7 @@ struct ProofRun {
         // per column: bf blinding rows (n - bf .. n)
         const fe* bl_prod = p.blind_dev.p + (size_t)(A + 2 * L) * rows;
         k_place_rows<<<(unsigned)(((size_t)bf * (S + L) + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.o_pz * n + (n - bf)), n, bl_prod, bf, S + L);
-        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[2], ms));
+        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[2].get(), ms));
         return p.commit(tr, p.cols.at((size_t)p.o_pz * n), S + L + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.bi_prod));
     }
     int restore_random() {      // (queued behind the MSM's kernels on the same stream)
@@ -821,11 +805,12 @@ struct ProofRun {
     int after_products_queued() {
         TRY(restore_random());
         if (!side) return 0;
-        TRY(side_ntt(p.o_pz, S + L, p.ev_ready[2]));
+        TRY(side_ntt(p.o_pz, S + L, p.ev_ready[2].get()));
         // the lookups' (compressed input + beta)(compressed table + gamma) over the extended domain need theta, beta, gamma and the advice /
         // fixed cosets: all there -- on the side context, beside the products' commitment, instead of after y
         if (L) {
-            std::vector<const dehalo_graph*> graphs(p.pk->lookup_graphs.begin(), p.pk->lookup_graphs.end());
+            std::vector<const dehalo_graph*> graphs;
+            for (auto& g : p.pk->lookup_graphs) graphs.push_back(g.get());
             std::vector<uint64_t*> outs;
             for (uint32_t l = 0; l < L; l++) outs.push_back(p.table_value.u64((size_t)l * m));
             EvalIn e = coset_inputs();
@@ -843,14 +828,14 @@ struct ProofRun {
             TRY(dehalo_coset_ntt_form_device(ctx, fid, p.cols.u64(), k, p.ext.u64(), ek, d.ext_omega.v, d.g_coset.v, nco, DEHALO_FORM_OUT_INTERNAL, nullptr));
             if (I) TRY(dehalo_coset_ntt_form_device(ctx, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         } else {      // queued phase by phase on the side context: wait for it
-            HIP_TRY(side, hipEventRecord(p.ev_side, ss));
-            HIP_TRY(ctx, hipStreamWaitEvent(ms, p.ev_side, 0));
+            HIP_TRY(side, hipEventRecord(p.ev_side.get(), ss));
+            HIP_TRY(ctx, hipStreamWaitEvent(ms, p.ev_side.get(), 0));
         }
         const uint64_t *l0 = p.pk->l_ext.u64(0), *l_last = p.pk->l_ext.u64(m), *l_active = p.pk->l_ext.u64(2 * m);
         if (!gates_early) {
             EvalIn e = coset_inputs();
             e.in.y = y.v;
-            TRY(dehalo_graph_evaluate_device(ctx, p.pk->custom_gates, &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
+            TRY(dehalo_graph_evaluate_device(ctx, p.pk->custom_gates.get(), &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
         }
         if (S) {
             std::vector<const uint64_t*> z, pcols, sigma;
@@ -871,7 +856,7 @@ struct ProofRun {
         for (uint32_t l = 0; l < L && !side; l++) {
             EvalIn e = coset_inputs();
             e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
-            TRY(dehalo_graph_evaluate_device(ctx, p.pk->lookup_graphs[l], &e.in, ek, rot_scale, nullptr, p.table_value.u64((size_t)l * m), nullptr));
+            TRY(dehalo_graph_evaluate_device(ctx, p.pk->lookup_graphs[l].get(), &e.in, ek, rot_scale, nullptr, p.table_value.u64((size_t)l * m), nullptr));
         }
         for (uint32_t first = 0; first < L; first += 8) {
             std::vector<dehalo_lookup_inputs> li;
@@ -1026,7 +1011,7 @@ struct ProofRun {
         TRY(draw_blinds());
         if (synth_in) {
             TRY(synthesize(synth_in, synth_info));
-            advice = p.adv_pin;
+            advice = p.adv_pin.get();
             flags = (flags & ~(uint32_t)DEHALO_PROOF_ADVICE_ON_DEVICE) | DEHALO_PROOF_ADVICE_CANONICAL;
         }
         TRY(upload_blinds());
@@ -1066,8 +1051,8 @@ int prove(dehalo_prover* p, const uint64_t* advice, const uint64_t* const* insta
     std::lock_guard<std::mutex> lk(p->mu);
     const int rc = ProofRun(*p, transcript, rng).run(advice, instances, instance_lens, num_instance_columns, flags, synth_in, synth_info);
     if (rc) {      // leave nothing of this proof in flight on either context
-        (void)hipStreamSynchronize(p->ctx->stream);
-        if (p->side) (void)hipStreamSynchronize(p->side->stream);
+        (void)hipStreamSynchronize(p->ctx->stream.get());
+        if (p->side) (void)hipStreamSynchronize(p->side->stream.get());
     }
     return rc;
 }
@@ -1092,8 +1077,8 @@ extern "C" int dehalo_prover_release(dehalo_prover* p) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p) return 0;
         (void)hipSetDevice(p->ctx->device);
-        (void)hipStreamSynchronize(p->ctx->stream);
-        if (p->side) (void)hipStreamSynchronize(p->side->stream);
+        (void)hipStreamSynchronize(p->ctx->stream.get());
+        if (p->side) (void)hipStreamSynchronize(p->side->stream.get());
         delete p;
         return 0;
     });

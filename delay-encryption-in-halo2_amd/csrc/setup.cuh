@@ -91,27 +91,23 @@ template <class CV>
 int kzg_setup_t(dehalo_ctx* ctx, uint32_t k, const uint64_t s[4], const uint64_t omega[4], const uint64_t cfac[4], affine_t* d_g, affine_t* d_gl, hipStream_t st) {
     typedef typename CV::Scalar FS;
     const u64 n = 1ull << k;
-    affine_t* table = nullptr;
-    fe *pw = nullptr, *w = nullptr, *lag = nullptr;
-    auto cleanup = [&]() { (void)hipFree(table); (void)hipFree(pw); (void)hipFree(w); (void)hipFree(lag); };
-    hipError_t e = hipMalloc((void**)&table, FB_WINDOWS * 256 * sizeof(affine_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&pw, n * sizeof(fe));
-    if (e == hipSuccess) e = hipMalloc((void**)&w, n * sizeof(fe));
-    if (e == hipSuccess) e = hipMalloc((void**)&lag, n * sizeof(fe));
-    if (e != hipSuccess) { cleanup(); return dh_fail(ctx, DEHALO_ERR_OOM, std::string("params_setup: ") + hipGetErrorString(e)); }
+    DevArray<affine_t> table;
+    DevMem pw, w, lag;
+    TRY(table.alloc(ctx, FB_WINDOWS * 256, false));
+    TRY(pw.alloc(ctx, n, false));
+    TRY(w.alloc(ctx, n, false));
+    TRY(lag.alloc(ctx, n, false));
     const unsigned runs = (unsigned)((n + 63) / 64), pb = (runs + 127) / 128, eb = (unsigned)((n + 255) / 256);
-    k_fb_table<CV><<<FB_WINDOWS * 256 / 64, 64, 0, st>>>(table);
-    k_powers_std<FS><<<pb, 128, 0, st>>>(pw, fe_from_u64(s), n);
-    k_powers_std<FS><<<pb, 128, 0, st>>>(w, fe_from_u64(omega), n);
-    k_lag_den<FS><<<eb, 256, 0, st>>>(w, fe_from_u64(s), lag, n);
-    int rc = hipGetLastError() == hipSuccess ? 0 : dh_fail(ctx, DEHALO_ERR_HIP, "params_setup: launch failed");
-    if (rc == 0) rc = dehalo_batch_invert_device(ctx, FS::ID, (uint64_t*)lag, n, st);
-    if (rc == 0) {
-        k_lag_fin<FS><<<eb, 256, 0, st>>>(lag, w, fe_from_u64(cfac), lag, n);
-        k_fb_mul<CV><<<(unsigned)((n + 127) / 128), 128, 0, st>>>(pw, table, d_g, n);
-        k_fb_mul<CV><<<(unsigned)((n + 127) / 128), 128, 0, st>>>(lag, table, d_gl, n);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = dh_fail(ctx, DEHALO_ERR_HIP, "params_setup: kernels failed");
-    }
-    cleanup();
-    return rc;
+    k_fb_table<CV><<<FB_WINDOWS * 256 / 64, 64, 0, st>>>(table.p);
+    k_powers_std<FS><<<pb, 128, 0, st>>>(pw.p, fe_from_u64(s), n);
+    k_powers_std<FS><<<pb, 128, 0, st>>>(w.p, fe_from_u64(omega), n);
+    k_lag_den<FS><<<eb, 256, 0, st>>>(w.p, fe_from_u64(s), lag.p, n);
+    HIP_TRY(ctx, hipGetLastError());
+    TRY(dehalo_batch_invert_device(ctx, FS::ID, lag.u64(), n, st));
+    k_lag_fin<FS><<<eb, 256, 0, st>>>(lag.p, w.p, fe_from_u64(cfac), lag.p, n);
+    k_fb_mul<CV><<<(unsigned)((n + 127) / 128), 128, 0, st>>>(pw.p, table.p, d_g, n);
+    k_fb_mul<CV><<<(unsigned)((n + 127) / 128), 128, 0, st>>>(lag.p, table.p, d_gl, n);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));      // (the temporaries above are freed on return: nothing may still read them)
+    return 0;
 }

@@ -8,31 +8,6 @@
 #include "internal.hpp"
 #include "plonk_host.hpp"
 
-// ---- device memory owned by an object of the whole call ----
-struct DevMem {
-    fe* p = nullptr;
-    size_t elems = 0;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { reset(); }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        elems = 0;
-    }
-    int alloc(dehalo_ctx* ctx, size_t n_elems, bool zero = true) {
-        reset();
-        if (!n_elems) return 0;
-        HIP_TRY(ctx, hipMalloc((void**)&p, n_elems * sizeof(fe)));
-        elems = n_elems;
-        if (zero) HIP_TRY(ctx, hipMemsetAsync(p, 0, n_elems * sizeof(fe), ctx->stream));
-        return 0;
-    }
-    fe* at(size_t elem) const { return p + elem; }
-    uint64_t* u64(size_t elem = 0) const { return (uint64_t*)(p + elem); }
-};
-
 // ================================================================================================ ParamsKZG / ParamsIPA (params.hip)
 struct dehalo_params {
     dehalo_ctx* ctx = nullptr;
@@ -41,11 +16,11 @@ struct dehalo_params {
     size_t n = 0;
     std::vector<uint64_t> g, g_lagrange;      // host copies (write())
     uint8_t g2[128] = {}, s_g2[128] = {};
-    dehalo_bases *bases_g = nullptr, *bases_gl = nullptr;
+    BasesPtr bases_g, bases_gl;
     int scheme = DEHALO_SCHEME_KZG;
     // ParamsIPA only: g as plain affine points followed by u, w (n + 2 points, standard Montgomery): the generator vector the opening collapses
     DevMem d_guw;
-    dehalo_bases* bases_uw = nullptr;         // [U | W] plain: the extra bases of round 1, whose G' part runs over bases_g
+    BasesPtr bases_uw;                        // [U | W] plain: the extra bases of round 1, whose G' part runs over bases_g
     uint64_t u[8] = {}, w[8] = {};
 };
 
@@ -121,11 +96,10 @@ struct dehalo_pk {
     Fe transcript_repr{};
     // device: values / polys in upstream's standard form, extended-domain columns in the kernels' internal form
     DevMem l_ext, fixed_values, fixed_polys, fixed_cosets, perm_values, perm_polys, perm_cosets;
-    dehalo_graph* custom_gates = nullptr;
-    std::vector<dehalo_graph*> lookup_graphs;
-    std::vector<std::pair<dehalo_graph*, dehalo_graph*>> compress_graphs;
+    GraphPtr custom_gates;
+    std::vector<GraphPtr> lookup_graphs;
+    std::vector<std::pair<GraphPtr, GraphPtr>> compress_graphs;
 
-    ~dehalo_pk();
     size_t vk_size() const;
     void vk_write(uint8_t* o) const;
     size_t size() const;

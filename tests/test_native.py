@@ -576,3 +576,32 @@ def test_params_setup_k20_and_its_limits(pkg, ctx):
     assert time.perf_counter() - t0 < 5.0, "k = 26 must be refused before the 2^27 fixed-base multiplications, not after"      # (those take tens of seconds)
     with pytest.raises(Exception):
         native.ParamsKZG.setup(ctx, pkg.fields.CURVES["pallas"], 6, 3)      # no pairing: not a KZG curve
+
+
+@pytest.mark.gpu
+def test_create_release_cycles_return_their_device_memory(pkg, co):
+    """A lifetime check (no stress, no failure provoked): one cycle is a context, ParamsKZG::setup at k = 6, keygen, a prover, one proof and the release of all
+    four.  The first cycle absorbs what the runtime allocates once (code objects, its own pools); after two more the device must have no less free memory
+    than after the first -- every allocation, event, stream and page-locked buffer of the four objects goes with its owner."""
+    import torch
+    from dehalo2_amd import circuits, native, prover
+
+    F = pkg.fields
+    k = 6
+    circ = circuits.synthesize(F.BN254.scalar.p, k, False, seed=3)
+    adv = np.stack([co.field_op(0, "to_mont", circ.advice[i]) for i in range(5)])
+
+    def cycle():
+        ctx = pkg.Context(0)
+        params = native.ParamsKZG.setup(ctx, F.BN254, k, 0x5EED)
+        pk = native.ProvingKey.keygen(ctx, params, circ.cs, circ.fixed, circ.assembly, circ.selectors)
+        pv = native.Prover(params, pk)
+        proof = pv.create_proof(adv, [[]], prover.SeededRng(7)).finalize()
+        assert len(proof) > 0
+        pv.release(); pk.release(); params.release(); ctx.close()
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    free = [cycle() for _ in range(3)]
+    print("free device memory after cycles 1..3: %r bytes" % (free,))
+    assert free[2] >= free[0], "device memory lost between the first and the third create / release cycle: %d bytes" % (free[0] - free[2])
