@@ -179,3 +179,51 @@ impl Drop for DehaloParamsIPA<'_> {
         unsafe { sys::dehalo_params_release(self.ctx.as_ptr(), self.raw) };
     }
 }
+
+/// `dehalo_fixed_base`: the window table of one point `P`, resident on the device -- `[s] P` without a doubling chain, for a few dozen scalars at a time.
+/// Device pointers in and out (the scalars are a proof's blinds, already in HBM); one launch per call, asynchronous on the stream.
+pub struct FixedBase<'c> {
+    ctx: &'c Context,
+    raw: *const sys::dehalo_fixed_base,
+    owned: bool,
+}
+
+impl<'c> FixedBase<'c> {
+    /// The table of `affine_xy` (`{x, y}`, Montgomery limbs as halo2curves holds them; all zero = the identity) on `curve` (`sys::DEHALO_CURVE_*`).
+    pub fn new(ctx: &'c Context, curve: i32, affine_xy: &[u64; 8]) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe { sys::dehalo_fixed_base_create(ctx.as_ptr(), curve, affine_xy.as_ptr(), &mut raw) })?;
+        Ok(Self { ctx, raw, owned: true })
+    }
+
+    /// `d_out_affine_xy[i] = [d_scalars[i]] P` for `i < count`: affine, `(0, 0)` for the identity.
+    ///
+    /// # Safety
+    /// `d_scalars` (32 B each) and `d_out_affine_xy` (64 B each) are device memory for `count` elements; `stream` is a `hipStream_t` or null.
+    pub unsafe fn mul_device(&self, d_scalars: *const u64, count: usize, d_out_affine_xy: *mut u64, stream: *mut core::ffi::c_void) -> Result<(), DehaloError> {
+        self.ctx.check(sys::dehalo_fixed_base_mul_device(self.ctx.as_ptr(), self.raw, d_scalars, count, d_out_affine_xy, stream))
+    }
+
+    /// `d_jacobian[i] += [d_blinds[i]] P` in place: the blinding term of `ParamsIPA::commit` over the results of one batched MSM.
+    ///
+    /// # Safety
+    /// `d_jacobian` (96 B each, as `dehalo_msm_device` leaves them) and `d_blinds` (32 B each) are device memory for `count` elements.
+    pub unsafe fn blind_device(&self, d_jacobian: *mut u64, d_blinds: *const u64, count: usize, stream: *mut core::ffi::c_void) -> Result<(), DehaloError> {
+        self.ctx.check(sys::dehalo_fixed_base_blind_device(self.ctx.as_ptr(), self.raw, d_jacobian, d_blinds, count, stream))
+    }
+}
+
+impl Drop for FixedBase<'_> {
+    fn drop(&mut self) {
+        if self.owned {
+            unsafe { sys::dehalo_fixed_base_release(self.ctx.as_ptr(), self.raw as *mut sys::dehalo_fixed_base) };
+        }
+    }
+}
+
+impl<'c> DehaloParamsIPA<'c> {
+    /// `W`'s table, which the params own (`dehalo_params_fixed_base`): borrowed, so it cannot outlive them.
+    pub fn fixed_base(&self) -> FixedBase<'_> {
+        FixedBase { ctx: self.ctx, raw: unsafe { sys::dehalo_params_fixed_base(self.raw) }, owned: false }
+    }
+}

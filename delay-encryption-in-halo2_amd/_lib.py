@@ -32,6 +32,7 @@ SYMBOLS = [
     "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs",
     "dehalo_params_ipa_create", "dehalo_params_scheme", "dehalo_generator_collapse_device", "dehalo_ipa_open", "dehalo_blind_commitments_device", "dehalo_prover_proof_size",
     "dehalo_g_to_lagrange_device", "dehalo_params_ipa_from_g", "dehalo_params_ipa_size", "dehalo_params_ipa_write", "dehalo_params_ipa_read",
+    "dehalo_fixed_base_create", "dehalo_fixed_base_release", "dehalo_fixed_base_mul_device", "dehalo_fixed_base_blind_device", "dehalo_params_fixed_base",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
 ]
 
@@ -163,6 +164,12 @@ def load_library():
     lib.dehalo_generator_collapse_device.argtypes = [P, C.c_int, u64p, sz, u64p, u64p, P]
     lib.dehalo_blind_commitments_device.argtypes = [P, C.c_int, u64p, u64p, sz, u64p, P]
     lib.dehalo_point_sum_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
+    lib.dehalo_fixed_base_create.argtypes = [P, C.c_int, u64p, C.POINTER(P)]
+    lib.dehalo_fixed_base_release.argtypes = [P, P]
+    lib.dehalo_fixed_base_mul_device.argtypes = [P, P, u64p, sz, u64p, P]
+    lib.dehalo_fixed_base_blind_device.argtypes = [P, P, u64p, u64p, sz, P]
+    lib.dehalo_params_fixed_base.argtypes = [P]
+    lib.dehalo_params_fixed_base.restype = C.c_void_p
     lib.dehalo_ntt.argtypes = [P, C.c_int, u64p, u32, u64p]
     lib.dehalo_ntt_device.argtypes = [P, C.c_int, u64p, u32, u64p, sz, P]
     lib.dehalo_intt_scaled.argtypes = [P, C.c_int, u64p, u32, u64p, u64p]
@@ -300,6 +307,27 @@ class Bases:
 
     def __len__(self):
         return self.n
+
+
+class FixedBase:
+    """dehalo_fixed_base: the window table of one point P, resident on the device -- [s] P without a doubling chain.  `owned` False: a table that belongs
+    to another object (ParamsIPA's table of W) and is released with it."""
+
+    def __init__(self, ctx: "Context", handle, curve: int, owned: bool = True):
+        self.ctx, self.handle, self.curve, self.owned = ctx, handle, curve, owned
+
+    def mul_device(self, d_scalars: int, count: int, d_out_affine: int, stream: int = 0):
+        """d_out_affine[i] = [d_scalars[i]] P: affine {x, y}, (0, 0) for the identity (device pointers; one launch)"""
+        self.ctx._check(self.ctx.lib.dehalo_fixed_base_mul_device(self.ctx.handle, self.handle, d_scalars or None, count, d_out_affine or None, stream or None))
+
+    def blind_device(self, d_jacobian: int, d_blinds: int, count: int, stream: int = 0):
+        """d_jacobian[i] += [d_blinds[i]] P, in place: Context.blind_commitments_device over the table (device pointers; one launch)"""
+        self.ctx._check(self.ctx.lib.dehalo_fixed_base_blind_device(self.ctx.handle, self.handle, d_jacobian or None, d_blinds or None, count, stream or None))
+
+    def release(self):
+        if self.handle is not None and self.owned:
+            self.ctx._check(self.ctx.lib.dehalo_fixed_base_release(self.ctx.handle, self.handle))
+        self.handle = None
 
 
 class Context:
@@ -443,6 +471,13 @@ class Context:
     def blind_commitments_device(self, curve: int, d_jacobian: int, d_blinds: int, count: int, d_w_affine: int, stream: int = 0):
         """ParamsIPA's blinding term for one batched MSM's results: d_jacobian[i] += [d_blinds[i]] W, in place (all device pointers; one launch)"""
         self._check(self.lib.dehalo_blind_commitments_device(self.handle, curve, d_jacobian or None, d_blinds or None, count, d_w_affine or None, stream or None))
+
+    def fixed_base(self, curve: int, affine_xy) -> FixedBase:
+        """the window table of the point affine_xy ({x, y}, 8 u64, standard Montgomery; all zero = the identity), built on the device (dehalo_fixed_base_create)"""
+        a = np.ascontiguousarray(affine_xy, dtype=np.uint64).reshape(8)
+        h = C.c_void_p()
+        self._check(self.lib.dehalo_fixed_base_create(self.handle, curve, _ptr(a), C.byref(h)))
+        return FixedBase(self, h, curve)
 
     def to_affine_device(self, curve: int, d_jacobian: int, count: int, d_affine: int, stream: int = 0):
         self._check(self.lib.dehalo_to_affine_device(self.handle, curve, d_jacobian, count, d_affine, stream or None))

@@ -633,6 +633,64 @@ int dehalo_blind_commitments_device(dehalo_ctx* ctx, int curve, uint64_t* d_jaco
     return dh_device(ctx, stream, [&](hipStream_t s) { return ops->blind(ctx, (jacobian_t*)d_jacobian, (const fe*)d_blinds, (const affine_t*)d_w_affine_xy, count, s); });
 }
 
+// ---- fixed-base tables (fixed_base.cuh) ------------------------------------------------------
+static const FixedBaseOps* fixed_base_ops(int curve) {
+    static const FixedBaseOps* const ops[] = {&bn254_fixed_base_ops(), &pallas_fixed_base_ops(), &vesta_fixed_base_ops()};
+    return curve >= 0 && curve < 3 ? ops[curve] : nullptr;
+}
+
+int dehalo_fixed_base_create(dehalo_ctx* ctx, int curve, const uint64_t affine_xy[8], dehalo_fixed_base** out) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    const FixedBaseOps* ops = fixed_base_ops(curve);
+    if (!ops) return unknown_curve(ctx);
+    if (!affine_xy || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "fixed_base_create: null argument");
+    return dh_guard(ctx, [&]() -> int {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        FixedBasePtr fb(new dehalo_fixed_base(), FixedBaseFree{ctx});
+        fb->curve = curve;
+        TRY(fb->table.alloc(ctx, 32 * 256, false));
+        DevArray<affine_t> tmp;      // the point, then its 32 window multiples
+        TRY(tmp.alloc(ctx, 1 + 32, false));
+        TRY(dh_h2d(ctx, tmp.p, affine_xy, 64, ctx->stream.get()));
+        TRY(ops->build(ctx, tmp.at(0), tmp.at(1), fb->table.p, ctx->stream.get()));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream.get()));      // (tmp is freed on return: nothing may still read it)
+        *out = fb.release();
+        return 0;
+    });
+}
+
+int dehalo_fixed_base_release(dehalo_ctx* ctx, dehalo_fixed_base* fb) {
+    if (!ctx || !fb) return DEHALO_ERR_INVALID;
+    return dh_guard(ctx, [&] {
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        (void)hipDeviceSynchronize();
+        delete fb;
+        return 0;
+    });
+}
+
+int dehalo_fixed_base_mul_device(dehalo_ctx* ctx, const dehalo_fixed_base* fb, const uint64_t* d_scalars, size_t count, uint64_t* d_out_affine_xy, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!fb || ((!d_scalars || !d_out_affine_xy) && count)) return dh_fail(ctx, DEHALO_ERR_INVALID, "fixed_base_mul: null argument");
+    const FixedBaseOps* ops = fixed_base_ops(fb->curve);
+    if (!ops) return unknown_curve(ctx);
+    if (count >= (1ull << 29)) return dh_fail(ctx, DEHALO_ERR_INVALID, "fixed_base_mul: too many scalars");
+    if (count == 0) return 0;
+    return dh_device(ctx, stream, [&](hipStream_t s) { return ops->mul(ctx, fb->table.p, (const fe*)d_scalars, (affine_t*)d_out_affine_xy, count, s); });
+}
+
+int dehalo_fixed_base_blind_device(dehalo_ctx* ctx, const dehalo_fixed_base* fb, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!fb || ((!d_jacobian || !d_blinds) && count)) return dh_fail(ctx, DEHALO_ERR_INVALID, "fixed_base_blind: null argument");
+    const FixedBaseOps* ops = fixed_base_ops(fb->curve);
+    if (!ops) return unknown_curve(ctx);
+    if (count >= (1ull << 29)) return dh_fail(ctx, DEHALO_ERR_INVALID, "fixed_base_blind: too many points");
+    if (count == 0) return 0;
+    return dh_device(ctx, stream, [&](hipStream_t s) { return ops->blind(ctx, fb->table.p, (jacobian_t*)d_jacobian, (const fe*)d_blinds, count, s); });
+}
+
 int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_t count, uint64_t* affine_xy) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!jacobian || !affine_xy) && count) return dh_fail(ctx, DEHALO_ERR_INVALID, "to_affine: null argument");

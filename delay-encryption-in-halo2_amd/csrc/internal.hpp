@@ -91,6 +91,11 @@ struct dehalo_bases {
     DevArray<affine_t> table;  // n * (precomp ? W : 1) affine points in HBM, internal (R' = 2^261) canonical form
 };
 
+struct dehalo_fixed_base {
+    int curve;
+    DevArray<affine_t> table;  // T[w][d] = [d 2^(8 w)] P: 32 x 256 affine points, internal (R' = 2^261) canonical form, all zero for d = 0 and for P the identity
+};
+
 // never throws, so that argument checks may run in front of an entry point's guard: a message that cannot be stored is dropped
 inline int dh_fail(dehalo_ctx* ctx, int code, const char* msg) noexcept {
     if (ctx) try {
@@ -313,6 +318,18 @@ const GfftOps& bn254_gfft_ops();
 const GfftOps& pallas_gfft_ops();
 const GfftOps& vesta_gfft_ops();
 const GfftOps* gfft_ops(int curve);     // capi.hip: null for an unknown curve
+// fixed-base scalar multiplication over the window table of one point, one table of kernels per curve (fixed_base.cuh, instantiated in msm_*.hip)
+struct FixedBaseOps {
+    // d_table (32 x 256 entries, packed internal form) from d_base (one affine point, standard Montgomery); d_pows: 32 points of scratch
+    int (*build)(dehalo_ctx* ctx, const affine_t* d_base, affine_t* d_pows, affine_t* d_table, hipStream_t s);
+    // out[i] = [scalars[i]] P for i < m, affine
+    int (*mul)(dehalo_ctx* ctx, const affine_t* d_table, const fe* d_scalars, affine_t* d_out, uint64_t m, hipStream_t s);
+    // pts[i] <- pts[i] + [blinds[i]] P for i < m: IpaOps::blind over the table
+    int (*blind)(dehalo_ctx* ctx, const affine_t* d_table, jacobian_t* d_pts, const fe* d_blinds, uint64_t m, hipStream_t s);
+};
+const FixedBaseOps& bn254_fixed_base_ops();
+const FixedBaseOps& pallas_fixed_base_ops();
+const FixedBaseOps& vesta_fixed_base_ops();
 // A plain (precompute 0) registration whose points are replaced on the stream, without a host wait or an allocation (capi.hip): the IPA rounds'
 // shrinking generator vector.  alloc: room for `cap` points, empty; rebuild: n <= cap points from d_points (standard Montgomery), the window
 // chosen for n as dehalo_bases_register_device would; queued on s, so the caller may overwrite d_points once later work on s reads the table.

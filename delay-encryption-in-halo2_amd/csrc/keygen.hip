@@ -44,7 +44,7 @@ int lagrange_to_all(dehalo_pk* pk, const dehalo_params* params, const fe* values
             TRY(bl.alloc(ctx, cnt, false));
             TRY(dehalo_upload(ctx, bh.data(), cnt * 32, bl.p));
             TRY(dehalo_msm_device(ctx, params->bases_gl.get(), (const uint64_t*)values, d.n, cnt, jac.u64(), nullptr));
-            TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64(), bl.u64(), cnt, params->d_guw.u64(2 * params->n + 2), nullptr));
+            TRY(dehalo_fixed_base_blind_device(ctx, params->fb_w.get(), jac.u64(), bl.u64(), cnt, nullptr));
             TRY(dehalo_to_affine_device(ctx, params->curve, jac.u64(), cnt, aff.u64(), nullptr));
         } else TRY(dehalo_msm_device_affine(ctx, params->bases_gl.get(), (const uint64_t*)values, d.n, cnt, nullptr, aff.u64(), nullptr));
     }

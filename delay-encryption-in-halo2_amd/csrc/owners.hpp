@@ -118,13 +118,15 @@ hipError_t make_pinned(Pinned<T>& out, size_t bytes) {
     return rc;
 }
 
-// ---- the objects behind dehalo_bases* / dehalo_graph*: released as dehalo_bases_release / dehalo_graph_release release them (under the context's lock, after a
+// ---- the objects behind dehalo_bases* / dehalo_graph* / dehalo_fixed_base*: released as dehalo_bases_release / dehalo_graph_release / dehalo_fixed_base_release release them (under the context's lock, after a
 // device synchronise), also when they never reached the caller.  adopt(ctx, dst) stands for the out-parameter of the function that creates one:
 // TRY(dehalo_graph_create(ctx, ..., adopt(ctx, g))) leaves the new handle, or none, in g. ----
 struct BasesFree { dehalo_ctx* ctx = nullptr; void operator()(dehalo_bases* b) const { (void)dehalo_bases_release(ctx, b); } };
 struct GraphFree { dehalo_ctx* ctx = nullptr; void operator()(dehalo_graph* g) const { (void)dehalo_graph_release(ctx, g); } };
+struct FixedBaseFree { dehalo_ctx* ctx = nullptr; void operator()(dehalo_fixed_base* f) const { (void)dehalo_fixed_base_release(ctx, f); } };
 using BasesPtr = std::unique_ptr<dehalo_bases, BasesFree>;
 using GraphPtr = std::unique_ptr<dehalo_graph, GraphFree>;
+using FixedBasePtr = std::unique_ptr<dehalo_fixed_base, FixedBaseFree>;
 
 template <class Ptr>
 struct Adopt {

@@ -283,7 +283,7 @@ extern "C" void dehalo_transcript_release(dehalo_transcript* t) { delete t; }
 namespace {
 
 // what dehalo_params_ipa_create and dehalo_params_ipa_from_g share once g_lagrange is known: the two resident MSM tables, g | u | w as plain points on the
-// device and the [U | W] registration
+// device, the [U | W] registration and W's fixed-base table
 int ipa_params_finish(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
                       dehalo_params** out) {
     const size_t n = (size_t)1 << k;
@@ -298,6 +298,7 @@ int ipa_params_finish(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g,
     TRY(dh_h2d(ctx, p->d_guw.at(2 * n), u, 64, ctx->stream.get()));
     TRY(dh_h2d(ctx, p->d_guw.at(2 * n + 2), w, 64, ctx->stream.get()));
     TRY(dehalo_bases_register_device(ctx, curve, p->d_guw.u64(2 * n), 2, 0, 0, adopt(ctx, p->bases_uw)));
+    TRY(dehalo_fixed_base_create(ctx, curve, w, adopt(ctx, p->fb_w)));
     *out = p.release();
     return 0;
 }
@@ -404,15 +405,17 @@ extern "C" int dehalo_params_ipa_read(dehalo_ctx* ctx, int curve, const uint8_t*
 }
 
 extern "C" int dehalo_params_scheme(const dehalo_params* p) { return p ? p->scheme : DEHALO_ERR_INVALID; }
+extern "C" const dehalo_fixed_base* dehalo_params_fixed_base(const dehalo_params* p) { return p ? p->fb_w.get() : nullptr; }
 
 namespace {
 
-// commit(poly, blind) of ParamsIPA = MSM(poly, g) + [blind] W, affine into d_pair[0] (d_pair: two points of scratch; [1] receives W): the MSM's affine
-// result and W make a two-point generator vector whose collapse by `blind` is exactly C + [blind] W
-int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, uint64_t* d_pair, hipStream_t s) {
-    TRY(dehalo_msm_device_affine(ctx, p->bases_g.get(), d_poly, p->n, 1, nullptr, d_pair, s));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pair + 8, p->d_guw.at(2 * p->n + 2), 64, hipMemcpyDeviceToDevice, s));
-    return dehalo_generator_collapse_device(ctx, p->curve, d_pair, 2, blind.v, d_pair, s);
+// commit(poly, blind) of ParamsIPA = MSM(poly, g) + [blind] W, affine into d_pts[0 .. 8) (d_pts: 8 field elements of scratch = 32 u64; the Jacobian
+// result sits in [8, 20), the blind in [20, 24)): the MSM, [blind] W from W's table on top of it, one normalisation -- all on the stream
+int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, uint64_t* d_pts, hipStream_t s) {
+    TRY(dh_h2d(ctx, d_pts + 20, blind.v, 32, s));
+    TRY(dehalo_msm_device(ctx, p->bases_g.get(), d_poly, p->n, 1, d_pts + 8, s));
+    TRY(dehalo_fixed_base_blind_device(ctx, p->fb_w.get(), d_pts + 8, d_pts + 20, 1, s));
+    return dehalo_to_affine_device(ctx, p->curve, d_pts + 8, 1, d_pts, s);
 }
 
 }   // namespace

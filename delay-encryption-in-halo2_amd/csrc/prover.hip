@@ -421,7 +421,7 @@ struct dehalo_prover {
             TRY(dehalo_msm_device(ctx, (lagrange ? params->bases_gl : params->bases_g).get(), (const uint64_t*)(src + lo * n), n, hi - lo, jac.u64() + 12 * lo, nullptr));
         if (ipa && !d_blinds) return dh_fail(ctx, DEHALO_ERR_INVALID, "commit: a ParamsIPA commitment without its blind");
         if (ipa && hi > lo)
-            TRY(dehalo_blind_commitments_device(ctx, params->curve, jac.u64() + 12 * lo, (const uint64_t*)(d_blinds + lo), hi - lo, params->d_guw.u64(2 * params->n + 2), nullptr));
+            TRY(dehalo_fixed_base_blind_device(ctx, params->fb_w.get(), jac.u64() + 12 * lo, (const uint64_t*)(d_blinds + lo), hi - lo, nullptr));
         tk("commit queued");
         if (before_sync) TRY(before_sync());
         tk("side work queued");

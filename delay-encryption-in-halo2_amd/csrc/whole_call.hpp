@@ -21,6 +21,7 @@ struct dehalo_params {
     // ParamsIPA only: g as plain affine points followed by u, w (n + 2 points, standard Montgomery): the generator vector the opening collapses
     DevMem d_guw;
     BasesPtr bases_uw;                        // [U | W] plain: the extra bases of round 1, whose G' part runs over bases_g
+    FixedBasePtr fb_w;                        // W's window table: the [blind] W of every commit / commit_lagrange (dehalo_fixed_base_blind_device)
     uint64_t u[8] = {}, w[8] = {};
 };
 

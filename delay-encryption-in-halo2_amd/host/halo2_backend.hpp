@@ -169,6 +169,36 @@ class ParamsIPA {
     dehalo_bases* gl_ = nullptr;
 };
 
+// [s] P for one fixed point P over its resident window table (dehalo_fixed_base_*): device pointers in and out, one launch per call, asynchronous on
+// the stream.  A table made here is released here; ParamsIPAHandle::fixed_base() lends the table of W, which the params own.
+class FixedBase {
+  public:
+    FixedBase(const Backend& be, dehalo_curve curve, const Affine& p) : be_(be), owned_(true) {
+        dehalo_fixed_base* fb = nullptr;
+        be_.check(dehalo_fixed_base_create(be_.raw(), curve, p.data(), &fb));
+        fb_ = fb;
+    }
+    FixedBase(const Backend& be, const dehalo_fixed_base* borrowed) : be_(be), fb_(borrowed), owned_(false) {}
+    ~FixedBase() { if (owned_ && fb_) dehalo_fixed_base_release(be_.raw(), const_cast<dehalo_fixed_base*>(fb_)); }
+    FixedBase(const FixedBase&) = delete;
+    FixedBase& operator=(const FixedBase&) = delete;
+    FixedBase(FixedBase&& o) : be_(o.be_), fb_(o.fb_), owned_(o.owned_) { o.fb_ = nullptr; }
+    // d_out_affine_xy[i] = [d_scalars[i]] P, (0, 0) for the identity
+    void mul_device(const uint64_t* d_scalars, size_t count, uint64_t* d_out_affine_xy, void* stream = nullptr) const {
+        be_.check(dehalo_fixed_base_mul_device(be_.raw(), fb_, d_scalars, count, d_out_affine_xy, stream));
+    }
+    // d_jacobian[i] += [d_blinds[i]] P in place: ParamsIPA's blinding term for the results of one batched MSM
+    void blind_device(uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, void* stream = nullptr) const {
+        be_.check(dehalo_fixed_base_blind_device(be_.raw(), fb_, d_jacobian, d_blinds, count, stream));
+    }
+    const dehalo_fixed_base* raw() const { return fb_; }
+
+  private:
+    const Backend& be_;
+    const dehalo_fixed_base* fb_ = nullptr;
+    bool owned_;
+};
+
 // ---- the whole call: plonk::{ConstraintSystem, keygen_vk, keygen_pk, create_proof}, ParamsKZG, Blake2bWrite ---------------------------
 // (include/dehalo.h "the whole call"; reference call sites benches/delay_enc.rs:41-54, 84-115, 120-134)
 
@@ -275,6 +305,8 @@ class ParamsIPAHandle {
         be_.check(dehalo_params_ipa_write(p_, out.data(), out.size()));
         return out;
     }
+    // W's window table: what every commit / commit_lagrange of these params adds [blind] W from
+    FixedBase fixed_base() const { return FixedBase(be_, dehalo_params_fixed_base(p_)); }
     dehalo_params* raw() const { return p_; }
 
   private:

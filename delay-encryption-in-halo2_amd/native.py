@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import plonk
-from ._lib import (CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, RNG_FILL_FN, load_library)
+from ._lib import (CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, FixedBase, RNG_FILL_FN, load_library)
 from .fields import CurveSpec, FieldSpec
 
 EXPR_KIND = {"const": 0, plonk.FIXED: 1, plonk.ADVICE: 2, plonk.INSTANCE: 3, "neg": 4, "sum": 5, "product": 6, "scaled": 7}
@@ -193,6 +193,11 @@ class ParamsIPA(ParamsKZG):
         out = np.empty(lib.dehalo_params_ipa_size(self.handle), dtype=np.uint8)
         _check(self.ctx, lib.dehalo_params_ipa_write(self.handle, out.ctypes.data, out.size))
         return out.tobytes()
+
+    @property
+    def fixed_base(self) -> FixedBase:
+        """W's window table (dehalo_params_fixed_base): what every commit / commit_lagrange adds [blind] W from.  It belongs to the params and goes with them."""
+        return FixedBase(self.ctx, C.c_void_p(load_library().dehalo_params_fixed_base(self.handle)), self.curve.id, owned=False)
 
     def open(self, d_poly: int, blind: int, x3: int, transcript: Optional["Blake2bWrite"] = None, rng=None) -> "Blake2bWrite":
         """commitment::create_proof of the 2^k coefficients at d_poly (device, Montgomery) with blind `blind` at x3 (dehalo_ipa_open)."""

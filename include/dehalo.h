@@ -168,6 +168,25 @@ int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t*
 int dehalo_blind_commitments_device(dehalo_ctx* ctx, int curve, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, const uint64_t* d_w_affine_xy,
                                     void* stream);
 
+/* ---- fixed-base scalar multiplication -----------------------------------------------------
+ * [s] P for ONE point P and many scalars, over a window table of P that stays resident: T[w][d] = [d 2^(8 w)] P, 32 byte-windows x 256 entries
+ * (512 KB of HBM), so that a multiplication is a sum of at most 32 table entries and no doubling.  One wave per scalar, six dependent group additions:
+ * the form for a few dozen scalars at a time (a proof phase's blinds), where the length of the dependent chain is the cost.  All three curves.
+ * ParamsIPA keeps such a table of W (every commit / commit_lagrange adds [blind] W); dehalo_blind_commitments_device above is the table-free form. */
+typedef struct dehalo_fixed_base dehalo_fixed_base;
+/* The table of P = affine_xy ({x, y}, 64 B, standard Montgomery, host memory; (0, 0), the identity, is legal: every product is then the identity).
+ * Built on the device (2 launches, about 250 dependent doublings) before the call returns. */
+int dehalo_fixed_base_create(dehalo_ctx* ctx, int curve, const uint64_t affine_xy[8], dehalo_fixed_base** out);
+int dehalo_fixed_base_release(dehalo_ctx* ctx, dehalo_fixed_base* fb);
+/* d_out_affine_xy[i] = [d_scalars[i]] P for i < count: affine {x, y} (64 B, (0, 0) for the identity, standard Montgomery), scalars 4 x u64 Montgomery,
+ * both device memory.  count < 2^29; count = 0 returns 0 with the other pointers null.  A null `fb` is DEHALO_ERR_INVALID at every count (the curve comes
+ * from the table), here and in dehalo_fixed_base_blind_device.  Asynchronous on the stream; no workspace. */
+int dehalo_fixed_base_mul_device(dehalo_ctx* ctx, const dehalo_fixed_base* fb, const uint64_t* d_scalars, size_t count, uint64_t* d_out_affine_xy, void* stream);
+/* d_jacobian[i] <- d_jacobian[i] + [d_blinds[i]] P for i < count, in place: the contract of dehalo_blind_commitments_device (Jacobian, 96 B, as
+ * dehalo_msm_device leaves it, z = 0: the identity; one launch queued behind the MSM on the stream) with the table in place of W.  count < 2^29.
+ * Asynchronous on the stream; no workspace. */
+int dehalo_fixed_base_blind_device(dehalo_ctx* ctx, const dehalo_fixed_base* fb, uint64_t* d_jacobian, const uint64_t* d_blinds, size_t count, void* stream);
+
 /* g_to_lagrange [UPSTREAM halo2_proofs/src/poly/commitment.rs, poly/ipa/commitment.rs: best_fft(&mut g, omega_inv, k); g[i] *= n_inv; batch_normalize]:
  * out[i] = [n^-1] sum_j [omega^(-i j)] g[j] over n = 2^k points, omega the 2^k-th root of unity of the curve's scalar field -- the group FFT that takes a
  * commitment key to its Lagrange basis.  Affine {x, y} (64 B, identity = (0, 0), standard Montgomery) in and out, device memory; the output is the
@@ -466,6 +485,9 @@ int dehalo_params_ipa_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, siz
 /* The commitment scheme of params: DEHALO_SCHEME_KZG (dehalo_params_create / _setup / _read) or DEHALO_SCHEME_IPA (dehalo_params_ipa_create / _from_g / _read); < 0 for null. */
 typedef enum { DEHALO_SCHEME_KZG = 0, DEHALO_SCHEME_IPA = 1 } dehalo_scheme;
 int dehalo_params_scheme(const dehalo_params* params);
+/* ParamsIPA's fixed-base table of W (dehalo_fixed_base_*: [blind] W of every commit / commit_lagrange), built once by whichever call made the params; null for
+ * ParamsKZG and for null.  It belongs to the params: valid until dehalo_params_release, never passed to dehalo_fixed_base_release. */
+const dehalo_fixed_base* dehalo_params_fixed_base(const dehalo_params* params);
 int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out);
 size_t dehalo_params_size(const dehalo_params* params);
 int dehalo_params_write(const dehalo_params* params, uint8_t* out, size_t cap);
@@ -577,7 +599,7 @@ size_t dehalo_prover_proof_size(const dehalo_prover* prover);
  *   instances  num_instance_columns arrays of instance_lens[i] scalars (Montgomery); the reference passes none (&[&[&[]]])
  * Errors follow upstream's: DEHALO_ERR_INVALID for instances.len() != num_instance_columns / an instance column longer than the usable
  * rows / a commitment at infinity; DEHALO_ERR_NOT_IN_TABLE when a lookup input is missing from its table.
- * Under ParamsIPA (create_proof::<IPACommitmentScheme<_>, ProverIPA<_>, ..>) every commitment carries its blind ([blind] W, dehalo_blind_commitments_device: one
+ * Under ParamsIPA (create_proof::<IPACommitmentScheme<_>, ProverIPA<_>, ..>) every commitment carries its blind ([blind] W from the table of W, dehalo_fixed_base_blind_device: one
  * launch per phase), the instance columns are committed with Blind::default() and absorbed as points, their evaluations are written first, and the proof ends
  * with ProverIPA's multiopen (x_1, x_2, f, x_3, the q evaluations, x_4) and the opening argument of dehalo_ipa_open on the same transcript and generator. */
 enum { DEHALO_PROOF_ADVICE_ON_DEVICE = 1, DEHALO_PROOF_ADVICE_CANONICAL = 2 /* plain integers < p: converted on the device */ };
