@@ -856,6 +856,18 @@ int dehalo_eval_polynomial_multi_masked_device(dehalo_ctx* ctx, int field, const
     });
 }
 
+int dehalo_eval_polynomial_points_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_polys, size_t count, size_t len, const uint64_t* points,
+                                         uint32_t num_points, const uint32_t* wanted, uint64_t* d_out, void* stream) {
+    if ((count && !d_polys) || !points || !d_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_points: null argument");
+    for (size_t j = 0; j < count; j++)
+        if (!d_polys[j] && len) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_points: null polynomial");
+    if (num_points == 0 || num_points > 32) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_points: 1 to 32 points");
+    if (count >= 65536) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_points: too many polynomials");
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return f.eval_poly_points(ctx, (const fe* const*)d_polys, count, len, points, num_points, (fe*)d_out, s, wanted);
+    });
+}
+
 int dehalo_eval_polynomial(dehalo_ctx* ctx, int field, const uint64_t* coeffs, size_t len, const uint64_t point[4], uint64_t out[4]) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if ((!coeffs && len) || !point || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial: null argument");

@@ -127,16 +127,20 @@ __global__ __launch_bounds__(POLY_THREADS) void k_poly_eval(const fe* coeffs, u6
 // 8 + 16 of k_poly_eval's multiplicative tree, at the same occupancy.  partials[pt][poly][block].
 #define POLY_MP_MAX 4
 struct MultiPoints { fe pt[POLY_MP_MAX]; u32 count; };
+#define POLY_PT_MAX 32                           // k_poly_eval_points: any set of rotations a circuit queries
+struct WidePoints { fe pt[POLY_PT_MAX]; u32 count; };
 // grid (points, levels): block (ip, l) tabulates level l's powers, whose point is x_ip^(2048^l); pw[l][ip][t], level_points[l][ip]
-template <class F>
-__global__ __launch_bounds__(POLY_THREADS) void k_poly_pow_table(MultiPoints P, fe* pw, fe* level_points) {
+// (PTS: MultiPoints, or WidePoints below -- the tables' rows are as many as the struct holds points)
+template <class F, class PTS = MultiPoints>
+__global__ __launch_bounds__(POLY_THREADS) void k_poly_pow_table(PTS P, fe* pw, fe* level_points) {
     typedef typename f29_of<F>::type F9;
+    constexpr u32 MAXP = sizeof(P.pt) / sizeof(fe);
     const u32 t = threadIdx.x, ip = blockIdx.x, lvl = blockIdx.y;
     f29 x = f29_from_std<F9>(P.pt[ip]);
     for (u32 l = 0; l < lvl; l++)
         for (int q = 0; q < 11; q++) x = f29_sqr<F9>(x);                          // x^2048 per level
-    if (t == 0) poly_store<F9>(&level_points[lvl * POLY_MP_MAX + ip], f29_norm(x));
-    pw += (u64)lvl * POLY_MP_MAX * POLY_THREADS;
+    if (t == 0) poly_store<F9>(&level_points[lvl * MAXP + ip], f29_norm(x));
+    pw += (u64)lvl * MAXP * POLY_THREADS;
     f29 base = f29_sqr<F9>(f29_sqr<F9>(f29_sqr<F9>(x)));                        // x^8
     f29 r = f29_one<F9>();
 #pragma unroll
@@ -195,6 +199,78 @@ __global__ __launch_bounds__(POLY_THREADS) void k_poly_eval_multi(PolyPtrs polys
         if (t == 0) {
             f29 r = f29_mul<F9>(sh[0], f29_one<F9>());
             f_store(out, f29_pack(f29_cond_sub(r, F9::P)));
+        }
+    }
+}
+
+// Up to POLY_PT_MAX points (a circuit whose gates query rotations beyond {-1, 0, 1}), the coefficients read ONCE: at level 0 a thread keeps its 8
+// coefficients in registers (as kate_apply_body does) and walks the set bits of the polynomial's mask in groups of at most four -- k_poly_eval_multi's
+// four independent Horner chains, table entry and LDS sum per point -- so a polynomial wanted at nine points crosses HBM once and not three times.
+// Levels >= 1 read every point's own partial sums (LEVEL0 false: nothing to keep).  Same layouts as k_poly_eval_multi with POLY_PT_MAX for POLY_MP_MAX.
+struct PolyPtrsWide { const fe* p[POLY_MP_POLYS]; u32 m[POLY_MP_POLYS]; };            // m: bit i = this polynomial is wanted at point i
+template <class F, bool LEVEL0>
+__global__ __launch_bounds__(POLY_THREADS) void k_poly_eval_points(PolyPtrsWide polys, const fe* coeffs, u64 len, u64 stride, u64 point_stride, u32 npts, const fe* point_ptr,
+                                                                   const fe* pw, fe* partials, u64 partial_stride, u64 partial_point_stride) {
+    typedef typename f29_of<F>::type F9;
+    __shared__ f29 sh[POLY_THREADS];
+    const u32 t = threadIdx.x;
+    const u64 base = (u64)blockIdx.x * POLY_EVAL_TILE + (u64)t * POLY_EVAL_EPT;
+    const u32 want = polys.m[blockIdx.y] & (npts >= 32 ? ~0u : (1u << npts) - 1);           // (uniform in the block)
+    fe* out0 = &partials[(u64)blockIdx.y * partial_stride + blockIdx.x];
+    if (t < npts && !((want >> t) & 1)) f_store(out0 + (u64)t * partial_point_stride, f_zero());      // points nobody asked for
+    const fe* c0 = LEVEL0 ? polys.p[blockIdx.y] : coeffs + (u64)blockIdx.y * stride;
+    f29 c[POLY_EVAL_EPT];
+#pragma unroll
+    for (int j = 0; j < POLY_EVAL_EPT; j++) c[j] = LEVEL0 && base + j < len ? f29_unpack(f_load(&c0[base + j])) : f29_zero();
+    u32 rem = want;
+    while (rem) {
+        u32 ip[POLY_MP_MAX], cnt = 0;
+#pragma unroll
+        for (int i = 0; i < POLY_MP_MAX; i++) {              // the next (up to) four wanted points
+            ip[i] = rem ? (u32)__ffs(rem) - 1 : 0;
+            cnt += rem ? 1 : 0;
+            rem &= rem - 1;
+        }
+        f29 x[POLY_MP_MAX], acc[POLY_MP_MAX];
+#pragma unroll
+        for (int i = 0; i < POLY_MP_MAX; i++) {
+            x[i] = (u32)i < cnt ? f29_from_std<F9>(f_load(&point_ptr[ip[i]])) : f29_zero();
+            acc[i] = f29_zero();
+        }
+#pragma nounroll
+        for (int j = POLY_EVAL_EPT - 1; j >= 0; j--) {       // (rolled, as in k_poly_eval_multi; c turns by one place a round so that no register is indexed by j, and is back in place after the eighth)
+            const f29 top = c[POLY_EVAL_EPT - 1];
+            if (LEVEL0) {
+#pragma unroll
+                for (int q = POLY_EVAL_EPT - 1; q > 0; q--) c[q] = c[q - 1];
+                c[0] = top;
+            }
+#pragma unroll
+            for (int i = 0; i < POLY_MP_MAX; i++) {
+                if ((u32)i >= cnt) continue;
+                f29 cj;
+                if (LEVEL0) cj = top;
+                else cj = base + j < len ? f29_unpack(f_load(&c0[(u64)ip[i] * point_stride + base + j])) : f29_zero();
+                acc[i] = f29_add(f29_mul<F9>(acc[i], x[i]), cj);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < POLY_MP_MAX; i++) {
+            if ((u32)i >= cnt) break;
+            f29 term = f29_mul<F9>(f29_norm(acc[i]), f29_unpack(f_load(&pw[ip[i] * POLY_THREADS + t])));     // < 2p
+            __syncthreads();                                     // the previous point's sums have been read
+            sh[t] = term;
+            __syncthreads();
+            for (u32 d = POLY_THREADS / 2; d >= 1; d >>= 1) {
+                if (t < d) sh[t] = f29_norm(f29_add(sh[t], sh[t + d]));               // < 512 p << 2^261
+                __syncthreads();
+            }
+            if (t == 0) {
+                // < 512 p p / 2^261 + p: up to 5p for the Pasta primes (p just above 2^254, 2^261 mod p just below p), and past 2p once in about seventy
+                // full tiles, whose 256 terms sum to 128 p on average: the full reduction, not one conditional subtraction
+                f29 r = f29_mul<F9>(sh[0], f29_one<F9>());
+                f_store(out0 + (u64)ip[i] * partial_point_stride, f29_to_packed_canon<F9>(r));
+            }
         }
     }
 }
@@ -599,6 +675,58 @@ int eval_poly_multi_t(dehalo_ctx* ctx, const fe* const* d_polys, size_t count, u
             } else {
                 k_poly_eval_multi<F><<<dim3((u32)nb, (u32)cnt), POLY_THREADS, 0, s>>>(pp, cur + first * cur_len, cur_len, cur_len, count * cur_len, npts, lp, lpw, dst + first * (last ? 1 : nb),
                                                                                           last ? 1 : nb, dst_pstride);
+            }
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        cur = dst; cur_len = nb;
+    }
+    return 0;
+}
+
+// eval_poly_multi_t for npts <= POLY_PT_MAX points and 32-bit masks: out[pt][poly]; the level-0 pass reads every polynomial once whatever its mask holds
+template <class F>
+int eval_poly_points_t(dehalo_ctx* ctx, const fe* const* d_polys, size_t count, uint64_t len, const uint64_t* points, uint32_t npts, fe* d_out, hipStream_t s,
+                       const uint32_t* masks) {
+    if (count == 0 || npts == 0) return 0;
+    if (len == 0) {
+        HIP_TRY(ctx, hipMemsetAsync(d_out, 0, (size_t)npts * count * sizeof(fe), s));
+        return 0;
+    }
+    ScopedTimer timer(ctx, s, DEHALO_K_POLY);
+    uint32_t levels = 1;
+    for (uint64_t l = len; l > POLY_EVAL_TILE; l = (l + POLY_EVAL_TILE - 1) / POLY_EVAL_TILE) levels++;
+    if (levels > 4) return dh_fail(ctx, DEHALO_ERR_INVALID, "eval_polynomial_points: polynomial too long");
+    const uint64_t nb0 = (len + POLY_EVAL_TILE - 1) / POLY_EVAL_TILE;
+    const uint64_t nb1 = (nb0 + POLY_EVAL_TILE - 1) / POLY_EVAL_TILE;
+    TRY(dh_ensure(ctx, ctx->ws_poly[0], std::max<size_t>(64, (size_t)npts * count * nb0 * sizeof(fe))));
+    TRY(dh_ensure(ctx, ctx->ws_poly[1], std::max<size_t>(64, (size_t)npts * count * nb1 * sizeof(fe))));
+    TRY(dh_ensure(ctx, ctx->ws_poly[2], (size_t)4 * (POLY_PT_MAX + POLY_PT_MAX * POLY_THREADS) * sizeof(fe)));
+    fe* bufs[2] = {(fe*)ctx->ws_poly[0].p, (fe*)ctx->ws_poly[1].p};
+    fe* lvl_pts = (fe*)ctx->ws_poly[2].p;                     // [level][point]
+    fe* pw = lvl_pts + 4 * POLY_PT_MAX;                       // [level][point][256]
+    WidePoints P{};
+    P.count = npts;
+    for (uint32_t i = 0; i < npts; i++) P.pt[i] = fe_from_u64(points + 4 * i);
+    k_poly_pow_table<F, WidePoints><<<dim3(npts, levels), POLY_THREADS, 0, s>>>(P, pw, lvl_pts);
+    uint64_t cur_len = len;
+    const fe* cur = nullptr;
+    for (uint32_t level = 0; level < levels; level++) {
+        const uint64_t nb = (cur_len + POLY_EVAL_TILE - 1) / POLY_EVAL_TILE;
+        const bool last = level + 1 == levels;
+        fe* dst = last ? d_out : bufs[level & 1];
+        const uint64_t dst_pstride = last ? count : count * nb;       // d_out is [pt][poly]; scratch is [pt][poly][block]
+        const fe* lp = lvl_pts + level * POLY_PT_MAX;
+        const fe* lpw = pw + (uint64_t)level * POLY_PT_MAX * POLY_THREADS;
+        for (size_t first = 0; first < count; first += POLY_MP_POLYS) {
+            PolyPtrsWide pp{};
+            const size_t cnt = std::min<size_t>(POLY_MP_POLYS, count - first);
+            for (size_t j = 0; j < cnt; j++) pp.m[j] = masks ? masks[first + j] : ~0u;
+            if (level == 0) {
+                for (size_t j = 0; j < cnt; j++) pp.p[j] = d_polys[first + j];
+                k_poly_eval_points<F, true><<<dim3((u32)nb, (u32)cnt), POLY_THREADS, 0, s>>>(pp, nullptr, cur_len, 0, 0, npts, lp, lpw, dst + first * (last ? 1 : nb), last ? 1 : nb, dst_pstride);
+            } else {
+                k_poly_eval_points<F, false><<<dim3((u32)nb, (u32)cnt), POLY_THREADS, 0, s>>>(pp, cur + first * cur_len, cur_len, cur_len, count * cur_len, npts, lp, lpw,
+                                                                                                 dst + first * (last ? 1 : nb), last ? 1 : nb, dst_pstride);
             }
         }
         HIP_TRY(ctx, hipGetLastError());

@@ -48,10 +48,12 @@ struct dehalo_prover {
     // the usable rows and the tuple's multiplicity, on the device; count 0: not such a table, or more distinct rows than the permutation's one-tile path takes
     struct TableRows { DevArray<uint32_t> d_rep, d_mult; uint32_t count = 0; };
     // opening plan (depends on the circuit only)
+    static constexpr size_t MAX_ROTATIONS = 32;
     std::vector<int32_t> rots;
     std::vector<const uint64_t*> plist;
     std::vector<int64_t> write_idx;
-    std::vector<uint8_t> eval_wanted;      // per polynomial of plist: the rotations (bits, in `rots` order) anyone reads its value at
+    std::vector<uint32_t> eval_wanted;     // per polynomial of plist: the rotations (bits, in `rots` order) anyone reads its value at
+    std::vector<uint8_t> eval_wanted8;     // the same as bytes, for the four-point evaluation (at most four rotations)
     struct Group { int32_t rot; std::vector<const uint64_t*> ptrs; std::vector<int64_t> idx; };
     std::vector<Group> groups;
     std::vector<const uint64_t*> hp_ptrs;
@@ -145,7 +147,8 @@ struct dehalo_prover {
         if (ipa) for (auto& q : cs.instance_q) rs.push_back(q.rotation);      // QUERY_INSTANCE = true
         std::sort(rs.begin(), rs.end());
         rs.erase(std::unique(rs.begin(), rs.end()), rs.end());
-        if (rs.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more than four distinct opening rotations");      // (the multi-point evaluation's pass takes four)
+        if (rs.size() > MAX_ROTATIONS)      // (the evaluation's masks are 32 bits wide; rs holds the prover's own four rotations too)
+            return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, std::to_string(rs.size()) + " distinct opening rotations: more than " + std::to_string(MAX_ROTATIONS));
         rots = rs;
         const size_t nfix = cs.num_fixed, npc = cs.perm_cols.size();
         hp_ptrs.clear();
@@ -213,7 +216,6 @@ struct dehalo_prover {
             g->ptrs.push_back(q.ptr);
             g->idx.push_back(q.i);
         }
-        if (!ipa && groups.size() > 4) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "more opening points than the prover's buffers hold");      // (GWC: qbuf / wbuf)
         ipa_inst_write.clear();
         if (ipa) {
             // the queries in upstream's order: the instance columns' (default blind) in front of the others
@@ -249,11 +251,13 @@ struct dehalo_prover {
         hpiece0 = (size_t)idx(b_hp, 0, 0);
         eval_count = rots.size() * ntot;
         eval_wanted.assign(ntot, 0);
-        auto want = [&](int64_t i) { if (i >= 0) eval_wanted[(size_t)i % ntot] |= (uint8_t)(1u << ((size_t)i / ntot)); };
+        auto want = [&](int64_t i) { if (i >= 0) eval_wanted[(size_t)i % ntot] |= 1u << ((size_t)i / ntot); };
         for (int64_t i : write_idx) want(i);
         for (int64_t i : ipa_inst_write) want(i);
         for (auto& g : groups) for (int64_t i : g.idx) want(i);
         for (uint32_t i = 0; i < pieces; i++) want((int64_t)hpiece0 + i);                // the pieces of h at x: the folded quotient's value
+        eval_wanted8.clear();
+        if (rots.size() <= 4) eval_wanted8.assign(eval_wanted.begin(), eval_wanted.end());
         return 0;
     }
 
@@ -285,10 +289,6 @@ struct dehalo_prover {
         TRY(h.alloc(ctx, m));
         TRY(table_value.alloc(ctx, (size_t)std::max<uint32_t>(L, 1) * m));
         TRY(hfold.alloc(ctx, n));
-        TRY(qbuf.alloc(ctx, 4 * n));
-        TRY(wbuf.alloc(ctx, 4 * n));
-        const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, 8), std::max<uint32_t>(I, pieces));      // the most points one phase commits
-        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
         // blinding values of a proof but the random polynomial, compacted: [advice rows | permuted rows | product rows]
         const size_t rows = n - u;
         TRY(blind_dev.alloc(ctx, std::max<size_t>(1, (size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf)));
@@ -299,6 +299,12 @@ struct dehalo_prover {
         TRY(find_table_rows());
         TRY(build_product_graphs());
         TRY(opening_plan());
+        // GWC: one folded polynomial and one witness per opening point (at least the four every circuit has)
+        const size_t ngroups = std::max<size_t>(4, groups.size());
+        TRY(qbuf.alloc(ctx, ngroups * n));
+        TRY(wbuf.alloc(ctx, ngroups * n));
+        const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, (uint32_t)std::max<size_t>(8, groups.size())), std::max<uint32_t>(I, pieces));      // the most points one phase commits
+        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
         if (ipa) {      // the multiopen's buffers, sized from the constraint system: one polynomial per point set, twice more for the division chain
             const size_t ns = ipa_sets.size();
             TRY(ipa_q.alloc(ctx, ns * n));
@@ -883,8 +889,12 @@ struct ProofRun {
     int evaluations() {
         point.resize(p.rots.size());
         for (size_t i = 0; i < p.rots.size(); i++) point[i] = d.rotate_omega(x, p.rots[i]);
-        TRY(dehalo_eval_polynomial_multi_masked_device(ctx, fid, p.plist.data(), p.plist.size(), n, (const uint64_t*)point.data(), (uint32_t)p.rots.size(), p.eval_wanted.data(),
-                                                       p.evals.u64(), nullptr));
+        if (p.rots.size() <= 4)
+            TRY(dehalo_eval_polynomial_multi_masked_device(ctx, fid, p.plist.data(), p.plist.size(), n, (const uint64_t*)point.data(), (uint32_t)p.rots.size(), p.eval_wanted8.data(),
+                                                           p.evals.u64(), nullptr));
+        else      // gates that query rotations beyond {-1, 0, 1}: up to 32 points, every polynomial still read once
+            TRY(dehalo_eval_polynomial_points_device(ctx, fid, p.plist.data(), p.plist.size(), n, (const uint64_t*)point.data(), (uint32_t)p.rots.size(), p.eval_wanted.data(),
+                                                     p.evals.u64(), nullptr));
         // the folded quotient h(X) = sum_i x^(n i) h_i(X) (opened below; its value at x comes from the pieces' values)
         xs = powers(f, f->pow_u64(x, (uint64_t)n), pieces);
         TRY(dehalo_lincomb_device(ctx, fid, p.hp_ptrs.data(), (const uint64_t*)xs.data(), pieces, n, p.hfold.u64(), nullptr, nullptr));
@@ -968,7 +978,8 @@ struct ProofRun {
     int open_gwc() {
         const Fe v = tr->squeeze();
         p.tk("v");
-        HIP_TRY(ctx, hipMemsetAsync(p.wbuf.p, 0, 4 * n * 32, ms));
+        const size_t ng = p.groups.size();
+        HIP_TRY(ctx, hipMemsetAsync(p.wbuf.p, 0, std::max<size_t>(4, ng) * n * 32, ms));
         std::vector<const uint64_t*> qptrs;
         std::vector<uint64_t*> wptrs;
         std::vector<Fe> qpoints;
@@ -983,8 +994,9 @@ struct ProofRun {
             wptrs.push_back(p.wbuf.u64(gi * n));
             qpoints.push_back(point[(size_t)(std::find(p.rots.begin(), p.rots.end(), g.rot) - p.rots.begin())]);
         }
-        TRY(dehalo_kate_division_batch_device(ctx, fid, qptrs.data(), n, (const uint64_t*)qpoints.data(), wptrs.data(), p.groups.size(), nullptr));
-        return p.commit(tr, p.wbuf.p, p.groups.size(), false);
+        for (size_t first = 0; first < ng; first += 8)      // (the batched division takes eight at a time); the witnesses are committed in one MSM
+            TRY(dehalo_kate_division_batch_device(ctx, fid, qptrs.data() + first, n, (const uint64_t*)(qpoints.data() + first), wptrs.data() + first, std::min<size_t>(8, ng - first), nullptr));
+        return p.commit(tr, p.wbuf.p, ng, false);
     }
 
     void finish() {

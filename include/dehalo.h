@@ -301,6 +301,11 @@ int dehalo_eval_polynomial_multi_device(dehalo_ctx* ctx, int field, const uint64
  * is wanted at point i.  The other entries of d_out are written as zero and cost nothing (a proof asks for about 60 of its 47 x 4 values). */
 int dehalo_eval_polynomial_multi_masked_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_polys, size_t count, size_t len, const uint64_t* points,
                                                uint32_t num_points, const uint8_t* wanted, uint64_t* d_out, void* stream);
+/* Any set of rotations a circuit queries: 1..32 points, wanted[j] (host, one 32-bit mask per polynomial; NULL = everything) with bit i set when polynomial j is
+ * wanted at point i.  d_out[point][polynomial][4], the pairs nobody wants written as zero.  Every polynomial's coefficients are read once however many points
+ * its mask holds (a block keeps its tile in registers and takes the points four at a time).  DEHALO_ERR_INVALID for 0 or more than 32 points. */
+int dehalo_eval_polynomial_points_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_polys, size_t count, size_t len, const uint64_t* points,
+                                         uint32_t num_points, const uint32_t* wanted, uint64_t* d_out, void* stream);
 int dehalo_batch_invert(dehalo_ctx* ctx, int field, uint64_t* values, size_t len);
 int dehalo_batch_invert_device(dehalo_ctx* ctx, int field, uint64_t* d_values, size_t len, void* stream);
 int dehalo_prefix_product_device(dehalo_ctx* ctx, int field, const uint64_t* d_in, size_t len, uint64_t* d_out, void* stream);
@@ -585,8 +590,8 @@ int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t
  * the same device; work no transcript challenge waits for (lagrange_to_coeff / coeff_to_extended of a phase's columns, the random
  * polynomial's commitment, the gate and table-value passes of evaluate_h) is queued there and runs beside the commitment phases.
  * Several provers over one key, each on its own context(s), may run concurrently from different threads (batch proving).
- * `params` decides the scheme: ParamsKZG -> ProverGWC, ParamsIPA (Pallas / Vesta) -> ProverIPA.  DEHALO_ERR_UNSUPPORTED: more than four distinct
- * opening rotations (either scheme), more than four opening points (KZG). */
+ * `params` decides the scheme: ParamsKZG -> ProverGWC, ParamsIPA (Pallas / Vesta) -> ProverIPA.  DEHALO_ERR_UNSUPPORTED: more than 32 distinct
+ * rotations among the circuit's queries and the prover's own {0, 1, -1, -(blinding_factors + 1)} (either scheme). */
 int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out);
 int dehalo_prover_release(dehalo_prover* prover);
 /* Byte length of one proof of this prover (its params' scheme, instance commitments and evaluations included); 0 for null.
