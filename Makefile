@@ -16,7 +16,7 @@ ifdef EXPERIMENTS
 HIPFLAGS += -DDEHALO_EXPERIMENTS
 endif
 LIB ?= $(PKG)/libdehalo.so
-UNITS := capi params keygen prover witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
+UNITS := capi params keygen prover check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
 OBJS := $(UNITS:%=$(OBJDIR)/%.o)
 HDRS := $(wildcard $(CSRC)/*.cuh) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hpp) include/dehalo.h
 

@@ -67,6 +67,24 @@ impl<'c> DehaloProvingKey<'c> {
     pub fn set_transcript_repr(&mut self, repr: &Fr) -> Result<(), DehaloError> {
         self.ctx.check(unsafe { sys::dehalo_pk_set_transcript_repr(self.raw, repr as *const Fr as *const u64) })
     }
+
+    /// `MockProver::run(k, &circuit, instances)?.verify()` over this key, on the device (`dehalo_check_witness`): `advice` and `instances` as `create_proof` takes
+    /// them, `mapping` = keygen's permutation assembly (`None`: the copy constraints are not checked).  Returns the exact totals and the first `cap` failures in
+    /// `(kind, index, row)` order: `DEHALO_CHECK_GATE` indexes `cs.gates().flat_map(polynomials)`, `DEHALO_CHECK_LOOKUP` `cs.lookups()`, `DEHALO_CHECK_COPY`
+    /// `cs.permutation().get_columns()`; the witness satisfies the circuit when the three totals are zero.  Naming a failure (gate name, region, offset) is the
+    /// caller's, from its own `ConstraintSystem` and layouter.
+    pub fn mock_verify(&self, advice: &[Fr], instances: &[&[Fr]], mapping: Option<&[u64]>, cap: usize) -> Result<(sys::dehalo_check_report, Vec<sys::dehalo_check_failure>), DehaloError> {
+        let inst_ptrs: Vec<*const u64> = instances.iter().map(|c| c.as_ptr() as *const u64).collect();
+        let inst_lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
+        let mut report: sys::dehalo_check_report = unsafe { core::mem::zeroed() };
+        let mut failures: Vec<sys::dehalo_check_failure> = Vec::with_capacity(cap);
+        self.ctx.check(unsafe {
+            sys::dehalo_check_witness(self.ctx.as_ptr(), self.raw, advice.as_ptr() as *const u64, inst_ptrs.as_ptr(), inst_lens.as_ptr(), inst_ptrs.len() as u32,
+                                      mapping.map_or(core::ptr::null(), |m| m.as_ptr()), 0, if cap == 0 { core::ptr::null_mut() } else { failures.as_mut_ptr() }, cap, &mut report)
+        })?;
+        unsafe { failures.set_len(report.written as usize) };
+        Ok((report, failures))
+    }
 }
 
 impl Drop for DehaloProvingKey<'_> {

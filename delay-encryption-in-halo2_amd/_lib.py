@@ -34,6 +34,7 @@ SYMBOLS = [
     "dehalo_g_to_lagrange_device", "dehalo_params_ipa_from_g", "dehalo_params_ipa_size", "dehalo_params_ipa_write", "dehalo_params_ipa_read",
     "dehalo_fixed_base_create", "dehalo_fixed_base_release", "dehalo_fixed_base_mul_device", "dehalo_fixed_base_blind_device", "dehalo_params_fixed_base",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
+    "dehalo_check_witness",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -107,6 +108,15 @@ class CProductInputs(C.Structure):
     _fields_ = [("columns", C.POINTER(C.c_void_p)), ("sigma", C.POINTER(C.c_void_p)), ("num_columns", C.c_uint32), ("chunk_len", C.c_uint32), ("omega_powers", C.c_void_p),
                 ("beta", C.c_void_p), ("gamma", C.c_void_p), ("delta", C.c_void_p), ("set_factors", C.c_void_p), ("compressed_input", C.POINTER(C.c_void_p)),
                 ("compressed_table", C.POINTER(C.c_void_p)), ("permuted_input", C.POINTER(C.c_void_p)), ("permuted_table", C.POINTER(C.c_void_p)), ("num_lookups", C.c_uint32)]
+
+
+class CCheckFailure(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("index", C.c_uint32), ("row", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CCheckReport(C.Structure):
+    _fields_ = [("gate_failures", C.c_uint64), ("lookup_failures", C.c_uint64), ("copy_failures", C.c_uint64), ("rows", C.c_uint64), ("lookup_inputs", C.c_uint64),
+                ("cells_in_cycles", C.c_uint64), ("written", C.c_uint64)]
 
 
 class DehaloError(RuntimeError):
@@ -268,6 +278,7 @@ def load_library():
     lib.dehalo_prover_create.argtypes = [P, P, P, P, PP]
     lib.dehalo_prover_release.argtypes = [P]
     lib.dehalo_create_proof.argtypes = [P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P, u32]
+    lib.dehalo_check_witness.argtypes = [P, P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u64p, u32, C.POINTER(CCheckFailure), sz, C.POINTER(CCheckReport)]
     lib.dehalo_create_proof_circuit.argtypes = [P, C.POINTER(CCircuitInputs), C.POINTER(CSynthesisInfo), C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P]
     lib.dehalo_create_proofs_circuit.argtypes = [C.POINTER(C.c_void_p), u32, C.POINTER(CCircuitInputs), u32, C.POINTER(CRng), C.POINTER(C.c_void_p), sz, C.POINTER(sz)]
     lib.dehalo_prover_last_timings.argtypes = [P, C.POINTER(C.c_double)]

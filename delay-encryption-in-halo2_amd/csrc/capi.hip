@@ -36,7 +36,9 @@ int unknown_curve(dehalo_ctx* ctx) { return dh_fail(ctx, DEHALO_ERR_INVALID, "un
 // live in LDS, the rest in an HBM scratch column).
 int compile_graph(dehalo_ctx* ctx, dehalo_graph* g, const int32_t* rotations, uint32_t num_rotations, const dehalo_calculation* calcs, uint32_t num_calcs,
                   const dehalo_source* parts, uint32_t num_parts, uint32_t num_intermediates, std::vector<DevCalc>& out_calcs, std::vector<DevSrc>& out_parts,
-                  bool propagate = true) {
+                  bool propagate = true, const uint32_t* root_of = nullptr, std::vector<uint32_t>* out_root_of = nullptr) {
+    // root_of (a checking program, dh_graph_create_roots): per calculation the root it is, or NEVER.  Such a calculation survives the copy
+    // propagation, and out_root_of says where it went.
     const uint32_t NEVER = 0xffffffffu;
     if (propagate) {
         // Copy propagation.  Upstream's GraphEvaluator::add_expression wraps EVERY column query in Calculation::Store(source) so that its
@@ -56,6 +58,7 @@ int compile_graph(dehalo_ctx* ctx, dehalo_graph* g, const int32_t* rotations, ui
         std::vector<int> aliased(num_intermediates, 0);
         std::vector<dehalo_source> alias(num_intermediates);
         std::vector<dehalo_calculation> cc;
+        std::vector<uint32_t> cc_root;
         std::vector<dehalo_source> pp(parts, parts + num_parts);
         auto sub = [&](dehalo_source s) { return (s.kind == DEHALO_SRC_INTERMEDIATE && aliased[s.index]) ? alias[s.index] : s; };
         for (uint32_t i = 0; i < num_calcs; i++) {
@@ -64,14 +67,17 @@ int compile_graph(dehalo_ctx* ctx, dehalo_graph* g, const int32_t* rotations, ui
             c.b = sub(c.b);
             if (c.op == DEHALO_CALC_HORNER)
                 for (uint32_t k = 0; k < c.parts_len; k++) pp[c.parts_begin + k] = sub(pp[c.parts_begin + k]);
-            if (c.op == DEHALO_CALC_STORE && c.a.kind != DEHALO_SRC_INTERMEDIATE && i + 1 != num_calcs && defs[c.target] == 1) {
+            const bool is_root = root_of && root_of[i] != NEVER;
+            if (!is_root && c.op == DEHALO_CALC_STORE && c.a.kind != DEHALO_SRC_INTERMEDIATE && i + 1 != num_calcs && defs[c.target] == 1) {
                 aliased[c.target] = 1;
                 alias[c.target] = c.a;
                 continue;
             }
             cc.push_back(c);
+            if (root_of) cc_root.push_back(root_of[i]);
         }
         g->num_calcs = (uint32_t)cc.size();
+        if (out_root_of) *out_root_of = cc_root;
         return compile_graph(ctx, g, rotations, num_rotations, cc.data(), (uint32_t)cc.size(), pp.data(), num_parts, num_intermediates, out_calcs, out_parts, false);
     }
     std::vector<uint32_t> last_use(num_intermediates, NEVER), first_def(num_intermediates, NEVER);
@@ -276,6 +282,8 @@ const IpaOps* ipa_ops(int curve) {
     if (curve == DEHALO_CURVE_VESTA) return &vesta_ipa_ops();
     return nullptr;
 }
+
+const FieldOps* dh_field_ops(int field) { return field_ops(field); }
 
 const GfftOps* gfft_ops(int curve) {
     static const GfftOps* const ops[] = {&bn254_gfft_ops(), &pallas_gfft_ops(), &vesta_gfft_ops()};
@@ -1070,9 +1078,9 @@ int dehalo_permute_expression_pair(dehalo_ctx* ctx, int field, const uint64_t* i
 }
 
 // ---- quotient numerator (evalh.cuh) -----------------------------------------------------------------
-int dehalo_graph_create(dehalo_ctx* ctx, int field, const uint64_t* constants, uint32_t num_constants, const int32_t* rotations, uint32_t num_rotations,
-                        const dehalo_calculation* calcs, uint32_t num_calcs, const dehalo_source* horner_parts, uint32_t num_horner_parts,
-                        uint32_t num_intermediates, dehalo_graph** out) {
+static int graph_create_impl(dehalo_ctx* ctx, int field, const uint64_t* constants, uint32_t num_constants, const int32_t* rotations, uint32_t num_rotations,
+                             const dehalo_calculation* calcs, uint32_t num_calcs, const dehalo_source* horner_parts, uint32_t num_horner_parts,
+                             uint32_t num_intermediates, const uint32_t* root_of, uint32_t num_roots, dehalo_graph** out) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (!out || (num_constants && !constants) || (num_rotations && !rotations) || (num_calcs && !calcs) || (num_horner_parts && !horner_parts))
         return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_create: null argument");
@@ -1086,16 +1094,28 @@ int dehalo_graph_create(dehalo_ctx* ctx, int field, const uint64_t* constants, u
         g->field = field; g->num_calcs = num_calcs; g->num_parts = num_horner_parts; g->num_constants = num_constants;
         std::vector<DevCalc> dc;
         std::vector<DevSrc> dp;
-        TRY(compile_graph(ctx, g.get(), rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, dc, dp));
+        std::vector<uint32_t> roots;
+        TRY(compile_graph(ctx, g.get(), rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, dc, dp, true, root_of, &roots));
         TRY(g->d_calcs.alloc(ctx, std::max<size_t>(1, dc.size()), false));
         TRY(g->d_parts.alloc(ctx, dp.size(), false));
         TRY(g->d_constants.alloc(ctx, std::max<size_t>(1, num_constants), false));
         if (!dc.empty()) HIP_TRY(ctx, hipMemcpy(g->d_calcs.p, dc.data(), dc.size() * sizeof(DevCalc), hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(g->d_parts.p, dp.data(), dp.size() * sizeof(DevSrc), hipMemcpyHostToDevice));
+        if (root_of) {
+            g->num_roots = num_roots;
+            TRY(g->d_root_of.alloc(ctx, std::max<size_t>(1, roots.size()), false));
+            if (!roots.empty()) HIP_TRY(ctx, hipMemcpy(g->d_root_of.p, roots.data(), roots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
         TRY(f->graph_upload(ctx, g.get(), constants, ctx->stream.get()));
         *out = g.release();
         return 0;
     });
+}
+
+int dehalo_graph_create(dehalo_ctx* ctx, int field, const uint64_t* constants, uint32_t num_constants, const int32_t* rotations, uint32_t num_rotations,
+                        const dehalo_calculation* calcs, uint32_t num_calcs, const dehalo_source* horner_parts, uint32_t num_horner_parts,
+                        uint32_t num_intermediates, dehalo_graph** out) {
+    return graph_create_impl(ctx, field, constants, num_constants, rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, nullptr, 0, out);
 }
 
 int dehalo_graph_release(dehalo_ctx* ctx, dehalo_graph* g) {
@@ -1252,3 +1272,12 @@ int dehalo_msm_last_shape(dehalo_ctx* ctx, uint32_t out[6]) {
 }
 
 }  // extern "C"
+
+// A checking program (check.cuh k_graph_check): calculation i with root_of[i] != 0xffffffff is root root_of[i] -- its value is tested, not kept.
+int dh_graph_create_roots(dehalo_ctx* ctx, int field, const uint64_t* constants, uint32_t num_constants, const int32_t* rotations, uint32_t num_rotations,
+                          const dehalo_calculation* calcs, uint32_t num_calcs, const dehalo_source* horner_parts, uint32_t num_horner_parts, uint32_t num_intermediates,
+                          const uint32_t* root_of, uint32_t num_roots, dehalo_graph** out) {
+    if (ctx && num_calcs && !root_of) return dh_fail(ctx, DEHALO_ERR_INVALID, "graph_create: null root table");
+    return graph_create_impl(ctx, field, constants, num_constants, rotations, num_rotations, calcs, num_calcs, horner_parts, num_horner_parts, num_intermediates, root_of,
+                             num_roots, out);
+}

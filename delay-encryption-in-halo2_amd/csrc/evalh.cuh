@@ -448,11 +448,10 @@ inline int evh_stage_ptrs(dehalo_ctx* ctx, const std::vector<const fe*>& ptrs, c
     return 0;
 }
 
+// stages one program's scalar table and column pointers (ws_evh[0], ws_evh[2]; the spill columns in ws_evh[3]) and fills everything of A but previous / out
 template <class F>
-int graph_evaluate_t(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale, const fe* d_previous,
-                     fe* d_out, hipStream_t s) {
+int evh_prepare(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale, hipStream_t s, EvhArgs& A) {
     const u64 rows = 1ull << log_rows;
-    ScopedTimer timer(ctx, s, DEHALO_K_EVAL_H);
     // scalar table: [beta, gamma, theta, y, constants..., challenges...]
     const u32 nsc = 4 + g->num_constants + in->num_challenges;
     TRY(dh_ensure(ctx, ctx->ws_evh[0], (size_t)(nsc + 8) * sizeof(fe)));
@@ -482,14 +481,25 @@ int graph_evaluate_t(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_i
         TRY(evh_stage_scalars<F>(ctx, chal, table + 4 + g->num_constants, s));
         TRY(evh_stage_ptrs(ctx, cols, (const void**)ctx->ws_evh[2].p, s));
     }
-    EvhArgs A{};
+    A = EvhArgs{};
     A.columns = (const fe* const*)ctx->ws_evh[2].p;
     if (g->hbm_slots) TRY(dh_ensure(ctx, ctx->ws_evh[3], (size_t)g->hbm_slots * rows * sizeof(fe)));
     A.calcs = g->d_calcs.p; A.parts = g->d_parts.p; A.scalars = table;
     A.num_calcs = g->num_calcs; A.fixed_base = 0; A.advice_base = in->num_fixed; A.instance_base = in->num_fixed + in->num_advice;
     A.rows_mask = (u32)(rows - 1); A.rot_scale = rot_scale;
-    A.previous = d_previous; A.out = d_out; A.spill = (fe*)ctx->ws_evh[3].p; A.rows = rows; A.result = g->result;
+    A.spill = (fe*)ctx->ws_evh[3].p; A.rows = rows; A.result = g->result;
     A.cols_internal = in->form_flags & DEHALO_EVAL_COLUMNS_INTERNAL; A.vals_internal = in->form_flags & DEHALO_EVAL_VALUES_INTERNAL;
+    return 0;
+}
+
+template <class F>
+int graph_evaluate_t(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint32_t rot_scale, const fe* d_previous,
+                     fe* d_out, hipStream_t s) {
+    const u64 rows = 1ull << log_rows;
+    ScopedTimer timer(ctx, s, DEHALO_K_EVAL_H);
+    EvhArgs A;
+    TRY(evh_prepare<F>(ctx, g, in, log_rows, rot_scale, s, A));
+    A.previous = d_previous; A.out = d_out;
     const size_t lds = (size_t)std::max<u32>(1, g->lds_slots) * EVH_SLOT_BYTES;
     if (lds > 48 * 1024)   // per call: the attribute belongs to the device the context is bound to
         HIP_TRY(ctx, dh_func_lds(ctx, (const void*)k_graph_eval<F>, EVH_LDS_BYTES));
@@ -668,6 +678,8 @@ int convert_form_t(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_in
     return 0;
 }
 
+#include "check.cuh"
+
 // the per-field table (internal.hpp FieldOps), in its members' order
 template <class F>
 constexpr FieldOps make_field_ops() {
@@ -675,5 +687,5 @@ constexpr FieldOps make_field_ops() {
             &eval_poly_t<F>, &eval_poly_multi_t<F>, &eval_poly_points_t<F>, &batch_invert_t<F>, &prefix_product_one_t<F>, &grand_product_t<F>, &lincomb_t<F>, &scale_t<F>,
             &kate_division_t<F>, &kate_division_batch_t<F>,
             &convert_form_t<F>, &graph_upload_t<F>, &graph_evaluate_t<F>, &graph_evaluate_batch_t<F>, &perm_h_t<F>, &lookup_h_t<F>, &lookup_h_batch_t<F>,
-            &product_terms_t<F>};
+            &product_terms_t<F>, &graph_check_t<F>, &check_member_t<F>};
 }

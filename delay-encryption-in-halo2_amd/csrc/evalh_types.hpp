@@ -34,5 +34,8 @@ struct dehalo_graph {
     DevArray<DevSrc> d_parts;
     DevArray<fe> d_constants;        // internal packed form
     DevSrc result;          // where the last calculation's value lives
+    // a checking program (dh_graph_create_roots) only: per calculation the root whose value it computes, or 0xffffffff
+    uint32_t num_roots = 0;
+    DevArray<uint32_t> d_root_of;
 };
 

@@ -58,7 +58,7 @@ struct dehalo_ctx {
     std::recursive_mutex mu;   // recursive: host-buffer entry points hold it across their device-form calls
     // workspace (grow-only)
     DevBuf ws_scalars, ws_out, ws_count, ws_counters, ws_off, ws_records, ws_merge_lists, ws_merge_parts, ws_bhist, ws_pcount, ws_pairs, ws_bsum, ws_idx, ws_partial0, ws_buckets,
-        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft;
+        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3];
     std::vector<TwiddleEntry> twiddles;
     affine_t* msm_affine_out = nullptr;   // set for the duration of dehalo_msm_device_affine (under mu): k_msm_final also writes affine points
     int msm_acc_points = 48; // > 0: the accumulation's grid is 4, 6, 8, ... layers of one wave per SIMD, the fewest that leave a lane <= this many
@@ -369,7 +369,17 @@ struct FieldOps {
     int (*lookup_h)(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);
     int (*lookup_h_batch)(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);
     int (*product_terms)(dehalo_ctx* ctx, const dehalo_product_inputs* in, uint64_t n, fe* num, fe* den, uint64_t stride, hipStream_t s);
+    // witness check (check.cuh): bitmap[root][row / 64] bit row % 64 = "root's value is non-zero at row", rows >= usable masked; words = 64-bit words per root
+    int (*graph_check)(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint64_t usable, uint64_t* bitmap, uint64_t words,
+                       hipStream_t s);
+    // bitmap[row / 64] bit row % 64 = "input[row] (standard form) is none of the n_keys sorted canonical keys", rows >= usable masked; every word of 2^log_rows rows written
+    int (*check_member)(dehalo_ctx* ctx, const fe* input, const fe* sorted_keys, uint64_t n_keys, uint32_t log_rows, uint64_t usable, uint64_t* bitmap, hipStream_t s);
 };
+const FieldOps* dh_field_ops(int field);      // capi.hip: null for an unknown field
+// capi.hip: dehalo_graph_create for a checking program -- calculation i with root_of[i] != 0xffffffff computes root root_of[i] (kept by the copy propagation)
+int dh_graph_create_roots(dehalo_ctx* ctx, int field, const uint64_t* constants, uint32_t num_constants, const int32_t* rotations, uint32_t num_rotations,
+                          const dehalo_calculation* calcs, uint32_t num_calcs, const dehalo_source* horner_parts, uint32_t num_horner_parts, uint32_t num_intermediates,
+                          const uint32_t* root_of, uint32_t num_roots, dehalo_graph** out);
 const FieldOps& bn254_fr_field_ops();
 const FieldOps& bn254_fq_field_ops();
 const FieldOps& pasta_fp_field_ops();
@@ -384,3 +394,6 @@ int lookup_permute_impl(dehalo_ctx* ctx, int field, const fe* d_inputs, const fe
 struct LookupDistinct { const uint32_t* d_rep_rows; const uint32_t* d_mult; uint32_t count; };
 int lookup_permute_ptrs(dehalo_ctx* ctx, int field, const fe* const* d_inputs, const fe* const* d_tables, uint64_t n, size_t batch, fe* const* d_out_inputs,
                         fe* const* d_out_tables, hipStream_t s, int* d_status = nullptr, const LookupDistinct* distinct = nullptr);
+// The first n values of `count` <= 16 table columns (standard form) as canonical keys sorted ascending (the tile sort and merge passes of the permutation), in the
+// context's lookup workspace: column t at *d_sorted + t * *npad, padded to whole tiles with all-ones keys.  Valid until the next call that uses that workspace.
+int lookup_sort_tables(dehalo_ctx* ctx, int field, const fe* const* d_tables, uint32_t count, uint64_t n, const fe** d_sorted, uint64_t* npad, hipStream_t s);

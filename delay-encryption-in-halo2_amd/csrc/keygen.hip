@@ -101,6 +101,8 @@ int dehalo_pk::compile_graphs() {
         TRY(compress_graph(cs, lk.tables, f).compile(ctx, adopt(ctx, gt)));
         compress_graphs.emplace_back(std::move(gi), std::move(gt));
     }
+    const GateCheckProgram chk = gate_check_graph(cs, f);
+    TRY(chk.g.compile(ctx, adopt(ctx, check_gates), &chk.root_of, (uint32_t)cs.gates.size()));
     return 0;
 }
 

@@ -684,7 +684,43 @@ int lp_run(dehalo_ctx* ctx, const LpCols& c, u32 B, u32 U, u64 n, hipStream_t s,
     return 0;
 }
 
+// the sort alone: canonical keys of U table columns, tile sort, merge passes
+template <class F>
+int lp_sort_only(dehalo_ctx* ctx, const LpCols& c, u32 U, u64 n, const fe** d_sorted, u64* npad_out, hipStream_t s) {
+    const u64 tiles = (n + LP_TILE - 1) / LP_TILE, npad = tiles * LP_TILE;
+    const size_t half = ((size_t)U * npad * sizeof(fe) + 255) & ~(size_t)255;
+    TRY(dh_ensure(ctx, ctx->ws_lookup, 2 * half));
+    fe* k0 = (fe*)ctx->ws_lookup.p;
+    fe* k1 = (fe*)((char*)ctx->ws_lookup.p + half);
+    const int lds_keys = LP_TILE * 32;
+    HIP_TRY(ctx, dh_func_lds(ctx, (const void*)k_lp_tile_sort, lds_keys));
+    fe *src = k1, *dst = k0;
+    k_lp_canon_tables<F><<<dim3((u32)((npad + 255) / 256), U), 256, 0, s>>>(c, n, npad, k0);
+    k_lp_tile_sort<<<dim3((u32)tiles, U), LP_SORT_THREADS, lds_keys, s>>>(k0, k1, npad);
+    for (u64 run = LP_TILE; run < npad; run <<= 1) {
+        k_lp_merge<<<dim3((u32)(npad / LP_MERGE_OUT), U), LP_MERGE_THREADS, 0, s>>>(src, dst, npad, run);
+        std::swap(src, dst);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    *d_sorted = src;
+    *npad_out = npad;
+    return 0;
+}
+
 }  // namespace
+
+int lookup_sort_tables(dehalo_ctx* ctx, int field, const fe* const* d_tables, uint32_t count, uint64_t n, const fe** d_sorted, uint64_t* npad, hipStream_t s) {
+    if (n == 0 || n >= (1ull << 31) || count == 0 || count > LP_MAX_BATCH) return dh_fail(ctx, DEHALO_ERR_INVALID, "lookup_sort_tables: bad shape");
+    LpCols c{};
+    for (u32 t = 0; t < count; t++) c.tab[t] = d_tables[t];
+    switch (field) {
+        case DEHALO_FIELD_BN254_FR: return lp_sort_only<Bn254Fr>(ctx, c, count, n, d_sorted, npad, s);
+        case DEHALO_FIELD_BN254_FQ: return lp_sort_only<Bn254Fq>(ctx, c, count, n, d_sorted, npad, s);
+        case DEHALO_FIELD_PASTA_FP: return lp_sort_only<PastaFp>(ctx, c, count, n, d_sorted, npad, s);
+        case DEHALO_FIELD_PASTA_FQ: return lp_sort_only<PastaFq>(ctx, c, count, n, d_sorted, npad, s);
+        default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
+    }
+}
 
 // `batch` lookups at once, given as pointer lists: lookups whose table pointers are equal share one sort.
 int lookup_permute_ptrs(dehalo_ctx* ctx, int field, const fe* const* d_inputs, const fe* const* d_tables, uint64_t n, size_t batch, fe* const* d_out_inputs,

@@ -163,6 +163,11 @@ struct HostCS {
     }
 };
 
+// capi.hip: dehalo_graph_create for a checking program (internal.hpp)
+int dh_graph_create_roots(dehalo_ctx* ctx, int field, const uint64_t* constants, uint32_t num_constants, const int32_t* rotations, uint32_t num_rotations,
+                          const dehalo_calculation* calcs, uint32_t num_calcs, const dehalo_source* horner_parts, uint32_t num_horner_parts, uint32_t num_intermediates,
+                          const uint32_t* root_of, uint32_t num_roots, dehalo_graph** out);
+
 // ---- GraphEvaluator under construction (plonk/evaluation.rs) ----
 struct GSrc {
     uint32_t kind, index, rot;
@@ -249,7 +254,8 @@ struct GraphBuilder {
         }
     }
 
-    int compile(dehalo_ctx* ctx, dehalo_graph** out) const {
+    // root_of (a checking program: gate_check_graph below): per calculation the root it computes, or 0xffffffff
+    int compile(dehalo_ctx* ctx, dehalo_graph** out, const std::vector<uint32_t>* root_of = nullptr, uint32_t num_roots = 0) const {
         std::vector<dehalo_calculation> cc;
         std::vector<dehalo_source> parts;
         auto src = [](const GSrc& s) { return dehalo_source{s.kind, s.index, s.rot}; };
@@ -264,6 +270,9 @@ struct GraphBuilder {
             for (auto& p : c.parts) parts.push_back(src(p));
             cc.push_back(d);
         }
+        if (root_of)
+            return dh_graph_create_roots(ctx, f->id, (const uint64_t*)constants.data(), (uint32_t)constants.size(), rotations.data(), (uint32_t)rotations.size(), cc.data(),
+                                         (uint32_t)cc.size(), parts.data(), (uint32_t)parts.size(), num_intermediates, root_of->data(), num_roots, out);
         return dehalo_graph_create(ctx, f->id, (const uint64_t*)constants.data(), (uint32_t)constants.size(), rotations.data(), (uint32_t)rotations.size(), cc.data(),
                                    (uint32_t)cc.size(), parts.data(), (uint32_t)parts.size(), num_intermediates, out);
     }
@@ -276,6 +285,19 @@ inline GraphBuilder custom_gates_graph(const HostCS& cs, const HostField* f) {
     for (uint32_t poly : cs.gates) parts.push_back(g.add_expression(cs, poly));
     g.add_calc(DEHALO_CALC_HORNER, GSrc{DEHALO_SRC_PREVIOUS, 0, 0}, GSrc{DEHALO_SRC_Y, 0, 0}, parts);
     return g;
+}
+// The witness check's program (dehalo_check_witness): every gate polynomial a root of its own -- no y, nothing folded --, subexpressions shared between the
+// gates as add_calc shares them.  A root is a Store of the polynomial's value in a calculation of its own (never deduplicated: two equal polynomials are two roots).
+struct GateCheckProgram { GraphBuilder g; std::vector<uint32_t> root_of; };
+inline GateCheckProgram gate_check_graph(const HostCS& cs, const HostField* f) {
+    GateCheckProgram p{GraphBuilder(f), {}};
+    for (uint32_t i = 0; i < cs.gates.size(); i++) {
+        const GSrc r = p.g.add_expression(cs, cs.gates[i]);
+        p.g.calcs.push_back(GCalc{DEHALO_CALC_STORE, r, GraphBuilder::ZERO, {}, p.g.num_intermediates++});
+        p.root_of.resize(p.g.calcs.size(), 0xffffffffu);
+        p.root_of.back() = i;
+    }
+    return p;
 }
 // Evaluator::new, one lookup: (theta-compressed input + beta) * (theta-compressed table + gamma)
 inline GraphBuilder lookup_table_value_graph(const HostCS& cs, const HostCS::Lookup& lk, const HostField* f) {

@@ -342,6 +342,20 @@ class ProvingKey {
         return out;
     }
     void set_transcript_repr(const Fe& r) { be_.check(dehalo_pk_set_transcript_repr(pk_, r.data())); }
+    // MockProver::verify over this key (dehalo_check_witness): advice / instances as Prover::create_proof takes them, mapping = keygen's (null: copies unchecked).
+    // The totals are exact; `failures` receives the first `cap` of them in (kind, index, row) order.  The witness satisfies the circuit when the totals are zero.
+    dehalo_check_report check_witness(const std::vector<Fe>& advice, const std::vector<std::vector<Fe>>& instances, const std::vector<uint64_t>* mapping,
+                                      std::vector<dehalo_check_failure>& failures, size_t cap = 64, uint32_t flags = 0) const {
+        std::vector<const uint64_t*> ip;
+        std::vector<size_t> il;
+        for (auto& col : instances) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
+        failures.assign(cap, dehalo_check_failure{});
+        dehalo_check_report rep{};
+        be_.check(dehalo_check_witness(be_.raw(), pk_, advice.empty() ? nullptr : advice[0].data(), ip.data(), il.data(), (uint32_t)ip.size(), mapping ? mapping->data() : nullptr, flags,
+                                       cap ? failures.data() : nullptr, cap, &rep));
+        failures.resize((size_t)rep.written);
+        return rep;
+    }
     dehalo_pk* raw() const { return pk_; }
 
   private:

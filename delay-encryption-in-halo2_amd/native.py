@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import plonk
-from ._lib import (CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, FixedBase, RNG_FILL_FN, load_library)
+from ._lib import (CCheckFailure, CCheckReport, CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, FixedBase, RNG_FILL_FN, load_library)
 from .fields import CurveSpec, FieldSpec
 
 EXPR_KIND = {"const": 0, plonk.FIXED: 1, plonk.ADVICE: 2, plonk.INSTANCE: 3, "neg": 4, "sum": 5, "product": 6, "scaled": 7}
@@ -20,6 +20,7 @@ RNG_OS, RNG_PCG64, RNG_CALLBACK = 0, 1, 2
 KEYGEN_FIXED_CANONICAL = 1
 PROOF_ADVICE_ON_DEVICE, PROOF_ADVICE_CANONICAL = 1, 2
 CIRCUIT_DELAY_ENC, CIRCUIT_MOD_POW, CIRCUIT_POSE_ENC = 0, 1, 2
+CHECK_GATE, CHECK_LOOKUP, CHECK_COPY = 0, 1, 2
 PHASES = ("advice", "lookups", "products", "random", "quotient", "evaluations", "openings", "total")
 
 
@@ -210,6 +211,26 @@ class ParamsIPA(ParamsKZG):
         return t
 
 
+class CheckReport:
+    """dehalo_check_report and the stored failures of one ProvingKey.check_witness: `failures` = tuples (kind, index, row) in (kind, index, row) order -- kind
+    CHECK_GATE: index into cs.gates' polynomials; CHECK_LOOKUP: index into cs.lookups; CHECK_COPY: index into cs.permutation_columns -- at most `cap` of them;
+    the six counters are exact whatever `cap` was."""
+
+    def __init__(self, rep: CCheckReport, failures):
+        self.failures = failures
+        self.gate_failures, self.lookup_failures, self.copy_failures = int(rep.gate_failures), int(rep.lookup_failures), int(rep.copy_failures)
+        self.rows, self.lookup_inputs, self.cells_in_cycles = int(rep.rows), int(rep.lookup_inputs), int(rep.cells_in_cycles)
+        self.written = int(rep.written)
+
+    @property
+    def ok(self) -> bool:
+        return self.gate_failures == 0 and self.lookup_failures == 0 and self.copy_failures == 0
+
+    def __repr__(self):
+        return "CheckReport(ok=%s, gate_failures=%d, lookup_failures=%d, copy_failures=%d, rows=%d, lookup_inputs=%d, cells_in_cycles=%d, failures=%r)" % (
+            self.ok, self.gate_failures, self.lookup_failures, self.copy_failures, self.rows, self.lookup_inputs, self.cells_in_cycles, self.failures)
+
+
 class ProvingKey:
     """dehalo_pk: ProvingKey (with its VerifyingKey and compiled programs) resident on the device."""
 
@@ -259,6 +280,34 @@ class ProvingKey:
     @transcript_repr.setter
     def transcript_repr(self, value: int):
         _check(self.ctx, load_library().dehalo_pk_set_transcript_repr(self.handle, self.curve.scalar.encode(value).ctypes.data))
+
+    def check_witness(self, advice, instances: Sequence[Sequence[int]] = ((),), assembly=None, canonical: bool = False, cap: int = 64, ctx: Optional[Context] = None) -> CheckReport:
+        """dehalo_check_witness -- MockProver::verify on the device: which gate polynomials, lookup inputs and copy constraints the witness breaks, and where.
+        advice / instances / canonical as Prover.create_proof takes them; assembly: the plonk.Assembly (or its mapping array) keygen was given, None = the copy
+        constraints are not checked; cap: how many failures are stored (the totals are exact regardless)."""
+        lib = load_library()
+        ctx = ctx if ctx is not None else self.ctx
+        f = self.curve.scalar
+        flags = PROOF_ADVICE_CANONICAL if canonical else 0
+        if hasattr(advice, "data_ptr"):
+            adv_ptr, flags = advice.data_ptr(), flags | PROOF_ADVICE_ON_DEVICE
+            if hasattr(advice, "is_cuda") and advice.is_cuda:
+                import torch
+                torch.cuda.current_stream().synchronize()      # the library reads the tensor on its own stream
+        else:
+            adv = np.ascontiguousarray(advice, dtype=np.uint64)
+            adv_ptr = adv.ctypes.data
+        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for v in instances]
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
+        lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
+        mapping = None
+        if assembly is not None:
+            mapping = np.ascontiguousarray(getattr(assembly, "mapping", assembly), dtype=np.uint64).reshape(-1)
+        fails = (CCheckFailure * cap)() if cap else None
+        rep = CCheckReport()
+        _check(ctx, lib.dehalo_check_witness(ctx.handle, self.handle, adv_ptr, ptrs, lens, len(cols), mapping.ctypes.data if mapping is not None else None, flags, fails, cap,
+                                             C.byref(rep)))
+        return CheckReport(rep, [(int(fails[i].kind), int(fails[i].index), int(fails[i].row)) for i in range(int(rep.written))])
 
     def info(self) -> dict:
         out = (C.c_uint32 * 8)()

@@ -610,6 +610,37 @@ size_t dehalo_prover_proof_size(const dehalo_prover* prover);
 enum { DEHALO_PROOF_ADVICE_ON_DEVICE = 1, DEHALO_PROOF_ADVICE_CANONICAL = 2 /* plain integers < p: converted on the device */ };
 int dehalo_create_proof(dehalo_prover* prover, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                         dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
+/* ---- MockProver::verify over a proving key [UPSTREAM halo2_proofs/src/dev.rs MockProver::verify] (csrc/check.hip) ----------------------------------
+ * dehalo_create_proof proves whatever advice it is handed; this call says WHERE a witness breaks the circuit of `pk`, on the device, before anything is proved.
+ *   advice, instances, instance_lens, num_instance_columns, flags   exactly dehalo_create_proof's (DEHALO_PROOF_ADVICE_ON_DEVICE and DEHALO_PROOF_ADVICE_CANONICAL
+ *                       included; the same instance checks, DEHALO_ERR_INVALID in the same cases); nothing is blinded: the rows beyond the usable ones are read as given
+ *   permutation_mapping dehalo_keygen's argument of that name (host memory).  NULL: the copy constraints are not checked (copy_failures = cells_in_cycles = 0).  An
+ *                       entry >= num_permutation_columns x 2^k is DEHALO_ERR_INVALID, decided by a kernel that only reads the mapping, before any kernel follows it.
+ *                       Whether the mapping is a bijection is NOT checked.
+ * What is checked (usable rows = [0, 2^k - (blinding_factors + 1))):
+ *   GATE    every gate polynomial on every usable row; rotations wrap mod 2^k; unusable rows are read, never checked
+ *   LOOKUP  the input tuple of every usable row must equal the table tuple of some usable row.  Tuples are compared through the lookup argument's compression
+ *           sum_i theta^i e_i with a theta fixed per key (Blake2b-512, personalisation "Dehalo-CheckTheta" cut to BLAKE2b's 16 bytes, over transcript_repr, reduced as
+ *           a transcript challenge is): the report of a key and a witness is reproducible, and two different tuples collide with probability ~ tuple length / p.
+ *           A debugging aid, not a verifier.
+ *   COPY    every cell c of a permutation column, all 2^k rows, with m = mapping[c] != c: value(c) == value(m).  Each end of a broken constraint is its own failure.
+ * The failures come ordered by (kind, index, row) ascending; the first `cap` are stored; the totals are exact however small `cap` is.  Returns 0 whenever the check
+ * ran: the witness satisfies the circuit when the three totals are 0.  `failures` may be NULL when cap is 0.  DEHALO_ERR_INVALID: null ctx / pk / report, a key of
+ * another device.  Allocates from the context's workspace only; everything is queued on the context's stream, which the call waits for once, before it returns.
+ * Upstream's failure NAMING (gate names, region offsets, cell values) is the front-end's: it maps (kind, index, row) back through its own ConstraintSystem. */
+typedef enum { DEHALO_CHECK_GATE = 0, DEHALO_CHECK_LOOKUP = 1, DEHALO_CHECK_COPY = 2 } dehalo_check_kind;
+typedef struct { uint32_t kind, index, row, reserved; } dehalo_check_failure;
+/*  GATE:   index = position in cs.gates (gates.flat_map(polynomials) order), row = the row whose polynomial is non-zero
+    LOOKUP: index = lookup, row = the row whose input tuple is no row of the table
+    COPY:   index = position j in cs.permutation_columns, row = i: cell (j, i) differs from the cell the mapping sends it to */
+typedef struct {
+    uint64_t gate_failures, lookup_failures, copy_failures;   /* totals, however small `cap` is */
+    uint64_t rows, lookup_inputs, cells_in_cycles;            /* what was checked: usable rows; usable rows x lookups; cells with mapping[c] != c */
+    uint64_t written;                                         /* entries stored in `failures` = min(cap, total) */
+} dehalo_check_report;
+int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
+                         const uint64_t* permutation_mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap, dehalo_check_report* report);
+
 /* ONE proof on several GPUs ("single-proof mode -- round-robin columns of the current phase across GPUs"): every one of `world` processes runs
  * the same dehalo_create_proof on its own GPU with the same inputs and the same seeded random stream (DEHALO_RNG_PCG64, or a callback that hands every process the
  * same scalars); of every commitment phase with more than one column (advice, permuted lookup columns, the grand products, the quotient's pieces, the openings) a
