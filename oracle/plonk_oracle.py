@@ -1,4 +1,4 @@
-"""CPU restatement of keygen + create_proof (KZG / GWC) for the parity tests.  TEST INFRASTRUCTURE ONLY: importable from
+"""CPU restatement of keygen + create_proof (KZG / GWC, and IPA through ipa.py) for the parity tests.  TEST INFRASTRUCTURE ONLY: importable from
 tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg; the product never imports it.
 
 Follows [UPSTREAM halo2_proofs @ v2023_04_20: plonk/keygen.rs, plonk/prover.rs, plonk/lookup/prover.rs,
@@ -7,6 +7,7 @@ poly/kzg/multiopen/gwc/prover.rs, transcript.rs] -- the code behind the referenc
 benches/delay_enc.rs:86,103 (keygen) and :123-131 (create_proof) -- written from the published algorithm (the crate is
 not in the container): **parity unpinned** against upstream itself; what pins it is oracle/verifier.py accepting the
 proofs (the reference's own end-to-end check, `assert!(accept)`, benches/delay_enc.rs:147-165).
+One create_proof body proves under both commitment schemes; what differs between them is a scheme object's (ProverGWC here, ipa.ProverIPA).
 
 The heavy steps go through oracle.c (best_multiexp, best_fft, evaluate_h's row loops, permute_expression_pair, batch
 inversion) with upstream's serial / chunk-per-thread structure; everything else is Python integers.
@@ -23,19 +24,11 @@ from typing import Dict, List, Sequence, Tuple
 import numpy as np
 
 import coracle as co
+import ipa
 import pyoracle as po
 
 
 # ---- small helpers -----------------------------------------------------------------------------------------
-def arr_from_ints(vals: Sequence[int]) -> np.ndarray:
-    return np.frombuffer(b"".join(int(v).to_bytes(32, "little") for v in vals), dtype=np.uint64).reshape(-1, 4).copy()
-
-
-def ints_from_arr(arr) -> List[int]:
-    b = np.ascontiguousarray(arr, dtype=np.uint64).tobytes()
-    return [int.from_bytes(b[i:i + 32], "little") for i in range(0, len(b), 32)]
-
-
 class Fld:
     """A scalar field with its Montgomery codec on 4 x u64 limbs."""
 
@@ -44,16 +37,16 @@ class Fld:
         self.R, self.Rinv = f.R, f.R_inv
 
     def m(self, x: int) -> np.ndarray:
-        return arr_from_ints([x % self.p * self.R % self.p])[0]
+        return ipa.enc(self.f, [x])[0]
 
     def many(self, xs: Sequence[int]) -> np.ndarray:
-        return arr_from_ints([x % self.p * self.R % self.p for x in xs])
+        return ipa.enc(self.f, xs)
 
     def un(self, limbs) -> int:
-        return ints_from_arr(np.asarray(limbs).reshape(1, 4))[0] * self.Rinv % self.p
+        return ipa.dec(self.f, limbs)[0]
 
     def un_many(self, arr) -> List[int]:
-        return [v * self.Rinv % self.p for v in ints_from_arr(arr)]
+        return ipa.dec(self.f, arr)
 
 
 def expr_degree(e) -> int:
@@ -145,9 +138,12 @@ class Transcript:
         self.common_scalar(s)
         self.proof += int(s).to_bytes(32, "little")
 
-    def write_point(self, P):
+    def common_point(self, P):
         assert P is not None, "cannot write points at infinity to the transcript"
         self.h.update(b"\x01" + P[0].to_bytes(32, "little") + P[1].to_bytes(32, "little"))
+
+    def write_point(self, P):
+        self.common_point(P)
         b = bytearray(P[0].to_bytes(32, "little"))
         b[31] |= (P[1] & 1) << 7
         self.proof += b
@@ -175,13 +171,7 @@ def setup_srs(curve: po.Curve, k: int, s: int, threads: int = 1) -> Dict[str, np
 def commit(curve: po.Curve, bases: np.ndarray, scalars: np.ndarray, threads: int):
     """params.commit / commit_lagrange -> affine (x, y) canonical | None."""
     cid = po.CURVE_IDS[curve.name]
-    n = scalars.shape[0]
-    aff = co.to_affine(cid, co.best_multiexp(cid, scalars, bases[:n], threads))
-    v = ints_from_arr(aff.reshape(2, 4))
-    if v[0] == 0 and v[1] == 0:
-        return None
-    ri = curve.base.R_inv
-    return (v[0] * ri % curve.base.p, v[1] * ri % curve.base.p)
+    return ipa.dec_point(curve, co.to_affine(cid, co.best_multiexp(cid, scalars, bases[:scalars.shape[0]], threads)))
 
 
 def keygen(curve: po.Curve, srs, desc, k: int, fixed_canonical: np.ndarray, mapping: np.ndarray, threads: int = 1) -> dict:
@@ -253,9 +243,70 @@ class ScalarStream:
 
 
 # ---- create_proof ---------------------------------------------------------------------------------------------
-def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, instances: Sequence[Sequence[int]], rng, vk_repr: int, threads: int = 1):
+def plonk_queries(sh: Shape, rotate, x, C: Dict[str, list], E: Dict[str, list]):
+    """The opening queries in upstream's order (instance, advice, permutation products, lookups, fixed, sigma, h, random) as (key, point, item, eval):
+    `key` names the commitment, `item` is whatever the caller opens (a commitment for a verifier, a (polynomial, blind) for a prover).  The one
+    statement of that order: both provers and both verifiers list their queries here.  E["instance"] is empty where instance columns are not queried.
+    [UPSTREAM permutation::{prover,verifier}: the products at x and omega x set by set, then at omega^last x over sets.iter().rev().skip(1)]"""
+    x_next, x_inv, x_last = rotate(1), rotate(-1), rotate(-(sh.blinding_factors + 1))
+    Q = []
+    for (c, r), e in zip(sh.instance_queries, E["instance"]):
+        Q.append((("instance", c), rotate(r), C["instance"][c], e))
+    for (c, r), e in zip(sh.advice_queries, E["advice"]):
+        Q.append((("advice", c), rotate(r), C["advice"][c], e))
+    for s, (zc, (e0, e1, _)) in enumerate(zip(C["perm_z"], E["perm"])):
+        Q += [(("perm_z", s), x, zc, e0), (("perm_z", s), x_next, zc, e1)]
+    for s in reversed(range(max(0, len(C["perm_z"]) - 1))):      # sets.iter().rev().skip(1)
+        Q.append((("perm_z", s), x_last, C["perm_z"][s], E["perm"][s][2]))
+    for l, ((ai, ti), zc, (z0, z1, a0, am1, s0)) in enumerate(zip(C["lookup_permuted"], C["lookup_z"], E["lookup"])):
+        Q += [(("lookup_z", l), x, zc, z0), (("lookup_a", l), x, ai, a0), (("lookup_s", l), x, ti, s0), (("lookup_a", l), x_inv, ai, am1), (("lookup_z", l), x_next, zc, z1)]
+    for (c, r), e in zip(sh.fixed_queries, E["fixed"]):
+        Q.append((("fixed", c), rotate(r), C["fixed"][c], e))
+    for j, (sc, e) in enumerate(zip(C["sigma"], E["sigma"])):
+        Q.append((("sigma", j), x, sc, e))
+    Q.append((("h",), x, C["h"], E["h"]))
+    Q.append((("random",), x, C["random"], E["random"]))
+    return Q
+
+
+class ProverGWC:
+    """What create_proof takes as its scheme under KZG: bare MSM commitments (the blinds are drawn and dropped), instance values absorbed as scalars
+    and not queried (QUERY_INSTANCE = false), GWC's multiopen.  ipa.ProverIPA is the other scheme."""
+    query_instance = False
+    default_blind = 0
+
+    def __init__(self, curve: po.Curve, srs, threads: int = 1):
+        self.curve, self.srs, self.threads = curve, srs, threads
+
+    def commit(self, bases, scalars, blind_mont):
+        return commit(self.curve, bases, scalars, self.threads)
+
+    def absorb_instance(self, T, values: Sequence[int], column: np.ndarray):
+        for v in values:
+            T.common_scalar(v)
+
+    def open(self, T, Q, rng, write_commit) -> dict:
+        """[UPSTREAM poly/kzg/multiopen/gwc/prover.rs]: per distinct point, in order of first appearance, one witness over its queries batched with v."""
+        F = Fld(self.curve.scalar)
+        p = F.p
+        v = T.challenge()
+        groups: Dict[int, list] = {}
+        for _, pt, (poly, _), e in Q:
+            groups.setdefault(pt, []).append((poly, e))
+        for pt, group in groups.items():
+            coefs = [pow(v, i, p) for i in range(len(group))]
+            eval_batch = sum(c * e for c, (_, e) in zip(coefs, group)) % p
+            poly_batch = co.lincomb(F.id, [q for q, _ in group], F.many(coefs), F.m(eval_batch))
+            write_commit(self.srs["g"], co.kate_division(F.id, poly_batch, F.m(pt)), F.m(0))
+        return dict(challenges=dict(v=v))
+
+
+def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, instances: Sequence[Sequence[int]], rng, vk_repr: int, threads: int = 1, scheme=None):
     """-> (proof bytes, trace) -- trace holds every commitment, challenge and evaluation in order, and h's coefficients.
-    advice_mont: (num_advice, n, 4) Montgomery; rng.scalars(count) -> (count, 4) Montgomery (consumed in upstream's order)."""
+    advice_mont: (num_advice, n, 4) Montgomery; rng.scalars(count) -> (count, 4) Montgomery (consumed in upstream's order: one body draws for both
+    schemes, with the multiopen's draws behind it).  scheme: ProverGWC (the default) or ipa.ProverIPA -- how instances enter the transcript and
+    whether they are queried, commit(bases, scalars, blind) and open(T, Q, rng, write_commit)."""
+    scheme = scheme if scheme is not None else ProverGWC(curve, srs, threads)
     F = Fld(curve.scalar)
     sh: Shape = key["shape"]
     d, n, p, k, u, bf = sh.dom, sh.n, F.p, sh.k, sh.usable, sh.blinding_factors
@@ -268,29 +319,27 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
     add = lambda a, b: co.field_op(F.id, "add", a, b)
     bc = lambda x: np.tile(mm(x), (n, 1))
 
-    def write_commit(bases, scalars):
-        P = commit(curve, bases, scalars, threads)
+    def write_commit(bases, scalars, blind_mont):
+        P = scheme.commit(bases, scalars, blind_mont)
         T.write_point(P)
         trace["commitments"].append(P)
+        return F.un(blind_mont)
 
     T.common_scalar(vk_repr)
     # instances
     inst_values = []
     for vals in instances:
-        for v in vals:
-            T.common_scalar(v)
         col = np.zeros((n, 4), dtype=np.uint64)
         if len(vals):
             col[:len(vals)] = F.many(vals)
         inst_values.append(col)
+        scheme.absorb_instance(T, vals, col)
     inst_polys = [l2c(v) for v in inst_values]
     # advice
     advice = [np.array(advice_mont[i], dtype=np.uint64).reshape(n, 4) for i in range(sh.num_advice)]
     for a in advice:
         a[u:] = rng.scalars(n - u)
-    rng.scalars(sh.num_advice)
-    for a in advice:
-        write_commit(srs["g_lagrange"], a)
+    advice_blinds = [write_commit(srs["g_lagrange"], a, b) for a, b in zip(advice, rng.scalars(sh.num_advice))]
     theta = T.challenge()
     # lookups: compress, permute
     fixed_v = key["fixed_values"]
@@ -310,15 +359,13 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
         pi, pt = (np.concatenate([x, np.zeros((n - u, 4), dtype=np.uint64)]) for x in res)
         pi[u:] = rng.scalars(n - u)
         pt[u:] = rng.scalars(n - u)
-        rng.scalars(2)
-        write_commit(srs["g_lagrange"], pi)
-        write_commit(srs["g_lagrange"], pt)
-        lookups.append(dict(ci=ci, ct=ct, pi=pi, pt=pt))
+        bi, bt = rng.scalars(2)
+        lookups.append(dict(ci=ci, ct=ct, pi=pi, pt=pt, pi_blind=write_commit(srs["g_lagrange"], pi, bi), pt_blind=write_commit(srs["g_lagrange"], pt, bt)))
     beta, gamma = T.challenge(), T.challenge()
     # permutation argument
     colvals = {"advice": advice, "fixed": fixed_v, "instance": inst_values}
     w = co.powers(F.id, mm(d.omega), mm(1), n)
-    perm_z, last_z, dcur = [], 1, 1
+    perm_z, perm_z_blinds, last_z, dcur = [], [], 1, 1
     for s in range(sh.num_sets):
         cols_s = sh.perm_columns[s * sh.chunk_len:(s + 1) * sh.chunk_len]
         den = np.tile(mm(1), (n, 1))
@@ -331,23 +378,21 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
             dcur = dcur * key["delta"] % p
         z = co.field_op(F.id, "mul", co.grand_product(F.id, modified, np.tile(mm(1), (n, 1))), bc(last_z))
         z[n - bf:] = rng.scalars(bf)
-        rng.scalars(1)
+        zb = rng.scalars(1)[0]
         last_z = F.un(z[u])
         perm_z.append(z)
-        write_commit(srs["g_lagrange"], z)
+        perm_z_blinds.append(write_commit(srs["g_lagrange"], z, zb))
     # lookup products
     for lk in lookups:
         den = mul(add(lk["pi"], bc(beta)), add(lk["pt"], bc(gamma)))
         num = mul(add(lk["ci"], bc(beta)), add(lk["ct"], bc(gamma)))
         z = co.grand_product(F.id, num, den)
         z[n - bf:] = rng.scalars(bf)
-        rng.scalars(1)
         lk["z"] = z
-        write_commit(srs["g_lagrange"], z)
+        lk["z_blind"] = write_commit(srs["g_lagrange"], z, rng.scalars(1)[0])
     # vanishing: random polynomial
     random_poly = rng.scalars(n)
-    rng.scalars(1)
-    write_commit(srs["g"], random_poly)
+    random_blind = write_commit(srs["g"], random_poly, rng.scalars(1)[0])
     y = T.challenge()
     # coefficient forms, cosets
     advice_polys = [l2c(a) for a in advice]
@@ -382,9 +427,7 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
     hc = co.extended_to_coeff(F.id, h, sh.ext_k, mm(d.ext_omega_inv), mm(d.ext_ifft_divisor), mm(d.g_coset), threads)
     pieces_n = sh.degree - 1
     pieces = [np.ascontiguousarray(hc[i * n:(i + 1) * n]) for i in range(pieces_n)]
-    rng.scalars(pieces_n)
-    for pc in pieces:
-        write_commit(srs["g"], pc)
+    h_blinds = [write_commit(srs["g"], pc, b) for pc, b in zip(pieces, rng.scalars(pieces_n))]
     x = T.challenge()
     xn = pow(x, n, p)
     rotate = lambda r: x * pow(d.omega if r >= 0 else d.omega_inv, abs(r), p) % p
@@ -396,7 +439,7 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
         trace["evals"].append(e)
         return e
 
-    Q = []          # (point, poly, eval)
+    inst_evals = [write_eval(inst_polys[c], rotate(r)) for c, r in sh.instance_queries] if scheme.query_instance else []
     adv_evals = [write_eval(advice_polys[c], rotate(r)) for c, r in sh.advice_queries]
     fix_evals = [write_eval(key["fixed_polys"][c], rotate(r)) for c, r in sh.fixed_queries]
     hfold = co.lincomb(F.id, pieces, F.many([pow(xn, i, p) for i in range(pieces_n)]))
@@ -412,38 +455,27 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
     for lk in lookups:
         lk_evals.append((write_eval(lk["z_poly"], x), write_eval(lk["z_poly"], x_next), write_eval(lk["pi_poly"], x), write_eval(lk["pi_poly"], x_inv),
                          write_eval(lk["pt_poly"], x)))
-    # queries
-    for (c, r), e in zip(sh.advice_queries, adv_evals):
-        Q.append((rotate(r), advice_polys[c], e))
-    for zp, (e0, e1, _) in zip(perm_z_polys, pz_evals):
-        Q += [(x, zp, e0), (x_next, zp, e1)]
-    for zp, (_, _, el) in reversed(list(zip(perm_z_polys, pz_evals))[:-1]):      # [UPSTREAM permutation::prover::Evaluated::open: sets.iter().rev().skip(1)]
-        Q.append((x_last, zp, el))
-    for lk, (z0, z1, a0, am1, t0) in zip(lookups, lk_evals):
-        Q += [(x, lk["z_poly"], z0), (x, lk["pi_poly"], a0), (x, lk["pt_poly"], t0), (x_inv, lk["pi_poly"], am1), (x_next, lk["z_poly"], z1)]
-    for (c, r), e in zip(sh.fixed_queries, fix_evals):
-        Q.append((rotate(r), key["fixed_polys"][c], e))
-    for sp, e in zip(key["perm_polys"], sigma_evals):
-        Q.append((x, sp, e))
-    Q.append((x, hfold, ev(hfold, x)))
-    Q.append((x, random_poly, random_eval))
-    # GWC
-    v = T.challenge()
-    points: List[int] = []
-    groups: Dict[int, list] = {}
-    for pt, poly, e in Q:
-        if pt not in groups:
-            groups[pt] = []
-            points.append(pt)
-        groups[pt].append((poly, e))
-    for pt in points:
-        coefs = [pow(v, i, p) for i in range(len(groups[pt]))]
-        eval_batch = sum(c * e for c, (_, e) in zip(coefs, groups[pt])) % p
-        poly_batch = co.lincomb(F.id, [q for q, _ in groups[pt]], F.many(coefs), mm(eval_batch))
-        witness = co.kate_division(F.id, poly_batch, mm(pt))
-        write_commit(srs["g"], witness)
-    trace["challenges"] = dict(theta=theta, beta=beta, gamma=gamma, y=y, x=x, v=v)
+    # queries, in upstream's order; the opened item is (polynomial, blind)
+    h_blind = sum(b * pow(xn, i, p) for i, b in enumerate(h_blinds)) % p      # folded with x^n as the pieces are
+    db = scheme.default_blind
+    Q = plonk_queries(sh, rotate, x,
+                      dict(instance=[(q, db) for q in inst_polys], advice=list(zip(advice_polys, advice_blinds)), perm_z=list(zip(perm_z_polys, perm_z_blinds)),
+                           lookup_permuted=[((lk["pi_poly"], lk["pi_blind"]), (lk["pt_poly"], lk["pt_blind"])) for lk in lookups],
+                           lookup_z=[(lk["z_poly"], lk["z_blind"]) for lk in lookups], fixed=[(q, db) for q in key["fixed_polys"]],
+                           sigma=[(q, db) for q in key["perm_polys"]], h=(hfold, h_blind), random=(random_poly, random_blind)),
+                      dict(instance=inst_evals, advice=adv_evals, perm=pz_evals, lookup=lk_evals, fixed=fix_evals, sigma=sigma_evals, h=ev(hfold, x), random=random_eval))
+    opened = scheme.open(T, Q, rng, write_commit)
+    trace["challenges"] = dict(theta=theta, beta=beta, gamma=gamma, y=y, x=x, **opened.pop("challenges"))
+    trace.update(opened)
     trace["perm_last_evals"] = [el for _, _, el in pz_evals[:-1]]                        # as written to the transcript: set 0, 1, ...
-    trace["x_last_group"] = [e for _, e in groups.get(x_last, [])] if sh.num_sets > 1 else []      # as batched with 1, v, v^2, ...
+    trace["x_last_group"] = [e for _, pt, _, e in Q if pt == x_last] if sh.num_sets > 1 else []      # as GWC batches them with 1, v, v^2, ...
     trace["h_coeffs"] = hc
     return bytes(T.proof), trace
+
+
+def create_proof_ipa(curve: po.Curve, srs, u_mont, w_mont, key: dict, advice_mont: np.ndarray, instances: Sequence[Sequence[int]], rng, vk_repr: int,
+                     threads: int = 1, default_blind: int = ipa.DEFAULT_BLIND):
+    """create_proof over IPACommitmentScheme / ProverIPA [UPSTREAM plonk/prover.rs with QUERY_INSTANCE = true, poly/ipa/multiopen/prover.rs].
+    srs: {"g", "g_lagrange"} (Montgomery points), u_mont / w_mont one point each; key: keygen's (bare commitments; the transcript representation is
+    taken over ipa.blinded_key_commitments').  The trace also holds point_sets and q_evals."""
+    return create_proof(curve, srs, key, advice_mont, instances, rng, vk_repr, threads, ipa.ProverIPA(curve, srs, u_mont, w_mont, threads, default_blind))

@@ -1,4 +1,4 @@
-"""verify_proof over KZG / GWC on Python integers.  TEST INFRASTRUCTURE ONLY.
+"""verify_proof over KZG / GWC and over IPA on Python integers.  TEST INFRASTRUCTURE ONLY.
 
 The reference's only check of the hot path's results is `assert!(accept)` after
 `verify_proof::<KZGCommitmentScheme<Bn256>, VerifierGWC<_>, Challenge255<_>, Blake2bRead<_, _, _>, SingleStrategy<_>>`
@@ -8,29 +8,53 @@ protocol: read the proof through the transcript, recompute h(x) from the evaluat
 with one pairing product.  A proof is accepted only if every commitment, evaluation and quotient in it is consistent --
 which is what ties the device's MSM / NTT results to the mathematics rather than to this repository's own oracles.
 
+One PLONK part (`read_plonk`) serves both schemes.  Under IPA (`verify_proof_ipa`, plonk/verifier.rs with QUERY_INSTANCE = true) the instance columns
+are committed (commit_lagrange with Blind::default()) and absorbed as points, their evaluations read first and queried first, and the queries go to
+ipa.verify_multiopen.  No halo2 source was at hand for the IPA side: parity with upstream's bytes is unpinned (see ipa.py); acceptance shows a proof
+is a sound proof for this restatement of the protocol.
+
 Inputs are plain data: the circuit description tuple (see plonk_oracle.py), the verifying key's commitments as canonical
-affine points, g[0], g2 and s_g2.
+affine points, g[0], g2 and s_g2 (KZG) or g, g_lagrange, u, w as Montgomery rows (IPA).
 """
 from __future__ import annotations
 
-import hashlib
-from typing import Dict, List, Sequence
+from typing import List, Optional, Sequence
 
+import ipa
 import pairing as pr
 import pyoracle as po
-from plonk_oracle import Shape
+from plonk_oracle import Shape, Transcript, plonk_queries
 
 
-class ReadTranscript:
+def sqrt(a: int, p: int) -> Optional[int]:
+    """Tonelli-Shanks: exact for every odd prime (BN254's base field is 3 mod 4, where it is a^((p + 1) / 4); the Pasta fields are 1 mod 4)."""
+    a %= p
+    if a == 0:
+        return 0
+    if pow(a, (p - 1) // 2, p) != 1:
+        return None
+    q, s = p - 1, 0
+    while q % 2 == 0:
+        q, s = q // 2, s + 1
+    z = 2
+    while pow(z, (p - 1) // 2, p) != p - 1:
+        z += 1
+    m, c, t, r = s, pow(z, q, p), pow(a, q, p), pow(a, (q + 1) // 2, p)
+    while t != 1:
+        i, t2 = 0, t
+        while t2 != 1:
+            t2, i = t2 * t2 % p, i + 1
+        b = pow(c, 1 << (m - i - 1), p)
+        m, c, t, r = i, b * b % p, t * b * b % p, r * b % p
+    return r
+
+
+class ReadTranscript(Transcript):
+    """Blake2bRead: points as x little-endian with bit 255 = sign of y; all zero = the identity, refused."""
+
     def __init__(self, curve: po.Curve, proof: bytes):
-        self.curve, self.h, self.data, self.pos = curve, hashlib.blake2b(digest_size=64, person=b"Halo2-Transcript"), bytes(proof), 0
-
-    def challenge(self) -> int:
-        self.h.update(b"\x00")
-        return int.from_bytes(self.h.copy().digest(), "little") % self.curve.scalar.p
-
-    def common_scalar(self, s: int):
-        self.h.update(b"\x02" + int(s).to_bytes(32, "little"))
+        super().__init__(curve)
+        self.data, self.pos = bytes(proof), 0
 
     def _take(self) -> bytes:
         if self.pos + 32 > len(self.data):
@@ -54,14 +78,12 @@ class ReadTranscript:
             raise ValueError("non-canonical x")
         if x == 0 and sign == 0:
             raise ValueError("identity in proof")
-        rhs = (x * x % p * x + self.curve.b) % p
-        assert p % 4 == 3
-        y = pow(rhs, (p + 1) // 4, p)
-        if y * y % p != rhs:
+        y = sqrt(x * x % p * x + self.curve.b, p)
+        if y is None:
             raise ValueError("not on curve")
         if (y & 1) != sign:
             y = p - y
-        self.h.update(b"\x01" + x.to_bytes(32, "little") + y.to_bytes(32, "little"))
+        self.common_point((x, y))
         return (x, y)
 
 
@@ -79,38 +101,43 @@ def eval_expr(e, p, fixed, advice, instance) -> int:
     raise ValueError(k)
 
 
-def verify_proof(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitments, vk_repr: int, g0, g2, s_g2, instances: Sequence[Sequence[int]], proof: bytes) -> bool:
+def read_plonk(T: ReadTranscript, curve: po.Curve, desc, k: int, fixed_commitments, perm_commitments, vk_repr: int, instances: Sequence[Sequence[int]],
+               instance_commitments=None):
+    """The PLONK part of verify_proof: reads T up to the evaluations, rebuilds expected_h and the folded h commitment -> the opening queries
+    (key, point, commitment, eval) in plonk_queries' order; raises ValueError on a malformed proof.  instance_commitments None (KZG, QUERY_INSTANCE =
+    false): the instance values are absorbed as scalars and their evaluations interpolated here; given (IPA): absorbed as points, evaluations read."""
     f = curve.scalar
     p = f.p
     sh = Shape(desc, k, f)
     d, n, bf = sh.dom, sh.n, sh.blinding_factors
-    T = ReadTranscript(curve, proof)
-    try:
-        T.common_scalar(vk_repr)
+    T.common_scalar(vk_repr)
+    if instance_commitments is None:
         for vals in instances:
             for v in vals:
                 T.common_scalar(v)
-        advice_commitments = [T.read_point() for _ in range(sh.num_advice)]
-        theta = T.challenge()
-        lookups_permuted = [(T.read_point(), T.read_point()) for _ in sh.lookups]
-        beta, gamma = T.challenge(), T.challenge()
-        perm_z_commitments = [T.read_point() for _ in range(sh.num_sets)]
-        lookup_z_commitments = [T.read_point() for _ in sh.lookups]
-        random_commitment = T.read_point()
-        y = T.challenge()
-        h_commitments = [T.read_point() for _ in range(sh.degree - 1)]
-        x = T.challenge()
-        advice_evals = [T.read_scalar() for _ in sh.advice_queries]
-        fixed_evals = [T.read_scalar() for _ in sh.fixed_queries]
-        random_eval = T.read_scalar()
-        sigma_evals = [T.read_scalar() for _ in sh.perm_columns]
-        perm_evals = []
-        for s in range(sh.num_sets):
-            e0, e1 = T.read_scalar(), T.read_scalar()
-            perm_evals.append((e0, e1, T.read_scalar() if s != sh.num_sets - 1 else None))
-        lookup_evals = [tuple(T.read_scalar() for _ in range(5)) for _ in sh.lookups]     # product, product_next, permuted_input, permuted_input_inv, permuted_table
-    except ValueError:
-        return False
+    else:
+        for P in instance_commitments:
+            T.common_point(P)
+    advice_commitments = [T.read_point() for _ in range(sh.num_advice)]
+    theta = T.challenge()
+    lookups_permuted = [(T.read_point(), T.read_point()) for _ in sh.lookups]
+    beta, gamma = T.challenge(), T.challenge()
+    perm_z_commitments = [T.read_point() for _ in range(sh.num_sets)]
+    lookup_z_commitments = [T.read_point() for _ in sh.lookups]
+    random_commitment = T.read_point()
+    y = T.challenge()
+    h_commitments = [T.read_point() for _ in range(sh.degree - 1)]
+    x = T.challenge()
+    instance_evals = [T.read_scalar() for _ in sh.instance_queries] if instance_commitments is not None else []
+    advice_evals = [T.read_scalar() for _ in sh.advice_queries]
+    fixed_evals = [T.read_scalar() for _ in sh.fixed_queries]
+    random_eval = T.read_scalar()
+    sigma_evals = [T.read_scalar() for _ in sh.perm_columns]
+    perm_evals = []
+    for s in range(sh.num_sets):
+        e0, e1 = T.read_scalar(), T.read_scalar()
+        perm_evals.append((e0, e1, T.read_scalar() if s != sh.num_sets - 1 else None))
+    lookup_evals = [tuple(T.read_scalar() for _ in range(5)) for _ in sh.lookups]     # product, product_next, permuted_input, permuted_input_inv, permuted_table
     xn = pow(x, n, p)
     rotate = lambda r: x * pow(d.omega if r >= 0 else d.omega_inv, abs(r), p) % p
     # l_i(x) for i in [-(bf+1), 0] (domain.l_i_range): l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
@@ -120,11 +147,10 @@ def verify_proof(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitme
     l_evals = [l_i(-i) for i in range(bf + 2)]            # l_0, l_{-1}, ..., l_{-(bf+1)}
     l_0, l_last = l_evals[0], l_evals[bf + 1]
     l_blind = sum(l_evals[1:bf + 1]) % p
-    # instance evaluations: interpolated by the verifier (KZG: QUERY_INSTANCE = false)
-    inst = {}
-    for (c, r) in sh.instance_queries:
-        vals = instances[c]
-        inst[(c, r)] = sum(v * l_i(j - r) for j, v in enumerate(vals)) % p
+    if instance_commitments is None:                       # interpolated by the verifier
+        inst = {(c, r): sum(v * l_i(j - r) for j, v in enumerate(instances[c])) % p for (c, r) in sh.instance_queries}
+    else:
+        inst = {q: e for q, e in zip(sh.instance_queries, instance_evals)}
     fx = {q: e for q, e in zip(sh.fixed_queries, fixed_evals)}
     av = {q: e for q, e in zip(sh.advice_queries, advice_evals)}
     # expressions, folded with y
@@ -165,37 +191,30 @@ def verify_proof(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitme
         expected_h = (expected_h * y + e) % p
     expected_h = expected_h * pow(xn - 1, -1, p) % p
     # h commitment folded with x^n
-    C = curve
     h_commitment = None
     for hc in reversed(h_commitments):
-        h_commitment = po.ec_add(C, po.ec_mul(C, xn, h_commitment) if h_commitment is not None else None, hc)
-    # queries (commitment, point, eval), in the prover's order
-    x_next, x_inv, x_last = rotate(1), rotate(-1), rotate(-(bf + 1))
-    Q = []
-    for (c, r), e in zip(sh.advice_queries, advice_evals):
-        Q.append((advice_commitments[c], rotate(r), e))
-    for zc, (e0, e1, _) in zip(perm_z_commitments, perm_evals):
-        Q += [(zc, x, e0), (zc, x_next, e1)]
-    for zc, (_, _, el) in reversed(list(zip(perm_z_commitments, perm_evals))[:-1]):      # [UPSTREAM permutation::verifier::Evaluated::queries: sets.iter().rev().skip(1)]
-        Q.append((zc, x_last, el))
-    for (ai, ti), zc, (z0, z1, a0, am1, s0) in zip(lookups_permuted, lookup_z_commitments, lookup_evals):
-        Q += [(zc, x, z0), (ai, x, a0), (ti, x, s0), (ai, x_inv, am1), (zc, x_next, z1)]
-    for (c, r), e in zip(sh.fixed_queries, fixed_evals):
-        Q.append((fixed_commitments[c], rotate(r), e))
-    for sc, e in zip(perm_commitments, sigma_evals):
-        Q.append((sc, x, e))
-    Q.append((h_commitment, x, expected_h))
-    Q.append((random_commitment, x, random_eval))
+        h_commitment = po.ec_add(curve, po.ec_mul(curve, xn, h_commitment) if h_commitment is not None else None, hc)
+    return plonk_queries(sh, rotate, x,
+                         dict(instance=instance_commitments, advice=advice_commitments, perm_z=perm_z_commitments, lookup_permuted=lookups_permuted,
+                              lookup_z=lookup_z_commitments, fixed=fixed_commitments, sigma=perm_commitments, h=h_commitment, random=random_commitment),
+                         dict(instance=instance_evals, advice=advice_evals, perm=perm_evals, lookup=lookup_evals, fixed=fixed_evals, sigma=sigma_evals,
+                              h=expected_h, random=random_eval))
+
+
+def verify_proof(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitments, vk_repr: int, g0, g2, s_g2, instances: Sequence[Sequence[int]], proof: bytes) -> bool:
+    p, C = curve.scalar.p, curve
+    T = ReadTranscript(curve, proof)
+    try:
+        Q = read_plonk(T, curve, desc, k, fixed_commitments, perm_commitments, vk_repr, instances)
+    except ValueError:
+        return False
     # VerifierGWC::verify_proof
     v = T.challenge()
-    points, groups = [], {}
-    for cm, pt, e in Q:
-        if pt not in groups:
-            groups[pt] = []
-            points.append(pt)
-        groups[pt].append((cm, e))
+    groups = {}                                          # by point, in order of first appearance
+    for _, pt, cm, e in Q:
+        groups.setdefault(pt, []).append((cm, e))
     try:
-        ws = [T.read_point() for _ in points]
+        ws = [T.read_point() for _ in groups]
     except ValueError:
         return False
     if T.pos != len(T.data):
@@ -203,9 +222,9 @@ def verify_proof(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitme
     u = T.challenge()
     commitment_multi, eval_multi, witness, witness_with_aux = None, 0, None, None
     pu = 1
-    for pt, wi in zip(points, ws):
+    for (pt, group), wi in zip(groups.items(), ws):
         cb, eb, pv = None, 0, 1
-        for cm, e in groups[pt]:
+        for cm, e in group:
             cb = po.ec_add(C, cb, po.ec_mul(C, pv, cm))
             eb = (eb + pv * e) % p
             pv = pv * v % p
@@ -217,3 +236,17 @@ def verify_proof(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitme
     right = po.ec_add(C, po.ec_add(C, witness_with_aux, commitment_multi), po.ec_neg(C, po.ec_mul(C, eval_multi, g0)))
     # e(witness, [s]G2) == e(right, G2)
     return pr.pairing_product_is_one([(witness, s_g2), (po.ec_neg(C, right), g2)])
+
+
+def verify_proof_ipa(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitments, vk_repr: int, g_mont, g_lagrange_mont, u_mont, w_mont,
+                     instances: Sequence[Sequence[int]], proof: bytes, default_blind: int = ipa.DEFAULT_BLIND) -> bool:
+    """fixed_commitments, perm_commitments: ipa.blinded_key_commitments'."""
+    instance_commitments = [ipa.commit_reference(curve, g_lagrange_mont, w_mont, list(vals), default_blind) for vals in instances]
+    if None in instance_commitments:
+        return False
+    T = ReadTranscript(curve, proof)
+    try:
+        Q = read_plonk(T, curve, desc, k, fixed_commitments, perm_commitments, vk_repr, instances, instance_commitments)
+    except ValueError:
+        return False
+    return ipa.verify_multiopen(T, curve, g_mont, u_mont, w_mont, Q)

@@ -8,7 +8,7 @@ group-law cases of the final addition included; ParamsIPA's own table of W and a
 import numpy as np
 import pytest
 
-from test_ipa_proof import F, accepts, ipa_chain, mods, native_ipa  # noqa: F401  (fixtures and helpers of the IPA proof tests, reused as they are)
+from test_ipa_proof import F, accepts, ipa_chain, native_ipa  # noqa: F401  (fixtures and helpers of the IPA proof tests, reused as they are)
 
 CURVES = ["bn254", "pallas", "vesta"]
 COUNTS = [1, 2, 3, 4, 5, 63, 64, 65, 257]      # 4 scalars per block: one block short, full, one over; a wave's worth of blocks; many blocks
@@ -188,13 +188,13 @@ def test_params_ipa_owns_the_table_of_w(ctx, co, F, ipa_chain, native_ipa):
 
 
 @pytest.mark.gpu
-def test_k6_proof_through_the_table_is_accepted(po, co, F, mods, ipa_chain, native_ipa):
+def test_k6_proof_through_the_table_is_accepted(po, co, F, ipa_chain, native_ipa):
     from dehalo2_amd import native, prover
 
     c, d = ipa_chain(6, False), native_ipa(6, False)
     P = native.Prover(d["params"], d["pk"])
     proof = P.create_proof(c["adv"], [[]], prover.SeededRng(7)).finalize()
-    assert accepts(po, co, F, mods, c, proof)
+    assert accepts(po, c, proof)
     P.release()
 
 

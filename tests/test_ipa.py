@@ -1,7 +1,7 @@
 """IPACommitmentScheme over Vesta / Pallas: ParamsIPA from its parts, the generator collapse kernel and the opening argument
 (dehalo_params_ipa_create, dehalo_generator_collapse_device, dehalo_ipa_open).
 
-CPU: the Python restatement of the opening (tests/ipa_verifier.py) accepts its own reference proofs and rejects every altered byte.
+CPU: the Python restatement of the opening (oracle/ipa.py) accepts its own reference proofs and rejects every altered byte.
 GPU: the collapse against the C restatement of best_multiexp, element by element (edge cases included); device openings accepted by the
 verifier, byte-identical to the reference prover under the same seeded scalar stream, and rejected once tampered with."""
 import ctypes as C
@@ -18,8 +18,22 @@ def F(pkg):
 
 @pytest.fixture(scope="module")
 def IV(oracles):
-    import ipa_verifier      # (imports the oracle's modules: on the path once the oracles fixture has loaded them)
-    return ipa_verifier
+    import ipa      # (the oracle's modules are on the path once the oracles fixture has loaded them)
+    return ipa
+
+
+def reference_opening(curve, g, u, w, poly, blind, x3, draw):
+    """a stand-alone opening: ipa.open_reference on a fresh transcript"""
+    import ipa
+    import plonk_oracle
+    return ipa.open_reference(plonk_oracle.Transcript(curve), curve, g, u, w, poly, blind, x3, draw)
+
+
+def opening_accepted(curve, g, u, w, P, x3, v, proof):
+    """a stand-alone opening's bytes, read through a fresh transcript"""
+    import ipa
+    import verifier
+    return ipa.verify_opening(verifier.ReadTranscript(curve, proof), curve, g, u, w, P, x3, v)
 
 
 def _srs(co, F, curve_spec, k, seed=7):
@@ -44,19 +58,19 @@ def test_reference_opening_verifies_and_tampering_is_rejected(IV, pkg, po, co, F
     g, u, w = _srs(co, F, cs, k)
     poly = _poly(F, cs, 1 << k, 10 + k)
     blind, x3 = 12345 + k, 0xABCDEF + k
-    proof = IV.open_reference(cs, curve, g, u, w, poly, blind, x3, SeededRng(3).scalars)
-    P = IV.commit_reference(co, cs, g, w, poly, blind)
+    proof = reference_opening(curve, g, u, w, poly, blind, x3, SeededRng(3).scalars)
+    P = IV.commit_reference(curve, g, w, poly, blind)
     v = po.eval_polynomial(curve.scalar, poly, x3)
     assert len(proof) == 32 + 64 * k + 64
-    assert IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, proof)
-    assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, (v + 1) % curve.scalar.p, proof)
-    assert not IV.verify_opening(co, cs, curve, g, u, w, P, (x3 + 1), v, proof)
-    assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, proof[:-1])
-    assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, proof + b"\0")
+    assert opening_accepted(curve, g, u, w, P, x3, v, proof)
+    assert not opening_accepted(curve, g, u, w, P, x3, (v + 1) % curve.scalar.p, proof)
+    assert not opening_accepted(curve, g, u, w, P, (x3 + 1), v, proof)
+    assert not opening_accepted(curve, g, u, w, P, x3, v, proof[:-1])
+    assert not opening_accepted(curve, g, u, w, P, x3, v, proof + b"\0")
     for i in range(len(proof)):
         bad = bytearray(proof)
         bad[i] ^= 1 << (i % 8)
-        assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, bytes(bad)), i
+        assert not opening_accepted(curve, g, u, w, P, x3, v, bytes(bad)), i
 
 
 def test_compute_b_is_the_folded_powers(IV, po):
@@ -171,26 +185,26 @@ def test_ipa_open_is_accepted_and_tampering_rejected(IV, pkg, ctx, po, co, F, k)
     d_poly = ctx.upload(cs.scalar.encode_many(poly))
     proof = prm.open(d_poly.data_ptr(), blind, x3, rng=SeededRng(11)).finalize()
     assert len(proof) == 32 + 64 * k + 64
-    P = IV.commit_reference(co, cs, g, w, poly, blind)
+    P = IV.commit_reference(curve, g, w, poly, blind)
     v = po.eval_polynomial(curve.scalar, poly, x3)
-    assert IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, proof)
+    assert opening_accepted(curve, g, u, w, P, x3, v, proof)
     # the same seed gives the same bytes; another seed other bytes, also accepted
     assert prm.open(d_poly.data_ptr(), blind, x3, rng=SeededRng(11)).finalize() == proof
     other = prm.open(d_poly.data_ptr(), blind, x3, rng=SeededRng(12)).finalize()
-    assert other != proof and IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, other)
+    assert other != proof and opening_accepted(curve, g, u, w, P, x3, v, other)
     # an altered S, L_j, R_j, c or f is rejected, as is a wrong claim
     for off in [0, 32, 32 + 32 * (k - 1), 32 + 64 * k - 32, len(proof) - 64, len(proof) - 32]:
         bad = bytearray(proof)
         bad[off + 3] ^= 0x10
-        assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, bytes(bad)), off
-    assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, (v + 1) % curve.scalar.p, proof)
-    assert not IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, proof[:-32])
+        assert not opening_accepted(curve, g, u, w, P, x3, v, bytes(bad)), off
+    assert not opening_accepted(curve, g, u, w, P, x3, (v + 1) % curve.scalar.p, proof)
+    assert not opening_accepted(curve, g, u, w, P, x3, v, proof[:-32])
     prm.release()
 
 
 @pytest.mark.gpu
 def test_ipa_open_matches_the_reference_prover(IV, pkg, ctx, po, co, F):
-    """Byte for byte against ipa_verifier.open_reference under the same PCG64 stream: draw order and transcript order pinned between the two."""
+    """Byte for byte against ipa.open_reference under the same PCG64 stream: draw order and transcript order pinned between the two."""
     from dehalo2_amd.prover import SeededRng
     cs, curve = F.VESTA, po.VESTA
     k = 5
@@ -202,7 +216,7 @@ def test_ipa_open_matches_the_reference_prover(IV, pkg, ctx, po, co, F):
     got = prm.open(d_poly.data_ptr(), blind, x3, rng=rng).finalize()
     after = rng.scalars(1)
     ref_rng = SeededRng(21)
-    want = IV.open_reference(cs, curve, g, u, w, poly, blind, x3, ref_rng.scalars)
+    want = reference_opening(curve, g, u, w, poly, blind, x3, ref_rng.scalars)
     assert got == want
     assert np.array_equal(after, ref_rng.scalars(1))      # the caller's generator moved past exactly the opening's draws
     prm.release()
@@ -219,9 +233,9 @@ def test_ipa_open_with_os_entropy(IV, pkg, ctx, po, co, F):
     d_poly = ctx.upload(cs.scalar.encode_many(poly))
     a = prm.open(d_poly.data_ptr(), blind, x3).finalize()
     b = prm.open(d_poly.data_ptr(), blind, x3).finalize()
-    P = IV.commit_reference(co, cs, g, w, poly, blind)
+    P = IV.commit_reference(curve, g, w, poly, blind)
     v = po.eval_polynomial(curve.scalar, poly, x3)
     assert a != b
-    assert IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, a)
-    assert IV.verify_opening(co, cs, curve, g, u, w, P, x3, v, b)
+    assert opening_accepted(curve, g, u, w, P, x3, v, a)
+    assert opening_accepted(curve, g, u, w, P, x3, v, b)
     prm.release()

@@ -1,7 +1,7 @@
 """Whole ProverIPA proofs over Vesta: blinded commitments (dehalo_blind_commitments_device), committed instance columns, ProverIPA's multiopen and the
 opening argument behind dehalo_create_proof with ParamsIPA.
 
-CPU: the Python restatement of the prover (tests/plonk_ipa_reference.py) is accepted by the restatement of the verifier (tests/plonk_ipa_verifier.py) at
+CPU: the Python restatement of the prover (oracle/plonk_oracle.py create_proof_ipa) is accepted by the restatement of the verifier (oracle/verifier.py) at
 k = 5 and 6 (and k = 9 with range lookups, the smallest size their table fits); every tampering is rejected; a proof made with Blind::default() = 0 is rejected by the verifier's 1; the query
 grouping is checked on a hand-written list.
 GPU: the blinding kernel against the C restatement of best_multiexp; native.Prover with ParamsIPA accepted at k = 6, 9, 11, 14, byte-identical to the
@@ -12,8 +12,6 @@ import ctypes as C
 import numpy as np
 import pytest
 
-S_TOXIC = 0x2468ACE02468ACE13579BDF13579BDF
-
 
 @pytest.fixture(scope="module")
 def F(pkg):
@@ -21,54 +19,33 @@ def F(pkg):
 
 
 @pytest.fixture(scope="module")
-def mods(oracles):
-    import plonk_ipa_reference as R      # (import the oracle's modules: on the path once the oracles fixture has loaded them)
-    import plonk_ipa_verifier as V
-    return R, V
-
-
-@pytest.fixture(scope="module")
-def ipa_chain(pkg, po, co, mods):
-    """(k, range_lookups) -> circuit, SRS (g_i = [s^i] G with its consistent g_lagrange; u, w as tests/test_ipa.py takes them), the oracle's key with
-    the commitments blinded by Blind::default(), advice."""
-    import plonk_oracle as PO
+def ipa_chain(pkg, po, co):
+    """(k, range_lookups) -> tests/proof_chains.py's IPA chain of circuits.synthesize(p, k, range_lookups, seed=3), with the circuit."""
+    import proof_chains as PC
     import shapes
     from dehalo2_amd import circuits
 
-    R, V = mods
     cache = {}
 
     def get(k, rl):
         if (k, rl) not in cache:
-            curve, cs = po.VESTA, pkg.fields.VESTA
-            circ = circuits.synthesize(curve.scalar.p, k, rl, seed=3)
+            circ = circuits.synthesize(po.VESTA.scalar.p, k, rl, seed=3)
             desc = shapes.maingate_description(rl)
             assert desc == circ.cs.description()
-            srs = PO.setup_srs(curve, k, S_TOXIC, 8)
-            uw = co.fixed_base_mul(cs.id, co.fill_scalars(cs.scalar.id, "uniform", 2, 7))
-            key = PO.keygen(curve, srs, desc, k, circ.fixed, circ.assembly.mapping, 8)
-            fc, pc = V.blinded_key_commitments(curve, cs, key, uw[1])
-            ipa_key = dict(key, fixed_commitments=fc, perm_commitments=pc)
-            rep = PO.transcript_repr(curve, ipa_key, circ.selectors)
-            Fl = PO.Fld(curve.scalar)
-            adv = np.stack([co.field_op(Fl.id, "to_mont", circ.advice[i]) for i in range(5)])
-            cache[(k, rl)] = dict(circ=circ, desc=desc, srs=srs, u=uw[0], w=uw[1], key=key, fc=fc, pc=pc, ipa_key=ipa_key, rep=rep, adv=adv, k=k)
+            cache[(k, rl)] = dict(PC.ipa_chain(po, co, desc, k, circ.fixed, circ.assembly.mapping, circ.advice, circ.selectors), circ=circ)
         return cache[(k, rl)]
 
     return get
 
 
-def reference_proof(po, F, mods, c, seed=7, default_blind=None, instances=([],)):
-    import plonk_oracle as PO
-    R, V = mods
-    kw = {} if default_blind is None else dict(default_blind=default_blind)
-    return R.create_proof(po.VESTA, F.VESTA, c["srs"], c["u"], c["w"], c["key"], c["adv"], [list(v) for v in instances], PO.ScalarStream(seed), c["rep"], 8, **kw)
+def reference_proof(po, c, instances=([],), **kw):
+    import proof_chains as PC
+    return PC.prove(po, c, instances, **kw)
 
 
-def accepts(po, co, F, mods, c, proof, instances=([],), desc=None):
-    R, V = mods
-    return V.verify_proof(co, po.VESTA, F.VESTA, desc if desc is not None else c["desc"], c["k"], c["fc"], c["pc"], c["rep"], c["srs"]["g"], c["srs"]["g_lagrange"],
-                          c["u"], c["w"], [list(v) for v in instances], proof)
+def accepts(po, c, proof, instances=([],)):
+    import proof_chains as PC
+    return PC.accepts(po, c, proof, instances)
 
 
 def layout(po, c, k):
@@ -94,8 +71,8 @@ def tamperings(po, c, k, proof):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ CPU
-def test_grouping_on_a_hand_written_query_list(mods):
-    R, V = mods
+def test_grouping_on_a_hand_written_query_list(oracles):
+    import ipa as V
     x, xw, xi = "x", "omega x", "omega^-1 x"
     queries = [("a", x), ("b", x), ("b", xw), ("z", x), ("z", xw), ("p", x), ("p", xi), ("c", xw), ("b", x), ("s", x), ("d", xi), ("d", x)]
     commitments, point_sets = V.construct_intermediate_sets(queries)
@@ -105,8 +82,8 @@ def test_grouping_on_a_hand_written_query_list(mods):
     assert dict((key, pis) for key, _, pis in commitments)["b"] == [0, 1, 0] and dict((key, pis) for key, _, pis in commitments)["d"] == [2, 0]
 
 
-def test_lagrange_eval(mods, po):
-    R, V = mods
+def test_lagrange_eval(po):
+    import ipa as V
     p = po.VESTA.scalar.p
     poly = [5, 7, 11]
     pts = [3, 10, 77]
@@ -115,29 +92,34 @@ def test_lagrange_eval(mods, po):
 
 
 @pytest.mark.parametrize("k,rl", [(5, False), (6, False), (9, True)])
-def test_reference_proof_is_accepted_and_tampering_rejected(po, co, F, mods, ipa_chain, k, rl):
+def test_reference_proof_is_accepted_and_tampering_rejected(po, co, F, ipa_chain, k, rl):
     """k = 5 and 6 without range lookups; with them at k = 9, the smallest size circuits.synthesize takes (the range table alone has 339 rows: at k = 5
     and 6 it refuses with "k too small for the range table")."""
     c = ipa_chain(k, rl)
-    proof, trace = reference_proof(po, F, mods, c)
+    proof, trace = reference_proof(po, c)
     lo = layout(po, c, k)
     # {x}, {x, omega x}, {x, omega x, omega^last x} and, with lookups, {x, omega^-1 x}
     assert [len(ps) for ps in trace["point_sets"]] == ([1, 2, 3, 2] if rl else [1, 2, 3])
     assert len(proof) == 32 * (lo["points"] + lo["evals"] + 1 + len(trace["point_sets"]) + 1 + 2 * k + 2)
-    assert accepts(po, co, F, mods, c, proof)
+    assert accepts(po, c, proof)
     for name, bad in tamperings(po, c, k, proof).items():
-        assert not accepts(po, co, F, mods, c, bad), name
-    assert not accepts(po, co, F, mods, c, proof, instances=([1],))
+        assert not accepts(po, c, bad), name
+    assert not accepts(po, c, proof, instances=([1],))
 
 
-def test_default_blind_is_live(pkg, po, co, F, mods):
+def test_default_blind_is_live(pkg, po, co):
     """A prover that takes Blind::default() = 0 for the instance, fixed and sigma commitments is rejected by the verifier, which takes 1."""
-    R, V = mods
-    assert V.DEFAULT_BLIND == 1 and R.DEFAULT_BLIND is V.DEFAULT_BLIND
-    c, cs, fixed, asm, inst = _instance_chain(pkg, po, co, F, mods, 5)      # (a non-empty instance column: its bare MSM is not the identity)
-    assert accepts(po, co, F, mods, c, reference_proof(po, F, mods, c, instances=(inst,))[0], instances=(inst,))
-    assert not accepts(po, co, F, mods, c, reference_proof(po, F, mods, c, instances=(inst,), default_blind=0)[0], instances=(inst,))
-    assert not accepts(po, co, F, mods, c, reference_proof(po, F, mods, c, instances=(inst,))[0], instances=([5, 7, 10, 11],))
+    import inspect
+
+    import ipa
+    import plonk_oracle as PO
+    import verifier as V
+    assert ipa.DEFAULT_BLIND == 1      # ... which the prover and the verifier both take unless told otherwise
+    assert all(inspect.signature(fn).parameters["default_blind"].default is ipa.DEFAULT_BLIND for fn in (PO.create_proof_ipa, V.verify_proof_ipa, ipa.ProverIPA))
+    c, cs, fixed, asm, inst = _instance_chain(pkg, po, co, 5)      # (a non-empty instance column: its bare MSM is not the identity)
+    assert accepts(po, c, reference_proof(po, c, instances=(inst,))[0], instances=(inst,))
+    assert not accepts(po, c, reference_proof(po, c, instances=(inst,), default_blind=0)[0], instances=(inst,))
+    assert not accepts(po, c, reference_proof(po, c, instances=(inst,))[0], instances=([5, 7, 10, 11],))
 
 
 def test_ipa_proof_abi_is_refused_without_device(pkg):
@@ -238,7 +220,7 @@ def native_ipa(pkg, ctx, ipa_chain):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,rl", [(6, False), (9, True), (11, False), (14, True)])
-def test_native_ipa_proof_is_accepted(pkg, po, co, F, mods, ctx, ipa_chain, native_ipa, k, rl):
+def test_native_ipa_proof_is_accepted(pkg, po, co, F, ctx, ipa_chain, native_ipa, k, rl):
     import plonk_oracle as PO
     from dehalo2_amd import native, prover
 
@@ -250,10 +232,10 @@ def test_native_ipa_proof_is_accepted(pkg, po, co, F, mods, ctx, ipa_chain, nati
     lo = layout(po, c, k)
     assert len(proof) == P.proof_size()
     assert len(proof) == 32 * (lo["points"] + lo["evals"] + 1 + (4 if rl else 3) + 1 + 2 * k + 2)
-    assert accepts(po, co, F, mods, c, proof)
+    assert accepts(po, c, proof)
     if k <= 9:
         for name, bad in tamperings(po, c, k, proof).items():
-            assert not accepts(po, co, F, mods, c, bad), name
+            assert not accepts(po, c, bad), name
     t = P.last_timings()
     assert t["total"] > 0 and t["openings"] > 0
     P.release()
@@ -261,15 +243,14 @@ def test_native_ipa_proof_is_accepted(pkg, po, co, F, mods, ctx, ipa_chain, nati
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,rl", [(6, False), (9, True)])
-def test_native_ipa_proof_matches_the_reference(pkg, po, co, F, mods, ctx, ipa_chain, native_ipa, k, rl):
+def test_native_ipa_proof_matches_the_reference(pkg, po, co, F, ctx, ipa_chain, native_ipa, k, rl):
     """Byte for byte under SeededRng(7); the caller's generator ends where the reference's ends."""
     import plonk_oracle as PO
     from dehalo2_amd import native, prover
 
-    R, V = mods
     c, d = ipa_chain(k, rl), native_ipa(k, rl)
     ref = PO.ScalarStream(7)
-    want = R.create_proof(po.VESTA, F.VESTA, c["srs"], c["u"], c["w"], c["key"], c["adv"], [[]], ref, c["rep"], 8)[0]
+    want = PO.create_proof_ipa(po.VESTA, c["srs"], c["u"], c["w"], c["key"], c["adv"], [[]], ref, c["rep"], 8)[0]
     P = native.Prover(d["params"], d["pk"])
     rng = prover.SeededRng(7)
     got = P.create_proof(c["adv"], [[]], rng).finalize()
@@ -281,7 +262,7 @@ def test_native_ipa_proof_matches_the_reference(pkg, po, co, F, mods, ctx, ipa_c
 
 
 @pytest.mark.gpu
-def test_native_ipa_determinism_entropy_and_side_context(pkg, po, co, F, mods, ctx, ipa_chain, native_ipa):
+def test_native_ipa_determinism_entropy_and_side_context(pkg, po, co, F, ctx, ipa_chain, native_ipa):
     from dehalo2_amd import native, prover
 
     k, rl = 9, True
@@ -290,16 +271,16 @@ def test_native_ipa_determinism_entropy_and_side_context(pkg, po, co, F, mods, c
     a = P.create_proof(c["adv"], [[]], prover.SeededRng(7)).finalize()
     assert P.create_proof(c["adv"], [[]], prover.SeededRng(7)).finalize() == a
     b = P.create_proof(c["adv"], [[]], prover.SeededRng(8)).finalize()
-    assert b != a and accepts(po, co, F, mods, c, b)
+    assert b != a and accepts(po, c, b)
     p1, p2 = P.create_proof(c["adv"], [[]]).finalize(), P.create_proof(c["adv"], [[]]).finalize()
     assert p1 != p2 and len(p1) == len(a) == len(p2)
-    assert accepts(po, co, F, mods, c, p1) and accepts(po, co, F, mods, c, p2)
+    assert accepts(po, c, p1) and accepts(po, c, p2)
     side = pkg.Context(0)
     P2 = native.Prover(d["params"], d["pk"], ctx, side)
     for _ in range(2):
         assert P2.create_proof(c["adv"], [[]], prover.SeededRng(7)).finalize() == a
     p3 = P2.create_proof(c["adv"], [[]]).finalize()
-    assert p3 != a and accepts(po, co, F, mods, c, p3)
+    assert p3 != a and accepts(po, c, p3)
     P.release(); P2.release(); side.close()
 
 
@@ -322,34 +303,25 @@ def _instance_circuit(pkg, po, k):
     return cs, desc, inst, fixed, advice, plonk.Assembly(1, n)
 
 
-def _instance_chain(pkg, po, co, F, mods, k):
-    import plonk_oracle as PO
+def _instance_chain(pkg, po, co, k):
+    import proof_chains as PC
 
-    R, V = mods
-    curve, cs_ = po.VESTA, F.VESTA
     cs, desc, inst, fixed, advice, asm = _instance_circuit(pkg, po, k)
-    srs = PO.setup_srs(curve, k, S_TOXIC, 8)
-    uw = co.fixed_base_mul(cs_.id, co.fill_scalars(cs_.scalar.id, "uniform", 2, 7))
-    key = PO.keygen(curve, srs, desc, k, fixed, asm.mapping, 8)
-    fc, pc = V.blinded_key_commitments(curve, cs_, key, uw[1])
-    rep = PO.transcript_repr(curve, dict(key, fixed_commitments=fc, perm_commitments=pc))
-    c = dict(desc=desc, k=k, fc=fc, pc=pc, rep=rep, srs=srs, u=uw[0], w=uw[1], key=key)
-    c["adv"] = np.stack([co.field_op(PO.Fld(curve.scalar).id, "to_mont", advice[0])])
-    return c, cs, fixed, asm, inst
+    return PC.ipa_chain(po, co, desc, k, fixed, asm.mapping, advice), cs, fixed, asm, inst
 
 
 @pytest.mark.gpu
-def test_native_ipa_instance_column(pkg, po, co, F, mods, ctx):
+def test_native_ipa_instance_column(pkg, po, co, F, ctx):
     """The instance column is committed, absorbed as a point, evaluated first and queried first; another instance value is rejected."""
     import plonk_oracle as PO
     from dehalo2_amd import native, prover
 
     k = 6
-    c, cs, fixed, asm, inst = _instance_chain(pkg, po, co, F, mods, k)
+    c, cs, fixed, asm, inst = _instance_chain(pkg, po, co, k)
     srs, uw, rep, cs_ = c["srs"], (c["u"], c["w"]), c["rep"], F.VESTA
     # the reference prover and the verifier agree on this circuit first
-    want = reference_proof(po, F, mods, c, instances=(inst,))[0]
-    assert accepts(po, co, F, mods, c, want, instances=(inst,))
+    want = reference_proof(po, c, instances=(inst,))[0]
+    assert accepts(po, c, want, instances=(inst,))
     params = native.ParamsIPA.create(ctx, cs_, k, srs["g"], srs["g_lagrange"], uw[1], uw[0])
     pk = native.ProvingKey.keygen(ctx, params, cs, fixed, asm, ())
     pk.transcript_repr = rep
@@ -357,13 +329,13 @@ def test_native_ipa_instance_column(pkg, po, co, F, mods, ctx):
     proof = P.create_proof(c["adv"], [inst], prover.SeededRng(7)).finalize()
     assert len(proof) == P.proof_size()
     assert proof == want
-    assert accepts(po, co, F, mods, c, proof, instances=(inst,))
-    assert not accepts(po, co, F, mods, c, proof, instances=([5, 7, 10, 11],))
+    assert accepts(po, c, proof, instances=(inst,))
+    assert not accepts(po, c, proof, instances=([5, 7, 10, 11],))
     P.release(); pk.release(); params.release()
 
 
 @pytest.mark.gpu
-def test_kzg_proof_is_unchanged_after_an_ipa_proof(pkg, po, co, F, mods, ctx, ipa_chain, native_ipa):
+def test_kzg_proof_is_unchanged_after_an_ipa_proof(pkg, po, co, F, ctx, ipa_chain, native_ipa):
     """The untouched path: on the same context, after an IPA proof, a KZG proof at k = 9 under SeededRng(7) equals plonk_oracle.create_proof's bytes
     and has the length proof_size() reports."""
     import pairing as pr
@@ -373,7 +345,7 @@ def test_kzg_proof_is_unchanged_after_an_ipa_proof(pkg, po, co, F, mods, ctx, ip
 
     c, d = ipa_chain(6, False), native_ipa(6, False)
     P = native.Prover(d["params"], d["pk"])
-    assert accepts(po, co, F, mods, c, P.create_proof(c["adv"], [[]], prover.SeededRng(7)).finalize())
+    assert accepts(po, c, P.create_proof(c["adv"], [[]], prover.SeededRng(7)).finalize())
     P.release()
     k, rl, s = 9, True, 0x5EED
     oc = po.BN254

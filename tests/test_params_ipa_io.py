@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_ipa_proof import F, accepts, ipa_chain, mods      # noqa: F401  (fixtures and the verifier call of the ProverIPA tests)
+from test_ipa_proof import F, accepts, ipa_chain      # noqa: F401  (fixtures and the verifier call of the ProverIPA tests)
 
 NEW_SYMBOLS = ["dehalo_g_to_lagrange_device", "dehalo_params_ipa_from_g", "dehalo_params_ipa_size", "dehalo_params_ipa_write", "dehalo_params_ipa_read"]
 
@@ -112,7 +112,7 @@ def _prove(pkg, ctx, c, params):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("k", [6, 11])
-def test_from_g_write_read(pkg, po, co, F, mods, ctx, ipa_chain, k):
+def test_from_g_write_read(pkg, po, co, F, ctx, ipa_chain, k):
     from dehalo2_amd import keygen, native
     c = ipa_chain(k, False)
     cs = pkg.fields.VESTA
@@ -125,7 +125,7 @@ def test_from_g_write_read(pkg, po, co, F, mods, ctx, ipa_chain, k):
         # from_g == create with the oracle's g_lagrange: the same proof, accepted
         proof = _prove(pkg, ctx, c, made)
         assert proof == _prove(pkg, ctx, c, given)
-        assert accepts(po, co, F, mods, c, proof)
+        assert accepts(po, c, proof)
         # write() is the mirror's bytes; dehalo_params_size stays 0 for IPA params
         data = made.write()
         assert len(data) == 4 + 64 * (1 << k) + 64 == lib.dehalo_params_ipa_size(made.handle)

@@ -7,14 +7,15 @@ on for rows 8..27; one copy constraint ties a[8] to b[40].  With `fib` = a(w^2 X
   R9     R7 + q(w^3 X) q(w^-2 X) fib (holds wherever R5's does)  nine rotations, eight opening points
   R9all  R9 with q(w^3 X) q(w^-2 X) (a(w X) - a(X) - a(w^-1 X))  as well: a is read at -1, so all nine rotations are opening points and GWC divides in two launches
   Rlast  R5 + q (b(w^-(bf+1) X) - b(X))                          the query lands on the prover's own last rotation: still five
-CPU: the restatements' proofs of every circuit are accepted (KZG: oracle/plonk_oracle.py + oracle/verifier.py; IPA: tests/plonk_ipa_reference.py +
-tests/plonk_ipa_verifier.py) and a one-value tamper is rejected.
+CPU: the restatements' proofs of every circuit are accepted under both schemes (oracle/plonk_oracle.py + oracle/verifier.py, oracle/ipa.py) and a one-value
+tamper is rejected.
 GPU: native proofs byte-identical to the restatements', accepted, of proof_size() bytes; dehalo_eval_polynomial_points_device against the C restatement of
 eval_polynomial; a rotation-{-1, 0, 1} circuit still proves to the restatement's bytes."""
 import numpy as np
 import pytest
 
-S_TOXIC = 0x2468ACE02468ACE13579BDF13579BDF
+from proof_chains import S_TOXIC      # noqa: F401  (tests/test_check_witness.py takes it from here)
+
 NAMES = ["R5", "R7", "R9", "R9all", "Rlast"]
 Q_LO, Q_HI = 8, 28
 
@@ -90,33 +91,37 @@ def test_the_circuits_have_the_rotations_they_are_named_for(pkg):
     assert (1, -(cs.blinding_factors() + 1)) in cs.advice_queries
 
 
-@pytest.fixture(scope="module")
-def kzg_chain(pkg, po, co):
-    import pairing as pr
-    import plonk_oracle as PO
-
+def _chains(pkg, po, co, make):
+    """(name, k) -> tests/proof_chains.py's chain of build_circuit(name, k), with the circuit"""
     cache = {}
 
     def get(name, k):
         if (name, k) not in cache:
-            curve = po.BN254
             cs, fixed, advice, asm = build_circuit(pkg, name, k)
-            desc = cs.description()
-            srs = PO.setup_srs(curve, k, S_TOXIC, 8)
-            key = PO.keygen(curve, srs, desc, k, fixed, asm.mapping, 8)
-            rep = PO.transcript_repr(curve, key)
-            adv = np.stack([co.field_op(PO.Fld(curve.scalar).id, "to_mont", advice[i]) for i in range(2)])
-            want, _ = PO.create_proof(curve, srs, key, adv, [], PO.ScalarStream(7), rep, 8)
-            cache[(name, k)] = dict(cs=cs, fixed=fixed, asm=asm, desc=desc, srs=srs, key=key, rep=rep, adv=adv, want=want, k=k, s_g2=pr.g2_mul(S_TOXIC, pr.G2))
+            cache[(name, k)] = dict(make(po, co, cs.description(), k, fixed, asm.mapping, advice), cs=cs, fixed=fixed, asm=asm)
         return cache[(name, k)]
 
     return get
 
 
+@pytest.fixture(scope="module")
+def kzg_chain(pkg, po, co):
+    """... and `want`, the restatement's proof under ScalarStream(7)"""
+    import proof_chains as PC
+    get = _chains(pkg, po, co, PC.kzg_chain)
+
+    def with_proof(name, k):
+        c = get(name, k)
+        if "want" not in c:
+            c["want"] = PC.prove(po, c, [])[0]
+        return c
+
+    return with_proof
+
+
 def kzg_accepts(po, c, proof):
-    import pairing as pr
-    import verifier as V
-    return V.verify_proof(po.BN254, c["desc"], c["k"], c["key"]["fixed_commitments"], c["key"]["perm_commitments"], c["rep"], (1, 2), pr.G2, c["s_g2"], [], proof)
+    import proof_chains as PC
+    return PC.accepts(po, c, proof, [])
 
 
 def num_commitments(cs):
@@ -128,11 +133,10 @@ def num_evals(cs):
     return len(cs.advice_queries) + len(cs.fixed_queries) + 1 + len(cs.permutation_columns) + (3 * S - 1) + 5 * len(cs.lookups)
 
 
-def tampered(cs, proof):
-    """one evaluation (the second) with one bit flipped"""
-    bad = bytearray(proof)
-    bad[32 * num_commitments(cs) + 32 + 5] ^= 0x04
-    return bytes(bad)
+def tampered(c, proof):
+    import proof_chains as PC
+    assert c["key"]["shape"].num_advice + c["key"]["shape"].num_sets + 1 + (c["key"]["shape"].degree - 1) == num_commitments(c["cs"])      # (no lookups here)
+    return PC.tampered(c, proof)
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -141,7 +145,7 @@ def test_kzg_restatement_handles_the_circuit(pkg, po, kzg_chain, name):
     cs, proof = c["cs"], c["want"]
     assert len(proof) == 32 * (num_commitments(cs) + num_evals(cs) + len(opening_points_of(cs)))
     assert kzg_accepts(po, c, proof)
-    assert not kzg_accepts(po, c, tampered(cs, proof))
+    assert not kzg_accepts(po, c, tampered(c, proof))
 
 
 def test_kzg_restatement_rejects_a_broken_witness(pkg, po, co, kzg_chain):
@@ -155,38 +159,19 @@ def test_kzg_restatement_rejects_a_broken_witness(pkg, po, co, kzg_chain):
 
 
 @pytest.fixture(scope="module")
-def ipa_chain(pkg, po, co, oracles):
-    import plonk_ipa_verifier as V
-    import plonk_oracle as PO
-
-    cache = {}
-
-    def get(name, k):
-        if (name, k) not in cache:
-            curve, spec = po.VESTA, pkg.fields.VESTA
-            cs, fixed, advice, asm = build_circuit(pkg, name, k)
-            desc = cs.description()
-            srs = PO.setup_srs(curve, k, S_TOXIC, 8)
-            uw = co.fixed_base_mul(spec.id, co.fill_scalars(spec.scalar.id, "uniform", 2, 7))
-            key = PO.keygen(curve, srs, desc, k, fixed, asm.mapping, 8)
-            fc, pc = V.blinded_key_commitments(curve, spec, key, uw[1])
-            rep = PO.transcript_repr(curve, dict(key, fixed_commitments=fc, perm_commitments=pc))
-            adv = np.stack([co.field_op(PO.Fld(curve.scalar).id, "to_mont", advice[i]) for i in range(2)])
-            cache[(name, k)] = dict(cs=cs, fixed=fixed, asm=asm, desc=desc, srs=srs, u=uw[0], w=uw[1], key=key, fc=fc, pc=pc, rep=rep, adv=adv, k=k)
-        return cache[(name, k)]
-
-    return get
+def ipa_chain(pkg, po, co):
+    import proof_chains as PC
+    return _chains(pkg, po, co, PC.ipa_chain)
 
 
 def ipa_reference(pkg, po, c):
-    import plonk_ipa_reference as R
-    import plonk_oracle as PO
-    return R.create_proof(po.VESTA, pkg.fields.VESTA, c["srs"], c["u"], c["w"], c["key"], c["adv"], [], PO.ScalarStream(7), c["rep"], 8)
+    import proof_chains as PC
+    return PC.prove(po, c, [])
 
 
 def ipa_accepts(pkg, po, co, c, proof):
-    import plonk_ipa_verifier as V
-    return V.verify_proof(co, po.VESTA, pkg.fields.VESTA, c["desc"], c["k"], c["fc"], c["pc"], c["rep"], c["srs"]["g"], c["srs"]["g_lagrange"], c["u"], c["w"], [], proof)
+    import proof_chains as PC
+    return PC.accepts(po, c, proof, [])
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -198,7 +183,7 @@ def test_ipa_restatement_handles_the_circuit(pkg, po, co, ipa_chain, name):
     assert max(cs.num_advice_queries()) in [len(ps) for ps in trace["point_sets"]]
     assert len(proof) == 32 * (num_commitments(cs) + num_evals(cs) + 1 + len(trace["point_sets"]) + 1 + 2 * 6 + 2)
     assert ipa_accepts(pkg, po, co, c, proof)
-    assert not ipa_accepts(pkg, po, co, c, tampered(cs, proof))
+    assert not ipa_accepts(pkg, po, co, c, tampered(c, proof))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ GPU
