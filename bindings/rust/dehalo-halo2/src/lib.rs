@@ -8,6 +8,7 @@
 //!   `ParamsKZG::{setup, commit, commit_lagrange}` to [`params::DehaloParamsKZG`] (the SRS stays resident in HBM);
 //! * one call: replace the body of `plonk::create_proof` for `KZGCommitmentScheme<Bn256>` / `ProverGWC` / `Blake2bWrite` by [`prover::create_proof`]
 //!   (benches/delay_enc.rs:123-131), keys and SRS read from the same RawBytes files the bench caches (`:45,54,88,94-98,105,111-115`).
+//!   A front-end that proves with `ProverSHPLONK` takes [`prover::create_proof_shplonk`] (`DehaloProver::set_multiopen`).
 pub mod arithmetic;
 pub mod constraint_system;
 pub mod params;

@@ -130,6 +130,12 @@ impl<'c> DehaloProver<'c> {
         self.ctx.check(sys::dehalo_prover_set_shard(self.raw, rank, world, gather, user))
     }
 
+    /// Which KZG multiopen the proofs carry (`dehalo_prover_set_multiopen`): `sys::DEHALO_MULTIOPEN_GWC` (`ProverGWC`, the default) or
+    /// `sys::DEHALO_MULTIOPEN_SHPLONK` (`ProverSHPLONK`: two commitments whatever the circuit's rotations are).  Everything up to the evaluations is the same proof.
+    pub fn set_multiopen(&self, multiopen: i32) -> Result<(), DehaloError> {
+        self.ctx.check(unsafe { sys::dehalo_prover_set_multiopen(self.raw, multiopen) })
+    }
+
     /// `create_proof(&params, &pk, &[circuit], &[instances], rng, &mut transcript)` for ONE circuit: `advice` = what `circuit.synthesize` assigned
     /// (`num_advice x 2^k` Montgomery elements, column after column, host memory); returns the transcript bytes (`transcript.finalize()`).
     pub fn create_proof<R: RngCore + Send>(&self, advice: &[Fr], instances: &[&[Fr]], rng: &mut R) -> Result<Vec<u8>, DehaloError> {
@@ -197,6 +203,20 @@ pub fn create_proof<R: RngCore + Send>(device: i32, params_raw_bytes: &[u8], cs:
     let mut pk = DehaloProvingKey::keygen(&ctx, &params, cs, fixed, mapping, selectors)?;
     pk.set_transcript_repr(transcript_repr)?;
     let prover = DehaloProver::new(&ctx, Some(&side), &params, &pk)?;
+    prover.create_proof(advice, instances, rng)
+}
+
+/// The same flow for `plonk::create_proof::<KZGCommitmentScheme<Bn256>, ProverSHPLONK<_>, Challenge255<_>, _, Blake2bWrite<_, _, _>, _>`: one more call on the
+/// prover; verify with `VerifierSHPLONK`.
+pub fn create_proof_shplonk<R: RngCore + Send>(device: i32, params_raw_bytes: &[u8], cs: &ConstraintSystem<Fr>, fixed: &[Fr], mapping: &[u64], selectors: &[Vec<u8>],
+                                        transcript_repr: &Fr, advice: &[Fr], instances: &[&[Fr]], rng: &mut R) -> Result<Vec<u8>, DehaloError> {
+    let ctx = Context::new(device)?;
+    let side = Context::with_priority(device, 1)?;
+    let params = DehaloParamsKZG::read(&ctx, params_raw_bytes)?;
+    let mut pk = DehaloProvingKey::keygen(&ctx, &params, cs, fixed, mapping, selectors)?;
+    pk.set_transcript_repr(transcript_repr)?;
+    let prover = DehaloProver::new(&ctx, Some(&side), &params, &pk)?;
+    prover.set_multiopen(sys::DEHALO_MULTIOPEN_SHPLONK as i32)?;
     prover.create_proof(advice, instances, rng)
 }
 

@@ -23,13 +23,13 @@ SYMBOLS = [
     "dehalo_prefix_product_device", "dehalo_grand_product", "dehalo_grand_product_device", "dehalo_grand_product_batch_device",
     "dehalo_permute_expression_pair", "dehalo_permute_expression_pair_device", "dehalo_permute_expression_pair_batch_device", "dehalo_permute_expression_pair_ptrs_device", "dehalo_permute_expression_pair_distinct_device", "dehalo_permute_expression_pair_ptrs_deferred_device",
     "dehalo_convert_form_device", "dehalo_coset_ntt_form_device", "dehalo_coset_intt_form_device",
-    "dehalo_lincomb_device", "dehalo_scale_device", "dehalo_kate_division", "dehalo_kate_division_device", "dehalo_kate_division_batch_device",
+    "dehalo_lincomb_device", "dehalo_scale_device", "dehalo_kate_division", "dehalo_kate_division_device", "dehalo_kate_division_batch_device", "dehalo_vanishing_quotient_batch_device",
     "dehalo_params_create", "dehalo_params_setup", "dehalo_bases_register_device", "dehalo_params_read", "dehalo_params_size", "dehalo_params_write", "dehalo_params_release", "dehalo_params_commit_device",
     "dehalo_create_proof_circuit", "dehalo_create_proofs_circuit", "dehalo_keygen", "dehalo_pk_read", "dehalo_pk_size", "dehalo_pk_write", "dehalo_vk_size", "dehalo_vk_write", "dehalo_pk_set_transcript_repr",
     "dehalo_pk_get_transcript_repr", "dehalo_pk_info", "dehalo_pk_release", "dehalo_rng_scalars", "dehalo_field_info", "dehalo_synthesize",
     "dehalo_transcript_create", "dehalo_transcript_common_scalar", "dehalo_transcript_write_scalar", "dehalo_transcript_write_point",
     "dehalo_transcript_squeeze_challenge", "dehalo_transcript_len", "dehalo_transcript_finalize", "dehalo_transcript_release",
-    "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs",
+    "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs", "dehalo_prover_set_multiopen",
     "dehalo_params_ipa_create", "dehalo_params_scheme", "dehalo_generator_collapse_device", "dehalo_ipa_open", "dehalo_blind_commitments_device", "dehalo_prover_proof_size",
     "dehalo_g_to_lagrange_device", "dehalo_params_ipa_from_g", "dehalo_params_ipa_size", "dehalo_params_ipa_write", "dehalo_params_ipa_read",
     "dehalo_fixed_base_create", "dehalo_fixed_base_release", "dehalo_fixed_base_mul_device", "dehalo_fixed_base_blind_device", "dehalo_params_fixed_base",
@@ -219,6 +219,7 @@ def load_library():
     lib.dehalo_kate_division.argtypes = [P, C.c_int, u64p, sz, u64p, u64p]
     lib.dehalo_kate_division_device.argtypes = [P, C.c_int, u64p, sz, u64p, u64p, P]
     lib.dehalo_kate_division_batch_device.argtypes = [P, C.c_int, C.POINTER(C.c_void_p), sz, u64p, C.POINTER(C.c_void_p), sz, P]
+    lib.dehalo_vanishing_quotient_batch_device.argtypes = [P, C.c_int, C.POINTER(C.c_void_p), sz, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), sz, P]
     lib.dehalo_convert_form_device.argtypes = [P, C.c_int, u64p, u64p, sz, C.c_int, P]
     lib.dehalo_coset_ntt_form_device.argtypes = [P, C.c_int, u64p, u32, u64p, u32, u64p, u64p, sz, u32, P]
     lib.dehalo_coset_intt_form_device.argtypes = [P, C.c_int, u64p, u32, u64p, u64p, u64p, sz, u32, P]
@@ -285,6 +286,7 @@ def load_library():
     lib.dehalo_prover_proof_size.argtypes = [P]
     lib.dehalo_prover_proof_size.restype = sz
     lib.dehalo_prover_set_shard.argtypes = [P, C.c_uint32, C.c_uint32, GATHER_FN, P]
+    lib.dehalo_prover_set_multiopen.argtypes = [P, C.c_int]
     lib.dehalo_create_proofs.argtypes = [C.POINTER(C.c_void_p), u32, C.POINTER(C.c_void_p), u32, C.POINTER(CRng), u32, C.POINTER(C.c_void_p), sz, C.POINTER(sz)]
     lib.dehalo_timing_enable.argtypes = [P, C.c_int]
     lib.dehalo_timing_reset.argtypes = [P]
@@ -652,6 +654,17 @@ class Context:
         pts = _u64(points, 4)
         ta, tq = (C.c_void_p * max(1, len(d_a)))(*d_a), (C.c_void_p * max(1, len(d_q)))(*d_q)
         self._check(self.lib.dehalo_kate_division_batch_device(self.handle, field, ta, length, _ptr(pts), tq, len(d_a), stream or None))
+
+    def vanishing_quotient_batch_device(self, field: int, d_a: Sequence[int], length: int, point_sets: Sequence, d_q: Sequence[int], stream: int = 0):
+        """d_q[i] = d_a[i] div prod_t (X - point_sets[i][t]), remainder dropped, `length` coefficients written (the top len(point_sets[i]) zero): up to 8
+        polynomials a call, each with its own 1..32 distinct points (Montgomery, (m, 4) u64 each)."""
+        if len(point_sets) != len(d_a) or len(d_q) != len(d_a):
+            raise ValueError("vanishing_quotient_batch: one point set and one output per polynomial")
+        sets = [_u64(ps, 4) for ps in point_sets]
+        ta, tq = (C.c_void_p * max(1, len(d_a)))(*d_a), (C.c_void_p * max(1, len(d_q)))(*d_q)
+        tp = (C.c_void_p * max(1, len(sets)))(*[ps.ctypes.data for ps in sets])
+        nums = (C.c_uint32 * max(1, len(sets)))(*[ps.shape[0] for ps in sets])
+        self._check(self.lib.dehalo_vanishing_quotient_batch_device(self.handle, field, ta, length, tp, nums, tq, len(d_a), stream or None))
 
     def kate_division_device(self, field: int, d_a: int, length: int, point, d_q: int, stream: int = 0):
         self._check(self.lib.dehalo_kate_division_device(self.handle, field, d_a, length, _ptr(_u64(point, 4)), d_q, stream or None))

@@ -974,6 +974,52 @@ int dehalo_kate_division_batch_device(dehalo_ctx* ctx, int field, const uint64_t
     });
 }
 
+int dehalo_vanishing_quotient_batch_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_a, size_t len, const uint64_t* const* points, const uint32_t* num_points,
+                                           uint64_t* const* d_q, size_t count, void* stream) {
+    // every check and the weights come before the first launch: a refused call leaves the outputs untouched
+    if (count && (!d_a || !d_q || !points || !num_points)) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: null argument");
+    if (count > 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: at most 8 polynomials per call");
+    if (len > (1ull << 22)) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: polynomials of at most 2^22 coefficients");
+    const HostField* hf = host_field(field);
+    if (!hf || !field_ops(field)) return unknown_field(ctx);
+    size_t total = 0;
+    for (size_t y = 0; y < count; y++) {
+        if (num_points[y] == 0 || num_points[y] > 32) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: 1 to 32 points per polynomial");
+        if (!points[y] || ((!d_a[y] || !d_q[y]) && len)) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: null polynomial or point set");
+        if (d_a[y] == d_q[y]) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: a and q may not alias");
+        total += num_points[y];
+    }
+    return dh_guard(ctx, [&]() -> int {
+        // per point {z, w, z^2048}: w_t = 1 / prod_{s != t} (z_t - z_s), every denominator of the call inverted together (Montgomery's trick)
+        std::vector<Fe> tab(3 * total), pre(total);
+        Fe acc = hf->one;
+        size_t o = 0;
+        for (size_t y = 0; y < count; y++) {
+            const Fe* z = (const Fe*)points[y];
+            for (uint32_t t = 0; t < num_points[y]; t++, o++) {
+                Fe den = hf->one;
+                for (uint32_t s2 = 0; s2 < num_points[y]; s2++)
+                    if (s2 != t) den = hf->mul(den, hf->sub(z[t], z[s2]));
+                if (den.is_zero()) return dh_fail(ctx, DEHALO_ERR_INVALID, "vanishing_quotient_batch: two equal points in one set");
+                Fe z2048 = z[t];
+                for (int q = 0; q < 11; q++) z2048 = hf->sqr(z2048);
+                tab[3 * o] = z[t]; tab[3 * o + 1] = den; tab[3 * o + 2] = z2048;
+                pre[o] = acc;
+                acc = hf->mul(acc, den);
+            }
+        }
+        Fe inv = hf->invert(acc);
+        for (size_t i = total; i-- > 0;) {
+            const Fe w = hf->mul(inv, pre[i]);
+            inv = hf->mul(inv, tab[3 * i + 1]);
+            tab[3 * i + 1] = w;
+        }
+        return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+            return f.vanishing_quotient_batch(ctx, (const fe* const*)d_a, len, tab.empty() ? nullptr : tab[0].v, num_points, (fe* const*)d_q, count, s);
+        });
+    });
+}
+
 int dehalo_kate_division(dehalo_ctx* ctx, int field, const uint64_t* a, size_t len, const uint64_t point[4], uint64_t* q) {
     if (!ctx) return DEHALO_ERR_INVALID;
     if (((!a || !q) && len > 1) || !point) return dh_fail(ctx, DEHALO_ERR_INVALID, "kate_division: null argument");

@@ -685,7 +685,7 @@ template <class F>
 constexpr FieldOps make_field_ops() {
     return {&run_ntt_t<F>, &field_op_t<F>,
             &eval_poly_t<F>, &eval_poly_multi_t<F>, &eval_poly_points_t<F>, &batch_invert_t<F>, &prefix_product_one_t<F>, &grand_product_t<F>, &lincomb_t<F>, &scale_t<F>,
-            &kate_division_t<F>, &kate_division_batch_t<F>,
+            &kate_division_t<F>, &kate_division_batch_t<F>, &vanishing_quotient_batch_t<F>,
             &convert_form_t<F>, &graph_upload_t<F>, &graph_evaluate_t<F>, &graph_evaluate_batch_t<F>, &perm_h_t<F>, &lookup_h_t<F>, &lookup_h_batch_t<F>,
             &product_terms_t<F>, &graph_check_t<F>, &check_member_t<F>};
 }

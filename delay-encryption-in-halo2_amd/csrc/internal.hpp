@@ -358,6 +358,8 @@ struct FieldOps {
     int (*scale)(dehalo_ctx* ctx, fe* a, uint64_t len, const uint64_t* pattern, uint32_t period, const fe* d_factor, hipStream_t s);
     int (*kate_division)(dehalo_ctx* ctx, const fe* a, uint64_t len, const uint64_t pt[4], fe* q, hipStream_t s);
     int (*kate_division_batch)(dehalo_ctx* ctx, const fe* const* a, uint64_t len, const uint64_t* pts, fe* const* q, size_t count, hipStream_t s);
+    // q[y] = a[y] div prod_t (X - z_t) over polynomial y's m[y] points; h_tab: {z, w, z^2048} per point, on the host (capi.hip: the weights w)
+    int (*vanishing_quotient_batch)(dehalo_ctx* ctx, const fe* const* a, uint64_t len, const uint64_t* h_tab, const uint32_t* m, fe* const* q, size_t count, hipStream_t s);
     // quotient-numerator kernels (evalh.cuh)
     int (*convert_form)(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_internal, hipStream_t s);
     int (*graph_upload)(dehalo_ctx* ctx, dehalo_graph* g, const uint64_t* constants, hipStream_t s);

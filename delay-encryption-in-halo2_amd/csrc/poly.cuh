@@ -594,6 +594,136 @@ __global__ __launch_bounds__(POLY_THREADS) void k_kate_sums_batch(KateBatch B, u
     }
 }
 
+// ---- division by a point set's vanishing polynomial -----------------------------------------------------
+// q = a div Z, Z(X) = prod_t (X - z_t) over m <= 32 distinct points, the remainder dropped [UPSTREAM poly/kzg/multiopen/shplonk/prover.rs: the
+// quotient of a rotation set, there (sum_j y^j (P_j - R_j)) / Z by a chain of kate_division].  Partial fractions: 1 / Z = sum_t w_t / (X - z_t) with
+// w_t = 1 / prod_{s != t} (z_t - z_s), so q = sum_t w_t kate_division(a, z_t): m INDEPENDENT suffix scans E_t over one read of a, not m dependent
+// divisions that each read and write every coefficient.  q[i - 1] = sum_t w_t E_t(i) for 1 <= i <= len: q has len coefficients and the top m come
+// out as zero (sum_t w_t z_t^k = 0 for k < m - 1, and E_t(len) = 0) -- congruent to zero before the last reduction, which then stores 0.
+// One pass (k_vq_pass), kate_apply_body's structure with k_poly_eval_points' walk over the points: a thread keeps its 8 coefficients and 8 output sums
+// in registers and takes the points four at a time -- per point a Horner chain for the thread's sum, a 257-slot Hillis-Steele suffix scan in LDS
+// (slot 256 = the block's carry), and a second Horner walk that adds w_t E_t(i) to the output sums -- then stores every output once.  Longer than one
+// block: the same kernel first leaves every (point, block)'s sum S (SUMS: a pairwise tree in the place of the scan, no second walk), and the carries
+// C_b = E_S(b + 1) are one kate_apply_body per point over its S sequence at z^2048 (so len <= 2^22, as the batched division).
+// tab: per point of the launch {z, w, z^2048}, standard form; polynomial y's points are tab[first[y] .. first[y] + m[y]).
+#define POLY_VQ_MAX 8
+#define POLY_VQ_POINTS 32
+struct VqBatch { const fe* a[POLY_VQ_MAX]; fe* q[POLY_VQ_MAX]; u32 first[POLY_VQ_MAX], m[POLY_VQ_MAX]; };
+// output i of a quotient: the sum for index i goes to q[i - 1]; q[len - 1] is the empty sum E_t(len) = 0 at every point
+template <class F9>
+FP_DEV void vq_store(fe* q, u64 i, u64 len, const f29& sum) {
+    if (i >= 1 && i < len) {
+        f29 r = f29_mul<F9>(sum, f29_one<F9>());                                  // < 64p p / 2^261 + p < 2p: one conditional subtraction leaves it canonical
+        f_store(&q[i - 1], f29_pack(f29_cond_sub(r, F9::P)));
+    }
+    if (i + 1 == len) f_store(&q[i], f_zero());
+}
+// the body once per point of the group, i a constant: written out, because the unroller takes a loop over the points with two products in its body only in
+// part, and e[i] under a running i is an array in scratch
+#define VQ_POINT(I, ...) if ((I) < cnt) { constexpr int i = (I); __VA_ARGS__ }
+#define VQ_EACH_POINT(...) { VQ_POINT(0, __VA_ARGS__) VQ_POINT(1, __VA_ARGS__) VQ_POINT(2, __VA_ARGS__) VQ_POINT(3, __VA_ARGS__) }
+static_assert(POLY_MP_MAX == 4, "VQ_EACH_POINT writes out four points");
+// SUMS: the block sums only.  WIDE: some polynomial of the launch has more than four points, so the output sums wait in registers for the later groups;
+// otherwise (every set of the reference's circuits) a group is the whole sum and each output is stored from the walk: no eight sums to keep, 2 waves a SIMD, not 1.
+template <class F, bool SUMS, bool WIDE>
+__global__ __launch_bounds__(POLY_THREADS) void k_vq_pass(VqBatch B, u64 len, const fe* tab, const fe* carries, fe* S, u64 nb) {
+    typedef typename f29_of<F>::type F9;
+    constexpr u32 VQ_CONSTS = 11;                                                // per point of a group: x, w, then x^8, x^16, .., x^2048 (the scan's nine levels)
+    constexpr int NO = WIDE && !SUMS ? POLY_EVAL_EPT : 1;
+    __shared__ f29 sh[POLY_MP_MAX][POLY_THREADS + 1];
+    __shared__ f29 kc[POLY_MP_MAX][VQ_CONSTS];
+    const u32 t = threadIdx.x, y = blockIdx.y;
+    const fe* a = B.a[y];
+    fe* q = B.q[y];
+    const u32 m = B.m[y], first = B.first[y];                                    // (uniform in the block)
+    const u64 base = (u64)blockIdx.x * POLY_EVAL_TILE + (u64)t * POLY_EVAL_EPT;
+    f29 c[POLY_EVAL_EPT], o[NO];
+#pragma unroll
+    for (int j = 0; j < POLY_EVAL_EPT; j++) c[j] = base + j < len ? f29_unpack(f_load(&a[base + j])) : f29_zero();   // plain integers of the standard form, as in kate_apply_body
+#pragma unroll
+    for (int j = 0; j < NO; j++) o[j] = f29_zero();
+    for (u32 g = 0; g < m; g += POLY_MP_MAX) {
+        const u32 cnt = m - g < POLY_MP_MAX ? m - g : POLY_MP_MAX;
+        const fe* row = tab + (u64)(first + g) * 3;
+        __syncthreads();                                     // the previous group's scans and constants have been read
+        if (t < cnt * VQ_CONSTS) {                           // what is uniform in the block lives in LDS, not in every lane's registers
+            const u32 i = t / VQ_CONSTS, r = t % VQ_CONSTS;
+            f29 v = f29_from_std<F9>(f_load(&row[3 * i + (r == 1 ? 1 : 0)]));
+            for (u32 s = 2; s < r + 3 && r >= 2; s++) v = f29_sqr<F9>(v);         // r >= 2: x^(8 2^(r - 2)), the scan's factor at level r - 2
+            kc[i][r] = f29_norm(v);
+        }
+        __syncthreads();
+        f29 e[POLY_MP_MAX];
+#pragma unroll
+        for (int i = 0; i < POLY_MP_MAX; i++) e[i] = f29_zero();
+#pragma nounroll
+        for (int j = POLY_EVAL_EPT - 1; j >= 0; j--) {       // (rolled; c turns by one place a round so that no register is indexed by j, and is back in place after the eighth)
+            const f29 top = c[POLY_EVAL_EPT - 1];
+#pragma unroll
+            for (int r = POLY_EVAL_EPT - 1; r > 0; r--) c[r] = c[r - 1];
+            c[0] = top;
+            VQ_EACH_POINT(e[i] = f29_norm(f29_add(f29_mul<F9>(e[i], kc[i][0]), top));)
+        }
+        VQ_EACH_POINT(
+            sh[i][t] = e[i];
+            if (t == 0) sh[i][POLY_THREADS] = !SUMS && carries ? f29_unpack(f_load(&carries[(u64)(first + g + i) * nb + blockIdx.x])) : f29_zero();)
+        __syncthreads();
+        if (SUMS) {                                          // the block's sum at every point: k_kate_sums_batch's pairwise tree
+            for (u32 d = 1, lvl = 2; d < POLY_THREADS; d <<= 1, lvl++) {
+                if ((t & (2 * d - 1)) == 0) { VQ_EACH_POINT(sh[i][t] = f29_norm(f29_add(sh[i][t], f29_mul<F9>(sh[i][t + d], kc[i][lvl])));) }
+                __syncthreads();
+            }
+            if (t < cnt) {
+                f29 r = f29_mul<F9>(sh[t][0], f29_one<F9>());
+                f_store(&S[(u64)(first + g + t) * nb + blockIdx.x], f29_pack(f29_cond_sub(r, F9::P)));
+            }
+            continue;
+        }
+        for (u32 d = 1, lvl = 2; d <= POLY_THREADS; d <<= 1, lvl++) {
+            VQ_EACH_POINT(
+                e[i] = sh[i][t];
+                if (t + d <= POLY_THREADS) e[i] = f29_norm(f29_add(e[i], f29_mul<F9>(sh[i][t + d], kc[i][lvl])));)      // grows by < 2p per level
+            __syncthreads();
+            VQ_EACH_POINT(sh[i][t] = e[i];)
+            __syncthreads();
+        }
+#pragma unroll
+        for (int i = 0; i < POLY_MP_MAX; i++) e[i] = (u32)i < cnt ? sh[i][t + 1] : f29_zero();      // E at the end of this thread's coefficients
+#pragma nounroll
+        for (int j = POLY_EVAL_EPT - 1; j >= 0; j--) {       // (o, where it is kept, turns with c)
+            const f29 top = c[POLY_EVAL_EPT - 1];
+            f29 acc = o[NO - 1];
+#pragma unroll
+            for (int r = POLY_EVAL_EPT - 1; r > 0; r--) c[r] = c[r - 1];
+            c[0] = top;
+#pragma unroll
+            for (int r = NO - 1; r > 0; r--) o[r] = o[r - 1];
+            VQ_EACH_POINT(
+                e[i] = f29_norm(f29_add(f29_mul<F9>(e[i], kc[i][0]), top));        // E_t(base + j)
+                acc = f29_norm(f29_add(acc, f29_mul<F9>(kc[i][1], e[i])));)        // < 2p a term, 32 terms: < 64p << 2^261
+            if (WIDE) o[0] = acc;
+            else vq_store<F9>(q, base + j, len, acc);
+        }
+    }
+    if (SUMS || !WIDE) return;
+#pragma nounroll
+    for (int j = POLY_EVAL_EPT - 1; j >= 0; j--) {           // (rolled, o turning, as above)
+        const f29 top = o[NO - 1];
+#pragma unroll
+        for (int r = NO - 1; r > 0; r--) o[r] = o[r - 1];
+        o[0] = top;
+        vq_store<F9>(q, base + j, len, top);
+    }
+}
+#undef VQ_EACH_POINT
+#undef VQ_POINT
+// C[y][b] = E_S(b + 1) over point y's block sums at z_y^2048, b < nb - 1 (C[y][nb - 1] stays zero: nothing above the last block)
+template <class F>
+__global__ __launch_bounds__(POLY_THREADS) void k_vq_carries(const fe* tab, const fe* S, fe* C, u64 nb) {
+    const u32 y = blockIdx.y;
+    kate_apply_body<F>(S + (u64)y * nb, nb, f_load(&tab[(u64)y * 3 + 2]), nullptr, C + (u64)y * nb);
+}
+
 // ==========================================================================================
 // host drivers (instantiated once per field next to the NTT in ntt_<field>.hip)
 // ==========================================================================================
@@ -869,6 +999,35 @@ int kate_division_batch_t(dehalo_ctx* ctx, const fe* const* d_a, uint64_t len, c
     for (size_t y = 0; y < count; y++) { B2.a[y] = S + y * nb; B2.q[y] = C + y * nb; }
     k_kate_apply_batch<F><<<dim3(1, (u32)count), POLY_THREADS, 0, s>>>(B2, nb, pt2, nullptr, 0);       // C[y][b] = E_S(b + 1), b < nb - 1
     k_kate_apply_batch<F><<<dim3((u32)nb, (u32)count), POLY_THREADS, 0, s>>>(B, len, nullptr, C, nb);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// `count` <= POLY_VQ_MAX quotients by vanishing polynomials, polynomial y by that of its m[y] <= POLY_VQ_POINTS points: one launch up to 2048 coefficients,
+// three (sums, carries, pass) beyond; 1 <= len <= 2^22.  h_tab: {z, w, z^2048} per point on the HOST (capi.hip computes the weights), polynomial after polynomial.
+template <class F>
+int vanishing_quotient_batch_t(dehalo_ctx* ctx, const fe* const* d_a, uint64_t len, const uint64_t* h_tab, const uint32_t* m, fe* const* d_q, size_t count, hipStream_t s) {
+    if (len == 0 || count == 0) return 0;
+    ScopedTimer timer(ctx, s, DEHALO_K_POLY);
+    const uint64_t nb = (len + POLY_EVAL_TILE - 1) / POLY_EVAL_TILE;
+    VqBatch B{};
+    uint32_t total = 0;
+    for (size_t y = 0; y < count; y++) { B.a[y] = d_a[y]; B.q[y] = d_q[y]; B.first[y] = total; B.m[y] = m[y]; total += m[y]; }
+    TRY(dh_ensure(ctx, ctx->ws_poly[0], ((size_t)3 * total + (nb > 1 ? 2 * (size_t)total * nb : 0)) * sizeof(fe)));
+    fe* tab = (fe*)ctx->ws_poly[0].p;                     // [point][3]
+    fe* S = tab + (size_t)3 * total;                      // [point][nb]
+    fe* C = S + (size_t)total * nb;                       // [point][nb]
+    TRY(dh_h2d(ctx, tab, h_tab, (size_t)3 * total * sizeof(fe), s));
+    bool wide = false;                                   // more than one group of four points somewhere: the pass that keeps its output sums in registers
+    for (size_t y = 0; y < count; y++) wide = wide || m[y] > POLY_MP_MAX;
+    const dim3 grid((u32)nb, (u32)count);
+    if (nb > 1) {
+        k_vq_pass<F, true, false><<<grid, POLY_THREADS, 0, s>>>(B, len, tab, nullptr, S, nb);
+        HIP_TRY(ctx, hipMemsetAsync(C, 0, (size_t)total * nb * sizeof(fe), s));
+        k_vq_carries<F><<<dim3(1, total), POLY_THREADS, 0, s>>>(tab, S, C, nb);
+    }
+    if (wide) k_vq_pass<F, false, true><<<grid, POLY_THREADS, 0, s>>>(B, len, tab, nb > 1 ? C : nullptr, nullptr, nb);
+    else k_vq_pass<F, false, false><<<grid, POLY_THREADS, 0, s>>>(B, len, tab, nb > 1 ? C : nullptr, nullptr, nb);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

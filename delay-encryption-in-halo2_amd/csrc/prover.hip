@@ -1,5 +1,5 @@
-// prover.hip -- create_proof behind the C ABI (KZG / GWC and IPA) [UPSTREAM halo2_proofs @ v2023_04_20: plonk/prover.rs,
-// plonk/{lookup,permutation,vanishing}/prover.rs, poly/kzg/multiopen/gwc/prover.rs, poly/ipa/multiopen/prover.rs] -- the call the reference makes at
+// prover.hip -- create_proof behind the C ABI (KZG / GWC or SHPLONK, and IPA) [UPSTREAM halo2_proofs @ v2023_04_20: plonk/prover.rs,
+// plonk/{lookup,permutation,vanishing}/prover.rs, poly/kzg/multiopen/{gwc,shplonk}/prover.rs, poly/ipa/multiopen/prover.rs] -- the call the reference makes at
 // benches/delay_enc.rs:120-134 (create_proof into a Blake2bWrite transcript).  dehalo_prover: what outlives a proof; ProofRun: one proof, a function per phase.
 //
 // Every C entry point runs its body under dh_guard (guard.hpp): an exception leaves as DEHALO_ERR_OOM (std::bad_alloc) or DEHALO_ERR_INVALID, never as an exception.
@@ -66,12 +66,18 @@ struct dehalo_prover {
     uint32_t bi_adv = 0, bi_perm = 0, bi_prod = 0, bi_rand = 0, bi_h = 0, bi_hfold = 0, bi_f = 0, bi_def = 0, bi_count = 0;
     // the multiopen's plan [UPSTREAM poly/ipa/multiopen.rs construct_intermediate_sets]: the distinct commitments in order of first appearance, each with its
     // blind and its point set; the point sets in order of first appearance, each an ascending list of point indices (points numbered by first appearance)
-    struct IpaCommitment { const uint64_t* ptr; uint32_t blind, set; };
+    // (built for KZG provers too, as data: ProverSHPLONK opens by the same sets [UPSTREAM poly/kzg/multiopen/shplonk.rs construct_intermediate_sets].  Both identify
+    // a commitment by its polynomial; upstream's SHPLONK verifier compares points instead, so two identical fixed columns would make one commitment there)
+    // evals: per point of the commitment's set, in the set's order, where the polynomial's value there is (opening-plan index; -1: the folded h's)
+    struct IpaCommitment { const uint64_t* ptr; uint32_t blind, set; std::vector<int64_t> evals; };
     std::vector<IpaCommitment> ipa_commitments;
     std::vector<std::vector<uint32_t>> ipa_sets;
     std::vector<int32_t> ipa_point_rot;      // point index -> rotation
     std::vector<int64_t> ipa_inst_write;     // the instance evaluations, written first
     const fe* blind_at(uint32_t i) const { return ipa ? ipa_blinds.at(i) : nullptr; }
+    // ---- ProverSHPLONK (dehalo_prover_set_multiopen; KZG only): per set its folded polynomial F_i and its quotient Q_i, then h and L; allocated at the first switch
+    int multiopen = DEHALO_MULTIOPEN_GWC;
+    DevMem shp_f, shp_q, shp_h, shp_l;
     // host staging
     std::vector<uint64_t> blind_host, host_aff, host_jac, host_evals;
     double timings[8] = {};
@@ -217,10 +223,10 @@ struct dehalo_prover {
             g->idx.push_back(q.i);
         }
         ipa_inst_write.clear();
-        if (ipa) {
-            // the queries in upstream's order: the instance columns' (default blind) in front of the others
+        {
+            // the queries in upstream's order: under IPA the instance columns' (default blind) in front of the others
             std::vector<Q> iq;
-            for (auto& q : cs.instance_q) {
+            if (ipa) for (auto& q : cs.instance_q) {
                 iq.push_back({q.rotation, col_ptr(instance, q.index, n), idx(b_inst, q.index, q.rotation), bi_def});
                 ipa_inst_write.push_back(iq.back().i);
             }
@@ -228,16 +234,19 @@ struct dehalo_prover {
             // construct_intermediate_sets
             ipa_commitments.clear(); ipa_sets.clear(); ipa_point_rot.clear();
             std::vector<std::vector<uint32_t>> cpoints;
+            std::vector<std::vector<int64_t>> cevals;
             for (auto& q : iq) {
                 uint32_t pi = (uint32_t)(std::find(ipa_point_rot.begin(), ipa_point_rot.end(), q.r) - ipa_point_rot.begin());
                 if (pi == ipa_point_rot.size()) ipa_point_rot.push_back(q.r);
                 size_t ci = 0;
                 while (ci < ipa_commitments.size() && !(ipa_commitments[ci].ptr == q.ptr && ipa_commitments[ci].blind == q.blind)) ci++;
                 if (ci == ipa_commitments.size()) {
-                    ipa_commitments.push_back({q.ptr, q.blind, 0});
+                    ipa_commitments.push_back({q.ptr, q.blind, 0, {}});
                     cpoints.push_back({});
+                    cevals.push_back({});
                 }
                 cpoints[ci].push_back(pi);
+                cevals[ci].push_back(q.i);
             }
             for (size_t ci = 0; ci < ipa_commitments.size(); ci++) {
                 std::vector<uint32_t> ps = cpoints[ci];
@@ -246,6 +255,7 @@ struct dehalo_prover {
                 const size_t si = (size_t)(std::find(ipa_sets.begin(), ipa_sets.end(), ps) - ipa_sets.begin());
                 if (si == ipa_sets.size()) ipa_sets.push_back(ps);
                 ipa_commitments[ci].set = (uint32_t)si;
+                for (uint32_t pt : ps) ipa_commitments[ci].evals.push_back(cevals[ci][(size_t)(std::find(cpoints[ci].begin(), cpoints[ci].end(), pt) - cpoints[ci].begin())]);
             }
         }
         hpiece0 = (size_t)idx(b_hp, 0, 0);
@@ -452,9 +462,20 @@ struct dehalo_prover {
         return 0;
     }
 
+    // the SHPLONK multiopen's buffers, sized from the plan: one folded polynomial and one quotient per point set, h, L
+    int alloc_shplonk() {
+        if (shp_l.p) return 0;      // (the last one allocated)
+        const size_t ns = ipa_sets.size();
+        TRY(shp_f.alloc(ctx, ns * n));
+        TRY(shp_q.alloc(ctx, ns * n));
+        TRY(shp_h.alloc(ctx, n));
+        TRY(shp_l.alloc(ctx, n));
+        return dehalo_ctx_synchronize(ctx);
+    }
+
     size_t proof_size() const {
         const size_t points = (size_t)A + 2 * L + S + L + 1 + pieces;
-        if (!ipa) return 32 * (points + groups.size() + write_idx.size());
+        if (!ipa) return 32 * (points + (multiopen == DEHALO_MULTIOPEN_SHPLONK ? 2 : groups.size()) + write_idx.size());      // SHPLONK: h and h'
         return 32 * (points + 2 + 2 * (size_t)k + ipa_inst_write.size() + write_idx.size() + ipa_sets.size() + 2);
     }
 };
@@ -999,6 +1020,93 @@ struct ProofRun {
         return p.commit(tr, p.wbuf.p, ng, false);
     }
 
+    // ---- ProverSHPLONK::create_proof [UPSTREAM poly/kzg/multiopen/shplonk/prover.rs]: two commitments whatever the rotations are.  Per rotation set i (the
+    // plan's sets: points T_i, polynomials P_ij in order of first appearance) F_i = sum_j y^j P_ij and Q_i = F_i div Z_i, Z_i = prod_{z in T_i} (X - z) -- upstream
+    // divides sum_j y^j (P_ij - R_ij), R_ij the polynomial of degree < |T_i| through P_ij's values on T_i: subtracting it only removes the remainder, which the
+    // division here drops.  h = sum_i v^i Q_i; then at u, with zdiff_i = prod_{z in super \ T_i} (u - z) and r_ij = R_ij(u),
+    //   L = sum_i v^i zdiff_i (F_i - sum_j y^j r_ij) - Z_T(u) h,  L(u) = 0,  h' = L / ((X - u) zdiff_0).
+    // Each committed polynomial is read once (into its F_i); the quotients come from one pass per eight sets (dehalo_vanishing_quotient_batch_device).
+    int open_shplonk() {
+        const Fe y_ = tr->squeeze();
+        const Fe v = tr->squeeze();
+        const size_t ns = p.ipa_sets.size();
+        std::vector<std::vector<Fe>> pts(ns), ycoef(ns);
+        std::vector<const uint64_t*> fptrs(ns), pt_ptrs(ns);
+        std::vector<uint64_t*> qptrs(ns);
+        std::vector<uint32_t> npts(ns);
+        for (size_t si = 0; si < ns; si++) {
+            std::vector<const uint64_t*> ptrs;
+            for (auto& cm : p.ipa_commitments)
+                if (cm.set == si) ptrs.push_back(cm.ptr);
+            ycoef[si] = powers(f, y_, ptrs.size());
+            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)ycoef[si].data(), ptrs.size(), n, p.shp_f.u64(si * n), nullptr, nullptr));
+            for (uint32_t pi : p.ipa_sets[si]) pts[si].push_back(d.rotate_omega(x, p.ipa_point_rot[pi]));
+            fptrs[si] = p.shp_f.u64(si * n); qptrs[si] = p.shp_q.u64(si * n); pt_ptrs[si] = pts[si][0].v; npts[si] = (uint32_t)pts[si].size();
+        }
+        for (size_t first = 0; first < ns; first += 8)      // (eight sets a launch; every Q_i comes out n coefficients long, its top |T_i| zero)
+            TRY(dehalo_vanishing_quotient_batch_device(ctx, fid, fptrs.data() + first, n, pt_ptrs.data() + first, npts.data() + first, qptrs.data() + first,
+                                                       std::min<size_t>(8, ns - first), nullptr));
+        const std::vector<Fe> vpow = powers(f, v, ns);
+        TRY(dehalo_lincomb_device(ctx, fid, (const uint64_t* const*)qptrs.data(), (const uint64_t*)vpow.data(), ns, n, p.shp_h.u64(), nullptr, nullptr));
+        TRY(p.commit(tr, p.shp_h.p, 1, false));      // (Blind::default() is dropped under KZG, as in GWC)
+        const Fe u_ = tr->squeeze();
+        // host: per set zdiff_i and the Lagrange basis of T_i at u, every denominator (and zdiff_0) inverted together
+        std::vector<Fe> super;
+        for (int32_t r : p.ipa_point_rot) super.push_back(d.rotate_omega(x, r));
+        Fe zt = f->one;
+        for (const Fe& z : super) zt = f->mul(zt, f->sub(u_, z));
+        std::vector<Fe> zdiff(ns, f->one), inv;      // inv: [zdiff_0 | per set, per point: prod_{s != t} (z_t - z_s)]
+        std::vector<std::vector<Fe>> basis(ns);      // prod_{s != t} (u - z_s), then times the inverted denominator
+        for (size_t si = 0; si < ns; si++) {
+            const std::vector<uint32_t>& T = p.ipa_sets[si];
+            for (uint32_t pi = 0; pi < super.size(); pi++)
+                if (std::find(T.begin(), T.end(), pi) == T.end()) zdiff[si] = f->mul(zdiff[si], f->sub(u_, super[pi]));
+            if (si == 0) inv.push_back(zdiff[0]);
+            for (size_t t = 0; t < T.size(); t++) {
+                Fe num = f->one, den = f->one;
+                for (size_t s2 = 0; s2 < T.size(); s2++)
+                    if (s2 != t) { num = f->mul(num, f->sub(u_, pts[si][s2])); den = f->mul(den, f->sub(pts[si][t], pts[si][s2])); }
+                basis[si].push_back(num);
+                inv.push_back(den);
+            }
+        }
+        {      // Montgomery's trick (u is none of the points and the points differ, but for a negligible probability: a zero here is refused, not divided by)
+            std::vector<Fe> pre(inv.size());
+            Fe acc = f->one;
+            for (size_t i = 0; i < inv.size(); i++) { pre[i] = acc; acc = f->mul(acc, inv[i]); }
+            if (acc.is_zero()) return dh_fail(ctx, DEHALO_ERR_INVALID, "shplonk: the challenge u is an opening point");
+            Fe a = f->invert(acc);
+            for (size_t i = inv.size(); i-- > 0;) { const Fe t = f->mul(a, pre[i]); a = f->mul(a, inv[i]); inv[i] = t; }
+        }
+        const Fe zdiff0_inv = inv[0];
+        // L's ns + 1 coefficients, already over zdiff_0, and its constant: sum_i v^i zdiff_i sum_j y^j r_ij, r_ij = sum_t basis_t eval_ij(z_t)
+        std::vector<const uint64_t*> lptrs(fptrs);
+        lptrs.push_back(p.shp_h.u64());
+        std::vector<Fe> lcoef(ns + 1);
+        Fe lconst = zero;
+        size_t io = 1;
+        for (size_t si = 0; si < ns; si++) {
+            for (Fe& b : basis[si]) b = f->mul(b, inv[io++]);
+            Fe rsum = zero;
+            size_t j = 0;
+            for (auto& cm : p.ipa_commitments) {
+                if (cm.set != si) continue;
+                Fe r = zero;
+                for (size_t t = 0; t < basis[si].size(); t++) r = f->add(r, f->mul(basis[si][t], cm.evals[t] >= 0 ? E[cm.evals[t]] : hfold_eval));
+                rsum = f->add(rsum, f->mul(ycoef[si][j++], r));
+            }
+            lcoef[si] = f->mul(f->mul(vpow[si], zdiff[si]), zdiff0_inv);
+            lconst = f->add(lconst, f->mul(lcoef[si], rsum));
+        }
+        lcoef[ns] = f->neg(f->mul(zt, zdiff0_inv));
+        TRY(dehalo_lincomb_device(ctx, fid, lptrs.data(), (const uint64_t*)lcoef.data(), ns + 1, n, p.shp_l.u64(), lconst.v, nullptr));
+        // h' = L / (X - u) into Q_0's buffer (read for the last time by h's fold): n - 1 coefficients under a top one that Q_0 left zero
+        const uint64_t* lp = p.shp_l.u64();
+        uint64_t* wp = p.shp_q.u64();
+        TRY(dehalo_kate_division_batch_device(ctx, fid, &lp, n, u_.v, &wp, 1, nullptr));
+        return p.commit(tr, p.shp_q.p, 1, false);
+    }
+
     void finish() {
         mark(6);
         p.timings[7] = ms_since(t_start);
@@ -1051,7 +1159,7 @@ struct ProofRun {
         x = tr->squeeze();
         TRY(evaluations());
         mark(5);
-        TRY(ipa ? open_ipa() : open_gwc());
+        TRY(ipa ? open_ipa() : p.multiopen == DEHALO_MULTIOPEN_SHPLONK ? open_shplonk() : open_gwc());
         finish();
         return 0;
     }
@@ -1108,6 +1216,22 @@ extern "C" int dehalo_prover_set_shard(dehalo_prover* p, uint32_t rank, uint32_t
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || world == 0 || rank >= world || (world > 1 && !gather)) return DEHALO_ERR_INVALID;
         p->shard_rank = rank; p->shard_world = world; p->shard_gather = world > 1 ? gather : nullptr; p->shard_user = user;
+        return 0;
+    });
+}
+
+extern "C" int dehalo_prover_set_multiopen(dehalo_prover* p, int multiopen) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p) return DEHALO_ERR_INVALID;
+        if (p->ipa) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "prover_set_multiopen: a prover over ParamsIPA has one multiopen");
+        if (multiopen != DEHALO_MULTIOPEN_GWC && multiopen != DEHALO_MULTIOPEN_SHPLONK) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "prover_set_multiopen: unknown multiopen");
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (multiopen == DEHALO_MULTIOPEN_SHPLONK) {
+            std::lock_guard<std::recursive_mutex> lc(p->ctx->mu);
+            (void)hipSetDevice(p->ctx->device);
+            TRY(p->alloc_shplonk());
+        }
+        p->multiopen = multiopen;
         return 0;
     });
 }

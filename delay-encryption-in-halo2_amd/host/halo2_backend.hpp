@@ -390,6 +390,9 @@ class Prover {
     }
     ~Prover() { dehalo_prover_release(p_); }
     Prover(const Prover&) = delete;
+    // create_proof::<_, ProverGWC<_>, ..> (DEHALO_MULTIOPEN_GWC, the default) or create_proof::<_, ProverSHPLONK<_>, ..> (DEHALO_MULTIOPEN_SHPLONK); KZG params only
+    void set_multiopen(dehalo_multiopen m) { be_.check(dehalo_prover_set_multiopen(p_, m)); }
+    size_t proof_size() const { return dehalo_prover_proof_size(p_); }
     // rng == nullptr: operating-system entropy (the reference's OsRng)
     void create_proof(const std::vector<Fe>& advice, const std::vector<std::vector<Fe>>& instances, dehalo_rng* rng, Blake2bWrite& transcript) const {
         std::vector<const uint64_t*> ip;

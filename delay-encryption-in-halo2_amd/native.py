@@ -403,12 +403,27 @@ def rng_writeback(rng, r: Optional[CRng]):
 class Prover:
     """dehalo_prover: the device buffers of one proof in flight; create_proof is ONE library call."""
 
-    def __init__(self, params: ParamsKZG, pk: ProvingKey, ctx: Optional[Context] = None, side_ctx: Optional[Context] = None):
+    MULTIOPEN = {"gwc": 0, "shplonk": 1}      # dehalo_multiopen
+
+    def __init__(self, params: ParamsKZG, pk: ProvingKey, ctx: Optional[Context] = None, side_ctx: Optional[Context] = None, multiopen: str = "gwc"):
+        """multiopen: which KZG multiopen the proofs carry, "gwc" (ProverGWC, the default) or "shplonk" (ProverSHPLONK); ParamsIPA takes "gwc" (unset) only."""
         self.params, self.pk = params, pk
         self.ctx = ctx if ctx is not None else pk.ctx
         self.side = side_ctx
         self.handle = C.c_void_p()
+        if multiopen not in self.MULTIOPEN:
+            raise ValueError("multiopen: 'gwc' or 'shplonk'")
         _check(self.ctx, load_library().dehalo_prover_create(self.ctx.handle, side_ctx.handle if side_ctx is not None else None, params.handle, pk.handle, C.byref(self.handle)))
+        if multiopen != "gwc":
+            try:
+                self.set_multiopen(multiopen)
+            except Exception:
+                self.release()
+                raise
+
+    def set_multiopen(self, multiopen):
+        """dehalo_prover_set_multiopen: "gwc" | "shplonk" (or the enum's value); DehaloError(-5) on a prover over ParamsIPA, (-1) for anything else."""
+        _check(self.ctx, load_library().dehalo_prover_set_multiopen(self.handle, self.MULTIOPEN.get(multiopen, multiopen)))
 
     def set_shard(self, rank: int, world: int, gather=None):
         """dehalo_prover_set_shard: this process runs the MSMs of its share of every multi-column commitment phase only; `gather(points, first, num)` --

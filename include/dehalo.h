@@ -336,6 +336,14 @@ int dehalo_kate_division_device(dehalo_ctx* ctx, int field, const uint64_t* d_a,
  * points = count x 4 u64 (ProverGWC::create_proof: one division per distinct opening point) */
 int dehalo_kate_division_batch_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_a, size_t len, const uint64_t* points, uint64_t* const* d_q,
                                       size_t count, void* stream);
+/* Division by a point set's vanishing polynomial: d_q[y] = d_a[y] div prod_t (X - points[y][t]), the remainder dropped, for up to 8 polynomials of `len`
+ * (<= 2^22) coefficients, polynomial y with its own 1 <= num_points[y] <= 32 DISTINCT points (points = HOST array of host pointers, num_points[y] x 4 u64
+ * each; d_a / d_q = HOST arrays of DEVICE pointers, no d_q[y] equal to d_a[y]).  d_q[y] receives all `len` coefficients: the top num_points[y] are written as
+ * zero, so a buffer of 2^k coefficients can go to a commitment as it is.  One pass over d_a[y] by partial fractions -- sum_t w_t kate_division(a, z_t) with
+ * w_t = 1 / prod_{s != t} (z_t - z_s), the weights computed on the host -- not num_points[y] dependent divisions (ProverSHPLONK::create_proof: one quotient
+ * per rotation set).  DEHALO_ERR_INVALID, before anything is launched, for count > 8, a null pointer, no or more than 32 points, or two equal points in a set. */
+int dehalo_vanishing_quotient_batch_device(dehalo_ctx* ctx, int field, const uint64_t* const* d_a, size_t len, const uint64_t* const* points,
+                                           const uint32_t* num_points, uint64_t* const* d_q, size_t count, void* stream);
 
 /* ---- quotient numerator: evaluate_h --------------------------------------
  * The row loops of halo2_proofs/src/plonk/evaluation.rs @ v2023_04_20 on device-resident
@@ -590,12 +598,20 @@ int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t
  * the same device; work no transcript challenge waits for (lagrange_to_coeff / coeff_to_extended of a phase's columns, the random
  * polynomial's commitment, the gate and table-value passes of evaluate_h) is queued there and runs beside the commitment phases.
  * Several provers over one key, each on its own context(s), may run concurrently from different threads (batch proving).
- * `params` decides the scheme: ParamsKZG -> ProverGWC, ParamsIPA (Pallas / Vesta) -> ProverIPA.  DEHALO_ERR_UNSUPPORTED: more than 32 distinct
+ * `params` decides the scheme: ParamsKZG -> ProverGWC (or ProverSHPLONK: dehalo_prover_set_multiopen), ParamsIPA (Pallas / Vesta) -> ProverIPA.  DEHALO_ERR_UNSUPPORTED: more than 32 distinct
  * rotations among the circuit's queries and the prover's own {0, 1, -1, -(blinding_factors + 1)} (either scheme). */
 int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out);
 int dehalo_prover_release(dehalo_prover* prover);
+/* Which KZG multiopen a prover over ParamsKZG writes [UPSTREAM poly/kzg/multiopen/{gwc,shplonk}]: ProverGWC (the default: one witness commitment per distinct
+ * opening point) or ProverSHPLONK (two commitments, h and h', whatever the circuit's rotations are).  Everything before the multiopen is the same proof.
+ * Takes the prover's lock (it waits for a proof in flight) and may be called again with either value; the SHPLONK buffers are allocated at the first switch
+ * to it.  Followed by dehalo_prover_proof_size, dehalo_create_proof(s)(_circuit) and a sharded prover alike (both commitments are single columns: nothing to
+ * split).  DEHALO_ERR_UNSUPPORTED for a prover over ParamsIPA, DEHALO_ERR_INVALID for any other value or a null prover. */
+typedef enum { DEHALO_MULTIOPEN_GWC = 0, DEHALO_MULTIOPEN_SHPLONK = 1 } dehalo_multiopen;
+int dehalo_prover_set_multiopen(dehalo_prover* prover, int multiopen);
 /* Byte length of one proof of this prover (its params' scheme, instance commitments and evaluations included); 0 for null.
  *   KZG / GWC: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + opening points) + 32 x evaluations
+ *   KZG / SHPLONK: the same with 2 in the place of the opening points
  *   IPA: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + 1 (f) + 1 (S) + 2 k) + 32 x (instance queries + evaluations + point sets + 2) */
 size_t dehalo_prover_proof_size(const dehalo_prover* prover);
 /* create_proof: one circuit, its instance columns, the caller's rng and transcript.
