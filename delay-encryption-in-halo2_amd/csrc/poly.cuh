@@ -197,8 +197,10 @@ __global__ __launch_bounds__(POLY_THREADS) void k_poly_eval_multi(PolyPtrs polys
             __syncthreads();
         }
         if (t == 0) {
+            // < 512 p p / 2^261 + p: below 2p for bn254 (2^261 mod p = 0.3 p), but up to 5p for the Pasta primes (2^261 mod p just below p, p / 2^261 = 1 / 128) --
+            // 2048 ones at the point 1 give 256 equal terms above p and a sum past 2p: the full reduction, as in k_poly_eval_points
             f29 r = f29_mul<F9>(sh[0], f29_one<F9>());
-            f_store(out, f29_pack(f29_cond_sub(r, F9::P)));
+            f_store(out, f29_to_packed_canon<F9>(r));
         }
     }
 }
