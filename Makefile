@@ -46,6 +46,11 @@ host_tsan: tests/native_host/host_sanitize.cpp $(CSRC)/witness.hip $(HDRS)
 msm_plan_check: tests/native_host/msm_plan_check.cpp $(CSRC)/msm_plan.hpp $(CSRC)/experiment_env.hpp $(CSRC)/field_constants.h
 	g++ -std=c++17 -O2 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/msm_plan_check tests/native_host/msm_plan_check.cpp
 
+# the prover's opening plan (csrc/opening_plan.hpp: host only) printed for the shapes on stdin under the same sanitizers (tests/test_opening_plan.py reads it);
+# -O0: the program runs for milliseconds, and builds in a fifth of the time
+opening_plan_check: tests/native_host/opening_plan_check.cpp $(CSRC)/opening_plan.hpp
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/opening_plan_check tests/native_host/opening_plan_check.cpp
+
 clean:
 	rm -rf $(LIB) $(OBJDIR) $(PKG)/host/example; $(MAKE) -C oracle clean
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check

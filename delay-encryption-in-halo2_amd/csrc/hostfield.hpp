@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "field_constants.h"
 
@@ -109,6 +110,23 @@ struct HostField {
         const uint64_t two[4] = {2, 0, 0, 0};
         sub_limbs(e, p, two);
         return pow(a, e);
+    }
+    // v[i] <- 1 / v[i] with one inversion (Montgomery's trick); false, and v untouched, if any element is zero
+    bool batch_invert(Fe* v, size_t count) const {
+        std::vector<Fe> pre(count);
+        Fe acc = one;
+        for (size_t i = 0; i < count; i++) {
+            if (v[i].is_zero()) return false;
+            pre[i] = acc;
+            acc = mul(acc, v[i]);
+        }
+        Fe inv = invert(acc);
+        for (size_t i = count; i-- > 0;) {
+            const Fe t = mul(inv, pre[i]);
+            inv = mul(inv, v[i]);
+            v[i] = t;
+        }
+        return true;
     }
     // 64 little-endian bytes taken as an integer, reduced mod p (FromUniformBytes<64>::from_uniform_bytes, Challenge255)
     Fe from_u512(const uint8_t b[64]) const {

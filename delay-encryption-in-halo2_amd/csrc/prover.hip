@@ -14,6 +14,7 @@
 #include <thread>
 #include <unordered_map>
 
+#include "opening_plan.hpp"
 #include "whole_call.hpp"
 
 namespace {
@@ -39,41 +40,22 @@ struct dehalo_prover {
     const dehalo_pk* pk = nullptr;
     const HostField* f = nullptr;
     size_t n = 0, m = 0, u = 0;
-    uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, I = 0, NC = 0, pieces = 0;
-    uint32_t o_adv = 0, o_perm = 0, o_pz = 0, o_lz = 0, o_rand = 0;
+    uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, I = 0, pieces = 0;
     DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, hfold, qbuf, wbuf, jac, evals, blind_dev, omega_col;
     fe* polys = nullptr;      // coefficient forms: polys_own with a side context, cols (in place) without
     std::vector<uint32_t> table_rep;      // per lookup: the first lookup with the same table expressions (shares its compressed table)
     // tables of fixed columns as distinct rows (lookup_permute.hip): per representative lookup one row index per distinct tuple of its table expressions' values over
     // the usable rows and the tuple's multiplicity, on the device; count 0: not such a table, or more distinct rows than the permutation's one-tile path takes
     struct TableRows { DevArray<uint32_t> d_rep, d_mult; uint32_t count = 0; };
-    // opening plan (depends on the circuit only)
-    static constexpr size_t MAX_ROTATIONS = 32;
-    std::vector<int32_t> rots;
+    // which value goes where in the evaluations and the multiopen (opening_plan.hpp: depends on the circuit only), with the column and blind layouts; plist: the
+    // device pointers in the plan's polynomial order, the folded h (plan.p_hfold, the last one) resolved to hfold
+    OpeningPlan plan;
     std::vector<const uint64_t*> plist;
-    std::vector<int64_t> write_idx;
-    std::vector<uint32_t> eval_wanted;     // per polynomial of plist: the rotations (bits, in `rots` order) anyone reads its value at
-    std::vector<uint8_t> eval_wanted8;     // the same as bytes, for the four-point evaluation (at most four rotations)
-    struct Group { int32_t rot; std::vector<const uint64_t*> ptrs; std::vector<int64_t> idx; };
-    std::vector<Group> groups;
-    std::vector<const uint64_t*> hp_ptrs;
-    size_t hpiece0 = 0, eval_count = 0;
     // ---- ProverIPA (params of DEHALO_SCHEME_IPA) ----
-    // One blind per commitment, in one device array: [advice A | permuted 2 L | products S + L | random 1 | h pieces | folded h | f | default x max(I, 1)].
-    // Everything up to the pieces is drawn before the first launch and uploaded with the blinding rows; the folded h's blind exists on the host only.
+    // One blind per commitment, in one device array laid out by the plan (bi_*).  Everything up to the pieces is drawn before the first launch and uploaded with the
+    // blinding rows; the folded h's blind exists on the host only.
     bool ipa = false;
     DevMem ipa_blinds, ipa_q, ipa_wa, ipa_wb, ipa_f, ipa_p;
-    uint32_t bi_adv = 0, bi_perm = 0, bi_prod = 0, bi_rand = 0, bi_h = 0, bi_hfold = 0, bi_f = 0, bi_def = 0, bi_count = 0;
-    // the multiopen's plan [UPSTREAM poly/ipa/multiopen.rs construct_intermediate_sets]: the distinct commitments in order of first appearance, each with its
-    // blind and its point set; the point sets in order of first appearance, each an ascending list of point indices (points numbered by first appearance)
-    // (built for KZG provers too, as data: ProverSHPLONK opens by the same sets [UPSTREAM poly/kzg/multiopen/shplonk.rs construct_intermediate_sets].  Both identify
-    // a commitment by its polynomial; upstream's SHPLONK verifier compares points instead, so two identical fixed columns would make one commitment there)
-    // evals: per point of the commitment's set, in the set's order, where the polynomial's value there is (opening-plan index; -1: the folded h's)
-    struct IpaCommitment { const uint64_t* ptr; uint32_t blind, set; std::vector<int64_t> evals; };
-    std::vector<IpaCommitment> ipa_commitments;
-    std::vector<std::vector<uint32_t>> ipa_sets;
-    std::vector<int32_t> ipa_point_rot;      // point index -> rotation
-    std::vector<int64_t> ipa_inst_write;     // the instance evaluations, written first
     const fe* blind_at(uint32_t i) const { return ipa ? ipa_blinds.at(i) : nullptr; }
     // ---- ProverSHPLONK (dehalo_prover_set_multiopen; KZG only): per set its folded polynomial F_i and its quotient Q_i, then h and L; allocated at the first switch
     int multiopen = DEHALO_MULTIOPEN_GWC;
@@ -93,183 +75,13 @@ struct dehalo_prover {
     std::mutex mu;      // one create_proof at a time per prover
 
     // Everything that is not plain device memory comes last and is declared in the reverse of the order it is released in: members are destroyed bottom-up, so the
-    // graphs go first, each behind a device synchronise, then the events, the page-locked buffers, the helper's stream, the tables' rows and the arrays above.
+    // events go first, then the page-locked buffers, the helper's stream, the tables' rows and the arrays above.
     std::vector<TableRows> table_rows;
     Stream hs;                     // a hipStreamSynchronize on the side stream holds that stream against the proving thread's launches (0.4 ms of the lookups' phase):
     Event ev_helper;               // the helper thread's upload runs on a stream of its own beside it, and the helper waits for ITS upload through this event
     Pinned<uint64_t> adv_pin;      // dehalo_create_proof_circuit: the advice columns the witness generator writes (page-locked, kept across proofs)
     Pinned<uint64_t> rand_pin;     // host-drawn random polynomial (page-locked: its upload is one DMA that holds no stream)
     Event ev_side, ev_inst, ev_ready[3];      // ev_ready: one per commitment phase
-    GraphPtr lookup_num, lookup_den;
-    std::vector<std::pair<GraphPtr, GraphPtr>> perm_graphs;      // per set: (denominator, numerator)
-
-    int build_product_graphs() {
-        const HostCS& cs = pk->cs;
-        const uint32_t chunk = cs.chunk_len(), nf = cs.num_fixed, npc = (uint32_t)cs.perm_cols.size();
-        auto kind = [](uint32_t k) { return k == DEHALO_COLUMN_ADVICE ? DEHALO_SRC_ADVICE : k == DEHALO_COLUMN_FIXED ? DEHALO_SRC_FIXED : DEHALO_SRC_INSTANCE; };
-        // fixed slots: [circuit fixed..., sigma_0.., omega column]; challenges: delta^j * beta per permutation column
-        for (uint32_t s = 0; s < S; s++) {
-            GraphBuilder gd(f), gn(f);
-            GSrc dacc{}, nacc{};
-            bool first = true;
-            for (uint32_t j = s * chunk; j < std::min((s + 1) * chunk, npc); j++) {
-                const auto& pc = cs.perm_cols[j];
-                GSrc col = gd.column(kind(pc.kind), pc.index);
-                GSrc t = gd.add_calc(DEHALO_CALC_MUL, GSrc{DEHALO_SRC_BETA, 0, 0}, gd.column(DEHALO_SRC_FIXED, nf + j));
-                t = gd.add_calc(DEHALO_CALC_ADD, gd.add_calc(DEHALO_CALC_ADD, col, t), GSrc{DEHALO_SRC_GAMMA, 0, 0});
-                dacc = first ? t : gd.add_calc(DEHALO_CALC_MUL, dacc, t);
-                col = gn.column(kind(pc.kind), pc.index);
-                t = gn.add_calc(DEHALO_CALC_MUL, GSrc{DEHALO_SRC_CHALLENGE, j, 0}, gn.column(DEHALO_SRC_FIXED, nf + npc));
-                t = gn.add_calc(DEHALO_CALC_ADD, gn.add_calc(DEHALO_CALC_ADD, col, t), GSrc{DEHALO_SRC_GAMMA, 0, 0});
-                nacc = first ? t : gn.add_calc(DEHALO_CALC_MUL, nacc, t);
-                first = false;
-            }
-            gd.add_calc(DEHALO_CALC_STORE, dacc);
-            gn.add_calc(DEHALO_CALC_STORE, nacc);
-            GraphPtr d, nn;
-            TRY(gd.compile(ctx, adopt(ctx, d)));
-            TRY(gn.compile(ctx, adopt(ctx, nn)));
-            perm_graphs.emplace_back(std::move(d), std::move(nn));
-        }
-        // advice slots: [compressed_input, compressed_table, permuted_input, permuted_table]
-        GraphBuilder gd(f), gn(f);
-        gd.add_calc(DEHALO_CALC_MUL, gd.add_calc(DEHALO_CALC_ADD, gd.column(DEHALO_SRC_ADVICE, 2), GSrc{DEHALO_SRC_BETA, 0, 0}),
-                    gd.add_calc(DEHALO_CALC_ADD, gd.column(DEHALO_SRC_ADVICE, 3), GSrc{DEHALO_SRC_GAMMA, 0, 0}));
-        gn.add_calc(DEHALO_CALC_MUL, gn.add_calc(DEHALO_CALC_ADD, gn.column(DEHALO_SRC_ADVICE, 0), GSrc{DEHALO_SRC_BETA, 0, 0}),
-                    gn.add_calc(DEHALO_CALC_ADD, gn.column(DEHALO_SRC_ADVICE, 1), GSrc{DEHALO_SRC_GAMMA, 0, 0}));
-        TRY(gd.compile(ctx, adopt(ctx, lookup_den)));
-        TRY(gn.compile(ctx, adopt(ctx, lookup_num)));
-        return 0;
-    }
-
-    // Which value goes where: the transcript's order of the evaluations [UPSTREAM plonk/prover.rs: advice, fixed, vanishing random_eval,
-    // permutation (sigma; products), lookups] and the opening queries grouped by point in order of first appearance [UPSTREAM
-    // permutation::Constructed::open, lookup::Evaluated::open, pk.permutation.open, vanishing::Evaluated::open; gwc/prover.rs].
-    int opening_plan() {
-        const HostCS& cs = pk->cs;
-        std::vector<int32_t> rs = {0, 1, -1, -(int32_t)(bf + 1)};
-        for (auto& q : cs.advice_q) rs.push_back(q.rotation);
-        for (auto& q : cs.fixed_q) rs.push_back(q.rotation);
-        if (ipa) for (auto& q : cs.instance_q) rs.push_back(q.rotation);      // QUERY_INSTANCE = true
-        std::sort(rs.begin(), rs.end());
-        rs.erase(std::unique(rs.begin(), rs.end()), rs.end());
-        if (rs.size() > MAX_ROTATIONS)      // (the evaluation's masks are 32 bits wide; rs holds the prover's own four rotations too)
-            return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, std::to_string(rs.size()) + " distinct opening rotations: more than " + std::to_string(MAX_ROTATIONS));
-        rots = rs;
-        const size_t nfix = cs.num_fixed, npc = cs.perm_cols.size();
-        hp_ptrs.clear();
-        for (uint32_t i = 0; i < pieces; i++) hp_ptrs.push_back((const uint64_t*)h.at(i * n));
-        plist.clear();
-        for (uint32_t c = 0; c < NC; c++) plist.push_back((const uint64_t*)(polys + c * n));
-        for (size_t c = 0; c < nfix; c++) plist.push_back(col_ptr(pk->fixed_polys, c, n));
-        for (size_t c = 0; c < npc; c++) plist.push_back(col_ptr(pk->perm_polys, c, n));
-        for (auto* p : hp_ptrs) plist.push_back(p);
-        if (ipa) for (uint32_t c = 0; c < I; c++) plist.push_back(col_ptr(instance, c, n));      // opened under IPA only
-        const size_t ntot = plist.size();
-        const size_t b_cols = 0, b_fixed = NC, b_sigma = NC + nfix, b_hp = NC + nfix + npc, b_inst = b_hp + pieces;
-        auto ridx = [&](int32_t r) { return (size_t)(std::find(rots.begin(), rots.end(), r) - rots.begin()); };
-        auto idx = [&](size_t base, size_t col, int32_t r) { return (int64_t)(ridx(r) * ntot + base + col); };
-        const int32_t last = -(int32_t)(bf + 1);
-        write_idx.clear();
-        for (auto& q : cs.advice_q) write_idx.push_back(idx(b_cols, o_adv + q.index, q.rotation));
-        for (auto& q : cs.fixed_q) write_idx.push_back(idx(b_fixed, q.index, q.rotation));
-        write_idx.push_back(idx(b_cols, o_rand, 0));                                   // vanishing: random_eval
-        for (size_t j = 0; j < npc; j++) write_idx.push_back(idx(b_sigma, j, 0));      // pk.permutation.evaluate
-        for (uint32_t s = 0; s < S; s++) {                                              // permutation products
-            write_idx.push_back(idx(b_cols, o_pz + s, 0));
-            write_idx.push_back(idx(b_cols, o_pz + s, 1));
-            if (s != S - 1) write_idx.push_back(idx(b_cols, o_pz + s, last));
-        }
-        for (uint32_t l = 0; l < L; l++) {                                              // lookups
-            const size_t zc = o_lz + l, ai = o_perm + 2 * l, ti = o_perm + 2 * l + 1;
-            write_idx.push_back(idx(b_cols, zc, 0));
-            write_idx.push_back(idx(b_cols, zc, 1));
-            write_idx.push_back(idx(b_cols, ai, 0));
-            write_idx.push_back(idx(b_cols, ai, -1));
-            write_idx.push_back(idx(b_cols, ti, 0));
-        }
-        struct Q { int32_t r; const uint64_t* ptr; int64_t i; uint32_t blind; };      // (blind: the commitment's, read by the IPA multiopen)
-        std::vector<Q> qs;
-        auto cptr = [&](size_t c) { return (const uint64_t*)(polys + c * n); };
-        for (auto& q : cs.advice_q) qs.push_back({q.rotation, cptr(o_adv + q.index), idx(b_cols, o_adv + q.index, q.rotation), bi_adv + q.index});
-        for (uint32_t s = 0; s < S; s++) {                                              // permutation::Constructed::open
-            qs.push_back({0, cptr(o_pz + s), idx(b_cols, o_pz + s, 0), bi_prod + s});
-            qs.push_back({1, cptr(o_pz + s), idx(b_cols, o_pz + s, 1), bi_prod + s});
-        }
-        for (int s = (int)S - 2; s >= 0; s--) qs.push_back({last, cptr(o_pz + s), idx(b_cols, o_pz + s, last), bi_prod + (uint32_t)s});      // sets.iter().rev().skip(1)
-        for (uint32_t l = 0; l < L; l++) {                                              // lookup::Evaluated::open
-            const size_t zc = o_lz + l, ai = o_perm + 2 * l, ti = o_perm + 2 * l + 1;
-            const uint32_t zb = bi_prod + S + l, ab = bi_perm + 2 * l, tb = bi_perm + 2 * l + 1;
-            qs.push_back({0, cptr(zc), idx(b_cols, zc, 0), zb});
-            qs.push_back({0, cptr(ai), idx(b_cols, ai, 0), ab});
-            qs.push_back({0, cptr(ti), idx(b_cols, ti, 0), tb});
-            qs.push_back({-1, cptr(ai), idx(b_cols, ai, -1), ab});
-            qs.push_back({1, cptr(zc), idx(b_cols, zc, 1), zb});
-        }
-        for (auto& q : cs.fixed_q) qs.push_back({q.rotation, col_ptr(pk->fixed_polys, q.index, n), idx(b_fixed, q.index, q.rotation), bi_def});
-        for (size_t j = 0; j < npc; j++) qs.push_back({0, col_ptr(pk->perm_polys, j, n), idx(b_sigma, j, 0), bi_def});      // pk.permutation.open
-        qs.push_back({0, hfold.u64(), -1, bi_hfold});                                  // vanishing::Evaluated::open: h, then the random polynomial
-        qs.push_back({0, cptr(o_rand), idx(b_cols, o_rand, 0), bi_rand});
-        groups.clear();
-        for (auto& q : qs) {
-            Group* g = nullptr;
-            for (auto& gg : groups)
-                if (gg.rot == q.r) { g = &gg; break; }
-            if (!g) {
-                groups.push_back(Group{q.r, {}, {}});
-                g = &groups.back();
-            }
-            g->ptrs.push_back(q.ptr);
-            g->idx.push_back(q.i);
-        }
-        ipa_inst_write.clear();
-        {
-            // the queries in upstream's order: under IPA the instance columns' (default blind) in front of the others
-            std::vector<Q> iq;
-            if (ipa) for (auto& q : cs.instance_q) {
-                iq.push_back({q.rotation, col_ptr(instance, q.index, n), idx(b_inst, q.index, q.rotation), bi_def});
-                ipa_inst_write.push_back(iq.back().i);
-            }
-            iq.insert(iq.end(), qs.begin(), qs.end());
-            // construct_intermediate_sets
-            ipa_commitments.clear(); ipa_sets.clear(); ipa_point_rot.clear();
-            std::vector<std::vector<uint32_t>> cpoints;
-            std::vector<std::vector<int64_t>> cevals;
-            for (auto& q : iq) {
-                uint32_t pi = (uint32_t)(std::find(ipa_point_rot.begin(), ipa_point_rot.end(), q.r) - ipa_point_rot.begin());
-                if (pi == ipa_point_rot.size()) ipa_point_rot.push_back(q.r);
-                size_t ci = 0;
-                while (ci < ipa_commitments.size() && !(ipa_commitments[ci].ptr == q.ptr && ipa_commitments[ci].blind == q.blind)) ci++;
-                if (ci == ipa_commitments.size()) {
-                    ipa_commitments.push_back({q.ptr, q.blind, 0, {}});
-                    cpoints.push_back({});
-                    cevals.push_back({});
-                }
-                cpoints[ci].push_back(pi);
-                cevals[ci].push_back(q.i);
-            }
-            for (size_t ci = 0; ci < ipa_commitments.size(); ci++) {
-                std::vector<uint32_t> ps = cpoints[ci];
-                std::sort(ps.begin(), ps.end());
-                ps.erase(std::unique(ps.begin(), ps.end()), ps.end());
-                const size_t si = (size_t)(std::find(ipa_sets.begin(), ipa_sets.end(), ps) - ipa_sets.begin());
-                if (si == ipa_sets.size()) ipa_sets.push_back(ps);
-                ipa_commitments[ci].set = (uint32_t)si;
-                for (uint32_t pt : ps) ipa_commitments[ci].evals.push_back(cevals[ci][(size_t)(std::find(cpoints[ci].begin(), cpoints[ci].end(), pt) - cpoints[ci].begin())]);
-            }
-        }
-        hpiece0 = (size_t)idx(b_hp, 0, 0);
-        eval_count = rots.size() * ntot;
-        eval_wanted.assign(ntot, 0);
-        auto want = [&](int64_t i) { if (i >= 0) eval_wanted[(size_t)i % ntot] |= 1u << ((size_t)i / ntot); };
-        for (int64_t i : write_idx) want(i);
-        for (int64_t i : ipa_inst_write) want(i);
-        for (auto& g : groups) for (int64_t i : g.idx) want(i);
-        for (uint32_t i = 0; i < pieces; i++) want((int64_t)hpiece0 + i);                // the pieces of h at x: the folded quotient's value
-        eval_wanted8.clear();
-        if (rots.size() <= 4) eval_wanted8.assign(eval_wanted.begin(), eval_wanted.end());
-        return 0;
-    }
 
     int init(dehalo_ctx* c, dehalo_ctx* s, const dehalo_params* pa, const dehalo_pk* key) {
         ctx = c; side = s; params = pa; pk = key; f = key->f;
@@ -281,12 +93,17 @@ struct dehalo_prover {
         u = n - (bf + 1);
         A = cs.num_advice; L = (uint32_t)cs.lookups.size(); S = cs.num_sets(); I = cs.num_instance;
         pieces = d.quotient_poly_degree;
-        NC = A + 2 * L + S + L + 1;
-        o_adv = 0; o_perm = A; o_pz = A + 2 * L; o_lz = A + 2 * L + S; o_rand = A + 2 * L + S + L;
         if ((size_t)pieces * n > m) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "quotient does not fit the extended domain");
-        bi_adv = 0; bi_perm = A; bi_prod = A + 2 * L; bi_rand = bi_prod + S + L; bi_h = bi_rand + 1; bi_hfold = bi_h + pieces; bi_f = bi_hfold + 1; bi_def = bi_f + 1;
-        bi_count = bi_def + std::max<uint32_t>(I, 1);
-        if (ipa) TRY(ipa_blinds.alloc(ctx, bi_count));
+        OpeningShape sh;      // (the plan before anything is allocated: it is host work, and a circuit it refuses costs nothing)
+        sh.k = k; sh.A = A; sh.num_fixed = cs.num_fixed; sh.I = I; sh.L = L; sh.S = S; sh.npc = (uint32_t)cs.perm_cols.size(); sh.bf = bf; sh.pieces = pieces;
+        sh.query_instance = ipa;
+        for (auto& q : cs.advice_q) sh.advice_q.push_back({q.index, q.rotation});
+        for (auto& q : cs.fixed_q) sh.fixed_q.push_back({q.index, q.rotation});
+        for (auto& q : cs.instance_q) sh.instance_q.push_back({q.index, q.rotation});
+        plan = OpeningPlan(sh);
+        if (!plan.error.empty()) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, plan.error);
+        const uint32_t NC = plan.NC;
+        if (ipa) TRY(ipa_blinds.alloc(ctx, plan.bi_count));
         TRY(cols.alloc(ctx, (size_t)NC * n));
         if (side) TRY(polys_own.alloc(ctx, (size_t)NC * n));
         polys = side ? polys_own.p : cols.p;
@@ -307,30 +124,35 @@ struct dehalo_prover {
         table_rep.clear();
         for (uint32_t l = 0; l < L; l++) table_rep.push_back(cs.table_representative(l));
         TRY(find_table_rows());
-        TRY(build_product_graphs());
-        TRY(opening_plan());
+        plist.clear();
+        for (uint32_t c = 0; c < NC; c++) plist.push_back((const uint64_t*)(polys + c * n));
+        for (uint32_t c = 0; c < cs.num_fixed; c++) plist.push_back(col_ptr(pk->fixed_polys, c, n));
+        for (uint32_t c = 0; c < sh.npc; c++) plist.push_back(col_ptr(pk->perm_polys, c, n));
+        for (uint32_t i = 0; i < pieces; i++) plist.push_back((const uint64_t*)h.at(i * n));
+        if (ipa) for (uint32_t c = 0; c < I; c++) plist.push_back(col_ptr(instance, c, n));      // opened under IPA only
+        plist.push_back(hfold.u64());      // plan.p_hfold
         // GWC: one folded polynomial and one witness per opening point (at least the four every circuit has)
-        const size_t ngroups = std::max<size_t>(4, groups.size());
+        const size_t ngroups = std::max<size_t>(4, plan.groups.size());
         TRY(qbuf.alloc(ctx, ngroups * n));
         TRY(wbuf.alloc(ctx, ngroups * n));
-        const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, (uint32_t)std::max<size_t>(8, groups.size())), std::max<uint32_t>(I, pieces));      // the most points one phase commits
+        const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, (uint32_t)std::max<size_t>(8, plan.groups.size())), std::max<uint32_t>(I, pieces));      // the most points one phase commits
         TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
         if (ipa) {      // the multiopen's buffers, sized from the constraint system: one polynomial per point set, twice more for the division chain
-            const size_t ns = ipa_sets.size();
+            const size_t ns = plan.point_sets.size();
             TRY(ipa_q.alloc(ctx, ns * n));
             TRY(ipa_wa.alloc(ctx, ns * n));
             TRY(ipa_wb.alloc(ctx, ns * n));
             TRY(ipa_f.alloc(ctx, n));
             TRY(ipa_p.alloc(ctx, n));
-            TRY(evals.alloc(ctx, eval_count + 8 + ns));
+            TRY(evals.alloc(ctx, plan.eval_count + 8 + ns));
         } else
-        TRY(evals.alloc(ctx, eval_count + 8));
+        TRY(evals.alloc(ctx, plan.eval_count + 8));
         for (Event* e : {&ev_ready[0], &ev_ready[1], &ev_ready[2], &ev_inst, &ev_side, &ev_helper}) HIP_TRY(ctx, make_event(*e, hipEventDisableTiming));
         HIP_TRY(ctx, make_pinned(rand_pin, (size_t)n * 32));
         if (side) HIP_TRY(ctx, make_stream(hs, hipStreamNonBlocking));
         host_aff.resize(8 * (size_t)maxpts);
         host_jac.resize(12 * (size_t)maxpts + 8 + L);
-        host_evals.resize(4 * eval_count);
+        host_evals.resize(4 * plan.eval_count);
         TRY(dehalo_ctx_synchronize(ctx));
         return 0;
     }
@@ -395,24 +217,16 @@ struct dehalo_prover {
         return 0;
     }
 
-    // Jacobian {x, y, z} (Montgomery, base field) -> affine on the HOST: one inversion per phase by Montgomery's trick (a dozen field
+    // Jacobian {x, y, z} (Montgomery, base field) -> affine on the HOST: one inversion per phase (HostField::batch_invert; a dozen field
     // multiplications per point, one exponentiation per call: ~15 us) instead of a 12 k-instruction safegcd chain on ONE lane of the MSM's last
     // kernel in front of every read-back (~50 us of device latency per commitment phase, six phases per proof).  false: a point at infinity.
     bool normalize_host(const uint64_t* jac, size_t count, uint64_t* affine_out) const {
         const HostField* fq = host_field(curve_base_field(pk->curve));
-        std::vector<Fe> z(count), pre(count);
-        Fe acc = fq->one;
+        std::vector<Fe> zinv(count);
+        for (size_t i = 0; i < count; i++) memcpy(zinv[i].v, jac + 12 * i + 8, 32);
+        if (!fq->batch_invert(zinv.data(), count)) return false;
         for (size_t i = 0; i < count; i++) {
-            memcpy(z[i].v, jac + 12 * i + 8, 32);
-            if (z[i].is_zero()) return false;
-            pre[i] = acc;
-            acc = fq->mul(acc, z[i]);
-        }
-        Fe inv = fq->invert(acc);
-        for (size_t i = count; i-- > 0;) {
-            const Fe zi = fq->mul(inv, pre[i]);
-            inv = fq->mul(inv, z[i]);
-            const Fe zi2 = fq->sqr(zi), zi3 = fq->mul(zi2, zi);
+            const Fe zi2 = fq->sqr(zinv[i]), zi3 = fq->mul(zi2, zinv[i]);
             Fe x, y;
             memcpy(x.v, jac + 12 * i, 32);
             memcpy(y.v, jac + 12 * i + 4, 32);
@@ -465,7 +279,7 @@ struct dehalo_prover {
     // the SHPLONK multiopen's buffers, sized from the plan: one folded polynomial and one quotient per point set, h, L
     int alloc_shplonk() {
         if (shp_l.p) return 0;      // (the last one allocated)
-        const size_t ns = ipa_sets.size();
+        const size_t ns = plan.point_sets.size();
         TRY(shp_f.alloc(ctx, ns * n));
         TRY(shp_q.alloc(ctx, ns * n));
         TRY(shp_h.alloc(ctx, n));
@@ -473,11 +287,7 @@ struct dehalo_prover {
         return dehalo_ctx_synchronize(ctx);
     }
 
-    size_t proof_size() const {
-        const size_t points = (size_t)A + 2 * L + S + L + 1 + pieces;
-        if (!ipa) return 32 * (points + (multiopen == DEHALO_MULTIOPEN_SHPLONK ? 2 : groups.size()) + write_idx.size());      // SHPLONK: h and h'
-        return 32 * (points + 2 + 2 * (size_t)k + ipa_inst_write.size() + write_idx.size() + ipa_sets.size() + 2);
-    }
+    size_t proof_size() const { return plan.proof_size(ipa ? OpeningPlan::IPA : multiopen == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC); }
 };
 
 namespace {
@@ -545,7 +355,7 @@ struct ProofRun {
 
     ProofRun(dehalo_prover& pv, dehalo_transcript* t, dehalo_rng* r)
         : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream.get()), ss(pv.side ? pv.side->stream.get() : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
-          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), pieces(pv.pieces), nco(pv.NC - 1),
+          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), pieces(pv.pieces), nco(pv.plan.NC - 1),
           rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1) {}
     ~ProofRun() {      // whatever path the proof took: the witness' copy (asynchronous) has landed before its pin goes, and the helper has finished
         if (pin_advice && pin_advice->p) (void)hipStreamSynchronize(ms);
@@ -575,17 +385,17 @@ struct ProofRun {
         rng.skip(n);                                             // the random polynomial: rng_poly's
         std::vector<Fe> late(1 + (size_t)pieces + (ipa ? 1 : 0));      // random_blind, h_blinds, (IPA) f_blind
         TRY(rng.scalars(late[0].v, late.size()));
-        bl.assign(p.bi_count, zero);
+        bl.assign(p.plan.bi_count, zero);
         if (ipa) {
             const Fe* B = (const Fe*)p.blind_host.data();
-            for (uint32_t i = 0; i < A; i++) bl[p.bi_adv + i] = B[c_adv + i];
-            for (uint32_t c = 0; c < 2 * L; c++) bl[p.bi_perm + c] = B[c_adv + c_advb + (size_t)(c / 2) * (2 * rows + 2) + 2 * rows + (c & 1)];
-            for (uint32_t s2 = 0; s2 < S + L; s2++) bl[p.bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
-            bl[p.bi_rand] = late[0];
-            for (uint32_t i = 0; i < pieces; i++) bl[p.bi_h + i] = late[1 + i];
-            bl[p.bi_f] = late[1 + pieces];
-            for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[p.bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
-            TRY(dh_h2d(ctx, p.ipa_blinds.p, bl.data(), (size_t)p.bi_count * 32, ctx->stream.get()));      // (waited for with the blinding rows, upload_blinds)
+            for (uint32_t i = 0; i < A; i++) bl[p.plan.bi_adv + i] = B[c_adv + i];
+            for (uint32_t c = 0; c < 2 * L; c++) bl[p.plan.bi_perm + c] = B[c_adv + c_advb + (size_t)(c / 2) * (2 * rows + 2) + 2 * rows + (c & 1)];
+            for (uint32_t s2 = 0; s2 < S + L; s2++) bl[p.plan.bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
+            bl[p.plan.bi_rand] = late[0];
+            for (uint32_t i = 0; i < pieces; i++) bl[p.plan.bi_h + i] = late[1 + i];
+            bl[p.plan.bi_f] = late[1 + pieces];
+            for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[p.plan.bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
+            TRY(dh_h2d(ctx, p.ipa_blinds.p, bl.data(), (size_t)p.plan.bi_count * 32, ctx->stream.get()));      // (waited for with the blinding rows, upload_blinds)
         }
         return 0;
     }
@@ -602,7 +412,7 @@ struct ProofRun {
         if (!device_rng) rc = rng_poly.scalars(p.rand_pin.get(), n);
         helper_ms[0] = ms_since(th0);
         if (!rc && side) {      // (without a side context only the draw is taken off the critical path; the upload is queued by the proving thread)
-            fe* dst = p.polys + (size_t)p.o_rand * n;
+            fe* dst = p.polys + (size_t)p.plan.o_rand * n;
             hipError_t e = hipSuccess;
             if (device_rng) rc = chacha_scalars_device(ctx, rng_poly, 1, dst, n, p.hs.get());
             else e = hipMemcpyAsync(dst, p.rand_pin.get(), n * 32, hipMemcpyHostToDevice, p.hs.get());
@@ -672,7 +482,7 @@ struct ProofRun {
             }
         }
         // IPA (QUERY_INSTANCE = true): commit_lagrange(instance, Blind::default()), absorbed as points
-        if (I && ipa) TRY(p.commit(tr, p.instance.p, I, true, nullptr, 0, p.blind_at(p.bi_def), false));
+        if (I && ipa) TRY(p.commit(tr, p.instance.p, I, true, nullptr, 0, p.blind_at(p.plan.bi_def), false));
         if (I) HIP_TRY(ctx, hipMemcpyAsync(p.instance_values.p, p.instance.p, (size_t)I * n * 32, hipMemcpyDeviceToDevice, ms));
         if (I && side) HIP_TRY(ctx, hipEventRecord(p.ev_inst.get(), ms));
         if (I && !side) TRY(dehalo_intt_scaled_device(ctx, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
@@ -702,16 +512,16 @@ struct ProofRun {
         if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
         const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin.get();      // (the witness generator's output is page-locked already)
         pin_advice.reset(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
-        fe* adv = p.cols.at((size_t)p.o_adv * n);
+        fe* adv = p.cols.at((size_t)p.plan.o_adv * n);
         if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
         else TRY(dh_h2d(ctx, adv, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
         if (flags & DEHALO_PROOF_ADVICE_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, (uint64_t*)adv, nullptr, (uint64_t*)adv, (size_t)A * n, nullptr));
         if (A) k_place_rows<<<(unsigned)((rows * A + 255) / 256), 256, 0, ms>>>(adv + u, n, p.blind_dev.p, (uint32_t)rows, A);
         if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[0].get(), ms));
         for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(p.pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(p.pk->fixed_cosets, i, m));
-        for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.o_adv + i, n)), adv_c.push_back(col_ptr(p.ext, p.o_adv + i, m));
+        for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.plan.o_adv + i, n)), adv_c.push_back(col_ptr(p.ext, p.plan.o_adv + i, m));
         for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(p.instance_values, i, n)), inst_c.push_back(col_ptr(p.ext, nco + i, m));
-        return p.commit(tr, adv, A, true, [this] { return after_advice_queued(); }, 0, p.blind_at(p.bi_adv));
+        return p.commit(tr, adv, A, true, [this] { return after_advice_queued(); }, 0, p.blind_at(p.plan.bi_adv));
     }
     int after_advice_queued() {
         if (I && side) {
@@ -719,7 +529,7 @@ struct ProofRun {
             TRY(dehalo_intt_scaled_device(side, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
             TRY(dehalo_coset_ntt_form_device(side, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         }
-        if (side) TRY(side_ntt(p.o_adv, A, p.ev_ready[0].get()));
+        if (side) TRY(side_ntt(p.plan.o_adv, A, p.ev_ready[0].get()));
         if (gates_early) {
             EvalIn e = coset_inputs();
             e.in.y = zero.v;
@@ -749,14 +559,14 @@ struct ProofRun {
         p.tk("compress queued");
         // the blinding rows [u, n) first: the permutation writes rows [0, u) only and ends with a read-back
         const fe* bl_perm = p.blind_dev.p + (size_t)A * rows;
-        k_place_rows<<<(unsigned)((rows * 2 * L + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.o_perm * n + u), n, bl_perm, (uint32_t)rows, 2 * L);
+        k_place_rows<<<(unsigned)((rows * 2 * L + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_perm * n + u), n, bl_perm, (uint32_t)rows, 2 * L);
         std::vector<const uint64_t*> pin, ptab;
         std::vector<uint64_t*> pout_in, pout_tab;
         for (uint32_t l = 0; l < L; l++) {
             pin.push_back(p.compressed.u64((size_t)2 * l * n));
             ptab.push_back(p.compressed.u64((size_t)(2 * p.table_rep[l] + 1) * n));
-            pout_in.push_back(p.cols.u64((size_t)(p.o_perm + 2 * l) * n));
-            pout_tab.push_back(p.cols.u64((size_t)(p.o_perm + 2 * l + 1) * n));
+            pout_in.push_back(p.cols.u64((size_t)(p.plan.o_perm + 2 * l) * n));
+            pout_tab.push_back(p.cols.u64((size_t)(p.plan.o_perm + 2 * l + 1) * n));
         }
         // status flags behind the 2 L points of this phase: the stream runs from the permutation straight into the commitment, the flags come back with the points
         std::vector<const uint32_t*> trep, tmult;
@@ -769,9 +579,9 @@ struct ProofRun {
                                                            reinterpret_cast<int32_t*>(p.jac.u64() + 12 * 2 * (size_t)L), nullptr));
         p.tk("permute queued");
         if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[1].get(), ms));
-        return p.commit(tr, p.cols.at((size_t)p.o_perm * n), 2 * L, true, side ? std::function<int()>([this] { return after_lookups_queued(); }) : nullptr, L, p.blind_at(p.bi_perm));
+        return p.commit(tr, p.cols.at((size_t)p.plan.o_perm * n), 2 * L, true, side ? std::function<int()>([this] { return after_lookups_queued(); }) : nullptr, L, p.blind_at(p.plan.bi_perm));
     }
-    int after_lookups_queued() { return side_ntt(p.o_perm, 2 * L, p.ev_ready[1].get()); }
+    int after_lookups_queued() { return side_ntt(p.plan.o_perm, 2 * L, p.ev_ready[1].get()); }
 
     // ---- grand products: permutation sets, then lookups; one batched inversion.  The random polynomial's values are the launch's last column
     // (cols[o_rand] sits right behind the products): its commitment is written with theirs
@@ -780,15 +590,15 @@ struct ProofRun {
         if (helper.joinable()) helper.join();              // (long finished: the draw takes 0.5 ms at k = 17 and started before the advice commitment)
         p.tk("helper joined");
         if (helper_rc.load()) return helper_rc.load();
-        fe* rl = p.cols.at((size_t)p.o_rand * n);
-        if (side) HIP_TRY(ctx, hipMemcpyAsync(rl, p.polys + (size_t)p.o_rand * n, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));      // (the helper put the coefficients there)
+        fe* rl = p.cols.at((size_t)p.plan.o_rand * n);
+        if (side) HIP_TRY(ctx, hipMemcpyAsync(rl, p.polys + (size_t)p.plan.o_rand * n, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));      // (the helper put the coefficients there)
         else {      // without a side context the coefficient forms live in `cols` itself: keep a copy for after the commitment
             if (device_rng) TRY(chacha_scalars_device(ctx, rng_poly, 1, rl, n, ms));
             else HIP_TRY(ctx, hipMemcpyAsync(rl, p.rand_pin.get(), n * 32, hipMemcpyHostToDevice, ms));      // (rand_pin: page-locked, the library's own)
             HIP_TRY(ctx, hipMemcpyAsync(p.wbuf.p, rl, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
         }
         TRY(dehalo_ntt_device(ctx, fid, (uint64_t*)rl, k, d.omega.v, 1, nullptr));
-        if (S + L == 0) return p.commit(tr, rl, 1, true, [this] { return restore_random(); }, 0, p.blind_at(p.bi_rand));
+        if (S + L == 0) return p.commit(tr, rl, 1, true, [this] { return restore_random(); }, 0, p.blind_at(p.plan.bi_rand));
         std::vector<Fe> chal(std::max<uint32_t>(npc, 1));
         Fe dj = beta;
         for (uint32_t j = 0; j < npc; j++) {
@@ -802,8 +612,8 @@ struct ProofRun {
         for (uint32_t l = 0; l < L; l++) {
             pA.push_back(col_ptr(p.compressed, 2 * l, n));
             pS.push_back(col_ptr(p.compressed, 2 * p.table_rep[l] + 1, n));
-            pa.push_back(col_ptr(p.cols, p.o_perm + 2 * l, n));
-            ps.push_back(col_ptr(p.cols, p.o_perm + 2 * l + 1, n));
+            pa.push_back(col_ptr(p.cols, p.plan.o_perm + 2 * l, n));
+            ps.push_back(col_ptr(p.cols, p.plan.o_perm + 2 * l + 1, n));
         }
         std::vector<Fe> set_factors(std::max<uint32_t>(S, 1));
         for (uint32_t s2 = 0; s2 < S; s2++) set_factors[s2] = chal[std::min<uint32_t>(s2 * cs.chunk_len(), npc ? npc - 1 : 0)];      // beta delta^(first column of the set)
@@ -816,23 +626,23 @@ struct ProofRun {
         pin.num_lookups = L;
         TRY(dehalo_product_terms_device(ctx, fid, &pin, n, p.num.u64(), p.den.u64(), n, nullptr));
         p.tk("product graphs queued");
-        TRY(dehalo_grand_product_batch_device(ctx, fid, p.num.u64(), p.den.u64(), n, S + L, n, p.cols.u64((size_t)p.o_pz * n), nullptr));
+        TRY(dehalo_grand_product_batch_device(ctx, fid, p.num.u64(), p.den.u64(), n, S + L, n, p.cols.u64((size_t)p.plan.o_pz * n), nullptr));
         for (uint32_t s = 1; s < S; s++)      // z_s starts where z_{s-1} ended: z = vec![last_z]
-            TRY(dehalo_scale_device(ctx, fid, p.cols.u64((size_t)(p.o_pz + s) * n), n, nullptr, 0, p.cols.u64((size_t)(p.o_pz + s - 1) * n + u), nullptr));
+            TRY(dehalo_scale_device(ctx, fid, p.cols.u64((size_t)(p.plan.o_pz + s) * n), n, nullptr, 0, p.cols.u64((size_t)(p.plan.o_pz + s - 1) * n + u), nullptr));
         // per column: bf blinding rows (n - bf .. n)
         const fe* bl_prod = p.blind_dev.p + (size_t)(A + 2 * L) * rows;
-        k_place_rows<<<(unsigned)(((size_t)bf * (S + L) + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.o_pz * n + (n - bf)), n, bl_prod, bf, S + L);
+        k_place_rows<<<(unsigned)(((size_t)bf * (S + L) + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_pz * n + (n - bf)), n, bl_prod, bf, S + L);
         if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[2].get(), ms));
-        return p.commit(tr, p.cols.at((size_t)p.o_pz * n), S + L + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.bi_prod));
+        return p.commit(tr, p.cols.at((size_t)p.plan.o_pz * n), S + L + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.plan.bi_prod));
     }
     int restore_random() {      // (queued behind the MSM's kernels on the same stream)
-        if (!side) HIP_TRY(ctx, hipMemcpyAsync(p.cols.at((size_t)p.o_rand * n), p.wbuf.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
+        if (!side) HIP_TRY(ctx, hipMemcpyAsync(p.cols.at((size_t)p.plan.o_rand * n), p.wbuf.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
         return 0;
     }
     int after_products_queued() {
         TRY(restore_random());
         if (!side) return 0;
-        TRY(side_ntt(p.o_pz, S + L, p.ev_ready[2].get()));
+        TRY(side_ntt(p.plan.o_pz, S + L, p.ev_ready[2].get()));
         // the lookups' (compressed input + beta)(compressed table + gamma) over the extended domain need theta, beta, gamma and the advice /
         // fixed cosets: all there -- on the side context, beside the products' commitment, instead of after y
         if (L) {
@@ -866,7 +676,7 @@ struct ProofRun {
         }
         if (S) {
             std::vector<const uint64_t*> z, pcols, sigma;
-            for (uint32_t s = 0; s < S; s++) z.push_back(col_ptr(p.ext, p.o_pz + s, m));
+            for (uint32_t s = 0; s < S; s++) z.push_back(col_ptr(p.ext, p.plan.o_pz + s, m));
             for (auto& pc : cs.perm_cols) pcols.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_c[pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_c[pc.index] : inst_c[pc.index]);
             for (uint32_t j = 0; j < npc; j++) sigma.push_back(col_ptr(p.pk->perm_cosets, j, m));
             const Fe beta_zeta = f->mul(beta, d.g_coset);
@@ -889,9 +699,9 @@ struct ProofRun {
             std::vector<dehalo_lookup_inputs> li;
             for (uint32_t l = first; l < std::min(L, first + 8); l++) {
                 dehalo_lookup_inputs q{};
-                q.product_coset = col_ptr(p.ext, p.o_lz + l, m);
-                q.permuted_input_coset = col_ptr(p.ext, p.o_perm + 2 * l, m);
-                q.permuted_table_coset = col_ptr(p.ext, p.o_perm + 2 * l + 1, m);
+                q.product_coset = col_ptr(p.ext, p.plan.o_lz + l, m);
+                q.permuted_input_coset = col_ptr(p.ext, p.plan.o_perm + 2 * l, m);
+                q.permuted_table_coset = col_ptr(p.ext, p.plan.o_perm + 2 * l + 1, m);
                 q.table_value = p.table_value.u64((size_t)l * m);
                 q.l0 = l0; q.l_last = l_last; q.l_active_row = l_active;
                 q.beta = beta.v; q.gamma = gamma.v; q.y = y.v;
@@ -903,29 +713,30 @@ struct ProofRun {
         TRY(dehalo_scale_device(ctx, fid, p.h.u64(), m, (const uint64_t*)d.t_inv.data(), (uint32_t)d.t_inv.size(), nullptr, nullptr));      // divide_by_vanishing_poly
         TRY(dehalo_coset_intt_form_device(ctx, fid, p.h.u64(), ek, d.ext_omega_inv.v, d.ext_ifft_divisor.v, d.g_coset.v, 1, DEHALO_FORM_IN_INTERNAL, nullptr));
         p.tk("quotient queued");
-        return p.commit(tr, p.h.p, pieces, false, nullptr, 0, p.blind_at(p.bi_h));
+        return p.commit(tr, p.h.p, pieces, false, nullptr, 0, p.blind_at(p.plan.bi_h));
     }
 
     // ---- evaluations, in upstream's order: every opened polynomial at every rotation in ONE call
     int evaluations() {
-        point.resize(p.rots.size());
-        for (size_t i = 0; i < p.rots.size(); i++) point[i] = d.rotate_omega(x, p.rots[i]);
-        if (p.rots.size() <= 4)
-            TRY(dehalo_eval_polynomial_multi_masked_device(ctx, fid, p.plist.data(), p.plist.size(), n, (const uint64_t*)point.data(), (uint32_t)p.rots.size(), p.eval_wanted8.data(),
+        const OpeningPlan& pl = p.plan;
+        point.resize(pl.rots.size());
+        for (size_t i = 0; i < pl.rots.size(); i++) point[i] = d.rotate_omega(x, pl.rots[i]);
+        if (pl.rots.size() <= 4)
+            TRY(dehalo_eval_polynomial_multi_masked_device(ctx, fid, p.plist.data(), pl.num_polys, n, (const uint64_t*)point.data(), (uint32_t)pl.rots.size(), pl.eval_wanted8.data(),
                                                            p.evals.u64(), nullptr));
         else      // gates that query rotations beyond {-1, 0, 1}: up to 32 points, every polynomial still read once
-            TRY(dehalo_eval_polynomial_points_device(ctx, fid, p.plist.data(), p.plist.size(), n, (const uint64_t*)point.data(), (uint32_t)p.rots.size(), p.eval_wanted.data(),
+            TRY(dehalo_eval_polynomial_points_device(ctx, fid, p.plist.data(), pl.num_polys, n, (const uint64_t*)point.data(), (uint32_t)pl.rots.size(), pl.eval_wanted.data(),
                                                      p.evals.u64(), nullptr));
         // the folded quotient h(X) = sum_i x^(n i) h_i(X) (opened below; its value at x comes from the pieces' values)
         xs = powers(f, f->pow_u64(x, (uint64_t)n), pieces);
-        TRY(dehalo_lincomb_device(ctx, fid, p.hp_ptrs.data(), (const uint64_t*)xs.data(), pieces, n, p.hfold.u64(), nullptr, nullptr));
+        TRY(dehalo_lincomb_device(ctx, fid, p.plist.data() + pl.p_hpiece, (const uint64_t*)xs.data(), pieces, n, p.hfold.u64(), nullptr, nullptr));
         p.tk("evaluations queued");
-        TRY(dehalo_download(ctx, p.evals.p, p.eval_count * 32, p.host_evals.data()));
+        TRY(dehalo_download(ctx, p.evals.p, pl.eval_count * 32, p.host_evals.data()));
         p.tk("evaluations on host");
         E = (const Fe*)p.host_evals.data();
-        hfold_eval = fold(f, xs.data(), E + p.hpiece0, pieces);
-        for (int64_t i : p.ipa_inst_write) tr->write_scalar(E[i]);      // (IPA: the instance evaluations come first)
-        for (int64_t i : p.write_idx) tr->write_scalar(E[i]);
+        hfold_eval = fold(f, xs.data(), E + pl.hpiece0, pieces);
+        for (int64_t i : pl.instance_write) tr->write_scalar(E[i]);      // (IPA: the instance evaluations come first)
+        for (int64_t i : pl.write) tr->write_scalar(E[i]);
         return 0;
     }
 
@@ -933,20 +744,20 @@ struct ProofRun {
     int open_ipa() {
         const Fe x1 = tr->squeeze();
         const Fe x2 = tr->squeeze();
-        bl[p.bi_hfold] = fold(f, xs.data(), &bl[p.bi_h], pieces);      // h's blinds fold with x^n as its pieces do
-        const size_t ns = p.ipa_sets.size();
+        bl[p.plan.bi_hfold] = fold(f, xs.data(), &bl[p.plan.bi_h], pieces);      // h's blinds fold with x^n as its pieces do
+        const OpeningPlan& pl = p.plan;
+        const size_t ns = pl.point_sets.size();
         // q_i = the set's polynomials folded with x_1 in commitment order (q <- x_1 q + poly), the blinds likewise
         std::vector<Fe> pblinds(1 + ns);      // of f and of every q_i
         size_t depth = 0;
         for (size_t si = 0; si < ns; si++) {
             std::vector<const uint64_t*> ptrs;
             std::vector<Fe> blinds;
-            for (auto& cm : p.ipa_commitments)
-                if (cm.set == si) { ptrs.push_back(cm.ptr); blinds.push_back(bl[cm.blind]); }
+            for (uint32_t ci : pl.set_members[si]) { ptrs.push_back(p.plist[pl.commitments[ci].poly]); blinds.push_back(bl[pl.commitments[ci].blind]); }
             const std::vector<Fe> coefs = powers(f, x1, ptrs.size(), true);
             pblinds[1 + si] = fold(f, coefs.data(), blinds.data(), ptrs.size());
             TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ptrs.size(), n, p.ipa_q.u64(si * n), nullptr, nullptr));
-            depth = std::max(depth, p.ipa_sets[si].size());
+            depth = std::max(depth, pl.point_sets[si].size());
         }
         // each q_i divided by (X - point) for every point of its set in turn, remainders dropped: one batched launch per division depth over the sets
         // that still have a point left (a division writes n - 1 coefficients: the top one of both buffers stays zero)
@@ -960,10 +771,10 @@ struct ProofRun {
             std::vector<Fe> pts;
             std::vector<size_t> which;
             for (size_t si = 0; si < ns; si++)
-                if (p.ipa_sets[si].size() > dd) {
+                if (pl.point_sets[si].size() > dd) {
                     ins.push_back(cur[si]);
                     outs.push_back((dd & 1 ? p.ipa_wb : p.ipa_wa).u64(si * n));
-                    pts.push_back(d.rotate_omega(x, p.ipa_point_rot[p.ipa_sets[si][dd]]));
+                    pts.push_back(d.rotate_omega(x, pl.point_rot[pl.point_sets[si][dd]]));
                     which.push_back(si);
                 }
             for (size_t first = 0; first < ins.size(); first += 8)      // (the batched division takes eight at a time)
@@ -973,10 +784,10 @@ struct ProofRun {
         }
         // f = the quotients folded with x_2; commit(f, f_blind)
         TRY(dehalo_lincomb_device(ctx, fid, cur.data(), (const uint64_t*)powers(f, x2, ns, true).data(), ns, n, p.ipa_f.u64(), nullptr, nullptr));
-        TRY(p.commit(tr, p.ipa_f.p, 1, false, nullptr, 0, p.blind_at(p.bi_f)));
+        TRY(p.commit(tr, p.ipa_f.p, 1, false, nullptr, 0, p.blind_at(p.plan.bi_f)));
         const Fe x3 = tr->squeeze();
         // q_i(x_3) for every set: one evaluation call, one download
-        fe* qe = p.evals.at(p.eval_count + 8);
+        fe* qe = p.evals.at(pl.eval_count + 8);
         TRY(dehalo_eval_polynomial_device(ctx, fid, p.ipa_q.u64(), n, n, ns, x3.v, (uint64_t*)qe, nullptr));
         std::vector<Fe> qev(ns);
         TRY(dehalo_download(ctx, qe, ns * 32, qev.data()));
@@ -985,7 +796,7 @@ struct ProofRun {
         // p = f, then p <- x_4 p + q_i over the sets; the blind likewise
         std::vector<const uint64_t*> ptrs = {p.ipa_f.u64()};
         for (size_t si = 0; si < ns; si++) ptrs.push_back(p.ipa_q.u64(si * n));
-        pblinds[0] = bl[p.bi_f];
+        pblinds[0] = bl[p.plan.bi_f];
         const std::vector<Fe> coefs = powers(f, x4, ns + 1, true);
         TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ns + 1, n, p.ipa_p.u64(), nullptr, nullptr));
         const Fe pblind = fold(f, coefs.data(), pblinds.data(), ns + 1);
@@ -999,21 +810,24 @@ struct ProofRun {
     int open_gwc() {
         const Fe v = tr->squeeze();
         p.tk("v");
-        const size_t ng = p.groups.size();
+        const OpeningPlan& pl = p.plan;
+        const size_t ng = pl.groups.size();
         HIP_TRY(ctx, hipMemsetAsync(p.wbuf.p, 0, std::max<size_t>(4, ng) * n * 32, ms));
         std::vector<const uint64_t*> qptrs;
         std::vector<uint64_t*> wptrs;
         std::vector<Fe> qpoints;
-        for (size_t gi = 0; gi < p.groups.size(); gi++) {
-            const dehalo_prover::Group& g = p.groups[gi];
-            const std::vector<Fe> coefs = powers(f, v, g.idx.size());
+        for (size_t gi = 0; gi < ng; gi++) {
+            const OpeningPlan::Group& g = pl.groups[gi];
+            const std::vector<Fe> coefs = powers(f, v, g.evals.size());
             std::vector<Fe> values;
-            for (int64_t i : g.idx) values.push_back(i >= 0 ? E[i] : hfold_eval);
+            for (int64_t i : g.evals) values.push_back(i >= 0 ? E[i] : hfold_eval);
             const Fe eval_batch = fold(f, coefs.data(), values.data(), values.size());
-            TRY(dehalo_lincomb_device(ctx, fid, g.ptrs.data(), (const uint64_t*)coefs.data(), g.ptrs.size(), n, p.qbuf.u64(gi * n), eval_batch.v, nullptr));
+            std::vector<const uint64_t*> ptrs;
+            for (uint32_t id : g.polys) ptrs.push_back(p.plist[id]);
+            TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)coefs.data(), ptrs.size(), n, p.qbuf.u64(gi * n), eval_batch.v, nullptr));
             qptrs.push_back(p.qbuf.u64(gi * n));
             wptrs.push_back(p.wbuf.u64(gi * n));
-            qpoints.push_back(point[(size_t)(std::find(p.rots.begin(), p.rots.end(), g.rot) - p.rots.begin())]);
+            qpoints.push_back(point[pl.rot_index(g.rot)]);
         }
         for (size_t first = 0; first < ng; first += 8)      // (the batched division takes eight at a time); the witnesses are committed in one MSM
             TRY(dehalo_kate_division_batch_device(ctx, fid, qptrs.data() + first, n, (const uint64_t*)(qpoints.data() + first), wptrs.data() + first, std::min<size_t>(8, ng - first), nullptr));
@@ -1029,18 +843,18 @@ struct ProofRun {
     int open_shplonk() {
         const Fe y_ = tr->squeeze();
         const Fe v = tr->squeeze();
-        const size_t ns = p.ipa_sets.size();
+        const OpeningPlan& pl = p.plan;
+        const size_t ns = pl.point_sets.size();
         std::vector<std::vector<Fe>> pts(ns), ycoef(ns);
         std::vector<const uint64_t*> fptrs(ns), pt_ptrs(ns);
         std::vector<uint64_t*> qptrs(ns);
         std::vector<uint32_t> npts(ns);
         for (size_t si = 0; si < ns; si++) {
             std::vector<const uint64_t*> ptrs;
-            for (auto& cm : p.ipa_commitments)
-                if (cm.set == si) ptrs.push_back(cm.ptr);
+            for (uint32_t ci : pl.set_members[si]) ptrs.push_back(p.plist[pl.commitments[ci].poly]);
             ycoef[si] = powers(f, y_, ptrs.size());
             TRY(dehalo_lincomb_device(ctx, fid, ptrs.data(), (const uint64_t*)ycoef[si].data(), ptrs.size(), n, p.shp_f.u64(si * n), nullptr, nullptr));
-            for (uint32_t pi : p.ipa_sets[si]) pts[si].push_back(d.rotate_omega(x, p.ipa_point_rot[pi]));
+            for (uint32_t pi : pl.point_sets[si]) pts[si].push_back(d.rotate_omega(x, pl.point_rot[pi]));
             fptrs[si] = p.shp_f.u64(si * n); qptrs[si] = p.shp_q.u64(si * n); pt_ptrs[si] = pts[si][0].v; npts[si] = (uint32_t)pts[si].size();
         }
         for (size_t first = 0; first < ns; first += 8)      // (eight sets a launch; every Q_i comes out n coefficients long, its top |T_i| zero)
@@ -1052,13 +866,13 @@ struct ProofRun {
         const Fe u_ = tr->squeeze();
         // host: per set zdiff_i and the Lagrange basis of T_i at u, every denominator (and zdiff_0) inverted together
         std::vector<Fe> super;
-        for (int32_t r : p.ipa_point_rot) super.push_back(d.rotate_omega(x, r));
+        for (int32_t r : pl.point_rot) super.push_back(d.rotate_omega(x, r));
         Fe zt = f->one;
         for (const Fe& z : super) zt = f->mul(zt, f->sub(u_, z));
         std::vector<Fe> zdiff(ns, f->one), inv;      // inv: [zdiff_0 | per set, per point: prod_{s != t} (z_t - z_s)]
         std::vector<std::vector<Fe>> basis(ns);      // prod_{s != t} (u - z_s), then times the inverted denominator
         for (size_t si = 0; si < ns; si++) {
-            const std::vector<uint32_t>& T = p.ipa_sets[si];
+            const std::vector<uint32_t>& T = pl.point_sets[si];
             for (uint32_t pi = 0; pi < super.size(); pi++)
                 if (std::find(T.begin(), T.end(), pi) == T.end()) zdiff[si] = f->mul(zdiff[si], f->sub(u_, super[pi]));
             if (si == 0) inv.push_back(zdiff[0]);
@@ -1070,14 +884,8 @@ struct ProofRun {
                 inv.push_back(den);
             }
         }
-        {      // Montgomery's trick (u is none of the points and the points differ, but for a negligible probability: a zero here is refused, not divided by)
-            std::vector<Fe> pre(inv.size());
-            Fe acc = f->one;
-            for (size_t i = 0; i < inv.size(); i++) { pre[i] = acc; acc = f->mul(acc, inv[i]); }
-            if (acc.is_zero()) return dh_fail(ctx, DEHALO_ERR_INVALID, "shplonk: the challenge u is an opening point");
-            Fe a = f->invert(acc);
-            for (size_t i = inv.size(); i-- > 0;) { const Fe t = f->mul(a, pre[i]); a = f->mul(a, inv[i]); inv[i] = t; }
-        }
+        // (u is none of the points and the points differ, but for a negligible probability: a zero here is refused, not divided by)
+        if (!f->batch_invert(inv.data(), inv.size())) return dh_fail(ctx, DEHALO_ERR_INVALID, "shplonk: the challenge u is an opening point");
         const Fe zdiff0_inv = inv[0];
         // L's ns + 1 coefficients, already over zdiff_0, and its constant: sum_i v^i zdiff_i sum_j y^j r_ij, r_ij = sum_t basis_t eval_ij(z_t)
         std::vector<const uint64_t*> lptrs(fptrs);
@@ -1089,8 +897,8 @@ struct ProofRun {
             for (Fe& b : basis[si]) b = f->mul(b, inv[io++]);
             Fe rsum = zero;
             size_t j = 0;
-            for (auto& cm : p.ipa_commitments) {
-                if (cm.set != si) continue;
+            for (uint32_t ci : pl.set_members[si]) {
+                const OpeningPlan::Commitment& cm = pl.commitments[ci];
                 Fe r = zero;
                 for (size_t t = 0; t < basis[si].size(); t++) r = f->add(r, f->mul(basis[si][t], cm.evals[t] >= 0 ? E[cm.evals[t]] : hfold_eval));
                 rsum = f->add(rsum, f->mul(ycoef[si][j++], r));

@@ -86,6 +86,19 @@ int main(int argc, char** argv) {
     std::vector<uint64_t> sc(4 * 1000);
     if (r.scalars(sc.data(), 1000) != 0) return 1;
     for (int i = 0; i < 1000; i++) if (HostField::geq(sc.data() + 4 * i, f->p)) { printf("scalar >= p\n"); return 1; }
+    // HostField::batch_invert: every inverse from one inversion; a zero anywhere is refused and nothing is written
+    {
+        std::vector<Fe> v(1000);
+        memcpy(v.data(), sc.data(), 32 * v.size());
+        std::vector<Fe> w = v;
+        if (!f->batch_invert(w.data(), w.size())) { printf("batch_invert refused non-zero scalars\n"); return 1; }
+        for (size_t i = 0; i < v.size(); i++) if (f->mul(v[i], w[i]) != f->one || w[i] != f->invert(v[i])) { printf("batch_invert: element %zu is not the inverse\n", i); return 1; }
+        w = v;
+        w[500] = Fe{{0, 0, 0, 0}};
+        const std::vector<Fe> before = w;
+        if (f->batch_invert(w.data(), w.size()) || memcmp(w.data(), before.data(), 32 * w.size())) { printf("batch_invert: a zero was not refused, or the values were touched\n"); return 1; }
+        if (!f->batch_invert(nullptr, 0)) { printf("batch_invert refused the empty list\n"); return 1; }
+    }
     dehalo_rng pr{};
     pr.kind = DEHALO_RNG_PCG64; pr.pcg_state[0] = 123; pr.pcg_inc[0] = 457;
     if (r.init(&pr, f) != 0) return 1;
