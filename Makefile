@@ -51,6 +51,10 @@ msm_plan_check: tests/native_host/msm_plan_check.cpp $(CSRC)/msm_plan.hpp $(CSRC
 opening_plan_check: tests/native_host/opening_plan_check.cpp $(CSRC)/opening_plan.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/opening_plan_check tests/native_host/opening_plan_check.cpp
 
+# the constraint system on the host (csrc/plonk_host.hpp: no HIP headers) with phases and challenges, under the same sanitizers (tests/test_phases_host.py runs it)
+host_cs_check: tests/native_host/host_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/hostfield.hpp
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/host_cs_check tests/native_host/host_cs_check.cpp
+
 clean:
 	rm -rf $(LIB) $(OBJDIR) $(PKG)/host/example; $(MAKE) -C oracle clean
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check host_cs_check

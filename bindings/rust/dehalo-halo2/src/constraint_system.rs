@@ -3,7 +3,8 @@
 //! (C++, host/halo2_backend.hpp); the library's tests pin both against the CPU restatement's statement of the MainGate + RangeChip shape (oracle/shapes.py).
 //!
 //! `Expression::{Constant, Fixed, Advice, Instance, Negated, Sum, Product, Scaled}` map 1:1 onto `DEHALO_EXPR_*` nodes, children before parents.  `Selector` does not
-//! occur after `compress_selectors`; `Challenge` does not occur in the reference's one-phase circuits (src/lib.rs:164-318).
+//! occur after `compress_selectors`; `Challenge(c)` becomes `DEHALO_EXPR_CHALLENGE` with `a = c.index()`, and `cs.advice_column_phase()` / `cs.challenge_phase()`
+//! travel as `advice_phases` / `challenge_phases` (null for the reference's one-phase circuits, src/lib.rs:164-318: their descriptor is what it was).
 use dehalo_sys as sys;
 use halo2_proofs::plonk::{Any, Column, ConstraintSystem, Expression};
 use halo2_proofs::poly::Rotation;
@@ -25,6 +26,8 @@ pub struct Descriptor<F: ff::Field = Fr> {
     num_fixed: u32,
     num_instance: u32,
     minimum_degree: u32,
+    advice_phases: Vec<u8>,
+    challenge_phases: Vec<u8>,
 }
 
 fn column_kind(any: &Any) -> u32 {
@@ -51,6 +54,8 @@ impl<F: ff::Field> Descriptor<F> {
             num_fixed: cs.num_fixed_columns() as u32,
             num_instance: cs.num_instance_columns() as u32,
             minimum_degree: cs.minimum_degree().unwrap_or(0) as u32,
+            advice_phases: cs.advice_column_phase(),
+            challenge_phases: cs.challenge_phase(),
         };
         for gate in cs.gates() {
             for poly in gate.polynomials() {
@@ -113,7 +118,7 @@ impl<F: ff::Field> Descriptor<F> {
                 self.push(sys::DEHALO_EXPR_SCALED as u32, a, i, 0)
             }
             Expression::Selector(_) => panic!("dehalo: selectors must be compressed into fixed columns first (keygen does)"),
-            Expression::Challenge(_) => panic!("dehalo: multi-phase circuits are outside the reference's shapes"),
+            Expression::Challenge(c) => self.push(sys::DEHALO_EXPR_CHALLENGE as u32, c.index() as u32, 0, 0),
         }
     }
 
@@ -130,6 +135,10 @@ impl<F: ff::Field> Descriptor<F> {
             advice_queries: self.advice_queries.as_ptr(), num_advice_queries: self.advice_queries.len() as u32,
             fixed_queries: self.fixed_queries.as_ptr(), num_fixed_queries: self.fixed_queries.len() as u32,
             instance_queries: self.instance_queries.as_ptr(), num_instance_queries: self.instance_queries.len() as u32,
+            // (null / 0 without later phases and challenges: the library then encodes the circuit as it always did)
+            advice_phases: if self.advice_phases.iter().any(|p| *p != 0) { self.advice_phases.as_ptr() } else { core::ptr::null() },
+            challenge_phases: if self.challenge_phases.is_empty() { core::ptr::null() } else { self.challenge_phases.as_ptr() },
+            num_challenges: self.challenge_phases.len() as u32,
         }
     }
 }

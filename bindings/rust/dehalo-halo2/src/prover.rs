@@ -13,7 +13,7 @@
 use crate::constraint_system::Descriptor;
 use crate::params::DehaloParamsKZG;
 use crate::{Context, DehaloError};
-use core::ffi::c_void;
+use core::ffi::{c_int, c_void};
 use dehalo_sys as sys;
 use ff::Field;
 use halo2_proofs::plonk::ConstraintSystem;
@@ -146,6 +146,42 @@ impl<'c> DehaloProver<'c> {
         self.ctx.check(unsafe { sys::dehalo_transcript_create(sys::DEHALO_CURVE_BN254_G1, &mut t) })?;
         let rc = unsafe {
             sys::dehalo_create_proof(self.raw, advice.as_ptr() as *const u64, inst_ptrs.as_ptr(), inst_lens.as_ptr(), inst_ptrs.len() as u32, &mut r, t, 0)
+        };
+        let out = if rc == 0 {
+            let mut bytes = vec![0u8; unsafe { sys::dehalo_transcript_len(t) }];
+            let rc2 = unsafe { sys::dehalo_transcript_finalize(t, bytes.as_mut_ptr(), bytes.len()) };
+            if rc2 == 0 { Ok(bytes) } else { self.ctx.check(rc2).map(|_| vec![]) }
+        } else {
+            self.ctx.check(rc).map(|_| vec![])
+        };
+        unsafe { sys::dehalo_transcript_release(t) };
+        out
+    }
+
+    /// `create_proof` for a circuit with later-phase advice columns (`advice_column_in(SecondPhase)`, `challenge_usable_after`): upstream synthesizes the circuit once
+    /// per phase, each time with the challenges squeezed so far; here `witness(phase, challenges)` plays that part (`dehalo_create_proof_phased`).  It is called
+    /// once per phase on this thread -- for phase p > 0 after the commitments of phase p - 1 are in the transcript -- with every challenge of the circuit by index
+    /// (those not squeezed yet are zero) and returns all `num_advice x 2^k` elements, of which the columns of `phase` are read.  The returned slice must stay valid
+    /// and unchanged until the next call of `witness` or the return of this function; `witness` must not use this prover.  `Err(code)` from `witness` (code != 0)
+    /// ends the proof with `DEHALO_ERR_INVALID`; the prover is usable afterwards.  On a one-phase key this writes `create_proof`'s bytes.
+    pub fn create_proof_phased<'a, R: RngCore + Send, W: FnMut(u32, &[Fr]) -> Result<&'a [Fr], i32>>(&self, mut witness: W, instances: &[&[Fr]], rng: &mut R) -> Result<Vec<u8>, DehaloError> {
+        unsafe extern "C" fn thunk<'a, W: FnMut(u32, &[Fr]) -> Result<&'a [Fr], i32>>(user: *mut c_void, phase: u32, challenges: *const u64, count: u32, advice: *mut *const u64) -> c_int {
+            let w = &mut *(user as *mut W);
+            let ch: &[Fr] = if count == 0 { &[] } else { core::slice::from_raw_parts(challenges as *const Fr, count as usize) };
+            // (a panic must not unwind through the C frames)
+            match std::panic::catch_unwind(std::panic::AssertUnwindSafe(|| w(phase, ch))) {
+                Ok(Ok(adv)) => { *advice = adv.as_ptr() as *const u64; 0 }
+                Ok(Err(code)) => if code != 0 { code } else { 1 },
+                Err(_) => 1,
+            }
+        }
+        let inst_ptrs: Vec<*const u64> = instances.iter().map(|c| c.as_ptr() as *const u64).collect();
+        let inst_lens: Vec<usize> = instances.iter().map(|c| c.len()).collect();
+        let mut r = sys::dehalo_rng { kind: sys::DEHALO_RNG_CALLBACK, pcg_state: [0; 2], pcg_inc: [0; 2], fill: Some(fill_from::<R>), user: rng as *mut R as *mut c_void };
+        let mut t = core::ptr::null_mut();
+        self.ctx.check(unsafe { sys::dehalo_transcript_create(sys::DEHALO_CURVE_BN254_G1, &mut t) })?;
+        let rc = unsafe {
+            sys::dehalo_create_proof_phased(self.raw, Some(thunk::<W>), &mut witness as *mut W as *mut c_void, inst_ptrs.as_ptr(), inst_lens.as_ptr(), inst_ptrs.len() as u32, &mut r, t, 0)
         };
         let out = if rc == 0 {
             let mut bytes = vec![0u8; unsafe { sys::dehalo_transcript_len(t) }];

@@ -34,7 +34,7 @@ SYMBOLS = [
     "dehalo_g_to_lagrange_device", "dehalo_params_ipa_from_g", "dehalo_params_ipa_size", "dehalo_params_ipa_write", "dehalo_params_ipa_read",
     "dehalo_fixed_base_create", "dehalo_fixed_base_release", "dehalo_fixed_base_mul_device", "dehalo_fixed_base_blind_device", "dehalo_params_fixed_base",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
-    "dehalo_check_witness",
+    "dehalo_check_witness", "dehalo_check_witness_challenges", "dehalo_create_proof_phased", "dehalo_pk_phases",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -84,7 +84,8 @@ class CConstraintSystem(C.Structure):
                 ("permutation_columns", C.POINTER(CColumnQuery)), ("num_permutation_columns", C.c_uint32),
                 ("advice_queries", C.POINTER(CColumnQuery)), ("num_advice_queries", C.c_uint32),
                 ("fixed_queries", C.POINTER(CColumnQuery)), ("num_fixed_queries", C.c_uint32),
-                ("instance_queries", C.POINTER(CColumnQuery)), ("num_instance_queries", C.c_uint32)]
+                ("instance_queries", C.POINTER(CColumnQuery)), ("num_instance_queries", C.c_uint32),
+                ("advice_phases", C.c_void_p), ("challenge_phases", C.c_void_p), ("num_challenges", C.c_uint32)]
 
 
 class CCircuitInputs(C.Structure):
@@ -98,6 +99,7 @@ class CSynthesisInfo(C.Structure):
 
 RNG_FILL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_uint64)
 GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint32)      # dehalo_gather_fn
+ADVICE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_void_p))      # dehalo_advice_fn
 
 
 class CRng(C.Structure):
@@ -280,6 +282,9 @@ def load_library():
     lib.dehalo_prover_release.argtypes = [P]
     lib.dehalo_create_proof.argtypes = [P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P, u32]
     lib.dehalo_check_witness.argtypes = [P, P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u64p, u32, C.POINTER(CCheckFailure), sz, C.POINTER(CCheckReport)]
+    lib.dehalo_check_witness_challenges.argtypes = [P, P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u64p, u32, u64p, u32, C.POINTER(CCheckFailure), sz, C.POINTER(CCheckReport)]
+    lib.dehalo_create_proof_phased.argtypes = [P, ADVICE_FN, P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P, u32]
+    lib.dehalo_pk_phases.argtypes = [P, C.POINTER(C.c_uint32)]
     lib.dehalo_create_proof_circuit.argtypes = [P, C.POINTER(CCircuitInputs), C.POINTER(CSynthesisInfo), C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P]
     lib.dehalo_create_proofs_circuit.argtypes = [C.POINTER(C.c_void_p), u32, C.POINTER(CCircuitInputs), u32, C.POINTER(CRng), C.POINTER(C.c_void_p), sz, C.POINTER(sz)]
     lib.dehalo_prover_last_timings.argtypes = [P, C.POINTER(C.c_double)]

@@ -131,7 +131,8 @@ __global__ __launch_bounds__(CK_THREADS) void k_check_emit(EmitArgs A) {
 struct CheckHeader { uint64_t bounds[3]; uint32_t bad_mapping, pad; };
 
 int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
-               const uint64_t* mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap, dehalo_check_report* report, std::vector<const fe*>& colptrs) {
+               const uint64_t* mapping, uint32_t flags, const uint64_t* challenges, uint32_t num_challenges, dehalo_check_failure* failures, size_t cap,
+               dehalo_check_report* report, std::vector<const fe*>& colptrs) {
     const HostCS& cs = pk->cs;
     const HostField* f = pk->f;
     const FieldOps* ops = dh_field_ops(f->id);
@@ -209,6 +210,7 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
     in.advice = adv_v.data(); in.num_advice = A;
     in.instance = inst_v.data(); in.num_instance = I;
     in.theta = theta.v;
+    in.challenges = challenges; in.num_challenges = num_challenges;      // (the caller's values; none for a key without challenges)
 
     // ---- gates
     if (G) TRY(ops->graph_check(ctx, pk->check_gates.get(), &in, k, u, d_bitmap, words, s));
@@ -285,12 +287,17 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
 
 }   // namespace
 
-extern "C" int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens,
-                                    uint32_t num_instance_columns, const uint64_t* permutation_mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap,
-                                    dehalo_check_report* report) {
+namespace {
+int check_entry(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
+                const uint64_t* permutation_mapping, uint32_t flags, const uint64_t* challenges, uint32_t num_challenges, bool with_challenges, dehalo_check_failure* failures,
+                size_t cap, dehalo_check_report* report) {
     if (!ctx) return DEHALO_ERR_INVALID;
     return dh_guard(ctx, [&]() -> int {
         if (!pk || !report) return dh_fail(ctx, DEHALO_ERR_INVALID, "check_witness: null argument");
+        if (!with_challenges && pk->cs.has_challenge_node())
+            return dh_fail(ctx, DEHALO_ERR_INVALID, "check_witness: the key's expressions read challenges; pass their values to dehalo_check_witness_challenges");
+        if (with_challenges && (num_challenges != pk->cs.challenge_phase.size() || (num_challenges && !challenges)))
+            return dh_fail(ctx, DEHALO_ERR_INVALID, "check_witness_challenges: one value per challenge of the key (dehalo_pk_phases)");
         if (cap && !failures) return dh_fail(ctx, DEHALO_ERR_INVALID, "check_witness: null failure array with a non-zero capacity");
         if (pk->ctx->device != ctx->device) return dh_fail(ctx, DEHALO_ERR_INVALID, "check_witness: the proving key lives on another device");
         const size_t n = pk->dom.n;
@@ -300,8 +307,22 @@ extern "C" int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const 
         std::vector<const fe*> colptrs;
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
-        const int rc = check_body(ctx, pk, advice, instances, instance_lens, num_instance_columns, permutation_mapping, flags, failures, cap, report, colptrs);
+        const int rc = check_body(ctx, pk, advice, instances, instance_lens, num_instance_columns, permutation_mapping, flags, challenges, num_challenges, failures, cap, report,
+                                  colptrs);
         if (rc) (void)hipStreamSynchronize(ctx->stream.get());      // nothing of this call stays in flight over the caller's buffers
         return rc;
     });
+}
+}   // namespace
+
+extern "C" int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens,
+                                    uint32_t num_instance_columns, const uint64_t* permutation_mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap,
+                                    dehalo_check_report* report) {
+    return check_entry(ctx, pk, advice, instances, instance_lens, num_instance_columns, permutation_mapping, flags, nullptr, 0, false, failures, cap, report);
+}
+
+extern "C" int dehalo_check_witness_challenges(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens,
+                                               uint32_t num_instance_columns, const uint64_t* permutation_mapping, uint32_t flags, const uint64_t* challenges,
+                                               uint32_t num_challenges, dehalo_check_failure* failures, size_t cap, dehalo_check_report* report) {
+    return check_entry(ctx, pk, advice, instances, instance_lens, num_instance_columns, permutation_mapping, flags, challenges, num_challenges, true, failures, cap, report);
 }

@@ -23,7 +23,7 @@ int pk_common_init(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* c
     pk->f = host_field(curve_scalar_field(curve));
     if (!pk->f) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown curve");
     const std::string err = pk->cs.load(csd);
-    if (!err.empty()) return dh_fail(ctx, DEHALO_ERR_INVALID, err);
+    if (!err.empty()) return dh_fail(ctx, pk->cs.unsupported ? DEHALO_ERR_UNSUPPORTED : DEHALO_ERR_INVALID, err);
     if (k > 28 || !pk->dom.init(pk->f, pk->cs.degree(), k)) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "extended_k exceeds the field's two-adicity");
     if (pk->dom.n < (size_t)pk->cs.blinding_factors() + 3) return dh_fail(ctx, DEHALO_ERR_INVALID, "not enough rows available");      // Error::NotEnoughRowsAvailable
     return 0;
@@ -329,6 +329,15 @@ extern "C" int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream.get());
         delete pk;
+        return 0;
+    });
+}
+
+extern "C" int dehalo_pk_phases(const dehalo_pk* pk, uint32_t out[2]) {
+    return dh_guard(pk ? pk->ctx : nullptr, [&]() -> int {
+        if (!pk || !out) return DEHALO_ERR_INVALID;
+        out[0] = pk->cs.num_phases;
+        out[1] = (uint32_t)pk->cs.challenge_phase.size();
         return 0;
     });
 }

@@ -18,15 +18,31 @@ struct HostCS {
     struct Lookup { std::vector<uint32_t> inputs, tables; };
     std::vector<Lookup> lookups;
     std::vector<dehalo_column_query> perm_cols, advice_q, fixed_q, instance_q;
+    // the Challenge API [UPSTREAM plonk/circuit.rs advice_column_phase, challenge_phase]: the phase of every advice column (0 .. 2) and, per challenge, the phase
+    // after whose commitments it is squeezed.  One phase and no challenge: the circuits of before
+    std::vector<uint8_t> advice_phase, challenge_phase;
+    uint32_t num_phases = 1;
+    bool unsupported = false;      // load(): the message describes a circuit this library does not take (DEHALO_ERR_UNSUPPORTED), not a malformed one
 
     // copies and validates; "" on success, otherwise what is wrong
     std::string load(const dehalo_constraint_system* d) {
         if (!d) return "null constraint system";
+        unsupported = false;
         num_advice = d->num_advice; num_fixed = d->num_fixed; num_instance = d->num_instance; minimum_degree = d->minimum_degree;
         if ((d->num_nodes && !d->nodes) || (d->num_constants && !d->constants) || (d->num_gates && !d->gates) ||
             (d->num_lookups && (!d->lookup_lens || !d->lookup_inputs || !d->lookup_tables)) || (d->num_permutation_columns && !d->permutation_columns) ||
             (d->num_advice_queries && !d->advice_queries) || (d->num_fixed_queries && !d->fixed_queries) || (d->num_instance_queries && !d->instance_queries))
             return "constraint system: null array with a non-zero count";
+        if (d->num_challenges && !d->challenge_phases) return "constraint system: null challenge phases with a non-zero count";
+        advice_phase.assign(num_advice, 0);
+        if (d->advice_phases) advice_phase.assign(d->advice_phases, d->advice_phases + num_advice);
+        challenge_phase.assign(d->challenge_phases, d->challenge_phases + d->num_challenges);
+        num_phases = 1;
+        for (uint8_t ph : advice_phase) num_phases = std::max<uint32_t>(num_phases, (uint32_t)ph + 1);
+        if (num_phases > 3) { unsupported = true; return "advice phases: at most three phases (First, Second, Third)"; }
+        for (uint32_t ph = 0; ph < num_phases && num_advice; ph++)
+            if (std::find(advice_phase.begin(), advice_phase.end(), (uint8_t)ph) == advice_phase.end()) return "advice phases: every phase up to the last needs an advice column";
+        for (uint8_t ph : challenge_phase) if (ph >= num_phases) return "challenge phase: no advice column has that phase";
         nodes.assign(d->nodes, d->nodes + d->num_nodes);
         constants.resize(d->num_constants);
         for (uint32_t i = 0; i < d->num_constants; i++) memcpy(constants[i].v, d->constants + 4 * i, 32);
@@ -40,6 +56,7 @@ struct HostCS {
                 case DEHALO_EXPR_NEGATED: if (e.a >= i) return "expression: child must precede its parent"; break;
                 case DEHALO_EXPR_SUM: case DEHALO_EXPR_PRODUCT: if (e.a >= i || e.b >= i) return "expression: child must precede its parent"; break;
                 case DEHALO_EXPR_SCALED: if (e.a >= i || e.b >= d->num_constants) return "expression: bad scaled node"; break;
+                case DEHALO_EXPR_CHALLENGE: if (e.a >= d->num_challenges) return "expression: challenge index out of range"; break;
                 default: return "expression: unknown node kind";
             }
         }
@@ -75,7 +92,7 @@ struct HostCS {
     uint32_t expr_degree(uint32_t i) const {      // Expression::degree
         const dehalo_expr_node& e = nodes[i];
         switch (e.kind) {
-            case DEHALO_EXPR_CONSTANT: return 0;
+            case DEHALO_EXPR_CONSTANT: case DEHALO_EXPR_CHALLENGE: return 0;
             case DEHALO_EXPR_FIXED: case DEHALO_EXPR_ADVICE: case DEHALO_EXPR_INSTANCE: return 1;
             case DEHALO_EXPR_NEGATED: case DEHALO_EXPR_SCALED: return expr_degree(e.a);
             case DEHALO_EXPR_SUM: return std::max(expr_degree(e.a), expr_degree(e.b));
@@ -88,17 +105,18 @@ struct HostCS {
         if (x.kind != y.kind) return false;
         switch (x.kind) {
             case DEHALO_EXPR_CONSTANT: return constants[x.a] == constants[y.a];
+            case DEHALO_EXPR_CHALLENGE: return x.a == y.a;
             case DEHALO_EXPR_FIXED: case DEHALO_EXPR_ADVICE: case DEHALO_EXPR_INSTANCE: return x.a == y.a && x.rotation == y.rotation;
             case DEHALO_EXPR_NEGATED: return expr_equal(x.a, y.a);
             case DEHALO_EXPR_SCALED: return constants[x.b] == constants[y.b] && expr_equal(x.a, y.a);
             default: return expr_equal(x.a, y.a) && expr_equal(x.b, y.b);
         }
     }
-    bool expr_fixed_only(uint32_t i) const {      // no advice / instance query anywhere below: the expression's values belong to the proving key
+    bool expr_fixed_only(uint32_t i) const {      // no advice / instance query and no challenge anywhere below: the expression's values belong to the proving key
         const dehalo_expr_node& e = nodes[i];
         switch (e.kind) {
             case DEHALO_EXPR_CONSTANT: case DEHALO_EXPR_FIXED: return true;
-            case DEHALO_EXPR_ADVICE: case DEHALO_EXPR_INSTANCE: return false;
+            case DEHALO_EXPR_ADVICE: case DEHALO_EXPR_INSTANCE: case DEHALO_EXPR_CHALLENGE: return false;
             case DEHALO_EXPR_NEGATED: case DEHALO_EXPR_SCALED: return expr_fixed_only(e.a);
             default: return expr_fixed_only(e.a) && expr_fixed_only(e.b);
         }
@@ -112,6 +130,11 @@ struct HostCS {
             default: break;
         }
     }
+    bool has_challenge_node() const {      // some expression reads a challenge: its value exists only inside a proof
+        for (auto& e : nodes) if (e.kind == DEHALO_EXPR_CHALLENGE) return true;
+        return false;
+    }
+    bool phased() const { return num_phases > 1 || !challenge_phase.empty(); }
     // the first lookup whose table expressions equal lookup l's (l itself if none before it): their theta-compressed table columns are
     // the same column, computed and sorted once
     uint32_t table_representative(uint32_t l) const {
@@ -160,6 +183,11 @@ struct HostCS {
         u32((uint32_t)lookups.size());
         for (auto& lk : lookups) { u32((uint32_t)lk.inputs.size()); for (size_t i = 0; i < lk.inputs.size(); i++) { u32(lk.inputs[i]); u32(lk.tables[i]); } }
         for (auto* v : {&perm_cols, &advice_q, &fixed_q, &instance_q}) { u32((uint32_t)v->size()); for (auto& q : *v) { u32(q.kind); u32(q.index); u32((uint32_t)q.rotation); } }
+        if (phased()) {      // (only then: the encoding, and with it the substitute transcript_repr, of every single-phase circuit stays what it was)
+            for (uint8_t ph : advice_phase) out.push_back(ph);
+            u32((uint32_t)challenge_phase.size());
+            for (uint8_t ph : challenge_phase) out.push_back(ph);
+        }
     }
 };
 
@@ -217,6 +245,7 @@ struct GraphBuilder {
             case DEHALO_EXPR_FIXED: return add_calc(DEHALO_CALC_STORE, column(DEHALO_SRC_FIXED, e.a, e.rotation));
             case DEHALO_EXPR_ADVICE: return add_calc(DEHALO_CALC_STORE, column(DEHALO_SRC_ADVICE, e.a, e.rotation));
             case DEHALO_EXPR_INSTANCE: return add_calc(DEHALO_CALC_STORE, column(DEHALO_SRC_INSTANCE, e.a, e.rotation));
+            case DEHALO_EXPR_CHALLENGE: return GSrc{DEHALO_SRC_CHALLENGE, e.a, 0};      // ValueSource::Challenge(index): no calculation
             case DEHALO_EXPR_NEGATED: {
                 if (cs.nodes[e.a].kind == DEHALO_EXPR_CONSTANT) return add_constant(f->neg(cs.constants[cs.nodes[e.a].a]));
                 const GSrc a = add_expression(cs, e.a);

@@ -41,6 +41,11 @@ struct dehalo_prover {
     const HostField* f = nullptr;
     size_t n = 0, m = 0, u = 0;
     uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, I = 0, pieces = 0;
+    // advice phases [UPSTREAM plonk/prover.rs `for current_phase in phases`]: a phase's columns are committed together, so they sit side by side in `cols` --
+    // column c in slot adv_slot[c], phase ph's columns (phase_cols[ph], ascending) in slots [phase_first[ph], phase_first[ph] + phase_cols[ph].size()).  With one
+    // phase a column is its own slot
+    uint32_t nph = 1, NCH = 0, phase_first[3] = {};
+    std::vector<uint32_t> adv_slot, phase_cols[3];
     DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, hfold, qbuf, wbuf, jac, evals, blind_dev, omega_col;
     fe* polys = nullptr;      // coefficient forms: polys_own with a side context, cols (in place) without
     std::vector<uint32_t> table_rep;      // per lookup: the first lookup with the same table expressions (shares its compressed table)
@@ -93,6 +98,14 @@ struct dehalo_prover {
         u = n - (bf + 1);
         A = cs.num_advice; L = (uint32_t)cs.lookups.size(); S = cs.num_sets(); I = cs.num_instance;
         pieces = d.quotient_poly_degree;
+        nph = cs.num_phases; NCH = (uint32_t)cs.challenge_phase.size();
+        adv_slot.assign(A, 0);
+        for (uint32_t ph = 0, slot = 0; ph < nph; ph++) {
+            phase_cols[ph].clear();
+            phase_first[ph] = slot;
+            for (uint32_t c = 0; c < A; c++)
+                if (cs.advice_phase[c] == ph) { phase_cols[ph].push_back(c); adv_slot[c] = slot++; }
+        }
         if ((size_t)pieces * n > m) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "quotient does not fit the extended domain");
         OpeningShape sh;      // (the plan before anything is allocated: it is host work, and a circuit it refuses costs nothing)
         sh.k = k; sh.A = A; sh.num_fixed = cs.num_fixed; sh.I = I; sh.L = L; sh.S = S; sh.npc = (uint32_t)cs.perm_cols.size(); sh.bf = bf; sh.pieces = pieces;
@@ -125,7 +138,10 @@ struct dehalo_prover {
         for (uint32_t l = 0; l < L; l++) table_rep.push_back(cs.table_representative(l));
         TRY(find_table_rows());
         plist.clear();
-        for (uint32_t c = 0; c < NC; c++) plist.push_back((const uint64_t*)(polys + c * n));
+        for (uint32_t c = 0; c < NC; c++) {
+            const uint32_t at = c >= plan.o_adv && c < plan.o_adv + A ? plan.o_adv + adv_slot[c - plan.o_adv] : c;
+            plist.push_back((const uint64_t*)(polys + (size_t)at * n));
+        }
         for (uint32_t c = 0; c < cs.num_fixed; c++) plist.push_back(col_ptr(pk->fixed_polys, c, n));
         for (uint32_t c = 0; c < sh.npc; c++) plist.push_back(col_ptr(pk->perm_polys, c, n));
         for (uint32_t i = 0; i < pieces; i++) plist.push_back((const uint64_t*)h.at(i * n));
@@ -165,6 +181,7 @@ struct dehalo_prover {
         switch (e.kind) {
             case DEHALO_EXPR_CONSTANT: return cs.constants[e.a];
             case DEHALO_EXPR_FIXED: return colv[e.a][(size_t)(((int64_t)row + e.rotation) % (int64_t)n + (int64_t)n) % n];
+            case DEHALO_EXPR_ADVICE: case DEHALO_EXPR_INSTANCE: case DEHALO_EXPR_CHALLENGE: return Fe{{0, 0, 0, 0}};      // (not reached: expr_fixed_only is false for them)
             case DEHALO_EXPR_NEGATED: return f->neg(eval_fixed_expr(e.a, row, colv));
             case DEHALO_EXPR_SCALED: return f->mul(eval_fixed_expr(e.a, row, colv), cs.constants[e.b]);
             case DEHALO_EXPR_SUM: return f->add(eval_fixed_expr(e.a, row, colv), eval_fixed_expr(e.b, row, colv));
@@ -334,7 +351,7 @@ struct ProofRun {
     const uint32_t k, ek, bf, A, L, S, I, pieces, nco, rot_scale;
     const bool ipa;
     // one gate polynomial: Horner(0, [g], y) = g does not depend on y, so the custom-gate pass of evaluate_h needs the advice (and instance)
-    // cosets only -- queued on the side context right behind them, long before y exists
+    // cosets only -- queued on the side context right behind the last phase's, long before y exists (a circuit with challenges waits for them instead)
     const bool gates_early;
     const clk::time_point t_start = clk::now();
     clk::time_point t_phase = t_start;
@@ -343,6 +360,11 @@ struct ProofRun {
     bool device_rng = false;    // the large draw comes from a ChaCha20 kernel keyed with this proof's entropy
     size_t c_adv = 0, c_advb = 0, c_lk = 0, c_pr = 0;      // how many scalars each group of blinding values draws
     std::vector<Fe> bl;         // the proof's blinds by commitment (dehalo_prover: ipa_blinds)
+    std::vector<Fe> bl_slots;   // several phases: the same with the advice blinds in slot order, as the device array holds them
+    size_t adv_off[3] = {};     // where a phase's draws start: its columns' blinding rows, then one blind per column
+    std::vector<Fe> chal;       // the circuit's challenges by index; zero until squeezed
+    dehalo_advice_fn advice_fn = nullptr;      // dehalo_create_proof_phased: the witness of a phase, asked for when its turn comes
+    void* advice_user = nullptr;
     std::thread helper;         // draws (and, with a side context, uploads) the random polynomial while the earlier phases run
     std::atomic<int> helper_rc{0};
     double helper_ms[3] = {};
@@ -356,7 +378,7 @@ struct ProofRun {
     ProofRun(dehalo_prover& pv, dehalo_transcript* t, dehalo_rng* r)
         : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream.get()), ss(pv.side ? pv.side->stream.get() : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
           fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), pieces(pv.pieces), nco(pv.plan.NC - 1),
-          rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1) {}
+          rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1 && pv.NCH == 0), chal(pv.NCH, Fe{{0, 0, 0, 0}}) {}
     ~ProofRun() {      // whatever path the proof took: the witness' copy (asynchronous) has landed before its pin goes, and the helper has finished
         if (pin_advice && pin_advice->p) (void)hipStreamSynchronize(ms);
         pin_advice.reset();
@@ -368,7 +390,7 @@ struct ProofRun {
         t_phase = now;
     }
 
-    // ---- random scalars, in upstream's order: advice blinding rows (column after column), one blind per advice column, per lookup (bf + 1 rows
+    // ---- random scalars, in upstream's order: per advice phase the blinding rows of its columns (column after column), then one blind per column of it; per lookup (bf + 1 rows
     // permuted input, bf + 1 permuted table, the two columns' blinds), per grand product (bf rows + its blind), the random polynomial (n), its blind,
     // the h pieces' blinds and, under IPA, f's blind.  KZG commitments are not hiding: it draws the blinds and drops them.  No draw depends on the
     // device, so all of them are made here, in that order, and the blinds go up with the blinding rows in one copy.
@@ -377,6 +399,7 @@ struct ProofRun {
         device_rng = rng.kind == DEHALO_RNG_OS;
         c_adv = (size_t)A * rows; c_advb = A; c_lk = (size_t)L * (2 * rows + 2); c_pr = (size_t)(S + L) * (bf + 1);
         const size_t draws_before = c_adv + c_advb + c_lk + c_pr;
+        for (uint32_t ph = 0, off = 0; ph < p.nph; ph++) { adv_off[ph] = off; off += (uint32_t)(p.phase_cols[ph].size() * (rows + 1)); }
         p.blind_host.resize(4 * std::max<size_t>(1, draws_before));
         // the one large draw (n scalars, drawn AFTER every blinding value) is produced and -- with a side context -- uploaded by a helper
         // thread while the earlier phases run
@@ -388,14 +411,21 @@ struct ProofRun {
         bl.assign(p.plan.bi_count, zero);
         if (ipa) {
             const Fe* B = (const Fe*)p.blind_host.data();
-            for (uint32_t i = 0; i < A; i++) bl[p.plan.bi_adv + i] = B[c_adv + i];
+            for (uint32_t ph = 0; ph < p.nph; ph++)
+                for (size_t j = 0; j < p.phase_cols[ph].size(); j++) bl[p.plan.bi_adv + p.phase_cols[ph][j]] = B[adv_off[ph] + p.phase_cols[ph].size() * rows + j];
             for (uint32_t c = 0; c < 2 * L; c++) bl[p.plan.bi_perm + c] = B[c_adv + c_advb + (size_t)(c / 2) * (2 * rows + 2) + 2 * rows + (c & 1)];
             for (uint32_t s2 = 0; s2 < S + L; s2++) bl[p.plan.bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
             bl[p.plan.bi_rand] = late[0];
             for (uint32_t i = 0; i < pieces; i++) bl[p.plan.bi_h + i] = late[1 + i];
             bl[p.plan.bi_f] = late[1 + pieces];
             for (uint32_t i = 0; i < std::max<uint32_t>(I, 1); i++) bl[p.plan.bi_def + i] = f->from_u64(IPA_DEFAULT_BLIND);
-            TRY(dh_h2d(ctx, p.ipa_blinds.p, bl.data(), (size_t)p.plan.bi_count * 32, ctx->stream.get()));      // (waited for with the blinding rows, upload_blinds)
+            const Fe* up = bl.data();
+            if (p.nph > 1) {
+                bl_slots = bl;
+                for (uint32_t c = 0; c < A; c++) bl_slots[p.plan.bi_adv + p.adv_slot[c]] = bl[p.plan.bi_adv + c];
+                up = bl_slots.data();
+            }
+            TRY(dh_h2d(ctx, p.ipa_blinds.p, up, (size_t)p.plan.bi_count * 32, ctx->stream.get()));      // (waited for with the blinding rows, upload_blinds)
         }
         return 0;
     }
@@ -446,7 +476,8 @@ struct ProofRun {
         std::vector<uint64_t>& b = p.blind_host;
         std::vector<uint64_t> packed(4 * std::max<size_t>(1, total));
         size_t o = c_adv;
-        memcpy(packed.data(), b.data(), 32 * c_adv);
+        for (uint32_t ph = 0; ph < p.nph; ph++)      // (slot order is draw order less the blinds between the phases)
+            memcpy(packed.data() + 4 * (size_t)p.phase_first[ph] * rows, b.data() + 4 * adv_off[ph], 32 * p.phase_cols[ph].size() * rows);
         const uint64_t* lk = b.data() + 4 * (c_adv + c_advb);
         for (uint32_t l = 0; l < L; l++) {      // (input rows, table rows, two unused blinds) per lookup
             memcpy(packed.data() + 4 * o, lk + 4 * (size_t)l * (2 * rows + 2), 32 * 2 * rows);
@@ -495,6 +526,7 @@ struct ProofRun {
         EvalIn e;
         e.cols(fixed_c, adv_c, inst_c);
         e.in.form_flags = FF;
+        e.in.challenges = (const uint64_t*)chal.data(); e.in.num_challenges = (uint32_t)chal.size();
         return e;
     }
     int side_ntt(uint32_t first, uint32_t count, hipEvent_t e) {
@@ -507,30 +539,56 @@ struct ProofRun {
         return 0;
     }
 
-    // ---- advice: witness, blinding rows, commitments
-    int advice_columns(const uint64_t* advice, uint32_t flags) {
-        if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
-        const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin.get();      // (the witness generator's output is page-locked already)
-        pin_advice.reset(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
-        fe* adv = p.cols.at((size_t)p.plan.o_adv * n);
-        if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
-        else TRY(dh_h2d(ctx, adv, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
-        if (flags & DEHALO_PROOF_ADVICE_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, (uint64_t*)adv, nullptr, (uint64_t*)adv, (size_t)A * n, nullptr));
-        if (A) k_place_rows<<<(unsigned)((rows * A + 255) / 256), 256, 0, ms>>>(adv + u, n, p.blind_dev.p, (uint32_t)rows, A);
-        if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[0].get(), ms));
-        for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(p.pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(p.pk->fixed_cosets, i, m));
-        for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.plan.o_adv + i, n)), adv_c.push_back(col_ptr(p.ext, p.plan.o_adv + i, m));
-        for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(p.instance_values, i, n)), inst_c.push_back(col_ptr(p.ext, nco + i, m));
-        return p.commit(tr, adv, A, true, [this] { return after_advice_queued(); }, 0, p.blind_at(p.plan.bi_adv));
+    // ---- advice, phase by phase: witness (the caller's, given every challenge squeezed so far), blinding rows, commitments, the phase's challenges
+    int advice_of_phase(uint32_t ph, const uint64_t* given, const uint64_t** advice) {
+        *advice = given;
+        if (!advice_fn) return 0;
+        *advice = nullptr;
+        const int rc = advice_fn(advice_user, ph, (const uint64_t*)chal.data(), p.NCH, advice);
+        if (rc) return dh_fail(ctx, DEHALO_ERR_INVALID, "create_proof_phased: the advice callback returned " + std::to_string(rc) + " in phase " + std::to_string(ph));
+        return 0;
     }
-    int after_advice_queued() {
-        if (I && side) {
+    int advice_columns(const uint64_t* given, uint32_t flags) {
+        for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(p.pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(p.pk->fixed_cosets, i, m));
+        for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.plan.o_adv + p.adv_slot[i], n)), adv_c.push_back(col_ptr(p.ext, p.plan.o_adv + p.adv_slot[i], m));
+        for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(p.instance_values, i, n)), inst_c.push_back(col_ptr(p.ext, nco + i, m));
+        for (uint32_t ph = 0; ph < p.nph; ph++) {
+            const uint64_t* advice = nullptr;
+            TRY(advice_of_phase(ph, given, &advice));
+            if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
+            const std::vector<uint32_t>& pc = p.phase_cols[ph];
+            const uint32_t first = p.phase_first[ph], cnt = (uint32_t)pc.size();
+            fe* adv = p.cols.at((size_t)(p.plan.o_adv + first) * n);
+            if (p.nph == 1) {      // every column at once
+                const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin.get();      // (the witness generator's output is page-locked already)
+                pin_advice.reset(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
+                if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
+                else TRY(dh_h2d(ctx, adv, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
+            } else      // the phase's columns only, a copy per run of neighbouring columns (they are neighbouring slots); the buffer is the caller's until the next
+                        // callback: nothing is pinned, and a copy that is still in flight (device or page-locked memory) lands before this phase's commitments come back
+                for (uint32_t j = 0, run; j < cnt; j += run) {
+                    for (run = 1; j + run < cnt && pc[j + run] == pc[j] + run; run++) {}
+                    const uint64_t* src = advice + 4 * (size_t)pc[j] * n;
+                    if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv + (size_t)j * n, src, (size_t)run * n * 32, hipMemcpyDeviceToDevice, ms));
+                    else TRY(dh_h2d(ctx, adv + (size_t)j * n, src, (size_t)run * n * 32, ms));
+                }
+            if (flags & DEHALO_PROOF_ADVICE_CANONICAL) TRY(dehalo_field_op_device(ctx, fid, 4, (uint64_t*)adv, nullptr, (uint64_t*)adv, (size_t)cnt * n, nullptr));
+            if (cnt) k_place_rows<<<(unsigned)((rows * cnt + 255) / 256), 256, 0, ms>>>(adv + u, n, p.blind_dev.p + (size_t)first * rows, (uint32_t)rows, cnt);
+            if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[0].get(), ms));
+            TRY(p.commit(tr, adv, cnt, true, [this, ph] { return after_advice_queued(ph); }, 0, p.blind_at(p.plan.bi_adv + first)));
+            for (uint32_t j = 0; j < p.NCH; j++)
+                if (cs.challenge_phase[j] == ph) chal[j] = tr->squeeze();
+        }
+        return 0;
+    }
+    int after_advice_queued(uint32_t ph) {
+        if (I && side && ph == 0) {
             HIP_TRY(side, hipStreamWaitEvent(ss, p.ev_inst.get(), 0));
             TRY(dehalo_intt_scaled_device(side, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
             TRY(dehalo_coset_ntt_form_device(side, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         }
-        if (side) TRY(side_ntt(p.plan.o_adv, A, p.ev_ready[0].get()));
-        if (gates_early) {
+        if (side) TRY(side_ntt(p.plan.o_adv + p.phase_first[ph], (uint32_t)p.phase_cols[ph].size(), p.ev_ready[0].get()));
+        if (gates_early && ph + 1 == p.nph) {
             EvalIn e = coset_inputs();
             e.in.y = zero.v;
             TRY(dehalo_graph_evaluate_device(side, p.pk->custom_gates.get(), &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
@@ -555,6 +613,7 @@ struct ProofRun {
         EvalIn e;
         e.cols(fixed_v, adv_v, inst_v);
         e.in.theta = theta.v;
+        e.in.challenges = (const uint64_t*)chal.data(); e.in.num_challenges = (uint32_t)chal.size();
         TRY(dehalo_graph_evaluate_batch_device(ctx, graphs.data(), (uint32_t)graphs.size(), &e.in, k, 1, outs.data(), nullptr));
         p.tk("compress queued");
         // the blinding rows [u, n) first: the permutation writes rows [0, u) only and ends with a read-back
@@ -599,10 +658,10 @@ struct ProofRun {
         }
         TRY(dehalo_ntt_device(ctx, fid, (uint64_t*)rl, k, d.omega.v, 1, nullptr));
         if (S + L == 0) return p.commit(tr, rl, 1, true, [this] { return restore_random(); }, 0, p.blind_at(p.plan.bi_rand));
-        std::vector<Fe> chal(std::max<uint32_t>(npc, 1));
+        std::vector<Fe> pchal(std::max<uint32_t>(npc, 1));
         Fe dj = beta;
         for (uint32_t j = 0; j < npc; j++) {
-            chal[j] = dj;
+            pchal[j] = dj;
             dj = f->mul(dj, f->delta);
         }
         // every product's numerator and denominator columns in ONE launch (k_product_terms) instead of a GraphEvaluator program per column
@@ -616,7 +675,7 @@ struct ProofRun {
             ps.push_back(col_ptr(p.cols, p.plan.o_perm + 2 * l + 1, n));
         }
         std::vector<Fe> set_factors(std::max<uint32_t>(S, 1));
-        for (uint32_t s2 = 0; s2 < S; s2++) set_factors[s2] = chal[std::min<uint32_t>(s2 * cs.chunk_len(), npc ? npc - 1 : 0)];      // beta delta^(first column of the set)
+        for (uint32_t s2 = 0; s2 < S; s2++) set_factors[s2] = pchal[std::min<uint32_t>(s2 * cs.chunk_len(), npc ? npc - 1 : 0)];      // beta delta^(first column of the set)
         dehalo_product_inputs pin{};
         pin.columns = pcolv.data(); pin.sigma = psig.data(); pin.num_columns = npc; pin.chunk_len = cs.chunk_len();
         pin.omega_powers = p.omega_col.u64();
@@ -931,7 +990,8 @@ struct ProofRun {
 
     // create_proof [UPSTREAM plonk/prover.rs]; `synth_in`: of a circuit, synthesized inside (its advice replaces `advice`)
     int run(const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, uint32_t flags,
-            const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
+            const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info, dehalo_advice_fn fn = nullptr, void* user = nullptr) {
+        advice_fn = fn; advice_user = user;
         p.ticks.clear();
         p.t0 = t_start;
         p.trace = getenv("DEHALO_PROVER_TRACE") != nullptr;
@@ -974,10 +1034,15 @@ struct ProofRun {
 };
 
 int prove(dehalo_prover* p, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng,
-          dehalo_transcript* transcript, uint32_t flags, const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info) {
+          dehalo_transcript* transcript, uint32_t flags, const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info, dehalo_advice_fn fn = nullptr,
+          void* user = nullptr) {
     if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
+    if (p->nph > 1 && synth_in) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "create_proof_circuit: the key has later-phase advice columns");
+    if (p->nph > 1 && !fn)      // (its advice would have to exist before the first commitment)
+        return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the key has later-phase advice columns, whose witness depends on the proof's challenges: use dehalo_create_proof_phased");
     std::lock_guard<std::mutex> lk(p->mu);
-    const int rc = ProofRun(*p, transcript, rng).run(advice, instances, instance_lens, num_instance_columns, flags, synth_in, synth_info);
+    if (p->nph > 1 && p->shard_world > 1) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "create_proof_phased: a sharded prover proves single-phase circuits only");
+    const int rc = ProofRun(*p, transcript, rng).run(advice, instances, instance_lens, num_instance_columns, flags, synth_in, synth_info, fn, user);
     if (rc) {      // leave nothing of this proof in flight on either context
         (void)hipStreamSynchronize(p->ctx->stream.get());
         if (p->side) (void)hipStreamSynchronize(p->side->stream.get());
@@ -1020,9 +1085,19 @@ extern "C" int dehalo_create_proof(dehalo_prover* p, const uint64_t* advice, con
     });
 }
 
+extern "C" int dehalo_create_proof_phased(dehalo_prover* p, dehalo_advice_fn fn, void* user, const uint64_t* const* instances, const size_t* instance_lens,
+                                          uint32_t num_instance_columns, dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !transcript) return DEHALO_ERR_INVALID;
+        if (!fn) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof_phased: null advice callback");
+        return prove(p, nullptr, instances, instance_lens, num_instance_columns, rng, transcript, flags, nullptr, nullptr, fn, user);
+    });
+}
+
 extern "C" int dehalo_prover_set_shard(dehalo_prover* p, uint32_t rank, uint32_t world, dehalo_gather_fn gather, void* user) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || world == 0 || rank >= world || (world > 1 && !gather)) return DEHALO_ERR_INVALID;
+        if (world > 1 && p->nph > 1) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "prover_set_shard: the key has later-phase advice columns");
         p->shard_rank = rank; p->shard_world = world; p->shard_gather = world > 1 ? gather : nullptr; p->shard_user = user;
         return 0;
     });
@@ -1097,6 +1172,8 @@ extern "C" int dehalo_create_proofs(dehalo_prover* const* provers, uint32_t num_
                                     uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens) {
     return dh_guard(nullptr, [&]() -> int {
         if (!provers || !num_provers || (count && (!advice || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
+        for (uint32_t i = 0; i < num_provers; i++)
+            if (provers[i] && provers[i]->nph > 1) return dh_fail(provers[i]->ctx, DEHALO_ERR_UNSUPPORTED, "create_proofs: the key has later-phase advice columns");
         return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
             return dehalo_create_proof(p, advice[i], nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr, flags);
         });
@@ -1108,6 +1185,8 @@ extern "C" int dehalo_create_proofs_circuit(dehalo_prover* const* provers, uint3
                                             uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens) {
     return dh_guard(nullptr, [&]() -> int {
         if (!provers || !num_provers || (count && (!inputs || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
+        for (uint32_t i = 0; i < num_provers; i++)
+            if (provers[i] && provers[i]->nph > 1) return dh_fail(provers[i]->ctx, DEHALO_ERR_UNSUPPORTED, "create_proofs_circuit: the key has later-phase advice columns");
         return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
             return dehalo_create_proof_circuit(p, &inputs[i], nullptr, nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr);
         });

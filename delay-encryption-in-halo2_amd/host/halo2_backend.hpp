@@ -8,6 +8,8 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <exception>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -215,6 +217,9 @@ class ConstraintSystem {
     Expr sum(Expr a, Expr b) { return node(DEHALO_EXPR_SUM, a, b, 0); }
     Expr product(Expr a, Expr b) { return node(DEHALO_EXPR_PRODUCT, a, b, 0); }
     Expr scaled(Expr a, const Fe& c) { return node(DEHALO_EXPR_SCALED, a, add_constant(c), 0); }
+    // the Challenge API: advice_column_in(phase) for column `col` (columns not named stay in the first phase); challenge_usable_after(phase).expr()
+    void set_advice_phase(uint32_t col, uint8_t phase) { if (aph_.size() < d_.num_advice) aph_.resize(d_.num_advice, 0); aph_.at(col) = phase; }
+    Expr challenge_usable_after(uint8_t phase) { cph_.push_back(phase); return node(DEHALO_EXPR_CHALLENGE, (uint32_t)cph_.size() - 1, 0, 0); }
     void enable_equality(dehalo_column_kind kind, uint32_t col) {
         std::vector<dehalo_column_query>& q = kind == DEHALO_COLUMN_ADVICE ? aq_ : kind == DEHALO_COLUMN_FIXED ? fq_ : iq_;
         query(q, kind, col, 0);
@@ -236,6 +241,8 @@ class ConstraintSystem {
         d_.advice_queries = aq_.data(); d_.num_advice_queries = (uint32_t)aq_.size();
         d_.fixed_queries = fq_.data(); d_.num_fixed_queries = (uint32_t)fq_.size();
         d_.instance_queries = iq_.data(); d_.num_instance_queries = (uint32_t)iq_.size();
+        d_.advice_phases = aph_.empty() ? nullptr : aph_.data();
+        d_.challenge_phases = cph_.empty() ? nullptr : cph_.data(); d_.num_challenges = (uint32_t)cph_.size();
         return &d_;
     }
 
@@ -255,6 +262,7 @@ class ConstraintSystem {
     std::vector<Fe> consts_;
     std::vector<uint32_t> gates_, lens_, lin_, ltab_;
     std::vector<dehalo_column_query> perm_, aq_, fq_, iq_;
+    std::vector<uint8_t> aph_, cph_;
 };
 
 // ParamsKZG<Bn256>
@@ -399,6 +407,31 @@ class Prover {
         std::vector<size_t> il;
         for (auto& col : instances) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
         be_.check(dehalo_create_proof(p_, advice[0].data(), ip.data(), il.data(), (uint32_t)ip.size(), rng, transcript.raw(), 0));
+    }
+    // The same for a circuit with later-phase advice (dehalo_create_proof_phased): witness(phase, challenges) is called once per phase on this thread -- for
+    // phase p > 0 after the commitments of phase p - 1 are in the transcript, with every challenge squeezed so far (the others zero) -- and returns all
+    // num_advice x 2^k elements, of which the columns of `phase` are read.  The returned vector must stay alive and unchanged until the next call of `witness`
+    // or the return of this function; `witness` may call nothing on this prover.  An exception thrown by `witness` ends the proof and is rethrown here.
+    using PhaseWitness = std::function<const std::vector<Fe>&(uint32_t phase, const std::vector<Fe>& challenges)>;
+    void create_proof_phased(const PhaseWitness& witness, const std::vector<std::vector<Fe>>& instances, dehalo_rng* rng, Blake2bWrite& transcript) const {
+        struct Call { const PhaseWitness* fn; std::exception_ptr error; } call{&witness, nullptr};
+        auto thunk = [](void* user, uint32_t phase, const uint64_t* challenges, uint32_t count, const uint64_t** advice) -> int {
+            Call* c = static_cast<Call*>(user);
+            try {
+                std::vector<Fe> ch(count);
+                for (uint32_t j = 0; j < count; j++) for (int w = 0; w < 4; w++) ch[j][w] = challenges[4 * j + w];
+                const std::vector<Fe>& adv = (*c->fn)(phase, ch);
+                if (adv.empty()) return 2;
+                *advice = adv[0].data();
+                return 0;
+            } catch (...) { c->error = std::current_exception(); return 1; }      // (an exception must not unwind through the C frames)
+        };
+        std::vector<const uint64_t*> ip;
+        std::vector<size_t> il;
+        for (auto& col : instances) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
+        const int rc = dehalo_create_proof_phased(p_, thunk, &call, ip.data(), il.data(), (uint32_t)ip.size(), rng, transcript.raw(), 0);
+        if (call.error) std::rethrow_exception(call.error);
+        be_.check(rc);
     }
 
   private:

@@ -14,7 +14,7 @@ from . import plonk
 from ._lib import (CCheckFailure, CCheckReport, CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, FixedBase, RNG_FILL_FN, load_library)
 from .fields import CurveSpec, FieldSpec
 
-EXPR_KIND = {"const": 0, plonk.FIXED: 1, plonk.ADVICE: 2, plonk.INSTANCE: 3, "neg": 4, "sum": 5, "product": 6, "scaled": 7}
+EXPR_KIND = {"const": 0, plonk.FIXED: 1, plonk.ADVICE: 2, plonk.INSTANCE: 3, "neg": 4, "sum": 5, "product": 6, "scaled": 7, "challenge": 8}
 COLUMN_KIND = {plonk.ADVICE: 0, plonk.FIXED: 1, plonk.INSTANCE: 2}
 RNG_OS, RNG_PCG64, RNG_CALLBACK = 0, 1, 2
 KEYGEN_FIXED_CANONICAL = 1
@@ -53,6 +53,8 @@ class ConstraintSystemDescriptor:
                 node = (EXPR_KIND[k], a, emit(e[2]), 0)
             elif k == "scaled":
                 node = (7, emit(e[1]), const(e[2]), 0)
+            elif k == "challenge":
+                node = (8, e[1], 0, 0)
             else:
                 raise ValueError("unknown expression node %r" % (k,))
             nodes.append(node)
@@ -84,6 +86,11 @@ class ConstraintSystemDescriptor:
         d.advice_queries, d.num_advice_queries = self._aq, len(cs.advice_queries)
         d.fixed_queries, d.num_fixed_queries = self._fq, len(cs.fixed_queries)
         d.instance_queries, d.num_instance_queries = self._iq, len(cs.instance_queries)
+        # the Challenge API: NULL / 0 for a circuit without later phases and challenges -- the descriptor of before
+        self._aph = np.asarray(cs.phases(), dtype=np.uint8) if any(cs.phases()) else None
+        self._cph = np.asarray(cs.challenge_phases, dtype=np.uint8) if cs.challenge_phases else None
+        d.advice_phases = self._aph.ctypes.data if self._aph is not None else None
+        d.challenge_phases, d.num_challenges = self._cph.ctypes.data if self._cph is not None else None, len(cs.challenge_phases)
         self.struct = d
 
     def ref(self):
@@ -281,10 +288,12 @@ class ProvingKey:
     def transcript_repr(self, value: int):
         _check(self.ctx, load_library().dehalo_pk_set_transcript_repr(self.handle, self.curve.scalar.encode(value).ctypes.data))
 
-    def check_witness(self, advice, instances: Sequence[Sequence[int]] = ((),), assembly=None, canonical: bool = False, cap: int = 64, ctx: Optional[Context] = None) -> CheckReport:
+    def check_witness(self, advice, instances: Sequence[Sequence[int]] = ((),), assembly=None, canonical: bool = False, cap: int = 64, ctx: Optional[Context] = None,
+                      challenges: Optional[Sequence[int]] = None) -> CheckReport:
         """dehalo_check_witness -- MockProver::verify on the device: which gate polynomials, lookup inputs and copy constraints the witness breaks, and where.
         advice / instances / canonical as Prover.create_proof takes them; assembly: the plonk.Assembly (or its mapping array) keygen was given, None = the copy
-        constraints are not checked; cap: how many failures are stored (the totals are exact regardless)."""
+        constraints are not checked; cap: how many failures are stored (the totals are exact regardless); challenges: one canonical int per challenge of the
+        constraint system (dehalo_check_witness_challenges) -- required, DehaloError(-1) otherwise, when an expression of the circuit reads a challenge."""
         lib = load_library()
         ctx = ctx if ctx is not None else self.ctx
         f = self.curve.scalar
@@ -305,9 +314,20 @@ class ProvingKey:
             mapping = np.ascontiguousarray(getattr(assembly, "mapping", assembly), dtype=np.uint64).reshape(-1)
         fails = (CCheckFailure * cap)() if cap else None
         rep = CCheckReport()
-        _check(ctx, lib.dehalo_check_witness(ctx.handle, self.handle, adv_ptr, ptrs, lens, len(cols), mapping.ctypes.data if mapping is not None else None, flags, fails, cap,
-                                             C.byref(rep)))
+        if challenges is None:
+            _check(ctx, lib.dehalo_check_witness(ctx.handle, self.handle, adv_ptr, ptrs, lens, len(cols), mapping.ctypes.data if mapping is not None else None, flags, fails, cap,
+                                                 C.byref(rep)))
+        else:
+            ch = f.encode_many([c % f.p for c in challenges]) if len(challenges) else np.zeros((1, 4), dtype=np.uint64)
+            _check(ctx, lib.dehalo_check_witness_challenges(ctx.handle, self.handle, adv_ptr, ptrs, lens, len(cols), mapping.ctypes.data if mapping is not None else None, flags,
+                                                            ch.ctypes.data, len(challenges), fails, cap, C.byref(rep)))
         return CheckReport(rep, [(int(fails[i].kind), int(fails[i].index), int(fails[i].row)) for i in range(int(rep.written))])
+
+    def phases(self) -> tuple:
+        """dehalo_pk_phases: (advice phases in use, challenges)."""
+        out = (C.c_uint32 * 2)()
+        _check(self.ctx, load_library().dehalo_pk_phases(self.handle, out))
+        return int(out[0]), int(out[1])
 
     def info(self) -> dict:
         out = (C.c_uint32 * 8)()
@@ -467,6 +487,56 @@ class Prover:
         rc = lib.dehalo_create_proof(self.handle, adv_ptr, ptrs, lens, len(cols), C.byref(r) if r is not None else None, tr.handle, flags)
         if rc != 0:
             msg = lib.dehalo_last_error(self.ctx.handle).decode()
+            if rc == -1 and ("instance" in msg or "infinity" in msg):
+                raise ValueError(msg)
+            raise DehaloError(rc, msg)
+        rng_writeback(rng, r)
+        return tr
+
+    def create_proof_phased(self, witness_fn, instances: Sequence[Sequence[int]] = ((),), rng=None, transcript: Optional[Blake2bWrite] = None, canonical: bool = False) -> Blake2bWrite:
+        """dehalo_create_proof_phased: witness_fn(phase, challenges) -> advice is called once per advice phase, in order, with the circuit's challenges as
+        canonical ints (those not yet squeezed are 0); it returns the advice as create_proof takes it -- every call a host array or every call a device tensor -- of
+        which the columns of `phase` are read.  An exception in witness_fn ends the proof (DehaloError(-1), the exception chained); the prover stays usable."""
+        from ._lib import ADVICE_FN
+        lib = load_library()
+        tr = transcript if transcript is not None else Blake2bWrite(self.pk.curve)
+        f = self.pk.curve.scalar
+        # whether the advice lives on the device is one of the call's flags, which exist before the first callback: phase 0's witness depends on no
+        # challenge, so it is asked for here and handed over when the library's turn comes
+        first = witness_fn(0, [0] * self.pk.phases()[1])
+        state = {"keep": None, "device": hasattr(first, "data_ptr"), "error": None}
+
+        def thunk(_user, phase, chal, count, out):
+            try:
+                values = [f.decode(np.ctypeslib.as_array(chal, shape=(count, 4))[j]) for j in range(count)] if count else []
+                advice = first if phase == 0 else witness_fn(int(phase), values)
+                if hasattr(advice, "data_ptr") != state["device"]:
+                    raise TypeError("witness_fn must return host arrays in every phase or device tensors in every phase")
+                if state["device"]:
+                    if hasattr(advice, "is_cuda") and advice.is_cuda:
+                        import torch
+                        torch.cuda.current_stream().synchronize()      # the library reads the tensor on its own stream
+                    state["keep"], ptr = advice, advice.data_ptr()
+                else:
+                    state["keep"] = np.ascontiguousarray(advice, dtype=np.uint64)      # (alive until the next callback or the return)
+                    ptr = state["keep"].ctypes.data
+                out[0] = ptr
+                return 0
+            except Exception as e:      # noqa: BLE001  (an exception must not unwind through the C frames)
+                state["error"] = e
+                return 1
+
+        flags = (PROOF_ADVICE_CANONICAL if canonical else 0) | (PROOF_ADVICE_ON_DEVICE if state["device"] else 0)
+        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for v in instances]
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
+        lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
+        r = rng_struct(rng)
+        cb = ADVICE_FN(thunk)
+        rc = lib.dehalo_create_proof_phased(self.handle, cb, None, ptrs, lens, len(cols), C.byref(r) if r is not None else None, tr.handle, flags)
+        if rc != 0:
+            msg = lib.dehalo_last_error(self.ctx.handle).decode()
+            if state["error"] is not None:
+                raise DehaloError(rc, msg) from state["error"]
             if rc == -1 and ("instance" in msg or "infinity" in msg):
                 raise ValueError(msg)
             raise DehaloError(rc, msg)

@@ -22,6 +22,7 @@ from . import evaluation as ev
 
 # Expression nodes (nested tuples): ("const", c) ("fixed", i, rot) ("advice", i, rot) ("instance", i, rot)
 #                                   ("neg", e) ("sum", a, b) ("product", a, b) ("scaled", e, c)
+#                                   ("challenge", j): Expression::Challenge, a transcript challenge of the proof (degree 0)
 Expr = tuple
 ADVICE, FIXED, INSTANCE = "advice", "fixed", "instance"
 
@@ -29,7 +30,7 @@ ADVICE, FIXED, INSTANCE = "advice", "fixed", "instance"
 def degree(e: Expr) -> int:
     """Expression::degree."""
     k = e[0]
-    if k == "const":
+    if k == "const" or k == "challenge":
         return 0
     if k in (ADVICE, FIXED, INSTANCE):
         return 1
@@ -66,6 +67,10 @@ class ConstraintSystem:
     fixed_queries: List[Tuple[int, int]] = dc_field(default_factory=list)
     instance_queries: List[Tuple[int, int]] = dc_field(default_factory=list)
     minimum_degree: int = 0
+    # the Challenge API (cs.advice_column_phase, cs.challenge_phase): the phase 0 / 1 / 2 of every advice column (empty: all 0) and, per challenge,
+    # the phase after whose commitments it is squeezed.  Not part of description(): a verifier reads them beside it
+    advice_phases: List[int] = dc_field(default_factory=list)
+    challenge_phases: List[int] = dc_field(default_factory=list)
 
     # ---- building (ConstraintSystem::{query_*_index, enable_equality, create_gate, lookup}) ----
     def _query(self, kind: str, index: int, rot: int) -> Expr:
@@ -93,6 +98,26 @@ class ConstraintSystem:
 
     def lookup(self, pairs: Sequence[Tuple[Expr, Expr]]):
         self.lookups.append(([p[0] for p in pairs], [p[1] for p in pairs]))
+
+    def advice_column_in(self, phase: int) -> int:
+        """ConstraintSystem::advice_column_in: a new advice column of `phase`; returns its index."""
+        if not 0 <= phase <= 2:
+            raise ValueError("advice phase %r: First, Second and Third (0, 1, 2) exist" % (phase,))
+        self.advice_phases = self.phases() + [phase]
+        self.num_advice += 1
+        return self.num_advice - 1
+
+    def challenge_usable_after(self, phase: int) -> Expr:
+        """ConstraintSystem::challenge_usable_after(phase).expr(): a challenge squeezed after the advice commitments of `phase`."""
+        self.challenge_phases.append(phase)
+        return ("challenge", len(self.challenge_phases) - 1)
+
+    def phases(self) -> List[int]:
+        """The phase of every advice column."""
+        return list(self.advice_phases) + [0] * (self.num_advice - len(self.advice_phases))
+
+    def num_phases(self) -> int:
+        return max(self.phases() + [0]) + 1
 
     def description(self) -> tuple:
         """The constraint system as plain data (what a verifier needs besides the key's commitments); its text is hashed into
@@ -142,6 +167,8 @@ def add_expression(g: ev.GraphEvaluator, e: Expr, p: int) -> ev.Source:
         return g.add_constant(e[1] % p)
     if k in _KIND:
         return g.add_calculation(ev.STORE, g.column(_KIND[k], e[1], e[2]))
+    if k == "challenge":                                      # ValueSource::Challenge(index): no calculation
+        return (ev.CHALLENGE, e[1], 0)
     if k == "neg":
         if e[1][0] == "const":
             return g.add_constant(-e[1][1] % p)

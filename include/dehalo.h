@@ -511,10 +511,16 @@ int dehalo_params_commit_device(dehalo_ctx* ctx, const dehalo_params* params, co
 /* The circuit as data: the fields of halo2_proofs::plonk::ConstraintSystem that keygen and the prover read
  * [UPSTREAM halo2_proofs/src/plonk/circuit.rs].  Expressions are a flat array of nodes, children before parents:
  *   CONSTANT  a = index into `constants`;     FIXED / ADVICE / INSTANCE  a = column index, rotation;
- *   NEGATED   a = child;  SUM / PRODUCT  a, b = children;  SCALED  a = child, b = index into `constants`.                          */
+ *   NEGATED   a = child;  SUM / PRODUCT  a, b = children;  SCALED  a = child, b = index into `constants`;
+ *   CHALLENGE a = challenge index (Expression::Challenge: degree 0, its value squeezed from the transcript during the proof).
+ * The Challenge API [cs.advice_column_phase, cs.challenge_phase; advice_column_in(SecondPhase), challenge_usable_after(FirstPhase)]:
+ *   advice_phases     num_advice entries, the phase 0 / 1 / 2 of every advice column; NULL = all 0.  The phases in use are 0 ..= the largest, each with at least
+ *                     one column (DEHALO_ERR_INVALID otherwise); more than three phases: DEHALO_ERR_UNSUPPORTED
+ *   challenge_phases  num_challenges entries: challenge j is squeezed after the advice commitments of phase challenge_phases[j] (a phase in use)
+ * A circuit with one phase and no challenge is described, encoded (the substitute transcript_repr) and proved exactly as before these fields existed.       */
 typedef enum {
     DEHALO_EXPR_CONSTANT = 0, DEHALO_EXPR_FIXED = 1, DEHALO_EXPR_ADVICE = 2, DEHALO_EXPR_INSTANCE = 3, DEHALO_EXPR_NEGATED = 4, DEHALO_EXPR_SUM = 5,
-    DEHALO_EXPR_PRODUCT = 6, DEHALO_EXPR_SCALED = 7
+    DEHALO_EXPR_PRODUCT = 6, DEHALO_EXPR_SCALED = 7, DEHALO_EXPR_CHALLENGE = 8
 } dehalo_expr_kind;
 typedef struct { uint32_t kind, a, b; int32_t rotation; } dehalo_expr_node;
 typedef enum { DEHALO_COLUMN_ADVICE = 0, DEHALO_COLUMN_FIXED = 1, DEHALO_COLUMN_INSTANCE = 2 } dehalo_column_kind;
@@ -530,6 +536,8 @@ typedef struct {
     const dehalo_column_query* advice_queries; uint32_t num_advice_queries;                /* first-use order: the order of the evaluations in the proof */
     const dehalo_column_query* fixed_queries; uint32_t num_fixed_queries;
     const dehalo_column_query* instance_queries; uint32_t num_instance_queries;
+    const uint8_t* advice_phases;                                   /* num_advice entries; NULL = every column in phase 0 */
+    const uint8_t* challenge_phases; uint32_t num_challenges;       /* the phase after which each challenge is squeezed */
 } dehalo_constraint_system;
 
 /* keygen_vk + keygen_pk [UPSTREAM halo2_proofs/src/plonk/keygen.rs; benches/delay_enc.rs:86,103] on the device: commit_lagrange,
@@ -555,6 +563,8 @@ int dehalo_pk_set_transcript_repr(dehalo_pk* pk, const uint64_t repr[4]);
 int dehalo_pk_get_transcript_repr(const dehalo_pk* pk, uint64_t repr[4]);
 /* out[0..7] = k, extended_k, blinding_factors, degree, permutation sets, commitments before the evaluations, evaluations, opening points */
 int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]);
+/* out[0] = advice phases in use (1 .. 3), out[1] = challenges of the key's constraint system */
+int dehalo_pk_phases(const dehalo_pk* pk, uint32_t out[2]);
 int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk);
 
 /* Random scalars of one proof (see csrc/hostrng.hpp).  DEHALO_RNG_OS is what a NULL pointer selects. */
@@ -626,6 +636,24 @@ size_t dehalo_prover_proof_size(const dehalo_prover* prover);
 enum { DEHALO_PROOF_ADVICE_ON_DEVICE = 1, DEHALO_PROOF_ADVICE_CANONICAL = 2 /* plain integers < p: converted on the device */ };
 int dehalo_create_proof(dehalo_prover* prover, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                         dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
+/* create_proof of a circuit with later-phase advice [UPSTREAM plonk/prover.rs: `for current_phase in phases`]: the witness of phase p may depend on the challenges
+ * squeezed after the commitments of the phases before it, so the caller supplies it through a callback, one call per phase.  After the instances are absorbed,
+ * for each phase in order: fn(user, phase, challenges, num_challenges, &advice); the blinding rows of that phase's columns (column order), one blind per column;
+ * commit_lagrange of each, written to the transcript in column order; one squeeze per challenge of that phase, in challenge-index order.  theta follows the
+ * last phase.  So the advice commitments stand phase-major in the proof and the generator's draws are phase-major; with one phase both are dehalo_create_proof's.
+ *   fn          called on the proving thread, once per phase; for phase p > 0 after the commitments of phase p - 1 are in the transcript.  It may call nothing
+ *               on this prover (the prover's lock is held) or on the prover's contexts' streams
+ *   challenges  num_challenges x 4 u64 Montgomery (the key's challenges, by index); those not squeezed yet are zero.  Valid during the callback only
+ *   *advice     set by fn: a buffer of dehalo_create_proof's layout (num_advice x 2^k x 4 u64) under this call's `flags` (host, or device memory with
+ *               DEHALO_PROOF_ADVICE_ON_DEVICE; DEHALO_PROOF_ADVICE_CANONICAL).  Only the columns of `phase` are read from it.  It must stay valid and unchanged until
+ *               the next callback or the return of this call
+ * A non-zero return of fn ends the proof with DEHALO_ERR_INVALID (the code is in dehalo_last_error's text); the prover is usable for the next proof.
+ * On a key with one phase fn is called once and the proof is dehalo_create_proof's, byte for byte.
+ * dehalo_create_proof on a key with more than one phase returns DEHALO_ERR_INVALID (its advice would have to exist before the first commitment).  On such a
+ * key dehalo_create_proofs, dehalo_create_proof_circuit, dehalo_create_proofs_circuit and dehalo_prover_set_shard (world > 1) return DEHALO_ERR_UNSUPPORTED. */
+typedef int (*dehalo_advice_fn)(void* user, uint32_t phase, const uint64_t* challenges, uint32_t num_challenges, const uint64_t** advice);
+int dehalo_create_proof_phased(dehalo_prover* prover, dehalo_advice_fn fn, void* user, const uint64_t* const* instances, const size_t* instance_lens,
+                               uint32_t num_instance_columns, dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
 /* ---- MockProver::verify over a proving key [UPSTREAM halo2_proofs/src/dev.rs MockProver::verify] (csrc/check.hip) ----------------------------------
  * dehalo_create_proof proves whatever advice it is handed; this call says WHERE a witness breaks the circuit of `pk`, on the device, before anything is proved.
  *   advice, instances, instance_lens, num_instance_columns, flags   exactly dehalo_create_proof's (DEHALO_PROOF_ADVICE_ON_DEVICE and DEHALO_PROOF_ADVICE_CANONICAL
@@ -656,6 +684,12 @@ typedef struct {
 } dehalo_check_report;
 int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                          const uint64_t* permutation_mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap, dehalo_check_report* report);
+/* The same checks for a key whose expressions read challenges, under the caller's values for them: challenges = num_challenges x 4 u64 Montgomery, num_challenges =
+ * the key's (dehalo_pk_phases; anything else is DEHALO_ERR_INVALID).  All advice columns, of every phase, are taken from `advice`.  dehalo_check_witness itself
+ * returns DEHALO_ERR_INVALID on a key one of whose expressions holds a challenge; on a key without one the two calls are the same. */
+int dehalo_check_witness_challenges(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens,
+                                    uint32_t num_instance_columns, const uint64_t* permutation_mapping, uint32_t flags, const uint64_t* challenges, uint32_t num_challenges,
+                                    dehalo_check_failure* failures, size_t cap, dehalo_check_report* report);
 
 /* ONE proof on several GPUs ("single-proof mode -- round-robin columns of the current phase across GPUs"): every one of `world` processes runs
  * the same dehalo_create_proof on its own GPU with the same inputs and the same seeded random stream (DEHALO_RNG_PCG64, or a callback that hands every process the

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-phase timings of the device create_proof (steady state).   python tools/profile_proof.py [k] [range_lookups] [reps]"""
+"""Per-phase timings of the device create_proof (steady state).   python tools/profile_proof.py [k] [range_lookups] [reps]
+Cost of an advice phase (dehalo_create_proof_phased on the three-phase circuit RLC3 of tests/phased_oracle.py):   python tools/profile_proof.py rlc3 [k] [reps]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,6 +11,55 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 pkg = entry.load_package(); po, co = entry.load_oracle()
 import plonk_oracle as PO, pairing as pr
 from dehalo2_amd import circuits, prover, keygen, transcript
+
+
+
+def profile_phases(k, reps):
+    """RLC3 through the native prover, every phase's witness resident on the device beforehand (same seed, so the same challenges: the callback only returns a
+    pointer).  The callback of phase p runs right behind the commitments and squeezes of phase p - 1, so the gaps between callbacks are the phases' own times."""
+    import phased_oracle as PH
+    from dehalo2_amd import native
+    curve = pkg.fields.BN254
+    p = curve.scalar.p
+    cs = PH.build_cs(pkg)
+    usable = (1 << k) - (cs.blinding_factors() + 1)
+    with pkg.Context(0) as ctx, pkg.Context(0) as side:
+        params = native.ParamsKZG.setup(ctx, curve, k, 0x1234567890abcdef)
+        pk = native.ProvingKey.keygen(ctx, params, cs, PH.fixed_columns(k), PH.assembly(pkg, cs, k), ())
+        for label, P in (("one context", native.Prover(params, pk)), ("with a side context", native.Prover(params, pk, ctx, side))):
+            fn, resident, stamps = PH.witness(p, k, usable), {}, []
+
+            def first(phase, challenges):
+                resident[phase] = ctx.upload(np.ascontiguousarray(fn(phase, challenges)))
+                return resident[phase]
+
+            def cached(phase, challenges):
+                stamps.append(time.perf_counter())
+                return resident[phase]
+
+            want = P.create_proof_phased(first, [], prover.SeededRng(7), canonical=True).finalize()
+            rows = []
+            for _ in range(reps + 2):
+                del stamps[:]
+                t0 = time.perf_counter()
+                got = P.create_proof_phased(cached, [], prover.SeededRng(7), canonical=True).finalize()
+                t1 = time.perf_counter()
+                assert got == want
+                tm = P.last_timings()
+                # (the wrapper asks for phase 0 before the call starts: stamps[0]; the library's calls for phases 1 and 2 follow)
+                start = t1 - tm["total"] / 1e3
+                rows.append((1e3 * (stamps[1] - start), 1e3 * (stamps[2] - stamps[1]), tm["advice"] - 1e3 * (stamps[2] - start), tm["advice"], tm["total"]))
+            rows = sorted(rows[2:], key=lambda r: r[-1])
+            best, med = rows[0], rows[len(rows) // 2]
+            print("RLC3 k = %d, %s: phase 0 (2 columns, with the draws and the blinds' upload) %.3f ms, phase 1 (2 columns) %.3f ms, phase 2 (1 column) %.3f ms; advice %.3f of "
+                  "%.3f ms in all (best of %d; median proof %.3f ms)" % ((k, label) + best + (reps, med[-1])))
+            P.release()
+        pk.release(); params.release()
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "rlc3":
+    profile_phases(int(sys.argv[2]) if len(sys.argv) > 2 else 17, int(sys.argv[3]) if len(sys.argv) > 3 else 9)
+    sys.exit(0)
 
 k = int(sys.argv[1]) if len(sys.argv) > 1 else 17
 rl = bool(int(sys.argv[2])) if len(sys.argv) > 2 else True
