@@ -13,7 +13,18 @@
 // LDS slots assigned by a liveness pass on the host (spilling to HBM beyond the LDS budget), and
 // columns are read with the rotation folded into the index:  (row + rot * rot_scale) mod rows.
 //
-// Values in a slot: x * 2^261, < 2p, limbs normalized.
+// Values in a slot: x * 2^261, <= 2p, limbs normalized.  2p itself has exactly one source: evh_neg(0) = 4p - 0, which the one conditional
+// subtraction of 2p takes to 2p (evh_neg of any other value, p included, is < 2p).  Every consumer takes it (p < 2^255; tools/fp29_model.py
+// evh_bounds() runs them all on {0, p, 2p} bit-accurately):
+//   f29_mul, f29_sqr     normalized limbs in, result < a b / 2^261 + p <= 4 p^2 / 2^261 + p < 2p
+//   f29_mul2             result < (a b + c d) / 2^261 + p <= 8 p^2 / 2^261 + p < 2p
+//   evh_add              a + b <= 4p, one conditional subtraction of 2p: <= 2p, and = 2p only for 2p + 2p
+//   evh_sub              KM = 4p dominates the normalized limbs of any subtrahend < 3p; a - b + 4p lies in [2p, 6p], the conditional
+//                        subtractions of 4p and 2p leave a value < 2p (6p -> 2p -> 0)
+//   evh_neg              4p - 2p = 2p -> 0
+//   f29_to_std           a FROM29 / 2^261 + p < 2p for any a < 16p; a nonzero multiple of p comes out as p, which the conditional subtraction
+//                        of p takes to 0
+//   f29_canon            conditional subtractions of 8p, 4p, 2p, p: 2p -> 0 at the third (f29_to_packed_canon: spills and internal-form stores)
 #pragma once
 #include <vector>
 
@@ -41,7 +52,7 @@ struct EvhArgs {
     u32 cols_internal, vals_internal;
 };
 
-// ---- lazily reduced helpers: every stored value is < 2p with normalized limbs ----------------
+// ---- lazily reduced helpers: every stored value is <= 2p with normalized limbs (2p: evh_neg(0) only, see the header) ----
 template <class F9> FP_DEV f29 evh_reduce_lt4p(const f29& a) { return f29_cond_sub(f29_norm(a), F9::P2); }
 template <class F9> FP_DEV f29 evh_add(const f29& a, const f29& b) { return evh_reduce_lt4p<F9>(f29_add(a, b)); }
 template <class F9> FP_DEV f29 evh_sub(const f29& a, const f29& b) {                  // a - b + 4p < 6p

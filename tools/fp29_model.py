@@ -206,6 +206,58 @@ class F29:
         assert v < (max_mult + 1) * self.p, "zero-test candidate set too small"
         return any(v == k * self.p for k in range(max_mult + 1))
 
+    # ---- the quotient kernels' lazily reduced helpers (csrc/evalh.cuh) ----
+    def cond_sub(self, a, c):
+        """f29_cond_sub: v >= c ? v - c : v on normalized limbs, with its 32-bit signed borrow chain"""
+        assert all(0 <= x <= MASK for x in a[:8]) and 0 <= a[8] < (1 << 31), "cond_sub: limbs not normalized"
+        cl = limbs(c)
+        d, borrow = [], 0
+        for i in range(8):
+            t = a[i] - cl[i] + borrow
+            assert -(1 << 31) <= t < (1 << 31)
+            d.append(t & MASK)
+            borrow = t >> 31
+        top = a[8] - cl[8] + borrow
+        assert -(1 << 31) <= top < (1 << 31)
+        out = d + [top] if top >= 0 else list(a)
+        assert value(out) == (value(a) - c if value(a) >= c else value(a))
+        return out
+
+    def evh_add(self, a, b):
+        return self.cond_sub(self.norm(self.add(a, b)), 2 * self.p)
+
+    def evh_sub(self, a, b):
+        t = self.norm(self.sub(a, b, self.KM))
+        return self.cond_sub(self.cond_sub(t, 4 * self.p), 2 * self.p)
+
+    def evh_neg(self, a):
+        return self.cond_sub(self.norm(self.sub([0] * L, a, self.KM)), 2 * self.p)
+
+    def evh_bounds(self, rnd):
+        """The stored-value invariant of evalh.cuh is <= 2p, with 2p itself produced by evh_neg(0) alone: every helper and every consumer on the representatives
+        0, p and 2p of zero, on the largest values below them and on random values <= 2p -- all stay <= 2p (the products and evh_sub strictly below), and the two
+        stores come out canonical."""
+        p = self.p
+        assert self.KM[1] == 4 * p
+        edge = [0, 1, p - 1, p, p + 1, 2 * p - 1, 2 * p]
+        vals = edge + [rnd.randrange(2 * p + 1) for _ in range(40)]
+        assert value(self.evh_neg(limbs(0))) == 2 * p
+        for x in vals:
+            a = limbs(x)
+            n = value(self.evh_neg(a))
+            assert n % p == -x % p and n <= 2 * p and (n < 2 * p or x == 0)
+            assert value(self.canon(a)) == x % p and value(self.cond_sub(self.cond_sub(self.cond_sub(self.cond_sub(a, 8 * p), 4 * p), 2 * p), p)) == x % p       # f29_canon
+            t = self.mont(a, limbs(self.FROM29))                                                 # f29_to_std
+            assert value(t) < 2 * p and value(self.cond_sub(t, p)) == x * pow(1 << (RBITS - 256), -1, p) % p
+            assert value(self.sqr(a)) < 2 * p
+            for y in vals:
+                b = limbs(y)
+                s, d, m = value(self.evh_add(a, b)), value(self.evh_sub(a, b)), value(self.mont(a, b))
+                assert s % p == (x + y) % p and s <= 2 * p and (s < 2 * p or x == y == 2 * p)
+                assert d % p == (x - y) % p and d < 2 * p
+                assert m < 2 * p
+                assert value(self.mont2(a, b, b, a)) < 2 * p
+
     # ---- codecs ----
     def enc(self, x):       # integer -> internal Montgomery limbs (canonical)
         return limbs(x * (1 << RBITS) % self.p)
@@ -362,6 +414,7 @@ def self_test():
             std = x * (1 << 256) % p
             assert F.dec(F.from_std(std)) == x
             assert F.to_std(F.enc(x)) == std
+        F.evh_bounds(random.Random(2))
         print(fname, "mont ok; KM mult", F.KM[1] // p, "KA mult", F.KA[1] // p, "KB mult", F.KB[1] // p, "KN mult", F.KN[1] // p, "INV", hex(F.INV), "P limbs", [hex(v) for v in F.P])
     for cname in ("pallas", "vesta", "bn254"):
         c = po.CURVES[cname]
