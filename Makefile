@@ -51,10 +51,14 @@ msm_plan_check: tests/native_host/msm_plan_check.cpp $(CSRC)/msm_plan.hpp $(CSRC
 opening_plan_check: tests/native_host/opening_plan_check.cpp $(CSRC)/opening_plan.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/opening_plan_check tests/native_host/opening_plan_check.cpp
 
+# the same plan for proofs over several circuits of one key (tests/test_multi_circuit.py reads it)
+opening_plan_multi_check: tests/native_host/opening_plan_multi_check.cpp $(CSRC)/opening_plan.hpp
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/opening_plan_multi_check tests/native_host/opening_plan_multi_check.cpp
+
 # the constraint system on the host (csrc/plonk_host.hpp: no HIP headers) with phases and challenges, under the same sanitizers (tests/test_phases_host.py runs it)
 host_cs_check: tests/native_host/host_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/hostfield.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/host_cs_check tests/native_host/host_cs_check.cpp
 
 clean:
 	rm -rf $(LIB) $(OBJDIR) $(PKG)/host/example; $(MAKE) -C oracle clean
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check host_cs_check
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check

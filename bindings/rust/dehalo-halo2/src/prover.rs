@@ -120,6 +120,16 @@ impl<'c> DehaloProver<'c> {
         Ok(DehaloProver { ctx, raw })
     }
 
+    /// A prover whose proofs are over `num_circuits` circuits of the key (`dehalo_prover_create_multi`): what `create_proof`'s `&[circuit_0, .., circuit_{N-1}]`
+    /// needs.  KZG, one advice phase; `new` is its `num_circuits == 1` case.  With more than one circuit only `create_proof_multi` proves on it.
+    pub fn new_multi(ctx: &'c Context, side: Option<&'c Context>, params: &DehaloParamsKZG<'c>, pk: &DehaloProvingKey<'c>, num_circuits: u32) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe {
+            sys::dehalo_prover_create_multi(ctx.as_ptr(), side.map_or(core::ptr::null_mut(), |s| s.as_ptr()), params.as_ptr(), pk.raw, num_circuits, &mut raw)
+        })?;
+        Ok(DehaloProver { ctx, raw })
+    }
+
     /// ONE proof on several GPUs (`dehalo_prover_set_shard`): of every multi-column commitment phase this process runs the MSMs of its share of the columns only and
     /// `gather` (an all-gather of at most ten affine points over RCCL / xGMI, see include/dehalo.h) fills in the rest; every process must then call `create_proof`
     /// with the same advice, instances and the same seeded generator.  `world == 1` switches it off.
@@ -146,6 +156,34 @@ impl<'c> DehaloProver<'c> {
         self.ctx.check(unsafe { sys::dehalo_transcript_create(sys::DEHALO_CURVE_BN254_G1, &mut t) })?;
         let rc = unsafe {
             sys::dehalo_create_proof(self.raw, advice.as_ptr() as *const u64, inst_ptrs.as_ptr(), inst_lens.as_ptr(), inst_ptrs.len() as u32, &mut r, t, 0)
+        };
+        let out = if rc == 0 {
+            let mut bytes = vec![0u8; unsafe { sys::dehalo_transcript_len(t) }];
+            let rc2 = unsafe { sys::dehalo_transcript_finalize(t, bytes.as_mut_ptr(), bytes.len()) };
+            if rc2 == 0 { Ok(bytes) } else { self.ctx.check(rc2).map(|_| vec![]) }
+        } else {
+            self.ctx.check(rc).map(|_| vec![])
+        };
+        unsafe { sys::dehalo_transcript_release(t) };
+        out
+    }
+
+    /// `create_proof(&params, &pk, &[circuit_0, .., circuit_{N-1}], &[instances_0, ..], rng, &mut transcript)`: ONE proof over `advice.len()` circuits of the key
+    /// (`dehalo_create_proof_multi`) on a prover of `new_multi` with that many.  `advice[c]` / `instances[c]`: circuit c's, as `create_proof` takes them; every
+    /// circuit brings the key's number of instance columns.  Returns the transcript bytes.
+    pub fn create_proof_multi<R: RngCore + Send>(&self, advice: &[&[Fr]], instances: &[&[&[Fr]]], rng: &mut R) -> Result<Vec<u8>, DehaloError> {
+        let columns = instances.first().map_or(0, |c| c.len());
+        if instances.len() != advice.len() || instances.iter().any(|c| c.len() != columns) {
+            return self.ctx.check(sys::DEHALO_ERR_INVALID).map(|_| vec![]);
+        }
+        let adv_ptrs: Vec<*const u64> = advice.iter().map(|a| a.as_ptr() as *const u64).collect();
+        let inst_ptrs: Vec<*const u64> = instances.iter().flat_map(|c| c.iter().map(|col| col.as_ptr() as *const u64)).collect();
+        let inst_lens: Vec<usize> = instances.iter().flat_map(|c| c.iter().map(|col| col.len())).collect();
+        let mut r = sys::dehalo_rng { kind: sys::DEHALO_RNG_CALLBACK, pcg_state: [0; 2], pcg_inc: [0; 2], fill: Some(fill_from::<R>), user: rng as *mut R as *mut c_void };
+        let mut t = core::ptr::null_mut();
+        self.ctx.check(unsafe { sys::dehalo_transcript_create(sys::DEHALO_CURVE_BN254_G1, &mut t) })?;
+        let rc = unsafe {
+            sys::dehalo_create_proof_multi(self.raw, adv_ptrs.as_ptr(), inst_ptrs.as_ptr(), inst_lens.as_ptr(), columns as u32, adv_ptrs.len() as u32, &mut r, t, 0)
         };
         let out = if rc == 0 {
             let mut bytes = vec![0u8; unsafe { sys::dehalo_transcript_len(t) }];

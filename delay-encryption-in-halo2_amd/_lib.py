@@ -35,6 +35,7 @@ SYMBOLS = [
     "dehalo_fixed_base_create", "dehalo_fixed_base_release", "dehalo_fixed_base_mul_device", "dehalo_fixed_base_blind_device", "dehalo_params_fixed_base",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
     "dehalo_check_witness", "dehalo_check_witness_challenges", "dehalo_create_proof_phased", "dehalo_pk_phases",
+    "dehalo_prover_create_multi", "dehalo_create_proof_multi",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -279,6 +280,8 @@ def load_library():
     lib.dehalo_transcript_release.argtypes = [P]
     lib.dehalo_transcript_release.restype = None
     lib.dehalo_prover_create.argtypes = [P, P, P, P, PP]
+    lib.dehalo_prover_create_multi.argtypes = [P, P, P, P, u32, PP]
+    lib.dehalo_create_proof_multi.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), P, u32]
     lib.dehalo_prover_release.argtypes = [P]
     lib.dehalo_create_proof.argtypes = [P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(CRng), P, u32]
     lib.dehalo_check_witness.argtypes = [P, P, u64p, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u64p, u32, C.POINTER(CCheckFailure), sz, C.POINTER(CCheckReport)]

@@ -4,6 +4,8 @@
 // permutation (sigma; products), lookups], the opening queries in upstream's order [UPSTREAM permutation::Constructed::open, lookup::Evaluated::open,
 // pk.permutation.open, vanishing::Evaluated::open] and the three multiopens' views of that one list: grouped by point (gwc/prover.rs), and as intermediate
 // sets (poly/ipa/multiopen.rs and poly/kzg/multiopen/shplonk.rs construct_intermediate_sets).  A polynomial is named by its id in the numbering below.
+// One proof over `circuits` witnesses of one key (upstream's slice of circuits): every per-circuit block below comes circuit after circuit, and what the key
+// owns (fixed, sigma) or the proof has once (the pieces of h, the random polynomial, the folded h) appears once.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -15,6 +17,7 @@
 struct OpeningShape {
     uint32_t k = 0, A = 0, num_fixed = 0, I = 0, L = 0, S = 0, npc = 0, bf = 0, pieces = 0;      // npc: permutation columns; pieces: of the quotient h
     bool query_instance = false;      // the scheme's QUERY_INSTANCE: true under IPA
+    uint32_t circuits = 1;            // witnesses proven in the one proof (KZG only)
     struct Query { uint32_t column; int32_t rotation; };
     std::vector<Query> advice_q, fixed_q, instance_q;
 };
@@ -27,8 +30,18 @@ struct OpeningPlan {
 
     // ---- layouts
     // the prover's own columns (values, then coefficient forms): [advice A | permuted (input, table) x L | permutation products S | lookup products L | random 1]
+    // With N circuits every block but the last holds circuit 0's columns, then circuit 1's ...: [advice A x N | permuted 2 L x N | (products S, products L) x N |
+    // random 1].  o_adv .. o_lz are circuit 0's; adv(c) .. lz(c) circuit c's.  A commitment phase is one run of columns: advice, permuted, products + random.
+    uint32_t circuits = 1, A = 0, L = 0, S = 0;
     uint32_t o_adv = 0, o_perm = 0, o_pz = 0, o_lz = 0, o_rand = 0, NC = 0;
-    // one blind per commitment: [advice A | permuted 2 L | products S + L | random 1 | h pieces | folded h | f | default x max(I, 1)].  Fixed, sigma and instance
+    uint32_t adv(uint32_t c) const { return o_adv + c * A; }
+    uint32_t perm(uint32_t c) const { return o_perm + c * 2 * L; }
+    uint32_t pz(uint32_t c) const { return o_pz + c * (S + L); }
+    uint32_t lz(uint32_t c) const { return o_lz + c * (S + L); }
+    // the order the products' commitments are written in: every circuit's permutation products, then every circuit's lookup products, then the random polynomial
+    // (as offsets from o_pz).  The identity with one circuit
+    std::vector<uint32_t> product_order;
+    // one blind per commitment: [the columns above, in their order | h pieces | folded h | f | default x max(I, 1)].  Fixed, sigma and instance
     // columns are committed under the default blind (bi_def); f is the IPA multiopen's own polynomial.  KZG commitments are not hiding: the slots exist, nobody reads them.
     uint32_t bi_adv = 0, bi_perm = 0, bi_prod = 0, bi_rand = 0, bi_h = 0, bi_hfold = 0, bi_f = 0, bi_def = 0, bi_count = 0;
     // polynomial ids: [NC columns | fixed | sigma | h pieces | instance (only when queried)]; the evaluation reads these num_polys.  One more id, p_hfold = num_polys,
@@ -69,9 +82,11 @@ struct OpeningPlan {
     }
 
     OpeningPlan() = default;
-    explicit OpeningPlan(const OpeningShape& sh) : k(sh.k) {
-        const uint32_t A = sh.A, L = sh.L, S = sh.S;
+    explicit OpeningPlan(const OpeningShape& sh) : k(sh.k), circuits(sh.circuits), A(sh.A), L(sh.L), S(sh.S) {
+        const uint32_t N = sh.circuits;
         const int32_t last = -(int32_t)(sh.bf + 1);
+        if (N == 0) { error = "no circuit"; return; }
+        if (N > 1 && sh.query_instance) { error = "several circuits in one proof: KZG only"; return; }
         rots = {0, 1, -1, last};
         for (auto& q : sh.advice_q) rots.push_back(q.rotation);
         for (auto& q : sh.fixed_q) rots.push_back(q.rotation);
@@ -83,8 +98,11 @@ struct OpeningPlan {
             rots.clear();
             return;
         }
-        o_adv = 0; o_perm = A; o_pz = A + 2 * L; o_lz = o_pz + S; o_rand = o_lz + L; NC = o_rand + 1;
-        bi_adv = 0; bi_perm = A; bi_prod = A + 2 * L; bi_rand = bi_prod + S + L; bi_h = bi_rand + 1; bi_hfold = bi_h + sh.pieces; bi_f = bi_hfold + 1; bi_def = bi_f + 1;
+        o_adv = 0; o_perm = N * A; o_pz = o_perm + N * 2 * L; o_lz = o_pz + S; o_rand = o_pz + N * (S + L); NC = o_rand + 1;
+        for (uint32_t c = 0; c < N; c++) for (uint32_t s = 0; s < S; s++) product_order.push_back(pz(c) + s - o_pz);
+        for (uint32_t c = 0; c < N; c++) for (uint32_t l = 0; l < L; l++) product_order.push_back(lz(c) + l - o_pz);
+        product_order.push_back(o_rand - o_pz);
+        bi_adv = o_adv; bi_perm = o_perm; bi_prod = o_pz; bi_rand = o_rand; bi_h = bi_rand + 1; bi_hfold = bi_h + sh.pieces; bi_f = bi_hfold + 1; bi_def = bi_f + 1;
         bi_count = bi_def + std::max<uint32_t>(sh.I, 1);
         p_fixed = NC; p_sigma = p_fixed + sh.num_fixed; p_hpiece = p_sigma + sh.npc; p_instance = p_hpiece + sh.pieces;
         num_polys = p_instance + (sh.query_instance ? sh.I : 0);
@@ -93,19 +111,22 @@ struct OpeningPlan {
         hpiece0 = (size_t)slot(p_hpiece, 0);
 
         auto wr = [&](uint32_t poly, int32_t r) { write.push_back(slot(poly, r)); };
-        for (auto& q : sh.advice_q) wr(o_adv + q.column, q.rotation);
+        for (uint32_t c = 0; c < N; c++)
+            for (auto& q : sh.advice_q) wr(adv(c) + q.column, q.rotation);
         for (auto& q : sh.fixed_q) wr(p_fixed + q.column, q.rotation);
         wr(o_rand, 0);                                                  // vanishing: random_eval
         for (uint32_t j = 0; j < sh.npc; j++) wr(p_sigma + j, 0);      // pk.permutation.evaluate
-        for (uint32_t s = 0; s < S; s++) {                              // permutation products
-            wr(o_pz + s, 0);
-            wr(o_pz + s, 1);
-            if (s != S - 1) wr(o_pz + s, last);
-        }
-        for (uint32_t l = 0; l < L; l++) {                              // lookups
-            const uint32_t zc = o_lz + l, ai = o_perm + 2 * l, ti = ai + 1;
-            wr(zc, 0); wr(zc, 1); wr(ai, 0); wr(ai, -1); wr(ti, 0);
-        }
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t s = 0; s < S; s++) {                          // permutation products
+                wr(pz(c) + s, 0);
+                wr(pz(c) + s, 1);
+                if (s != S - 1) wr(pz(c) + s, last);
+            }
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t l = 0; l < L; l++) {                          // lookups
+                const uint32_t zc = lz(c) + l, ai = perm(c) + 2 * l, ti = ai + 1;
+                wr(zc, 0); wr(zc, 1); wr(ai, 0); wr(ai, -1); wr(ti, 0);
+            }
 
         auto qu = [&](int32_t r, uint32_t poly, uint32_t blind) { queries.push_back({r, poly, slot(poly, r), blind}); };
         if (sh.query_instance)      // under IPA the instance columns' queries come first, and so do their values in the transcript
@@ -113,16 +134,17 @@ struct OpeningPlan {
                 qu(q.rotation, p_instance + q.column, bi_def);
                 instance_write.push_back(queries.back().eval);
             }
-        for (auto& q : sh.advice_q) qu(q.rotation, o_adv + q.column, bi_adv + q.column);
-        for (uint32_t s = 0; s < S; s++) {                              // permutation::Constructed::open
-            qu(0, o_pz + s, bi_prod + s);
-            qu(1, o_pz + s, bi_prod + s);
-        }
-        for (uint32_t s = S > 1 ? S - 1 : 0; s-- > 0;) qu(last, o_pz + s, bi_prod + s);      // sets.iter().rev().skip(1)
-        for (uint32_t l = 0; l < L; l++) {                              // lookup::Evaluated::open
-            const uint32_t zc = o_lz + l, ai = o_perm + 2 * l, ti = ai + 1;
-            const uint32_t zb = bi_prod + S + l, ab = bi_perm + 2 * l, tb = ab + 1;
-            qu(0, zc, zb); qu(0, ai, ab); qu(0, ti, tb); qu(-1, ai, ab); qu(1, zc, zb);
+        for (uint32_t c = 0; c < N; c++) {      // (a column of the prover's own has the blind of its number)
+            for (auto& q : sh.advice_q) qu(q.rotation, adv(c) + q.column, adv(c) + q.column);
+            for (uint32_t s = 0; s < S; s++) {                              // permutation::Constructed::open
+                qu(0, pz(c) + s, pz(c) + s);
+                qu(1, pz(c) + s, pz(c) + s);
+            }
+            for (uint32_t s = S > 1 ? S - 1 : 0; s-- > 0;) qu(last, pz(c) + s, pz(c) + s);      // sets.iter().rev().skip(1)
+            for (uint32_t l = 0; l < L; l++) {                              // lookup::Evaluated::open
+                const uint32_t zc = lz(c) + l, ai = perm(c) + 2 * l, ti = ai + 1;
+                qu(0, zc, zc); qu(0, ai, ai); qu(0, ti, ti); qu(-1, ai, ai); qu(1, zc, zc);
+            }
         }
         for (auto& q : sh.fixed_q) qu(q.rotation, p_fixed + q.column, bi_def);
         for (uint32_t j = 0; j < sh.npc; j++) qu(0, p_sigma + j, bi_def);      // pk.permutation.open

@@ -41,6 +41,9 @@ struct dehalo_prover {
     const HostField* f = nullptr;
     size_t n = 0, m = 0, u = 0;
     uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, I = 0, pieces = 0;
+    // circuits proven in one proof [UPSTREAM create_proof's `circuits: &[ConcreteCircuit]`]: N witnesses of the one key.  Every per-circuit buffer below holds
+    // circuit 0's columns, then circuit 1's ... (the plan's layout for `cols`), so a commitment phase of all circuits is one run of columns and one MSM launch
+    uint32_t N = 1;
     // advice phases [UPSTREAM plonk/prover.rs `for current_phase in phases`]: a phase's columns are committed together, so they sit side by side in `cols` --
     // column c in slot adv_slot[c], phase ph's columns (phase_cols[ph], ascending) in slots [phase_first[ph], phase_first[ph] + phase_cols[ph].size()).  With one
     // phase a column is its own slot
@@ -88,9 +91,12 @@ struct dehalo_prover {
     Pinned<uint64_t> rand_pin;     // host-drawn random polynomial (page-locked: its upload is one DMA that holds no stream)
     Event ev_side, ev_inst, ev_ready[3];      // ev_ready: one per commitment phase
 
-    int init(dehalo_ctx* c, dehalo_ctx* s, const dehalo_params* pa, const dehalo_pk* key) {
+    int init(dehalo_ctx* c, dehalo_ctx* s, const dehalo_params* pa, const dehalo_pk* key, uint32_t num_circuits) {
         ctx = c; side = s; params = pa; pk = key; f = key->f;
         ipa = pa->scheme == DEHALO_SCHEME_IPA;
+        N = num_circuits;
+        if (N > 1 && ipa) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "prover_create_multi: several circuits in one proof under ParamsKZG only");
+        if (N > 1 && key->cs.num_phases > 1) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "prover_create_multi: the key has later-phase advice columns");
         const HostCS& cs = pk->cs;
         const HostDomain& d = pk->dom;
         n = d.n; m = d.m; k = d.k; ek = d.extended_k;
@@ -110,6 +116,7 @@ struct dehalo_prover {
         OpeningShape sh;      // (the plan before anything is allocated: it is host work, and a circuit it refuses costs nothing)
         sh.k = k; sh.A = A; sh.num_fixed = cs.num_fixed; sh.I = I; sh.L = L; sh.S = S; sh.npc = (uint32_t)cs.perm_cols.size(); sh.bf = bf; sh.pieces = pieces;
         sh.query_instance = ipa;
+        sh.circuits = N;
         for (auto& q : cs.advice_q) sh.advice_q.push_back({q.index, q.rotation});
         for (auto& q : cs.fixed_q) sh.fixed_q.push_back({q.index, q.rotation});
         for (auto& q : cs.instance_q) sh.instance_q.push_back({q.index, q.rotation});
@@ -120,18 +127,18 @@ struct dehalo_prover {
         TRY(cols.alloc(ctx, (size_t)NC * n));
         if (side) TRY(polys_own.alloc(ctx, (size_t)NC * n));
         polys = side ? polys_own.p : cols.p;
-        TRY(instance.alloc(ctx, (size_t)std::max<uint32_t>(I, 1) * n));
-        TRY(instance_values.alloc(ctx, (size_t)std::max<uint32_t>(I, 1) * n));
-        TRY(compressed.alloc(ctx, (size_t)std::max<uint32_t>(2 * L, 1) * n));
-        TRY(num.alloc(ctx, (size_t)std::max<uint32_t>(S + L, 1) * n));
-        TRY(den.alloc(ctx, (size_t)std::max<uint32_t>(S + L, 1) * n));
-        TRY(ext.alloc(ctx, (size_t)(NC - 1 + I) * m));
+        TRY(instance.alloc(ctx, (size_t)std::max<uint32_t>(N * I, 1) * n));
+        TRY(instance_values.alloc(ctx, (size_t)std::max<uint32_t>(N * I, 1) * n));
+        TRY(compressed.alloc(ctx, (size_t)std::max<uint32_t>(N * 2 * L, 1) * n));
+        TRY(num.alloc(ctx, (size_t)std::max<uint32_t>(N * (S + L), 1) * n));
+        TRY(den.alloc(ctx, (size_t)std::max<uint32_t>(N * (S + L), 1) * n));
+        TRY(ext.alloc(ctx, (size_t)(NC - 1 + N * I) * m));
         TRY(h.alloc(ctx, m));
-        TRY(table_value.alloc(ctx, (size_t)std::max<uint32_t>(L, 1) * m));
+        TRY(table_value.alloc(ctx, (size_t)std::max<uint32_t>(N * L, 1) * m));
         TRY(hfold.alloc(ctx, n));
         // blinding values of a proof but the random polynomial, compacted: [advice rows | permuted rows | product rows]
         const size_t rows = n - u;
-        TRY(blind_dev.alloc(ctx, std::max<size_t>(1, (size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf)));
+        TRY(blind_dev.alloc(ctx, std::max<size_t>(1, (size_t)N * ((size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf))));
         TRY(omega_col.alloc(ctx, n, false));
         TRY(omega_powers(ctx, d, omega_col.p));
         table_rep.clear();
@@ -152,7 +159,7 @@ struct dehalo_prover {
         TRY(qbuf.alloc(ctx, ngroups * n));
         TRY(wbuf.alloc(ctx, ngroups * n));
         const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, (uint32_t)std::max<size_t>(8, plan.groups.size())), std::max<uint32_t>(I, pieces));      // the most points one phase commits
-        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + (L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
+        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + ((size_t)N * L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
         if (ipa) {      // the multiopen's buffers, sized from the constraint system: one polynomial per point set, twice more for the division chain
             const size_t ns = plan.point_sets.size();
             TRY(ipa_q.alloc(ctx, ns * n));
@@ -167,7 +174,7 @@ struct dehalo_prover {
         HIP_TRY(ctx, make_pinned(rand_pin, (size_t)n * 32));
         if (side) HIP_TRY(ctx, make_stream(hs, hipStreamNonBlocking));
         host_aff.resize(8 * (size_t)maxpts);
-        host_jac.resize(12 * (size_t)maxpts + 8 + L);
+        host_jac.resize(12 * (size_t)maxpts + 8 + (size_t)N * L);
         host_evals.resize(4 * plan.eval_count);
         TRY(dehalo_ctx_synchronize(ctx));
         return 0;
@@ -259,8 +266,9 @@ struct dehalo_prover {
     // `flags` > 0: that many int32 status words sit behind the points in `jac` (deferred lookup permutation) and come back with them; any non-zero one fails the call
     // `d_blinds` (ParamsIPA; null under KZG): one blind per column on the device -- [blind] W joins each point on the stream, behind the MSM, in one launch
     // `to_proof` false: absorbed only (common_point: the instance commitments)
+    // `order` (null: column order): the i-th point written is column order[i]'s -- several circuits' products sit circuit by circuit and are written kind by kind
     int commit(dehalo_transcript* tr, const fe* src, size_t count, bool lagrange, const std::function<int()>& before_sync = nullptr, size_t flags = 0,
-               const fe* d_blinds = nullptr, bool to_proof = true) {
+               const fe* d_blinds = nullptr, bool to_proof = true, const uint32_t* order = nullptr) {
         // sharded (dehalo_prover_set_shard): this process's share of the columns only; everything else of the proof is computed by every process
         const bool sharded = shard_world > 1 && shard_gather && count > 1;
         const size_t lo = sharded ? count * shard_rank / shard_world : 0, hi = sharded ? count * (shard_rank + 1) / shard_world : count;
@@ -276,7 +284,8 @@ struct dehalo_prover {
         tk("points on host");
         for (size_t i = 0; i < flags; i++)
             if (reinterpret_cast<const int32_t*>(host_jac.data() + 12 * count)[i])
-                return dh_fail(ctx, DEHALO_ERR_NOT_IN_TABLE, "permute_expression_pair: an input value of lookup " + std::to_string(i) + " is not in the table (ConstraintSystemFailure)");
+                return dh_fail(ctx, DEHALO_ERR_NOT_IN_TABLE, "permute_expression_pair: an input value of lookup " + std::to_string(i % L) + (N > 1 ? " of circuit " + std::to_string(i / L) : std::string()) +
+                                                                 " is not in the table (ConstraintSystemFailure)");
         if (hi > lo && !normalize_host(host_jac.data() + 12 * lo, hi - lo, host_aff.data() + 8 * lo)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
         if (sharded) {      // every process ends with all `count` affine points, in column order
             std::vector<uint32_t> first(shard_world), num(shard_world);
@@ -289,7 +298,7 @@ struct dehalo_prover {
             tk("points gathered");
         }
         for (size_t i = 0; i < count; i++)
-            if (!tr->write_point(host_aff.data() + 8 * i, to_proof)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
+            if (!tr->write_point(host_aff.data() + 8 * (order ? order[i] : i), to_proof)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
         return 0;
     }
 
@@ -348,10 +357,11 @@ struct ProofRun {
     const HostDomain& d;
     const int fid;
     const size_t n, m, u, rows;
-    const uint32_t k, ek, bf, A, L, S, I, pieces, nco, rot_scale;
+    const uint32_t k, ek, bf, A, L, S, I, N, pieces, nco, rot_scale;
     const bool ipa;
     // one gate polynomial: Horner(0, [g], y) = g does not depend on y, so the custom-gate pass of evaluate_h needs the advice (and instance)
-    // cosets only -- queued on the side context right behind the last phase's, long before y exists (a circuit with challenges waits for them instead)
+    // cosets only -- queued on the side context right behind the last phase's, long before y exists (a circuit with challenges waits for them instead).
+    // Of several circuits only the first starts the running value at zero: the others' gate passes multiply by y and wait for it
     const bool gates_early;
     const clk::time_point t_start = clk::now();
     clk::time_point t_phase = t_start;
@@ -369,19 +379,21 @@ struct ProofRun {
     std::atomic<int> helper_rc{0};
     double helper_ms[3] = {};
     // a host witness is pinned until this proof ends (every stream has been synchronised by then); one that is page-locked already stays as it is
-    std::unique_ptr<HostPin> pin_advice;
-    std::vector<const uint64_t*> fixed_v, adv_v, inst_v, fixed_c, adv_c, inst_c;      // pointer tables of the phases: values, cosets
+    std::vector<std::unique_ptr<HostPin>> pin_advice;
+    std::vector<const uint64_t*> fixed_v, fixed_c;                                    // pointer tables of the phases: values, cosets;
+    std::vector<std::vector<const uint64_t*>> adv_v, inst_v, adv_c, inst_c;           // a circuit's own by circuit
     Fe theta{}, beta{}, gamma{}, y{}, x{}, hfold_eval{};
     std::vector<Fe> point, xs;      // x at every rotation of the plan; x^(n i)
     const Fe* E = nullptr;          // the evaluations on the host, indexed by the opening plan
 
     ProofRun(dehalo_prover& pv, dehalo_transcript* t, dehalo_rng* r)
         : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream.get()), ss(pv.side ? pv.side->stream.get() : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
-          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), pieces(pv.pieces), nco(pv.plan.NC - 1),
+          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), N(pv.N), pieces(pv.pieces), nco(pv.plan.NC - 1),
           rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1 && pv.NCH == 0), chal(pv.NCH, Fe{{0, 0, 0, 0}}) {}
     ~ProofRun() {      // whatever path the proof took: the witness' copy (asynchronous) has landed before its pin goes, and the helper has finished
-        if (pin_advice && pin_advice->p) (void)hipStreamSynchronize(ms);
-        pin_advice.reset();
+        for (auto& pin : pin_advice)
+            if (pin && pin->p) { (void)hipStreamSynchronize(ms); break; }
+        pin_advice.clear();
         if (helper.joinable()) helper.join();
     }
     void mark(int slot) {
@@ -390,14 +402,15 @@ struct ProofRun {
         t_phase = now;
     }
 
-    // ---- random scalars, in upstream's order: per advice phase the blinding rows of its columns (column after column), then one blind per column of it; per lookup (bf + 1 rows
+    // ---- random scalars, in upstream's order, circuit after circuit within each step (advice: rows then blinds of circuit 0, rows then blinds of circuit 1, ...;
+    // the products: every circuit's permutation products, then every circuit's lookup products): per advice phase the blinding rows of its columns (column after column), then one blind per column of it; per lookup (bf + 1 rows
     // permuted input, bf + 1 permuted table, the two columns' blinds), per grand product (bf rows + its blind), the random polynomial (n), its blind,
     // the h pieces' blinds and, under IPA, f's blind.  KZG commitments are not hiding: it draws the blinds and drops them.  No draw depends on the
     // device, so all of them are made here, in that order, and the blinds go up with the blinding rows in one copy.
     int draw_blinds() {
         TRY(rng.init(rng_in, f));
         device_rng = rng.kind == DEHALO_RNG_OS;
-        c_adv = (size_t)A * rows; c_advb = A; c_lk = (size_t)L * (2 * rows + 2); c_pr = (size_t)(S + L) * (bf + 1);
+        c_adv = (size_t)N * A * rows; c_advb = (size_t)N * A; c_lk = (size_t)N * L * (2 * rows + 2); c_pr = (size_t)N * (S + L) * (bf + 1);
         const size_t draws_before = c_adv + c_advb + c_lk + c_pr;
         for (uint32_t ph = 0, off = 0; ph < p.nph; ph++) { adv_off[ph] = off; off += (uint32_t)(p.phase_cols[ph].size() * (rows + 1)); }
         p.blind_host.resize(4 * std::max<size_t>(1, draws_before));
@@ -409,7 +422,7 @@ struct ProofRun {
         std::vector<Fe> late(1 + (size_t)pieces + (ipa ? 1 : 0));      // random_blind, h_blinds, (IPA) f_blind
         TRY(rng.scalars(late[0].v, late.size()));
         bl.assign(p.plan.bi_count, zero);
-        if (ipa) {
+        if (ipa) {      // (one circuit)
             const Fe* B = (const Fe*)p.blind_host.data();
             for (uint32_t ph = 0; ph < p.nph; ph++)
                 for (size_t j = 0; j < p.phase_cols[ph].size(); j++) bl[p.plan.bi_adv + p.phase_cols[ph][j]] = B[adv_off[ph] + p.phase_cols[ph].size() * rows + j];
@@ -472,22 +485,21 @@ struct ProofRun {
 
     // compacted blinding rows [advice | permuted | products] -> one upload
     int upload_blinds() {
-        const size_t total = (size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf;
+        const size_t total = (size_t)N * ((size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf);
         std::vector<uint64_t>& b = p.blind_host;
         std::vector<uint64_t> packed(4 * std::max<size_t>(1, total));
         size_t o = c_adv;
-        for (uint32_t ph = 0; ph < p.nph; ph++)      // (slot order is draw order less the blinds between the phases)
-            memcpy(packed.data() + 4 * (size_t)p.phase_first[ph] * rows, b.data() + 4 * adv_off[ph], 32 * p.phase_cols[ph].size() * rows);
+        for (uint32_t c = 0; c < N; c++)      // (a circuit's draws: its columns' rows, then its columns' blinds)
+            for (uint32_t ph = 0; ph < p.nph; ph++)      // (slot order is draw order less the blinds between the phases)
+                memcpy(packed.data() + 4 * ((size_t)c * A + p.phase_first[ph]) * rows, b.data() + 4 * ((size_t)c * A * (rows + 1) + adv_off[ph]), 32 * p.phase_cols[ph].size() * rows);
         const uint64_t* lk = b.data() + 4 * (c_adv + c_advb);
-        for (uint32_t l = 0; l < L; l++) {      // (input rows, table rows, two unused blinds) per lookup
+        for (uint32_t l = 0; l < N * L; l++) {      // (input rows, table rows, two unused blinds) per lookup, circuit after circuit
             memcpy(packed.data() + 4 * o, lk + 4 * (size_t)l * (2 * rows + 2), 32 * 2 * rows);
             o += 2 * rows;
         }
         const uint64_t* pr = b.data() + 4 * (c_adv + c_advb + c_lk);
-        for (uint32_t s = 0; s < S + L; s++) {      // (bf rows, one unused blind) per product
-            memcpy(packed.data() + 4 * o, pr + 4 * (size_t)s * (bf + 1), 32 * bf);
-            o += bf;
-        }
+        for (uint32_t s = 0; s < N * (S + L); s++)      // (bf rows, one unused blind) per product, drawn in the order they are written: into its column's place
+            memcpy(packed.data() + 4 * (o + (size_t)p.plan.product_order[s] * bf), pr + 4 * (size_t)s * (bf + 1), 32 * bf);
         if (total) TRY(dh_h2d(ctx, p.blind_dev.p, packed.data(), total * 32, ms));
         if (total || ipa) HIP_TRY(ctx, hipStreamSynchronize(ms));      // `packed` is a local (and the blinds' copy of draw_blinds lands here)
         p.tk("blinds drawn and uploaded");
@@ -497,8 +509,9 @@ struct ProofRun {
     // ---- instance columns: values into the transcript (KZG: QUERY_INSTANCE = false), polynomials on the device
     int instance_columns(const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns) {
         if (num_instance_columns != I) return dh_fail(ctx, DEHALO_ERR_INVALID, "instances.len() != num_instance_columns");      // Error::InvalidInstances
-        if (I) HIP_TRY(ctx, hipMemsetAsync(p.instance.p, 0, (size_t)I * n * 32, ms));
-        for (uint32_t i = 0; i < I; i++) {
+        const uint32_t NI = N * I;      // circuit c's column i is column c * I + i of the arrays and of the buffers
+        if (I) HIP_TRY(ctx, hipMemsetAsync(p.instance.p, 0, (size_t)NI * n * 32, ms));
+        for (uint32_t i = 0; i < NI; i++) {
             const size_t len = instance_lens ? instance_lens[i] : 0;
             if (len > u) return dh_fail(ctx, DEHALO_ERR_INVALID, "instance column too long");      // Error::InstanceTooLarge
             if (len && (!instances || !instances[i])) return dh_fail(ctx, DEHALO_ERR_INVALID, "null instance column");
@@ -514,17 +527,17 @@ struct ProofRun {
         }
         // IPA (QUERY_INSTANCE = true): commit_lagrange(instance, Blind::default()), absorbed as points
         if (I && ipa) TRY(p.commit(tr, p.instance.p, I, true, nullptr, 0, p.blind_at(p.plan.bi_def), false));
-        if (I) HIP_TRY(ctx, hipMemcpyAsync(p.instance_values.p, p.instance.p, (size_t)I * n * 32, hipMemcpyDeviceToDevice, ms));
+        if (I) HIP_TRY(ctx, hipMemcpyAsync(p.instance_values.p, p.instance.p, (size_t)NI * n * 32, hipMemcpyDeviceToDevice, ms));
         if (I && side) HIP_TRY(ctx, hipEventRecord(p.ev_inst.get(), ms));
-        if (I && !side) TRY(dehalo_intt_scaled_device(ctx, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
+        if (I && !side) TRY(dehalo_intt_scaled_device(ctx, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, NI, nullptr));
         return 0;
     }
 
     // polys[first..] = lagrange_to_coeff(cols[..]), ext[..] = coeff_to_extended(..) on the side context once `e` (recorded BEFORE the phase's
     // commitment was queued) has passed; the launches themselves are made after the commitment's, while this thread would only wait
-    EvalIn coset_inputs() const {      // every column over the extended domain, internal form
+    EvalIn coset_inputs(uint32_t c) const {      // every column of circuit c over the extended domain, internal form
         EvalIn e;
-        e.cols(fixed_c, adv_c, inst_c);
+        e.cols(fixed_c, adv_c[c], inst_c[c]);
         e.in.form_flags = FF;
         e.in.challenges = (const uint64_t*)chal.data(); e.in.num_challenges = (uint32_t)chal.size();
         return e;
@@ -548,22 +561,30 @@ struct ProofRun {
         if (rc) return dh_fail(ctx, DEHALO_ERR_INVALID, "create_proof_phased: the advice callback returned " + std::to_string(rc) + " in phase " + std::to_string(ph));
         return 0;
     }
-    int advice_columns(const uint64_t* given, uint32_t flags) {
+    int advice_columns(const uint64_t* const* given, uint32_t flags) {
         for (uint32_t i = 0; i < cs.num_fixed; i++) fixed_v.push_back(col_ptr(p.pk->fixed_values, i, n)), fixed_c.push_back(col_ptr(p.pk->fixed_cosets, i, m));
-        for (uint32_t i = 0; i < A; i++) adv_v.push_back(col_ptr(p.cols, p.plan.o_adv + p.adv_slot[i], n)), adv_c.push_back(col_ptr(p.ext, p.plan.o_adv + p.adv_slot[i], m));
-        for (uint32_t i = 0; i < I; i++) inst_v.push_back(col_ptr(p.instance_values, i, n)), inst_c.push_back(col_ptr(p.ext, nco + i, m));
+        adv_v.resize(N); adv_c.resize(N); inst_v.resize(N); inst_c.resize(N);
+        for (uint32_t c = 0; c < N; c++) {
+            for (uint32_t i = 0; i < A; i++) adv_v[c].push_back(col_ptr(p.cols, p.plan.adv(c) + p.adv_slot[i], n)), adv_c[c].push_back(col_ptr(p.ext, p.plan.adv(c) + p.adv_slot[i], m));
+            for (uint32_t i = 0; i < I; i++) inst_v[c].push_back(col_ptr(p.instance_values, c * I + i, n)), inst_c[c].push_back(col_ptr(p.ext, nco + c * I + i, m));
+        }
         for (uint32_t ph = 0; ph < p.nph; ph++) {
             const uint64_t* advice = nullptr;
-            TRY(advice_of_phase(ph, given, &advice));
+            TRY(advice_of_phase(ph, given ? given[0] : nullptr, &advice));
             if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
             const std::vector<uint32_t>& pc = p.phase_cols[ph];
-            const uint32_t first = p.phase_first[ph], cnt = (uint32_t)pc.size();
+            const uint32_t first = p.phase_first[ph], cnt = N * (uint32_t)pc.size();      // (several circuits: one phase, whose columns are all of them)
             fe* adv = p.cols.at((size_t)(p.plan.o_adv + first) * n);
-            if (p.nph == 1) {      // every column at once
-                const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin.get();      // (the witness generator's output is page-locked already)
-                pin_advice.reset(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
-                if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(adv, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
-                else TRY(dh_h2d(ctx, adv, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
+            if (p.nph == 1) {      // every column at once, circuit after circuit
+                for (uint32_t c = 0; c < N; c++) {
+                    if (c) advice = given[c];
+                    if (!advice) return dh_fail(ctx, DEHALO_ERR_INVALID, "null advice");
+                    fe* dst = p.cols.at((size_t)p.plan.adv(c) * n);
+                    const bool pin = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) && advice != p.adv_pin.get();      // (the witness generator's output is page-locked already)
+                    pin_advice.emplace_back(new HostPin(pin ? advice : nullptr, (size_t)A * n * 32));
+                    if (flags & DEHALO_PROOF_ADVICE_ON_DEVICE) HIP_TRY(ctx, hipMemcpyAsync(dst, advice, (size_t)A * n * 32, hipMemcpyDeviceToDevice, ms));
+                    else TRY(dh_h2d(ctx, dst, advice, (size_t)A * n * 32, ms));      // a DMA from the pinned pages, or staged (witness below 4 MiB)
+                }
             } else      // the phase's columns only, a copy per run of neighbouring columns (they are neighbouring slots); the buffer is the caller's until the next
                         // callback: nothing is pinned, and a copy that is still in flight (device or page-locked memory) lands before this phase's commitments come back
                 for (uint32_t j = 0, run; j < cnt; j += run) {
@@ -584,12 +605,12 @@ struct ProofRun {
     int after_advice_queued(uint32_t ph) {
         if (I && side && ph == 0) {
             HIP_TRY(side, hipStreamWaitEvent(ss, p.ev_inst.get(), 0));
-            TRY(dehalo_intt_scaled_device(side, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, I, nullptr));
-            TRY(dehalo_coset_ntt_form_device(side, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
+            TRY(dehalo_intt_scaled_device(side, fid, p.instance.u64(), k, d.omega_inv.v, d.ifft_divisor.v, N * I, nullptr));
+            TRY(dehalo_coset_ntt_form_device(side, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, N * I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         }
-        if (side) TRY(side_ntt(p.plan.o_adv + p.phase_first[ph], (uint32_t)p.phase_cols[ph].size(), p.ev_ready[0].get()));
-        if (gates_early && ph + 1 == p.nph) {
-            EvalIn e = coset_inputs();
+        if (side) TRY(side_ntt(p.plan.o_adv + p.phase_first[ph], N * (uint32_t)p.phase_cols[ph].size(), p.ev_ready[0].get()));
+        if (gates_early && ph + 1 == p.nph) {      // (circuit 0's)
+            EvalIn e = coset_inputs(0);
             e.in.y = zero.v;
             TRY(dehalo_graph_evaluate_device(side, p.pk->custom_gates.get(), &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
         }
@@ -600,47 +621,49 @@ struct ProofRun {
     // ---- lookups: compress, permute, blind, commit
     int lookups() {
         if (!L) return 0;
-        std::vector<const dehalo_graph*> graphs;
-        std::vector<uint64_t*> outs;
-        for (uint32_t l = 0; l < L; l++) {      // lookups with the same table expressions share ONE compressed table column (their representative's)
-            graphs.push_back(p.pk->compress_graphs[l].first.get());
-            outs.push_back(p.compressed.u64((size_t)2 * l * n));
-            if (p.table_rep[l] == l) {
-                graphs.push_back(p.pk->compress_graphs[l].second.get());
-                outs.push_back(p.compressed.u64((size_t)(2 * l + 1) * n));
+        const uint32_t NL = N * L;      // circuit c's lookup l is pair c * L + l of `compressed` and of the permuted columns
+        for (uint32_t c = 0; c < N; c++) {      // (the compressions of a circuit read its own columns: a call per circuit)
+            std::vector<const dehalo_graph*> graphs;
+            std::vector<uint64_t*> outs;
+            for (uint32_t l = 0; l < L; l++) {      // lookups with the same table expressions share ONE compressed table column (their representative's)
+                graphs.push_back(p.pk->compress_graphs[l].first.get());
+                outs.push_back(p.compressed.u64((size_t)2 * (c * L + l) * n));
+                if (p.table_rep[l] == l) {
+                    graphs.push_back(p.pk->compress_graphs[l].second.get());
+                    outs.push_back(p.compressed.u64((size_t)(2 * (c * L + l) + 1) * n));
+                }
             }
+            EvalIn e;
+            e.cols(fixed_v, adv_v[c], inst_v[c]);
+            e.in.theta = theta.v;
+            e.in.challenges = (const uint64_t*)chal.data(); e.in.num_challenges = (uint32_t)chal.size();
+            TRY(dehalo_graph_evaluate_batch_device(ctx, graphs.data(), (uint32_t)graphs.size(), &e.in, k, 1, outs.data(), nullptr));
         }
-        EvalIn e;
-        e.cols(fixed_v, adv_v, inst_v);
-        e.in.theta = theta.v;
-        e.in.challenges = (const uint64_t*)chal.data(); e.in.num_challenges = (uint32_t)chal.size();
-        TRY(dehalo_graph_evaluate_batch_device(ctx, graphs.data(), (uint32_t)graphs.size(), &e.in, k, 1, outs.data(), nullptr));
         p.tk("compress queued");
         // the blinding rows [u, n) first: the permutation writes rows [0, u) only and ends with a read-back
-        const fe* bl_perm = p.blind_dev.p + (size_t)A * rows;
-        k_place_rows<<<(unsigned)((rows * 2 * L + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_perm * n + u), n, bl_perm, (uint32_t)rows, 2 * L);
+        const fe* bl_perm = p.blind_dev.p + (size_t)N * A * rows;
+        k_place_rows<<<(unsigned)((rows * 2 * NL + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_perm * n + u), n, bl_perm, (uint32_t)rows, 2 * NL);
         std::vector<const uint64_t*> pin, ptab;
         std::vector<uint64_t*> pout_in, pout_tab;
-        for (uint32_t l = 0; l < L; l++) {
-            pin.push_back(p.compressed.u64((size_t)2 * l * n));
-            ptab.push_back(p.compressed.u64((size_t)(2 * p.table_rep[l] + 1) * n));
-            pout_in.push_back(p.cols.u64((size_t)(p.plan.o_perm + 2 * l) * n));
-            pout_tab.push_back(p.cols.u64((size_t)(p.plan.o_perm + 2 * l + 1) * n));
-        }
-        // status flags behind the 2 L points of this phase: the stream runs from the permutation straight into the commitment, the flags come back with the points
+        // status flags behind the 2 N L points of this phase: the stream runs from the permutation straight into the commitment, the flags come back with the points
         std::vector<const uint32_t*> trep, tmult;
         std::vector<uint32_t> tcount;
-        for (uint32_t l = 0; l < L; l++) {
-            const dehalo_prover::TableRows& t = p.table_rows[p.table_rep[l]];
-            trep.push_back(t.d_rep.p); tmult.push_back(t.d_mult.p); tcount.push_back(t.count);
-        }
-        TRY(dehalo_permute_expression_pair_distinct_device(ctx, fid, pin.data(), ptab.data(), u, L, pout_in.data(), pout_tab.data(), trep.data(), tmult.data(), tcount.data(),
-                                                           reinterpret_cast<int32_t*>(p.jac.u64() + 12 * 2 * (size_t)L), nullptr));
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t l = 0; l < L; l++) {
+                pin.push_back(p.compressed.u64((size_t)2 * (c * L + l) * n));
+                ptab.push_back(p.compressed.u64((size_t)(2 * (c * L + p.table_rep[l]) + 1) * n));
+                pout_in.push_back(p.cols.u64((size_t)(p.plan.perm(c) + 2 * l) * n));
+                pout_tab.push_back(p.cols.u64((size_t)(p.plan.perm(c) + 2 * l + 1) * n));
+                const dehalo_prover::TableRows& t = p.table_rows[p.table_rep[l]];      // (of the key: every circuit's)
+                trep.push_back(t.d_rep.p); tmult.push_back(t.d_mult.p); tcount.push_back(t.count);
+            }
+        TRY(dehalo_permute_expression_pair_distinct_device(ctx, fid, pin.data(), ptab.data(), u, NL, pout_in.data(), pout_tab.data(), trep.data(), tmult.data(), tcount.data(),
+                                                           reinterpret_cast<int32_t*>(p.jac.u64() + 12 * 2 * (size_t)NL), nullptr));
         p.tk("permute queued");
         if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[1].get(), ms));
-        return p.commit(tr, p.cols.at((size_t)p.plan.o_perm * n), 2 * L, true, side ? std::function<int()>([this] { return after_lookups_queued(); }) : nullptr, L, p.blind_at(p.plan.bi_perm));
+        return p.commit(tr, p.cols.at((size_t)p.plan.o_perm * n), 2 * NL, true, side ? std::function<int()>([this] { return after_lookups_queued(); }) : nullptr, NL, p.blind_at(p.plan.bi_perm));
     }
-    int after_lookups_queued() { return side_ntt(p.plan.o_perm, 2 * L, p.ev_ready[1].get()); }
+    int after_lookups_queued() { return side_ntt(p.plan.o_perm, 2 * N * L, p.ev_ready[1].get()); }
 
     // ---- grand products: permutation sets, then lookups; one batched inversion.  The random polynomial's values are the launch's last column
     // (cols[o_rand] sits right behind the products): its commitment is written with theirs
@@ -664,35 +687,42 @@ struct ProofRun {
             pchal[j] = dj;
             dj = f->mul(dj, f->delta);
         }
-        // every product's numerator and denominator columns in ONE launch (k_product_terms) instead of a GraphEvaluator program per column
-        std::vector<const uint64_t*> pcolv, psig, pA, pS, pa, ps;
-        for (auto& pc : cs.perm_cols) pcolv.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_v[pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_v[pc.index] : inst_v[pc.index]);
+        // every product's numerator and denominator columns in ONE launch per circuit (k_product_terms) instead of a GraphEvaluator program per column: circuit c's
+        // S + L columns at its place in num / den, which is its products' place in `cols`
+        std::vector<const uint64_t*> psig;
         for (uint32_t j = 0; j < npc; j++) psig.push_back(col_ptr(p.pk->perm_values, j, n));
-        for (uint32_t l = 0; l < L; l++) {
-            pA.push_back(col_ptr(p.compressed, 2 * l, n));
-            pS.push_back(col_ptr(p.compressed, 2 * p.table_rep[l] + 1, n));
-            pa.push_back(col_ptr(p.cols, p.plan.o_perm + 2 * l, n));
-            ps.push_back(col_ptr(p.cols, p.plan.o_perm + 2 * l + 1, n));
-        }
         std::vector<Fe> set_factors(std::max<uint32_t>(S, 1));
         for (uint32_t s2 = 0; s2 < S; s2++) set_factors[s2] = pchal[std::min<uint32_t>(s2 * cs.chunk_len(), npc ? npc - 1 : 0)];      // beta delta^(first column of the set)
-        dehalo_product_inputs pin{};
-        pin.columns = pcolv.data(); pin.sigma = psig.data(); pin.num_columns = npc; pin.chunk_len = cs.chunk_len();
-        pin.omega_powers = p.omega_col.u64();
-        pin.beta = beta.v; pin.gamma = gamma.v; pin.delta = f->delta.v;
-        pin.set_factors = (const uint64_t*)set_factors.data();
-        pin.compressed_input = pA.data(); pin.compressed_table = pS.data(); pin.permuted_input = pa.data(); pin.permuted_table = ps.data();
-        pin.num_lookups = L;
-        TRY(dehalo_product_terms_device(ctx, fid, &pin, n, p.num.u64(), p.den.u64(), n, nullptr));
+        const uint32_t NP = N * (S + L);
+        for (uint32_t c = 0; c < N; c++) {
+            std::vector<const uint64_t*> pcolv, pA, pS, pa, ps;
+            for (auto& pc : cs.perm_cols) pcolv.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_v[c][pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_v[pc.index] : inst_v[c][pc.index]);
+            for (uint32_t l = 0; l < L; l++) {
+                pA.push_back(col_ptr(p.compressed, 2 * (c * L + l), n));
+                pS.push_back(col_ptr(p.compressed, 2 * (c * L + p.table_rep[l]) + 1, n));
+                pa.push_back(col_ptr(p.cols, p.plan.perm(c) + 2 * l, n));
+                ps.push_back(col_ptr(p.cols, p.plan.perm(c) + 2 * l + 1, n));
+            }
+            dehalo_product_inputs pin{};
+            pin.columns = pcolv.data(); pin.sigma = psig.data(); pin.num_columns = npc; pin.chunk_len = cs.chunk_len();
+            pin.omega_powers = p.omega_col.u64();
+            pin.beta = beta.v; pin.gamma = gamma.v; pin.delta = f->delta.v;
+            pin.set_factors = (const uint64_t*)set_factors.data();
+            pin.compressed_input = pA.data(); pin.compressed_table = pS.data(); pin.permuted_input = pa.data(); pin.permuted_table = ps.data();
+            pin.num_lookups = L;
+            TRY(dehalo_product_terms_device(ctx, fid, &pin, n, p.num.u64((size_t)c * (S + L) * n), p.den.u64((size_t)c * (S + L) * n), n, nullptr));
+        }
         p.tk("product graphs queued");
-        TRY(dehalo_grand_product_batch_device(ctx, fid, p.num.u64(), p.den.u64(), n, S + L, n, p.cols.u64((size_t)p.plan.o_pz * n), nullptr));
-        for (uint32_t s = 1; s < S; s++)      // z_s starts where z_{s-1} ended: z = vec![last_z]
-            TRY(dehalo_scale_device(ctx, fid, p.cols.u64((size_t)(p.plan.o_pz + s) * n), n, nullptr, 0, p.cols.u64((size_t)(p.plan.o_pz + s - 1) * n + u), nullptr));
+        TRY(dehalo_grand_product_batch_device(ctx, fid, p.num.u64(), p.den.u64(), n, NP, n, p.cols.u64((size_t)p.plan.o_pz * n), nullptr));
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t s = 1; s < S; s++)      // z_s starts where z_{s-1} ended: z = vec![last_z] (a circuit's first set starts at 1)
+                TRY(dehalo_scale_device(ctx, fid, p.cols.u64((size_t)(p.plan.pz(c) + s) * n), n, nullptr, 0, p.cols.u64((size_t)(p.plan.pz(c) + s - 1) * n + u), nullptr));
         // per column: bf blinding rows (n - bf .. n)
-        const fe* bl_prod = p.blind_dev.p + (size_t)(A + 2 * L) * rows;
-        k_place_rows<<<(unsigned)(((size_t)bf * (S + L) + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_pz * n + (n - bf)), n, bl_prod, bf, S + L);
+        const fe* bl_prod = p.blind_dev.p + (size_t)N * (A + 2 * L) * rows;
+        k_place_rows<<<(unsigned)(((size_t)bf * NP + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_pz * n + (n - bf)), n, bl_prod, bf, NP);
         if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[2].get(), ms));
-        return p.commit(tr, p.cols.at((size_t)p.plan.o_pz * n), S + L + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.plan.bi_prod));
+        return p.commit(tr, p.cols.at((size_t)p.plan.o_pz * n), NP + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.plan.bi_prod), true,
+                        N > 1 ? p.plan.product_order.data() : nullptr);
     }
     int restore_random() {      // (queued behind the MSM's kernels on the same stream)
         if (!side) HIP_TRY(ctx, hipMemcpyAsync(p.cols.at((size_t)p.plan.o_rand * n), p.wbuf.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
@@ -701,15 +731,15 @@ struct ProofRun {
     int after_products_queued() {
         TRY(restore_random());
         if (!side) return 0;
-        TRY(side_ntt(p.plan.o_pz, S + L, p.ev_ready[2].get()));
+        TRY(side_ntt(p.plan.o_pz, N * (S + L), p.ev_ready[2].get()));
         // the lookups' (compressed input + beta)(compressed table + gamma) over the extended domain need theta, beta, gamma and the advice /
         // fixed cosets: all there -- on the side context, beside the products' commitment, instead of after y
-        if (L) {
+        for (uint32_t c = 0; c < N && L; c++) {
             std::vector<const dehalo_graph*> graphs;
             for (auto& g : p.pk->lookup_graphs) graphs.push_back(g.get());
             std::vector<uint64_t*> outs;
-            for (uint32_t l = 0; l < L; l++) outs.push_back(p.table_value.u64((size_t)l * m));
-            EvalIn e = coset_inputs();
+            for (uint32_t l = 0; l < L; l++) outs.push_back(p.table_value.u64((size_t)(c * L + l) * m));
+            EvalIn e = coset_inputs(c);
             e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
             TRY(dehalo_graph_evaluate_batch_device(side, graphs.data(), L, &e.in, ek, rot_scale, outs.data(), nullptr));
         }
@@ -722,52 +752,56 @@ struct ProofRun {
         if (!side) {
             TRY(dehalo_intt_scaled_device(ctx, fid, p.cols.u64(), k, d.omega_inv.v, d.ifft_divisor.v, nco, nullptr));
             TRY(dehalo_coset_ntt_form_device(ctx, fid, p.cols.u64(), k, p.ext.u64(), ek, d.ext_omega.v, d.g_coset.v, nco, DEHALO_FORM_OUT_INTERNAL, nullptr));
-            if (I) TRY(dehalo_coset_ntt_form_device(ctx, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, I, DEHALO_FORM_OUT_INTERNAL, nullptr));
+            if (I) TRY(dehalo_coset_ntt_form_device(ctx, fid, p.instance.u64(), k, p.ext.u64((size_t)nco * m), ek, d.ext_omega.v, d.g_coset.v, N * I, DEHALO_FORM_OUT_INTERNAL, nullptr));
         } else {      // queued phase by phase on the side context: wait for it
             HIP_TRY(side, hipEventRecord(p.ev_side.get(), ss));
             HIP_TRY(ctx, hipStreamWaitEvent(ms, p.ev_side.get(), 0));
         }
         const uint64_t *l0 = p.pk->l_ext.u64(0), *l_last = p.pk->l_ext.u64(m), *l_active = p.pk->l_ext.u64(2 * m);
-        if (!gates_early) {
-            EvalIn e = coset_inputs();
-            e.in.y = y.v;
-            TRY(dehalo_graph_evaluate_device(ctx, p.pk->custom_gates.get(), &e.in, ek, rot_scale, nullptr, p.h.u64(), nullptr));
-        }
-        if (S) {
-            std::vector<const uint64_t*> z, pcols, sigma;
-            for (uint32_t s = 0; s < S; s++) z.push_back(col_ptr(p.ext, p.plan.o_pz + s, m));
-            for (auto& pc : cs.perm_cols) pcols.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_c[pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_c[pc.index] : inst_c[pc.index]);
-            for (uint32_t j = 0; j < npc; j++) sigma.push_back(col_ptr(p.pk->perm_cosets, j, m));
-            const Fe beta_zeta = f->mul(beta, d.g_coset);
-            dehalo_perm_inputs pi{};
-            pi.z = z.data(); pi.num_sets = S;
-            pi.columns = pcols.data(); pi.sigma = sigma.data(); pi.num_columns = npc;
-            pi.chunk_len = cs.chunk_len();
-            pi.last_rotation = -(int32_t)(bf + 1);
-            pi.l0 = l0; pi.l_last = l_last; pi.l_active_row = l_active;
-            pi.beta = beta.v; pi.gamma = gamma.v; pi.y = y.v; pi.delta = f->delta.v; pi.beta_zeta = beta_zeta.v; pi.extended_omega = d.ext_omega.v;
-            pi.form_flags = FF;
-            TRY(dehalo_permutation_h_device(ctx, fid, &pi, ek, rot_scale, p.h.u64(), nullptr));
-        }
-        for (uint32_t l = 0; l < L && !side; l++) {
-            EvalIn e = coset_inputs();
-            e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
-            TRY(dehalo_graph_evaluate_device(ctx, p.pk->lookup_graphs[l].get(), &e.in, ek, rot_scale, nullptr, p.table_value.u64((size_t)l * m), nullptr));
-        }
-        for (uint32_t first = 0; first < L; first += 8) {
-            std::vector<dehalo_lookup_inputs> li;
-            for (uint32_t l = first; l < std::min(L, first + 8); l++) {
-                dehalo_lookup_inputs q{};
-                q.product_coset = col_ptr(p.ext, p.plan.o_lz + l, m);
-                q.permuted_input_coset = col_ptr(p.ext, p.plan.o_perm + 2 * l, m);
-                q.permuted_table_coset = col_ptr(p.ext, p.plan.o_perm + 2 * l + 1, m);
-                q.table_value = p.table_value.u64((size_t)l * m);
-                q.l0 = l0; q.l_last = l_last; q.l_active_row = l_active;
-                q.beta = beta.v; q.gamma = gamma.v; q.y = y.v;
-                q.form_flags = FF;
-                li.push_back(q);
+        // evaluate_h: ONE running value over the circuits -- circuit c's gates, permutation terms and lookup terms continue from circuit c - 1's value
+        std::vector<const uint64_t*> sigma;
+        for (uint32_t j = 0; j < npc; j++) sigma.push_back(col_ptr(p.pk->perm_cosets, j, m));
+        const Fe beta_zeta = f->mul(beta, d.g_coset);
+        for (uint32_t c = 0; c < N; c++) {
+            if (c || !gates_early) {
+                EvalIn e = coset_inputs(c);
+                e.in.y = y.v;
+                TRY(dehalo_graph_evaluate_device(ctx, p.pk->custom_gates.get(), &e.in, ek, rot_scale, c ? p.h.u64() : nullptr, p.h.u64(), nullptr));
             }
-            TRY(dehalo_lookup_h_batch_device(ctx, fid, li.data(), (uint32_t)li.size(), ek, rot_scale, p.h.u64(), nullptr));
+            if (S) {
+                std::vector<const uint64_t*> z, pcols;
+                for (uint32_t s = 0; s < S; s++) z.push_back(col_ptr(p.ext, p.plan.pz(c) + s, m));
+                for (auto& pc : cs.perm_cols) pcols.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_c[c][pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_c[pc.index] : inst_c[c][pc.index]);
+                dehalo_perm_inputs pi{};
+                pi.z = z.data(); pi.num_sets = S;
+                pi.columns = pcols.data(); pi.sigma = sigma.data(); pi.num_columns = npc;
+                pi.chunk_len = cs.chunk_len();
+                pi.last_rotation = -(int32_t)(bf + 1);
+                pi.l0 = l0; pi.l_last = l_last; pi.l_active_row = l_active;
+                pi.beta = beta.v; pi.gamma = gamma.v; pi.y = y.v; pi.delta = f->delta.v; pi.beta_zeta = beta_zeta.v; pi.extended_omega = d.ext_omega.v;
+                pi.form_flags = FF;
+                TRY(dehalo_permutation_h_device(ctx, fid, &pi, ek, rot_scale, p.h.u64(), nullptr));
+            }
+            for (uint32_t l = 0; l < L && !side; l++) {
+                EvalIn e = coset_inputs(c);
+                e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
+                TRY(dehalo_graph_evaluate_device(ctx, p.pk->lookup_graphs[l].get(), &e.in, ek, rot_scale, nullptr, p.table_value.u64((size_t)(c * L + l) * m), nullptr));
+            }
+            for (uint32_t first = 0; first < L; first += 8) {
+                std::vector<dehalo_lookup_inputs> li;
+                for (uint32_t l = first; l < std::min(L, first + 8); l++) {
+                    dehalo_lookup_inputs q{};
+                    q.product_coset = col_ptr(p.ext, p.plan.lz(c) + l, m);
+                    q.permuted_input_coset = col_ptr(p.ext, p.plan.perm(c) + 2 * l, m);
+                    q.permuted_table_coset = col_ptr(p.ext, p.plan.perm(c) + 2 * l + 1, m);
+                    q.table_value = p.table_value.u64((size_t)(c * L + l) * m);
+                    q.l0 = l0; q.l_last = l_last; q.l_active_row = l_active;
+                    q.beta = beta.v; q.gamma = gamma.v; q.y = y.v;
+                    q.form_flags = FF;
+                    li.push_back(q);
+                }
+                TRY(dehalo_lookup_h_batch_device(ctx, fid, li.data(), (uint32_t)li.size(), ek, rot_scale, p.h.u64(), nullptr));
+            }
         }
         TRY(dehalo_scale_device(ctx, fid, p.h.u64(), m, (const uint64_t*)d.t_inv.data(), (uint32_t)d.t_inv.size(), nullptr, nullptr));      // divide_by_vanishing_poly
         TRY(dehalo_coset_intt_form_device(ctx, fid, p.h.u64(), ek, d.ext_omega_inv.v, d.ext_ifft_divisor.v, d.g_coset.v, 1, DEHALO_FORM_IN_INTERNAL, nullptr));
@@ -989,7 +1023,7 @@ struct ProofRun {
     }
 
     // create_proof [UPSTREAM plonk/prover.rs]; `synth_in`: of a circuit, synthesized inside (its advice replaces `advice`)
-    int run(const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, uint32_t flags,
+    int run(const uint64_t* const* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, uint32_t flags,
             const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info, dehalo_advice_fn fn = nullptr, void* user = nullptr) {
         advice_fn = fn; advice_user = user;
         p.ticks.clear();
@@ -997,9 +1031,11 @@ struct ProofRun {
         p.trace = getenv("DEHALO_PROVER_TRACE") != nullptr;
         (void)hipSetDevice(ctx->device);
         TRY(draw_blinds());
+        const uint64_t* synthesized = nullptr;
         if (synth_in) {
             TRY(synthesize(synth_in, synth_info));
-            advice = p.adv_pin.get();
+            synthesized = p.adv_pin.get();
+            advice = &synthesized;
             flags = (flags & ~(uint32_t)DEHALO_PROOF_ADVICE_ON_DEVICE) | DEHALO_PROOF_ADVICE_CANONICAL;
         }
         TRY(upload_blinds());
@@ -1033,15 +1069,18 @@ struct ProofRun {
     }
 };
 
-int prove(dehalo_prover* p, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng,
+// `advice`: one witness per circuit of the prover (null: synthesized inside, or asked for phase by phase)
+int prove(dehalo_prover* p, const uint64_t* const* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, dehalo_rng* rng,
           dehalo_transcript* transcript, uint32_t flags, const dehalo_circuit_inputs* synth_in, dehalo_synthesis_info* synth_info, dehalo_advice_fn fn = nullptr,
           void* user = nullptr) {
+    if (p->N > 1 && (synth_in || fn)) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "a prover of several circuits takes their witnesses through dehalo_create_proof_multi only");
     if (transcript->curve != p->pk->curve) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the transcript's curve differs from the key's");
     if (p->nph > 1 && synth_in) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "create_proof_circuit: the key has later-phase advice columns");
     if (p->nph > 1 && !fn)      // (its advice would have to exist before the first commitment)
         return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the key has later-phase advice columns, whose witness depends on the proof's challenges: use dehalo_create_proof_phased");
     std::lock_guard<std::mutex> lk(p->mu);
     if (p->nph > 1 && p->shard_world > 1) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "create_proof_phased: a sharded prover proves single-phase circuits only");
+    if (p->N > 1 && p->shard_world > 1) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "create_proof_multi: a sharded prover proves one circuit per proof");
     const int rc = ProofRun(*p, transcript, rng).run(advice, instances, instance_lens, num_instance_columns, flags, synth_in, synth_info, fn, user);
     if (rc) {      // leave nothing of this proof in flight on either context
         (void)hipStreamSynchronize(p->ctx->stream.get());
@@ -1053,14 +1092,19 @@ int prove(dehalo_prover* p, const uint64_t* advice, const uint64_t* const* insta
 }   // namespace
 
 extern "C" int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out) {
+    return dehalo_prover_create_multi(ctx, side_ctx, params, pk, 1, out);
+}
+
+extern "C" int dehalo_prover_create_multi(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, uint32_t num_circuits, dehalo_prover** out) {
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !params || !pk || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: null argument");
+        if (!num_circuits) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create_multi: no circuit");
         if (params->k != pk->k || params->curve != pk->curve) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: params and proving key disagree on k / curve");
         if (side_ctx && (side_ctx == ctx || side_ctx->device != ctx->device)) return dh_fail(ctx, DEHALO_ERR_INVALID, "prover_create: the side context must be another context of the same device");
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         (void)hipSetDevice(ctx->device);
         std::unique_ptr<dehalo_prover> p(new dehalo_prover);
-        TRY(p->init(ctx, side_ctx, params, pk));
+        TRY(p->init(ctx, side_ctx, params, pk, num_circuits));
         *out = p.release();
         return 0;
     });
@@ -1081,6 +1125,17 @@ extern "C" int dehalo_create_proof(dehalo_prover* p, const uint64_t* advice, con
                                    dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags) {
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || !transcript) return DEHALO_ERR_INVALID;
+        if (p->N > 1) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof: the prover was made for several circuits: use dehalo_create_proof_multi");
+        return prove(p, &advice, instances, instance_lens, num_instance_columns, rng, transcript, flags, nullptr, nullptr);
+    });
+}
+
+extern "C" int dehalo_create_proof_multi(dehalo_prover* p, const uint64_t* const* advice, const uint64_t* const* instances, const size_t* instance_lens,
+                                         uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !transcript) return DEHALO_ERR_INVALID;
+        if (!num_circuits || num_circuits != p->N) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "create_proof_multi: num_circuits differs from the prover's");
+        if (!advice) return dh_fail(p->ctx, DEHALO_ERR_INVALID, "null advice");
         return prove(p, advice, instances, instance_lens, num_instance_columns, rng, transcript, flags, nullptr, nullptr);
     });
 }
@@ -1098,6 +1153,7 @@ extern "C" int dehalo_prover_set_shard(dehalo_prover* p, uint32_t rank, uint32_t
     return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
         if (!p || world == 0 || rank >= world || (world > 1 && !gather)) return DEHALO_ERR_INVALID;
         if (world > 1 && p->nph > 1) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "prover_set_shard: the key has later-phase advice columns");
+        if (world > 1 && p->N > 1) return dh_fail(p->ctx, DEHALO_ERR_UNSUPPORTED, "prover_set_shard: the prover was made for several circuits");
         p->shard_rank = rank; p->shard_world = world; p->shard_gather = world > 1 ? gather : nullptr; p->shard_user = user;
         return 0;
     });
@@ -1173,7 +1229,8 @@ extern "C" int dehalo_create_proofs(dehalo_prover* const* provers, uint32_t num_
     return dh_guard(nullptr, [&]() -> int {
         if (!provers || !num_provers || (count && (!advice || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
         for (uint32_t i = 0; i < num_provers; i++)
-            if (provers[i] && provers[i]->nph > 1) return dh_fail(provers[i]->ctx, DEHALO_ERR_UNSUPPORTED, "create_proofs: the key has later-phase advice columns");
+            if (provers[i] && (provers[i]->nph > 1 || provers[i]->N > 1))
+                return dh_fail(provers[i]->ctx, DEHALO_ERR_UNSUPPORTED, provers[i]->N > 1 ? "create_proofs: the prover was made for several circuits" : "create_proofs: the key has later-phase advice columns");
         return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
             return dehalo_create_proof(p, advice[i], nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr, flags);
         });
@@ -1186,7 +1243,8 @@ extern "C" int dehalo_create_proofs_circuit(dehalo_prover* const* provers, uint3
     return dh_guard(nullptr, [&]() -> int {
         if (!provers || !num_provers || (count && (!inputs || !proofs_out || !proof_lens))) return DEHALO_ERR_INVALID;
         for (uint32_t i = 0; i < num_provers; i++)
-            if (provers[i] && provers[i]->nph > 1) return dh_fail(provers[i]->ctx, DEHALO_ERR_UNSUPPORTED, "create_proofs_circuit: the key has later-phase advice columns");
+            if (provers[i] && (provers[i]->nph > 1 || provers[i]->N > 1))
+                return dh_fail(provers[i]->ctx, DEHALO_ERR_UNSUPPORTED, provers[i]->N > 1 ? "create_proofs_circuit: the prover was made for several circuits" : "create_proofs_circuit: the key has later-phase advice columns");
         return proofs_on_threads(provers, num_provers, count, proofs_out, proof_cap, proof_lens, [&](dehalo_prover* p, uint32_t i, dehalo_transcript* tr) {
             return dehalo_create_proof_circuit(p, &inputs[i], nullptr, nullptr, nullptr, p->I ? p->I : 0, rngs ? &rngs[i] : nullptr, tr);
         });

@@ -393,8 +393,9 @@ class Blake2bWrite {
 // create_proof(&params, &pk, &[circuit], &[instances], rng, &mut transcript): `advice` is what circuit.synthesize assigned
 class Prover {
   public:
-    Prover(const Backend& be, const ParamsKZG& params, const ProvingKey& pk, const Backend* side = nullptr) : be_(be) {
-        be_.check(dehalo_prover_create(be_.raw(), side ? side->raw() : nullptr, params.raw(), pk.raw(), &p_));
+    // num_circuits: how many circuits of the key one proof is over (create_proof's `&[circuit]`); more than one proves through create_proof_multi
+    Prover(const Backend& be, const ParamsKZG& params, const ProvingKey& pk, const Backend* side = nullptr, uint32_t num_circuits = 1) : be_(be) {
+        be_.check(dehalo_prover_create_multi(be_.raw(), side ? side->raw() : nullptr, params.raw(), pk.raw(), num_circuits, &p_));
     }
     ~Prover() { dehalo_prover_release(p_); }
     Prover(const Prover&) = delete;
@@ -407,6 +408,21 @@ class Prover {
         std::vector<size_t> il;
         for (auto& col : instances) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
         be_.check(dehalo_create_proof(p_, advice[0].data(), ip.data(), il.data(), (uint32_t)ip.size(), rng, transcript.raw(), 0));
+    }
+    // create_proof(&params, &pk, &[circuit_0, .., circuit_{N-1}], &[instances_0, ..], rng, &mut transcript): ONE proof over advice.size() circuits of the key, on
+    // a prover made for that many (dehalo_create_proof_multi).  advice[c] / instances[c]: circuit c's, as create_proof takes them
+    void create_proof_multi(const std::vector<std::vector<Fe>>& advice, const std::vector<std::vector<std::vector<Fe>>>& instances, dehalo_rng* rng,
+                            Blake2bWrite& transcript) const {
+        std::vector<const uint64_t*> ap, ip;
+        std::vector<size_t> il;
+        for (auto& a : advice) ap.push_back(a.empty() ? nullptr : a[0].data());
+        for (auto& circuit : instances)
+            for (auto& col : circuit) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
+        const uint32_t columns = instances.empty() ? 0 : (uint32_t)instances[0].size();
+        for (auto& circuit : instances)
+            if (circuit.size() != columns) be_.check(DEHALO_ERR_INVALID);      // (every circuit has the key's instance columns)
+        if (instances.size() != advice.size()) be_.check(DEHALO_ERR_INVALID);
+        be_.check(dehalo_create_proof_multi(p_, ap.data(), ip.data(), il.data(), columns, (uint32_t)ap.size(), rng, transcript.raw(), 0));
     }
     // The same for a circuit with later-phase advice (dehalo_create_proof_phased): witness(phase, challenges) is called once per phase on this thread -- for
     // phase p > 0 after the commitments of phase p - 1 are in the transcript, with every challenge squeezed so far (the others zero) -- and returns all

@@ -425,15 +425,18 @@ class Prover:
 
     MULTIOPEN = {"gwc": 0, "shplonk": 1}      # dehalo_multiopen
 
-    def __init__(self, params: ParamsKZG, pk: ProvingKey, ctx: Optional[Context] = None, side_ctx: Optional[Context] = None, multiopen: str = "gwc"):
-        """multiopen: which KZG multiopen the proofs carry, "gwc" (ProverGWC, the default) or "shplonk" (ProverSHPLONK); ParamsIPA takes "gwc" (unset) only."""
-        self.params, self.pk = params, pk
+    def __init__(self, params: ParamsKZG, pk: ProvingKey, ctx: Optional[Context] = None, side_ctx: Optional[Context] = None, multiopen: str = "gwc",
+                 num_circuits: int = 1):
+        """multiopen: which KZG multiopen the proofs carry, "gwc" (ProverGWC, the default) or "shplonk" (ProverSHPLONK); ParamsIPA takes "gwc" (unset) only.
+        num_circuits: how many witnesses of the key one proof is over (dehalo_prover_create_multi; create_proof_multi); 1: create_proof and the rest."""
+        self.params, self.pk, self.num_circuits = params, pk, num_circuits
         self.ctx = ctx if ctx is not None else pk.ctx
         self.side = side_ctx
         self.handle = C.c_void_p()
         if multiopen not in self.MULTIOPEN:
             raise ValueError("multiopen: 'gwc' or 'shplonk'")
-        _check(self.ctx, load_library().dehalo_prover_create(self.ctx.handle, side_ctx.handle if side_ctx is not None else None, params.handle, pk.handle, C.byref(self.handle)))
+        _check(self.ctx, load_library().dehalo_prover_create_multi(self.ctx.handle, side_ctx.handle if side_ctx is not None else None, params.handle, pk.handle, num_circuits,
+                                                                   C.byref(self.handle)))
         if multiopen != "gwc":
             try:
                 self.set_multiopen(multiopen)
@@ -485,6 +488,45 @@ class Prover:
         lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
         r = rng_struct(rng)
         rc = lib.dehalo_create_proof(self.handle, adv_ptr, ptrs, lens, len(cols), C.byref(r) if r is not None else None, tr.handle, flags)
+        if rc != 0:
+            msg = lib.dehalo_last_error(self.ctx.handle).decode()
+            if rc == -1 and ("instance" in msg or "infinity" in msg):
+                raise ValueError(msg)
+            raise DehaloError(rc, msg)
+        rng_writeback(rng, r)
+        return tr
+
+    def create_proof_multi(self, advices, instances: Sequence[Sequence[Sequence[int]]], rng=None, transcript: Optional[Blake2bWrite] = None, canonical: bool = False,
+                           num_circuits: Optional[int] = None) -> Blake2bWrite:
+        """dehalo_create_proof_multi: ONE proof over len(advices) witnesses of the key.  advices: create_proof's `advice`, one per circuit (all host arrays or all
+        device tensors); instances[c]: circuit c's instance columns, each a list of canonical ints (every circuit the same number of columns)."""
+        lib = load_library()
+        tr = transcript if transcript is not None else Blake2bWrite(self.pk.curve)
+        f = self.pk.curve.scalar
+        flags = PROOF_ADVICE_CANONICAL if canonical else 0
+        on_device = [hasattr(a, "data_ptr") for a in advices]
+        if any(on_device) and not all(on_device):
+            raise ValueError("create_proof_multi: the witnesses are all host arrays or all device tensors")
+        if advices and all(on_device):
+            flags |= PROOF_ADVICE_ON_DEVICE
+            if any(getattr(a, "is_cuda", False) for a in advices):
+                import torch
+                torch.cuda.current_stream().synchronize()      # the library reads the tensors on its own stream
+            keep, adv_ptrs = list(advices), [a.data_ptr() for a in advices]
+        else:
+            keep = [np.ascontiguousarray(a, dtype=np.uint64) for a in advices]
+            adv_ptrs = [a.ctypes.data for a in keep]
+        per_circuit = {len(inst) for inst in instances}
+        if len(instances) != len(advices) or len(per_circuit) > 1:
+            raise ValueError("create_proof_multi: one list of instance columns per circuit, every circuit the same number of columns")
+        ncols = per_circuit.pop() if per_circuit else 0
+        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for inst in instances for v in inst]
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
+        lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
+        r = rng_struct(rng)
+        rc = lib.dehalo_create_proof_multi(self.handle, (C.c_void_p * max(1, len(adv_ptrs)))(*adv_ptrs), ptrs, lens, ncols, len(advices) if num_circuits is None else num_circuits,
+                                           C.byref(r) if r is not None else None, tr.handle, flags)
+        del keep
         if rc != 0:
             msg = lib.dehalo_last_error(self.ctx.handle).decode()
             if rc == -1 and ("instance" in msg or "infinity" in msg):

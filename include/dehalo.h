@@ -611,6 +611,14 @@ int dehalo_ipa_open(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t
  * `params` decides the scheme: ParamsKZG -> ProverGWC (or ProverSHPLONK: dehalo_prover_set_multiopen), ParamsIPA (Pallas / Vesta) -> ProverIPA.  DEHALO_ERR_UNSUPPORTED: more than 32 distinct
  * rotations among the circuit's queries and the prover's own {0, 1, -1, -(blinding_factors + 1)} (either scheme). */
 int dehalo_prover_create(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_prover** out);
+/* A prover whose proofs are over `num_circuits` witnesses of the one key [UPSTREAM create_proof(&params, &pk, &[circuit_0, .., circuit_{N-1}], &[instances_0, ..], ..)]:
+ * one transcript, one random polynomial, one quotient, one set of fixed and sigma evaluations and one multiopen for all of them (dehalo_create_proof_multi).
+ * dehalo_prover_create is its num_circuits = 1 case.  Every per-circuit buffer is num_circuits times a single prover's; the quotient's and the multiopen's are not.
+ * DEHALO_ERR_INVALID for num_circuits = 0; with num_circuits > 1 DEHALO_ERR_UNSUPPORTED for ParamsIPA and for a key with more than one advice phase;
+ * DEHALO_ERR_OOM when the buffers do not fit.  No cap on num_circuits is set here; the batched entry points a phase goes through take num_circuits x lookups
+ * < 4096 pairs (the permutation), < 65536 columns per transform or grand-product call and columns x 2^k x windows < 2^32 per MSM launch, and refuse more
+ * with DEHALO_ERR_INVALID at the proof. */
+int dehalo_prover_create_multi(dehalo_ctx* ctx, dehalo_ctx* side_ctx, const dehalo_params* params, const dehalo_pk* pk, uint32_t num_circuits, dehalo_prover** out);
 int dehalo_prover_release(dehalo_prover* prover);
 /* Which KZG multiopen a prover over ParamsKZG writes [UPSTREAM poly/kzg/multiopen/{gwc,shplonk}]: ProverGWC (the default: one witness commitment per distinct
  * opening point) or ProverSHPLONK (two commitments, h and h', whatever the circuit's rotations are).  Everything before the multiopen is the same proof.
@@ -624,7 +632,8 @@ int dehalo_prover_set_multiopen(dehalo_prover* prover, int multiopen);
  *   KZG / SHPLONK: the same with 2 in the place of the opening points
  *   IPA: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + 1 (f) + 1 (S) + 2 k) + 32 x (instance queries + evaluations + point sets + 2) */
 size_t dehalo_prover_proof_size(const dehalo_prover* prover);
-/* create_proof: one circuit, its instance columns, the caller's rng and transcript.
+/* create_proof: one circuit (of a prover made for one: DEHALO_ERR_INVALID on a prover of dehalo_prover_create_multi with num_circuits > 1), its instance columns,
+ * the caller's rng and transcript.
  *   advice     num_advice x 2^k x 4 u64 Montgomery (rows >= usable are overwritten by blinding), host memory, or device memory when
  *              DEHALO_PROOF_ADVICE_ON_DEVICE
  *   instances  num_instance_columns arrays of instance_lens[i] scalars (Montgomery); the reference passes none (&[&[&[]]])
@@ -636,6 +645,24 @@ size_t dehalo_prover_proof_size(const dehalo_prover* prover);
 enum { DEHALO_PROOF_ADVICE_ON_DEVICE = 1, DEHALO_PROOF_ADVICE_CANONICAL = 2 /* plain integers < p: converted on the device */ };
 int dehalo_create_proof(dehalo_prover* prover, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                         dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
+/* create_proof over the N = num_circuits witnesses of a prover made by dehalo_prover_create_multi: ONE proof [UPSTREAM plonk/prover.rs, the loops over `circuits`].
+ *   advice      N pointers, each a buffer of dehalo_create_proof's layout (all on the host, or all on the device with DEHALO_PROOF_ADVICE_ON_DEVICE)
+ *   instances   N x num_instance_columns arrays, circuit-major (circuit c's column i is entry c * num_instance_columns + i); instance_lens likewise
+ * Order of the transcript: the key's representation; every circuit's instance values (circuit after circuit, column after column); every circuit's advice
+ * commitments; theta; every circuit's permuted lookup pairs; beta, gamma; every circuit's permutation products, THEN every circuit's lookup products, then the
+ * random polynomial; y; the pieces of the one quotient, whose numerator is one running value v = v y + term over circuit 0's gates, permutation and lookup terms,
+ * circuit 1's, ...; x; the evaluations -- every circuit's advice queries | fixed | random | sigma | every circuit's permutation products | every circuit's
+ * lookups -- and the multiopen over the queries of circuit 0, circuit 1, ..., then once fixed, sigma, h, random.  The generator's draws are circuit-major the
+ * same way: the blinding rows of circuit c's advice columns, then its columns' blinds, then circuit c + 1's.  A PCG64 generator is advanced past all of them.
+ * Proof bytes (GWC; SHPLONK: 2 for `points`): 32 x (N (advice + 3 lookups + sets) + 1 + (degree - 1) + points)
+ *                                             + 32 x (N (advice queries + (3 sets - 1 if sets) + 5 lookups) + fixed queries + 1 + permutation columns).
+ * With N = 1 the proof is dehalo_create_proof's, byte for byte.  Each commitment phase is one MSM launch over all circuits' columns.
+ * Errors: dehalo_create_proof's for every circuit (DEHALO_ERR_NOT_IN_TABLE when any circuit's lookup input is missing from its table; the prover stays
+ * usable); DEHALO_ERR_INVALID for num_circuits = 0 or other than the prover's.  A prover with num_circuits > 1 proves through this call only:
+ * dehalo_create_proofs, dehalo_create_proof_circuit, dehalo_create_proofs_circuit, dehalo_create_proof_phased and dehalo_prover_set_shard (world > 1)
+ * return DEHALO_ERR_UNSUPPORTED on it. */
+int dehalo_create_proof_multi(dehalo_prover* prover, const uint64_t* const* advice, const uint64_t* const* instances, const size_t* instance_lens,
+                              uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
 /* create_proof of a circuit with later-phase advice [UPSTREAM plonk/prover.rs: `for current_phase in phases`]: the witness of phase p may depend on the challenges
  * squeezed after the commitments of the phases before it, so the caller supplies it through a callback, one call per phase.  After the instances are absorbed,
  * for each phase in order: fn(user, phase, challenges, num_challenges, &advice); the blinding rows of that phase's columns (column order), one blind per column;
