@@ -61,4 +61,8 @@ host_cs_check: tests/native_host/host_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC
 
 clean:
 	rm -rf $(LIB) $(OBJDIR) $(PKG)/host/example; $(MAKE) -C oracle clean
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check
+# the shuffle argument on the host (plonk_host.hpp, opening_plan.hpp) under ASan + UBSan (tests/test_shuffle.py)
+shuffle_cs_check: tests/native_host/shuffle_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/opening_plan.hpp
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/shuffle_cs_check tests/native_host/shuffle_cs_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check

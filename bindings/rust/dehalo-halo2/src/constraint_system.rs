@@ -18,6 +18,9 @@ pub struct Descriptor<F: ff::Field = Fr> {
     lookup_lens: Vec<u32>,
     lookup_inputs: Vec<u32>,
     lookup_tables: Vec<u32>,
+    shuffle_lens: Vec<u32>,
+    shuffle_inputs: Vec<u32>,
+    shuffle_tables: Vec<u32>,
     permutation_columns: Vec<sys::dehalo_column_query>,
     advice_queries: Vec<sys::dehalo_column_query>,
     fixed_queries: Vec<sys::dehalo_column_query>,
@@ -45,7 +48,7 @@ fn query(col: &Column<Any>, rot: Rotation) -> sys::dehalo_column_query {
 impl<F: ff::Field> Descriptor<F> {
     pub fn from_constraint_system(cs: &ConstraintSystem<F>) -> Self {
         let mut d = Descriptor {
-            nodes: vec![], constants: vec![], gates: vec![], lookup_lens: vec![], lookup_inputs: vec![], lookup_tables: vec![],
+            nodes: vec![], constants: vec![], gates: vec![], lookup_lens: vec![], lookup_inputs: vec![], lookup_tables: vec![], shuffle_lens: vec![], shuffle_inputs: vec![], shuffle_tables: vec![],
             permutation_columns: cs.permutation().get_columns().iter().map(|c| query(c, Rotation::cur())).collect(),
             advice_queries: cs.advice_queries().iter().map(|(c, r)| sys::dehalo_column_query { kind: sys::DEHALO_COLUMN_ADVICE as u32, index: c.index() as u32, rotation: r.0 }).collect(),
             fixed_queries: cs.fixed_queries().iter().map(|(c, r)| sys::dehalo_column_query { kind: sys::DEHALO_COLUMN_FIXED as u32, index: c.index() as u32, rotation: r.0 }).collect(),
@@ -72,6 +75,18 @@ impl<F: ff::Field> Descriptor<F> {
             for e in lookup.table_expressions() {
                 let r = d.lower(e);
                 d.lookup_tables.push(r);
+            }
+        }
+        // cs.shuffles() (halo2_proofs v0.3.0 and later: plonk::shuffle::Argument): (input, shuffle) expression pairs, as a lookup's
+        for shuffle in cs.shuffles() {
+            d.shuffle_lens.push(shuffle.input_expressions().len() as u32);
+            for e in shuffle.input_expressions() {
+                let r = d.lower(e);
+                d.shuffle_inputs.push(r);
+            }
+            for e in shuffle.shuffle_expressions() {
+                let r = d.lower(e);
+                d.shuffle_tables.push(r);
             }
         }
         d
@@ -139,6 +154,11 @@ impl<F: ff::Field> Descriptor<F> {
             advice_phases: if self.advice_phases.iter().any(|p| *p != 0) { self.advice_phases.as_ptr() } else { core::ptr::null() },
             challenge_phases: if self.challenge_phases.is_empty() { core::ptr::null() } else { self.challenge_phases.as_ptr() },
             num_challenges: self.challenge_phases.len() as u32,
+            // (null / 0 without a shuffle argument, likewise)
+            shuffle_lens: if self.shuffle_lens.is_empty() { core::ptr::null() } else { self.shuffle_lens.as_ptr() },
+            shuffle_inputs: if self.shuffle_lens.is_empty() { core::ptr::null() } else { self.shuffle_inputs.as_ptr() },
+            shuffle_tables: if self.shuffle_lens.is_empty() { core::ptr::null() } else { self.shuffle_tables.as_ptr() },
+            num_shuffles: self.shuffle_lens.len() as u32,
         }
     }
 }

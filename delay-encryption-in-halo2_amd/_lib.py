@@ -35,7 +35,7 @@ SYMBOLS = [
     "dehalo_fixed_base_create", "dehalo_fixed_base_release", "dehalo_fixed_base_mul_device", "dehalo_fixed_base_blind_device", "dehalo_params_fixed_base",
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
     "dehalo_check_witness", "dehalo_check_witness_challenges", "dehalo_create_proof_phased", "dehalo_pk_phases",
-    "dehalo_prover_create_multi", "dehalo_create_proof_multi",
+    "dehalo_prover_create_multi", "dehalo_create_proof_multi", "dehalo_shuffle_h_batch_device",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -69,6 +69,11 @@ class CLookupInputs(C.Structure):
                 ("form_flags", C.c_uint32)]
 
 
+class CShuffleInputs(C.Structure):
+    _fields_ = [("product_coset", C.c_void_p), ("input_value", C.c_void_p), ("shuffle_value", C.c_void_p),
+                ("l0", C.c_void_p), ("l_last", C.c_void_p), ("l_active_row", C.c_void_p), ("y", C.c_void_p), ("form_flags", C.c_uint32)]
+
+
 class CExprNode(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("a", C.c_uint32), ("b", C.c_uint32), ("rotation", C.c_int32)]
 
@@ -86,7 +91,8 @@ class CConstraintSystem(C.Structure):
                 ("advice_queries", C.POINTER(CColumnQuery)), ("num_advice_queries", C.c_uint32),
                 ("fixed_queries", C.POINTER(CColumnQuery)), ("num_fixed_queries", C.c_uint32),
                 ("instance_queries", C.POINTER(CColumnQuery)), ("num_instance_queries", C.c_uint32),
-                ("advice_phases", C.c_void_p), ("challenge_phases", C.c_void_p), ("num_challenges", C.c_uint32)]
+                ("advice_phases", C.c_void_p), ("challenge_phases", C.c_void_p), ("num_challenges", C.c_uint32),
+                ("shuffle_lens", C.POINTER(C.c_uint32)), ("shuffle_inputs", C.POINTER(C.c_uint32)), ("shuffle_tables", C.POINTER(C.c_uint32)), ("num_shuffles", C.c_uint32)]
 
 
 class CCircuitInputs(C.Structure):
@@ -119,7 +125,7 @@ class CCheckFailure(C.Structure):
 
 class CCheckReport(C.Structure):
     _fields_ = [("gate_failures", C.c_uint64), ("lookup_failures", C.c_uint64), ("copy_failures", C.c_uint64), ("rows", C.c_uint64), ("lookup_inputs", C.c_uint64),
-                ("cells_in_cycles", C.c_uint64), ("written", C.c_uint64)]
+                ("cells_in_cycles", C.c_uint64), ("written", C.c_uint64), ("shuffle_failures", C.c_uint64), ("shuffle_inputs", C.c_uint64)]
 
 
 class DehaloError(RuntimeError):
@@ -235,6 +241,7 @@ def load_library():
     if hasattr(lib, "dehalo_product_terms_device"):
         lib.dehalo_product_terms_device.argtypes = [P, C.c_int, C.POINTER(CProductInputs), sz, u64p, u64p, sz, P]
     lib.dehalo_lookup_h_batch_device.argtypes = [P, C.c_int, C.POINTER(CLookupInputs), u32, u32, u32, u64p, P]
+    lib.dehalo_shuffle_h_batch_device.argtypes = [P, C.c_int, C.POINTER(CShuffleInputs), u32, u32, u32, u64p, P]
     PP = C.POINTER(P)
     lib.dehalo_params_create.argtypes = [P, C.c_int, u32, u64p, u64p, P, P, PP]
     lib.dehalo_params_setup.argtypes = [P, C.c_int, u32, u64p, PP]
@@ -790,6 +797,13 @@ class Context:
         arr = (CLookupInputs * len(lookups))(*[CLookupInputs(z, a, s_, tv, l0, l_last, l_active, *[k.ctypes.data for k in keep], form_flags)
                                                for z, a, s_, tv in lookups])
         self._check(self.lib.dehalo_lookup_h_batch_device(self.handle, field, arr, len(lookups), log_rows, rot_scale, d_values, stream or None))
+
+    def shuffle_h_batch_device(self, field: int, shuffles: Sequence[Tuple[int, int, int]], l0: int, l_last: int, l_active: int, y, log_rows: int, rot_scale: int,
+                               d_values: int, stream: int = 0, form_flags: int = 0):
+        """shuffles: (product, input_value, shuffle_value) device pointers per shuffle, in the constraint system's order; one pass, at most 8."""
+        keep = np.ascontiguousarray(y, dtype=np.uint64).reshape(4)
+        arr = (CShuffleInputs * max(1, len(shuffles)))(*[CShuffleInputs(z, iv, sv, l0, l_last, l_active, keep.ctypes.data, form_flags) for z, iv, sv in shuffles])
+        self._check(self.lib.dehalo_shuffle_h_batch_device(self.handle, field, arr, len(shuffles), log_rows, rot_scale, d_values, stream or None))
 
     # ---- measurement ----
     def product_terms_device(self, field: int, columns: Sequence[int], sigma: Sequence[int], chunk_len: int, omega_powers: int, beta, gamma, delta, set_factors,

@@ -1258,6 +1258,21 @@ int dehalo_lookup_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_lookup
     return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.lookup_h_batch(ctx, in, count, log_rows, rot_scale, (fe*)d_values, s); });
 }
 
+int dehalo_shuffle_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_shuffle_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale,
+                                  uint64_t* d_values, void* stream) {
+    if (!in || !d_values || count == 0) return dh_fail(ctx, DEHALO_ERR_INVALID, "shuffle_h_batch: null argument");
+    if (count > 8) return dh_fail(ctx, DEHALO_ERR_INVALID, "shuffle_h_batch: more than 8 shuffles in one call");
+    for (uint32_t j = 0; j < count; j++) {
+        const dehalo_shuffle_inputs& q = in[j];
+        if (!q.product_coset || !q.input_value || !q.shuffle_value || !q.l0 || !q.l_last || !q.l_active_row || !q.y)
+            return dh_fail(ctx, DEHALO_ERR_INVALID, "shuffle_h_batch: null argument");
+        if (q.l0 != in[0].l0 || q.l_last != in[0].l_last || q.l_active_row != in[0].l_active_row || q.form_flags != in[0].form_flags || memcmp(q.y, in[0].y, 32))
+            return dh_fail(ctx, DEHALO_ERR_INVALID, "shuffle_h_batch: the shuffles of one call share l0 / l_last / l_active_row, y and the form flags");
+    }
+    if (log_rows > 30) return dh_fail(ctx, DEHALO_ERR_INVALID, "shuffle_h_batch: log_rows > 30");
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) { return f.shuffle_h_batch(ctx, in, count, log_rows, rot_scale, (fe*)d_values, s); });
+}
+
 // ---- measurement ------------------------------------------------------------------------------
 int dehalo_timing_enable(dehalo_ctx* ctx, int on) {
     if (!ctx) return DEHALO_ERR_INVALID;

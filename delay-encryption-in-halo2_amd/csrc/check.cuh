@@ -5,6 +5,8 @@
 //                    At a root the lane reduces the value fully, decides "zero or not", the wave ballots and one lane stores the 64-bit word:
 //                    one bit per (polynomial, row) where k_graph_eval writes 32 bytes per row.
 //   k_check_member   one lane per row: is the lookup's compressed input a key of its sorted table (binary search, full 256-bit compare)?
+//   k_check_shuffle  one lane per row: does the shuffle's compressed input occur as often among the sorted inputs as among the sorted shuffle side (two binary
+//                    searches in each)?  Both lists hold the same number of values, so no row fails exactly when the two multisets are equal.
 //
 // Both write whole bitmap words with ordinary stores, every word of their region exactly once: no atomics, nothing depends on the order of the launches' waves.
 // Included by evalh.cuh (instantiated per field in ntt_*.hip through FieldOps).
@@ -92,6 +94,33 @@ __global__ __launch_bounds__(CHK_THREADS) void k_check_member(const fe* __restri
     if ((threadIdx.x & 63) == 0) bitmap[row >> 6] = mask;
 }
 
+// the number of keys below `a` (upper: not above `a`) among n sorted canonical keys
+FP_DEV u64 chk_bound(const fe* __restrict__ keys, u64 n, const fe& a, bool upper) {
+    u64 lo = 0;
+    for (u64 len = n; len > 0;) {                            // invariant: the bound lies in [lo, lo + len]
+        const u64 half = len >> 1;
+        const int c = chk_cmp(f_load(&keys[lo + half]), a);
+        if (c < 0 || (upper && c == 0)) { lo += half + 1; len -= half + 1; }
+        else len = half;
+    }
+    return lo;
+}
+template <class F>
+__global__ __launch_bounds__(CHK_THREADS) void k_check_shuffle(const fe* __restrict__ input, const fe* __restrict__ keys_in, const fe* __restrict__ keys_side, u64 n_keys,
+                                                               u64 rows, u64 usable, u64* __restrict__ bitmap) {
+    const u64 row = (u64)blockIdx.x * CHK_THREADS + threadIdx.x;
+    if (row >= rows) return;
+    bool miss = false;
+    if (row < usable) {
+        const fe a = f_from_mont<F>(f_load(&input[row]));
+        const u64 m_in = chk_bound(keys_in, n_keys, a, true) - chk_bound(keys_in, n_keys, a, false);
+        const u64 m_side = chk_bound(keys_side, n_keys, a, true) - chk_bound(keys_side, n_keys, a, false);
+        miss = m_in != m_side;
+    }
+    const u64 mask = __ballot(miss);
+    if ((threadIdx.x & 63) == 0) bitmap[row >> 6] = mask;
+}
+
 template <class F>
 int graph_check_t(dehalo_ctx* ctx, const dehalo_graph* g, const dehalo_eval_inputs* in, uint32_t log_rows, uint64_t usable, uint64_t* bitmap, uint64_t words,
                   hipStream_t s) {
@@ -114,6 +143,16 @@ int check_member_t(dehalo_ctx* ctx, const fe* input, const fe* sorted_keys, uint
     const u64 rows = 1ull << log_rows;
     if (!n_keys || usable > rows) return dh_fail(ctx, DEHALO_ERR_INVALID, "check_member: bad shape");
     k_check_member<F><<<(u32)((rows + CHK_THREADS - 1) / CHK_THREADS), CHK_THREADS, 0, s>>>(input, sorted_keys, n_keys, rows, usable, (u64*)bitmap);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+template <class F>
+int check_shuffle_t(dehalo_ctx* ctx, const fe* input, const fe* sorted_inputs, const fe* sorted_side, uint64_t n_keys, uint32_t log_rows, uint64_t usable, uint64_t* bitmap,
+                    hipStream_t s) {
+    const u64 rows = 1ull << log_rows;
+    if (!n_keys || usable > rows || usable > n_keys) return dh_fail(ctx, DEHALO_ERR_INVALID, "check_shuffle: bad shape");
+    k_check_shuffle<F><<<(u32)((rows + CHK_THREADS - 1) / CHK_THREADS), CHK_THREADS, 0, s>>>(input, sorted_inputs, sorted_side, n_keys, rows, usable, (u64*)bitmap);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }

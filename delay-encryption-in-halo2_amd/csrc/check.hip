@@ -87,10 +87,10 @@ struct EmitArgs {
     const uint64_t* bitmap;
     const uint64_t* tile_prefix;
     uint64_t W, words;                  // words in all, words per bitmap row
-    uint32_t gates, lookups;            // rows of the first two regions (the rest: permutation columns)
+    uint32_t gates, lookups, copies;    // rows of the first three regions (the rest: shuffles)
     dehalo_check_failure* out;
     uint64_t cap;
-    uint64_t* bounds;                   // [3]: set bits in front of the lookups' region, in front of the copies' region, in all
+    uint64_t* bounds;                   // [4]: set bits in front of the lookups' region, in front of the copies' region, in front of the shuffles' region, in all
 };
 // the position of every set bit among all set bits = tile prefix + scan inside the tile; the first `cap` are written as failures, in bitmap order
 __global__ __launch_bounds__(CK_THREADS) void k_check_emit(EmitArgs A) {
@@ -108,16 +108,17 @@ __global__ __launch_bounds__(CK_THREADS) void k_check_emit(EmitArgs A) {
     for (uint32_t k = 0; k < wave; k++) before += wave_sums[k];
     if (w >= A.W) return;
     uint64_t off = A.tile_prefix[blockIdx.x] + before + (incl - cnt);
-    const uint64_t bound[3] = {(uint64_t)A.gates * A.words, (uint64_t)(A.gates + A.lookups) * A.words, A.W};
+    const uint64_t bound[4] = {(uint64_t)A.gates * A.words, (uint64_t)(A.gates + A.lookups) * A.words, (uint64_t)(A.gates + A.lookups + A.copies) * A.words, A.W};
 #pragma unroll
-    for (int b = 0; b < 3; b++) {
+    for (int b = 0; b < 4; b++) {
         if (w == bound[b]) A.bounds[b] = off;
         if (w == A.W - 1 && bound[b] == A.W) A.bounds[b] = off + cnt;
     }
     const uint32_t row_of = (uint32_t)(w / A.words);
     const uint64_t row0 = (w % A.words) * 64;
     uint32_t kind = DEHALO_CHECK_GATE, index = row_of;
-    if (row_of >= A.gates + A.lookups) { kind = DEHALO_CHECK_COPY; index = row_of - A.gates - A.lookups; }
+    if (row_of >= A.gates + A.lookups + A.copies) { kind = DEHALO_CHECK_SHUFFLE; index = row_of - A.gates - A.lookups - A.copies; }
+    else if (row_of >= A.gates + A.lookups) { kind = DEHALO_CHECK_COPY; index = row_of - A.gates - A.lookups; }
     else if (row_of >= A.gates) { kind = DEHALO_CHECK_LOOKUP; index = row_of - A.gates; }
     while (bits && off < A.cap) {
         const uint32_t bit = (uint32_t)__builtin_ctzll(bits);
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(CK_THREADS) void k_check_emit(EmitArgs A) {
     }
 }
 
-struct CheckHeader { uint64_t bounds[3]; uint32_t bad_mapping, pad; };
+struct CheckHeader { uint64_t bounds[4]; uint32_t bad_mapping, pad; };
 
 int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                const uint64_t* mapping, uint32_t flags, const uint64_t* challenges, uint32_t num_challenges, dehalo_check_failure* failures, size_t cap,
@@ -138,7 +139,7 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
     const FieldOps* ops = dh_field_ops(f->id);
     if (!ops) return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
     hipStream_t s = ctx->stream.get();
-    const uint32_t k = pk->k, A = cs.num_advice, I = cs.num_instance, NF = cs.num_fixed, G = (uint32_t)cs.gates.size(), L = (uint32_t)cs.lookups.size();
+    const uint32_t k = pk->k, A = cs.num_advice, I = cs.num_instance, NF = cs.num_fixed, G = (uint32_t)cs.gates.size(), L = (uint32_t)cs.lookups.size(), H = (uint32_t)cs.shuffles.size();
     const uint32_t P = mapping ? (uint32_t)cs.perm_cols.size() : 0;
     const size_t n = pk->dom.n, u = n - (cs.blinding_factors() + 1);
     const uint64_t words = (n + 63) / 64;
@@ -154,15 +155,16 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
     uint32_t T = 0;
     for (uint32_t l = 0; l < L; l++) { rep[l] = cs.table_representative(l); if (rep[l] == l) tslot[l] = T++; }
 
-    // ---- workspace: [advice copy | instance | compressed inputs | compressed tables], [bitmap | tile sums | tile prefixes | mapping | column pointers], [header | failures]
+    // ---- workspace: [advice copy | instance | compressed inputs | compressed tables | per shuffle: compressed inputs, compressed shuffle side], [bitmap | tile sums | tile prefixes | mapping | column pointers], [header | failures]
     const bool own_advice = !(flags & DEHALO_PROOF_ADVICE_ON_DEVICE) || (flags & DEHALO_PROOF_ADVICE_CANONICAL);
     const size_t adv_elems = own_advice ? (size_t)A * n : 0;
-    TRY(dh_ensure(ctx, ctx->ws_check[0], std::max<size_t>(32, (adv_elems + (size_t)(I + L + T) * n) * sizeof(fe))));
+    TRY(dh_ensure(ctx, ctx->ws_check[0], std::max<size_t>(32, (adv_elems + (size_t)(I + L + T + 2 * H) * n) * sizeof(fe))));
     fe* d_adv = (fe*)ctx->ws_check[0].p;
     fe* d_inst = d_adv + adv_elems;
     fe* d_cin = d_inst + (size_t)I * n;
     fe* d_ctab = d_cin + (size_t)L * n;
-    const uint64_t R = (uint64_t)G + L + P, W = R * words, tiles = (W + CK_THREADS - 1) / CK_THREADS;
+    fe* d_shuf = d_ctab + (size_t)T * n;      // shuffle j: inputs at 2 j, shuffle side at 2 j + 1
+    const uint64_t R = (uint64_t)G + L + P + H, W = R * words, tiles = (W + CK_THREADS - 1) / CK_THREADS;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_sums = up(W * 8), o_prefix = o_sums + up(tiles * 4), o_map = o_prefix + up(tiles * 8), o_ptrs = o_map + up((size_t)P * n * 8);
     TRY(dh_ensure(ctx, ctx->ws_check[1], o_ptrs + up((size_t)P * sizeof(void*)) + 256));
@@ -257,11 +259,35 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
         k_check_copy<<<dim3((unsigned)((n + CK_THREADS - 1) / CK_THREADS), P), CK_THREADS, 0, s>>>(C);
         HIP_TRY(ctx, hipGetLastError());
     }
+    // ---- shuffles: both sides compressed with the key's theta (the programs of the proof, gamma = 0) on the original domain, the usable rows' values of each
+    // sorted; every usable input row counts its value in both lists
+    if (H) {
+        std::vector<const dehalo_graph*> graphs;
+        std::vector<fe*> outs;
+        for (uint32_t j = 0; j < H; j++) {
+            graphs.push_back(pk->shuffle_graphs[j].first.get());
+            outs.push_back(d_shuf + (size_t)(2 * j) * n);
+            graphs.push_back(pk->shuffle_graphs[j].second.get());
+            outs.push_back(d_shuf + (size_t)(2 * j + 1) * n);
+        }
+        TRY(ops->graph_evaluate_batch(ctx, graphs.data(), (uint32_t)graphs.size(), &in, k, 1, outs.data(), s));
+        for (uint32_t j0 = 0; j0 < H; j0 += 8) {      // (the sort takes 16 columns a call: eight shuffles; its output lives until the next one)
+            const uint32_t jc = std::min<uint32_t>(8, H - j0);
+            std::vector<const fe*> tabs(2 * jc);
+            for (uint32_t t = 0; t < 2 * jc; t++) tabs[t] = d_shuf + (size_t)(2 * j0 + t) * n;
+            const fe* sorted = nullptr;
+            uint64_t npad = 0;
+            TRY(lookup_sort_tables(ctx, f->id, tabs.data(), 2 * jc, u, &sorted, &npad, s));
+            for (uint32_t j = 0; j < jc; j++)
+                TRY(ops->check_shuffle(ctx, d_shuf + (size_t)(2 * (j0 + j)) * n, sorted + (size_t)(2 * j) * npad, sorted + (size_t)(2 * j + 1) * npad, u, k, u,
+                                       d_bitmap + (uint64_t)(G + L + P + j0 + j) * words, s));
+        }
+    }
     // ---- count, scan, emit
     if (W) {
         k_check_count<<<(unsigned)tiles, CK_THREADS, 0, s>>>(d_bitmap, W, d_sums);
         k_check_scan<<<1, 1024, 0, s>>>(d_sums, tiles, d_prefix);
-        EmitArgs E{d_bitmap, d_prefix, W, words, G, L, d_fail, capd, d_hdr->bounds};
+        EmitArgs E{d_bitmap, d_prefix, W, words, G, L, P, d_fail, capd, d_hdr->bounds};
         k_check_emit<<<(unsigned)tiles, CK_THREADS, 0, s>>>(E);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -280,7 +306,9 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
     report->rows = u;
     report->lookup_inputs = (uint64_t)u * L;
     report->cells_in_cycles = in_cycles;
-    report->written = std::min<uint64_t>(cap, hdr.bounds[2]);
+    report->shuffle_failures = hdr.bounds[3] - hdr.bounds[2];
+    report->shuffle_inputs = (uint64_t)u * H;
+    report->written = std::min<uint64_t>(cap, hdr.bounds[3]);
     if (report->written) memcpy(failures, host.data() + sizeof hdr, (size_t)report->written * sizeof(dehalo_check_failure));
     return 0;
 }

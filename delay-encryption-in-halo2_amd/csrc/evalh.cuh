@@ -375,6 +375,51 @@ __global__ __launch_bounds__(EVH_THREADS) void k_lookup_h_batch(LookupBatchArgs 
     f_store(&A.values[row], A.vals_internal ? f29_to_packed_canon<F9>(v) : f29_to_std<F9>(v));
 }
 
+// ---- shuffle argument terms [halo2_proofs v0.3.0 plonk/evaluation.rs, "Shuffle constraints"] ----------------------
+// input_value[row] = compressed input + gamma and shuffle_value[row] = compressed shuffle side + gamma come from the shuffle's two GraphEvaluator programs
+// (k_graph_eval_batch into scratch columns).  Per row, shuffle after shuffle, in ONE pass (the running value and the three Lagrange columns are read once):
+//   v = v y + l0 (1 - z)
+//   v = v y + l_last (z^2 - z)
+//   v = v y + l_active ( z(wX) shuffle_value - z(X) input_value )
+// Operands (the header's discipline: every value <= 2p, normalized limbs).  Loads: an internal-form element is canonical (< p), f29_from_std gives < 2p.
+//   evh_sub(one, z), evh_sub(z^2, z), evh_sub(lhs, rhs)   subtrahends z, rhs < 2p < 3p: results < 2p
+//   f29_sqr(z), f29_mul(z_next, sv), f29_mul(z, iv)       operands <= 2p: results < 2p
+//   f29_mul2(v, y, t, l)                                   v, t < 2p, y and the Lagrange values < 2p: result < 2p, which is the next term's v
+//   the store                                              f29_to_packed_canon / f29_to_std take any value <= 2p
+// (tools/fp29_model.py evh_bounds() runs the three terms on {0, p, 2p}.)
+#define EVH_SHUFFLE_BATCH 8
+struct ShuffleBatchArgs {
+    const fe* z[EVH_SHUFFLE_BATCH]; const fe* input_value[EVH_SHUFFLE_BATCH]; const fe* shuffle_value[EVH_SHUFFLE_BATCH];
+    u32 count;
+    const fe* l0; const fe* l_last; const fe* l_active;
+    const fe* scalars;         // internal packed: [y]
+    u32 rows_mask, rot_scale;
+    fe* values;
+    u64 rows;
+    u32 cols_internal, vals_internal;
+};
+template <class F>
+__global__ __launch_bounds__(EVH_THREADS) void k_shuffle_h_batch(ShuffleBatchArgs A) {
+    typedef typename f29_of<F>::type F9;
+    const u64 row = (u64)blockIdx.x * EVH_THREADS + threadIdx.x;
+    if (row >= A.rows) return;
+    const f29 y = f29_unpack(f_load(&A.scalars[0]));
+    const f29 one = f29_one<F9>();
+    const u32 r_next = ((u32)row + A.rot_scale) & A.rows_mask;
+    auto ld = [&](const fe* p, u64 i) __attribute__((always_inline)) { return A.cols_internal ? f29_unpack(f_load(&p[i])) : f29_from_std<F9>(f_load(&p[i])); };
+    auto ldv = [&](const fe* p, u64 i) __attribute__((always_inline)) { return A.vals_internal ? f29_unpack(f_load(&p[i])) : f29_from_std<F9>(f_load(&p[i])); };
+    f29 v = ldv(A.values, row);
+    const f29 l0 = ld(A.l0, row), l_last = ld(A.l_last, row), l_active = ld(A.l_active, row);
+    for (u32 j = 0; j < A.count; j++) {
+        const fe* zc = A.z[j];
+        const f29 z = ld(zc, row), z_next = ld(zc, r_next), iv = ldv(A.input_value[j], row), sv = ldv(A.shuffle_value[j], row);
+        v = f29_mul2<F9>(v, y, evh_sub<F9>(one, z), l0);
+        v = f29_mul2<F9>(v, y, evh_sub<F9>(f29_sqr<F9>(z), z), l_last);
+        const f29 lhs = f29_mul<F9>(z_next, sv), rhs = f29_mul<F9>(z, iv);
+        v = f29_mul2<F9>(v, y, evh_sub<F9>(lhs, rhs), l_active);
+    }
+    f_store(&A.values[row], A.vals_internal ? f29_to_packed_canon<F9>(v) : f29_to_std<F9>(v));
+}
 
 // ---- the grand products' per-row factors (permutation::Argument::commit, lookup::Permuted::commit_product) --------------------
 // [UPSTREAM halo2_proofs/src/plonk/permutation/prover.rs: "modified_values" -- per set of columns the denominator prod_j (value_j + beta
@@ -650,6 +695,26 @@ int lookup_h_batch_t(dehalo_ctx* ctx, const dehalo_lookup_inputs* in, uint32_t c
     return 0;
 }
 
+template <class F>
+int shuffle_h_batch_t(dehalo_ctx* ctx, const dehalo_shuffle_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* d_values, hipStream_t s) {
+    const u64 rows = 1ull << log_rows;
+    ScopedTimer timer(ctx, s, DEHALO_K_EVAL_H);
+    std::vector<fe> sc = {fe_from_u64(in[0].y)};
+    TRY(dh_ensure(ctx, ctx->ws_evh[0], 16 * sizeof(fe)));
+    TRY(evh_stage_scalars<F>(ctx, sc, (fe*)ctx->ws_evh[0].p, s));
+    ShuffleBatchArgs A{};
+    A.count = count;
+    for (uint32_t j = 0; j < count; j++) {
+        A.z[j] = (const fe*)in[j].product_coset; A.input_value[j] = (const fe*)in[j].input_value; A.shuffle_value[j] = (const fe*)in[j].shuffle_value;
+    }
+    A.l0 = (const fe*)in[0].l0; A.l_last = (const fe*)in[0].l_last; A.l_active = (const fe*)in[0].l_active_row;
+    A.scalars = (const fe*)ctx->ws_evh[0].p;
+    A.rows_mask = (u32)(rows - 1); A.rot_scale = rot_scale; A.values = d_values; A.rows = rows;
+    A.cols_internal = in[0].form_flags & DEHALO_EVAL_COLUMNS_INTERNAL; A.vals_internal = in[0].form_flags & DEHALO_EVAL_VALUES_INTERNAL;
+    k_shuffle_h_batch<F><<<(u32)((rows + EVH_THREADS - 1) / EVH_THREADS), EVH_THREADS, 0, s>>>(A);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
 
 template <class F>
 int product_terms_t(dehalo_ctx* ctx, const dehalo_product_inputs* in, uint64_t n, fe* d_num, fe* d_den, uint64_t stride, hipStream_t s) {
@@ -698,5 +763,5 @@ constexpr FieldOps make_field_ops() {
             &eval_poly_t<F>, &eval_poly_multi_t<F>, &eval_poly_points_t<F>, &batch_invert_t<F>, &prefix_product_one_t<F>, &grand_product_t<F>, &lincomb_t<F>, &scale_t<F>,
             &kate_division_t<F>, &kate_division_batch_t<F>, &vanishing_quotient_batch_t<F>,
             &convert_form_t<F>, &graph_upload_t<F>, &graph_evaluate_t<F>, &graph_evaluate_batch_t<F>, &perm_h_t<F>, &lookup_h_t<F>, &lookup_h_batch_t<F>,
-            &product_terms_t<F>, &graph_check_t<F>, &check_member_t<F>};
+            &product_terms_t<F>, &graph_check_t<F>, &check_member_t<F>, &shuffle_h_batch_t<F>, &check_shuffle_t<F>};
 }

@@ -376,6 +376,12 @@ struct FieldOps {
                        hipStream_t s);
     // bitmap[row / 64] bit row % 64 = "input[row] (standard form) is none of the n_keys sorted canonical keys", rows >= usable masked; every word of 2^log_rows rows written
     int (*check_member)(dehalo_ctx* ctx, const fe* input, const fe* sorted_keys, uint64_t n_keys, uint32_t log_rows, uint64_t usable, uint64_t* bitmap, hipStream_t s);
+    // the shuffle arguments' terms of the quotient numerator (evalh.cuh), count <= 8
+    int (*shuffle_h_batch)(dehalo_ctx* ctx, const dehalo_shuffle_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale, fe* v, hipStream_t s);
+    // witness check (check.cuh): bitmap[row / 64] bit row % 64 = "input[row] (standard form) occurs another number of times among the n_keys sorted canonical keys of the
+    // inputs than among those of the shuffle side", rows >= usable masked; every word of 2^log_rows rows written
+    int (*check_shuffle)(dehalo_ctx* ctx, const fe* input, const fe* sorted_inputs, const fe* sorted_side, uint64_t n_keys, uint32_t log_rows, uint64_t usable,
+                         uint64_t* bitmap, hipStream_t s);
 };
 const FieldOps* dh_field_ops(int field);      // capi.hip: null for an unknown field
 // capi.hip: dehalo_graph_create for a checking program -- calculation i with root_of[i] != 0xffffffff computes root root_of[i] (kept by the copy propagation)

@@ -101,6 +101,12 @@ int dehalo_pk::compile_graphs() {
         TRY(compress_graph(cs, lk.tables, f).compile(ctx, adopt(ctx, gt)));
         compress_graphs.emplace_back(std::move(gi), std::move(gt));
     }
+    for (auto& sf : cs.shuffles) {
+        GraphPtr gi, gs;
+        TRY(shuffle_side_graph(cs, sf.inputs, f).compile(ctx, adopt(ctx, gi)));
+        TRY(shuffle_side_graph(cs, sf.tables, f).compile(ctx, adopt(ctx, gs)));
+        shuffle_graphs.emplace_back(std::move(gi), std::move(gs));
+    }
     const GateCheckProgram chk = gate_check_graph(cs, f);
     TRY(chk.g.compile(ctx, adopt(ctx, check_gates), &chk.root_of, (uint32_t)cs.gates.size()));
     return 0;
@@ -352,8 +358,8 @@ extern "C" int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]) {
         out[2] = cs.blinding_factors();
         out[3] = cs.degree();
         out[4] = S;
-        out[5] = cs.num_advice + 2 * L + S + L + 1 + (cs.degree() - 1);
-        out[6] = (uint32_t)(cs.advice_q.size() + cs.fixed_q.size() + 1 + cs.perm_cols.size() + (S ? 3 * S - 1 : 0) + 5 * L);
+        out[5] = cs.num_advice + 2 * L + S + L + (uint32_t)cs.shuffles.size() + 1 + (cs.degree() - 1);
+        out[6] = (uint32_t)(cs.advice_q.size() + cs.fixed_q.size() + 1 + cs.perm_cols.size() + (S ? 3 * S - 1 : 0) + 5 * L + 2 * cs.shuffles.size());
         std::vector<int32_t> rs = {0, 1, -(int32_t)(cs.blinding_factors() + 1)};
         if (L) rs.push_back(-1);
         for (auto& q : cs.advice_q) rs.push_back(q.rotation);

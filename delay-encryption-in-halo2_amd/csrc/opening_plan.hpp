@@ -1,7 +1,7 @@
 // opening_plan.hpp -- which value goes where in create_proof's last two phases, from the circuit's shape alone (host only: no HIP header, no device pointer;
 // tests/native_host/opening_plan_check.cpp prints it under ASan + UBSan and tests/test_opening_plan.py compares it with the CPU restatement's, symbol by symbol).
 // The transcript's order of the evaluations [UPSTREAM halo2_proofs @ v2023_04_20 plonk/prover.rs: instance (IPA), advice, fixed, vanishing random_eval,
-// permutation (sigma; products), lookups], the opening queries in upstream's order [UPSTREAM permutation::Constructed::open, lookup::Evaluated::open,
+// permutation (sigma; products), lookups, shuffles (halo2_proofs v0.3.0)], the opening queries in upstream's order [UPSTREAM permutation::Constructed::open, lookup::Evaluated::open,
 // pk.permutation.open, vanishing::Evaluated::open] and the three multiopens' views of that one list: grouped by point (gwc/prover.rs), and as intermediate
 // sets (poly/ipa/multiopen.rs and poly/kzg/multiopen/shplonk.rs construct_intermediate_sets).  A polynomial is named by its id in the numbering below.
 // One proof over `circuits` witnesses of one key (upstream's slice of circuits): every per-circuit block below comes circuit after circuit, and what the key
@@ -18,6 +18,7 @@ struct OpeningShape {
     uint32_t k = 0, A = 0, num_fixed = 0, I = 0, L = 0, S = 0, npc = 0, bf = 0, pieces = 0;      // npc: permutation columns; pieces: of the quotient h
     bool query_instance = false;      // the scheme's QUERY_INSTANCE: true under IPA
     uint32_t circuits = 1;            // witnesses proven in the one proof (KZG only)
+    uint32_t shuffles = 0;            // shuffle arguments: one grand product each
     struct Query { uint32_t column; int32_t rotation; };
     std::vector<Query> advice_q, fixed_q, instance_q;
 };
@@ -29,16 +30,18 @@ struct OpeningPlan {
     uint32_t k = 0;         // (an IPA proof has 2 k rounds)
 
     // ---- layouts
-    // the prover's own columns (values, then coefficient forms): [advice A | permuted (input, table) x L | permutation products S | lookup products L | random 1]
-    // With N circuits every block but the last holds circuit 0's columns, then circuit 1's ...: [advice A x N | permuted 2 L x N | (products S, products L) x N |
-    // random 1].  o_adv .. o_lz are circuit 0's; adv(c) .. lz(c) circuit c's.  A commitment phase is one run of columns: advice, permuted, products + random.
-    uint32_t circuits = 1, A = 0, L = 0, S = 0;
-    uint32_t o_adv = 0, o_perm = 0, o_pz = 0, o_lz = 0, o_rand = 0, NC = 0;
+    // the prover's own columns (values, then coefficient forms): [advice A | permuted (input, table) x L | permutation products S | lookup products L | shuffle products H | random 1]
+    // With N circuits every block but the last holds circuit 0's columns, then circuit 1's ...: [advice A x N | permuted 2 L x N | (products S, products L,
+    // products H) x N | random 1].  o_adv .. o_sz are circuit 0's; adv(c) .. sz(c) circuit c's.  A commitment phase is one run of columns: advice, permuted, products + random.
+    uint32_t circuits = 1, A = 0, L = 0, S = 0, H = 0;
+    uint32_t o_adv = 0, o_perm = 0, o_pz = 0, o_lz = 0, o_sz = 0, o_rand = 0, NC = 0;
     uint32_t adv(uint32_t c) const { return o_adv + c * A; }
     uint32_t perm(uint32_t c) const { return o_perm + c * 2 * L; }
-    uint32_t pz(uint32_t c) const { return o_pz + c * (S + L); }
-    uint32_t lz(uint32_t c) const { return o_lz + c * (S + L); }
-    // the order the products' commitments are written in: every circuit's permutation products, then every circuit's lookup products, then the random polynomial
+    uint32_t pz(uint32_t c) const { return o_pz + c * (S + L + H); }
+    uint32_t lz(uint32_t c) const { return o_lz + c * (S + L + H); }
+    uint32_t sz(uint32_t c) const { return o_sz + c * (S + L + H); }
+    // the order the products' commitments are written in: every circuit's permutation products, then every circuit's lookup products, then every circuit's
+    // shuffle products, then the random polynomial
     // (as offsets from o_pz).  The identity with one circuit
     std::vector<uint32_t> product_order;
     // one blind per commitment: [the columns above, in their order | h pieces | folded h | f | default x max(I, 1)].  Fixed, sigma and instance
@@ -82,7 +85,7 @@ struct OpeningPlan {
     }
 
     OpeningPlan() = default;
-    explicit OpeningPlan(const OpeningShape& sh) : k(sh.k), circuits(sh.circuits), A(sh.A), L(sh.L), S(sh.S) {
+    explicit OpeningPlan(const OpeningShape& sh) : k(sh.k), circuits(sh.circuits), A(sh.A), L(sh.L), S(sh.S), H(sh.shuffles) {
         const uint32_t N = sh.circuits;
         const int32_t last = -(int32_t)(sh.bf + 1);
         if (N == 0) { error = "no circuit"; return; }
@@ -98,9 +101,10 @@ struct OpeningPlan {
             rots.clear();
             return;
         }
-        o_adv = 0; o_perm = N * A; o_pz = o_perm + N * 2 * L; o_lz = o_pz + S; o_rand = o_pz + N * (S + L); NC = o_rand + 1;
+        o_adv = 0; o_perm = N * A; o_pz = o_perm + N * 2 * L; o_lz = o_pz + S; o_sz = o_lz + L; o_rand = o_pz + N * (S + L + H); NC = o_rand + 1;
         for (uint32_t c = 0; c < N; c++) for (uint32_t s = 0; s < S; s++) product_order.push_back(pz(c) + s - o_pz);
         for (uint32_t c = 0; c < N; c++) for (uint32_t l = 0; l < L; l++) product_order.push_back(lz(c) + l - o_pz);
+        for (uint32_t c = 0; c < N; c++) for (uint32_t j = 0; j < H; j++) product_order.push_back(sz(c) + j - o_pz);
         product_order.push_back(o_rand - o_pz);
         bi_adv = o_adv; bi_perm = o_perm; bi_prod = o_pz; bi_rand = o_rand; bi_h = bi_rand + 1; bi_hfold = bi_h + sh.pieces; bi_f = bi_hfold + 1; bi_def = bi_f + 1;
         bi_count = bi_def + std::max<uint32_t>(sh.I, 1);
@@ -127,6 +131,8 @@ struct OpeningPlan {
                 const uint32_t zc = lz(c) + l, ai = perm(c) + 2 * l, ti = ai + 1;
                 wr(zc, 0); wr(zc, 1); wr(ai, 0); wr(ai, -1); wr(ti, 0);
             }
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t j = 0; j < H; j++) { wr(sz(c) + j, 0); wr(sz(c) + j, 1); }      // shuffles
 
         auto qu = [&](int32_t r, uint32_t poly, uint32_t blind) { queries.push_back({r, poly, slot(poly, r), blind}); };
         if (sh.query_instance)      // under IPA the instance columns' queries come first, and so do their values in the transcript
@@ -145,6 +151,7 @@ struct OpeningPlan {
                 const uint32_t zc = lz(c) + l, ai = perm(c) + 2 * l, ti = ai + 1;
                 qu(0, zc, zc); qu(0, ai, ai); qu(0, ti, ti); qu(-1, ai, ai); qu(1, zc, zc);
             }
+            for (uint32_t j = 0; j < H; j++) { qu(0, sz(c) + j, sz(c) + j); qu(1, sz(c) + j, sz(c) + j); }      // shuffle::Evaluated::open
         }
         for (auto& q : sh.fixed_q) qu(q.rotation, p_fixed + q.column, bi_def);
         for (uint32_t j = 0; j < sh.npc; j++) qu(0, p_sigma + j, bi_def);      // pk.permutation.open

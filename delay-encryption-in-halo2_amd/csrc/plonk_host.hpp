@@ -17,6 +17,7 @@ struct HostCS {
     std::vector<uint32_t> gates;
     struct Lookup { std::vector<uint32_t> inputs, tables; };
     std::vector<Lookup> lookups;
+    std::vector<Lookup> shuffles;      // the shuffle arguments: `tables` holds the shuffle side's expressions
     std::vector<dehalo_column_query> perm_cols, advice_q, fixed_q, instance_q;
     // the Challenge API [UPSTREAM plonk/circuit.rs advice_column_phase, challenge_phase]: the phase of every advice column (0 .. 2) and, per challenge, the phase
     // after whose commitments it is squeezed.  One phase and no challenge: the circuits of before
@@ -34,6 +35,7 @@ struct HostCS {
             (d->num_advice_queries && !d->advice_queries) || (d->num_fixed_queries && !d->fixed_queries) || (d->num_instance_queries && !d->instance_queries))
             return "constraint system: null array with a non-zero count";
         if (d->num_challenges && !d->challenge_phases) return "constraint system: null challenge phases with a non-zero count";
+        if (d->num_shuffles && (!d->shuffle_lens || !d->shuffle_inputs || !d->shuffle_tables)) return "constraint system: null shuffle array with a non-zero count";
         advice_phase.assign(num_advice, 0);
         if (d->advice_phases) advice_phase.assign(d->advice_phases, d->advice_phases + num_advice);
         challenge_phase.assign(d->challenge_phases, d->challenge_phases + d->num_challenges);
@@ -73,6 +75,18 @@ struct HostCS {
             }
             if (lk.inputs.empty()) return "lookup without expressions";
             lookups.push_back(lk);
+        }
+        shuffles.clear();
+        off = 0;
+        for (uint32_t j = 0; j < d->num_shuffles; j++) {
+            Lookup sf;
+            for (uint32_t i = 0; i < d->shuffle_lens[j]; i++, off++) {
+                if (d->shuffle_inputs[off] >= d->num_nodes || d->shuffle_tables[off] >= d->num_nodes) return "shuffle expression root out of range";
+                sf.inputs.push_back(d->shuffle_inputs[off]);
+                sf.tables.push_back(d->shuffle_tables[off]);
+            }
+            if (sf.inputs.empty()) return "shuffle without expressions";
+            shuffles.push_back(sf);
         }
         auto copyq = [](std::vector<dehalo_column_query>& dst, const dehalo_column_query* src, uint32_t cnt) { dst.assign(src, src + cnt); };
         copyq(perm_cols, d->permutation_columns, d->num_permutation_columns);
@@ -154,8 +168,14 @@ struct HostCS {
         if (cnt.empty()) factors = 1;
         return std::max<uint32_t>(3, factors) + 2;
     }
-    uint32_t degree() const {                     // permutation: 3; a lookup: max(4, 2 + input + table); gates: their own
+    uint32_t degree() const {                     // permutation: 3; a lookup: max(4, 2 + input + table); a shuffle: max(2 + input, 2 + shuffle); gates: their own
         uint32_t d = 3;
+        for (auto& sf : shuffles) {
+            uint32_t di = 1, ds = 1;
+            for (uint32_t e : sf.inputs) di = std::max(di, expr_degree(e));
+            for (uint32_t e : sf.tables) ds = std::max(ds, expr_degree(e));
+            d = std::max(d, std::max(2 + di, 2 + ds));
+        }
         for (auto& lk : lookups) {
             uint32_t di = 1, dt = 1;
             for (uint32_t e : lk.inputs) di = std::max(di, expr_degree(e));
@@ -187,6 +207,11 @@ struct HostCS {
             for (uint8_t ph : advice_phase) out.push_back(ph);
             u32((uint32_t)challenge_phase.size());
             for (uint8_t ph : challenge_phase) out.push_back(ph);
+        }
+        if (!shuffles.empty()) {      // (only then, behind a marker no phase list can be taken for: every key without a shuffle keeps its encoding)
+            u32(0x46554853u);         // "SHUF"
+            u32((uint32_t)shuffles.size());
+            for (auto& sf : shuffles) { u32((uint32_t)sf.inputs.size()); for (size_t i = 0; i < sf.inputs.size(); i++) { u32(sf.inputs[i]); u32(sf.tables[i]); } }
         }
     }
 };
@@ -347,6 +372,17 @@ inline GraphBuilder compress_graph(const HostCS& cs, const std::vector<uint32_t>
     std::vector<GSrc> parts;
     for (uint32_t e : exprs) parts.push_back(g.add_expression(cs, e));
     g.add_calc(DEHALO_CALC_HORNER, GraphBuilder::ZERO, GSrc{DEHALO_SRC_THETA, 0, 0}, parts);
+    return g;
+}
+
+// One side of a shuffle argument: theta-compressed expressions + gamma.  Run over the extended domain it is the side's value in the quotient's term, run over the
+// original domain it is the side's column of the grand product (numerator: the inputs, denominator: the shuffle side)
+inline GraphBuilder shuffle_side_graph(const HostCS& cs, const std::vector<uint32_t>& exprs, const HostField* f) {
+    GraphBuilder g(f);
+    std::vector<GSrc> parts;
+    for (uint32_t e : exprs) parts.push_back(g.add_expression(cs, e));
+    const GSrc c = g.add_calc(DEHALO_CALC_HORNER, GraphBuilder::ZERO, GSrc{DEHALO_SRC_THETA, 0, 0}, parts);
+    g.add_calc(DEHALO_CALC_ADD, c, GSrc{DEHALO_SRC_GAMMA, 0, 0});
     return g;
 }
 

@@ -29,6 +29,16 @@ __global__ void k_place_rows(fe* __restrict__ dst, uint64_t dst_pitch, const fe*
     if (i < rows * ncols) dst[(uint64_t)(i / rows) * dst_pitch + i % rows] = src[i];
 }
 
+// status[i] = "shuffle product i does not come back to 1 at row u" for the `count` products of `circuits` circuits: circuit c's `per` products start
+// circuit_pitch elements behind circuit c - 1's, a product's column is n elements long.  `one`: 1 in the columns' (standard Montgomery) form
+__global__ void k_shuffle_closed(const fe* __restrict__ z, uint64_t circuit_pitch, uint64_t n, uint64_t u, uint32_t per, uint32_t count, fe one, int32_t* __restrict__ status) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t* v = (const uint64_t*)&z[(uint64_t)(i / per) * circuit_pitch + (uint64_t)(i % per) * n + u];
+    const uint64_t* o = (const uint64_t*)&one;
+    status[i] = (v[0] != o[0]) | (v[1] != o[1]) | (v[2] != o[2]) | (v[3] != o[3]);
+}
+
 const uint64_t* col_ptr(const DevMem& mem, size_t col, size_t len) { return (const uint64_t*)mem.at(col * len); }
 
 }   // namespace
@@ -40,7 +50,7 @@ struct dehalo_prover {
     const dehalo_pk* pk = nullptr;
     const HostField* f = nullptr;
     size_t n = 0, m = 0, u = 0;
-    uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, I = 0, pieces = 0;
+    uint32_t k = 0, ek = 0, bf = 0, A = 0, L = 0, S = 0, H = 0, I = 0, pieces = 0;      // H: shuffle arguments
     // circuits proven in one proof [UPSTREAM create_proof's `circuits: &[ConcreteCircuit]`]: N witnesses of the one key.  Every per-circuit buffer below holds
     // circuit 0's columns, then circuit 1's ... (the plan's layout for `cols`), so a commitment phase of all circuits is one run of columns and one MSM launch
     uint32_t N = 1;
@@ -49,7 +59,7 @@ struct dehalo_prover {
     // phase a column is its own slot
     uint32_t nph = 1, NCH = 0, phase_first[3] = {};
     std::vector<uint32_t> adv_slot, phase_cols[3];
-    DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, hfold, qbuf, wbuf, jac, evals, blind_dev, omega_col;
+    DevMem cols, polys_own, instance, instance_values, compressed, num, den, ext, h, table_value, shuffle_value, hfold, qbuf, wbuf, jac, evals, blind_dev, omega_col;
     fe* polys = nullptr;      // coefficient forms: polys_own with a side context, cols (in place) without
     std::vector<uint32_t> table_rep;      // per lookup: the first lookup with the same table expressions (shares its compressed table)
     // tables of fixed columns as distinct rows (lookup_permute.hip): per representative lookup one row index per distinct tuple of its table expressions' values over
@@ -102,7 +112,7 @@ struct dehalo_prover {
         n = d.n; m = d.m; k = d.k; ek = d.extended_k;
         bf = cs.blinding_factors();
         u = n - (bf + 1);
-        A = cs.num_advice; L = (uint32_t)cs.lookups.size(); S = cs.num_sets(); I = cs.num_instance;
+        A = cs.num_advice; L = (uint32_t)cs.lookups.size(); S = cs.num_sets(); H = (uint32_t)cs.shuffles.size(); I = cs.num_instance;
         pieces = d.quotient_poly_degree;
         nph = cs.num_phases; NCH = (uint32_t)cs.challenge_phase.size();
         adv_slot.assign(A, 0);
@@ -117,6 +127,7 @@ struct dehalo_prover {
         sh.k = k; sh.A = A; sh.num_fixed = cs.num_fixed; sh.I = I; sh.L = L; sh.S = S; sh.npc = (uint32_t)cs.perm_cols.size(); sh.bf = bf; sh.pieces = pieces;
         sh.query_instance = ipa;
         sh.circuits = N;
+        sh.shuffles = H;
         for (auto& q : cs.advice_q) sh.advice_q.push_back({q.index, q.rotation});
         for (auto& q : cs.fixed_q) sh.fixed_q.push_back({q.index, q.rotation});
         for (auto& q : cs.instance_q) sh.instance_q.push_back({q.index, q.rotation});
@@ -130,15 +141,16 @@ struct dehalo_prover {
         TRY(instance.alloc(ctx, (size_t)std::max<uint32_t>(N * I, 1) * n));
         TRY(instance_values.alloc(ctx, (size_t)std::max<uint32_t>(N * I, 1) * n));
         TRY(compressed.alloc(ctx, (size_t)std::max<uint32_t>(N * 2 * L, 1) * n));
-        TRY(num.alloc(ctx, (size_t)std::max<uint32_t>(N * (S + L), 1) * n));
-        TRY(den.alloc(ctx, (size_t)std::max<uint32_t>(N * (S + L), 1) * n));
+        TRY(num.alloc(ctx, (size_t)std::max<uint32_t>(N * (S + L + H), 1) * n));
+        TRY(den.alloc(ctx, (size_t)std::max<uint32_t>(N * (S + L + H), 1) * n));
         TRY(ext.alloc(ctx, (size_t)(NC - 1 + N * I) * m));
         TRY(h.alloc(ctx, m));
         TRY(table_value.alloc(ctx, (size_t)std::max<uint32_t>(N * L, 1) * m));
+        if (H) TRY(shuffle_value.alloc(ctx, (size_t)N * 2 * H * m));      // per circuit and shuffle: compressed input + gamma, compressed shuffle side + gamma
         TRY(hfold.alloc(ctx, n));
         // blinding values of a proof but the random polynomial, compacted: [advice rows | permuted rows | product rows]
         const size_t rows = n - u;
-        TRY(blind_dev.alloc(ctx, std::max<size_t>(1, (size_t)N * ((size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf))));
+        TRY(blind_dev.alloc(ctx, std::max<size_t>(1, (size_t)N * ((size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L + H) * bf))));
         TRY(omega_col.alloc(ctx, n, false));
         TRY(omega_powers(ctx, d, omega_col.p));
         table_rep.clear();
@@ -159,7 +171,7 @@ struct dehalo_prover {
         TRY(qbuf.alloc(ctx, ngroups * n));
         TRY(wbuf.alloc(ctx, ngroups * n));
         const uint32_t maxpts = std::max<uint32_t>(std::max<uint32_t>(NC, (uint32_t)std::max<size_t>(8, plan.groups.size())), std::max<uint32_t>(I, pieces));      // the most points one phase commits
-        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + ((size_t)N * L + 7) / 8));      // + the lookups' status flags behind a phase's points (one int32 each)
+        TRY(jac.alloc(ctx, 3 * (size_t)maxpts + 2 + ((size_t)N * std::max(L, H) + 7) / 8));      // + the lookups' / shuffles' status flags behind a phase's points (one int32 each)
         if (ipa) {      // the multiopen's buffers, sized from the constraint system: one polynomial per point set, twice more for the division chain
             const size_t ns = plan.point_sets.size();
             TRY(ipa_q.alloc(ctx, ns * n));
@@ -174,7 +186,7 @@ struct dehalo_prover {
         HIP_TRY(ctx, make_pinned(rand_pin, (size_t)n * 32));
         if (side) HIP_TRY(ctx, make_stream(hs, hipStreamNonBlocking));
         host_aff.resize(8 * (size_t)maxpts);
-        host_jac.resize(12 * (size_t)maxpts + 8 + (size_t)N * L);
+        host_jac.resize(12 * (size_t)maxpts + 8 + (size_t)N * std::max(L, H));
         host_evals.resize(4 * plan.eval_count);
         TRY(dehalo_ctx_synchronize(ctx));
         return 0;
@@ -263,12 +275,13 @@ struct dehalo_prover {
     }
 
     // commit `count` columns starting at `src`, read back, normalise, absorb (and append to the proof)
-    // `flags` > 0: that many int32 status words sit behind the points in `jac` (deferred lookup permutation) and come back with them; any non-zero one fails the call
+    // `flags` > 0: that many int32 status words sit behind the points in `jac` (deferred lookup permutation; `shuffle_flags`: the shuffle products' closing
+    // test) and come back with them; any non-zero one fails the call
     // `d_blinds` (ParamsIPA; null under KZG): one blind per column on the device -- [blind] W joins each point on the stream, behind the MSM, in one launch
     // `to_proof` false: absorbed only (common_point: the instance commitments)
     // `order` (null: column order): the i-th point written is column order[i]'s -- several circuits' products sit circuit by circuit and are written kind by kind
     int commit(dehalo_transcript* tr, const fe* src, size_t count, bool lagrange, const std::function<int()>& before_sync = nullptr, size_t flags = 0,
-               const fe* d_blinds = nullptr, bool to_proof = true, const uint32_t* order = nullptr) {
+               const fe* d_blinds = nullptr, bool to_proof = true, const uint32_t* order = nullptr, bool shuffle_flags = false) {
         // sharded (dehalo_prover_set_shard): this process's share of the columns only; everything else of the proof is computed by every process
         const bool sharded = shard_world > 1 && shard_gather && count > 1;
         const size_t lo = sharded ? count * shard_rank / shard_world : 0, hi = sharded ? count * (shard_rank + 1) / shard_world : count;
@@ -283,7 +296,11 @@ struct dehalo_prover {
         TRY(dehalo_download(ctx, jac.p, count * 96 + flags * 4, host_jac.data()));
         tk("points on host");
         for (size_t i = 0; i < flags; i++)
-            if (reinterpret_cast<const int32_t*>(host_jac.data() + 12 * count)[i])
+            if (!reinterpret_cast<const int32_t*>(host_jac.data() + 12 * count)[i]) continue;
+            else if (shuffle_flags)
+                return dh_fail(ctx, DEHALO_ERR_SHUFFLE, "shuffle " + std::to_string(i % H) + (N > 1 ? " of circuit " + std::to_string(i / H) : std::string()) +
+                                                            ": its input and shuffle expressions are not a permutation of each other over the usable rows (the product does not end at 1)");
+            else
                 return dh_fail(ctx, DEHALO_ERR_NOT_IN_TABLE, "permute_expression_pair: an input value of lookup " + std::to_string(i % L) + (N > 1 ? " of circuit " + std::to_string(i / L) : std::string()) +
                                                                  " is not in the table (ConstraintSystemFailure)");
         if (hi > lo && !normalize_host(host_jac.data() + 12 * lo, hi - lo, host_aff.data() + 8 * lo)) return dh_fail(ctx, DEHALO_ERR_INVALID, "cannot write points at infinity to the transcript");
@@ -357,7 +374,7 @@ struct ProofRun {
     const HostDomain& d;
     const int fid;
     const size_t n, m, u, rows;
-    const uint32_t k, ek, bf, A, L, S, I, N, pieces, nco, rot_scale;
+    const uint32_t k, ek, bf, A, L, S, H, I, N, pieces, nco, rot_scale;
     const bool ipa;
     // one gate polynomial: Horner(0, [g], y) = g does not depend on y, so the custom-gate pass of evaluate_h needs the advice (and instance)
     // cosets only -- queued on the side context right behind the last phase's, long before y exists (a circuit with challenges waits for them instead).
@@ -388,7 +405,7 @@ struct ProofRun {
 
     ProofRun(dehalo_prover& pv, dehalo_transcript* t, dehalo_rng* r)
         : p(pv), tr(t), rng_in(r), ctx(pv.ctx), side(pv.side), ms(pv.ctx->stream.get()), ss(pv.side ? pv.side->stream.get() : nullptr), f(pv.f), cs(pv.pk->cs), d(pv.pk->dom),
-          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), I(pv.I), N(pv.N), pieces(pv.pieces), nco(pv.plan.NC - 1),
+          fid(pv.f->id), n(pv.n), m(pv.m), u(pv.u), rows(pv.n - pv.u), k(pv.k), ek(pv.ek), bf(pv.bf), A(pv.A), L(pv.L), S(pv.S), H(pv.H), I(pv.I), N(pv.N), pieces(pv.pieces), nco(pv.plan.NC - 1),
           rot_scale((uint32_t)(pv.m / pv.n)), ipa(pv.ipa), gates_early(pv.side && pv.pk->cs.gates.size() == 1 && pv.NCH == 0), chal(pv.NCH, Fe{{0, 0, 0, 0}}) {}
     ~ProofRun() {      // whatever path the proof took: the witness' copy (asynchronous) has landed before its pin goes, and the helper has finished
         for (auto& pin : pin_advice)
@@ -403,14 +420,14 @@ struct ProofRun {
     }
 
     // ---- random scalars, in upstream's order, circuit after circuit within each step (advice: rows then blinds of circuit 0, rows then blinds of circuit 1, ...;
-    // the products: every circuit's permutation products, then every circuit's lookup products): per advice phase the blinding rows of its columns (column after column), then one blind per column of it; per lookup (bf + 1 rows
+    // the products: every circuit's permutation products, then every circuit's lookup products, then every circuit's shuffle products): per advice phase the blinding rows of its columns (column after column), then one blind per column of it; per lookup (bf + 1 rows
     // permuted input, bf + 1 permuted table, the two columns' blinds), per grand product (bf rows + its blind), the random polynomial (n), its blind,
     // the h pieces' blinds and, under IPA, f's blind.  KZG commitments are not hiding: it draws the blinds and drops them.  No draw depends on the
     // device, so all of them are made here, in that order, and the blinds go up with the blinding rows in one copy.
     int draw_blinds() {
         TRY(rng.init(rng_in, f));
         device_rng = rng.kind == DEHALO_RNG_OS;
-        c_adv = (size_t)N * A * rows; c_advb = (size_t)N * A; c_lk = (size_t)N * L * (2 * rows + 2); c_pr = (size_t)N * (S + L) * (bf + 1);
+        c_adv = (size_t)N * A * rows; c_advb = (size_t)N * A; c_lk = (size_t)N * L * (2 * rows + 2); c_pr = (size_t)N * (S + L + H) * (bf + 1);
         const size_t draws_before = c_adv + c_advb + c_lk + c_pr;
         for (uint32_t ph = 0, off = 0; ph < p.nph; ph++) { adv_off[ph] = off; off += (uint32_t)(p.phase_cols[ph].size() * (rows + 1)); }
         p.blind_host.resize(4 * std::max<size_t>(1, draws_before));
@@ -427,7 +444,7 @@ struct ProofRun {
             for (uint32_t ph = 0; ph < p.nph; ph++)
                 for (size_t j = 0; j < p.phase_cols[ph].size(); j++) bl[p.plan.bi_adv + p.phase_cols[ph][j]] = B[adv_off[ph] + p.phase_cols[ph].size() * rows + j];
             for (uint32_t c = 0; c < 2 * L; c++) bl[p.plan.bi_perm + c] = B[c_adv + c_advb + (size_t)(c / 2) * (2 * rows + 2) + 2 * rows + (c & 1)];
-            for (uint32_t s2 = 0; s2 < S + L; s2++) bl[p.plan.bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
+            for (uint32_t s2 = 0; s2 < S + L + H; s2++) bl[p.plan.bi_prod + s2] = B[c_adv + c_advb + c_lk + (size_t)s2 * (bf + 1) + bf];
             bl[p.plan.bi_rand] = late[0];
             for (uint32_t i = 0; i < pieces; i++) bl[p.plan.bi_h + i] = late[1 + i];
             bl[p.plan.bi_f] = late[1 + pieces];
@@ -485,7 +502,7 @@ struct ProofRun {
 
     // compacted blinding rows [advice | permuted | products] -> one upload
     int upload_blinds() {
-        const size_t total = (size_t)N * ((size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L) * bf);
+        const size_t total = (size_t)N * ((size_t)A * rows + (size_t)2 * L * rows + (size_t)(S + L + H) * bf);
         std::vector<uint64_t>& b = p.blind_host;
         std::vector<uint64_t> packed(4 * std::max<size_t>(1, total));
         size_t o = c_adv;
@@ -498,7 +515,7 @@ struct ProofRun {
             o += 2 * rows;
         }
         const uint64_t* pr = b.data() + 4 * (c_adv + c_advb + c_lk);
-        for (uint32_t s = 0; s < N * (S + L); s++)      // (bf rows, one unused blind) per product, drawn in the order they are written: into its column's place
+        for (uint32_t s = 0; s < N * (S + L + H); s++)      // (bf rows, one unused blind) per product, drawn in the order they are written: into its column's place
             memcpy(packed.data() + 4 * (o + (size_t)p.plan.product_order[s] * bf), pr + 4 * (size_t)s * (bf + 1), 32 * bf);
         if (total) TRY(dh_h2d(ctx, p.blind_dev.p, packed.data(), total * 32, ms));
         if (total || ipa) HIP_TRY(ctx, hipStreamSynchronize(ms));      // `packed` is a local (and the blinds' copy of draw_blinds lands here)
@@ -665,7 +682,7 @@ struct ProofRun {
     }
     int after_lookups_queued() { return side_ntt(p.plan.o_perm, 2 * N * L, p.ev_ready[1].get()); }
 
-    // ---- grand products: permutation sets, then lookups; one batched inversion.  The random polynomial's values are the launch's last column
+    // ---- grand products: permutation sets, then lookups, then shuffles; one batched inversion.  The random polynomial's values are the launch's last column
     // (cols[o_rand] sits right behind the products): its commitment is written with theirs
     int products_and_random() {
         const uint32_t npc = (uint32_t)cs.perm_cols.size();
@@ -680,7 +697,7 @@ struct ProofRun {
             HIP_TRY(ctx, hipMemcpyAsync(p.wbuf.p, rl, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
         }
         TRY(dehalo_ntt_device(ctx, fid, (uint64_t*)rl, k, d.omega.v, 1, nullptr));
-        if (S + L == 0) return p.commit(tr, rl, 1, true, [this] { return restore_random(); }, 0, p.blind_at(p.plan.bi_rand));
+        if (S + L + H == 0) return p.commit(tr, rl, 1, true, [this] { return restore_random(); }, 0, p.blind_at(p.plan.bi_rand));
         std::vector<Fe> pchal(std::max<uint32_t>(npc, 1));
         Fe dj = beta;
         for (uint32_t j = 0; j < npc; j++) {
@@ -693,7 +710,7 @@ struct ProofRun {
         for (uint32_t j = 0; j < npc; j++) psig.push_back(col_ptr(p.pk->perm_values, j, n));
         std::vector<Fe> set_factors(std::max<uint32_t>(S, 1));
         for (uint32_t s2 = 0; s2 < S; s2++) set_factors[s2] = pchal[std::min<uint32_t>(s2 * cs.chunk_len(), npc ? npc - 1 : 0)];      // beta delta^(first column of the set)
-        const uint32_t NP = N * (S + L);
+        const uint32_t PC = S + L + H, NP = N * PC;      // products per circuit, of the proof
         for (uint32_t c = 0; c < N; c++) {
             std::vector<const uint64_t*> pcolv, pA, pS, pa, ps;
             for (auto& pc : cs.perm_cols) pcolv.push_back(pc.kind == DEHALO_COLUMN_ADVICE ? adv_v[c][pc.index] : pc.kind == DEHALO_COLUMN_FIXED ? fixed_v[pc.index] : inst_v[c][pc.index]);
@@ -710,19 +727,42 @@ struct ProofRun {
             pin.set_factors = (const uint64_t*)set_factors.data();
             pin.compressed_input = pA.data(); pin.compressed_table = pS.data(); pin.permuted_input = pa.data(); pin.permuted_table = ps.data();
             pin.num_lookups = L;
-            TRY(dehalo_product_terms_device(ctx, fid, &pin, n, p.num.u64((size_t)c * (S + L) * n), p.den.u64((size_t)c * (S + L) * n), n, nullptr));
+            if (S + L) TRY(dehalo_product_terms_device(ctx, fid, &pin, n, p.num.u64((size_t)c * PC * n), p.den.u64((size_t)c * PC * n), n, nullptr));
+            if (H) {      // a shuffle's numerator and denominator columns are its two programs' values on the original domain: compress(inputs) + gamma, compress(shuffle side) + gamma
+                std::vector<const dehalo_graph*> graphs;
+                std::vector<uint64_t*> outs;
+                for (uint32_t j = 0; j < H; j++) {
+                    graphs.push_back(p.pk->shuffle_graphs[j].first.get());
+                    outs.push_back(p.num.u64((size_t)(c * PC + S + L + j) * n));
+                    graphs.push_back(p.pk->shuffle_graphs[j].second.get());
+                    outs.push_back(p.den.u64((size_t)(c * PC + S + L + j) * n));
+                }
+                EvalIn e;
+                e.cols(fixed_v, adv_v[c], inst_v[c]);
+                e.in.theta = theta.v; e.in.gamma = gamma.v;
+                e.in.challenges = (const uint64_t*)chal.data(); e.in.num_challenges = (uint32_t)chal.size();
+                TRY(dehalo_graph_evaluate_batch_device(ctx, graphs.data(), (uint32_t)graphs.size(), &e.in, k, 1, outs.data(), nullptr));
+            }
         }
         p.tk("product graphs queued");
         TRY(dehalo_grand_product_batch_device(ctx, fid, p.num.u64(), p.den.u64(), n, NP, n, p.cols.u64((size_t)p.plan.o_pz * n), nullptr));
         for (uint32_t c = 0; c < N; c++)
             for (uint32_t s = 1; s < S; s++)      // z_s starts where z_{s-1} ended: z = vec![last_z] (a circuit's first set starts at 1)
                 TRY(dehalo_scale_device(ctx, fid, p.cols.u64((size_t)(p.plan.pz(c) + s) * n), n, nullptr, 0, p.cols.u64((size_t)(p.plan.pz(c) + s - 1) * n + u), nullptr));
+        // a shuffle's product ends at 1 exactly when its two sides are a permutation of each other (but for a negligible probability over gamma): one flag per
+        // shuffle behind the phase's points, read with them
+        if (H) {
+            fe one_std;
+            memcpy(&one_std, f->one.v, 32);
+            k_shuffle_closed<<<(N * H + 63) / 64, 64, 0, ms>>>(p.cols.at((size_t)p.plan.o_sz * n), (uint64_t)PC * n, n, u, H, N * H, one_std,
+                                                               reinterpret_cast<int32_t*>(p.jac.u64() + 12 * (size_t)(NP + 1)));
+        }
         // per column: bf blinding rows (n - bf .. n)
         const fe* bl_prod = p.blind_dev.p + (size_t)N * (A + 2 * L) * rows;
         k_place_rows<<<(unsigned)(((size_t)bf * NP + 255) / 256), 256, 0, ms>>>(p.cols.at((size_t)p.plan.o_pz * n + (n - bf)), n, bl_prod, bf, NP);
         if (side) HIP_TRY(ctx, hipEventRecord(p.ev_ready[2].get(), ms));
-        return p.commit(tr, p.cols.at((size_t)p.plan.o_pz * n), NP + 1, true, [this] { return after_products_queued(); }, 0, p.blind_at(p.plan.bi_prod), true,
-                        N > 1 ? p.plan.product_order.data() : nullptr);
+        return p.commit(tr, p.cols.at((size_t)p.plan.o_pz * n), NP + 1, true, [this] { return after_products_queued(); }, (size_t)N * H, p.blind_at(p.plan.bi_prod), true,
+                        N > 1 ? p.plan.product_order.data() : nullptr, true);
     }
     int restore_random() {      // (queued behind the MSM's kernels on the same stream)
         if (!side) HIP_TRY(ctx, hipMemcpyAsync(p.cols.at((size_t)p.plan.o_rand * n), p.wbuf.p, n * sizeof(fe), hipMemcpyDeviceToDevice, ms));
@@ -731,7 +771,7 @@ struct ProofRun {
     int after_products_queued() {
         TRY(restore_random());
         if (!side) return 0;
-        TRY(side_ntt(p.plan.o_pz, N * (S + L), p.ev_ready[2].get()));
+        TRY(side_ntt(p.plan.o_pz, N * (S + L + H), p.ev_ready[2].get()));
         // the lookups' (compressed input + beta)(compressed table + gamma) over the extended domain need theta, beta, gamma and the advice /
         // fixed cosets: all there -- on the side context, beside the products' commitment, instead of after y
         for (uint32_t c = 0; c < N && L; c++) {
@@ -743,7 +783,22 @@ struct ProofRun {
             e.in.beta = beta.v; e.in.gamma = gamma.v; e.in.theta = theta.v;
             TRY(dehalo_graph_evaluate_batch_device(side, graphs.data(), L, &e.in, ek, rot_scale, outs.data(), nullptr));
         }
+        for (uint32_t c = 0; c < N && H; c++) TRY(shuffle_values(side, c));      // likewise the shuffles' two sides
         return 0;
+    }
+    // circuit c's shuffles over the extended domain: compress(inputs) + gamma and compress(shuffle side) + gamma, one call for all of them
+    int shuffle_values(dehalo_ctx* on, uint32_t c) {
+        std::vector<const dehalo_graph*> graphs;
+        std::vector<uint64_t*> outs;
+        for (uint32_t j = 0; j < H; j++) {
+            graphs.push_back(p.pk->shuffle_graphs[j].first.get());
+            outs.push_back(p.shuffle_value.u64((size_t)(2 * (c * H + j)) * m));
+            graphs.push_back(p.pk->shuffle_graphs[j].second.get());
+            outs.push_back(p.shuffle_value.u64((size_t)(2 * (c * H + j) + 1) * m));
+        }
+        EvalIn e = coset_inputs(c);
+        e.in.gamma = gamma.v; e.in.theta = theta.v;
+        return dehalo_graph_evaluate_batch_device(on, graphs.data(), (uint32_t)graphs.size(), &e.in, ek, rot_scale, outs.data(), nullptr);
     }
 
     // ---- coefficient forms and cosets of everything committed so far; evaluate_h, / t(X), extended_to_coeff; the pieces' commitments
@@ -801,6 +856,21 @@ struct ProofRun {
                     li.push_back(q);
                 }
                 TRY(dehalo_lookup_h_batch_device(ctx, fid, li.data(), (uint32_t)li.size(), ek, rot_scale, p.h.u64(), nullptr));
+            }
+            if (H && !side) TRY(shuffle_values(ctx, c));
+            for (uint32_t first = 0; first < H; first += 8) {      // (the batched pass takes eight at a time)
+                std::vector<dehalo_shuffle_inputs> si;
+                for (uint32_t j = first; j < std::min(H, first + 8); j++) {
+                    dehalo_shuffle_inputs q{};
+                    q.product_coset = col_ptr(p.ext, p.plan.sz(c) + j, m);
+                    q.input_value = p.shuffle_value.u64((size_t)(2 * (c * H + j)) * m);
+                    q.shuffle_value = p.shuffle_value.u64((size_t)(2 * (c * H + j) + 1) * m);
+                    q.l0 = l0; q.l_last = l_last; q.l_active_row = l_active;
+                    q.y = y.v;
+                    q.form_flags = FF;
+                    si.push_back(q);
+                }
+                TRY(dehalo_shuffle_h_batch_device(ctx, fid, si.data(), (uint32_t)si.size(), ek, rot_scale, p.h.u64(), nullptr));
             }
         }
         TRY(dehalo_scale_device(ctx, fid, p.h.u64(), m, (const uint64_t*)d.t_inv.data(), (uint32_t)d.t_inv.size(), nullptr, nullptr));      // divide_by_vanishing_poly

@@ -100,6 +100,7 @@ struct dehalo_pk {
     GraphPtr custom_gates;
     std::vector<GraphPtr> lookup_graphs;
     std::vector<std::pair<GraphPtr, GraphPtr>> compress_graphs;
+    std::vector<std::pair<GraphPtr, GraphPtr>> shuffle_graphs;      // per shuffle: compress(inputs) + gamma, compress(shuffle side) + gamma
     GraphPtr check_gates;      // every gate polynomial as a root of its own (dehalo_check_witness)
 
     size_t vk_size() const;

@@ -118,3 +118,13 @@ def lookup_h_batch_device(ctx: Context, field: FieldSpec, lookups, l0: int, l_la
     pointers per lookup argument, in order; each lookup's five terms are folded into d_values as lookup_h_device folds them."""
     e = field.encode
     ctx.lookup_h_batch_device(field.id, list(lookups), l0, l_last, l_active_row, e(beta), e(gamma), e(y), log_rows, rot_scale, d_values, stream, form_flags)
+
+
+def shuffle_h_batch_device(ctx: Context, field: FieldSpec, shuffles, l0: int, l_last: int, l_active_row: int, y: int, log_rows: int, rot_scale: int, d_values: int,
+                           stream: int = 0, form_flags: int = 0):
+    """The shuffle arguments' terms of evaluate_h: `shuffles` = (product, input_value, shuffle_value) device pointers per shuffle, in order; each shuffle's three
+    terms -- l0 (1 - z), l_last (z^2 - z), l_active (z(wX) shuffle_value - z(X) input_value) -- are folded into d_values.  One pass over the rows per eight
+    shuffles (a launch takes at most eight: more are split here, as the prover splits them)."""
+    shuffles = list(shuffles)
+    for first in range(0, len(shuffles), 8):
+        ctx.shuffle_h_batch_device(field.id, shuffles[first:first + 8], l0, l_last, l_active_row, field.encode(y), log_rows, rot_scale, d_values, stream, form_flags)

@@ -231,6 +231,11 @@ class ConstraintSystem {
         lens_.push_back((uint32_t)pairs.size());
         for (auto& pr : pairs) { lin_.push_back(pr.first); ltab_.push_back(pr.second); }
     }
+    // ConstraintSystem::shuffle: the rows' input tuples are a permutation of the rows' shuffle tuples; at least one (input, shuffle) pair
+    void shuffle(const std::vector<std::pair<Expr, Expr>>& pairs) {
+        slens_.push_back((uint32_t)pairs.size());
+        for (auto& pr : pairs) { sin_.push_back(pr.first); stab_.push_back(pr.second); }
+    }
     void set_minimum_degree(uint32_t d) { d_.minimum_degree = d; }
     const dehalo_constraint_system* descriptor() {
         d_.nodes = nodes_.data(); d_.num_nodes = (uint32_t)nodes_.size();
@@ -243,6 +248,8 @@ class ConstraintSystem {
         d_.instance_queries = iq_.data(); d_.num_instance_queries = (uint32_t)iq_.size();
         d_.advice_phases = aph_.empty() ? nullptr : aph_.data();
         d_.challenge_phases = cph_.empty() ? nullptr : cph_.data(); d_.num_challenges = (uint32_t)cph_.size();
+        d_.shuffle_lens = slens_.empty() ? nullptr : slens_.data(); d_.shuffle_inputs = slens_.empty() ? nullptr : sin_.data();
+        d_.shuffle_tables = slens_.empty() ? nullptr : stab_.data(); d_.num_shuffles = (uint32_t)slens_.size();
         return &d_;
     }
 
@@ -260,7 +267,7 @@ class ConstraintSystem {
     dehalo_constraint_system d_{};
     std::vector<dehalo_expr_node> nodes_;
     std::vector<Fe> consts_;
-    std::vector<uint32_t> gates_, lens_, lin_, ltab_;
+    std::vector<uint32_t> gates_, lens_, lin_, ltab_, slens_, sin_, stab_;
     std::vector<dehalo_column_query> perm_, aq_, fq_, iq_;
     std::vector<uint8_t> aph_, cph_;
 };

@@ -20,7 +20,7 @@ RNG_OS, RNG_PCG64, RNG_CALLBACK = 0, 1, 2
 KEYGEN_FIXED_CANONICAL = 1
 PROOF_ADVICE_ON_DEVICE, PROOF_ADVICE_CANONICAL = 1, 2
 CIRCUIT_DELAY_ENC, CIRCUIT_MOD_POW, CIRCUIT_POSE_ENC = 0, 1, 2
-CHECK_GATE, CHECK_LOOKUP, CHECK_COPY = 0, 1, 2
+CHECK_GATE, CHECK_LOOKUP, CHECK_COPY, CHECK_SHUFFLE = 0, 1, 2, 3
 PHASES = ("advice", "lookups", "products", "random", "quotient", "evaluations", "openings", "total")
 
 
@@ -69,6 +69,13 @@ class ConstraintSystemDescriptor:
             lens.append(len(inputs))
             lin += [emit(e) for e in inputs]
             ltab += [emit(e) for e in tables]
+        slens, sin, stab = [], [], []
+        for inputs, sides in cs.shuffles:
+            if len(inputs) != len(sides):
+                raise ValueError("shuffle: input and shuffle expression counts differ")
+            slens.append(len(inputs))
+            sin += [emit(e) for e in inputs]
+            stab += [emit(e) for e in sides]
         self._nodes = (CExprNode * max(1, len(nodes)))(*[CExprNode(*nd) for nd in nodes])
         self._consts = field.encode_many(consts) if consts else np.zeros((1, 4), dtype=np.uint64)
         u32 = lambda xs: (C.c_uint32 * max(1, len(xs)))(*xs)
@@ -91,6 +98,10 @@ class ConstraintSystemDescriptor:
         self._cph = np.asarray(cs.challenge_phases, dtype=np.uint8) if cs.challenge_phases else None
         d.advice_phases = self._aph.ctypes.data if self._aph is not None else None
         d.challenge_phases, d.num_challenges = self._cph.ctypes.data if self._cph is not None else None, len(cs.challenge_phases)
+        # shuffle arguments: NULL / 0 for a circuit without one -- the descriptor of before
+        if slens:
+            self._slens, self._sin, self._stab = u32(slens), u32(sin), u32(stab)
+            d.shuffle_lens, d.shuffle_inputs, d.shuffle_tables, d.num_shuffles = self._slens, self._sin, self._stab, len(slens)
         self.struct = d
 
     def ref(self):
@@ -220,18 +231,19 @@ class ParamsIPA(ParamsKZG):
 
 class CheckReport:
     """dehalo_check_report and the stored failures of one ProvingKey.check_witness: `failures` = tuples (kind, index, row) in (kind, index, row) order -- kind
-    CHECK_GATE: index into cs.gates' polynomials; CHECK_LOOKUP: index into cs.lookups; CHECK_COPY: index into cs.permutation_columns -- at most `cap` of them;
-    the six counters are exact whatever `cap` was."""
+    CHECK_GATE: index into cs.gates' polynomials; CHECK_LOOKUP: index into cs.lookups; CHECK_COPY: index into cs.permutation_columns; CHECK_SHUFFLE:
+    index into cs.shuffles -- at most `cap` of them; the counters are exact whatever `cap` was."""
 
     def __init__(self, rep: CCheckReport, failures):
         self.failures = failures
         self.gate_failures, self.lookup_failures, self.copy_failures = int(rep.gate_failures), int(rep.lookup_failures), int(rep.copy_failures)
         self.rows, self.lookup_inputs, self.cells_in_cycles = int(rep.rows), int(rep.lookup_inputs), int(rep.cells_in_cycles)
         self.written = int(rep.written)
+        self.shuffle_failures, self.shuffle_inputs = int(rep.shuffle_failures), int(rep.shuffle_inputs)
 
     @property
     def ok(self) -> bool:
-        return self.gate_failures == 0 and self.lookup_failures == 0 and self.copy_failures == 0
+        return self.gate_failures == 0 and self.lookup_failures == 0 and self.copy_failures == 0 and self.shuffle_failures == 0
 
     def __repr__(self):
         return "CheckReport(ok=%s, gate_failures=%d, lookup_failures=%d, copy_failures=%d, rows=%d, lookup_inputs=%d, cells_in_cycles=%d, failures=%r)" % (

@@ -71,6 +71,9 @@ class ConstraintSystem:
     # the phase after whose commitments it is squeezed.  Not part of description(): a verifier reads them beside it
     advice_phases: List[int] = dc_field(default_factory=list)
     challenge_phases: List[int] = dc_field(default_factory=list)
+    # the shuffle arguments (cs.shuffle, halo2_proofs v0.3.0): (input_expressions, shuffle_expressions), at least one pair each.  Not part of description()
+    # either, so that a circuit without one keeps its description: a verifier reads them beside it
+    shuffles: List[Tuple[List[Expr], List[Expr]]] = dc_field(default_factory=list)
 
     # ---- building (ConstraintSystem::{query_*_index, enable_equality, create_gate, lookup}) ----
     def _query(self, kind: str, index: int, rot: int) -> Expr:
@@ -98,6 +101,12 @@ class ConstraintSystem:
 
     def lookup(self, pairs: Sequence[Tuple[Expr, Expr]]):
         self.lookups.append(([p[0] for p in pairs], [p[1] for p in pairs]))
+
+    def shuffle(self, pairs: Sequence[Tuple[Expr, Expr]]):
+        """ConstraintSystem::shuffle: the rows' input tuples are a permutation of the rows' shuffle tuples (over the usable rows)."""
+        if not pairs:
+            raise ValueError("a shuffle needs at least one (input, shuffle) pair")
+        self.shuffles.append(([p[0] for p in pairs], [p[1] for p in pairs]))
 
     def advice_column_in(self, phase: int) -> int:
         """ConstraintSystem::advice_column_in: a new advice column of `phase`; returns its index."""
@@ -138,8 +147,10 @@ class ConstraintSystem:
         return max(3, factors) + 2
 
     def degree(self) -> int:
-        """ConstraintSystem::degree: the permutation argument needs 3, a lookup max(4, 2 + input + table), gates their own."""
+        """ConstraintSystem::degree: the permutation argument needs 3, a lookup max(4, 2 + input + table), a shuffle max(2 + input, 2 + shuffle), gates their own."""
         d = 3                                                 # permutation::Argument::required_degree() == 3, unconditionally
+        for inputs, sides in self.shuffles:
+            d = max(d, 2 + max([1] + [degree(e) for e in inputs]), 2 + max([1] + [degree(e) for e in sides]))
         for inputs, tables in self.lookups:
             di = max([1] + [degree(e) for e in inputs])
             dt = max([1] + [degree(e) for e in tables])

@@ -83,9 +83,9 @@ class SeededRng:
 def proof_layout(cs: plonk.ConstraintSystem) -> Tuple[int, int]:
     """(commitments written before the evaluations, evaluations) of a proof of this constraint system; the opening quotients
     (one per distinct opening point) follow the evaluations."""
-    L, S = len(cs.lookups), cs.num_permutation_sets()
-    head = cs.num_advice + 2 * L + S + L + 1 + (cs.degree() - 1)
-    evals = len(cs.advice_queries) + len(cs.fixed_queries) + 1 + len(cs.permutation_columns) + max(0, 3 * S - 1) + 5 * L
+    L, S, H = len(cs.lookups), cs.num_permutation_sets(), len(cs.shuffles)
+    head = cs.num_advice + 2 * L + S + L + H + 1 + (cs.degree() - 1)
+    evals = len(cs.advice_queries) + len(cs.fixed_queries) + 1 + len(cs.permutation_columns) + max(0, 3 * S - 1) + 5 * L + 2 * H
     return head, evals
 
 

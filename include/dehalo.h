@@ -46,7 +46,8 @@ typedef enum {
     DEHALO_ERR_OOM = -3,        /* device allocation failed */
     DEHALO_ERR_HIP = -4,        /* any other HIP runtime error (see dehalo_last_error) */
     DEHALO_ERR_UNSUPPORTED = -5, /* e.g. NTT over a field whose two-adicity is too small */
-    DEHALO_ERR_NOT_IN_TABLE = -6 /* permute_expression_pair: upstream's Error::ConstraintSystemFailure */
+    DEHALO_ERR_NOT_IN_TABLE = -6, /* permute_expression_pair: upstream's Error::ConstraintSystemFailure */
+    DEHALO_ERR_SHUFFLE = -7       /* create_proof: a shuffle argument's two sides are not a permutation of each other (its product does not end at 1) */
 } dehalo_status;
 
 /* halo2curves curve / field identities */
@@ -445,6 +446,22 @@ int dehalo_lookup_h_device(dehalo_ctx* ctx, int field, const dehalo_lookup_input
 int dehalo_lookup_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_lookup_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale,
                                  uint64_t* d_values, void* stream);
 
+/* The shuffle argument's terms for `count` <= 8 shuffles (in[0], in[1], ... in the constraint system's order) in ONE pass over the rows, folded into d_values
+ * in place (value = value * y + term):
+ *   l0 (1 - z); l_last (z^2 - z); l_active (z(wX) shuffle_value - z(X) input_value),
+ * input_value = compressed input + gamma and shuffle_value = compressed shuffle side + gamma: the outputs of the shuffle's two GraphEvaluator programs for the
+ * row.  d_values and the three Lagrange columns are read once; each shuffle reads z[row], z[row + rot_scale] and its two value columns.  The shuffles of one
+ * call share l0 / l_last / l_active_row, y and form_flags (checked).  form_flags: product_coset and the Lagrange columns are columns, input_value /
+ * shuffle_value and d_values are values. */
+typedef struct {
+    const uint64_t *product_coset, *input_value, *shuffle_value;   /* device */
+    const uint64_t *l0, *l_last, *l_active_row;                    /* device */
+    const uint64_t* y;                                             /* host */
+    uint32_t form_flags;                                           /* 0, or DEHALO_EVAL_* */
+} dehalo_shuffle_inputs;
+int dehalo_shuffle_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_shuffle_inputs* in, uint32_t count, uint32_t log_rows, uint32_t rot_scale,
+                                  uint64_t* d_values, void* stream);
+
 /* ==== the whole call: halo2_proofs::plonk::{keygen_vk, keygen_pk, create_proof} over KZG / GWC =====================================
  * The reference's timed call is
  *     create_proof::<KZGCommitmentScheme<Bn256>, ProverGWC<_>, Challenge255<_>, _, Blake2bWrite<_, _, _>, _>(&params, &pk, &[circuit],
@@ -517,7 +534,13 @@ int dehalo_params_commit_device(dehalo_ctx* ctx, const dehalo_params* params, co
  *   advice_phases     num_advice entries, the phase 0 / 1 / 2 of every advice column; NULL = all 0.  The phases in use are 0 ..= the largest, each with at least
  *                     one column (DEHALO_ERR_INVALID otherwise); more than three phases: DEHALO_ERR_UNSUPPORTED
  *   challenge_phases  num_challenges entries: challenge j is squeezed after the advice commitments of phase challenge_phases[j] (a phase in use)
- * A circuit with one phase and no challenge is described, encoded (the substitute transcript_repr) and proved exactly as before these fields existed.       */
+ * A circuit with one phase and no challenge is described, encoded (the substitute transcript_repr) and proved exactly as before these fields existed.
+ * The shuffle argument [cs.shuffle(name, |meta| vec![(input_i, shuffle_i)]); halo2_proofs v0.3.0 plonk/shuffle]: the rows' input tuples are a permutation of
+ * the rows' shuffle tuples over the usable rows.  Both sides are compressed with theta as a lookup's are (the first expression carries the highest power);
+ * the argument is one grand product z with z[0] = 1, z[i + 1] = z[i] (A[i] + gamma) / (S[i] + gamma), committed behind the lookups' products, three
+ * quotient terms -- l0 (1 - z), l_last (z^2 - z), l_active (z(wX)(S + gamma) - z(X)(A + gamma)) -- behind the lookups' terms, and z(x), z(wx) behind every
+ * circuit's lookup evaluations.  It requires degree max(2 + deg input, 2 + deg shuffle), either at least 1.  A constraint system with num_shuffles = 0 is
+ * described, encoded and proved exactly as before these fields existed.       */
 typedef enum {
     DEHALO_EXPR_CONSTANT = 0, DEHALO_EXPR_FIXED = 1, DEHALO_EXPR_ADVICE = 2, DEHALO_EXPR_INSTANCE = 3, DEHALO_EXPR_NEGATED = 4, DEHALO_EXPR_SUM = 5,
     DEHALO_EXPR_PRODUCT = 6, DEHALO_EXPR_SCALED = 7, DEHALO_EXPR_CHALLENGE = 8
@@ -538,6 +561,9 @@ typedef struct {
     const dehalo_column_query* instance_queries; uint32_t num_instance_queries;
     const uint8_t* advice_phases;                                   /* num_advice entries; NULL = every column in phase 0 */
     const uint8_t* challenge_phases; uint32_t num_challenges;       /* the phase after which each challenge is squeezed */
+    const uint32_t* shuffle_lens;                                   /* shuffle j has shuffle_lens[j] >= 1 (input, shuffle) expression pairs ...    */
+    const uint32_t* shuffle_inputs; const uint32_t* shuffle_tables; /* ... their root nodes, shuffles concatenated; NULL / 0: no shuffle argument  */
+    uint32_t num_shuffles;
 } dehalo_constraint_system;
 
 /* keygen_vk + keygen_pk [UPSTREAM halo2_proofs/src/plonk/keygen.rs; benches/delay_enc.rs:86,103] on the device: commit_lagrange,
@@ -561,7 +587,8 @@ int dehalo_vk_write(const dehalo_pk* pk, uint8_t* out, size_t cap);
  * substitute: Blake2b-512("Halo2-Verify-Key") over the key's RawBytes and a binary encoding of the constraint system. */
 int dehalo_pk_set_transcript_repr(dehalo_pk* pk, const uint64_t repr[4]);
 int dehalo_pk_get_transcript_repr(const dehalo_pk* pk, uint64_t repr[4]);
-/* out[0..7] = k, extended_k, blinding_factors, degree, permutation sets, commitments before the evaluations, evaluations, opening points */
+/* out[0..7] = k, extended_k, blinding_factors, degree, permutation sets, commitments before the evaluations (advice + 3 lookups + sets + shuffles + 1 +
+ * (degree - 1)), evaluations (advice queries + fixed queries + 1 + permutation columns + 3 sets - 1 + 5 lookups + 2 shuffles), opening points */
 int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]);
 /* out[0] = advice phases in use (1 .. 3), out[1] = challenges of the key's constraint system */
 int dehalo_pk_phases(const dehalo_pk* pk, uint32_t out[2]);
@@ -628,9 +655,10 @@ int dehalo_prover_release(dehalo_prover* prover);
 typedef enum { DEHALO_MULTIOPEN_GWC = 0, DEHALO_MULTIOPEN_SHPLONK = 1 } dehalo_multiopen;
 int dehalo_prover_set_multiopen(dehalo_prover* prover, int multiopen);
 /* Byte length of one proof of this prover (its params' scheme, instance commitments and evaluations included); 0 for null.
- *   KZG / GWC: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + opening points) + 32 x evaluations
+ *   KZG / GWC: 32 x (advice + 3 lookups + permutation sets + shuffles + 1 + (degree - 1) + opening points) + 32 x evaluations
  *   KZG / SHPLONK: the same with 2 in the place of the opening points
- *   IPA: 32 x (advice + 3 lookups + permutation sets + 1 + (degree - 1) + 1 (f) + 1 (S) + 2 k) + 32 x (instance queries + evaluations + point sets + 2) */
+ *   IPA: 32 x (advice + 3 lookups + permutation sets + shuffles + 1 + (degree - 1) + 1 (f) + 1 (S) + 2 k) + 32 x (instance queries + evaluations + point sets + 2)
+ * A shuffle adds one commitment and two evaluations (its product at x and at omega x). */
 size_t dehalo_prover_proof_size(const dehalo_prover* prover);
 /* create_proof: one circuit (of a prover made for one: DEHALO_ERR_INVALID on a prover of dehalo_prover_create_multi with num_circuits > 1), its instance columns,
  * the caller's rng and transcript.
@@ -638,7 +666,9 @@ size_t dehalo_prover_proof_size(const dehalo_prover* prover);
  *              DEHALO_PROOF_ADVICE_ON_DEVICE
  *   instances  num_instance_columns arrays of instance_lens[i] scalars (Montgomery); the reference passes none (&[&[&[]]])
  * Errors follow upstream's: DEHALO_ERR_INVALID for instances.len() != num_instance_columns / an instance column longer than the usable
- * rows / a commitment at infinity; DEHALO_ERR_NOT_IN_TABLE when a lookup input is missing from its table.
+ * rows / a commitment at infinity; DEHALO_ERR_NOT_IN_TABLE when a lookup input is missing from its table; DEHALO_ERR_SHUFFLE when the two sides of a shuffle
+ * argument are not a permutation of each other over the usable rows (its product does not come back to 1; upstream only debug-asserts this).  The flag is read
+ * with the products' commitments, at the wait the proof makes there anyway; the prover is usable for the next proof.
  * Under ParamsIPA (create_proof::<IPACommitmentScheme<_>, ProverIPA<_>, ..>) every commitment carries its blind ([blind] W from the table of W, dehalo_fixed_base_blind_device: one
  * launch per phase), the instance columns are committed with Blind::default() and absorbed as points, their evaluations are written first, and the proof ends
  * with ProverIPA's multiopen (x_1, x_2, f, x_3, the q evaluations, x_4) and the opening argument of dehalo_ipa_open on the same transcript and generator. */
@@ -649,16 +679,16 @@ int dehalo_create_proof(dehalo_prover* prover, const uint64_t* advice, const uin
  *   advice      N pointers, each a buffer of dehalo_create_proof's layout (all on the host, or all on the device with DEHALO_PROOF_ADVICE_ON_DEVICE)
  *   instances   N x num_instance_columns arrays, circuit-major (circuit c's column i is entry c * num_instance_columns + i); instance_lens likewise
  * Order of the transcript: the key's representation; every circuit's instance values (circuit after circuit, column after column); every circuit's advice
- * commitments; theta; every circuit's permuted lookup pairs; beta, gamma; every circuit's permutation products, THEN every circuit's lookup products, then the
- * random polynomial; y; the pieces of the one quotient, whose numerator is one running value v = v y + term over circuit 0's gates, permutation and lookup terms,
+ * commitments; theta; every circuit's permuted lookup pairs; beta, gamma; every circuit's permutation products, THEN every circuit's lookup products, THEN every
+ * circuit's shuffle products, then the random polynomial; y; the pieces of the one quotient, whose numerator is one running value v = v y + term over circuit 0's gates, permutation, lookup and shuffle terms,
  * circuit 1's, ...; x; the evaluations -- every circuit's advice queries | fixed | random | sigma | every circuit's permutation products | every circuit's
- * lookups -- and the multiopen over the queries of circuit 0, circuit 1, ..., then once fixed, sigma, h, random.  The generator's draws are circuit-major the
+ * lookups | every circuit's shuffles -- and the multiopen over the queries of circuit 0, circuit 1, ..., then once fixed, sigma, h, random.  The generator's draws are circuit-major the
  * same way: the blinding rows of circuit c's advice columns, then its columns' blinds, then circuit c + 1's.  A PCG64 generator is advanced past all of them.
- * Proof bytes (GWC; SHPLONK: 2 for `points`): 32 x (N (advice + 3 lookups + sets) + 1 + (degree - 1) + points)
- *                                             + 32 x (N (advice queries + (3 sets - 1 if sets) + 5 lookups) + fixed queries + 1 + permutation columns).
+ * Proof bytes (GWC; SHPLONK: 2 for `points`): 32 x (N (advice + 3 lookups + sets + shuffles) + 1 + (degree - 1) + points)
+ *                                             + 32 x (N (advice queries + (3 sets - 1 if sets) + 5 lookups + 2 shuffles) + fixed queries + 1 + permutation columns).
  * With N = 1 the proof is dehalo_create_proof's, byte for byte.  Each commitment phase is one MSM launch over all circuits' columns.
- * Errors: dehalo_create_proof's for every circuit (DEHALO_ERR_NOT_IN_TABLE when any circuit's lookup input is missing from its table; the prover stays
- * usable); DEHALO_ERR_INVALID for num_circuits = 0 or other than the prover's.  A prover with num_circuits > 1 proves through this call only:
+ * Errors: dehalo_create_proof's for every circuit (DEHALO_ERR_NOT_IN_TABLE when any circuit's lookup input is missing from its table, DEHALO_ERR_SHUFFLE when
+ * any circuit's shuffle does not close; the prover stays usable); DEHALO_ERR_INVALID for num_circuits = 0 or other than the prover's.  A prover with num_circuits > 1 proves through this call only:
  * dehalo_create_proofs, dehalo_create_proof_circuit, dehalo_create_proofs_circuit, dehalo_create_proof_phased and dehalo_prover_set_shard (world > 1)
  * return DEHALO_ERR_UNSUPPORTED on it. */
 int dehalo_create_proof_multi(dehalo_prover* prover, const uint64_t* const* advice, const uint64_t* const* instances, const size_t* instance_lens,
@@ -695,19 +725,26 @@ int dehalo_create_proof_phased(dehalo_prover* prover, dehalo_advice_fn fn, void*
  *           a transcript challenge is): the report of a key and a witness is reproducible, and two different tuples collide with probability ~ tuple length / p.
  *           A debugging aid, not a verifier.
  *   COPY    every cell c of a permutation column, all 2^k rows, with m = mapping[c] != c: value(c) == value(m).  Each end of a broken constraint is its own failure.
+ *   SHUFFLE the input tuples of the usable rows must be a permutation of the shuffle tuples of the usable rows.  Both sides are compressed with the LOOKUP check's
+ *           theta and sorted; a usable row fails when its input value occurs another number of times among the inputs than on the shuffle side.  Both lists hold
+ *           as many values, so no row fails exactly when the two multisets are equal; a value of the shuffle side that no input has shows through the input rows
+ *           whose values it displaces.
  * The failures come ordered by (kind, index, row) ascending; the first `cap` are stored; the totals are exact however small `cap` is.  Returns 0 whenever the check
- * ran: the witness satisfies the circuit when the three totals are 0.  `failures` may be NULL when cap is 0.  DEHALO_ERR_INVALID: null ctx / pk / report, a key of
+ * ran: the witness satisfies the circuit when the four totals are 0.  `failures` may be NULL when cap is 0.  DEHALO_ERR_INVALID: null ctx / pk / report, a key of
  * another device.  Allocates from the context's workspace only; everything is queued on the context's stream, which the call waits for once, before it returns.
  * Upstream's failure NAMING (gate names, region offsets, cell values) is the front-end's: it maps (kind, index, row) back through its own ConstraintSystem. */
-typedef enum { DEHALO_CHECK_GATE = 0, DEHALO_CHECK_LOOKUP = 1, DEHALO_CHECK_COPY = 2 } dehalo_check_kind;
+typedef enum { DEHALO_CHECK_GATE = 0, DEHALO_CHECK_LOOKUP = 1, DEHALO_CHECK_COPY = 2, DEHALO_CHECK_SHUFFLE = 3 } dehalo_check_kind;
 typedef struct { uint32_t kind, index, row, reserved; } dehalo_check_failure;
 /*  GATE:   index = position in cs.gates (gates.flat_map(polynomials) order), row = the row whose polynomial is non-zero
     LOOKUP: index = lookup, row = the row whose input tuple is no row of the table
-    COPY:   index = position j in cs.permutation_columns, row = i: cell (j, i) differs from the cell the mapping sends it to */
+    COPY:   index = position j in cs.permutation_columns, row = i: cell (j, i) differs from the cell the mapping sends it to
+    SHUFFLE: index = shuffle, row = the row whose input tuple occurs another number of times among the inputs than on the shuffle side */
+/* (The struct GREW by its last two members when the shuffle argument came: a caller built against the older header passes a shorter struct and must be rebuilt.) */
 typedef struct {
     uint64_t gate_failures, lookup_failures, copy_failures;   /* totals, however small `cap` is */
     uint64_t rows, lookup_inputs, cells_in_cycles;            /* what was checked: usable rows; usable rows x lookups; cells with mapping[c] != c */
     uint64_t written;                                         /* entries stored in `failures` = min(cap, total) */
+    uint64_t shuffle_failures, shuffle_inputs;                /* total; usable rows x shuffles */
 } dehalo_check_report;
 int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                          const uint64_t* permutation_mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap, dehalo_check_report* report);

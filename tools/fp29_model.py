@@ -257,6 +257,25 @@ class F29:
                 assert d % p == (x - y) % p and d < 2 * p
                 assert m < 2 * p
                 assert value(self.mont2(a, b, b, a)) < 2 * p
+        # k_shuffle_h_batch: v = v y + l0 (1 - z); v = v y + l_last (z^2 - z); v = v y + l_active (z(wX) sv - z iv) -- every operand a stored value <= 2p, every
+        # result the next term's v: z, z(wX) over the representatives of zero and their neighbours, the two side values over all pairs of them
+        one = limbs((1 << RBITS) % p)
+        inv = pow(1 << RBITS, -1, p)
+        for z_ in edge:
+            for zn_ in edge:
+                for iv_ in edge:
+                    for sv_ in (edge[(edge.index(iv_) + 3) % len(edge)], iv_):
+                        v_, y_, l_ = (vals[(z_ + zn_ + iv_ + sv_ + i) % len(vals)] for i in range(3))
+                        z, zn, iv, sv, v, y, l = (limbs(t) for t in (z_, zn_, iv_, sv_, v_, y_, l_))
+                        t1, t2 = self.evh_sub(one, z), self.evh_sub(self.sqr(z), z)
+                        lhs, rhs = self.mont(zn, sv), self.mont(z, iv)
+                        t3 = self.evh_sub(lhs, rhs)
+                        assert max(value(t) for t in (t1, t2, lhs, rhs, t3)) < 2 * p
+                        assert value(t3) % p == (zn_ * sv_ - z_ * iv_) * inv % p and value(t2) % p == (z_ * z_ * inv - z_) % p
+                        for t in (t1, t2, t3):
+                            v = self.mont2(v, y, t, l)
+                            assert value(v) < 2 * p
+                        assert value(self.canon(v)) < p
 
     # ---- codecs ----
     def enc(self, x):       # integer -> internal Montgomery limbs (canonical)
