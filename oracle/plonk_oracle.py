@@ -7,13 +7,15 @@ poly/kzg/multiopen/gwc/prover.rs, transcript.rs] -- the code behind the referenc
 benches/delay_enc.rs:86,103 (keygen) and :123-131 (create_proof) -- written from the published algorithm (the crate is
 not in the container): **parity unpinned** against upstream itself; what pins it is oracle/verifier.py accepting the
 proofs (the reference's own end-to-end check, `assert!(accept)`, benches/delay_enc.rs:147-165).
-One create_proof body proves under both commitment schemes; what differs between them is a scheme object's (ProverGWC here, ipa.ProverIPA).
+One create_proof body (`create_proof_multi`) proves under every commitment scheme, over one or several circuits of a key, with or without later advice
+phases, challenges and shuffle arguments; what differs between the schemes is a scheme object's (ProverGWC here, ipa.ProverIPA, tests/shplonk_oracle.py's).
 
 The heavy steps go through oracle.c (best_multiexp, best_fft, evaluate_h's row loops, permute_expression_pair, batch
 inversion) with upstream's serial / chunk-per-thread structure; everything else is Python integers.
 The circuit arrives as plain data: `desc` = (num_advice, num_fixed, num_instance, gates, lookups, permutation_columns,
 advice_queries, fixed_queries, instance_queries, minimum_degree) with expressions as nested tuples
-("const", c) ("fixed" | "advice" | "instance", index, rotation) ("neg", e) ("sum", a, b) ("product", a, b) ("scaled", e, c).
+("const", c) ("fixed" | "advice" | "instance", index, rotation) ("challenge", index) ("neg", e) ("sum", a, b) ("product", a, b) ("scaled", e, c).
+What a constraint system has beside that tuple -- shuffle arguments, the advice columns' phases, the challenges' phases -- travels on it: `Desc`.
 """
 from __future__ import annotations
 
@@ -51,11 +53,28 @@ class Fld:
 
 def expr_degree(e) -> int:
     k = e[0]
-    if k == "const": return 0
+    if k in ("const", "challenge"): return 0
     if k in ("fixed", "advice", "instance"): return 1
     if k in ("neg", "scaled"): return expr_degree(e[1])
     if k == "sum": return max(expr_degree(e[1]), expr_degree(e[2]))
     return expr_degree(e[1]) + expr_degree(e[2])
+
+
+class Desc(tuple):
+    """The description tuple + the shuffles [(inputs, shuffle side)], the phase of every advice column and the phase after which each challenge is squeezed.
+    A plain 10-tuple is a description with none of them."""
+    shuffles, phases, challenge_phases = (), (), ()
+
+    def __new__(cls, desc, shuffles=(), phases=(), challenge_phases=()):
+        self = super().__new__(cls, tuple(desc))
+        self.shuffles = tuple((tuple(i), tuple(s)) for i, s in shuffles)
+        self.phases, self.challenge_phases = tuple(phases) or (0,) * self[0], tuple(challenge_phases)
+        return self
+
+
+def describe(cs) -> Desc:
+    """the Desc of a constraint system object (description(), shuffles, phases(), challenge_phases)"""
+    return Desc(cs.description(), cs.shuffles, cs.phases(), cs.challenge_phases)
 
 
 class Shape:
@@ -64,6 +83,9 @@ class Shape:
     def __init__(self, desc, k: int, field: po.Field):
         (self.num_advice, self.num_fixed, self.num_instance, self.gates, self.lookups, self.perm_columns, self.advice_queries, self.fixed_queries,
          self.instance_queries, self.minimum_degree) = desc
+        self.shuffles, self.challenge_phases = getattr(desc, "shuffles", ()), getattr(desc, "challenge_phases", ())
+        self.phases = getattr(desc, "phases", ()) or (0,) * self.num_advice
+        self.num_phases = max(self.phases + (0,)) + 1
         cnt = [0] * self.num_advice
         for c, _ in self.advice_queries:
             cnt[c] += 1
@@ -71,6 +93,8 @@ class Shape:
         d = 3                                                  # permutation::Argument::required_degree() is 3 whether or not a column is enabled
         for ins, tabs in self.lookups:
             d = max(d, max(4, 2 + max([1] + [expr_degree(e) for e in ins]) + max([1] + [expr_degree(e) for e in tabs])))
+        for ins, sides in self.shuffles:
+            d = max(d, 2 + max([1] + [expr_degree(e) for e in ins]), 2 + max([1] + [expr_degree(e) for e in sides]))
         for g in self.gates:
             d = max(d, expr_degree(g))
         self.degree = max(d, self.minimum_degree)
@@ -109,6 +133,7 @@ class Prog:
         if k == "fixed": return (po.SRC_FIXED, e[1], self.rot(e[2]))
         if k == "advice": return (po.SRC_ADVICE, e[1], self.rot(e[2]))
         if k == "instance": return (po.SRC_INSTANCE, e[1], self.rot(e[2]))
+        if k == "challenge": return (po.SRC_CHALLENGE, e[1], 0)
         if k == "neg": return self.calc(po.CALC_NEGATE, self.expr(e[1]))
         if k == "sum": return self.calc(po.CALC_ADD, self.expr(e[1]), self.expr(e[2]))
         if k == "product": return self.calc(po.CALC_MUL, self.expr(e[1]), self.expr(e[2]))
@@ -220,8 +245,19 @@ def vk_bytes(curve: po.Curve, key: dict, selectors: Sequence[np.ndarray] = ()) -
     return out
 
 
+def description_text(desc) -> str:
+    """What transcript_repr hashes of a description: the tuple's text; with phases or challenges (description, phases, challenge phases)'s; with shuffles
+    (description, shuffles, phases, challenge phases)'s."""
+    shuffles, phases, challenge_phases = getattr(desc, "shuffles", ()), getattr(desc, "phases", ()), getattr(desc, "challenge_phases", ())
+    if shuffles:
+        return repr((tuple(desc), shuffles, phases, challenge_phases))
+    if challenge_phases or any(phases):
+        return repr((tuple(desc), phases, challenge_phases))
+    return repr(desc)
+
+
 def transcript_repr(curve: po.Curve, key: dict, selectors=()) -> int:
-    body = vk_bytes(curve, key, selectors) + repr(key["desc"]).encode()
+    body = vk_bytes(curve, key, selectors) + description_text(key["desc"]).encode()
     h = hashlib.blake2b(digest_size=64, person=b"Halo2-Verify-Key")
     h.update(struct.pack("<Q", len(body)) + body)
     return int.from_bytes(h.digest(), "little") % curve.scalar.p
@@ -242,33 +278,79 @@ class ScalarStream:
         return a
 
 
-# ---- create_proof ---------------------------------------------------------------------------------------------
-def plonk_queries(sh: Shape, rotate, x, C: Dict[str, list], E: Dict[str, list]):
-    """The opening queries in upstream's order (instance, advice, permutation products, lookups, fixed, sigma, h, random) as (key, point, item, eval):
-    `key` names the commitment, `item` is whatever the caller opens (a commitment for a verifier, a (polynomial, blind) for a prover).  The one
-    statement of that order: both provers and both verifiers list their queries here.  E["instance"] is empty where instance columns are not queried.
+# ---- the order of things: one statement each, over circuits and shuffles ------------------------------------------------------------------------
+# A commitment or evaluation of a circuit's own is keyed (name, circuit, index); what the proof has once is keyed (name, index), ("random",), ("h",).
+def evaluation_order(sh: Shape, circuits: int = 1, query_instance: bool = False):
+    """The evaluations a proof over `circuits` circuits writes, in upstream's order, as (key, rotation): per circuit instance (where queried) | per circuit
+    advice | fixed | random | sigma | per circuit permutation products | per circuit lookups | per circuit shuffles."""
+    L, S, H, last = len(sh.lookups), sh.num_sets, len(sh.shuffles), -(sh.blinding_factors + 1)
+    W = [(("instance", c, col), r) for c in range(circuits) for col, r in sh.instance_queries] if query_instance else []
+    W += [(("advice", c, col), r) for c in range(circuits) for col, r in sh.advice_queries]
+    W += [(("fixed", col), r) for col, r in sh.fixed_queries] + [(("random",), 0)] + [(("sigma", j), 0) for j in range(len(sh.perm_columns))]
+    for c in range(circuits):
+        for s in range(S):
+            W += [(("perm_z", c, s), 0), (("perm_z", c, s), 1)] + ([(("perm_z", c, s), last)] if s != S - 1 else [])
+    for c in range(circuits):
+        for l in range(L):
+            W += [(("lookup_z", c, l), 0), (("lookup_z", c, l), 1), (("lookup_a", c, l), 0), (("lookup_a", c, l), -1), (("lookup_s", c, l), 0)]
+    for c in range(circuits):
+        for j in range(H):
+            W += [(("shuffle_z", c, j), 0), (("shuffle_z", c, j), 1)]
+    return W
+
+
+def plonk_queries(sh: Shape, circuits: int, query_instance: bool, rotate, item, ev):
+    """The opening queries in upstream's order as (key, point, item(key), ev(key, rotation)): circuit after circuit its instance (where queried), advice,
+    permutation product, lookup and shuffle queries, then once fixed, sigma, h, random.  `item` gives whatever the caller opens (a commitment for a
+    verifier, a (polynomial, blind) for a prover), `ev` the evaluation.  The one statement of that order: every prover and verifier lists its queries here.
     [UPSTREAM permutation::{prover,verifier}: the products at x and omega x set by set, then at omega^last x over sets.iter().rev().skip(1)]"""
-    x_next, x_inv, x_last = rotate(1), rotate(-1), rotate(-(sh.blinding_factors + 1))
+    L, S, H, last = len(sh.lookups), sh.num_sets, len(sh.shuffles), -(sh.blinding_factors + 1)
     Q = []
-    for (c, r), e in zip(sh.instance_queries, E["instance"]):
-        Q.append((("instance", c), rotate(r), C["instance"][c], e))
-    for (c, r), e in zip(sh.advice_queries, E["advice"]):
-        Q.append((("advice", c), rotate(r), C["advice"][c], e))
-    for s, (zc, (e0, e1, _)) in enumerate(zip(C["perm_z"], E["perm"])):
-        Q += [(("perm_z", s), x, zc, e0), (("perm_z", s), x_next, zc, e1)]
-    for s in reversed(range(max(0, len(C["perm_z"]) - 1))):      # sets.iter().rev().skip(1)
-        Q.append((("perm_z", s), x_last, C["perm_z"][s], E["perm"][s][2]))
-    for l, ((ai, ti), zc, (z0, z1, a0, am1, s0)) in enumerate(zip(C["lookup_permuted"], C["lookup_z"], E["lookup"])):
-        Q += [(("lookup_z", l), x, zc, z0), (("lookup_a", l), x, ai, a0), (("lookup_s", l), x, ti, s0), (("lookup_a", l), x_inv, ai, am1), (("lookup_z", l), x_next, zc, z1)]
-    for (c, r), e in zip(sh.fixed_queries, E["fixed"]):
-        Q.append((("fixed", c), rotate(r), C["fixed"][c], e))
-    for j, (sc, e) in enumerate(zip(C["sigma"], E["sigma"])):
-        Q.append((("sigma", j), x, sc, e))
-    Q.append((("h",), x, C["h"], E["h"]))
-    Q.append((("random",), x, C["random"], E["random"]))
+    q = lambda key, r: Q.append((key, rotate(r), item(key), ev(key, r)))
+    for c in range(circuits):
+        for col, r in (sh.instance_queries if query_instance else ()):
+            q(("instance", c, col), r)
+        for col, r in sh.advice_queries:
+            q(("advice", c, col), r)
+        for s in range(S):
+            q(("perm_z", c, s), 0), q(("perm_z", c, s), 1)
+        for s in reversed(range(max(0, S - 1))):      # sets.iter().rev().skip(1)
+            q(("perm_z", c, s), last)
+        for l in range(L):
+            q(("lookup_z", c, l), 0), q(("lookup_a", c, l), 0), q(("lookup_s", c, l), 0), q(("lookup_a", c, l), -1), q(("lookup_z", c, l), 1)
+        for j in range(H):
+            q(("shuffle_z", c, j), 0), q(("shuffle_z", c, j), 1)
+    for col, r in sh.fixed_queries:
+        q(("fixed", col), r)
+    for j in range(len(sh.perm_columns)):
+        q(("sigma", j), 0)
+    q(("h",), 0), q(("random",), 0)
     return Q
 
 
+def symbolic_queries(sh: Shape, circuits: int = 1, query_instance: bool = False):
+    """plonk_queries with rotations for points and (key, rotation) for evaluations (None: the folded h's) -> [(key, rotation, eval)]"""
+    Q = plonk_queries(sh, circuits, query_instance, lambda r: r, lambda key: key, lambda key, r: None if key == ("h",) else (key, r))
+    return [(key, pt, e) for key, pt, _, e in Q]
+
+
+def proof_length(sh: Shape, circuits: int, scheme: str) -> int:
+    """KZG: 32 [N (A + 3 L + S + H) + 1 + pieces + groups] + 32 [N (|advice_q| + (3 S - 1 if S) + 5 L + 2 H) + |fixed_q| + 1 + npc]; SHPLONK: 2 for `groups`.
+    IPA (N = 1): 32 [A + 3 L + S + H + 1 + pieces + 1 (f) + 1 (S) + 2 k] + 32 [|instance_q| + evaluations + point sets + 2]"""
+    A, L, S, H, N = sh.num_advice, len(sh.lookups), sh.num_sets, len(sh.shuffles), circuits
+    Q = symbolic_queries(sh, circuits, scheme == "ipa")
+    evals = N * (len(sh.advice_queries) + (3 * S - 1 if S else 0) + 5 * L + 2 * H) + len(sh.fixed_queries) + 1 + len(sh.perm_columns)
+    head = N * (A + 3 * L + S + H) + 1 + (sh.degree - 1)
+    if scheme == "ipa":
+        sets = {}
+        for key, pt, _ in Q:
+            sets.setdefault(key, set()).add(pt)
+        return 32 * (head + 2 + 2 * sh.k) + 32 * (N * len(sh.instance_queries) + evals + len({frozenset(v) for v in sets.values()}) + 2)
+    groups = 2 if scheme == "shplonk" else len({pt for _, pt, _ in Q})
+    return 32 * (head + groups) + 32 * evals
+
+
+# ---- create_proof ---------------------------------------------------------------------------------------------
 class ProverGWC:
     """What create_proof takes as its scheme under KZG: bare MSM commitments (the blinds are drawn and dropped), instance values absorbed as scalars
     and not queried (QUERY_INSTANCE = false), GWC's multiopen.  ipa.ProverIPA is the other scheme."""
@@ -301,14 +383,44 @@ class ProverGWC:
         return dict(challenges=dict(v=v))
 
 
-def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, instances: Sequence[Sequence[int]], rng, vk_repr: int, threads: int = 1, scheme=None):
-    """-> (proof bytes, trace) -- trace holds every commitment, challenge and evaluation in order, and h's coefficients.
-    advice_mont: (num_advice, n, 4) Montgomery; rng.scalars(count) -> (count, 4) Montgomery (consumed in upstream's order: one body draws for both
-    schemes, with the multiopen's draws behind it).  scheme: ProverGWC (the default) or ipa.ProverIPA -- how instances enter the transcript and
-    whether they are queried, commit(bases, scalars, blind) and open(T, Q, rng, write_commit)."""
-    scheme = scheme if scheme is not None else ProverGWC(curve, srs, threads)
+def scheme_object(curve: po.Curve, srs, threads: int, scheme):
+    """"gwc" (or None), "shplonk" (tests/shplonk_oracle.py's) or a scheme object as it is"""
+    if scheme is None or scheme == "gwc":
+        return ProverGWC(curve, srs, threads)
+    if scheme == "shplonk":
+        import shplonk_oracle
+        return shplonk_oracle.ProverSHPLONK(curve, srs, threads)
+    return scheme
+
+
+def create_proof_multi(curve: po.Curve, srs, key: dict, witnesses: Sequence, instances: Sequence[Sequence[Sequence[int]]], rng, vk_repr: int, threads: int = 1,
+                       scheme=None):
+    """One proof over len(witnesses) circuits of one key -> (proof bytes, trace) -- trace holds every commitment, challenge and evaluation in order, and h's
+    coefficients.  witnesses[c]: (num_advice, n, 4) Montgomery advice, or for a key with later phases a function (phase, challenges) -> such an array with
+    the columns of phases <= phase filled; instances[c]: circuit c's instance columns.  rng.scalars(count) -> (count, 4) Montgomery, consumed in upstream's
+    order (one body draws for every scheme, the multiopen's draws behind it).  scheme: "gwc" (the default), "shplonk" or a scheme object (ProverGWC,
+    ipa.ProverIPA) -- how instances enter the transcript and whether they are queried, commit(bases, scalars, blind) and open(T, Q, rng, write_commit).
+
+    [UPSTREAM plonk/prover.rs] takes `&[circuit]` and `&[instances]`: every step that concerns a witness loops over the circuits, every step that concerns the
+    key or the quotient happens once.
+      instances        for each circuit, for each instance column: absorbed
+      advice           for each phase: for each circuit the blinding rows of the phase's columns (ascending), one blind per column, the commitments;
+                       then one challenge per challenge of that phase                                                     -> theta
+      lookups          for each circuit, for each lookup: the permuted pair                                               -> beta, gamma
+      products         every circuit's permutation products (last_z starts again at 1) | every circuit's lookup products | every circuit's shuffle
+                       products: z[0] = 1, z[i + 1] = z[i] (A[i] + gamma) / (S[i] + gamma), A and S the sides compressed with theta as a lookup's are
+      vanishing        the random polynomial, once                                                                        -> y
+      evaluate_h       one running value: for each circuit its gates, its permutation terms, its lookup terms, per shuffle
+                       l0 (1 - z), l_last (z^2 - z), l_active (z(wX)(S + gamma) - z(X)(A + gamma)); / t(X); the pieces committed once   -> x
+      evaluations      `evaluation_order`;  queries  `plonk_queries`
+    Several circuits are proved under KZG only, and only where the key has one phase and no challenge."""
+    scheme = scheme_object(curve, srs, threads, scheme)
+    N = len(witnesses)
     F = Fld(curve.scalar)
     sh: Shape = key["shape"]
+    assert N >= 1 and len(instances) == N
+    assert N == 1 or not scheme.query_instance, "IPA proves one circuit"
+    assert N == 1 or (sh.num_phases == 1 and not sh.challenge_phases), "later phases and challenges: one circuit"
     d, n, p, k, u, bf = sh.dom, sh.n, F.p, sh.k, sh.usable, sh.blinding_factors
     mm = F.m
     T = Transcript(curve)
@@ -317,7 +429,8 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
     c2e = lambda a: co.coeff_to_extended(F.id, a, k, sh.ext_k, mm(d.ext_omega), mm(d.g_coset), threads)
     mul = lambda a, b: co.field_op(F.id, "mul", a, b)
     add = lambda a, b: co.field_op(F.id, "add", a, b)
-    bc = lambda x: np.tile(mm(x), (n, 1))
+    sub = lambda a, b: co.field_op(F.id, "sub", a, b)
+    bc = lambda v, rows=n: np.tile(mm(v), (rows, 1))
 
     def write_commit(bases, scalars, blind_mont):
         P = scheme.commit(bases, scalars, blind_mont)
@@ -326,101 +439,142 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
         return F.un(blind_mont)
 
     T.common_scalar(vk_repr)
-    # instances
-    inst_values = []
-    for vals in instances:
-        col = np.zeros((n, 4), dtype=np.uint64)
-        if len(vals):
-            col[:len(vals)] = F.many(vals)
-        inst_values.append(col)
-        scheme.absorb_instance(T, vals, col)
-    inst_polys = [l2c(v) for v in inst_values]
-    # advice
-    advice = [np.array(advice_mont[i], dtype=np.uint64).reshape(n, 4) for i in range(sh.num_advice)]
-    for a in advice:
-        a[u:] = rng.scalars(n - u)
-    advice_blinds = [write_commit(srs["g_lagrange"], a, b) for a, b in zip(advice, rng.scalars(sh.num_advice))]
+    circuits = [dict(advice=[None] * sh.num_advice, advice_blinds=[None] * sh.num_advice) for _ in range(N)]
+    # instances: circuit after circuit
+    for cc, inst in zip(circuits, instances):
+        assert len(inst) == sh.num_instance, "instances.len() != num_instance_columns"
+        cc["inst_values"] = []
+        for vals in inst:
+            assert len(vals) <= u, "instance column too long"
+            col = np.zeros((n, 4), dtype=np.uint64)
+            if len(vals):
+                col[:len(vals)] = F.many(vals)
+            cc["inst_values"].append(col)
+            scheme.absorb_instance(T, vals, col)
+        cc["inst_polys"] = [l2c(v) for v in cc["inst_values"]]
+    # advice, phase by phase: the phase's rows, its blinds, its commitments, its challenges
+    challenges = [0] * len(sh.challenge_phases)
+    for ph in range(sh.num_phases):
+        cols = [c for c in range(sh.num_advice) if sh.phases[c] == ph]
+        for cc, witness in zip(circuits, witnesses):
+            advice_mont = witness(ph, list(challenges)) if callable(witness) else witness
+            for c in cols:
+                cc["advice"][c] = np.array(advice_mont[c], dtype=np.uint64).reshape(n, 4)
+                cc["advice"][c][u:] = rng.scalars(n - u)
+            for c, b in zip(cols, rng.scalars(len(cols))):
+                cc["advice_blinds"][c] = write_commit(srs["g_lagrange"], cc["advice"][c], b)
+        for j, q in enumerate(sh.challenge_phases):
+            if q == ph:
+                challenges[j] = T.challenge()
     theta = T.challenge()
     # lookups: compress, permute
     fixed_v = key["fixed_values"]
-    lookups = []
-    for ins, tabs in sh.lookups:
-        def compress(exprs):
-            acc = np.zeros((n, 4), dtype=np.uint64)
-            for e in exprs:
-                pr = Prog(p)
-                pr.calc(po.CALC_STORE, pr.expr(e))
-                val = pr.run(F, fixed_v, advice, inst_values, None, None, None, None, None, k, 1, None, threads)
-                acc = add(mul(acc, bc(theta)), val)
-            return acc
-        ci, ct = compress(ins), compress(tabs)
-        res = co.permute_expression_pair(F.id, ci, ct, u)
-        assert res is not None, "lookup input not in table (ConstraintSystemFailure)"
-        pi, pt = (np.concatenate([x, np.zeros((n - u, 4), dtype=np.uint64)]) for x in res)
-        pi[u:] = rng.scalars(n - u)
-        pt[u:] = rng.scalars(n - u)
-        bi, bt = rng.scalars(2)
-        lookups.append(dict(ci=ci, ct=ct, pi=pi, pt=pt, pi_blind=write_commit(srs["g_lagrange"], pi, bi), pt_blind=write_commit(srs["g_lagrange"], pt, bt)))
+
+    def compress(cc, exprs):
+        acc = np.zeros((n, 4), dtype=np.uint64)
+        for e in exprs:
+            pr = Prog(p)
+            pr.calc(po.CALC_STORE, pr.expr(e))
+            val = pr.run(F, fixed_v, cc["advice"], cc["inst_values"], challenges, None, None, None, None, k, 1, None, threads)
+            acc = add(mul(acc, bc(theta)), val)
+        return acc
+
+    for cc in circuits:
+        cc["lookups"] = []
+        for ins, tabs in sh.lookups:
+            ci, ct = compress(cc, ins), compress(cc, tabs)
+            res = co.permute_expression_pair(F.id, ci, ct, u)
+            assert res is not None, "lookup input not in table (ConstraintSystemFailure)"
+            pi, pt = (np.concatenate([v, np.zeros((n - u, 4), dtype=np.uint64)]) for v in res)
+            pi[u:] = rng.scalars(n - u)
+            pt[u:] = rng.scalars(n - u)
+            bi, bt = rng.scalars(2)
+            cc["lookups"].append(dict(ci=ci, ct=ct, pi=pi, pt=pt, pi_blind=write_commit(srs["g_lagrange"], pi, bi), pt_blind=write_commit(srs["g_lagrange"], pt, bt)))
     beta, gamma = T.challenge(), T.challenge()
-    # permutation argument
-    colvals = {"advice": advice, "fixed": fixed_v, "instance": inst_values}
+    # permutation products of every circuit
     w = co.powers(F.id, mm(d.omega), mm(1), n)
-    perm_z, perm_z_blinds, last_z, dcur = [], [], 1, 1
-    for s in range(sh.num_sets):
-        cols_s = sh.perm_columns[s * sh.chunk_len:(s + 1) * sh.chunk_len]
-        den = np.tile(mm(1), (n, 1))
-        for j, (ck, cidx) in enumerate(cols_s, start=s * sh.chunk_len):
-            den = mul(den, add(add(mul(bc(beta), key["perm_values"][j]), bc(gamma)), colvals[ck][cidx]))
-        den = co.batch_invert(F.id, den)
-        modified = den
-        for ck, cidx in cols_s:
-            modified = mul(modified, add(add(mul(w, bc(dcur * beta % p)), bc(gamma)), colvals[ck][cidx]))
-            dcur = dcur * key["delta"] % p
-        z = co.field_op(F.id, "mul", co.grand_product(F.id, modified, np.tile(mm(1), (n, 1))), bc(last_z))
-        z[n - bf:] = rng.scalars(bf)
-        zb = rng.scalars(1)[0]
-        last_z = F.un(z[u])
-        perm_z.append(z)
-        perm_z_blinds.append(write_commit(srs["g_lagrange"], z, zb))
-    # lookup products
-    for lk in lookups:
-        den = mul(add(lk["pi"], bc(beta)), add(lk["pt"], bc(gamma)))
-        num = mul(add(lk["ci"], bc(beta)), add(lk["ct"], bc(gamma)))
-        z = co.grand_product(F.id, num, den)
-        z[n - bf:] = rng.scalars(bf)
-        lk["z"] = z
-        lk["z_blind"] = write_commit(srs["g_lagrange"], z, rng.scalars(1)[0])
-    # vanishing: random polynomial
+    for cc in circuits:
+        colvals = {"advice": cc["advice"], "fixed": fixed_v, "instance": cc["inst_values"]}
+        cc["perm_z"], cc["perm_z_blinds"] = [], []
+        last_z, dcur = 1, 1
+        for s in range(sh.num_sets):
+            cols_s = sh.perm_columns[s * sh.chunk_len:(s + 1) * sh.chunk_len]
+            den = np.tile(mm(1), (n, 1))
+            for j, (ck, cidx) in enumerate(cols_s, start=s * sh.chunk_len):
+                den = mul(den, add(add(mul(bc(beta), key["perm_values"][j]), bc(gamma)), colvals[ck][cidx]))
+            modified = co.batch_invert(F.id, den)
+            for ck, cidx in cols_s:
+                modified = mul(modified, add(add(mul(w, bc(dcur * beta % p)), bc(gamma)), colvals[ck][cidx]))
+                dcur = dcur * key["delta"] % p
+            z = co.field_op(F.id, "mul", co.grand_product(F.id, modified, np.tile(mm(1), (n, 1))), bc(last_z))
+            z[n - bf:] = rng.scalars(bf)
+            zb = rng.scalars(1)[0]
+            last_z = F.un(z[u])
+            cc["perm_z"].append(z)
+            cc["perm_z_blinds"].append(write_commit(srs["g_lagrange"], z, zb))
+    # then the lookup products of every circuit
+    for cc in circuits:
+        for lk in cc["lookups"]:
+            den = mul(add(lk["pi"], bc(beta)), add(lk["pt"], bc(gamma)))
+            num = mul(add(lk["ci"], bc(beta)), add(lk["ct"], bc(gamma)))
+            z = co.grand_product(F.id, num, den)
+            z[n - bf:] = rng.scalars(bf)
+            lk["z"] = z
+            lk["z_blind"] = write_commit(srs["g_lagrange"], z, rng.scalars(1)[0])
+    # then the shuffle products of every circuit
+    for cc in circuits:
+        cc["shuffles"] = []
+        for ins, sides in sh.shuffles:
+            z = co.grand_product(F.id, add(compress(cc, ins), bc(gamma)), add(compress(cc, sides), bc(gamma)))
+            closed = F.un(z[u]) == 1
+            z[n - bf:] = rng.scalars(bf)
+            cc["shuffles"].append(dict(z=z, closed=closed, z_blind=write_commit(srs["g_lagrange"], z, rng.scalars(1)[0])))
+    # vanishing: the random polynomial, once
     random_poly = rng.scalars(n)
     random_blind = write_commit(srs["g"], random_poly, rng.scalars(1)[0])
     y = T.challenge()
-    # coefficient forms, cosets
-    advice_polys = [l2c(a) for a in advice]
-    perm_z_polys = [l2c(z) for z in perm_z]
-    for lk in lookups:
-        lk["pi_poly"], lk["pt_poly"], lk["z_poly"] = l2c(lk["pi"]), l2c(lk["pt"]), l2c(lk["z"])
-    advice_c, inst_c = [c2e(a) for a in advice_polys], [c2e(a) for a in inst_polys]
+    # evaluate_h: one running value over the circuits
     fixed_c = key["fixed_cosets"]
     rot_scale = sh.ext_n // n
-    # evaluate_h
-    pr = Prog(p)
-    parts = [pr.expr(g) for g in sh.gates]
-    pr.calc(po.CALC_HORNER, (po.SRC_PREVIOUS, 0, 0), (po.SRC_Y, 0, 0), parts)
-    h = pr.run(F, fixed_c, advice_c, inst_c, None, None, None, None, y, sh.ext_k, rot_scale, None, threads)
-    if sh.num_sets:
-        cmap = {"advice": advice_c, "fixed": fixed_c, "instance": inst_c}
-        pcols = [cmap[ck][ci] for ck, ci in sh.perm_columns]
-        h = co.permutation_h(F.id, h, [c2e(zp) for zp in perm_z_polys], pcols, key["perm_cosets"], sh.chunk_len, -(bf + 1), key["l0"], key["l_last"], key["l_active"],
-                             mm(beta), mm(gamma), mm(y), mm(key["delta"]), mm(beta * d.g_coset % p), mm(d.ext_omega), sh.ext_k, rot_scale, threads)
-    for (ins, tabs), lk in zip(sh.lookups, lookups):
+    h = None
+    for cc in circuits:
+        cc["advice_polys"] = [l2c(a) for a in cc["advice"]]
+        cc["perm_z_polys"] = [l2c(z) for z in cc["perm_z"]]
+        for lk in cc["lookups"]:
+            lk["pi_poly"], lk["pt_poly"], lk["z_poly"] = l2c(lk["pi"]), l2c(lk["pt"]), l2c(lk["z"])
+        for sf in cc["shuffles"]:
+            sf["z_poly"] = l2c(sf["z"])
+        advice_c, inst_c = [c2e(a) for a in cc["advice_polys"]], [c2e(a) for a in cc["inst_polys"]]
+        run = lambda pr, beta, gamma, theta, y, previous: pr.run(F, fixed_c, advice_c, inst_c, challenges, beta, gamma, theta, y, sh.ext_k, rot_scale, previous, threads)
         pr = Prog(p)
-        ci = pr.calc(po.CALC_HORNER, (po.SRC_CONSTANT, 0, 0), (po.SRC_THETA, 0, 0), [pr.expr(e) for e in ins])
-        ct = pr.calc(po.CALC_HORNER, (po.SRC_CONSTANT, 0, 0), (po.SRC_THETA, 0, 0), [pr.expr(e) for e in tabs])
-        pr.calc(po.CALC_MUL, pr.calc(po.CALC_ADD, ci, (po.SRC_BETA, 0, 0)), pr.calc(po.CALC_ADD, ct, (po.SRC_GAMMA, 0, 0)))
-        tv = pr.run(F, fixed_c, advice_c, inst_c, None, beta, gamma, theta, None, sh.ext_k, rot_scale, None, threads)
-        h = co.lookup_h(F.id, h, c2e(lk["z_poly"]), c2e(lk["pi_poly"]), c2e(lk["pt_poly"]), tv, key["l0"], key["l_last"], key["l_active"], mm(beta), mm(gamma), mm(y),
-                        sh.ext_k, rot_scale, threads)
-    # divide by t(X), back to coefficients, split, commit
+        parts = [pr.expr(g) for g in sh.gates]
+        pr.calc(po.CALC_HORNER, (po.SRC_PREVIOUS, 0, 0), (po.SRC_Y, 0, 0), parts)
+        h = run(pr, None, None, None, y, h)
+        if sh.num_sets:
+            cmap = {"advice": advice_c, "fixed": fixed_c, "instance": inst_c}
+            pcols = [cmap[ck][ci] for ck, ci in sh.perm_columns]
+            h = co.permutation_h(F.id, h, [c2e(zp) for zp in cc["perm_z_polys"]], pcols, key["perm_cosets"], sh.chunk_len, -(bf + 1), key["l0"], key["l_last"],
+                                 key["l_active"], mm(beta), mm(gamma), mm(y), mm(key["delta"]), mm(beta * d.g_coset % p), mm(d.ext_omega), sh.ext_k, rot_scale, threads)
+        for (ins, tabs), lk in zip(sh.lookups, cc["lookups"]):
+            pr = Prog(p)
+            ci = pr.calc(po.CALC_HORNER, (po.SRC_CONSTANT, 0, 0), (po.SRC_THETA, 0, 0), [pr.expr(e) for e in ins])
+            ct = pr.calc(po.CALC_HORNER, (po.SRC_CONSTANT, 0, 0), (po.SRC_THETA, 0, 0), [pr.expr(e) for e in tabs])
+            pr.calc(po.CALC_MUL, pr.calc(po.CALC_ADD, ci, (po.SRC_BETA, 0, 0)), pr.calc(po.CALC_ADD, ct, (po.SRC_GAMMA, 0, 0)))
+            tv = run(pr, beta, gamma, theta, None, None)
+            h = co.lookup_h(F.id, h, c2e(lk["z_poly"]), c2e(lk["pi_poly"]), c2e(lk["pt_poly"]), tv, key["l0"], key["l_last"], key["l_active"], mm(beta), mm(gamma), mm(y),
+                            sh.ext_k, rot_scale, threads)
+        for (ins, sides), sf in zip(sh.shuffles, cc["shuffles"]):      # element-wise, on Montgomery columns of the extended domain
+            def side_value(exprs):
+                pr = Prog(p)
+                cv = pr.calc(po.CALC_HORNER, (po.SRC_CONSTANT, 0, 0), (po.SRC_THETA, 0, 0), [pr.expr(e) for e in exprs])
+                pr.calc(po.CALC_ADD, cv, (po.SRC_GAMMA, 0, 0))
+                return run(pr, None, gamma, theta, None, None)
+            iv, sv = side_value(ins), side_value(sides)
+            z = c2e(sf["z_poly"])
+            z_next = np.roll(z, -rot_scale, axis=0)
+            for term, lag in ((sub(bc(1, sh.ext_n), z), key["l0"]), (sub(mul(z, z), z), key["l_last"]), (sub(mul(z_next, sv), mul(z, iv)), key["l_active"])):
+                h = add(mul(h, bc(y, sh.ext_n)), mul(term, lag))
+    # divide by t(X), back to coefficients, split, commit: once
     orig, step = pow(d.g_coset, n, p), pow(d.ext_omega, n, p)
     t_inv = F.many([pow((orig * pow(step, i, p) - 1) % p, -1, p) for i in range(rot_scale)])
     h = co.scale_periodic(F.id, h, t_inv)
@@ -432,48 +586,46 @@ def create_proof(curve: po.Curve, srs, key: dict, advice_mont: np.ndarray, insta
     xn = pow(x, n, p)
     rotate = lambda r: x * pow(d.omega if r >= 0 else d.omega_inv, abs(r), p) % p
     ev = lambda poly, pt: F.un(co.eval_polynomial(F.id, poly, mm(pt), threads))
-
-    def write_eval(poly, pt):
-        e = ev(poly, pt)
-        T.write_scalar(e)
-        trace["evals"].append(e)
-        return e
-
-    inst_evals = [write_eval(inst_polys[c], rotate(r)) for c, r in sh.instance_queries] if scheme.query_instance else []
-    adv_evals = [write_eval(advice_polys[c], rotate(r)) for c, r in sh.advice_queries]
-    fix_evals = [write_eval(key["fixed_polys"][c], rotate(r)) for c, r in sh.fixed_queries]
-    hfold = co.lincomb(F.id, pieces, F.many([pow(xn, i, p) for i in range(pieces_n)]))
-    random_eval = write_eval(random_poly, x)
-    sigma_evals = [write_eval(sp, x) for sp in key["perm_polys"]]
-    x_next, x_inv, x_last = rotate(1), rotate(-1), rotate(-(bf + 1))
-    pz_evals = []
-    for s, zp in enumerate(perm_z_polys):
-        e0, e1 = write_eval(zp, x), write_eval(zp, x_next)
-        el = write_eval(zp, x_last) if s != len(perm_z_polys) - 1 else None
-        pz_evals.append((e0, e1, el))
-    lk_evals = []
-    for lk in lookups:
-        lk_evals.append((write_eval(lk["z_poly"], x), write_eval(lk["z_poly"], x_next), write_eval(lk["pi_poly"], x), write_eval(lk["pi_poly"], x_inv),
-                         write_eval(lk["pt_poly"], x)))
-    # queries, in upstream's order; the opened item is (polynomial, blind)
-    h_blind = sum(b * pow(xn, i, p) for i, b in enumerate(h_blinds)) % p      # folded with x^n as the pieces are
+    # what is opened, key -> (polynomial, blind), and the evaluations, in evaluation_order
     db = scheme.default_blind
-    Q = plonk_queries(sh, rotate, x,
-                      dict(instance=[(q, db) for q in inst_polys], advice=list(zip(advice_polys, advice_blinds)), perm_z=list(zip(perm_z_polys, perm_z_blinds)),
-                           lookup_permuted=[((lk["pi_poly"], lk["pi_blind"]), (lk["pt_poly"], lk["pt_blind"])) for lk in lookups],
-                           lookup_z=[(lk["z_poly"], lk["z_blind"]) for lk in lookups], fixed=[(q, db) for q in key["fixed_polys"]],
-                           sigma=[(q, db) for q in key["perm_polys"]], h=(hfold, h_blind), random=(random_poly, random_blind)),
-                      dict(instance=inst_evals, advice=adv_evals, perm=pz_evals, lookup=lk_evals, fixed=fix_evals, sigma=sigma_evals, h=ev(hfold, x), random=random_eval))
-    opened = scheme.open(T, Q, rng, write_commit)
-    trace["challenges"] = dict(theta=theta, beta=beta, gamma=gamma, y=y, x=x, **opened.pop("challenges"))
-    trace.update(opened)
-    trace["perm_last_evals"] = [el for _, _, el in pz_evals[:-1]]                        # as written to the transcript: set 0, 1, ...
-    trace["x_last_group"] = [e for _, pt, _, e in Q if pt == x_last] if sh.num_sets > 1 else []      # as GWC batches them with 1, v, v^2, ...
+    opened = {("random",): (random_poly, random_blind)}
+    opened.update({("fixed", i): (q, db) for i, q in enumerate(key["fixed_polys"])})
+    opened.update({("sigma", j): (q, db) for j, q in enumerate(key["perm_polys"])})
+    for c, cc in enumerate(circuits):
+        opened.update({("instance", c, i): (q, db) for i, q in enumerate(cc["inst_polys"])})
+        opened.update({("advice", c, i): item for i, item in enumerate(zip(cc["advice_polys"], cc["advice_blinds"]))})
+        opened.update({("perm_z", c, s): item for s, item in enumerate(zip(cc["perm_z_polys"], cc["perm_z_blinds"]))})
+        for l, lk in enumerate(cc["lookups"]):
+            opened.update({("lookup_z", c, l): (lk["z_poly"], lk["z_blind"]), ("lookup_a", c, l): (lk["pi_poly"], lk["pi_blind"]),
+                           ("lookup_s", c, l): (lk["pt_poly"], lk["pt_blind"])})
+        opened.update({("shuffle_z", c, j): (sf["z_poly"], sf["z_blind"]) for j, sf in enumerate(cc["shuffles"])})
+    E = {}
+    for key_, r in evaluation_order(sh, N, scheme.query_instance):
+        E[(key_, r)] = ev(opened[key_][0], rotate(r))
+        T.write_scalar(E[(key_, r)])
+        trace["evals"].append(E[(key_, r)])
+    hfold = co.lincomb(F.id, pieces, F.many([pow(xn, i, p) for i in range(pieces_n)]))
+    opened[("h",)] = (hfold, sum(b * pow(xn, i, p) for i, b in enumerate(h_blinds)) % p)      # the blinds folded with x^n as the pieces are
+    E[(("h",), 0)] = ev(hfold, x)
+    Q = plonk_queries(sh, N, scheme.query_instance, rotate, opened.__getitem__, lambda key_, r: E[(key_, r)])
+    multiopen = scheme.open(T, Q, rng, write_commit)
+    trace["challenges"] = dict(theta=theta, beta=beta, gamma=gamma, y=y, x=x, **multiopen.pop("challenges"))
+    trace.update(multiopen)
+    last = -(bf + 1)
+    trace["perm_last_evals"] = [E[(("perm_z", c, s), last)] for c in range(N) for s in range(sh.num_sets - 1)]      # as written to the transcript: set 0, 1, ...
+    trace["x_last_group"] = [e for _, pt, _, e in Q if pt == rotate(last)] if sh.num_sets > 1 else []      # as GWC batches them with 1, v, v^2, ...
     trace["h_coeffs"] = hc
+    trace["phase_challenges"] = challenges
+    trace["shuffles_closed"] = [[sf["closed"] for sf in cc["shuffles"]] for cc in circuits]
     return bytes(T.proof), trace
 
 
-def create_proof_ipa(curve: po.Curve, srs, u_mont, w_mont, key: dict, advice_mont: np.ndarray, instances: Sequence[Sequence[int]], rng, vk_repr: int,
+def create_proof(curve: po.Curve, srs, key: dict, advice_mont, instances: Sequence[Sequence[int]], rng, vk_repr: int, threads: int = 1, scheme=None):
+    """create_proof_multi over one circuit: advice_mont its witness, instances its instance columns."""
+    return create_proof_multi(curve, srs, key, [advice_mont], [instances], rng, vk_repr, threads, scheme)
+
+
+def create_proof_ipa(curve: po.Curve, srs, u_mont, w_mont, key: dict, advice_mont, instances: Sequence[Sequence[int]], rng, vk_repr: int,
                      threads: int = 1, default_blind: int = ipa.DEFAULT_BLIND):
     """create_proof over IPACommitmentScheme / ProverIPA [UPSTREAM plonk/prover.rs with QUERY_INSTANCE = true, poly/ipa/multiopen/prover.rs].
     srs: {"g", "g_lagrange"} (Montgomery points), u_mont / w_mont one point each; key: keygen's (bare commitments; the transcript representation is

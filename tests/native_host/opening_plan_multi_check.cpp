@@ -1,5 +1,5 @@
 // opening_plan_multi_check.cpp -- the prover's opening plan (csrc/opening_plan.hpp) for a proof over several circuits of one key, printed as JSON; built by g++
-// with ASan + UBSan (make opening_plan_multi_check), run by tests/test_multi_circuit.py, which compares every plan with tests/multi_oracle.py's lists.
+// with ASan + UBSan (make opening_plan_multi_check), run by tests/test_multi_circuit.py, which compares every plan with oracle/plonk_oracle.py's lists.
 //
 // One shape per line, plain integers (opening_plan_check.cpp's line behind the number of circuits):
 //   circuits  k A num_fixed I L S npc bf pieces query_instance  n_advice_q (column rotation)*  n_fixed_q (column rotation)*  n_instance_q (column rotation)*

@@ -37,6 +37,12 @@ def ipa_chain(po, co, desc, k, fixed, mapping, advice, selectors=()):
     return dict(c, u=uw[0], w=uw[1], fc=fc, pc=pc, ipa_key=ipa_key, rep=PO.transcript_repr(po.VESTA, ipa_key, selectors))
 
 
+def scheme_of(po, c, multiopen="gwc"):
+    """what create_proof takes as its scheme on chain c: ProverIPA for an IPA chain, else the KZG multiopen's name"""
+    import ipa
+    return ipa.ProverIPA(po.VESTA, c["srs"], c["u"], c["w"], THREADS, ipa.DEFAULT_BLIND) if "u" in c else multiopen
+
+
 def prove(po, c, instances, seed=7, **kw):
     """-> (proof, trace) of the scheme's restated prover under ScalarStream(seed)."""
     import plonk_oracle as PO
@@ -46,14 +52,35 @@ def prove(po, c, instances, seed=7, **kw):
     return PO.create_proof(po.BN254, c["srs"], c["key"], c["adv"], instances, PO.ScalarStream(seed), c["rep"], THREADS)
 
 
-def accepts(po, c, proof, instances):
-    """The scheme's restated verifier on `proof`."""
+def prove_circuits(po, c, witnesses, instances, multiopen="gwc", seed=7):
+    """-> (proof, trace) over len(witnesses) circuits of chain c: Montgomery advice arrays or, for a phased key, a function (phase, challenges) -> advice"""
+    import plonk_oracle as PO
+    curve = po.VESTA if "u" in c else po.BN254
+    return PO.create_proof_multi(curve, c["srs"], c["key"], witnesses, instances, PO.ScalarStream(seed), c["rep"], THREADS, scheme_of(po, c, multiopen))
+
+
+def accepts(po, c, proof, instances, multiopen="gwc", circuits=None):
+    """The scheme's restated verifier (KZG: of `multiopen`) on `proof`.  circuits None: over one circuit, `instances` its columns; N: instances[c] circuit c's."""
     import pairing as pr
+    import shplonk_oracle
     import verifier as V
-    instances = [list(v) for v in instances]
+    instances = [list(v) for v in instances] if circuits is None else [[list(v) for v in inst] for inst in instances]
     if "u" in c:
-        return V.verify_proof_ipa(po.VESTA, c["desc"], c["k"], c["fc"], c["pc"], c["rep"], c["srs"]["g"], c["srs"]["g_lagrange"], c["u"], c["w"], instances, proof)
-    return V.verify_proof(po.BN254, c["desc"], c["k"], c["key"]["fixed_commitments"], c["key"]["perm_commitments"], c["rep"], (1, 2), pr.G2, c["s_g2"], instances, proof)
+        return V.verify_proof_ipa(po.VESTA, c["desc"], c["k"], c["fc"], c["pc"], c["rep"], c["srs"]["g"], c["srs"]["g_lagrange"], c["u"], c["w"], instances, proof,
+                                  circuits=circuits)
+    verify = shplonk_oracle.verify_proof_shplonk if multiopen == "shplonk" else V.verify_proof
+    return verify(po.BN254, c["desc"], c["k"], c["key"]["fixed_commitments"], c["key"]["perm_commitments"], c["rep"], (1, 2), pr.G2, c["s_g2"], instances, proof, circuits)
+
+
+def phase_challenges(po, c, proof):
+    """the phase challenges the verifier squeezes while it reads `proof` (a chain without instance columns); None for a proof malformed before its evaluations end"""
+    import verifier as V
+    curve, ipa_ = (po.VESTA, True) if "u" in c else (po.BN254, False)
+    fc, pc = (c["fc"], c["pc"]) if ipa_ else (c["key"]["fixed_commitments"], c["key"]["perm_commitments"])
+    try:
+        return V.read_plonk(V.ReadTranscript(curve, proof), curve, c["desc"], c["k"], fc, pc, c["rep"], [], [] if ipa_ else None)[1]
+    except ValueError:
+        return None
 
 
 def tampered(c, proof):

@@ -160,16 +160,16 @@ class ProverSHPLONK(PO.ProverGWC):
 
 
 def create_proof(curve: po.Curve, srs, key: dict, advice_mont, instances, rng, vk_repr: int, threads: int = 1):
-    return PO.create_proof(curve, srs, key, advice_mont, instances, rng, vk_repr, threads, ProverSHPLONK(curve, srs, threads))
+    return PO.create_proof(curve, srs, key, advice_mont, instances, rng, vk_repr, threads, "shplonk")
 
 
-def verify_proof_shplonk(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitments, vk_repr: int, g0, g2, s_g2, instances, proof: bytes) -> bool:
+def verify_proof_shplonk(curve: po.Curve, desc, k: int, fixed_commitments, perm_commitments, vk_repr: int, g0, g2, s_g2, instances, proof: bytes, circuits=None) -> bool:
     """VerifierSHPLONK::verify_proof behind plonk/verifier.rs: with c_i = v^i zdiff_i / zdiff_0 and z_0 = Z_0(u),
     M = sum_i c_i sum_j y^j [P_ij] - (sum_i c_i sum_j y^j r_ij) G - z_0 [h] + u [h'];  accept iff e([h'], [s]G2) = e(M, G2) and no bytes trail."""
     p, C = curve.scalar.p, curve
     T = V.ReadTranscript(curve, proof)
     try:
-        Q = V.read_plonk(T, curve, desc, k, fixed_commitments, perm_commitments, vk_repr, instances)
+        Q, _ = V.read_plonk(T, curve, desc, k, fixed_commitments, perm_commitments, vk_repr, instances, None, circuits)
         y, v = T.challenge(), T.challenge()
         h = T.read_point()
         u = T.challenge()

@@ -1,4 +1,4 @@
-"""One proof over several circuits of one proving key (KZG: GWC and SHPLONK): tests/multi_oracle.py's restatement against the single-circuit oracle and the
+"""One proof over several circuits of one proving key (KZG: GWC and SHPLONK): the oracle's create_proof_multi against the pinned single-circuit proofs and the
 restated verifiers (CPU), the opening plan's circuit dimension against the restatement's lists (CPU, a sanitized program of its own), and whole proofs through
 native.Prover(num_circuits=N).create_proof_multi against the restatement byte for byte (GPU).
 
@@ -93,13 +93,16 @@ def build_case(pkg, po, co, name):
 _CASES = {}
 
 
+def case_of(pkg, po, co, name):
+    """build_case, made once per process (tests/test_oracle_variants_pinned.py shares it)"""
+    if name not in _CASES:
+        _CASES[name] = build_case(pkg, po, co, name)
+    return _CASES[name]
+
+
 @pytest.fixture(scope="module")
 def case(pkg, po, co):
-    def get(name):
-        if name not in _CASES:
-            _CASES[name] = build_case(pkg, po, co, name)
-        return _CASES[name]
-    return get
+    return lambda name: case_of(pkg, po, co, name)
 
 
 _PROOFS, _STREAMS = {}, {}
@@ -107,7 +110,6 @@ _PROOFS, _STREAMS = {}, {}
 
 def reference(po, cs, N, scheme, order=None, seed=SEED):
     """the restatement's (proof, trace) over the first N witnesses of case `cs` (or those of `order`), made once"""
-    import multi_oracle as MO
     import plonk_oracle as PO
     import proof_chains as PC
     order = tuple(order if order is not None else range(N))
@@ -115,7 +117,7 @@ def reference(po, cs, N, scheme, order=None, seed=SEED):
     if key not in _PROOFS:
         c = cs["chain"]
         stream = PO.ScalarStream(seed)
-        _PROOFS[key] = MO.create_proof_multi(po.BN254, c["srs"], c["key"], [cs["advs"][i] for i in order], [cs["insts"][i] for i in order], stream, c["rep"],
+        _PROOFS[key] = PO.create_proof_multi(po.BN254, c["srs"], c["key"], [cs["advs"][i] for i in order], [cs["insts"][i] for i in order], stream, c["rep"],
                                              PC.THREADS, scheme)
         _STREAMS[key] = stream.gen.bit_generator.state      # where the restatement's draws ended
     return _PROOFS[key]
@@ -129,58 +131,71 @@ def layout(sh, N):
     return first_eval, n_evals
 
 
+def tampered_last_circuit_evaluation(sh, N, proof):
+    """one bit of the last evaluation of the last circuit flipped: its last lookup's or permutation product's, else its last advice query"""
+    first_eval, n_evals = layout(sh, N)
+    offset = first_eval + 32 * (n_evals - 1) if (len(sh.lookups) or sh.num_sets) else first_eval + 32 * (N * len(sh.advice_queries) - 1)
+    bad = bytearray(proof)
+    bad[offset + 5] ^= 0x04
+    return bytes(bad)
+
+
 # ---- CPU: the restatement ---------------------------------------------------------------------------------------------------------------------------------
+def accepts(po, chain, proof, insts, scheme):
+    """the restated verifier of `scheme` on a proof over len(insts) circuits"""
+    import proof_chains as PC
+    return PC.accepts(po, chain, proof, insts, scheme, len(insts))
+
+
 @pytest.mark.parametrize("scheme", SCHEMES)
 @pytest.mark.parametrize("name", KZG_CHAINS)
-def test_restatement_with_one_circuit_is_the_single_circuit_oracle(po, case, name, scheme):
+def test_restatement_with_one_circuit_is_the_single_circuit_oracle(po, case, golden_loader, name, scheme):
+    """The one-circuit calls and the call over a list of one write the bytes pinned when the single-circuit and the multi-circuit restatement were two functions
+    (tests/golden/oracle_variant_proof_digests.json; under GWC also oracle_proof_digests.json's, taken from the single-circuit one alone)."""
     import plonk_oracle as PO
     import proof_chains as PC
     import shplonk_oracle as SO
     cs = case(name)
     c = cs["chain"]
+    want = golden_loader("oracle_variant_proof_digests")["multi/%s/1/%s" % (name, scheme)]
     single = SO.create_proof if scheme == "shplonk" else PO.create_proof
-    want, wtrace = single(po.BN254, c["srs"], c["key"], c["adv"], cs["insts"][0], PO.ScalarStream(SEED), c["rep"], PC.THREADS)
-    got, gtrace = reference(po, cs, 1, scheme)
-    assert got == want
-    assert gtrace["commitments"] == wtrace["commitments"] and gtrace["evals"] == wtrace["evals"] and gtrace["challenges"] == wtrace["challenges"]
+    for proof, trace in (single(po.BN254, c["srs"], c["key"], c["adv"], cs["insts"][0], PO.ScalarStream(SEED), c["rep"], PC.THREADS), reference(po, cs, 1, scheme)):
+        assert PC.digests(proof, trace) == want
+        if scheme == "gwc":
+            assert PC.digests(proof, trace) == golden_loader("oracle_proof_digests")["kzg/" + name]
 
 
 @pytest.mark.parametrize("scheme", SCHEMES)
 @pytest.mark.parametrize("N", (2, 3))
 @pytest.mark.parametrize("name", KZG_CHAINS)
 def test_restatement_proofs_are_accepted_and_tampering_rejected(po, case, name, N, scheme):
-    import multi_oracle as MO
+    import plonk_oracle as PO
     cs = case(name)
     sh = cs["chain"]["key"]["shape"]
     proof, _ = reference(po, cs, N, scheme)
     insts = cs["insts"][:N]
     other = "shplonk" if scheme == "gwc" else "gwc"
-    assert len(proof) == MO.proof_length(sh, N, scheme)
-    assert MO.accepts(po, cs["chain"], proof, insts, scheme)
-    assert not MO.accepts(po, cs["chain"], proof, insts, other), "a proof of one multiopen passes for the other's"
-    first_eval, n_evals = layout(sh, N)
-    # the last evaluation of the last circuit: its last lookup's or permutation product's, else its last advice query
-    A, L, S = sh.num_advice, len(sh.lookups), sh.num_sets
-    last_circuit_eval = first_eval + 32 * (n_evals - 1) if (L or S) else first_eval + 32 * (N * len(sh.advice_queries) - 1)
-    for offset, what in ((last_circuit_eval + 5, "an evaluation of the last circuit"), (32 * A + 3, "an advice commitment of circuit 1")):
-        bad = bytearray(proof)
-        bad[offset] ^= 0x04
-        assert not MO.accepts(po, cs["chain"], bytes(bad), insts, scheme), what
-    assert not MO.accepts(po, cs["chain"], proof + proof[-32:], insts, scheme), "32 trailing bytes"
-    assert not MO.accepts(po, cs["chain"], proof, cs["insts"][:N - 1], scheme), "one circuit fewer"
+    assert len(proof) == PO.proof_length(sh, N, scheme)
+    assert accepts(po, cs["chain"], proof, insts, scheme)
+    assert not accepts(po, cs["chain"], proof, insts, other), "a proof of one multiopen passes for the other's"
+    assert not accepts(po, cs["chain"], tampered_last_circuit_evaluation(sh, N, proof), insts, scheme), "an evaluation of the last circuit"
+    bad = bytearray(proof)
+    bad[32 * sh.num_advice + 3] ^= 0x04
+    assert not accepts(po, cs["chain"], bytes(bad), insts, scheme), "an advice commitment of circuit 1"
+    assert not accepts(po, cs["chain"], proof + proof[-32:], insts, scheme), "32 trailing bytes"
+    assert not accepts(po, cs["chain"], proof, cs["insts"][:N - 1], scheme), "one circuit fewer"
     if name == "instance_k5":
         swapped = [insts[1], insts[0]] + insts[2:]
-        assert swapped != insts and not MO.accepts(po, cs["chain"], proof, swapped, scheme), "two circuits' instance lists exchanged"
+        assert swapped != insts and not accepts(po, cs["chain"], proof, swapped, scheme), "two circuits' instance lists exchanged"
 
 
 @pytest.mark.parametrize("name", ("Rlast_k6", "instance_k5"))
 def test_swapping_two_witnesses_gives_another_accepted_proof(po, case, name):
-    import multi_oracle as MO
     cs = case(name)
     a, _ = reference(po, cs, 2, "gwc")
     b, _ = reference(po, cs, 2, "gwc", order=(1, 0))
     assert a != b and len(a) == len(b)
-    assert MO.accepts(po, cs["chain"], b, [cs["insts"][1], cs["insts"][0]], "gwc")
+    assert accepts(po, cs["chain"], b, [cs["insts"][1], cs["insts"][0]], "gwc")
 
 
 # ---- CPU: the opening plan's circuit dimension -----------------------------------------------------------------------------------------------------------
@@ -238,7 +253,7 @@ def test_opening_plan_refuses_what_it_cannot_order(plans):
 @pytest.mark.parametrize("name,N", PLAN_CASES)
 def test_opening_plan_equals_the_restatements_lists(plans, name, N):
     import ipa as IPA
-    import multi_oracle as MO
+    import plonk_oracle as PO
     shs, printed, _ = plans
     sh, P = shs[name], printed[(name, N)]
     A, NF, L, S, npc, pieces = sh.num_advice, sh.num_fixed, len(sh.lookups), sh.num_sets, len(sh.perm_columns), sh.degree - 1
@@ -264,10 +279,10 @@ def test_opening_plan_equals_the_restatements_lists(plans, name, N):
 
     assert decode(P["hpiece0"]) == (("hpiece", 0), 0)
     # ---- the transcript's order
-    W = MO.evaluation_order(sh, N)
+    W = PO.evaluation_order(sh, N)
     assert [decode(s) for s in P["write"]] == W
     # ---- the queries
-    Q = MO.symbolic_queries(sh, N)
+    Q = PO.symbolic_queries(sh, N)
     assert [(tup(q["poly"]), q["rot"]) for q in P["queries"]] == [(key, pt) for key, pt, _ in Q]
     assert [decode(q["eval"]) for q in P["queries"]] == [e for _, _, e in Q]
     assert len({q["blind"] for q in P["queries"] if tup(q["poly"])[0] not in ("fixed", "sigma")}) == len({key for key, _, _ in Q if key[0] not in ("fixed", "sigma")})
@@ -292,7 +307,7 @@ def test_opening_plan_equals_the_restatements_lists(plans, name, N):
     read = set(W) | {e for _, _, e in Q if e is not None} | {(("hpiece", i), 0) for i in range(pieces)}
     assert P["eval_wanted"] == [sum(1 << ri for ri, r in enumerate(rots) if (key, r) in read) for key in polys]
     # ---- the length of the proof
-    assert P["proof_size"] == dict(gwc=MO.proof_length(sh, N, "gwc"), shplonk=MO.proof_length(sh, N, "shplonk"))
+    assert P["proof_size"] == dict(gwc=PO.proof_length(sh, N, "gwc"), shplonk=PO.proof_length(sh, N, "shplonk"))
     if name == "R9all_k6":
         assert len(points) > 8
 
@@ -359,19 +374,19 @@ GPU_CASES = [(name, N) for name in ("maingate_k5", "Rlast_k6", "R9all_k6", "inst
 @pytest.mark.parametrize("scheme", SCHEMES)
 @pytest.mark.parametrize("name,N", GPU_CASES)
 def test_native_proof_over_several_circuits_equals_the_restatement(pkg, po, ctx, side_ctx, case, native_key, name, N, scheme, with_side):
-    import multi_oracle as MO
+    import plonk_oracle as PO
     from dehalo2_amd import native, prover
     cs = case(name)
     params, pk = native_key(name)
     want, _ = reference(po, cs, N, scheme)
     P = native.Prover(params, pk, side_ctx=side_ctx if with_side else None, multiopen=scheme, num_circuits=N)
     try:
-        assert P.proof_size() == len(want) == MO.proof_length(cs["chain"]["key"]["shape"], N, scheme)
+        assert P.proof_size() == len(want) == PO.proof_length(cs["chain"]["key"]["shape"], N, scheme)
         rng = prover.SeededRng(SEED)
         proof = P.create_proof_multi(cs["advs"][:N], cs["insts"][:N], rng).finalize()
         assert len(proof) == len(want) and not first_difference(proof, want), "proof items differ from the restatement's: %r" % first_difference(proof, want)
         assert rng.gen.bit_generator.state == _STREAMS[(name, tuple(range(N)), scheme, SEED)], "the generator is not where the restatement's draws ended"
-        assert MO.accepts(po, cs["chain"], proof, cs["insts"][:N], scheme)
+        assert accepts(po, cs["chain"], proof, cs["insts"][:N], scheme)
     finally:
         P.release()
 
@@ -380,7 +395,6 @@ def test_native_proof_over_several_circuits_equals_the_restatement(pkg, po, ctx,
 @pytest.mark.parametrize("with_side", (False, True), ids=("one_context", "side_context"))
 def test_native_proof_beyond_the_batch_tiles(pkg, po, ctx, side_ctx, case, native_key, with_side):
     """N L = 20 > 16 (the permutation's batch tile) and N (S + L) = 28 > 8 (the lookup pass's launch tile): N = 4 is the smallest N of the lookup chain past both"""
-    import multi_oracle as MO
     from dehalo2_amd import native, prover
     cs, N = case("maingate_range_k9"), 4
     sh = cs["chain"]["key"]["shape"]
@@ -391,7 +405,7 @@ def test_native_proof_beyond_the_batch_tiles(pkg, po, ctx, side_ctx, case, nativ
     try:
         proof = P.create_proof_multi(cs["advs"][:N], cs["insts"][:N], prover.SeededRng(SEED)).finalize()
         assert not first_difference(proof, want), first_difference(proof, want)
-        assert MO.accepts(po, cs["chain"], proof, cs["insts"][:N], "gwc")
+        assert accepts(po, cs["chain"], proof, cs["insts"][:N], "gwc")
     finally:
         P.release()
 
@@ -413,7 +427,6 @@ def test_native_one_circuit_through_the_multi_call_is_create_proof(pkg, po, ctx,
 
 @pytest.mark.gpu
 def test_native_two_proofs_in_a_row_and_device_entropy(pkg, po, ctx, side_ctx, case, native_key):
-    import multi_oracle as MO
     from dehalo2_amd import native, prover
     cs = case("Rlast_k6")
     params, pk = native_key("Rlast_k6")
@@ -425,7 +438,7 @@ def test_native_two_proofs_in_a_row_and_device_entropy(pkg, po, ctx, side_ctx, c
         assert P.create_proof_multi([cs["advs"][1], cs["advs"][0]], [cs["insts"][1], cs["insts"][0]], prover.SeededRng(SEED)).finalize() == second      # a fresh prover's
         assert P.create_proof_multi(cs["advs"][:2], cs["insts"][:2], prover.SeededRng(SEED)).finalize() == first
         hidden = P.create_proof_multi(cs["advs"][:2], cs["insts"][:2], None).finalize()      # device ChaCha
-        assert hidden != first and len(hidden) == len(first) and MO.accepts(po, cs["chain"], hidden, cs["insts"][:2], "gwc")
+        assert hidden != first and len(hidden) == len(first) and accepts(po, cs["chain"], hidden, cs["insts"][:2], "gwc")
     finally:
         P.release()
 
@@ -466,7 +479,7 @@ def test_native_error_table(pkg, po, co, ctx, case, native_key):
     finally:
         P2.release(); P1.release()
     # ParamsIPA, and a key with later-phase advice
-    import phased_oracle as PH
+    import phased_circuits as PH
     import pairing as pr
     ic, _ = PC.pinned_case(pkg, po, co, "ipa", "instance_k5")
     ip = native.ParamsIPA.create(ctx, pkg.fields.VESTA, 5, ic["srs"]["g"], ic["srs"]["g_lagrange"], ic["w"], ic["u"])

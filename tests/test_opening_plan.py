@@ -2,8 +2,9 @@
 
 The plan says which polynomial is opened at which rotation, in which order, under which blind, and where its evaluation lands -- for GWC, SHPLONK and IPA alike.
 tests/native_host/opening_plan_check.cpp (g++, ASan + UBSan, a program of its own) prints it for every shape below, once; here each printed plan is compared,
-by exact equality, with what oracle/plonk_oracle.py plonk_queries and oracle/ipa.py construct_intermediate_sets make of the same shape when commitments are
-their keys, points their rotations and evaluations the pairs (key, rotation).  The transcript's write order, the layouts and the proof sizes are this file's
+by exact equality, with what oracle/plonk_oracle.py symbolic_queries (plonk_queries with commitments their keys, points their rotations and evaluations the pairs
+(key, rotation)) and oracle/ipa.py construct_intermediate_sets make of the same shape.  The oracle keys what a circuit has of its own (name, circuit, index):
+the printed (name, index) are read as circuit 0's.  The transcript's write order, the layouts and the proof sizes are this file's
 own statement of upstream's."""
 import json
 import os
@@ -66,44 +67,34 @@ def plans(pkg, po):
     return {case: (shs[case[0]], plan) for case, plan in zip(CASES, printed)}
 
 
+OWN = ("instance", "advice", "perm_z", "lookup_a", "lookup_s", "lookup_z")      # a circuit's own: keyed (name, circuit, index)
+
+
 def tup(x):
-    return tuple(tup(v) for v in x) if isinstance(x, list) else x
-
-
-def oracle_queries(sh, ipa):
-    """plonk_queries with keys for commitments, rotations for points and (key, rotation) for evaluations (None: the folded h's)"""
-    import plonk_oracle as PO
-    L, S, last = len(sh.lookups), sh.num_sets, -(sh.blinding_factors + 1)
-    C = {"instance": [("instance", c) for c in range(sh.num_instance)], "advice": [("advice", c) for c in range(sh.num_advice)],
-         "perm_z": [("perm_z", s) for s in range(S)], "lookup_permuted": [(("lookup_a", l), ("lookup_s", l)) for l in range(L)],
-         "lookup_z": [("lookup_z", l) for l in range(L)], "fixed": [("fixed", c) for c in range(sh.num_fixed)],
-         "sigma": [("sigma", j) for j in range(len(sh.perm_columns))], "h": ("h",), "random": ("random",)}
-    E = {"instance": [(("instance", c), r) for c, r in sh.instance_queries] if ipa else [],
-         "advice": [(("advice", c), r) for c, r in sh.advice_queries], "fixed": [(("fixed", c), r) for c, r in sh.fixed_queries],
-         "perm": [tuple((("perm_z", s), r) for r in (0, 1, last)) for s in range(S)],
-         "lookup": [((("lookup_z", l), 0), (("lookup_z", l), 1), (("lookup_a", l), 0), (("lookup_a", l), -1), (("lookup_s", l), 0)) for l in range(L)],
-         "sigma": [(("sigma", j), 0) for j in range(len(sh.perm_columns))], "h": None, "random": (("random",), 0)}
-    Q = PO.plonk_queries(sh, rotate=lambda r: r, x=0, C=C, E=E)
-    assert all(key == item for key, _, item, _ in Q)
-    return [(key, pt, e) for key, pt, _, e in Q]
+    """a printed value as the oracle spells it: lists are tuples, a circuit's own polynomial is circuit 0's"""
+    if not isinstance(x, list):
+        return x
+    x = tuple(tup(v) for v in x)
+    return (x[0], 0) + x[1:] if x and x[0] in OWN else x
 
 
 def transcript_order(sh, ipa):
     """upstream's order of the evaluations in the proof, as (key, rotation): the instance queries, then the rest"""
     L, S, last = len(sh.lookups), sh.num_sets, -(sh.blinding_factors + 1)
-    inst = [(("instance", c), r) for c, r in sh.instance_queries] if ipa else []
-    W = [(("advice", c), r) for c, r in sh.advice_queries] + [(("fixed", c), r) for c, r in sh.fixed_queries] + [(("random",), 0)]
+    inst = [(("instance", 0, c), r) for c, r in sh.instance_queries] if ipa else []
+    W = [(("advice", 0, c), r) for c, r in sh.advice_queries] + [(("fixed", c), r) for c, r in sh.fixed_queries] + [(("random",), 0)]
     W += [(("sigma", j), 0) for j in range(len(sh.perm_columns))]
     for s in range(S):
-        W += [(("perm_z", s), 0), (("perm_z", s), 1)] + ([(("perm_z", s), last)] if s != S - 1 else [])
+        W += [(("perm_z", 0, s), 0), (("perm_z", 0, s), 1)] + ([(("perm_z", 0, s), last)] if s != S - 1 else [])
     for l in range(L):
-        W += [(("lookup_z", l), 0), (("lookup_z", l), 1), (("lookup_a", l), 0), (("lookup_a", l), -1), (("lookup_s", l), 0)]
+        W += [(("lookup_z", 0, l), 0), (("lookup_z", 0, l), 1), (("lookup_a", 0, l), 0), (("lookup_a", 0, l), -1), (("lookup_s", 0, l), 0)]
     return inst, W
 
 
 @pytest.mark.parametrize("name,scheme", CASES)
 def test_opening_plan_equals_the_oracles(plans, name, scheme):
     import ipa as IPA
+    import plonk_oracle as PO
     sh, P = plans[(name, scheme)]
     ipa = scheme == "ipa"
     if name == "rotations_33":
@@ -115,18 +106,18 @@ def test_opening_plan_equals_the_oracles(plans, name, scheme):
 
     # ---- layouts: columns, polynomial numbering, blinds
     assert P["columns"] == dict(o_adv=0, o_perm=A, o_pz=A + 2 * L, o_lz=A + 2 * L + S, o_rand=A + 3 * L + S, NC=A + 3 * L + S + 1)
-    polys = [("advice", c) for c in range(A)] + [(kind, l) for l in range(L) for kind in ("lookup_a", "lookup_s")] + [("perm_z", s) for s in range(S)]
-    polys += [("lookup_z", l) for l in range(L)] + [("random",)] + [("fixed", c) for c in range(NF)] + [("sigma", j) for j in range(npc)]
-    polys += [("hpiece", i) for i in range(pieces)] + ([("instance", c) for c in range(I)] if ipa else [])
+    polys = [("advice", 0, c) for c in range(A)] + [(kind, 0, l) for l in range(L) for kind in ("lookup_a", "lookup_s")] + [("perm_z", 0, s) for s in range(S)]
+    polys += [("lookup_z", 0, l) for l in range(L)] + [("random",)] + [("fixed", c) for c in range(NF)] + [("sigma", j) for j in range(npc)]
+    polys += [("hpiece", i) for i in range(pieces)] + ([("instance", 0, c) for c in range(I)] if ipa else [])
     assert [tup(k) for k in P["polys"]] == polys + [("h",)] and P["num_polys"] == len(polys)
     B = dict(bi_adv=0, bi_perm=A, bi_prod=A + 2 * L, bi_rand=A + 3 * L + S)
     B.update(bi_h=B["bi_rand"] + 1, bi_hfold=B["bi_rand"] + 1 + pieces, bi_f=B["bi_rand"] + 2 + pieces, bi_def=B["bi_rand"] + 3 + pieces, bi_count=B["bi_rand"] + 3 + pieces + max(I, 1))
     assert P["blinds"] == B
-    hiding = {("advice", c): c for c in range(A)}
-    hiding.update({("lookup_a", l): A + 2 * l for l in range(L)})
-    hiding.update({("lookup_s", l): A + 2 * l + 1 for l in range(L)})
-    hiding.update({("perm_z", s): B["bi_prod"] + s for s in range(S)})
-    hiding.update({("lookup_z", l): B["bi_prod"] + S + l for l in range(L)})
+    hiding = {("advice", 0, c): c for c in range(A)}
+    hiding.update({("lookup_a", 0, l): A + 2 * l for l in range(L)})
+    hiding.update({("lookup_s", 0, l): A + 2 * l + 1 for l in range(L)})
+    hiding.update({("perm_z", 0, s): B["bi_prod"] + s for s in range(S)})
+    hiding.update({("lookup_z", 0, l): B["bi_prod"] + S + l for l in range(L)})
     hiding.update({("random",): B["bi_rand"], ("h",): B["bi_hfold"]})
     hiding.update({("hpiece", i): B["bi_h"] + i for i in range(pieces)})
     assert len(set(hiding.values()) | {B["bi_f"], B["bi_def"]}) == len(hiding) + 2 and max(hiding.values()) < B["bi_f"] < B["bi_def"] < B["bi_count"]
@@ -149,7 +140,7 @@ def test_opening_plan_equals_the_oracles(plans, name, scheme):
     assert decode(P["hpiece0"]) == (("hpiece", 0), 0)
 
     # ---- the queries
-    Q = oracle_queries(sh, ipa)
+    Q = PO.symbolic_queries(sh, 1, ipa)
     assert [(tup(q["poly"]), q["rot"]) for q in P["queries"]] == [(key, pt) for key, pt, _ in Q]
     assert [decode(q["eval"]) for q in P["queries"]] == [e for _, _, e in Q]
     assert [q["blind"] for q in P["queries"]] == [blind_of(key) for key, _, _ in Q]

@@ -1,6 +1,6 @@
 """Circuits with later-phase advice columns and challenges (halo2's Challenge API): whole proofs under KZG (GWC, SHPLONK) and IPA, and the witness check.
 
-The circuits, their witness and the restatements' phase loop live in tests/phased_oracle.py.
+The circuits and their witness live in tests/phased_circuits.py; the phase loop is the oracle's.
 CPU: the restatement's RLC3 proof is accepted under both schemes, a tampered evaluation and a witness made with a wrong c0 are rejected; the new expression
 node has degree 0; the descriptor of a circuit without phases is what it was.
 GPU: dehalo_create_proof_phased byte for byte against the restatement, the phase-major order, single-phase equivalence with dehalo_create_proof,
@@ -9,40 +9,44 @@ import hashlib
 
 import pytest
 
-import phased_oracle as PH
+import phased_circuits as PH
+import proof_chains as PC
+
+
+_CHAINS = {}      # made once per process (tests/test_oracle_variants_pinned.py shares them)
+
+
+def chain_of(pkg, po, co, scheme, k):
+    """the RLC3 chain with `want`, `trace`, `challenges`: the restatement's proof under ScalarStream(7)"""
+    if (scheme, k) not in _CHAINS:
+        c = PH.chain(pkg, po, co, scheme, k)
+        p = c["curve"].scalar.p
+        c["p"], c["usable"] = p, c["key"]["shape"].usable
+        c["want"], c["trace"] = PC.prove_circuits(po, c, [PH.mont_witness(po, co, c, PH.witness(p, k, c["usable"]))], [[]])
+        c["challenges"] = c["trace"]["phase_challenges"]
+        _CHAINS[(scheme, k)] = c
+    return _CHAINS[(scheme, k)]
 
 
 @pytest.fixture(scope="module")
 def chains(pkg, po, co):
-    """(scheme, k) -> the RLC3 chain with `want`, `trace`, `challenges`: the restatement's proof under ScalarStream(7), computed once"""
-    cache = {}
-
-    def get(scheme, k):
-        if (scheme, k) not in cache:
-            c = PH.chain(pkg, po, co, scheme, k)
-            p = c["curve"].scalar.p
-            c["p"], c["usable"] = p, c["key"]["shape"].usable
-            c["want"], c["trace"], c["challenges"] = PH.prove(po, co, c, PH.witness(p, k, c["usable"]))
-            cache[(scheme, k)] = c
-        return cache[(scheme, k)]
-
-    return get
+    return lambda scheme, k: chain_of(pkg, po, co, scheme, k)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ CPU
 @pytest.mark.parametrize("scheme", ["kzg", "ipa"])
 def test_restatement_proves_rlc3(pkg, po, co, chains, scheme):
     c = chains(scheme, 5)
-    assert PH.recover(po, c, c["want"]) == c["challenges"] and len(set(c["challenges"])) == 3 and 0 not in c["challenges"]
-    assert PH.accepts(po, c, c["want"])
-    assert not PH.accepts(po, c, PH.tampered(c, c["want"]))
+    assert PC.phase_challenges(po, c, c["want"]) == c["challenges"] and len(set(c["challenges"])) == 3 and 0 not in c["challenges"]
+    assert PC.accepts(po, c, c["want"], [])
+    assert not PC.accepts(po, c, PC.tampered(c, c["want"]), [])
 
 
 @pytest.mark.parametrize("scheme", ["kzg", "ipa"])
 def test_restatement_rejects_r_made_with_a_wrong_c0(pkg, po, co, chains, scheme):
     c = chains(scheme, 5)
-    bad, _, _ = PH.prove(po, co, c, PH.witness(c["p"], 5, c["usable"], wrong_c0=True))
-    assert not PH.accepts(po, c, bad)
+    bad, _ = PC.prove_circuits(po, c, [PH.mont_witness(po, co, c, PH.witness(c["p"], 5, c["usable"], wrong_c0=True))], [[]])
+    assert not PC.accepts(po, c, bad, [])
 
 
 def test_a_challenge_has_degree_zero(pkg, po):
@@ -51,7 +55,8 @@ def test_a_challenge_has_degree_zero(pkg, po):
     for name in ("RLC3", "RLC3perm"):
         cs = PH.build_cs(pkg, name)
         assert plonk.degree(("challenge", 0)) == 0
-        sh = PO.Shape(PH.substituted_description(cs, [5, 6, 7]), 5, po.BN254.scalar)
+        sh = PO.Shape(PO.describe(cs), 5, po.BN254.scalar)
+        assert PO.expr_degree(("challenge", 0)) == 0 and (sh.phases, sh.challenge_phases) == (tuple(cs.phases()), (0, 1, 2))
         assert (cs.degree(), cs.blinding_factors()) == (sh.degree, sh.blinding_factors) == (4, 5)
         assert len(cs.description()) == 10 and cs.num_phases() == 3 and cs.challenge_phases == [0, 1, 2]
     assert PH.build_cs(pkg, "RLC3").phases() == [0, 0, 1, 1, 2] and PH.build_cs(pkg, "RLC3perm").phases() == [1, 0, 2, 0, 1]
@@ -91,12 +96,12 @@ def test_descriptor_of_a_circuit_without_phases_is_unchanged(pkg):
 
 # ------------------------------------------------------------------------------------------------------------------------------ GPU
 def _mont_witness(po, co, c, k, name="RLC3", log=None):
-    fn = PH.witness(c["p"], k, c["usable"], name)
+    fn = PH.mont_witness(po, co, c, PH.witness(c["p"], k, c["usable"], name))
 
     def wfn(phase, challenges):
         if log is not None:
             log.append((phase, list(challenges)))
-        return PH.to_mont(co, c["curve"], po, fn(phase, challenges))
+        return fn(phase, challenges)
 
     return wfn
 
@@ -137,8 +142,8 @@ def test_native_phased_proof_is_the_restatements(pkg, po, co, ctx, chains, schem
     assert len(proof) == P.proof_size() == len(want)
     diff = _items_differing(proof, want)
     assert not diff, "proof items differ from the restatement's: %r" % diff[:8]
-    assert PH.accepts(po, c, proof) and not PH.accepts(po, c, PH.tampered(c, proof))
-    c0, c1, _ = PH.recover(po, c, proof)
+    assert PC.accepts(po, c, proof, []) and not PC.accepts(po, c, PC.tampered(c, proof), [])
+    c0, c1, _ = PC.phase_challenges(po, c, proof)
     assert log == [(0, [0, 0, 0]), (1, [c0, 0, 0]), (2, [c0, c1, 0])]
     assert P.create_proof_phased(_mont_witness(po, co, c, k), [], prover.SeededRng(7)).finalize() == want      # the prover's buffers are clean for the next proof
     P.release(); pk.release(); params.release()

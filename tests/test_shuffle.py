@@ -1,8 +1,8 @@
 """The shuffle argument (ConstraintSystem::shuffle of halo2_proofs v0.3.0): whole proofs under KZG (GWC, SHPLONK) and IPA, the quotient kernel, the host logic.
 
-The circuits, their witnesses and the restatement (prover and the verifiers' PLONK part) live in tests/shuffle_oracle.py.
-CPU: the restatement's proofs are accepted by its verifiers, a tampered product evaluation and a witness that is no shuffle are rejected, without shuffles the
-bytes are plonk_oracle's; HostCS and OpeningPlan through tests/native_host/shuffle_cs_check.cpp (g++, ASan + UBSan); the proof-size formulas.
+The circuits and their witnesses live in tests/shuffle_circuits.py; the restatement (prover and the verifiers' PLONK part) is the oracle's.
+CPU: the restatement's proofs are accepted by its verifiers, a tampered product evaluation and a witness that is no shuffle are rejected, under a description
+that carries no shuffle the bytes are the pinned ones; HostCS and OpeningPlan through tests/native_host/shuffle_cs_check.cpp (g++, ASan + UBSan); the proof-size formulas.
 GPU: device proofs byte for byte against the restatement under all three multiopens, through create_proof, create_proof_multi and create_proof_phased;
 DEHALO_ERR_SHUFFLE; dehalo_shuffle_h_batch_device against Python integers."""
 import json
@@ -15,39 +15,41 @@ import pytest
 import __graft_entry__ as entry
 
 entry.load_oracle()      # (puts oracle/ on the path: the restatement below imports it)
-import shuffle_oracle as SO  # noqa: E402
+import phased_circuits as PH  # noqa: E402
+import plonk_oracle as PO  # noqa: E402
+import shuffle_circuits as SO  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CIRCUITS = [("SHUF1", 5), ("SHUF2", 6), ("SHUF5", 5), ("SHUFRLC", 5)]
 K_OF = dict(CIRCUITS)
 
 
+_CHAINS, _PROOFS = {}, {}      # made once per process (tests/test_oracle_variants_pinned.py shares them)
+
+
+def chain_of(pkg, po, co, scheme, name):
+    if (scheme, name) not in _CHAINS:
+        _CHAINS[(scheme, name)] = SO.chain(pkg, po, co, scheme, name, K_OF[name])
+    return _CHAINS[(scheme, name)]
+
+
+def proof_of(pkg, po, co, scheme, multiopen, name, circuits=1):
+    """-> (proof, trace) of the restatement under ScalarStream(7)"""
+    key = (scheme, multiopen, name, circuits)
+    if key not in _PROOFS:
+        c = chain_of(pkg, po, co, scheme, name)
+        _PROOFS[key] = SO.prove(po, co, c, witnesses_of(c, circuits), multiopen)
+    return _PROOFS[key]
+
+
 @pytest.fixture(scope="module")
 def chains(pkg, po, co):
-    """(scheme, name) -> the chain, computed once"""
-    cache = {}
-
-    def get(scheme, name):
-        if (scheme, name) not in cache:
-            cache[(scheme, name)] = SO.chain(pkg, po, co, scheme, name, K_OF[name])
-        return cache[(scheme, name)]
-
-    return get
+    return lambda scheme, name: chain_of(pkg, po, co, scheme, name)
 
 
 @pytest.fixture(scope="module")
-def proofs(po, co, chains):
-    """(scheme, multiopen, name, circuits) -> (proof, trace) of the restatement under ScalarStream(7), computed once"""
-    cache = {}
-
-    def get(scheme, multiopen, name, circuits=1):
-        key = (scheme, multiopen, name, circuits)
-        if key not in cache:
-            c = chains(scheme, name)
-            cache[key] = SO.prove(po, co, c, witnesses_of(c, circuits), multiopen)
-        return cache[key]
-
-    return get
+def proofs(pkg, po, co):
+    return lambda scheme, multiopen, name, circuits=1: proof_of(pkg, po, co, scheme, multiopen, name, circuits)
 
 
 def witnesses_of(c, circuits=1, bad=False):
@@ -70,7 +72,7 @@ def test_restatement_proves_and_verifies(po, co, chains, proofs, scheme, multiop
     proof, trace = proofs(scheme, multiopen, name)
     sh = c["key"]["shape"]
     assert all(all(row) for row in trace["shuffles_closed"])
-    assert len(proof) == SO.proof_length(sh, 1, "ipa" if scheme == "ipa" else multiopen)
+    assert len(proof) == PO.proof_length(sh, 1, "ipa" if scheme == "ipa" else multiopen)
     assert SO.accepts(po, c, proof, 1, multiopen)
     assert not SO.accepts(po, c, SO.tampered_product_evaluation(c, proof), 1, multiopen)
 
@@ -88,24 +90,24 @@ def test_restatement_rejects_a_witness_that_is_no_shuffle(po, co, chains, scheme
 def test_restatement_over_two_circuits(po, co, chains, proofs, multiopen):
     c = chains("kzg", "SHUF2")
     proof, _ = proofs("kzg", multiopen, "SHUF2", 2)
-    assert len(proof) == SO.proof_length(c["key"]["shape"], 2, multiopen)
+    assert len(proof) == PO.proof_length(c["key"]["shape"], 2, multiopen)
     assert SO.accepts(po, c, proof, 2, multiopen)
     assert not SO.accepts(po, c, SO.tampered_product_evaluation(c, proof, 2), 2, multiopen)
     assert not SO.accepts(po, c, proof, 1, multiopen)
 
 
 @pytest.mark.parametrize("scheme", ["kzg", "ipa"])
-def test_without_shuffles_the_bytes_are_plonk_oracles(pkg, po, co, scheme):
+def test_without_shuffles_the_bytes_are_plonk_oracles(pkg, po, co, golden_loader, scheme):
+    """R9all through the call over a list of circuits, its description carried as a Desc without shuffles: the proof pinned from the single-circuit
+    restatement when it knew no shuffle (tests/golden/oracle_proof_digests.json)"""
     import proof_chains as PC
     c, inst = PC.pinned_case(pkg, po, co, scheme, "R9all_k6")
     assert inst == []
-    want, _ = PC.prove(po, c, inst)
-    import plonk_oracle as PO
     curve = po.VESTA if scheme == "ipa" else po.BN254
-    key = dict(c["key"], shape=SO.ShuffleShape(SO.Desc(c["desc"]), c["k"], curve.scalar))
-    assert key["shape"].degree == c["key"]["shape"].degree
-    got, _ = SO.create_proof(curve, c["srs"], key, [c["adv"]], PO.ScalarStream(7), c["rep"], PC.THREADS, SO._scheme(po, c, "gwc"))
-    assert got == want
+    key = dict(c["key"], shape=PO.Shape(PO.Desc(c["desc"]), c["k"], curve.scalar))
+    assert key["shape"].degree == c["key"]["shape"].degree and key["shape"].shuffles == ()
+    got, trace = PO.create_proof_multi(curve, c["srs"], key, [c["adv"]], [[]], PO.ScalarStream(7), c["rep"], PC.THREADS, PC.scheme_of(po, c))
+    assert PC.digests(got, trace) == golden_loader("oracle_proof_digests")["%s/R9all_k6" % scheme]
 
 
 def test_degrees_and_sizes(pkg, po):
@@ -114,12 +116,12 @@ def test_degrees_and_sizes(pkg, po):
     want = {"SHUF1": (3, 5), "SHUF2": (4, 5), "SHUF5": (5, 5), "SHUFRLC": (3, 5)}
     for name, k in CIRCUITS:
         cs = SO.build(pkg, name, k)["cs"]
-        sh = SO.ShuffleShape(SO.description(cs, [0] * len(cs.challenge_phases)), k, po.BN254.scalar)
+        sh = PO.Shape(PO.describe(cs), k, po.BN254.scalar)
         assert (cs.degree(), cs.blinding_factors()) == (sh.degree, sh.blinding_factors) == want[name], name
         head, evals = prover.proof_layout(cs)
         for scheme in ("gwc", "shplonk"):
-            groups = 2 if scheme == "shplonk" else len({pt for _, pt, _ in SO.symbolic_queries(sh, 1)})
-            assert 32 * (head + evals + groups) == SO.proof_length(sh, 1, scheme)
+            groups = 2 if scheme == "shplonk" else len({pt for _, pt, _ in PO.symbolic_queries(sh, 1)})
+            assert 32 * (head + evals + groups) == PO.proof_length(sh, 1, scheme)
     # a shuffle's degree rule on its own: max(2 + inputs, 2 + shuffle side), either at least 1
     cs = P.ConstraintSystem(num_advice=2)
     cs.shuffle([(("const", 3), ("const", 4))])
@@ -160,7 +162,7 @@ def test_opening_plan_with_shuffles(pkg, po, circuits):
         if scheme == "ipa" and circuits > 1:
             continue
         cs = SO.build(pkg, name, K_OF[name])["cs"]
-        sh = SO.ShuffleShape(SO.description(cs), K_OF[name], (po.VESTA if scheme == "ipa" else po.BN254).scalar)
+        sh = PO.Shape(PO.describe(cs), K_OF[name], (po.VESTA if scheme == "ipa" else po.BN254).scalar)
         L, S, H = len(sh.lookups), sh.num_sets, len(sh.shuffles)
         q = lambda lst: "%d %s" % (len(lst), " ".join("%d %d" % (c, r) for c, r in lst))
         line = "%d %d %d %d %d %d %d %d %d %d %d %d %s %s %s\n" % (circuits, H, sh.k, sh.num_advice, sh.num_fixed, 0, L, S, len(sh.perm_columns), sh.blinding_factors,
@@ -169,23 +171,22 @@ def test_opening_plan_with_shuffles(pkg, po, circuits):
         assert run.returncode == 0, run.stdout + run.stderr
         plan = json.loads(run.stdout)
         norm = lambda v: tuple(norm(i) for i in v) if isinstance(v, list) else v
-        want_q = [(key, rot, ev) for key, rot, ev in SO.symbolic_queries(sh, circuits)]
+        want_q = [(key, rot, ev) for key, rot, ev in PO.symbolic_queries(sh, circuits)]
         got_q = [(norm(qq["poly"]), qq["rot"], (norm(qq["eval"][0]), qq["eval"][1]) if qq["eval"] else None) for qq in plan["queries"]]
         assert got_q == want_q, name
-        assert [(norm(w[0]), w[1]) for w in plan["write"]] == SO.evaluation_order(sh, circuits), name
+        assert [(norm(w[0]), w[1]) for w in plan["write"]] == PO.evaluation_order(sh, circuits), name
         order = [("perm_z", c, s) for c in range(circuits) for s in range(S)] + [("lookup_z", c, l) for c in range(circuits) for l in range(L)]
         order += [("shuffle_z", c, j) for c in range(circuits) for j in range(H)] + [("random",)]
         assert [norm(k) for k in plan["product_order"]] == order, name
         mo = {"gwc": "gwc", "shplonk": "shplonk", "ipa": "ipa"}
         for scheme_name in (("ipa",) if scheme == "ipa" else ("gwc", "shplonk")):
-            assert plan["proof_size"][mo[scheme_name]] == SO.proof_length(sh, circuits, scheme_name), (name, scheme_name)
+            assert plan["proof_size"][mo[scheme_name]] == PO.proof_length(sh, circuits, scheme_name), (name, scheme_name)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ GPU, whole proofs
 def _native(pkg, ctx, po, c):
     """-> (params, pk) of the chain's SRS and circuit, vk checked against the restatement's, transcript_repr set"""
     import pairing as pr
-    import plonk_oracle as PO
     from dehalo2_amd import native
     k, circ = c["k"], c["circ"]
     if "u" in c:
@@ -204,16 +205,11 @@ def _items_differing(got, want):
     return [i // 32 for i in range(0, max(len(got), len(want)), 32) if got[i:i + 32] != want[i:i + 32]]
 
 
-def _mont_fn(po, co, c, fn):
-    import phased_oracle as PH
-    return lambda phase, challenges: PH.to_mont(co, c["curve"], po, fn(phase, challenges))
-
-
 def _device_proof(po, co, c, P, bad=False):
     from dehalo2_amd import prover
     w = witnesses_of(c, bad=bad)
     if callable(w):
-        return P.create_proof_phased(_mont_fn(po, co, c, w), [], prover.SeededRng(7)).finalize()
+        return P.create_proof_phased(PH.mont_witness(po, co, c, w), [], prover.SeededRng(7)).finalize()
     return P.create_proof(w[0], [], prover.SeededRng(7), canonical=True).finalize()
 
 
@@ -431,7 +427,6 @@ def test_check_witness_shuffle_reading_a_challenge(pkg, po, co, ctx, chains):
 @pytest.mark.gpu
 def test_batch_mode_proves_shuffles(pkg, po, co, ctx, chains, proofs):
     """dehalo_create_proofs: two proofs of SHUF2 on one prover, each the restatement's"""
-    import phased_oracle as PH
     from dehalo2_amd import native, prover
     c = chains("kzg", "SHUF2")
     want, _ = proofs("kzg", "gwc", "SHUF2")

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The parent commit's tree (tools/ab/parent: `git archive HEAD~ | tar -x -C tools/ab/parent`, then `make` in it) against this one on ONE box, alternating pairs
 # (default five): bench.py's delay_enc_k17_ms and the k = 14 / 20 delay_enc proofs -- what a change to the prover's host code must leave alone.  Then the cost of an
-# advice phase (RLC3 of tests/phased_oracle.py at k = 17).  Every step has its own time limit; the first failure ends the script.
+# advice phase (RLC3 of tests/phased_circuits.py at k = 17).  Every step has its own time limit; the first failure ends the script.
 #   bash tools/ab_parent.sh [pairs]     -> build/ab/ab_parent_vs_this.txt, build/ab/rlc3_k17_phases.txt (build/ is ignored by git; the kept copies live in profiles/)
 set -o pipefail
 mkdir -p build/ab

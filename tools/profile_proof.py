@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-phase timings of the device create_proof (steady state).   python tools/profile_proof.py [k] [range_lookups] [reps]
-Cost of an advice phase (dehalo_create_proof_phased on the three-phase circuit RLC3 of tests/phased_oracle.py):   python tools/profile_proof.py rlc3 [k] [reps]"""
+Cost of an advice phase (dehalo_create_proof_phased on the three-phase circuit RLC3 of tests/phased_circuits.py):   python tools/profile_proof.py rlc3 [k] [reps]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,7 +17,7 @@ from dehalo2_amd import circuits, prover, keygen, transcript
 def profile_phases(k, reps):
     """RLC3 through the native prover, every phase's witness resident on the device beforehand (same seed, so the same challenges: the callback only returns a
     pointer).  The callback of phase p runs right behind the commitments and squeezes of phase p - 1, so the gaps between callbacks are the phases' own times."""
-    import phased_oracle as PH
+    import phased_circuits as PH
     from dehalo2_amd import native
     curve = pkg.fields.BN254
     p = curve.scalar.p
