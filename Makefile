@@ -65,4 +65,9 @@ clean:
 shuffle_cs_check: tests/native_host/shuffle_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/opening_plan.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/shuffle_cs_check tests/native_host/shuffle_cs_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check
+# the acceptance step of the ChaCha20 generator kinds (csrc/hostrng.hpp, shared by the host and the kernel) on crafted candidates, and HostRng's keyed kind,
+# under ASan + UBSan (tests/test_rng_chacha.py)
+hostrng_check: tests/native_host/hostrng_check.cpp $(CSRC)/hostrng.hpp $(CSRC)/hostfield.hpp include/dehalo.h
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/hostrng_check tests/native_host/hostrng_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check

@@ -26,7 +26,7 @@ SYMBOLS = [
     "dehalo_lincomb_device", "dehalo_scale_device", "dehalo_kate_division", "dehalo_kate_division_device", "dehalo_kate_division_batch_device", "dehalo_vanishing_quotient_batch_device",
     "dehalo_params_create", "dehalo_params_setup", "dehalo_bases_register_device", "dehalo_params_read", "dehalo_params_size", "dehalo_params_write", "dehalo_params_release", "dehalo_params_commit_device",
     "dehalo_create_proof_circuit", "dehalo_create_proofs_circuit", "dehalo_keygen", "dehalo_pk_read", "dehalo_pk_size", "dehalo_pk_write", "dehalo_vk_size", "dehalo_vk_write", "dehalo_pk_set_transcript_repr",
-    "dehalo_pk_get_transcript_repr", "dehalo_pk_info", "dehalo_pk_release", "dehalo_rng_scalars", "dehalo_field_info", "dehalo_synthesize",
+    "dehalo_pk_get_transcript_repr", "dehalo_pk_info", "dehalo_pk_release", "dehalo_rng_scalars", "dehalo_rng_scalars_device", "dehalo_field_info", "dehalo_synthesize",
     "dehalo_transcript_create", "dehalo_transcript_common_scalar", "dehalo_transcript_write_scalar", "dehalo_transcript_write_point",
     "dehalo_transcript_squeeze_challenge", "dehalo_transcript_len", "dehalo_transcript_finalize", "dehalo_transcript_release",
     "dehalo_prover_create", "dehalo_prover_release", "dehalo_create_proof", "dehalo_prover_set_shard", "dehalo_prover_last_timings", "dehalo_create_proofs", "dehalo_prover_set_multiopen",
@@ -275,6 +275,7 @@ def load_library():
     lib.dehalo_synthesize.argtypes = [C.POINTER(CCircuitInputs), u64p, u64p, u64p, C.POINTER(C.c_void_p), C.POINTER(CSynthesisInfo)]
     lib.dehalo_field_info.argtypes = [C.c_int, u64p]
     lib.dehalo_rng_scalars.argtypes = [C.POINTER(CRng), C.c_int, C.c_uint64, u64p, sz]
+    lib.dehalo_rng_scalars_device.argtypes = [P, C.POINTER(CRng), C.c_int, C.c_uint64, u64p, sz, P]
     lib.dehalo_ipa_open.argtypes = [P, P, u64p, u64p, u64p, C.POINTER(CRng), P]
     lib.dehalo_transcript_create.argtypes = [C.c_int, PP]
     lib.dehalo_transcript_common_scalar.argtypes = [P, u64p]
@@ -507,6 +508,10 @@ class Context:
         h = C.c_void_p()
         self._check(self.lib.dehalo_fixed_base_create(self.handle, curve, _ptr(a), C.byref(h)))
         return FixedBase(self, h, curve)
+
+    def rng_scalars_device(self, rng: "CRng", field: int, cha_stream: int, d_out: int, n: int, stream: int = 0):
+        """d_out[0 .. n) = the indexed ChaCha20 draw of stream `cha_stream` under rng's key (a DEHALO_RNG_CHACHA20 struct: native.rng_struct(prover.KeyedRng(key)))"""
+        self._check(self.lib.dehalo_rng_scalars_device(self.handle, C.byref(rng) if rng is not None else None, field, cha_stream, d_out or None, n, stream or None))
 
     def to_affine_device(self, curve: int, d_jacobian: int, count: int, d_affine: int, stream: int = 0):
         self._check(self.lib.dehalo_to_affine_device(self.handle, curve, d_jacobian, count, d_affine, stream or None))

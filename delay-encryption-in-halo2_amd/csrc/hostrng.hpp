@@ -6,7 +6,10 @@
 //   DEHALO_RNG_PCG64     TESTS / BENCHMARKS ONLY (not a CSPRNG): numpy's PCG64 stream from a given state, four 64-bit outputs per scalar,
 //                        top word masked to 61 bits -- the stream dehalo2_amd.prover.SeededRng and the CPU restatement consume, so that
 //                        proofs can be compared byte for byte;
-//   DEHALO_RNG_CALLBACK  the caller's own generator.
+//   DEHALO_RNG_CALLBACK  the caller's own generator;
+//   DEHALO_RNG_CHACHA20  the DEHALO_RNG_OS generator with the caller's key instead of 32 bytes of operating-system entropy: reproducible, and as
+//                        strong as the key.  From the key on the two kinds are ONE path (HostRng::chacha()); the schedule of their draws is written
+//                        down in include/dehalo.h (dehalo_rng_kind).
 // A scalar is handed over as a Montgomery REPRESENTATION (multiplication by R is a bijection of the field: uniform stays uniform).
 #pragma once
 #include <sys/random.h>
@@ -18,6 +21,26 @@
 #include "hostfield.hpp"
 
 typedef unsigned __int128 u128;
+
+#ifdef __HIPCC__
+#define DH_HOST_DEVICE __host__ __device__
+#define DH_UNROLL _Pragma("unroll")
+#else
+#define DH_HOST_DEVICE
+#define DH_UNROLL
+#endif
+
+// From 256 candidate bits to a scalar -- the one acceptance step of the ChaCha20 kinds, on the host (HostRng::scalars) and in the kernel
+// (k_chacha_scalars, params.hip): v = eight 32-bit words, least significant first, is masked to the modulus' `bits` (225 .. 256) and accepted iff
+// the masked value is < p.  v holds the masked value afterwards either way.
+DH_HOST_DEVICE inline bool chacha_accept(uint32_t v[8], const uint32_t p[8], uint32_t bits) {
+    if (bits < 256) v[7] &= ((uint32_t)1 << (bits - 224)) - 1;
+    bool below = false, decided = false;
+    DH_UNROLL
+    for (int j = 7; j >= 0; j--)
+        if (!decided && v[j] != p[j]) { below = v[j] < p[j]; decided = true; }
+    return below;
+}
 
 struct Pcg64 {
     u128 state, inc;
@@ -86,16 +109,24 @@ struct HostRng {
     uint64_t position = 0;
     dehalo_rng* caller = nullptr;      // PCG64: the caller's state is advanced when the proof is done
 
+    // the two ChaCha20 kinds: they differ in where init takes `key` from and in nothing else
+    bool chacha() const { return kind == DEHALO_RNG_OS || kind == DEHALO_RNG_CHACHA20; }
+
     int init(const dehalo_rng* r, const HostField* field) {
         f = field;
         kind = r ? r->kind : DEHALO_RNG_OS;
         position = 0;
-        if (kind == DEHALO_RNG_OS) {
-            size_t got = 0;
-            while (got < 32) {
-                const ssize_t n = getrandom(key + got, 32 - got, 0);
-                if (n <= 0) return DEHALO_ERR_UNSUPPORTED;
-                got += (size_t)n;
+        if (chacha()) {
+            if (kind == DEHALO_RNG_OS) {
+                size_t got = 0;
+                while (got < 32) {
+                    const ssize_t n = getrandom(key + got, 32 - got, 0);
+                    if (n <= 0) return DEHALO_ERR_UNSUPPORTED;
+                    got += (size_t)n;
+                }
+            } else {      // the caller's key: pcg_state | pcg_inc as they lie in memory
+                memcpy(key, r->pcg_state, 16);
+                memcpy(key + 16, r->pcg_inc, 16);
             }
             cc.init(key, 0);
             ccpos = 16;
@@ -117,29 +148,28 @@ struct HostRng {
         HostRng o = *this;
         o.position = position + skip;
         if (kind == DEHALO_RNG_PCG64) o.pcg.advance((u128)4 * skip);
-        if (kind == DEHALO_RNG_OS) {      // an independent ChaCha20 stream under the same key
+        if (chacha()) {      // an independent ChaCha20 stream under the same key
             o.cc.init(key, stream);
             o.ccpos = 16;
         }
         return o;
     }
-    void skip(uint64_t count) {
+    void skip(uint64_t count) {      // (ChaCha20 kinds: only `position` moves -- what is skipped is drawn from another stream, and the serial stream stays where it is)
         position += count;
         if (kind == DEHALO_RNG_PCG64) pcg.advance((u128)4 * count);
     }
-    void write_back(dehalo_rng* r) const {      // a PCG64 caller's generator moves past the call's draws (upstream's `&mut rng`)
+    void write_back(dehalo_rng* r) const {      // a PCG64 caller's generator moves past the call's draws (upstream's `&mut rng`); a ChaCha20 key stays as it is
         if (!r || r->kind != DEHALO_RNG_PCG64) return;
         r->pcg_state[0] = (uint64_t)pcg.state;
         r->pcg_state[1] = (uint64_t)(pcg.state >> 64);
     }
-    uint64_t cc64() {
+    void cc_candidate(uint32_t w[8]) {      // the next eight words of the serial stream: half a block, used or rejected
         if (ccpos >= 16) {
             cc.block(ccbuf);
             ccpos = 0;
         }
-        const uint64_t v = (uint64_t)ccbuf[ccpos] | ((uint64_t)ccbuf[ccpos + 1] << 32);
-        ccpos += 2;
-        return v;
+        memcpy(w, ccbuf + ccpos, 32);
+        ccpos += 8;
     }
     int scalars(uint64_t* out, size_t count) {
         if (kind == DEHALO_RNG_PCG64) {
@@ -147,14 +177,13 @@ struct HostRng {
                 for (int j = 0; j < 4; j++) out[4 * i + j] = pcg.next();
                 out[4 * i + 3] &= ((uint64_t)1 << 61) - 1;
             }
-        } else if (kind == DEHALO_RNG_OS) {
-            const uint64_t mask = f->bits >= 256 ? ~(uint64_t)0 : (((uint64_t)1 << (f->bits - 192)) - 1);
+        } else if (chacha()) {
+            uint32_t pw[8], w[8];
+            for (int j = 0; j < 4; j++) { pw[2 * j] = (uint32_t)f->p[j]; pw[2 * j + 1] = (uint32_t)(f->p[j] >> 32); }
             for (size_t i = 0; i < count; i++) {
-                uint64_t* o = out + 4 * i;
-                do {
-                    for (int j = 0; j < 4; j++) o[j] = cc64();
-                    o[3] &= mask;
-                } while (HostField::geq(o, f->p));
+                do cc_candidate(w);
+                while (!chacha_accept(w, pw, f->bits));
+                for (int j = 0; j < 4; j++) out[4 * i + j] = (uint64_t)w[2 * j] | ((uint64_t)w[2 * j + 1] << 32);
             }
         } else {
             const int rc = fill_fn(user, out, count, position);

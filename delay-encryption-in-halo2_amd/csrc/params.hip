@@ -9,12 +9,13 @@
 
 namespace {
 
-// DEHALO_RNG_OS, the vanishing argument's random polynomial (n scalars: 4 MiB at k = 17): generated ON THE DEVICE from the proof's ChaCha20 key (32 bytes of
-// operating-system entropy) instead of being drawn on a host thread and uploaded.  Scalar i = the first of ChaCha20 blocks (counter low = i, counter high =
-// attempt 0, 1, ...), nonce = the helper's stream, whose first 256 bits masked to the modulus' length are < p: uniform over the field.
+// The ChaCha20 kinds (DEHALO_RNG_OS, DEHALO_RNG_CHACHA20), the vanishing argument's random polynomial (n scalars: 4 MiB at k = 17): generated ON THE DEVICE from
+// the proof's ChaCha20 key (32 bytes of operating-system entropy, or the caller's) instead of being drawn on a host thread and uploaded.  Scalar i = the first of
+// ChaCha20 blocks (counter low = i, counter high = attempt 0, 1, ...), nonce = the helper's stream, whose first 256 bits masked to the modulus' length are < p
+// (chacha_accept, hostrng.hpp): uniform over the field.  The schedule of all draws: include/dehalo.h, dehalo_rng_kind.
 struct ChaKey { u32 k[8]; };
 __device__ __forceinline__ u32 cha_rotl(u32 x, int n) { return (x << n) | (x >> (32 - n)); }
-__global__ void k_chacha_scalars(ChaKey key, u64 stream, fe p, u32 top_mask, fe* out, u64 n) {
+__global__ void k_chacha_scalars(ChaKey key, u64 stream, fe p, u32 bits, fe* out, u64 n) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     for (u32 attempt = 0;; attempt++) {
@@ -34,12 +35,7 @@ __global__ void k_chacha_scalars(ChaKey key, u64 stream, fe p, u32 top_mask, fe*
         fe v;
 #pragma unroll
         for (int j = 0; j < 8; j++) v.v[j] = x[j] + st[j];
-        v.v[7] &= top_mask;
-        bool below = false, decided = false;
-#pragma unroll
-        for (int j = 7; j >= 0; j--)
-            if (!decided && v.v[j] != p.v[j]) { below = v.v[j] < p.v[j]; decided = true; }
-        if (below) {
+        if (chacha_accept(v.v, p.v, bits)) {
             out[i] = v;
             return;
         }
@@ -48,15 +44,14 @@ __global__ void k_chacha_scalars(ChaKey key, u64 stream, fe p, u32 top_mask, fe*
 
 }   // namespace
 
-// the ChaCha20 draw of DEHALO_RNG_OS: key from the proof's generator, modulus and mask of its field
+// the ChaCha20 kinds' indexed draw: key from the proof's generator, modulus and bit length of its field
 int chacha_scalars_device(dehalo_ctx* ctx, const HostRng& rng, uint64_t cha_stream, fe* out, size_t n, hipStream_t s) {
     const HostField* f = rng.f;
     ChaKey ck;
     memcpy(ck.k, rng.key, 32);
     fe pw;
     for (int i = 0; i < 4; i++) { pw.v[2 * i] = (u32)f->p[i]; pw.v[2 * i + 1] = (u32)(f->p[i] >> 32); }
-    const u32 top_mask = f->bits >= 256 ? 0xffffffffu : ((1u << (f->bits - 224)) - 1);
-    k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ck, /* stream of the fork */ cha_stream, pw, top_mask, out, n);
+    k_chacha_scalars<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(ck, /* stream of the fork */ cha_stream, pw, f->bits, out, n);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -421,7 +416,7 @@ int ipa_commit_blinded(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* 
 }   // namespace
 
 // commitment::create_proof on `rng` as it stands (dehalo_ipa_open: a fresh generator; a whole proof: the proof's generator, right behind f's blind).
-// cha_stream: the ChaCha20 stream of the n-scalar draw under DEHALO_RNG_OS -- within one proof it must differ from the random polynomial's (1).
+// cha_stream: the ChaCha20 stream of the n-scalar draw under the ChaCha20 kinds -- within one proof it must differ from the random polynomial's (1).
 int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t) {
         const hipStream_t s = ctx->stream.get();
         const int fid = curve_scalar_field(p->curve);
@@ -441,7 +436,7 @@ int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_pol
         TRY(pts.alloc(ctx, 8, false));
         TRY(uwsc.alloc(ctx, 4, false));
         // ---- draws, in upstream's order: s_poly (n), s_poly_blind, (l_rand, r_rand) per round.  The n scalars are the proof's large draw and come, as
-        // the prover's random polynomial does, from the generator forked at their position: for DEHALO_RNG_OS a ChaCha20 kernel under the call's key
+        // the prover's random polynomial does, from the generator forked at their position: for the ChaCha20 kinds a ChaCha20 kernel under the call's key
         // (stream 1); for PCG64 / a callback the fork yields exactly the scalars a serial draw would, drawn on the host and uploaded.
         HostRng rng_poly = rng.fork(0, cha_stream);
         rng.skip(n);
@@ -449,7 +444,7 @@ int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_pol
         std::vector<uint64_t> rands(8 * (size_t)k);
         TRY(rng.scalars(s_blind.v, 1));
         TRY(rng.scalars(rands.data(), 2 * (size_t)k));
-        if (rng.kind == DEHALO_RNG_OS) TRY(chacha_scalars_device(ctx, rng, cha_stream, s_poly.p, n, s));
+        if (rng.chacha()) TRY(chacha_scalars_device(ctx, rng, cha_stream, s_poly.p, n, s));
         else {
             std::vector<uint64_t> s_host(4 * n);
             TRY(rng_poly.scalars(s_host.data(), n));
@@ -577,5 +572,22 @@ extern "C" int dehalo_rng_scalars(dehalo_rng* rng, int field, uint64_t skip, uin
         TRY(r.init(rng, f));
         r.skip(skip);
         return r.scalars(out, count);
+    });
+}
+
+extern "C" int dehalo_rng_scalars_device(dehalo_ctx* ctx, dehalo_rng* rng, int field, uint64_t cha_stream, uint64_t* d_out, size_t n, void* stream) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx) return DEHALO_ERR_INVALID;
+        const HostField* f = host_field(field);
+        if (!f) return dh_fail(ctx, DEHALO_ERR_INVALID, "rng_scalars_device: unknown field");
+        if (!rng || rng->kind != DEHALO_RNG_CHACHA20) return dh_fail(ctx, DEHALO_ERR_INVALID, "rng_scalars_device: needs a keyed ChaCha20 generator (kind 3)");
+        if (n >= ((size_t)1 << 29)) return dh_fail(ctx, DEHALO_ERR_INVALID, "rng_scalars_device: too many scalars");
+        if (n == 0) return 0;
+        if (!d_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "rng_scalars_device: null output");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        HostRng r;
+        TRY(r.init(rng, f));
+        return chacha_scalars_device(ctx, r, cha_stream, (fe*)d_out, n, pick_stream(ctx, stream));
     });
 }

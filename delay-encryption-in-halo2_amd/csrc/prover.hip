@@ -426,7 +426,7 @@ struct ProofRun {
     // device, so all of them are made here, in that order, and the blinds go up with the blinding rows in one copy.
     int draw_blinds() {
         TRY(rng.init(rng_in, f));
-        device_rng = rng.kind == DEHALO_RNG_OS;
+        device_rng = rng.chacha();
         c_adv = (size_t)N * A * rows; c_advb = (size_t)N * A; c_lk = (size_t)N * L * (2 * rows + 2); c_pr = (size_t)N * (S + L + H) * (bf + 1);
         const size_t draws_before = c_adv + c_advb + c_lk + c_pr;
         for (uint32_t ph = 0, off = 0; ph < p.nph; ph++) { adv_off[ph] = off; off += (uint32_t)(p.phase_cols[ph].size() * (rows + 1)); }

@@ -113,7 +113,7 @@ struct dehalo_pk {
 // ================================================================================================ functions that cross units
 // params.hip: commitment::create_proof of ParamsIPA on `rng` as it stands, into `t` (dehalo_ipa_open; the last step of a ProverIPA proof)
 int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t);
-// params.hip: out[0 .. n) = uniform scalars of rng's field from ChaCha20 stream `cha_stream` under rng's key (DEHALO_RNG_OS), one kernel launch on `s`
+// params.hip: out[0 .. n) = uniform scalars of rng's field from ChaCha20 stream `cha_stream` under rng's key (rng.chacha()), one kernel launch on `s`
 int chacha_scalars_device(dehalo_ctx* ctx, const HostRng& rng, uint64_t cha_stream, fe* out, size_t n, hipStream_t s);
 // keygen.hip: (n, 4) device column of omega^i
 int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col);

@@ -16,7 +16,7 @@ from .fields import CurveSpec, FieldSpec
 
 EXPR_KIND = {"const": 0, plonk.FIXED: 1, plonk.ADVICE: 2, plonk.INSTANCE: 3, "neg": 4, "sum": 5, "product": 6, "scaled": 7, "challenge": 8}
 COLUMN_KIND = {plonk.ADVICE: 0, plonk.FIXED: 1, plonk.INSTANCE: 2}
-RNG_OS, RNG_PCG64, RNG_CALLBACK = 0, 1, 2
+RNG_OS, RNG_PCG64, RNG_CALLBACK, RNG_CHACHA20 = 0, 1, 2, 3
 KEYGEN_FIXED_CANONICAL = 1
 PROOF_ADVICE_ON_DEVICE, PROOF_ADVICE_CANONICAL = 1, 2
 CIRCUIT_DELAY_ENC, CIRCUIT_MOD_POW, CIRCUIT_POSE_ENC = 0, 1, 2
@@ -401,11 +401,16 @@ class Blake2bWrite:
 
 
 def rng_struct(rng) -> Optional[CRng]:
-    """None / prover.OsRng -> NULL (operating-system entropy inside the library); prover.SeededRng -> its PCG64 state; any other object
-    with .scalars(count) -> a callback."""
+    """None / prover.OsRng -> NULL (operating-system entropy inside the library); prover.KeyedRng -> its ChaCha20 key; prover.SeededRng -> its PCG64
+    state; any other object with .scalars(count) -> a callback."""
     if rng is None or type(rng).__name__ == "OsRng":
         return None
     r = CRng()
+    if type(rng).__name__ == "KeyedRng":
+        r.kind = RNG_CHACHA20
+        C.memmove(r.pcg_state, rng.key, 16)
+        C.memmove(r.pcg_inc, rng.key[16:], 16)
+        return r
     gen = getattr(rng, "gen", None)
     if gen is not None and type(gen.bit_generator).__name__ == "PCG64":
         st = gen.bit_generator.state["state"]

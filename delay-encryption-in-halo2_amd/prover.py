@@ -1,5 +1,5 @@
-"""What the proving calls share on the Python side: the two scalar sources a proof draws its blinding from (`OsRng`, `SeededRng` -- the PCG64 stream the
-C++ side reproduces, include/dehalo.h `dehalo_rng`) and the layout of a proof's bytes (`proof_layout`, `proof_commitments`: what a batch prover all-gathers,
+"""What the proving calls share on the Python side: the scalar sources a proof draws its blinding from (`OsRng`, its keyed form `KeyedRng`, `SeededRng` --
+the PCG64 stream the C++ side reproduces, include/dehalo.h `dehalo_rng`) and the layout of a proof's bytes (`proof_layout`, `proof_commitments`: what a batch prover all-gathers,
 SURVEY.md 8(e)).
 
 `create_proof` itself -- halo2_proofs::plonk::create_proof over KZG / GWC [UPSTREAM halo2_proofs/src/plonk/prover.rs @ v2023_04_20], the call the reference
@@ -78,6 +78,18 @@ class SeededRng:
 
     def skip(self, count: int):
         self.gen.bit_generator.advance(4 * count)
+
+
+class KeyedRng:
+    """The default generator with the caller's 32-byte key instead of operating-system entropy (DEHALO_RNG_CHACHA20, include/dehalo.h): the ChaCha20
+    streams a proof under `OsRng` draws from, reproducible, and as strong as the key.  Two proofs under one key draw the same scalars -- a key serves one
+    proof.  It holds only the key: the draws are made inside the library."""
+
+    def __init__(self, key: bytes):
+        key = bytes(key)
+        if len(key) != 32:
+            raise ValueError("KeyedRng: the key is 32 bytes")
+        self.key = key
 
 
 def proof_layout(cs: plonk.ConstraintSystem) -> Tuple[int, int]:

@@ -594,18 +594,37 @@ int dehalo_pk_info(const dehalo_pk* pk, uint32_t out[8]);
 int dehalo_pk_phases(const dehalo_pk* pk, uint32_t out[2]);
 int dehalo_pk_release(dehalo_ctx* ctx, dehalo_pk* pk);
 
-/* Random scalars of one proof (see csrc/hostrng.hpp).  DEHALO_RNG_OS is what a NULL pointer selects. */
-typedef enum { DEHALO_RNG_OS = 0, DEHALO_RNG_PCG64 = 1, DEHALO_RNG_CALLBACK = 2 } dehalo_rng_kind;
+/* Random scalars of one proof (see csrc/hostrng.hpp).  DEHALO_RNG_OS is what a NULL pointer selects.
+ * DEHALO_RNG_CHACHA20 is the DEHALO_RNG_OS generator with the caller's key instead of 32 bytes of operating-system entropy: reproducible, and as strong as
+ * the key.  The key is the 32 bytes of pcg_state[2] | pcg_inc[2], read as they lie in memory; it is never written back, so two calls with the same key give
+ * the same proof -- a key must not be used for two different proofs.  From the key on the two kinds are one code path, and their schedule is:
+ *   - ChaCha20 (RFC 8439's block function) over the state words sigma | key | w12 w13 | w14 w15, where w14 | w15 is a 64-bit stream id, low word first;
+ *   - a scalar is 256 candidate bits (eight 32-bit words, least significant first) masked to the modulus' bit length and accepted iff the result is < p,
+ *     handed over as a Montgomery representation;
+ *   - stream 0, the SERIAL stream, serves every small draw on the host (blinding rows, blinds, l_rand / r_rand), in upstream's order: consecutive blocks
+ *     with a 64-bit block counter in w12 | w13 from 0, each block two candidates; a rejected candidate consumes its half block;
+ *   - a draw of n = 2^k scalars is INDEXED and made by a kernel: scalar i is the first accepted candidate among the first halves of the blocks
+ *     w12 = i mod 2^32, w13 = (i >> 32 & 0xffff) | attempt << 16 for attempt = 0, 1, ...; it consumes nothing of the serial stream.  Stream 1: the vanishing
+ *     argument's random polynomial, and s_poly of a stand-alone dehalo_ipa_open; stream 2: s_poly of the opening inside an IPA proof. */
+typedef enum { DEHALO_RNG_OS = 0, DEHALO_RNG_PCG64 = 1, DEHALO_RNG_CALLBACK = 2, DEHALO_RNG_CHACHA20 = 3 } dehalo_rng_kind;
 /* fills `count` scalars (4 x u64 Montgomery representations, < p); `position` = index of the first one in upstream's draw order.  May be
  * called from a helper thread of the library, never concurrently for one proof.  Returns 0. */
 typedef int (*dehalo_rng_fill_fn)(void* user, uint64_t* out, size_t count, uint64_t position);
 typedef struct {
     int kind;
-    uint64_t pcg_state[2], pcg_inc[2];     /* DEHALO_RNG_PCG64: numpy PCG64 state / increment, low word first; advanced past the proof's draws on return */
+    uint64_t pcg_state[2], pcg_inc[2];     /* DEHALO_RNG_PCG64: numpy PCG64 state / increment, low word first; advanced past the proof's draws on return.
+                                            * DEHALO_RNG_CHACHA20: the 32-byte key, left as it is */
     dehalo_rng_fill_fn fill; void* user;   /* DEHALO_RNG_CALLBACK */
 } dehalo_rng;
-/* `count` scalars of the field from a generator (what create_proof draws): lets a test pin the three kinds without a device. */
+/* `count` scalars of the field from a generator (what create_proof draws): lets a test pin the kinds without a device.  `skip`: PCG64 is advanced past
+ * that many scalars and a callback sees it as `position`; under the ChaCha20 kinds it moves no stream (what a proof skips there is an indexed draw, which
+ * consumes nothing of the serial stream), so any `skip` returns the scalars of skip = 0. */
 int dehalo_rng_scalars(dehalo_rng* rng, int field, uint64_t skip, uint64_t* out, size_t count);
+/* An indexed draw of the schedule above on the device: d_out[0 .. n) = n scalars of `field` (a dehalo_field id) from ChaCha20 stream `cha_stream` under rng's
+ * key, one kernel launch on `stream` (NULL: the context's) -- the launch create_proof makes for its random polynomial.  Only DEHALO_RNG_CHACHA20 is taken:
+ * DEHALO_ERR_INVALID for a NULL rng, any other kind (DEHALO_RNG_OS as well: its output could not be checked), an unknown field or n >= 2^29; n = 0 does
+ * nothing and returns 0. */
+int dehalo_rng_scalars_device(dehalo_ctx* ctx, dehalo_rng* rng, int field, uint64_t cha_stream, uint64_t* d_out, size_t n, void* stream);
 
 /* Blake2bWrite / Challenge255 [UPSTREAM halo2_proofs/src/transcript.rs; benches/delay_enc.rs:120,134]. */
 int dehalo_transcript_create(int curve, dehalo_transcript** out);
@@ -622,7 +641,7 @@ void dehalo_transcript_release(dehalo_transcript* t);
  * can call on its own.  params: dehalo_params_ipa_create; d_poly: 2^k coefficients in device memory (Montgomery, read only); blind, x3: Montgomery.
  * Neither P nor p(x_3) is written: the caller's transcript holds them already, as upstream's does.
  * Draws, in upstream's order: s_poly (2^k scalars), s_poly_blind, then (l_rand, r_rand) for each of the k rounds.  s_poly is the call's large draw and
- * comes from the generator forked at its position, as create_proof's random polynomial does: with DEHALO_RNG_OS a ChaCha20 kernel (fork stream 1) under
+ * comes from the generator forked at its position, as create_proof's random polynomial does: with DEHALO_RNG_OS / DEHALO_RNG_CHACHA20 a ChaCha20 kernel (stream 1) under
  * the call's key, with PCG64 / a callback exactly the scalars a serial draw would give.  A PCG64 rng is advanced past all of them.
  * Writes: the point S = commit(s_poly, s_poly_blind); squeezes xi, z; per round j < k the points L_j, R_j and squeezes u_j; then the scalars c, f.
  * Proof bytes: 32 (S) + k x 64 (L_j | R_j) + 64 (c | f).  Each round queues its launches on the context's stream and waits once (L_j, R_j): round 1
