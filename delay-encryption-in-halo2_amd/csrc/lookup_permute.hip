@@ -610,7 +610,7 @@ __global__ void k_lp_emit(LpCols c, const fe* sorted, u64 n, u64 npad, const u32
 }
 
 template <class F>
-int lp_run(dehalo_ctx* ctx, const LpCols& c, u32 B, u32 U, u64 n, hipStream_t s, int* d_status) {
+int lp_run(dehalo_ctx* ctx, const LpCols& c, u32 B, u32 U, u64 n, hipStream_t s, int* d_status, size_t first) {      // first: the call's index of this launch group's lookup 0
     const u64 tiles = (n + LP_TILE - 1) / LP_TILE, npad = tiles * LP_TILE;
     const size_t pad = 256;
     const size_t bytes = 2 * ((size_t)U * npad * sizeof(fe) + pad) + 4 * ((size_t)B * std::max<size_t>(n, LP_TILE + 1) * 4 + pad) + ((size_t)B * tiles * 8 + pad) + 2 * ((size_t)B * 8 + pad) + 4096 +
@@ -680,7 +680,7 @@ int lp_run(dehalo_ctx* ctx, const LpCols& c, u32 B, u32 U, u64 n, hipStream_t s,
     HIP_TRY(ctx, hipStreamSynchronize(s));     // upstream returns Err(ConstraintSystemFailure) from this call: so must we
     for (u32 y = 0; y < B; y++)
         if (host_err[y])
-            return dh_fail(ctx, DEHALO_ERR_NOT_IN_TABLE, "permute_expression_pair: an input value of lookup " + std::to_string(y) + " of the call is not in the table (ConstraintSystemFailure)");
+            return dh_fail(ctx, DEHALO_ERR_NOT_IN_TABLE, "permute_expression_pair: an input value of lookup " + std::to_string(first + y) + " of the call is not in the table (ConstraintSystemFailure)");
     return 0;
 }
 
@@ -749,10 +749,10 @@ int lookup_permute_ptrs(dehalo_ctx* ctx, int field, const fe* const* d_inputs, c
         }
         int rc;
         switch (field) {
-            case DEHALO_FIELD_BN254_FR: rc = lp_run<Bn254Fr>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr); break;
-            case DEHALO_FIELD_BN254_FQ: rc = lp_run<Bn254Fq>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr); break;
-            case DEHALO_FIELD_PASTA_FP: rc = lp_run<PastaFp>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr); break;
-            case DEHALO_FIELD_PASTA_FQ: rc = lp_run<PastaFq>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr); break;
+            case DEHALO_FIELD_BN254_FR: rc = lp_run<Bn254Fr>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr, first); break;
+            case DEHALO_FIELD_BN254_FQ: rc = lp_run<Bn254Fq>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr, first); break;
+            case DEHALO_FIELD_PASTA_FP: rc = lp_run<PastaFp>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr, first); break;
+            case DEHALO_FIELD_PASTA_FQ: rc = lp_run<PastaFq>(ctx, c, B, U, n, s, d_status ? d_status + first : nullptr, first); break;
             default: return dh_fail(ctx, DEHALO_ERR_INVALID, "unknown field id");
         }
         if (rc) return rc;

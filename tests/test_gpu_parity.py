@@ -985,7 +985,8 @@ def test_permute_expression_pair_tables_given_as_distinct_rows(pkg, co, ctx):
 
 
 def test_permute_expression_pair_small_values(pkg, co, ctx):
-    """Range-table shaped columns (values < 2^16): the sort skips the limbs that are zero everywhere."""
+    """Range-table shaped columns (values < 2^16): seven of a key's eight words are zero everywhere, so word 0 decides every comparison
+    of the full-key merge sort (there is no limb-skipping path)."""
     fid, n = 0, 40000
     small = np.zeros((1 << 12, 4), dtype=np.uint64)
     small[:, 0] = np.arange(1 << 12, dtype=np.uint64) * 13 % 65521
@@ -1251,8 +1252,8 @@ def test_params_ipa_commit_vs_oracle(pkg, co, ctx, cname, k):
 
 @pytest.mark.gpu
 def test_permute_expression_pair_leading_bit_ties_fall_back(pkg, po, co, ctx):
-    """The lookup sort's fast path orders on the leading 48 bits of the top limb and verifies the full order: values that agree
-    on those bits and differ below must take the full sort and still match upstream's order."""
+    """Values that share their leading bits and differ in word 0, 2 or 4 only: the merge sort compares all eight words of a key,
+    so the order must still be upstream's (tests/test_lookup_permute_structured.py decides every word, on every path)."""
     f, of = pkg.fields.BN254_FR, po.BN254_FR
     n = 3000
     rng = po.Xoshiro(77)
