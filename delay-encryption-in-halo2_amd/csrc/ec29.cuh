@@ -76,7 +76,9 @@ FP_DEV xyzz29 x29_from_affine(const aff29& q, bool q_is_identity) {
 template <class F>
 FP_DEV xyzz29 x29_double(const xyzz29& a) {
     f29 u = f29_dbl(a.y);                       // limbs < 2^30
-    f29 v = f29_sqr<F>(u);
+    // additive columns: column 7 of U^2 holds 4 cross products of 2^31 * 2^30, which leaves the signed columns of the Pasta reduction
+    // (< 2^63) a margin of 2^34 only (tools/fp29_model.py call_site_bounds)
+    f29 v = f29_sqr<F, false>(u);
     f29 w = f29_mul<F>(u, v);
     f29 s = f29_mul<F>(a.x, v);
     f29 xx = f29_sqr<F>(a.x);
@@ -275,7 +277,7 @@ FP_DEV xyzz29 x29_double_quad(const xyzz29& a) {
     f29 u = f29_dbl(a.y);
     // level 1: v = U^2 | xx = X^2
     f29 op = f29_sel4(u, a.x, u, a.x, role);
-    f29 m = f29_mul<F>(op, op);
+    f29 m = f29_mul<F, false>(op, op);          // additive columns: 8 products of 2^30 * 2^30 in column 7, as in x29_double
     f29 v = f29_quad_bcast<0>(m), xx = f29_quad_bcast<1>(m);
     f29 mm_in = f29_norm(f29_add(f29_dbl(xx), xx));
     // level 2: w = U V | s = X V | mm = M^2 | zz3 = V ZZ

@@ -8,8 +8,10 @@
 // 297 moves; profiles/r01_ubench_instruction_rates.txt).  With 29-bit limbs a 64-bit
 // accumulator absorbs every product of a column (<= 9 products of <= 2^60 plus 9 reduction
 // terms of <= 2^58 < 2^64) with the multiply-add itself: D = a_i * b_j + D, in place, no carry
-// instruction, no moves.  81 + 81 mads (81 + 45 for the Pasta primes, whose limbs 5..7 are
-// zero) against 64 + 64, but nothing else in the inner loop.
+// instruction, no moves.  81 + 81 mads against 64 + 64, but nothing else in the inner loop.  The
+// Pasta primes (limbs 5..7 zero, limb 0 = 1) take 81 + 46 = 127: their reduction subtracts m p, which
+// needs no multiply-add by limb 0 (f29_montgomery_columns, f29_os_subtract_row); the additive form they used
+// before, and f29_mul2 still uses, takes 81 + 54 = 135.
 //
 // Values are kept lazily reduced: a product is < a*b/2^261 + p, sums are limb-wise adds,
 // differences add a multiple of p whose limbs dominate the subtrahend's (constants KM/KA/KB/KN,
@@ -114,16 +116,51 @@ FP_DEV f29 f29_sub(const f29& a, const f29& b, const u32 (&K)[9]) {
 }
 
 FP_DEV u64 mad_wide(u32 a, u32 b, u64 c) { return (u64)a * b + c; }
+// the signed forms of the Pasta primes' subtractive reduction: acc += m * np with both factors signed (v_mad_i64_i32), and the carry of a signed column
+FP_DEV u64 mad_wide_signed(u32 m, u32 np, u64 acc) { return (u64)((int64_t)(int32_t)m * (int32_t)np + (int64_t)acc); }
+FP_DEV u64 f29_carry_signed(u64 acc) { return (u64)((int64_t)acc >> F29_BITS); }
 
+// Row i of the subtractive reduction of the Pasta primes (p = 1 mod 2^29): m p is SUBTRACTED with m = acc[i] & MASK, so the row's own column keeps only
+// its carry and the other columns receive -m P[j] as signed multiply-adds; the last row's m is biased by -2^29 (see f29_montgomery_columns below, which
+// states the signed column budget -- the same here, every accumulator being a partial sum of one column).
+template <class F>
+FP_DEV void f29_os_subtract_row(u64 (&acc)[18], int i) {
+    const u32 m = i < 8 ? (u32)acc[i] & F29_MASK : (u32)acc[i] | ~F29_MASK;
+#pragma unroll
+    for (int j = 0; j < 9; j++)
+        if (F::P[j] != 0 && (j > 0 || i == 8)) acc[i + j] = mad_wide_signed(m, 0u - F::P[j], acc[i + j]);
+    acc[i + 1] += f29_carry_signed(acc[i]);
+}
+FP_DEV f29 f29_os_emit_signed(const u64 (&acc)[18]) {
+    f29 r;
+    u64 c = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        u64 t = acc[9 + j] + c;
+        r.v[j] = (u32)t & F29_MASK;
+        c = f29_carry_signed(t);      // an upper column may be negative until the carries arrive
+    }
+    r.v[8] = (u32)(acc[17] + c);
+    return r;
+}
 // Operand scanning (18 independent column accumulators).  More instructions
 // than product scanning (a carry add per column) but no dependent multiply-add chain, hence none
 // of the s_nop wait states hipcc must put between dependent v_mad_u64_u32 (about 130 per
-// multiplication, 4 cycles each when a wave runs alone).  Same values.
-template <class F>
+// multiplication, 4 cycles each when a wave runs alone).  Same values.  SUB = false: the additive rows for the Pasta primes too.
+template <class F, bool SUB = true>
 FP_DEV f29 f29_mul_os(const f29& a, const f29& b) {
     u64 acc[18];
 #pragma unroll
     for (int i = 0; i < 18; i++) acc[i] = 0;
+    if constexpr (SUB && F::INV == F29_MASK) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+#pragma unroll
+            for (int j = 0; j < 9; j++) acc[i + j] = mad_wide(a.v[i], b.v[j], acc[i + j]);
+            f29_os_subtract_row<F>(acc, i);
+        }
+        return f29_os_emit_signed(acc);
+    }
 #pragma unroll
     for (int i = 0; i < 9; i++) {
 #pragma unroll
@@ -149,7 +186,7 @@ FP_DEV f29 f29_mul_os(const f29& a, const f29& b) {
 }
 
 // a^2, latency schedule
-template <class F>
+template <class F, bool SUB = true>
 FP_DEV f29 f29_sqr_os(const f29& a) {
     u64 acc[18];
 #pragma unroll
@@ -163,6 +200,11 @@ FP_DEV f29 f29_sqr_os(const f29& a) {
         acc[2 * i] = mad_wide(a.v[i], a.v[i], acc[2 * i]);
 #pragma unroll
         for (int j = i + 1; j < 9; j++) acc[i + j] = mad_wide(d[i], a.v[j], acc[i + j]);
+    }
+    if constexpr (SUB && F::INV == F29_MASK) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) f29_os_subtract_row<F>(acc, i);
+        return f29_os_emit_signed(acc);
     }
 #pragma unroll
     for (int i = 0; i < 9; i++) {
@@ -211,35 +253,89 @@ FP_DEV void f29_load_p(u32 (&P)[9]) {
         if (F::P[j] != 0) asm("" : "+s"(P[j]));
     }
 }
+// Subtractive reduction (the Pasta primes, p = 1 mod 2^29: P[0] == 1, INV == F29_MASK).  With m_k = acc & MASK and
+// m_k p SUBTRACTED, column k loses exactly its low limb, so its carry is the arithmetic shift of the accumulator as it
+// stands: no negation, no multiply-add by P[0] = 1.  The later columns receive -m_i P[k - i] as a signed multiply-add
+// (v_mad_i64_i32) against the negated modulus limbs.  The last multiplier is biased, m_8' = (acc & MASK) - 2^29 =
+// acc | ~MASK, so that (M - 2^261) p is subtracted in all: the result (T + (2^261 - M) p) / 2^261 is limb for limb the
+// additive form's, except for T = 0 mod 2^261 (a zero operand), where it is the additive form's value + p -- inside
+// the bound  a b / 2^261 + p  (reached, not exceeded).  8 multiply-adds and 9 subtractions less per reduction.
+// Signed column budget: the products of a column + carry < 2^63 (reduction terms only lower it, by < 9 * 2^58):
+// bits(max a limb) + bits(max b limb) <= 59, or a normalized operand against limbs < 1.75 * 2^30 (an un-normalized
+// f29_sub by KM / KA / KN, a sum of two normalized values).  tools/fp29_model.py asserts it at every call site's
+// operand bounds; the call sites it refuses keep the additive columns (SUB = false) and say which bound failed.
+template <class F>
+constexpr bool f29_subtractive() { return F::INV == F29_MASK && F::P[0] == 1; }
+FP_DEV void f29_col_msub(u64& acc, u32 m, u32 np) {
+    acc = mad_wide_signed(m, np, acc);
+    asm("" : "+v"(acc));
+}
+FP_DEV void f29_col_msub_pin(u64& acc, u32 m, u32 np) {
+    acc = mad_wide_signed(m, np, acc);
+    asm("" : "+v"(acc));
+    __builtin_amdgcn_sched_barrier(0);
+}
+// the negated modulus limbs, opaque in scalar registers like f29_load_p's
+template <class F>
+FP_DEV void f29_load_np(u32 (&NP)[9]) {
+#pragma unroll
+    for (int j = 0; j < 9; j++) {
+        NP[j] = 0u - F::P[j];
+        if (F::P[j] != 0) asm("" : "+s"(NP[j]));
+    }
+}
+
 // Montgomery reduction interleaved column by column (product scanning).  Column k of
 // a*b + sum_i m_i p 2^(29 i) is accumulated in ONE 64-bit register that starts as the carry of
 // column k-1, so the only non-multiply work per column is m_k (k < 9) or the 29-bit mask
 // (k >= 9) and one 64-bit shift.  Same values as operand scanning; measured on MI355X
 // (tools/ubench_mul.hip): Pasta 172 -> 200 Gmul/s, BN254 172 -> 175.
-// Column bound: <= 9 products of <= 2^60 + 9 reduction terms of <= 2^58 + carry < 2^64.
-template <class F, class PROD>
+// Column bound, additive form: <= 9 products of <= 2^60 + 9 reduction terms of <= 2^58 + carry < 2^64.
+// Column bound, subtractive form (Pasta unless SUB = false): products + carry < 2^63, see above.
+template <class F, bool SUB = true, class PROD>
 FP_DEV f29 f29_montgomery_columns(const PROD& products) {
-    u32 m[9], P[9];
-    f29_load_p<F>(P);
-    f29 r;
-    u64 acc = 0;
+    if constexpr (SUB && F::INV == F29_MASK) {
+        static_assert(f29_subtractive<F>(), "INV == MASK means p = 1 mod 2^29");
+        u32 m[9], NP[9];
+        f29_load_np<F>(NP);
+        f29 r;
+        u64 acc = 0;
 #pragma unroll
-    for (int k = 0; k < 17; k++) {
-        products(k, acc);
+        for (int k = 0; k < 17; k++) {
+            products(k, acc);
 #pragma unroll
-        for (int i = 0; i < 9; i++)
-            if (i < k && k - i < 9 && F::P[k - i] != 0) f29_col_mad(acc, m[i], P[k - i]);
-        if (k < 9) {
-            if (F::INV == F29_MASK) m[k] = (0u - (u32)acc) & F29_MASK;   // p = 1 mod 2^29 (Pasta)
-            else m[k] = ((u32)acc * F::INV) & F29_MASK;
-            f29_col_mad(acc, m[k], P[0]);
-        } else {
-            r.v[k - 9] = (u32)acc & F29_MASK;
+            for (int i = 0; i < 9; i++)
+                if (i < k && k - i < 9 && F::P[k - i] != 0) f29_col_msub(acc, m[i], NP[k - i]);
+            if (k < 8) m[k] = (u32)acc & F29_MASK;
+            else if (k == 8) { m[8] = (u32)acc | ~F29_MASK; f29_col_msub(acc, m[8], NP[0]); }
+            else r.v[k - 9] = (u32)acc & F29_MASK;
+            acc = f29_carry_signed(acc);
         }
-        acc >>= F29_BITS;
+        r.v[8] = (u32)acc;
+        return r;
+    } else {
+        u32 m[9], P[9];
+        f29_load_p<F>(P);
+        f29 r;
+        u64 acc = 0;
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+            products(k, acc);
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+                if (i < k && k - i < 9 && F::P[k - i] != 0) f29_col_mad(acc, m[i], P[k - i]);
+            if (k < 9) {
+                if (F::INV == F29_MASK) m[k] = (0u - (u32)acc) & F29_MASK;   // p = 1 mod 2^29 (Pasta)
+                else m[k] = ((u32)acc * F::INV) & F29_MASK;
+                f29_col_mad(acc, m[k], P[0]);
+            } else {
+                r.v[k - 9] = (u32)acc & F29_MASK;
+            }
+            acc >>= F29_BITS;
+        }
+        r.v[8] = (u32)acc;
+        return r;
     }
-    r.v[8] = (u32)acc;
-    return r;
 }
 
 // as f29_col_mad, and the machine scheduler may not move anything across it: keeps two interleaved
@@ -254,36 +350,92 @@ FP_DEV void f29_col_mad_pin(u64& acc, u32 a, u32 b) {
 // to separate dependent v_mad_u64_u32 by s_nop wait states: ~130 per multiplication).
 template <class F, class PROD1, class PROD2>
 FP_DEV void f29_montgomery_columns2(const PROD1& products1, const PROD2& products2, f29& r1, f29& r2) {
-    u32 m1[9], m2[9], P[9];
-    f29_load_p<F>(P);
-    u64 x = 0, y = 0;
+    if constexpr (F::INV == F29_MASK) {
+        // subtractive columns (see f29_montgomery_columns), the same pinning
+        static_assert(f29_subtractive<F>(), "INV == MASK means p = 1 mod 2^29");
+        u32 m1[9], m2[9], NP[9];
+        f29_load_np<F>(NP);
+        u64 x = 0, y = 0;
 #pragma unroll
-    for (int k = 0; k < 17; k++) {
-        products1(k, x);
-        products2(k, y);
+        for (int k = 0; k < 17; k++) {
+            products1(k, x);
+            products2(k, y);
 #pragma unroll
-        for (int i = 0; i < 9; i++)
-            if (i < k && k - i < 9 && F::P[k - i] != 0) { f29_col_mad_pin(x, m1[i], P[k - i]); f29_col_mad_pin(y, m2[i], P[k - i]); }
-        if (k < 9) {
-            if (F::INV == F29_MASK) { m1[k] = (0u - (u32)x) & F29_MASK; m2[k] = (0u - (u32)y) & F29_MASK; }
-            else { m1[k] = ((u32)x * F::INV) & F29_MASK; m2[k] = ((u32)y * F::INV) & F29_MASK; }
-            f29_col_mad_pin(x, m1[k], P[0]);
-            f29_col_mad_pin(y, m2[k], P[0]);
-        } else {
-            r1.v[k - 9] = (u32)x & F29_MASK;
-            r2.v[k - 9] = (u32)y & F29_MASK;
+            for (int i = 0; i < 9; i++)
+                if (i < k && k - i < 9 && F::P[k - i] != 0) { f29_col_msub_pin(x, m1[i], NP[k - i]); f29_col_msub_pin(y, m2[i], NP[k - i]); }
+            if (k < 8) { m1[k] = (u32)x & F29_MASK; m2[k] = (u32)y & F29_MASK; }
+            else if (k == 8) {
+                m1[8] = (u32)x | ~F29_MASK; m2[8] = (u32)y | ~F29_MASK;
+                f29_col_msub_pin(x, m1[8], NP[0]);
+                f29_col_msub_pin(y, m2[8], NP[0]);
+            } else {
+                r1.v[k - 9] = (u32)x & F29_MASK;
+                r2.v[k - 9] = (u32)y & F29_MASK;
+            }
+            x = f29_carry_signed(x);
+            y = f29_carry_signed(y);
         }
-        x >>= F29_BITS;
-        y >>= F29_BITS;
+        r1.v[8] = (u32)x;
+        r2.v[8] = (u32)y;
+    } else {
+        u32 m1[9], m2[9], P[9];
+        f29_load_p<F>(P);
+        u64 x = 0, y = 0;
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+            products1(k, x);
+            products2(k, y);
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+                if (i < k && k - i < 9 && F::P[k - i] != 0) { f29_col_mad_pin(x, m1[i], P[k - i]); f29_col_mad_pin(y, m2[i], P[k - i]); }
+            if (k < 9) {
+                m1[k] = ((u32)x * F::INV) & F29_MASK; m2[k] = ((u32)y * F::INV) & F29_MASK;
+                f29_col_mad_pin(x, m1[k], P[0]);
+                f29_col_mad_pin(y, m2[k], P[0]);
+            } else {
+                r1.v[k - 9] = (u32)x & F29_MASK;
+                r2.v[k - 9] = (u32)y & F29_MASK;
+            }
+            x >>= F29_BITS;
+            y >>= F29_BITS;
+        }
+        r1.v[8] = (u32)x;
+        r2.v[8] = (u32)y;
     }
-    r1.v[8] = (u32)x;
-    r2.v[8] = (u32)y;
 }
 // r1 = a * b, r2 = c * d (each * 2^-261), interleaved
 template <class F>
 FP_DEV void f29_mul_pair(const f29& a, const f29& b, const f29& c, const f29& d, f29& r1, f29& r2) {
     if constexpr (f29_is_lat<F>::value) { r1 = f29_mul_os<F>(a, b); r2 = f29_mul_os<F>(c, d); }
-    else {
+    else if constexpr (F::INV == F29_MASK) {
+        // subtractive columns (see f29_montgomery_columns); the products of one column alternate between the two accumulators too
+        static_assert(f29_subtractive<F>(), "INV == MASK means p = 1 mod 2^29");
+        u32 m1[9], m2[9], NP[9];
+        f29_load_np<F>(NP);
+        u64 x = 0, y = 0;
+#pragma unroll
+        for (int k = 0; k < 17; k++) {
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+                if (k - i >= 0 && k - i < 9) { f29_col_mad_pin(x, a.v[i], b.v[k - i]); f29_col_mad_pin(y, c.v[i], d.v[k - i]); }
+#pragma unroll
+            for (int i = 0; i < 9; i++)
+                if (i < k && k - i < 9 && F::P[k - i] != 0) { f29_col_msub_pin(x, m1[i], NP[k - i]); f29_col_msub_pin(y, m2[i], NP[k - i]); }
+            if (k < 8) { m1[k] = (u32)x & F29_MASK; m2[k] = (u32)y & F29_MASK; }
+            else if (k == 8) {
+                m1[8] = (u32)x | ~F29_MASK; m2[8] = (u32)y | ~F29_MASK;
+                f29_col_msub_pin(x, m1[8], NP[0]);
+                f29_col_msub_pin(y, m2[8], NP[0]);
+            } else {
+                r1.v[k - 9] = (u32)x & F29_MASK;
+                r2.v[k - 9] = (u32)y & F29_MASK;
+            }
+            x = f29_carry_signed(x);
+            y = f29_carry_signed(y);
+        }
+        r1.v[8] = (u32)x;
+        r2.v[8] = (u32)y;
+    } else {
         // the products of one column alternate between the two accumulators too
         u32 m1[9], m2[9], P[9];
         f29_load_p<F>(P);
@@ -297,8 +449,7 @@ FP_DEV void f29_mul_pair(const f29& a, const f29& b, const f29& c, const f29& d,
             for (int i = 0; i < 9; i++)
                 if (i < k && k - i < 9 && F::P[k - i] != 0) { f29_col_mad_pin(x, m1[i], P[k - i]); f29_col_mad_pin(y, m2[i], P[k - i]); }
             if (k < 9) {
-                if (F::INV == F29_MASK) { m1[k] = (0u - (u32)x) & F29_MASK; m2[k] = (0u - (u32)y) & F29_MASK; }
-                else { m1[k] = ((u32)x * F::INV) & F29_MASK; m2[k] = ((u32)y * F::INV) & F29_MASK; }
+                m1[k] = ((u32)x * F::INV) & F29_MASK; m2[k] = ((u32)y * F::INV) & F29_MASK;
                 f29_col_mad_pin(x, m1[k], P[0]);
                 f29_col_mad_pin(y, m2[k], P[0]);
             } else {
@@ -337,12 +488,14 @@ FP_DEV void f29_sqr_pair(const f29& a, const f29& c, f29& r1, f29& r2) {
     }
 }
 
-// a * b * 2^-261 mod p, lazily reduced: result limbs normalized, value < a*b/2^261 + p.
-// Limb-size contract: bits(max a limb) + bits(max b limb) <= 60.
-template <class F>
+// a * b * 2^-261 mod p, lazily reduced: result limbs normalized, value < a*b/2^261 + p (Pasta: = a*b/2^261 + p when
+// a*b = 0 mod 2^261, so a zero operand gives p, not 0).
+// Limb-size contract: bits(max a limb) + bits(max b limb) <= 60; for the Pasta primes' product-scanning schedule (signed
+// columns) <= 59, or a normalized operand against limbs < 1.75 * 2^30.  127 multiply-adds for Pasta (81 + 45 + 1), 162 for BN254.
+template <class F, bool SUB = true>
 FP_DEV f29 f29_mul(const f29& a, const f29& b) {
-    if constexpr (f29_is_lat<F>::value) return f29_mul_os<F>(a, b);
-    else return f29_montgomery_columns<F>([&](int k, u64& acc) {
+    if constexpr (f29_is_lat<F>::value) return f29_mul_os<F, SUB>(a, b);
+    else return f29_montgomery_columns<F, SUB>([&](int k, u64& acc) {
 #pragma unroll
         for (int i = 0; i < 9; i++)
             if (k - i >= 0 && k - i < 9) f29_col_mad(acc, a.v[i], b.v[k - i]);
@@ -352,9 +505,10 @@ FP_DEV f29 f29_mul(const f29& a, const f29& b) {
 // (a * b + c * d) * 2^-261 with ONE reduction: both products go into the same columns
 // (result < (a b + c d) / 2^261 + p).  Column budget: limbs of a, c, d < 2^29 and of b < 2^31:
 // 9 * 2^60 + 9 * 2^58 products + 9 * 2^58 reduction terms + carry < 2^64 (tools/fp29_model.py mont2).
+// Additive columns for every field: 9 * 2^60 + 9 * 2^58 of products does not fit the signed accumulator of the subtractive form (< 2^63).
 template <class F>
 FP_DEV f29 f29_mul2(const f29& a, const f29& b, const f29& c, const f29& d) {
-    return f29_montgomery_columns<F>([&](int k, u64& acc) {
+    return f29_montgomery_columns<F, false>([&](int k, u64& acc) {
 #pragma unroll
         for (int i = 0; i < 9; i++)
             if (k - i >= 0 && k - i < 9) {
@@ -364,14 +518,15 @@ FP_DEV f29 f29_mul2(const f29& a, const f29& b, const f29& c, const f29& d) {
     });
 }
 
-// a^2 * 2^-261: cross products once, against the doubled operand (limbs < 2^30 for a normalized a)
-template <class F>
+// a^2 * 2^-261: cross products once, against the doubled operand (limbs < 2^30 for a normalized a).
+// SUB = false keeps the additive columns for an operand with limbs of 30 bits (see f29_montgomery_columns).
+template <class F, bool SUB = true>
 FP_DEV f29 f29_sqr(const f29& a) {
-    if constexpr (f29_is_lat<F>::value) return f29_sqr_os<F>(a);
+    if constexpr (f29_is_lat<F>::value) return f29_sqr_os<F, SUB>(a);
     u32 d[9];
 #pragma unroll
     for (int i = 0; i < 9; i++) d[i] = a.v[i] << 1;
-    return f29_montgomery_columns<F>([&](int k, u64& acc) {
+    return f29_montgomery_columns<F, SUB>([&](int k, u64& acc) {
 #pragma unroll
         for (int i = 0; i < 9; i++)
             if (k - i > i && k - i < 9) f29_col_mad(acc, d[i], a.v[k - i]);
@@ -420,7 +575,7 @@ FP_DEV bool f29_is_zero_lt2p(const f29& a) {
 template <class F>
 FP_DEV bool f29_maybe_zero_lt2p(const f29& a) { return (a.v[0] == 0) | (a.v[0] == F::P[0]); }
 
-// exact zero test of any lazily reduced value (< 16 p, limbs < 2^31): one multiplication by R' mod p
+// exact zero test of any lazily reduced value (< 16 p, limbs < 1.75 * 2^30): one multiplication by R' mod p
 template <class F>
 FP_DEV bool f29_is_zero_slow(const f29& a) {
     f29 w = f29_mul<F>(a, f29_one<F>());     // = a mod p, value < (1 + 16 p / 2^261) p < 2p

@@ -68,7 +68,7 @@ FP_DEV void x29q_double_mem(u32* out, const u32* a) {
     const f29 u = f29_dbl(ay);
     // level 1: v = U^2 | xx = X^2
     f29 op = (role & 1) ? ax : u;
-    f29 m = f29_mul<F>(op, op);
+    f29 m = f29_mul<F, false>(op, op);          // additive columns: 8 products of 2^30 * 2^30 in column 7 (U = 2 Y1), as in x29_double_quad
     const f29 v = f29_quad_bcast<0>(m), xx = f29_quad_bcast<1>(m);
     const f29 mm_in = f29_norm(f29_add(f29_dbl(xx), xx));
     // level 2: w = U V | s = X V | mm = M^2 | zz3 = V ZZ

@@ -24,6 +24,7 @@ MASK = (1 << B) - 1
 RBITS = B * L  # 261
 U32 = 1 << 32
 U64 = 1 << 64
+I63 = 1 << 63
 
 
 def limbs(x):
@@ -41,6 +42,9 @@ class F29:
         self.p = f.p
         self.P = limbs(f.p)
         self.INV = (-pow(f.p, -1, 1 << B)) % (1 << B)
+        self.subtractive = self.INV == MASK           # p = 1 mod 2^29 (Pasta): the product-scanning schedule subtracts m p (sub_columns)
+        assert not self.subtractive or self.P[0] == 1
+        self.col_min = self.col_max = 0                # extremes of the signed column accumulator seen so far
         self.R = (1 << RBITS) % f.p            # Montgomery one
         self.R2 = pow(1 << RBITS, 2, f.p)
         # converts: standard form (x * 2^256) <-> internal (x * 2^261)
@@ -70,8 +74,106 @@ class F29:
         return out, K
 
     # ---- primitives (mirroring the HIP code) ----
-    def mont(self, a, b):
-        """a * b * 2^-261 mod p, not fully reduced.  Result limbs normalized (< 2^29), value < a*b/2^261 + p."""
+    def sub_columns(self, prod):
+        """The subtractive product-scanning reduction of f29_montgomery_columns / columns2 / f29_mul_pair for p = 1 mod 2^29: prod[k] is the list of the
+        products of column k in issue order.  ONE signed 64-bit accumulator; m_k = acc & MASK, the carry is the arithmetic shift, the later columns get
+        -m_i P[k - i]; m_8 is biased by -2^29 and keeps its multiply-add by -P[0] = -1.  Asserts every intermediate accumulator in [-2^63, 2^63), every emitted
+        limb in [0, 2^29) and the top limb non-negative."""
+        assert self.subtractive
+        NP = [-x for x in self.P]
+        m, out, acc = [0] * L, [], 0
+
+        def step(term):
+            nonlocal acc
+            acc += term
+            assert -I63 <= acc < I63, "signed column overflow"
+            self.col_min, self.col_max = min(self.col_min, acc), max(self.col_max, acc)
+
+        for k in range(2 * L - 1):
+            for t in prod[k]:
+                assert 0 <= t < U64
+                step(t)                                   # v_mad_u64_u32
+            for i in range(L):
+                if i < k and k - i < L and self.P[k - i] != 0:
+                    assert -(1 << 31) <= m[i] < (1 << 31) and -(1 << 31) <= NP[k - i] < (1 << 31)
+                    step(m[i] * NP[k - i])                # v_mad_i64_i32
+            if k < L - 1:
+                m[k] = acc & MASK
+            elif k == L - 1:
+                m[k] = (acc & MASK) - (1 << B)           # (u32)acc | ~MASK as an int32
+                step(m[k] * NP[0])
+                assert acc & MASK == 0
+            else:
+                out.append(acc & MASK)
+            acc >>= B                                     # arithmetic shift (floor), the low limb is m_k or the emitted limb
+        assert 0 <= acc < (1 << B), "top limb negative or result exceeds 2^261"
+        out.append(acc)
+        self.m_seen = m
+        return out
+
+    def os_sub(self, a, b=None):
+        """The subtractive rows of the operand-scanning schedule (f29_mul_os, or f29_sqr_os for b = None: all products first): 18 signed accumulators, each a
+        partial sum of one column in the order the HIP code adds to it -- products of the rows so far, minus the reduction terms so far, plus the carry."""
+        assert self.subtractive
+        acc = [0] * (2 * L)
+
+        def add(k, term):
+            acc[k] += term
+            assert -I63 <= acc[k] < I63, "signed column overflow"
+            self.col_min, self.col_max = min(self.col_min, acc[k]), max(self.col_max, acc[k])
+
+        def reduce_row(i):
+            m = (acc[i] & MASK) - ((1 << B) if i == L - 1 else 0)
+            for j in range(L):
+                if self.P[j] != 0 and (j > 0 or i == L - 1):
+                    add(i + j, -m * self.P[j])
+            if i == L - 1:
+                assert acc[i] & MASK == 0
+            add(i + 1, acc[i] >> B)
+
+        if b is None:
+            for i in range(L):
+                add(2 * i, a[i] * a[i])
+                for j in range(i + 1, L):
+                    add(i + j, 2 * a[i] * a[j])
+            for i in range(L):
+                reduce_row(i)
+        else:
+            for i in range(L):
+                for j in range(L):
+                    add(i + j, a[i] * b[j])
+                reduce_row(i)
+        out, c = [], 0
+        for j in range(L - 1):
+            t = acc[L + j] + c
+            assert -I63 <= t < I63
+            out.append(t & MASK)
+            c = t >> B
+        assert 0 <= acc[2 * L - 1] + c < (1 << B), "top limb negative or result exceeds 2^261"
+        return out + [acc[2 * L - 1] + c]
+
+    def sub_check(self, out_add, out_sub, T):
+        """the subtractive form against the additive one: identical limbs unless T = 0 mod 2^261, then exactly + p"""
+        if T % (1 << RBITS) != 0:
+            assert out_sub == out_add, "subtractive reduction differs from the additive one"
+        else:
+            assert value(out_sub) == value(out_add) + self.p and all(0 <= v <= MASK for v in out_sub[:8])
+        assert value(out_sub) * (1 << RBITS) % self.p == T % self.p and value(out_sub) <= T // (1 << RBITS) + self.p
+        return out_sub
+
+    def mont(self, a, b, sub=True):
+        """a * b * 2^-261 mod p, not fully reduced.  Result limbs normalized (< 2^29), value < a*b/2^261 + p.  The additive columns (every field's operand
+        scanning, BN254's product scanning); for the Pasta primes also the subtractive columns of the product-scanning schedule, whose result is returned
+        (sub=False: a call site that keeps the additive form)."""
+        out = self.mont_additive(a, b)
+        if sub and self.subtractive:
+            prod = [[a[i] * b[k - i] for i in range(L) if 0 <= k - i < L] for k in range(2 * L - 1)]
+            res = self.sub_check(out, self.sub_columns(prod), value(a) * value(b))
+            assert self.os_sub(a, b) == res            # the operand-scanning schedule (f29_lat<F>): same limbs
+            return res
+        return out
+
+    def mont_additive(self, a, b):
         assert len(a) == L and len(b) == L
         assert all(0 <= x < U32 for x in a) and all(0 <= x < U32 for x in b)
         acc = [0] * (2 * L)
@@ -132,8 +234,26 @@ class F29:
         assert value(out) < (value(a) * value(b) + value(c) * value(d)) // (1 << RBITS) + self.p + 1
         return out
 
-    def sqr(self, a):
-        """a^2 * 2^-261 with cross products taken once against the doubled operand (f29_sqr)."""
+    def sqr(self, a, sub=True):
+        """a^2 * 2^-261 with cross products taken once against the doubled operand (f29_sqr); sub as in mont."""
+        out = self.sqr_additive(a)
+        if sub and self.subtractive:
+            d = [2 * x for x in a]
+            prod = [[d[i] * a[k - i] for i in range(L) if i < k - i < L] + ([a[k // 2] * a[k // 2]] if k % 2 == 0 else []) for k in range(2 * L - 1)]
+            res = self.sub_check(out, self.sub_columns(prod), value(a) * value(a))
+            assert self.os_sub(a) == res
+            return res
+        return out
+
+    def mont_pair(self, a, b, c, d):
+        """f29_mul_pair: two multiplications in lockstep -- the columns of each are mont's"""
+        return self.mont(a, b), self.mont(c, d)
+
+    def sqr_pair(self, a, c):
+        """f29_sqr_pair (f29_montgomery_columns2): the columns of each are sqr's"""
+        return self.sqr(a), self.sqr(c)
+
+    def sqr_additive(self, a):
         assert all(0 <= x < U32 for x in a)
         d = [2 * x for x in a]
         assert all(x < U32 for x in d)
@@ -161,7 +281,7 @@ class F29:
             else:
                 assert v < (1 << B)
                 out.append(v)
-        assert out == self.mont(a, a)
+        assert out == self.mont_additive(a, a)
         return out
 
     def norm(self, a):
@@ -366,7 +486,7 @@ class XYZZ29:
         F = self.F
         X1, Y1, ZZ1, ZZZ1 = A
         U = F.dbl(Y1)                       # limbs < 2^30
-        V = F.sqr(U)
+        V = F.sqr(U, sub=False)             # additive columns: see call_site_bounds
         W = F.mont(U, V)
         S = F.mont(X1, V)
         XX = F.sqr(X1)
@@ -413,6 +533,52 @@ class XYZZ29:
         return (X3, Y3, ZZ3, ZZZ3)
 
 
+def call_site_operands(F):
+    """The largest operands each class of call site of the product-scanning multiplications admits (csrc/ec29.cuh, ntt.cuh, poly.cuh, evalh.cuh), as
+    (name, kind, operands, fits): limbs at their bound, the top limb from the value bound.  fits says whether the subtractive columns (< 2^63) hold them;
+    the call sites that do not fit keep the additive columns in the HIP code (SUB = false)."""
+    p = F.p
+    top = lambda mult: (int(mult * p) >> (B * 8)) + 1
+    norm = lambda mult: [MASK] * 8 + [top(mult)]                       # normalized limbs, value < mult p
+    loose = lambda K, mult: [MASK + K[0][i] for i in range(8)] + [top(mult)]      # x - y + K, un-normalized: x normalized, y = 0
+    two = lambda mult: [2 * MASK] * 8 + [top(mult)]                    # a sum of two normalized values / a doubled one
+    return [
+        ("normalized x normalized (poly, evalh, conversions, zero tests)", "mul", (norm(16), norm(3)), True),
+        ("add_mixed: x2 ZZ1, (p' - y2) ZZZ1", "pair", (norm(1), norm(1.1), list(F.KN[0]), norm(1.1)), True),
+        ("add_mixed: P^2, R^2 (P, R = product - coordinate + KA, normalized)", "sqr_pair", (norm(F.KA[1] // p + 3), norm(F.KA[1] // p + 3)), True),
+        ("add_mixed: P PP, X1 PP; ZZ1 PP, ZZZ1 PPP", "pair", (norm(F.KA[1] // p + 3), norm(3), norm(9.5), norm(3)), True),
+        ("add / double: R T, M T with T = Q - X3 + KA un-normalized", "mul", (norm(F.KA[1] // p + 3), loose(F.KA, F.KA[1] // p + 3)), True),
+        ("double: U V with U = 2 Y1", "mul", (two(19), norm(3)), True),
+        ("double: U^2 with U = 2 Y1 (4 cross products of 2^31 * 2^30 in column 7)", "sqr", (two(19),), False),
+        ("double_quad: U U as a multiplication (8 products of 2^30 * 2^30 in column 7)", "mul", (two(19), two(19)), False),
+        ("NTT butterfly, second stage of a round: v = u - t + KM un-normalized, canonical twiddle", "mul", (loose(F.KM, 30), norm(1)), True),
+        ("Horner step: (acc x + c) x, acc x + c a sum of two normalized values", "mul", (two(3), norm(2)), True),
+    ]
+
+
+def call_site_bounds(F, rnd):
+    """every call-site class on its largest operands and on random ones under them: the subtractive columns stay signed 64-bit where the HIP code uses
+    them; a refused class either overflows or comes closer to 2^63 than 2^35 (one carry): no margin to rely on"""
+    refused = []
+    for name, kind, ops, fits in call_site_operands(F):
+        run = {"mul": lambda o: F.mont(*o), "sqr": lambda o: F.sqr(*o), "pair": lambda o: F.mont_pair(*o), "sqr_pair": lambda o: F.sqr_pair(*o)}[kind]
+        F.col_min = F.col_max = 0
+        try:
+            run(ops)
+            ok = F.col_max < I63 - (1 << 35)
+        except AssertionError as e:
+            assert "signed column overflow" in str(e), (name, e)
+            ok = False
+        assert ok == fits, (name, ok, F.col_max.bit_length())
+        if not ok:
+            refused.append(name)
+            continue
+        for _ in range(40):
+            run(tuple([rnd.randrange(v + 1) for v in o] for o in ops))
+        assert -I63 <= F.col_min and F.col_max < I63
+    return refused
+
+
 def self_test():
     rnd = random.Random(1)
     for fname in ("pasta_fp", "pasta_fq", "bn254_fq", "bn254_fr"):
@@ -424,9 +590,12 @@ def self_test():
             assert F.dec(F.mont(F.enc(a), F.enc(b))) == a * b % p
         worst_a = [(1 << 31) + (1 << 30) - 1] * 8 + [(1 << 26)]     # loose-31 limbs, ~2^258
         worst_b = [MASK] * 8 + [1 << 26]
-        F.mont(worst_a, worst_b)
+        F.mont_additive(worst_a, worst_b)          # the additive columns' contract (60 bits); the subtractive ones': call_site_bounds
         loose30 = [(1 << 30) - 1] * 8 + [1 << 27]
-        F.mont(loose30, loose30)
+        F.mont_additive(loose30, loose30)
+        if F.subtractive:
+            refused = call_site_bounds(F, rnd)
+            print(fname, "subtractive columns: refused call sites (additive in the HIP code):", refused)
         # conversions
         for _ in range(50):
             x = rnd.randrange(p)

@@ -31,6 +31,15 @@ __global__ void NAME(u32* out, u32 seed) {                                      
 #define AND32(r) { u32 t = (u32)r; asm volatile("v_and_b32 %0, %0, %1" : "+v"(t) : "v"(b)); r = t; }
 #define MOV32(r) { u32 t = (u32)r; asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(b)); r = t; }
 #define LSHLADD64S(r) asm volatile("v_lshl_add_u64 %0, %1, 3, %0" : "+v"(r) : "v"((u64)b));
+// the multiply-adds of the Montgomery reduction: the multiplier in a VGPR, the modulus limb a constant in a scalar register
+#define MAD64S(r) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(r) : "v"(a), "s"(b) : "vcc");
+#define MADI64(r) asm volatile("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(r) : "v"(a), "v"(b) : "vcc");
+#define MADI64S(r) asm volatile("v_mad_i64_i32 %0, vcc, %1, %2, %0" : "+v"(r) : "v"(a), "s"(b) : "vcc");
+#define ASHR64(r) asm volatile("v_ashrrev_i64 %0, 3, %0" : "+v"(r));
+DEF_INT_BENCH(k_mad64s, MAD64S)
+DEF_INT_BENCH(k_madi64, MADI64)
+DEF_INT_BENCH(k_madi64s, MADI64S)
+DEF_INT_BENCH(k_ashr64, ASHR64)
 DEF_INT_BENCH(k_shr64, SHR64)
 DEF_INT_BENCH(k_shl64, SHL64)
 DEF_INT_BENCH(k_alignb, ALIGNB)
@@ -147,6 +156,10 @@ int main() {
     double ops = (double)blocks * threads * ITERS * 8;
     struct { const char* n; float ms; } rows[] = {
         {"v_mad_u64_u32", time_kernel(k_mad64, dim3(blocks), dim3(threads), d, 7u)},
+        {"v_mad_u64_u32 (sgpr)", time_kernel(k_mad64s, dim3(blocks), dim3(threads), d, 7u)},
+        {"v_mad_i64_i32", time_kernel(k_madi64, dim3(blocks), dim3(threads), d, 7u)},
+        {"v_mad_i64_i32 (sgpr)", time_kernel(k_madi64s, dim3(blocks), dim3(threads), d, 7u)},
+        {"v_ashrrev_i64", time_kernel(k_ashr64, dim3(blocks), dim3(threads), d, 7u)},
         {"v_mul_lo_u32", time_kernel(k_mullo, dim3(blocks), dim3(threads), d, 7u)},
         {"v_mul_hi_u32", time_kernel(k_mulhi, dim3(blocks), dim3(threads), d, 7u)},
         {"v_mad_u32_u24", time_kernel(k_mad24, dim3(blocks), dim3(threads), d, 7u)},

@@ -6,6 +6,7 @@
 #include "ec29.cuh"
 template <class F> __device__ void msm_emit(const xyzz29&, jacobian_t*, affine_t*) {}
 __device__ __forceinline__ void msm_tail_prio() {}
+struct dehalo_ctx;      // (msm_bred.cuh's host-side stamp hooks name it)
 #include "msm_bred.cuh"
 
 template <class CV>
