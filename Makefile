@@ -70,4 +70,9 @@ shuffle_cs_check: tests/native_host/shuffle_cs_check.cpp $(CSRC)/plonk_host.hpp 
 hostrng_check: tests/native_host/hostrng_check.cpp $(CSRC)/hostrng.hpp $(CSRC)/hostfield.hpp include/dehalo.h
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/hostrng_check tests/native_host/hostrng_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check
+# ParamsKZG's on-disk formats (csrc/params_format.hpp: host only): layouts, the header of untrusted bytes and the G2 codec, under ASan + UBSan
+# (tests/test_params_format_host.py compares it with the Python mirror)
+params_format_check: tests/native_host/params_format_check.cpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/params_format_check tests/native_host/params_format_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check

@@ -19,6 +19,28 @@ use halo2curves::bn256::{Fr, G1};
 use rand_core::RngCore;
 use std::cell::Cell;
 
+/// halo2curves' `SerdeFormat` as the library numbers it (`dehalo_serde_format`): `Processed` = compressed points, `RawBytes` = Montgomery limbs with every
+/// point checked when read, `RawBytesUnchecked` = the same bytes copied in unseen (what `read` / `write` below have always taken).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum SerdeFormat {
+    Processed,
+    RawBytes,
+    RawBytesUnchecked,
+}
+
+impl From<SerdeFormat> for sys::dehalo_serde_format {
+    fn from(f: SerdeFormat) -> Self {
+        match f {
+            SerdeFormat::Processed => sys::DEHALO_SERDE_PROCESSED,
+            SerdeFormat::RawBytes => sys::DEHALO_SERDE_RAW_BYTES,
+            SerdeFormat::RawBytesUnchecked => sys::DEHALO_SERDE_RAW_BYTES_UNCHECKED,
+        }
+    }
+}
+
+/// `DEHALO_KEEP_K`: `read_custom` keeps the file's `k`.
+const KEEP_K: u32 = 0xffff_ffff;
+
 /// `dehalo_params`: the SRS with its precomputed window tables on the device and the RawBytes image on the host.
 pub struct DehaloParamsKZG<'c> {
     pub(crate) ctx: &'c Context,
@@ -55,6 +77,39 @@ impl<'c> DehaloParamsKZG<'c> {
             sys::dehalo_params_create(ctx.as_ptr(), sys::DEHALO_CURVE_BN254_G1, k, g.as_ptr() as *const u64, g_lagrange.as_ptr() as *const u64, g2.as_ptr(), s_g2.as_ptr(), &mut raw)
         })?;
         Self::finish(ctx, raw, k)
+    }
+
+    /// `ParamsKZG::read_custom(&mut reader, format)`, and with `downsize = Some(k')` the same followed by `Params::downsize(k')` in one step: only
+    /// `g[0 .. 2^k')` is taken from the file and `g_lagrange` is the group FFT of it on the device -- a large SRS, a small circuit (`dehalo_params_read_custom`).
+    pub fn read_custom(ctx: &'c Context, bytes: &[u8], format: SerdeFormat, downsize: Option<u32>) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe {
+            sys::dehalo_params_read_custom(ctx.as_ptr(), sys::DEHALO_CURVE_BN254_G1, bytes.as_ptr(), bytes.len(), format.into(), downsize.unwrap_or(KEEP_K), &mut raw)
+        })?;
+        let k = downsize.unwrap_or_else(|| u32::from_le_bytes([bytes[0], bytes[1], bytes[2], bytes[3]]));
+        Self::finish(ctx, raw, k)
+    }
+
+    /// From `g`, `g2` and `s_g2` alone: `g_lagrange = g_to_lagrange(g, k)` on the device (`dehalo_params_from_g`), as upstream's `from_parts` with `g_lagrange: None`.
+    pub fn from_g(ctx: &'c Context, k: u32, g: &[halo2curves::bn256::G1Affine], g2: &[u8; 128], s_g2: &[u8; 128]) -> Result<Self, DehaloError> {
+        assert_eq!(g.len(), 1usize << k);
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe { sys::dehalo_params_from_g(ctx.as_ptr(), sys::DEHALO_CURVE_BN254_G1, k, g.as_ptr() as *const u64, g2.as_ptr(), s_g2.as_ptr(), &mut raw) })?;
+        Self::finish(ctx, raw, k)
+    }
+
+    /// `Params::downsize(k)` as a new object; `self` stays as it is (`dehalo_params_downsize`).
+    pub fn downsize(&self, k: u32) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        self.ctx.check(unsafe { sys::dehalo_params_downsize(self.ctx.as_ptr(), self.raw, k, &mut raw) })?;
+        Self::finish(self.ctx, raw, k)
+    }
+
+    /// `params.write_custom(&mut writer, format)` (`dehalo_params_write_custom`); `Processed` compresses the points on the device.
+    pub fn write_custom(&self, format: SerdeFormat) -> Result<Vec<u8>, DehaloError> {
+        let mut out = vec![0u8; unsafe { sys::dehalo_params_size_custom(self.raw, format.into()) }];
+        self.ctx.check(unsafe { sys::dehalo_params_write_custom(self.raw, format.into(), out.as_mut_ptr(), out.len()) })?;
+        Ok(out)
     }
 
     fn finish(ctx: &'c Context, raw: *mut sys::dehalo_params, k: u32) -> Result<Self, DehaloError> {
@@ -164,6 +219,13 @@ impl<'c> DehaloParamsIPA<'c> {
         ctx.check(unsafe { sys::dehalo_params_ipa_read(ctx.as_ptr(), sys::DEHALO_CURVE_VESTA, bytes.as_ptr(), bytes.len(), &mut raw) })?;
         let k = if bytes.len() >= 4 { u32::from_le_bytes([bytes[0], bytes[1], bytes[2], bytes[3]]) } else { 0 };
         Ok(Self { ctx, raw, k })
+    }
+
+    /// `Params::downsize(k)` as a new object with its own table of `W`; `self` stays as it is (`dehalo_params_downsize`)
+    pub fn downsize(&self, k: u32) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        self.ctx.check(unsafe { sys::dehalo_params_downsize(self.ctx.as_ptr(), self.raw, k, &mut raw) })?;
+        Ok(Self { ctx: self.ctx, raw, k })
     }
 
     /// `params.write(&mut writer)` (`dehalo_params_ipa_write`)

@@ -36,6 +36,8 @@ SYMBOLS = [
     "dehalo_graph_create", "dehalo_graph_release", "dehalo_graph_evaluate_device", "dehalo_graph_evaluate_batch_device", "dehalo_permutation_h_device", "dehalo_lookup_h_device",
     "dehalo_check_witness", "dehalo_check_witness_challenges", "dehalo_create_proof_phased", "dehalo_pk_phases",
     "dehalo_prover_create_multi", "dehalo_create_proof_multi", "dehalo_shuffle_h_batch_device",
+    "dehalo_points_compress_device", "dehalo_points_decompress_device", "dehalo_points_check_device",
+    "dehalo_params_size_custom", "dehalo_params_write_custom", "dehalo_params_read_custom", "dehalo_params_from_g", "dehalo_params_downsize",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -260,6 +262,15 @@ def load_library():
     lib.dehalo_params_ipa_size.restype = sz
     lib.dehalo_params_ipa_write.argtypes = [P, P, sz]
     lib.dehalo_params_ipa_read.argtypes = [P, C.c_int, P, sz, PP]
+    lib.dehalo_points_compress_device.argtypes = [P, C.c_int, u64p, sz, P, P]
+    lib.dehalo_points_decompress_device.argtypes = [P, C.c_int, P, sz, u64p, C.POINTER(C.c_uint32), P]
+    lib.dehalo_points_check_device.argtypes = [P, C.c_int, u64p, sz, C.POINTER(C.c_uint32), P]
+    lib.dehalo_params_size_custom.argtypes = [P, C.c_int]
+    lib.dehalo_params_size_custom.restype = sz
+    lib.dehalo_params_write_custom.argtypes = [P, C.c_int, P, sz]
+    lib.dehalo_params_read_custom.argtypes = [P, C.c_int, P, sz, C.c_int, u32, PP]
+    lib.dehalo_params_from_g.argtypes = [P, C.c_int, u32, u64p, P, P, PP]
+    lib.dehalo_params_downsize.argtypes = [P, P, u32, PP]
     lib.dehalo_keygen.argtypes = [P, P, C.POINTER(CConstraintSystem), u64p, u64p, C.POINTER(C.c_void_p), u32, u32, PP]
     lib.dehalo_pk_read.argtypes = [P, C.c_int, C.POINTER(CConstraintSystem), P, sz, u32, PP]
     lib.dehalo_pk_size.argtypes = [P]
@@ -497,6 +508,24 @@ class Context:
     def g_to_lagrange(self, curve: int, d_g: int, k: int, d_out: Optional[int] = None, stream: int = 0):
         """g_to_lagrange: d_out[i] = [n^-1] sum_j [omega^(-i j)] d_g[j] over 2^k affine points (64 B each, device); d_out None: in place"""
         self._check(self.lib.dehalo_g_to_lagrange_device(self.handle, curve, d_g, k, d_g if d_out is None else d_out, stream or None))
+
+    def points_compress(self, curve: int, d_affine: int, count: int, d_out32: int, stream: int = 0):
+        """GroupEncoding::to_bytes of `count` affine points (64 B each, device) into 32-byte encodings at d_out32 (device); one launch, asynchronous"""
+        self._check(self.lib.dehalo_points_compress_device(self.handle, curve, d_affine or None, count, d_out32 or None, stream or None))
+
+    def points_decompress(self, curve: int, d_in32: int, count: int, d_affine: int, stream: int = 0) -> int:
+        """GroupEncoding::from_bytes of `count` 32-byte encodings (device) into affine points at d_affine (device) -> the status bits: 1 = an x not below the
+        modulus, 2 = an x not on the curve, 4 = x = 0 with the sign bit set; 0 = every encoding was a point"""
+        st = C.c_uint32(0)
+        self._check(self.lib.dehalo_points_decompress_device(self.handle, curve, d_in32 or None, count, d_affine or None, C.byref(st), stream or None))
+        return st.value
+
+    def points_check(self, curve: int, d_affine: int, count: int, stream: int = 0) -> int:
+        """a checked from_raw_bytes over `count` affine points (device, read only) -> the status bits: 1 = a coordinate's stored word is not below the modulus,
+        2 = a point neither on the curve nor (0, 0)"""
+        st = C.c_uint32(0)
+        self._check(self.lib.dehalo_points_check_device(self.handle, curve, d_affine or None, count, C.byref(st), stream or None))
+        return st.value
 
     def blind_commitments_device(self, curve: int, d_jacobian: int, d_blinds: int, count: int, d_w_affine: int, stream: int = 0):
         """ParamsIPA's blinding term for one batched MSM's results: d_jacobian[i] += [d_blinds[i]] W, in place (all device pointers; one launch)"""

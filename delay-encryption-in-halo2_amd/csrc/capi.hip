@@ -277,6 +277,31 @@ int register_entry(dehalo_ctx* ctx, int curve, const uint64_t* affine_xy, size_t
 
 }  // namespace
 
+// ---- the point codec (gfft.cuh): GroupEncoding::to_bytes / from_bytes and the checked from_raw_bytes over vectors of points ----
+namespace {
+// the argument checks the three calls share; ops stays null when the call has nothing to launch (count = 0)
+int points_codec_args(dehalo_ctx* ctx, const char* who, int curve, const void* d_affine, const void* d_bytes32, size_t count, const GfftOps** ops) {
+    *ops = nullptr;
+    const GfftOps* o = gfft_ops(curve);
+    if (!o) return unknown_curve(ctx);
+    if (count >= ((size_t)1 << 29)) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": too many points");
+    if (count == 0) return 0;
+    if (!d_affine || ((uintptr_t)d_affine & 15)) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": the points are null or not 16-byte aligned");
+    if (d_bytes32 && ((uintptr_t)d_bytes32 & 3)) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": the encodings are not 4-byte aligned");
+    *ops = o;
+    return 0;
+}
+// zero the context's status word on s, run `launch` with it, bring it to the host: the one host wait of a call that reports a status
+template <class Launch>
+int points_status(dehalo_ctx* ctx, uint32_t* status_out, hipStream_t s, Launch&& launch) {
+    TRY(dh_ensure(ctx, ctx->ws_codec, 16));
+    uint32_t* d_status = (uint32_t*)ctx->ws_codec.p;
+    HIP_TRY(ctx, hipMemsetAsync(d_status, 0, 4, s));
+    TRY(launch(d_status));
+    return dh_d2h(ctx, status_out, d_status, 4, s);
+}
+}   // namespace
+
 const IpaOps* ipa_ops(int curve) {
     if (curve == DEHALO_CURVE_PALLAS) return &pallas_ipa_ops();
     if (curve == DEHALO_CURVE_VESTA) return &vesta_ipa_ops();
@@ -627,6 +652,40 @@ int dehalo_g_to_lagrange_device(dehalo_ctx* ctx, int curve, const uint64_t* d_g_
             return 0;
         }
         return ops->g_to_lagrange(ctx, (const affine_t*)d_g_affine_xy, k, omega_inv.v, n_inv.v, (affine_t*)d_out_affine_xy, s);
+    });
+}
+
+// ---- the point codec (gfft.cuh; its argument checks: points_codec_args above) ----
+int dehalo_points_compress_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t count, uint8_t* d_out32, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    const GfftOps* ops;
+    TRY(points_codec_args(ctx, "points_compress", curve, d_affine_xy, d_out32, count, &ops));
+    if (!ops) return 0;
+    if (!d_out32) return dh_fail(ctx, DEHALO_ERR_INVALID, "points_compress: null output");
+    return dh_device(ctx, stream, [&](hipStream_t s) { return ops->compress(ctx, (const affine_t*)d_affine_xy, d_out32, count, s); });
+}
+
+int dehalo_points_decompress_device(dehalo_ctx* ctx, int curve, const uint8_t* d_in32, size_t count, uint64_t* d_affine_xy, uint32_t* status_out, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    const GfftOps* ops;
+    TRY(points_codec_args(ctx, "points_decompress", curve, d_affine_xy, d_in32, count, &ops));
+    if (status_out) *status_out = 0;
+    if (!ops) return 0;
+    if (!d_in32 || !status_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "points_decompress: null argument");
+    return dh_device(ctx, stream, [&](hipStream_t s) {
+        return points_status(ctx, status_out, s, [&](uint32_t* d_status) { return ops->decompress(ctx, d_in32, (affine_t*)d_affine_xy, count, d_status, s); });
+    });
+}
+
+int dehalo_points_check_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t count, uint32_t* status_out, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    const GfftOps* ops;
+    TRY(points_codec_args(ctx, "points_check", curve, d_affine_xy, nullptr, count, &ops));
+    if (status_out) *status_out = 0;
+    if (!ops) return 0;
+    if (!status_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "points_check: null status");
+    return dh_device(ctx, stream, [&](hipStream_t s) {
+        return points_status(ctx, status_out, s, [&](uint32_t* d_status) { return ops->points_check(ctx, (const affine_t*)d_affine_xy, count, d_status, s); });
     });
 }
 

@@ -261,7 +261,65 @@ int decompress_t(dehalo_ctx* ctx, const uint8_t* d_in, affine_t* d_out, uint64_t
     return 0;
 }
 
+// ---- GroupEncoding::to_bytes for a vector of points, the inverse of k_decompress: in = affine standard Montgomery, out = 32 B per point (x little-endian
+// canonical, bit 255 = y is odd, (0, 0) -> all zero).  One lane per point: two f_from_mont (reduction rows only, no multiplication), no scratch.
+template <class CV>
+__global__ __launch_bounds__(128) void k_compress(const affine_t* __restrict__ in, u32* __restrict__ out, u32 count) {
+    typedef typename CV::Base F;
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const affine_t a = aff_load(&in[i]);
+    fe x = f_zero();
+    if (!aff_is_identity(a)) {
+        x = f_from_mont<F>(a.x);
+        x.v[7] |= (f_from_mont<F>(a.y).v[0] & 1u) << 31;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) out[(u64)i * 8 + j] = x.v[j];
+}
+
+template <class CV>
+int compress_t(dehalo_ctx* ctx, const affine_t* d_in, uint8_t* d_out, uint64_t count, hipStream_t s) {
+    if (count == 0) return 0;
+    k_compress<CV><<<(u32)((count + 127) / 128), 128, 0, s>>>(d_in, (u32*)d_out, (u32)count);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
+// ---- what a checked from_raw_bytes does per point [UPSTREAM halo2curves SerdeObject::from_raw_bytes: each coordinate's stored word below the modulus,
+// then is_on_curve, which the identity passes]: in = affine standard Montgomery as it arrived, read only.  status[0] |= 1: a coordinate's stored word is
+// not below p; 2: neither on y^2 = x^3 + b nor (0, 0).  One lane per point, three multiplications (a lane with status 1 makes none: f_mul wants operands
+// below p), no scratch.
+template <class F>
+FP_DEV bool f_below_p(const fe& a) {
+    bool below = false, decided = false;
+#pragma unroll
+    for (int j = 7; j >= 0; j--)
+        if (!decided && a.v[j] != F::P[j]) { below = a.v[j] < F::P[j]; decided = true; }
+    return below;
+}
+
+template <class CV>
+__global__ __launch_bounds__(128) void k_points_check(const affine_t* __restrict__ in, u32 count, u32* status) {
+    typedef typename CV::Base F;
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const affine_t a = aff_load(&in[i]);
+    if (!f_below_p<F>(a.x) || !f_below_p<F>(a.y)) { atomicOr(status, 1u); return; }
+    if (aff_is_identity(a)) return;
+    const fe rhs = f_add<F>(f_mul<F>(f_sqr<F>(a.x), a.x), f_const<F>(CV::B_M));
+    if (!f_eq(f_sqr<F>(a.y), rhs)) atomicOr(status, 2u);
+}
+
+template <class CV>
+int points_check_t(dehalo_ctx* ctx, const affine_t* d_in, uint64_t count, uint32_t* d_status, hipStream_t s) {
+    if (count == 0) return 0;
+    k_points_check<CV><<<(u32)((count + 127) / 128), 128, 0, s>>>(d_in, (u32)count, d_status);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 template <class CV>
 constexpr GfftOps make_gfft_ops() {
-    return {&gfft_t<CV>, &decompress_t<CV>};
+    return {&gfft_t<CV>, &decompress_t<CV>, &compress_t<CV>, &points_check_t<CV>};
 }

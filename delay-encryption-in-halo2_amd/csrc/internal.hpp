@@ -58,7 +58,7 @@ struct dehalo_ctx {
     std::recursive_mutex mu;   // recursive: host-buffer entry points hold it across their device-form calls
     // workspace (grow-only)
     DevBuf ws_scalars, ws_out, ws_count, ws_counters, ws_off, ws_records, ws_merge_lists, ws_merge_parts, ws_bhist, ws_pcount, ws_pairs, ws_bsum, ws_idx, ws_partial0, ws_buckets,
-        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3];
+        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3], ws_codec;
     std::vector<TwiddleEntry> twiddles;
     affine_t* msm_affine_out = nullptr;   // set for the duration of dehalo_msm_device_affine (under mu): k_msm_final also writes affine points
     int msm_acc_points = 48; // > 0: the accumulation's grid is 4, 6, 8, ... layers of one wave per SIMD, the fewest that leave a lane <= this many
@@ -307,12 +307,16 @@ struct IpaOps {
 const IpaOps& pallas_ipa_ops();
 const IpaOps& vesta_ipa_ops();
 const IpaOps* ipa_ops(int curve);       // capi.hip: null unless Pallas / Vesta
-// g_to_lagrange (the group FFT) and point decompression, one table per curve (gfft.cuh, instantiated in msm_*.hip)
+// g_to_lagrange (the group FFT) and the point codec (decompress, compress, check), one table per curve (gfft.cuh, instantiated in msm_*.hip)
 struct GfftOps {
     // d_out = g_to_lagrange(d_g): 2^k affine points, 1 <= k; d_out == d_g or disjoint; omega_inv standard Montgomery, n_inv canonical (4 x u64 each)
     int (*g_to_lagrange)(dehalo_ctx* ctx, const affine_t* d_g, uint32_t k, const uint64_t omega_inv[4], const uint64_t n_inv_canon[4], affine_t* d_out, hipStream_t s);
     // GroupEncoding::from_bytes of `count` 32-byte encodings (4-byte aligned) into affine points; d_status[0] |= 1 (x >= p) | 2 (not on the curve) | 4 (x = 0, sign set)
     int (*decompress)(dehalo_ctx* ctx, const uint8_t* d_in, affine_t* d_out, uint64_t count, uint32_t* d_status, hipStream_t s);
+    // GroupEncoding::to_bytes of `count` affine points into 32-byte encodings (4-byte aligned): the inverse of decompress
+    int (*compress)(dehalo_ctx* ctx, const affine_t* d_in, uint8_t* d_out, uint64_t count, hipStream_t s);
+    // a checked from_raw_bytes over `count` affine points, read only; d_status[0] |= 1 (a coordinate's word >= p) | 2 (neither on the curve nor (0, 0))
+    int (*points_check)(dehalo_ctx* ctx, const affine_t* d_in, uint64_t count, uint32_t* d_status, hipStream_t s);
 };
 const GfftOps& bn254_gfft_ops();
 const GfftOps& pallas_gfft_ops();

@@ -1,10 +1,11 @@
-// params.hip -- the commitment schemes' parameters, the transcript and the IPA opening argument behind the C ABI: ParamsKZG (setup / read / write),
-// ParamsIPA, Blake2bWrite, commitment::create_proof of ParamsIPA and the scalar draws [UPSTREAM halo2_proofs @ v2023_04_20: poly/kzg/commitment.rs,
+// params.hip -- the commitment schemes' parameters, the transcript and the IPA opening argument behind the C ABI: ParamsKZG (setup / read / write,
+// the three SerdeFormats, from_g, downsize), ParamsIPA, Blake2bWrite, commitment::create_proof of ParamsIPA and the scalar draws [UPSTREAM halo2_proofs @ v2023_04_20: poly/kzg/commitment.rs,
 // poly/ipa/commitment.rs, poly/ipa/commitment/prover.rs, transcript.rs] -- the calls the reference makes at benches/delay_enc.rs:41-54 (params) and,
 // through create_proof, :120-134 (the Blake2bWrite transcript).
 // C entry points run under dh_guard and the column work goes through the library's device entry points, as in prover.hip; the one kernel here is the ChaCha20 draw.
 #include <memory>
 
+#include "params_format.hpp"
 #include "whole_call.hpp"
 
 namespace {
@@ -75,57 +76,7 @@ extern "C" int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, cons
     });
 }
 
-// ---- ParamsKZG::setup: the two G2 points on the host (O(1): one 254-bit scalar multiplication over Fq2 = Fq[i] / (i^2 + 1)) -------------------
-namespace {
-struct Fq2 { Fe a, b; };
-struct G2Host {
-    const HostField* q;
-    explicit G2Host(const HostField* f) : q(f) {}
-    Fq2 add(const Fq2& x, const Fq2& y) const { return {q->add(x.a, y.a), q->add(x.b, y.b)}; }
-    Fq2 sub(const Fq2& x, const Fq2& y) const { return {q->sub(x.a, y.a), q->sub(x.b, y.b)}; }
-    Fq2 mul(const Fq2& x, const Fq2& y) const { return {q->sub(q->mul(x.a, y.a), q->mul(x.b, y.b)), q->add(q->mul(x.a, y.b), q->mul(x.b, y.a))}; }
-    Fq2 inv(const Fq2& x) const {
-        const Fe d = q->invert(q->add(q->sqr(x.a), q->sqr(x.b)));
-        return {q->mul(x.a, d), q->neg(q->mul(x.b, d))};
-    }
-    bool is_zero(const Fq2& x) const { return x.a.is_zero() && x.b.is_zero(); }
-    struct Pt { Fq2 x, y; bool inf; };
-    Pt padd(const Pt& P, const Pt& Q) const {      // affine chord-and-tangent (a = 0): 381 inversions for one scalar multiplication are nothing here
-        if (P.inf) return Q;
-        if (Q.inf) return P;
-        Fq2 lam;
-        if (is_zero(sub(P.x, Q.x))) {
-            if (is_zero(add(P.y, Q.y))) return Pt{{}, {}, true};
-            const Fq2 xx = mul(P.x, P.x);
-            lam = mul(add(add(xx, xx), xx), inv(add(P.y, P.y)));
-        } else lam = mul(sub(Q.y, P.y), inv(sub(Q.x, P.x)));
-        Pt R;
-        R.inf = false;
-        R.x = sub(sub(mul(lam, lam), P.x), Q.x);
-        R.y = sub(mul(lam, sub(P.x, R.x)), P.y);
-        return R;
-    }
-    Pt scalar_mul(const uint64_t k_canonical[4], Pt P) const {
-        Pt acc{{}, {}, true};
-        for (int i = 0; i < 256; i++) {
-            if ((k_canonical[i >> 6] >> (i & 63)) & 1) acc = padd(acc, P);
-            P = padd(P, P);
-        }
-        return acc;
-    }
-    void to_raw(const Pt& P, uint8_t out[128]) const {      // G2Affine RawBytes: x.c0 | x.c1 | y.c0 | y.c1, Montgomery limbs; all zero = identity
-        memset(out, 0, 128);
-        if (P.inf) return;
-        memcpy(out, P.x.a.v, 32); memcpy(out + 32, P.x.b.v, 32); memcpy(out + 64, P.y.a.v, 32); memcpy(out + 96, P.y.b.v, 32);
-    }
-};
-// the generator of BN254's G2 (halo2curves bn256::G2Affine::generator(); canonical limbs)
-const uint64_t BN254_G2_GEN[4][4] = {{0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull},
-                                     {0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull},
-                                     {0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull},
-                                     {0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull}};
-}   // namespace
-
+// ---- ParamsKZG::setup: the two G2 points on the host (O(1): one 254-bit scalar multiplication over Fq2 = Fq[i] / (i^2 + 1); G2Host and the generator: params_format.hpp) ----
 extern "C" int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s[4], dehalo_params** out) {
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !out || !s) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_setup: null argument");
@@ -160,11 +111,7 @@ extern "C" int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const
         {   // g2 = the generator, s_g2 = [s] g2
             const HostField* q = host_field(curve_base_field(curve));
             G2Host g2(q);
-            G2Host::Pt G;
-            G.inf = false;
-            Fe c[4];
-            for (int i = 0; i < 4; i++) { memcpy(c[i].v, BN254_G2_GEN[i], 32); c[i] = q->from_canonical(c[i]); }
-            G.x = {c[0], c[1]}; G.y = {c[2], c[3]};
+            const G2Host::Pt G = bn254_g2_generator(q);
             const Fe sc = f->to_canonical(sm);
             g2.to_raw(G, p->g2);
             g2.to_raw(g2.scalar_mul(sc.v, G), p->s_g2);
@@ -396,6 +343,182 @@ extern "C" int dehalo_params_ipa_read(dehalo_ctx* ctx, int curve, const uint8_t*
         std::vector<uint64_t> host(8 * count);
         TRY(dehalo_download(ctx, pts.p, 64 * count, host.data()));
         return ipa_params_finish(ctx, curve, k, host.data(), host.data() + 8 * n, host.data() + 16 * n, host.data() + 16 * n + 8, out);
+    });
+}
+
+// ================================================================================================ ParamsKZG from any SRS
+// SerdeFormat read / write, ParamsKZG from g alone, Params::downsize [UPSTREAM halo2_proofs/src/poly/kzg/commitment.rs: write_custom, read_custom, from_parts,
+// downsize; poly/ipa/commitment.rs: downsize].  Layout, header and the two G2 points: params_format.hpp, on the host; the G1 vectors: the point codec and the
+// group FFT, on the device (gfft.cuh).
+namespace {
+
+// ParamsKZG over g and g_lagrange as they stand on the device (2^k affine points each, standard Montgomery): both tables registered from there, the
+// host copies downloaded -- what dehalo_params_setup does with its own two vectors
+int kzg_from_device(dehalo_ctx* ctx, int curve, uint32_t k, const affine_t* d_g, const affine_t* d_gl, const uint8_t* g2, const uint8_t* s_g2, dehalo_params** out) {
+    const size_t n = (size_t)1 << k;
+    std::unique_ptr<dehalo_params> p(new dehalo_params);
+    p->ctx = ctx; p->curve = curve; p->k = k; p->n = n;
+    if (g2) memcpy(p->g2, g2, 128);
+    if (s_g2) memcpy(p->s_g2, s_g2, 128);
+    TRY(dehalo_bases_register_device(ctx, curve, (const uint64_t*)d_g, n, 0, 1, adopt(ctx, p->bases_g)));
+    TRY(dehalo_bases_register_device(ctx, curve, (const uint64_t*)d_gl, n, 0, 1, adopt(ctx, p->bases_gl)));
+    p->g.resize(8 * n); p->g_lagrange.resize(8 * n);
+    TRY(dehalo_download(ctx, d_g, 64 * n, p->g.data()));
+    TRY(dehalo_download(ctx, d_gl, 64 * n, p->g_lagrange.data()));
+    *out = p.release();
+    return 0;
+}
+
+// the range checks of a ParamsKZG built here, before any device work: the two precomputed tables must fit (as dehalo_params_setup checks)
+int kzg_params_check(dehalo_ctx* ctx, const std::string& who, int curve, uint32_t k) {
+    const HostField* f = host_field(curve_scalar_field(curve));
+    if (!f) return dh_fail(ctx, DEHALO_ERR_INVALID, who + ": unknown curve");
+    if (k > PARAMS_MAX_K || k > f->two_adicity) return dh_fail(ctx, DEHALO_ERR_INVALID, who + ": k out of range");
+    if (!dh_precomputed_table_fits(curve, (size_t)1 << k)) return dh_fail(ctx, DEHALO_ERR_INVALID, who + ": 2^k x windows >= 2^30: precomputed table too large");
+    return 0;
+}
+
+const char* point_status_text(uint32_t status, bool encodings) {
+    if (status & POINT_NOT_BELOW_P) return encodings ? "an x coordinate is not below the modulus" : "a coordinate's stored word is not below the modulus";
+    if (status & POINT_ZERO_X_SIGNED) return "x = 0 with the sign bit set is not an encoding";
+    if (status & POINT_NOT_ON_CURVE) return encodings ? "an x coordinate is not on the curve" : "a point is neither on the curve nor the identity";
+    return "";
+}
+
+// one G2 point of a file into the 128 raw bytes the params keep, validated as the format asks
+int g2_read(dehalo_ctx* ctx, const G2Host& g2, int format, const uint8_t* in, uint8_t raw[128]) {
+    int status = 0;
+    if (format == DEHALO_SERDE_PROCESSED) status = g2.decompress_raw(in, raw);
+    else {
+        memcpy(raw, in, 128);
+        G2Host::Pt P;
+        if (format == DEHALO_SERDE_RAW_BYTES) status = g2.from_raw_checked(raw, P);
+    }
+    if (status) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string("params_read_custom: G2: ") + point_status_text((uint32_t)status, format == DEHALO_SERDE_PROCESSED));
+    return 0;
+}
+
+}   // namespace
+
+extern "C" size_t dehalo_params_size_custom(const dehalo_params* p, int format) {
+    ParamsLayout L;
+    return p && p->scheme == DEHALO_SCHEME_KZG && params_layout(format, p->k, L) ? L.size : 0;
+}
+
+extern "C" int dehalo_params_write_custom(const dehalo_params* p, int format, uint8_t* out, size_t cap) {
+    return dh_guard(p ? p->ctx : nullptr, [&]() -> int {
+        if (!p || !out) return DEHALO_ERR_INVALID;
+        dehalo_ctx* ctx = p->ctx;
+        if (p->scheme != DEHALO_SCHEME_KZG) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_write_custom: ParamsIPA has one format (dehalo_params_ipa_write)");
+        ParamsLayout L;
+        if (!params_layout(format, p->k, L)) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_write_custom: unknown format");
+        if (cap < L.size) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_write_custom: buffer too small");
+        if (format != DEHALO_SERDE_PROCESSED) return dehalo_params_write(p, out, cap);      // both raw formats: the same bytes
+        if (curve_base_field(p->curve) != DEHALO_FIELD_BN254_FQ) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_write_custom: the G2 encoding is BN254's");
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        for (int i = 0; i < 4; i++) out[i] = (uint8_t)(p->k >> (8 * i));
+        // one vector at a time: up as the host copy, compressed by one lane per point, down at 32 B per point
+        DevMem pts, enc;
+        TRY(pts.alloc(ctx, 2 * L.n, false));
+        TRY(enc.alloc(ctx, L.n, false));
+        const std::vector<uint64_t>* vec[2] = {&p->g, &p->g_lagrange};
+        const size_t off[2] = {L.off_g, L.off_gl};
+        for (int v = 0; v < 2; v++) {
+            TRY(dh_h2d(ctx, pts.p, vec[v]->data(), 64 * L.n, ctx->stream.get()));
+            TRY(dehalo_points_compress_device(ctx, p->curve, pts.u64(), L.n, (uint8_t*)enc.p, ctx->stream.get()));
+            TRY(dehalo_download(ctx, enc.p, 32 * L.n, out + off[v]));
+        }
+        const G2Host g2(host_field(DEHALO_FIELD_BN254_FQ));
+        g2.compress_raw(p->g2, out + L.off_g2);
+        g2.compress_raw(p->s_g2, out + L.off_sg2);
+        return 0;
+    });
+}
+
+extern "C" int dehalo_params_read_custom(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, int format, uint32_t downsize_k, dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !bytes || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read_custom: null argument");
+        ParamsLayout L;
+        const ParamsHeaderError he = params_parse_header(bytes, len, format, L);
+        if (he != PARAMS_HEADER_OK) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string("params_read_custom: ") + params_header_error_text(he));
+        const bool keep = downsize_k == DEHALO_KEEP_K;
+        if (!keep && downsize_k > L.k) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_read_custom: downsize_k is above the file's k");
+        if (keep && format == DEHALO_SERDE_RAW_BYTES_UNCHECKED) return dehalo_params_read(ctx, curve, bytes, len, out);
+        const uint32_t k = keep ? L.k : downsize_k;
+        TRY(kzg_params_check(ctx, "params_read_custom", curve, k));
+        if (curve_base_field(curve) != DEHALO_FIELD_BN254_FQ && format != DEHALO_SERDE_RAW_BYTES_UNCHECKED)
+            return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "params_read_custom: the G2 encoding and its curve are BN254's");
+        // the two G2 points, on the host
+        uint8_t g2raw[128], sg2raw[128];
+        {
+            const G2Host g2(host_field(DEHALO_FIELD_BN254_FQ));
+            TRY(g2_read(ctx, g2, format, bytes + L.off_g2, g2raw));
+            TRY(g2_read(ctx, g2, format, bytes + L.off_sg2, sg2raw));
+        }
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        // the G1 points that are kept: g | g_lagrange (adjacent in the file), or the first 2^k of g alone -- the rest of the file is never read
+        const size_t n = (size_t)1 << k, count = keep ? 2 * n : n;
+        DevMem pts, enc, gl;
+        TRY(pts.alloc(ctx, 2 * count, false));
+        uint32_t status = 0;
+        if (format == DEHALO_SERDE_PROCESSED) {
+            TRY(enc.alloc(ctx, count, false));
+            TRY(dh_h2d(ctx, enc.p, bytes + L.off_g, 32 * count, ctx->stream.get()));
+            TRY(dehalo_points_decompress_device(ctx, curve, (const uint8_t*)enc.p, count, pts.u64(), &status, ctx->stream.get()));
+        } else {
+            TRY(dh_h2d(ctx, pts.p, bytes + L.off_g, 64 * count, ctx->stream.get()));
+            if (format == DEHALO_SERDE_RAW_BYTES) TRY(dehalo_points_check_device(ctx, curve, pts.u64(), count, &status, ctx->stream.get()));
+        }
+        if (status) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string("params_read_custom: ") + point_status_text(status, format == DEHALO_SERDE_PROCESSED));
+        const affine_t* d_gl = (const affine_t*)pts.at(2 * n);
+        if (!keep) {
+            TRY(gl.alloc(ctx, 2 * n, false));
+            TRY(dehalo_g_to_lagrange_device(ctx, curve, pts.u64(), k, gl.u64(), ctx->stream.get()));
+            d_gl = (const affine_t*)gl.p;
+        }
+        return kzg_from_device(ctx, curve, k, (const affine_t*)pts.p, d_gl, g2raw, sg2raw, out);
+    });
+}
+
+extern "C" int dehalo_params_from_g(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint8_t* g2, const uint8_t* s_g2, dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !out || !g) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_from_g: null argument");
+        TRY(kzg_params_check(ctx, "params_from_g", curve, k));
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const size_t n = (size_t)1 << k;
+        DevMem dg, dgl;
+        TRY(dg.alloc(ctx, 2 * n, false));
+        TRY(dgl.alloc(ctx, 2 * n, false));
+        TRY(dh_h2d(ctx, dg.p, g, 64 * n, ctx->stream.get()));
+        TRY(dehalo_g_to_lagrange_device(ctx, curve, dg.u64(), k, dgl.u64(), ctx->stream.get()));
+        return kzg_from_device(ctx, curve, k, (const affine_t*)dg.p, (const affine_t*)dgl.p, g2, s_g2, out);
+    });
+}
+
+extern "C" int dehalo_params_downsize(dehalo_ctx* ctx, const dehalo_params* p, uint32_t k, dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !p || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_downsize: null argument");
+        if (k > p->k) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_downsize: k is above the params'");
+        const bool ipa = p->scheme == DEHALO_SCHEME_IPA;
+        if (ipa) TRY(ipa_params_check(ctx, "params_downsize", p->curve, k));
+        else TRY(kzg_params_check(ctx, "params_downsize", p->curve, k));
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const size_t n = (size_t)1 << k;
+        DevMem dg, dgl;
+        TRY(dg.alloc(ctx, 2 * n, false));
+        TRY(dgl.alloc(ctx, 2 * n, false));
+        // the first 2^k of g: from the plain points ParamsIPA keeps on the device (when it is this context's device), else from the host copy
+        if (ipa && p->d_guw.p && p->ctx && p->ctx->device == ctx->device) HIP_TRY(ctx, hipMemcpyAsync(dg.p, p->d_guw.p, 64 * n, hipMemcpyDeviceToDevice, ctx->stream.get()));
+        else TRY(dh_h2d(ctx, dg.p, p->g.data(), 64 * n, ctx->stream.get()));
+        TRY(dehalo_g_to_lagrange_device(ctx, p->curve, dg.u64(), k, dgl.u64(), ctx->stream.get()));
+        if (!ipa) return kzg_from_device(ctx, p->curve, k, (const affine_t*)dg.p, (const affine_t*)dgl.p, p->g2, p->s_g2, out);
+        std::vector<uint64_t> gl(8 * n);
+        TRY(dehalo_download(ctx, dgl.p, 64 * n, gl.data()));
+        return ipa_params_finish(ctx, p->curve, k, p->g.data(), gl.data(), p->w, p->u, out);
     });
 }
 

@@ -3,7 +3,8 @@
 //
 //   example                 build / link check: one tiny best_fft (needs a GPU to run)
 //   example <dir>           <dir>/params.bin   ParamsKZG RawBytes; when it does not exist it is MADE (ParamsKZG::setup on the device) from
-//                                              <dir>/secret.bin (32 B: the scalar the reference would draw from OsRng, Montgomery form) and written
+//                                              <dir>/secret.bin (32 B: the scalar the reference would draw from OsRng, Montgomery form) and written;
+//                                              the proof then runs under the same SRS cut out of a Processed file written at k + 1 (read_custom)
 //                           <dir>/circuit.bin  u32 k | fixed columns (9 x 2^k x 32 B, Montgomery) | permutation mapping (6 x 2^k u64) |
 //                                              advice (5 x 2^k x 32 B, Montgomery) | transcript_repr (32 B) | PCG64 state, inc (2 x 16 B)
 //                           -> <dir>/pk.bin (ProvingKey RawBytes), <dir>/vk.bin, <dir>/proof.bin
@@ -94,6 +95,12 @@ int main(int argc, char** argv) {
             memcpy(s.data(), sb.data(), 32);
             params_owner.reset(new ParamsKZG(be, DEHALO_CURVE_BN254_G1, k, s));
             dump(dir + "/params.bin", params_owner->write());
+            // what a deployment does with a universal SRS: the file was written at a larger k, with compressed points; the circuit's prefix of it is read,
+            // g_lagrange comes from the group FFT -- and the proof below runs under THOSE params, which must be the ones just written
+            const std::vector<uint8_t> universal = ParamsKZG(be, DEHALO_CURVE_BN254_G1, k + 1, s).write_custom(DEHALO_SERDE_PROCESSED);
+            std::unique_ptr<ParamsKZG> cut(new ParamsKZG(ParamsKZG::read_custom(be, DEHALO_CURVE_BN254_G1, universal, DEHALO_SERDE_PROCESSED, k)));
+            if (cut->write() != params_owner->write()) throw std::runtime_error("ParamsKZG: setup(k + 1) -> write_custom(Processed) -> read_custom(downsize = k) is not setup(k)");
+            params_owner = std::move(cut);
         }
         ParamsKZG& params = *params_owner;
         const size_t n = (size_t)1 << k;

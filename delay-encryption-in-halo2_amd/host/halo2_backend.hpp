@@ -280,16 +280,44 @@ class ParamsKZG {
     }
     // ParamsKZG::setup(k, rng) with the rng's draw handed over: `s` = the secret scalar in Montgomery form (benches/delay_enc.rs:43); made on the device
     ParamsKZG(const Backend& be, dehalo_curve curve, uint32_t k, const Fe& s) : be_(be) { be_.check(dehalo_params_setup(be_.raw(), curve, k, s.data(), &p_)); }
-    ~ParamsKZG() { dehalo_params_release(be_.raw(), p_); }
+    // ParamsKZG::read_custom(reader, format), and with downsize_k = k' the same followed by Params::downsize(k') in one step: only g[0 .. 2^k') is taken
+    // from the file, g_lagrange is the group FFT of it on the device -- a large SRS and a small circuit
+    static ParamsKZG read_custom(const Backend& be, dehalo_curve curve, const std::vector<uint8_t>& bytes, dehalo_serde_format format, uint32_t downsize_k = DEHALO_KEEP_K) {
+        ParamsKZG p(be);
+        be.check(dehalo_params_read_custom(be.raw(), curve, bytes.data(), bytes.size(), format, downsize_k, &p.p_));
+        return p;
+    }
+    // from g, g2 and s_g2 alone: g_lagrange = g_to_lagrange(g) on the device
+    static ParamsKZG from_g(const Backend& be, dehalo_curve curve, uint32_t k, const std::vector<Affine>& g, const std::array<uint8_t, 128>& g2, const std::array<uint8_t, 128>& s_g2) {
+        if (g.size() != (size_t(1) << k)) throw std::invalid_argument("ParamsKZG::from_g: g.len() != 1 << k");
+        ParamsKZG p(be);
+        be.check(dehalo_params_from_g(be.raw(), curve, k, g[0].data(), g2.data(), s_g2.data(), &p.p_));
+        return p;
+    }
+    ~ParamsKZG() { if (p_) dehalo_params_release(be_.raw(), p_); }
     ParamsKZG(const ParamsKZG&) = delete;
+    ParamsKZG(ParamsKZG&& o) : be_(o.be_), p_(o.p_) { o.p_ = nullptr; }
     std::vector<uint8_t> write() const {
         std::vector<uint8_t> out(dehalo_params_size(p_));
         be_.check(dehalo_params_write(p_, out.data(), out.size()));
         return out;
     }
+    // ParamsKZG::write_custom(writer, format); Processed compresses the points on the device
+    std::vector<uint8_t> write_custom(dehalo_serde_format format) const {
+        std::vector<uint8_t> out(dehalo_params_size_custom(p_, format));
+        be_.check(dehalo_params_write_custom(p_, format, out.data(), out.size()));
+        return out;
+    }
+    // Params::downsize(k) as a new object; this one stays as it is
+    ParamsKZG downsize(uint32_t k) const {
+        ParamsKZG p(be_);
+        be_.check(dehalo_params_downsize(be_.raw(), p_, k, &p.p_));
+        return p;
+    }
     dehalo_params* raw() const { return p_; }
 
   private:
+    explicit ParamsKZG(const Backend& be) : be_(be) {}
     const Backend& be_;
     dehalo_params* p_ = nullptr;
 };
@@ -319,6 +347,12 @@ class ParamsIPAHandle {
         std::vector<uint8_t> out(dehalo_params_ipa_size(p_));
         be_.check(dehalo_params_ipa_write(p_, out.data(), out.size()));
         return out;
+    }
+    // Params::downsize(k) as a new object with its own table of W; this one stays as it is
+    ParamsIPAHandle downsize(uint32_t k) const {
+        ParamsIPAHandle p(be_);
+        be_.check(dehalo_params_downsize(be_.raw(), p_, k, &p.p_));
+        return p;
     }
     // W's window table: what every commit / commit_lagrange of these params adds [blind] W from
     FixedBase fixed_base() const { return FixedBase(be_, dehalo_params_fixed_base(p_)); }

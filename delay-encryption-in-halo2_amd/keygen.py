@@ -5,6 +5,7 @@ upstream's on-disk formats.
   ParamsKZG::{write, read}      [UPSTREAM halo2_proofs/src/poly/kzg/commitment.rs, SerdeFormat::RawBytes]
       k: u32 LE | g[0..n) | g_lagrange[0..n) | g2 | s_g2 ; a G1 point = x, y as 4 x u64 LE Montgomery limbs (64 B),
       a G2 point = x.c0, x.c1, y.c0, y.c1 (128 B).
+  ParamsKZG::{write_custom, read_custom}   [the same file in the three SerdeFormats: params_bytes / params_from_bytes, g2_compress / g2_decompress]
   ParamsIPA::{write, read}      [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs]
       k: u32 LE | g[0..n) | g_lagrange[0..n) | w | u ; a point = its 32-byte GroupEncoding (params_ipa_bytes / params_ipa_from_bytes).
   VerifyingKey::{write, read}   [UPSTREAM halo2_proofs/src/plonk.rs]
@@ -138,6 +139,209 @@ class ParamsKZG:
         gl = np.frombuffer(_exact(fh, 64 * n), dtype=np.uint64).reshape(n, 8)
         g2, s_g2 = _exact(fh, 128), _exact(fh, 128)
         return cls(ctx, curve, k, g, gl, g2, s_g2, window_bits)
+
+
+# ---- ParamsKZG::{write_custom, read_custom}: the host mirror of csrc/params_format.hpp ---------------------------------
+# [UPSTREAM halo2_proofs/src/poly/kzg/commitment.rs, halo2curves 0.3.x SerdeFormat; restated from memory like the formats above]
+#   k: u32 LE | g | g_lagrange | g2 | s_g2.  "processed": compressed points (G1 32 B: transcript.compress; G2 64 B: g2_compress); "raw" and "raw-unchecked":
+#   Montgomery limbs (G1 64 B, G2 128 B), the first validated when read.
+SERDE_FORMATS = ("processed", "raw", "raw-unchecked")
+# the generator of BN254's G2 (halo2curves bn256::G2Affine::generator()): ((x.c0, x.c1), (y.c0, y.c1)), canonical
+BN254_G2_GENERATOR = ((0x1800DEEF121F1E76426A00665E5C4479674322D4F75EDADD46DEBD5CD992F6ED, 0x198E9393920D483A7260BFB731FB5D25F1AA493335A9E71297E485B7AEF312C2),
+                      (0x12C85EA5DB8C6DEB4AAB71808DCB408FE3D1E7690C43D37B4CE6CC0166FA7DAA, 0x090689D0585FF075EC9E99AD690C3395BC4B313370B38EF355ACDADCD122975B))
+
+
+class Fq2Arith:
+    """Fq2 = Fq[i] / (i^2 + 1) over pairs of Python integers (q = 3 mod 4), and the twist y^2 = x^3 + 3 / (9 + i) that BN254's G2 lives on"""
+
+    def __init__(self, q: int):
+        assert q % 4 == 3
+        self.q = q
+        self.b = self.mul((3, 0), self.inv((9, 1)))
+
+    def add(self, x, y):
+        return ((x[0] + y[0]) % self.q, (x[1] + y[1]) % self.q)
+
+    def sub(self, x, y):
+        return ((x[0] - y[0]) % self.q, (x[1] - y[1]) % self.q)
+
+    def mul(self, x, y):
+        return ((x[0] * y[0] - x[1] * y[1]) % self.q, (x[0] * y[1] + x[1] * y[0]) % self.q)
+
+    def inv(self, x):
+        d = pow(x[0] * x[0] + x[1] * x[1], -1, self.q)
+        return (x[0] * d % self.q, -x[1] * d % self.q)
+
+    def _sqrt_fq(self, a):
+        r = pow(a, (self.q + 1) // 4, self.q)
+        return r if r * r % self.q == a % self.q else None
+
+    def sqrt(self, a):
+        """a square root of a, or None: for a1 = 0, sqrt(a0) or i sqrt(-a0); otherwise through the norm"""
+        q = self.q
+        if a[1] == 0:
+            s = self._sqrt_fq(a[0])
+            if s is not None:
+                return (s, 0)
+            s = self._sqrt_fq(-a[0] % q)
+            return None if s is None else (0, s)
+        n = self._sqrt_fq((a[0] * a[0] + a[1] * a[1]) % q)
+        if n is None:
+            return None
+        half = pow(2, -1, q)
+        x0 = self._sqrt_fq((a[0] + n) * half % q)
+        if x0 is None:
+            x0 = self._sqrt_fq((a[0] - n) * half % q)
+        if x0 is None or x0 == 0:
+            return None
+        r = (x0, a[1] * pow(2 * x0, -1, q) % q)
+        return r if self.mul(r, r) == (a[0] % q, a[1] % q) else None
+
+    def on_curve(self, P) -> bool:
+        return P is None or self.mul(P[1], P[1]) == self.add(self.mul(self.mul(P[0], P[0]), P[0]), self.b)
+
+    def point_add(self, P, Q):
+        if P is None:
+            return Q
+        if Q is None:
+            return P
+        if P[0] == Q[0]:
+            if self.add(P[1], Q[1]) == (0, 0):
+                return None
+            xx = self.mul(P[0], P[0])
+            lam = self.mul(self.add(self.add(xx, xx), xx), self.inv(self.add(P[1], P[1])))
+        else:
+            lam = self.mul(self.sub(Q[1], P[1]), self.inv(self.sub(Q[0], P[0])))
+        x = self.sub(self.sub(self.mul(lam, lam), P[0]), Q[0])
+        return (x, self.sub(self.mul(lam, self.sub(P[0], x)), P[1]))
+
+    def point_mul(self, s: int, P):
+        acc = None
+        while s:
+            if s & 1:
+                acc = self.point_add(acc, P)
+            P = self.point_add(P, P)
+            s >>= 1
+        return acc
+
+
+def g2_compress(curve: CurveSpec, P) -> bytes:
+    """G2 GroupEncoding::to_bytes: P = ((x.c0, x.c1), (y.c0, y.c1)) canonical or None -> x.c0 | x.c1 little-endian, bit 7 of byte 63 = y.c0 is odd; None: 64 zero bytes"""
+    if P is None:
+        return bytes(64)
+    b = bytearray(P[0][0].to_bytes(32, "little") + P[0][1].to_bytes(32, "little"))
+    b[63] |= (P[1][0] & 1) << 7
+    return bytes(b)
+
+
+def g2_decompress(curve: CurveSpec, data: bytes):
+    """G2 GroupEncoding::from_bytes; ValueError for an encoding that is not a point of the twist"""
+    if len(data) != 64:
+        raise ValueError("compressed G2 point must be 64 bytes")
+    q = curve.base.p
+    sign = data[63] >> 7
+    x = (int.from_bytes(data[:32], "little"), int.from_bytes(data[32:63] + bytes([data[63] & 0x7F]), "little"))
+    if x[0] >= q or x[1] >= q:
+        raise ValueError("x coordinate is not canonical")
+    if x == (0, 0):
+        if sign:
+            raise ValueError("x = 0 with the sign bit set")
+        return None
+    F2 = Fq2Arith(q)
+    y = F2.sqrt(F2.add(F2.mul(F2.mul(x, x), x), F2.b))
+    if y is None:
+        raise ValueError("not on the curve")
+    if (y[0] & 1) != sign:
+        y = ((-y[0]) % q, (-y[1]) % q)
+    return (x, y)
+
+
+def g2_to_raw(curve: CurveSpec, P) -> bytes:
+    """G2Affine RawBytes: x.c0 | x.c1 | y.c0 | y.c1 as Montgomery limbs (128 B); None: all zero"""
+    if P is None:
+        return bytes(128)
+    R, q = 1 << 256, curve.base.p
+    return b"".join((c * R % q).to_bytes(32, "little") for c in (P[0][0], P[0][1], P[1][0], P[1][1]))
+
+
+def g2_from_raw(curve: CurveSpec, raw: bytes, checked: bool = True):
+    """the inverse of g2_to_raw; checked: ValueError for a stored word not below q or a point off the twist"""
+    if len(raw) != 128:
+        raise ValueError("raw G2 point must be 128 bytes")
+    q = curve.base.p
+    w = [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(4)]
+    if checked and any(v >= q for v in w):
+        raise ValueError("a coordinate's stored word is not below the modulus")
+    if not any(w):
+        return None
+    c = [v * _rinv(q) % q for v in w]
+    P = ((c[0], c[1]), (c[2], c[3]))
+    if checked and not Fq2Arith(q).on_curve(P):
+        raise ValueError("not on the curve")
+    return P
+
+
+def _params_sizes(format: str):
+    if format not in SERDE_FORMATS:
+        raise ValueError("unknown format %r" % (format,))
+    return (32, 64) if format == "processed" else (64, 128)
+
+
+def params_size(k: int, format: str) -> int:
+    g1, g2 = _params_sizes(format)
+    return 4 + 2 * g1 * (1 << k) + 2 * g2
+
+
+def params_bytes(curve: CurveSpec, k: int, g, g_lagrange, g2: bytes, s_g2: bytes, format: str = "raw-unchecked") -> bytes:
+    """ParamsKZG::write_custom: g, g_lagrange (2^k, 8) u64 Montgomery affine; g2, s_g2 the 128 raw bytes ParamsKZG keeps (shorter: zero-padded)"""
+    from .transcript import compress
+
+    _params_sizes(format)
+    g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+    gl = np.ascontiguousarray(g_lagrange, dtype=np.uint64).reshape(-1, 8)
+    if g.shape[0] != 1 << k or gl.shape[0] != 1 << k:
+        raise ValueError("g and g_lagrange must hold 2^k points")
+    raw2 = [bytes(b).ljust(128, b"\0") for b in (g2, s_g2)]
+    if format != "processed":
+        return struct.pack("<I", k) + g.tobytes() + gl.tobytes() + raw2[0] + raw2[1]
+    pts = decode_points(curve, g) + decode_points(curve, gl)
+    return struct.pack("<I", k) + b"".join(compress(curve, P) for P in pts) + b"".join(g2_compress(curve, g2_from_raw(curve, b, checked=False)) for b in raw2)
+
+
+def params_from_bytes(curve: CurveSpec, data: bytes, format: str = "raw-unchecked"):
+    """ParamsKZG::read_custom: -> (k, g, g_lagrange, g2, s_g2) in the layout params_bytes takes; ValueError for a wrong length, k > 28, and -- "processed", "raw" --
+    anything that is not a point"""
+    from .transcript import decompress
+
+    g1, g2 = _params_sizes(format)
+    data = bytes(data)
+    if len(data) < 4:
+        raise ValueError("unexpected end of input")
+    (k,) = struct.unpack("<I", data[:4])
+    if k > 28:
+        raise ValueError("params: k out of range")
+    n = 1 << k
+    if len(data) != params_size(k, format):
+        raise ValueError("params: length does not match k")
+    o2 = 4 + 2 * g1 * n
+    tail = [data[o2:o2 + g2], data[o2 + g2:o2 + 2 * g2]]
+    if format == "processed":
+        pts = encode_points(curve, [decompress(curve, data[4 + 32 * i:36 + 32 * i]) for i in range(2 * n)])
+        raw2 = [g2_to_raw(curve, g2_decompress(curve, b)) for b in tail]
+    else:
+        pts = np.frombuffer(data[4:o2], dtype=np.uint64).reshape(2 * n, 8).copy()
+        raw2 = tail
+        if format == "raw":
+            p = curve.base.p
+            words = array_to_ints(pts.reshape(-1, 4))
+            if any(v >= p for v in words):
+                raise ValueError("a coordinate's stored word is not below the modulus")
+            for P in decode_points(curve, pts):
+                if P is not None and (P[1] * P[1] - P[0] * P[0] * P[0] - curve.b) % p:
+                    raise ValueError("not on the curve")
+            for b in tail:
+                g2_from_raw(curve, b, checked=True)
+    return k, pts[:n], pts[n:], raw2[0], raw2[1]
 
 
 # ---- ParamsIPA::{write, read} ----------------------------------------------------------------------------

@@ -20,6 +20,8 @@ RNG_OS, RNG_PCG64, RNG_CALLBACK, RNG_CHACHA20 = 0, 1, 2, 3
 KEYGEN_FIXED_CANONICAL = 1
 PROOF_ADVICE_ON_DEVICE, PROOF_ADVICE_CANONICAL = 1, 2
 CIRCUIT_DELAY_ENC, CIRCUIT_MOD_POW, CIRCUIT_POSE_ENC = 0, 1, 2
+SERDE_FORMATS = {"processed": 0, "raw": 1, "raw-unchecked": 2}      # dehalo_serde_format
+KEEP_K = 0xFFFFFFFF                                                # DEHALO_KEEP_K
 CHECK_GATE, CHECK_LOOKUP, CHECK_COPY, CHECK_SHUFFLE = 0, 1, 2, 3
 PHASES = ("advice", "lookups", "products", "random", "quotient", "evaluations", "openings", "total")
 
@@ -147,17 +149,48 @@ class ParamsKZG:
         return cls(ctx, curve, h)
 
     @classmethod
-    def read(cls, ctx: Context, curve: CurveSpec, data: bytes) -> "ParamsKZG":
+    def from_g(cls, ctx: Context, curve: CurveSpec, k: int, g, g2: bytes = b"", s_g2: bytes = b"") -> "ParamsKZG":
+        """ParamsKZG from g, g2 and s_g2 alone: g_lagrange = g_to_lagrange(g), a group FFT on the device (dehalo_params_from_g)."""
+        g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+        if g.shape[0] != 1 << k:
+            raise ValueError("g must hold 2^k points")
         h = C.c_void_p()
-        buf = np.frombuffer(data, dtype=np.uint8)
-        _check(ctx, load_library().dehalo_params_read(ctx.handle, curve.id, buf.ctypes.data, len(data), C.byref(h)))
+        b2, bs = bytes(g2).ljust(128, b"\0"), bytes(s_g2).ljust(128, b"\0")
+        _check(ctx, load_library().dehalo_params_from_g(ctx.handle, curve.id, k, g.ctypes.data, _bytes_ptr(b2), _bytes_ptr(bs), C.byref(h)))
         return cls(ctx, curve, h)
 
-    def write(self) -> bytes:
+    @classmethod
+    def read(cls, ctx: Context, curve: CurveSpec, data: bytes, format: str = "raw-unchecked", downsize: Optional[int] = None) -> "ParamsKZG":
+        """ParamsKZG::read_custom: `format` one of SERDE_FORMATS ("processed": compressed points, decompressed on the device; "raw": Montgomery limbs, every point
+        checked; "raw-unchecked": the same bytes copied in unseen).  downsize = k': read + downsize(k') in one step -- only g[0 .. 2^k') is taken from the file,
+        g_lagrange is the group FFT of it (dehalo_params_read_custom).  The defaults are dehalo_params_read."""
+        h = C.c_void_p()
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
         lib = load_library()
-        out = np.empty(lib.dehalo_params_size(self.handle), dtype=np.uint8)
-        _check(self.ctx, lib.dehalo_params_write(self.handle, out.ctypes.data, out.size))
+        if format == "raw-unchecked" and downsize is None:
+            _check(ctx, lib.dehalo_params_read(ctx.handle, curve.id, buf.ctypes.data if buf.size else None, buf.size, C.byref(h)))
+        else:
+            _check(ctx, lib.dehalo_params_read_custom(ctx.handle, curve.id, buf.ctypes.data if buf.size else None, buf.size, SERDE_FORMATS[format],
+                                                      KEEP_K if downsize is None else downsize, C.byref(h)))
+        return cls(ctx, curve, h)
+
+    def write(self, format: str = "raw-unchecked") -> bytes:
+        """ParamsKZG::write_custom (dehalo_params_write_custom); the default is dehalo_params_write, whose bytes both raw formats are."""
+        lib = load_library()
+        if format == "raw-unchecked":
+            out = np.empty(lib.dehalo_params_size(self.handle), dtype=np.uint8)
+            _check(self.ctx, lib.dehalo_params_write(self.handle, out.ctypes.data, out.size))
+        else:
+            out = np.empty(lib.dehalo_params_size_custom(self.handle, SERDE_FORMATS[format]), dtype=np.uint8)
+            _check(self.ctx, lib.dehalo_params_write_custom(self.handle, SERDE_FORMATS[format], out.ctypes.data, out.size))
         return out.tobytes()
+
+    def downsize(self, k: int):
+        """Params::downsize(k) as a new object of the same scheme: the first 2^k of g, g_lagrange by the group FFT on the device (dehalo_params_downsize).  This
+        object stays as it is and is released on its own."""
+        h = C.c_void_p()
+        _check(self.ctx, load_library().dehalo_params_downsize(self.ctx.handle, self.handle, k, C.byref(h)))
+        return type(self)(self.ctx, self.curve, h)
 
     def release(self):
         if self.handle is not None:

@@ -196,6 +196,20 @@ int dehalo_fixed_base_blind_device(dehalo_ctx* ctx, const dehalo_fixed_base* fb,
  * multiplications, k + 2 launches.  Asynchronous on the stream; workspace: 32 B x 2^(k-1) of twiddles, kept by the context. */
 int dehalo_g_to_lagrange_device(dehalo_ctx* ctx, int curve, const uint64_t* d_g_affine_xy, uint32_t k, uint64_t* d_out_affine_xy, void* stream);
 
+/* The point codec: vectors of points between their in-memory form (affine {x, y}, 64 B, standard Montgomery, (0, 0) = the identity; 16-byte aligned) and the
+ * two forms they take on disk [UPSTREAM halo2curves 0.3.x GroupEncoding, SerdeObject::from_raw_bytes; restated from memory: INTEGRATION.md section 7].  Streaming
+ * maps, one lane per point, device memory in and out, all three curves (an unknown curve is DEHALO_ERR_INVALID); count < 2^29, and count = 0 returns 0 without a
+ * launch (status 0).  The 32-byte encodings are 4-byte aligned.  Asynchronous on the stream except for a status word's download; no workspace beyond that word.
+ *   compress    GroupEncoding::to_bytes: x little-endian canonical, bit 255 = y is odd, (0, 0) -> 32 zero bytes.
+ *   decompress  GroupEncoding::from_bytes: y = sqrt(x^3 + b) with the encoded parity.  *status_out (host) collects, over all points, 1 = an x not below the
+ *               modulus, 2 = an x that is not on the curve, 4 = x = 0 with the sign bit set (x = 0 belongs to the identity, whose only encoding is
+ *               all zero).  A point that raises a bit is written as (0, 0); the call still returns 0: the status is the verdict.
+ *   check       what a checked from_raw_bytes does per point; reads only.  *status_out collects 1 = a coordinate whose stored Montgomery word is not below the
+ *               modulus, 2 = a point that is neither on y^2 = x^3 + b nor (0, 0). */
+int dehalo_points_compress_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t count, uint8_t* d_out32, void* stream);
+int dehalo_points_decompress_device(dehalo_ctx* ctx, int curve, const uint8_t* d_in32, size_t count, uint64_t* d_affine_xy, uint32_t* status_out, void* stream);
+int dehalo_points_check_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t count, uint32_t* status_out, void* stream);
+
 /* ---- NTT == halo2_proofs::arithmetic::best_fft(a, omega, log_n) ---------------------------
  * [halo2_proofs/src/arithmetic.rs].  In place, natural order in and out,
  * a'[i] = sum_j a[j] * omega^(i*j), no scaling.  a: 2^log_n x 4 u64.  omega must be a
@@ -521,6 +535,32 @@ const dehalo_fixed_base* dehalo_params_fixed_base(const dehalo_params* params);
 int dehalo_params_read(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, dehalo_params** out);
 size_t dehalo_params_size(const dehalo_params* params);
 int dehalo_params_write(const dehalo_params* params, uint8_t* out, size_t cap);
+/* ParamsKZG from any SRS [UPSTREAM halo2_proofs/src/poly/kzg/commitment.rs write_custom / read_custom / from_parts, Params::downsize; halo2curves 0.3.x SerdeFormat;
+ * restated from memory: INTEGRATION.md section 7].  The file is k: u32 LE | g | g_lagrange | g2 | s_g2 in every format:
+ *   DEHALO_SERDE_PROCESSED            compressed points: G1 32 B (the point codec above), G2 64 B (x.c0 | x.c1 little-endian canonical, bit 7 of byte 63 = y.c0 is
+ *                                     odd, the identity all zero): 4 + 64 x 2^k + 128 bytes;
+ *   DEHALO_SERDE_RAW_BYTES            Montgomery limbs, G1 64 B, G2 128 B: 4 + 128 x 2^k + 256 bytes; every point is checked when read;
+ *   DEHALO_SERDE_RAW_BYTES_UNCHECKED  the same bytes, copied in unseen: what dehalo_params_read / _write above have always read and written.
+ * size_custom / write_custom: ParamsKZG only (ParamsIPA, which has one format upstream: 0 / DEHALO_ERR_UNSUPPORTED); both raw formats write dehalo_params_write's
+ * bytes; Processed compresses g and g_lagrange on the device.
+ * read_custom with downsize_k = DEHALO_KEEP_K reads the whole file: RAW_BYTES checks all 2 x 2^k points on the device (dehalo_points_check_device) and the two G2
+ * points on the host, PROCESSED decompresses them, RAW_BYTES_UNCHECKED is dehalo_params_read.  With downsize_k <= k it is read + Params::downsize(downsize_k) in one
+ * step, for a large SRS and a small circuit: only g[0 .. 2^downsize_k) is taken from the file (checked or decompressed as the format says), g_lagrange comes from
+ * dehalo_g_to_lagrange_device, and tables of the small size alone are registered; the file's g_lagrange section is never read, so a checked format then vouches only
+ * for what was kept (and for the two G2 points).  downsize_k above the file's k is DEHALO_ERR_INVALID.  Every failure is DEHALO_ERR_INVALID with a message naming its
+ * kind -- the length, k, an x not below the modulus, an x not on the curve, x = 0 with the sign bit set, a stored coordinate word not below the modulus, a point
+ * off the curve -- leaves nothing allocated and the context usable.  Processed and the checked G2 points are BN254's (other curves: DEHALO_ERR_UNSUPPORTED).
+ * from_g: ParamsKZG from g, g2 and s_g2 alone (host pointers as dehalo_params_create takes them): g_lagrange = g_to_lagrange(g) on the device -- the KZG twin of
+ * dehalo_params_ipa_from_g.
+ * downsize: Params::downsize(k) as a NEW object (the caller keeps and releases `params`), under either scheme: the first 2^k of g, g_lagrange by the group FFT; KZG
+ * keeps g2 / s_g2, IPA keeps w / u and gets its own table of W.  k above the params' is DEHALO_ERR_INVALID; k equal to it gives an equal copy. */
+typedef enum { DEHALO_SERDE_PROCESSED = 0, DEHALO_SERDE_RAW_BYTES = 1, DEHALO_SERDE_RAW_BYTES_UNCHECKED = 2 } dehalo_serde_format;
+#define DEHALO_KEEP_K 0xffffffffu
+size_t dehalo_params_size_custom(const dehalo_params* params, int format);
+int dehalo_params_write_custom(const dehalo_params* params, int format, uint8_t* out, size_t cap);
+int dehalo_params_read_custom(dehalo_ctx* ctx, int curve, const uint8_t* bytes, size_t len, int format, uint32_t downsize_k, dehalo_params** out);
+int dehalo_params_from_g(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint8_t* g2, const uint8_t* s_g2, dehalo_params** out);
+int dehalo_params_downsize(dehalo_ctx* ctx, const dehalo_params* params, uint32_t k, dehalo_params** out);
 int dehalo_params_release(dehalo_ctx* ctx, dehalo_params* params);
 /* ParamsKZG::{commit, commit_lagrange} of `batch` device-resident columns of 2^k elements (n apart) -> affine points in HBM. */
 int dehalo_params_commit_device(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t* d_polys, size_t batch, int lagrange, uint64_t* d_out_affine, void* stream);
