@@ -29,7 +29,35 @@ struct CopyArgs {
     uint32_t log_n;
     const uint32_t* flag;       // k_check_range's: set = the mapping is not followed at all
     uint64_t* bitmap;           // [column][words]
+    uint64_t p[4];              // the field's modulus
 };
+// a - b as 4 x u64 -> the borrow
+__device__ __forceinline__ uint64_t ck_sub4(uint64_t (&r)[4], const uint64_t (&a)[4], const uint64_t (&b)[4]) {
+    uint64_t borrow = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint64_t d = a[i] - b[i], d2 = d - borrow;
+        borrow = (a[i] < b[i]) | (d < borrow);
+        r[i] = d2;
+    }
+    return borrow;
+}
+// do two stored words stand for the same element?  A witness word is any 256-bit integer and stands for its residue (dehalo.h "Non-canonical words"): the
+// larger minus the smaller is a multiple of p below 2^256, one of 0, p, .., 5p
+__device__ bool ck_same_residue(const fe& a, const fe& b, const uint64_t (&p)[4]) {
+    uint64_t x[4], y[4], d[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { x[i] = (uint64_t)a.v[2 * i] | (uint64_t)a.v[2 * i + 1] << 32; y[i] = (uint64_t)b.v[2 * i] | (uint64_t)b.v[2 * i + 1] << 32; }
+    if (ck_sub4(d, x, y)) ck_sub4(d, y, x);
+    for (int k = 0; k < 6; k++) {
+        if (!(d[0] | d[1] | d[2] | d[3])) return true;
+        uint64_t e[4];
+        if (ck_sub4(e, d, p)) return false;
+#pragma unroll
+        for (int i = 0; i < 4; i++) d[i] = e[i];
+    }
+    return false;
+}
 // one lane per cell (column blockIdx.y, row): bit = "the cell the mapping sends it to holds another value"
 __global__ __launch_bounds__(CK_THREADS) void k_check_copy(CopyArgs A) {
     const uint64_t row = (uint64_t)blockIdx.x * CK_THREADS + threadIdx.x;
@@ -42,7 +70,7 @@ __global__ __launch_bounds__(CK_THREADS) void k_check_copy(CopyArgs A) {
         uint32_t d = 0;
 #pragma unroll
         for (int w = 0; w < 8; w++) d |= a.v[w] ^ b.v[w];
-        bad = d != 0;
+        bad = d != 0 && !ck_same_residue(a, b, A.p);      // (equal words, the case of every witness halo2curves writes, decide at once)
     }
     const uint64_t mask = __ballot(bad);
     if ((threadIdx.x & 63) == 0) A.bitmap[(uint64_t)j * A.words + (row >> 6)] = mask;
@@ -255,7 +283,7 @@ int check_body(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, con
             colptrs[j] = q.kind == DEHALO_COLUMN_ADVICE ? adv + (size_t)q.index * n : q.kind == DEHALO_COLUMN_FIXED ? pk->fixed_values.at((size_t)q.index * n) : d_inst + (size_t)q.index * n;
         }
         TRY(dh_h2d(ctx, d_ptrs, colptrs.data(), (size_t)P * sizeof(void*), s));
-        CopyArgs C{d_map, d_ptrs, n, words, k, &d_hdr->bad_mapping, d_bitmap + (uint64_t)(G + L) * words};
+        CopyArgs C{d_map, d_ptrs, n, words, k, &d_hdr->bad_mapping, d_bitmap + (uint64_t)(G + L) * words, {f->p[0], f->p[1], f->p[2], f->p[3]}};
         k_check_copy<<<dim3((unsigned)((n + CK_THREADS - 1) / CK_THREADS), P), CK_THREADS, 0, s>>>(C);
         HIP_TRY(ctx, hipGetLastError());
     }

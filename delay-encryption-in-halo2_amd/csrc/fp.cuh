@@ -90,6 +90,15 @@ FP_DEV fe f_reduce_once(const fe& a, u32 hi) {
     return r;
 }
 
+// any 256-bit word -> its residue in [0, p): 2^256 < 6p for every field here, so five conditional subtractions (words read from a caller; cold paths only)
+template <class F>
+FP_DEV fe f_canon_word(const fe& a) {
+    fe r = a;
+#pragma unroll
+    for (int i = 0; i < 5; i++) r = f_reduce_once<F>(r, 0);
+    return r;
+}
+
 template <class F>
 FP_DEV fe f_add(const fe& a, const fe& b) {
     fe s;

@@ -750,6 +750,9 @@ __global__ __launch_bounds__(128) void k_msm_build_table(const affine_t* std_poi
     u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     affine_t p = aff_load(&std_points[i]);
+    // a caller's coordinate is any 256-bit word (dehalo.h "Non-canonical words"); the doublings below run on ec.cuh's arithmetic, which wants operands
+    // below p.  The identity is the 64 zero bytes and nothing else.
+    if (!aff_is_identity(p)) { p.x = f_canon_word<F>(p.x); p.y = f_canon_word<F>(p.y); }
     xyzz_t cur = xyzz_from_affine<F>(p);
     for (u32 w = 0; w < rows; w++) {
         affine_t a = p;

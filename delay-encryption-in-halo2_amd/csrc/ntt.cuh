@@ -90,7 +90,8 @@ FP_DEV fe tw_lookup(const fe* tw, u64 e, u32 log_n, bool full) {
 // 9 x 29-bit limbs (five planes: four u64 limb pairs + one u32, 36 B per element, conflict-free
 // ds_read/write_b64) and the butterflies are decimation-in-time:
 //     t = w * v (carry-free multiplier, < 2p);  u' = u + t;  v' = u - t + 4p
-// so values grow ADDITIVELY (< p + 4p per stage, < 30p after 7 stages, far inside 2^261) and no
+// (the first two stages' butterflies without a multiplication: t = v, any 256-bit word or the sum of two, and v' = u - t + KW, 9p or 11p: below 23p after them)
+// so values grow ADDITIVELY (< p + 4p per stage, < 23p + 9 * 4p after the 11 stages of a tile, far inside 2^261 > 128p) and no
 // stage needs a modular reduction -- only a carry normalisation every second stage.  Two stages
 // run in registers per LDS round trip (radix 4).  The element is the plain integer of upstream's
 // standard form (x * 2^256); twiddles are w * 2^261, so products stay in that form, and the
@@ -140,12 +141,14 @@ FP_DEV u32 ntt_at(u32 row, u32 c, u32 log_c, u32) { return (row << log_c) + c; }
 FP_DEV u32 ntt_at(u32 row, u32 c, u32 log_c, u32 sw_shift) { return (row << log_c) + (c ^ ((row >> sw_shift) & ((1u << log_c) - 1))); }
 #endif
 
-// DIT butterfly on lazily reduced limbs; v may carry limbs < 2^31, w is normalized
-template <class F9>
-FP_DEV void bfly29(f29& u, f29& v, const f29& w, bool mul) {
-    f29 t = mul ? f29_mul<F9>(v, w) : f29_norm(v);
+// DIT butterfly on lazily reduced limbs; v may carry limbs < 2^31, w is normalized.  MUL = false: the twiddle is one (stage 0, and the first butterfly of
+// stage 1), so v is subtracted as it is -- a word of the caller's, any 256-bit integer (dehalo.h "Non-canonical words"), or the sum of two of them: KW
+// dominates those (KM, 4p, covers a product only: 2^256 is more than 5p for BN254).
+template <class F9, bool MUL>
+FP_DEV void bfly29(f29& u, f29& v, const f29& w) {
+    f29 t = MUL ? f29_mul<F9>(v, w) : f29_norm(v);
     f29 nu = f29_add(u, t);
-    v = f29_sub(u, t, F9::KM);
+    v = MUL ? f29_sub(u, t, F9::KM) : f29_sub(u, t, F9::KW);
     u = nu;
 }
 
@@ -294,14 +297,15 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(NttPassParams P) {
             f29 e0 = lds29_load(L, a0), e1 = lds29_load(L, a1), e2 = lds29_load(L, a2), e3 = lds29_load(L, a3);
             // stage s: (e0, e1) and (e2, e3), twiddle w_R^(pos * R / 2h)
             f29 w = ltw[pos << (r - 1 - s)];
-            bfly29<F9>(e0, e1, w, s != 0);
-            bfly29<F9>(e2, e3, w, s != 0);
+            if (s != 0) { bfly29<F9, true>(e0, e1, w); bfly29<F9, true>(e2, e3, w); }
+            else { bfly29<F9, false>(e0, e1, w); bfly29<F9, false>(e2, e3, w); }
             // stage s + 1: (e0, e2) with pos, (e1, e3) with pos + h, twiddle w_R^(pos' * R / 4h);
             // in the first round pos = 0, so the (e0, e2) twiddle is 1
             f29 w0 = ltw[pos << (r - 2 - s)];
             f29 w1 = ltw[(pos + h) << (r - 2 - s)];
-            bfly29<F9>(e0, e2, w0, s != 0);
-            bfly29<F9>(e1, e3, w1, true);
+            if (s != 0) bfly29<F9, true>(e0, e2, w0);
+            else bfly29<F9, false>(e0, e2, w0);
+            bfly29<F9, true>(e1, e3, w1);
             lds29_store(L, a0, f29_norm(e0)); lds29_store(L, a1, f29_norm(e1));
             lds29_store(L, a2, f29_norm(e2)); lds29_store(L, a3, f29_norm(e3));
         }
@@ -317,7 +321,8 @@ __global__ __launch_bounds__(NTT_THREADS) void k_ntt_pass(NttPassParams P) {
             const u32 a0 = ntt_at(i0, c, log_c, sw), a1 = ntt_at(i0 + h, c, log_c, sw);
             f29 e0 = lds29_load(L, a0), e1 = lds29_load(L, a1);
             f29 w = ltw[pos << (r - 1 - s)];
-            bfly29<F9>(e0, e1, w, s != 0);
+            if (s != 0) bfly29<F9, true>(e0, e1, w);
+            else bfly29<F9, false>(e0, e1, w);
             lds29_store(L, a0, f29_norm(e0)); lds29_store(L, a1, f29_norm(e1));
         }
         __syncthreads();
@@ -408,9 +413,13 @@ __global__ void k_field_op(int op, const fe* a, const fe* b, fe* out, u64 n) {
     if (i >= n) return;
     fe x = f_load(&a[i]);
     fe y = b ? f_load(&b[i]) : x;
+    // A caller's word is any 256-bit integer and stands for its residue (dehalo.h "Non-canonical words").  f_add / f_sub / f_mul return a value below p for
+    // operands below p only, and the zero test of the inversion is a test of the residue: add, sub, mul and inv take the canonical representatives.  The
+    // conversions (4, 5, 6) multiply by a canonical constant, which reduces any word.
+    if (op <= 3) { x = f_canon_word<F>(x); y = f_canon_word<F>(y); }
     fe r;
     switch (op) {
-        case 0: r = f_add<F>(x, y); break;
+        case 0: r = f_add<F>(x, y); break;      // (ops 0 - 3 on canonical representatives: see above)
         case 1: r = f_sub<F>(x, y); break;
         case 2: r = f_mul<F>(x, y); break;
         case 3: r = f_is_zero(x) ? f_zero() : f_inv<F>(x); break;

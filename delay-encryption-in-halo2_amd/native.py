@@ -26,6 +26,14 @@ CHECK_GATE, CHECK_LOOKUP, CHECK_COPY, CHECK_SHUFFLE = 0, 1, 2, 3
 PHASES = ("advice", "lookups", "products", "random", "quotient", "evaluations", "openings", "total")
 
 
+def _instance_words(f, v) -> np.ndarray:
+    """one instance column as (len, 4) u64 Montgomery words: a list of ints is encoded (canonical words); a (len, 4) uint64 array is taken as the words
+    themselves, as a C caller would hand them over -- any 256-bit word, standing for its residue (dehalo.h "Non-canonical words")"""
+    if isinstance(v, np.ndarray) and v.dtype == np.uint64 and v.ndim == 2 and v.shape[1] == 4:
+        return np.ascontiguousarray(v)
+    return f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64)
+
+
 class ConstraintSystemDescriptor:
     """dehalo_constraint_system built from a plonk.ConstraintSystem; owns the arrays the C struct points into."""
 
@@ -351,7 +359,7 @@ class ProvingKey:
         else:
             adv = np.ascontiguousarray(advice, dtype=np.uint64)
             adv_ptr = adv.ctypes.data
-        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for v in instances]
+        cols = [_instance_words(f, v) for v in instances]
         ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
         lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
         mapping = None
@@ -533,7 +541,7 @@ class Prover:
         else:
             adv = np.ascontiguousarray(advice, dtype=np.uint64)
             adv_ptr = adv.ctypes.data
-        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for v in instances]
+        cols = [_instance_words(f, v) for v in instances]
         ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
         lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
         r = rng_struct(rng)
@@ -570,7 +578,7 @@ class Prover:
         if len(instances) != len(advices) or len(per_circuit) > 1:
             raise ValueError("create_proof_multi: one list of instance columns per circuit, every circuit the same number of columns")
         ncols = per_circuit.pop() if per_circuit else 0
-        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for inst in instances for v in inst]
+        cols = [_instance_words(f, v) for inst in instances for v in inst]
         ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
         lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
         r = rng_struct(rng)
@@ -619,7 +627,7 @@ class Prover:
                 return 1
 
         flags = (PROOF_ADVICE_CANONICAL if canonical else 0) | (PROOF_ADVICE_ON_DEVICE if state["device"] else 0)
-        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for v in instances]
+        cols = [_instance_words(f, v) for v in instances]
         ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
         lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
         r = rng_struct(rng)
@@ -643,7 +651,7 @@ class Prover:
         tr = transcript if transcript is not None else Blake2bWrite(self.pk.curve)
         f = self.pk.curve.scalar
         inp, keep = circuit_inputs(circuit, self.pk.info()["k"], **inputs)
-        cols = [f.encode_many(list(v)) if len(v) else np.zeros((0, 4), dtype=np.uint64) for v in instances]
+        cols = [_instance_words(f, v) for v in instances]
         ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
         lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
         r = rng_struct(rng)

@@ -28,6 +28,30 @@
  *    different phases) goes to DIFFERENT contexts; registered bases and compiled graphs may be
  *    shared between contexts of the same device.  There is NO CPU fallback: without a usable
  *    gfx950 device dehalo_ctx_create fails with DEHALO_ERR_NO_DEVICE.
+ *
+ * Non-canonical words.  halo2curves only ever stores words below the modulus; a C or Rust caller can hand over anything.  The rules hold for every
+ * entry point; tests/test_noncanonical_inputs.py pins them on dehalo_field_op, the NTT family and the domain transforms, dehalo_eval_polynomial (host,
+ * device, multi, points), dehalo_kate_division (host, batch) and the vanishing quotient, lincomb, scale, batch inversion, the grand and prefix
+ * products, product_terms, graph_evaluate and the permutation / lookup / shuffle terms of h, dehalo_permute_expression_pair (host, device, pointer
+ * table), dehalo_check_witness, whole proofs (KZG and IPA, advice and instances), every MSM form, best_multiexp, the fixed-base and blinding calls, the
+ * generator collapse, registration, points_check and points_compress.  Without a row of their own -- they read caller words through the kernels and
+ * conversions (f29_from_std / f_from_mont) of the rows above, which is an argument from reading, not a test: dehalo_keygen's fixed columns, dehalo_ipa_open, dehalo_convert_form_device and the *_form_device
+ * transforms, dehalo_kate_division_device, dehalo_g_to_lagrange_device, the masked evaluation, the batch / deferred / distinct permute forms and the
+ * transcript's common_scalar / write_scalar.  dehalo_points_decompress_device refuses an x not below p (status bit 1), as upstream's from_bytes does.
+ *  (1) A field element or scalar READ from caller memory, host or device, is any 256-bit word w and stands for w mod p (w mod r for a scalar): every
+ *      result is that of the canonical word, and every "is this zero" or "are these equal" decision -- the elements a batch inversion skips, the
+ *      denominators of a grand product, the operand of an inversion, a zero scalar, the keys of a lookup (x and x + p are one key), the two cells of a
+ *      copy constraint in dehalo_check_witness -- is made mod p.
+ *  (2) A field element the library COMPUTES and writes is canonical, below p.  An element a batch inversion leaves alone because it is zero mod p is
+ *      written as 0.  The permuted columns of dehalo_permute_expression_pair* are computed (written back from the sorted canonical keys): canonical too.
+ *      A transform of ONE element (log_n = 0) is computed like every other size and stores the canonical word.
+ *  (3) The entry points that only MOVE bytes copy the caller's words unchanged, canonical or not: dehalo_upload and dehalo_download, and the copies of a
+ *      caller's advice and instance columns that dehalo_create_proof* / dehalo_check_witness make before their kernels read them under rule 1.  (The
+ *      prover's own gathers and row placements move values the library made, which are canonical by rule 2.)
+ *  (4) The coordinates of a point are field elements under rule 1.  The identity is exactly 64 zero bytes and nothing else: a pair that is (0, 0) mod p
+ *      without being zero bytes is not on the curve and what an MSM makes of it is undefined.  Registration does not check; dehalo_points_check_device
+ *      reports such a pair, and every other coordinate that is not below p, as status bit 1.  dehalo_points_compress_device writes the canonical encoding.
+ *  (5) dehalo_bases_register with stride_bytes > 64: the first 64 bytes of each slot are the point, the rest is ignored (see there).
  */
 #ifndef DEHALO_H
 #define DEHALO_H
@@ -107,7 +131,9 @@ int dehalo_upload(dehalo_ctx* ctx, const void* host_src, size_t bytes, void* d_d
  * [halo2_proofs/src/poly/kzg/commitment.rs, .../ipa/commitment.rs; built at
  * benches/delay_enc.rs:41-54].  Bases are constant per SRS, so they are uploaded once and
  * stay resident in HBM.
- *   affine_xy     n points, `stride_bytes` apart (>= 64; 64 for halo2curves' {x, y} structs)
+ *   affine_xy     n points, `stride_bytes` apart (>= 64; 64 for halo2curves' {x, y} structs).  With stride_bytes > 64 the FIRST 64 bytes of each slot are
+ *                 the point {x, y} and the remaining bytes are ignored: a flag byte kept there (an "is identity" marker, say) is not read, and an identity
+ *                 must be x = y = 0 like everywhere else.  Coordinates are words under "Non-canonical words" (4) above.
  *   window_bits   0 = choose from n (with precompute = 1: 17 from 2^20 points, 16 at 2^19, 15 from 2^17, 13 below); otherwise the Pippenger window c in [4, 16], or 17 with precompute = 1
  *   precompute    1 = also store [2^(c*w)]P_i for every window w (n * ceil(256/c) * 64 B of
  *                 HBM): all windows then share one bucket set and the per-window doublings
@@ -246,7 +272,9 @@ int dehalo_coset_intt_device(dehalo_ctx* ctx, int field, uint64_t* d_a, uint32_t
  * Used by the parity tests to pin the device field arithmetic directly (e.g. against the
  * reference's Poseidon known-answer vectors).  Host buffers, n elements each.
  * op: 0 add, 1 sub, 2 mul, 3 invert, 4 canonical->Montgomery, 5 Montgomery->canonical,
- *     6 mul evaluated through the kernels' internal carry-free 29-bit-limb representation.     */
+ *     6 mul evaluated through the kernels' internal carry-free 29-bit-limb representation.
+ * Operands are words under "Non-canonical words" (1): the outputs are canonical whatever multiples of p the operands carry, and the inverse of a word
+ * that is zero mod p is 0.                                                                      */
 int dehalo_field_op(dehalo_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
 /* device-pointer form (d_b may be NULL for the unary ops; d_out may alias d_a): e.g. canonical -> Montgomery of a column uploaded as raw integers */
 int dehalo_field_op_device(dehalo_ctx* ctx, int field, int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream);
@@ -261,20 +289,22 @@ int dehalo_field_op_device(dehalo_ctx* ctx, int field, int op, const uint64_t* d
  *   called for every opened polynomial in plonk/prover.rs after the challenge x is squeezed).
  *   The device form evaluates `batch` polynomials (stride_elems apart) at the same point into
  *   d_out[batch][4].
- * dehalo_batch_invert: values[i] <- values[i]^-1 in place, zero elements left zero.  Replaces
+ * dehalo_batch_invert: values[i] <- values[i]^-1 in place, zero elements left zero -- zero mod p: an element stored as p or another multiple of p is
+ *   skipped like a stored 0 and written back as 0 ("Non-canonical words" (1), (2) at the top; the other elements are inverted all the same).  Replaces
  *   ff::BatchInvert::batch_invert as used on the denominators of the permutation and lookup
  *   grand products (plonk/permutation/prover.rs, plonk/lookup/prover.rs).
  * dehalo_prefix_product_device: out[0] = 1, out[i] = in[0] * ... * in[i-1]  (in == out allowed).
  * dehalo_grand_product: z[0] = 1, z[i] = prod_{j<i} num[j] / den[j] -- the running product
  *   upstream builds after its batch_invert ("z.push(one); for row in 1..n { tmp *= product[row-1] }");
  *   the caller appends upstream's blinding rows.  A zero denominator behaves like upstream's
- *   batch_invert (left zero), so the product is zero from that row on.                          */
+ *   batch_invert (left zero), so the product is zero from that row on; "zero" is zero mod p ("Non-canonical words" (1)).   */
 /* dehalo_permute_expression_pair: the lookup argument's permuted columns, replacing
  *   plonk/lookup/prover.rs permute_expression_pair: permuted_input = the `usable_rows` input values
  *   sorted ascending by canonical value; permuted_table[row] = permuted_input[row] at every first
  *   occurrence, the table's remaining values (ascending) in the repeated rows taken from the end.
  *   Only the table is sorted (merge sort on the 256-bit keys); every input value finds its table position by binary search and the
  *   outputs are written from the position counts (csrc/lookup_permute.hip).
+ *   Keys are compared mod p and both outputs are canonical words ("Non-canonical words" (1), (2)): not the caller's words moved.
  *   DEHALO_ERR_NOT_IN_TABLE when an input value does not occur in the table.  The caller appends
  *   upstream's random blinding rows.  The device form synchronises its stream (it has to return
  *   that error).                                                                                 */
@@ -730,7 +760,9 @@ size_t dehalo_prover_proof_size(const dehalo_prover* prover);
  * with the products' commitments, at the wait the proof makes there anyway; the prover is usable for the next proof.
  * Under ParamsIPA (create_proof::<IPACommitmentScheme<_>, ProverIPA<_>, ..>) every commitment carries its blind ([blind] W from the table of W, dehalo_fixed_base_blind_device: one
  * launch per phase), the instance columns are committed with Blind::default() and absorbed as points, their evaluations are written first, and the proof ends
- * with ProverIPA's multiopen (x_1, x_2, f, x_3, the q evaluations, x_4) and the opening argument of dehalo_ipa_open on the same transcript and generator. */
+ * with ProverIPA's multiopen (x_1, x_2, f, x_3, the q evaluations, x_4) and the opening argument of dehalo_ipa_open on the same transcript and generator.
+ * Advice and instance values are words under "Non-canonical words" (1), (3) at the top: a value given as x + j p proves what x proves, byte for byte (the
+ * instance values a KZG proof hashes are hashed as their canonical encodings). */
 enum { DEHALO_PROOF_ADVICE_ON_DEVICE = 1, DEHALO_PROOF_ADVICE_CANONICAL = 2 /* plain integers < p: converted on the device */ };
 int dehalo_create_proof(dehalo_prover* prover, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                         dehalo_rng* rng, dehalo_transcript* transcript, uint32_t flags);
@@ -805,6 +837,8 @@ typedef struct {
     uint64_t written;                                         /* entries stored in `failures` = min(cap, total) */
     uint64_t shuffle_failures, shuffle_inputs;                /* total; usable rows x shuffles */
 } dehalo_check_report;
+/* Advice and instance values are words under "Non-canonical words" (1) at the top: gates and lookups are judged on the residues, and the two cells of a copy
+ * constraint are equal when their words are equal mod p. */
 int dehalo_check_witness(dehalo_ctx* ctx, const dehalo_pk* pk, const uint64_t* advice, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns,
                          const uint64_t* permutation_mapping, uint32_t flags, dehalo_check_failure* failures, size_t cap, dehalo_check_report* report);
 /* The same checks for a key whose expressions read challenges, under the caller's values for them: challenges = num_challenges x 4 u64 Montgomery, num_challenges =

@@ -56,11 +56,13 @@ class F29:
         self.KA = self.sub_const(9.5, 29)    # subtrahend: a stored coordinate (normalized limbs, value < 9.5 p)
         self.KB = self.sub_const(4.5, 31)    # subtrahend: PPP + 2Q (limbs < 3 * 2^29, value < 4.5 p)
         self.KN = self.sub_const(1.0, 29)    # negation of a canonical value (< p)
+        # subtrahend: a caller's 256-bit word, or the sum of two (the NTT's butterflies without a multiplication: normalized limbs, value < 2^257)
+        self.KW = self.sub_const(None, 29, vmax=(1 << 257) - 1)
 
-    def sub_const(self, vbound, s):
+    def sub_const(self, vbound, s, vmax=None):
         """limbs K'_i of a multiple K of p such that K'_i >= (max subtrahend limb_i) for i < 8 and
-        K'_8 >= (max subtrahend top limb); offsets 2^s borrowed from the next limb."""
-        top_need = (int(vbound * self.p) >> (B * 8)) + 1
+        K'_8 >= (max subtrahend top limb); offsets 2^s borrowed from the next limb.  The subtrahend's value is below vbound p, or at most vmax."""
+        top_need = ((int(vbound * self.p) if vmax is None else vmax) >> (B * 8)) + 1
         borrow = 1 << (s - B)
         k = 1
         while True:
@@ -315,6 +317,21 @@ class F29:
             assert v < U32
             out.append(v)
         return out
+
+    def bfly(self, u, v, w, mul, kc):
+        """bfly29 of csrc/ntt.cuh: t = v w (or v itself, normalized, where the twiddle is one); -> (u + t, u - t + K)"""
+        t = self.mont(v, w) if mul else self.norm(v)
+        return self.add(u, t), self.sub(u, t, kc)
+
+    def ntt_first_round(self, e, w1, kc):
+        """the first radix-4 round of k_ntt_pass on four loaded words e (limbs of plain 256-bit integers): stage 0 without a multiplication, stage 1 with the
+        twiddles 1 and w1; kc: the constant of the butterflies that do not multiply.  -> the four values as stored (normalized)"""
+        e0, e1, e2, e3 = e
+        e0, e1 = self.bfly(e0, e1, None, False, kc)
+        e2, e3 = self.bfly(e2, e3, None, False, kc)
+        e0, e2 = self.bfly(e0, e2, None, False, kc)
+        e1, e3 = self.bfly(e1, e3, w1, True, self.KM)
+        return [self.norm(x) for x in (e0, e1, e2, e3)]
 
     def canon(self, a):
         """fully reduced value in [0, p), normalized limbs"""
@@ -669,6 +686,7 @@ def emit():
                 "  static constexpr uint32_t KA[9] = {%s};  // %d p, dominates normalized limbs of a value < 9.5 p" % (w(F.KA[0]), F.KA[1] // F.p),
                 "  static constexpr uint32_t KB[9] = {%s};  // %d p, dominates limbs < 3 * 2^29" % (w(F.KB[0]), F.KB[1] // F.p),
                 "  static constexpr uint32_t KN[9] = {%s};  // %d p, negation of a canonical value" % (w(F.KN[0]), F.KN[1] // F.p),
+                "  static constexpr uint32_t KW[9] = {%s};  // %d p, dominates normalized limbs of a value < 2^257 (one or two 256-bit words of a caller)" % (w(F.KW[0]), F.KW[1] // F.p),
                 "  static constexpr uint32_t P2[9] = {%s};  // 2p" % w(limbs(2 * F.p)),
                 "  static constexpr uint32_t P4[9] = {%s};  // 4p" % w(limbs(4 * F.p)),
                 "  static constexpr uint32_t P8[9] = {%s};  // 8p" % w(limbs(8 * F.p)),
