@@ -75,4 +75,9 @@ hostrng_check: tests/native_host/hostrng_check.cpp $(CSRC)/hostrng.hpp $(CSRC)/h
 params_format_check: tests/native_host/params_format_check.cpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/params_format_check tests/native_host/params_format_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check
+# VerifyingKey / ProvingKey on disk (csrc/key_format.hpp: host only): layouts, the header, the length and the count / length words of untrusted bytes, under
+# ASan + UBSan (tests/test_key_format_host.py compares it with the Python mirror)
+key_format_check: tests/native_host/key_format_check.cpp $(CSRC)/key_format.hpp include/dehalo.h
+	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/key_format_check tests/native_host/key_format_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check

@@ -11,7 +11,7 @@
 //! transcript.write_raw(&proof)                                                // same wire format: 32-byte compressed points, 32-byte LE scalars
 //! ```
 use crate::constraint_system::Descriptor;
-use crate::params::DehaloParamsKZG;
+use crate::params::{DehaloParamsKZG, SerdeFormat};
 use crate::{Context, DehaloError};
 use core::ffi::{c_int, c_void};
 use dehalo_sys as sys;
@@ -40,26 +40,45 @@ impl<'c> DehaloProvingKey<'c> {
         Ok(DehaloProvingKey { ctx, raw })
     }
 
-    /// `ProvingKey::read::<_, Circuit>(&mut reader, SerdeFormat::RawBytes)` of the file the bench caches (benches/delay_enc.rs:111-115).
-    pub fn read(ctx: &'c Context, cs: &ConstraintSystem<Fr>, bytes: &[u8], num_selectors: u32) -> Result<Self, DehaloError> {
+    /// `VerifyingKey::read(&mut reader, vk_format)` + `keygen_pk(&params, vk, &circuit)` (benches/delay_enc.rs:96-103): the proving key of these columns UNDER the
+    /// verifying key `vk_bytes`.  Its commitments are taken as they are -- not recomputed (no MSM runs) and, as upstream, not compared with the columns; a checked
+    /// format validates them (`dehalo_keygen_pk`).
+    pub fn keygen_pk(ctx: &'c Context, params: &DehaloParamsKZG<'c>, cs: &ConstraintSystem<Fr>, vk_bytes: &[u8], vk_format: SerdeFormat, num_selectors: u32, fixed: &[Fr],
+                     mapping: &[u64]) -> Result<Self, DehaloError> {
         let d = Descriptor::from_constraint_system(cs);
         let c = d.as_c();
         let mut raw = core::ptr::null_mut();
-        ctx.check(unsafe { sys::dehalo_pk_read(ctx.as_ptr(), sys::DEHALO_CURVE_BN254_G1, &c, bytes.as_ptr(), bytes.len(), num_selectors, &mut raw) })?;
+        ctx.check(unsafe {
+            sys::dehalo_keygen_pk(ctx.as_ptr(), params.as_ptr(), &c, vk_bytes.as_ptr(), vk_bytes.len(), vk_format.into(), num_selectors, fixed.as_ptr() as *const u64,
+                                  mapping.as_ptr(), 0, &mut raw)
+        })?;
         Ok(DehaloProvingKey { ctx, raw })
     }
 
-    /// `pk.write(&mut writer, SerdeFormat::RawBytes)` (`:105`)
-    pub fn write(&self) -> Result<Vec<u8>, DehaloError> {
-        let mut out = vec![0u8; unsafe { sys::dehalo_pk_size(self.raw) }];
-        self.ctx.check(unsafe { sys::dehalo_pk_write(self.ctx.as_ptr(), self.raw, out.as_mut_ptr(), out.len()) })?;
+    /// `ProvingKey::read::<_, Circuit>(&mut reader, format)` of the file the bench caches (benches/delay_enc.rs:111-115, which passes `SerdeFormat::RawBytes`):
+    /// `Processed` decompresses the commitments and converts every element on the device, `RawBytes` checks every point and every element there, and
+    /// `RawBytesUnchecked` copies the bytes in unseen (`dehalo_pk_read_custom`).
+    pub fn read(ctx: &'c Context, cs: &ConstraintSystem<Fr>, bytes: &[u8], format: SerdeFormat, num_selectors: u32) -> Result<Self, DehaloError> {
+        let d = Descriptor::from_constraint_system(cs);
+        let c = d.as_c();
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe {
+            sys::dehalo_pk_read_custom(ctx.as_ptr(), sys::DEHALO_CURVE_BN254_G1, &c, bytes.as_ptr(), bytes.len(), format.into(), num_selectors, &mut raw)
+        })?;
+        Ok(DehaloProvingKey { ctx, raw })
+    }
+
+    /// `pk.write(&mut writer, format)` (`:105`); both raw formats write the same bytes (`dehalo_pk_write_custom`)
+    pub fn write(&self, format: SerdeFormat) -> Result<Vec<u8>, DehaloError> {
+        let mut out = vec![0u8; unsafe { sys::dehalo_pk_size_custom(self.raw, format.into()) }];
+        self.ctx.check(unsafe { sys::dehalo_pk_write_custom(self.ctx.as_ptr(), self.raw, format.into(), out.as_mut_ptr(), out.len()) })?;
         Ok(out)
     }
 
-    /// `vk.write(..)` (`:88`)
-    pub fn vk_write(&self) -> Result<Vec<u8>, DehaloError> {
-        let mut out = vec![0u8; unsafe { sys::dehalo_vk_size(self.raw) }];
-        self.ctx.check(unsafe { sys::dehalo_vk_write(self.raw, out.as_mut_ptr(), out.len()) })?;
+    /// `vk.write(&mut writer, format)` (`:88`) (`dehalo_vk_write_custom`)
+    pub fn vk_write(&self, format: SerdeFormat) -> Result<Vec<u8>, DehaloError> {
+        let mut out = vec![0u8; unsafe { sys::dehalo_vk_size_custom(self.raw, format.into()) }];
+        self.ctx.check(unsafe { sys::dehalo_vk_write_custom(self.ctx.as_ptr(), self.raw, format.into(), out.as_mut_ptr(), out.len()) })?;
         Ok(out)
     }
 

@@ -38,6 +38,8 @@ SYMBOLS = [
     "dehalo_prover_create_multi", "dehalo_create_proof_multi", "dehalo_shuffle_h_batch_device",
     "dehalo_points_compress_device", "dehalo_points_decompress_device", "dehalo_points_check_device",
     "dehalo_params_size_custom", "dehalo_params_write_custom", "dehalo_params_read_custom", "dehalo_params_from_g", "dehalo_params_downsize",
+    "dehalo_scalars_from_repr_device", "dehalo_scalars_check_device",
+    "dehalo_vk_size_custom", "dehalo_vk_write_custom", "dehalo_pk_size_custom", "dehalo_pk_write_custom", "dehalo_pk_read_custom", "dehalo_keygen_pk",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -279,6 +281,16 @@ def load_library():
     lib.dehalo_vk_size.argtypes = [P]
     lib.dehalo_vk_size.restype = sz
     lib.dehalo_vk_write.argtypes = [P, P, sz]
+    lib.dehalo_vk_size_custom.argtypes = [P, C.c_int]
+    lib.dehalo_vk_size_custom.restype = sz
+    lib.dehalo_vk_write_custom.argtypes = [P, P, C.c_int, P, sz]
+    lib.dehalo_pk_size_custom.argtypes = [P, C.c_int]
+    lib.dehalo_pk_size_custom.restype = sz
+    lib.dehalo_pk_write_custom.argtypes = [P, P, C.c_int, P, sz]
+    lib.dehalo_pk_read_custom.argtypes = [P, C.c_int, C.POINTER(CConstraintSystem), P, sz, C.c_int, u32, PP]
+    lib.dehalo_keygen_pk.argtypes = [P, P, C.POINTER(CConstraintSystem), P, sz, C.c_int, u32, u64p, u64p, u32, PP]
+    lib.dehalo_scalars_from_repr_device.argtypes = [P, C.c_int, P, sz, u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), P]
+    lib.dehalo_scalars_check_device.argtypes = [P, C.c_int, u64p, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), P]
     lib.dehalo_pk_set_transcript_repr.argtypes = [P, u64p]
     lib.dehalo_pk_get_transcript_repr.argtypes = [P, u64p]
     lib.dehalo_pk_info.argtypes = [P, C.POINTER(C.c_uint32)]
@@ -526,6 +538,20 @@ class Context:
         st = C.c_uint32(0)
         self._check(self.lib.dehalo_points_check_device(self.handle, curve, d_affine or None, count, C.byref(st), stream or None))
         return st.value
+
+    def scalars_from_repr(self, field: int, d_in32: int, count: int, d_out: int, stream: int = 0) -> tuple:
+        """PrimeField::from_repr of `count` 32-byte little-endian integers (device, 4-byte aligned) into Montgomery words at d_out (device; d_in32 itself: in place)
+        -> (status, first_bad): status 1 = an element not below the modulus (written as 0), first_bad = the lowest such index, `count` if none"""
+        st, fb = C.c_uint32(0), C.c_uint64(0)
+        self._check(self.lib.dehalo_scalars_from_repr_device(self.handle, field, d_in32 or None, count, d_out or None, C.byref(st), C.byref(fb), stream or None))
+        return st.value, fb.value
+
+    def scalars_check(self, field: int, d_words: int, count: int, stream: int = 0) -> tuple:
+        """a checked from_raw_bytes over `count` field elements (device, read only) -> (status, first_bad): status 1 = a stored Montgomery word not below the modulus,
+        first_bad = the lowest such index, `count` if none"""
+        st, fb = C.c_uint32(0), C.c_uint64(0)
+        self._check(self.lib.dehalo_scalars_check_device(self.handle, field, d_words or None, count, C.byref(st), C.byref(fb), stream or None))
+        return st.value, fb.value
 
     def blind_commitments_device(self, curve: int, d_jacobian: int, d_blinds: int, count: int, d_w_affine: int, stream: int = 0):
         """ParamsIPA's blinding term for one batched MSM's results: d_jacobian[i] += [d_blinds[i]] W, in place (all device pointers; one launch)"""

@@ -300,6 +300,31 @@ int points_status(dehalo_ctx* ctx, uint32_t* status_out, hipStream_t s, Launch&&
     TRY(launch(d_status));
     return dh_d2h(ctx, status_out, d_status, 4, s);
 }
+// ---- the scalar codec's host half (scalar_codec.cuh) ----
+// The context's codec words: status (u32) at byte 0, the lowest offending index (u64) at byte 8.  Both are reset on s (status 0, index all ones), `launch` runs
+// with them, and one download brings them to the host: the one host wait of the call.  An index still all ones means no element was reported: count.
+template <class Launch>
+int scalars_status(dehalo_ctx* ctx, size_t count, uint32_t* status_out, uint64_t* first_bad_out, hipStream_t s, Launch&& launch) {
+    TRY(dh_ensure(ctx, ctx->ws_codec, 16));
+    uint8_t* d = (uint8_t*)ctx->ws_codec.p;
+    HIP_TRY(ctx, hipMemsetAsync(d, 0, 8, s));
+    HIP_TRY(ctx, hipMemsetAsync(d + 8, 0xff, 8, s));
+    TRY(launch((uint32_t*)d, (uint64_t*)(d + 8)));
+    uint64_t h[2] = {0, 0};
+    TRY(dh_d2h(ctx, h, d, 16, s));
+    *status_out = (uint32_t)h[0];
+    *first_bad_out = h[1] == ~(uint64_t)0 ? (uint64_t)count : h[1];
+    return 0;
+}
+int scalars_codec_args(dehalo_ctx* ctx, const char* who, int field, const void* d_words, size_t count, uint32_t* status_out, uint64_t* first_bad_out) {
+    if (!field_ops(field)) return unknown_field(ctx);
+    if (count >= ((size_t)1 << 29)) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": too many elements");
+    if (!status_out || !first_bad_out) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": null status");
+    *status_out = 0;
+    *first_bad_out = 0;
+    if (count && (!d_words || ((uintptr_t)d_words & 15))) return dh_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": the elements are null or not 16-byte aligned");
+    return 0;
+}
 }   // namespace
 
 const IpaOps* ipa_ops(int curve) {
@@ -686,6 +711,31 @@ int dehalo_points_check_device(dehalo_ctx* ctx, int curve, const uint64_t* d_aff
     if (!status_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "points_check: null status");
     return dh_device(ctx, stream, [&](hipStream_t s) {
         return points_status(ctx, status_out, s, [&](uint32_t* d_status) { return ops->points_check(ctx, (const affine_t*)d_affine_xy, count, d_status, s); });
+    });
+}
+
+// ---- the scalar codec (scalar_codec.cuh): from_repr and the checked from_raw_bytes over vectors of field elements ----
+int dehalo_scalars_from_repr_device(dehalo_ctx* ctx, int field, const uint8_t* d_in32, size_t count, uint64_t* d_out, uint32_t* status_out, uint64_t* first_bad_out,
+                                    void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    TRY(scalars_codec_args(ctx, "scalars_from_repr", field, d_out, count, status_out, first_bad_out));
+    if (count == 0) return 0;
+    if (!d_in32 || ((uintptr_t)d_in32 & 3)) return dh_fail(ctx, DEHALO_ERR_INVALID, "scalars_from_repr: the encodings are null or not 4-byte aligned");
+    const uintptr_t a = (uintptr_t)d_in32, b = (uintptr_t)d_out, bytes = (uintptr_t)count * 32;
+    if (a != b && a < b + bytes && b < a + bytes) return dh_fail(ctx, DEHALO_ERR_INVALID, "scalars_from_repr: the output overlaps the input without being it");
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return scalars_status(ctx, count, status_out, first_bad_out, s,
+                              [&](uint32_t* d_status, uint64_t* d_first) { return f.scalars_from_repr(ctx, d_in32, (fe*)d_out, count, d_status, d_first, s); });
+    });
+}
+
+int dehalo_scalars_check_device(dehalo_ctx* ctx, int field, const uint64_t* d_words, size_t count, uint32_t* status_out, uint64_t* first_bad_out, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    TRY(scalars_codec_args(ctx, "scalars_check", field, d_words, count, status_out, first_bad_out));
+    if (count == 0) return 0;
+    return field_device(ctx, field, stream, [&](const FieldOps& f, hipStream_t s) {
+        return scalars_status(ctx, count, status_out, first_bad_out, s,
+                              [&](uint32_t* d_status, uint64_t* d_first) { return f.scalars_check(ctx, (const fe*)d_words, count, d_status, d_first, s); });
     });
 }
 

@@ -755,6 +755,7 @@ int convert_form_t(dehalo_ctx* ctx, const fe* in, fe* out, uint64_t n, int to_in
 }
 
 #include "check.cuh"
+#include "scalar_codec.cuh"
 
 // the per-field table (internal.hpp FieldOps), in its members' order
 template <class F>
@@ -763,5 +764,5 @@ constexpr FieldOps make_field_ops() {
             &eval_poly_t<F>, &eval_poly_multi_t<F>, &eval_poly_points_t<F>, &batch_invert_t<F>, &prefix_product_one_t<F>, &grand_product_t<F>, &lincomb_t<F>, &scale_t<F>,
             &kate_division_t<F>, &kate_division_batch_t<F>, &vanishing_quotient_batch_t<F>,
             &convert_form_t<F>, &graph_upload_t<F>, &graph_evaluate_t<F>, &graph_evaluate_batch_t<F>, &perm_h_t<F>, &lookup_h_t<F>, &lookup_h_batch_t<F>,
-            &product_terms_t<F>, &graph_check_t<F>, &check_member_t<F>, &shuffle_h_batch_t<F>, &check_shuffle_t<F>};
+            &product_terms_t<F>, &graph_check_t<F>, &check_member_t<F>, &shuffle_h_batch_t<F>, &check_shuffle_t<F>, &scalars_from_repr_t<F>, &scalars_check_t<F>};
 }

@@ -386,6 +386,10 @@ struct FieldOps {
     // inputs than among those of the shuffle side", rows >= usable masked; every word of 2^log_rows rows written
     int (*check_shuffle)(dehalo_ctx* ctx, const fe* input, const fe* sorted_inputs, const fe* sorted_side, uint64_t n_keys, uint32_t log_rows, uint64_t usable,
                          uint64_t* bitmap, hipStream_t s);
+    // the scalar codec (scalar_codec.cuh).  from_repr: n 32-byte little-endian integers (4-byte aligned) -> Montgomery words, out == in or disjoint; an integer not
+    // below p is written as 0, d_status[0] |= 1 and d_first_bad[0] = min(d_first_bad[0], its index).  check: the same report for stored words not below p; reads only
+    int (*scalars_from_repr)(dehalo_ctx* ctx, const uint8_t* in, fe* out, uint64_t n, uint32_t* d_status, uint64_t* d_first_bad, hipStream_t s);
+    int (*scalars_check)(dehalo_ctx* ctx, const fe* in, uint64_t n, uint32_t* d_status, uint64_t* d_first_bad, hipStream_t s);
 };
 const FieldOps* dh_field_ops(int field);      // capi.hip: null for an unknown field
 // capi.hip: dehalo_graph_create for a checking program -- calculation i with root_of[i] != 0xffffffff computes root root_of[i] (kept by the copy propagation)

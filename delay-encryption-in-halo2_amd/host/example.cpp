@@ -1,5 +1,6 @@
 // example.cpp -- the reference's bench flow (benches/pose_enc.rs:41-135: ParamsKZG::setup when no params file is cached, else read it; keygen_vk /
-// keygen_pk, write and re-read the proving key, create_proof into a Blake2bWrite transcript) from C++ over the C ABI, with no interpreter anywhere.
+// keygen_pk, write and re-read the proving key, create_proof into a Blake2bWrite transcript) from C++ over the C ABI, with no interpreter anywhere.  The
+// key the proof runs under comes from keygen_pk under the verifying key in its Processed form (benches/delay_enc.rs:88-103).
 //
 //   example                 build / link check: one tiny best_fft (needs a GPU to run)
 //   example <dir>           <dir>/params.bin   ParamsKZG RawBytes; when it does not exist it is MADE (ParamsKZG::setup on the device) from
@@ -125,7 +126,20 @@ int main(int argc, char** argv) {
             dump(dir + "/pk.bin", fresh.write());
             dump(dir + "/vk.bin", fresh.vk_write());
         }
-        ProvingKey pk(be, DEHALO_CURVE_BN254_G1, cs, slurp(dir + "/pk.bin"), 0);      // ... cached on disk, read back (benches/pose_enc.rs:103-115)
+        {   // benches/delay_enc.rs:88-103: the vk leaves in the portable format, and keygen_pk under it (no commitment is recomputed) gives the key just written;
+            // so does reading that key back from its Processed form
+            const std::vector<uint8_t> raw = slurp(dir + "/pk.bin");
+            ProvingKey cached(be, DEHALO_CURVE_BN254_G1, cs, raw, 0);
+            const std::vector<uint8_t> vk_processed = cached.vk_write(DEHALO_SERDE_PROCESSED);
+            if (ProvingKey::keygen_pk(be, params, cs, vk_processed, DEHALO_SERDE_PROCESSED, 0, fixed, mapping).write() != raw)
+                throw std::runtime_error("keygen_pk under the Processed vk is not the key keygen made");
+            const std::vector<uint8_t> processed = cached.write(DEHALO_SERDE_PROCESSED);
+            if (processed.size() + 32 * (9 + 6) != raw.size() || ProvingKey::read(be, DEHALO_CURVE_BN254_G1, cs, processed, 0, DEHALO_SERDE_PROCESSED).write() != raw)
+                throw std::runtime_error("ProvingKey: write(Processed) -> read(Processed) changed the key");
+        }
+        // the proof runs under the key that keygen_pk builds from the Processed vk on disk
+        ProvingKey pk = ProvingKey::keygen_pk(be, params, cs, ProvingKey(be, DEHALO_CURVE_BN254_G1, cs, slurp(dir + "/pk.bin"), 0).vk_write(DEHALO_SERDE_PROCESSED),
+                                                    DEHALO_SERDE_PROCESSED, 0, fixed, mapping);
         pk.set_transcript_repr(repr);
         Backend side(0);
         Prover prover(be, params, pk, &side);

@@ -378,16 +378,45 @@ class ProvingKey {
     ProvingKey(const Backend& be, dehalo_curve curve, ConstraintSystem& cs, const std::vector<uint8_t>& raw_bytes, uint32_t num_selectors) : be_(be) {
         be_.check(dehalo_pk_read(be_.raw(), curve, cs.descriptor(), raw_bytes.data(), raw_bytes.size(), num_selectors, &pk_));
     }
+    // ProvingKey::read::<_, Circuit>(.., format): Processed decompresses the commitments and converts the elements on the device, RawBytes checks every point and
+    // every element, RawBytesUnchecked is the constructor above (dehalo_pk_read_custom)
+    static ProvingKey read(const Backend& be, dehalo_curve curve, ConstraintSystem& cs, const std::vector<uint8_t>& bytes, uint32_t num_selectors, dehalo_serde_format format) {
+        dehalo_pk* h = nullptr;
+        be.check(dehalo_pk_read_custom(be.raw(), curve, cs.descriptor(), bytes.data(), bytes.size(), format, num_selectors, &h));
+        return ProvingKey(be, h);
+    }
+    // VerifyingKey::read(.., vk_format) + keygen_pk(&params, vk, &circuit): the key of these columns UNDER the verifying key `vk_bytes`, whose commitments are
+    // taken as they are -- not recomputed (no MSM runs) and not compared with the columns (dehalo_keygen_pk)
+    static ProvingKey keygen_pk(const Backend& be, const ParamsKZG& params, ConstraintSystem& cs, const std::vector<uint8_t>& vk_bytes, dehalo_serde_format vk_format,
+                                uint32_t num_selectors, const std::vector<Fe>& fixed, const std::vector<uint64_t>& mapping, uint32_t flags = 0) {
+        dehalo_pk* h = nullptr;
+        be.check(dehalo_keygen_pk(be.raw(), params.raw(), cs.descriptor(), vk_bytes.data(), vk_bytes.size(), vk_format, num_selectors,
+                                  fixed.empty() ? nullptr : fixed[0].data(), mapping.data(), flags, &h));
+        return ProvingKey(be, h);
+    }
     ~ProvingKey() { dehalo_pk_release(be_.raw(), pk_); }
     ProvingKey(const ProvingKey&) = delete;
+    ProvingKey(ProvingKey&& o) noexcept : be_(o.be_), pk_(o.pk_) { o.pk_ = nullptr; }
     std::vector<uint8_t> write() const {
         std::vector<uint8_t> out(dehalo_pk_size(pk_));
         be_.check(dehalo_pk_write(be_.raw(), pk_, out.data(), out.size()));
         return out;
     }
+    // ProvingKey::write(.., format); both raw formats write write()'s bytes
+    std::vector<uint8_t> write(dehalo_serde_format format) const {
+        std::vector<uint8_t> out(dehalo_pk_size_custom(pk_, format));
+        be_.check(dehalo_pk_write_custom(be_.raw(), pk_, format, out.data(), out.size()));
+        return out;
+    }
     std::vector<uint8_t> vk_write() const {
         std::vector<uint8_t> out(dehalo_vk_size(pk_));
         be_.check(dehalo_vk_write(pk_, out.data(), out.size()));
+        return out;
+    }
+    // VerifyingKey::write(.., format); both raw formats write vk_write()'s bytes
+    std::vector<uint8_t> vk_write(dehalo_serde_format format) const {
+        std::vector<uint8_t> out(dehalo_vk_size_custom(pk_, format));
+        be_.check(dehalo_vk_write_custom(be_.raw(), pk_, format, out.data(), out.size()));
         return out;
     }
     void set_transcript_repr(const Fe& r) { be_.check(dehalo_pk_set_transcript_repr(pk_, r.data())); }
@@ -408,6 +437,7 @@ class ProvingKey {
     dehalo_pk* raw() const { return pk_; }
 
   private:
+    ProvingKey(const Backend& be, dehalo_pk* adopted) : be_(be), pk_(adopted) {}
     const Backend& be_;
     dehalo_pk* pk_ = nullptr;
 };

@@ -15,6 +15,8 @@ upstream's on-disk formats.
       vk | l0 | l_last | l_active_row (extended polynomials) | fixed_values | fixed_polys | fixed_cosets |
       permutation values | polys | cosets ; a polynomial = len: u32 BE | elements (32 B raw Montgomery);
       a slice of polynomials = count: u32 BE | polynomials.
+  Both take a format (SERDE_FORMATS): the layouts above are "raw" / "raw-unchecked"; "processed" writes a commitment as its 32-byte
+  GroupEncoding and an element as its canonical integer, and the two checked formats validate what they read (HostProvingKey).
 Reading a key needs the circuit's ConstraintSystem, as upstream's `read::<_, ConcreteCircuit>` does.
 
 keygen_vk / keygen_pk [UPSTREAM halo2_proofs/src/plonk/keygen.rs] run on the device: commit_lagrange of every fixed
@@ -381,29 +383,198 @@ def _exact(fh, nbytes: int) -> bytes:
     return b
 
 
-def _write_poly(fh, arr: np.ndarray):
-    fh.write(struct.pack(">I", arr.shape[0]))
-    fh.write(np.ascontiguousarray(arr, dtype=np.uint64).tobytes())
+# ---- keys in the three SerdeFormats: the host mirror of csrc/key_format.hpp and of the two device codecs ------------------
+# [UPSTREAM halo2_proofs/src/plonk.rs VerifyingKey / ProvingKey::{write, read}(.., SerdeFormat), halo2curves 0.3.x SerdeObject; restated from memory]
+#   "processed": a commitment is its 32-byte GroupEncoding (transcript.compress), an element its canonical integer, 32 B little-endian (to_repr);
+#   "raw", "raw-unchecked": a commitment is 64 B and an element 32 B of Montgomery limbs; "raw" validates every one of them when read.
+KEY_SECTION_NAMES = ("fixed commitments", "permutation commitments", "l0", "l_last", "l_active_row", "fixed_values", "fixed_polys", "fixed_cosets",
+                     "permutation values", "permutation polys", "permutation cosets")
 
 
-def _read_poly(fh, expect_len: int) -> np.ndarray:
-    (ln,) = struct.unpack(">I", _exact(fh, 4))
-    if ln != expect_len:
-        raise ValueError("polynomial length %d, expected %d" % (ln, expect_len))
-    return np.frombuffer(_exact(fh, 32 * ln), dtype=np.uint64).reshape(ln, 4)
+def _check_format(format: str):
+    if format not in SERDE_FORMATS:
+        raise ValueError("unknown format %r" % (format,))
 
 
-def _write_poly_slice(fh, arrs):
-    fh.write(struct.pack(">I", len(arrs)))
-    for a in arrs:
-        _write_poly(fh, a)
+def key_layout(format: str, k: int, nf: int, npc: int, nsel: int, ext_shift: int) -> dict:
+    """where every section of a vk / pk lies (csrc/key_format.hpp key_layout): `polys` maps a section name to (off, count, len, slice) -- a slice starts with its
+    count word at off, polynomial i's length word is at off + (4 if slice) + i * (4 + 32 len)"""
+    _check_format(format)
+    if not 0 <= k <= 28:
+        raise ValueError("k out of range")
+    n, point = 1 << k, 32 if format == "processed" else 64
+    m = n << ext_shift
+    L = dict(k=k, n=n, m=m, point=point, off_fixed_c=8, off_perm_c=8 + point * nf, off_selectors=8 + point * (nf + npc), sel_bytes=(n + 7) // 8)
+    o = L["vk_size"] = L["off_selectors"] + L["sel_bytes"] * nsel
+    polys = {}
+    for name, cnt, ln in zip(KEY_SECTION_NAMES[2:], (1, 1, 1, nf, nf, nf, npc, npc, npc), (m, m, m, n, n, m, n, n, m)):
+        sl = not name.startswith("l")
+        polys[name] = (o, cnt, ln, sl)
+        o += (4 if sl else 0) + cnt * (4 + 32 * ln)
+    L["polys"], L["pk_size"] = polys, o
+    return L
 
 
-def _read_poly_slice(fh, expect_count: int, expect_len: int) -> np.ndarray:
-    (cnt,) = struct.unpack(">I", _exact(fh, 4))
-    if cnt != expect_count:
-        raise ValueError("polynomial slice of %d, expected %d" % (cnt, expect_count))
-    return np.stack([_read_poly(fh, expect_len) for _ in range(cnt)]) if cnt else np.zeros((0, expect_len, 4), dtype=np.uint64)
+def key_header_error(data: bytes, format: str, nf: int, npc: int, nsel: int, ext_shift: int, pk: bool, want_k: Optional[int] = None, length: Optional[int] = None) -> str:
+    """the verdict of csrc/key_format.hpp key_parse_header on a key's header and length: "" when it passes, the error's text otherwise.  `length`: the key's
+    length when `data` is only its first eight bytes"""
+    if format not in SERDE_FORMATS:
+        return "unknown format"
+    length = len(data) if length is None else length
+    if length < 8:
+        return "length: unexpected end of input"
+    k, nf_file = struct.unpack(">II", data[:8])
+    if k > 28:
+        return "k out of range"
+    if want_k is not None and k != want_k:
+        return "k differs from the params'"
+    if k + ext_shift > 32:
+        return "k out of range"
+    L = key_layout(format, k, nf, npc, nsel, ext_shift)
+    if nf_file != nf:
+        return "fixed-column count: the key's number of fixed commitments differs from the circuit's fixed columns"
+    if length != (L["pk_size"] if pk else L["vk_size"]):
+        return "length does not match the circuit (unexpected end of input or trailing bytes)"
+    return ""
+
+
+def scalars_to_repr(f: FieldSpec, words) -> bytes:
+    """to_repr of Montgomery words ((.., 4) u64): every word w as (w R^-1 mod p), 32 bytes little-endian"""
+    rinv = _rinv(f.p)
+    return b"".join((w * rinv % f.p).to_bytes(32, "little") for w in array_to_ints(np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, 4)))
+
+
+def scalars_from_repr(f: FieldSpec, data: bytes, section: str = "") -> np.ndarray:
+    """from_repr: 32-byte little-endian integers -> (count, 4) u64 Montgomery words; ValueError naming the lowest index that is not below p"""
+    R = (1 << 256) % f.p
+    vals = [int.from_bytes(data[i:i + 32], "little") for i in range(0, len(data), 32)]
+    for i, v in enumerate(vals):
+        if v >= f.p:
+            raise ValueError("an element is not below the modulus: %s, element %d" % (section, i))
+    return ints_to_array([v * R % f.p for v in vals]).reshape(-1, 4)
+
+
+def scalars_check(f: FieldSpec, words, section: str = ""):
+    """a checked from_raw_bytes: ValueError naming the lowest index whose stored Montgomery word is not below p"""
+    for i, w in enumerate(array_to_ints(np.ascontiguousarray(words, dtype=np.uint64).reshape(-1, 4))):
+        if w >= f.p:
+            raise ValueError("an element's stored word is not below the modulus: %s, element %d" % (section, i))
+
+
+def commitments_bytes(curve: CurveSpec, pts, format: str) -> bytes:
+    from .transcript import compress
+
+    pts = np.ascontiguousarray(pts, dtype=np.uint64).reshape(-1, 8)
+    return pts.tobytes() if format != "processed" else b"".join(compress(curve, P) for P in decode_points(curve, pts))
+
+
+def commitments_from_bytes(curve: CurveSpec, data: bytes, format: str, section: str = "") -> np.ndarray:
+    """a commitment list as the format reads it -> (count, 8) u64 Montgomery affine; "processed" and "raw" raise ValueError for anything that is not a point"""
+    from .transcript import decompress
+
+    p = curve.base.p
+    if format == "processed":
+        out = []
+        for i in range(0, len(data), 32):
+            e = data[i:i + 32]
+            x = int.from_bytes(e[:31] + bytes([e[31] & 0x7F]), "little")
+            if x >= p:
+                raise ValueError("an x coordinate is not below the modulus: " + section)
+            if x == 0 and e[31] >> 7:
+                raise ValueError("x = 0 with the sign bit set is not an encoding: " + section)
+            try:
+                out.append(decompress(curve, e))
+            except ValueError:
+                raise ValueError("an x coordinate is not on the curve: " + section) from None
+        return encode_points(curve, out) if out else np.zeros((0, 8), dtype=np.uint64)
+    pts = np.frombuffer(data, dtype=np.uint64).reshape(-1, 8).copy()
+    if format == "raw":
+        if any(v >= p for v in array_to_ints(pts.reshape(-1, 4))):
+            raise ValueError("a coordinate's stored word is not below the modulus: " + section)
+        for P in decode_points(curve, pts):
+            if P is not None and (P[1] * P[1] - P[0] * P[0] * P[0] - curve.b) % p:
+                raise ValueError("a point is neither on the curve nor the identity: " + section)
+    return pts
+
+
+def _elements_bytes(f: FieldSpec, arr, format: str) -> bytes:
+    return scalars_to_repr(f, arr) if format == "processed" else np.ascontiguousarray(arr, dtype=np.uint64).tobytes()
+
+
+class HostProvingKey:
+    """A proving key as it lies on disk, on the host: the verifying key and the nine polynomial sections in upstream's standard Montgomery form (numpy, no device).
+    l: (3, m, 4) = l0, l_last, l_active_row; the six slices: (count, len, 4).  write / read speak the three SerdeFormats; the device-resident ProvingKey goes
+    through this class, and the tests build keys by hand with it."""
+
+    SLICES = ("fixed_values", "fixed_polys", "fixed_cosets", "perm_values", "perm_polys", "perm_cosets")
+
+    def __init__(self, vk: "VerifyingKey", l, fixed_values, fixed_polys, fixed_cosets, perm_values, perm_polys, perm_cosets):
+        self.vk = vk
+        self.l = np.ascontiguousarray(l, dtype=np.uint64)
+        for name, a in zip(self.SLICES, (fixed_values, fixed_polys, fixed_cosets, perm_values, perm_polys, perm_cosets)):
+            setattr(self, name, np.ascontiguousarray(a, dtype=np.uint64))
+
+    def sections(self):
+        """(section name, (count, len, 4) array, is a slice) in file order"""
+        out = [(KEY_SECTION_NAMES[2 + i], self.l[i:i + 1], False) for i in range(3)]
+        return out + [(KEY_SECTION_NAMES[5 + i], getattr(self, name), True) for i, name in enumerate(self.SLICES)]
+
+    def write(self, fh, format: str = "raw-unchecked"):
+        _check_format(format)
+        f = self.vk.curve.scalar
+        self.vk.write(fh, format)
+        for _, arr, sl in self.sections():
+            if sl:
+                fh.write(struct.pack(">I", arr.shape[0]))
+            for poly in arr:
+                fh.write(struct.pack(">I", poly.shape[0]))
+                fh.write(_elements_bytes(f, poly, format))
+
+    def to_bytes(self, format: str = "raw-unchecked") -> bytes:
+        buf = io.BytesIO()
+        self.write(buf, format)
+        return buf.getvalue()
+
+    @classmethod
+    def read(cls, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0, format: str = "raw-unchecked") -> "HostProvingKey":
+        """ProvingKey::read(.., SerdeFormat) on the host.  ValueError for a key that does not fit the circuit and -- "processed", "raw" -- for a commitment that is
+        not a point or an element that is not below the modulus, naming the section and, for an element, its lowest index within the section.  Trailing bytes
+        are the caller's to check (from_bytes does)."""
+        _check_format(format)
+        vk = VerifyingKey.read(curve, cs, fh, num_selectors, format)
+        f = curve.scalar
+        n = 1 << vk.k
+        m = EvaluationDomain(None, f, cs.degree(), vk.k).extended_len()
+        nf, npc = cs.num_fixed, len(cs.permutation_columns)
+        got = []
+        for name, cnt, ln, sl in zip(KEY_SECTION_NAMES[2:], (1, 1, 1, nf, nf, nf, npc, npc, npc), (m, m, m, n, n, m, n, n, m), (False,) * 3 + (True,) * 6):
+            if sl:
+                (c,) = struct.unpack(">I", _exact(fh, 4))
+                if c != cnt:
+                    raise ValueError("polynomial count differs from the circuit's: %s" % name)
+            raw = []
+            for _ in range(cnt):
+                (l_,) = struct.unpack(">I", _exact(fh, 4))
+                if l_ != ln:
+                    raise ValueError("polynomial length differs from the domain's: %s" % name)
+                raw.append(_exact(fh, 32 * ln))
+            data = b"".join(raw)
+            if format == "processed":
+                arr = scalars_from_repr(f, data, name)
+            else:
+                arr = np.frombuffer(data, dtype=np.uint64).reshape(-1, 4).copy()
+                if format == "raw":
+                    scalars_check(f, arr, name)
+            got.append(arr.reshape(cnt, ln, 4))
+        return cls(vk, np.concatenate(got[:3]), *got[3:])
+
+    @classmethod
+    def from_bytes(cls, curve: CurveSpec, cs: plonk.ConstraintSystem, data: bytes, num_selectors: int = 0, format: str = "raw-unchecked") -> "HostProvingKey":
+        fh = io.BytesIO(bytes(data))
+        key = cls.read(curve, cs, fh, num_selectors, format)
+        if fh.read(1):
+            raise ValueError("length does not match the circuit (unexpected end of input or trailing bytes)")
+        return key
 
 
 # ---- keys -----------------------------------------------------------------------------------------------
@@ -428,23 +599,30 @@ class VerifyingKey:
         h.update(body)
         return int.from_bytes(h.digest(), "little") % self.curve.scalar.p
 
-    def write(self, fh):
+    def write(self, fh, format: str = "raw-unchecked"):
+        """VerifyingKey::write(.., SerdeFormat); both raw formats write the same bytes"""
+        _check_format(format)
         fh.write(struct.pack(">I", self.k))
         fh.write(struct.pack(">I", self.fixed_commitments.shape[0]))
-        fh.write(self.fixed_commitments.tobytes())
-        fh.write(self.permutation_commitments.tobytes())
+        fh.write(commitments_bytes(self.curve, self.fixed_commitments, format))
+        fh.write(commitments_bytes(self.curve, self.permutation_commitments, format))
         for sel in self.selectors:
             fh.write(np.packbits(sel, bitorder="little").tobytes())
 
     @classmethod
-    def read(cls, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0) -> "VerifyingKey":
+    def read(cls, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0, format: str = "raw-unchecked") -> "VerifyingKey":
+        """VerifyingKey::read(.., SerdeFormat); "processed" and "raw" raise ValueError for a commitment that is not a point, naming the list"""
+        _check_format(format)
         (k,) = struct.unpack(">I", _exact(fh, 4))
         (nf,) = struct.unpack(">I", _exact(fh, 4))
+        if k > 28 and format != "raw-unchecked":      # (the default format reads as it always has)
+            raise ValueError("k out of range")
         if nf != cs.num_fixed:
             raise ValueError("vk holds %d fixed commitments, the circuit has %d fixed columns" % (nf, cs.num_fixed))
-        fixed = np.frombuffer(_exact(fh, 64 * nf), dtype=np.uint64).reshape(nf, 8)
+        point = 32 if format == "processed" else 64
+        fixed = commitments_from_bytes(curve, _exact(fh, point * nf), format, KEY_SECTION_NAMES[0])
         npc = len(cs.permutation_columns)
-        perm = np.frombuffer(_exact(fh, 64 * npc), dtype=np.uint64).reshape(npc, 8)
+        perm = commitments_from_bytes(curve, _exact(fh, point * npc), format, KEY_SECTION_NAMES[1])
         n = 1 << k
         sels = [np.unpackbits(np.frombuffer(_exact(fh, (n + 7) // 8), dtype=np.uint8), bitorder="little")[:n].astype(bool) for _ in range(num_selectors)]
         return cls(curve, k, cs, fixed, perm, sels)
@@ -474,43 +652,38 @@ class ProvingKey:
         self.ctx.synchronize()
         return to_host(out)
 
-    def write(self, fh):
+    def to_host_key(self) -> HostProvingKey:
+        """the key's sections on the host, extended-domain columns converted out of the internal form"""
         with self.ctx.torch_stream():
-            self._write(fh)
+            def host(t, internal=False):
+                if not t.shape[0]:
+                    return np.zeros(tuple(t.shape), dtype=np.uint64)
+                return self._std(t) if internal else to_host(t)
 
-    def _write(self, fh):
-        self.vk.write(fh)
-        l = self._std(self.l_ext)
-        for i in range(3):
-            _write_poly(fh, l[i])
-        _write_poly_slice(fh, list(to_host(self.fixed_values)))
-        _write_poly_slice(fh, list(to_host(self.fixed_polys)))
-        _write_poly_slice(fh, list(self._std(self.fixed_cosets)) if self.fixed_cosets.shape[0] else [])
-        _write_poly_slice(fh, list(to_host(self.perm_values)))
-        _write_poly_slice(fh, list(to_host(self.perm_polys)))
-        _write_poly_slice(fh, list(self._std(self.perm_cosets)) if self.perm_cosets.shape[0] else [])
+            return HostProvingKey(self.vk, self._std(self.l_ext), host(self.fixed_values), host(self.fixed_polys), host(self.fixed_cosets, True),
+                                  host(self.perm_values), host(self.perm_polys), host(self.perm_cosets, True))
+
+    def write(self, fh, format: str = "raw-unchecked"):
+        """ProvingKey::write(.., SerdeFormat)"""
+        self.to_host_key().write(fh, format)
 
     @classmethod
-    def read(cls, ctx: Context, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0) -> "ProvingKey":
+    def read(cls, ctx: Context, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0, format: str = "raw-unchecked") -> "ProvingKey":
+        """ProvingKey::read(.., SerdeFormat); the checked formats raise ValueError (HostProvingKey.read)"""
         with ctx.torch_stream():
-            return cls._read(ctx, curve, cs, fh, num_selectors)
+            return cls._read(ctx, curve, cs, fh, num_selectors, format)
 
     @classmethod
-    def _read(cls, ctx: Context, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0) -> "ProvingKey":
-        vk = VerifyingKey.read(curve, cs, fh, num_selectors)
+    def _read(cls, ctx: Context, curve: CurveSpec, cs: plonk.ConstraintSystem, fh, num_selectors: int = 0, format: str = "raw-unchecked") -> "ProvingKey":
+        hk = HostProvingKey.read(curve, cs, fh, num_selectors, format)
         f = curve.scalar
-        domain = EvaluationDomain(ctx, f, cs.degree(), vk.k)
-        n, m = domain.n, domain.extended_len()
-        l = np.stack([_read_poly(fh, m) for _ in range(3)])
-        nf, npc = cs.num_fixed, len(cs.permutation_columns)
-        fv, fp, fc = _read_poly_slice(fh, nf, n), _read_poly_slice(fh, nf, n), _read_poly_slice(fh, nf, m)
-        pv, pp, pc = _read_poly_slice(fh, npc, n), _read_poly_slice(fh, npc, n), _read_poly_slice(fh, npc, m)
-        dev = [to_device(a) for a in (l, fv, fp, fc, pv, pp, pc)]
+        domain = EvaluationDomain(ctx, f, cs.degree(), hk.vk.k)
+        dev = [to_device(a) for a in (hk.l, hk.fixed_values, hk.fixed_polys, hk.fixed_cosets, hk.perm_values, hk.perm_polys, hk.perm_cosets)]
         for t in (dev[0], dev[3], dev[6]):
             if t.numel():
                 ctx.convert_form_device(f.id, t.data_ptr(), t.data_ptr(), t.numel() // 4, True, 0)
         ctx.synchronize()
-        return cls(ctx, vk, domain, *dev)
+        return cls(ctx, hk.vk, domain, *dev)
 
 
 def vk_size(cs: plonk.ConstraintSystem, k: int, num_selectors: int) -> int:

@@ -123,6 +123,12 @@ def _check(ctx: Context, rc: int):
         raise DehaloError(rc, load_library().dehalo_last_error(ctx.handle).decode())
 
 
+def _serde(format: str) -> int:
+    if format not in SERDE_FORMATS:
+        raise ValueError("unknown format %r" % (format,))
+    return SERDE_FORMATS[format]
+
+
 def _bytes_ptr(b):
     return C.cast(C.c_char_p(bytes(b)), C.c_void_p)
 
@@ -312,23 +318,54 @@ class ProvingKey:
         return cls(ctx, params.curve, cs, h)
 
     @classmethod
-    def read(cls, ctx: Context, curve: CurveSpec, cs: plonk.ConstraintSystem, data: bytes, num_selectors: int = 0) -> "ProvingKey":
-        desc = ConstraintSystemDescriptor(cs, curve.scalar)
-        buf = np.frombuffer(data, dtype=np.uint8)
+    def keygen_pk(cls, ctx: Context, params: ParamsKZG, cs: plonk.ConstraintSystem, vk_bytes: bytes, fixed_canonical, assembly: plonk.Assembly, num_selectors: int = 0,
+                  format: str = "raw-unchecked") -> "ProvingKey":
+        """VerifyingKey::read + keygen_pk(params, vk, circuit) (benches/delay_enc.rs:96-103): the proving key of the columns UNDER the verifying key `vk_bytes` (in
+        `format`, one of SERDE_FORMATS) -- its commitments are taken, not recomputed and not compared with the columns; no MSM runs (dehalo_keygen_pk)."""
+        f = params.curve.scalar
+        desc = ConstraintSystemDescriptor(cs, f)
+        fixed = np.ascontiguousarray(fixed_canonical, dtype=np.uint64)
+        mapping = np.ascontiguousarray(assembly.mapping, dtype=np.uint64)
+        buf = np.frombuffer(bytes(vk_bytes), dtype=np.uint8)
         h = C.c_void_p()
-        _check(ctx, load_library().dehalo_pk_read(ctx.handle, curve.id, desc.ref(), buf.ctypes.data, len(data), num_selectors, C.byref(h)))
+        _check(ctx, load_library().dehalo_keygen_pk(ctx.handle, params.handle, desc.ref(), buf.ctypes.data if buf.size else None, buf.size, _serde(format), num_selectors,
+                                                    fixed.ctypes.data, mapping.ctypes.data, KEYGEN_FIXED_CANONICAL, C.byref(h)))
+        return cls(ctx, params.curve, cs, h)
+
+    @classmethod
+    def read(cls, ctx: Context, curve: CurveSpec, cs: plonk.ConstraintSystem, data: bytes, num_selectors: int = 0, format: str = "raw-unchecked") -> "ProvingKey":
+        """ProvingKey::read(.., SerdeFormat): `format` one of SERDE_FORMATS ("processed": compressed commitments and canonical elements, decompressed / converted on the
+        device; "raw": Montgomery limbs, every point and every element checked; "raw-unchecked": the same bytes copied in unseen).  The default is dehalo_pk_read."""
+        desc = ConstraintSystemDescriptor(cs, curve.scalar)
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        h = C.c_void_p()
+        lib = load_library()
+        if format == "raw-unchecked":
+            _check(ctx, lib.dehalo_pk_read(ctx.handle, curve.id, desc.ref(), buf.ctypes.data if buf.size else None, buf.size, num_selectors, C.byref(h)))
+        else:
+            _check(ctx, lib.dehalo_pk_read_custom(ctx.handle, curve.id, desc.ref(), buf.ctypes.data if buf.size else None, buf.size, _serde(format), num_selectors, C.byref(h)))
         return cls(ctx, curve, cs, h)
 
-    def write(self) -> bytes:
+    def write(self, format: str = "raw-unchecked") -> bytes:
+        """ProvingKey::write(.., SerdeFormat) (dehalo_pk_write_custom); the default is dehalo_pk_write, whose bytes both raw formats are."""
         lib = load_library()
-        out = np.empty(lib.dehalo_pk_size(self.handle), dtype=np.uint8)
-        _check(self.ctx, lib.dehalo_pk_write(self.ctx.handle, self.handle, out.ctypes.data, out.size))
+        if format == "raw-unchecked":
+            out = np.empty(lib.dehalo_pk_size(self.handle), dtype=np.uint8)
+            _check(self.ctx, lib.dehalo_pk_write(self.ctx.handle, self.handle, out.ctypes.data, out.size))
+        else:
+            out = np.empty(lib.dehalo_pk_size_custom(self.handle, _serde(format)), dtype=np.uint8)
+            _check(self.ctx, lib.dehalo_pk_write_custom(self.ctx.handle, self.handle, _serde(format), out.ctypes.data, out.size))
         return out.tobytes()
 
-    def vk_bytes(self) -> bytes:
+    def vk_bytes(self, format: str = "raw-unchecked") -> bytes:
+        """VerifyingKey::write(.., SerdeFormat) (dehalo_vk_write_custom); the default is dehalo_vk_write, whose bytes both raw formats are."""
         lib = load_library()
-        out = np.empty(lib.dehalo_vk_size(self.handle), dtype=np.uint8)
-        _check(self.ctx, lib.dehalo_vk_write(self.handle, out.ctypes.data, out.size))
+        if format == "raw-unchecked":
+            out = np.empty(lib.dehalo_vk_size(self.handle), dtype=np.uint8)
+            _check(self.ctx, lib.dehalo_vk_write(self.handle, out.ctypes.data, out.size))
+        else:
+            out = np.empty(lib.dehalo_vk_size_custom(self.handle, _serde(format)), dtype=np.uint8)
+            _check(self.ctx, lib.dehalo_vk_write_custom(self.ctx.handle, self.handle, _serde(format), out.ctypes.data, out.size))
         return out.tobytes()
 
     @property

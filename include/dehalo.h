@@ -236,6 +236,19 @@ int dehalo_points_compress_device(dehalo_ctx* ctx, int curve, const uint64_t* d_
 int dehalo_points_decompress_device(dehalo_ctx* ctx, int curve, const uint8_t* d_in32, size_t count, uint64_t* d_affine_xy, uint32_t* status_out, void* stream);
 int dehalo_points_check_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t count, uint32_t* status_out, void* stream);
 
+/* The scalar codec, the point codec's twin: vectors of field elements between their in-memory form (4 x u64 Montgomery limbs, 16-byte aligned) and the two forms
+ * they take in a key on disk [UPSTREAM halo2curves 0.3.x PrimeField::from_repr, SerdeObject::from_raw_bytes; restated from memory: INTEGRATION.md section 7].
+ * Streaming maps, one lane per element, device memory in and out, every field id (an unknown field is DEHALO_ERR_INVALID); count < 2^29, and count = 0 returns 0
+ * without a launch, with status 0 and first_bad 0.  Asynchronous on the stream except for the download of the two result words; no workspace beyond them.
+ *   from_repr  `count` 32-byte little-endian integers (4-byte aligned) -> Montgomery words.  *status_out (host) collects 1 = an element not below the modulus;
+ *              such an element is written as 0 and the call still returns 0: the status is the verdict.  *first_bad_out (host) = the lowest offending index,
+ *              `count` if there is none.  d_out may be d_in32 itself (in place) and may overlap it in no other way (DEHALO_ERR_INVALID).
+ *   check      what a checked from_raw_bytes does per element; reads only.  Status 1 = a stored Montgomery word not below the modulus; first_bad as above.
+ * The other direction, to_repr, is dehalo_field_op_device op 5. */
+int dehalo_scalars_from_repr_device(dehalo_ctx* ctx, int field, const uint8_t* d_in32, size_t count, uint64_t* d_out, uint32_t* status_out, uint64_t* first_bad_out,
+                                    void* stream);
+int dehalo_scalars_check_device(dehalo_ctx* ctx, int field, const uint64_t* d_words, size_t count, uint32_t* status_out, uint64_t* first_bad_out, void* stream);
+
 /* ---- NTT == halo2_proofs::arithmetic::best_fft(a, omega, log_n) ---------------------------
  * [halo2_proofs/src/arithmetic.rs].  In place, natural order in and out,
  * a'[i] = sum_j a[j] * omega^(i*j), no scaling.  a: 2^log_n x 4 u64.  omega must be a
@@ -652,6 +665,39 @@ size_t dehalo_pk_size(const dehalo_pk* pk);
 int dehalo_pk_write(dehalo_ctx* ctx, const dehalo_pk* pk, uint8_t* out, size_t cap);
 size_t dehalo_vk_size(const dehalo_pk* pk);
 int dehalo_vk_write(const dehalo_pk* pk, uint8_t* out, size_t cap);
+/* Keys in every SerdeFormat [UPSTREAM halo2_proofs/src/plonk.rs VerifyingKey / ProvingKey::{write, read}(.., SerdeFormat), poly.rs, helpers.rs; restated from memory:
+ * INTEGRATION.md sections 7 and 15].  The formats are dehalo_serde_format's (declared with the params above; plain int here):
+ *   vk   = k: u32 BE | num_fixed: u32 BE | fixed commitments | permutation commitments | selectors (2^k bits each, packed LSB first)
+ *   pk   = vk | l0 | l_last | l_active_row | slice(fixed_values) | slice(fixed_polys) | slice(fixed_cosets) | slice(perm values) | slice(perm polys) | slice(perm cosets)
+ *   poly = len: u32 BE | len elements          slice = count: u32 BE | count polys
+ *   DEHALO_SERDE_PROCESSED            a commitment is 32 B (the point codec's compressed form), an element its canonical integer, 32 B little-endian (to_repr).
+ *                                     Read: every point is decompressed on the device (status 1 / 2 / 4 fail), every element must be below p (from_repr).
+ *   DEHALO_SERDE_RAW_BYTES            a commitment is 64 B, an element 32 B, Montgomery limbs.  Read: every point goes through dehalo_points_check_device (status
+ *                                     1 / 2 fail; (0, 0) is legal), every element's stored word must be below p (dehalo_scalars_check_device).
+ *   DEHALO_SERDE_RAW_BYTES_UNCHECKED  the same bytes, copied in unseen: dehalo_pk_read itself, giving an equal key.
+ * Both raw formats write dehalo_pk_write's / dehalo_vk_write's bytes; the Processed vk and pk are each 32 x (num_fixed + permutation columns) bytes shorter.  All
+ * three curves.  Extended-domain columns leave in upstream's standard form.  size_custom returns 0 for null or an unknown format.  A null ctx in a write means the
+ * key's own.  The read uploads one slice at a time and runs one conversion or check launch per slice (one
+ * per 2^28 elements of a slice that holds more: the scalar codec's count limit is not the key's).
+ * Every failure of a read is DEHALO_ERR_INVALID, with a message that names its kind -- the length, k, the fixed-column count, a polynomial length or count, an x
+ * not below the modulus, an x not on the curve, x = 0 with the sign bit set, a stored coordinate word not below the modulus, a point off the curve, an element (or
+ * its stored word) not below the modulus -- and the section (which commitment list, which polynomial slice), for an element also the lowest offending index
+ * within that section; it leaves nothing allocated and the context usable.  An unknown format is DEHALO_ERR_INVALID from every call. */
+size_t dehalo_vk_size_custom(const dehalo_pk* pk, int format);
+int dehalo_vk_write_custom(dehalo_ctx* ctx, const dehalo_pk* pk, int format, uint8_t* out, size_t cap);
+size_t dehalo_pk_size_custom(const dehalo_pk* pk, int format);
+int dehalo_pk_write_custom(dehalo_ctx* ctx, const dehalo_pk* pk, int format, uint8_t* out, size_t cap);
+int dehalo_pk_read_custom(dehalo_ctx* ctx, int curve, const dehalo_constraint_system* cs, const uint8_t* bytes, size_t len, int format, uint32_t num_selectors,
+                          dehalo_pk** out);
+/* VerifyingKey::read + keygen_pk(params, vk, circuit) [UPSTREAM halo2_proofs/src/plonk/keygen.rs; benches/delay_enc.rs:96-103]: the proving key of `fixed` /
+ * `permutation_mapping` UNDER the given verifying key.  The vk is parsed in vk_format (a checked format checks its commitments as above); its commitments and packed
+ * selectors become the key's, and fixed_values / polys / cosets, the permutation's three column sets and l0 / l_last / l_active_row are built exactly as
+ * dehalo_keygen builds them -- without launching an MSM.  The vk's commitments are NOT compared with the columns, as upstream does not: a vk that belongs to other
+ * columns gives a key whose proofs a verifier rejects.  DEHALO_ERR_INVALID when the vk's k differs from the params', its num_fixed from the circuit's, or the length
+ * does not fit.  flags: dehalo_keygen's.  Both schemes; under ParamsIPA the vk's commitments already carry [Blind::default()] W.  The substitute transcript_repr is
+ * the one dehalo_keygen would give for the same vk bytes. */
+int dehalo_keygen_pk(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len, int vk_format,
+                     uint32_t num_selectors, const uint64_t* fixed, const uint64_t* permutation_mapping, uint32_t flags, dehalo_pk** out);
 /* vk.transcript_repr, the first thing create_proof absorbs.  Upstream derives it from the Debug text of the pinned verifying key, which
  * cannot be reproduced outside the crate: an integrator passes upstream's value (4 x u64 Montgomery).  Until set, the key carries a
  * substitute: Blake2b-512("Halo2-Verify-Key") over the key's RawBytes and a binary encoding of the constraint system. */
