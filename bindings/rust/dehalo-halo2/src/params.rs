@@ -181,7 +181,8 @@ impl Drop for DehaloParamsKZG<'_> {
 
 /// `ParamsIPA<EqAffine>` (Vesta) from the vectors upstream's `ParamsIPA` holds (`params.g`, `params.g_lagrange`, `params.w`, `params.u`):
 /// `dehalo_params_ipa_create`; from `params.g`, `params.w`, `params.u` alone (`from_g`: `g_to_lagrange` runs on the device); or from `ParamsIPA::write`'s
-/// bytes (`read` / `write`).  `ParamsIPA::new` (the hash-to-curve generators) is not provided by the library; what it provides over these params is
+/// bytes (`read` / `write`).  `ParamsIPA::new` (the hash-to-curve generators) is not provided by the library; `generate` derives generators of the library's
+/// own public rule instead.  What it provides over these params is
 /// keygen (`commit_lagrange` with `Blind::default()`), whole `ProverIPA` proofs (`prover::create_proof_ipa`) and the opening argument of one
 /// polynomial (`dehalo_ipa_open`, upstream's `poly::ipa::commitment::create_proof`).
 pub struct DehaloParamsIPA<'c> {
@@ -210,6 +211,16 @@ impl<'c> DehaloParamsIPA<'c> {
         ctx.check(unsafe {
             sys::dehalo_params_ipa_from_g(ctx.as_ptr(), sys::DEHALO_CURVE_VESTA, k, g.as_ptr() as *const u64, w as *const _ as *const u64, u as *const _ as *const u64, &mut raw)
         })?;
+        Ok(Self { ctx, raw, k })
+    }
+
+    /// `ParamsIPA` at any `k` without a file: `g`, `W`, `U` derived on the device by the library's public rule (include/dehalo.h, "Generated points":
+    /// ChaCha20 under `key`, `None` = the default key), `g_lagrange` by the group FFT (`dehalo_params_ipa_generate`).  These are NOT the generators of
+    /// upstream's `ParamsIPA::new`: an upstream verifier gets them through `write` and `ParamsIPA::read`.
+    pub fn generate(ctx: &'c Context, k: u32, key: Option<&[u8; 32]>) -> Result<Self, DehaloError> {
+        let mut raw = core::ptr::null_mut();
+        let key_ptr = key.map_or(core::ptr::null(), |b| b.as_ptr());
+        ctx.check(unsafe { sys::dehalo_params_ipa_generate(ctx.as_ptr(), sys::DEHALO_CURVE_VESTA, k, key_ptr, &mut raw) })?;
         Ok(Self { ctx, raw, k })
     }
 

@@ -40,6 +40,7 @@ SYMBOLS = [
     "dehalo_params_size_custom", "dehalo_params_write_custom", "dehalo_params_read_custom", "dehalo_params_from_g", "dehalo_params_downsize",
     "dehalo_scalars_from_repr_device", "dehalo_scalars_check_device",
     "dehalo_vk_size_custom", "dehalo_vk_write_custom", "dehalo_pk_size_custom", "dehalo_pk_write_custom", "dehalo_pk_read_custom", "dehalo_keygen_pk",
+    "dehalo_points_generate_device", "dehalo_params_ipa_generate",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -267,6 +268,8 @@ def load_library():
     lib.dehalo_points_compress_device.argtypes = [P, C.c_int, u64p, sz, P, P]
     lib.dehalo_points_decompress_device.argtypes = [P, C.c_int, P, sz, u64p, C.POINTER(C.c_uint32), P]
     lib.dehalo_points_check_device.argtypes = [P, C.c_int, u64p, sz, C.POINTER(C.c_uint32), P]
+    lib.dehalo_points_generate_device.argtypes = [P, C.c_int, P, C.c_uint64, C.c_uint64, u64p, sz, P]
+    lib.dehalo_params_ipa_generate.argtypes = [P, C.c_int, u32, P, PP]
     lib.dehalo_params_size_custom.argtypes = [P, C.c_int]
     lib.dehalo_params_size_custom.restype = sz
     lib.dehalo_params_write_custom.argtypes = [P, C.c_int, P, sz]
@@ -538,6 +541,14 @@ class Context:
         st = C.c_uint32(0)
         self._check(self.lib.dehalo_points_check_device(self.handle, curve, d_affine or None, count, C.byref(st), stream or None))
         return st.value
+
+    def points_generate(self, curve: int, d_affine: int, count: int, first_index: int = 0, chacha_stream: int = 0, key: Optional[bytes] = None, stream: int = 0):
+        """the generated points (curve, key, chacha_stream, first_index + i), i < count, as affine points at d_affine (device): the public rule of include/dehalo.h,
+        "Generated points"; key = 32 bytes, None = DEHALO_GENERATORS_DEFAULT_KEY (dehalo_points_generate_device)"""
+        if key is not None and len(key) != 32:
+            raise ValueError("key must be 32 bytes")
+        kb = None if key is None else np.frombuffer(bytes(key), dtype=np.uint8)
+        self._check(self.lib.dehalo_points_generate_device(self.handle, curve, None if kb is None else kb.ctypes.data, chacha_stream, first_index, d_affine or None, count, stream or None))
 
     def scalars_from_repr(self, field: int, d_in32: int, count: int, d_out: int, stream: int = 0) -> tuple:
         """PrimeField::from_repr of `count` 32-byte little-endian integers (device, 4-byte aligned) into Montgomery words at d_out (device; d_in32 itself: in place)

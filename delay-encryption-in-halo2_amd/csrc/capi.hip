@@ -714,6 +714,25 @@ int dehalo_points_check_device(dehalo_ctx* ctx, int curve, const uint64_t* d_aff
     });
 }
 
+// ---- generated points (gfft.cuh k_points_generate; the rule: include/dehalo.h) ----
+int dehalo_points_generate_device(dehalo_ctx* ctx, int curve, const uint8_t* key32, uint64_t chacha_stream, uint64_t first_index, uint64_t* d_affine_xy, size_t count,
+                                  void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    const GfftOps* ops;
+    TRY(points_codec_args(ctx, "points_generate", curve, d_affine_xy, nullptr, count, &ops));
+    const uint64_t index_end = (uint64_t)1 << 48;
+    if (first_index > index_end || count > index_end - first_index) return dh_fail(ctx, DEHALO_ERR_INVALID, "points_generate: first_index + count > 2^48");
+    if (!ops) return 0;
+    uint32_t key[8];
+    memcpy(key, key32 ? (const void*)key32 : (const void*)DEHALO_GENERATORS_DEFAULT_KEY, 32);
+    uint32_t status = 0;
+    TRY(dh_device(ctx, stream, [&](hipStream_t s) {
+        return points_status(ctx, &status, s, [&](uint32_t* d_status) { return ops->points_generate(ctx, key, chacha_stream, first_index, (affine_t*)d_affine_xy, count, d_status, s); });
+    }));
+    if (status) return dh_fail(ctx, DEHALO_ERR_INVALID, "points_generate: an index found no point in 256 attempts (written as (0, 0))");
+    return 0;
+}
+
 // ---- the scalar codec (scalar_codec.cuh): from_repr and the checked from_raw_bytes over vectors of field elements ----
 int dehalo_scalars_from_repr_device(dehalo_ctx* ctx, int field, const uint8_t* d_in32, size_t count, uint64_t* d_out, uint32_t* status_out, uint64_t* first_bad_out,
                                     void* stream) {

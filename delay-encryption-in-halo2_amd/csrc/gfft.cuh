@@ -20,6 +20,7 @@
 // Exceptional group-law cases (identity inputs, a = +-[t] b: a constant g collapses to one non-zero output) pass through the quad operations'
 // own exceptional paths.  No scratch memory.
 #pragma once
+#include "hostrng.hpp"      // chacha_indexed_block: the block function k_points_generate shares with k_chacha_scalars (params.hip)
 #include "ipa.cuh"
 
 // tw[j] = base^j (standard Montgomery), j < count
@@ -184,6 +185,41 @@ int gfft_t(dehalo_ctx* ctx, const affine_t* d_g, uint32_t k, const uint64_t omeg
     return 0;
 }
 
+// r = a square root of a (standard Montgomery, below p), false when a is a non-residue (r is then meaningless); a = 0 gives r = 0.  Which of the two roots
+// is the caller's to choose.  t_exp = (p - 1) / 2^S, canonical (sqrt_t_exp below).  Shared by k_decompress and k_points_generate.
+template <class F>
+FP_DEV bool f_sqrt_ts(const fe& a, const fe& t_exp, fe& r) {
+    // Tonelli-Shanks: p - 1 = t 2^S.  w = a^((t - 1) / 2); r = a w (a^((t + 1) / 2)); tt = r w (a^t); c = ROOT_OF_UNITY (a generator of the 2^S-th roots)
+    fe e = t_exp;                                                                     // (t - 1) / 2: t is odd
+#pragma unroll
+    for (int j = 0; j < 8; j++) e.v[j] = (e.v[j] >> 1) | (j < 7 ? e.v[j + 1] << 31 : 0);
+    fe w = f_one<F>();
+    for (int bit = 0; bit < 256; bit++) {                                             // (the exponent is shifted through its top bit: no indexed register)
+        w = f_sqr<F>(w);
+        if (e.v[7] >> 31) w = f_mul<F>(w, a);
+#pragma unroll
+        for (int j = 7; j >= 0; j--) e.v[j] = (e.v[j] << 1) | (j ? e.v[j - 1] >> 31 : 0);
+    }
+    r = f_mul<F>(a, w);
+    fe tt = f_mul<F>(r, w), c = f_const<F>(F::ROOT_OF_UNITY_M);
+    const fe one = f_one<F>();
+    if (f_is_zero(a)) { r = f_zero(); tt = one; }
+    u32 m = F::TWO_ADICITY;
+    while (!f_eq(tt, one)) {
+        u32 l = 0;
+        fe t2 = tt;
+        while (!f_eq(t2, one) && l < m) { t2 = f_sqr<F>(t2); l++; }
+        if (l >= m) return false;                                                     // the order of a^t is 2^S: a is a non-residue
+        fe bb = c;
+        for (u32 z = 0; z + l + 1 < m; z++) bb = f_sqr<F>(bb);
+        m = l;
+        c = f_sqr<F>(bb);
+        tt = f_mul<F>(tt, c);
+        r = f_mul<F>(r, bb);
+    }
+    return true;
+}
+
 // ---- GroupEncoding::from_bytes for a vector of points (ParamsIPA::read): in = 32 B per point (x little-endian, bit 255 = y is odd, all zero = the
 // identity), out = affine standard Montgomery.  One lane per point, plain fp.cuh arithmetic: y = sqrt(x^3 + b) by Tonelli-Shanks with the field's
 // 2-adicity S (read from the field's constants); not throughput-critical.  status[0] |= 1: an x not below p; 2: not on the curve; 4: x = 0 with the
@@ -212,51 +248,30 @@ __global__ __launch_bounds__(128) void k_decompress(const u32* __restrict__ in, 
     }
     const fe xm = f_to_mont<F>(x);
     const fe a = f_add<F>(f_mul<F>(f_sqr<F>(xm), xm), f_const<F>(CV::B_M));        // x^3 + b
-    // Tonelli-Shanks: p - 1 = t 2^S.  w = a^((t - 1) / 2); r = a w (a^((t + 1) / 2)); tt = r w (a^t); c = ROOT_OF_UNITY (a generator of the 2^S-th roots)
-    fe e = t_exp;                                                                     // (t - 1) / 2: t is odd
-#pragma unroll
-    for (int j = 0; j < 8; j++) e.v[j] = (e.v[j] >> 1) | (j < 7 ? e.v[j + 1] << 31 : 0);
-    fe w = f_one<F>();
-    for (int bit = 0; bit < 256; bit++) {                                             // (the exponent is shifted through its top bit: no indexed register)
-        w = f_sqr<F>(w);
-        if (e.v[7] >> 31) w = f_mul<F>(w, a);
-#pragma unroll
-        for (int j = 7; j >= 0; j--) e.v[j] = (e.v[j] << 1) | (j ? e.v[j - 1] >> 31 : 0);
-    }
-    fe r = f_mul<F>(a, w), tt = f_mul<F>(r, w), c = f_const<F>(F::ROOT_OF_UNITY_M);
-    const fe one = f_one<F>();
-    bool ok = true;
-    if (f_is_zero(a)) { r = f_zero(); tt = one; }
-    u32 m = F::TWO_ADICITY;
-    while (!f_eq(tt, one)) {
-        u32 l = 0;
-        fe t2 = tt;
-        while (!f_eq(t2, one) && l < m) { t2 = f_sqr<F>(t2); l++; }
-        if (l >= m) { ok = false; break; }                                            // the order of a^t is 2^S: a is a non-residue
-        fe bb = c;
-        for (u32 z = 0; z + l + 1 < m; z++) bb = f_sqr<F>(bb);
-        m = l;
-        c = f_sqr<F>(bb);
-        tt = f_mul<F>(tt, c);
-        r = f_mul<F>(r, bb);
-    }
+    fe r;
+    const bool ok = f_sqrt_ts<F>(a, t_exp, r);
     if (!ok) { atomicOr(status, 2u); aff_store(&out[i], o); return; }
     if ((f_from_mont<F>(r).v[0] & 1u) != sign) r = f_neg<F>(r);
     o.x = xm; o.y = r;
     aff_store(&out[i], o);
 }
 
-template <class CV>
-int decompress_t(dehalo_ctx* ctx, const uint8_t* d_in, affine_t* d_out, uint64_t count, uint32_t* d_status, hipStream_t s) {
-    typedef typename CV::Base F;
-    if (count == 0) return 0;
-    // (p - 1) >> S
+// f_sqrt_ts's exponent, on the host: (p - 1) >> S
+template <class F>
+fe sqrt_t_exp() {
     fe t;
     for (int i = 0; i < 8; i++) t.v[i] = F::P[i];
     t.v[0] -= 1;                                                                      // p is odd
     for (int sh = 0; sh < F::TWO_ADICITY; sh++)
         for (int i = 0; i < 8; i++) t.v[i] = (t.v[i] >> 1) | (i < 7 ? t.v[i + 1] << 31 : 0);
-    k_decompress<CV><<<(u32)((count + 127) / 128), 128, 0, s>>>((const u32*)d_in, d_out, (u32)count, t, d_status);
+    return t;
+}
+
+template <class CV>
+int decompress_t(dehalo_ctx* ctx, const uint8_t* d_in, affine_t* d_out, uint64_t count, uint32_t* d_status, hipStream_t s) {
+    typedef typename CV::Base F;
+    if (count == 0) return 0;
+    k_decompress<CV><<<(u32)((count + 127) / 128), 128, 0, s>>>((const u32*)d_in, d_out, (u32)count, sqrt_t_exp<F>(), d_status);
     HIP_TRY(ctx, hipGetLastError());
     return 0;
 }
@@ -319,7 +334,61 @@ int points_check_t(dehalo_ctx* ctx, const affine_t* d_in, uint64_t count, uint32
     return 0;
 }
 
+// ---- points by a public rule (include/dehalo.h, "Generated points"): out[i] = the point named (curve, key, stream, first + i) -- the first ChaCha20 block
+// (indexed schedule, attempt = 0, 1, ...) whose first 32 bytes k_decompress's rules decode to a point other than the identity.  One lane per index, plain
+// fp.cuh arithmetic, no scratch.  Two loops, so that a wave pays a square root only for candidates that can be a point: the inner one draws blocks until
+// 0 < x < p (word compares, no field arithmetic: half of all Pasta candidates end here) and the lanes of a wave meet again in front of f_sqrt_ts, which then
+// runs once per outer trip for every lane still searching.  A wave makes as many trips as its slowest lane (about 7 where a lane needs 2 on Pasta:
+// DESIGN.md section 4 for what that costs and why it was left).  Both loops are bounded by DEHALO_GENERATORS_MAX_ATTEMPTS blocks per index; an index that
+// uses them up is written as (0, 0) and raises status[0] |= 1.  That path cannot be reached with a real key ((3/4)^256) and is not tested.
+template <class CV>
+__global__ __launch_bounds__(128) void k_points_generate(ChaKey key, u64 stream, u64 first, affine_t* out, u32 count, fe t_exp, u32* status) {
+    typedef typename CV::Base F;
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const u64 index = first + i;
+    affine_t o;
+    o.x = f_zero(); o.y = f_zero();
+    bool found = false;
+    u32 attempt = 0;
+    while (attempt < DEHALO_GENERATORS_MAX_ATTEMPTS) {
+        fe x;
+        u32 sign = 0;
+        bool in_range = false;
+        while (attempt < DEHALO_GENERATORS_MAX_ATTEMPTS && !in_range) {
+            chacha_indexed_block(key.k, stream, index, attempt, x.v);
+            attempt++;
+            sign = x.v[7] >> 31;
+            x.v[7] &= 0x7fffffffu;
+            in_range = f_below_p<F>(x) && !f_is_zero(x);
+        }
+        if (!in_range) break;
+        const fe xm = f_to_mont<F>(x);
+        const fe a = f_add<F>(f_mul<F>(f_sqr<F>(xm), xm), f_const<F>(CV::B_M));    // x^3 + b
+        fe r;
+        if (f_sqrt_ts<F>(a, t_exp, r) && !f_is_zero(a)) {
+            if ((f_from_mont<F>(r).v[0] & 1u) != sign) r = f_neg<F>(r);
+            o.x = xm; o.y = r;
+            found = true;
+            break;
+        }
+    }
+    if (!found) atomicOr(status, 1u);
+    aff_store(&out[i], o);
+}
+
+template <class CV>
+int points_generate_t(dehalo_ctx* ctx, const uint32_t key[8], uint64_t cha_stream, uint64_t first, affine_t* d_out, uint64_t count, uint32_t* d_status, hipStream_t s) {
+    typedef typename CV::Base F;
+    if (count == 0) return 0;
+    ChaKey ck;
+    memcpy(ck.k, key, 32);
+    k_points_generate<CV><<<(u32)((count + 127) / 128), 128, 0, s>>>(ck, cha_stream, first, d_out, (u32)count, sqrt_t_exp<F>(), d_status);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 template <class CV>
 constexpr GfftOps make_gfft_ops() {
-    return {&gfft_t<CV>, &decompress_t<CV>, &compress_t<CV>, &points_check_t<CV>};
+    return {&gfft_t<CV>, &decompress_t<CV>, &compress_t<CV>, &points_check_t<CV>, &points_generate_t<CV>};
 }

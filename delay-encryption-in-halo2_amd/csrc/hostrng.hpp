@@ -42,6 +42,29 @@ DH_HOST_DEVICE inline bool chacha_accept(uint32_t v[8], const uint32_t p[8], uin
     return below;
 }
 
+// The ChaCha20 block function (RFC 8439) over the INDEXED schedule, in the two kernels that draw by index (k_chacha_scalars, params.hip; k_points_generate,
+// gfft.cuh): state = sigma | key | index mod 2^32 | (index >> 32 & 0xffff) | attempt << 16 | stream, low word first.  v = the block's first eight words
+// (its first 32 bytes, little-endian): the others are never formed.
+struct ChaKey { uint32_t k[8]; };      // a key as a kernel argument
+DH_HOST_DEVICE inline uint32_t chacha_rotl(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
+DH_HOST_DEVICE inline void chacha_indexed_block(const uint32_t key[8], uint64_t stream, uint64_t index, uint32_t attempt, uint32_t v[8]) {
+    const uint32_t st[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7],
+                             (uint32_t)index, ((uint32_t)(index >> 32) & 0xffffu) | (attempt << 16), (uint32_t)stream, (uint32_t)(stream >> 32)};
+    uint32_t x[16];
+    DH_UNROLL
+    for (int j = 0; j < 16; j++) x[j] = st[j];
+#define CHA_QR(a, b, c, d)                                                                                                 \
+    x[a] += x[b]; x[d] = chacha_rotl(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = chacha_rotl(x[b] ^ x[c], 12);                  \
+    x[a] += x[b]; x[d] = chacha_rotl(x[d] ^ x[a], 8);  x[c] += x[d]; x[b] = chacha_rotl(x[b] ^ x[c], 7);
+    for (int r = 0; r < 10; r++) {
+        CHA_QR(0, 4, 8, 12) CHA_QR(1, 5, 9, 13) CHA_QR(2, 6, 10, 14) CHA_QR(3, 7, 11, 15)
+        CHA_QR(0, 5, 10, 15) CHA_QR(1, 6, 11, 12) CHA_QR(2, 7, 8, 13) CHA_QR(3, 4, 9, 14)
+    }
+#undef CHA_QR
+    DH_UNROLL
+    for (int j = 0; j < 8; j++) v[j] = x[j] + st[j];
+}
+
 struct Pcg64 {
     u128 state, inc;
     static u128 mult() { return ((u128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL; }

@@ -307,7 +307,7 @@ struct IpaOps {
 const IpaOps& pallas_ipa_ops();
 const IpaOps& vesta_ipa_ops();
 const IpaOps* ipa_ops(int curve);       // capi.hip: null unless Pallas / Vesta
-// g_to_lagrange (the group FFT) and the point codec (decompress, compress, check), one table per curve (gfft.cuh, instantiated in msm_*.hip)
+// g_to_lagrange (the group FFT), the point codec (decompress, compress, check) and the generated points, one table per curve (gfft.cuh, instantiated in msm_*.hip)
 struct GfftOps {
     // d_out = g_to_lagrange(d_g): 2^k affine points, 1 <= k; d_out == d_g or disjoint; omega_inv standard Montgomery, n_inv canonical (4 x u64 each)
     int (*g_to_lagrange)(dehalo_ctx* ctx, const affine_t* d_g, uint32_t k, const uint64_t omega_inv[4], const uint64_t n_inv_canon[4], affine_t* d_out, hipStream_t s);
@@ -317,6 +317,9 @@ struct GfftOps {
     int (*compress)(dehalo_ctx* ctx, const affine_t* d_in, uint8_t* d_out, uint64_t count, hipStream_t s);
     // a checked from_raw_bytes over `count` affine points, read only; d_status[0] |= 1 (a coordinate's word >= p) | 2 (neither on the curve nor (0, 0))
     int (*points_check)(dehalo_ctx* ctx, const affine_t* d_in, uint64_t count, uint32_t* d_status, hipStream_t s);
+    // d_out[i] = the point named (curve, key, cha_stream, first + i) by the generated-points rule of include/dehalo.h, i < count; d_status[0] |= 1 (an index used up
+    // its attempts and was written as (0, 0))
+    int (*points_generate)(dehalo_ctx* ctx, const uint32_t key[8], uint64_t cha_stream, uint64_t first, affine_t* d_out, uint64_t count, uint32_t* d_status, hipStream_t s);
 };
 const GfftOps& bn254_gfft_ops();
 const GfftOps& pallas_gfft_ops();

@@ -14,28 +14,13 @@ namespace {
 // the proof's ChaCha20 key (32 bytes of operating-system entropy, or the caller's) instead of being drawn on a host thread and uploaded.  Scalar i = the first of
 // ChaCha20 blocks (counter low = i, counter high = attempt 0, 1, ...), nonce = the helper's stream, whose first 256 bits masked to the modulus' length are < p
 // (chacha_accept, hostrng.hpp): uniform over the field.  The schedule of all draws: include/dehalo.h, dehalo_rng_kind.
-struct ChaKey { u32 k[8]; };
-__device__ __forceinline__ u32 cha_rotl(u32 x, int n) { return (x << n) | (x >> (32 - n)); }
+// (the block function: chacha_indexed_block, hostrng.hpp, shared with the generator kernel of gfft.cuh)
 __global__ void k_chacha_scalars(ChaKey key, u64 stream, fe p, u32 bits, fe* out, u64 n) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     for (u32 attempt = 0;; attempt++) {
-        u32 st[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key.k[0], key.k[1], key.k[2], key.k[3], key.k[4], key.k[5], key.k[6], key.k[7],
-                      (u32)i, ((u32)(i >> 32) & 0xffffu) | (attempt << 16), (u32)stream, (u32)(stream >> 32)};
-        u32 x[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) x[j] = st[j];
-#define CHA_QR(a, b, c, d)                                                                                         \
-    x[a] += x[b]; x[d] = cha_rotl(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = cha_rotl(x[b] ^ x[c], 12);                \
-    x[a] += x[b]; x[d] = cha_rotl(x[d] ^ x[a], 8);  x[c] += x[d]; x[b] = cha_rotl(x[b] ^ x[c], 7);
-        for (int r = 0; r < 10; r++) {
-            CHA_QR(0, 4, 8, 12) CHA_QR(1, 5, 9, 13) CHA_QR(2, 6, 10, 14) CHA_QR(3, 7, 11, 15)
-            CHA_QR(0, 5, 10, 15) CHA_QR(1, 6, 11, 12) CHA_QR(2, 7, 8, 13) CHA_QR(3, 4, 9, 14)
-        }
-#undef CHA_QR
         fe v;
-#pragma unroll
-        for (int j = 0; j < 8; j++) v.v[j] = x[j] + st[j];
+        chacha_indexed_block(key.k, stream, i, attempt, v.v);
         if (chacha_accept(v.v, p.v, bits)) {
             out[i] = v;
             return;
@@ -282,6 +267,37 @@ extern "C" int dehalo_params_ipa_from_g(dehalo_ctx* ctx, int curve, uint32_t k, 
         std::vector<uint64_t> gl(8 * n);
         TRY(dehalo_download(ctx, dgl.p, 64 * n, gl.data()));
         return ipa_params_finish(ctx, curve, k, g, gl.data(), w, u, out);
+    });
+}
+
+// ParamsIPA without a file: g | W | U are generated points (gfft.cuh k_points_generate; the rule: include/dehalo.h), g_lagrange the group FFT of g where it lies,
+// then as dehalo_params_ipa_from_g
+extern "C" int dehalo_params_ipa_generate(dehalo_ctx* ctx, int curve, uint32_t k, const uint8_t* key32, dehalo_params** out) {
+    return dh_guard(ctx, [&]() -> int {
+        if (!ctx || !out) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_generate: null argument");
+        TRY(ipa_params_check(ctx, "params_ipa_generate", curve, k));
+        std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+        (void)hipSetDevice(ctx->device);
+        const size_t n = (size_t)1 << k;
+        uint32_t key[8];
+        memcpy(key, key32 ? (const void*)key32 : (const void*)DEHALO_GENERATORS_DEFAULT_KEY, 32);
+        DevMem dg, dwu, dgl, status;
+        TRY(dg.alloc(ctx, 2 * n, false));
+        TRY(dwu.alloc(ctx, 4, false));
+        TRY(dgl.alloc(ctx, 2 * n, false));
+        TRY(status.alloc(ctx, 1, true));
+        hipStream_t s = ctx->stream.get();
+        TRY(gfft_ops(curve)->points_generate(ctx, key, /* stream */ 0, 0, (affine_t*)dg.p, n, (uint32_t*)status.p, s));
+        TRY(gfft_ops(curve)->points_generate(ctx, key, /* stream */ 1, 0, (affine_t*)dwu.p, 2, (uint32_t*)status.p, s));
+        TRY(dehalo_g_to_lagrange_device(ctx, curve, dg.u64(), k, dgl.u64(), s));
+        uint32_t bad[8];
+        TRY(dehalo_download(ctx, status.p, 32, bad));
+        if (bad[0]) return dh_fail(ctx, DEHALO_ERR_INVALID, "params_ipa_generate: an index found no point in 256 attempts");
+        std::vector<uint64_t> g(8 * n), gl(8 * n), wu(16);
+        TRY(dehalo_download(ctx, dg.p, 64 * n, g.data()));
+        TRY(dehalo_download(ctx, dgl.p, 64 * n, gl.data()));
+        TRY(dehalo_download(ctx, dwu.p, 128, wu.data()));
+        return ipa_params_finish(ctx, curve, k, g.data(), gl.data(), wu.data(), wu.data() + 8, out);
     });
 }
 

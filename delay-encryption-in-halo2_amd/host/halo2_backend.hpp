@@ -333,6 +333,13 @@ class ParamsIPAHandle {
         be.check(dehalo_params_ipa_from_g(be.raw(), curve, k, g[0].data(), w.data(), u.data(), &p.p_));
         return p;
     }
+    // ParamsIPA at any k without a file: g, W, U derived on the device by the library's public rule (include/dehalo.h, "Generated points"; key32 = 32 bytes,
+    // null = the default key), g_lagrange by the group FFT.  Not upstream's ParamsIPA::new generators: an upstream verifier reads write()'s bytes
+    static ParamsIPAHandle generate(const Backend& be, dehalo_curve curve, uint32_t k, const uint8_t* key32 = nullptr) {
+        ParamsIPAHandle p(be);
+        be.check(dehalo_params_ipa_generate(be.raw(), curve, k, key32, &p.p_));
+        return p;
+    }
     // ParamsIPA::read: k: u32 LE | g | g_lagrange | w | u, 32-byte compressed points
     static ParamsIPAHandle read(const Backend& be, dehalo_curve curve, const std::vector<uint8_t>& bytes) {
         ParamsIPAHandle p(be);

@@ -214,7 +214,7 @@ class ParamsKZG:
 
 class ParamsIPA(ParamsKZG):
     """dehalo_params over IPACommitmentScheme<C> (Pallas / Vesta): g, g_lagrange, w, u handed over as the caller's ParamsIPA holds them
-    (dehalo_params_ipa_create), built from g, w, u alone (from_g) or read from ParamsIPA::write's bytes (read).  ProvingKey.keygen and Prover take it as they take ParamsKZG: Prover(params, pk).create_proof then writes a ProverIPA
+    (dehalo_params_ipa_create), built from g, w, u alone (from_g), read from ParamsIPA::write's bytes (read) or derived with nothing handed over (generate).  ProvingKey.keygen and Prover take it as they take ParamsKZG: Prover(params, pk).create_proof then writes a ProverIPA
     proof (blinded commitments, committed instance columns, the multiopen and the opening argument).  `open` opens one polynomial."""
 
     @classmethod
@@ -239,6 +239,17 @@ class ParamsIPA(ParamsKZG):
             raise ValueError("g must hold 2^k points")
         h = C.c_void_p()
         _check(ctx, load_library().dehalo_params_ipa_from_g(ctx.handle, curve.id, k, g.ctypes.data, w.ctypes.data, u.ctypes.data, C.byref(h)))
+        return cls(ctx, curve, h)
+
+    @classmethod
+    def generate(cls, ctx: Context, curve: CurveSpec, k: int, key: Optional[bytes] = None) -> "ParamsIPA":
+        """ParamsIPA at any k without a file: g, W, U derived on the device by the library's public rule (include/dehalo.h, "Generated points": ChaCha20 under
+        `key`, 32 bytes, None = the default key; try-and-increment onto the curve), g_lagrange by the group FFT (dehalo_params_ipa_generate).  Not upstream's
+        generators: an upstream verifier takes them from write()'s bytes through ParamsIPA::read."""
+        if key is not None and len(key) != 32:
+            raise ValueError("key must be 32 bytes")
+        h = C.c_void_p()
+        _check(ctx, load_library().dehalo_params_ipa_generate(ctx.handle, curve.id, k, _bytes_ptr(bytes(key)) if key is not None else None, C.byref(h)))
         return cls(ctx, curve, h)
 
     @classmethod

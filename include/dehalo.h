@@ -236,6 +236,34 @@ int dehalo_points_compress_device(dehalo_ctx* ctx, int curve, const uint64_t* d_
 int dehalo_points_decompress_device(dehalo_ctx* ctx, int curve, const uint8_t* d_in32, size_t count, uint64_t* d_affine_xy, uint32_t* status_out, void* stream);
 int dehalo_points_check_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t count, uint32_t* status_out, void* stream);
 
+/* Generated points: curve points with no known relation between them, derived by a public rule -- what a caller without a ParamsIPA file builds its
+ * generators from (dehalo_params_ipa_generate).  They are NOT upstream's ParamsIPA::new generators (hash-to-curve: see dehalo_params_ipa_create).
+ * THE RULE.  A point is named by (curve, key, stream, index), index < 2^48.
+ *   Block       For attempt = 0, 1, ... the ChaCha20 block (RFC 8439 block function) over the state
+ *                   sigma | key | w12 = index mod 2^32 | w13 = (index >> 32 & 0xffff) | attempt << 16 | w14 | w15 = stream, low word first
+ *               -- the indexed schedule of the prover's device draws (dehalo_rng_kind, INDEXED).
+ *   Candidate   The block's first 32 bytes, read as a GroupEncoding: x = the little-endian integer of the low 255 bits, s = bit 255.
+ *   Acceptance  The candidate is accepted iff 0 < x < p (p the curve's base-field modulus) and x^3 + b is a non-zero square; the point is (x, y) with y the root
+ *               whose canonical value has parity s.  That is: the first candidate that dehalo_points_decompress_device's rules decode to a point other than
+ *               the identity.  The result is uniform over the curve's affine points with x != 0.
+ *   Attempt cap Attempts stop at DEHALO_GENERATORS_MAX_ATTEMPTS = 256.  The cap is not part of the mathematics: it bounds the kernel's loop, so that a defect in
+ *               the acceptance test cannot spin a wave.  For Pasta (3/4)^256 is about 1e-32.  An index that exhausts the cap is written as (0, 0) and the
+ *               call fails with DEHALO_ERR_INVALID and a message.
+ *   Key         32 bytes from the caller; NULL selects DEHALO_GENERATORS_DEFAULT_KEY, the 30 ASCII bytes "dehalo ParamsIPA generators v1" followed by two
+ *               zero bytes.
+ *   ParamsIPA   g[i] = (stream 0, index i); W = (stream 1, index 0); U = (stream 1, index 1).  So g at k is a prefix of g at k' > k, and W, U do not depend
+ *               on k, as upstream's do not.
+ * What is claimed: nobody knows a relation between the points, provided ChaCha20 under a public key behaves as a random function of (stream, index, attempt) --
+ * the usual nothing-up-my-sleeve argument.  Every input is public, so nothing here runs in constant time.
+ * dehalo_points_generate_device: d_affine_xy[i] = the point (curve, key, chacha_stream, first_index + i), i < count: affine {x, y} (64 B, standard Montgomery,
+ * canonical words, 16-byte aligned: the point codec's layout), device memory.  All three curves.  Asynchronous on the stream except for the download of a status
+ * word; no workspace beyond that word.  count = 0 returns 0 without a launch.  DEHALO_ERR_INVALID: a null context or output, an unknown curve, count >= 2^29,
+ * first_index + count > 2^48. */
+#define DEHALO_GENERATORS_DEFAULT_KEY "dehalo ParamsIPA generators v1\0"
+#define DEHALO_GENERATORS_MAX_ATTEMPTS 256
+int dehalo_points_generate_device(dehalo_ctx* ctx, int curve, const uint8_t* key32, uint64_t chacha_stream, uint64_t first_index, uint64_t* d_affine_xy, size_t count,
+                                  void* stream);
+
 /* The scalar codec, the point codec's twin: vectors of field elements between their in-memory form (4 x u64 Montgomery limbs, 16-byte aligned) and the two forms
  * they take in a key on disk [UPSTREAM halo2curves 0.3.x PrimeField::from_repr, SerdeObject::from_raw_bytes; restated from memory: INTEGRATION.md section 7].
  * Streaming maps, one lane per element, device memory in and out, every field id (an unknown field is DEHALO_ERR_INVALID); count < 2^29, and count = 0 returns 0
@@ -552,13 +580,20 @@ int dehalo_params_setup(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t s
  * dehalo_params_commit_device is the bare MSM under either scheme.  g, u and w also stay on the device as plain points for the opening argument.
  * Not provided: ParamsIPA::new.  Its generators are hash-to-curve outputs ("Halo2-Parameters"), and the simplified SWU map of the Pasta curves needs the
  * constants of their 3-isogenies, which this library has no checked source for and will not restate from memory: the caller passes params.g, params.w and
- * params.u (dehalo_params_ipa_from_g) or a written ParamsIPA (dehalo_params_ipa_read).
+ * params.u (dehalo_params_ipa_from_g) or a written ParamsIPA (dehalo_params_ipa_read), or asks for generators of the library's own public rule
+ * (dehalo_params_ipa_generate).
  * Whole proofs: dehalo_prover_create / dehalo_create_proof with these params write a ProverIPA proof (below). */
 int dehalo_params_ipa_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
                              dehalo_params** out);
 /* ParamsIPA from g alone, as upstream builds it: g_lagrange = g_to_lagrange(g) on the device (dehalo_g_to_lagrange_device), then exactly
  * dehalo_params_ipa_create(g, g_lagrange, w, u).  Host pointers; the same range checks and return codes as dehalo_params_ipa_create. */
 int dehalo_params_ipa_from_g(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t w[8], const uint64_t u[8], dehalo_params** out);
+/* ParamsIPA at any k without a file: g, W and U are generated points ("Generated points" above: g[i] = (stream 0, index i), W = (stream 1, index 0),
+ * U = (stream 1, index 1) under key32, NULL = DEHALO_GENERATORS_DEFAULT_KEY), made on the device; g_lagrange = dehalo_g_to_lagrange_device on the points where
+ * they lie; then as dehalo_params_ipa_from_g, W's fixed-base table included.  The same range checks and return codes as dehalo_params_ipa_create.  The result is
+ * an ordinary ParamsIPA: write, downsize, keygen and the provers take it as any other.  These are not upstream's generators: a proof made under generated
+ * params verifies against the same params only, which an upstream verifier gets from dehalo_params_ipa_write's bytes through ParamsIPA::read. */
+int dehalo_params_ipa_generate(dehalo_ctx* ctx, int curve, uint32_t k, const uint8_t* key32, dehalo_params** out);
 /* ParamsIPA::{write, read} [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs]: k: u32 LE | g (2^k x 32 B) | g_lagrange (2^k x 32 B) | w (32 B) | u (32 B), every
  * point GroupEncoding::to_bytes -- x little-endian, bit 255 = y & 1, the identity all zeros: the encoding dehalo_transcript_write_point appends to a proof.
  * size = 4 + 64 x 2^k + 64; for ParamsKZG size is 0 and write DEHALO_ERR_UNSUPPORTED.  These are entry points of their own, beside dehalo_params_size /
