@@ -16,7 +16,7 @@ ifdef EXPERIMENTS
 HIPFLAGS += -DDEHALO_EXPERIMENTS
 endif
 LIB ?= $(PKG)/libdehalo.so
-UNITS := capi params keygen prover check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
+UNITS := capi params keygen prover verify check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
 OBJS := $(UNITS:%=$(OBJDIR)/%.o)
 HDRS := $(wildcard $(CSRC)/*.cuh) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hpp) include/dehalo.h
 
@@ -80,4 +80,12 @@ params_format_check: tests/native_host/params_format_check.cpp $(CSRC)/params_fo
 key_format_check: tests/native_host/key_format_check.cpp $(CSRC)/key_format.hpp include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/key_format_check tests/native_host/key_format_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check
+# the BN254 pairing check (csrc/pairing_host.hpp: host only) under ASan + UBSan (tests/test_pairing_host.py compares its verdicts with the oracle's and the library's)
+pairing_check: tests/native_host/pairing_check.cpp $(CSRC)/pairing_host.hpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/pairing_check tests/native_host/pairing_check.cpp
+
+# verify_proof on the host (csrc/verify_host.hpp: host only) on proofs the test writes to a file, under ASan + UBSan (tests/test_verify_host.py)
+verify_host_check: tests/native_host/verify_host_check.cpp $(CSRC)/verify_host.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
+	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/verify_host_check tests/native_host/verify_host_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check

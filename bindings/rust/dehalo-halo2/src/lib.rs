@@ -9,10 +9,13 @@
 //! * one call: replace the body of `plonk::create_proof` for `KZGCommitmentScheme<Bn256>` / `ProverGWC` / `Blake2bWrite` by [`prover::create_proof`]
 //!   (benches/delay_enc.rs:123-131), keys and SRS read from the same RawBytes files the bench caches (`:45,54,88,94-98,105,111-115`).
 //!   A front-end that proves with `ProverSHPLONK` takes [`prover::create_proof_shplonk`] (`DehaloProver::set_multiopen`).
+//! * the check the benches end with (`:147-165`): [`verifier::verify_proof`] / [`verifier::verify_proof_shplonk`] on a [`verifier::DehaloVerifier`], which needs
+//!   the verifying key and three points of the params only, and with `ctx = None` no device.
 pub mod arithmetic;
 pub mod constraint_system;
 pub mod params;
 pub mod prover;
+pub mod verifier;
 
 use dehalo_sys as sys;
 use std::ffi::CStr;

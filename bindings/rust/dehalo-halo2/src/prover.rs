@@ -82,6 +82,10 @@ impl<'c> DehaloProvingKey<'c> {
         Ok(out)
     }
 
+    pub fn as_ptr(&self) -> *const sys::dehalo_pk {
+        self.raw
+    }
+
     /// upstream derives `vk.transcript_repr` from Rust `Debug` text, so it is passed in: with upstream's value set, the first absorbed scalar is upstream's
     pub fn set_transcript_repr(&mut self, repr: &Fr) -> Result<(), DehaloError> {
         self.ctx.check(unsafe { sys::dehalo_pk_set_transcript_repr(self.raw, repr as *const Fr as *const u64) })

@@ -41,6 +41,9 @@ SYMBOLS = [
     "dehalo_scalars_from_repr_device", "dehalo_scalars_check_device",
     "dehalo_vk_size_custom", "dehalo_vk_write_custom", "dehalo_pk_size_custom", "dehalo_pk_write_custom", "dehalo_pk_read_custom", "dehalo_keygen_pk",
     "dehalo_points_generate_device", "dehalo_params_ipa_generate",
+    "dehalo_transcript_create_read", "dehalo_transcript_read_point", "dehalo_transcript_read_scalar", "dehalo_transcript_remaining", "dehalo_pairing_check",
+    "dehalo_verifier_create", "dehalo_verifier_create_vk", "dehalo_verifier_set_transcript_repr", "dehalo_verifier_set_multiopen", "dehalo_verifier_release",
+    "dehalo_verifier_create_error", "dehalo_verifier_last_error","dehalo_verifier_last_timings", "dehalo_verify_proof", "dehalo_verify_proofs",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -313,6 +316,24 @@ def load_library():
     lib.dehalo_transcript_finalize.argtypes = [P, P, sz]
     lib.dehalo_transcript_release.argtypes = [P]
     lib.dehalo_transcript_release.restype = None
+    lib.dehalo_transcript_create_read.argtypes = [C.c_int, P, sz, PP]
+    lib.dehalo_transcript_read_point.argtypes = [P, u64p]
+    lib.dehalo_transcript_read_scalar.argtypes = [P, u64p]
+    lib.dehalo_transcript_remaining.argtypes = [P]
+    lib.dehalo_transcript_remaining.restype = sz
+    lib.dehalo_pairing_check.argtypes = [C.c_int, u64p, P, sz, C.POINTER(C.c_int)]
+    lib.dehalo_verifier_create.argtypes = [P, P, P, PP]
+    lib.dehalo_verifier_create_vk.argtypes = [P, C.c_int, u32, u64p, P, P, C.POINTER(CConstraintSystem), P, sz, C.c_int, u32, PP]
+    lib.dehalo_verifier_set_transcript_repr.argtypes = [P, u64p]
+    lib.dehalo_verifier_set_multiopen.argtypes = [P, C.c_int]
+    lib.dehalo_verifier_release.argtypes = [P]
+    lib.dehalo_verifier_last_error.argtypes = [P]
+    lib.dehalo_verifier_last_error.restype = C.c_char_p
+    lib.dehalo_verifier_create_error.argtypes = [C.c_char_p, sz]
+    lib.dehalo_verifier_last_timings.argtypes = [P, C.POINTER(C.c_double)]
+    lib.dehalo_verify_proof.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, P, sz, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.dehalo_verify_proofs.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int64)]
     lib.dehalo_prover_create.argtypes = [P, P, P, P, PP]
     lib.dehalo_prover_create_multi.argtypes = [P, P, P, P, u32, PP]
     lib.dehalo_create_proof_multi.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), P, u32]

@@ -128,6 +128,32 @@ struct HostField {
         }
         return true;
     }
+    // r = a square root of a (Tonelli-Shanks over the 2^S-th root of unity, every odd p: the twin of gfft.cuh's f_sqrt_ts); false when a is not a square.
+    // a canonical (below p).  Which of the two roots comes out is the caller's to choose.
+    bool sqrt(const Fe& a, Fe& r) const {
+        if (a.is_zero()) { r = a; return true; }
+        uint64_t t[4] = {p[0] - 1, p[1], p[2], p[3]};      // (p - 1) >> S, then ((p - 1) >> S - 1) / 2
+        for (uint32_t s = 0; s < two_adicity + 1; s++) {
+            for (int i = 0; i < 3; i++) t[i] = (t[i] >> 1) | (t[i + 1] << 63);
+            t[3] >>= 1;
+        }
+        const Fe w = pow(a, t);
+        Fe x = mul(a, w), b = mul(x, w), z = root_of_unity;      // x^2 = a b, b = a^((p - 1) >> S) of order dividing 2^(S - 1) when a is a square
+        uint32_t v = two_adicity;
+        while (b != one) {
+            uint32_t m = 0;
+            Fe c = b;
+            while (c != one && m < v) { c = sqr(c); m++; }
+            if (m >= v) return false;
+            for (uint32_t i = 0; i + m + 1 < v; i++) z = sqr(z);
+            x = mul(x, z);
+            z = sqr(z);
+            b = mul(b, z);
+            v = m;
+        }
+        r = x;
+        return sqr(r) == a;
+    }
     // 64 little-endian bytes taken as an integer, reduced mod p (FromUniformBytes<64>::from_uniform_bytes, Challenge255)
     Fe from_u512(const uint8_t b[64]) const {
         Fe lo, hi;

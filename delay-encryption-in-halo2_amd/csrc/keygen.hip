@@ -85,19 +85,7 @@ size_t dehalo_pk::size() const {
     KeyLayout L;
     return key_layout(DEHALO_SERDE_RAW_BYTES, k, key_shape(this), L) ? L.pk_size : 0;
 }
-void dehalo_pk::default_transcript_repr() {
-    std::vector<uint8_t> body(vk_size());
-    vk_write(body.data());
-    cs.encode(body);
-    Blake2b h;
-    h.init(64, "Halo2-Verify-Key");
-    const uint64_t len = body.size();
-    h.update(&len, 8);
-    h.update(body.data(), body.size());
-    uint8_t d[64];
-    h.digest(d);
-    transcript_repr = f->from_u512(d);
-}
+void dehalo_pk::default_transcript_repr() { transcript_repr = substitute_transcript_repr(f, k, cs, fixed_commitments, perm_commitments, selectors); }      // (plonk_host.hpp)
 int dehalo_pk::compile_graphs() {
     TRY(custom_gates_graph(cs, f).compile(ctx, adopt(ctx, custom_gates)));
     for (auto& lk : cs.lookups) {

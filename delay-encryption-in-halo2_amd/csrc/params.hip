@@ -5,6 +5,7 @@
 // C entry points run under dh_guard and the column work goes through the library's device entry points, as in prover.hip; the one kernel here is the ChaCha20 draw.
 #include <memory>
 
+#include "pairing_host.hpp"
 #include "params_format.hpp"
 #include "whole_call.hpp"
 
@@ -174,7 +175,7 @@ extern "C" int dehalo_transcript_common_scalar(dehalo_transcript* t, const uint6
 }
 extern "C" int dehalo_transcript_write_scalar(dehalo_transcript* t, const uint64_t s[4]) {
     return dh_guard(nullptr, [&]() -> int {
-        if (!t || !s) return DEHALO_ERR_INVALID;
+        if (!t || !s || t->reader) return DEHALO_ERR_INVALID;
         Fe v;
         memcpy(v.v, s, 32);
         t->write_scalar(v);
@@ -183,7 +184,7 @@ extern "C" int dehalo_transcript_write_scalar(dehalo_transcript* t, const uint64
 }
 extern "C" int dehalo_transcript_write_point(dehalo_transcript* t, const uint64_t xy[8]) {
     return dh_guard(nullptr, [&]() -> int {
-        if (!t || !xy) return DEHALO_ERR_INVALID;
+        if (!t || !xy || t->reader) return DEHALO_ERR_INVALID;
         return t->write_point(xy) ? 0 : DEHALO_ERR_INVALID;
     });
 }
@@ -205,6 +206,46 @@ extern "C" int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* o
     });
 }
 extern "C" void dehalo_transcript_release(dehalo_transcript* t) { delete t; }
+
+// ---- Blake2bRead: the same object over a proof's bytes (copied: the caller's buffer is not retained)
+extern "C" int dehalo_transcript_create_read(int curve, const uint8_t* proof, size_t len, dehalo_transcript** out) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!out || (!proof && len) || curve_scalar_field(curve) < 0) return DEHALO_ERR_INVALID;
+        std::unique_ptr<dehalo_transcript> t(new dehalo_transcript);
+        t->init_read(curve, proof, len);
+        *out = t.release();
+        return 0;
+    });
+}
+extern "C" int dehalo_transcript_read_point(dehalo_transcript* t, uint64_t affine_xy[8]) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || !affine_xy || !t->reader) return DEHALO_ERR_INVALID;
+        uint64_t xy[8];
+        if (!t->read_point(xy)) return DEHALO_ERR_INVALID;
+        memcpy(affine_xy, xy, 64);
+        return 0;
+    });
+}
+extern "C" int dehalo_transcript_read_scalar(dehalo_transcript* t, uint64_t s[4]) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (!t || !s || !t->reader) return DEHALO_ERR_INVALID;
+        Fe v;
+        if (!t->read_scalar(v)) return DEHALO_ERR_INVALID;
+        memcpy(s, v.v, 32);
+        return 0;
+    });
+}
+extern "C" size_t dehalo_transcript_remaining(const dehalo_transcript* t) { return t && t->reader ? t->remaining() : 0; }
+
+// ================================================================================================ the pairing check (pairing_host.hpp; host only)
+extern "C" int dehalo_pairing_check(int curve, const uint64_t* g1_affine_xy, const uint8_t* g2_raw, size_t count, int* is_one) {
+    return dh_guard(nullptr, [&]() -> int {
+        if (curve_scalar_field(curve) < 0 || !is_one || (count && (!g1_affine_xy || !g2_raw))) return DEHALO_ERR_INVALID;
+        const PairingHost* ph = pairing_host(curve);
+        if (!ph) return DEHALO_ERR_UNSUPPORTED;      // Pallas and Vesta have no pairing
+        return ph->check(g1_affine_xy, g2_raw, count, is_one);
+    });
+}
 
 // ================================================================================================ ParamsIPA and the IPA opening argument
 namespace {

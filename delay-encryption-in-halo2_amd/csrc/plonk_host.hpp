@@ -8,7 +8,9 @@
 #include <vector>
 
 #include "../../include/dehalo.h"
+#include "blake2b.hpp"
 #include "hostfield.hpp"
+#include "key_format.hpp"
 
 struct HostCS {
     uint32_t num_advice = 0, num_fixed = 0, num_instance = 0, minimum_degree = 0;
@@ -425,3 +427,26 @@ struct HostDomain {
         return f->mul(x, f->pow_u64(rot >= 0 ? omega : omega_inv, (uint64_t)(rot >= 0 ? rot : -rot)));
     }
 };
+
+// ---- the substitute for vk.transcript_repr (upstream's comes from Rust Debug text): Blake2b-512("Halo2-Verify-Key") over the length and the RawBytes verifying
+// key -- k, num_fixed, the fixed and permutation commitments (Montgomery affine, 8 u64 each), the packed selectors -- followed by the circuit's encoding, reduced
+// as a transcript challenge is.  The one statement of it: keygen (dehalo_pk::default_transcript_repr) and a verifier made from vk bytes both call this.
+inline Fe substitute_transcript_repr(const HostField* f, uint32_t k, const HostCS& cs, const std::vector<uint64_t>& fixed_commitments,
+                                     const std::vector<uint64_t>& perm_commitments, const std::vector<std::vector<uint8_t>>& selectors) {
+    std::vector<uint8_t> body(8);
+    key_put_u32_be(body.data(), k);
+    key_put_u32_be(body.data() + 4, cs.num_fixed);
+    const uint8_t *fc = (const uint8_t*)fixed_commitments.data(), *pc = (const uint8_t*)perm_commitments.data();
+    body.insert(body.end(), fc, fc + 64 * (size_t)cs.num_fixed);
+    body.insert(body.end(), pc, pc + 64 * cs.perm_cols.size());
+    for (auto& s : selectors) body.insert(body.end(), s.begin(), s.end());
+    cs.encode(body);
+    Blake2b h;
+    h.init(64, "Halo2-Verify-Key");
+    const uint64_t len = body.size();
+    h.update(&len, 8);
+    h.update(body.data(), body.size());
+    uint8_t d[64];
+    h.digest(d);
+    return f->from_u512(d);
+}

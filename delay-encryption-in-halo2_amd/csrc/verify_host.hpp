@@ -1,0 +1,563 @@
+// verify_host.hpp -- verify_proof for KZG on the host [UPSTREAM halo2_proofs @ v2023_04_20: plonk/verifier.rs, plonk/{permutation,lookup,vanishing}/verifier.rs,
+// poly/kzg/multiopen/{gwc,shplonk}/verifier.rs, poly/kzg/strategy.rs (SingleStrategy, AccumulatorStrategy); shuffles: halo2_proofs v0.3.0], written from the
+// published protocol.  A proof is read through the Blake2bRead transcript, the challenges squeezed in the prover's order, the gate, permutation, lookup and shuffle
+// expressions evaluated at the read evaluations into expected_h, and either multiopen reduced to TWO term lists  L = sum a_j P_j,  R = sum b_j P_j  over the
+// proof's points, the key's commitments and g[0], with  accept  iff  e(L, s_g2) e(-R, g2) = 1:
+//   GWC      L = sum_i u^i W_i;  R = sum_i u^i z_i W_i + sum_i u^i sum_j v^j C_ij - (sum_i u^i sum_j v^j e_ij) g[0]
+//   SHPLONK  L = h';  R = sum_i c_i sum_j y^j P_ij - (sum_i c_i sum_j y^j r_ij) g[0] - Z_0(u) h + u h',  c_i = v^i zdiff_i / zdiff_0
+// (the folded quotient commitment is never computed as a point: its scalar goes to the pieces, times x^(n i)).  A batch multiplies proof i's lists by a weight
+// w_i and checks the concatenation with one pairing check.  The order of the evaluations, the queries, their groups and intermediate sets are the EXISTING
+// OpeningPlan's (opening_plan.hpp): prover and verifier cannot disagree about layout.
+// The points of a proof stand at offsets its shape fixes; they are decompressed before the walk by a backend -- the host's below, or the device's (verify.hip:
+// one dehalo_points_decompress_device launch for all proofs of a call) -- and the two sums go through the backend's MSM.  The pairing is pairing_host.hpp's.
+// Host only, no HIP header: verify.hip includes it, and tests/native_host/verify_host_check.cpp drives it on the CPU under ASan + UBSan.
+#pragma once
+#include <chrono>
+#include <string>
+#include <vector>
+
+#include "../../include/dehalo.h"
+#include "hostfield.hpp"
+#include "key_format.hpp"
+#include "opening_plan.hpp"
+#include "pairing_host.hpp"
+#include "plonk_host.hpp"
+#include "transcript_host.hpp"
+
+// ---- G1 on the host: y^2 = x^3 + b, Jacobian accumulator, affine addends ((0, 0) = the identity)
+struct G1Host {
+    const HostField* q;
+    Fe b;
+    struct Jac { Fe x, y, z; };
+    G1Host(const HostField* fq, uint64_t curve_b) : q(fq), b(fq->from_u64(curve_b)) {}
+    Jac identity() const { return Jac{q->one, q->one, Fe{}}; }
+    Jac dbl(const Jac& P) const {
+        if (P.z.is_zero() || P.y.is_zero()) return identity();
+        const Fe A = q->sqr(P.x), B = q->sqr(P.y), C = q->sqr(B);
+        Fe D = q->sub(q->sub(q->sqr(q->add(P.x, B)), A), C);
+        D = q->add(D, D);
+        const Fe E = q->add(q->add(A, A), A), F = q->sqr(E);
+        Jac R;
+        R.x = q->sub(F, q->add(D, D));
+        Fe C8 = q->add(C, C);
+        C8 = q->add(C8, C8);
+        C8 = q->add(C8, C8);
+        R.y = q->sub(q->mul(E, q->sub(D, R.x)), C8);
+        R.z = q->mul(q->add(P.y, P.y), P.z);
+        return R;
+    }
+    Jac add_affine(const Jac& P, const Fe& x2, const Fe& y2) const {
+        if (x2.is_zero() && y2.is_zero()) return P;
+        if (P.z.is_zero()) return Jac{x2, y2, q->one};
+        const Fe zz = q->sqr(P.z), u2 = q->mul(x2, zz), s2 = q->mul(q->mul(y2, P.z), zz);
+        if (u2 == P.x) return s2 == P.y ? dbl(P) : identity();
+        const Fe h = q->sub(u2, P.x), hh = q->sqr(h), hhh = q->mul(h, hh), r = q->sub(s2, P.y), v = q->mul(P.x, hh);
+        Jac R;
+        R.x = q->sub(q->sub(q->sqr(r), hhh), q->add(v, v));
+        R.y = q->sub(q->mul(r, q->sub(v, R.x)), q->mul(P.y, hhh));
+        R.z = q->mul(P.z, h);
+        return R;
+    }
+    void to_affine(const Jac& P, uint64_t xy[8]) const {
+        memset(xy, 0, 64);
+        if (P.z.is_zero()) return;
+        const Fe zi = q->invert(P.z), zi2 = q->sqr(zi), x = q->mul(P.x, zi2), y = q->mul(P.y, q->mul(zi2, zi));
+        memcpy(xy, x.v, 32);
+        memcpy(xy + 4, y.v, 32);
+    }
+    // sum_i [s_i] P_i, s canonical integers: one accumulator, 256 doublings, one mixed addition per set bit (a verifier's sums have about 10^2 terms)
+    void msm(const Fe* canonical_scalars, const uint64_t* xy, size_t len, uint64_t out_affine[8]) const {
+        Jac acc = identity();
+        for (int bit = 255; bit >= 0; bit--) {
+            acc = dbl(acc);
+            for (size_t i = 0; i < len; i++)
+                if ((canonical_scalars[i].v[bit >> 6] >> (bit & 63)) & 1) {
+                    Fe x, y;
+                    memcpy(x.v, xy + 8 * i, 32);
+                    memcpy(y.v, xy + 8 * i + 4, 32);
+                    acc = add_affine(acc, x, y);
+                }
+        }
+        to_affine(acc, out_affine);
+    }
+    bool on_curve(const Fe& x, const Fe& y) const { return q->sqr(y) == q->add(q->mul(q->sqr(x), x), b); }
+    // GroupEncoding::from_bytes with the device codec's verdicts (dehalo_points_decompress_device): 0, or POINT_NOT_BELOW_P / POINT_NOT_ON_CURVE /
+    // POINT_ZERO_X_SIGNED; a refused point and the all-zero identity are written as (0, 0)
+    uint32_t decompress(const uint8_t in[32], uint64_t xy[8]) const { return g1_decompress_host(q, b, in, xy); }      // (transcript_host.hpp: the one host decoder)
+};
+
+// ---- what decompresses a call's points and sums its two term lists: the host (below) or the device (verify.hip).  A non-zero return is an error of the
+// backend (a device error stays an error: nothing falls back to the host)
+struct VerifyBackend {
+    virtual ~VerifyBackend() {}
+    // count x 32 B -> count x {x, y}; a point that is refused is written as (0, 0) (so is the identity's all-zero encoding, which no proof may hold)
+    virtual int decompress(const uint8_t* in32, size_t count, uint64_t* xy) = 0;
+    // sum_i [scalars_i] xy_i -> one affine point ((0, 0): the identity); scalars Montgomery, canonical words
+    virtual int msm(const Fe* scalars, const uint64_t* xy, size_t len, uint64_t out_affine[8]) = 0;
+};
+struct HostVerifyBackend : VerifyBackend {
+    const HostField* fr;
+    G1Host g1;
+    HostVerifyBackend(const HostField* fq, const HostField* fr_, uint64_t curve_b) : fr(fr_), g1(fq, curve_b) {}
+    int decompress(const uint8_t* in32, size_t count, uint64_t* xy) override {
+        for (size_t i = 0; i < count; i++) g1.decompress(in32 + 32 * i, xy + 8 * i);
+        return 0;
+    }
+    int msm(const Fe* scalars, const uint64_t* xy, size_t len, uint64_t out_affine[8]) override {
+        std::vector<Fe> c(len);
+        for (size_t i = 0; i < len; i++) c[i] = fr->to_canonical(scalars[i]);
+        g1.msm(c.data(), xy, len, out_affine);
+        return 0;
+    }
+};
+
+// where a call's time went, in milliseconds (dehalo_verifier_last_timings)
+struct VerifyStats { double decompress = 0, walk = 0, msm = 0, pairing = 0; };
+
+// ---- the verifying half of a key, and of the params: all a verifier keeps
+struct VerifierKey {
+    int curve = 0;
+    const HostField *f = nullptr, *fq = nullptr;
+    HostCS cs;
+    HostDomain dom;
+    uint32_t k = 0, num_selectors = 0;
+    std::vector<uint64_t> fixed_commitments, perm_commitments;      // Montgomery affine, 8 u64 each
+    std::vector<std::vector<uint8_t>> selectors;                    // packed, as the vk holds them: hashed into the substitute transcript_repr
+    Fe transcript_repr{};
+    uint64_t g0[8] = {};
+    uint8_t g2[128] = {}, s_g2[128] = {};
+    int multiopen = DEHALO_MULTIOPEN_GWC;
+    bool unsupported = false;      // init_cs: the message describes a circuit this library does not take
+
+    KeyShape shape() const {
+        KeyShape sh;
+        sh.nf = cs.num_fixed; sh.npc = cs.perm_cols.size(); sh.nsel = num_selectors; sh.ext_shift = dom.extended_k - dom.k;
+        return sh;
+    }
+    // "" or what is wrong with the circuit / k
+    std::string init_cs(int curve_, const dehalo_constraint_system* csd, uint32_t k_) {
+        curve = curve_; k = k_;
+        f = host_field(curve_scalar_field(curve));
+        fq = host_field(curve_base_field(curve));
+        const std::string err = cs.load(csd);
+        unsupported = cs.unsupported;
+        if (!err.empty()) return err;
+        if (k > 28 || !dom.init(f, cs.degree(), k)) { unsupported = true; return "extended_k exceeds the field's two-adicity"; }
+        if (dom.n < (size_t)cs.blinding_factors() + 3) return "not enough rows available";
+        return "";
+    }
+    // g2 and s_g2: on the twist and in the order-r subgroup
+    std::string check_g2() const {
+        const PairingHost* ph = pairing_host(curve);
+        if (!ph || !ph->ok) return "no pairing on this curve";
+        G2Host::Pt Q;
+        if (ph->load_g2(g2, Q) != PairingHost::G2_OK || Q.inf) return "g2 is not a point of the order-r subgroup of the twist";
+        if (ph->load_g2(s_g2, Q) != PairingHost::G2_OK || Q.inf) return "s_g2 is not a point of the order-r subgroup of the twist";
+        return "";
+    }
+    // vk bytes in any SerdeFormat -> commitments and selectors; "" or what is wrong.  Processed: every commitment decoded (the identity's all-zero encoding is a
+    // commitment to the zero column); RawBytes: every stored word below the modulus and every point on the curve or (0, 0); RawBytesUnchecked: copied.
+    std::string load_vk(const uint8_t* bytes, size_t len, int format, uint32_t nsel) {
+        num_selectors = nsel;
+        KeyLayout L;
+        const KeyHeaderError he = key_parse_header(bytes, len, format, shape(), k, false, L);
+        if (he != KEY_HEADER_OK) return key_header_error_text(he);
+        const G1Host g1(fq, curve == DEHALO_CURVE_BN254_G1 ? 3 : 5);
+        const size_t nf = cs.num_fixed, npc = cs.perm_cols.size();
+        fixed_commitments.assign(8 * nf, 0);
+        perm_commitments.assign(8 * npc, 0);
+        for (size_t i = 0; i < nf + npc; i++) {
+            const uint8_t* src = bytes + (i < nf ? L.off_fixed_c + L.point * i : L.off_perm_c + L.point * (i - nf));
+            uint64_t* dst = i < nf ? &fixed_commitments[8 * i] : &perm_commitments[8 * (i - nf)];
+            if (format == DEHALO_SERDE_PROCESSED) {
+                const uint32_t st = g1.decompress(src, dst);
+                if (st) return key_point_status_text(st, true);
+                continue;
+            }
+            memcpy(dst, src, 64);
+            if (format == DEHALO_SERDE_RAW_BYTES_UNCHECKED) continue;
+            Fe x, y;
+            memcpy(x.v, dst, 32);
+            memcpy(y.v, dst + 4, 32);
+            if (HostField::geq(x.v, fq->p) || HostField::geq(y.v, fq->p)) return key_point_status_text(1, false);
+            if (!(x.is_zero() && y.is_zero()) && !g1.on_curve(x, y)) return key_point_status_text(2, false);
+        }
+        selectors.clear();
+        for (uint32_t s = 0; s < nsel; s++) selectors.emplace_back(bytes + L.off_selectors + L.sel_bytes * s, bytes + L.off_selectors + L.sel_bytes * (s + 1));
+        return "";
+    }
+    // the substitute transcript_repr keygen gives this key (plonk_host.hpp: the one statement of it)
+    void default_transcript_repr() { transcript_repr = substitute_transcript_repr(f, k, cs, fixed_commitments, perm_commitments, selectors); }
+    OpeningShape opening_shape(uint32_t circuits) const {
+        OpeningShape sh;
+        sh.k = k; sh.A = cs.num_advice; sh.num_fixed = cs.num_fixed; sh.I = cs.num_instance; sh.L = (uint32_t)cs.lookups.size(); sh.S = cs.num_sets();
+        sh.npc = (uint32_t)cs.perm_cols.size(); sh.bf = cs.blinding_factors(); sh.pieces = dom.quotient_poly_degree;
+        sh.query_instance = false;
+        sh.circuits = circuits;
+        sh.shuffles = (uint32_t)cs.shuffles.size();
+        for (auto& q : cs.advice_q) sh.advice_q.push_back({q.index, q.rotation});
+        for (auto& q : cs.fixed_q) sh.fixed_q.push_back({q.index, q.rotation});
+        for (auto& q : cs.instance_q) sh.instance_q.push_back({q.index, q.rotation});
+        return sh;
+    }
+};
+
+// ---- the two term lists of a call, every proof's appended under its weight
+struct VerifyTerms {
+    std::vector<Fe> ls, rs;
+    std::vector<uint64_t> lp, rp;      // 8 u64 a point
+    void left(const Fe& s, const uint64_t* p) { ls.push_back(s); lp.insert(lp.end(), p, p + 8); }
+    void right(const Fe& s, const uint64_t* p) { rs.push_back(s); rp.insert(rp.end(), p, p + 8); }
+};
+
+// the points of one proof: [every commitment before the evaluations | the multiopen's], in the order of the bytes
+inline size_t verify_points_before_evals(const OpeningPlan& pl) { return (size_t)pl.NC + pl.p_instance - pl.p_hpiece; }
+inline size_t verify_multiopen_points(const OpeningPlan& pl, int multiopen) { return multiopen == DEHALO_MULTIOPEN_SHPLONK ? 2 : pl.groups.size(); }
+
+// One proof whose length is the shape's and whose points are decoded (none refused): the transcript walk, expected_h and the reduction of the multiopen, appended
+// to `out` under `weight`.  false: a scalar is not below r (the proof is MALFORMED); nothing of `out` is then meaningful.
+// instances: [circuit][column] -> values (Montgomery, canonical).
+inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N, const uint8_t* proof, size_t len, const uint64_t* pts,
+                        const std::vector<std::vector<std::vector<Fe>>>& instances, const Fe& weight, VerifyTerms& out) {
+    const HostField* f = vk.f;
+    const HostCS& cs = vk.cs;
+    const HostDomain& d = vk.dom;
+    const Fe zero{}, one = f->one;
+    const uint32_t A = pl.A, L = pl.L, S = pl.S, H = pl.H, bf = cs.blinding_factors(), pieces = d.quotient_poly_degree;
+    const int32_t last = -(int32_t)(bf + 1);
+    dehalo_transcript t;
+    t.init_read(vk.curve, proof, len);
+    size_t next_pt = 0;
+    auto point = [&]() -> const uint64_t* {      // the next 32 bytes are a point, decoded already: absorbed as the reader would absorb it
+        const uint64_t* p = pts + 8 * next_pt++;
+        t.write_point(p, false);
+        t.pos += 32;
+        return p;
+    };
+    std::vector<const uint64_t*> cm(pl.num_polys, nullptr);      // polynomial id -> its commitment
+    t.common_scalar(vk.transcript_repr);
+    for (auto& circuit : instances)
+        for (auto& column : circuit)
+            for (const Fe& v : column) t.common_scalar(v);
+    std::vector<Fe> challenges(cs.challenge_phase.size(), zero);
+    for (uint32_t ph = 0; ph < cs.num_phases; ph++) {
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t col = 0; col < A; col++)
+                if (cs.advice_phase[col] == ph) cm[pl.adv(c) + col] = point();
+        for (size_t j = 0; j < challenges.size(); j++)
+            if (cs.challenge_phase[j] == ph) challenges[j] = t.squeeze();
+    }
+    const Fe theta = t.squeeze();
+    for (uint32_t c = 0; c < N; c++)
+        for (uint32_t l = 0; l < L; l++) {
+            cm[pl.perm(c) + 2 * l] = point();
+            cm[pl.perm(c) + 2 * l + 1] = point();
+        }
+    const Fe beta = t.squeeze(), gamma = t.squeeze();
+    for (uint32_t off : pl.product_order) cm[pl.o_pz + off] = point();      // every circuit's permutation, lookup, shuffle products; the random polynomial
+    const Fe y = t.squeeze();
+    for (uint32_t i = 0; i < pieces; i++) cm[pl.p_hpiece + i] = point();
+    const Fe x = t.squeeze();
+    for (uint32_t i = 0; i < cs.num_fixed; i++) cm[pl.p_fixed + i] = &vk.fixed_commitments[8 * i];
+    for (size_t j = 0; j < cs.perm_cols.size(); j++) cm[pl.p_sigma + j] = &vk.perm_commitments[8 * j];
+    std::vector<Fe> E(pl.eval_count, zero);
+    for (int64_t slot : pl.write)
+        if (!t.read_scalar(E[(size_t)slot])) return false;
+
+    // ---- expected_h
+    Fe xn = x;
+    for (uint32_t i = 0; i < d.k; i++) xn = f->sqr(xn);
+    const Fe xn1 = f->sub(xn, one), n_fe = f->from_u64((uint64_t)d.n);
+    auto l_i = [&](int64_t i) {      // l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
+        const int64_t m = ((i % (int64_t)d.n) + (int64_t)d.n) % (int64_t)d.n;
+        const Fe wi = f->pow_u64(d.omega, (uint64_t)m);
+        return f->mul(f->mul(wi, xn1), f->invert(f->mul(n_fe, f->sub(x, wi))));
+    };
+    std::vector<Fe> l_evals;      // l_0, l_{-1}, ..., l_{-(bf + 1)}
+    for (uint32_t i = 0; i < bf + 2; i++) l_evals.push_back(l_i(-(int64_t)i));
+    const Fe l_0 = l_evals[0], l_last = l_evals[bf + 1];
+    Fe l_blind = zero;
+    for (uint32_t i = 1; i <= bf; i++) l_blind = f->add(l_blind, l_evals[i]);
+    const Fe active = f->sub(one, f->add(l_last, l_blind));
+    auto ev = [&](uint32_t poly, int32_t rot) -> const Fe& { return E[(size_t)pl.slot(poly, rot)]; };
+    Fe expected_h = zero;
+    for (uint32_t c = 0; c < N; c++) {
+        auto instance_eval = [&](uint32_t col, int32_t rot) {      // QUERY_INSTANCE = false: interpolated from the values
+            Fe acc = zero;
+            const std::vector<Fe>& vals = instances[c][col];
+            for (size_t j = 0; j < vals.size(); j++)
+                if (!vals[j].is_zero()) acc = f->add(acc, f->mul(vals[j], l_i((int64_t)j - rot)));
+            return acc;
+        };
+        std::vector<Fe> val(cs.nodes.size());      // children precede their parents
+        for (size_t i = 0; i < cs.nodes.size(); i++) {
+            const dehalo_expr_node& e = cs.nodes[i];
+            switch (e.kind) {
+                case DEHALO_EXPR_CONSTANT: val[i] = f->mul(cs.constants[e.a], one); break;
+                case DEHALO_EXPR_FIXED: val[i] = ev(pl.p_fixed + e.a, e.rotation); break;
+                case DEHALO_EXPR_ADVICE: val[i] = ev(pl.adv(c) + e.a, e.rotation); break;
+                case DEHALO_EXPR_INSTANCE: val[i] = instance_eval(e.a, e.rotation); break;
+                case DEHALO_EXPR_CHALLENGE: val[i] = challenges[e.a]; break;
+                case DEHALO_EXPR_NEGATED: val[i] = f->neg(val[e.a]); break;
+                case DEHALO_EXPR_SUM: val[i] = f->add(val[e.a], val[e.b]); break;
+                case DEHALO_EXPR_PRODUCT: val[i] = f->mul(val[e.a], val[e.b]); break;
+                default: val[i] = f->mul(val[e.a], f->mul(cs.constants[e.b], one)); break;      // SCALED
+            }
+        }
+        auto fold = [&](const Fe& term) { expected_h = f->add(f->mul(expected_h, y), term); };
+        auto compress = [&](const std::vector<uint32_t>& es) {
+            Fe acc = zero;
+            for (uint32_t e : es) acc = f->add(f->mul(acc, theta), val[e]);
+            return acc;
+        };
+        for (uint32_t g : cs.gates) fold(val[g]);
+        if (S) {      // permutation::verifier::Evaluated::expressions
+            auto column_eval = [&](const dehalo_column_query& q) {
+                return q.kind == DEHALO_COLUMN_ADVICE ? ev(pl.adv(c) + q.index, 0) : q.kind == DEHALO_COLUMN_FIXED ? ev(pl.p_fixed + q.index, 0) : instance_eval(q.index, 0);
+            };
+            const uint32_t chunk = cs.chunk_len();
+            fold(f->mul(l_0, f->sub(one, ev(pl.pz(c), 0))));
+            const Fe zl = ev(pl.pz(c) + S - 1, 0);
+            fold(f->mul(l_last, f->sub(f->sqr(zl), zl)));
+            for (uint32_t s = 1; s < S; s++) fold(f->mul(l_0, f->sub(ev(pl.pz(c) + s, 0), ev(pl.pz(c) + s - 1, last))));
+            Fe cur = f->mul(beta, x);      // beta x delta^j, running across the sets' column chunks
+            for (uint32_t s = 0; s < S; s++) {
+                Fe left = ev(pl.pz(c) + s, 1), right = ev(pl.pz(c) + s, 0);
+                for (size_t j = (size_t)s * chunk; j < std::min<size_t>((size_t)(s + 1) * chunk, cs.perm_cols.size()); j++) {
+                    const Fe cv = column_eval(cs.perm_cols[j]);
+                    left = f->mul(left, f->add(f->add(cv, f->mul(beta, ev(pl.p_sigma + (uint32_t)j, 0))), gamma));
+                    right = f->mul(right, f->add(f->add(cv, cur), gamma));
+                    cur = f->mul(cur, f->delta);
+                }
+                fold(f->mul(f->sub(left, right), active));
+            }
+        }
+        for (uint32_t l = 0; l < L; l++) {      // lookup::verifier::Evaluated::expressions
+            const uint32_t zc = pl.lz(c) + l, ai = pl.perm(c) + 2 * l, ti = ai + 1;
+            const Fe &z0 = ev(zc, 0), &z1 = ev(zc, 1), &a0 = ev(ai, 0), &am1 = ev(ai, -1), &s0 = ev(ti, 0);
+            const Fe left = f->mul(f->mul(z1, f->add(a0, beta)), f->add(s0, gamma));
+            const Fe right = f->mul(f->mul(z0, f->add(compress(cs.lookups[l].inputs), beta)), f->add(compress(cs.lookups[l].tables), gamma));
+            fold(f->mul(l_0, f->sub(one, z0)));
+            fold(f->mul(l_last, f->sub(f->sqr(z0), z0)));
+            fold(f->mul(f->sub(left, right), active));
+            fold(f->mul(l_0, f->sub(a0, s0)));
+            fold(f->mul(f->mul(f->sub(a0, s0), f->sub(a0, am1)), active));
+        }
+        for (uint32_t j = 0; j < H; j++) {      // shuffles: l0 (1 - z), l_last (z^2 - z), l_active (z(wx) (S + gamma) - z(x) (A + gamma))
+            const Fe &z0 = ev(pl.sz(c) + j, 0), &z1 = ev(pl.sz(c) + j, 1);
+            fold(f->mul(l_0, f->sub(one, z0)));
+            fold(f->mul(l_last, f->sub(f->sqr(z0), z0)));
+            fold(f->mul(f->sub(f->mul(z1, f->add(compress(cs.shuffles[j].tables), gamma)), f->mul(z0, f->add(compress(cs.shuffles[j].inputs), gamma))), active));
+        }
+    }
+    const Fe hfold_eval = f->mul(expected_h, f->invert(xn1));      // (x^n = 1 with negligible probability: the value is then 0 and the check fails)
+    auto eval_of = [&](int64_t slot) -> const Fe& { return slot >= 0 ? E[(size_t)slot] : hfold_eval; };
+    // coef x the commitment of polynomial `poly`; the folded quotient h = sum_i x^(n i) h_i goes to its pieces
+    auto commitment_term = [&](const Fe& coef, uint32_t poly) {
+        if (poly != pl.p_hfold) { out.right(coef, cm[poly]); return; }
+        Fe xp = coef;
+        for (uint32_t i = 0; i < pieces; i++) {
+            out.right(xp, cm[pl.p_hpiece + i]);
+            xp = f->mul(xp, xn);
+        }
+    };
+
+    if (vk.multiopen != DEHALO_MULTIOPEN_SHPLONK) {      // VerifierGWC::verify_proof
+        const Fe v = t.squeeze();
+        std::vector<const uint64_t*> W;
+        for (size_t gi = 0; gi < pl.groups.size(); gi++) W.push_back(point());
+        const Fe u = t.squeeze();
+        Fe pu = weight, eval_multi = zero;
+        for (size_t gi = 0; gi < pl.groups.size(); gi++) {
+            const OpeningPlan::Group& g = pl.groups[gi];
+            out.left(pu, W[gi]);
+            out.right(f->mul(pu, d.rotate_omega(x, g.rot)), W[gi]);
+            Fe pv = pu;
+            for (size_t j = 0; j < g.polys.size(); j++) {
+                commitment_term(pv, g.polys[j]);
+                eval_multi = f->add(eval_multi, f->mul(pv, eval_of(g.evals[j])));
+                pv = f->mul(pv, v);
+            }
+            pu = f->mul(pu, u);
+        }
+        out.right(f->neg(eval_multi), vk.g0);
+        return true;
+    }
+    // VerifierSHPLONK::verify_proof over the plan's intermediate sets
+    const Fe y_ = t.squeeze(), v = t.squeeze();
+    const uint64_t* h = point();
+    const Fe u = t.squeeze();
+    const uint64_t* h2 = point();
+    const size_t ns = pl.point_sets.size();
+    std::vector<Fe> super;
+    for (int32_t r : pl.point_rot) super.push_back(d.rotate_omega(x, r));
+    std::vector<Fe> zdiff(ns, one), inv;      // inv: [zdiff_0 | per set, per point: prod_{s != t} (z_t - z_s)]
+    std::vector<std::vector<Fe>> basis(ns);   // prod_{s != t} (u - z_s), then times the inverted denominator: the Lagrange basis of the set at u
+    Fe z_0 = one;
+    for (size_t si = 0; si < ns; si++) {
+        const std::vector<uint32_t>& T = pl.point_sets[si];
+        for (uint32_t pi = 0; pi < super.size(); pi++)
+            if (std::find(T.begin(), T.end(), pi) == T.end()) zdiff[si] = f->mul(zdiff[si], f->sub(u, super[pi]));
+        if (si == 0) {
+            inv.push_back(zdiff[0]);
+            for (uint32_t pi : T) z_0 = f->mul(z_0, f->sub(u, super[pi]));
+        }
+        for (size_t a = 0; a < T.size(); a++) {
+            Fe num = one, den = one;
+            for (size_t b = 0; b < T.size(); b++)
+                if (b != a) { num = f->mul(num, f->sub(u, super[T[b]])); den = f->mul(den, f->sub(super[T[a]], super[T[b]])); }
+            basis[si].push_back(num);
+            inv.push_back(den);
+        }
+    }
+    // (u is an opening point, or two points coincide, with negligible probability: the inverses are then taken as 0 and the check fails)
+    if (!f->batch_invert(inv.data(), inv.size())) for (Fe& e : inv) e = f->invert(e);
+    Fe vi = weight, r_total = zero;
+    size_t io = 1;
+    for (size_t si = 0; si < ns; si++) {
+        for (Fe& b : basis[si]) b = f->mul(b, inv[io++]);
+        const Fe c = f->mul(f->mul(vi, zdiff[si]), inv[0]);
+        Fe yj = c;
+        for (uint32_t ci : pl.set_members[si]) {
+            const OpeningPlan::Commitment& m = pl.commitments[ci];
+            Fe r = zero;
+            for (size_t a = 0; a < basis[si].size(); a++) r = f->add(r, f->mul(basis[si][a], eval_of(m.evals[a])));
+            commitment_term(yj, m.poly);
+            r_total = f->add(r_total, f->mul(yj, r));
+            yj = f->mul(yj, y_);
+        }
+        vi = f->mul(vi, v);
+    }
+    out.right(f->neg(r_total), vk.g0);
+    out.right(f->neg(f->mul(weight, z_0)), h);
+    out.right(f->mul(weight, u), h2);
+    out.left(weight, h2);
+    return true;
+}
+
+// `count` proofs under one key: *accept = 1 iff every proof is readable and  e(sum_i w_i L_i, s_g2) e(-sum_i w_i R_i, g2) = 1.  *first_malformed: the first
+// unreadable proof or -1; *reason: a dehalo_reject_reason.  instances[(i N + c) nic + j] / instance_lens likewise: proof i's circuit c's column j (Montgomery words,
+// any residue).  weights: count scalars (Montgomery).  Returns 0 whenever the check ran; DEHALO_ERR_INVALID for the caller's errors, DEHALO_ERR_UNSUPPORTED for a
+// shape the opening plan refuses, or the backend's error.
+// the caller's errors of a verify call, before anything is read or drawn: 0, DEHALO_ERR_INVALID, or DEHALO_ERR_UNSUPPORTED for a shape the opening plan refuses
+inline int verify_check_arguments(const VerifierKey& vk, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
+                                  const size_t* instance_lens, uint32_t num_instance_columns, uint32_t N, std::string* error) {
+    auto fail = [&](int rc, const std::string& why) { if (error) *error = why; return rc; };
+    const HostCS& cs = vk.cs;
+    if (count && (!proofs || !lens)) return fail(DEHALO_ERR_INVALID, "verify_proofs: null argument");
+    if (N == 0) return fail(DEHALO_ERR_INVALID, "verify_proofs: no circuit");
+    if (count && num_instance_columns != cs.num_instance) return fail(DEHALO_ERR_INVALID, "verify_proofs: instances.len() != num_instance_columns");
+    if (num_instance_columns && count && (!instances || !instance_lens)) return fail(DEHALO_ERR_INVALID, "verify_proofs: null instances");
+    const OpeningPlan pl(vk.opening_shape(N));
+    if (!pl.error.empty()) return fail(DEHALO_ERR_UNSUPPORTED, pl.error);
+    const size_t usable = vk.dom.n - (cs.blinding_factors() + 1);
+    for (size_t e = 0; e < (size_t)count * N * num_instance_columns; e++) {
+        if (instance_lens[e] > usable) return fail(DEHALO_ERR_INVALID, "verify_proofs: an instance column is longer than the usable rows");
+        if (instance_lens[e] && !instances[e]) return fail(DEHALO_ERR_INVALID, "verify_proofs: null instance column");
+    }
+    return 0;
+}
+
+inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
+                              const size_t* instance_lens, uint32_t num_instance_columns, uint32_t N, const Fe* weights, int* accept, int64_t* first_malformed, int* reason,
+                              VerifyStats* stats, std::string* error) {
+    typedef std::chrono::steady_clock clk;
+    auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
+    auto fail = [&](int rc, const std::string& why) { if (error) *error = why; return rc; };
+    const HostField* f = vk.f;
+    if (!accept || (count && !weights)) return fail(DEHALO_ERR_INVALID, "verify_proofs: null argument");
+    const int bad = verify_check_arguments(vk, proofs, lens, count, instances, instance_lens, num_instance_columns, N, error);
+    if (bad) return bad;
+    const OpeningPlan pl(vk.opening_shape(N));
+    const int mo = vk.multiopen == DEHALO_MULTIOPEN_SHPLONK ? DEHALO_MULTIOPEN_SHPLONK : DEHALO_MULTIOPEN_GWC;
+    const size_t size = pl.proof_size(mo == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC);
+    const size_t p0 = verify_points_before_evals(pl), p1 = verify_multiopen_points(pl, mo), np = p0 + p1, off1 = size - 32 * p1;
+    if (first_malformed) *first_malformed = -1;
+    if (reason) *reason = DEHALO_REJECT_NONE;
+    *accept = 0;
+    VerifyStats st;
+
+    // ---- every proof's points, decoded in one call of the backend
+    std::vector<uint8_t> malformed(count, 0);
+    std::vector<size_t> slot_of(count, 0);
+    std::vector<uint8_t> enc;
+    size_t sized = 0;
+    for (uint32_t i = 0; i < count; i++) {
+        if (lens[i] != size || !proofs[i]) { malformed[i] = 1; continue; }      // bytes missing or trailing
+        slot_of[i] = sized++;
+        enc.insert(enc.end(), proofs[i], proofs[i] + 32 * p0);
+        enc.insert(enc.end(), proofs[i] + off1, proofs[i] + size);
+    }
+    std::vector<uint64_t> xy(8 * np * sized + 8);
+    clk::time_point t0 = clk::now();
+    if (sized) {
+        const int rc = be.decompress(enc.data(), np * sized, xy.data());
+        if (rc) return fail(rc, "verify_proofs: point decompression failed");
+    }
+    st.decompress = ms(t0);
+
+    // ---- the walks
+    t0 = clk::now();
+    VerifyTerms terms;
+    for (uint32_t i = 0; i < count; i++) {
+        if (malformed[i]) continue;
+        const uint64_t* pts = xy.data() + 8 * np * slot_of[i];
+        for (size_t j = 0; j < np && !malformed[i]; j++) {
+            bool zero = true;
+            for (int w = 0; w < 8; w++) zero = zero && pts[8 * j + w] == 0;
+            if (zero) malformed[i] = 1;      // refused by the decoder, or the identity
+        }
+        if (malformed[i]) continue;
+        std::vector<std::vector<std::vector<Fe>>> inst(N, std::vector<std::vector<Fe>>(num_instance_columns));
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t j = 0; j < num_instance_columns; j++) {
+                const size_t e = ((size_t)i * N + c) * num_instance_columns + j;
+                inst[c][j].resize(instance_lens[e]);
+                for (size_t r = 0; r < instance_lens[e]; r++) {
+                    Fe w;
+                    memcpy(w.v, instances[e] + 4 * r, 32);
+                    inst[c][j][r] = f->mul(w, f->one);      // a word stands for its residue
+                }
+            }
+        if (!verify_walk(vk, pl, N, proofs[i], lens[i], pts, inst, f->mul(weights[i], f->one), terms)) malformed[i] = 1;
+    }
+    st.walk = ms(t0);
+    for (uint32_t i = 0; i < count; i++)
+        if (malformed[i]) {
+            if (first_malformed) *first_malformed = i;
+            if (reason) *reason = DEHALO_REJECT_MALFORMED;
+            if (stats) *stats = st;
+            return 0;
+        }
+
+    // ---- the two sums and the pairing check
+    t0 = clk::now();
+    uint64_t sums[16] = {};      // L | R
+    if (!terms.ls.empty()) {
+        int rc = be.msm(terms.ls.data(), terms.lp.data(), terms.ls.size(), sums);
+        if (!rc) rc = be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), sums + 8);
+        if (rc) return fail(rc, "verify_proofs: the multi-scalar multiplication failed");
+    }
+    st.msm = ms(t0);
+    t0 = clk::now();
+    Fe ry;
+    memcpy(ry.v, sums + 12, 32);
+    ry = vk.fq->neg(ry);      // -R ((0, 0) stays the identity)
+    memcpy(sums + 12, ry.v, 32);
+    uint8_t g2s[256];
+    memcpy(g2s, vk.s_g2, 128);
+    memcpy(g2s + 128, vk.g2, 128);
+    int is_one = 0;
+    const PairingHost* ph = pairing_host(vk.curve);
+    if (!ph) return fail(DEHALO_ERR_UNSUPPORTED, "verify_proofs: no pairing on this curve");
+    // (g2 and s_g2 passed the constructor's checks, a proof's points the decoder's: a sum off the curve can only come from a key's commitment that was read
+    // unchecked and is no point.  Nothing such a key verifies is valid: the proof is rejected, the call is not in error.)
+    const int rc = ph->check(sums, g2s, 2, &is_one, /* g2_subgroup_known */ true);
+    if (rc == DEHALO_ERR_INVALID) is_one = 0;
+    else if (rc) return fail(rc, "verify_proofs: the pairing check failed");
+    st.pairing = ms(t0);
+    *accept = is_one ? 1 : 0;
+    if (reason && !is_one) *reason = DEHALO_REJECT_PAIRING;
+    if (stats) *stats = st;
+    return 0;
+}

@@ -7,6 +7,7 @@
 #include "hostrng.hpp"
 #include "internal.hpp"
 #include "plonk_host.hpp"
+#include "transcript_host.hpp"      // dehalo_transcript: Blake2bWrite / Blake2bRead (C entry points: params.hip)
 
 // ================================================================================================ ParamsKZG / ParamsIPA (params.hip)
 struct dehalo_params {
@@ -29,60 +30,6 @@ struct dehalo_params {
 // under IPA, the instance columns.  Taken to be Blind(F::ONE) (no upstream source at hand: parity unpinned).  Keygen and the prover
 // read this constant only; the CPU restatement and the verifier of the tests have its twin (tests/plonk_ipa_reference.py DEFAULT_BLIND).
 constexpr uint64_t IPA_DEFAULT_BLIND = 1;
-
-// ================================================================================================ transcript (C entry points: params.hip)
-struct dehalo_transcript {
-    int curve = 0;
-    const HostField *fq = nullptr, *fr = nullptr;      // base field (coordinates), scalar field (challenges)
-    Blake2b state;
-    std::vector<uint8_t> proof;
-
-    void init(int c) {
-        curve = c;
-        fq = host_field(curve_base_field(c));
-        fr = host_field(curve_scalar_field(c));
-        state.init(64, "Halo2-Transcript");
-        proof.clear();
-    }
-    Fe squeeze() {      // Challenge255: Blake2b-512 over everything absorbed + the prefix byte 0 (which stays absorbed), reduced mod r
-        const uint8_t z = 0;
-        state.update(&z, 1);
-        uint8_t d[64];
-        state.digest(d);
-        return fr->from_u512(d);
-    }
-    void common_scalar(const Fe& s) {
-        uint8_t b[33];
-        b[0] = 2;
-        fr->to_bytes(s, b + 1);
-        state.update(b, 33);
-    }
-    void write_scalar(const Fe& s) {
-        common_scalar(s);
-        uint8_t b[32];
-        fr->to_bytes(s, b);
-        proof.insert(proof.end(), b, b + 32);
-    }
-    // affine {x, y} Montgomery; false for the identity (upstream: "cannot write points at infinity to the transcript")
-    bool write_point(const uint64_t xy[8], bool also_to_proof = true) {
-        Fe x, y;
-        memcpy(x.v, xy, 32);
-        memcpy(y.v, xy + 4, 32);
-        if (x.is_zero() && y.is_zero()) return false;
-        uint8_t b[65];
-        b[0] = 1;
-        fq->to_bytes(x, b + 1);
-        fq->to_bytes(y, b + 33);
-        state.update(b, 65);
-        if (also_to_proof) {      // GroupEncoding: x little-endian, bit 7 of the last byte = y is odd
-            uint8_t c[32];
-            memcpy(c, b + 1, 32);
-            c[31] |= (uint8_t)((b[33] & 1) << 7);
-            proof.insert(proof.end(), c, c + 32);
-        }
-        return true;
-    }
-};
 
 // ================================================================================================ keys (keygen.hip, which defines the member functions)
 struct dehalo_pk {

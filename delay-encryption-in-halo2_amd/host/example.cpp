@@ -148,6 +148,22 @@ int main(int argc, char** argv) {
         const std::vector<uint8_t> proof = transcript.finalize();
         dump(dir + "/proof.bin", proof);
         std::printf("k = %u: proof of %zu bytes written\n", k, proof.size());
+        // benches/delay_enc.rs:147-165: verify_proof(..) and assert!(accept) -- on the device verifier made from the objects at hand, and on a host verifier made
+        // from what a verifier elsewhere would hold: g[0], g2, s_g2 of the params file and the Processed vk
+        Verifier verifier(be, params, pk);
+        int reason = 0;
+        if (!verifier.verify(proof, {{}}, &reason)) throw std::runtime_error("verify_proof rejected the proof just made (reason " + std::to_string(reason) + ")");
+        std::vector<uint8_t> tampered = proof;
+        tampered[tampered.size() / 2] ^= 1;
+        if (verifier.verify(tampered, {{}}, &reason) || reason == DEHALO_REJECT_NONE) throw std::runtime_error("verify_proof accepted a tampered proof");
+        const std::vector<uint8_t> pbytes = params.write();
+        Affine g0;
+        memcpy(g0.data(), pbytes.data() + 4, 64);
+        Verifier elsewhere(nullptr, DEHALO_CURVE_BN254_G1, k, g0, pbytes.data() + pbytes.size() - 256, pbytes.data() + pbytes.size() - 128, cs,
+                           ProvingKey(be, DEHALO_CURVE_BN254_G1, cs, slurp(dir + "/pk.bin"), 0).vk_write(DEHALO_SERDE_PROCESSED), DEHALO_SERDE_PROCESSED, 0);
+        elsewhere.set_transcript_repr(repr);
+        if (!elsewhere.verify(proof, {{}}) || elsewhere.verify(tampered, {{}})) throw std::runtime_error("the host verifier disagrees with the device verifier");
+        std::printf("k = %u: proof accepted by the device verifier and by a host verifier made from the vk bytes\n", k);
     } catch (const std::exception& e) {
         std::printf("error: %s\n", e.what());
         return 1;

@@ -533,4 +533,65 @@ class Prover {
     dehalo_prover* p_ = nullptr;
 };
 
+// verify_proof::<KZGCommitmentScheme<Bn256>, VerifierGWC | VerifierSHPLONK, Challenge255<_>, Blake2bRead<_, _, _>, SingleStrategy | AccumulatorStrategy>
+// (benches/delay_enc.rs:147-165): the verifying half of the params and of the key.  Made from a Backend, the points and the two sums of the reduction run on
+// the device; made without one (the second constructor with be == nullptr) it is a host verifier -- a mode the caller chooses, not a fallback.
+class Verifier {
+  public:
+    Verifier(const Backend& be, const ParamsKZG& params, const ProvingKey& pk, dehalo_multiopen m = DEHALO_MULTIOPEN_GWC) {
+        be.check(dehalo_verifier_create(be.raw(), params.raw(), pk.raw(), &v_));
+        check(dehalo_verifier_set_multiopen(v_, m));
+    }
+    // ParamsVerifierKZG + VerifyingKey::read: g0 = g[0], g2 / s_g2 the params' 128 raw bytes, the vk in any format
+    Verifier(const Backend* be, dehalo_curve curve, uint32_t k, const Affine& g0, const uint8_t g2[128], const uint8_t s_g2[128], ConstraintSystem& cs,
+             const std::vector<uint8_t>& vk_bytes, dehalo_serde_format vk_format, uint32_t num_selectors, dehalo_multiopen m = DEHALO_MULTIOPEN_GWC) {
+        const int rc = dehalo_verifier_create_vk(be ? be->raw() : nullptr, curve, k, g0.data(), g2, s_g2, cs.descriptor(), vk_bytes.data(), vk_bytes.size(), vk_format,
+                                                 num_selectors, &v_);
+        if (be) be->check(rc);
+        else if (rc != 0) {      // no context to ask: the constructor's own text
+            char why[512];
+            dehalo_verifier_create_error(why, sizeof why);
+            throw std::runtime_error(std::string(why) + " (" + std::to_string(rc) + ")");
+        }
+        check(dehalo_verifier_set_multiopen(v_, m));
+    }
+    ~Verifier() { dehalo_verifier_release(v_); }
+    Verifier(const Verifier&) = delete;
+    void set_transcript_repr(const Fe& r) { check(dehalo_verifier_set_transcript_repr(v_, r.data())); }
+    // true: accepted.  false: *reason (if given) says why -- DEHALO_REJECT_MALFORMED or DEHALO_REJECT_PAIRING.  instances: one vector per instance column
+    bool verify(const std::vector<uint8_t>& proof, const std::vector<std::vector<Fe>>& instances, int* reason = nullptr) const {
+        std::vector<const uint64_t*> ip;
+        std::vector<size_t> il;
+        for (auto& col : instances) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
+        int accept = 0;
+        check(dehalo_verify_proof(v_, ip.data(), il.data(), (uint32_t)ip.size(), 1, proof.data(), proof.size(), &accept, reason));
+        return accept != 0;
+    }
+    // proofs over one circuit each with the same instance columns' count; ONE pairing check for all (rng == nullptr: operating-system entropy for the weights,
+    // which must be unpredictable to whoever made the proofs).  *first_malformed: the first unreadable proof, or -1
+    bool verify_batch(const std::vector<std::vector<uint8_t>>& proofs, const std::vector<std::vector<std::vector<Fe>>>& instances, dehalo_rng* rng = nullptr,
+                      int64_t* first_malformed = nullptr) const {
+        std::vector<const uint8_t*> pp;
+        std::vector<size_t> pl, il;
+        std::vector<const uint64_t*> ip;
+        for (auto& p : proofs) { pp.push_back(p.data()); pl.push_back(p.size()); }
+        if (instances.size() != proofs.size()) check(DEHALO_ERR_INVALID);
+        const uint32_t columns = instances.empty() ? 0 : (uint32_t)instances[0].size();
+        for (auto& one : instances) {
+            if (one.size() != columns) check(DEHALO_ERR_INVALID);
+            for (auto& col : one) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
+        }
+        int accept = 0;
+        check(dehalo_verify_proofs(v_, pp.data(), pl.data(), (uint32_t)pp.size(), ip.data(), il.data(), columns, 1, rng, &accept, first_malformed));
+        return accept != 0;
+    }
+    dehalo_verifier* raw() const { return v_; }
+
+  private:
+    void check(int rc) const {
+        if (rc != 0) throw std::runtime_error(std::string("dehalo verifier: ") + dehalo_verifier_last_error(v_) + " (" + std::to_string(rc) + ")");
+    }
+    dehalo_verifier* v_ = nullptr;
+};
+
 }  // namespace halo2_amd

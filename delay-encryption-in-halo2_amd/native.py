@@ -489,6 +489,60 @@ class Blake2bWrite:
             pass
 
 
+class Blake2bRead(Blake2bWrite):
+    """dehalo_transcript over a proof's bytes: Blake2bRead<_, C, Challenge255<C>>.  common_scalar and squeeze_challenge_scalar are the writer's; a read that
+    the library refuses (bytes missing, a scalar not below r, an x not below p or not on the curve, the all-zero identity) raises ValueError and consumes nothing."""
+
+    def __init__(self, curve: CurveSpec, proof: bytes):
+        self.curve = curve
+        self.handle = C.c_void_p()
+        data = np.frombuffer(bytes(proof), dtype=np.uint8)
+        rc = load_library().dehalo_transcript_create_read(curve.id, data.ctypes.data if data.size else None, data.size, C.byref(self.handle))
+        if rc:
+            raise DehaloError(rc, "transcript_create_read")
+
+    def write_scalar(self, s: int):
+        raise TypeError("Blake2bRead: a reading transcript writes nothing")
+
+    def write_point(self, P):
+        raise TypeError("Blake2bRead: a reading transcript writes nothing")
+
+    def read_scalar(self) -> int:
+        out = np.zeros(4, dtype=np.uint64)
+        if load_library().dehalo_transcript_read_scalar(self.handle, out.ctypes.data):
+            raise ValueError("read_scalar: no canonical scalar at this position")
+        return self.curve.scalar.decode(out)
+
+    def read_point(self):
+        out = np.zeros(8, dtype=np.uint64)
+        if load_library().dehalo_transcript_read_point(self.handle, out.ctypes.data):
+            raise ValueError("read_point: no curve point at this position")
+        return (self.curve.base.decode(out[:4]), self.curve.base.decode(out[4:]))
+
+    @property
+    def remaining(self) -> int:
+        return load_library().dehalo_transcript_remaining(self.handle)
+
+
+def pairing_check(curve: CurveSpec, pairs) -> bool:
+    """dehalo_pairing_check: prod e(P_i, Q_i) == 1 for [(P in G1, Q in G2)] on the host.  P = (x, y) canonical integers or None (the identity); Q = the 128 raw
+    bytes ParamsKZG keeps for g2 / s_g2 (all zero: the identity).  DehaloError for a point off its curve or subgroup (-1) and for a curve without a pairing (-5)."""
+    g1 = np.zeros((max(1, len(pairs)), 8), dtype=np.uint64)
+    g2 = bytearray()
+    for i, (P1, Q2) in enumerate(pairs):
+        if P1 is not None:
+            g1[i, :4], g1[i, 4:] = curve.base.encode(P1[0]), curve.base.encode(P1[1])
+        if len(Q2) != 128:
+            raise ValueError("pairing_check: a G2 point is 128 raw bytes")
+        g2 += bytes(Q2)
+    raw = np.frombuffer(bytes(g2) or bytes(1), dtype=np.uint8)
+    is_one = C.c_int(-1)
+    rc = load_library().dehalo_pairing_check(curve.id, g1.ctypes.data, raw.ctypes.data, len(pairs), C.byref(is_one))
+    if rc:
+        raise DehaloError(rc, "pairing_check")
+    return bool(is_one.value)
+
+
 def rng_struct(rng) -> Optional[CRng]:
     """None / prover.OsRng -> NULL (operating-system entropy inside the library); prover.KeyedRng -> its ChaCha20 key; prover.SeededRng -> its PCG64
     state; any other object with .scalars(count) -> a callback."""
@@ -516,6 +570,140 @@ def rng_struct(rng) -> Optional[CRng]:
     r._keep = RNG_FILL_FN(fill)
     r.fill = r._keep
     return r
+
+
+REJECT_NONE, REJECT_MALFORMED, REJECT_PAIRING = 0, 1, 2      # dehalo_reject_reason
+
+
+def _create_error() -> str:
+    """dehalo_verifier_create_error: why this thread's last verifier constructor failed (a host verifier has no context to ask)"""
+    buf = C.create_string_buffer(512)
+    load_library().dehalo_verifier_create_error(buf, len(buf))
+    return buf.value.decode()
+
+
+class Verifier:
+    """dehalo_verifier: verify_proof for KZG (GWC and SHPLONK), one proof or a batch.  It holds the verifying half of the params and of the key only.
+    With a Context the proofs' points are decompressed and the two sums of the reduction are formed on the device; with ctx=None it is a HOST verifier -- a mode
+    the caller chooses (machines without a GPU), never a fallback.  The pairing check runs on the host in both."""
+
+    MULTIOPEN = {"gwc": 0, "shplonk": 1}      # dehalo_multiopen
+
+    def __init__(self, ctx: Optional[Context], curve: CurveSpec, handle, multiopen: str = "gwc"):
+        self.ctx, self.curve, self.handle = ctx, curve, handle
+        self.last_reject = REJECT_NONE          # why the last verify / verify_batch said no
+        self.first_malformed = -1               # verify_batch: the first unreadable proof
+        self.set_multiopen(multiopen)
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise DehaloError(rc, load_library().dehalo_verifier_last_error(self.handle).decode() if self.handle else "verifier")
+
+    @classmethod
+    def from_pk(cls, params: ParamsKZG, pk: "ProvingKey", multiopen: str = "gwc") -> "Verifier":
+        """from objects the caller already has (dehalo_verifier_create): g[0], g2, s_g2, k of the params; the commitments, constraint system and transcript_repr of the key"""
+        h = C.c_void_p()
+        rc = load_library().dehalo_verifier_create(params.ctx.handle, params.handle, pk.handle, C.byref(h))
+        if rc:
+            raise DehaloError(rc, _create_error())
+        return cls(params.ctx, params.curve, h, multiopen)
+
+    @classmethod
+    def from_vk(cls, curve: CurveSpec, k: int, g0, g2: bytes, s_g2: bytes, cs: plonk.ConstraintSystem, vk_bytes: bytes, num_selectors: int = 0,
+                format: str = "raw-unchecked", ctx: Optional[Context] = None, multiopen: str = "gwc", transcript_repr: Optional[int] = None) -> "Verifier":
+        """ParamsVerifierKZG + VerifyingKey::read (dehalo_verifier_create_vk): g0 = g[0] as (x, y) canonical ints or 8 Montgomery words; g2, s_g2 the 128 raw bytes
+        ParamsKZG keeps; vk_bytes in `format` (one of SERDE_FORMATS).  transcript_repr: None = the substitute keygen gives the same vk bytes."""
+        if isinstance(g0, tuple):
+            g0 = np.concatenate([curve.base.encode(g0[0]), curve.base.encode(g0[1])])
+        g0 = np.ascontiguousarray(g0, dtype=np.uint64).reshape(8)
+        desc = ConstraintSystemDescriptor(cs, curve.scalar)
+        buf = np.frombuffer(bytes(vk_bytes), dtype=np.uint8)
+        h = C.c_void_p()
+        lib = load_library()
+        rc = lib.dehalo_verifier_create_vk(ctx.handle if ctx is not None else None, curve.id, k, g0.ctypes.data, _bytes_ptr(bytes(g2).ljust(128, b"\0")),
+                                           _bytes_ptr(bytes(s_g2).ljust(128, b"\0")), desc.ref(), buf.ctypes.data if buf.size else None, buf.size, _serde(format), num_selectors,
+                                           C.byref(h))
+        if rc:
+            raise DehaloError(rc, _create_error())
+        v = cls(ctx, curve, h, multiopen)
+        if transcript_repr is not None:
+            v.transcript_repr = transcript_repr
+        return v
+
+    def set_multiopen(self, multiopen: str):
+        if multiopen not in self.MULTIOPEN:
+            raise ValueError("multiopen: 'gwc' or 'shplonk'")
+        self._check(load_library().dehalo_verifier_set_multiopen(self.handle, self.MULTIOPEN[multiopen]))
+
+    def _set_repr(self, value: int):
+        self._check(load_library().dehalo_verifier_set_transcript_repr(self.handle, self.curve.scalar.encode(value).ctypes.data))
+
+    transcript_repr = property(None, _set_repr)
+
+    def _instances(self, per_proof):
+        """[proof][circuit][column] -> the pointer and length tables of dehalo_verify_proofs, the arrays they point into, columns per circuit, circuits"""
+        f = self.curve.scalar
+        circuits = len(per_proof[0]) if per_proof else 1
+        ncols = len(per_proof[0][0]) if per_proof and circuits else 0
+        cols = []
+        for inst in per_proof:
+            if len(inst) != circuits or any(len(c) != ncols for c in inst):
+                raise ValueError("every proof needs the same number of circuits and instance columns")
+            cols += [_instance_words(f, v) for c in inst for v in c]
+        ptrs = (C.c_void_p * max(1, len(cols)))(*[c.ctypes.data if c.size else None for c in cols])
+        lens = (C.c_size_t * max(1, len(cols)))(*[c.shape[0] for c in cols])
+        return ptrs, lens, cols, ncols, circuits
+
+    def verify(self, proof: bytes, instances: Sequence = ((),), num_circuits: Optional[int] = None) -> bool:
+        """dehalo_verify_proof.  instances: one list of canonical ints per instance column; with num_circuits = N, instances[c] circuit c's columns.  False: see
+        last_reject (REJECT_MALFORMED: a read failed, bytes missing or trailing; REJECT_PAIRING).  DehaloError(-1): a wrong number of instance columns or a column
+        longer than the usable rows."""
+        per_circuit = [list(instances)] if num_circuits is None else [list(c) for c in instances]
+        ptrs, lens, keep, ncols, circuits = self._instances([per_circuit])
+        buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+        accept, reason = C.c_int(0), C.c_int(0)
+        self._check(load_library().dehalo_verify_proof(self.handle, ptrs, lens, ncols, circuits, buf.ctypes.data if buf.size else None, buf.size, C.byref(accept), C.byref(reason)))
+        self.last_reject = int(reason.value)
+        return bool(accept.value)
+
+    def verify_batch(self, proofs: Sequence[bytes], instances: Optional[Sequence] = None, rng=None, num_circuits: Optional[int] = None) -> bool:
+        """dehalo_verify_proofs: every proof read, then ONE pairing check over the weighted sums (w_0 = 1, the others the first len(proofs) - 1 scalars of rng;
+        None = OS entropy -- the weights must be unpredictable to whoever made the proofs).  instances[i]: proof i's, as verify takes them (None: no instance
+        values anywhere).  False: first_malformed names the first unreadable proof, or is -1 (the pairing failed: verify singly to find which)."""
+        bufs = [np.frombuffer(bytes(p), dtype=np.uint8) for p in proofs]
+        if instances is None:
+            instances = [((),) if num_circuits is None else [((),)] * num_circuits] * len(bufs)
+        per_proof = [[list(i)] if num_circuits is None else [list(c) for c in i] for i in instances]
+        if len(per_proof) != len(bufs):
+            raise ValueError("one instance list per proof")
+        ptrs, lens, keep, ncols, circuits = self._instances(per_proof)
+        pp = (C.c_void_p * max(1, len(bufs)))(*[b.ctypes.data if b.size else None for b in bufs])
+        pl = (C.c_size_t * max(1, len(bufs)))(*[b.size for b in bufs])
+        r = rng_struct(rng)
+        accept, first = C.c_int(0), C.c_int64(-1)
+        self._check(load_library().dehalo_verify_proofs(self.handle, pp, pl, len(bufs), ptrs, lens, ncols, circuits if bufs else (num_circuits or 1),
+                                                       C.byref(r) if r is not None else None, C.byref(accept), C.byref(first)))
+        rng_writeback(rng, r)
+        self.first_malformed = int(first.value)
+        self.last_reject = REJECT_NONE if accept.value else (REJECT_MALFORMED if first.value >= 0 else REJECT_PAIRING)
+        return bool(accept.value)
+
+    def last_timings(self) -> dict:
+        """milliseconds of the last call: point decompression, the transcript walks, the two MSMs, the pairing check"""
+        out = (C.c_double * 4)()
+        self._check(load_library().dehalo_verifier_last_timings(self.handle, out))
+        return dict(zip(("decompress", "walk", "msm", "pairing"), out))
+
+    def release(self):
+        if self.handle is not None:
+            load_library().dehalo_verifier_release(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:      # noqa: BLE001 -- interpreter shutdown
+            pass
 
 
 def rng_writeback(rng, r: Optional[CRng]):

@@ -560,10 +560,10 @@ int dehalo_shuffle_h_batch_device(dehalo_ctx* ctx, int field, const dehalo_shuff
 typedef struct dehalo_params dehalo_params;         /* ParamsKZG<E>: k, g, g_lagrange (resident MSM tables), g2, s_g2; or ParamsIPA<C>: k, g, g_lagrange, w, u */
 typedef struct dehalo_pk dehalo_pk;                 /* ProvingKey<C> incl. its VerifyingKey and the compiled GraphEvaluator programs */
 typedef struct dehalo_prover dehalo_prover;         /* device buffers of ONE proof in flight (reused by every create_proof on it) */
-typedef struct dehalo_transcript dehalo_transcript; /* Blake2bWrite<Vec<u8>, C, Challenge255<C>> */
+typedef struct dehalo_transcript dehalo_transcript; /* Blake2bWrite<Vec<u8>, C, Challenge255<C>>, or Blake2bRead over a proof's bytes (dehalo_transcript_create_read) */
 
 /* ParamsKZG [UPSTREAM halo2_proofs/src/poly/kzg/commitment.rs].  g / g_lagrange: 2^k affine points each ({x, y} Montgomery, 64 B);
- * g2 / s_g2: 128 raw bytes each (kept for write(); the prover never uses them).  read / write: SerdeFormat::RawBytes --
+ * g2 / s_g2: 128 raw bytes each (kept for write() and for a verifier made from these params, dehalo_verifier_create, whose pairing check reads them; the prover never uses them).  read / write: SerdeFormat::RawBytes --
  * k: u32 LE | g | g_lagrange | g2 | s_g2  (what benches/delay_enc.rs:45,54 write and read). */
 int dehalo_params_create(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint8_t* g2, const uint8_t* s_g2,
                          dehalo_params** out);
@@ -786,6 +786,23 @@ int dehalo_transcript_squeeze_challenge(dehalo_transcript* t, uint64_t out[4]); 
 size_t dehalo_transcript_len(const dehalo_transcript* t);
 int dehalo_transcript_finalize(const dehalo_transcript* t, uint8_t* out, size_t cap);                /* the proof bytes written so far */
 void dehalo_transcript_release(dehalo_transcript* t);
+/* Blake2bRead<_, C, Challenge255<C>>: the same object over the `len` bytes of a proof (copied; `proof` may be NULL when len = 0).  common_scalar and
+ * squeeze_challenge work on both kinds; the write_* calls on a reader and the read_* calls on a writer return DEHALO_ERR_INVALID, and a reader's _len is 0.
+ * A read takes the next 32 bytes, absorbs what it decoded exactly as the writer absorbed it, and returns it (Montgomery words, canonical).  It fails with
+ * DEHALO_ERR_INVALID, leaving the position and the hash state where they were, when fewer than 32 bytes are left; for a scalar, when the integer is not below
+ * r; for a point (GroupEncoding::from_bytes: x little-endian, bit 255 = y is odd), when x is not below p, when x^3 + b is not a square, or when the bytes
+ * are all zero (the identity, which no writer can have written).  All three curves.  _remaining: the bytes not read yet (0 for a writer). */
+int dehalo_transcript_create_read(int curve, const uint8_t* proof, size_t len, dehalo_transcript** out);
+int dehalo_transcript_read_point(dehalo_transcript* t, uint64_t affine_xy[8]);
+int dehalo_transcript_read_scalar(dehalo_transcript* t, uint64_t scalar[4]);
+size_t dehalo_transcript_remaining(const dehalo_transcript* t);
+
+/* The pairing check a KZG verifier ends with [UPSTREAM halo2_proofs/src/poly/kzg/strategy.rs; halo2curves bn256: multi_miller_loop, final_exponentiation]:
+ * prod_i e(P_i, Q_i) == 1 in GT.  P_i: affine x | y, 8 u64 Montgomery ((0, 0) = the identity, whose factor is 1); Q_i: the 128-byte raw form dehalo_params_create takes
+ * for g2 / s_g2 (all zero = the identity).  A P_i or Q_i off its curve, or a Q_i outside the order-r subgroup: DEHALO_ERR_INVALID.  count = 0: *is_one = 1.  Host only, no context.
+ * BN254 only: DEHALO_ERR_UNSUPPORTED for Pallas and Vesta.  Optimal ate over 6x + 2 and one final exponentiation for the whole product (csrc/pairing_host.hpp: every
+ * derived constant is computed at first use); a two-pair check takes milliseconds.  Nothing here runs in constant time: every input of a verifier is public. */
+int dehalo_pairing_check(int curve, const uint64_t* g1_affine_xy, const uint8_t* g2_raw, size_t count, int* is_one);
 
 /* The IPA opening of ONE polynomial [UPSTREAM halo2_proofs/src/poly/ipa/commitment/prover.rs: create_proof(params, rng, transcript, p_poly, p_blind,
  * x_3)]: proves that the commitment P = MSM(p, g) + [blind] W opens to p(x_3) -- what ProverIPA's multiopen ends with, and what a test or an integrator
@@ -988,6 +1005,52 @@ int dehalo_create_proof_circuit(dehalo_prover* prover, const dehalo_circuit_inpu
  * prover (witness generation of one proof runs beside the device work of the others). */
 int dehalo_create_proofs_circuit(dehalo_prover* const* provers, uint32_t num_provers, const dehalo_circuit_inputs* inputs, uint32_t count, dehalo_rng* rngs,
                                  uint8_t* const* proofs_out, size_t proof_cap, size_t* proof_lens);
+
+/* ---- verify_proof for KZG: GWC and SHPLONK, one proof or a batch (csrc/verify_host.hpp, verify.hip) ----------------------------------------------------------
+ * [UPSTREAM halo2_proofs plonk/verifier.rs verify_proof::<KZGCommitmentScheme<Bn256>, VerifierGWC | VerifierSHPLONK, Challenge255, Blake2bRead, SingleStrategy |
+ * AccumulatorStrategy>; benches/delay_enc.rs:147-165].  Everything the KZG prover proves is verified: N circuits in one proof, up to three advice phases with
+ * challenges, lookups, shuffles, up to 32 rotations, both multiopens.  A verifier holds the verifying half of the params (g[0], g2, s_g2, k) and of the key (the
+ * commitments, the constraint system, transcript_repr): no proving key, no SRS table.
+ * The host reads the proof through the Blake2bRead transcript, evaluates the gate, permutation, lookup and shuffle expressions at the read evaluations and
+ * reduces either multiopen to two sums L and R over the proof's points, the key's commitments and g[0]; accept iff e(L, s_g2) e(-R, g2) = 1
+ * (dehalo_pairing_check's code, on the host).  With a context the points of all proofs of a call are decompressed in ONE dehalo_points_decompress_device launch and
+ * the two sums are fresh-bases MSMs on the device (dehalo_best_multiexp); with ctx = NULL -- a HOST verifier, a mode the caller chooses, for machines without a
+ * GPU -- both run on the host (a plain double-and-add).  It is never a fallback: a verifier made with a context reports a device error as that error.
+ * IPA verification is not part of this: every entry point returns DEHALO_ERR_UNSUPPORTED for ParamsIPA or a Pasta curve. */
+typedef struct dehalo_verifier dehalo_verifier;
+/* from objects the caller already has: g[0], g2, s_g2, k of the params; the vk half of the key (commitments, constraint system, transcript_repr) */
+int dehalo_verifier_create(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_verifier** out);
+/* ParamsVerifierKZG + VerifyingKey::read: vk bytes in any dehalo_serde_format, parsed as dehalo_keygen_pk parses them; transcript_repr = the substitute dehalo_keygen
+ * gives for the same vk bytes until set.  ctx may be NULL: a HOST verifier (above). */
+int dehalo_verifier_create_vk(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t g0[8], const uint8_t g2[128], const uint8_t s_g2[128],
+                              const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len, int vk_format, uint32_t num_selectors, dehalo_verifier** out);
+/* Both constructors check g2 and s_g2: on the twist, in the order-r subgroup, not the identity; otherwise DEHALO_ERR_INVALID. */
+int dehalo_verifier_set_transcript_repr(dehalo_verifier* v, const uint64_t repr[4]);
+int dehalo_verifier_set_multiopen(dehalo_verifier* v, int multiopen);      /* DEHALO_MULTIOPEN_GWC (default) | _SHPLONK */
+int dehalo_verifier_release(dehalo_verifier* v);
+/* Why the calling thread's last dehalo_verifier_create / _create_vk failed (a bad g2, the vk's header, a point's status, ...): a host verifier has no context
+ * whose dehalo_last_error could say, and a failed constructor leaves no verifier.  The text is copied into out[0 .. cap), cut to cap - 1 bytes, NUL-terminated. */
+int dehalo_verifier_create_error(char* out, size_t cap);
+/* Text of the last error of a call on this verifier (a host verifier has no context to keep it); valid until the next call on it. */
+const char* dehalo_verifier_last_error(const dehalo_verifier* v);
+/* Where the last dehalo_verify_proof(s) call spent its time, milliseconds: out[0] point decompression, out[1] the transcript walks (hashing, expected_h, the
+ * term lists), out[2] the two MSMs, out[3] the pairing check. */
+int dehalo_verifier_last_timings(const dehalo_verifier* v, double out[4]);
+
+typedef enum { DEHALO_REJECT_NONE = 0, DEHALO_REJECT_MALFORMED = 1 /* a read failed, bytes missing or trailing */, DEHALO_REJECT_PAIRING = 2 } dehalo_reject_reason;
+/* instances / instance_lens / num_instance_columns / num_circuits: dehalo_create_proof_multi's layout.  Returns 0 whenever the check ran; *accept = 1 or 0, *reason (may be
+ * NULL) why not.  A wrong number of instance columns or a column longer than the usable rows is the caller's error: DEHALO_ERR_INVALID. */
+int dehalo_verify_proof(dehalo_verifier* v, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, uint32_t num_circuits,
+                        const uint8_t* proof, size_t len, int* accept, int* reason);
+/* `count` proofs under one verifier (upstream's BatchVerifier / AccumulatorStrategy): every proof is read as above, then sum_i w_i L_i and sum_i w_i R_i are checked with
+ * ONE pairing check.  w_0 = 1; w_1 .. w_{count-1} are the first count - 1 scalars of `rng` (NULL = DEHALO_RNG_OS), in order.  instances: proof i's circuit c's column j at
+ * [(i * num_circuits + c) * num_instance_columns + j], instance_lens likewise.  *accept = 1 iff every proof was readable and the combined check holds; *first_malformed = index of the first
+ * unreadable proof or -1 (a pairing failure does not say which proof: verify those singly).  With a context: all proofs' points in one decompress launch, the term lists
+ * concatenated into one MSM pair.
+ * THE WEIGHTS MUST BE UNPREDICTABLE TO WHOEVER MADE THE PROOFS: someone who knows w_i before choosing the proofs can make invalid proofs whose errors cancel in the
+ * weighted sums (two copies of one invalid proof under w_1 = -1 pass).  Use DEHALO_RNG_OS (rng = NULL) outside tests. */
+int dehalo_verify_proofs(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
+                         uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* accept, int64_t* first_malformed);
 
 /* The grand products' per-row factors, every product of a proof in one launch [UPSTREAM plonk/permutation/prover.rs Argument::commit:
  * per set of columns  den = prod_j (value_j + beta sigma_j + gamma),  num = prod_j (value_j + delta^j beta omega^i + gamma);
