@@ -16,7 +16,7 @@ ifdef EXPERIMENTS
 HIPFLAGS += -DDEHALO_EXPERIMENTS
 endif
 LIB ?= $(PKG)/libdehalo.so
-UNITS := capi params keygen prover verify check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
+UNITS := capi params transcript ipa_open keygen prover verify check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
 OBJS := $(UNITS:%=$(OBJDIR)/%.o)
 HDRS := $(wildcard $(CSRC)/*.cuh) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hpp) include/dehalo.h
 
@@ -56,13 +56,13 @@ opening_plan_multi_check: tests/native_host/opening_plan_multi_check.cpp $(CSRC)
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/opening_plan_multi_check tests/native_host/opening_plan_multi_check.cpp
 
 # the constraint system on the host (csrc/plonk_host.hpp: no HIP headers) with phases and challenges, under the same sanitizers (tests/test_phases_host.py runs it)
-host_cs_check: tests/native_host/host_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/hostfield.hpp
+host_cs_check: tests/native_host/host_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/host_cs_check tests/native_host/host_cs_check.cpp
 
 clean:
 	rm -rf $(LIB) $(OBJDIR) $(PKG)/host/example; $(MAKE) -C oracle clean
 # the shuffle argument on the host (plonk_host.hpp, opening_plan.hpp) under ASan + UBSan (tests/test_shuffle.py)
-shuffle_cs_check: tests/native_host/shuffle_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/opening_plan.hpp
+shuffle_cs_check: tests/native_host/shuffle_cs_check.cpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/opening_plan.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/shuffle_cs_check tests/native_host/shuffle_cs_check.cpp
 
 # the acceptance step of the ChaCha20 generator kinds (csrc/hostrng.hpp, shared by the host and the kernel) on crafted candidates, and HostRng's keyed kind,
@@ -72,20 +72,25 @@ hostrng_check: tests/native_host/hostrng_check.cpp $(CSRC)/hostrng.hpp $(CSRC)/h
 
 # ParamsKZG's on-disk formats (csrc/params_format.hpp: host only): layouts, the header of untrusted bytes and the G2 codec, under ASan + UBSan
 # (tests/test_params_format_host.py compares it with the Python mirror)
-params_format_check: tests/native_host/params_format_check.cpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+params_format_check: tests/native_host/params_format_check.cpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/params_format_check tests/native_host/params_format_check.cpp
 
 # VerifyingKey / ProvingKey on disk (csrc/key_format.hpp: host only): layouts, the header, the length and the count / length words of untrusted bytes, under
 # ASan + UBSan (tests/test_key_format_host.py compares it with the Python mirror)
-key_format_check: tests/native_host/key_format_check.cpp $(CSRC)/key_format.hpp include/dehalo.h
+key_format_check: tests/native_host/key_format_check.cpp $(CSRC)/key_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/key_format_check tests/native_host/key_format_check.cpp
 
 # the BN254 pairing check (csrc/pairing_host.hpp: host only) under ASan + UBSan (tests/test_pairing_host.py compares its verdicts with the oracle's and the library's)
-pairing_check: tests/native_host/pairing_check.cpp $(CSRC)/pairing_host.hpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+pairing_check: tests/native_host/pairing_check.cpp $(CSRC)/pairing_host.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/pairing_check tests/native_host/pairing_check.cpp
 
 # verify_proof on the host (csrc/verify_host.hpp: host only) on proofs the test writes to a file, under ASan + UBSan (tests/test_verify_host.py)
-verify_host_check: tests/native_host/verify_host_check.cpp $(CSRC)/verify_host.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
+verify_host_check: tests/native_host/verify_host_check.cpp $(CSRC)/verify_host.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/verify_host_check tests/native_host/verify_host_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check
+# G1 points on the host (csrc/g1_host.hpp: the codec of one point, the status texts, the group law) against the transcript's proof bytes, under ASan + UBSan
+# (tests/test_g1_host.py runs it)
+g1_host_check: tests/native_host/g1_host_check.cpp $(CSRC)/g1_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/blake2b.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/g1_host_check tests/native_host/g1_host_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check g1_host_check

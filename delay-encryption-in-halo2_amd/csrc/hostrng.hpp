@@ -2,7 +2,7 @@
 // `rng: R` argument of create_proof [UPSTREAM halo2_proofs/src/plonk/prover.rs; the reference passes OsRng, benches/delay_enc.rs:128].
 //   DEHALO_RNG_OS        the default: 32 bytes of operating-system entropy (getrandom) key a ChaCha20 stream per call; every scalar is
 //                        256 stream bits masked to the modulus' bit length and rejected when >= p -- uniform over the field (the blinding
-//                        rows on the host; the random polynomial's n scalars by a ChaCha20 KERNEL under the same key, params.hip);
+//                        rows on the host; the random polynomial's n scalars by a ChaCha20 KERNEL under the same key, transcript.hip);
 //   DEHALO_RNG_PCG64     TESTS / BENCHMARKS ONLY (not a CSPRNG): numpy's PCG64 stream from a given state, four 64-bit outputs per scalar,
 //                        top word masked to 61 bits -- the stream dehalo2_amd.prover.SeededRng and the CPU restatement consume, so that
 //                        proofs can be compared byte for byte;
@@ -31,7 +31,7 @@ typedef unsigned __int128 u128;
 #endif
 
 // From 256 candidate bits to a scalar -- the one acceptance step of the ChaCha20 kinds, on the host (HostRng::scalars) and in the kernel
-// (k_chacha_scalars, params.hip): v = eight 32-bit words, least significant first, is masked to the modulus' `bits` (225 .. 256) and accepted iff
+// (k_chacha_scalars, transcript.hip): v = eight 32-bit words, least significant first, is masked to the modulus' `bits` (225 .. 256) and accepted iff
 // the masked value is < p.  v holds the masked value afterwards either way.
 DH_HOST_DEVICE inline bool chacha_accept(uint32_t v[8], const uint32_t p[8], uint32_t bits) {
     if (bits < 256) v[7] &= ((uint32_t)1 << (bits - 224)) - 1;
@@ -42,7 +42,7 @@ DH_HOST_DEVICE inline bool chacha_accept(uint32_t v[8], const uint32_t p[8], uin
     return below;
 }
 
-// The ChaCha20 block function (RFC 8439) over the INDEXED schedule, in the two kernels that draw by index (k_chacha_scalars, params.hip; k_points_generate,
+// The ChaCha20 block function (RFC 8439) over the INDEXED schedule, in the two kernels that draw by index (k_chacha_scalars, transcript.hip; k_points_generate,
 // gfft.cuh): state = sigma | key | index mod 2^32 | (index >> 32 & 0xffff) | attempt << 16 | stream, low word first.  v = the block's first eight words
 // (its first 32 bytes, little-endian): the others are never formed.
 struct ChaKey { uint32_t k[8]; };      // a key as a kernel argument

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/dehalo.h"
+#include "g1_host.hpp"      // serde_format_known, point_status_text
 
 // what the circuit fixes of a key's shape: fixed columns, permutation columns, selectors serialised with the vk, and extended_k - k (from the degree)
 struct KeyShape {
@@ -56,11 +57,9 @@ struct KeyLayout {
 };
 constexpr uint32_t KEY_MAX_K = 28;
 
-inline bool key_format_known(int format) { return format == DEHALO_SERDE_PROCESSED || format == DEHALO_SERDE_RAW_BYTES || format == DEHALO_SERDE_RAW_BYTES_UNCHECKED; }
-
 // false for an unknown format, k > 28, an extended domain above 2^32 rows (its length word is a u32) or a size beyond size_t
 inline bool key_layout(int format, uint32_t k, const KeyShape& sh, KeyLayout& L) {
-    if (!key_format_known(format) || k > KEY_MAX_K || sh.ext_shift > 32 || k + sh.ext_shift > 32) return false;
+    if (!serde_format_known(format) || k > KEY_MAX_K || sh.ext_shift > 32 || k + sh.ext_shift > 32) return false;
     const uint64_t n = (uint64_t)1 << k, m = n << sh.ext_shift;
     if (m > 0xffffffffull || sh.nf > 0xffffffffull || sh.npc > 0xffffffffull || sh.nsel > 0xffffffffull) return false;
     const uint64_t point = format == DEHALO_SERDE_PROCESSED ? 32 : 64;
@@ -100,7 +99,7 @@ inline void key_put_u32_be(uint8_t* o, uint32_t v) { for (int i = 0; i < 4; i++)
 
 // k of `len` bytes that claim to be a key in `format`: reads bytes[0 .. 4), and only when len >= 8 (a key has both header words)
 inline KeyHeaderError key_peek_k(const uint8_t* bytes, size_t len, int format, uint32_t& k) {
-    if (!key_format_known(format)) return KEY_HEADER_FORMAT;
+    if (!serde_format_known(format)) return KEY_HEADER_FORMAT;
     if (len < 8) return KEY_HEADER_SHORT;
     k = key_u32_be(bytes);
     return k > KEY_MAX_K ? KEY_HEADER_K : KEY_HEADER_OK;
@@ -132,13 +131,6 @@ inline KeyHeaderError key_check_poly_words(const uint8_t* bytes, const KeyLayout
     return KEY_HEADER_OK;
 }
 
-// the status bits of the point codec (include/dehalo.h) as the kind of failure; encodings: the Processed form
-inline const char* key_point_status_text(uint32_t status, bool encodings) {
-    if (status & 1) return encodings ? "an x coordinate is not below the modulus" : "a coordinate's stored word is not below the modulus";
-    if (status & 4) return "x = 0 with the sign bit set is not an encoding";
-    if (status & 2) return encodings ? "an x coordinate is not on the curve" : "a point is neither on the curve nor the identity";
-    return "";
-}
 inline std::string key_element_error_text(bool encodings, int section, uint64_t index) {
     return std::string(encodings ? "an element is not below the modulus" : "an element's stored word is not below the modulus") + ": " + key_section_name(section) + ", element " +
            std::to_string(index);

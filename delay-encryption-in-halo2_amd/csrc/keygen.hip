@@ -416,7 +416,7 @@ int vk_parse(dehalo_ctx* ctx, const char* who, int curve, const uint8_t* bytes, 
             TRY(dehalo_upload(ctx, bytes + off[v], 64 * cnt[v], pts.p));
             if (format == DEHALO_SERDE_RAW_BYTES) TRY(dehalo_points_check_device(ctx, curve, pts.u64(), cnt[v], &status, nullptr));
         }
-        if (status) return key_fail(ctx, who, std::string(key_point_status_text(status, enc)) + ": " + key_section_name(v == 0 ? KEY_FIXED_COMMITMENTS : KEY_PERM_COMMITMENTS));
+        if (status) return key_fail(ctx, who, std::string(point_status_text(status, enc)) + ": " + key_section_name(v == 0 ? KEY_FIXED_COMMITMENTS : KEY_PERM_COMMITMENTS));
         TRY(dehalo_download(ctx, pts.p, 64 * cnt[v], dst[v]->data()));
     }
     const uint8_t* p = bytes + L.off_selectors;

@@ -4,7 +4,7 @@
 // two Frobenius line steps, and the final exponentiation (q^12 - 1) / r = (q^6 - 1)(q^2 + 1) . (q^4 - q^2 + 1) / r, the last factor by plain square-and-multiply.
 // The only typed constant is the curve parameter x: the Frobenius coefficient xi^((q - 1) / 6) and the hard exponent (q^4 - q^2 + 1) / r are computed at first use
 // from q, r and xi.  O(1) per proof: affine line steps with one Fq2 inversion each, no sparse multiplication -- a check costs milliseconds beside a proof's.
-// Host only, no HIP header: params.hip includes it, and tests/native_host/pairing_check.cpp drives it on the CPU against an independent pairing's verdicts.
+// Host only, no HIP header: transcript.hip includes it, and tests/native_host/pairing_check.cpp drives it on the CPU against an independent pairing's verdicts.
 #pragma once
 #include <cstddef>
 #include <cstdint>

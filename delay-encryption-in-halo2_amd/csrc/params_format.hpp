@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "../../include/dehalo.h"
+#include "g1_host.hpp"      // the point codec's status bits (POINT_*), serde_format_known
 #include "hostfield.hpp"
 
 // ---- layout -------------------------------------------------------------------------------------------------------------------------------------
@@ -22,11 +23,9 @@ struct ParamsLayout {
 };
 constexpr uint32_t PARAMS_MAX_K = 28;
 
-inline bool params_format_known(int format) { return format == DEHALO_SERDE_PROCESSED || format == DEHALO_SERDE_RAW_BYTES || format == DEHALO_SERDE_RAW_BYTES_UNCHECKED; }
-
 // false for an unknown format or k > 28 (at k = 28 the largest size is 4 + 2^35 + 256: far inside 64 bits; size_t narrower than that is refused)
 inline bool params_layout(int format, uint32_t k, ParamsLayout& L) {
-    if (!params_format_known(format) || k > PARAMS_MAX_K) return false;
+    if (!serde_format_known(format) || k > PARAMS_MAX_K) return false;
     const uint64_t n = (uint64_t)1 << k, g1 = format == DEHALO_SERDE_PROCESSED ? 32 : 64, g2 = 2 * g1;
     const uint64_t size = 4 + 2 * g1 * n + 2 * g2;
     if (size > (uint64_t)SIZE_MAX) return false;
@@ -40,11 +39,13 @@ inline const char* params_header_error_text(int e) {
     static const char* const text[] = {"", "unknown format", "unexpected end of input", "k out of range", "length does not match k"};
     return e >= 0 && e <= PARAMS_HEADER_LENGTH ? text[e] : "";
 }
+// k: u32 LE, the first word of every params file (ParamsKZG in each format, ParamsIPA)
+inline uint32_t params_u32_le(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }
 // The header of `len` bytes in `format`: reads bytes[0 .. 4) only, and only when len >= 4; the length must be exactly the layout's.
 inline ParamsHeaderError params_parse_header(const uint8_t* bytes, size_t len, int format, ParamsLayout& L) {
-    if (!params_format_known(format)) return PARAMS_HEADER_FORMAT;
+    if (!serde_format_known(format)) return PARAMS_HEADER_FORMAT;
     if (len < 4) return PARAMS_HEADER_SHORT;
-    const uint32_t k = (uint32_t)bytes[0] | ((uint32_t)bytes[1] << 8) | ((uint32_t)bytes[2] << 16) | ((uint32_t)bytes[3] << 24);      // u32 LE
+    const uint32_t k = params_u32_le(bytes);
     if (!params_layout(format, k, L)) return PARAMS_HEADER_K;
     if (len != L.size) return PARAMS_HEADER_LENGTH;
     return PARAMS_HEADER_OK;
@@ -52,8 +53,6 @@ inline ParamsHeaderError params_parse_header(const uint8_t* bytes, size_t len, i
 
 // ---- G2 on the host ---------------------------------------------------------------------------------------------------------------------------
 struct Fq2 { Fe a, b; };      // a + b i, Montgomery
-// the status bits of a point codec, host and device alike (include/dehalo.h, dehalo_points_decompress_device / dehalo_points_check_device)
-enum { POINT_NOT_BELOW_P = 1, POINT_NOT_ON_CURVE = 2, POINT_ZERO_X_SIGNED = 4 };
 
 struct G2Host {
     const HostField* q;

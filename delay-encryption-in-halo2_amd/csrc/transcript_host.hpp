@@ -1,38 +1,14 @@
 // transcript_host.hpp -- the object behind dehalo_transcript: Blake2bWrite and Blake2bRead over Challenge255 [UPSTREAM halo2_proofs @ v2023_04_20 transcript.rs].
-// Host only, no HIP header: whole_call.hpp includes it for the prover, verify_host.hpp for the verifier.  The C entry points are params.hip's.
+// Host only, no HIP header: whole_call.hpp includes it for the prover, verify_host.hpp for the verifier.  The C entry points are transcript.hip's.
 #pragma once
 #include <vector>
 
 #include "../../include/dehalo.h"
 #include "blake2b.hpp"
+#include "g1_host.hpp"      // the one host codec of a G1 point
 #include "hostfield.hpp"
-#include "params_format.hpp"      // the point codec's status bits
 
-// y^2 = x^3 + b: 3 on BN254's G1, 5 on Pallas and Vesta
-inline uint64_t curve_b_host(int curve) { return curve == DEHALO_CURVE_BN254_G1 ? 3 : 5; }
-
-// GroupEncoding::from_bytes on the host, with the device codec's verdicts (dehalo_points_decompress_device): 0, or POINT_NOT_BELOW_P / POINT_NOT_ON_CURVE /
-// POINT_ZERO_X_SIGNED; a refused point and the all-zero identity are written as (0, 0).  The one host decoder: the reading transcript, the host verifier and
-// the verifying key's Processed commitments go through it.  (Upstream sends x = 0 with the sign bit set to the square root like every other x; b is no square
-// on any of the three curves -- a group of prime order has no point of order 3 -- so that path refuses it too.)
-inline uint32_t g1_decompress_host(const HostField* q, const Fe& b, const uint8_t in[32], uint64_t xy[8]) {
-    memset(xy, 0, 64);
-    Fe c;
-    memcpy(c.v, in, 32);
-    const unsigned sign = (unsigned)(c.v[3] >> 63);
-    c.v[3] &= ~((uint64_t)1 << 63);
-    if (HostField::geq(c.v, q->p)) return POINT_NOT_BELOW_P;
-    if (c.is_zero()) return sign ? POINT_ZERO_X_SIGNED : 0;
-    const Fe x = q->from_canonical(c);
-    Fe y;
-    if (!q->sqrt(q->add(q->mul(q->sqr(x), x), b), y)) return POINT_NOT_ON_CURVE;
-    if ((unsigned)(q->to_canonical(y).v[0] & 1) != sign) y = q->neg(y);
-    memcpy(xy, x.v, 32);
-    memcpy(xy + 4, y.v, 32);
-    return 0;
-}
-
-// ================================================================================================ transcript (C entry points: params.hip)
+// ================================================================================================ transcript (C entry points: transcript.hip)
 struct dehalo_transcript {
     int curve = 0;
     const HostField *fq = nullptr, *fr = nullptr;      // base field (coordinates), scalar field (challenges)
@@ -76,10 +52,9 @@ struct dehalo_transcript {
         fq->to_bytes(x, b + 1);
         fq->to_bytes(y, b + 33);
         state.update(b, 65);
-        if (also_to_proof) {      // GroupEncoding: x little-endian, bit 7 of the last byte = y is odd
+        if (also_to_proof) {
             uint8_t c[32];
-            memcpy(c, b + 1, 32);
-            c[31] |= (uint8_t)((b[33] & 1) << 7);
+            g1_compress_host(fq, xy, c);
             proof.insert(proof.end(), c, c + 32);
         }
         return true;

@@ -17,74 +17,13 @@
 #include <vector>
 
 #include "../../include/dehalo.h"
+#include "g1_host.hpp"
 #include "hostfield.hpp"
 #include "key_format.hpp"
 #include "opening_plan.hpp"
 #include "pairing_host.hpp"
 #include "plonk_host.hpp"
 #include "transcript_host.hpp"
-
-// ---- G1 on the host: y^2 = x^3 + b, Jacobian accumulator, affine addends ((0, 0) = the identity)
-struct G1Host {
-    const HostField* q;
-    Fe b;
-    struct Jac { Fe x, y, z; };
-    G1Host(const HostField* fq, uint64_t curve_b) : q(fq), b(fq->from_u64(curve_b)) {}
-    Jac identity() const { return Jac{q->one, q->one, Fe{}}; }
-    Jac dbl(const Jac& P) const {
-        if (P.z.is_zero() || P.y.is_zero()) return identity();
-        const Fe A = q->sqr(P.x), B = q->sqr(P.y), C = q->sqr(B);
-        Fe D = q->sub(q->sub(q->sqr(q->add(P.x, B)), A), C);
-        D = q->add(D, D);
-        const Fe E = q->add(q->add(A, A), A), F = q->sqr(E);
-        Jac R;
-        R.x = q->sub(F, q->add(D, D));
-        Fe C8 = q->add(C, C);
-        C8 = q->add(C8, C8);
-        C8 = q->add(C8, C8);
-        R.y = q->sub(q->mul(E, q->sub(D, R.x)), C8);
-        R.z = q->mul(q->add(P.y, P.y), P.z);
-        return R;
-    }
-    Jac add_affine(const Jac& P, const Fe& x2, const Fe& y2) const {
-        if (x2.is_zero() && y2.is_zero()) return P;
-        if (P.z.is_zero()) return Jac{x2, y2, q->one};
-        const Fe zz = q->sqr(P.z), u2 = q->mul(x2, zz), s2 = q->mul(q->mul(y2, P.z), zz);
-        if (u2 == P.x) return s2 == P.y ? dbl(P) : identity();
-        const Fe h = q->sub(u2, P.x), hh = q->sqr(h), hhh = q->mul(h, hh), r = q->sub(s2, P.y), v = q->mul(P.x, hh);
-        Jac R;
-        R.x = q->sub(q->sub(q->sqr(r), hhh), q->add(v, v));
-        R.y = q->sub(q->mul(r, q->sub(v, R.x)), q->mul(P.y, hhh));
-        R.z = q->mul(P.z, h);
-        return R;
-    }
-    void to_affine(const Jac& P, uint64_t xy[8]) const {
-        memset(xy, 0, 64);
-        if (P.z.is_zero()) return;
-        const Fe zi = q->invert(P.z), zi2 = q->sqr(zi), x = q->mul(P.x, zi2), y = q->mul(P.y, q->mul(zi2, zi));
-        memcpy(xy, x.v, 32);
-        memcpy(xy + 4, y.v, 32);
-    }
-    // sum_i [s_i] P_i, s canonical integers: one accumulator, 256 doublings, one mixed addition per set bit (a verifier's sums have about 10^2 terms)
-    void msm(const Fe* canonical_scalars, const uint64_t* xy, size_t len, uint64_t out_affine[8]) const {
-        Jac acc = identity();
-        for (int bit = 255; bit >= 0; bit--) {
-            acc = dbl(acc);
-            for (size_t i = 0; i < len; i++)
-                if ((canonical_scalars[i].v[bit >> 6] >> (bit & 63)) & 1) {
-                    Fe x, y;
-                    memcpy(x.v, xy + 8 * i, 32);
-                    memcpy(y.v, xy + 8 * i + 4, 32);
-                    acc = add_affine(acc, x, y);
-                }
-        }
-        to_affine(acc, out_affine);
-    }
-    bool on_curve(const Fe& x, const Fe& y) const { return q->sqr(y) == q->add(q->mul(q->sqr(x), x), b); }
-    // GroupEncoding::from_bytes with the device codec's verdicts (dehalo_points_decompress_device): 0, or POINT_NOT_BELOW_P / POINT_NOT_ON_CURVE /
-    // POINT_ZERO_X_SIGNED; a refused point and the all-zero identity are written as (0, 0)
-    uint32_t decompress(const uint8_t in[32], uint64_t xy[8]) const { return g1_decompress_host(q, b, in, xy); }      // (transcript_host.hpp: the one host decoder)
-};
 
 // ---- what decompresses a call's points and sums its two term lists: the host (below) or the device (verify.hip).  A non-zero return is an error of the
 // backend (a device error stays an error: nothing falls back to the host)
@@ -162,7 +101,7 @@ struct VerifierKey {
         KeyLayout L;
         const KeyHeaderError he = key_parse_header(bytes, len, format, shape(), k, false, L);
         if (he != KEY_HEADER_OK) return key_header_error_text(he);
-        const G1Host g1(fq, curve == DEHALO_CURVE_BN254_G1 ? 3 : 5);
+        const G1Host g1(fq, curve_b_host(curve));
         const size_t nf = cs.num_fixed, npc = cs.perm_cols.size();
         fixed_commitments.assign(8 * nf, 0);
         perm_commitments.assign(8 * npc, 0);
@@ -171,7 +110,7 @@ struct VerifierKey {
             uint64_t* dst = i < nf ? &fixed_commitments[8 * i] : &perm_commitments[8 * (i - nf)];
             if (format == DEHALO_SERDE_PROCESSED) {
                 const uint32_t st = g1.decompress(src, dst);
-                if (st) return key_point_status_text(st, true);
+                if (st) return point_status_text(st, true);
                 continue;
             }
             memcpy(dst, src, 64);
@@ -179,8 +118,8 @@ struct VerifierKey {
             Fe x, y;
             memcpy(x.v, dst, 32);
             memcpy(y.v, dst + 4, 32);
-            if (HostField::geq(x.v, fq->p) || HostField::geq(y.v, fq->p)) return key_point_status_text(1, false);
-            if (!(x.is_zero() && y.is_zero()) && !g1.on_curve(x, y)) return key_point_status_text(2, false);
+            if (HostField::geq(x.v, fq->p) || HostField::geq(y.v, fq->p)) return point_status_text(POINT_NOT_BELOW_P, false);
+            if (!(x.is_zero() && y.is_zero()) && !g1.on_curve(x, y)) return point_status_text(POINT_NOT_ON_CURVE, false);
         }
         selectors.clear();
         for (uint32_t s = 0; s < nsel; s++) selectors.emplace_back(bytes + L.off_selectors + L.sel_bytes * s, bytes + L.off_selectors + L.sel_bytes * (s + 1));

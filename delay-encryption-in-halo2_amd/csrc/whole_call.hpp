@@ -1,5 +1,5 @@
-// whole_call.hpp -- what the three units of the whole call share (host only): params.hip (ParamsKZG / ParamsIPA, the Blake2b transcript, the IPA opening
-// argument), keygen.hip (keygen_vk / keygen_pk, the RawBytes formats) and prover.hip (create_proof).  The objects behind the C ABI's opaque handles
+// whole_call.hpp -- what the units of the whole call share (host only): params.hip (ParamsKZG / ParamsIPA), transcript.hip (the Blake2b transcript, the scalar
+// draws), ipa_open.hip (the IPA opening argument), keygen.hip (keygen_vk / keygen_pk, the key formats) and prover.hip (create_proof).  The objects behind the C ABI's opaque handles
 // [UPSTREAM halo2_proofs @ v2023_04_20: poly/kzg/commitment.rs ParamsKZG, poly/ipa/commitment.rs ParamsIPA, transcript.rs Blake2bWrite, plonk.rs
 // ProvingKey / VerifyingKey] and the few functions one unit calls in another.  Everything else of a unit stays in its anonymous namespace.
 #pragma once
@@ -7,7 +7,7 @@
 #include "hostrng.hpp"
 #include "internal.hpp"
 #include "plonk_host.hpp"
-#include "transcript_host.hpp"      // dehalo_transcript: Blake2bWrite / Blake2bRead (C entry points: params.hip)
+#include "transcript_host.hpp"      // dehalo_transcript: Blake2bWrite / Blake2bRead (C entry points: transcript.hip)
 
 // ================================================================================================ ParamsKZG / ParamsIPA (params.hip)
 struct dehalo_params {
@@ -28,7 +28,7 @@ struct dehalo_params {
 
 // Blind::default() of upstream's poly/commitment.rs, the blind of every commitment that is not hiding: the verifying key's fixed and permutation columns and,
 // under IPA, the instance columns.  Taken to be Blind(F::ONE) (no upstream source at hand: parity unpinned).  Keygen and the prover
-// read this constant only; the CPU restatement and the verifier of the tests have its twin (tests/plonk_ipa_reference.py DEFAULT_BLIND).
+// read this constant only; the CPU restatement and the verifier of the tests have its twin (DEFAULT_BLIND in the reference prover's ipa.py, which INTEGRATION.md names).
 constexpr uint64_t IPA_DEFAULT_BLIND = 1;
 
 // ================================================================================================ keys (keygen.hip, which defines the member functions)
@@ -58,9 +58,9 @@ struct dehalo_pk {
 };
 
 // ================================================================================================ functions that cross units
-// params.hip: commitment::create_proof of ParamsIPA on `rng` as it stands, into `t` (dehalo_ipa_open; the last step of a ProverIPA proof)
+// ipa_open.hip: commitment::create_proof of ParamsIPA on `rng` as it stands, into `t` (dehalo_ipa_open; the last step of a ProverIPA proof)
 int ipa_open_body(dehalo_ctx* ctx, const dehalo_params* p, const uint64_t* d_poly, const Fe& blind, const Fe& x3, HostRng& rng, uint64_t cha_stream, dehalo_transcript* t);
-// params.hip: out[0 .. n) = uniform scalars of rng's field from ChaCha20 stream `cha_stream` under rng's key (rng.chacha()), one kernel launch on `s`
+// transcript.hip: out[0 .. n) = uniform scalars of rng's field from ChaCha20 stream `cha_stream` under rng's key (rng.chacha()), one kernel launch on `s`
 int chacha_scalars_device(dehalo_ctx* ctx, const HostRng& rng, uint64_t cha_stream, fe* out, size_t n, hipStream_t s);
 // keygen.hip: (n, 4) device column of omega^i
 int omega_powers(dehalo_ctx* ctx, const HostDomain& d, fe* col);

@@ -86,8 +86,8 @@ int main() {
             for (int s = 0; s < KEY_SECTIONS; s++) printf("%s\"%s\"", s ? ", " : "", key_section_name(s));
             printf("], \"element_processed\": \"%s\", \"element_raw\": \"%s\", \"points_processed\": [\"%s\", \"%s\", \"%s\"], \"points_raw\": [\"%s\", \"%s\"]}\n",
                    key_element_error_text(true, KEY_FIXED_POLYS, 7).c_str(), key_element_error_text(false, KEY_PERM_COSETS, 12345678901ull).c_str(),
-                   key_point_status_text(1, true), key_point_status_text(2, true), key_point_status_text(4, true), key_point_status_text(1, false),
-                   key_point_status_text(2, false));
+                   point_status_text(1, true), point_status_text(2, true), point_status_text(4, true), point_status_text(1, false),
+                   point_status_text(2, false));
         } else if (!cmd.empty()) {
             printf("{\"unknown\": true}\n");
         }
