@@ -3,6 +3,10 @@
 //! `BatchVerifier` / `AccumulatorStrategy` as one call.  The verifier holds the verifying half of the params and of the key; made with a context it decompresses
 //! the proofs' points and forms the two sums of the reduction on the device, made without one it runs on the host (`dehalo_verifier_create_vk` with a null
 //! context: a mode the caller chooses, never a fallback).  The pairing check runs on the host in both.
+//!
+//! `plonk::verify_proof::<IPACommitmentScheme<EqAffine>, VerifierIPA<_>, Challenge255<_>, Blake2bRead<_, _, _>, SingleStrategy<_>>` is the same verifier type
+//! made by `DehaloVerifierIPA::from_vk` (`dehalo_verifier_create_ipa_vk`: `ParamsIPA::read` + `VerifyingKey::read`) and `verify_proof_ipa` below: the instance
+//! columns enter as commitments, and acceptance is one multi-scalar multiplication over the params' generators whose scalars are built on the device.
 use crate::constraint_system::Descriptor;
 use crate::params::{DehaloParamsKZG, SerdeFormat};
 use crate::prover::DehaloProvingKey;
@@ -22,6 +26,8 @@ pub enum Reject {
     Malformed,
     /// the proof was read and the pairing check failed
     Pairing,
+    /// IPA: the proof was read and the final sum is not the identity (or `x_3` hit an opening point, or a round challenge was zero)
+    Opening,
 }
 
 pub struct DehaloVerifier {
@@ -134,4 +140,55 @@ pub fn verify_proof(verifier: &mut DehaloVerifier, instances: &[&[Fr]], proof: &
 pub fn verify_proof_shplonk(verifier: &mut DehaloVerifier, instances: &[&[Fr]], proof: &[u8]) -> Result<bool, DehaloError> {
     verifier.set_multiopen(sys::DEHALO_MULTIOPEN_SHPLONK)?;
     Ok(verifier.verify(&[instances], proof)?.is_ok())
+}
+
+/// The IPA verifier over Vesta (scalars in `pasta::Fp`): `dehalo_verifier` made by `dehalo_verifier_create_ipa_vk`.  It borrows the params.
+pub struct DehaloVerifierIPA<'p, 'c> {
+    raw: *mut sys::dehalo_verifier,
+    _params: &'p crate::params::DehaloParamsIPA<'c>,
+}
+
+impl<'p, 'c> DehaloVerifierIPA<'p, 'c> {
+    /// `ParamsIPA::read` + `VerifyingKey::read(&mut reader, vk_format)`: the key's commitments are the blinded ones a key made under `ParamsIPA` holds.
+    /// `transcript_repr` starts as the library's substitute: set upstream's with `set_transcript_repr`.
+    pub fn from_vk(ctx: &Context, params: &'p crate::params::DehaloParamsIPA<'c>, cs: &ConstraintSystem<halo2curves::pasta::Fp>, vk_bytes: &[u8], vk_format: SerdeFormat,
+                   num_selectors: u32) -> Result<Self, DehaloError> {
+        let d = Descriptor::from_constraint_system(cs);
+        let c = d.as_c();
+        let mut raw = core::ptr::null_mut();
+        ctx.check(unsafe { sys::dehalo_verifier_create_ipa_vk(ctx.as_ptr(), params.raw, &c, vk_bytes.as_ptr(), vk_bytes.len(), vk_format.into(), num_selectors, &mut raw) })?;
+        Ok(DehaloVerifierIPA { raw, _params: params })
+    }
+
+    fn check(&self, rc: i32) -> Result<(), DehaloError> {
+        if rc == 0 {
+            return Ok(());
+        }
+        let message = unsafe { CStr::from_ptr(sys::dehalo_verifier_last_error(self.raw)) }.to_string_lossy().into_owned();
+        Err(DehaloError { code: rc, message })
+    }
+
+    pub fn set_transcript_repr(&mut self, repr: &halo2curves::pasta::Fp) -> Result<(), DehaloError> {
+        self.check(unsafe { sys::dehalo_verifier_set_transcript_repr(self.raw, repr as *const _ as *const u64) })
+    }
+
+    /// one proof over one circuit; `instances`: one slice per instance column
+    pub fn verify(&self, instances: &[&[halo2curves::pasta::Fp]], proof: &[u8]) -> Result<Result<(), Reject>, DehaloError> {
+        let ptrs: Vec<*const u64> = instances.iter().map(|col| col.as_ptr() as *const u64).collect();
+        let lens: Vec<usize> = instances.iter().map(|col| col.len()).collect();
+        let (mut accept, mut reason) = (0, 0);
+        self.check(unsafe { sys::dehalo_verify_proof(self.raw, ptrs.as_ptr(), lens.as_ptr(), ptrs.len() as u32, 1, proof.as_ptr(), proof.len(), &mut accept, &mut reason) })?;
+        Ok(if accept != 0 { Ok(()) } else if reason == sys::DEHALO_REJECT_MALFORMED { Err(Reject::Malformed) } else { Err(Reject::Opening) })
+    }
+}
+
+impl Drop for DehaloVerifierIPA<'_, '_> {
+    fn drop(&mut self) {
+        unsafe { sys::dehalo_verifier_release(self.raw) };
+    }
+}
+
+/// `verify_proof::<IPACommitmentScheme<EqAffine>, VerifierIPA<_>, ..>` of one proof over one circuit: `accept`
+pub fn verify_proof_ipa(verifier: &DehaloVerifierIPA<'_, '_>, instances: &[&[halo2curves::pasta::Fp]], proof: &[u8]) -> Result<bool, DehaloError> {
+    Ok(verifier.verify(instances, proof)?.is_ok())
 }

@@ -44,6 +44,7 @@ SYMBOLS = [
     "dehalo_transcript_create_read", "dehalo_transcript_read_point", "dehalo_transcript_read_scalar", "dehalo_transcript_remaining", "dehalo_pairing_check",
     "dehalo_verifier_create", "dehalo_verifier_create_vk", "dehalo_verifier_set_transcript_repr", "dehalo_verifier_set_multiopen", "dehalo_verifier_release",
     "dehalo_verifier_create_error", "dehalo_verifier_last_error","dehalo_verifier_last_timings", "dehalo_verify_proof", "dehalo_verify_proofs",
+    "dehalo_ipa_s_device", "dehalo_verifier_create_ipa", "dehalo_verifier_create_ipa_vk", "dehalo_verifier_create_ipa_host", "dehalo_ipa_verify",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -189,6 +190,7 @@ def load_library():
     lib.dehalo_to_affine.argtypes = [P, C.c_int, u64p, sz, u64p]
     lib.dehalo_to_affine_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
     lib.dehalo_generator_collapse_device.argtypes = [P, C.c_int, u64p, sz, u64p, u64p, P]
+    lib.dehalo_ipa_s_device.argtypes = [P, C.c_int, u64p, u64p, sz, C.c_uint32, u64p, P]
     lib.dehalo_blind_commitments_device.argtypes = [P, C.c_int, u64p, u64p, sz, u64p, P]
     lib.dehalo_point_sum_device.argtypes = [P, C.c_int, u64p, sz, u64p, P]
     lib.dehalo_fixed_base_create.argtypes = [P, C.c_int, u64p, C.POINTER(P)]
@@ -331,6 +333,10 @@ def load_library():
     lib.dehalo_verifier_last_error.restype = C.c_char_p
     lib.dehalo_verifier_create_error.argtypes = [C.c_char_p, sz]
     lib.dehalo_verifier_last_timings.argtypes = [P, C.POINTER(C.c_double)]
+    lib.dehalo_verifier_create_ipa.argtypes = [P, P, P, PP]
+    lib.dehalo_verifier_create_ipa_vk.argtypes = [P, P, C.POINTER(CConstraintSystem), P, sz, C.c_int, u32, PP]
+    lib.dehalo_verifier_create_ipa_host.argtypes = [C.c_int, u32, u64p, u64p, u64p, u64p, C.POINTER(CConstraintSystem), P, sz, C.c_int, u32, PP]
+    lib.dehalo_ipa_verify.argtypes = [P, P, u64p, u64p, u64p, P, sz, C.POINTER(C.c_int)]
     lib.dehalo_verify_proof.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, P, sz, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.dehalo_verify_proofs.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int64)]
@@ -540,6 +546,11 @@ class Context:
         """parallel_generator_collapse: d_out[i] = g[i] + [challenge] g[length / 2 + i] (challenge = 4 x u64 Montgomery)"""
         ch = np.ascontiguousarray(challenge, dtype=np.uint64).reshape(4)
         self._check(self.lib.dehalo_generator_collapse_device(self.handle, curve, d_affine, length, ch.ctypes.data, d_out, stream or None))
+
+    def ipa_s_device(self, curve: int, d_challenges: int, d_inits: int, count: int, k: int, d_out: int, stream: int = 0):
+        """the IPA verifier's scalars over g for `count` proofs: d_out[idx] = sum_i inits[i] prod_{bit j of idx set} challenges[i][k - 1 - j], idx < 2^k
+        (GuardIPA::compute_s summed under the inits); challenges count x k and inits count scalars of 4 x u64 Montgomery, all device memory"""
+        self._check(self.lib.dehalo_ipa_s_device(self.handle, curve, d_challenges or None, d_inits or None, count, k, d_out or None, stream or None))
 
     def g_to_lagrange(self, curve: int, d_g: int, k: int, d_out: Optional[int] = None, stream: int = 0):
         """g_to_lagrange: d_out[i] = [n^-1] sum_j [omega^(-i j)] d_g[j] over 2^k affine points (64 B each, device); d_out None: in place"""

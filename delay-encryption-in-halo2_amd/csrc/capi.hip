@@ -655,6 +655,20 @@ int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t*
     return dh_device(ctx, stream, [&](hipStream_t s) { return ops->collapse(ctx, (const affine_t*)d_affine_xy, half, uc.v, (affine_t*)d_out_affine_xy, s); });
 }
 
+int dehalo_ipa_s_device(dehalo_ctx* ctx, int curve, const uint64_t* d_challenges, const uint64_t* d_inits, size_t count, uint32_t k, uint64_t* d_out, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    if (!curve_ops(curve)) return unknown_curve(ctx);
+    const IpaOps* ops = ipa_ops(curve);
+    if (!ops) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "ipa_s: Pallas and Vesta only (IPA)");
+    if (!d_challenges || !d_inits || !d_out) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_s: null argument");
+    if (k < 1 || k > 28) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_s: k out of range");
+    if (count < 1 || count >= ((size_t)1 << 24)) return dh_fail(ctx, DEHALO_ERR_INVALID, "ipa_s: count out of range");
+    return dh_device(ctx, stream, [&](hipStream_t s) -> int {
+        TRY(dh_ensure(ctx, ctx->ws_ipa_s, 32 * ipa_s_table_elems(k, count)));
+        return ops->s_vector(ctx, (const fe*)d_challenges, (const fe*)d_inits, (uint32_t)count, k, (fe*)ctx->ws_ipa_s.p, (fe*)d_out, s);
+    });
+}
+
 int dehalo_g_to_lagrange_device(dehalo_ctx* ctx, int curve, const uint64_t* d_g_affine_xy, uint32_t k, uint64_t* d_out_affine_xy, void* stream) {
     if (!ctx) return DEHALO_ERR_INVALID;
     const GfftOps* ops = gfft_ops(curve);

@@ -58,7 +58,7 @@ struct dehalo_ctx {
     std::recursive_mutex mu;   // recursive: host-buffer entry points hold it across their device-form calls
     // workspace (grow-only)
     DevBuf ws_scalars, ws_out, ws_count, ws_counters, ws_off, ws_records, ws_merge_lists, ws_merge_parts, ws_bhist, ws_pcount, ws_pairs, ws_bsum, ws_idx, ws_partial0, ws_buckets,
-        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3], ws_codec;
+        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3], ws_codec, ws_ipa_s, ws_verify[2];
     std::vector<TwiddleEntry> twiddles;
     affine_t* msm_affine_out = nullptr;   // set for the duration of dehalo_msm_device_affine (under mu): k_msm_final also writes affine points
     int msm_acc_points = 48; // > 0: the accumulation's grid is 4, 6, 8, ... layers of one wave per SIMD, the fewest that leave a lane <= this many
@@ -303,7 +303,12 @@ struct IpaOps {
     int (*slots)(dehalo_ctx* ctx, const fe* d_evals, const uint64_t coef_l[4], const uint64_t coef_r[4], const fe* d_rands, fe* d_sl, fe* d_sr, hipStream_t s);
     // pts[i] <- pts[i] + [blinds[i]] W for i < m: Jacobian points as dehalo_msm_device leaves them, blinds standard Montgomery, all on the device
     int (*blind)(dehalo_ctx* ctx, jacobian_t* d_pts, const fe* d_blinds, const affine_t* d_w, uint64_t m, hipStream_t s);
+    // the verifier's scalars over g: out[idx] = sum_i inits[i] prod_{bit j of idx} challenges[i k + k - 1 - j], idx < 2^k; d_tables: ipa_s_table_elems(k, count)
+    // elements of workspace (ipa.cuh)
+    int (*s_vector)(dehalo_ctx* ctx, const fe* d_challenges, const fe* d_inits, uint32_t count, uint32_t k, fe* d_tables, fe* d_out, hipStream_t s);
 };
+// the workspace of IpaOps::s_vector in elements, h = ceil(k / 2): count x (2^h + 2^(k - h))
+inline size_t ipa_s_table_elems(uint32_t k, size_t count) { const uint32_t h = (k + 1) / 2; return count * (((size_t)1 << h) + ((size_t)1 << (k - h))); }
 const IpaOps& pallas_ipa_ops();
 const IpaOps& vesta_ipa_ops();
 const IpaOps* ipa_ops(int curve);       // capi.hip: null unless Pallas / Vesta

@@ -162,7 +162,73 @@ int ipa_slots_t(dehalo_ctx* ctx, const fe* d_evals, const uint64_t coef_l[4], co
     return 0;
 }
 
+// The verifier's scalar vector over g [UPSTREAM halo2_proofs/src/poly/ipa/strategy.rs @ v2023_04_20: GuardIPA::compute_s, and the accumulation of the
+// guards' s vectors under random weights]: for `count` proofs with round challenges u_{i, 0 .. k} and one scalar init_i each,
+//     out[idx] = sum_i init_i prod_{j < k, bit j of idx set} u_{i, k - 1 - j},    idx < 2^k.
+// With idx = hi 2^h + lo, h = ceil(k / 2), a term is  (init_i H_i[hi]) L_i[lo]:  k_ipa_s_tables writes, per proof, the 2^h low products and the 2^(k - h)
+// high products (those carry init_i), every entry as the product over its own set bits (at most h multiplications an entry; the tables are
+// count x (2^h + 2^(k - h)) entries, a 2^-(k / 2) fraction of the second pass), and k_ipa_s_sum spends ONE multiplication per proof and output: the
+// high entry -- one address per wave once 2^h >= 64 -- times the low entry, read coalesced.  The high table is kept in the multiplier's internal form
+// (x 2^261, canonical, packed), the low table in the standard form, so that their product is the standard form of the term as it stands (the trick of
+// k_lincomb, poly.cuh); the sum is brought below 16 p every 8 terms and leaves canonical.  Field type and multiplier are poly.cuh's (f29 over the curve's
+// scalar field, product scanning).  No LDS beyond the k converted challenges, no scratch memory.
+#define IPA_S_THREADS 256
+#define IPA_S_MAX_K 28
+template <class CV>
+__global__ __launch_bounds__(IPA_S_THREADS) void k_ipa_s_tables(const fe* __restrict__ challenges, const fe* __restrict__ inits, u32 k, u32 h, u32 blocks_per_proof, fe* lo_tab,
+                                                                    fe* hi_tab) {
+    typedef typename f29_of<typename CV::Scalar>::type F9;
+    __shared__ f29 us[IPA_S_MAX_K];      // us[j] = the challenge bit j of an index selects: u_{i, k - 1 - j}
+    const u32 proof = blockIdx.x / blocks_per_proof, t = threadIdx.x;
+    if (t < k) us[t] = f29_from_std<F9>(f_load(&challenges[(u64)proof * k + (k - 1 - t)]));
+    __syncthreads();
+    const u32 n_lo = 1u << h, n_hi = 1u << (k - h);
+    const u32 e = (blockIdx.x % blocks_per_proof) * IPA_S_THREADS + t;      // entry of [low table | high table]
+    if (e >= n_lo + n_hi) return;
+    const bool high = e >= n_lo;
+    const u32 bits = high ? e - n_lo : e, first = high ? h : 0, nbits = high ? k - h : h;
+    f29 acc = high ? f29_from_std<F9>(f_load(&inits[proof])) : f29_one<F9>();      // < 2p; every product below is < 4 p^2 / 2^261 + p < 2p
+    for (u32 j = 0; j < nbits; j++)
+        if ((bits >> j) & 1u) acc = f29_mul<F9>(acc, us[first + j]);
+    if (high) f_store(&hi_tab[(u64)proof * n_hi + bits], f29_to_packed_canon<F9>(acc));
+    else f_store(&lo_tab[(u64)proof * n_lo + bits], f29_to_std<F9>(acc));
+}
+
+template <class CV>
+__global__ __launch_bounds__(IPA_S_THREADS) void k_ipa_s_sum(const fe* __restrict__ lo_tab, const fe* __restrict__ hi_tab, u32 count, u32 k, u32 h, fe* out) {
+    typedef typename f29_of<typename CV::Scalar>::type F9;
+    const u64 idx = (u64)blockIdx.x * IPA_S_THREADS + threadIdx.x;
+    if (idx >= ((u64)1 << k)) return;
+    const u32 n_lo = 1u << h, n_hi = 1u << (k - h);
+    const fe* lo = lo_tab + (idx & (n_lo - 1));
+    const fe* hi = hi_tab + (idx >> h);
+    f29 acc = f29_zero();
+    for (u32 i = 0; i < count; i++) {
+        // (x 2^261, < p) (y 2^256, < p) / 2^261 + p: the term's standard form, < 1.04 p
+        const f29 term = f29_mul<F9>(f29_unpack(f_load(&hi[(u64)i * n_hi])), f29_unpack(f_load(&lo[(u64)i * n_lo])));
+        acc = f29_norm(f29_add(acc, term));
+        if ((i & 7u) == 7u) acc = f29_canon<F9>(acc);      // < p + 8 x 1.04 p < 16 p
+    }
+    f_store(&out[idx], f29_pack(f29_canon<F9>(acc)));
+}
+
+// d_tables: ipa_s_table_elems(k, count) elements of workspace (internal.hpp): [every proof's low table | every proof's high table]
+inline uint32_t ipa_s_split(uint32_t k) { return (k + 1) / 2; }
+template <class CV>
+int ipa_s_t(dehalo_ctx* ctx, const fe* d_challenges, const fe* d_inits, uint32_t count, uint32_t k, fe* d_tables, fe* d_out, hipStream_t s) {
+    const uint32_t h = ipa_s_split(k);
+    const size_t n_lo = (size_t)1 << h, n_hi = (size_t)1 << (k - h);
+    fe* lo_tab = d_tables;
+    fe* hi_tab = d_tables + count * n_lo;
+    const u32 blocks_per_proof = (u32)((n_lo + n_hi + IPA_S_THREADS - 1) / IPA_S_THREADS);      // <= 128; count < 2^24 (the caller's check)
+    k_ipa_s_tables<CV><<<blocks_per_proof * count, IPA_S_THREADS, 0, s>>>(d_challenges, d_inits, k, h, blocks_per_proof, lo_tab, hi_tab);
+    HIP_TRY(ctx, hipGetLastError());
+    k_ipa_s_sum<CV><<<(u32)((((size_t)1 << k) + IPA_S_THREADS - 1) / IPA_S_THREADS), IPA_S_THREADS, 0, s>>>(lo_tab, hi_tab, count, k, h, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return 0;
+}
+
 template <class CV>
 constexpr IpaOps make_ipa_ops() {
-    return {&ipa_collapse_t<CV>, &ipa_slots_t<CV>, &ipa_blind_t<CV>};
+    return {&ipa_collapse_t<CV>, &ipa_slots_t<CV>, &ipa_blind_t<CV>, &ipa_s_t<CV>};
 }

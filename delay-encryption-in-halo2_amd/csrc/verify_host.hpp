@@ -10,7 +10,12 @@
 // OpeningPlan's (opening_plan.hpp): prover and verifier cannot disagree about layout.
 // The points of a proof stand at offsets its shape fixes; they are decompressed before the walk by a backend -- the host's below, or the device's (verify.hip:
 // one dehalo_points_decompress_device launch for all proofs of a call) -- and the two sums go through the backend's MSM.  The pairing is pairing_host.hpp's.
-// Host only, no HIP header: verify.hip includes it, and tests/native_host/verify_host_check.cpp drives it on the CPU under ASan + UBSan.
+// IPA over Pallas / Vesta [UPSTREAM plonk/verifier.rs with QUERY_INSTANCE = true, poly/ipa/multiopen/verifier.rs, poly/ipa/commitment/verifier.rs, poly/ipa/strategy.rs] is
+// a second reduction behind the same walk: the instance columns enter as commitments (the backend's instance_commitments), the multiopen and the opening argument
+// (ipa_reduce_opening) leave ONE term list over the proof's points, the key's and the instance commitments, g[0], U and W, plus per proof k round challenges and
+// init = -w c; accept iff  (sum over the list) + sum_idx s[idx] g[idx]  is the identity, s = sum_i compute_s(u_i, init_i) (the backend's g_sum: on the device the
+// kernel of ipa.cuh into the MSM over the params' resident g).
+// Host only, no HIP header: verify.hip includes it, and tests/native_host/verify_host_check.cpp and verify_ipa_host_check.cpp drive it on the CPU under ASan + UBSan.
 #pragma once
 #include <chrono>
 #include <string>
@@ -25,6 +30,9 @@
 #include "plonk_host.hpp"
 #include "transcript_host.hpp"
 
+// Blind::default() of the instance columns' commitments (whole_call.hpp IPA_DEFAULT_BLIND is the prover's twin; this header includes no HIP header)
+constexpr uint64_t VERIFY_IPA_DEFAULT_BLIND = 1;
+
 // ---- what decompresses a call's points and sums its two term lists: the host (below) or the device (verify.hip).  A non-zero return is an error of the
 // backend (a device error stays an error: nothing falls back to the host)
 struct VerifyBackend {
@@ -33,11 +41,46 @@ struct VerifyBackend {
     virtual int decompress(const uint8_t* in32, size_t count, uint64_t* xy) = 0;
     // sum_i [scalars_i] xy_i -> one affine point ((0, 0): the identity); scalars Montgomery, canonical words
     virtual int msm(const Fe* scalars, const uint64_t* xy, size_t len, uint64_t out_affine[8]) = 0;
+    // IPA only (a backend without ParamsIPA's points refuses both).  commit_lagrange(column, Blind::default()) of `count` instance columns in one batch: column i
+    // has lens[i] values (Montgomery, canonical), zero from there on -> count x {x, y}
+    virtual int instance_commitments(const Fe* const*, const size_t*, size_t, uint64_t*) { return DEHALO_ERR_UNSUPPORTED; }
+    // sum_idx s[idx] g[idx] over the params' 2^k generators, s = sum_i compute_s(challenges[i k .. i k + k), inits[i]) (GuardIPA::compute_s under the inits) -> one
+    // affine point
+    virtual int g_sum(const Fe*, const Fe*, size_t, uint32_t, uint64_t[8]) { return DEHALO_ERR_UNSUPPORTED; }
 };
+// compute_s of one proof added into s (2^k scalars): s[idx] += init prod_{bit j of idx set} us[k - 1 - j]
+inline void ipa_add_s(const HostField* f, const Fe* us, uint32_t k, const Fe& init, std::vector<Fe>& s) {
+    std::vector<Fe> v((size_t)1 << k);
+    v[0] = init;
+    for (uint32_t j = 0; j < k; j++)
+        for (size_t t = 0; t < ((size_t)1 << j); t++) v[((size_t)1 << j) + t] = f->mul(v[t], us[k - 1 - j]);
+    for (size_t i = 0; i < v.size(); i++) s[i] = f->add(s[i], v[i]);
+}
 struct HostVerifyBackend : VerifyBackend {
     const HostField* fr;
     G1Host g1;
+    // ParamsIPA's points, borrowed (set_ipa): g and g_lagrange 2^k affine points each, w one
+    const uint64_t *g = nullptr, *g_lagrange = nullptr, *w = nullptr;
+    uint32_t k = 0;
     HostVerifyBackend(const HostField* fq, const HostField* fr_, uint64_t curve_b) : fr(fr_), g1(fq, curve_b) {}
+    void set_ipa(const uint64_t* g_, const uint64_t* g_lagrange_, const uint64_t* w_, uint32_t k_) { g = g_; g_lagrange = g_lagrange_; w = w_; k = k_; }
+    int instance_commitments(const Fe* const* cols, const size_t* lens, size_t count, uint64_t* xy) override {
+        if (!g_lagrange) return DEHALO_ERR_UNSUPPORTED;
+        for (size_t i = 0; i < count; i++) {      // a short MSM over g_lagrange[0 .. len) and [Blind::default()] W
+            std::vector<Fe> sc(cols[i], cols[i] + lens[i]);
+            std::vector<uint64_t> bs(g_lagrange, g_lagrange + 8 * lens[i]);
+            sc.push_back(fr->from_u64(VERIFY_IPA_DEFAULT_BLIND));
+            bs.insert(bs.end(), w, w + 8);
+            msm(sc.data(), bs.data(), sc.size(), xy + 8 * i);
+        }
+        return 0;
+    }
+    int g_sum(const Fe* challenges, const Fe* inits, size_t count, uint32_t k_, uint64_t out_affine[8]) override {
+        if (!g || k_ != k) return DEHALO_ERR_UNSUPPORTED;
+        std::vector<Fe> s((size_t)1 << k, Fe{});
+        for (size_t i = 0; i < count; i++) ipa_add_s(fr, challenges + i * k, k, inits[i], s);
+        return msm(s.data(), g, s.size(), out_affine);
+    }
     int decompress(const uint8_t* in32, size_t count, uint64_t* xy) override {
         for (size_t i = 0; i < count; i++) g1.decompress(in32 + 32 * i, xy + 8 * i);
         return 0;
@@ -51,7 +94,7 @@ struct HostVerifyBackend : VerifyBackend {
 };
 
 // where a call's time went, in milliseconds (dehalo_verifier_last_timings)
-struct VerifyStats { double decompress = 0, walk = 0, msm = 0, pairing = 0; };
+struct VerifyStats { double decompress = 0, walk = 0, msm = 0, pairing = 0; };      // (pairing: under IPA the sum over g)
 
 // ---- the verifying half of a key, and of the params: all a verifier keeps
 struct VerifierKey {
@@ -66,6 +109,8 @@ struct VerifierKey {
     uint64_t g0[8] = {};
     uint8_t g2[128] = {}, s_g2[128] = {};
     int multiopen = DEHALO_MULTIOPEN_GWC;
+    int scheme = DEHALO_SCHEME_KZG;      // DEHALO_SCHEME_IPA: the instance columns are committed and queried, the multiopen is the IPA's; g0 = g[0], and u, w below
+    uint64_t u[8] = {}, w[8] = {};
     bool unsupported = false;      // init_cs: the message describes a circuit this library does not take
 
     KeyShape shape() const {
@@ -131,7 +176,7 @@ struct VerifierKey {
         OpeningShape sh;
         sh.k = k; sh.A = cs.num_advice; sh.num_fixed = cs.num_fixed; sh.I = cs.num_instance; sh.L = (uint32_t)cs.lookups.size(); sh.S = cs.num_sets();
         sh.npc = (uint32_t)cs.perm_cols.size(); sh.bf = cs.blinding_factors(); sh.pieces = dom.quotient_poly_degree;
-        sh.query_instance = false;
+        sh.query_instance = scheme == DEHALO_SCHEME_IPA;
         sh.circuits = circuits;
         sh.shuffles = (uint32_t)cs.shuffles.size();
         for (auto& q : cs.advice_q) sh.advice_q.push_back({q.index, q.rotation});
@@ -142,9 +187,12 @@ struct VerifierKey {
 };
 
 // ---- the two term lists of a call, every proof's appended under its weight
+// (IPA has one list, the right one, over the proof's points, the key's and the instance commitments, g[0], U and W; what goes over the params' g is kept as
+// each proof's k round challenges and its init = -w c: the backend's g_sum makes the 2^k scalars from them)
 struct VerifyTerms {
     std::vector<Fe> ls, rs;
     std::vector<uint64_t> lp, rp;      // 8 u64 a point
+    std::vector<Fe> us, inits;         // IPA: k challenges and one init a proof
     void left(const Fe& s, const uint64_t* p) { ls.push_back(s); lp.insert(lp.end(), p, p + 8); }
     void right(const Fe& s, const uint64_t* p) { rs.push_back(s); rp.insert(rp.end(), p, p + 8); }
 };
@@ -152,12 +200,78 @@ struct VerifyTerms {
 // the points of one proof: [every commitment before the evaluations | the multiopen's], in the order of the bytes
 inline size_t verify_points_before_evals(const OpeningPlan& pl) { return (size_t)pl.NC + pl.p_instance - pl.p_hpiece; }
 inline size_t verify_multiopen_points(const OpeningPlan& pl, int multiopen) { return multiopen == DEHALO_MULTIOPEN_SHPLONK ? 2 : pl.groups.size(); }
+// where the points of a proof stand, in the order of the bytes: (byte offset, count) runs.  KZG: the commitments, then the multiopen's at the end; IPA: the
+// commitments, f behind the evaluations, then S and the k rounds' (L_j, R_j) behind the q evaluations
+inline std::vector<std::pair<size_t, size_t>> verify_point_runs(const OpeningPlan& pl, int scheme, int multiopen) {
+    const size_t p0 = verify_points_before_evals(pl);
+    if (scheme != DEHALO_SCHEME_IPA) {
+        const size_t p1 = verify_multiopen_points(pl, multiopen);
+        return {{0, p0}, {pl.proof_size(multiopen == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC) - 32 * p1, p1}};
+    }
+    const size_t off_f = 32 * (p0 + pl.instance_write.size() + pl.write.size()), off_s = off_f + 32 * (1 + pl.point_sets.size());
+    return {{0, p0}, {off_f, 1}, {off_s, 1 + 2 * (size_t)pl.k}};
+}
+
+// a + b = the identity, for two affine points ((0, 0): the identity): the IPA verifier's acceptance, on the host
+inline bool ipa_sums_cancel(const HostField* fq, const uint64_t a[8], const uint64_t b[8]) {
+    Fe by;
+    memcpy(by.v, b + 4, 32);
+    by = fq->neg(by);      // -(x, y) = (x, -y); (0, 0) stays the identity
+    return memcmp(a, b, 32) == 0 && memcmp(a + 4, by.v, 32) == 0;
+}
+
+// what a walk makes of one proof
+enum VerifyWalkResult { VERIFY_WALK_OK = 0, VERIFY_WALK_MALFORMED = 1, VERIFY_WALK_OPENING = 2 };
+
+// The IPA opening argument's check [UPSTREAM poly/ipa/commitment/verifier.rs verify_proof, poly/ipa/strategy.rs GuardIPA] on the rest of transcript t, for a commitment
+// P whose terms the caller has appended to `out` under `weight` already:  w (P - [v] G_0 + [xi] S + sum_j ([u_j^-1] L_j + [u_j] R_j) - [c b z] U - [f] W) goes to
+// out's right list, the k challenges and init = -w c to out.us / out.inits (the sum over g, - w c <s, G>, is the backend's g_sum).  point(): the next 32 bytes as
+// a point, absorbed; null when they are none.  The one routine behind a whole proof's last step and dehalo_ipa_verify.
+template <class NextPoint>
+inline VerifyWalkResult ipa_reduce_opening(const HostField* f, dehalo_transcript& t, NextPoint&& point, uint32_t k, const Fe& weight, const Fe& x3, const Fe& v,
+                                           const uint64_t* g0, const uint64_t* U, const uint64_t* W, VerifyTerms& out) {
+    const uint64_t* S = point();
+    if (!S) return VERIFY_WALK_MALFORMED;
+    const Fe xi = t.squeeze(), z = t.squeeze();
+    std::vector<const uint64_t*> Ls(k), Rs(k);
+    std::vector<Fe> us(k);
+    for (uint32_t j = 0; j < k; j++) {
+        Ls[j] = point();
+        Rs[j] = Ls[j] ? point() : nullptr;
+        if (!Rs[j]) return VERIFY_WALK_MALFORMED;
+        us[j] = t.squeeze();
+    }
+    Fe c, fv;
+    if (!t.read_scalar(c) || !t.read_scalar(fv) || t.remaining()) return VERIFY_WALK_MALFORMED;
+    std::vector<Fe> inv = us;
+    if (!f->batch_invert(inv.data(), inv.size())) return VERIFY_WALK_OPENING;      // a round challenge is zero
+    Fe b = f->one, cur = x3;      // compute_b: prod_j (1 + u_{k - j} x3^(2^j))
+    for (uint32_t j = k; j-- > 0;) {
+        b = f->mul(b, f->add(f->one, f->mul(us[j], cur)));
+        cur = f->sqr(cur);
+    }
+    out.right(f->mul(weight, xi), S);
+    for (uint32_t j = 0; j < k; j++) {
+        out.right(f->mul(weight, inv[j]), Ls[j]);
+        out.right(f->mul(weight, us[j]), Rs[j]);
+    }
+    const Fe wc = f->mul(weight, c);
+    out.right(f->neg(f->mul(wc, f->mul(b, z))), U);
+    out.right(f->neg(f->mul(weight, fv)), W);
+    out.right(f->neg(f->mul(weight, v)), g0);      // what verify_opening subtracts from s[0]
+    out.us.insert(out.us.end(), us.begin(), us.end());
+    out.inits.push_back(f->neg(wc));
+    return VERIFY_WALK_OK;
+}
 
 // One proof whose length is the shape's and whose points are decoded (none refused): the transcript walk, expected_h and the reduction of the multiopen, appended
-// to `out` under `weight`.  false: a scalar is not below r (the proof is MALFORMED); nothing of `out` is then meaningful.
+// to `out` under `weight`.  MALFORMED: a scalar is not below r; OPENING (IPA): x_3 is an opening point, a round challenge is zero or an instance commitment is the
+// identity; nothing of `out` is then meaningful.  One walk for the three schemes: the key's scheme decides how the instance columns enter (KZG: their values, as
+// scalars, interpolated here; IPA: their commitments instance_cm -- 8 u64 a column -- as points, their evaluations read first) and which reduction the queries go to.
 // instances: [circuit][column] -> values (Montgomery, canonical).
-inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N, const uint8_t* proof, size_t len, const uint64_t* pts,
-                        const std::vector<std::vector<std::vector<Fe>>>& instances, const Fe& weight, VerifyTerms& out) {
+inline VerifyWalkResult verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N, const uint8_t* proof, size_t len, const uint64_t* pts,
+                                    const std::vector<std::vector<std::vector<Fe>>>& instances, const uint64_t* instance_cm, const Fe& weight, VerifyTerms& out) {
+    const bool ipa = vk.scheme == DEHALO_SCHEME_IPA;
     const HostField* f = vk.f;
     const HostCS& cs = vk.cs;
     const HostDomain& d = vk.dom;
@@ -175,9 +289,15 @@ inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N
     };
     std::vector<const uint64_t*> cm(pl.num_polys, nullptr);      // polynomial id -> its commitment
     t.common_scalar(vk.transcript_repr);
-    for (auto& circuit : instances)
-        for (auto& column : circuit)
-            for (const Fe& v : column) t.common_scalar(v);
+    if (ipa) {
+        for (uint32_t i = 0; i < cs.num_instance; i++) {
+            if (!t.write_point(instance_cm + 8 * i, false)) return VERIFY_WALK_OPENING;
+            cm[pl.p_instance + i] = instance_cm + 8 * i;
+        }
+    } else
+        for (auto& circuit : instances)
+            for (auto& column : circuit)
+                for (const Fe& v : column) t.common_scalar(v);
     std::vector<Fe> challenges(cs.challenge_phase.size(), zero);
     for (uint32_t ph = 0; ph < cs.num_phases; ph++) {
         for (uint32_t c = 0; c < N; c++)
@@ -200,8 +320,10 @@ inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N
     for (uint32_t i = 0; i < cs.num_fixed; i++) cm[pl.p_fixed + i] = &vk.fixed_commitments[8 * i];
     for (size_t j = 0; j < cs.perm_cols.size(); j++) cm[pl.p_sigma + j] = &vk.perm_commitments[8 * j];
     std::vector<Fe> E(pl.eval_count, zero);
+    for (int64_t slot : pl.instance_write)      // (none unless the instance columns are queried)
+        if (!t.read_scalar(E[(size_t)slot])) return VERIFY_WALK_MALFORMED;
     for (int64_t slot : pl.write)
-        if (!t.read_scalar(E[(size_t)slot])) return false;
+        if (!t.read_scalar(E[(size_t)slot])) return VERIFY_WALK_MALFORMED;
 
     // ---- expected_h
     Fe xn = x;
@@ -221,7 +343,8 @@ inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N
     auto ev = [&](uint32_t poly, int32_t rot) -> const Fe& { return E[(size_t)pl.slot(poly, rot)]; };
     Fe expected_h = zero;
     for (uint32_t c = 0; c < N; c++) {
-        auto instance_eval = [&](uint32_t col, int32_t rot) {      // QUERY_INSTANCE = false: interpolated from the values
+        auto instance_eval = [&](uint32_t col, int32_t rot) -> Fe {      // QUERY_INSTANCE = false: interpolated from the values; true (IPA): read
+            if (ipa) return ev(pl.p_instance + col, rot);
             Fe acc = zero;
             const std::vector<Fe>& vals = instances[c][col];
             for (size_t j = 0; j < vals.size(); j++)
@@ -301,6 +424,52 @@ inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N
         }
     };
 
+    if (ipa) {      // VerifierIPA::verify_proof over the plan's intermediate sets, then the opening argument's check of the final commitment P
+        const Fe x1 = t.squeeze(), x2 = t.squeeze();
+        const uint64_t* f_commitment = point();
+        const Fe x3 = t.squeeze();
+        const size_t ns = pl.point_sets.size();
+        std::vector<Fe> q_evals(ns);
+        for (Fe& e : q_evals)
+            if (!t.read_scalar(e)) return VERIFY_WALK_MALFORMED;
+        std::vector<Fe> super;
+        for (int32_t r : pl.point_rot) super.push_back(d.rotate_omega(x, r));
+        // per set: the x_1-folded evaluations at its points, their interpolant's value at x_3, and (q_eval - that) / prod (x_3 - point), folded with x_2
+        Fe f_eval = zero;
+        for (size_t si = 0; si < ns; si++) {
+            const std::vector<uint32_t>& T = pl.point_sets[si];
+            std::vector<Fe> evs(T.size(), zero);
+            for (uint32_t ci : pl.set_members[si])
+                for (size_t a = 0; a < T.size(); a++) evs[a] = f->add(f->mul(evs[a], x1), eval_of(pl.commitments[ci].evals[a]));
+            Fe r = zero, den_all = one;
+            for (size_t a = 0; a < T.size(); a++) {
+                Fe num = one, den = one;
+                for (size_t b = 0; b < T.size(); b++)
+                    if (b != a) { num = f->mul(num, f->sub(x3, super[T[b]])); den = f->mul(den, f->sub(super[T[a]], super[T[b]])); }
+                r = f->add(r, f->mul(evs[a], f->mul(num, f->invert(den))));
+                const Fe diff = f->sub(x3, super[T[a]]);
+                if (diff.is_zero()) return VERIFY_WALK_OPENING;
+                den_all = f->mul(den_all, diff);
+            }
+            f_eval = f->add(f->mul(f_eval, x2), f->mul(f->sub(q_evals[si], r), f->invert(den_all)));
+        }
+        const Fe x4 = t.squeeze();
+        // P = x_4^ns f + sum_si x_4^(ns - 1 - si) q_si,  q_si = sum_m x_1^(M - 1 - m) C_m: never formed, its scalars go to the commitments; v likewise
+        std::vector<Fe> x4p(ns + 1, weight);      // weight x_4^i
+        for (size_t i = 1; i <= ns; i++) x4p[i] = f->mul(x4p[i - 1], x4);
+        out.right(x4p[ns], f_commitment);
+        Fe v = f_eval;
+        for (size_t si = 0; si < ns; si++) {
+            const std::vector<uint32_t>& M = pl.set_members[si];
+            Fe coef = x4p[ns - 1 - si];
+            for (size_t m = M.size(); m-- > 0;) {
+                commitment_term(coef, pl.commitments[M[m]].poly);
+                coef = f->mul(coef, x1);
+            }
+            v = f->add(f->mul(v, x4), q_evals[si]);
+        }
+        return ipa_reduce_opening(f, t, point, pl.k, weight, x3, v, vk.g0, vk.u, vk.w, out);
+    }
     if (vk.multiopen != DEHALO_MULTIOPEN_SHPLONK) {      // VerifierGWC::verify_proof
         const Fe v = t.squeeze();
         std::vector<const uint64_t*> W;
@@ -320,7 +489,7 @@ inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N
             pu = f->mul(pu, u);
         }
         out.right(f->neg(eval_multi), vk.g0);
-        return true;
+        return VERIFY_WALK_OK;
     }
     // VerifierSHPLONK::verify_proof over the plan's intermediate sets
     const Fe y_ = t.squeeze(), v = t.squeeze();
@@ -371,7 +540,7 @@ inline bool verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N
     out.right(f->neg(f->mul(weight, z_0)), h);
     out.right(f->mul(weight, u), h2);
     out.left(weight, h2);
-    return true;
+    return VERIFY_WALK_OK;
 }
 
 // `count` proofs under one key: *accept = 1 iff every proof is readable and  e(sum_i w_i L_i, s_g2) e(-sum_i w_i R_i, g2) = 1.  *first_malformed: the first
@@ -408,9 +577,12 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const ui
     const int bad = verify_check_arguments(vk, proofs, lens, count, instances, instance_lens, num_instance_columns, N, error);
     if (bad) return bad;
     const OpeningPlan pl(vk.opening_shape(N));
+    const bool ipa = vk.scheme == DEHALO_SCHEME_IPA;
     const int mo = vk.multiopen == DEHALO_MULTIOPEN_SHPLONK ? DEHALO_MULTIOPEN_SHPLONK : DEHALO_MULTIOPEN_GWC;
-    const size_t size = pl.proof_size(mo == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC);
-    const size_t p0 = verify_points_before_evals(pl), p1 = verify_multiopen_points(pl, mo), np = p0 + p1, off1 = size - 32 * p1;
+    const size_t size = pl.proof_size(ipa ? OpeningPlan::IPA : mo == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC);
+    const std::vector<std::pair<size_t, size_t>> runs = verify_point_runs(pl, vk.scheme, mo);
+    size_t np = 0;
+    for (auto& r : runs) np += r.second;
     if (first_malformed) *first_malformed = -1;
     if (reason) *reason = DEHALO_REJECT_NONE;
     *accept = 0;
@@ -424,8 +596,7 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const ui
     for (uint32_t i = 0; i < count; i++) {
         if (lens[i] != size || !proofs[i]) { malformed[i] = 1; continue; }      // bytes missing or trailing
         slot_of[i] = sized++;
-        enc.insert(enc.end(), proofs[i], proofs[i] + 32 * p0);
-        enc.insert(enc.end(), proofs[i] + off1, proofs[i] + size);
+        for (auto& r : runs) enc.insert(enc.end(), proofs[i] + r.first, proofs[i] + r.first + 32 * r.second);
     }
     std::vector<uint64_t> xy(8 * np * sized + 8);
     clk::time_point t0 = clk::now();
@@ -435,9 +606,37 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const ui
     }
     st.decompress = ms(t0);
 
+    // ---- the instance columns' values; under IPA their commitments, every column of every proof in one batch of the backend
+    const uint32_t nic = num_instance_columns;
+    std::vector<std::vector<std::vector<std::vector<Fe>>>> inst_of(count);
+    for (uint32_t i = 0; i < count; i++) {
+        if (malformed[i]) continue;
+        inst_of[i].assign(N, std::vector<std::vector<Fe>>(nic));
+        for (uint32_t c = 0; c < N; c++)
+            for (uint32_t j = 0; j < nic; j++) {
+                const size_t e = ((size_t)i * N + c) * nic + j;
+                inst_of[i][c][j].resize(instance_lens[e]);
+                for (size_t r = 0; r < instance_lens[e]; r++) {
+                    Fe w;
+                    memcpy(w.v, instances[e] + 4 * r, 32);
+                    inst_of[i][c][j][r] = f->mul(w, f->one);      // a word stands for its residue
+                }
+            }
+    }
+    std::vector<uint64_t> inst_cm(8 * (size_t)sized * nic + 8);
+    if (ipa && sized && nic) {      // (N = 1: the plan refuses more)
+        std::vector<const Fe*> cols;
+        std::vector<size_t> col_lens;
+        for (uint32_t i = 0; i < count; i++)
+            for (uint32_t j = 0; j < nic && !malformed[i]; j++) { cols.push_back(inst_of[i][0][j].data()); col_lens.push_back(inst_of[i][0][j].size()); }
+        const int rc = be.instance_commitments(cols.data(), col_lens.data(), cols.size(), inst_cm.data());
+        if (rc) return fail(rc, "verify_proofs: the instance columns' commitments failed");
+    }
+
     // ---- the walks
     t0 = clk::now();
     VerifyTerms terms;
+    bool opening_rejected = false;
     for (uint32_t i = 0; i < count; i++) {
         if (malformed[i]) continue;
         const uint64_t* pts = xy.data() + 8 * np * slot_of[i];
@@ -447,18 +646,9 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const ui
             if (zero) malformed[i] = 1;      // refused by the decoder, or the identity
         }
         if (malformed[i]) continue;
-        std::vector<std::vector<std::vector<Fe>>> inst(N, std::vector<std::vector<Fe>>(num_instance_columns));
-        for (uint32_t c = 0; c < N; c++)
-            for (uint32_t j = 0; j < num_instance_columns; j++) {
-                const size_t e = ((size_t)i * N + c) * num_instance_columns + j;
-                inst[c][j].resize(instance_lens[e]);
-                for (size_t r = 0; r < instance_lens[e]; r++) {
-                    Fe w;
-                    memcpy(w.v, instances[e] + 4 * r, 32);
-                    inst[c][j][r] = f->mul(w, f->one);      // a word stands for its residue
-                }
-            }
-        if (!verify_walk(vk, pl, N, proofs[i], lens[i], pts, inst, f->mul(weights[i], f->one), terms)) malformed[i] = 1;
+        const VerifyWalkResult wr = verify_walk(vk, pl, N, proofs[i], lens[i], pts, inst_of[i], inst_cm.data() + 8 * slot_of[i] * nic, f->mul(weights[i], f->one), terms);
+        if (wr == VERIFY_WALK_MALFORMED) malformed[i] = 1;
+        if (wr == VERIFY_WALK_OPENING) opening_rejected = true;
     }
     st.walk = ms(t0);
     for (uint32_t i = 0; i < count; i++)
@@ -468,6 +658,32 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const ui
             if (stats) *stats = st;
             return 0;
         }
+
+    if (opening_rejected) {      // readable, and no proof: x_3 at an opening point, a zero round challenge
+        if (reason) *reason = DEHALO_REJECT_OPENING;
+        if (stats) *stats = st;
+        return 0;
+    }
+    if (ipa) {      // ---- accept iff  sum over the fresh bases + sum over g = the identity: two affine results, compared here
+        t0 = clk::now();
+        uint64_t fresh[8] = {}, gs[8] = {};
+        if (count) {
+            const int rc = be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), fresh);
+            if (rc) return fail(rc, "verify_proofs: the multi-scalar multiplication failed");
+        }
+        st.msm = ms(t0);
+        t0 = clk::now();
+        if (count) {
+            const int rc = be.g_sum(terms.us.data(), terms.inits.data(), count, pl.k, gs);
+            if (rc) return fail(rc, "verify_proofs: the sum over g failed");
+        }
+        st.pairing = ms(t0);
+        const bool is_identity = ipa_sums_cancel(vk.fq, fresh, gs);
+        *accept = is_identity ? 1 : 0;
+        if (reason && !is_identity) *reason = DEHALO_REJECT_OPENING;
+        if (stats) *stats = st;
+        return 0;
+    }
 
     // ---- the two sums and the pairing check
     t0 = clk::now();

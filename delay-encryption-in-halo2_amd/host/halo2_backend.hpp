@@ -555,10 +555,17 @@ class Verifier {
         }
         check(dehalo_verifier_set_multiopen(v_, m));
     }
+    // IPA (Pallas / Vesta): from a ParamsIPA and a key made under it.  The params are borrowed: they must outlive the verifier.  One multiopen: none to choose
+    Verifier(const Backend& be, const ParamsIPAHandle& params, const ProvingKey& pk) { be.check(dehalo_verifier_create_ipa(be.raw(), params.raw(), pk.raw(), &v_)); }
+    // IPA, the verifier's side: ParamsIPA::read + VerifyingKey::read, the vk in any format
+    Verifier(const Backend& be, const ParamsIPAHandle& params, ConstraintSystem& cs, const std::vector<uint8_t>& vk_bytes, dehalo_serde_format vk_format,
+             uint32_t num_selectors) {
+        be.check(dehalo_verifier_create_ipa_vk(be.raw(), params.raw(), cs.descriptor(), vk_bytes.data(), vk_bytes.size(), vk_format, num_selectors, &v_));
+    }
     ~Verifier() { dehalo_verifier_release(v_); }
     Verifier(const Verifier&) = delete;
     void set_transcript_repr(const Fe& r) { check(dehalo_verifier_set_transcript_repr(v_, r.data())); }
-    // true: accepted.  false: *reason (if given) says why -- DEHALO_REJECT_MALFORMED or DEHALO_REJECT_PAIRING.  instances: one vector per instance column
+    // true: accepted.  false: *reason (if given) says why -- DEHALO_REJECT_MALFORMED, DEHALO_REJECT_PAIRING or (IPA) DEHALO_REJECT_OPENING.  instances: one vector per instance column
     bool verify(const std::vector<uint8_t>& proof, const std::vector<std::vector<Fe>>& instances, int* reason = nullptr) const {
         std::vector<const uint64_t*> ip;
         std::vector<size_t> il;

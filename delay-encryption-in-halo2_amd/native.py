@@ -572,7 +572,7 @@ def rng_struct(rng) -> Optional[CRng]:
     return r
 
 
-REJECT_NONE, REJECT_MALFORMED, REJECT_PAIRING = 0, 1, 2      # dehalo_reject_reason
+REJECT_NONE, REJECT_MALFORMED, REJECT_PAIRING, REJECT_OPENING = 0, 1, 2, 3      # dehalo_reject_reason
 
 
 def _create_error() -> str:
@@ -583,17 +583,20 @@ def _create_error() -> str:
 
 
 class Verifier:
-    """dehalo_verifier: verify_proof for KZG (GWC and SHPLONK), one proof or a batch.  It holds the verifying half of the params and of the key only.
+    """dehalo_verifier: verify_proof for KZG (GWC and SHPLONK) and for IPA over Pallas / Vesta (from_ipa, from_ipa_vk, from_ipa_host), one proof or a batch.  It holds the verifying half of the params and of the key only.
     With a Context the proofs' points are decompressed and the two sums of the reduction are formed on the device; with ctx=None it is a HOST verifier -- a mode
     the caller chooses (machines without a GPU), never a fallback.  The pairing check runs on the host in both."""
 
     MULTIOPEN = {"gwc": 0, "shplonk": 1}      # dehalo_multiopen
 
-    def __init__(self, ctx: Optional[Context], curve: CurveSpec, handle, multiopen: str = "gwc"):
+    def __init__(self, ctx: Optional[Context], curve: CurveSpec, handle, multiopen: Optional[str] = "gwc"):
         self.ctx, self.curve, self.handle = ctx, curve, handle
         self.last_reject = REJECT_NONE          # why the last verify / verify_batch said no
         self.first_malformed = -1               # verify_batch: the first unreadable proof
-        self.set_multiopen(multiopen)
+        self.ipa = multiopen is None            # an IPA verifier has one multiopen: nothing to set
+        self._params = None                     # IPA with a context: the borrowed ParamsIPA, kept alive
+        if not self.ipa:
+            self.set_multiopen(multiopen)
 
     def _check(self, rc: int):
         if rc != 0:
@@ -626,6 +629,57 @@ class Verifier:
         if rc:
             raise DehaloError(rc, _create_error())
         v = cls(ctx, curve, h, multiopen)
+        if transcript_repr is not None:
+            v.transcript_repr = transcript_repr
+        return v
+
+    @classmethod
+    def from_ipa(cls, params: "ParamsIPA", pk: "ProvingKey") -> "Verifier":
+        """verify_proof for IPA from a ParamsIPA and a key made under it (dehalo_verifier_create_ipa).  The params are borrowed: this object keeps them referenced."""
+        h = C.c_void_p()
+        rc = load_library().dehalo_verifier_create_ipa(params.ctx.handle, params.handle, pk.handle, C.byref(h))
+        if rc:
+            raise DehaloError(rc, _create_error())
+        v = cls(params.ctx, params.curve, h, None)
+        v._params = params
+        return v
+
+    @classmethod
+    def from_ipa_vk(cls, params: "ParamsIPA", cs: plonk.ConstraintSystem, vk_bytes: bytes, num_selectors: int = 0, format: str = "raw-unchecked",
+                    transcript_repr: Optional[int] = None) -> "Verifier":
+        """the verifier's side under IPA: ParamsIPA::read + VerifyingKey::read, no proving key (dehalo_verifier_create_ipa_vk); vk_bytes in `format`"""
+        desc = ConstraintSystemDescriptor(cs, params.curve.scalar)
+        buf = np.frombuffer(bytes(vk_bytes), dtype=np.uint8)
+        h = C.c_void_p()
+        rc = load_library().dehalo_verifier_create_ipa_vk(params.ctx.handle, params.handle, desc.ref(), buf.ctypes.data if buf.size else None, buf.size, _serde(format),
+                                                         num_selectors, C.byref(h))
+        if rc:
+            raise DehaloError(rc, _create_error())
+        v = cls(params.ctx, params.curve, h, None)
+        v._params = params
+        if transcript_repr is not None:
+            v.transcript_repr = transcript_repr
+        return v
+
+    @classmethod
+    def from_ipa_host(cls, curve: CurveSpec, k: int, g, g_lagrange, w, u, cs: plonk.ConstraintSystem, vk_bytes: bytes, num_selectors: int = 0,
+                      format: str = "raw-unchecked", transcript_repr: Optional[int] = None) -> "Verifier":
+        """a HOST verifier for IPA over points the caller holds (dehalo_verifier_create_ipa_host): g, g_lagrange 2^k rows of 8 Montgomery words, w, u one row each.
+        About 380 x 2^k group operations a call on one thread: for small k and machines without a GPU.  A mode, never a fallback."""
+        g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1, 8)
+        gl = np.ascontiguousarray(g_lagrange, dtype=np.uint64).reshape(-1, 8)
+        w = np.ascontiguousarray(w, dtype=np.uint64).reshape(8)
+        u = np.ascontiguousarray(u, dtype=np.uint64).reshape(8)
+        if not 0 <= k < 64 or g.shape[0] != 1 << k or gl.shape[0] != 1 << k:
+            raise ValueError("g and g_lagrange must hold 2^k points")
+        desc = ConstraintSystemDescriptor(cs, curve.scalar)
+        buf = np.frombuffer(bytes(vk_bytes), dtype=np.uint8)
+        h = C.c_void_p()
+        rc = load_library().dehalo_verifier_create_ipa_host(curve.id, k, g.ctypes.data, gl.ctypes.data, w.ctypes.data, u.ctypes.data, desc.ref(),
+                                                           buf.ctypes.data if buf.size else None, buf.size, _serde(format), num_selectors, C.byref(h))
+        if rc:
+            raise DehaloError(rc, _create_error())
+        v = cls(None, curve, h, None)
         if transcript_repr is not None:
             v.transcript_repr = transcript_repr
         return v
@@ -685,14 +739,14 @@ class Verifier:
                                                        C.byref(r) if r is not None else None, C.byref(accept), C.byref(first)))
         rng_writeback(rng, r)
         self.first_malformed = int(first.value)
-        self.last_reject = REJECT_NONE if accept.value else (REJECT_MALFORMED if first.value >= 0 else REJECT_PAIRING)
+        self.last_reject = REJECT_NONE if accept.value else (REJECT_MALFORMED if first.value >= 0 else REJECT_OPENING if self.ipa else REJECT_PAIRING)
         return bool(accept.value)
 
     def last_timings(self) -> dict:
         """milliseconds of the last call: point decompression, the transcript walks, the two MSMs, the pairing check"""
         out = (C.c_double * 4)()
         self._check(load_library().dehalo_verifier_last_timings(self.handle, out))
-        return dict(zip(("decompress", "walk", "msm", "pairing"), out))
+        return dict(zip(("decompress", "walk", "msm", "g_sum" if self.ipa else "pairing"), out))
 
     def release(self):
         if self.handle is not None:
@@ -712,6 +766,21 @@ def rng_writeback(rng, r: Optional[CRng]):
         st = rng.gen.bit_generator.state
         st["state"]["state"] = int(r.pcg_state[0]) | (int(r.pcg_state[1]) << 64)
         rng.gen.bit_generator.state = st
+
+
+def ipa_verify(params: "ParamsIPA", commitment, x3: int, v: int, proof: bytes) -> bool:
+    """dehalo_ipa_verify: does `proof` (a stand-alone opening, ParamsIPA.open's bytes) open `commitment` -- (x, y) canonical ints or 8 Montgomery words -- to v at x3?"""
+    curve = params.curve
+    if isinstance(commitment, tuple):
+        commitment = np.concatenate([curve.base.encode(commitment[0]), curve.base.encode(commitment[1])])
+    cm = np.ascontiguousarray(commitment, dtype=np.uint64).reshape(8)
+    f = curve.scalar
+    xe, ve = f.encode(x3 % f.p), f.encode(v % f.p)
+    buf = np.frombuffer(bytes(proof), dtype=np.uint8)
+    accept = C.c_int(0)
+    _check(params.ctx, load_library().dehalo_ipa_verify(params.ctx.handle, params.handle, cm.ctypes.data, xe.ctypes.data, ve.ctypes.data, buf.ctypes.data if buf.size else None,
+                                                       buf.size, C.byref(accept)))
+    return bool(accept.value)
 
 
 class Prover:

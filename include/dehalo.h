@@ -187,6 +187,15 @@ int dehalo_to_affine_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobi
  * overlap it in no other way.  Pallas and Vesta only (DEHALO_ERR_UNSUPPORTED otherwise).  Asynchronous on the stream; no workspace. */
 int dehalo_generator_collapse_device(dehalo_ctx* ctx, int curve, const uint64_t* d_affine_xy, size_t len, const uint64_t challenge[4], uint64_t* d_out_affine_xy,
                                      void* stream);
+/* The scalars over g of the IPA verifier's one multi-scalar multiplication [UPSTREAM halo2_proofs/src/poly/ipa/strategy.rs: GuardIPA::compute_s, summed over the
+ * proofs of a batch under their weights]: for `count` proofs, proof i with round challenges d_challenges[i k .. i k + k) (u_1 .. u_k in the transcript's order) and
+ * one scalar d_inits[i] (a verifier passes -w_i c_i),
+ *     d_out[idx] = sum_i init_i prod_{j < k, bit j of idx set} u_{i, k - j},    idx < 2^k:
+ * bit j of the index selects the j-th challenge from the END, as compute_s does.  All three arrays are device memory, scalars of 4 x u64 Montgomery (any word
+ * stands for its residue); the output is canonical.  Two launches, about one multiplication per proof and output; the workspace, count x (2^ceil(k / 2) + 2^floor(k / 2))
+ * scalars, is the context's.  1 <= k <= 28 (the largest ParamsIPA), 1 <= count < 2^24, else DEHALO_ERR_INVALID.  Pallas and Vesta only (DEHALO_ERR_UNSUPPORTED otherwise).
+ * Asynchronous on the stream. */
+int dehalo_ipa_s_device(dehalo_ctx* ctx, int curve, const uint64_t* d_challenges, const uint64_t* d_inits, size_t count, uint32_t k, uint64_t* d_out, void* stream);
 /* The blinding term of ParamsIPA::commit / commit_lagrange [UPSTREAM halo2_proofs/src/poly/ipa/commitment.rs: MSM(poly, g) + [blind] W] for the results of
  * one batched MSM: d_jacobian[i] <- d_jacobian[i] + [d_blinds[i]] W for i < count, in place.  Points as dehalo_msm_device leaves them (Jacobian, 96 B,
  * z = 0: the identity), blinds one scalar per point (4 x u64 Montgomery), W one affine point {x, y} (64 B, standard Montgomery): all device memory.
@@ -1016,7 +1025,18 @@ int dehalo_create_proofs_circuit(dehalo_prover* const* provers, uint32_t num_pro
  * (dehalo_pairing_check's code, on the host).  With a context the points of all proofs of a call are decompressed in ONE dehalo_points_decompress_device launch and
  * the two sums are fresh-bases MSMs on the device (dehalo_best_multiexp); with ctx = NULL -- a HOST verifier, a mode the caller chooses, for machines without a
  * GPU -- both run on the host (a plain double-and-add).  It is never a fallback: a verifier made with a context reports a device error as that error.
- * IPA verification is not part of this: every entry point returns DEHALO_ERR_UNSUPPORTED for ParamsIPA or a Pasta curve. */
+ *
+ * IPA over Pallas / Vesta [UPSTREAM plonk/verifier.rs with QUERY_INSTANCE = true, poly/ipa/multiopen/verifier.rs, poly/ipa/commitment/verifier.rs, poly/ipa/strategy.rs
+ * GuardIPA / AccumulatorStrategy]: the SAME verifier type and verify calls, made by the three _ipa constructors below (the two constructors above the line keep
+ * refusing ParamsIPA and the Pasta curves with DEHALO_ERR_UNSUPPORTED).  Everything the IPA prover proves is verified: phases and challenges, lookups, shuffles, up
+ * to 32 rotations, committed instance columns; one circuit a proof (num_circuits != 1 is DEHALO_ERR_UNSUPPORTED, as for the prover).  The same walk reads the proof
+ * -- the instance columns enter as commitments (commit_lagrange + [Blind::default()] W, every column of every proof of a call in one batch) and their evaluations are
+ * read first -- and the IPA multiopen and opening argument are reduced to one term list over the proof's points, the key's and the instance commitments, g[0], U and
+ * W, plus per proof its k round challenges and init = -w c.  Accept iff  (sum over the term list) + sum_idx s[idx] g[idx] = the identity,  s = sum_i compute_s(u_i, init_i):
+ * with a context s is built on the device (dehalo_ipa_s_device) and summed by dehalo_msm_device over the params' resident table -- one kernel pass and one MSM over
+ * g whatever the number of proofs; a host verifier (dehalo_verifier_create_ipa_host) builds s and both sums on the host.
+ * Still not provided: ParamsIPA::new's hash-to-curve generators (a ParamsIPA is read, made from g, or generated by this library's own rule), and several circuits
+ * in one IPA proof. */
 typedef struct dehalo_verifier dehalo_verifier;
 /* from objects the caller already has: g[0], g2, s_g2, k of the params; the vk half of the key (commitments, constraint system, transcript_repr) */
 int dehalo_verifier_create(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_verifier** out);
@@ -1025,8 +1045,20 @@ int dehalo_verifier_create(dehalo_ctx* ctx, const dehalo_params* params, const d
 int dehalo_verifier_create_vk(dehalo_ctx* ctx, int curve, uint32_t k, const uint64_t g0[8], const uint8_t g2[128], const uint8_t s_g2[128],
                               const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len, int vk_format, uint32_t num_selectors, dehalo_verifier** out);
 /* Both constructors check g2 and s_g2: on the twist, in the order-r subgroup, not the identity; otherwise DEHALO_ERR_INVALID. */
+/* IPA, from a ParamsIPA and a key made under it.  The params are borrowed as a prover borrows them: they must outlive the verifier.  DEHALO_ERR_INVALID for
+ * ParamsKZG, a key over another curve or of another k. */
+int dehalo_verifier_create_ipa(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_verifier** out);
+/* IPA, the verifier's side: ParamsIPA::read + VerifyingKey::read, no proving key.  vk bytes in any dehalo_serde_format, read as dehalo_verifier_create_vk reads them
+ * (the commitments are the blinded ones a key made under ParamsIPA holds); curve and k are the params'. */
+int dehalo_verifier_create_ipa_vk(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len, int vk_format,
+                                  uint32_t num_selectors, dehalo_verifier** out);
+/* IPA, a HOST verifier over points the caller holds (g, g_lagrange: 2^k affine {x, y} of 8 u64 each, standard Montgomery; w, u: one each; all copied), without a
+ * context.  Every verify call costs on the order of 380 x 2^k group operations on one thread (256 doublings and about 128 additions per generator's scalar, and as
+ * much again per instance value): meant for small k and for machines without a GPU.  A mode the caller chooses, never a fallback. */
+int dehalo_verifier_create_ipa_host(int curve, uint32_t k, const uint64_t* g, const uint64_t* g_lagrange, const uint64_t w[8], const uint64_t u[8],
+                                    const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len, int vk_format, uint32_t num_selectors, dehalo_verifier** out);
 int dehalo_verifier_set_transcript_repr(dehalo_verifier* v, const uint64_t repr[4]);
-int dehalo_verifier_set_multiopen(dehalo_verifier* v, int multiopen);      /* DEHALO_MULTIOPEN_GWC (default) | _SHPLONK */
+int dehalo_verifier_set_multiopen(dehalo_verifier* v, int multiopen);      /* DEHALO_MULTIOPEN_GWC (default) | _SHPLONK; DEHALO_ERR_INVALID on an IPA verifier */
 int dehalo_verifier_release(dehalo_verifier* v);
 /* Why the calling thread's last dehalo_verifier_create / _create_vk failed (a bad g2, the vk's header, a point's status, ...): a host verifier has no context
  * whose dehalo_last_error could say, and a failed constructor leaves no verifier.  The text is copied into out[0 .. cap), cut to cap - 1 bytes, NUL-terminated. */
@@ -1034,10 +1066,13 @@ int dehalo_verifier_create_error(char* out, size_t cap);
 /* Text of the last error of a call on this verifier (a host verifier has no context to keep it); valid until the next call on it. */
 const char* dehalo_verifier_last_error(const dehalo_verifier* v);
 /* Where the last dehalo_verify_proof(s) call spent its time, milliseconds: out[0] point decompression, out[1] the transcript walks (hashing, expected_h, the
- * term lists), out[2] the two MSMs, out[3] the pairing check. */
+ * term lists), out[2] the two MSMs (IPA: the one over the term list), out[3] the pairing check (IPA: the sum over g -- kernel, MSM, download). */
 int dehalo_verifier_last_timings(const dehalo_verifier* v, double out[4]);
 
-typedef enum { DEHALO_REJECT_NONE = 0, DEHALO_REJECT_MALFORMED = 1 /* a read failed, bytes missing or trailing */, DEHALO_REJECT_PAIRING = 2 } dehalo_reject_reason;
+typedef enum {
+    DEHALO_REJECT_NONE = 0, DEHALO_REJECT_MALFORMED = 1 /* a read failed, bytes missing or trailing */, DEHALO_REJECT_PAIRING = 2,
+    DEHALO_REJECT_OPENING = 3 /* IPA: the proof was readable and the final sum is not the identity, x_3 hit an opening point, or a round challenge was zero */
+} dehalo_reject_reason;
 /* instances / instance_lens / num_instance_columns / num_circuits: dehalo_create_proof_multi's layout.  Returns 0 whenever the check ran; *accept = 1 or 0, *reason (may be
  * NULL) why not.  A wrong number of instance columns or a column longer than the usable rows is the caller's error: DEHALO_ERR_INVALID. */
 int dehalo_verify_proof(dehalo_verifier* v, const uint64_t* const* instances, const size_t* instance_lens, uint32_t num_instance_columns, uint32_t num_circuits,
@@ -1051,6 +1086,11 @@ int dehalo_verify_proof(dehalo_verifier* v, const uint64_t* const* instances, co
  * weighted sums (two copies of one invalid proof under w_1 = -1 pass).  Use DEHALO_RNG_OS (rng = NULL) outside tests. */
 int dehalo_verify_proofs(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
                          uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* accept, int64_t* first_malformed);
+/* The IPA opening argument's check alone, the counterpart of dehalo_ipa_open: *accept = 1 iff `proof` (S, the k rounds' L_j, R_j, then c and f: 32 (2 k + 3) bytes,
+ * read through a fresh transcript) opens `commitment` (affine {x, y}, standard Montgomery) to v at x3 (4 x u64 Montgomery each) under the ParamsIPA `params`.  The
+ * reduction is the whole proof's; the two sums run on the device.  Returns 0 whenever the check ran. */
+int dehalo_ipa_verify(dehalo_ctx* ctx, const dehalo_params* params, const uint64_t commitment[8], const uint64_t x3[4], const uint64_t v[4], const uint8_t* proof, size_t len,
+                      int* accept);
 
 /* The grand products' per-row factors, every product of a proof in one launch [UPSTREAM plonk/permutation/prover.rs Argument::commit:
  * per set of columns  den = prod_j (value_j + beta sigma_j + gamma),  num = prod_j (value_j + delta^j beta omega^i + gamma);
