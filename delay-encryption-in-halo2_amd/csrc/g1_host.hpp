@@ -26,6 +26,9 @@ inline const char* point_status_text(uint32_t status, bool encodings) {
 // y^2 = x^3 + b: 3 on BN254's G1, 5 on Pallas and Vesta
 inline uint64_t curve_b_host(int curve) { return curve == DEHALO_CURVE_BN254_G1 ? 3 : 5; }
 
+// an affine {x, y} whose eight words are zero: the identity, and what a decoder writes for a point it refuses
+inline bool g1_affine_is_zero(const uint64_t xy[8]) { return (xy[0] | xy[1] | xy[2] | xy[3] | xy[4] | xy[5] | xy[6] | xy[7]) == 0; }
+
 // GroupEncoding::from_bytes on the host, with the device codec's verdicts (dehalo_points_decompress_device): 0, or POINT_NOT_BELOW_P / POINT_NOT_ON_CURVE /
 // POINT_ZERO_X_SIGNED; a refused point and the all-zero identity are written as (0, 0).  The one host decoder: the reading transcript, the host verifier and
 // the verifying key's Processed commitments go through it.  (Upstream sends x = 0 with the sign bit set to the square root like every other x; b is no square
@@ -117,6 +120,14 @@ struct G1Host {
         to_affine(acc, out_affine);
     }
     bool on_curve(const Fe& x, const Fe& y) const { return q->sqr(y) == q->add(q->mul(q->sqr(x), x), b); }
+    // stored Montgomery words {x, y}: 0, POINT_NOT_BELOW_P, or POINT_NOT_ON_CURVE -- that for (0, 0) too: who takes the identity asks g1_affine_is_zero
+    uint32_t check_stored(const uint64_t xy[8]) const {
+        Fe x, y;
+        memcpy(x.v, xy, 32);
+        memcpy(y.v, xy + 4, 32);
+        if (HostField::geq(x.v, q->p) || HostField::geq(y.v, q->p)) return POINT_NOT_BELOW_P;
+        return on_curve(x, y) ? 0 : POINT_NOT_ON_CURVE;
+    }
     // GroupEncoding::from_bytes with the device codec's verdicts (dehalo_points_decompress_device): 0, or POINT_NOT_BELOW_P / POINT_NOT_ON_CURVE /
     // POINT_ZERO_X_SIGNED; a refused point and the all-zero identity are written as (0, 0)
     uint32_t decompress(const uint8_t in[32], uint64_t xy[8]) const { return g1_decompress_host(q, b, in, xy); }

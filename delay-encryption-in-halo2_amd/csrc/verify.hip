@@ -107,14 +107,16 @@ int verifier_finish(dehalo_ctx* ctx, std::unique_ptr<dehalo_verifier>& v, dehalo
     return 0;
 }
 
+// the caller's errors, the weights' draw, then the work on the verifier's backend; the verdict goes to the caller's pointers here and nowhere else
 int verify_body(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
                 uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* accept, int64_t* first_malformed, int* reason) {
     std::lock_guard<std::mutex> lk(v->mu);
     v->error.clear();
     const HostField* f = v->key.f;
     std::string err;
+    VerifyInput in{proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, nullptr, OpeningPlan()};
     {   // the caller's errors first: a call that is refused has drawn nothing from the caller's generator
-        const int bad = verify_check_arguments(v->key, proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, &err);
+        const int bad = verify_check_arguments(v->key, in, &err);
         if (bad) return verifier_fail(v, v->ctx, bad, err);
     }
     std::vector<Fe> weights(std::max<uint32_t>(count, 1), f->one);      // w_0 = 1, then the generator's first count - 1 scalars
@@ -124,24 +126,58 @@ int verify_body(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* 
         if (hr.scalars((uint64_t*)(weights.data() + 1), count - 1) != 0) return verifier_fail(v, v->ctx, DEHALO_ERR_INVALID, "verify_proofs: the rng callback failed");
         hr.write_back(rng);
     }
-    int rc;
+    in.weights = weights.data();
+    std::unique_lock<std::recursive_mutex> hold;      // a device verifier's context, for the length of the work
+    std::unique_ptr<VerifyBackend> be;
     if (v->ctx) {
-        std::lock_guard<std::recursive_mutex> hold(v->ctx->mu);
+        hold = std::unique_lock<std::recursive_mutex>(v->ctx->mu);
         (void)hipSetDevice(v->ctx->device);
-        DeviceVerifyBackend be(v->ctx, v->key.curve, v->params);
-        rc = verify_proofs_host(v->key, be, proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, weights.data(), accept, first_malformed, reason,
-                                &v->stats, &err);
+        be.reset(new DeviceVerifyBackend(v->ctx, v->key.curve, v->params));
     } else {
-        HostVerifyBackend be(v->key.fq, v->key.f, curve_b_host(v->key.curve));
-        if (v->key.scheme == DEHALO_SCHEME_IPA) be.set_ipa(v->g.data(), v->g_lagrange.data(), v->key.w, v->key.k);
-        rc = verify_proofs_host(v->key, be, proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, weights.data(), accept, first_malformed, reason,
-                                &v->stats, &err);
+        std::unique_ptr<HostVerifyBackend> host(new HostVerifyBackend(v->key.fq, v->key.f, curve_b_host(v->key.curve)));
+        if (v->key.scheme == DEHALO_SCHEME_IPA) host->set_ipa(v->g.data(), v->g_lagrange.data(), v->key.w, v->key.k);
+        be = std::move(host);
     }
+    VerifyVerdict verdict;
+    verdict.stats = v->stats;      // (a call in error leaves the last call's timings)
+    const int rc = verify_proofs_host(v->key, *be, in, verdict, &err);
+    *accept = verdict.accept;
+    if (first_malformed) *first_malformed = verdict.first_malformed;
+    if (reason) *reason = verdict.reason;
+    v->stats = verdict.stats;
     if (rc && !err.empty()) {
         v->error = err;
         if (v->ctx && (rc == DEHALO_ERR_INVALID || rc == DEHALO_ERR_UNSUPPORTED)) dh_fail(v->ctx, rc, err);      // (a device error has its own text already)
     }
     return rc;
+}
+
+// the vk half of a key from the key at hand
+void key_from_pk(VerifierKey& key, const dehalo_pk* pk) {
+    key.curve = pk->curve; key.k = pk->k;
+    key.f = pk->f; key.fq = host_field(curve_base_field(pk->curve));
+    key.cs = pk->cs; key.dom = pk->dom;
+    key.fixed_commitments = pk->fixed_commitments; key.perm_commitments = pk->perm_commitments;
+    key.num_selectors = pk->num_selectors; key.selectors = pk->selectors;
+    key.transcript_repr = pk->transcript_repr;
+}
+// the vk half from the circuit and the vk's bytes; who: the constructor, as its messages name it
+int key_from_vk(dehalo_ctx* ctx, const char* who, VerifierKey& key, int scheme, int curve, uint32_t k, const dehalo_constraint_system* cs, const uint8_t* vk_bytes,
+                size_t vk_len, int vk_format, uint32_t num_selectors) {
+    key.scheme = scheme;
+    std::string err = key.init_cs(curve, cs, k);
+    if (!err.empty()) return create_fail(ctx, key.unsupported ? DEHALO_ERR_UNSUPPORTED : DEHALO_ERR_INVALID, std::string(who) + ": " + err);
+    err = key.load_vk(vk_bytes, vk_len, vk_format, num_selectors);
+    if (!err.empty()) return create_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": " + err);
+    key.default_transcript_repr();
+    return 0;
+}
+// a point of the caller's: both words below the modulus and on the key's curve
+bool key_point_ok(const VerifierKey& key, const uint64_t* xy) { return G1Host(key.fq, curve_b_host(key.curve)).check_stored(xy) == 0; }
+void ipa_key_points(VerifierKey& key, const uint64_t* g0, const uint64_t* u, const uint64_t* w) {
+    memcpy(key.g0, g0, 64);
+    memcpy(key.u, u, 64);
+    memcpy(key.w, w, 64);
 }
 
 }   // namespace
@@ -155,16 +191,7 @@ extern "C" int dehalo_verifier_create(dehalo_ctx* ctx, const dehalo_params* para
         std::unique_ptr<dehalo_verifier> v(new dehalo_verifier);
         v->ctx = ctx;
         VerifierKey& key = v->key;
-        key.curve = pk->curve; key.k = pk->k;
-        key.f = pk->f;
-        key.fq = host_field(curve_base_field(pk->curve));
-        key.cs = pk->cs;
-        key.dom = pk->dom;
-        key.num_selectors = pk->num_selectors;
-        key.fixed_commitments = pk->fixed_commitments;
-        key.perm_commitments = pk->perm_commitments;
-        key.selectors = pk->selectors;
-        key.transcript_repr = pk->transcript_repr;
+        key_from_pk(key, pk);
         memcpy(key.g0, params->g.data(), 64);
         memcpy(key.g2, params->g2, 128);
         memcpy(key.s_g2, params->s_g2, 128);
@@ -181,51 +208,16 @@ extern "C" int dehalo_verifier_create_vk(dehalo_ctx* ctx, int curve, uint32_t k,
         std::unique_ptr<dehalo_verifier> v(new dehalo_verifier);
         v->ctx = ctx;
         VerifierKey& key = v->key;
-        std::string err = key.init_cs(curve, cs, k);
-        if (!err.empty()) return create_fail(ctx, key.unsupported ? DEHALO_ERR_UNSUPPORTED : DEHALO_ERR_INVALID, "verifier_create_vk: " + err);
-        err = key.load_vk(vk_bytes, vk_len, vk_format, num_selectors);
-        if (!err.empty()) return create_fail(ctx, DEHALO_ERR_INVALID, "verifier_create_vk: " + err);
-        key.default_transcript_repr();
+        TRY(key_from_vk(ctx, "verifier_create_vk", key, DEHALO_SCHEME_KZG, curve, k, cs, vk_bytes, vk_len, vk_format, num_selectors));
         memcpy(key.g0, g0, 64);
         memcpy(key.g2, g2, 128);
         memcpy(key.s_g2, s_g2, 128);
-        const G1Host g1(key.fq, 3);
-        Fe x, y;
-        memcpy(x.v, g0, 32);
-        memcpy(y.v, g0 + 4, 32);
-        if (HostField::geq(x.v, key.fq->p) || HostField::geq(y.v, key.fq->p) || !g1.on_curve(x, y)) return create_fail(ctx, DEHALO_ERR_INVALID, "verifier_create_vk: g0 is not a curve point");
+        if (!key_point_ok(key, g0)) return create_fail(ctx, DEHALO_ERR_INVALID, "verifier_create_vk: g0 is not a curve point");
         return verifier_finish(ctx, v, out);
     });
 }
 
 // ---- the IPA verifier's constructors
-namespace {
-// a point of the caller's: both words below the modulus and on the curve
-bool ipa_point_ok(const VerifierKey& key, const uint64_t* xy) {
-    const G1Host g1(key.fq, curve_b_host(key.curve));
-    Fe x, y;
-    memcpy(x.v, xy, 32);
-    memcpy(y.v, xy + 4, 32);
-    return !HostField::geq(x.v, key.fq->p) && !HostField::geq(y.v, key.fq->p) && g1.on_curve(x, y);
-}
-// the vk half from bytes, as dehalo_verifier_create_vk reads it
-int ipa_key_from_vk(dehalo_ctx* ctx, const char* who, VerifierKey& key, int curve, uint32_t k, const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len,
-                    int vk_format, uint32_t num_selectors) {
-    key.scheme = DEHALO_SCHEME_IPA;
-    std::string err = key.init_cs(curve, cs, k);
-    if (!err.empty()) return create_fail(ctx, key.unsupported ? DEHALO_ERR_UNSUPPORTED : DEHALO_ERR_INVALID, std::string(who) + ": " + err);
-    err = key.load_vk(vk_bytes, vk_len, vk_format, num_selectors);
-    if (!err.empty()) return create_fail(ctx, DEHALO_ERR_INVALID, std::string(who) + ": " + err);
-    key.default_transcript_repr();
-    return 0;
-}
-void ipa_key_points(VerifierKey& key, const uint64_t* g0, const uint64_t* u, const uint64_t* w) {
-    memcpy(key.g0, g0, 64);
-    memcpy(key.u, u, 64);
-    memcpy(key.w, w, 64);
-}
-}   // namespace
-
 extern "C" int dehalo_verifier_create_ipa(dehalo_ctx* ctx, const dehalo_params* params, const dehalo_pk* pk, dehalo_verifier** out) {
     return dh_guard(ctx, [&]() -> int {
         if (!ctx || !params || !pk || !out) return create_fail(ctx, DEHALO_ERR_INVALID, "verifier_create_ipa: null argument");
@@ -237,16 +229,7 @@ extern "C" int dehalo_verifier_create_ipa(dehalo_ctx* ctx, const dehalo_params* 
         v->params = params;
         VerifierKey& key = v->key;
         key.scheme = DEHALO_SCHEME_IPA;
-        key.curve = pk->curve; key.k = pk->k;
-        key.f = pk->f;
-        key.fq = host_field(curve_base_field(pk->curve));
-        key.cs = pk->cs;
-        key.dom = pk->dom;
-        key.num_selectors = pk->num_selectors;
-        key.fixed_commitments = pk->fixed_commitments;
-        key.perm_commitments = pk->perm_commitments;
-        key.selectors = pk->selectors;
-        key.transcript_repr = pk->transcript_repr;
+        key_from_pk(key, pk);
         ipa_key_points(key, params->g.data(), params->u, params->w);
         return verifier_finish(ctx, v, out);
     });
@@ -260,7 +243,7 @@ extern "C" int dehalo_verifier_create_ipa_vk(dehalo_ctx* ctx, const dehalo_param
         std::unique_ptr<dehalo_verifier> v(new dehalo_verifier);
         v->ctx = ctx;
         v->params = params;
-        TRY(ipa_key_from_vk(ctx, "verifier_create_ipa_vk", v->key, params->curve, params->k, cs, vk_bytes, vk_len, vk_format, num_selectors));
+        TRY(key_from_vk(ctx, "verifier_create_ipa_vk", v->key, DEHALO_SCHEME_IPA, params->curve, params->k, cs, vk_bytes, vk_len, vk_format, num_selectors));
         ipa_key_points(v->key, params->g.data(), params->u, params->w);
         return verifier_finish(ctx, v, out);
     });
@@ -275,14 +258,14 @@ extern "C" int dehalo_verifier_create_ipa_host(int curve, uint32_t k, const uint
         if (curve != DEHALO_CURVE_PALLAS && curve != DEHALO_CURVE_VESTA) return create_fail(nullptr, DEHALO_ERR_UNSUPPORTED, "verifier_create_ipa_host: IPA over Pallas / Vesta only");
         if (k < 1 || k > 28) return create_fail(nullptr, DEHALO_ERR_INVALID, "verifier_create_ipa_host: k out of range");
         std::unique_ptr<dehalo_verifier> v(new dehalo_verifier);
-        TRY(ipa_key_from_vk(nullptr, "verifier_create_ipa_host", v->key, curve, k, cs, vk_bytes, vk_len, vk_format, num_selectors));
+        TRY(key_from_vk(nullptr, "verifier_create_ipa_host", v->key, DEHALO_SCHEME_IPA, curve, k, cs, vk_bytes, vk_len, vk_format, num_selectors));
         const size_t n = (size_t)1 << k;
         v->g.assign(g, g + 8 * n);
         v->g_lagrange.assign(g_lagrange, g_lagrange + 8 * n);
         for (size_t i = 0; i < n; i++)      // (the identity is no generator: the sums would not see its scalar)
-            if (!ipa_point_ok(v->key, &v->g[8 * i]) || !ipa_point_ok(v->key, &v->g_lagrange[8 * i]))
+            if (!key_point_ok(v->key, &v->g[8 * i]) || !key_point_ok(v->key, &v->g_lagrange[8 * i]))
                 return create_fail(nullptr, DEHALO_ERR_INVALID, "verifier_create_ipa_host: g or g_lagrange holds a word that is no curve point");
-        if (!ipa_point_ok(v->key, w) || !ipa_point_ok(v->key, u)) return create_fail(nullptr, DEHALO_ERR_INVALID, "verifier_create_ipa_host: w or u is not a curve point");
+        if (!key_point_ok(v->key, w) || !key_point_ok(v->key, u)) return create_fail(nullptr, DEHALO_ERR_INVALID, "verifier_create_ipa_host: w or u is not a curve point");
         ipa_key_points(v->key, g, u, w);
         return verifier_finish(nullptr, v, out);
     });
@@ -301,9 +284,7 @@ extern "C" int dehalo_ipa_verify(dehalo_ctx* ctx, const dehalo_params* p, const 
         memcpy(v.v, v_in, 32);
         x3 = f->mul(x3, f->one);
         v = f->mul(v, f->one);
-        bool id = true;
-        for (int i = 0; i < 8; i++) id = id && commitment[i] == 0;
-        if (id) return 0;      // (the identity is no commitment the transcript could have absorbed)
+        if (g1_affine_is_zero(commitment)) return 0;      // (the identity is no commitment the transcript could have absorbed)
         dehalo_transcript t;
         t.init_read(p->curve, proof, len);
         std::vector<uint64_t> store(8 * (2 * (size_t)p->k + 1));
@@ -320,11 +301,7 @@ extern "C" int dehalo_ipa_verify(dehalo_ctx* ctx, const dehalo_params* p, const 
         std::lock_guard<std::recursive_mutex> hold(ctx->mu);
         (void)hipSetDevice(ctx->device);
         DeviceVerifyBackend be(ctx, p->curve, p);
-        uint64_t fresh[8], gs[8];
-        TRY(be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), fresh));
-        TRY(be.g_sum(terms.us.data(), terms.inits.data(), 1, p->k, gs));
-        *accept = ipa_sums_cancel(host_field(curve_base_field(p->curve)), fresh, gs) ? 1 : 0;
-        return 0;
+        return decide_ipa(be, terms, 1, p->k, host_field(curve_base_field(p->curve)), accept);
     });
 }
 

@@ -11,10 +11,13 @@
 // The points of a proof stand at offsets its shape fixes; they are decompressed before the walk by a backend -- the host's below, or the device's (verify.hip:
 // one dehalo_points_decompress_device launch for all proofs of a call) -- and the two sums go through the backend's MSM.  The pairing is pairing_host.hpp's.
 // IPA over Pallas / Vesta [UPSTREAM plonk/verifier.rs with QUERY_INSTANCE = true, poly/ipa/multiopen/verifier.rs, poly/ipa/commitment/verifier.rs, poly/ipa/strategy.rs] is
-// a second reduction behind the same walk: the instance columns enter as commitments (the backend's instance_commitments), the multiopen and the opening argument
+// a third reduction behind the same read: the instance columns enter as commitments (the backend's instance_commitments), the multiopen and the opening argument
 // (ipa_reduce_opening) leave ONE term list over the proof's points, the key's and the instance commitments, g[0], U and W, plus per proof k round challenges and
 // init = -w c; accept iff  (sum over the list) + sum_idx s[idx] g[idx]  is the identity, s = sum_i compute_s(u_i, init_i) (the backend's g_sum: on the device the
 // kernel of ipa.cuh into the MSM over the params' resident g).
+// The map.  One proof (verify_walk): walk_read fills a WalkRead (commitments, challenges, evaluations), expected_h evaluates the circuit over it, and one of
+// reduce_gwc / reduce_shplonk / reduce_ipa_multiopen appends the proof's terms through a WalkQueries.  One call (verify_proofs_host, after
+// verify_check_arguments has made its VerifyInput): stage_points, stage_instances, run_walks, then decide_kzg or decide_ipa into a VerifyVerdict.
 // Host only, no HIP header: verify.hip includes it, and tests/native_host/verify_host_check.cpp and verify_ipa_host_check.cpp drive it on the CPU under ASan + UBSan.
 #pragma once
 #include <chrono>
@@ -95,6 +98,15 @@ struct HostVerifyBackend : VerifyBackend {
 
 // where a call's time went, in milliseconds (dehalo_verifier_last_timings)
 struct VerifyStats { double decompress = 0, walk = 0, msm = 0, pairing = 0; };      // (pairing: under IPA the sum over g)
+struct VerifyClock {      // lap(): milliseconds since it was made or last read
+    typedef std::chrono::steady_clock clk;
+    clk::time_point t0 = clk::now();
+    double lap() {
+        const clk::time_point t = t0;
+        t0 = clk::now();
+        return std::chrono::duration<double, std::milli>(t0 - t).count();
+    }
+};
 
 // ---- the verifying half of a key, and of the params: all a verifier keeps
 struct VerifierKey {
@@ -160,11 +172,8 @@ struct VerifierKey {
             }
             memcpy(dst, src, 64);
             if (format == DEHALO_SERDE_RAW_BYTES_UNCHECKED) continue;
-            Fe x, y;
-            memcpy(x.v, dst, 32);
-            memcpy(y.v, dst + 4, 32);
-            if (HostField::geq(x.v, fq->p) || HostField::geq(y.v, fq->p)) return point_status_text(POINT_NOT_BELOW_P, false);
-            if (!(x.is_zero() && y.is_zero()) && !g1.on_curve(x, y)) return point_status_text(POINT_NOT_ON_CURVE, false);
+            const uint32_t st = g1.check_stored(dst);
+            if (st && !g1_affine_is_zero(dst)) return point_status_text(st, false);
         }
         selectors.clear();
         for (uint32_t s = 0; s < nsel; s++) selectors.emplace_back(bytes + L.off_selectors + L.sel_bytes * s, bytes + L.off_selectors + L.sel_bytes * (s + 1));
@@ -197,27 +206,16 @@ struct VerifyTerms {
     void right(const Fe& s, const uint64_t* p) { rs.push_back(s); rp.insert(rp.end(), p, p + 8); }
 };
 
-// the points of one proof: [every commitment before the evaluations | the multiopen's], in the order of the bytes
-inline size_t verify_points_before_evals(const OpeningPlan& pl) { return (size_t)pl.NC + pl.p_instance - pl.p_hpiece; }
-inline size_t verify_multiopen_points(const OpeningPlan& pl, int multiopen) { return multiopen == DEHALO_MULTIOPEN_SHPLONK ? 2 : pl.groups.size(); }
-// where the points of a proof stand, in the order of the bytes: (byte offset, count) runs.  KZG: the commitments, then the multiopen's at the end; IPA: the
-// commitments, f behind the evaluations, then S and the k rounds' (L_j, R_j) behind the q evaluations
+// where the points of a proof stand, in the order of the bytes: (byte offset, count) runs.  KZG: every commitment before the evaluations, then the multiopen's at
+// the end; IPA: the commitments, f behind the evaluations, then S and the k rounds' (L_j, R_j) behind the q evaluations
 inline std::vector<std::pair<size_t, size_t>> verify_point_runs(const OpeningPlan& pl, int scheme, int multiopen) {
-    const size_t p0 = verify_points_before_evals(pl);
+    const size_t p0 = (size_t)pl.NC + pl.p_instance - pl.p_hpiece;
     if (scheme != DEHALO_SCHEME_IPA) {
-        const size_t p1 = verify_multiopen_points(pl, multiopen);
+        const size_t p1 = multiopen == DEHALO_MULTIOPEN_SHPLONK ? 2 : pl.groups.size();
         return {{0, p0}, {pl.proof_size(multiopen == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC) - 32 * p1, p1}};
     }
     const size_t off_f = 32 * (p0 + pl.instance_write.size() + pl.write.size()), off_s = off_f + 32 * (1 + pl.point_sets.size());
     return {{0, p0}, {off_f, 1}, {off_s, 1 + 2 * (size_t)pl.k}};
-}
-
-// a + b = the identity, for two affine points ((0, 0): the identity): the IPA verifier's acceptance, on the host
-inline bool ipa_sums_cancel(const HostField* fq, const uint64_t a[8], const uint64_t b[8]) {
-    Fe by;
-    memcpy(by.v, b + 4, 32);
-    by = fq->neg(by);      // -(x, y) = (x, -y); (0, 0) stays the identity
-    return memcmp(a, b, 32) == 0 && memcmp(a + 4, by.v, 32) == 0;
 }
 
 // what a walk makes of one proof
@@ -264,437 +262,484 @@ inline VerifyWalkResult ipa_reduce_opening(const HostField* f, dehalo_transcript
     return VERIFY_WALK_OK;
 }
 
-// One proof whose length is the shape's and whose points are decoded (none refused): the transcript walk, expected_h and the reduction of the multiopen, appended
-// to `out` under `weight`.  MALFORMED: a scalar is not below r; OPENING (IPA): x_3 is an opening point, a round challenge is zero or an instance commitment is the
-// identity; nothing of `out` is then meaningful.  One walk for the three schemes: the key's scheme decides how the instance columns enter (KZG: their values, as
-// scalars, interpolated here; IPA: their commitments instance_cm -- 8 u64 a column -- as points, their evaluations read first) and which reduction the queries go to.
-// instances: [circuit][column] -> values (Montgomery, canonical).
-inline VerifyWalkResult verify_walk(const VerifierKey& vk, const OpeningPlan& pl, uint32_t N, const uint8_t* proof, size_t len, const uint64_t* pts,
-                                    const std::vector<std::vector<std::vector<Fe>>>& instances, const uint64_t* instance_cm, const Fe& weight, VerifyTerms& out) {
-    const bool ipa = vk.scheme == DEHALO_SCHEME_IPA;
-    const HostField* f = vk.f;
-    const HostCS& cs = vk.cs;
-    const HostDomain& d = vk.dom;
-    const Fe zero{}, one = f->one;
-    const uint32_t A = pl.A, L = pl.L, S = pl.S, H = pl.H, bf = cs.blinding_factors(), pieces = d.quotient_poly_degree;
-    const int32_t last = -(int32_t)(bf + 1);
+// ---- one proof, a function per phase: walk_read -> expected_h -> reduce_gwc | reduce_shplonk | reduce_ipa_multiopen (verify_walk)
+// the instance columns' values of one proof: [circuit][column] -> values (Montgomery, canonical)
+typedef std::vector<std::vector<std::vector<Fe>>> InstanceValues;
+
+// what reading a proof up to the end of its evaluations leaves
+struct WalkRead {
     dehalo_transcript t;
-    t.init_read(vk.curve, proof, len);
-    size_t next_pt = 0;
-    auto point = [&]() -> const uint64_t* {      // the next 32 bytes are a point, decoded already: absorbed as the reader would absorb it
+    const uint64_t* pts = nullptr; size_t next_pt = 0;      // the proof's points, decoded already, in the order of the bytes, and the cursor over them
+    std::vector<const uint64_t*> cm;    // polynomial id -> its commitment
+    std::vector<Fe> challenges, E;      // the phases' challenges; the evaluations, by the plan's slot
+    Fe theta{}, beta{}, gamma{}, y{}, x{}, xn{};      // xn = x^n
+    const uint64_t* point() {           // the next 32 bytes are a point: absorbed as the reader would absorb it
         const uint64_t* p = pts + 8 * next_pt++;
         t.write_point(p, false);
         t.pos += 32;
         return p;
-    };
-    std::vector<const uint64_t*> cm(pl.num_polys, nullptr);      // polynomial id -> its commitment
+    }
+};
+
+// The transcript from its start to the last evaluation [UPSTREAM plonk/verifier.rs].  The key's scheme decides how the instance columns enter: KZG their values, as
+// scalars; IPA their commitments instance_cm (8 u64 a column), their evaluations read first.  MALFORMED: a scalar is not below r; OPENING (IPA): an identity instance_cm.
+inline VerifyWalkResult walk_read(const VerifierKey& vk, const OpeningPlan& pl, const uint8_t* proof, size_t len, const uint64_t* pts, const InstanceValues& instances,
+                                  const uint64_t* instance_cm, WalkRead& w) {
+    const HostCS& cs = vk.cs;
+    dehalo_transcript& t = w.t;
+    t.init_read(vk.curve, proof, len);
+    w.pts = pts; w.cm.assign(pl.num_polys, nullptr);
     t.common_scalar(vk.transcript_repr);
-    if (ipa) {
+    if (vk.scheme == DEHALO_SCHEME_IPA) {
         for (uint32_t i = 0; i < cs.num_instance; i++) {
             if (!t.write_point(instance_cm + 8 * i, false)) return VERIFY_WALK_OPENING;
-            cm[pl.p_instance + i] = instance_cm + 8 * i;
+            w.cm[pl.p_instance + i] = instance_cm + 8 * i;
         }
     } else
         for (auto& circuit : instances)
             for (auto& column : circuit)
                 for (const Fe& v : column) t.common_scalar(v);
-    std::vector<Fe> challenges(cs.challenge_phase.size(), zero);
+    w.challenges.assign(cs.challenge_phase.size(), Fe{});
     for (uint32_t ph = 0; ph < cs.num_phases; ph++) {
-        for (uint32_t c = 0; c < N; c++)
-            for (uint32_t col = 0; col < A; col++)
-                if (cs.advice_phase[col] == ph) cm[pl.adv(c) + col] = point();
-        for (size_t j = 0; j < challenges.size(); j++)
-            if (cs.challenge_phase[j] == ph) challenges[j] = t.squeeze();
+        for (uint32_t c = 0; c < pl.circuits; c++)
+            for (uint32_t col = 0; col < pl.A; col++)
+                if (cs.advice_phase[col] == ph) w.cm[pl.adv(c) + col] = w.point();
+        for (size_t j = 0; j < w.challenges.size(); j++)
+            if (cs.challenge_phase[j] == ph) w.challenges[j] = t.squeeze();
     }
-    const Fe theta = t.squeeze();
-    for (uint32_t c = 0; c < N; c++)
-        for (uint32_t l = 0; l < L; l++) {
-            cm[pl.perm(c) + 2 * l] = point();
-            cm[pl.perm(c) + 2 * l + 1] = point();
+    w.theta = t.squeeze();
+    for (uint32_t c = 0; c < pl.circuits; c++)
+        for (uint32_t l = 0; l < pl.L; l++) {
+            w.cm[pl.perm(c) + 2 * l] = w.point();
+            w.cm[pl.perm(c) + 2 * l + 1] = w.point();
         }
-    const Fe beta = t.squeeze(), gamma = t.squeeze();
-    for (uint32_t off : pl.product_order) cm[pl.o_pz + off] = point();      // every circuit's permutation, lookup, shuffle products; the random polynomial
-    const Fe y = t.squeeze();
-    for (uint32_t i = 0; i < pieces; i++) cm[pl.p_hpiece + i] = point();
-    const Fe x = t.squeeze();
-    for (uint32_t i = 0; i < cs.num_fixed; i++) cm[pl.p_fixed + i] = &vk.fixed_commitments[8 * i];
-    for (size_t j = 0; j < cs.perm_cols.size(); j++) cm[pl.p_sigma + j] = &vk.perm_commitments[8 * j];
-    std::vector<Fe> E(pl.eval_count, zero);
+    w.beta = t.squeeze(); w.gamma = t.squeeze();
+    for (uint32_t off : pl.product_order) w.cm[pl.o_pz + off] = w.point();      // every circuit's permutation, lookup, shuffle products; the random polynomial
+    w.y = t.squeeze();
+    for (uint32_t i = 0; i < vk.dom.quotient_poly_degree; i++) w.cm[pl.p_hpiece + i] = w.point();
+    w.x = t.squeeze();
+    for (uint32_t i = 0; i < cs.num_fixed; i++) w.cm[pl.p_fixed + i] = &vk.fixed_commitments[8 * i];
+    for (size_t j = 0; j < cs.perm_cols.size(); j++) w.cm[pl.p_sigma + j] = &vk.perm_commitments[8 * j];
+    w.E.assign(pl.eval_count, Fe{});
     for (int64_t slot : pl.instance_write)      // (none unless the instance columns are queried)
-        if (!t.read_scalar(E[(size_t)slot])) return VERIFY_WALK_MALFORMED;
+        if (!t.read_scalar(w.E[(size_t)slot])) return VERIFY_WALK_MALFORMED;
     for (int64_t slot : pl.write)
-        if (!t.read_scalar(E[(size_t)slot])) return VERIFY_WALK_MALFORMED;
-
-    // ---- expected_h
-    Fe xn = x;
-    for (uint32_t i = 0; i < d.k; i++) xn = f->sqr(xn);
-    const Fe xn1 = f->sub(xn, one), n_fe = f->from_u64((uint64_t)d.n);
-    auto l_i = [&](int64_t i) {      // l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
-        const int64_t m = ((i % (int64_t)d.n) + (int64_t)d.n) % (int64_t)d.n;
-        const Fe wi = f->pow_u64(d.omega, (uint64_t)m);
-        return f->mul(f->mul(wi, xn1), f->invert(f->mul(n_fe, f->sub(x, wi))));
-    };
-    std::vector<Fe> l_evals;      // l_0, l_{-1}, ..., l_{-(bf + 1)}
-    for (uint32_t i = 0; i < bf + 2; i++) l_evals.push_back(l_i(-(int64_t)i));
-    const Fe l_0 = l_evals[0], l_last = l_evals[bf + 1];
-    Fe l_blind = zero;
-    for (uint32_t i = 1; i <= bf; i++) l_blind = f->add(l_blind, l_evals[i]);
-    const Fe active = f->sub(one, f->add(l_last, l_blind));
-    auto ev = [&](uint32_t poly, int32_t rot) -> const Fe& { return E[(size_t)pl.slot(poly, rot)]; };
-    Fe expected_h = zero;
-    for (uint32_t c = 0; c < N; c++) {
-        auto instance_eval = [&](uint32_t col, int32_t rot) -> Fe {      // QUERY_INSTANCE = false: interpolated from the values; true (IPA): read
-            if (ipa) return ev(pl.p_instance + col, rot);
-            Fe acc = zero;
-            const std::vector<Fe>& vals = instances[c][col];
-            for (size_t j = 0; j < vals.size(); j++)
-                if (!vals[j].is_zero()) acc = f->add(acc, f->mul(vals[j], l_i((int64_t)j - rot)));
-            return acc;
-        };
-        std::vector<Fe> val(cs.nodes.size());      // children precede their parents
-        for (size_t i = 0; i < cs.nodes.size(); i++) {
-            const dehalo_expr_node& e = cs.nodes[i];
-            switch (e.kind) {
-                case DEHALO_EXPR_CONSTANT: val[i] = f->mul(cs.constants[e.a], one); break;
-                case DEHALO_EXPR_FIXED: val[i] = ev(pl.p_fixed + e.a, e.rotation); break;
-                case DEHALO_EXPR_ADVICE: val[i] = ev(pl.adv(c) + e.a, e.rotation); break;
-                case DEHALO_EXPR_INSTANCE: val[i] = instance_eval(e.a, e.rotation); break;
-                case DEHALO_EXPR_CHALLENGE: val[i] = challenges[e.a]; break;
-                case DEHALO_EXPR_NEGATED: val[i] = f->neg(val[e.a]); break;
-                case DEHALO_EXPR_SUM: val[i] = f->add(val[e.a], val[e.b]); break;
-                case DEHALO_EXPR_PRODUCT: val[i] = f->mul(val[e.a], val[e.b]); break;
-                default: val[i] = f->mul(val[e.a], f->mul(cs.constants[e.b], one)); break;      // SCALED
-            }
-        }
-        auto fold = [&](const Fe& term) { expected_h = f->add(f->mul(expected_h, y), term); };
-        auto compress = [&](const std::vector<uint32_t>& es) {
-            Fe acc = zero;
-            for (uint32_t e : es) acc = f->add(f->mul(acc, theta), val[e]);
-            return acc;
-        };
-        for (uint32_t g : cs.gates) fold(val[g]);
-        if (S) {      // permutation::verifier::Evaluated::expressions
-            auto column_eval = [&](const dehalo_column_query& q) {
-                return q.kind == DEHALO_COLUMN_ADVICE ? ev(pl.adv(c) + q.index, 0) : q.kind == DEHALO_COLUMN_FIXED ? ev(pl.p_fixed + q.index, 0) : instance_eval(q.index, 0);
-            };
-            const uint32_t chunk = cs.chunk_len();
-            fold(f->mul(l_0, f->sub(one, ev(pl.pz(c), 0))));
-            const Fe zl = ev(pl.pz(c) + S - 1, 0);
-            fold(f->mul(l_last, f->sub(f->sqr(zl), zl)));
-            for (uint32_t s = 1; s < S; s++) fold(f->mul(l_0, f->sub(ev(pl.pz(c) + s, 0), ev(pl.pz(c) + s - 1, last))));
-            Fe cur = f->mul(beta, x);      // beta x delta^j, running across the sets' column chunks
-            for (uint32_t s = 0; s < S; s++) {
-                Fe left = ev(pl.pz(c) + s, 1), right = ev(pl.pz(c) + s, 0);
-                for (size_t j = (size_t)s * chunk; j < std::min<size_t>((size_t)(s + 1) * chunk, cs.perm_cols.size()); j++) {
-                    const Fe cv = column_eval(cs.perm_cols[j]);
-                    left = f->mul(left, f->add(f->add(cv, f->mul(beta, ev(pl.p_sigma + (uint32_t)j, 0))), gamma));
-                    right = f->mul(right, f->add(f->add(cv, cur), gamma));
-                    cur = f->mul(cur, f->delta);
-                }
-                fold(f->mul(f->sub(left, right), active));
-            }
-        }
-        for (uint32_t l = 0; l < L; l++) {      // lookup::verifier::Evaluated::expressions
-            const uint32_t zc = pl.lz(c) + l, ai = pl.perm(c) + 2 * l, ti = ai + 1;
-            const Fe &z0 = ev(zc, 0), &z1 = ev(zc, 1), &a0 = ev(ai, 0), &am1 = ev(ai, -1), &s0 = ev(ti, 0);
-            const Fe left = f->mul(f->mul(z1, f->add(a0, beta)), f->add(s0, gamma));
-            const Fe right = f->mul(f->mul(z0, f->add(compress(cs.lookups[l].inputs), beta)), f->add(compress(cs.lookups[l].tables), gamma));
-            fold(f->mul(l_0, f->sub(one, z0)));
-            fold(f->mul(l_last, f->sub(f->sqr(z0), z0)));
-            fold(f->mul(f->sub(left, right), active));
-            fold(f->mul(l_0, f->sub(a0, s0)));
-            fold(f->mul(f->mul(f->sub(a0, s0), f->sub(a0, am1)), active));
-        }
-        for (uint32_t j = 0; j < H; j++) {      // shuffles: l0 (1 - z), l_last (z^2 - z), l_active (z(wx) (S + gamma) - z(x) (A + gamma))
-            const Fe &z0 = ev(pl.sz(c) + j, 0), &z1 = ev(pl.sz(c) + j, 1);
-            fold(f->mul(l_0, f->sub(one, z0)));
-            fold(f->mul(l_last, f->sub(f->sqr(z0), z0)));
-            fold(f->mul(f->sub(f->mul(z1, f->add(compress(cs.shuffles[j].tables), gamma)), f->mul(z0, f->add(compress(cs.shuffles[j].inputs), gamma))), active));
-        }
-    }
-    const Fe hfold_eval = f->mul(expected_h, f->invert(xn1));      // (x^n = 1 with negligible probability: the value is then 0 and the check fails)
-    auto eval_of = [&](int64_t slot) -> const Fe& { return slot >= 0 ? E[(size_t)slot] : hfold_eval; };
-    // coef x the commitment of polynomial `poly`; the folded quotient h = sum_i x^(n i) h_i goes to its pieces
-    auto commitment_term = [&](const Fe& coef, uint32_t poly) {
-        if (poly != pl.p_hfold) { out.right(coef, cm[poly]); return; }
-        Fe xp = coef;
-        for (uint32_t i = 0; i < pieces; i++) {
-            out.right(xp, cm[pl.p_hpiece + i]);
-            xp = f->mul(xp, xn);
-        }
-    };
-
-    if (ipa) {      // VerifierIPA::verify_proof over the plan's intermediate sets, then the opening argument's check of the final commitment P
-        const Fe x1 = t.squeeze(), x2 = t.squeeze();
-        const uint64_t* f_commitment = point();
-        const Fe x3 = t.squeeze();
-        const size_t ns = pl.point_sets.size();
-        std::vector<Fe> q_evals(ns);
-        for (Fe& e : q_evals)
-            if (!t.read_scalar(e)) return VERIFY_WALK_MALFORMED;
-        std::vector<Fe> super;
-        for (int32_t r : pl.point_rot) super.push_back(d.rotate_omega(x, r));
-        // per set: the x_1-folded evaluations at its points, their interpolant's value at x_3, and (q_eval - that) / prod (x_3 - point), folded with x_2
-        Fe f_eval = zero;
-        for (size_t si = 0; si < ns; si++) {
-            const std::vector<uint32_t>& T = pl.point_sets[si];
-            std::vector<Fe> evs(T.size(), zero);
-            for (uint32_t ci : pl.set_members[si])
-                for (size_t a = 0; a < T.size(); a++) evs[a] = f->add(f->mul(evs[a], x1), eval_of(pl.commitments[ci].evals[a]));
-            Fe r = zero, den_all = one;
-            for (size_t a = 0; a < T.size(); a++) {
-                Fe num = one, den = one;
-                for (size_t b = 0; b < T.size(); b++)
-                    if (b != a) { num = f->mul(num, f->sub(x3, super[T[b]])); den = f->mul(den, f->sub(super[T[a]], super[T[b]])); }
-                r = f->add(r, f->mul(evs[a], f->mul(num, f->invert(den))));
-                const Fe diff = f->sub(x3, super[T[a]]);
-                if (diff.is_zero()) return VERIFY_WALK_OPENING;
-                den_all = f->mul(den_all, diff);
-            }
-            f_eval = f->add(f->mul(f_eval, x2), f->mul(f->sub(q_evals[si], r), f->invert(den_all)));
-        }
-        const Fe x4 = t.squeeze();
-        // P = x_4^ns f + sum_si x_4^(ns - 1 - si) q_si,  q_si = sum_m x_1^(M - 1 - m) C_m: never formed, its scalars go to the commitments; v likewise
-        std::vector<Fe> x4p(ns + 1, weight);      // weight x_4^i
-        for (size_t i = 1; i <= ns; i++) x4p[i] = f->mul(x4p[i - 1], x4);
-        out.right(x4p[ns], f_commitment);
-        Fe v = f_eval;
-        for (size_t si = 0; si < ns; si++) {
-            const std::vector<uint32_t>& M = pl.set_members[si];
-            Fe coef = x4p[ns - 1 - si];
-            for (size_t m = M.size(); m-- > 0;) {
-                commitment_term(coef, pl.commitments[M[m]].poly);
-                coef = f->mul(coef, x1);
-            }
-            v = f->add(f->mul(v, x4), q_evals[si]);
-        }
-        return ipa_reduce_opening(f, t, point, pl.k, weight, x3, v, vk.g0, vk.u, vk.w, out);
-    }
-    if (vk.multiopen != DEHALO_MULTIOPEN_SHPLONK) {      // VerifierGWC::verify_proof
-        const Fe v = t.squeeze();
-        std::vector<const uint64_t*> W;
-        for (size_t gi = 0; gi < pl.groups.size(); gi++) W.push_back(point());
-        const Fe u = t.squeeze();
-        Fe pu = weight, eval_multi = zero;
-        for (size_t gi = 0; gi < pl.groups.size(); gi++) {
-            const OpeningPlan::Group& g = pl.groups[gi];
-            out.left(pu, W[gi]);
-            out.right(f->mul(pu, d.rotate_omega(x, g.rot)), W[gi]);
-            Fe pv = pu;
-            for (size_t j = 0; j < g.polys.size(); j++) {
-                commitment_term(pv, g.polys[j]);
-                eval_multi = f->add(eval_multi, f->mul(pv, eval_of(g.evals[j])));
-                pv = f->mul(pv, v);
-            }
-            pu = f->mul(pu, u);
-        }
-        out.right(f->neg(eval_multi), vk.g0);
-        return VERIFY_WALK_OK;
-    }
-    // VerifierSHPLONK::verify_proof over the plan's intermediate sets
-    const Fe y_ = t.squeeze(), v = t.squeeze();
-    const uint64_t* h = point();
-    const Fe u = t.squeeze();
-    const uint64_t* h2 = point();
-    const size_t ns = pl.point_sets.size();
-    std::vector<Fe> super;
-    for (int32_t r : pl.point_rot) super.push_back(d.rotate_omega(x, r));
-    std::vector<Fe> zdiff(ns, one), inv;      // inv: [zdiff_0 | per set, per point: prod_{s != t} (z_t - z_s)]
-    std::vector<std::vector<Fe>> basis(ns);   // prod_{s != t} (u - z_s), then times the inverted denominator: the Lagrange basis of the set at u
-    Fe z_0 = one;
-    for (size_t si = 0; si < ns; si++) {
-        const std::vector<uint32_t>& T = pl.point_sets[si];
-        for (uint32_t pi = 0; pi < super.size(); pi++)
-            if (std::find(T.begin(), T.end(), pi) == T.end()) zdiff[si] = f->mul(zdiff[si], f->sub(u, super[pi]));
-        if (si == 0) {
-            inv.push_back(zdiff[0]);
-            for (uint32_t pi : T) z_0 = f->mul(z_0, f->sub(u, super[pi]));
-        }
-        for (size_t a = 0; a < T.size(); a++) {
-            Fe num = one, den = one;
-            for (size_t b = 0; b < T.size(); b++)
-                if (b != a) { num = f->mul(num, f->sub(u, super[T[b]])); den = f->mul(den, f->sub(super[T[a]], super[T[b]])); }
-            basis[si].push_back(num);
-            inv.push_back(den);
-        }
-    }
-    // (u is an opening point, or two points coincide, with negligible probability: the inverses are then taken as 0 and the check fails)
-    if (!f->batch_invert(inv.data(), inv.size())) for (Fe& e : inv) e = f->invert(e);
-    Fe vi = weight, r_total = zero;
-    size_t io = 1;
-    for (size_t si = 0; si < ns; si++) {
-        for (Fe& b : basis[si]) b = f->mul(b, inv[io++]);
-        const Fe c = f->mul(f->mul(vi, zdiff[si]), inv[0]);
-        Fe yj = c;
-        for (uint32_t ci : pl.set_members[si]) {
-            const OpeningPlan::Commitment& m = pl.commitments[ci];
-            Fe r = zero;
-            for (size_t a = 0; a < basis[si].size(); a++) r = f->add(r, f->mul(basis[si][a], eval_of(m.evals[a])));
-            commitment_term(yj, m.poly);
-            r_total = f->add(r_total, f->mul(yj, r));
-            yj = f->mul(yj, y_);
-        }
-        vi = f->mul(vi, v);
-    }
-    out.right(f->neg(r_total), vk.g0);
-    out.right(f->neg(f->mul(weight, z_0)), h);
-    out.right(f->mul(weight, u), h2);
-    out.left(weight, h2);
+        if (!t.read_scalar(w.E[(size_t)slot])) return VERIFY_WALK_MALFORMED;
+    w.xn = w.x;
+    for (uint32_t i = 0; i < vk.dom.k; i++) w.xn = vk.f->sqr(w.xn);
     return VERIFY_WALK_OK;
 }
 
-// `count` proofs under one key: *accept = 1 iff every proof is readable and  e(sum_i w_i L_i, s_g2) e(-sum_i w_i R_i, g2) = 1.  *first_malformed: the first
-// unreadable proof or -1; *reason: a dehalo_reject_reason.  instances[(i N + c) nic + j] / instance_lens likewise: proof i's circuit c's column j (Montgomery words,
-// any residue).  weights: count scalars (Montgomery).  Returns 0 whenever the check ran; DEHALO_ERR_INVALID for the caller's errors, DEHALO_ERR_UNSUPPORTED for a
-// shape the opening plan refuses, or the backend's error.
-// the caller's errors of a verify call, before anything is read or drawn: 0, DEHALO_ERR_INVALID, or DEHALO_ERR_UNSUPPORTED for a shape the opening plan refuses
-inline int verify_check_arguments(const VerifierKey& vk, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
-                                  const size_t* instance_lens, uint32_t num_instance_columns, uint32_t N, std::string* error) {
-    auto fail = [&](int rc, const std::string& why) { if (error) *error = why; return rc; };
-    const HostCS& cs = vk.cs;
-    if (count && (!proofs || !lens)) return fail(DEHALO_ERR_INVALID, "verify_proofs: null argument");
-    if (N == 0) return fail(DEHALO_ERR_INVALID, "verify_proofs: no circuit");
-    if (count && num_instance_columns != cs.num_instance) return fail(DEHALO_ERR_INVALID, "verify_proofs: instances.len() != num_instance_columns");
-    if (num_instance_columns && count && (!instances || !instance_lens)) return fail(DEHALO_ERR_INVALID, "verify_proofs: null instances");
-    const OpeningPlan pl(vk.opening_shape(N));
-    if (!pl.error.empty()) return fail(DEHALO_ERR_UNSUPPORTED, pl.error);
-    const size_t usable = vk.dom.n - (cs.blinding_factors() + 1);
-    for (size_t e = 0; e < (size_t)count * N * num_instance_columns; e++) {
-        if (instance_lens[e] > usable) return fail(DEHALO_ERR_INVALID, "verify_proofs: an instance column is longer than the usable rows");
-        if (instance_lens[e] && !instances[e]) return fail(DEHALO_ERR_INVALID, "verify_proofs: null instance column");
+// expected_h's working state: the Lagrange values at x every circuit shares, then per circuit c the expression graph's values `val` and the three arguments'
+// expressions, each folded into acc with y.  Reads no transcript and makes no term.
+struct ExpectedH {
+    const OpeningPlan& pl; const WalkRead& w; const InstanceValues& instances;
+    const HostField* f; const HostCS& cs; const HostDomain& d;
+    const bool ipa; const int32_t last;
+    Fe xn1, n_fe, l_0, l_last, active, acc{};
+    uint32_t c = 0;
+    std::vector<Fe> val;
+    ExpectedH(const VerifierKey& vk, const OpeningPlan& pl_, const WalkRead& w_, const InstanceValues& instances_)
+        : pl(pl_), w(w_), instances(instances_), f(vk.f), cs(vk.cs), d(vk.dom), ipa(vk.scheme == DEHALO_SCHEME_IPA), last(-(int32_t)(vk.cs.blinding_factors() + 1)) {
+        xn1 = f->sub(w.xn, f->one); n_fe = f->from_u64((uint64_t)d.n);
+        l_0 = l_i(0); l_last = l_i(last);
+        Fe l_blind{};
+        for (int32_t i = -1; i > last; i--) l_blind = f->add(l_blind, l_i(i));
+        active = f->sub(f->one, f->add(l_last, l_blind));
+    }
+    Fe l_i(int64_t i) const {      // l_i(x) = omega^i (x^n - 1) / (n (x - omega^i))
+        const int64_t m = ((i % (int64_t)d.n) + (int64_t)d.n) % (int64_t)d.n;
+        const Fe wi = f->pow_u64(d.omega, (uint64_t)m);
+        return f->mul(f->mul(wi, xn1), f->invert(f->mul(n_fe, f->sub(w.x, wi))));
+    }
+    const Fe& ev(uint32_t poly, int32_t rot) const { return w.E[(size_t)pl.slot(poly, rot)]; }
+    Fe instance_eval(uint32_t col, int32_t rot) const {      // QUERY_INSTANCE = false: interpolated from the values; true (IPA): read
+        if (ipa) return ev(pl.p_instance + col, rot);
+        Fe sum{};
+        const std::vector<Fe>& vals = instances[c][col];
+        for (size_t j = 0; j < vals.size(); j++)
+            if (!vals[j].is_zero()) sum = f->add(sum, f->mul(vals[j], l_i((int64_t)j - rot)));
+        return sum;
+    }
+    void fold(const Fe& term) { acc = f->add(f->mul(acc, w.y), term); }
+    Fe compress(const std::vector<uint32_t>& es) const {
+        Fe sum{};
+        for (uint32_t e : es) sum = f->add(f->mul(sum, w.theta), val[e]);
+        return sum;
+    }
+    void graph() {      // every node of the circuit's expressions at the evaluations: children precede their parents
+        val.resize(cs.nodes.size());
+        for (size_t i = 0; i < cs.nodes.size(); i++) {
+            const dehalo_expr_node& e = cs.nodes[i];
+            switch (e.kind) {
+                case DEHALO_EXPR_CONSTANT: val[i] = f->mul(cs.constants[e.a], f->one); break;
+                case DEHALO_EXPR_FIXED: val[i] = ev(pl.p_fixed + e.a, e.rotation); break;
+                case DEHALO_EXPR_ADVICE: val[i] = ev(pl.adv(c) + e.a, e.rotation); break;
+                case DEHALO_EXPR_INSTANCE: val[i] = instance_eval(e.a, e.rotation); break;
+                case DEHALO_EXPR_CHALLENGE: val[i] = w.challenges[e.a]; break;
+                case DEHALO_EXPR_NEGATED: val[i] = f->neg(val[e.a]); break;
+                case DEHALO_EXPR_SUM: val[i] = f->add(val[e.a], val[e.b]); break;
+                case DEHALO_EXPR_PRODUCT: val[i] = f->mul(val[e.a], val[e.b]); break;
+                default: val[i] = f->mul(val[e.a], f->mul(cs.constants[e.b], f->one)); break;      // SCALED
+            }
+        }
+    }
+    void permutation() {      // permutation::verifier::Evaluated::expressions
+        const uint32_t S = pl.S, chunk = cs.chunk_len();
+        auto column_eval = [&](const dehalo_column_query& q) {
+            return q.kind == DEHALO_COLUMN_ADVICE ? ev(pl.adv(c) + q.index, 0) : q.kind == DEHALO_COLUMN_FIXED ? ev(pl.p_fixed + q.index, 0) : instance_eval(q.index, 0);
+        };
+        fold(f->mul(l_0, f->sub(f->one, ev(pl.pz(c), 0))));
+        const Fe zl = ev(pl.pz(c) + S - 1, 0);
+        fold(f->mul(l_last, f->sub(f->sqr(zl), zl)));
+        for (uint32_t s = 1; s < S; s++) fold(f->mul(l_0, f->sub(ev(pl.pz(c) + s, 0), ev(pl.pz(c) + s - 1, last))));
+        Fe cur = f->mul(w.beta, w.x);      // beta x delta^j, running across the sets' column chunks
+        for (uint32_t s = 0; s < S; s++) {
+            Fe left = ev(pl.pz(c) + s, 1), right = ev(pl.pz(c) + s, 0);
+            for (size_t j = (size_t)s * chunk; j < std::min<size_t>((size_t)(s + 1) * chunk, cs.perm_cols.size()); j++) {
+                const Fe cv = column_eval(cs.perm_cols[j]);
+                left = f->mul(left, f->add(f->add(cv, f->mul(w.beta, ev(pl.p_sigma + (uint32_t)j, 0))), w.gamma));
+                right = f->mul(right, f->add(f->add(cv, cur), w.gamma));
+                cur = f->mul(cur, f->delta);
+            }
+            fold(f->mul(f->sub(left, right), active));
+        }
+    }
+    void lookup(uint32_t l) {      // lookup::verifier::Evaluated::expressions
+        const uint32_t zc = pl.lz(c) + l, ai = pl.perm(c) + 2 * l, ti = ai + 1;
+        const Fe &z0 = ev(zc, 0), &z1 = ev(zc, 1), &a0 = ev(ai, 0), &am1 = ev(ai, -1), &s0 = ev(ti, 0);
+        const Fe left = f->mul(f->mul(z1, f->add(a0, w.beta)), f->add(s0, w.gamma));
+        const Fe right = f->mul(f->mul(z0, f->add(compress(cs.lookups[l].inputs), w.beta)), f->add(compress(cs.lookups[l].tables), w.gamma));
+        fold(f->mul(l_0, f->sub(f->one, z0)));
+        fold(f->mul(l_last, f->sub(f->sqr(z0), z0)));
+        fold(f->mul(f->sub(left, right), active));
+        fold(f->mul(l_0, f->sub(a0, s0)));
+        fold(f->mul(f->mul(f->sub(a0, s0), f->sub(a0, am1)), active));
+    }
+    void shuffle(uint32_t j) {      // shuffles: l0 (1 - z), l_last (z^2 - z), l_active (z(wx) (S + gamma) - z(x) (A + gamma))
+        const Fe &z0 = ev(pl.sz(c) + j, 0), &z1 = ev(pl.sz(c) + j, 1);
+        fold(f->mul(l_0, f->sub(f->one, z0)));
+        fold(f->mul(l_last, f->sub(f->sqr(z0), z0)));
+        fold(f->mul(f->sub(f->mul(z1, f->add(compress(cs.shuffles[j].tables), w.gamma)), f->mul(z0, f->add(compress(cs.shuffles[j].inputs), w.gamma))), active));
+    }
+};
+// expected_h [UPSTREAM plonk/verifier.rs]: every circuit's gates, then its permutation, lookup and shuffle expressions, at the read evaluations, folded with y
+inline Fe expected_h(const VerifierKey& vk, const OpeningPlan& pl, const WalkRead& w, const InstanceValues& instances) {
+    ExpectedH h(vk, pl, w, instances);
+    for (h.c = 0; h.c < pl.circuits; h.c++) {
+        h.graph();
+        for (uint32_t g : vk.cs.gates) h.fold(h.val[g]);
+        if (pl.S) h.permutation();
+        for (uint32_t l = 0; l < pl.L; l++) h.lookup(l);
+        for (uint32_t j = 0; j < pl.H; j++) h.shuffle(j);
+    }
+    return h.acc;
+}
+
+// What the three reductions share: the value and the commitment behind a query, and the points x omega^rot of the plan's rotations (points[i]: pl.point_rot[i]).
+struct WalkQueries {
+    const HostField* f; const OpeningPlan& pl; WalkRead& w; VerifyTerms& out;
+    Fe hfold_eval;     // the folded quotient's value, expected_h / (x^n - 1)  (x^n = 1 with negligible probability: the value is then 0 and the check fails)
+    std::vector<Fe> points;
+    WalkQueries(const VerifierKey& vk, const OpeningPlan& pl_, WalkRead& w_, const Fe& expected_h_, VerifyTerms& out_) : f(vk.f), pl(pl_), w(w_), out(out_) {
+        hfold_eval = f->mul(expected_h_, f->invert(f->sub(w.xn, f->one)));
+        for (int32_t r : pl.point_rot) points.push_back(vk.dom.rotate_omega(w.x, r));
+    }
+    const Fe& eval_of(int64_t slot) const { return slot >= 0 ? w.E[(size_t)slot] : hfold_eval; }
+    // coef x the commitment of polynomial `poly`, to the right list; the folded quotient h = sum_i x^(n i) h_i goes to its pieces
+    void commitment_term(const Fe& coef, uint32_t poly) {
+        if (poly != pl.p_hfold) { out.right(coef, w.cm[poly]); return; }
+        Fe xp = coef;
+        for (uint32_t i = pl.p_hpiece; i < pl.p_instance; i++) {
+            out.right(xp, w.cm[i]);
+            xp = f->mul(xp, w.xn);
+        }
+    }
+};
+
+// The Lagrange bases of the point sets `sets` (indices into points) at `at`, set after set: per point a of a set  prod_{b != a} (at - z_b) / (z_a - z_b).  The
+// denominators are inverted in ONE batch, and with them the caller's own in `also`, in place.  A zero among them (two points coincide, `at` is an opening point:
+// negligible probability) has the inverse 0.
+inline std::vector<Fe> lagrange_basis_at(const HostField* f, const std::vector<Fe>& points, const std::vector<std::vector<uint32_t>>& sets, const Fe& at, std::vector<Fe>& also) {
+    std::vector<Fe> basis, inv = also;
+    for (const std::vector<uint32_t>& T : sets)
+        for (size_t a = 0; a < T.size(); a++) {
+            Fe num = f->one, den = f->one;
+            for (size_t b = 0; b < T.size(); b++)
+                if (b != a) { num = f->mul(num, f->sub(at, points[T[b]])); den = f->mul(den, f->sub(points[T[a]], points[T[b]])); }
+            basis.push_back(num);
+            inv.push_back(den);
+        }
+    if (!f->batch_invert(inv.data(), inv.size())) for (Fe& e : inv) e = f->invert(e);
+    std::copy(inv.begin(), inv.begin() + also.size(), also.begin());
+    for (size_t i = 0; i < basis.size(); i++) basis[i] = f->mul(basis[i], inv[also.size() + i]);
+    return basis;
+}
+
+// VerifierGWC::verify_proof.  (Groups and points are numbered alike, by the first appearance of their rotation: group gi opens at points[gi].)
+inline VerifyWalkResult reduce_gwc(const VerifierKey& vk, WalkQueries& q, const Fe& weight) {
+    const HostField* f = q.f; const OpeningPlan& pl = q.pl;
+    const Fe v = q.w.t.squeeze();
+    std::vector<const uint64_t*> W;
+    for (size_t gi = 0; gi < pl.groups.size(); gi++) W.push_back(q.w.point());
+    const Fe u = q.w.t.squeeze();
+    Fe pu = weight, eval_multi{};
+    for (size_t gi = 0; gi < pl.groups.size(); gi++) {
+        const OpeningPlan::Group& g = pl.groups[gi];
+        q.out.left(pu, W[gi]);
+        q.out.right(f->mul(pu, q.points[gi]), W[gi]);
+        Fe pv = pu;
+        for (size_t j = 0; j < g.polys.size(); j++) {
+            q.commitment_term(pv, g.polys[j]);
+            eval_multi = f->add(eval_multi, f->mul(pv, q.eval_of(g.evals[j])));
+            pv = f->mul(pv, v);
+        }
+        pu = f->mul(pu, u);
+    }
+    q.out.right(f->neg(eval_multi), vk.g0);
+    return VERIFY_WALK_OK;
+}
+
+// VerifierSHPLONK::verify_proof over the plan's intermediate sets.  (u an opening point, or two points coinciding: inverses taken as 0, and the pairing fails.)
+inline VerifyWalkResult reduce_shplonk(const VerifierKey& vk, WalkQueries& q, const Fe& weight) {
+    const HostField* f = q.f; const OpeningPlan& pl = q.pl;
+    const Fe y = q.w.t.squeeze(), v = q.w.t.squeeze();
+    const uint64_t* h = q.w.point();
+    const Fe u = q.w.t.squeeze();
+    const uint64_t* h2 = q.w.point();
+    const size_t ns = pl.point_sets.size();
+    std::vector<Fe> zdiff(ns, f->one);      // per set: prod over the points outside it (u - point)
+    Fe z_0 = f->one;                        // prod over set 0's points (u - point)
+    for (size_t si = 0; si < ns; si++) {
+        const std::vector<uint32_t>& T = pl.point_sets[si];
+        for (uint32_t pi = 0; pi < q.points.size(); pi++)
+            if (std::find(T.begin(), T.end(), pi) == T.end()) zdiff[si] = f->mul(zdiff[si], f->sub(u, q.points[pi]));
+            else if (si == 0) z_0 = f->mul(z_0, f->sub(u, q.points[pi]));
+    }
+    std::vector<Fe> zdiff_0_inv(zdiff.begin(), zdiff.begin() + 1);      // (the quotient's query makes every plan's first set)
+    const std::vector<Fe> basis = lagrange_basis_at(f, q.points, pl.point_sets, u, zdiff_0_inv);
+    Fe vi = weight, r_total{};
+    const Fe* set_basis = basis.data();
+    for (size_t si = 0; si < ns; si++) {
+        const size_t np = pl.point_sets[si].size();
+        Fe yj = f->mul(f->mul(vi, zdiff[si]), zdiff_0_inv[0]);      // c_i = v^i zdiff_i / zdiff_0, then times y^j
+        for (uint32_t ci : pl.set_members[si]) {
+            const OpeningPlan::Commitment& m = pl.commitments[ci];
+            Fe r{};
+            for (size_t a = 0; a < np; a++) r = f->add(r, f->mul(set_basis[a], q.eval_of(m.evals[a])));
+            q.commitment_term(yj, m.poly);
+            r_total = f->add(r_total, f->mul(yj, r));
+            yj = f->mul(yj, y);
+        }
+        vi = f->mul(vi, v);
+        set_basis += np;
+    }
+    q.out.right(f->neg(r_total), vk.g0);
+    q.out.right(f->neg(f->mul(weight, z_0)), h);
+    q.out.right(f->mul(weight, u), h2);
+    q.out.left(weight, h2);
+    return VERIFY_WALK_OK;
+}
+
+// VerifierIPA::verify_proof over the plan's intermediate sets, then the opening argument's check of the final commitment P (ipa_reduce_opening).  MALFORMED: a
+// scalar is not below r; OPENING: x_3 is an opening point, a round challenge is zero.
+inline VerifyWalkResult reduce_ipa_multiopen(const VerifierKey& vk, WalkQueries& q, const Fe& weight) {
+    const HostField* f = q.f; const OpeningPlan& pl = q.pl;
+    dehalo_transcript& t = q.w.t;
+    const Fe x1 = t.squeeze(), x2 = t.squeeze();
+    const uint64_t* f_commitment = q.w.point();
+    const Fe x3 = t.squeeze();
+    const size_t ns = pl.point_sets.size();
+    std::vector<Fe> q_evals(ns);
+    for (Fe& e : q_evals)
+        if (!t.read_scalar(e)) return VERIFY_WALK_MALFORMED;
+    std::vector<Fe> vanish_inv(ns, f->one);      // per set: prod over its points (x_3 - point), then its inverse
+    for (size_t si = 0; si < ns; si++)
+        for (uint32_t pi : pl.point_sets[si]) {
+            const Fe diff = f->sub(x3, q.points[pi]);
+            if (diff.is_zero()) return VERIFY_WALK_OPENING;
+            vanish_inv[si] = f->mul(vanish_inv[si], diff);
+        }
+    const std::vector<Fe> basis = lagrange_basis_at(f, q.points, pl.point_sets, x3, vanish_inv);
+    // per set: the x_1-folded evaluations at its points, their interpolant's value at x_3, and (q_eval - that) / prod (x_3 - point), folded with x_2
+    Fe f_eval{};
+    const Fe* set_basis = basis.data();
+    for (size_t si = 0; si < ns; si++) {
+        const size_t np = pl.point_sets[si].size();
+        std::vector<Fe> evs(np, Fe{});
+        for (uint32_t ci : pl.set_members[si])
+            for (size_t a = 0; a < np; a++) evs[a] = f->add(f->mul(evs[a], x1), q.eval_of(pl.commitments[ci].evals[a]));
+        Fe r{};
+        for (size_t a = 0; a < np; a++) r = f->add(r, f->mul(evs[a], set_basis[a]));
+        f_eval = f->add(f->mul(f_eval, x2), f->mul(f->sub(q_evals[si], r), vanish_inv[si]));
+        set_basis += np;
+    }
+    const Fe x4 = t.squeeze();
+    // P = x_4^ns f + sum_si x_4^(ns - 1 - si) q_si,  q_si = sum_m x_1^(M - 1 - m) C_m: never formed, its scalars go to the commitments; v likewise
+    std::vector<Fe> x4p(ns + 1, weight);      // weight x_4^i
+    for (size_t i = 1; i <= ns; i++) x4p[i] = f->mul(x4p[i - 1], x4);
+    q.out.right(x4p[ns], f_commitment);
+    Fe v = f_eval;
+    for (size_t si = 0; si < ns; si++) {
+        const std::vector<uint32_t>& M = pl.set_members[si];
+        Fe coef = x4p[ns - 1 - si];
+        for (size_t m = M.size(); m-- > 0;) {
+            q.commitment_term(coef, pl.commitments[M[m]].poly);
+            coef = f->mul(coef, x1);
+        }
+        v = f->add(f->mul(v, x4), q_evals[si]);
+    }
+    return ipa_reduce_opening(f, t, [&] { return q.w.point(); }, pl.k, weight, x3, v, vk.g0, vk.u, vk.w, q.out);
+}
+
+// One proof whose length is the shape's and whose points are decoded (none refused): read, expected_h and the reduction of the key's scheme and multiopen, the
+// terms appended to `out` under `weight`.  On MALFORMED or OPENING (walk_read, reduce_ipa_multiopen) nothing of `out` is meaningful.
+inline VerifyWalkResult verify_walk(const VerifierKey& vk, const OpeningPlan& pl, const uint8_t* proof, size_t len, const uint64_t* pts, const InstanceValues& instances,
+                                    const uint64_t* instance_cm, const Fe& weight, VerifyTerms& out) {
+    WalkRead w;
+    const VerifyWalkResult read = walk_read(vk, pl, proof, len, pts, instances, instance_cm, w);
+    if (read != VERIFY_WALK_OK) return read;
+    WalkQueries q(vk, pl, w, expected_h(vk, pl, w, instances), out);
+    if (vk.scheme == DEHALO_SCHEME_IPA) return reduce_ipa_multiopen(vk, q, weight);
+    return vk.multiopen == DEHALO_MULTIOPEN_SHPLONK ? reduce_shplonk(vk, q, weight) : reduce_gwc(vk, q, weight);
+}
+
+// ---- one call: `count` proofs under one key.  instances[(i N + c) nic + j] / instance_lens likewise: proof i's circuit c's column j (Montgomery words, any
+// residue); weights: count scalars (Montgomery).  verify_check_arguments fills `plan`; the caller sets `weights` after it.
+struct VerifyInput {
+    const uint8_t* const* proofs = nullptr; const size_t* lens = nullptr; uint32_t count = 0;
+    const uint64_t* const* instances = nullptr; const size_t* instance_lens = nullptr;
+    uint32_t nic = 0, N = 0;      // instance columns; circuits a proof
+    const Fe* weights = nullptr;
+    OpeningPlan plan;
+};
+// What the call found.  accept: every proof is readable and the check holds; first_malformed: the first unreadable proof or -1; reason: a dehalo_reject_reason
+struct VerifyVerdict { int accept = 0; int64_t first_malformed = -1; int reason = DEHALO_REJECT_NONE; VerifyStats stats; };
+inline int verify_fail(std::string* error, int rc, const std::string& why) { if (error) *error = why; return rc; }
+
+// the caller's errors of a verify call, before anything is read or drawn: 0 -- and in.plan is the call's opening plan --, DEHALO_ERR_INVALID, or
+// DEHALO_ERR_UNSUPPORTED for a shape the opening plan refuses
+inline int verify_check_arguments(const VerifierKey& vk, VerifyInput& in, std::string* error) {
+    if (in.count && (!in.proofs || !in.lens)) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: null argument");
+    if (in.N == 0) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: no circuit");
+    if (in.count && in.nic != vk.cs.num_instance) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: instances.len() != num_instance_columns");
+    if (in.nic && in.count && (!in.instances || !in.instance_lens)) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: null instances");
+    in.plan = OpeningPlan(vk.opening_shape(in.N));
+    if (!in.plan.error.empty()) return verify_fail(error, DEHALO_ERR_UNSUPPORTED, in.plan.error);
+    const size_t usable = vk.dom.n - (vk.cs.blinding_factors() + 1);
+    for (size_t e = 0; e < (size_t)in.count * in.N * in.nic; e++) {
+        if (in.instance_lens[e] > usable) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: an instance column is longer than the usable rows");
+        if (in.instance_lens[e] && !in.instances[e]) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: null instance column");
     }
     return 0;
 }
 
-inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
-                              const size_t* instance_lens, uint32_t num_instance_columns, uint32_t N, const Fe* weights, int* accept, int64_t* first_malformed, int* reason,
-                              VerifyStats* stats, std::string* error) {
-    typedef std::chrono::steady_clock clk;
-    auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
-    auto fail = [&](int rc, const std::string& why) { if (error) *error = why; return rc; };
-    const HostField* f = vk.f;
-    if (!accept || (count && !weights)) return fail(DEHALO_ERR_INVALID, "verify_proofs: null argument");
-    const int bad = verify_check_arguments(vk, proofs, lens, count, instances, instance_lens, num_instance_columns, N, error);
-    if (bad) return bad;
-    const OpeningPlan pl(vk.opening_shape(N));
-    const bool ipa = vk.scheme == DEHALO_SCHEME_IPA;
+// the proofs of a call whose length is the shape's (`sized` of them, proof i the slot_of[i]-th), their np points each decoded, their instance columns' values and,
+// under IPA, those columns' commitments (nic a proof, in the order of the slots)
+struct VerifyStaged {
+    size_t np = 0, sized = 0;
+    std::vector<size_t> slot_of;
+    std::vector<uint8_t> malformed;      // per proof: bytes missing or trailing; later a refused point, a scalar not below r
+    std::vector<uint64_t> xy, inst_cm;
+    std::vector<InstanceValues> inst_of;
+    const uint64_t* points(uint32_t i) const { return xy.data() + 8 * np * slot_of[i]; }
+};
+
+// every proof's points, decoded in one call of the backend
+inline int stage_points(const VerifierKey& vk, VerifyBackend& be, const VerifyInput& in, VerifyStaged& sg, VerifyStats& st, std::string* error) {
     const int mo = vk.multiopen == DEHALO_MULTIOPEN_SHPLONK ? DEHALO_MULTIOPEN_SHPLONK : DEHALO_MULTIOPEN_GWC;
-    const size_t size = pl.proof_size(ipa ? OpeningPlan::IPA : mo == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC);
-    const std::vector<std::pair<size_t, size_t>> runs = verify_point_runs(pl, vk.scheme, mo);
-    size_t np = 0;
-    for (auto& r : runs) np += r.second;
-    if (first_malformed) *first_malformed = -1;
-    if (reason) *reason = DEHALO_REJECT_NONE;
-    *accept = 0;
-    VerifyStats st;
-
-    // ---- every proof's points, decoded in one call of the backend
-    std::vector<uint8_t> malformed(count, 0);
-    std::vector<size_t> slot_of(count, 0);
+    const size_t size = in.plan.proof_size(vk.scheme == DEHALO_SCHEME_IPA ? OpeningPlan::IPA : mo == DEHALO_MULTIOPEN_SHPLONK ? OpeningPlan::SHPLONK : OpeningPlan::GWC);
+    const std::vector<std::pair<size_t, size_t>> runs = verify_point_runs(in.plan, vk.scheme, mo);
+    for (auto& r : runs) sg.np += r.second;
+    sg.malformed.assign(in.count, 0);
+    sg.slot_of.assign(in.count, 0);
     std::vector<uint8_t> enc;
-    size_t sized = 0;
-    for (uint32_t i = 0; i < count; i++) {
-        if (lens[i] != size || !proofs[i]) { malformed[i] = 1; continue; }      // bytes missing or trailing
-        slot_of[i] = sized++;
-        for (auto& r : runs) enc.insert(enc.end(), proofs[i] + r.first, proofs[i] + r.first + 32 * r.second);
+    for (uint32_t i = 0; i < in.count; i++) {
+        if (in.lens[i] != size || !in.proofs[i]) { sg.malformed[i] = 1; continue; }      // bytes missing or trailing
+        sg.slot_of[i] = sg.sized++;
+        for (auto& r : runs) enc.insert(enc.end(), in.proofs[i] + r.first, in.proofs[i] + r.first + 32 * r.second);
     }
-    std::vector<uint64_t> xy(8 * np * sized + 8);
-    clk::time_point t0 = clk::now();
-    if (sized) {
-        const int rc = be.decompress(enc.data(), np * sized, xy.data());
-        if (rc) return fail(rc, "verify_proofs: point decompression failed");
-    }
-    st.decompress = ms(t0);
+    sg.xy.assign(8 * sg.np * sg.sized + 8, 0);
+    VerifyClock clock;
+    const int rc = sg.sized ? be.decompress(enc.data(), sg.np * sg.sized, sg.xy.data()) : 0;
+    st.decompress = clock.lap();
+    return rc ? verify_fail(error, rc, "verify_proofs: point decompression failed") : 0;
+}
 
-    // ---- the instance columns' values; under IPA their commitments, every column of every proof in one batch of the backend
-    const uint32_t nic = num_instance_columns;
-    std::vector<std::vector<std::vector<std::vector<Fe>>>> inst_of(count);
-    for (uint32_t i = 0; i < count; i++) {
-        if (malformed[i]) continue;
-        inst_of[i].assign(N, std::vector<std::vector<Fe>>(nic));
-        for (uint32_t c = 0; c < N; c++)
-            for (uint32_t j = 0; j < nic; j++) {
-                const size_t e = ((size_t)i * N + c) * nic + j;
-                inst_of[i][c][j].resize(instance_lens[e]);
-                for (size_t r = 0; r < instance_lens[e]; r++) {
+// the instance columns' values; under IPA their commitments, every column of every proof in one batch of the backend
+inline int stage_instances(const VerifierKey& vk, VerifyBackend& be, const VerifyInput& in, VerifyStaged& sg, std::string* error) {
+    sg.inst_of.resize(in.count);
+    for (uint32_t i = 0; i < in.count; i++) {
+        if (sg.malformed[i]) continue;
+        sg.inst_of[i].assign(in.N, std::vector<std::vector<Fe>>(in.nic));
+        for (uint32_t c = 0; c < in.N; c++)
+            for (uint32_t j = 0; j < in.nic; j++) {
+                const size_t e = ((size_t)i * in.N + c) * in.nic + j;
+                std::vector<Fe>& column = sg.inst_of[i][c][j];
+                column.resize(in.instance_lens[e]);
+                for (size_t r = 0; r < column.size(); r++) {
                     Fe w;
-                    memcpy(w.v, instances[e] + 4 * r, 32);
-                    inst_of[i][c][j][r] = f->mul(w, f->one);      // a word stands for its residue
+                    memcpy(w.v, in.instances[e] + 4 * r, 32);
+                    column[r] = vk.f->mul(w, vk.f->one);      // a word stands for its residue
                 }
             }
     }
-    std::vector<uint64_t> inst_cm(8 * (size_t)sized * nic + 8);
-    if (ipa && sized && nic) {      // (N = 1: the plan refuses more)
-        std::vector<const Fe*> cols;
-        std::vector<size_t> col_lens;
-        for (uint32_t i = 0; i < count; i++)
-            for (uint32_t j = 0; j < nic && !malformed[i]; j++) { cols.push_back(inst_of[i][0][j].data()); col_lens.push_back(inst_of[i][0][j].size()); }
-        const int rc = be.instance_commitments(cols.data(), col_lens.data(), cols.size(), inst_cm.data());
-        if (rc) return fail(rc, "verify_proofs: the instance columns' commitments failed");
-    }
+    sg.inst_cm.assign(8 * sg.sized * in.nic + 8, 0);
+    if (vk.scheme != DEHALO_SCHEME_IPA || !sg.sized || !in.nic) return 0;
+    std::vector<const Fe*> cols;      // (N = 1: the plan refuses more)
+    std::vector<size_t> col_lens;
+    for (uint32_t i = 0; i < in.count; i++)
+        for (uint32_t j = 0; j < in.nic && !sg.malformed[i]; j++) { cols.push_back(sg.inst_of[i][0][j].data()); col_lens.push_back(sg.inst_of[i][0][j].size()); }
+    const int rc = be.instance_commitments(cols.data(), col_lens.data(), cols.size(), sg.inst_cm.data());
+    return rc ? verify_fail(error, rc, "verify_proofs: the instance columns' commitments failed") : 0;
+}
 
-    // ---- the walks
-    t0 = clk::now();
-    VerifyTerms terms;
+// the walks: every staged proof's terms under its weight.  -> some readable proof is no proof (x_3 at an opening point, a zero round challenge)
+inline bool run_walks(const VerifierKey& vk, const VerifyInput& in, VerifyStaged& sg, VerifyTerms& terms) {
     bool opening_rejected = false;
-    for (uint32_t i = 0; i < count; i++) {
-        if (malformed[i]) continue;
-        const uint64_t* pts = xy.data() + 8 * np * slot_of[i];
-        for (size_t j = 0; j < np && !malformed[i]; j++) {
-            bool zero = true;
-            for (int w = 0; w < 8; w++) zero = zero && pts[8 * j + w] == 0;
-            if (zero) malformed[i] = 1;      // refused by the decoder, or the identity
-        }
-        if (malformed[i]) continue;
-        const VerifyWalkResult wr = verify_walk(vk, pl, N, proofs[i], lens[i], pts, inst_of[i], inst_cm.data() + 8 * slot_of[i] * nic, f->mul(weights[i], f->one), terms);
-        if (wr == VERIFY_WALK_MALFORMED) malformed[i] = 1;
+    for (uint32_t i = 0; i < in.count; i++) {
+        if (sg.malformed[i]) continue;
+        const uint64_t* pts = sg.points(i);
+        for (size_t j = 0; j < sg.np && !sg.malformed[i]; j++)
+            if (g1_affine_is_zero(pts + 8 * j)) sg.malformed[i] = 1;      // refused by the decoder, or the identity
+        if (sg.malformed[i]) continue;
+        const VerifyWalkResult wr = verify_walk(vk, in.plan, in.proofs[i], in.lens[i], pts, sg.inst_of[i], sg.inst_cm.data() + 8 * sg.slot_of[i] * in.nic,
+                                                vk.f->mul(in.weights[i], vk.f->one), terms);
+        if (wr == VERIFY_WALK_MALFORMED) sg.malformed[i] = 1;
         if (wr == VERIFY_WALK_OPENING) opening_rejected = true;
     }
-    st.walk = ms(t0);
-    for (uint32_t i = 0; i < count; i++)
-        if (malformed[i]) {
-            if (first_malformed) *first_malformed = i;
-            if (reason) *reason = DEHALO_REJECT_MALFORMED;
-            if (stats) *stats = st;
-            return 0;
-        }
+    return opening_rejected;
+}
 
-    if (opening_rejected) {      // readable, and no proof: x_3 at an opening point, a zero round challenge
-        if (reason) *reason = DEHALO_REJECT_OPENING;
-        if (stats) *stats = st;
-        return 0;
-    }
-    if (ipa) {      // ---- accept iff  sum over the fresh bases + sum over g = the identity: two affine results, compared here
-        t0 = clk::now();
-        uint64_t fresh[8] = {}, gs[8] = {};
-        if (count) {
-            const int rc = be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), fresh);
-            if (rc) return fail(rc, "verify_proofs: the multi-scalar multiplication failed");
-        }
-        st.msm = ms(t0);
-        t0 = clk::now();
-        if (count) {
-            const int rc = be.g_sum(terms.us.data(), terms.inits.data(), count, pl.k, gs);
-            if (rc) return fail(rc, "verify_proofs: the sum over g failed");
-        }
-        st.pairing = ms(t0);
-        const bool is_identity = ipa_sums_cancel(vk.fq, fresh, gs);
-        *accept = is_identity ? 1 : 0;
-        if (reason && !is_identity) *reason = DEHALO_REJECT_OPENING;
-        if (stats) *stats = st;
-        return 0;
-    }
+// The IPA acceptance, the one statement of it (a call's last step, and dehalo_ipa_verify's): *accept = 1 iff  sum over the fresh bases + sum over g = the identity
+// -- two affine results of the backend, compared here.  Returns the backend's error.
+inline int decide_ipa(VerifyBackend& be, const VerifyTerms& terms, size_t count, uint32_t k, const HostField* fq, int* accept, VerifyStats* st = nullptr,
+                      std::string* error = nullptr) {
+    VerifyClock clock;
+    uint64_t fresh[8] = {}, gs[8] = {};      // (no proof: both sums are the identity)
+    int rc = count ? be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), fresh) : 0;
+    if (rc) return verify_fail(error, rc, "verify_proofs: the multi-scalar multiplication failed");
+    if (st) st->msm = clock.lap();
+    rc = count ? be.g_sum(terms.us.data(), terms.inits.data(), count, k, gs) : 0;
+    if (rc) return verify_fail(error, rc, "verify_proofs: the sum over g failed");
+    if (st) st->pairing = clock.lap();
+    Fe gy;
+    memcpy(gy.v, gs + 4, 32);
+    gy = fq->neg(gy);      // -(x, y) = (x, -y); (0, 0) stays the identity
+    *accept = memcmp(fresh, gs, 32) == 0 && memcmp(fresh + 4, gy.v, 32) == 0 ? 1 : 0;
+    return 0;
+}
 
-    // ---- the two sums and the pairing check
-    t0 = clk::now();
+// The KZG acceptance: the two sums, then *accept = 1 iff  e(L, s_g2) e(-R, g2) = 1
+inline int decide_kzg(const VerifierKey& vk, VerifyBackend& be, const VerifyTerms& terms, int* accept, VerifyStats& st, std::string* error) {
+    VerifyClock clock;
     uint64_t sums[16] = {};      // L | R
     if (!terms.ls.empty()) {
         int rc = be.msm(terms.ls.data(), terms.lp.data(), terms.ls.size(), sums);
         if (!rc) rc = be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), sums + 8);
-        if (rc) return fail(rc, "verify_proofs: the multi-scalar multiplication failed");
+        if (rc) return verify_fail(error, rc, "verify_proofs: the multi-scalar multiplication failed");
     }
-    st.msm = ms(t0);
-    t0 = clk::now();
+    st.msm = clock.lap();
     Fe ry;
     memcpy(ry.v, sums + 12, 32);
     ry = vk.fq->neg(ry);      // -R ((0, 0) stays the identity)
@@ -702,17 +747,42 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const ui
     uint8_t g2s[256];
     memcpy(g2s, vk.s_g2, 128);
     memcpy(g2s + 128, vk.g2, 128);
-    int is_one = 0;
     const PairingHost* ph = pairing_host(vk.curve);
-    if (!ph) return fail(DEHALO_ERR_UNSUPPORTED, "verify_proofs: no pairing on this curve");
+    if (!ph) return verify_fail(error, DEHALO_ERR_UNSUPPORTED, "verify_proofs: no pairing on this curve");
     // (g2 and s_g2 passed the constructor's checks, a proof's points the decoder's: a sum off the curve can only come from a key's commitment that was read
     // unchecked and is no point.  Nothing such a key verifies is valid: the proof is rejected, the call is not in error.)
+    int is_one = 0;
     const int rc = ph->check(sums, g2s, 2, &is_one, /* g2_subgroup_known */ true);
     if (rc == DEHALO_ERR_INVALID) is_one = 0;
-    else if (rc) return fail(rc, "verify_proofs: the pairing check failed");
-    st.pairing = ms(t0);
+    else if (rc) return verify_fail(error, rc, "verify_proofs: the pairing check failed");
+    st.pairing = clock.lap();
     *accept = is_one ? 1 : 0;
-    if (reason && !is_one) *reason = DEHALO_REJECT_PAIRING;
-    if (stats) *stats = st;
+    return 0;
+}
+
+// `in` as verify_check_arguments left it, with its weights: out.accept = 1 iff every proof is readable and  e(sum_i w_i L_i, s_g2) e(-sum_i w_i R_i, g2) = 1  (IPA:
+// decide_ipa's identity).  Returns 0 whenever the check ran; DEHALO_ERR_INVALID without weights or the backend's error, and `out` is then as it was made.
+inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const VerifyInput& in, VerifyVerdict& out, std::string* error) {
+    if (in.count && !in.weights) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs: null argument");
+    VerifyVerdict v;
+    VerifyStaged sg;
+    int rc = stage_points(vk, be, in, sg, v.stats, error);
+    if (!rc) rc = stage_instances(vk, be, in, sg, error);
+    if (rc) return rc;
+    VerifyClock clock;
+    VerifyTerms terms;
+    const bool opening_rejected = run_walks(vk, in, sg, terms);
+    v.stats.walk = clock.lap();
+    for (uint32_t i = 0; i < in.count && v.first_malformed < 0; i++)
+        if (sg.malformed[i]) v.first_malformed = i;
+    if (v.first_malformed >= 0) v.reason = DEHALO_REJECT_MALFORMED;
+    else if (opening_rejected) v.reason = DEHALO_REJECT_OPENING;      // readable, and no proof
+    else {
+        const bool ipa = vk.scheme == DEHALO_SCHEME_IPA;
+        rc = ipa ? decide_ipa(be, terms, in.count, in.plan.k, vk.fq, &v.accept, &v.stats, error) : decide_kzg(vk, be, terms, &v.accept, v.stats, error);
+        if (rc) return rc;
+        if (!v.accept) v.reason = ipa ? DEHALO_REJECT_OPENING : DEHALO_REJECT_PAIRING;
+    }
+    out = v;
     return 0;
 }
