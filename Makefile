@@ -98,4 +98,9 @@ verify_ipa_host_check: tests/native_host/verify_ipa_host_check.cpp tests/native_
 g1_host_check: tests/native_host/g1_host_check.cpp $(CSRC)/g1_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/blake2b.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/g1_host_check tests/native_host/g1_host_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check verify_ipa_host_check g1_host_check
+# the units of witness generation below dehalo_synthesize (csrc/bigint_host.hpp, poseidon_host.hpp, maingate_host.hpp: host only) on the cases on stdin, under
+# ASan + UBSan (tests/test_witness.py feeds it Knuth's add-back cases, the reference's Poseidon vectors and the RangeChip tables); -O0 as for opening_plan_check
+witness_units_check: tests/native_host/witness_units_check.cpp $(CSRC)/bigint_host.hpp $(CSRC)/poseidon_host.hpp $(CSRC)/maingate_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/witness_units_check tests/native_host/witness_units_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan witness_units_check msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check verify_ipa_host_check g1_host_check

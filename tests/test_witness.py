@@ -617,3 +617,82 @@ def test_synthesized_circuits_pass_the_checkers_own_row_check(pkg, oracles):
         kw.update(bad_inputs)
         with pytest.raises(ValueError):
             native.synthesize(native.CIRCUIT_DELAY_ENC, 14, **kw)
+
+
+_POOL = [0, 1, 2, (1 << 32) - 1, 1 << 32, (1 << 63) - 1, 1 << 63, (1 << 63) + 1, (1 << 64) - 2, (1 << 64) - 1]
+
+
+def _int_of(limbs):
+    return sum(v << (64 * i) for i, v in enumerate(limbs))
+
+
+def _knuth_d_add_backs(u, v):
+    """Knuth's algorithm D on 64-bit limbs as csrc/bigint_host.hpp big_divmod runs it (same normalisation, same qhat correction): how many quotient digits
+    needed the add-back step.  0 on the paths that never reach the loop (u < v, a one-limb divisor)."""
+    M, U, V = (1 << 64) - 1, _int_of(u), _int_of(v)
+    n, nu = (V.bit_length() + 63) // 64, (U.bit_length() + 63) // 64
+    if n < 2 or U < V:
+        return 0
+    s = 64 * n - V.bit_length()
+    vn = [((V << s) >> (64 * i)) & M for i in range(n)]
+    un = [((U << s) >> (64 * i)) & M for i in range(nu + 1)]
+    hits = 0
+    for j in range(nu - n, -1, -1):
+        qhat, rhat = divmod((un[j + n] << 64) | un[j + n - 1], vn[n - 1])
+        while qhat >> 64 or qhat * vn[n - 2] > ((rhat << 64) | un[j + n - 2]):
+            qhat, rhat = qhat - 1, rhat + vn[n - 1]
+            if rhat >> 64:
+                break
+        w = _int_of(un[j:j + n + 1]) - qhat * (V << s)
+        if w < 0:      # qhat was one too large: add back
+            hits, w = hits + 1, w + (V << s)
+        un[j:j + n + 1] = [(w >> (64 * i)) & M for i in range(n + 1)]
+    assert _int_of(un) >> s == U % V
+    return hits
+
+
+def test_witness_units_on_their_own(pkg):
+    """The units below dehalo_synthesize, in a stand-alone program built with -fsanitize=address,undefined (make witness_units_check):
+    big_divmod / big_mul against Python's integers on the paths by hand (one-limb divisor, u < v, equal operands, shift 0, zero high limbs) and on 6000
+    seeded cases with limbs from a small structured pool, of which the model above sends 38 through Knuth's add-back step (uniform limbs send none: the
+    floor of 20 keeps the draw from silently losing the branch, with a margin of 18 at this seed); PoseidonSpec::permute on the reference's vectors;
+    RangeLens against plonk.range_bit_lens / range_tag at 16, 32 and 33 limbs."""
+    import random
+    import subprocess
+    from conftest import ROOT
+    from dehalo2_amd import plonk
+
+    M = (1 << 64) - 1
+    top = 1 << 63
+    divs = [([5, 6, 7], [9]), ([5, 6, 7], [9, 0, 0]), ([M, M, M], [M]), ([1, 2], [3, 4, 5]), ([0], [7, 1]), ([], [7, 1]), ([3, 4, 5], [3, 4, 5]), ([3, 4, 5, 0], [3, 4, 5]),
+            ([M, M, M, M], [1, top]), ([0, 0, 0, top], [M, top | 1]), ([7, 0, M, M, 0, 0], [M, 1, 0]), ([0, 0, 1], [0, 1]), ([M, M, M, M, M], [M, M, M])]
+    rnd = random.Random(2)
+    while len(divs) < 13 + 6000:
+        nv, extra = rnd.randint(2, 4), rnd.randint(1, 3)
+        v, u = [rnd.choice(_POOL) for _ in range(nv)], [rnd.choice(_POOL) for _ in range(nv + extra)]
+        if any(v):
+            divs.append((u, v))
+    add_backs = sum(1 for u, v in divs[13:] if _knuth_d_add_backs(u, v))
+    print("cases through the add-back step: %d of %d" % (add_backs, len(divs) - 13))
+    assert add_backs >= 20
+    num = lambda x: int(x, 0) if isinstance(x, str) else int(x)
+    kats = golden("poseidon_kat")
+    lines = ["div %s | %s" % (" ".join("%x" % x for x in u), " ".join("%x" % x for x in v)) for u, v in divs]
+    lines += ["kat %d %d %d %s" % (k["t"], k["r_f"], k["r_p"], " ".join("%x" % num(x) for x in k["input"])) for k in kats]
+    lines += ["range %d" % nl for nl in (16, 32, 33)]
+    out = subprocess.run(["make", "-C", ROOT, "witness_units_check"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "warning" not in out.stdout + out.stderr, out.stdout + out.stderr
+    run = subprocess.run([os.path.join(ROOT, "tests", "native_host", "witness_units_check")], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0 and "runtime error" not in run.stderr and "AddressSanitizer" not in run.stderr, run.stdout[-2000:] + run.stderr
+    got = run.stdout.splitlines()
+    assert len(got) == len(lines)
+    for (u, v), line in zip(divs, got):
+        U, V = _int_of(u), _int_of(v)
+        assert [int(w, 16) for w in line.split()] == [U // V, U % V, U * V], (u, v)
+    for k, line in zip(kats, got[len(divs):]):
+        assert [int(w, 16) for w in line.split()] == [num(x) for x in k["expected"]]
+    for nl, line in zip((16, 32, 33), got[len(divs) + len(kats):]):
+        bits, tags = (part.split() for part in line.split("|"))
+        want = plonk.range_bit_lens(nl)
+        assert tuple(int(b) for b in bits) == want
+        assert [int(t) for t in tags] == [plonk.range_tag(b, nl) if b in want else 0 for b in range(17)]
