@@ -85,12 +85,12 @@ pairing_check: tests/native_host/pairing_check.cpp $(CSRC)/pairing_host.hpp $(CS
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/pairing_check tests/native_host/pairing_check.cpp
 
 # verify_proof on the host (csrc/verify_host.hpp: host only) on proofs the test writes to a file, under ASan + UBSan (tests/test_verify_host.py)
-verify_host_check: tests/native_host/verify_host_check.cpp tests/native_host/verify_case_reader.hpp $(CSRC)/verify_host.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
+verify_host_check: tests/native_host/verify_host_check.cpp tests/native_host/verify_case_reader.hpp $(CSRC)/verify_host.hpp $(CSRC)/blame_search.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/verify_host_check tests/native_host/verify_host_check.cpp
 
 # verify_proof for IPA on the host (the same header, its IPA reduction and the host sums over g and g_lagrange) on proofs the test writes to a file, under ASan + UBSan
 # (tests/test_verify_ipa_host.py)
-verify_ipa_host_check: tests/native_host/verify_ipa_host_check.cpp tests/native_host/verify_case_reader.hpp $(CSRC)/verify_host.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
+verify_ipa_host_check: tests/native_host/verify_ipa_host_check.cpp tests/native_host/verify_case_reader.hpp $(CSRC)/verify_host.hpp $(CSRC)/blame_search.hpp $(CSRC)/pairing_host.hpp $(CSRC)/transcript_host.hpp $(CSRC)/opening_plan.hpp $(CSRC)/plonk_host.hpp $(CSRC)/key_format.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/blake2b.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/verify_ipa_host_check tests/native_host/verify_ipa_host_check.cpp
 
 # G1 points on the host (csrc/g1_host.hpp: the codec of one point, the status texts, the group law) against the transcript's proof bytes, under ASan + UBSan
@@ -103,4 +103,9 @@ g1_host_check: tests/native_host/g1_host_check.cpp $(CSRC)/g1_host.hpp $(CSRC)/t
 witness_units_check: tests/native_host/witness_units_check.cpp $(CSRC)/bigint_host.hpp $(CSRC)/poseidon_host.hpp $(CSRC)/maingate_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/witness_units_check tests/native_host/witness_units_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan witness_units_check msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check verify_ipa_host_check g1_host_check
+# the search behind dehalo_verify_proofs_each (csrc/blame_search.hpp: host only) over every bad set of up to 12 members, under ASan + UBSan
+# (tests/test_blame_search_host.py runs it); -O0 as for opening_plan_check
+blame_search_check: tests/native_host/blame_search_check.cpp $(CSRC)/blame_search.hpp
+	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/blame_search_check tests/native_host/blame_search_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan witness_units_check msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check verify_ipa_host_check g1_host_check blame_search_check

@@ -10,7 +10,8 @@
 //!   (benches/delay_enc.rs:123-131), keys and SRS read from the same RawBytes files the bench caches (`:45,54,88,94-98,105,111-115`).
 //!   A front-end that proves with `ProverSHPLONK` takes [`prover::create_proof_shplonk`] (`DehaloProver::set_multiopen`).
 //! * the check the benches end with (`:147-165`): [`verifier::verify_proof`] / [`verifier::verify_proof_shplonk`] on a [`verifier::DehaloVerifier`], which needs
-//!   the verifying key and three points of the params only, and with `ctx = None` no device.
+//!   the verifying key and three points of the params only, and with `ctx = None` no device; for many clients' proofs at once,
+//!   [`verifier::verify_proofs_each`]: a verdict per proof from one batch verification.
 pub mod arithmetic;
 pub mod constraint_system;
 pub mod params;

@@ -122,6 +122,29 @@ impl DehaloVerifier {
         })?;
         Ok(if accept != 0 { Ok(()) } else if first >= 0 { Err((Reject::Malformed, first)) } else { Err((Reject::Pairing, -1)) })
     }
+
+    /// A verdict per proof from one batch verification (`dehalo_verify_proofs_each`): entry i is `Ok(())` for a valid proof and otherwise what `verify` says of
+    /// proof i alone.  Arguments and the warning about `rng` as for `verify_batch`.  The second value is the number of pairing checks made: 1 when every
+    /// readable proof is valid, at most `1 + 2 b ceil(log2 n)` for b invalid proofs among n.
+    pub fn verify_each<R: RngCore + Send>(&self, instances: &[&[&[&[Fr]]]], proofs: &[&[u8]], rng: &mut R) -> Result<(Vec<Result<(), Reject>>, u32), DehaloError> {
+        let circuits = instances.first().map_or(1, |p| p.len().max(1));
+        let columns = instances.first().and_then(|p| p.first()).map_or(0, |c| c.len());
+        let ptrs: Vec<*const u64> = instances.iter().flat_map(|p| p.iter().flat_map(|c| c.iter().map(|col| col.as_ptr() as *const u64))).collect();
+        let lens: Vec<usize> = instances.iter().flat_map(|p| p.iter().flat_map(|c| c.iter().map(|col| col.len()))).collect();
+        let pp: Vec<*const u8> = proofs.iter().map(|p| p.as_ptr()).collect();
+        let pl: Vec<usize> = proofs.iter().map(|p| p.len()).collect();
+        let mut r = sys::dehalo_rng { kind: sys::DEHALO_RNG_CALLBACK, pcg_state: [0; 2], pcg_inc: [0; 2], fill: Some(fill_from::<R>), user: rng as *mut R as *mut c_void };
+        let mut reasons = vec![sys::DEHALO_REJECT_NONE; pp.len().max(1)];
+        let mut checks = 0u32;
+        self.check(unsafe {
+            sys::dehalo_verify_proofs_each(self.raw, pp.as_ptr(), pl.as_ptr(), pp.len() as u32, ptrs.as_ptr(), lens.as_ptr(), columns as u32, circuits as u32, &mut r,
+                                           reasons.as_mut_ptr(), &mut checks)
+        })?;
+        let verdicts = reasons[..pp.len()].iter().map(|&why| {
+            if why == sys::DEHALO_REJECT_NONE { Ok(()) } else if why == sys::DEHALO_REJECT_MALFORMED { Err(Reject::Malformed) } else { Err(Reject::Pairing) }
+        }).collect();
+        Ok((verdicts, checks))
+    }
 }
 
 impl Drop for DehaloVerifier {
@@ -140,6 +163,16 @@ pub fn verify_proof(verifier: &mut DehaloVerifier, instances: &[&[Fr]], proof: &
 pub fn verify_proof_shplonk(verifier: &mut DehaloVerifier, instances: &[&[Fr]], proof: &[u8]) -> Result<bool, DehaloError> {
     verifier.set_multiopen(sys::DEHALO_MULTIOPEN_SHPLONK)?;
     Ok(verifier.verify(&[instances], proof)?.is_ok())
+}
+
+/// Many clients prove, one party verifies: a verdict per proof from ONE batch verification (`dehalo_verify_proofs_each`).  `instances[i]`: proof i's instance
+/// columns (one circuit a proof); entry i of the result is `true` iff proof i is valid.  `rng` draws the batch weights and must be unpredictable to whoever made
+/// the proofs (`OsRng`).  One pairing check when every proof is valid, 13 for one invalid proof among 64 -- against 64 for verifying them singly.
+pub fn verify_proofs_each<R: RngCore + Send>(verifier: &DehaloVerifier, instances: &[&[&[Fr]]], proofs: &[&[u8]], rng: &mut R) -> Result<Vec<bool>, DehaloError> {
+    let circuits: Vec<[&[&[Fr]]; 1]> = instances.iter().map(|columns| [*columns]).collect();
+    let per_proof: Vec<&[&[&[Fr]]]> = circuits.iter().map(|c| &c[..]).collect();
+    let (verdicts, _checks) = verifier.verify_each(&per_proof, proofs, rng)?;
+    Ok(verdicts.iter().map(|v| v.is_ok()).collect())
 }
 
 /// The IPA verifier over Vesta (scalars in `pasta::Fp`): `dehalo_verifier` made by `dehalo_verifier_create_ipa_vk`.  It borrows the params.

@@ -45,6 +45,7 @@ SYMBOLS = [
     "dehalo_verifier_create", "dehalo_verifier_create_vk", "dehalo_verifier_set_transcript_repr", "dehalo_verifier_set_multiopen", "dehalo_verifier_release",
     "dehalo_verifier_create_error", "dehalo_verifier_last_error","dehalo_verifier_last_timings", "dehalo_verify_proof", "dehalo_verify_proofs",
     "dehalo_ipa_s_device", "dehalo_verifier_create_ipa", "dehalo_verifier_create_ipa_vk", "dehalo_verifier_create_ipa_host", "dehalo_ipa_verify",
+    "dehalo_msm_segments", "dehalo_msm_segments_device", "dehalo_verify_proofs_each",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -340,6 +341,10 @@ def load_library():
     lib.dehalo_verify_proof.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, P, sz, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.dehalo_verify_proofs.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), C.POINTER(C.c_int),
                                          C.POINTER(C.c_int64)]
+    lib.dehalo_verify_proofs_each.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(sz), u32, C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), C.POINTER(C.c_int),
+                                              C.POINTER(u32)]
+    lib.dehalo_msm_segments.argtypes = [P, C.c_int, u64p, u64p, P, u32, u64p]
+    lib.dehalo_msm_segments_device.argtypes = [P, C.c_int, u64p, u64p, P, u32, u64p, P]
     lib.dehalo_prover_create.argtypes = [P, P, P, P, PP]
     lib.dehalo_prover_create_multi.argtypes = [P, P, P, P, u32, PP]
     lib.dehalo_create_proof_multi.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(sz), u32, u32, C.POINTER(CRng), P, u32]
@@ -531,6 +536,19 @@ class Context:
             raise ValueError("best_multiexp: coeffs.len() != bases.len()")  # upstream assert_eq!
         out = np.zeros(12, dtype=np.uint64)
         self._check(self.lib.dehalo_best_multiexp(self.handle, curve, _ptr(s), _ptr(a), s.shape[0], _ptr(out)))
+        return out
+
+    def msm_segments(self, curve: int, scalars, affine_xy, offsets) -> np.ndarray:
+        """dehalo_msm_segments: many short independent sums in one launch.  out[s] = sum over offsets[s] <= i < offsets[s + 1] of scalars[i] * points[i], as
+        (segments, 8) affine rows, (0, 0) the identity; offsets: segments + 1 values that do not decrease (DehaloError(-1) otherwise)."""
+        s, a = _u64(scalars, 4), _u64(affine_xy, 8)
+        off = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        if off.size == 0:
+            raise ValueError("msm_segments: offsets holds segments + 1 values")
+        if s.shape[0] != a.shape[0] or int(off.max()) > s.shape[0]:
+            raise ValueError("msm_segments: the offsets reach past the terms, or scalars and points differ in length")
+        out = np.zeros((off.size - 1, 8), dtype=np.uint64)
+        self._check(self.lib.dehalo_msm_segments(self.handle, curve, _ptr(s), _ptr(a), off.ctypes.data, off.size - 1, _ptr(out)))
         return out
 
     def to_affine(self, curve: int, jacobian) -> np.ndarray:

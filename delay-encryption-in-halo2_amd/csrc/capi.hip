@@ -616,6 +616,60 @@ int dehalo_best_multiexp(dehalo_ctx* ctx, int curve, const uint64_t* scalars, co
     });
 }
 
+// ---- segmented sums (msm_segments.cuh): many short independent sums in one launch ----
+static MsmSegmentsFn msm_segments_fn(int curve) {
+    static const MsmSegmentsFn fns[] = {&msm_segments_bn254, &msm_segments_pallas, &msm_segments_vesta};
+    return curve >= 0 && curve < 3 ? fns[curve] : nullptr;
+}
+// what both forms refuse before anything is read: 0 and *fn, or the error
+static int msm_segments_args(dehalo_ctx* ctx, int curve, const void* offsets, uint32_t segments, const void* out, MsmSegmentsFn* fn) {
+    *fn = msm_segments_fn(curve);
+    if (!*fn) return unknown_curve(ctx);
+    if (!offsets || (!out && segments)) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_segments: null argument");
+    if (segments > DEHALO_MSM_SEGMENTS_MAX) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_segments: more than 2^24 segments");
+    return 0;
+}
+// the offsets on the host: segments + 1 words that do not decrease and end within the limit; terms behind them need their scalars and points
+static int msm_segments_offsets(dehalo_ctx* ctx, const uint32_t* offsets, uint32_t segments, const void* scalars, const void* points) {
+    for (uint32_t s = 0; s < segments; s++)
+        if (offsets[s + 1] < offsets[s]) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_segments: the offsets decrease");
+    if (offsets[segments] > DEHALO_MSM_SEGMENTS_MAX_TERMS) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_segments: more than 2^30 terms");
+    if (offsets[segments] > offsets[0] && (!scalars || !points)) return dh_fail(ctx, DEHALO_ERR_INVALID, "msm_segments: null argument");
+    return 0;
+}
+
+int dehalo_msm_segments_device(dehalo_ctx* ctx, int curve, const uint64_t* d_scalars, const uint64_t* d_affine_xy, const uint32_t* d_offsets, uint32_t segments,
+                               uint64_t* d_out_affine, void* stream) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    MsmSegmentsFn fn;
+    TRY(msm_segments_args(ctx, curve, d_offsets, segments, d_out_affine, &fn));
+    if (segments == 0) return 0;
+    return dh_device(ctx, stream, [&](hipStream_t s) -> int {
+        // the offsets come back and are checked BEFORE the launch (one small copy and a wait for the stream): a block then walks its own segment or nothing
+        std::vector<uint32_t> offsets((size_t)segments + 1);
+        TRY(dh_d2h(ctx, offsets.data(), d_offsets, 4 * offsets.size(), s));
+        TRY(msm_segments_offsets(ctx, offsets.data(), segments, d_scalars, d_affine_xy));
+        return fn(ctx, (const fe*)d_scalars, (const affine_t*)d_affine_xy, d_offsets, segments, (affine_t*)d_out_affine, s);
+    });
+}
+
+int dehalo_msm_segments(dehalo_ctx* ctx, int curve, const uint64_t* scalars, const uint64_t* affine_xy, const uint32_t* offsets, uint32_t segments, uint64_t* out_affine) {
+    if (!ctx) return DEHALO_ERR_INVALID;
+    MsmSegmentsFn fn;
+    TRY(msm_segments_args(ctx, curve, offsets, segments, out_affine, &fn));
+    if (segments == 0) return 0;
+    TRY(msm_segments_offsets(ctx, offsets, segments, scalars, affine_xy));
+    return dh_guard(ctx, [&] {
+        // (the kernel indexes scalars and points by the offsets themselves: the copies start at term 0)
+        const size_t terms = offsets[segments];
+        DevBuf* w = ctx->ws_segments;
+        return with_host_io(ctx, {{w[0], terms ? scalars : nullptr, terms * 32}, {w[1], terms ? affine_xy : nullptr, terms * 64}, {w[2], offsets, 4 * ((size_t)segments + 1)}},
+                            w[3], out_affine, 64 * (size_t)segments, [&] {
+            return fn(ctx, (const fe*)w[0].p, (const affine_t*)w[1].p, (const uint32_t*)w[2].p, segments, (affine_t*)w[3].p, ctx->stream.get());
+        });
+    });
+}
+
 int dehalo_point_sum_device(dehalo_ctx* ctx, int curve, const uint64_t* d_jacobian, size_t count, uint64_t* d_out_jacobian, void* stream) {
     if ((!d_jacobian && count) || !d_out_jacobian) return dh_fail(ctx, DEHALO_ERR_INVALID, "point_sum: null argument");
     if (count >= (1ull << 31)) return dh_fail(ctx, DEHALO_ERR_INVALID, "point_sum: too many points");

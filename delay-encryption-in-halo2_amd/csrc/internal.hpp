@@ -58,7 +58,7 @@ struct dehalo_ctx {
     std::recursive_mutex mu;   // recursive: host-buffer entry points hold it across their device-form calls
     // workspace (grow-only)
     DevBuf ws_scalars, ws_out, ws_count, ws_counters, ws_off, ws_records, ws_merge_lists, ws_merge_parts, ws_bhist, ws_pcount, ws_pairs, ws_bsum, ws_idx, ws_partial0, ws_buckets,
-        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3], ws_codec, ws_ipa_s, ws_verify[2];
+        ws_contrib, ws_tree, ws_bred_cnt, ws_gsums, ws_ntt_scratch, ws_ntt_io, ws_ntt_io2, ws_fop[3], ws_tmp_bases, ws_poly[5], ws_poly_io[3], ws_evh[4], ws_lookup, ws_gfft, ws_check[3], ws_codec, ws_ipa_s, ws_verify[2], ws_segments[4];
     std::vector<TwiddleEntry> twiddles;
     affine_t* msm_affine_out = nullptr;   // set for the duration of dehalo_msm_device_affine (under mu): k_msm_final also writes affine points
     int msm_acc_points = 48; // > 0: the accumulation's grid is 4, 6, 8, ... layers of one wave per SIMD, the fewest that leave a lane <= this many
@@ -342,6 +342,12 @@ struct FixedBaseOps {
 const FixedBaseOps& bn254_fixed_base_ops();
 const FixedBaseOps& pallas_fixed_base_ops();
 const FixedBaseOps& vesta_fixed_base_ops();
+// out[s] = sum over d_offsets[s] <= i < d_offsets[s + 1] of [d_scalars[i]] d_points[i], affine, s < segments: one launch, one function per curve (msm_segments.cuh,
+// instantiated in msm_*.hip).  d_offsets: segments + 1 words that do not decrease -- the caller has checked
+typedef int (*MsmSegmentsFn)(dehalo_ctx* ctx, const fe* d_scalars, const affine_t* d_points, const uint32_t* d_offsets, uint32_t segments, affine_t* d_out, hipStream_t s);
+int msm_segments_bn254(dehalo_ctx* ctx, const fe* d_scalars, const affine_t* d_points, const uint32_t* d_offsets, uint32_t segments, affine_t* d_out, hipStream_t s);
+int msm_segments_pallas(dehalo_ctx* ctx, const fe* d_scalars, const affine_t* d_points, const uint32_t* d_offsets, uint32_t segments, affine_t* d_out, hipStream_t s);
+int msm_segments_vesta(dehalo_ctx* ctx, const fe* d_scalars, const affine_t* d_points, const uint32_t* d_offsets, uint32_t segments, affine_t* d_out, hipStream_t s);
 // A plain (precompute 0) registration whose points are replaced on the stream, without a host wait or an allocation (capi.hip): the IPA rounds'
 // shrinking generator vector.  alloc: room for `cap` points, empty; rebuild: n <= cap points from d_points (standard Montgomery), the window
 // chosen for n as dehalo_bases_register_device would; queued on s, so the caller may overwrite d_points once later work on s reads the table.

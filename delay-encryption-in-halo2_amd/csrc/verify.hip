@@ -1,6 +1,6 @@
-// verify.hip -- verify_proof for KZG and for IPA behind the C ABI: the verifier object, its constructors, dehalo_verify_proof / dehalo_verify_proofs, dehalo_ipa_verify.
+// verify.hip -- verify_proof for KZG and for IPA behind the C ABI: the verifier object, its constructors, dehalo_verify_proof / dehalo_verify_proofs / dehalo_verify_proofs_each, dehalo_ipa_verify.
 // The protocol is verify_host.hpp's (host only); this unit adds the device backend -- every point of a call's proofs through one dehalo_points_decompress_device
-// launch, the term lists through the fresh-bases MSM (dehalo_best_multiexp); under IPA the instance columns' commitments over the params' Lagrange table and the
+// launch, the term lists through the fresh-bases MSM (dehalo_best_multiexp), a call's per-proof sums through one dehalo_msm_segments launch; under IPA the instance columns' commitments over the params' Lagrange table and the
 // sum over g: dehalo_ipa_s_device (ipa.cuh) into dehalo_msm_device over the params' resident table, the 2^k scalars never leaving the device -- and the batch
 // weights' draw.  No kernel of its own.  A verifier made without a context uses the host backend: a mode the caller chose, never a fallback.
 #include <memory>
@@ -90,6 +90,10 @@ struct DeviceVerifyBackend : VerifyBackend {
         TRY(dehalo_best_multiexp(ctx, curve, (const uint64_t*)scalars, xy, len, jac));
         return dehalo_to_affine(ctx, curve, jac, 1, out_affine);
     }
+    // every segment in ONE launch (msm_segments.cuh)
+    int msm_segments(const Fe* scalars, const uint64_t* xy, const uint32_t* offsets, uint32_t segments, uint64_t* out_affine) override {
+        return dehalo_msm_segments(ctx, curve, (const uint64_t*)scalars, xy, offsets, segments, out_affine);
+    }
 };
 
 int verifier_fail(dehalo_verifier* v, dehalo_ctx* ctx, int code, const std::string& msg) {
@@ -107,9 +111,10 @@ int verifier_finish(dehalo_ctx* ctx, std::unique_ptr<dehalo_verifier>& v, dehalo
     return 0;
 }
 
-// the caller's errors, the weights' draw, then the work on the verifier's backend; the verdict goes to the caller's pointers here and nowhere else
-int verify_body(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
-                uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* accept, int64_t* first_malformed, int* reason) {
+// what every verify call does around its work: the caller's errors, the weights' draw, then work(backend, input, error text) on the verifier's backend
+template <class Work>
+int verify_call(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
+                uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, Work&& work) {
     std::lock_guard<std::mutex> lk(v->mu);
     v->error.clear();
     const HostField* f = v->key.f;
@@ -138,18 +143,27 @@ int verify_body(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* 
         if (v->key.scheme == DEHALO_SCHEME_IPA) host->set_ipa(v->g.data(), v->g_lagrange.data(), v->key.w, v->key.k);
         be = std::move(host);
     }
-    VerifyVerdict verdict;
-    verdict.stats = v->stats;      // (a call in error leaves the last call's timings)
-    const int rc = verify_proofs_host(v->key, *be, in, verdict, &err);
-    *accept = verdict.accept;
-    if (first_malformed) *first_malformed = verdict.first_malformed;
-    if (reason) *reason = verdict.reason;
-    v->stats = verdict.stats;
+    const int rc = work(*be, in, err);
     if (rc && !err.empty()) {
         v->error = err;
         if (v->ctx && (rc == DEHALO_ERR_INVALID || rc == DEHALO_ERR_UNSUPPORTED)) dh_fail(v->ctx, rc, err);      // (a device error has its own text already)
     }
     return rc;
+}
+
+// one combined check; the verdict goes to the caller's pointers here and nowhere else
+int verify_body(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
+                uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* accept, int64_t* first_malformed, int* reason) {
+    return verify_call(v, proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, rng, [&](VerifyBackend& be, const VerifyInput& in, std::string& err) {
+        VerifyVerdict verdict;
+        verdict.stats = v->stats;      // (a call in error leaves the last call's timings)
+        const int rc = verify_proofs_host(v->key, be, in, verdict, &err);
+        *accept = verdict.accept;
+        if (first_malformed) *first_malformed = verdict.first_malformed;
+        if (reason) *reason = verdict.reason;
+        v->stats = verdict.stats;
+        return rc;
+    });
 }
 
 // the vk half of a key from the key at hand
@@ -349,6 +363,23 @@ extern "C" int dehalo_verify_proofs(dehalo_verifier* v, const uint8_t* const* pr
     return dh_guard(v ? v->ctx : nullptr, [&]() -> int {
         if (!v || !accept) return DEHALO_ERR_INVALID;
         return verify_body(v, proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, rng, accept, first_malformed, nullptr);
+    });
+}
+
+// a verdict per proof (verify_host.hpp verify_proofs_each_host); a call in error leaves reasons, checks and the last call's timings as they were
+extern "C" int dehalo_verify_proofs_each(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
+                                         const size_t* instance_lens, uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* reasons, uint32_t* checks) {
+    return dh_guard(v ? v->ctx : nullptr, [&]() -> int {
+        if (!v || (!reasons && count)) return DEHALO_ERR_INVALID;
+        return verify_call(v, proofs, lens, count, instances, instance_lens, num_instance_columns, num_circuits, rng, [&](VerifyBackend& be, const VerifyInput& in, std::string& err) {
+            VerifyEachVerdict verdict;
+            const int rc = verify_proofs_each_host(v->key, be, in, verdict, &err);
+            if (rc) return rc;
+            std::copy(verdict.reasons.begin(), verdict.reasons.end(), reasons);
+            if (checks) *checks = verdict.checks;
+            v->stats = verdict.stats;
+            return 0;
+        });
     });
 }
 

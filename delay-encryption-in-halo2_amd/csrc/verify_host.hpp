@@ -17,7 +17,8 @@
 // kernel of ipa.cuh into the MSM over the params' resident g).
 // The map.  One proof (verify_walk): walk_read fills a WalkRead (commitments, challenges, evaluations), expected_h evaluates the circuit over it, and one of
 // reduce_gwc / reduce_shplonk / reduce_ipa_multiopen appends the proof's terms through a WalkQueries.  One call (verify_proofs_host, after
-// verify_check_arguments has made its VerifyInput): stage_points, stage_instances, run_walks, then decide_kzg or decide_ipa into a VerifyVerdict.
+// verify_check_arguments has made its VerifyInput): stage_points, stage_instances, run_walks, then decide_kzg or decide_ipa into a VerifyVerdict.  A verdict per
+// proof (verify_proofs_each_host): the same three stages, then the backend's msm_segments sums each proof's runs apart and blame_search.hpp names the proofs that fail.
 // Host only, no HIP header: verify.hip includes it, and tests/native_host/verify_host_check.cpp and verify_ipa_host_check.cpp drive it on the CPU under ASan + UBSan.
 #pragma once
 #include <chrono>
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "../../include/dehalo.h"
+#include "blame_search.hpp"
 #include "g1_host.hpp"
 #include "hostfield.hpp"
 #include "key_format.hpp"
@@ -44,6 +46,8 @@ struct VerifyBackend {
     virtual int decompress(const uint8_t* in32, size_t count, uint64_t* xy) = 0;
     // sum_i [scalars_i] xy_i -> one affine point ((0, 0): the identity); scalars Montgomery, canonical words
     virtual int msm(const Fe* scalars, const uint64_t* xy, size_t len, uint64_t out_affine[8]) = 0;
+    // segment s < segments: sum over offsets[s] <= i < offsets[s + 1] of [scalars_i] xy_i -> segments affine points; the offsets do not decrease
+    virtual int msm_segments(const Fe* scalars, const uint64_t* xy, const uint32_t* offsets, uint32_t segments, uint64_t* out_affine) = 0;
     // IPA only (a backend without ParamsIPA's points refuses both).  commit_lagrange(column, Blind::default()) of `count` instance columns in one batch: column i
     // has lens[i] values (Montgomery, canonical), zero from there on -> count x {x, y}
     virtual int instance_commitments(const Fe* const*, const size_t*, size_t, uint64_t*) { return DEHALO_ERR_UNSUPPORTED; }
@@ -92,6 +96,10 @@ struct HostVerifyBackend : VerifyBackend {
         std::vector<Fe> c(len);
         for (size_t i = 0; i < len; i++) c[i] = fr->to_canonical(scalars[i]);
         g1.msm(c.data(), xy, len, out_affine);
+        return 0;
+    }
+    int msm_segments(const Fe* scalars, const uint64_t* xy, const uint32_t* offsets, uint32_t segments, uint64_t* out_affine) override {
+        for (uint32_t s = 0; s < segments; s++) msm(scalars + offsets[s], xy + 8 * (size_t)offsets[s], offsets[s + 1] - offsets[s], out_affine + 8 * (size_t)s);
         return 0;
     }
 };
@@ -202,6 +210,11 @@ struct VerifyTerms {
     std::vector<Fe> ls, rs;
     std::vector<uint64_t> lp, rp;      // 8 u64 a point
     std::vector<Fe> us, inits;         // IPA: k challenges and one init a proof
+    // where each walked proof's terms stand (run_walks): its index in the call and the first term of its run in ls and in rs.  The runs are contiguous and in
+    // the order of `runs` -- one ends where the next starts, the last at the list's end -- and so are the proofs' challenges (k each) and inits (one each)
+    struct Run { uint32_t proof; size_t l0, r0; };
+    std::vector<Run> runs;
+    void truncate(size_t nl, size_t nr, size_t nu, size_t ni) { ls.resize(nl); lp.resize(8 * nl); rs.resize(nr); rp.resize(8 * nr); us.resize(nu); inits.resize(ni); }
     void left(const Fe& s, const uint64_t* p) { ls.push_back(s); lp.insert(lp.end(), p, p + 8); }
     void right(const Fe& s, const uint64_t* p) { rs.push_back(s); rp.insert(rp.end(), p, p + 8); }
 };
@@ -640,6 +653,7 @@ struct VerifyStaged {
     size_t np = 0, sized = 0;
     std::vector<size_t> slot_of;
     std::vector<uint8_t> malformed;      // per proof: bytes missing or trailing; later a refused point, a scalar not below r
+    std::vector<uint8_t> opening;        // per proof: readable and no proof (run_walks)
     std::vector<uint64_t> xy, inst_cm;
     std::vector<InstanceValues> inst_of;
     const uint64_t* points(uint32_t i) const { return xy.data() + 8 * np * slot_of[i]; }
@@ -652,6 +666,7 @@ inline int stage_points(const VerifierKey& vk, VerifyBackend& be, const VerifyIn
     const std::vector<std::pair<size_t, size_t>> runs = verify_point_runs(in.plan, vk.scheme, mo);
     for (auto& r : runs) sg.np += r.second;
     sg.malformed.assign(in.count, 0);
+    sg.opening.assign(in.count, 0);
     sg.slot_of.assign(in.count, 0);
     std::vector<uint8_t> enc;
     for (uint32_t i = 0; i < in.count; i++) {
@@ -694,7 +709,8 @@ inline int stage_instances(const VerifierKey& vk, VerifyBackend& be, const Verif
     return rc ? verify_fail(error, rc, "verify_proofs: the instance columns' commitments failed") : 0;
 }
 
-// the walks: every staged proof's terms under its weight.  -> some readable proof is no proof (x_3 at an opening point, a zero round challenge)
+// the walks: every staged proof's terms under its weight, and where they stand (terms.runs); a proof the walk rejects leaves nothing in the lists.
+// -> some readable proof is no proof (x_3 at an opening point, a zero round challenge: sg.opening says which)
 inline bool run_walks(const VerifierKey& vk, const VerifyInput& in, VerifyStaged& sg, VerifyTerms& terms) {
     bool opening_rejected = false;
     for (uint32_t i = 0; i < in.count; i++) {
@@ -703,12 +719,23 @@ inline bool run_walks(const VerifierKey& vk, const VerifyInput& in, VerifyStaged
         for (size_t j = 0; j < sg.np && !sg.malformed[i]; j++)
             if (g1_affine_is_zero(pts + 8 * j)) sg.malformed[i] = 1;      // refused by the decoder, or the identity
         if (sg.malformed[i]) continue;
+        const size_t l0 = terms.ls.size(), r0 = terms.rs.size(), u0 = terms.us.size(), i0 = terms.inits.size();
         const VerifyWalkResult wr = verify_walk(vk, in.plan, in.proofs[i], in.lens[i], pts, sg.inst_of[i], sg.inst_cm.data() + 8 * sg.slot_of[i] * in.nic,
                                                 vk.f->mul(in.weights[i], vk.f->one), terms);
+        if (wr == VERIFY_WALK_OK) terms.runs.push_back({i, l0, r0});
+        else terms.truncate(l0, r0, u0, i0);
         if (wr == VERIFY_WALK_MALFORMED) sg.malformed[i] = 1;
-        if (wr == VERIFY_WALK_OPENING) opening_rejected = true;
+        if (wr == VERIFY_WALK_OPENING) { sg.opening[i] = 1; opening_rejected = true; }
     }
     return opening_rejected;
+}
+
+// two affine sums cancel: fresh = -(gs), (0, 0) the identity
+inline bool ipa_sums_cancel(const HostField* fq, const uint64_t fresh[8], const uint64_t gs[8]) {
+    Fe gy;
+    memcpy(gy.v, gs + 4, 32);
+    gy = fq->neg(gy);      // -(x, y) = (x, -y); (0, 0) stays the identity
+    return memcmp(fresh, gs, 32) == 0 && memcmp(fresh + 4, gy.v, 32) == 0;
 }
 
 // The IPA acceptance, the one statement of it (a call's last step, and dehalo_ipa_verify's): *accept = 1 iff  sum over the fresh bases + sum over g = the identity
@@ -723,23 +750,14 @@ inline int decide_ipa(VerifyBackend& be, const VerifyTerms& terms, size_t count,
     rc = count ? be.g_sum(terms.us.data(), terms.inits.data(), count, k, gs) : 0;
     if (rc) return verify_fail(error, rc, "verify_proofs: the sum over g failed");
     if (st) st->pairing = clock.lap();
-    Fe gy;
-    memcpy(gy.v, gs + 4, 32);
-    gy = fq->neg(gy);      // -(x, y) = (x, -y); (0, 0) stays the identity
-    *accept = memcmp(fresh, gs, 32) == 0 && memcmp(fresh + 4, gy.v, 32) == 0 ? 1 : 0;
+    *accept = ipa_sums_cancel(fq, fresh, gs) ? 1 : 0;
     return 0;
 }
 
-// The KZG acceptance: the two sums, then *accept = 1 iff  e(L, s_g2) e(-R, g2) = 1
-inline int decide_kzg(const VerifierKey& vk, VerifyBackend& be, const VerifyTerms& terms, int* accept, VerifyStats& st, std::string* error) {
-    VerifyClock clock;
-    uint64_t sums[16] = {};      // L | R
-    if (!terms.ls.empty()) {
-        int rc = be.msm(terms.ls.data(), terms.lp.data(), terms.ls.size(), sums);
-        if (!rc) rc = be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), sums + 8);
-        if (rc) return verify_fail(error, rc, "verify_proofs: the multi-scalar multiplication failed");
-    }
-    st.msm = clock.lap();
+// The KZG pairing check of two sums L | R (affine): *accept = 1 iff  e(L, s_g2) e(-R, g2) = 1
+inline int kzg_pairing(const VerifierKey& vk, const uint64_t lr[16], int* accept, std::string* error) {
+    uint64_t sums[16];
+    memcpy(sums, lr, 128);
     Fe ry;
     memcpy(ry.v, sums + 12, 32);
     ry = vk.fq->neg(ry);      // -R ((0, 0) stays the identity)
@@ -755,8 +773,23 @@ inline int decide_kzg(const VerifierKey& vk, VerifyBackend& be, const VerifyTerm
     const int rc = ph->check(sums, g2s, 2, &is_one, /* g2_subgroup_known */ true);
     if (rc == DEHALO_ERR_INVALID) is_one = 0;
     else if (rc) return verify_fail(error, rc, "verify_proofs: the pairing check failed");
-    st.pairing = clock.lap();
     *accept = is_one ? 1 : 0;
+    return 0;
+}
+
+// The KZG acceptance: the two sums, then the pairing check
+inline int decide_kzg(const VerifierKey& vk, VerifyBackend& be, const VerifyTerms& terms, int* accept, VerifyStats& st, std::string* error) {
+    VerifyClock clock;
+    uint64_t sums[16] = {};      // L | R
+    if (!terms.ls.empty()) {
+        int rc = be.msm(terms.ls.data(), terms.lp.data(), terms.ls.size(), sums);
+        if (!rc) rc = be.msm(terms.rs.data(), terms.rp.data(), terms.rs.size(), sums + 8);
+        if (rc) return verify_fail(error, rc, "verify_proofs: the multi-scalar multiplication failed");
+    }
+    st.msm = clock.lap();
+    const int rc = kzg_pairing(vk, sums, accept, error);
+    if (rc) return rc;
+    st.pairing = clock.lap();
     return 0;
 }
 
@@ -784,5 +817,86 @@ inline int verify_proofs_host(const VerifierKey& vk, VerifyBackend& be, const Ve
         if (!v.accept) v.reason = ipa ? DEHALO_REJECT_OPENING : DEHALO_REJECT_PAIRING;
     }
     out = v;
+    return 0;
+}
+
+// What dehalo_verify_proofs_each found: reasons[i] = a dehalo_reject_reason, NONE for a valid proof; checks: the subset checks made
+struct VerifyEachVerdict { std::vector<int> reasons; uint32_t checks = 0; VerifyStats stats; };
+
+// A verdict per proof from one batch: the staging and the walks of verify_proofs_host; the proofs a walk rejects are named there (MALFORMED, OPENING) and take no
+// part in what follows.  ONE msm_segments call of the backend then sums every remaining proof's runs apart -- w_i L_i and w_i R_i (IPA: the weighted fresh sum)
+// --, a subset's sums are point additions on the host, and blame_search names the proofs that fail with few checks of subsets: KZG one pairing check on the
+// subset's two sums, IPA the subset's fresh sum against the backend's g_sum over the subset's challenges and inits (ipa_sums_cancel).  A proof the search names is
+// PAIRING under KZG and OPENING under IPA.  Returns 0 whenever the checks ran; DEHALO_ERR_INVALID without weights or the backend's error, and `out` is then as it was.
+inline int verify_proofs_each_host(const VerifierKey& vk, VerifyBackend& be, const VerifyInput& in, VerifyEachVerdict& out, std::string* error) {
+    if (in.count && !in.weights) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs_each: null argument");
+    VerifyEachVerdict v;
+    VerifyStaged sg;
+    int rc = stage_points(vk, be, in, sg, v.stats, error);
+    if (!rc) rc = stage_instances(vk, be, in, sg, error);
+    if (rc) return rc;
+    VerifyClock clock;
+    VerifyTerms terms;
+    run_walks(vk, in, sg, terms);
+    v.stats.walk = clock.lap();
+    v.reasons.assign(in.count, DEHALO_REJECT_NONE);
+    for (uint32_t i = 0; i < in.count; i++) v.reasons[i] = sg.malformed[i] ? DEHALO_REJECT_MALFORMED : sg.opening[i] ? DEHALO_REJECT_OPENING : DEHALO_REJECT_NONE;
+    const bool ipa = vk.scheme == DEHALO_SCHEME_IPA;
+    const size_t live = terms.runs.size(), nl = terms.ls.size(), nr = terms.rs.size(), k = in.plan.k;
+    if (live) {
+        if (nl + nr > DEHALO_MSM_SEGMENTS_MAX_TERMS) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs_each: too many terms in one call");
+        // one list: every left run, then every right run (IPA has no left list); segment p < live is proof p's left run, live + p its right run
+        std::vector<Fe> scalars(terms.ls);
+        scalars.insert(scalars.end(), terms.rs.begin(), terms.rs.end());
+        std::vector<uint64_t> points(terms.lp);
+        points.insert(points.end(), terms.rp.begin(), terms.rp.end());
+        std::vector<uint32_t> offsets;
+        for (const VerifyTerms::Run& r : terms.runs)
+            if (!ipa) offsets.push_back((uint32_t)r.l0);
+        for (const VerifyTerms::Run& r : terms.runs) offsets.push_back((uint32_t)(nl + r.r0));
+        offsets.push_back((uint32_t)(nl + nr));
+        const uint32_t segments = (uint32_t)offsets.size() - 1;
+        std::vector<uint64_t> sums(8 * (size_t)segments);
+        rc = be.msm_segments(scalars.data(), points.data(), offsets.data(), segments, sums.data());
+        if (rc) return verify_fail(error, rc, "verify_proofs_each: the segmented sums failed");
+        v.stats.msm = clock.lap();
+        const uint64_t* right = sums.data() + (ipa ? 0 : 8 * live);
+        const G1Host g1(vk.fq, curve_b_host(vk.curve));
+        auto range_sum = [&](const uint64_t* per_proof, size_t first, size_t count, uint64_t out_affine[8]) {
+            G1Host::Jac acc = g1.identity();
+            for (size_t p = first; p < first + count; p++) {
+                Fe x, y;
+                memcpy(x.v, per_proof + 8 * p, 32);
+                memcpy(y.v, per_proof + 8 * p + 4, 32);
+                acc = g1.add_affine(acc, x, y);
+            }
+            g1.to_affine(acc, out_affine);
+        };
+        int check_rc = 0;      // an error of a check ends the search: every later check "passes" unasked
+        auto check = [&](size_t first, size_t count) -> bool {
+            if (check_rc) return true;
+            int ok = 0;
+            if (ipa) {
+                uint64_t fresh[8], gs[8] = {};
+                range_sum(right, first, count, fresh);
+                check_rc = be.g_sum(terms.us.data() + first * k, terms.inits.data() + first, count, (uint32_t)k, gs);
+                if (check_rc) verify_fail(error, check_rc, "verify_proofs_each: the sum over g failed");
+                ok = ipa_sums_cancel(vk.fq, fresh, gs);
+            } else {
+                uint64_t lr[16];
+                range_sum(sums.data(), first, count, lr);
+                range_sum(right, first, count, lr + 8);
+                check_rc = kzg_pairing(vk, lr, &ok, error);
+            }
+            return !check_rc && ok;
+        };
+        std::vector<uint8_t> bad;
+        v.checks = blame_search(live, check, bad);
+        if (check_rc) return check_rc;
+        v.stats.pairing = clock.lap();
+        for (size_t p = 0; p < live; p++)
+            if (bad[p]) v.reasons[terms.runs[p].proof] = ipa ? DEHALO_REJECT_OPENING : DEHALO_REJECT_PAIRING;
+    }
+    out = std::move(v);
     return 0;
 }

@@ -592,6 +592,24 @@ class Verifier {
         check(dehalo_verify_proofs(v_, pp.data(), pl.data(), (uint32_t)pp.size(), ip.data(), il.data(), columns, 1, rng, &accept, first_malformed));
         return accept != 0;
     }
+    // a verdict per proof from one batch verification (dehalo_verify_proofs_each): DEHALO_REJECT_NONE for a valid proof, otherwise what verify says of that proof
+    // alone.  Arguments and the weights' warning as for verify_batch.  *checks: the subset checks made (1 when every readable proof is valid)
+    std::vector<int> verify_each(const std::vector<std::vector<uint8_t>>& proofs, const std::vector<std::vector<std::vector<Fe>>>& instances, dehalo_rng* rng = nullptr,
+                                 uint32_t* checks = nullptr) const {
+        std::vector<const uint8_t*> pp;
+        std::vector<size_t> pl, il;
+        std::vector<const uint64_t*> ip;
+        for (auto& p : proofs) { pp.push_back(p.data()); pl.push_back(p.size()); }
+        if (instances.size() != proofs.size()) check(DEHALO_ERR_INVALID);
+        const uint32_t columns = instances.empty() ? 0 : (uint32_t)instances[0].size();
+        for (auto& one : instances) {
+            if (one.size() != columns) check(DEHALO_ERR_INVALID);
+            for (auto& col : one) { ip.push_back(col.empty() ? nullptr : col[0].data()); il.push_back(col.size()); }
+        }
+        std::vector<int> reasons(proofs.size(), DEHALO_REJECT_NONE);
+        check(dehalo_verify_proofs_each(v_, pp.data(), pl.data(), (uint32_t)pp.size(), ip.data(), il.data(), columns, 1, rng, reasons.data(), checks));
+        return reasons;
+    }
     dehalo_verifier* raw() const { return v_; }
 
   private:

@@ -593,6 +593,7 @@ class Verifier:
         self.ctx, self.curve, self.handle = ctx, curve, handle
         self.last_reject = REJECT_NONE          # why the last verify / verify_batch said no
         self.first_malformed = -1               # verify_batch: the first unreadable proof
+        self.last_checks = 0                    # verify_each: the subset checks of the last call
         self.ipa = multiopen is None            # an IPA verifier has one multiopen: nothing to set
         self._params = None                     # IPA with a context: the borrowed ParamsIPA, kept alive
         if not self.ipa:
@@ -742,8 +743,30 @@ class Verifier:
         self.last_reject = REJECT_NONE if accept.value else (REJECT_MALFORMED if first.value >= 0 else REJECT_OPENING if self.ipa else REJECT_PAIRING)
         return bool(accept.value)
 
+    def verify_each(self, proofs: Sequence[bytes], instances: Optional[Sequence] = None, rng=None, num_circuits: Optional[int] = None) -> List[int]:
+        """dehalo_verify_proofs_each: a verdict per proof from one batch verification -- REJECT_NONE for a valid proof, otherwise what verify says of that proof
+        alone (REJECT_MALFORMED, REJECT_PAIRING, IPA: REJECT_OPENING).  Arguments as verify_batch takes them, the weights' draw and the warning about it too.
+        last_checks: the subset checks the call made (1 when every readable proof is valid, 13 for one invalid proof among 64)."""
+        bufs = [np.frombuffer(bytes(p), dtype=np.uint8) for p in proofs]
+        if instances is None:
+            instances = [((),) if num_circuits is None else [((),)] * num_circuits] * len(bufs)
+        per_proof = [[list(i)] if num_circuits is None else [list(c) for c in i] for i in instances]
+        if len(per_proof) != len(bufs):
+            raise ValueError("one instance list per proof")
+        ptrs, lens, keep, ncols, circuits = self._instances(per_proof)
+        pp = (C.c_void_p * max(1, len(bufs)))(*[b.ctypes.data if b.size else None for b in bufs])
+        pl = (C.c_size_t * max(1, len(bufs)))(*[b.size for b in bufs])
+        r = rng_struct(rng)
+        reasons, checks = (C.c_int * max(1, len(bufs)))(), C.c_uint32(0)
+        self._check(load_library().dehalo_verify_proofs_each(self.handle, pp, pl, len(bufs), ptrs, lens, ncols, circuits if bufs else (num_circuits or 1),
+                                                            C.byref(r) if r is not None else None, reasons, C.byref(checks)))
+        rng_writeback(rng, r)
+        self.last_checks = int(checks.value)
+        return [int(reasons[i]) for i in range(len(bufs))]
+
     def last_timings(self) -> dict:
-        """milliseconds of the last call: point decompression, the transcript walks, the two MSMs, the pairing check"""
+        """milliseconds of the last call: point decompression, the transcript walks, the two MSMs (verify_each: the per-proof sums), the pairing check (verify_each:
+        the total of the subset checks)"""
         out = (C.c_double * 4)()
         self._check(load_library().dehalo_verifier_last_timings(self.handle, out))
         return dict(zip(("decompress", "walk", "msm", "g_sum" if self.ipa else "pairing"), out))

@@ -34,7 +34,7 @@
  * device, multi, points), dehalo_kate_division (host, batch) and the vanishing quotient, lincomb, scale, batch inversion, the grand and prefix
  * products, product_terms, graph_evaluate and the permutation / lookup / shuffle terms of h, dehalo_permute_expression_pair (host, device, pointer
  * table), dehalo_check_witness, whole proofs (KZG and IPA, advice and instances), every MSM form, best_multiexp, the fixed-base and blinding calls, the
- * generator collapse, registration, points_check and points_compress.  Without a row of their own -- they read caller words through the kernels and
+ * generator collapse, registration, points_check and points_compress (dehalo_msm_segments: in tests/test_msm_segments.py).  Without a row of their own -- they read caller words through the kernels and
  * conversions (f29_from_std / f_from_mont) of the rows above, which is an argument from reading, not a test: dehalo_keygen's fixed columns, dehalo_ipa_open, dehalo_convert_form_device and the *_form_device
  * transforms, dehalo_kate_division_device, dehalo_g_to_lagrange_device, the masked evaluation, the batch / deferred / distinct permute forms and the
  * transcript's common_scalar / write_scalar.  dehalo_points_decompress_device refuses an x not below p (status bit 1), as upstream's from_bytes does.
@@ -173,6 +173,26 @@ int dehalo_msm_device_affine(dehalo_ctx* ctx, const dehalo_bases* bases, const u
 /* One-shot best_multiexp over bases that are not registered (uploaded, used, dropped). */
 int dehalo_best_multiexp(dehalo_ctx* ctx, int curve, const uint64_t* scalars, const uint64_t* affine_xy, size_t len,
                          uint64_t out_jacobian[12]);
+/* Many short independent sums in ONE launch (csrc/msm_segments.cuh):
+ *     out[s] = sum over offsets[s] <= i < offsets[s + 1] of scalars[i] * points[i],    s < segments.
+ * The per-proof sums of dehalo_verify_proofs_each are its use: about 10^2 terms a segment and 10^2 segments a call, where one dehalo_best_multiexp per segment
+ * would be launch latency 10^2 times over.  One workgroup per segment, one quad of lanes per term (a 255-step double-and-add), so the call's time is that of its
+ * LONGEST segment in steps of 128 terms; for sums of 2^12 terms and more the Pippenger calls above are the right ones.  All three curves.
+ *   scalars    offsets[segments] x 4 u64, Montgomery; words under "Non-canonical words" (1): a word stands for its residue mod r, zero is zero mod r
+ *   points     offsets[segments] x {x, y} of 64 B, standard Montgomery, (0, 0) the identity, coordinates under "Non-canonical words" (4).  Both arrays are indexed
+ *              by the offsets themselves (entries below offsets[0] are not read)
+ *   offsets    segments + 1 words that do not decrease; an empty segment (two equal offsets) sums to the identity
+ *   out        segments x {x, y}, affine, canonical, (0, 0) for the identity
+ * The group law is exact in every case: equal, opposite and identity operands, zero scalars, one point listed several times in a segment.
+ * Limits: segments <= DEHALO_MSM_SEGMENTS_MAX (2^24), offsets[segments] <= DEHALO_MSM_SEGMENTS_MAX_TERMS (2^30).  DEHALO_ERR_INVALID beyond them, for offsets that
+ * decrease, an unknown curve, and a null argument (scalars and points may be null when no segment has a term; out when segments = 0, which does nothing).
+ * The device form reads the offsets back and checks them BEFORE it launches (one small copy and a wait for the stream), so a refused call has written nothing;
+ * the kernel is then queued on the stream and the call returns.  The host form uploads, runs and downloads: for tests and small callers. */
+#define DEHALO_MSM_SEGMENTS_MAX (1u << 24)
+#define DEHALO_MSM_SEGMENTS_MAX_TERMS (1u << 30)
+int dehalo_msm_segments_device(dehalo_ctx* ctx, int curve, const uint64_t* d_scalars, const uint64_t* d_affine_xy, const uint32_t* d_offsets, uint32_t segments,
+                               uint64_t* d_out_affine, void* stream);
+int dehalo_msm_segments(dehalo_ctx* ctx, int curve, const uint64_t* scalars, const uint64_t* affine_xy, const uint32_t* offsets, uint32_t segments, uint64_t* out_affine);
 /* G1::to_affine / batch_normalize of MSM outputs: count x 12 u64 -> count x 8 u64 (host buffers). */
 int dehalo_to_affine(dehalo_ctx* ctx, int curve, const uint64_t* jacobian, size_t count, uint64_t* affine_xy);
 /* Sum of `count` Jacobian points -> one Jacobian point (identity for count == 0): the combine step when ONE large MSM
@@ -1066,7 +1086,8 @@ int dehalo_verifier_create_error(char* out, size_t cap);
 /* Text of the last error of a call on this verifier (a host verifier has no context to keep it); valid until the next call on it. */
 const char* dehalo_verifier_last_error(const dehalo_verifier* v);
 /* Where the last dehalo_verify_proof(s) call spent its time, milliseconds: out[0] point decompression, out[1] the transcript walks (hashing, expected_h, the
- * term lists), out[2] the two MSMs (IPA: the one over the term list), out[3] the pairing check (IPA: the sum over g -- kernel, MSM, download). */
+ * term lists), out[2] the two MSMs (IPA: the one over the term list), out[3] the pairing check (IPA: the sum over g -- kernel, MSM, download).  After
+ * dehalo_verify_proofs_each: out[2] the per-proof sums (one dehalo_msm_segments call), out[3] the total of the subset checks. */
 int dehalo_verifier_last_timings(const dehalo_verifier* v, double out[4]);
 
 typedef enum {
@@ -1080,12 +1101,28 @@ int dehalo_verify_proof(dehalo_verifier* v, const uint64_t* const* instances, co
 /* `count` proofs under one verifier (upstream's BatchVerifier / AccumulatorStrategy): every proof is read as above, then sum_i w_i L_i and sum_i w_i R_i are checked with
  * ONE pairing check.  w_0 = 1; w_1 .. w_{count-1} are the first count - 1 scalars of `rng` (NULL = DEHALO_RNG_OS), in order.  instances: proof i's circuit c's column j at
  * [(i * num_circuits + c) * num_instance_columns + j], instance_lens likewise.  *accept = 1 iff every proof was readable and the combined check holds; *first_malformed = index of the first
- * unreadable proof or -1 (a pairing failure does not say which proof: verify those singly).  With a context: all proofs' points in one decompress launch, the term lists
+ * unreadable proof or -1 (a pairing failure does not say which proof: dehalo_verify_proofs_each below does).  With a context: all proofs' points in one decompress launch, the term lists
  * concatenated into one MSM pair.
  * THE WEIGHTS MUST BE UNPREDICTABLE TO WHOEVER MADE THE PROOFS: someone who knows w_i before choosing the proofs can make invalid proofs whose errors cancel in the
  * weighted sums (two copies of one invalid proof under w_1 = -1 pass).  Use DEHALO_RNG_OS (rng = NULL) outside tests. */
 int dehalo_verify_proofs(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances, const size_t* instance_lens,
                          uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* accept, int64_t* first_malformed);
+/* A verdict PER PROOF from one batch verification: what a verifier of untrusted proofs needs, since whoever submits one invalid proof otherwise turns a batch call
+ * into `count` single calls.  Arguments, argument errors and the weights' draw are dehalo_verify_proofs's (w_0 = 1, the rest from `rng`, NULL = DEHALO_RNG_OS), and so is
+ * the warning: THE WEIGHTS MUST BE UNPREDICTABLE TO WHOEVER MADE THE PROOFS -- under known weights invalid proofs can cancel each other and all be reported valid.
+ *   reasons   count x int, a dehalo_reject_reason each: DEHALO_REJECT_NONE for a valid proof, otherwise what dehalo_verify_proof says of that proof alone
+ *             (MALFORMED; PAIRING under KZG; OPENING under IPA).  May be NULL only when count = 0
+ *   checks    optional: the number of subset checks made (KZG: pairing checks; IPA: sums over g)
+ * Every proof is read ONCE, as in the batch call.  Proofs the read rejects (MALFORMED, or IPA's OPENING for x_3 at an opening point or a zero round challenge) get
+ * their reason there and take no part in what follows.  One dehalo_msm_segments launch then sums each remaining proof's weighted term lists apart (w_i L_i and w_i R_i;
+ * IPA: the weighted sum over the fresh bases), a subset's sums are point additions on the host, and a search over subsets names the proofs that fail (csrc/blame_search.hpp:
+ * a set that fails and whose first half passes has its second half bad without a check of it): 0 checks when no proof is left, 1 when all of them are valid, at most
+ * 1 + 2 b ceil(log2 n) for b >= 1 invalid among n -- 13 for one invalid proof among 64, 127 when all 64 are invalid.  Two copies of one invalid proof are both named.
+ * A check is one pairing check on the host (KZG) or one dehalo_ipa_s_device + MSM over g (IPA; a host verifier: 2^k group operations each).
+ * Returns 0 whenever the checks ran; on an error `reasons` and `checks` are not written.  dehalo_verifier_last_timings: out[2] the dehalo_msm_segments call, out[3] the
+ * total of the subset checks.  dehalo_verify_proof and dehalo_verify_proofs are what they were. */
+int dehalo_verify_proofs_each(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
+                              const size_t* instance_lens, uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* reasons, uint32_t* checks);
 /* The IPA opening argument's check alone, the counterpart of dehalo_ipa_open: *accept = 1 iff `proof` (S, the k rounds' L_j, R_j, then c and f: 32 (2 k + 3) bytes,
  * read through a fresh transcript) opens `commitment` (affine {x, y}, standard Montgomery) to v at x3 (4 x u64 Montgomery each) under the ParamsIPA `params`.  The
  * reduction is the whole proof's; the two sums run on the device.  Returns 0 whenever the check ran. */
