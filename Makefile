@@ -16,7 +16,7 @@ ifdef EXPERIMENTS
 HIPFLAGS += -DDEHALO_EXPERIMENTS
 endif
 LIB ?= $(PKG)/libdehalo.so
-UNITS := capi params transcript ipa_open keygen prover verify check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
+UNITS := capi params transcript ipa_open keygen prover verify pairing check witness lookup_permute msm_bn254 msm_pallas msm_vesta ntt_bn254_fr ntt_bn254_fq ntt_pasta_fp ntt_pasta_fq
 OBJS := $(UNITS:%=$(OBJDIR)/%.o)
 HDRS := $(wildcard $(CSRC)/*.cuh) $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.hpp) include/dehalo.h
 
@@ -108,4 +108,9 @@ witness_units_check: tests/native_host/witness_units_check.cpp $(CSRC)/bigint_ho
 blame_search_check: tests/native_host/blame_search_check.cpp $(CSRC)/blame_search.hpp
 	g++ -std=c++17 -O0 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/blame_search_check tests/native_host/blame_search_check.cpp
 
-.PHONY: all oracle clean host_example host_sanitize host_tsan witness_units_check msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check verify_ipa_host_check g1_host_check blame_search_check
+# the line tables of fixed G2 points (csrc/pairing_host.hpp: line_table, miller_table) against miller() word for word, under ASan + UBSan
+# (tests/test_pairing_lines_host.py runs it)
+pairing_lines_check: tests/native_host/pairing_lines_check.cpp $(CSRC)/pairing_host.hpp $(CSRC)/params_format.hpp $(CSRC)/g1_host.hpp $(CSRC)/hostfield.hpp $(CSRC)/field_constants.h include/dehalo.h
+	g++ -std=c++17 -O1 -g -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=undefined -o tests/native_host/pairing_lines_check tests/native_host/pairing_lines_check.cpp
+
+.PHONY: all oracle clean host_example host_sanitize host_tsan witness_units_check msm_plan_check opening_plan_check opening_plan_multi_check host_cs_check shuffle_cs_check hostrng_check params_format_check key_format_check pairing_check verify_host_check verify_ipa_host_check g1_host_check blame_search_check pairing_lines_check

@@ -92,6 +92,13 @@ impl DehaloVerifier {
         self.check(unsafe { sys::dehalo_verifier_set_multiopen(self.raw, multiopen) })
     }
 
+    /// Where the pairing checks run: `sys::DEHALO_PAIRING_ON_HOST` (the default) or `sys::DEHALO_PAIRING_ON_DEVICE` -- `verify` and `verify_batch` then make their
+    /// one check through the kernel, and `verify_each` gives every live proof its own check in ONE launch, without a search (`checks` = the live proofs).
+    /// `Err` on a verifier without a context and on an IPA verifier.
+    pub fn set_pairing(&mut self, mode: u32) -> Result<(), DehaloError> {
+        self.check(unsafe { sys::dehalo_verifier_set_pairing(self.raw, mode as i32) })
+    }
+
     /// `verify_proof(&params, &vk, strategy, &[instances_0, .., instances_{N-1}], &mut transcript)` with `SingleStrategy`: `Ok(Ok(()))` accepted, `Ok(Err(why))`
     /// rejected, `Err(_)` the caller's error (a wrong number of instance columns, a column longer than the usable rows) or the device's.
     pub fn verify(&self, instances: &[&[&[Fr]]], proof: &[u8]) -> Result<Result<(), Reject>, DehaloError> {

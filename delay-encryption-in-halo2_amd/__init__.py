@@ -12,7 +12,7 @@ The directory name has a hyphen, so load it with ``__graft_entry__.load_package(
 (module name ``dehalo2_amd``).
 """
 from . import fields  # noqa: F401
-from ._lib import Context, DehaloError, Bases, FixedBase, library_path, load_library  # noqa: F401
+from ._lib import Context, DehaloError, Bases, FixedBase, PairingTable, library_path, load_library  # noqa: F401
 from .arithmetic import batch_invert, best_fft, best_multiexp, eval_polynomial, grand_product  # noqa: F401
 from .domain import EvaluationDomain  # noqa: F401
 from .commitment import Params, ParamsIPA  # noqa: F401

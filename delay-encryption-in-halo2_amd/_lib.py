@@ -46,6 +46,8 @@ SYMBOLS = [
     "dehalo_verifier_create_error", "dehalo_verifier_last_error","dehalo_verifier_last_timings", "dehalo_verify_proof", "dehalo_verify_proofs",
     "dehalo_ipa_s_device", "dehalo_verifier_create_ipa", "dehalo_verifier_create_ipa_vk", "dehalo_verifier_create_ipa_host", "dehalo_ipa_verify",
     "dehalo_msm_segments", "dehalo_msm_segments_device", "dehalo_verify_proofs_each",
+    "dehalo_pairing_table_create", "dehalo_pairing_table_release", "dehalo_pairing_checks_device", "dehalo_pairing_checks", "dehalo_pairing_checks_per_block",
+    "dehalo_verifier_set_pairing",
 ]
 
 K_MSM_ACCUMULATE, K_MSM_SORT, K_MSM_REDUCE, K_NTT_PASS, K_POLY, K_EVAL_H = 0, 1, 2, 3, 4, 5
@@ -325,6 +327,14 @@ def load_library():
     lib.dehalo_transcript_remaining.argtypes = [P]
     lib.dehalo_transcript_remaining.restype = sz
     lib.dehalo_pairing_check.argtypes = [C.c_int, u64p, P, sz, C.POINTER(C.c_int)]
+    lib.dehalo_pairing_table_create.argtypes = [P, C.c_int, P, u32, PP]
+    lib.dehalo_pairing_table_release.argtypes = [P]
+    lib.dehalo_pairing_table_release.restype = None
+    lib.dehalo_pairing_checks_device.argtypes = [P, P, u64p, u32, P, u64p, P]
+    lib.dehalo_pairing_checks.argtypes = [P, u64p, u32, P, u64p]
+    lib.dehalo_pairing_checks_per_block.argtypes = [P]
+    lib.dehalo_pairing_checks_per_block.restype = u32
+    lib.dehalo_verifier_set_pairing.argtypes = [P, C.c_int]
     lib.dehalo_verifier_create.argtypes = [P, P, P, PP]
     lib.dehalo_verifier_create_vk.argtypes = [P, C.c_int, u32, u64p, P, P, C.POINTER(CConstraintSystem), P, sz, C.c_int, u32, PP]
     lib.dehalo_verifier_set_transcript_repr.argtypes = [P, u64p]
@@ -416,6 +426,51 @@ class FixedBase:
         if self.handle is not None and self.owned:
             self.ctx._check(self.ctx.lib.dehalo_fixed_base_release(self.ctx.handle, self.handle))
         self.handle = None
+
+
+PAIRING_NOT_ONE, PAIRING_ONE, PAIRING_OFF_CURVE = 0, 1, 2      # dehalo_pairing_checks' statuses
+
+
+class PairingTable:
+    """dehalo_pairing_table: the line tables of `pairs` fixed G2 points (128 raw bytes each, all zero = the identity), made once on the host.  With a Context the
+    checks run on the device, one launch for all of them; with ctx=None it is a HOST table -- a mode the caller chooses, never a fallback.  DehaloError(-1): a
+    point off the twist or outside the order-r subgroup, a word not below q, no points or more than 8; (-5): a curve without a pairing."""
+
+    def __init__(self, ctx: Optional["Context"], curve: int, g2_raw: Sequence[bytes]):
+        self.lib = load_library()
+        raw = b"".join(bytes(q) for q in g2_raw)
+        if any(len(bytes(q)) != 128 for q in g2_raw):
+            raise ValueError("PairingTable: a G2 point is 128 raw bytes")
+        self.ctx, self.pairs = ctx, len(g2_raw)
+        buf = np.frombuffer(raw or bytes(1), dtype=np.uint8)
+        h = C.c_void_p()
+        rc = self.lib.dehalo_pairing_table_create(ctx.handle if ctx is not None else None, curve, buf.ctypes.data, self.pairs, C.byref(h))
+        if rc != 0:
+            raise DehaloError(rc, self.lib.dehalo_last_error(ctx.handle).decode() if ctx is not None else "pairing_table_create")
+        self.handle = h
+
+    def checks(self, g1_affine_xy, gt: bool = False):
+        """dehalo_pairing_checks: g1_affine_xy (checks, pairs, 8) Montgomery words, (0, 0) the identity -> the statuses, (checks,) uint8 of PAIRING_NOT_ONE /
+        _ONE / _OFF_CURVE; with gt=True also the GT values, (checks, 12, 4) words: the Fq2 coefficients of w^0 .. w^5, a | b each, canonical"""
+        g1 = np.ascontiguousarray(g1_affine_xy, dtype=np.uint64).reshape(-1, self.pairs, 8)
+        n = g1.shape[0]
+        status = np.zeros(max(1, n), dtype=np.uint8)
+        out = np.zeros((max(1, n), 12, 4), dtype=np.uint64)
+        rc = self.lib.dehalo_pairing_checks(self.handle, g1.ctypes.data if n else None, n, status.ctypes.data if n else None, out.ctypes.data if gt and n else None)
+        if rc != 0:
+            raise DehaloError(rc, self.lib.dehalo_last_error(self.ctx.handle).decode() if self.ctx is not None else "pairing_checks")
+        return (status[:n], out[:n]) if gt else status[:n]
+
+    def release(self):
+        if self.handle is not None:
+            self.lib.dehalo_pairing_table_release(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class Context:
@@ -550,6 +605,16 @@ class Context:
         out = np.zeros((off.size - 1, 8), dtype=np.uint64)
         self._check(self.lib.dehalo_msm_segments(self.handle, curve, _ptr(s), _ptr(a), off.ctypes.data, off.size - 1, _ptr(out)))
         return out
+
+    def pairing_checks(self, table: PairingTable, g1_affine_xy, gt: bool = False):
+        """dehalo_pairing_checks on a table of this context: every check of g1_affine_xy (checks, pairs, 8) in one launch (PairingTable.checks)"""
+        if table.ctx is not self:
+            raise ValueError("pairing_checks: the table belongs to another context (or to the host)")
+        return table.checks(g1_affine_xy, gt)
+
+    def pairing_checks_device(self, table: PairingTable, d_g1: int, checks: int, d_status: int, d_gt: int = 0, stream: int = 0):
+        """dehalo_pairing_checks_device: all arrays in device memory (d_gt = 0: no GT values)"""
+        self._check(self.lib.dehalo_pairing_checks_device(self.handle, table.handle, d_g1 or None, checks, d_status or None, d_gt or None, stream or None))
 
     def to_affine(self, curve: int, jacobian) -> np.ndarray:
         j = _u64(jacobian, 12)

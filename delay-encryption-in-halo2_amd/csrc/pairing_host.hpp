@@ -204,6 +204,95 @@ struct PairingHost {
         return pow12(b, hard);
     }
 
+    // ---- The line table of a FIXED Q (a KZG verifier's g2 and s_g2): everything miller() does on the twist depends on Q alone, so it is done once.  Step by
+    // step in miller()'s own order -- for i = 63 .. 0 the tangent, then the addition where bit i of 6x + 2 is set, then pi(Q) and -pi^2(Q): 64 + 36 + 2 = 102
+    // steps -- the table keeps lam and lam xt - yt, the two values line() needs besides xp and yp.  one: Q is the identity, the factor 1, no steps.
+    static constexpr size_t LINE_STEPS = 102;
+    struct LineTable { std::vector<Fq2> lines; bool one = false; };      // lines: lam | lam xt - yt per step
+    // step()'s slope and T <- T + S; false: a degenerate step (T or S at infinity, a vertical line), which a Q of order r never meets
+    bool table_step(G2Host::Pt& T, const G2Host::Pt& S, LineTable& t) const {
+        if (T.inf || S.inf) return false;
+        Fq2 lam;
+        if (e2.eq(T.x, S.x)) {
+            if (!e2.eq(T.y, S.y) || e2.is_zero(T.y)) return false;
+            const Fq2 xx = e2.mul(T.x, T.x);
+            lam = e2.mul(e2.add(e2.add(xx, xx), xx), e2.inv(e2.add(T.y, T.y)));
+        } else lam = e2.mul(e2.sub(S.y, T.y), e2.inv(e2.sub(S.x, T.x)));
+        t.lines.push_back(lam);
+        t.lines.push_back(e2.sub(e2.mul(lam, T.x), T.y));
+        T = e2.padd(T, S);
+        return true;
+    }
+    // Q as load_g2 left it; false: a degenerate step
+    bool line_table(const G2Host::Pt& Q, LineTable& t) const {
+        t.lines.clear();
+        t.one = Q.inf;
+        if (Q.inf) return true;
+        const unsigned __int128 loop = (unsigned __int128)6 * BN254_X + 2;
+        G2Host::Pt T = Q;
+        for (int i = 63; i >= 0; i--) {
+            if (!table_step(T, T, t)) return false;
+            if (((uint64_t)(loop >> i) & 1) && !table_step(T, Q, t)) return false;
+        }
+        const G2Host::Pt Q1 = frob_pt(Q);
+        G2Host::Pt Q2 = frob_pt(Q1);
+        Q2.y = e2.neg(Q2.y);
+        return table_step(T, Q1, t) && table_step(T, Q2, t) && t.lines.size() == 2 * LINE_STEPS;
+    }
+    // line() from a table's step
+    Fq12 table_line(const Fq2& lam, const Fq2& mu, const Fe& xp, const Fe& yp) const {
+        Fq12 l = {{{yp, Fe{}}, zero2(), zero2()}, {zero2(), zero2(), zero2()}};
+        l.b.a = e2.neg({q->mul(lam.a, xp), q->mul(lam.b, xp)});
+        l.b.b = mu;
+        return l;
+    }
+    // miller() of the table's Q, word for word
+    Fq12 miller_table(const Fe& xp, const Fe& yp, bool p_inf, const LineTable& t) const {
+        Fq12 f = one12();
+        if (p_inf || t.one) return f;
+        const unsigned __int128 loop = (unsigned __int128)6 * BN254_X + 2;
+        const Fq2* ln = t.lines.data();
+        for (int i = 63; i >= 0; i--) {
+            f = mul12(f, f);
+            f = mul12(f, table_line(ln[0], ln[1], xp, yp));
+            ln += 2;
+            if ((uint64_t)(loop >> i) & 1) { f = mul12(f, table_line(ln[0], ln[1], xp, yp)); ln += 2; }
+        }
+        f = mul12(f, table_line(ln[0], ln[1], xp, yp));
+        return mul12(f, table_line(ln[2], ln[3], xp, yp));
+    }
+    // an Fq12 value as the C ABI hands it out: the Fq2 coefficients of w^0 .. w^5, a | b each, 48 words
+    void store12(const Fq12& x, uint64_t out[48]) const {
+        const Fq2* c[6] = {&x.a.a, &x.b.a, &x.a.b, &x.b.b, &x.a.c, &x.b.c};
+        for (int j = 0; j < 6; j++) {
+            memcpy(out + 8 * j, c[j]->a.v, 32);
+            memcpy(out + 8 * j + 4, c[j]->b.v, 32);
+        }
+    }
+    // checks independent checks over the same tables: status[c] = DEHALO_PAIRING_ONE iff prod_j e(P[c][j], Q_j) = 1, _OFF_CURVE (and gt zero words) for a P off
+    // y^2 = x^3 + 3; gt (may be null): 48 words a check
+    void table_checks(const std::vector<LineTable>& tables, const uint64_t* g1_affine_xy, uint32_t checks, uint8_t* status, uint64_t* gt) const {
+        const size_t pairs = tables.size();
+        for (uint32_t c = 0; c < checks; c++) {
+            Fq12 f = one12();
+            bool on_curve = true;
+            for (size_t j = 0; j < pairs && on_curve; j++) {
+                Fe x, y;
+                bool inf;
+                on_curve = load_g1(g1_affine_xy + 8 * ((size_t)c * pairs + j), x, y, inf);
+                if (on_curve) f = mul12(f, miller_table(x, y, inf, tables[j]));
+            }
+            if (!on_curve) {
+                status[c] = DEHALO_PAIRING_OFF_CURVE;
+                if (gt) memset(gt + 48 * (size_t)c, 0, 48 * 8);
+                continue;
+            }
+            const Fq12 g = final_exponentiation(f);
+            status[c] = is_one12(g) ? DEHALO_PAIRING_ONE : DEHALO_PAIRING_NOT_ONE;
+            if (gt) store12(g, gt + 48 * (size_t)c);
+        }
+    }
+
     // ---- points as the C ABI hands them over
     // G1: affine x | y, Montgomery words standing for their residues; (0, 0) words = the identity.  false: not on y^2 = x^3 + 3
     bool load_g1(const uint64_t xy[8], Fe& x, Fe& y, bool& inf) const {

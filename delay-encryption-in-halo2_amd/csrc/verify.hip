@@ -16,6 +16,8 @@ struct dehalo_verifier {
     VerifyStats stats;
     std::string error;
     std::mutex mu;
+    dehalo_pairing_table* pairing_table = nullptr;      // (s_g2, g2) for the device's pairing checks: made when dehalo_verifier_set_pairing first asks for them
+    ~dehalo_verifier() { dehalo_pairing_table_release(pairing_table); }
 };
 
 namespace {
@@ -31,7 +33,13 @@ struct DeviceVerifyBackend : VerifyBackend {
     dehalo_ctx* ctx;
     int curve;
     const dehalo_params* params;      // IPA: the tables the two new sums run over; null for KZG
-    DeviceVerifyBackend(dehalo_ctx* c, int cv, const dehalo_params* p = nullptr) : ctx(c), curve(cv), params(p) {}
+    const dehalo_pairing_table* pairing_table;      // KZG in device mode: the verifier's (s_g2, g2); null otherwise
+    DeviceVerifyBackend(dehalo_ctx* c, int cv, const dehalo_params* p = nullptr, const dehalo_pairing_table* t = nullptr) : ctx(c), curve(cv), params(p), pairing_table(t) {}
+    // every check in ONE launch (pairing.cuh)
+    int pairing_checks(const uint64_t* lr, uint32_t count, uint8_t* status) override {
+        if (!pairing_table) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "verify_proofs: no pairing table behind this verifier");
+        return dehalo_pairing_checks(pairing_table, lr, count, status, nullptr);
+    }
     // (both sums work in the context's grow-only workspace ws_verify: [0] scalars in, [1] points out -- no allocation per call once it has grown)
     int instance_commitments(const Fe* const* cols, const size_t* lens, size_t count, uint64_t* xy) override {
         if (!params) return dh_fail(ctx, DEHALO_ERR_UNSUPPORTED, "verify_proofs: no ParamsIPA behind this verifier");
@@ -137,7 +145,7 @@ int verify_call(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* 
     if (v->ctx) {
         hold = std::unique_lock<std::recursive_mutex>(v->ctx->mu);
         (void)hipSetDevice(v->ctx->device);
-        be.reset(new DeviceVerifyBackend(v->ctx, v->key.curve, v->params));
+        be.reset(new DeviceVerifyBackend(v->ctx, v->key.curve, v->params, v->pairing_table));
     } else {
         std::unique_ptr<HostVerifyBackend> host(new HostVerifyBackend(v->key.fq, v->key.f, curve_b_host(v->key.curve)));
         if (v->key.scheme == DEHALO_SCHEME_IPA) host->set_ipa(v->g.data(), v->g_lagrange.data(), v->key.w, v->key.k);
@@ -335,6 +343,24 @@ extern "C" int dehalo_verifier_set_multiopen(dehalo_verifier* v, int multiopen) 
         if (v->key.scheme == DEHALO_SCHEME_IPA) return verifier_fail(v, v->ctx, DEHALO_ERR_INVALID, "verifier_set_multiopen: an IPA verifier has one multiopen");
         std::lock_guard<std::mutex> lk(v->mu);
         v->key.multiopen = multiopen;
+        return 0;
+    });
+}
+extern "C" int dehalo_verifier_set_pairing(dehalo_verifier* v, int mode) {
+    return dh_guard(v ? v->ctx : nullptr, [&]() -> int {
+        if (!v || (mode != DEHALO_PAIRING_ON_HOST && mode != DEHALO_PAIRING_ON_DEVICE)) return DEHALO_ERR_INVALID;
+        std::lock_guard<std::mutex> lk(v->mu);
+        if (mode == DEHALO_PAIRING_ON_DEVICE) {
+            if (v->key.scheme == DEHALO_SCHEME_IPA) return verifier_fail(v, v->ctx, DEHALO_ERR_INVALID, "verifier_set_pairing: an IPA verifier has no pairing");
+            if (!v->ctx) return verifier_fail(v, nullptr, DEHALO_ERR_INVALID, "verifier_set_pairing: a host verifier has no device");
+            if (!v->pairing_table) {
+                uint8_t g2s[256];
+                memcpy(g2s, v->key.s_g2, 128);
+                memcpy(g2s + 128, v->key.g2, 128);
+                TRY(dehalo_pairing_table_create(v->ctx, v->key.curve, g2s, 2, &v->pairing_table));
+            }
+        }
+        v->key.pairing = mode;
         return 0;
     });
 }

@@ -54,6 +54,9 @@ struct VerifyBackend {
     // sum_idx s[idx] g[idx] over the params' 2^k generators, s = sum_i compute_s(challenges[i k .. i k + k), inits[i]) (GuardIPA::compute_s under the inits) -> one
     // affine point
     virtual int g_sum(const Fe*, const Fe*, size_t, uint32_t, uint64_t[8]) { return DEHALO_ERR_UNSUPPORTED; }
+    // KZG in device mode only (VerifierKey::pairing): count independent checks e(lr[i][0], s_g2) e(lr[i][1], g2) == 1 in one launch, lr count x 2 affine points ->
+    // count bytes, a DEHALO_PAIRING_* status each
+    virtual int pairing_checks(const uint64_t*, uint32_t, uint8_t*) { return DEHALO_ERR_UNSUPPORTED; }
 };
 // compute_s of one proof added into s (2^k scalars): s[idx] += init prod_{bit j of idx set} us[k - 1 - j]
 inline void ipa_add_s(const HostField* f, const Fe* us, uint32_t k, const Fe& init, std::vector<Fe>& s) {
@@ -129,6 +132,7 @@ struct VerifierKey {
     uint64_t g0[8] = {};
     uint8_t g2[128] = {}, s_g2[128] = {};
     int multiopen = DEHALO_MULTIOPEN_GWC;
+    int pairing = DEHALO_PAIRING_ON_HOST;      // _ON_DEVICE: the checks go through the backend's pairing_checks (dehalo_verifier_set_pairing)
     int scheme = DEHALO_SCHEME_KZG;      // DEHALO_SCHEME_IPA: the instance columns are committed and queried, the multiopen is the IPA's; g0 = g[0], and u, w below
     uint64_t u[8] = {}, w[8] = {};
     bool unsupported = false;      // init_cs: the message describes a circuit this library does not take
@@ -755,13 +759,34 @@ inline int decide_ipa(VerifyBackend& be, const VerifyTerms& terms, size_t count,
 }
 
 // The KZG pairing check of two sums L | R (affine): *accept = 1 iff  e(L, s_g2) e(-R, g2) = 1
-inline int kzg_pairing(const VerifierKey& vk, const uint64_t lr[16], int* accept, std::string* error) {
-    uint64_t sums[16];
+// L | R -> L | -R ((0, 0) stays the identity)
+inline void kzg_negate_right(const VerifierKey& vk, const uint64_t lr[16], uint64_t sums[16]) {
     memcpy(sums, lr, 128);
     Fe ry;
     memcpy(ry.v, sums + 12, 32);
-    ry = vk.fq->neg(ry);      // -R ((0, 0) stays the identity)
+    ry = vk.fq->neg(ry);
     memcpy(sums + 12, ry.v, 32);
+}
+// In device mode: `count` pairs L_i | R_i, each its own check in ONE launch of the backend; accept[i] = 1 iff the status is DEHALO_PAIRING_ONE (a sum off the
+// curve is a rejection, as on the host)
+inline int kzg_pairings_device(const VerifierKey& vk, VerifyBackend& be, const uint64_t* lr, uint32_t count, uint8_t* accept, std::string* error) {
+    std::vector<uint64_t> sums(16 * (size_t)count);
+    for (uint32_t i = 0; i < count; i++) kzg_negate_right(vk, lr + 16 * (size_t)i, sums.data() + 16 * (size_t)i);
+    const int rc = be.pairing_checks(sums.data(), count, accept);
+    if (rc) return verify_fail(error, rc, "verify_proofs: the pairing checks on the device failed");
+    for (uint32_t i = 0; i < count; i++) accept[i] = accept[i] == DEHALO_PAIRING_ONE ? 1 : 0;
+    return 0;
+}
+inline int kzg_pairing(const VerifierKey& vk, VerifyBackend& be, const uint64_t lr[16], int* accept, std::string* error) {
+    if (vk.pairing == DEHALO_PAIRING_ON_DEVICE) {
+        uint8_t ok = 0;
+        const int rc = kzg_pairings_device(vk, be, lr, 1, &ok, error);
+        if (rc) return rc;
+        *accept = ok;
+        return 0;
+    }
+    uint64_t sums[16];
+    kzg_negate_right(vk, lr, sums);
     uint8_t g2s[256];
     memcpy(g2s, vk.s_g2, 128);
     memcpy(g2s + 128, vk.g2, 128);
@@ -787,7 +812,7 @@ inline int decide_kzg(const VerifierKey& vk, VerifyBackend& be, const VerifyTerm
         if (rc) return verify_fail(error, rc, "verify_proofs: the multi-scalar multiplication failed");
     }
     st.msm = clock.lap();
-    const int rc = kzg_pairing(vk, sums, accept, error);
+    const int rc = kzg_pairing(vk, be, sums, accept, error);
     if (rc) return rc;
     st.pairing = clock.lap();
     return 0;
@@ -827,7 +852,8 @@ struct VerifyEachVerdict { std::vector<int> reasons; uint32_t checks = 0; Verify
 // part in what follows.  ONE msm_segments call of the backend then sums every remaining proof's runs apart -- w_i L_i and w_i R_i (IPA: the weighted fresh sum)
 // --, a subset's sums are point additions on the host, and blame_search names the proofs that fail with few checks of subsets: KZG one pairing check on the
 // subset's two sums, IPA the subset's fresh sum against the backend's g_sum over the subset's challenges and inits (ipa_sums_cancel).  A proof the search names is
-// PAIRING under KZG and OPENING under IPA.  Returns 0 whenever the checks ran; DEHALO_ERR_INVALID without weights or the backend's error, and `out` is then as it was.
+// PAIRING under KZG and OPENING under IPA.  KZG in device mode (vk.pairing): no search -- every live proof's two sums go through ONE pairing_checks call of the
+// backend, a check each, and `checks` is the number of live proofs.  Returns 0 whenever the checks ran; DEHALO_ERR_INVALID without weights or the backend's error, and `out` is then as it was.
 inline int verify_proofs_each_host(const VerifierKey& vk, VerifyBackend& be, const VerifyInput& in, VerifyEachVerdict& out, std::string* error) {
     if (in.count && !in.weights) return verify_fail(error, DEHALO_ERR_INVALID, "verify_proofs_each: null argument");
     VerifyEachVerdict v;
@@ -886,12 +912,23 @@ inline int verify_proofs_each_host(const VerifierKey& vk, VerifyBackend& be, con
                 uint64_t lr[16];
                 range_sum(sums.data(), first, count, lr);
                 range_sum(right, first, count, lr + 8);
-                check_rc = kzg_pairing(vk, lr, &ok, error);
+                check_rc = kzg_pairing(vk, be, lr, &ok, error);
             }
             return !check_rc && ok;
         };
         std::vector<uint8_t> bad;
-        v.checks = blame_search(live, check, bad);
+        if (!ipa && vk.pairing == DEHALO_PAIRING_ON_DEVICE) {
+            // every live proof's (w_i L_i, -w_i R_i) its own check, all in one launch: no search, and no verdict depends on another proof's weight
+            std::vector<uint64_t> lr(16 * live);
+            for (size_t p = 0; p < live; p++) {
+                memcpy(&lr[16 * p], sums.data() + 8 * p, 64);
+                memcpy(&lr[16 * p + 8], right + 8 * p, 64);
+            }
+            bad.assign(live, 0);
+            check_rc = kzg_pairings_device(vk, be, lr.data(), (uint32_t)live, bad.data(), error);
+            for (size_t p = 0; p < live; p++) bad[p] = !bad[p];
+            v.checks = (uint32_t)live;
+        } else v.checks = blame_search(live, check, bad);
         if (check_rc) return check_rc;
         v.stats.pairing = clock.lap();
         for (size_t p = 0; p < live; p++)

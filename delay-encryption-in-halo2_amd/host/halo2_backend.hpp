@@ -565,6 +565,9 @@ class Verifier {
     ~Verifier() { dehalo_verifier_release(v_); }
     Verifier(const Verifier&) = delete;
     void set_transcript_repr(const Fe& r) { check(dehalo_verifier_set_transcript_repr(v_, r.data())); }
+    // DEHALO_PAIRING_ON_HOST (the default) | DEHALO_PAIRING_ON_DEVICE: the pairing checks through the kernel -- verify_each then gives every live proof its own
+    // check in ONE launch, without a search.  Throws on a host verifier and on an IPA verifier
+    void set_pairing(int mode) { check(dehalo_verifier_set_pairing(v_, mode)); }
     // true: accepted.  false: *reason (if given) says why -- DEHALO_REJECT_MALFORMED, DEHALO_REJECT_PAIRING or (IPA) DEHALO_REJECT_OPENING.  instances: one vector per instance column
     bool verify(const std::vector<uint8_t>& proof, const std::vector<std::vector<Fe>>& instances, int* reason = nullptr) const {
         std::vector<const uint64_t*> ip;

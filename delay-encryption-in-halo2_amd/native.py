@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from . import plonk
-from ._lib import (CCheckFailure, CCheckReport, CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, FixedBase, RNG_FILL_FN, load_library)
+from ._lib import (CCheckFailure, CCheckReport, CCircuitInputs, CColumnQuery, CConstraintSystem, CExprNode, CRng, CSynthesisInfo, Context, DehaloError, FixedBase, PairingTable, RNG_FILL_FN, load_library)
 from .fields import CurveSpec, FieldSpec
 
 EXPR_KIND = {"const": 0, plonk.FIXED: 1, plonk.ADVICE: 2, plonk.INSTANCE: 3, "neg": 4, "sum": 5, "product": 6, "scaled": 7, "challenge": 8}
@@ -585,11 +585,13 @@ def _create_error() -> str:
 class Verifier:
     """dehalo_verifier: verify_proof for KZG (GWC and SHPLONK) and for IPA over Pallas / Vesta (from_ipa, from_ipa_vk, from_ipa_host), one proof or a batch.  It holds the verifying half of the params and of the key only.
     With a Context the proofs' points are decompressed and the two sums of the reduction are formed on the device; with ctx=None it is a HOST verifier -- a mode
-    the caller chooses (machines without a GPU), never a fallback.  The pairing check runs on the host in both."""
+    the caller chooses (machines without a GPU), never a fallback.  The pairing check runs on the host in both, unless a verifier with a Context is switched to
+    pairing="device" (set_pairing): the checks then go through the device kernel, verify_each's all in one launch."""
 
     MULTIOPEN = {"gwc": 0, "shplonk": 1}      # dehalo_multiopen
+    PAIRING = {"host": 0, "device": 1}        # dehalo_verifier_set_pairing
 
-    def __init__(self, ctx: Optional[Context], curve: CurveSpec, handle, multiopen: Optional[str] = "gwc"):
+    def __init__(self, ctx: Optional[Context], curve: CurveSpec, handle, multiopen: Optional[str] = "gwc", pairing: str = "host"):
         self.ctx, self.curve, self.handle = ctx, curve, handle
         self.last_reject = REJECT_NONE          # why the last verify / verify_batch said no
         self.first_malformed = -1               # verify_batch: the first unreadable proof
@@ -598,23 +600,25 @@ class Verifier:
         self._params = None                     # IPA with a context: the borrowed ParamsIPA, kept alive
         if not self.ipa:
             self.set_multiopen(multiopen)
+        if pairing != "host":
+            self.set_pairing(pairing)
 
     def _check(self, rc: int):
         if rc != 0:
             raise DehaloError(rc, load_library().dehalo_verifier_last_error(self.handle).decode() if self.handle else "verifier")
 
     @classmethod
-    def from_pk(cls, params: ParamsKZG, pk: "ProvingKey", multiopen: str = "gwc") -> "Verifier":
+    def from_pk(cls, params: ParamsKZG, pk: "ProvingKey", multiopen: str = "gwc", pairing: str = "host") -> "Verifier":
         """from objects the caller already has (dehalo_verifier_create): g[0], g2, s_g2, k of the params; the commitments, constraint system and transcript_repr of the key"""
         h = C.c_void_p()
         rc = load_library().dehalo_verifier_create(params.ctx.handle, params.handle, pk.handle, C.byref(h))
         if rc:
             raise DehaloError(rc, _create_error())
-        return cls(params.ctx, params.curve, h, multiopen)
+        return cls(params.ctx, params.curve, h, multiopen, pairing)
 
     @classmethod
     def from_vk(cls, curve: CurveSpec, k: int, g0, g2: bytes, s_g2: bytes, cs: plonk.ConstraintSystem, vk_bytes: bytes, num_selectors: int = 0,
-                format: str = "raw-unchecked", ctx: Optional[Context] = None, multiopen: str = "gwc", transcript_repr: Optional[int] = None) -> "Verifier":
+                format: str = "raw-unchecked", ctx: Optional[Context] = None, multiopen: str = "gwc", transcript_repr: Optional[int] = None, pairing: str = "host") -> "Verifier":
         """ParamsVerifierKZG + VerifyingKey::read (dehalo_verifier_create_vk): g0 = g[0] as (x, y) canonical ints or 8 Montgomery words; g2, s_g2 the 128 raw bytes
         ParamsKZG keeps; vk_bytes in `format` (one of SERDE_FORMATS).  transcript_repr: None = the substitute keygen gives the same vk bytes."""
         if isinstance(g0, tuple):
@@ -629,7 +633,7 @@ class Verifier:
                                            C.byref(h))
         if rc:
             raise DehaloError(rc, _create_error())
-        v = cls(ctx, curve, h, multiopen)
+        v = cls(ctx, curve, h, multiopen, pairing)
         if transcript_repr is not None:
             v.transcript_repr = transcript_repr
         return v
@@ -689,6 +693,13 @@ class Verifier:
         if multiopen not in self.MULTIOPEN:
             raise ValueError("multiopen: 'gwc' or 'shplonk'")
         self._check(load_library().dehalo_verifier_set_multiopen(self.handle, self.MULTIOPEN[multiopen]))
+
+    def set_pairing(self, where: str):
+        """dehalo_verifier_set_pairing: "host" (the default) or "device" -- the pairing checks through the kernel: verify and verify_batch one check, verify_each
+        every live proof its own check in ONE launch, no search (last_checks = the live proofs).  DehaloError(-1) on a host or an IPA verifier."""
+        if where not in self.PAIRING:
+            raise ValueError("pairing: 'host' or 'device'")
+        self._check(load_library().dehalo_verifier_set_pairing(self.handle, self.PAIRING[where]))
 
     def _set_repr(self, value: int):
         self._check(load_library().dehalo_verifier_set_transcript_repr(self.handle, self.curve.scalar.encode(value).ctypes.data))

@@ -833,6 +833,38 @@ size_t dehalo_transcript_remaining(const dehalo_transcript* t);
  * derived constant is computed at first use); a two-pair check takes milliseconds.  Nothing here runs in constant time: every input of a verifier is public. */
 int dehalo_pairing_check(int curve, const uint64_t* g1_affine_xy, const uint8_t* g2_raw, size_t count, int* is_one);
 
+/* Many INDEPENDENT pairing checks against FIXED G2 points, on the device in one launch (csrc/pairing.cuh): what a KZG verifier of many proofs needs, whose
+ * s_g2 and g2 are fixed when it is made.  For check c < checks and the table's `pairs` points Q_j:
+ *     gt[c] = (prod_j miller(P[c][j], Q_j)) ^ ((q^12 - 1) / r),    status[c] = DEHALO_PAIRING_ONE iff gt[c] = 1.
+ * A table is made once from `pairs` G2 points in dehalo_pairing_check's 128-byte raw form: all the Miller loop does on the twist -- the 64 doublings, the 36
+ * additions of 6x + 2, the two Frobenius steps, an Fq2 inversion each -- depends on Q alone and is done then, on the host; the table keeps the two line
+ * coefficients of each of the 102 steps (128 B a step).  An all-zero Q is the identity: its factor is 1.  A Q that dehalo_pairing_check would refuse (off the
+ * twist, outside the order-r subgroup, a word not below q) is DEHALO_ERR_INVALID, and so are pairs = 0 or > DEHALO_PAIRING_MAX_PAIRS and a null argument;
+ * DEHALO_ERR_UNSUPPORTED for Pallas and Vesta.  ctx = NULL makes a HOST table: dehalo_pairing_checks then runs on the host through the same table (a mode the
+ * caller chooses, never a fallback), and dehalo_pairing_checks_device refuses it with DEHALO_ERR_INVALID.
+ *   g1_affine_xy  checks x pairs x {x, y}, 8 u64 standard Montgomery a point; (0, 0) words = the identity, whose factor is 1; a coordinate word not below q
+ *                 stands for its residue ("Non-canonical words" (4) at the top)
+ *   status        checks bytes: DEHALO_PAIRING_NOT_ONE, _ONE, or _OFF_CURVE for a check one of whose P is not on y^2 = x^3 + 3 (its gt is zero words, and no
+ *                 other check is affected)
+ *   gt            optional, checks x 12 x 4 u64: the Fq2 coefficients of w^0 .. w^5 in that order, each as a | b (a + b i), canonical words, standard
+ *                 Montgomery.  In the tower Fq12 = Fq6[w] / (w^2 - v), Fq6 = Fq2[v] / (v^3 - (9 + i)), an element a + b w with a, b = (a, b, c) in Fq6 has
+ *                 w^0, w^2, w^4 = a.a, a.b, a.c and w^1, w^3, w^5 = b.a, b.b, b.c.  The value is the host pairing's, bit for bit.
+ * checks = 0 does nothing and accepts null arrays; checks > DEHALO_PAIRING_MAX_CHECKS is DEHALO_ERR_INVALID.  dehalo_pairing_checks takes host arrays: with a
+ * device table it uploads, runs the kernel on the context's stream and downloads.  One wave per check, the running product in LDS, no workspace; nothing here
+ * runs in constant time. */
+#define DEHALO_PAIRING_MAX_PAIRS 8
+#define DEHALO_PAIRING_MAX_CHECKS (1u << 20)
+enum { DEHALO_PAIRING_NOT_ONE = 0, DEHALO_PAIRING_ONE = 1, DEHALO_PAIRING_OFF_CURVE = 2 };
+typedef struct dehalo_pairing_table dehalo_pairing_table;
+int dehalo_pairing_table_create(dehalo_ctx* ctx, int curve, const uint8_t* g2_raw /* pairs x 128 */, uint32_t pairs, dehalo_pairing_table** out);
+void dehalo_pairing_table_release(dehalo_pairing_table* t);
+int dehalo_pairing_checks_device(dehalo_ctx* ctx, const dehalo_pairing_table* t, const uint64_t* d_g1_affine_xy, uint32_t checks, uint8_t* d_status, uint64_t* d_gt,
+                                 void* stream);
+int dehalo_pairing_checks(const dehalo_pairing_table* t, const uint64_t* g1_affine_xy, uint32_t checks, uint8_t* status, uint64_t* gt);
+/* the number of checks one block of the kernel holds for this table's launches (ceil(checks / this) blocks a launch; t may be NULL: the same for every
+ * table today): for tests of the launch's edges */
+uint32_t dehalo_pairing_checks_per_block(const dehalo_pairing_table* t);
+
 /* The IPA opening of ONE polynomial [UPSTREAM halo2_proofs/src/poly/ipa/commitment/prover.rs: create_proof(params, rng, transcript, p_poly, p_blind,
  * x_3)]: proves that the commitment P = MSM(p, g) + [blind] W opens to p(x_3) -- what ProverIPA's multiopen ends with, and what a test or an integrator
  * can call on its own.  params: dehalo_params_ipa_create; d_poly: 2^k coefficients in device memory (Montgomery, read only); blind, x3: Montgomery.
@@ -1079,6 +1111,15 @@ int dehalo_verifier_create_ipa_host(int curve, uint32_t k, const uint64_t* g, co
                                     const dehalo_constraint_system* cs, const uint8_t* vk_bytes, size_t vk_len, int vk_format, uint32_t num_selectors, dehalo_verifier** out);
 int dehalo_verifier_set_transcript_repr(dehalo_verifier* v, const uint64_t repr[4]);
 int dehalo_verifier_set_multiopen(dehalo_verifier* v, int multiopen);      /* DEHALO_MULTIOPEN_GWC (default) | _SHPLONK; DEHALO_ERR_INVALID on an IPA verifier */
+/* Where a KZG verifier's pairing checks run: DEHALO_PAIRING_ON_HOST (the default: every call is what it was before this mode existed) or DEHALO_PAIRING_ON_DEVICE
+ * (dehalo_pairing_checks_device over the verifier's table of (s_g2, g2), built when the mode is first set).  On the device dehalo_verify_proof and
+ * dehalo_verify_proofs make their one check through the kernel (checks = 1), and dehalo_verify_proofs_each puts EVERY live proof's (w_i L_i, -w_i R_i) through ONE
+ * launch after the dehalo_msm_segments sums: each proof is checked by itself, there is no search over subsets, *checks is the number of live proofs, out[3] of
+ * dehalo_verifier_last_timings is that launch, and a verdict no longer depends on the weights.  A status of NOT_ONE or OFF_CURVE is DEHALO_REJECT_PAIRING.  A mode
+ * the caller switches on, never a fallback: a device error is that error.  DEHALO_ERR_INVALID for ON_DEVICE on a verifier made without a context, for an IPA
+ * verifier, and for any other value. */
+enum { DEHALO_PAIRING_ON_HOST = 0, DEHALO_PAIRING_ON_DEVICE = 1 };
+int dehalo_verifier_set_pairing(dehalo_verifier* v, int mode);
 int dehalo_verifier_release(dehalo_verifier* v);
 /* Why the calling thread's last dehalo_verifier_create / _create_vk failed (a bad g2, the vk's header, a point's status, ...): a host verifier has no context
  * whose dehalo_last_error could say, and a failed constructor leaves no verifier.  The text is copied into out[0 .. cap), cut to cap - 1 bytes, NUL-terminated. */
@@ -1120,7 +1161,8 @@ int dehalo_verify_proofs(dehalo_verifier* v, const uint8_t* const* proofs, const
  * 1 + 2 b ceil(log2 n) for b >= 1 invalid among n -- 13 for one invalid proof among 64, 127 when all 64 are invalid.  Two copies of one invalid proof are both named.
  * A check is one pairing check on the host (KZG) or one dehalo_ipa_s_device + MSM over g (IPA; a host verifier: 2^k group operations each).
  * Returns 0 whenever the checks ran; on an error `reasons` and `checks` are not written.  dehalo_verifier_last_timings: out[2] the dehalo_msm_segments call, out[3] the
- * total of the subset checks.  dehalo_verify_proof and dehalo_verify_proofs are what they were. */
+ * total of the subset checks.  dehalo_verify_proof and dehalo_verify_proofs are what they were.  A KZG verifier switched to DEHALO_PAIRING_ON_DEVICE
+ * (dehalo_verifier_set_pairing above) makes no search: every live proof gets its own check in one launch, and *checks is the number of live proofs. */
 int dehalo_verify_proofs_each(dehalo_verifier* v, const uint8_t* const* proofs, const size_t* lens, uint32_t count, const uint64_t* const* instances,
                               const size_t* instance_lens, uint32_t num_instance_columns, uint32_t num_circuits, dehalo_rng* rng, int* reasons, uint32_t* checks);
 /* The IPA opening argument's check alone, the counterpart of dehalo_ipa_open: *accept = 1 iff `proof` (S, the k rounds' L_j, R_j, then c and f: 32 (2 k + 3) bytes,
